@@ -8,17 +8,25 @@ BASELINE.json configs[1], a 1080p30 60 s clip sampled at 2 fps = 120 BGR frames
 With N > 1 ranks every rank analyses its own clip (whole clips per GPU) and one
 RCCL all-gather of the 32-byte per-frame records reassembles all timelines: weak scaling.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 (`python bench.py --gpus N` with N > 1 and no WORLD_SIZE in the environment starts the N ranks itself -- a fresh
 `python -m torch.distributed.run` child, before this process has touched the GPU -- and relays rank 0's line.)
 
+A plain run measures the headline figure only: it sets up, runs W warm-up steps, times EXACTLY K steps once, writes
+the last step's outputs if --dump-outputs DIR is given, and prints the line.  Everything below `value / ms_per_step`
+(and the --repeats statistic) is measured with --full only.
+
 Prints ONE JSON line on rank 0.  What is measured, and how:
-  value / ms_per_step   W untimed warm-up steps, then EXACTLY K steps between barrier + synchronize, max over ranks;
-                        the K-step region is repeated --repeats times in the same process and the MEDIAN repeat is
-                        reported (min / max beside it: boxes and DVFS move a single 25 ms region by several percent).
-                        --inflight clips are in flight per GPU, each on its own avd context AND its own copy of the
-                        input in HBM (a service never analyses the same buffer three times at once).
+  value / ms_per_step   W untimed warm-up steps, then EXACTLY K steps between barrier + synchronize, max over ranks.
+                        With --full the K-step region is repeated --repeats times in the same process and the MEDIAN
+                        repeat is reported (min / max beside it: boxes and DVFS move a single 25 ms region by several
+                        percent).  --inflight clips are in flight per GPU, each on its own avd context AND its own copy
+                        of the input in HBM (a service never analyses the same buffer three times at once).
+  --dump-outputs DIR    after the timed steps: what the last step handed its caller (rank 0's clip), one float32 /
+                        float64 .npy per array -- the per-frame records (records_<field>.npy), the video result
+                        (timeline.npy, summary_<key>.npy) and the fused result (fused_<key>.npy).  The input clip is
+                        seeded (--seed), so two builds run with the same arguments can be compared output for output.
   roofline              the kernel with the largest share of the step: the Farneback level kernel at 320x320 (fb_mode
                         fast, the default and what `value` uses: one launch per blur iteration), timed with HIP events
                         around its three launches on the library's own stream while clips run ALONE (an exclusive pass
@@ -218,14 +226,15 @@ def compact_line(full, details_path=None):
                                            "fb_mode", "fb_wide160", "sec_per_video", "sec_per_video_resident", "sec_per_video_nv12", "parallelism", "rccl_ranks_seen",
                                            "collective_backend"))
     line["repeats"] = pick(full.get("repeats"), ("n", "statistic", "value_min", "value_max"))
-    r = full["roofline"]
-    line["roofline"] = pick(r, ("kernel", "bound", "achieved", "peak", "unit", "frac", "hbm", "traffic", "traffic_from_profiles",
-                                "algorithmic_bytes_per_launch", "avg_launch_ms", "launches_per_step", "share_of_step", "limiter",
-                                "frac_of_vector_peak", "valu_issue_frac_from_profiles", "ta_busy_frac_from_profiles", "kernels",
-                                "whole_step_frac", "preprocess_frac", "timed"))
+    r = full.get("roofline")                       # roofline and cpu_baseline: --full records only
+    if r is not None:
+        line["roofline"] = pick(r, ("kernel", "bound", "achieved", "peak", "unit", "frac", "hbm", "traffic", "traffic_from_profiles",
+                                    "algorithmic_bytes_per_launch", "avg_launch_ms", "launches_per_step", "share_of_step", "limiter",
+                                    "frac_of_vector_peak", "valu_issue_frac_from_profiles", "ta_busy_frac_from_profiles", "kernels",
+                                    "whole_step_frac", "preprocess_frac", "timed"))
     if full.get("cpu_baseline"):
         line["cpu_baseline"] = pick(full["cpu_baseline"], ("value", "unit", "cores", "kind", "sample", "single_thread_value", "cores_usable_how"))
-    else:
+    elif "cpu_baseline" in full:
         line["cpu_baseline"] = None
     if full.get("fb_modes"):
         line["fb_modes"] = pick(full["fb_modes"], ("value_uses", "rerun_pairs", "guarantee", "exact_frames_per_s", "fast_without_rerun_frames_per_s",
@@ -257,6 +266,34 @@ def compact_line(full, details_path=None):
     if details_path:
         line["details"] = details_path
     return line
+
+
+DUMP_RECORD_FIELDS = ("lap_sum", "lap_sumsq", "flow_mean", "flow_var", "ham")
+
+
+def dump_outputs(path, rec, video, fused):
+    """--dump-outputs DIR: what one step handed its caller, as DIR/<name>.npy -- the per-frame records (float32 fields as
+    float32; the integer fields as float64, exact: |lap_sumsq| < 2**53), the video result (`timeline`, one summary_<key>
+    per summary scalar) and the fused result (every number or list of numbers under it, the strings left out).  A few KB
+    for the bench clip.  -> the names written"""
+    arrays = {}
+    for f in DUMP_RECORD_FIELDS:
+        arrays["records_" + f] = np.asarray(rec[f], np.float32 if rec.dtype[f].kind == "f" else np.float64)
+    arrays["timeline"] = np.asarray(video["timeline"], np.float64)
+    for k, v in video["summary"].items():
+        arrays["summary_" + k] = np.asarray(v, np.float64)
+
+    def numbers(prefix, d):
+        for k, v in d.items():
+            if isinstance(v, dict):
+                numbers(f"{prefix}{k}_", v)
+            elif isinstance(v, (bool, int, float)) or (isinstance(v, list) and all(isinstance(x, (int, float)) for x in v)):
+                arrays[prefix + k] = np.asarray(v, np.float64)
+    numbers("fused_", fused)
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return sorted(arrays)
 
 
 _CPU_CHILD = r"""
@@ -392,21 +429,26 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--repeats", type=int, default=25, help="the K-step timed region is repeated this many times in-process; "
-                                                            "the median repeat is reported (1 = a single region)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline figure (CPU baseline, roofline and per-kernel times, latencies, "
+                         "PCIe / NV12, extensions, exact mode, re-run cost, batches, --repeats timed regions); off by default")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (float32 / float64)")
+    ap.add_argument("--repeats", type=int, default=25, help="with --full: the K-step timed region is repeated this many times in-process; "
+                                                            "the median repeat is reported (1 = a single region).  A plain run times it once")
     ap.add_argument("--frames", type=int, default=120, help="sampled frames per clip (120 = 60 s at 2 fps)")
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--width", type=int, default=1920)
-    ap.add_argument("--cpu-frames", type=int, default=120, help="frames timed on the CPU oracle (0 = skip)")
+    ap.add_argument("--cpu-frames", type=int, default=120, help="--full: frames timed on the CPU oracle (0 = skip)")
     ap.add_argument("--cpu-procs", type=int, default=0,
-                    help="processes of the clip-parallel CPU baseline: 0 (default) = one per host core; 1 = single thread only")
-    ap.add_argument("--no-extras", action="store_true", help="skip the exact-mode pass and the short-clip / mixed-stream batches")
+                    help="--full: processes of the clip-parallel CPU baseline: 0 (default) = one per host core; 1 = single thread only")
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip the exact-mode pass and the short-clip / mixed-stream batches")
     ap.add_argument("--launch-check", action="store_true", help="multi-rank plumbing check without a GPU (gloo); not a measurement")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--details", default=None, metavar="FILE",
                     help="also write the verbose record (every sub-object and note behind the printed line) to FILE")
-    ap.add_argument("--no-pcie", action="store_true", help="skip the host-buffer (PCIe-inclusive) measurements")
-    ap.add_argument("--no-vit", action="store_true", help="skip the extensions reported apart (ViT patch-embed GEMM, CNN forward, audio analyzer)")
+    ap.add_argument("--no-pcie", action="store_true", help="--full: skip the host-buffer (PCIe-inclusive) measurements")
+    ap.add_argument("--no-vit", action="store_true", help="--full: skip the extensions reported apart (ViT patch-embed GEMM, CNN forward, audio analyzer)")
     ap.add_argument("--pcie", action="store_true", help="accepted for compatibility (the PCIe-inclusive figures are on by default)")
     ap.add_argument("--inflight", type=int, default=3,
                     help="clips in flight per GPU, each on its own avd context / stream / workspace / input copy.  3 (default) = "
@@ -446,7 +488,7 @@ def main():
     # CPU legs FIRST, before this process makes any GPU call: the baseline (its children are fresh interpreters) and the
     # oracle's exact operation counts
     cpu_base = ops = None
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         from oracle import oracle as O
         two = np.stack([O.resize_linear(O.bgr2gray(f), 320, 320) for f in clip[:2]])
         ops = oracle_op_counts(two)
@@ -516,7 +558,7 @@ def main():
             c.set_profiling(bool(on))
         prof["on"] = bool(on)
 
-    set_prof(True)
+    set_prof(args.full)
     recs = [np.zeros(n, avd_hip.RECORD_DTYPE) for _ in range(m)]
     if use_dist and args.collective == "native":
         for c in ctxs:                                      # one communicator per context (each has its own stream)
@@ -526,6 +568,7 @@ def main():
     hints = heuristics_v2.compute_hints({**meta, "bit_rate": 8_000_000}, "")
     stage = np.zeros(6)
     pending = []
+    last = {}                                       # what the most recently retired step handed back (--dump-outputs)
 
     def submit(i, src=None):
         j = i % m
@@ -549,6 +592,7 @@ def main():
         # scalar tail (video.py:54-83) + fusion (fusion.py:16) for this rank's clip; other clips' records are local too
         video = records_to_result(allrec[rank * n:(rank + 1) * n], h * w, w, h, meta["fps"], meta["duration"])
         fused = fusion.fuse(audio_unavailable("", meta), video, hints)
+        last.update(rec=rec, video=video, fused=fused)
         return video, fused
 
     def run(steps, src=None):
@@ -566,38 +610,40 @@ def main():
             tdist.barrier()
         torch.cuda.synchronize()
 
-    # EXCLUSIVE pass, before the timed region: clips submitted and drained alone.  It gives (a) the resident latency of
-    # one clip and (b) per-kernel durations from HIP events on the kernels' own stream that are not mixed with another
-    # clip's kernels.
-    for _ in range(args.warmup):
-        submit(0)
-        retire()
     lat, excl = [], np.zeros(6)
     n_excl = 10
     kms = {}                                # per-kernel device times of a clip run alone (avd_kernel_ms), mean of the pass
-    for _ in range(n_excl):
-        stage[:] = 0
-        submit(0)
-        retire()
-        excl += stage
-        for kk, vv in ctxs[0].kernel_ms().items():
-            kms[kk] = kms.get(kk, 0.0) + vv / n_excl
-    excl /= n_excl
-    rerun_pairs = ctxs[0].get_option("rerun_pairs")
+    latency_ms = rerun_pairs = None
     fb_mode_used = {0: "exact", 1: "fast+rerun" if ctxs[0].get_option("fb_rerun") else "fast (re-run off)"}[ctxs[0].get_option("fb_mode")]
-    set_prof(False)                   # from here on nothing but the work itself is on the streams
-    submit(0)
-    retire()
-    for _ in range(n_excl):
-        t1 = time.perf_counter()
+    if args.full:
+        # EXCLUSIVE pass, before the timed region: clips submitted and drained alone.  It gives (a) the resident latency of
+        # one clip and (b) per-kernel durations from HIP events on the kernels' own stream that are not mixed with another
+        # clip's kernels.
+        for _ in range(args.warmup):
+            submit(0)
+            retire()
+        for _ in range(n_excl):
+            stage[:] = 0
+            submit(0)
+            retire()
+            excl += stage
+            for kk, vv in ctxs[0].kernel_ms().items():
+                kms[kk] = kms.get(kk, 0.0) + vv / n_excl
+        excl /= n_excl
+        rerun_pairs = ctxs[0].get_option("rerun_pairs")
+        set_prof(False)                   # from here on nothing but the work itself is on the streams
         submit(0)
         retire()
-        lat.append(time.perf_counter() - t1)
-    latency_ms = statistics.median(lat) * 1e3
+        for _ in range(n_excl):
+            t1 = time.perf_counter()
+            submit(0)
+            retire()
+            lat.append(time.perf_counter() - t1)
+        latency_ms = statistics.median(lat) * 1e3
 
     # decoded frames in PINNED HOST memory -> result: BASELINE.json's "end-to-end sec/video" (decode excluded)
     host_lat_ms = pcie_fps = pcie_fps_inflight = None
-    if not args.no_pcie:
+    if args.full and not args.no_pcie:
         pinned = host.pin_memory()
         submit(0, pinned)
         retire()
@@ -618,7 +664,7 @@ def main():
 
     # NV12 ingest: the same clip as decoder surfaces (1.5 B per pixel), reported apart -- never `value`
     nv12 = None
-    if not args.no_pcie and (h % 2 == 0 and w % 2 == 0):
+    if args.full and not args.no_pcie and (h % 2 == 0 and w % 2 == 0):
         k = min(n, 8)
         ys, cs = synth.bgr_to_nv12(clip[:k])                  # a few distinct surfaces, cycled: the kernel time does not depend on content
         idx = np.arange(n) % k
@@ -663,7 +709,7 @@ def main():
     # ViT-B/16 patch-embed MFMA stage (a build-defined extension, NOT part of `value`): the GEMM
     # [M = frames x 196, 768] x [768, 768] on 8 x the clip's frames (a shape that fills the chip several times over)
     vit = None
-    if not args.no_vit and world == 1:
+    if args.full and not args.no_vit and world == 1:
         rngv = np.random.default_rng(7)
         ctxs[0].vit_set_weights((rngv.standard_normal((768, 768)) * 0.02).astype(np.float32),
                                 (rngv.standard_normal(768) * 0.1).astype(np.float32))
@@ -682,7 +728,7 @@ def main():
 
     # CNN extension (build-defined, NOT part of `value`): ResNet-50-style forward of the clip's frames
     cnn = None
-    if not args.no_vit and world == 1:
+    if args.full and not args.no_vit and world == 1:
         from avd_hip import cnn as host_cnn
         wts, bss = host_cnn.seeded_parameters(0)
         ctxs[0].cnn_set_weights(wts, bss)
@@ -706,7 +752,7 @@ def main():
 
     # LayerNorm over the patch-embed tokens and softmax over the CNN's logits (north_star's stack; extensions, reported apart)
     norm = None
-    if not args.no_vit and world == 1:
+    if args.full and not args.no_vit and world == 1:
         rows = 960 * 196
         tokb = torch.randn((rows, 768), dtype=torch.float32, device=dev).to(torch.bfloat16)
         gam, bet = np.ones(768, np.float32), np.zeros(768, np.float32)
@@ -721,7 +767,7 @@ def main():
 
     # audio analyzer, reported apart: the clip's 60 s sound track as 120 half-second windows
     audio = None
-    if not args.no_vit and world == 1:
+    if args.full and not args.no_vit and world == 1:
         from avd_hip import audio as host_audio
         rnga = np.random.default_rng(11)
         ta = np.arange(int(16000 * meta["duration"])) / 16000.0
@@ -740,7 +786,7 @@ def main():
 
     # ---- fb_mode exact beside the default (fast): latency of a clip alone, level-0 time, throughput with clips in flight
     exact = None
-    if not args.no_extras and world == 1:
+    if args.full and not args.no_extras and world == 1:
         ectx = [avd_hip.Context(dev_index) for _ in range(m)]
         for c in ectx:
             c.set_option("fb_mode", 0)
@@ -785,7 +831,7 @@ def main():
     # kernels flag (vertical sinusoid stripes: 1-D structure, the normal equations are singular) -- latency of the clip alone and throughput with
     # clips in flight, beside the unflagged clip and fb_mode = exact.  The bench clip itself flags nothing (fb_modes.rerun_pairs).
     rerun_cost = None
-    if not args.no_extras and world == 1 and ctxs[0].get_option("fb_mode") == 1 and ctxs[0].get_option("fb_rerun"):
+    if args.full and not args.no_extras and world == 1 and ctxs[0].get_option("fb_mode") == 1 and ctxs[0].get_option("fb_rerun"):
         xs = torch.arange(w, device=dev, dtype=torch.float32)
 
         def stripe_frame(phase):
@@ -841,7 +887,7 @@ def main():
 
     # ---- batches: configs[0]-sized short clips and a configs[4] mixed-resolution stream (avd_analyze_batch)
     batches = None
-    if not args.no_extras and world == 1:
+    if args.full and not args.no_extras and world == 1:
         def stream_fps(make_calls, frames_per_round, rounds=6):
             """make_calls(ctx_index) enqueues one round on that context; m rounds in flight"""
             for j in range(m):
@@ -897,7 +943,7 @@ def main():
     run(args.warmup)                  # W untimed warm-up steps in the timed region's own (pipelined) mode
     elapsed_all, timed_stage = [], np.zeros(6)
     result = fused = None
-    for _ in range(max(1, args.repeats)):
+    for _ in range(max(1, args.repeats) if args.full else 1):
         stage[:] = 0
         barrier()
         t0 = time.perf_counter()
@@ -910,46 +956,22 @@ def main():
             elapsed = float(t.item())
         elapsed_all.append(elapsed)
     elapsed = statistics.median(elapsed_all)
-    # the same pipelined mode once more with the stage events on, after the timed repeats: event-to-event stage times under load
-    set_prof(True)
-    run(min(args.warmup, 2))
-    stage[:] = 0
-    run(args.steps)
-    timed_stage = stage / max(args.steps, 1)
-    set_prof(False)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last["rec"], last["video"], last["fused"])
+    if rerun_pairs is None:
+        rerun_pairs = ctxs[0].get_option("rerun_pairs")
+    if args.full:
+        # the same pipelined mode once more with the stage events on, after the timed repeats: event-to-event stage times under load
+        set_prof(True)
+        run(min(args.warmup, 2))
+        stage[:] = 0
+        run(args.steps)
+        timed_stage = stage / max(args.steps, 1)
+        set_prof(False)
 
     if rank == 0:
         ms_per_step = elapsed / args.steps * 1e3
         fps = lambda e: world * n * args.steps / e          # noqa: E731
-        dominant, pre, fb = roofline_objects(n, h, w, excl, latency_ms, "exact" if fb_mode_used == "exact" else "fast", ops)
-        pmc_k = load_pmc().get("k_fb_level<320>" if fb_mode_used == "exact" else "k_fb_fast<320>", {}) if (n, h, w) == (120, 1080, 1920) else {}
-        dominant["traffic_from_profiles"] = os.path.relpath(PMC_FILE, ROOT) if dominant.get("traffic") is not None else None
-        dominant["valu_issue_frac_from_profiles"] = pmc_k.get("valu_issue_frac")
-        dominant["ta_busy_frac_from_profiles"] = pmc_k.get("ta_busy_frac")
-        dominant["frac_of_vector_peak"] = (dominant.get("valu") or {}).get("frac_of_vector_peak")
-        if fb_mode_used != "exact":
-            # the Farneback yardstick is the vector peak, not HBM.  The headline triple prices the oracle's EXACT operation counts of the
-            # level (avdo_ops_*) against the vector peaks of their mix; the bytes view stays beside it (`hbm`).  What sets the step time is in
-            # `limiter`: the ISA table of the three role loops (tools/isa_loop_table.py, profiles/r05_isa_k_fb_fast320.txt).
-            v = dominant.get("valu") or {}
-            dominant["hbm"] = {"achieved": dominant["achieved"], "peak": dominant["peak"], "unit": "GB/s", "frac": dominant["frac"]}
-            if v.get("frac_of_vector_peak"):
-                t_lvl = float(excl[4]) * 1e-3
-                ops_t = (v["f32_ops_per_level"] + v["f64_ops_per_level"]) / t_lvl / 1e12 if t_lvl > 0 else 0.0
-                dominant.update({"bound": "valu", "achieved": round(ops_t, 2), "peak": round(ops_t / v["frac_of_vector_peak"], 2),
-                                 "unit": "Top/s", "frac": v["frac_of_vector_peak"]})
-            dominant["limiter"] = ("two co-limiters that do not overlap, and a workgroup barrier per 4-row step: vector-ALU issue on the three SIMDs that carry a "
-                                   "solver wave -- per step X (window sums + 2 x 2 solve in double: 159 f64 + 100 f32 instructions, 849 cycles) + one normal-equation "
-                                   "wave (168 f32 + 20 loads, 335) + the chain wave (89 f32 + 35 f64, 307) = ~1 490 of the ~3 200 cycles a step takes (84 steps per launch; "
-                                   "PMC: VALU issue 0.54 chip-wide) -- and the texture addresser (129 vector-memory instructions x 16 cycles per step = 0.65; PMC 0.53); "
-                                   "the normal-equation waves are both the loads' only issuers and the second-largest VALU consumer "
-                                   "(tools/isa_loop_table.py, profiles/r05_isa_k_fb_fast320.txt)")
-        else:
-            dominant["limiter"] = "the dependent double-add chain of the horizontal scan + VALU issue of the vertical waves, one workgroup per pair on 119 of 256 CUs"
-        dominant["kernels"] = kernel_table(n, h, w, kms, None if nv12 is None else nv12["pre_ms"])
-        # north_star's ">= 60 % of the HBM peak on preprocessing": the fused kernel alone (its row of the table), not the stage that also
-        # holds the aHash kernel and the profiling events
-        dominant["preprocess_frac"] = next((k["frac"] for k in dominant["kernels"] if k["name"] == "preprocess"), pre["frac"])
         out = {
             "metric": "sampled frames/sec analysed (1080p30 60 s clip, 2 fps sampling)",
             "value": round(fps(elapsed), 2), "unit": "frames/s", "n_gpus": world, "steps": args.steps,
@@ -965,157 +987,188 @@ def main():
                        "fb_mode": fb_mode_used,
                        "fb_wide160": int(ctxs[0].get_option("fb_wide160")),      # 2 (default) = per call: one strip per pair with clips in flight, two strips for a clip alone
                        "input_copies_in_hbm": m,
-                       "sec_per_video": round((host_lat_ms if host_lat_ms is not None else latency_ms) / 1e3, 6),
-                       "sec_per_video_note": ("one clip alone, from decoded frames in pinned host memory to the fused result "
-                                              "(PCIe-inclusive, median of 5)" if host_lat_ms is not None else
-                                              "one clip alone, frames resident in HBM (--no-pcie)"),
-                       "sec_per_video_nv12": None if nv12 is None else round(nv12["host_latency_ms"] / 1e3, 6),
-                       "sec_per_video_nv12_note": "the same clip handed over as pinned NV12 decoder surfaces (1.5 B per pixel over PCIe, median of 5)",
-                       "sec_per_video_resident": round(latency_ms / 1e3, 6),
-                       "sec_per_video_resident_note": f"one clip alone, frames already in HBM (median of {n_excl}, before the timed region)",
                        "decoded_frame_equivalent_fps": round(fps(elapsed) * 15, 1),
                        "parallelism": f"clip-parallel x{world}, one all-gather ({args.backend}) of 32 B/frame records" if world > 1 else "single GPU",
                        # what the process group itself reports after init (a SCALE record can be checked for N ranks at a glance)
                        "rccl_ranks_seen": (tdist.get_world_size() if use_dist else 1), "collective_backend": (args.backend if use_dist else None)},
-            "roofline": dominant,
-            "roofline_preprocess": pre,
-            "roofline_farneback_stage": fb,
-            "stages_ms": {"preprocess": round(float(excl[0]), 4), "clip_table_upload": round(float(excl[1]), 4),
-                          "farneback_and_flow_stats": round(float(excl[2]), 4), "records_copy_out": round(float(excl[3]), 4),
-                          "level0_all_iterations": round(float(excl[4]), 4),
-                          "note": "HIP events on the library's stream, clips run alone before the timed region; preprocess includes the aHash kernel, "
-                                  "farneback_and_flow_stats the record kernel (Hamming distances, record assembly)"},
-            "stages_ms_timed_region": {"preprocess": round(float(timed_stage[0]), 4),
-                                       "farneback_and_flow_stats": round(float(timed_stage[2]), 4),
-                                       "level0_all_iterations": round(float(timed_stage[4]), 4),
-                                       "note": "event-to-event times while other clips share the GPU"},
             "result_check": {"ai_timeline_head": [round(v, 6) for v in result["timeline"][:3]],
                              "dup_density": result["summary"]["dup_density"], **fused["result"]},
         }
-        # the whole step against the HBM roofline: PMC traffic of one clip (every kernel of the path) over the time the GPU
-        # spends per clip at the bench's throughput -- the figure the per-kernel fractions cannot show (the level kernels
-        # hold 119 of 256 CUs and leave the bandwidth to the other clips' kernels)
-        whole = load_pmc().get("whole_clip", {}).get("hbm_bytes") if (n, h, w) == (120, 1080, 1920) else None
-        if whole is not None and world == 1:
-            gbs = whole / (ms_per_step * 1e-3) / 1e9
-            out["roofline_whole_step"] = {
-                "what": "all kernels of one clip (preprocess, hash, pyramid, polynomial expansion, 4 level kernels, flow_up, statistics)",
-                "bound": "hbm", "traffic": whole, "algorithmic_bytes_input_only": preprocess_bytes_per_frame(h, w) * n,
-                "achieved": round(gbs, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(gbs / HBM_PEAK_GBS, 4),
-                "note": "PMC HBM traffic per clip (traffic replayed from " + os.path.relpath(PMC_FILE, ROOT) + ") / ms_per_step with clips in flight"}
-            out["roofline"]["whole_step_frac"] = out["roofline_whole_step"]["frac"]
-        if pcie_fps is not None:
-            out["pcie_inclusive_fps"] = round(pcie_fps_inflight if pcie_fps_inflight is not None else pcie_fps, 1)
-            out["pcie_inclusive_fps_one_clip_at_a_time"] = round(pcie_fps, 1)
-        if nv12 is not None:
-            nv_alg = n * (h * w * 3 // 2 + 320 * 320 + 1024 + 16)
-            nv_ach = nv_alg / (nv12["pre_ms"] * 1e-3) / 1e9
-            out["roofline_nv12_ingest"] = {
-                "kernel": "k_preprocess_nv12 (NV12 surface -> libswscale-style BGR in registers -> gray in LDS -> the fused phases; no BGR in HBM)",
-                "bound": "hbm", "achieved": round(nv_ach, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(nv_ach / HBM_PEAK_GBS, 4),
-                "traffic": None, "algorithmic_bytes_per_launch": nv_alg, "bytes_per_frame_read": h * w * 3 // 2,
-                "avg_launch_ms": round(nv12["pre_ms"], 4),
-                "stage_ms_with_hash_and_events": round(nv12["pre_stage_ms"], 4),   # what `avg_launch_ms` held in rounds 3 and 4 (0.27-0.28)
-                "bound_note": "VALU-bound: ~20 integer operations per pixel for the three clipped table values and the gray",
-                "pcie_inclusive_fps_one_clip_at_a_time": round(nv12["host_fps"], 1),
-                "pcie_inclusive_fps": None if "host_fps_inflight" not in nv12 else round(nv12["host_fps_inflight"], 1),
-                "pcie_note": "pinned NV12 surfaces staged inside the call: 373 MB per clip, the link (~55 GB/s) bounds it at ~17.6 k frames/s"}
-        if vit is not None:
-            mm = vit["frames"] * 196
-            fl = 2.0 * mm * 768 * 768
-            tf = fl / (vit["gemm_ms"] * 1e-3) / 1e12
-            out["mfma_patch_embed"] = {
-                "kernel": "k_gemm_bf16_nt_persistent (ViT-B/16 patch embedding: [frames x 196, 768] x [768, 768], bf16 in, f32 accumulate, "
-                          "v_mfma_f32_16x16x32_bf16, 256x256 tiles, LDS-DMA ring that runs on across tiles, one workgroup per CU)",
-                "extension": "no reference counterpart (the reference has no learned model); seeded random weights; not part of value / ai_score",
-                "bound": "mfma", "achieved": round(tf, 1), "peak": 2500.0, "unit": "TFLOP/s", "frac": round(tf / 2500.0, 4),
-                "tokens_dtype": "bf16 (f32 accumulate, rounded once)", "achieved_with_f32_tokens": round(fl / (vit["gemm_ms_f32_tokens"] * 1e-3) / 1e12, 1),
-                "M": mm, "N": 768, "K": 768, "flops_per_launch": fl, "avg_launch_ms": round(vit["gemm_ms"], 4),
-                "frames_per_launch": vit["frames"], "patchify_plus_call_overhead_ms": round(vit["whole_call_ms"], 3),
-                "timed": "20 launches between two HIP events on the library's stream, patches resident in HBM"}
-        if cnn is not None:
-            fl = 2.0 * cnn["macs_per_frame"] * cnn["frames"]
-            tf = fl / (cnn["forward_ms"] * 1e-3) / 1e12
-            cnn_traffic, cnn_traffic_file = None, None
-            try:
-                for name in ("r04_pmc_extensions.json", "r02_pmc_extensions.json"):
-                    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "profiles", name)
-                    if os.path.exists(path):
-                        ext = json.load(open(path))
-                        if cnn["frames"] == 120:
-                            cnn_traffic = ext["cnn_forward_120_frames"]["hbm_bytes"]
-                            cnn_traffic_file = "profiles/" + name
-                        break
-            except (OSError, KeyError, ValueError):
-                pass
-            tf4 = 2.0 * cnn["macs_per_frame"] * cnn["frames_four_clips"] / (cnn["forward_ms_four_clips"] * 1e-3) / 1e12
-            out["mfma_cnn_forward"] = {
-                "kernel": "k_conv_bf16 + k_conv3_expand (ResNet-50-style forward: every convolution one implicit GEMM, the activation operand gathered by "
-                          "LDS-DMA from blocked + swizzled bf16 activations, bias / residual / ReLU fused; in the 56x56 and 28x28 stages a block's 3x3 and its "
-                          "expanding 1x1 are ONE launch with the mid activation in LDS, in the stride-1 blocks with the 3x3's input as one slab in LDS (k_slab3_expand); the 7x7 stem gathers pixel pairs from a zero-bordered input image) + input conversion, max / average pooling, linear",
-                "extension": "no reference counterpart (the reference has no learned model); seeded random weights; not part of value / ai_score",
-                "bound": "mfma", "achieved": round(tf, 1), "peak": 2500.0, "unit": "TFLOP/s", "frac": round(tf / 2500.0, 4),
-                "frames_per_forward": cnn["frames"], "gmac_per_frame": round(cnn["macs_per_frame"] / 1e9, 3),
-                "forward_ms": round(cnn["forward_ms"], 3), "frames_per_s": round(cnn["frames"] / (cnn["forward_ms"] * 1e-3), 1),
-                "launches_per_forward": 50 if cnn["fused"] else 57, "top1_head": cnn["top1_head"],
-                "forward_ms_layer_by_layer": round(cnn["forward_ms_layer_by_layer"], 3),
-                "four_clips_per_pass": {"frames": cnn["frames_four_clips"], "forward_ms": round(cnn["forward_ms_four_clips"], 3),
-                                        "achieved": round(tf4, 1), "frac": round(tf4 / 2500.0, 4)},
-                "hbm_traffic_bytes_per_forward": cnn_traffic, "hbm_traffic_from_profiles": cnn_traffic_file,
-                "hbm_gbps": None if cnn_traffic is None else round(cnn_traffic / (cnn["forward_ms"] * 1e-3) / 1e9, 1),
-                "hbm_note": "PMC traffic of 120 frames: bf16 activations written and read once per layer were 63 MB per frame layer by layer (round 2); "
-                            "what bounds a layer is the per-CU L2 -> LDS ingest (~40 GB/s per CU, tools/ldsdma_bench.hip), see profiles/r04_experiments.md section 5",
-                "timed": "5 whole forward passes (BGR frames in HBM to logits) between two HIP events on the library's stream"}
-        if norm is not None:
-            lnb = norm["rows"] * 768 * 4                             # bf16 tokens read once and written once
-            gbs = lnb / (norm["ln_ms"] * 1e-3) / 1e9
-            out["layernorm_tokens"] = {
-                "kernel": "k_layernorm<3, bf16> (LayerNorm over the 768 values of a patch-embed token: one wave per row, the row in registers, "
-                          "wave-shuffle reductions, float32 statistics; one pass over HBM)",
-                "extension": "no reference counterpart; north_star's conv / GEMM / LayerNorm / softmax stack; not part of value / ai_score",
-                "bound": "hbm", "achieved": round(gbs, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(gbs / HBM_PEAK_GBS, 4),
-                "rows": norm["rows"], "algorithmic_bytes_per_launch": lnb, "avg_launch_ms": round(norm["ln_ms"], 4),
-                "softmax_1000_logits": {"rows": norm["softmax_rows"], "avg_launch_ms": round(norm["softmax_ms"], 4),
-                                        "note": "120 rows of 4 KB: a launch-latency-sized kernel (one wave per row)"}}
-        if audio is not None:
-            out["audio_analyzer"] = {
-                "what": "avd_audio_features: RMS / zero crossings / Hann + 8000-point real DFT in double (80 x 100 two-step, exact twiddle table) / flatness, roll-off, centroid "
-                        "sums for every half-second window of a 60 s 16 kHz sound track in one call (reference audio.py:40-61), reported apart",
-                "windows": audio["windows"], "gpu_call_ms": round(audio["features_ms"], 3), "host_tail_ms": round(audio["tail_ms"], 3),
-                "windows_per_s": round(audio["windows"] / (audio["features_ms"] * 1e-3), 1), "f64_gflop_per_call_direct_form": round(audio["windows"] * 4001 * 8000 * 4 / 1e9, 2)}
-        if exact is not None:
-            edom, _, efb = roofline_objects(n, h, w, exact["stage"], exact["latency_ms"], "exact", ops)
-            out["fb_modes"] = {
-                "value_uses": fb_mode_used, "rerun_pairs": rerun_pairs,
-                "guarantee": "pairs flagged by the level kernels (singular normal equations; sign of a residue-sized flow at the top / left border) re-run by the "
-                             "exact kernels: bit-identical; others flow <= 1e-5 px, flow_mean/var rel 1e-6, ai_susp 1e-6 -- no content family excepted "
-                             "(tests/test_gpu_fbfast.py, tests/test_gpu_soak.py: 28 families)",
-                "exact_frames_per_s": round(exact["fps"], 2), "exact_level320_ms": round(float(exact["stage"][4]), 4),
-                "rerun_cost": rerun_cost,
-                "fast": {"what": "csrc/avd_fbfast.hip + exact re-run of flagged pairs (host-driven, compacted list): flow identical to the oracle on well-posed inputs (<= 1e-5 px), ill-posed pairs re-run exactly",
-                         "frames_per_s": out["value"], "sec_per_video_resident": round(latency_ms / 1e3, 6),
-                         "level0_all_iterations_ms": round(float(excl[4]), 4), "farneback_and_flow_stats_ms": round(float(excl[2]), 4),
-                         "flow_mean_head": [float(v) for v in recs[0]["flow_mean"][1:4]]},
-                "exact": {"what": "csrc/avd_fbfused.hip: bit-identical to the oracle, one workgroup per pair",
-                          "frames_per_s": round(exact["fps"], 2), "sec_per_video_resident": round(exact["latency_ms"] / 1e3, 6),
-                          "level0_all_iterations_ms": round(float(exact["stage"][4]), 4),
-                          "farneback_and_flow_stats_ms": round(float(exact["stage"][2]), 4),
-                          "flow_mean_head": exact["flow_mean_head"], "roofline": edom}}
-        if batches is not None:
-            out["short_clips_fps"] = {
-                "workload": "BASELINE.json configs[0]-sized clips: 20 sampled 720p frames each, resident in HBM, 13 clips per batch "
-                            "(avd_analyze_batch: one Farneback launch sequence over the 259 pairs of a batch), batches in flight as clips are",
-                "value": round(batches["short"][0], 1), "unit": "frames/s",
-                "one_clip_per_call": round(batches["short"][1], 1)}
-            out["mixed_stream_fps"] = {
-                "workload": "BASELINE.json configs[4]: shuffled stream of 20-frame clips, 6 x 720p + 4 x 1080p + 2 x 4K per batch of 240 frames "
-                            "(cached geometry tables, nothing allocated in steady state; the Farneback stage batches uniformly at 320 x 320)",
-                "value": round(batches["mixed"][0], 1), "unit": "frames/s",
-                "one_clip_per_call": round(batches["mixed"][1], 1)}
+        if args.full:
+            dominant, pre, fb = roofline_objects(n, h, w, excl, latency_ms, "exact" if fb_mode_used == "exact" else "fast", ops)
+            pmc_k = load_pmc().get("k_fb_level<320>" if fb_mode_used == "exact" else "k_fb_fast<320>", {}) if (n, h, w) == (120, 1080, 1920) else {}
+            dominant["traffic_from_profiles"] = os.path.relpath(PMC_FILE, ROOT) if dominant.get("traffic") is not None else None
+            dominant["valu_issue_frac_from_profiles"] = pmc_k.get("valu_issue_frac")
+            dominant["ta_busy_frac_from_profiles"] = pmc_k.get("ta_busy_frac")
+            dominant["frac_of_vector_peak"] = (dominant.get("valu") or {}).get("frac_of_vector_peak")
+            if fb_mode_used != "exact":
+                # the Farneback yardstick is the vector peak, not HBM.  The headline triple prices the oracle's EXACT operation counts of the
+                # level (avdo_ops_*) against the vector peaks of their mix; the bytes view stays beside it (`hbm`).  What sets the step time is in
+                # `limiter`: the ISA table of the three role loops (tools/isa_loop_table.py, profiles/r05_isa_k_fb_fast320.txt).
+                v = dominant.get("valu") or {}
+                dominant["hbm"] = {"achieved": dominant["achieved"], "peak": dominant["peak"], "unit": "GB/s", "frac": dominant["frac"]}
+                if v.get("frac_of_vector_peak"):
+                    t_lvl = float(excl[4]) * 1e-3
+                    ops_t = (v["f32_ops_per_level"] + v["f64_ops_per_level"]) / t_lvl / 1e12 if t_lvl > 0 else 0.0
+                    dominant.update({"bound": "valu", "achieved": round(ops_t, 2), "peak": round(ops_t / v["frac_of_vector_peak"], 2),
+                                     "unit": "Top/s", "frac": v["frac_of_vector_peak"]})
+                dominant["limiter"] = ("two co-limiters that do not overlap, and a workgroup barrier per 4-row step: vector-ALU issue on the three SIMDs that carry a "
+                                       "solver wave -- per step X (window sums + 2 x 2 solve in double: 159 f64 + 100 f32 instructions, 849 cycles) + one normal-equation "
+                                       "wave (168 f32 + 20 loads, 335) + the chain wave (89 f32 + 35 f64, 307) = ~1 490 of the ~3 200 cycles a step takes (84 steps per launch; "
+                                       "PMC: VALU issue 0.54 chip-wide) -- and the texture addresser (129 vector-memory instructions x 16 cycles per step = 0.65; PMC 0.53); "
+                                       "the normal-equation waves are both the loads' only issuers and the second-largest VALU consumer "
+                                       "(tools/isa_loop_table.py, profiles/r05_isa_k_fb_fast320.txt)")
+            else:
+                dominant["limiter"] = "the dependent double-add chain of the horizontal scan + VALU issue of the vertical waves, one workgroup per pair on 119 of 256 CUs"
+            dominant["kernels"] = kernel_table(n, h, w, kms, None if nv12 is None else nv12["pre_ms"])
+            # north_star's ">= 60 % of the HBM peak on preprocessing": the fused kernel alone (its row of the table), not the stage that also
+            # holds the aHash kernel and the profiling events
+            dominant["preprocess_frac"] = next((k["frac"] for k in dominant["kernels"] if k["name"] == "preprocess"), pre["frac"])
+            out["config"].update({"sec_per_video": round((host_lat_ms if host_lat_ms is not None else latency_ms) / 1e3, 6),
+                                  "sec_per_video_note": ("one clip alone, from decoded frames in pinned host memory to the fused result "
+                                                         "(PCIe-inclusive, median of 5)" if host_lat_ms is not None else
+                                                         "one clip alone, frames resident in HBM (--no-pcie)"),
+                                  "sec_per_video_nv12": None if nv12 is None else round(nv12["host_latency_ms"] / 1e3, 6),
+                                  "sec_per_video_nv12_note": "the same clip handed over as pinned NV12 decoder surfaces (1.5 B per pixel over PCIe, median of 5)",
+                                  "sec_per_video_resident": round(latency_ms / 1e3, 6),
+                                  "sec_per_video_resident_note": f"one clip alone, frames already in HBM (median of {n_excl}, before the timed region)"})
+            out.update({
+                "roofline": dominant,
+                "roofline_preprocess": pre,
+                "roofline_farneback_stage": fb,
+                "stages_ms": {"preprocess": round(float(excl[0]), 4), "clip_table_upload": round(float(excl[1]), 4),
+                              "farneback_and_flow_stats": round(float(excl[2]), 4), "records_copy_out": round(float(excl[3]), 4),
+                              "level0_all_iterations": round(float(excl[4]), 4),
+                              "note": "HIP events on the library's stream, clips run alone before the timed region; preprocess includes the aHash kernel, "
+                                      "farneback_and_flow_stats the record kernel (Hamming distances, record assembly)"},
+                "stages_ms_timed_region": {"preprocess": round(float(timed_stage[0]), 4),
+                                           "farneback_and_flow_stats": round(float(timed_stage[2]), 4),
+                                           "level0_all_iterations": round(float(timed_stage[4]), 4),
+                                           "note": "event-to-event times while other clips share the GPU"}})
+            # the whole step against the HBM roofline: PMC traffic of one clip (every kernel of the path) over the time the GPU
+            # spends per clip at the bench's throughput -- the figure the per-kernel fractions cannot show (the level kernels
+            # hold 119 of 256 CUs and leave the bandwidth to the other clips' kernels)
+            whole = load_pmc().get("whole_clip", {}).get("hbm_bytes") if (n, h, w) == (120, 1080, 1920) else None
+            if whole is not None and world == 1:
+                gbs = whole / (ms_per_step * 1e-3) / 1e9
+                out["roofline_whole_step"] = {
+                    "what": "all kernels of one clip (preprocess, hash, pyramid, polynomial expansion, 4 level kernels, flow_up, statistics)",
+                    "bound": "hbm", "traffic": whole, "algorithmic_bytes_input_only": preprocess_bytes_per_frame(h, w) * n,
+                    "achieved": round(gbs, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(gbs / HBM_PEAK_GBS, 4),
+                    "note": "PMC HBM traffic per clip (traffic replayed from " + os.path.relpath(PMC_FILE, ROOT) + ") / ms_per_step with clips in flight"}
+                out["roofline"]["whole_step_frac"] = out["roofline_whole_step"]["frac"]
+            if pcie_fps is not None:
+                out["pcie_inclusive_fps"] = round(pcie_fps_inflight if pcie_fps_inflight is not None else pcie_fps, 1)
+                out["pcie_inclusive_fps_one_clip_at_a_time"] = round(pcie_fps, 1)
+            if nv12 is not None:
+                nv_alg = n * (h * w * 3 // 2 + 320 * 320 + 1024 + 16)
+                nv_ach = nv_alg / (nv12["pre_ms"] * 1e-3) / 1e9
+                out["roofline_nv12_ingest"] = {
+                    "kernel": "k_preprocess_nv12 (NV12 surface -> libswscale-style BGR in registers -> gray in LDS -> the fused phases; no BGR in HBM)",
+                    "bound": "hbm", "achieved": round(nv_ach, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(nv_ach / HBM_PEAK_GBS, 4),
+                    "traffic": None, "algorithmic_bytes_per_launch": nv_alg, "bytes_per_frame_read": h * w * 3 // 2,
+                    "avg_launch_ms": round(nv12["pre_ms"], 4),
+                    "stage_ms_with_hash_and_events": round(nv12["pre_stage_ms"], 4),   # what `avg_launch_ms` held in rounds 3 and 4 (0.27-0.28)
+                    "bound_note": "VALU-bound: ~20 integer operations per pixel for the three clipped table values and the gray",
+                    "pcie_inclusive_fps_one_clip_at_a_time": round(nv12["host_fps"], 1),
+                    "pcie_inclusive_fps": None if "host_fps_inflight" not in nv12 else round(nv12["host_fps_inflight"], 1),
+                    "pcie_note": "pinned NV12 surfaces staged inside the call: 373 MB per clip, the link (~55 GB/s) bounds it at ~17.6 k frames/s"}
+            if vit is not None:
+                mm = vit["frames"] * 196
+                fl = 2.0 * mm * 768 * 768
+                tf = fl / (vit["gemm_ms"] * 1e-3) / 1e12
+                out["mfma_patch_embed"] = {
+                    "kernel": "k_gemm_bf16_nt_persistent (ViT-B/16 patch embedding: [frames x 196, 768] x [768, 768], bf16 in, f32 accumulate, "
+                              "v_mfma_f32_16x16x32_bf16, 256x256 tiles, LDS-DMA ring that runs on across tiles, one workgroup per CU)",
+                    "extension": "no reference counterpart (the reference has no learned model); seeded random weights; not part of value / ai_score",
+                    "bound": "mfma", "achieved": round(tf, 1), "peak": 2500.0, "unit": "TFLOP/s", "frac": round(tf / 2500.0, 4),
+                    "tokens_dtype": "bf16 (f32 accumulate, rounded once)", "achieved_with_f32_tokens": round(fl / (vit["gemm_ms_f32_tokens"] * 1e-3) / 1e12, 1),
+                    "M": mm, "N": 768, "K": 768, "flops_per_launch": fl, "avg_launch_ms": round(vit["gemm_ms"], 4),
+                    "frames_per_launch": vit["frames"], "patchify_plus_call_overhead_ms": round(vit["whole_call_ms"], 3),
+                    "timed": "20 launches between two HIP events on the library's stream, patches resident in HBM"}
+            if cnn is not None:
+                fl = 2.0 * cnn["macs_per_frame"] * cnn["frames"]
+                tf = fl / (cnn["forward_ms"] * 1e-3) / 1e12
+                cnn_traffic, cnn_traffic_file = None, None
+                try:
+                    for name in ("r04_pmc_extensions.json", "r02_pmc_extensions.json"):
+                        path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "profiles", name)
+                        if os.path.exists(path):
+                            ext = json.load(open(path))
+                            if cnn["frames"] == 120:
+                                cnn_traffic = ext["cnn_forward_120_frames"]["hbm_bytes"]
+                                cnn_traffic_file = "profiles/" + name
+                            break
+                except (OSError, KeyError, ValueError):
+                    pass
+                tf4 = 2.0 * cnn["macs_per_frame"] * cnn["frames_four_clips"] / (cnn["forward_ms_four_clips"] * 1e-3) / 1e12
+                out["mfma_cnn_forward"] = {
+                    "kernel": "k_conv_bf16 + k_conv3_expand (ResNet-50-style forward: every convolution one implicit GEMM, the activation operand gathered by "
+                              "LDS-DMA from blocked + swizzled bf16 activations, bias / residual / ReLU fused; in the 56x56 and 28x28 stages a block's 3x3 and its "
+                              "expanding 1x1 are ONE launch with the mid activation in LDS, in the stride-1 blocks with the 3x3's input as one slab in LDS (k_slab3_expand); the 7x7 stem gathers pixel pairs from a zero-bordered input image) + input conversion, max / average pooling, linear",
+                    "extension": "no reference counterpart (the reference has no learned model); seeded random weights; not part of value / ai_score",
+                    "bound": "mfma", "achieved": round(tf, 1), "peak": 2500.0, "unit": "TFLOP/s", "frac": round(tf / 2500.0, 4),
+                    "frames_per_forward": cnn["frames"], "gmac_per_frame": round(cnn["macs_per_frame"] / 1e9, 3),
+                    "forward_ms": round(cnn["forward_ms"], 3), "frames_per_s": round(cnn["frames"] / (cnn["forward_ms"] * 1e-3), 1),
+                    "launches_per_forward": 50 if cnn["fused"] else 57, "top1_head": cnn["top1_head"],
+                    "forward_ms_layer_by_layer": round(cnn["forward_ms_layer_by_layer"], 3),
+                    "four_clips_per_pass": {"frames": cnn["frames_four_clips"], "forward_ms": round(cnn["forward_ms_four_clips"], 3),
+                                            "achieved": round(tf4, 1), "frac": round(tf4 / 2500.0, 4)},
+                    "hbm_traffic_bytes_per_forward": cnn_traffic, "hbm_traffic_from_profiles": cnn_traffic_file,
+                    "hbm_gbps": None if cnn_traffic is None else round(cnn_traffic / (cnn["forward_ms"] * 1e-3) / 1e9, 1),
+                    "hbm_note": "PMC traffic of 120 frames: bf16 activations written and read once per layer were 63 MB per frame layer by layer (round 2); "
+                                "what bounds a layer is the per-CU L2 -> LDS ingest (~40 GB/s per CU, tools/ldsdma_bench.hip), see profiles/r04_experiments.md section 5",
+                    "timed": "5 whole forward passes (BGR frames in HBM to logits) between two HIP events on the library's stream"}
+            if norm is not None:
+                lnb = norm["rows"] * 768 * 4                             # bf16 tokens read once and written once
+                gbs = lnb / (norm["ln_ms"] * 1e-3) / 1e9
+                out["layernorm_tokens"] = {
+                    "kernel": "k_layernorm<3, bf16> (LayerNorm over the 768 values of a patch-embed token: one wave per row, the row in registers, "
+                              "wave-shuffle reductions, float32 statistics; one pass over HBM)",
+                    "extension": "no reference counterpart; north_star's conv / GEMM / LayerNorm / softmax stack; not part of value / ai_score",
+                    "bound": "hbm", "achieved": round(gbs, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(gbs / HBM_PEAK_GBS, 4),
+                    "rows": norm["rows"], "algorithmic_bytes_per_launch": lnb, "avg_launch_ms": round(norm["ln_ms"], 4),
+                    "softmax_1000_logits": {"rows": norm["softmax_rows"], "avg_launch_ms": round(norm["softmax_ms"], 4),
+                                            "note": "120 rows of 4 KB: a launch-latency-sized kernel (one wave per row)"}}
+            if audio is not None:
+                out["audio_analyzer"] = {
+                    "what": "avd_audio_features: RMS / zero crossings / Hann + 8000-point real DFT in double (80 x 100 two-step, exact twiddle table) / flatness, roll-off, centroid "
+                            "sums for every half-second window of a 60 s 16 kHz sound track in one call (reference audio.py:40-61), reported apart",
+                    "windows": audio["windows"], "gpu_call_ms": round(audio["features_ms"], 3), "host_tail_ms": round(audio["tail_ms"], 3),
+                    "windows_per_s": round(audio["windows"] / (audio["features_ms"] * 1e-3), 1), "f64_gflop_per_call_direct_form": round(audio["windows"] * 4001 * 8000 * 4 / 1e9, 2)}
+            if exact is not None:
+                edom, _, efb = roofline_objects(n, h, w, exact["stage"], exact["latency_ms"], "exact", ops)
+                out["fb_modes"] = {
+                    "value_uses": fb_mode_used, "rerun_pairs": rerun_pairs,
+                    "guarantee": "pairs flagged by the level kernels (singular normal equations; sign of a residue-sized flow at the top / left border) re-run by the "
+                                 "exact kernels: bit-identical; others flow <= 1e-5 px, flow_mean/var rel 1e-6, ai_susp 1e-6 -- no content family excepted "
+                                 "(tests/test_gpu_fbfast.py, tests/test_gpu_soak.py: 28 families)",
+                    "exact_frames_per_s": round(exact["fps"], 2), "exact_level320_ms": round(float(exact["stage"][4]), 4),
+                    "rerun_cost": rerun_cost,
+                    "fast": {"what": "csrc/avd_fbfast.hip + exact re-run of flagged pairs (host-driven, compacted list): flow identical to the oracle on well-posed inputs (<= 1e-5 px), ill-posed pairs re-run exactly",
+                             "frames_per_s": out["value"], "sec_per_video_resident": round(latency_ms / 1e3, 6),
+                             "level0_all_iterations_ms": round(float(excl[4]), 4), "farneback_and_flow_stats_ms": round(float(excl[2]), 4),
+                             "flow_mean_head": [float(v) for v in recs[0]["flow_mean"][1:4]]},
+                    "exact": {"what": "csrc/avd_fbfused.hip: bit-identical to the oracle, one workgroup per pair",
+                              "frames_per_s": round(exact["fps"], 2), "sec_per_video_resident": round(exact["latency_ms"] / 1e3, 6),
+                              "level0_all_iterations_ms": round(float(exact["stage"][4]), 4),
+                              "farneback_and_flow_stats_ms": round(float(exact["stage"][2]), 4),
+                              "flow_mean_head": exact["flow_mean_head"], "roofline": edom}}
+            if batches is not None:
+                out["short_clips_fps"] = {
+                    "workload": "BASELINE.json configs[0]-sized clips: 20 sampled 720p frames each, resident in HBM, 13 clips per batch "
+                                "(avd_analyze_batch: one Farneback launch sequence over the 259 pairs of a batch), batches in flight as clips are",
+                    "value": round(batches["short"][0], 1), "unit": "frames/s",
+                    "one_clip_per_call": round(batches["short"][1], 1)}
+                out["mixed_stream_fps"] = {
+                    "workload": "BASELINE.json configs[4]: shuffled stream of 20-frame clips, 6 x 720p + 4 x 1080p + 2 x 4K per batch of 240 frames "
+                                "(cached geometry tables, nothing allocated in steady state; the Farneback stage batches uniformly at 320 x 320)",
+                    "value": round(batches["mixed"][0], 1), "unit": "frames/s",
+                    "one_clip_per_call": round(batches["mixed"][1], 1)}
+            out["ops"] = ops
+            out["cpu_baseline"] = cpu_base
         if "fb_modes" not in out:
             out["fb_modes"] = {"value_uses": fb_mode_used, "rerun_pairs": rerun_pairs}
-        out["ops"] = ops
-        out["cpu_baseline"] = cpu_base
         if args.details:
             with open(args.details, "w") as fh:
                 json.dump(out, fh, indent=1, default=lambda o: o.tolist() if hasattr(o, "tolist") else str(o))

@@ -190,3 +190,78 @@ def test_the_printed_line_is_compact_and_keeps_what_the_driver_reads():
     full["n_gpus"] = 8
     l8 = b.compact_line(full)
     assert l8["cpu_baseline"] is None and l8["roofline"]["kernels"] and "details" not in l8
+
+
+def test_plain_run_times_k_steps_once_and_the_rest_waits_for_full():
+    """A plain run sets up, warms up, times EXACTLY --steps steps once and prints the line; every other measurement (CPU
+    baseline, exclusive pass, PCIe / NV12, extensions, exact mode, re-run cost, batches, repeats, the profiled pass after
+    the timed region) runs with --full only."""
+    src = open(os.path.join(ROOT, "bench.py")).read()
+    assert 'ap.add_argument("--full", action="store_true"' in src
+    assert 'ap.add_argument("--dump-outputs", default=None, metavar="DIR"' in src
+    assert "for _ in range(max(1, args.repeats) if args.full else 1):" in src
+    assert "if args.full and rank == 0 and world == 1:" in src                   # CPU legs
+    for cond in ("if args.full and not args.no_pcie", "if args.full and not args.no_vit and world == 1:",
+                 "if args.full and not args.no_extras and world == 1"):
+        assert src.count(cond) >= 1, cond
+    assert src.count("if not args.no_") == 0                                      # nothing left ungated
+    main = src[src.index("def main():"):]
+    assert main.index("set_prof(args.full)") < main.index("    if args.full:\n        # EXCLUSIVE pass")
+
+
+def test_plain_line_keeps_the_headline_keys():
+    """The line of a plain run: the headline keys mean what they meant before, nothing that --full measures is printed."""
+    import json
+    b = _bench()
+    full = _verbose_sample(b)
+    plain = {k: full[k] for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+                                  "vs_baseline", "dtype", "data", "fb_mode_used", "result_check")}
+    plain["repeats"] = {"n": 1, "statistic": "median", "value_min": 126000.0, "value_max": 126000.0}
+    plain["config"] = {k: full["config"][k] for k in ("workload", "frames_per_clip", "height", "width", "clips_per_step",
+                                                      "clips_in_flight_per_gpu", "fb_mode", "parallelism")}
+    plain["fb_modes"] = {"value_uses": "fast+rerun", "rerun_pairs": 0}
+    line = json.loads(json.dumps(b.compact_line(plain)))
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert line[key] == full[key], key
+    assert "roofline" not in line and "cpu_baseline" not in line and "extensions" not in line and "sec_per_video" not in line["config"]
+    assert line["repeats"]["n"] == 1 and line["fb_modes"] == {"value_uses": "fast+rerun", "rerun_pairs": 0}
+
+
+def test_dump_outputs_writes_what_the_caller_receives(tmp_path):
+    """--dump-outputs DIR: the records, the video result and the fused result of one step as float32 / float64 .npy files,
+    equal to the values the caller holds (integer record fields exactly), far below 64 MB."""
+    import numpy as np
+    import avd_hip
+    from avd_hip.pipeline import audio_unavailable
+    from avd_hip.timeline import records_to_result
+    from app.analyzers import fusion, heuristics_v2
+    b = _bench()
+    n, h, w = 120, 1080, 1920
+    rng = np.random.default_rng(5)
+    rec = np.zeros(n, avd_hip.RECORD_DTYPE)
+    rec["lap_sum"] = rng.integers(-10**6, 10**6, n)
+    rec["lap_sumsq"] = rng.integers(10**9, 10**11, n)
+    rec["flow_mean"] = rng.random(n, dtype=np.float32) * 4
+    rec["flow_var"] = rng.random(n, dtype=np.float32)
+    rec["ham"] = rng.integers(0, 40, n)
+    rec["ham"][0] = -1
+    meta = {"width": w, "height": h, "fps": 30.0, "duration": n / 2.0}
+    video = records_to_result(rec, 320 * 320, w, h, meta["fps"], meta["duration"])
+    fused = fusion.fuse(audio_unavailable("", meta), video, heuristics_v2.compute_hints({**meta, "bit_rate": 8_000_000}, ""))
+    names = b.dump_outputs(str(tmp_path / "out"), rec, video, fused)
+    files = sorted(p.name for p in (tmp_path / "out").iterdir())
+    assert files == sorted(nm + ".npy" for nm in names)
+    total = 0
+    for nm in names:
+        a = np.load(tmp_path / "out" / (nm + ".npy"))
+        assert a.dtype in (np.float32, np.float64), nm
+        total += a.nbytes
+    assert total < 64 << 20
+    for f in b.DUMP_RECORD_FIELDS:
+        got = np.load(tmp_path / "out" / f"records_{f}.npy")
+        assert np.array_equal(got, rec[f]) and (got.dtype == np.float32) == (rec.dtype[f].kind == "f"), f
+    assert np.array_equal(np.load(tmp_path / "out" / "timeline.npy"), np.asarray(video["timeline"]))
+    for k, v in video["summary"].items():
+        assert float(np.load(tmp_path / "out" / f"summary_{k}.npy")) == v, k
+    assert float(np.load(tmp_path / "out" / "fused_result_ai_score.npy")) == fused["result"]["ai_score"]
+    assert np.array_equal(np.load(tmp_path / "out" / "fused_timeline_binned.npy"), np.asarray(fused["timeline_binned"]))

@@ -66,18 +66,33 @@ def test_without_a_reference_checkout_only_the_hot_path_modules_exist():
     assert r.returncode != 0 and "cannot import name 'meta'" in r.stderr
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/app/analyzers"), reason="reference checkout not present")
-def test_real_reference_modules_resolve_behind_the_dropin():
-    """With the real checkout behind the package: meta / forensic import from it (stdlib only); video and audio are
-    this build's (the reference's audio.py would need soundfile, which this image lacks)."""
+def _reference_like_tree(base):
+    """A checkout shaped like the reference's, without a stub that raises: its package init imports all six analyzers
+    eagerly, its video / audio modules need cv2 / soundfile (absent here, so they only work if this build's copy wins),
+    its meta / forensic modules need nothing beyond the standard library."""
+    an = base / "app" / "analyzers"
+    an.mkdir(parents=True)
+    (base / "app" / "__init__.py").write_text("")
+    (an / "__init__.py").write_text("from . import video, audio, fusion, meta, forensic, heuristics_v2\n")
+    needs = {"video": "import cv2\n", "audio": "import soundfile\n", "meta": "import json\nimport subprocess\n",
+             "forensic": "import json\nimport subprocess\n", "fusion": "import os\n", "heuristics_v2": ""}
+    for name, imports in needs.items():
+        (an / f"{name}.py").write_text(imports + f"ORIGIN = 'reference-like'\nNAME = {name!r}\n")
+    return base
+
+
+def test_real_reference_modules_resolve_behind_the_dropin(tmp_path):
+    """With a reference-shaped checkout behind the package: meta / forensic import from it (stdlib only); video and
+    audio are this build's (the reference's need cv2 / soundfile)."""
+    ref = _reference_like_tree(tmp_path / "reference")
     code = textwrap.dedent("""
         from app.analyzers import video, fusion, heuristics_v2, meta, forensic, audio
         print(meta.__file__); print(forensic.__file__); print(video.__file__); print(audio.__file__)
     """)
-    r = _run(code, [PKG, "/root/reference"])
+    r = _run(code, [PKG, str(ref)])
     assert r.returncode == 0, r.stderr
     lines = r.stdout.strip().splitlines()
-    assert lines[0] == "/root/reference/app/analyzers/meta.py" and lines[1] == "/root/reference/app/analyzers/forensic.py"
+    assert lines[0] == str(ref / "app" / "analyzers" / "meta.py") and lines[1] == str(ref / "app" / "analyzers" / "forensic.py")
     assert lines[2].startswith(PKG)
     assert lines[3].startswith(PKG)
 

@@ -6,7 +6,7 @@ L=ai-video-detector_amd/lib
 for i in 1 2 3; do
   for v in A T; do
     cp ai-video-detector_amd/lib_ab/$v.so $L/libavd_hip.so
-    timeout -k 10 300 python bench.py --cpu-frames 0 --no-vit --no-extras --repeats 3 2>/dev/null | python -c "
+    timeout -k 10 300 python bench.py --full --cpu-frames 0 --no-vit --no-extras --repeats 3 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 e = d['extensions']['nv12_ingest']

@@ -7,7 +7,7 @@ L=ai-video-detector_amd/lib
 for i in 1 2 3; do
   for v in A B C D; do
     cp ai-video-detector_amd/lib_ab/$v.so $L/libavd_hip.so
-    timeout -k 10 200 python bench.py --cpu-frames 0 --no-extras --no-vit --no-pcie --repeats 9 2>/dev/null | python -c "
+    timeout -k 10 200 python bench.py --full --cpu-frames 0 --no-extras --no-vit --no-pcie --repeats 9 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1]); r = d['roofline']
 k = {x['name']: x['us'] for x in r['kernels']}
