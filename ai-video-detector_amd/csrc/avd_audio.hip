@@ -253,8 +253,7 @@ int launch_audio_features(avd_ctx* ctx, const float* d_wav, int64_t n, int win, 
     }
     // full windows of 8000 samples (the reference's half second at 16 kHz) take the two-step FFT path, everything else
     // (another window length, the short last window of a stream) the direct form
-    static const bool no_fft = [] { const char* e = std::getenv("AVD_AUDIO_DIRECT"); return e && std::atoi(e) != 0; }();   // A/B switch
-    const int nfull = (win == kFftN && !no_fft) ? (last == win ? nwin : nwin - 1) : 0;
+    const int nfull = win == kFftN ? (last == win ? nwin : nwin - 1) : 0;
     const size_t xw_need = (size_t)nwin * win, mag_need = (size_t)nwin * (win / 2 + 1), b_need = (size_t)nfull * kFftN * 2;
     if (ws.audio_buf_elems < xw_need + mag_need + b_need) {
         if (ws.d_audio_buf) (void)hipFree(ws.d_audio_buf);

@@ -932,15 +932,13 @@ int launch_conv(avd_ctx* ctx, const uint16_t* x, const uint16_t* w, const float*
     // workgroups per CU) where 256-pixel tiles would leave most of the chip idle (the 14 x 14 and 7 x 7 stages), and for the
     // short-K 1x1 layers, which move bytes rather than multiply: there the time goes to load / store latency, and
     // co-resident workgroups are what hides it.
-    static const int env_force = [] { const char* e = std::getenv("AVD_CNN_TILES"); return e ? std::atoi(e) : 0; }();
-    const int force = ctx->cnn_tiles ? ctx->cnn_tiles : env_force;   // avd_set_option "cnn_tiles" / AVD_CNN_TILES: 1 = always 256-pixel tiles, 2 = 128 x 128 wherever possible
+    const int force = ctx->cnn_tiles;   // avd_set_option "cnn_tiles": 1 = always 256-pixel tiles, 2 = 128 x 128 wherever possible
     const int bn_big = cout % 256 == 0 ? 256 : cout % 128 == 0 ? 128 : 64;
     const int wgs_big = ((g.m_out + 255) / 256) * (cout / bn_big);
     const bool small_ok = cout % 128 == 0;
-    // tuning knobs (A/B only): AVD_CNN_FILL = workgroups of the 256-pixel tiling, in percent of the CU count, below which the
-    // 128 x 128 tiling is taken; AVD_CNN_SHORTK = largest number of half stages that counts as "short K"
-    static const int fill_pct = [] { const char* e = std::getenv("AVD_CNN_FILL"); return e ? std::atoi(e) : 150; }();
-    static const int short_k = [] { const char* e = std::getenv("AVD_CNN_SHORTK"); return e ? std::atoi(e) : 8; }();
+    // fill_pct = workgroups of the 256-pixel tiling, in percent of the CU count, below which the 128 x 128 tiling is taken;
+    // short_k = largest number of half stages that counts as "short K"
+    constexpr int fill_pct = 150, short_k = 8;
     const bool want_small = wgs_big * 100 < ctx->num_cus * fill_pct || g.nh <= short_k;
     if (ksize == 3) {
         if (small_ok && force != 1 && (want_small || force == 2)) return go(k_conv_bf16<128, 4, 2, 0, 3>, 128, 128);

@@ -268,18 +268,11 @@ __device__ __forceinline__ void polyexp_rows320(const float* __restrict__ img, c
         if (i > 0) {                                     // row i - 1 is complete in outb[par ^ 1]: 1600 floats = 400 16-byte pieces
             f4* dst = reinterpret_cast<f4*>(out + (int64_t)(y - 1) * w * 5);
             const f4* srcv = reinterpret_cast<const f4*>(outb[par ^ 1]);
-#if !(defined(AVD_POLY_ABL) && (AVD_POLY_ABL & 8))   // timing experiment: no stores of the 320-px scale
             __builtin_nontemporal_store(srcv[x], dst + x);
             if (x < S * 5 / 4 - 320) __builtin_nontemporal_store(srcv[x + 320], dst + x + 320);
-#else
-            if (x == 0) __builtin_nontemporal_store(srcv[x], dst + x);
-#endif
         }
         const float* r0 = rowb[par][0] + x + 5; const float* r1 = rowb[par][1] + x + 5; const float* r2 = rowb[par][2] + x + 5;
         double b1 = (double)(r0[0] * g[0]), b2 = 0, b3 = (double)(r1[0] * g[0]), b4 = 0, b5 = (double)(r2[0] * g[0]), b6 = 0;
-#if defined(AVD_POLY_ABL) && (AVD_POLY_ABL & 4)      // timing experiment: no horizontal pass (results are wrong)
-        b2 = r0[1]; b4 = r1[1]; b6 = r2[1];
-#else
 #pragma unroll
         for (int q = 1; q <= 5; q++) {
             // scalar float operations on purpose: formed as two-component vectors ((r0, r1) differences, (r1, r2) sums) every pair had to
@@ -296,7 +289,6 @@ __device__ __forceinline__ void polyexp_rows320(const float* __restrict__ img, c
             b6 += (double)((r1p - r1m) * xg[q]);
             b5 += (double)((r2p + r2m) * g[q]);
         }
-#endif
         float* o = outb[par] + x * 5;
         o[0] = (float)(b3 * ig11);
         o[1] = (float)(b2 * ig11);
@@ -357,11 +349,7 @@ __global__ __launch_bounds__(320) void k_polyexp_all(PolyPtrs P, int n, const Fb
         float t0 = img[y * w + x] * g[0], t1 = 0.f, t2 = 0.f;
 #pragma unroll
         for (int q = 1; q <= 5; q++) {
-#if defined(AVD_POLY_ABL) && (AVD_POLY_ABL & 1)      // timing experiment: one load per pixel instead of eleven
-            const float a = t0 * (float)q, bb = t0 - (float)q;
-#else
             const float a = img[max(y - q, 0) * w + x], bb = img[min(y + q, h - 1) * w + x];
-#endif
             const float p = a + bb;
             t0 = t0 + g[q] * p;
             t1 = t1 + xg[q] * (bb - a);
@@ -375,27 +363,17 @@ __global__ __launch_bounds__(320) void k_polyexp_all(PolyPtrs P, int n, const Fb
     }
     __syncthreads();
     const float* r0 = r0s + x + 5; const float* r1 = r1s + x + 5; const float* r2 = r2s + x + 5;
-#if defined(AVD_POLY_ABL) && (AVD_POLY_ABL & 2)      // timing experiment: float accumulators (results differ)
-    typedef float acc_t;
-#else
-    typedef double acc_t;
-#endif
-    acc_t b1 = (acc_t)(r0[0] * g[0]), b2 = 0, b3 = (acc_t)(r1[0] * g[0]), b4 = 0,
-           b5 = (acc_t)(r2[0] * g[0]), b6 = 0;
+    double b1 = (double)(r0[0] * g[0]), b2 = 0, b3 = (double)(r1[0] * g[0]), b4 = 0,
+           b5 = (double)(r2[0] * g[0]), b6 = 0;
 #pragma unroll
     for (int q = 1; q <= 5; q++) {
-        const acc_t tg = (acc_t)(r0[q] + r0[-q]);
-#if defined(AVD_POLY_ABL) && (AVD_POLY_ABL & 2)
-        b1 += tg * (acc_t)g[q];
-        b4 += tg * (acc_t)xxg[q];
-#else
+        const double tg = (double)(r0[q] + r0[-q]);
         b1 = __builtin_fma(tg, (double)g[q], b1);          // exact products (two float values): the fma IS cv2's multiply, then add
         b4 = __builtin_fma(tg, (double)xxg[q], b4);
-#endif
-        b2 += (acc_t)((r0[q] - r0[-q]) * xg[q]);
-        b3 += (acc_t)((r1[q] + r1[-q]) * g[q]);
-        b6 += (acc_t)((r1[q] - r1[-q]) * xg[q]);
-        b5 += (acc_t)((r2[q] + r2[-q]) * g[q]);
+        b2 += (double)((r0[q] - r0[-q]) * xg[q]);
+        b3 += (double)((r1[q] + r1[-q]) * g[q]);
+        b6 += (double)((r1[q] - r1[-q]) * xg[q]);
+        b5 += (double)((r2[q] + r2[-q]) * g[q]);
     }
     float* o = outb + tid * 5;                           // (sub-row, x) order = memory order of the workgroup's rows
     o[0] = (float)(b3 * C->ig11);
@@ -1220,11 +1198,9 @@ template <int W>
 void blur_iteration(const Seg& g, int k, int np, float* flow, const int* plist)
 {
     constexpr int NSTRIP = (W + kStripW - 1) / kStripW;
-    // AVD_UV_VARIANT (A/B knob): 0 = k_uv everywhere, 1 = k_uvp (4 producers) everywhere, 2 (default) = k_uvp
-    // below 320x320 (latency / issue bound levels) and, at 320x320, k_uv for long clips (every design measured there
-    // with 119 pairs lands at ~290-300 us: HBM read/write mix; k_uvp with 2 / 3 / 4 producers 293 / 377 / 340 us)
-    // and k_uvp for clips short enough to be resident in one round
-    static const int variant = [] { const char* e = std::getenv("AVD_UV_VARIANT"); return e ? std::atoi(e) : 2; }();
+    // k_uvp<W, 4> below 320x320 (latency / issue bound levels); at 320x320 k_uv for long clips (every design measured
+    // there with 119 pairs lands at ~290-300 us: HBM read/write mix; k_uvp with 2 / 3 / 4 producers 293 / 377 / 340 us)
+    // and k_uvp<W, 4> for clips short enough to be resident in one round
     // profiling: HIP events around the two full-resolution kernels (avd_stage_ms 4 and 5)
     auto mark = [&](void) {
         if (W == S && g.prof && g.prof->kern_ev_used < 12) (void)hipEventRecord(g.prof->kern_ev[g.prof->kern_ev_used++], g.stream);
@@ -1244,7 +1220,7 @@ void blur_iteration(const Seg& g, int k, int np, float* flow, const int* plist)
         }
     }
     if (latency_shape) {
-    } else if (variant == 1 || (variant == 2 && (W < S || uvp_fits))) {
+    } else if (W < S || uvp_fits) {
         hipLaunchKernelGGL((k_uvp<W, 4>), dim3(grid), dim3(384), 0, g.stream, (const float*)g.poly[k],
                            (const float*)flow, g.vs, g.vs0, np, plist);
     } else {

@@ -317,27 +317,8 @@ __device__ __forceinline__ float ne_branch_jump(const NeIn& in, const NeG2& g)
     return fmaxf(j, fabsf(in.r0[4] - g.t1.x));
 }
 
-// 1 / d as the compiler's IEEE division sequence computes it (v_rcp_f64, two Newton steps, a correction of the quotient)
-// minus its scaling and fix-up instructions: they only act on denormal / huge / special operands, and d is a determinant
-// plus 1e-3 in [1e-3, ~1e13].  Same result as 1. / d, bit for bit, on that range (tests/test_gpu_fbfast.py compares the
-// flow of the exact kernels, which divide, against this one).
-__device__ __forceinline__ double recip_exact(double d)
-{
-#ifdef AVD_FBF_PLAIN_DIV
-    return 1. / d;
-#else
-    const double r0 = __builtin_amdgcn_rcp(d);
-    const double e0 = __builtin_fma(-d, r0, 1.);
-    const double r1 = __builtin_fma(r0, e0, r0);
-    const double e1 = __builtin_fma(-d, r1, 1.);
-    const double r2 = __builtin_fma(r1, e1, r1);
-    const double q = 1. * r2;
-    const double e2 = __builtin_fma(-d, q, 1.);
-    return __builtin_fma(e2, r2, q);
-#endif
-}
-
-// the same without the final quotient step: two Newton steps on v_rcp_f64 (relative error ~1e-16 on [1e-3, 1e13]), for the fast level kernels
+// 1 / d by two Newton steps on v_rcp_f64 (relative error ~1e-16 on [1e-3, 1e13]; the compiler's IEEE division adds a correction
+// of the quotient and fix-ups for special operands), for the fast level kernels
 __device__ __forceinline__ double recip_newton2(double d)
 {
     const double r0 = __builtin_amdgcn_rcp(d);

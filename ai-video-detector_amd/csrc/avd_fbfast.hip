@@ -32,8 +32,10 @@
 // iteration: the flow is read from one buffer and written to another (strips of a pair read each other's columns), and the
 // next iteration is the next launch.
 //
-// Bound: HBM.  Per iteration every frame's R is read once (20 B/px; pair p's R1 is pair p+1's R0 and neighbouring pairs
-// share an XCD's L2), the flow is read and written (16 B/px per pair): 441 MB at 320 px x 119 pairs.
+// Bound: VALU issue and the texture addresser together (round-5 counters: VALU issue ~0.54, TA busy ~0.53 of the launch), at
+// ~0.4 of the HBM peak (profiles/r05_pmc.json).  Per iteration every frame's R is read once (20 B/px;
+// pair p's R1 is pair p+1's R0 and neighbouring pairs share an XCD's L2), the flow is read and written (16 B/px per pair):
+// 441 MB at 320 px x 119 pairs.
 #include <cstdio>
 #include <cstdlib>
 #include <type_traits>
@@ -47,12 +49,6 @@ namespace {
 constexpr int kM = 7;                 // (winsize - 1) / 2
 
 typedef double dbl2 __attribute__((ext_vector_type(2)));
-
-#ifdef AVD_FBF_NO_SCALAR_ROW       // A/B builds (tools/r05_ab_solve.sh)
-constexpr bool kScalarRow = false;
-#else
-constexpr bool kScalarRow = true;
-#endif
 
 // W level size; NB 64-column blocks per strip; GD lead of the bilinear gather; NPB normal-equation waves per block (2: two
 // entries each per step, 4: one each); XPB solver waves per block (1: four columns per lane, 2: two columns per lane).
@@ -156,7 +152,7 @@ __device__ __forceinline__ bool role_ne(const float* __restrict__ R, const float
     auto flow_of = [&](int row, NeIn& s) { const float* f = fring + (row & 15) * Ge::F_SLOT + lane; s.dx = f[0]; s.dy = f[64]; };
     auto load_in = [&](int row, NeIn& s) {
         if (UP) ne_load_r0(R, r0base, x, row, W, s);
-        else ne_load<Ge::PN && kScalarRow>(R, flow, r0base, flbase, x, row, W, plane, s);
+        else ne_load<Ge::PN>(R, flow, r0base, flbase, x, row, W, plane, s);
     };
     bool first = skip != nullptr;                          // the first barrier of this role has not been passed yet
     if (UP) {
@@ -179,12 +175,8 @@ __device__ __forceinline__ bool role_ne(const float* __restrict__ R, const float
             const int e = ent(i);
             // refills first: the gather GD entries ahead goes into the slot the previous entry released, the inputs
             // NIS - 1 entries ahead into the slot of the entry before this one (rows beyond the image clamp to the last)
-#ifndef AVD_FBF_NOGATHER          // timing-only ablation builds (results are wrong)
             gather(in[(ii + GD) % NIS], row_of(ent(i + GD)), g[(ii + GD) % NGS]);
-#endif
-#ifndef AVD_FBF_NOINLOAD
             load_in(row_of(ent(i + NIS - 1)), in[(ii + NIS - 1) % NIS]);
-#endif
             if (UP) flow_of(row_of(ent(i + GD + 1)), in[(ii + GD + 1) % NIS]);   // for the gather issued with the next entry
             __builtin_amdgcn_sched_barrier(0);
             float a[5];                                                      // r2 .. r6: the chain wave attenuates and multiplies (PN: done here)
@@ -389,7 +381,6 @@ __device__ __forceinline__ bool role_solve(const double* __restrict__ vsring, fl
     const long long fbf_t0 = __builtin_amdgcn_s_memtime();
 #endif
     constexpr int W = Ge::W, H = W, plane = W * H, CPL = Ge::CPL, NV = 14 + CPL;
-    [[maybe_unused]] const double scale = 1. / (15 * 15);
     const int r = lane >> 4, j = 16 * (Ge::XPB * b + xi) + (lane & 15);      // chunk of CPL columns: output columns CPL j ..
     const bool colok = CPL * j < ow;
     float* fl = flow_out + (size_t)p * 2 * plane + o0 + CPL * j;
@@ -408,11 +399,7 @@ __device__ __forceinline__ bool role_solve(const double* __restrict__ vsring, fl
             fb_barrier();
             if (first) { first = false; if (*skip) return true; }
             const int y = 4 * t - 15 + r;
-#ifdef AVD_FBF_NOSOLVE
-            if (false) {
-#else
             if (t >= 2 && colok && y >= 0 && y < H) {
-#endif
                 const dbl2* s = reinterpret_cast<const dbl2*>(vsrc + (y & 7) * Ge::VS_SLOT);
                 double o[5][CPL];
 #pragma unroll
@@ -427,20 +414,12 @@ __device__ __forceinline__ bool role_solve(const double* __restrict__ vsring, fl
                         double A = v[3];
 #pragma unroll
                         for (int i = 4; i < 15; i++) A += v[i];
-#ifdef AVD_FBF_SOLVE_R4
-                        const double p12 = v[1] + v[2], q2 = v[15] + v[16];
-                        o[c][0] = A + (v[0] + p12);
-                        o[c][1] = A + (p12 + v[15]);
-                        o[c][2] = A + (v[2] + q2);
-                        o[c][CPL - 1] = A + (q2 + v[NV - 1]);
-#else
                         // four windows of fifteen from eighteen values in 19 additions: the twelve they share, then the two pairs next to them
                         const double Bl = A + (v[1] + v[2]), Br = A + (v[15] + v[16]);
                         o[c][0] = Bl + v[0];
                         o[c][1] = Bl + v[15];
                         o[c][2] = Br + v[2];
                         o[c][CPL - 1] = Br + v[NV - 1];
-#endif
                     } else {
                         double A = v[1];
 #pragma unroll
@@ -452,15 +431,6 @@ __device__ __forceinline__ bool role_solve(const double* __restrict__ vsring, fl
                 float fx[CPL], fy[CPL];
 #pragma unroll
                 for (int i = 0; i < CPL; i++) {
-#ifdef AVD_FBF_SOLVE_R4
-                    const double g11 = o[0][i] * scale, g12 = o[1][i] * scale, g22 = o[2][i] * scale;
-                    const double h1 = o[3][i] * scale, h2 = o[4][i] * scale;
-                    const double t1 = g11 * g22, t2 = g12 * g12, den = t1 - t2 + 1e-3;      // cv2's determinant, its operation order
-                    const double idet = recip_exact(den);
-                    fx[i] = (float)((g11 * h2 - g12 * h1) * idet);
-                    fy[i] = (float)((g22 * h1 - g12 * h2) * idet);
-                    ill |= !(t1 + t2 <= kCondMax * den) | !(fmaxf(fabsf(fx[i]), fabsf(fy[i])) <= kFlowMax * (float)W);
-#else
                     // cv2 scales the five sums by 1 / 225 and adds 1e-3 to the determinant; the scale cancels in the quotient, so the sums stay as
                     // they are and the 1e-3 becomes 1e-3 * 225^2 (round 5: 14 double operations per column instead of 28; this mode's flow is held
                     // to a tolerance, not to cv2's rounding -- the exact kernels keep cv2's order).  The criterion t1 + t2 <= kCondMax den with
@@ -472,7 +442,6 @@ __device__ __forceinline__ bool role_solve(const double* __restrict__ vsring, fl
                     fx[i] = (float)(__builtin_fma(a, h2, -(b * h1)) * idet);
                     fy[i] = (float)(__builtin_fma(d, h1, -(b * h2)) * idet);
                     ill |= !(t2 <= __builtin_fma(0.5 * (kCondMax - 1.), den, 0.5 * kC)) | !(fmaxf(fabsf(fx[i]), fabsf(fy[i])) <= kFlowMax * (float)W);
-#endif
                 }
                 // last iteration of the 320-px level: |flow| as np.sqrt(fx * fx + fy * fy) forms it in float32 (video.py:46), for the
                 // statistics kernels -- they then read 4 bytes per pixel twice instead of 8, and the flow only once, here
@@ -521,7 +490,7 @@ __device__ __forceinline__ void phase_sync()
 template <typename Ge, bool UP, int IT = 1, bool PRO = false>
 __global__ __launch_bounds__((64 * Ge::NWAVES)) void k_fb_fast(const float* __restrict__ R, const float* flow_in, float* flow_out, float* flow_tmp,
                                                               float* __restrict__ mag_out, int* __restrict__ flags, const int* __restrict__ pairdiff,
-                                                              int npairs, int nstrips, int ow, int zero_first, int dbg)
+                                                              int npairs, int nstrips, int ow, int zero_first)
 {
     constexpr int W = Ge::W, NB = Ge::NB;
     static_assert(IT == 1 || IT == 3, "one iteration per launch, or all three");
@@ -593,7 +562,7 @@ __global__ __launch_bounds__((64 * Ge::NWAVES)) void k_fb_fast(const float* __re
             else if (role_ne<Ge, UP, false>(R, fin, mring, fring, p, x, role, lane, flags, chk, sk)) return;
         }
     } else if (role == Ge::NPB) {
-        if (!(dbg & 4)) __builtin_amdgcn_s_setprio(3);    // the only sequential part: take the issue slot whenever ready
+        __builtin_amdgcn_s_setprio(3);    // the only sequential part: take the issue slot whenever ready
 #pragma unroll 1
         for (int it = 0; it < IT; it++) {
             if (it > 0) phase_sync();
@@ -617,23 +586,22 @@ void launch_fast(hipStream_t stream, const float* R, const float* fin, float* fo
                  int nstrips, int ow, int zero_first, int mode)
 {
     const int grid = 8 * ((np + 7) / 8) * nstrips;
-    static const int dbg = [] { const char* e = std::getenv("AVD_FBF_DBG"); return e ? std::atoi(e) : 0; }();   // tuning experiments
     const dim3 g(grid), t(64 * Ge::NWAVES);
     // the chain wave's resize only exists where it pays: at 320 px it costs the launch 3.5 us and saves k_flow_up's 37; the small
     // levels are latency-bound on exactly the chain wave that would do it (160 px: 45 -> 84 us per launch against 12 saved)
     if constexpr (Ge::W == 320) {
-        if (mode == 1) { hipLaunchKernelGGL((k_fb_fast<Ge, true>), g, t, 0, stream, R, fin, fout, ftmp, mag, flags, pairdiff, np, nstrips, ow, 0, dbg); return; }
+        if (mode == 1) { hipLaunchKernelGGL((k_fb_fast<Ge, true>), g, t, 0, stream, R, fin, fout, ftmp, mag, flags, pairdiff, np, nstrips, ow, 0); return; }
     }
     if constexpr (Ge::W == 160 || Ge::W == 80) {
-        if (mode == 2) { hipLaunchKernelGGL((k_fb_fast<Ge, false, 1, true>), g, t, 0, stream, R, fin, fout, ftmp, mag, flags, pairdiff, np, nstrips, ow, 0, dbg); return; }
+        if (mode == 2) { hipLaunchKernelGGL((k_fb_fast<Ge, false, 1, true>), g, t, 0, stream, R, fin, fout, ftmp, mag, flags, pairdiff, np, nstrips, ow, 0); return; }
     }
     if constexpr (Ge::W == 80) {
-        if (mode == 4) { hipLaunchKernelGGL((k_fb_fast<Ge, false, 3, true>), g, t, 0, stream, R, fin, fout, ftmp, mag, flags, pairdiff, np, nstrips, ow, 0, dbg); return; }
+        if (mode == 4) { hipLaunchKernelGGL((k_fb_fast<Ge, false, 3, true>), g, t, 0, stream, R, fin, fout, ftmp, mag, flags, pairdiff, np, nstrips, ow, 0); return; }
     }
     if constexpr (Ge::W == 80 || Ge::W == 40) {
-        if (mode == 3) { hipLaunchKernelGGL((k_fb_fast<Ge, false, 3, false>), g, t, 0, stream, R, fin, fout, ftmp, mag, flags, pairdiff, np, nstrips, ow, zero_first, dbg); return; }
+        if (mode == 3) { hipLaunchKernelGGL((k_fb_fast<Ge, false, 3, false>), g, t, 0, stream, R, fin, fout, ftmp, mag, flags, pairdiff, np, nstrips, ow, zero_first); return; }
     }
-    hipLaunchKernelGGL((k_fb_fast<Ge, false>), g, t, 0, stream, R, fin, fout, ftmp, mag, flags, pairdiff, np, nstrips, ow, zero_first, dbg);
+    hipLaunchKernelGGL((k_fb_fast<Ge, false>), g, t, 0, stream, R, fin, fout, ftmp, mag, flags, pairdiff, np, nstrips, ow, zero_first);
 }
 
 }  // namespace

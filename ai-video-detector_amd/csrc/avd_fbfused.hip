@@ -94,7 +94,7 @@ __device__ __forceinline__ unsigned next_buf(unsigned off, unsigned group, unsig
 // ------------------------------------------------------------------------------------------------------------------
 template <int W, int K, int G>
 __device__ __forceinline__ void role_vertical(const float* __restrict__ R, const float* __restrict__ flow,
-                                              double* __restrict__ buf, int p, int vw, int lane, int dbg, long long& fb_wait, int& fb_nbar,
+                                              double* __restrict__ buf, int p, int vw, int lane, long long& fb_wait, int& fb_nbar,
                                               bool zf)
 {
     using Ge = Geo<W, K, G>;
@@ -122,8 +122,8 @@ __device__ __forceinline__ void role_vertical(const float* __restrict__ R, const
         // the other one) and the inputs three entries ahead into the slot of entry e - 1, so nothing this entry still
         // needs is overwritten -- and the gather gets a whole row of lead instead of the tail of one (issued after the
         // arithmetic it had ~300 cycles before its use at the top of the next step: less than an L2 round trip).
-        if (refill_g && !(dbg & 4)) ne_gather2(R, r1base, in[(kk + 1) & 3], x, row_of(e + 1), W, H, g[(kk + 1) & 1], zf);
-        if (refill_in && !(dbg & 4)) ne_load(R, flow, r0base, flbase, x, row_of(e + 3), W, plane, in[(kk + 3) & 3]);
+        if (refill_g) ne_gather2(R, r1base, in[(kk + 1) & 3], x, row_of(e + 1), W, H, g[(kk + 1) & 1], zf);
+        if (refill_in) ne_load(R, flow, r0base, flbase, x, row_of(e + 3), W, plane, in[(kk + 3) & 3]);
         __builtin_amdgcn_sched_barrier(0);
         float a[5];
         ne_finish2(in[kk & 3], g[kk & 1], x, row_of(e), W, H, sx, border_factor(row_of(e), H), a, zf);
@@ -269,10 +269,10 @@ __device__ __forceinline__ void scan_segment(double* __restrict__ q, double* __r
 }
 
 template <int W, int K, int G>
-__device__ __forceinline__ void role_scan(double* __restrict__ buf, double* __restrict__ hand, int lane, int dbg, long long& fb_wait, int& fb_nbar)
+__device__ __forceinline__ void role_scan(double* __restrict__ buf, double* __restrict__ hand, int lane, long long& fb_wait, int& fb_nbar)
 {
     using Ge = Geo<W, K, G>;
-    const bool on = lane < Ge::SLANES && !(dbg & 1);
+    const bool on = lane < Ge::SLANES;
     const int seg = on ? lane / Ge::LINES : 0, line = on ? lane - seg * Ge::LINES : 0;
     // after barrier j segment k works on group j - k, which lives in buffer (j - k) mod NBUF
     int grp = -seg;
@@ -296,7 +296,7 @@ __device__ __forceinline__ void role_scan(double* __restrict__ buf, double* __re
 // ------------------------------------------------------------------------------------------------------------------
 template <int W, int K, int G>
 __device__ __forceinline__ void role_solve(const float* __restrict__ R, const double* __restrict__ buf,
-                                           float* __restrict__ flow, int p, int xi, int lane, int dbg, long long& fb_wait, int& fb_nbar)
+                                           float* __restrict__ flow, int p, int xi, int lane, long long& fb_wait, int& fb_nbar)
 {
     using Ge = Geo<W, K, G>;
     constexpr int H = W;
@@ -325,7 +325,7 @@ __device__ __forceinline__ void role_solve(const float* __restrict__ R, const do
         // V is filling group j + 1 now; rows [y0, y0 + G) enter its box filter PF_ROWS rows later.  Plain loads on purpose:
         // as non-temporal loads (no L1 allocation, streaming hint) the level kernel took 0.95 instead of 0.87 ms
         const int y0 = G * (j + 1) + kM + PF_ROWS;
-        if (y0 >= H || (dbg & 8)) return;
+        if (y0 >= H) return;
         const int rows = y0 + G <= H ? G : H - y0;
         const unsigned rbytes = (unsigned)rows * W * 20u, fbytes = (unsigned)rows * W * 4u;
         const unsigned rbeg = (unsigned)y0 * W * 20u, fbeg = (unsigned)y0 * W * 4u;
@@ -349,7 +349,7 @@ __device__ __forceinline__ void role_solve(const float* __restrict__ R, const do
         if (g >= 0) {
 #pragma unroll
             for (int item = 0; item < G * Ge::NVW; item++) {
-                if ((item & 1) != xi || (dbg & 2)) continue;
+                if ((item & 1) != xi) continue;
                 const int r = item / Ge::NVW, b = item % Ge::NVW;
                 const int x = b * 64 + lane;
                 if (x < W) {
@@ -386,7 +386,7 @@ __device__ __forceinline__ void role_solve(const float* __restrict__ R, const do
 // re-run kernel below is launched with the widest level's wave count) only keep the barrier count.
 template <int W, int K, int G>
 __device__ __forceinline__ void level_body(const float* __restrict__ R, float* __restrict__ flow, double* __restrict__ lds, int p, int iterations,
-                                           int dbg, int zero_first, int lane, int wave)
+                                           int zero_first, int lane, int wave)
 {
     using Ge = Geo<W, K, G>;
     double* buf = lds;
@@ -415,15 +415,15 @@ __device__ __forceinline__ void level_body(const float* __restrict__ R, float* _
         for (int it = 0; it < iterations; it++) {
             // flow rows cached in this CU's L1 during the previous iteration are stale now
             if (it > 0) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            role_vertical<W, K, G>(R, flow, buf, p, ridx, lane, dbg, fb_wait, fb_nbar, zero_first && it == 0);
+            role_vertical<W, K, G>(R, flow, buf, p, ridx, lane, fb_wait, fb_nbar, zero_first && it == 0);
         }
         if (wave >= 4) __builtin_amdgcn_s_setprio(0);
     } else if (wave == smap) {
         __builtin_amdgcn_s_setprio(3);                    // its operands are rarely ready: take the slot when they are
-        for (int it = 0; it < iterations; it++) role_scan<W, K, G>(buf, hand, lane, dbg, fb_wait, fb_nbar);
+        for (int it = 0; it < iterations; it++) role_scan<W, K, G>(buf, hand, lane, fb_wait, fb_nbar);
         __builtin_amdgcn_s_setprio(0);
     } else {
-        for (int it = 0; it < iterations; it++) role_solve<W, K, G>(R, buf, flow, p, ridx - Ge::NVW, lane, dbg, fb_wait, fb_nbar);
+        for (int it = 0; it < iterations; it++) role_solve<W, K, G>(R, buf, flow, p, ridx - Ge::NVW, lane, fb_wait, fb_nbar);
     }
 #ifdef AVD_FB_DEBUG
     if (W == 320 && p == 0 && lane == 0) {
@@ -436,13 +436,8 @@ __device__ __forceinline__ void level_body(const float* __restrict__ R, float* _
 
 template <int W, int K, int G>
 __global__ __launch_bounds__((64 * Geo<W, K, G>::NWAVES)) void k_fb_level(const float* __restrict__ R, float* __restrict__ flow,
-                                                                        int npairs, int iterations, int dbg_arg, int zero_first, const int* __restrict__ plist)
+                                                                        int npairs, int iterations, int zero_first, const int* __restrict__ plist)
 {
-#ifdef AVD_FB_DEBUG
-    const int dbg = dbg_arg;                              // timing experiments (AVD_FB_DBG), see launch_fb_level
-#else
-    constexpr int dbg = 0;
-#endif
     using Ge = Geo<W, K, G>;
     __shared__ __align__(16) double lds[Ge::LDS_DOUBLES];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -452,13 +447,13 @@ __global__ __launch_bounds__((64 * Geo<W, K, G>::NWAVES)) void k_fb_level(const 
     const int pi = (blockIdx.x & 7) * ppx + (blockIdx.x >> 3);
     if (pi >= npairs) return;                             // whole workgroup
     const int p = plist ? plist[pi] : pi;                 // (exact re-run of the flagged pairs of the fast mode: a compacted list)
-    level_body<W, K, G>(R, flow, lds, p, iterations, dbg, zero_first, lane, wave);
+    level_body<W, K, G>(R, flow, lds, p, iterations, zero_first, lane, wave);
 }
 
 template <int W, int K, int G>
-void launch_one(hipStream_t stream, int grid, const float* R, float* flow, int np, int iterations, int dbg, int zero_first, const int* plist)
+void launch_one(hipStream_t stream, int grid, const float* R, float* flow, int np, int iterations, int zero_first, const int* plist)
 {
-    hipLaunchKernelGGL((k_fb_level<W, K, G>), dim3(grid), dim3(64 * Geo<W, K, G>::NWAVES), 0, stream, R, flow, np, iterations, dbg, zero_first, plist);
+    hipLaunchKernelGGL((k_fb_level<W, K, G>), dim3(grid), dim3(64 * Geo<W, K, G>::NWAVES), 0, stream, R, flow, np, iterations, zero_first, plist);
 }
 
 }  // namespace
@@ -469,17 +464,11 @@ int launch_fb_level(avd_ctx* ctx, hipStream_t stream, int w, const float* R, flo
 {
     if (np <= 0) return 0;
     const int grid = 8 * ((np + 7) / 8);
-    // timing experiments only (results are wrong when set): 1 no scan, 2 no solve / stores, 4 no refill loads, 8 no touch loads
-    static const int dbg = [] { const char* e = std::getenv("AVD_FB_DBG"); return e ? std::atoi(e) : 0; }();
-    static const int var = [] { const char* e = std::getenv("AVD_FB_VARIANT"); return e ? std::atoi(e) : 0; }();
     switch (w) {
-    case 320:
-        if (var == 1) launch_one<320, 2, 2>(stream, grid, R, flow, np, iterations, dbg, zero_first, plist);      // A/B: two segments (slower)
-        else launch_one<320, 4, 2>(stream, grid, R, flow, np, iterations, dbg, zero_first, plist);
-        break;
-    case 160: launch_one<160, 2, 4>(stream, grid, R, flow, np, iterations, dbg, zero_first, plist); break;
-    case 80: launch_one<80, 1, 4>(stream, grid, R, flow, np, iterations, dbg, zero_first, plist); break;
-    case 40: launch_one<40, 1, 4>(stream, grid, R, flow, np, iterations, dbg, zero_first, plist); break;
+    case 320: launch_one<320, 4, 2>(stream, grid, R, flow, np, iterations, zero_first, plist); break;
+    case 160: launch_one<160, 2, 4>(stream, grid, R, flow, np, iterations, zero_first, plist); break;
+    case 80: launch_one<80, 1, 4>(stream, grid, R, flow, np, iterations, zero_first, plist); break;
+    case 40: launch_one<40, 1, 4>(stream, grid, R, flow, np, iterations, zero_first, plist); break;
     default: ctx->err = "launch_fb_level: unsupported level size"; return AVD_ERR_ARG;
     }
     HIP_TRY(ctx, hipGetLastError());

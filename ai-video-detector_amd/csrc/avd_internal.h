@@ -75,7 +75,6 @@ struct PreParams {
     int area_x_uniform4;               // every x cell: begin%4==0, count%4==0, single weight
     int h, w, rows_per_band, nbands, pitch;
     int64_t row_stride, frame_stride;
-    int dbg_skip;                      // timing experiments only (AVD_DBG_SKIP): 1 lap, 2 area, 4 linear, 8 gray math, 16 loads
 };
 
 struct HashParams {

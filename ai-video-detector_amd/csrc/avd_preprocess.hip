@@ -157,7 +157,7 @@ __device__ __forceinline__ Moments band_phases(const uint8_t* tile, const LdsTab
     // accumulate in place; the <= 4 boundary rows use a multiply-add per product.  What the
     // column shifts miss at x = 0 / w-1 is added per band row as exact scalar edge terms.
     long long s_acc = 0, q_acc = 0;
-    if (!(P.dbg_skip & 1)) {
+    {
         const int quads = (w + 3) >> 2;
         const int trows = rows + 2;
         const unsigned ones = 0x01010101u;
@@ -281,7 +281,7 @@ __device__ __forceinline__ Moments band_phases(const uint8_t* tile, const LdsTab
     // ---- INTER_AREA horizontal partials, one float chain per (row, cell), cv2's order ----
     // The chain of a cell is sequential by definition (float adds in cv2's order); a lane runs the
     // chains of two different rows interleaved so that dependent adds of one hide behind the other.
-    if (!(P.dbg_skip & 2)) {
+    {
         float* out = rowbuf + ((int64_t)f * h + r0) * AVD_HASH;
         const int dx = tid & 31;
         const int xb = LTAB ? lt->ax_begin[dx] : P.ax_begin[dx];
@@ -331,7 +331,7 @@ __device__ __forceinline__ Moments band_phases(const uint8_t* tile, const LdsTab
     }
 
     // ---- INTER_LINEAR 320x320 rows whose upper source row lies in this band ----------------
-    if (!(P.dbg_skip & 4)) {
+    {
         const int d0 = P.band_dy[band], d1 = P.band_dy[band + 1];        // wave-uniform scalar loads
         uint8_t* dst = small + (int64_t)f * AVD_NPIX;
         // a lane owns output COLUMNS (its x taps are unpacked once); the rows of the band are walked with
@@ -444,15 +444,13 @@ __global__ __launch_bounds__(NT, 4) void k_preprocess_vec(const uint8_t* __restr
             const int t = min(rsub + k * rpp, trows - 1);  // surplus items re-read the last row (same bytes)
             const int y = reflect_once(r0 - 1 + t, h);
             const uint4* src = reinterpret_cast<const uint4*>(col + (int64_t)y * P.row_stride);
-            if (P.dbg_skip & 16) { q[k][0] = q[k][1] = q[k][2] = make_uint4(t, y, k, c); continue; }
             q[k][0] = src[0]; q[k][1] = src[1]; q[k][2] = src[2];
         }
         uint8_t* dst = tile + kPad + c * 16;
 #pragma unroll
         for (int k = 0; k < NI; k++) {
             const int t = min(rsub + k * rpp, trows - 1);
-            const uint4 g = (P.dbg_skip & 8) ? make_uint4(q[k][0].x ^ q[k][1].y, q[k][0].y ^ q[k][2].x, q[k][1].z ^ q[k][2].w, q[k][0].w ^ q[k][1].x ^ q[k][2].z)
-                                             : gray16(q[k][0], q[k][1], q[k][2]);
+            const uint4 g = gray16(q[k][0], q[k][1], q[k][2]);
             uint8_t* d = dst + t * pitch;
             *reinterpret_cast<uint4*>(d) = g;
             if (c == 0) d[-1] = (uint8_t)(g.x >> 8);                 // pixel -1 := pixel 1
@@ -544,7 +542,6 @@ __global__ __launch_bounds__(kThreads) void k_preprocess_nv12(const uint8_t* __r
     const uint8_t* cfr = nv.uv + (int64_t)f * nv.uv_frame_stride;
     const int trows = rows + 2;                            // tile row 0 = image row r0-1
     if (VEC) {
-#ifndef AVD_NV12_ARITH
         // libswscale's converter IS a table lookup: B = T[Y + ob(U)], G = T[Y + og(U, V)], R = T[Y + or(V)] with one clip table T(i) = clip8((c0 + i cy) >> 16).
         // Round 5: three LDS tables of cv2's gray weight times T (3735 T, 19235 T + the rounding 2^14, 9798 T; 32-bit entries, index bias kNvBias), so a pixel is
         // three index additions, three ds_read_b32, one three-operand add and a shift -- instead of three multiply-adds, three shifts, three clamps and
@@ -557,7 +554,6 @@ __global__ __launch_bounds__(kThreads) void k_preprocess_nv12(const uint8_t* __r
             tabB[i] = v * 3735u; tabG[i] = v * 19235u + (1u << 14); tabR[i] = v * 9798u;
         }
         __syncthreads();
-#endif
         // one work item = one chroma row x one 16-pixel chunk: the eight chroma-term triples are formed once and serve the
         // two luma rows that share them (they are 8.5 of the ~27 integer operations a pixel costs otherwise)
         const int ylo = r0 - 1, yhi = r0 + rows;              // image rows of tile rows 0 and trows - 1, before reflection
@@ -571,13 +567,8 @@ __global__ __launch_bounds__(kThreads) void k_preprocess_nv12(const uint8_t* __r
             ChromaTerms t[8];
 #pragma unroll
             for (int j = 0; j < 4; j++) {
-#ifndef AVD_NV12_ARITH
                 t[2 * j] = chroma_offsets(cw[j] & 0xFF, (cw[j] >> 8) & 0xFF, nv.k);
                 t[2 * j + 1] = chroma_offsets((cw[j] >> 16) & 0xFF, cw[j] >> 24, nv.k);
-#else
-                t[2 * j] = chroma_terms(cw[j] & 0xFF, (cw[j] >> 8) & 0xFF, nv.k);
-                t[2 * j + 1] = chroma_terms((cw[j] >> 16) & 0xFF, cw[j] >> 24, nv.k);
-#endif
             }
 #pragma unroll
             for (int s2 = 0; s2 < 2; s2++) {
@@ -588,15 +579,8 @@ __global__ __launch_bounds__(kThreads) void k_preprocess_nv12(const uint8_t* __r
                 unsigned g[4];
 #pragma unroll
                 for (int j = 0; j < 4; j++)
-#ifdef AVD_NV12_NOCONV      // timing experiment: no conversion arithmetic (results are wrong)
-                    g[j] = yw[j] ^ cw[j];
-#elif !defined(AVD_NV12_ARITH)
                     g[j] = gray_from_tables(yw[j] & 0xFF, t[2 * j], tabB, tabG, tabR) | (gray_from_tables((yw[j] >> 8) & 0xFF, t[2 * j], tabB, tabG, tabR) << 8) |
                            (gray_from_tables((yw[j] >> 16) & 0xFF, t[2 * j + 1], tabB, tabG, tabR) << 16) | (gray_from_tables(yw[j] >> 24, t[2 * j + 1], tabB, tabG, tabR) << 24);
-#else
-                    g[j] = gray_from_yuv(yw[j] & 0xFF, t[2 * j], nv.k.cy) | (gray_from_yuv((yw[j] >> 8) & 0xFF, t[2 * j], nv.k.cy) << 8) |
-                           (gray_from_yuv((yw[j] >> 16) & 0xFF, t[2 * j + 1], nv.k.cy) << 16) | (gray_from_yuv(yw[j] >> 24, t[2 * j + 1], nv.k.cy) << 24);
-#endif
                 *reinterpret_cast<uint4*>(tile + (y - ylo) * pitch + kPad + c * 16) = make_uint4(g[0], g[1], g[2], g[3]);
             }
         }
@@ -733,11 +717,6 @@ int launch_preprocess(avd_ctx* ctx, const uint8_t* d_bgr, int n, int h, int w,
     PreParams P = ws.pre;
     P.row_stride = row_stride;
     P.frame_stride = frame_stride;
-#ifdef AVD_TIMING_EXPERIMENTS      // make EXTRA=-DAVD_TIMING_EXPERIMENTS: phase ablation (results are WRONG with a non-zero mask)
-    { const char* e = std::getenv("AVD_DBG_SKIP"); P.dbg_skip = e ? std::atoi(e) : 0; }
-#else
-    P.dbg_skip = 0;
-#endif
     const int total = n * P.nbands;
     const bool vec = (w % 16 == 0) && (row_stride % 16 == 0) && (frame_stride % 16 == 0) &&
                      (reinterpret_cast<uintptr_t>(d_bgr) % 16 == 0);
@@ -745,21 +724,12 @@ int launch_preprocess(avd_ctx* ctx, const uint8_t* d_bgr, int n, int h, int w,
     const size_t lds1 = (size_t)(P.rows_per_band + 2) * P.pitch;
     const size_t lds_vec = lds1 + sizeof(LdsTabs);
     const int grid1 = ((total + 7) / 8) * 8;
-    static const int nt_pref = [] { const char* e = std::getenv("AVD_PRE_NT"); return e ? std::atoi(e) : 256; }();
-    const int nt = (nt_pref == 512 && chunks <= 512) ? 512 : 256;
-    const int ni_nt = (vec && chunks <= nt) ? (P.rows_per_band + 2 + nt / chunks - 1) / (nt / chunks) : 0;
+    const int ni_nt = (vec && chunks <= kThreads) ? (P.rows_per_band + 2 + kThreads / chunks - 1) / (kThreads / chunks) : 0;
     ws.lap_waves = kThreads / 64;
     if (ni_nt > 0 && ni_nt <= 9) {
-        ws.lap_waves = nt / 64;
-#define AVD_VEC_CASE(N)                                                                                              \
-    do {                                                                                                             \
-        if (nt == 512)                                                                                               \
-            hipLaunchKernelGGL((k_preprocess_vec<N, 512>), dim3(grid1), dim3(512), lds_vec, ctx->stream, d_bgr, n, P, \
-                               ws.d_small + (size_t)ws.f0 * AVD_NPIX, ws.d_rowbuf + ws.rowbuf_off, ws.d_lap_part + ws.lappart_off);                                              \
-        else                                                                                                         \
-            hipLaunchKernelGGL((k_preprocess_vec<N, 256>), dim3(grid1), dim3(256), lds_vec, ctx->stream, d_bgr, n, P, \
-                               ws.d_small + (size_t)ws.f0 * AVD_NPIX, ws.d_rowbuf + ws.rowbuf_off, ws.d_lap_part + ws.lappart_off);                                              \
-    } while (0)
+#define AVD_VEC_CASE(N)                                                                                                     \
+    hipLaunchKernelGGL((k_preprocess_vec<N, kThreads>), dim3(grid1), dim3(kThreads), lds_vec, ctx->stream, d_bgr, n, P,   \
+                       ws.d_small + (size_t)ws.f0 * AVD_NPIX, ws.d_rowbuf + ws.rowbuf_off, ws.d_lap_part + ws.lappart_off)
         switch (ni_nt) {
         case 1: case 2: case 3: AVD_VEC_CASE(3); break;
         case 4: AVD_VEC_CASE(4); break;
@@ -791,16 +761,13 @@ int launch_preprocess_nv12(avd_ctx* ctx, const uint8_t* d_y, const Nv12Params& n
     PreParams P = ws.pre;
     P.row_stride = row_stride;
     P.frame_stride = frame_stride;
-    P.dbg_skip = 0;
     const int total = n * P.nbands;
     const bool vec = (w % 16 == 0) && (row_stride % 16 == 0) && (frame_stride % 16 == 0) && (nv.uv_row_stride % 16 == 0) &&
                      (nv.uv_frame_stride % 16 == 0) && (reinterpret_cast<uintptr_t>(d_y) % 16 == 0) &&
                      (reinterpret_cast<uintptr_t>(nv.uv) % 16 == 0);
     const int grid = ((total + 7) / 8) * 8;
     size_t lds = (size_t)(P.rows_per_band + 2) * P.pitch;
-#ifndef AVD_NV12_ARITH
     if (vec) lds = (lds + 15) / 16 * 16 + 3 * sizeof(unsigned) * 704;     // the three conversion tables behind the tile (k_preprocess_nv12, kNvTab)
-#endif
     // (a register-staged variant in the style of k_preprocess_vec measured no faster: the kernel is bound by the
     // conversion's integer arithmetic, not by how its loads are issued -- profiles/r02_experiments.md)
     ws.lap_waves = kThreads / 64;

@@ -136,7 +136,7 @@ __device__ __forceinline__ void stage_offsets(unsigned (&voff)[(R + 15) / 16], i
 
 #define AVD_WAIT_VM(n) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(n) : "memory")
 
-template <int K, int OUT_BF16, class T, int DBG = 0>
+template <int K, int OUT_BF16, class T>
 __global__ __launch_bounds__(64 * T::NWAVES) void k_gemm_bf16_nt_persistent(const uint16_t* __restrict__ A, const uint16_t* __restrict__ Bt,
                                                                 const float* __restrict__ bias, void* __restrict__ Cv, int M, int N_)
 {
@@ -167,7 +167,6 @@ __global__ __launch_bounds__(64 * T::NWAVES) void k_gemm_bf16_nt_persistent(cons
     stage_offsets<T::RA>(voa, K, wave, lane);
     stage_offsets<T::RB>(vob, K, wave, lane);
     auto issue = [&](int m0, int n0, int hs, int slot) __attribute__((always_inline)) {
-        if (DBG & 1) return;                                 // timing experiment: no global -> LDS traffic
         char* st = lds + slot * T::STAGE;
         stage_rows<T::RA>(reinterpret_cast<const char*>(A + ((int64_t)(m0 >> 4) * (K >> 5) + hs) * 512), voa, st, wave, lane);
         stage_rows<T::RB>(reinterpret_cast<const char*>(Bt + ((int64_t)(n0 >> 4) * (K >> 5) + hs) * 512), vob, st + T::HALF_A, wave, lane);
@@ -195,8 +194,7 @@ __global__ __launch_bounds__(64 * T::NWAVES) void k_gemm_bf16_nt_persistent(cons
                 const f32x4 lo = acc[i][2 * jp] + *reinterpret_cast<const f32x4*>(lb);
                 const f32x4 hi = acc[i][2 * jp + 1] + *reinterpret_cast<const f32x4*>(lb + 4);
                 char* piece = static_cast<char*>(Cv) + ((int64_t)row0 * N + col0) * ESZ;   // scalar base, 32-bit lane offset
-                // DBG 16 (timing experiment): the stores stay in the program, so the MFMAs are not dead code, but never execute
-                if (row0 + (lane & 15) < M && !(DBG & 4) && (!(DBG & 16) || lo[0] == 12345.678f)) {
+                if (row0 + (lane & 15) < M) {
                     if (OUT_BF16) {
                         uint4 pk;
                         pk.x = pack_bf16x2(lo[0], lo[1]);
@@ -223,14 +221,7 @@ __global__ __launch_bounds__(64 * T::NWAVES) void k_gemm_bf16_nt_persistent(cons
     auto run = [&](auto late_c) __attribute__((always_inline)) {
         constexpr bool LATE = decltype(late_c)::value;
         bf16x8 a[TI], b[TJ];
-        if (DBG & 8) {
-#pragma unroll
-            for (int i = 0; i < TI; i++) a[i] = bf16x8{(short)lane, 1, 2, 3, 4, 5, 6, 7};
-#pragma unroll
-            for (int j = 0; j < TJ; j++) b[j] = bf16x8{(short)wave, 1, 2, 3, 4, 5, 6, 7};
-        }
         auto read_frags = [&](int hs) __attribute__((always_inline)) {
-            if (DBG & 8) return;                             // timing experiment: no LDS fragment reads
             const char* cur = lds + (hs % kStages) * T::STAGE;
             const int chunk = lane >> 4, r16 = lane & 15;
 #pragma unroll
@@ -239,13 +230,6 @@ __global__ __launch_bounds__(64 * T::NWAVES) void k_gemm_bf16_nt_persistent(cons
             for (int i = 0; i < TI; i++) a[i] = frag(cur, (wm * TI + i) * 16 + r16, chunk);
         };
         auto multiply = [&]() __attribute__((always_inline)) {
-            if (DBG & 2) {                                   // timing experiment: no MFMA (keep the fragments alive)
-#pragma unroll
-                for (int i = 0; i < TI; i++) asm volatile("" ::"v"(a[i]));
-#pragma unroll
-                for (int j = 0; j < TJ; j++) asm volatile("" ::"v"(b[j]));
-                return;
-            }
 #pragma unroll
             for (int i = 0; i < TI; i++)
 #pragma unroll
@@ -254,7 +238,6 @@ __global__ __launch_bounds__(64 * T::NWAVES) void k_gemm_bf16_nt_persistent(cons
         // sixteen-wave shape without the half-step skew: four waves per SIMD hide each other's LDS latency, so a wave reads its A fragments
         // one MFMA row ahead instead of all at once (128 registers per wave: the accumulators take 64 of them)
         auto read_multiply = [&](int hs) __attribute__((always_inline)) {
-            if (DBG & 10) { read_frags(hs); multiply(); return; }      // timing experiments go through the separately switchable halves
             const char* cur = lds + (hs % kStages) * T::STAGE;
             const int chunk = lane >> 4, r16 = lane & 15;
 #pragma unroll
@@ -387,19 +370,6 @@ int launch_gemm_bf16_nt(avd_ctx* ctx, const uint16_t* d_a, const uint16_t* d_bt,
         if (grid_sq < 8) grid_sq = 8;
         if (grid_sq > (tiles + 7) / 8 * 8) grid_sq = (tiles + 7) / 8 * 8;
         const size_t lds = (size_t)Sq::LDS + (size_t)N * sizeof(float);
-#ifdef AVD_GEMM_DEBUG
-        // timing experiments (tools/gemm_dbg.sh, tools/r05_gemm_dbg.sh): AVD_GEMM_DBG bits 1 = no LDS-DMA, 2 = no MFMA, 4 = no stores, 8 = no fragment reads
-        static const int dbg = [] { const char* e = std::getenv("AVD_GEMM_DBG"); return e ? std::atoi(e) : 0; }();
-        using Dbg16 = TileShape<4, 4, 4, 16, false>;
-        switch (dbg) {
-#define AVD_DBG_CASE(D) case D: if (ctx->gemm_waves == 16) return go(k_gemm_bf16_nt_persistent<kDim, 1, Dbg16, D>, 1024, grid_sq, lds, d_a, d_bt, d_bias, d_c, M, N); \
-                                return go(k_gemm_bf16_nt_persistent<kDim, 1, Sq, D>, 512, grid_sq, lds, d_a, d_bt, d_bias, d_c, M, N);
-            AVD_DBG_CASE(1) AVD_DBG_CASE(2) AVD_DBG_CASE(4) AVD_DBG_CASE(8) AVD_DBG_CASE(3) AVD_DBG_CASE(5) AVD_DBG_CASE(6) AVD_DBG_CASE(7)
-            AVD_DBG_CASE(10) AVD_DBG_CASE(12) AVD_DBG_CASE(14) AVD_DBG_CASE(16) AVD_DBG_CASE(17) AVD_DBG_CASE(24)
-#undef AVD_DBG_CASE
-        default: break;
-        }
-#endif
         // ctx->gemm_waves (option "gemm_waves", AVD_GEMM_WAVES): 8 (default) = eight waves of 8 x 4 MFMA tiles, half of them half a step late;
         // 16 = the same tile on sixteen waves of 4 x 4 tiles, no skew (round 5: an operand stream that sixteen waves issue runs at 92-99 instead of
         // 60-72 GB/s per CU in isolation, tools/ldsdma_occ_bench.hip -- measured no faster in the kernel, 0.268-0.276 against 0.252-0.267 ms:

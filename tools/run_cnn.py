@@ -11,10 +11,12 @@ avd_hip.load()
 import torch
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 120
 reps = int(sys.argv[2]) if len(sys.argv) > 2 else 3
+tiles = int(sys.argv[3]) if len(sys.argv) > 3 else 0        # option "cnn_tiles": 0 = heuristic, 1 = 256-pixel tiles, 2 = 128 x 128
 clip = synth.random_frames(4, 360, 640, seed=1)
 frames = torch.from_numpy(np.concatenate([clip] * (n // 4))).to("cuda:0")
 ctx = avd_hip.Context(0)
 ctx.set_option("cnn_chunk", int(os.environ.get("AVD_CNN_CHUNK", "128")))     # frames per forward pass
+ctx.set_option("cnn_tiles", tiles)
 if os.environ.get("AVD_CNN_FUSE"):
     ctx.set_option("cnn_fuse", int(os.environ["AVD_CNN_FUSE"]))
 ctx.cnn_set_weights(*cnn.seeded_parameters(0))
