@@ -333,13 +333,12 @@ static void launch_records(avd_ctx* ctx, int p0, int np, int fa, const int* clip
 // (nothing is launched when nothing is flagged -- the usual case).  For the last chunk of an asynchronous call that happens when the call is
 // drained (ctx->tail, impl_synchronize): the flags travel with the records.  A chunk that is followed by another one (> 512 pairs in a call), and
 // every chunk of a call that hands statistics straight to the host, is settled here, before its scratch is reused.
-static void tail_unregister(avd_ctx* ctx);
 static int run_flow_chunks(avd_ctx* ctx, const uint8_t* d_small, int n, float* h_mean, float* h_var,
                            float* h_flow_out, bool into_records, const int* records_clipstart = nullptr)
 {
     Workspace& ws = ctx->ws;
-    tail_unregister(ctx);
-    ctx->tail.active = 0;
+    // every entry point completes a pending asynchronous call before it runs (guarded, drain_pending): a tail found here would be dropped
+    if (ctx->tail.active) { ctx->err = "internal error: the re-run of a pending call was not settled"; return AVD_ERR_DEVICE; }
     if (n < 2) return 0;
     if (int e = avd_ws_reserve_fb(ctx, n)) return e;
     const int chunk = ws.fb_cap;
@@ -678,7 +677,6 @@ static int impl_analyze_batch_async(avd_ctx* ctx, const avd_clip* clips, int ncl
     if (!records) { ctx->err = "null pointer"; return AVD_ERR_ARG; }
     const int n = (int)total;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (ctx->pending_out) { if (int e = impl_synchronize(ctx)) return e; }     // a previous call was never drained
     Workspace& ws = ctx->ws;
     // pass 1: geometry tables (cached) and sizes -- everything is reserved before the first launch of the call
     size_t rowbuf_elems = 0, lappart_elems = 0, stage_bytes = 0;
@@ -754,6 +752,12 @@ static int impl_analyze_batch_async(avd_ctx* ctx, const avd_clip* clips, int ncl
         clipstart = ws.d_clipstart;
     }
     stage_mark(ctx, 2);
+    // from here on an error return must not leave a tail behind: a later avd_synchronize would settle it from a stale h_rec
+    struct TailOnError {
+        avd_ctx* c;
+        bool ok = false;
+        ~TailOnError() { if (!ok) c->tail.active = 0; }
+    } tail_on_error{ctx};
     if (n < 2)
         hipLaunchKernelGGL(k_records, dim3(n), dim3(256), 0, ctx->stream, (const unsigned long long*)ws.d_lap, (const uint8_t*)ws.d_hash,
                            (const float*)nullptr, (const int*)nullptr, 0, ws.d_rec, 0, clipstart, 0);
@@ -763,6 +767,7 @@ static int impl_analyze_batch_async(avd_ctx* ctx, const avd_clip* clips, int ncl
     // into PINNED memory: a device-to-host copy into the caller's pageable buffer would block this thread until
     // the whole call is done and it would not be asynchronous at all; avd_synchronize hands the records over
     HIP_TRY(ctx, hipMemcpyAsync(ws.h_rec, ws.d_rec, sizeof(avd_frame_record) * n, hipMemcpyDeviceToHost, ctx->stream));
+    tail_on_error.ok = true;
     ctx->pending_out = records; ctx->pending_n = n;
     if (ctx->tail.active) tail_register(ctx);              // from here on a waiting thread may settle this call's tail
     if (!ctx->counted_in_flight) { ctx->counted_in_flight = 1; g_calls_in_flight.fetch_add(1, std::memory_order_relaxed); }
@@ -1249,14 +1254,29 @@ static int impl_audio_features(avd_ctx* ctx, const float* wav, int mem, int64_t 
     return AVD_OK;
 }
 
+// An asynchronous call still pending on the context (records not handed over, or its last chunk's re-run not settled) is completed
+// first: the workspace, the pinned records buffer and the options it was submitted with belong to it until then.  A failure of the
+// pending call is returned instead of running the new one.
+static int drain_pending(avd_ctx* ctx)
+{
+    if (!ctx->pending_out && !ctx->tail.active) return AVD_OK;
+    return impl_synchronize(ctx);
+}
+
+// Pending::keep: the entry points that neither enqueue work, nor touch the workspace, nor change an option (avd_synchronize itself,
+// avd_get_option, the timers and timings, avd_wait_stream); every other one drains.
+enum class Pending { drain, keep };
+
 // Nothing may propagate across the C boundary: std::vector / std::string members of the context and the table
 // builders can throw std::bad_alloc (or length_error), so every entry point runs inside this guard.
 template <typename F>
-static int guarded(avd_ctx* ctx, F&& f) noexcept
+static int guarded(avd_ctx* ctx, F&& f, Pending pending = Pending::drain) noexcept
 {
     try {
         if (!ctx) return f();
         std::lock_guard<std::recursive_mutex> lk(ctx->api_mu);     // one call at a time per context; helpers of other contexts only try_lock (tail_help_others)
+        if (pending == Pending::drain)
+            if (int e = drain_pending(ctx)) return e;
         return f();
     } catch (const std::bad_alloc&) {
         if (ctx) { try { ctx->err = "out of host memory"; } catch (...) {} }
@@ -1301,7 +1321,7 @@ int avd_analyze_frames_async(avd_ctx* ctx, const uint8_t* bgr, int mem, int n, i
     return guarded(ctx, [&] { return impl_analyze_frames_async(ctx, bgr, mem, n, h, w, row_stride, frame_stride, records); });
 }
 
-int avd_synchronize(avd_ctx* ctx) { return guarded(ctx, [&] { return impl_synchronize(ctx); }); }
+int avd_synchronize(avd_ctx* ctx) { return guarded(ctx, [&] { return impl_synchronize(ctx); }, Pending::keep); }
 
 int avd_analyze_batch_async(avd_ctx* ctx, const avd_clip* clips, int nclips, avd_frame_record* records)
 {
@@ -1423,23 +1443,20 @@ int avd_allgather_records(avd_ctx* ctx, const avd_frame_record* local, int count
 int avd_allgather_last_records(avd_ctx* ctx, int count, avd_frame_record* all)
 {
     if (!ctx) return AVD_ERR_ARG;
-    return guarded(ctx, [&] {
-        // a pending asynchronous call is drained FIRST: the exact re-run of the pairs its fast level kernels flagged happens there, and the
-        // records on the device are final only after it
-        if (ctx->pending_out || ctx->tail.active) { if (int e = impl_synchronize(ctx)) return e; }
-        return comm_allgather_last_records(ctx, count, all);
-    });
+    // guarded drains a pending asynchronous call FIRST: the exact re-run of the pairs its fast level kernels flagged happens there, and the
+    // records on the device are final only after it
+    return guarded(ctx, [&] { return comm_allgather_last_records(ctx, count, all); });
 }
 
-int avd_wait_stream(avd_ctx* ctx, void* producer_stream) { return guarded(ctx, [&] { return impl_wait_stream(ctx, producer_stream); }); }
+int avd_wait_stream(avd_ctx* ctx, void* producer_stream) { return guarded(ctx, [&] { return impl_wait_stream(ctx, producer_stream); }, Pending::keep); }
 int avd_release_workspace(avd_ctx* ctx) { return guarded(ctx, [&] { return impl_release_workspace(ctx); }); }
-int avd_timer_start(avd_ctx* ctx) { return guarded(ctx, [&] { return impl_timer_start(ctx); }); }
-int avd_timer_stop(avd_ctx* ctx, float* elapsed_ms) { return guarded(ctx, [&] { return impl_timer_stop(ctx, elapsed_ms); }); }
+int avd_timer_start(avd_ctx* ctx) { return guarded(ctx, [&] { return impl_timer_start(ctx); }, Pending::keep); }
+int avd_timer_stop(avd_ctx* ctx, float* elapsed_ms) { return guarded(ctx, [&] { return impl_timer_stop(ctx, elapsed_ms); }, Pending::keep); }
 int avd_set_option(avd_ctx* ctx, const char* name, int value) { return guarded(ctx, [&] { return impl_set_option(ctx, name, value); }); }
-int avd_get_option(avd_ctx* ctx, const char* name, int* value) { return guarded(ctx, [&] { return impl_get_option(ctx, name, value); }); }
+int avd_get_option(avd_ctx* ctx, const char* name, int* value) { return guarded(ctx, [&] { return impl_get_option(ctx, name, value); }, Pending::keep); }
 int avd_set_profiling(avd_ctx* ctx, int enable) { return guarded(ctx, [&] { return impl_set_profiling(ctx, enable); }); }
-int avd_stage_ms(avd_ctx* ctx, int stage, float* ms) { return guarded(ctx, [&] { return impl_stage_ms(ctx, stage, ms); }); }
-int avd_kernel_ms(avd_ctx* ctx, int kernel_id, float* ms) { return guarded(ctx, [&] { return impl_kernel_ms(ctx, kernel_id, ms); }); }
+int avd_stage_ms(avd_ctx* ctx, int stage, float* ms) { return guarded(ctx, [&] { return impl_stage_ms(ctx, stage, ms); }, Pending::keep); }
+int avd_kernel_ms(avd_ctx* ctx, int kernel_id, float* ms) { return guarded(ctx, [&] { return impl_kernel_ms(ctx, kernel_id, ms); }, Pending::keep); }
 
 int64_t avd_debug_fetch(avd_ctx* ctx, const char* name, void* out, size_t out_bytes)
 {

@@ -102,8 +102,14 @@ int avd_analyze_frames(avd_ctx* ctx, const uint8_t* bgr, int mem, int n, int h, 
 /* Same, but only enqueues the work on ctx's stream and returns; records (any HOST
  * memory) are filled by avd_synchronize: the device-to-host copy lands in a pinned
  * buffer of the library, so the call never blocks on it and several contexts can
- * keep clips in flight on one GPU.  One call may be outstanding per context (a
- * second one drains the first).  With AVD_MEM_HOST input the frames are staged by
+ * keep clips in flight on one GPU.  One call may be outstanding per context: any
+ * other call on the context first completes it -- its records buffer is filled and
+ * the re-run of its flagged pairs (fb_mode 1) is settled -- and returns its error
+ * instead of running if it failed.  Exempt: avd_synchronize, avd_destroy,
+ * avd_last_error, avd_get_option, avd_stage_ms, avd_kernel_ms, avd_timer_start /
+ * avd_timer_stop and avd_wait_stream.  An option set while a call is pending applies
+ * to the calls submitted after it; "rerun_pairs" reports the last call that ran the
+ * Farneback stage.  With AVD_MEM_HOST input the frames are staged by
  * hipMemcpyAsync from the caller's buffer, which is only asynchronous if that buffer
  * is pinned. */
 int avd_analyze_frames_async(avd_ctx* ctx, const uint8_t* bgr, int mem, int n, int h, int w,

@@ -276,3 +276,17 @@ def families():
     fam["checker_overlay"] = checker_overlay
 
     return fam
+
+
+def flagged_mix(n_pairs, seed):
+    """n_pairs + 1 frames uint8[320, 320] whose consecutive pairs alternate between content the fast Farneback level kernels flag (ramps
+    rolled, stripes, 2-px checkerboards against their inverse) and content they do not (smooth translation).  Used by tests/test_gpu_fbfast.py
+    and tests/test_gpu_pending_call.py."""
+    fam = families()
+    rng = np.random.default_rng(seed)
+    names = ["ramp_roll", "smooth_shift", "stripes", "checker", "pink_shift"]
+    frames = []
+    while len(frames) < n_pairs + 1:
+        a, b = fam[names[(len(frames) // 2) % len(names)]](rng)
+        frames += [a, b]
+    return np.stack(frames[:n_pairs + 1])

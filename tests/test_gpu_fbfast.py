@@ -25,6 +25,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 from avd_hip import synth  # noqa: E402
+from tests.content_families import flagged_mix as _flagged_mix  # noqa: E402
 
 FLOW_TOL = 1e-5      # px
 SUSP_TOL = 1e-6
@@ -193,20 +194,6 @@ def test_folded_launches_are_bit_identical(oracle):
                 for k, lv in enumerate(levels(c, len(frames))):            # and the final flow of every pyramid level
                     assert np.array_equal(lv.view(np.uint32), lvl0[k].view(np.uint32)), (mask, k)
             c.set_option("fb_fold_up", 5)
-
-
-def _flagged_mix(n_pairs, seed):
-    """frames whose consecutive pairs alternate between content the level kernels flag (ramps rolled, stripes, 2-px checkerboards against
-    their inverse) and content they do not (smooth translation)"""
-    from tests.content_families import families
-    fam = families()
-    rng = np.random.default_rng(seed)
-    names = ["ramp_roll", "smooth_shift", "stripes", "checker", "pink_shift"]
-    frames = []
-    while len(frames) < n_pairs + 1:
-        a, b = fam[names[(len(frames) // 2) % len(names)]](rng)
-        frames += [a, b]
-    return np.stack(frames[:n_pairs + 1])
 
 
 def test_rerun_paths_are_the_exact_kernels(ctxs, oracle):
