@@ -234,13 +234,7 @@ int launch_audio_features(avd_ctx* ctx, const float* d_wav, int64_t n, int win, 
         for (int j = 0; j < last; j++) { cl[j] = std::cos(2.0 * M_PI * (double)j / (double)last); sl[j] = std::sin(2.0 * M_PI * (double)j / (double)last); }
         const size_t need = (size_t)3 * win + 3 * (size_t)last;
         ws.audio_win = ws.audio_last = 0;                     // the tables are not valid again until every copy below is enqueued
-        if (ws.audio_tab_elems < need) {
-            if (ws.d_audio_tab) (void)hipFree(ws.d_audio_tab);
-            ws.d_audio_tab = nullptr;
-            ws.audio_tab_elems = 0;
-            if (hipMalloc((void**)&ws.d_audio_tab, need * sizeof(double)) != hipSuccess) { ctx->err = "hipMalloc (audio tables)"; return AVD_ERR_NOMEM; }
-            ws.audio_tab_elems = need;
-        }
+        if (int e = ws.d_audio_tab.reserve(ctx, need)) return e;
         double* t = ws.d_audio_tab;
         HIP_TRY(ctx, hipMemcpyAsync(t, hf.data(), sizeof(double) * win, hipMemcpyHostToDevice, ctx->stream));
         HIP_TRY(ctx, hipMemcpyAsync(t + win, cf.data(), sizeof(double) * win, hipMemcpyHostToDevice, ctx->stream));
@@ -255,13 +249,7 @@ int launch_audio_features(avd_ctx* ctx, const float* d_wav, int64_t n, int win, 
     // (another window length, the short last window of a stream) the direct form
     const int nfull = win == kFftN ? (last == win ? nwin : nwin - 1) : 0;
     const size_t xw_need = (size_t)nwin * win, mag_need = (size_t)nwin * (win / 2 + 1), b_need = (size_t)nfull * kFftN * 2;
-    if (ws.audio_buf_elems < xw_need + mag_need + b_need) {
-        if (ws.d_audio_buf) (void)hipFree(ws.d_audio_buf);
-        ws.d_audio_buf = nullptr;
-        ws.audio_buf_elems = 0;
-        if (hipMalloc((void**)&ws.d_audio_buf, (xw_need + mag_need + b_need) * sizeof(double)) != hipSuccess) { ctx->err = "hipMalloc (audio scratch)"; return AVD_ERR_NOMEM; }
-        ws.audio_buf_elems = xw_need + mag_need + b_need;
-    }
+    if (int e = ws.d_audio_buf.reserve(ctx, xw_need + mag_need + b_need)) return e;
     double* t = ws.d_audio_tab;
     double *xw = ws.d_audio_buf, *mag = ws.d_audio_buf + xw_need;
     double2* bbuf = reinterpret_cast<double2*>(ws.d_audio_buf + xw_need + mag_need);

@@ -42,36 +42,13 @@ struct TableBlob {
     }
 };
 
-// keep_weights: avd_release_workspace gives SCRATCH back; the weights a caller uploaded (avd_cnn_set_weights,
-// avd_vit_set_weights) are state, not scratch, and stay
-void free_ws(Workspace& ws, bool keep_weights = false)
+// bytes spanned by n frames of `rows` rows of `row_bytes` bytes each, with the given strides
+size_t plane_span(int64_t frame_stride, int n, int64_t row_stride, int rows, size_t row_bytes)
 {
-    auto F = [](auto*& p) { if (p) { (void)hipFree(p); p = nullptr; } };
-    uint16_t *kw = ws.d_cnn_w, *vw = ws.d_vit_w;
-    float *kb = ws.d_cnn_b, *vb = ws.d_vit_bias;
-    const int vhb = ws.vit_has_bias;
-    std::vector<size_t> woff = ws.cnn_w_off;
-    const size_t fcoff = ws.cnn_fc_off;
-    if (keep_weights) { ws.d_cnn_w = nullptr; ws.d_cnn_b = nullptr; ws.d_vit_w = nullptr; ws.d_vit_bias = nullptr; }
-    F(ws.d_stage); F(ws.d_small); F(ws.d_rowbuf); F(ws.d_area); F(ws.d_hash); F(ws.d_ham); F(ws.d_lap); F(ws.d_lap_part);
-    for (Geom& g : ws.geoms) F(g.d_tables);
-    F(ws.d_clipstart);
-    if (ws.h_clipstart) (void)hipHostFree(ws.h_clipstart);
-    for (int k = 0; k < AVD_FB_LEVELS; k++) { F(ws.d_pyr[k]); F(ws.d_poly[k]); F(ws.d_flow[k]); F(ws.d_flow2[k]); }
-    F(ws.d_vs); F(ws.d_vs0); F(ws.d_flow_il); F(ws.d_stats); F(ws.d_rec); F(ws.d_mag); F(ws.d_fbflags); F(ws.d_pairdiff);
-    F(ws.d_rlist); F(ws.d_vs_rerun); F(ws.d_vs0_rerun);
-    if (ws.h_rlist) (void)hipHostFree(ws.h_rlist);
-    F(ws.d_vit_w); F(ws.d_vit_bias); F(ws.d_vit_patches); F(ws.d_vit_tokens);
-    F(ws.d_audio_tab); F(ws.d_audio_buf); F(ws.d_audio_out);
-    F(ws.d_cnn_w); F(ws.d_cnn_b); F(ws.d_cnn_img); F(ws.d_cnn_pool); F(ws.d_cnn_logits);
-    for (int i = 0; i < 4; i++) F(ws.d_cnn_act[i]);
-    if (ws.h_rec) (void)hipHostFree(ws.h_rec);
-    ws = Workspace{};
-    if (keep_weights) {
-        ws.d_cnn_w = kw; ws.d_cnn_b = kb; ws.d_vit_w = vw; ws.d_vit_bias = vb; ws.vit_has_bias = vhb;
-        ws.cnn_w_off = woff; ws.cnn_fc_off = fcoff;
-    }
+    return (size_t)frame_stride * (n - 1) + (size_t)row_stride * (rows - 1) + row_bytes;
 }
+
+size_t round256(size_t v) { return (v + 255) / 256 * 256; }
 
 int check_geometry(avd_ctx* ctx, int n, int h, int w, int64_t row_stride, int64_t frame_stride)
 {
@@ -116,17 +93,11 @@ static int build_geom(avd_ctx* ctx, Geom& g, int h, int w)
     const size_t o_ayb = tb.push(at.y.begin), o_ayc = tb.push(at.y.count);
     const size_t o_ayf = tb.push(at.y.w_first), o_aym = tb.push(at.y.w_mid), o_ayl = tb.push(at.y.w_last);
     g.h = g.w = 0;                                     // not valid until everything below succeeded
-    uint8_t* dt = (uint8_t*)g.d_tables;
-    if (g.tables_bytes < tb.bytes.size()) {
-        // an evicted entry's tables may still be read by a kernel in flight on this context's stream: drain it first
-        // (only on the first use of a FIFTH distinct geometry, or of one with larger tables)
-        if (dt) HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        g.tables_bytes = 0;
-        if (int e = dev_alloc(ctx, dt, tb.bytes.size())) { g.d_tables = nullptr; return e; }
-        g.d_tables = dt; g.tables_bytes = tb.bytes.size();
-    } else if (dt) {
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));   // re-using the buffer of an evicted geometry
-    }
+    // an evicted entry's tables may still be read by a kernel in flight on this context's stream: drain it before the buffer is
+    // freed (larger tables) or re-used (only on the first use of a FIFTH distinct geometry)
+    if (g.d_tables) HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (int e = g.d_tables.reserve(ctx, tb.bytes.size())) return e;
+    uint8_t* dt = g.d_tables;
     HIP_TRY(ctx, hipMemcpyAsync(dt, tb.bytes.data(), tb.bytes.size(), hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));      // tb goes out of scope
     PreParams& P = g.pre;
@@ -167,13 +138,11 @@ int avd_ws_geometry(avd_ctx* ctx, int h, int w)
         if (!victim || (g.h == 0 && victim->h != 0) || (g.h != 0 && victim->h != 0 && g.stamp < victim->stamp)) victim = &g;
     }
     if (!hit) {
-        ws.h = ws.w = 0;
         if (int e = build_geom(ctx, *victim, h, w)) return e;
         hit = victim;
     }
     hit->stamp = ++ws.geom_clock;
     ws.pre = hit->pre; ws.hsh = hit->hsh;
-    ws.h = h; ws.w = w;
     return 0;
 }
 
@@ -183,34 +152,20 @@ int avd_ws_reserve_frames(avd_ctx* ctx, int n, size_t rowbuf_elems, size_t lappa
 {
     Workspace& ws = ctx->ws;
     if (n > ws.cap_n) {
-        const int cap = std::max(n, 1);
+        const size_t cap = (size_t)std::max(n, 1);
         ws.cap_n = 0;                                  // not valid again until every buffer below exists
-        if (int e = dev_alloc(ctx, ws.d_small, (size_t)cap * AVD_NPIX)) return e;
-        if (int e = dev_alloc(ctx, ws.d_area, (size_t)cap * 1024)) return e;
-        if (int e = dev_alloc(ctx, ws.d_hash, (size_t)cap * 1024)) return e;
-        if (int e = dev_alloc(ctx, ws.d_ham, (size_t)cap)) return e;
-        if (int e = dev_alloc(ctx, ws.d_lap, (size_t)cap * 2)) return e;
-        if (int e = dev_alloc(ctx, ws.d_rec, (size_t)cap)) return e;
-        if (int e = dev_alloc(ctx, ws.d_clipstart, (size_t)cap)) return e;
-        if (ws.h_rec) { (void)hipHostFree(ws.h_rec); ws.h_rec = nullptr; }
-        if (ws.h_clipstart) { (void)hipHostFree(ws.h_clipstart); ws.h_clipstart = nullptr; }
-        if (hipHostMalloc((void**)&ws.h_rec, sizeof(avd_frame_record) * cap, hipHostMallocDefault) != hipSuccess ||
-            hipHostMalloc((void**)&ws.h_clipstart, sizeof(int) * cap, hipHostMallocDefault) != hipSuccess) {
-            ctx->err = "hipHostMalloc failed"; return AVD_ERR_NOMEM;
-        }
-        ws.cap_n = cap;
+        if (int e = ws.d_small.reserve(ctx, cap * AVD_NPIX)) return e;
+        if (int e = ws.d_area.reserve(ctx, cap * 1024)) return e;
+        if (int e = ws.d_hash.reserve(ctx, cap * 1024)) return e;
+        if (int e = ws.d_lap.reserve(ctx, cap * 2)) return e;
+        if (int e = ws.d_rec.reserve(ctx, cap)) return e;
+        if (int e = ws.d_clipstart.reserve(ctx, cap)) return e;
+        if (int e = ws.h_rec.reserve(ctx, cap)) return e;
+        if (int e = ws.h_clipstart.reserve(ctx, cap)) return e;
+        ws.cap_n = (int)cap;
     }
-    if (rowbuf_elems > ws.rowbuf_cap) {
-        ws.rowbuf_cap = 0;
-        if (int e = dev_alloc(ctx, ws.d_rowbuf, rowbuf_elems)) return e;
-        ws.rowbuf_cap = rowbuf_elems;
-    }
-    if (lappart_elems > ws.lappart_cap) {
-        ws.lappart_cap = 0;
-        if (int e = dev_alloc(ctx, ws.d_lap_part, lappart_elems)) return e;
-        ws.lappart_cap = lappart_elems;
-    }
-    return 0;
+    if (int e = ws.d_rowbuf.reserve(ctx, rowbuf_elems)) return e;
+    return ws.d_lap_part.reserve(ctx, lappart_elems);
 }
 
 static size_t rowbuf_elems_for(const Workspace& ws, int n) { return (size_t)n * ws.pre.h * AVD_HASH; }
@@ -233,38 +188,34 @@ int avd_ws_reserve_fb(avd_ctx* ctx, int n)
     Workspace& ws = ctx->ws;
     const int want = std::max(kFbChunk, std::min(std::max(n - 1, 0), kFbChunkMax));
     if (want > ws.fb_cap) {
-        const size_t nf = (size_t)want + 2, np = (size_t)want;       // +1 frame: the two segments of a chunk overlap by one frame
-        ws.fb_cap = 0;
+        const size_t nf = (size_t)want + 2, np = (size_t)want;       // frames = pairs + 1, and one spare
+        ws.fb_cap = 0;                                 // not valid again until every buffer below exists
         for (int k = 0; k < AVD_FB_LEVELS; k++) {
             const size_t plane = (size_t)(AVD_SMALL >> k) * (AVD_SMALL >> k);
             // the 320-px scale of the pyramid exists only with fb_fold_blur off (the polynomial expansion forms that blur itself): 49 MB per 120 frames
-            if (k > 0 || !ctx->fb_fold_blur) { if (int e = dev_alloc(ctx, ws.d_pyr[k], nf * plane)) return e; }
-            else if (ws.d_pyr[0]) { (void)hipFree(ws.d_pyr[0]); ws.d_pyr[0] = nullptr; }
-            if (int e = dev_alloc(ctx, ws.d_poly[k], nf * 5 * plane)) return e;
-            if (int e = dev_alloc(ctx, ws.d_flow[k], np * 2 * plane)) return e;
-            if (int e = dev_alloc(ctx, ws.d_flow2[k], np * 2 * plane)) return e;
+            if (k > 0 || !ctx->fb_fold_blur) { if (int e = ws.d_pyr[k].reserve(ctx, nf * plane)) return e; }
+            else ws.d_pyr[0].reset();
+            if (int e = ws.d_poly[k].reserve(ctx, nf * 5 * plane)) return e;
+            if (int e = ws.d_flow[k].reserve(ctx, np * 2 * plane)) return e;
+            if (int e = ws.d_flow2[k].reserve(ctx, np * 2 * plane)) return e;
             ws.flow_res[k] = nullptr;
         }
-        if (int e = dev_alloc(ctx, ws.d_stats, np * 2)) return e;
-        if (int e = dev_alloc(ctx, ws.d_mag, np * (size_t)AVD_NPIX)) return e;
-        if (int e = dev_alloc(ctx, ws.d_fbflags, np)) return e;
-        if (int e = dev_alloc(ctx, ws.d_pairdiff, np * kPairDiffTilesHost)) return e;
-        if (ws.d_rlist) { (void)hipFree(ws.d_rlist); ws.d_rlist = nullptr; ws.rlist_cap = 0; }
-        if (ws.h_rlist) { (void)hipHostFree(ws.h_rlist); ws.h_rlist = nullptr; }
-        if (hipHostMalloc((void**)&ws.h_rlist, sizeof(int) * np) != hipSuccess) { ws.h_rlist = nullptr; ctx->err = "hipHostMalloc (re-run list)"; return AVD_ERR_NOMEM; }
-        if (ws.d_vs) { (void)hipFree(ws.d_vs); ws.d_vs = nullptr; }
-        if (ws.d_vs0) { (void)hipFree(ws.d_vs0); ws.d_vs0 = nullptr; }
-        if (ws.d_flow_il) { (void)hipFree(ws.d_flow_il); ws.d_flow_il = nullptr; }
+        if (int e = ws.d_stats.reserve(ctx, np * 2)) return e;
+        if (int e = ws.d_mag.reserve(ctx, np * (size_t)AVD_NPIX)) return e;
+        if (int e = ws.d_fbflags.reserve(ctx, np)) return e;
+        if (int e = ws.d_pairdiff.reserve(ctx, np * kPairDiffTilesHost)) return e;
+        if (int e = ws.h_rlist.reserve(ctx, np)) return e;
+        // sized by the chunk, allocated by whoever first needs them
+        ws.d_rlist.reset(); ws.d_vs.reset(); ws.d_vs0.reset(); ws.d_flow_il.reset();
         ws.fb_cap = want;
     }
-    if (!ctx->fb_fold_blur && !ws.d_pyr[0])
-        if (int e = dev_alloc(ctx, ws.d_pyr[0], ((size_t)ws.fb_cap + 2) * AVD_NPIX)) return e;
+    if (!ctx->fb_fold_blur)
+        if (int e = ws.d_pyr[0].reserve(ctx, ((size_t)ws.fb_cap + 2) * AVD_NPIX)) return e;
     // the double intermediate of the two-kernel fallback (4 MB per pair): only when that path is selected
-    const bool two_kernel = ctx->fb_mode == 0 && ctx->fb_fused != 0xF;
-    if (two_kernel && !ws.d_vs) {
+    if (ctx->fb_mode == 0 && ctx->fb_fused != 0xF) {
         const size_t np = (size_t)ws.fb_cap;
-        if (int e = dev_alloc(ctx, ws.d_vs0, np * 5 * AVD_SMALL * 8)) return e;
-        if (int e = dev_alloc(ctx, ws.d_vs, np * (5 * AVD_NPIX + 512))) return e;      // + one pad tile per pair
+        if (int e = ws.d_vs0.reserve(ctx, np * 5 * AVD_SMALL * 8)) return e;
+        if (int e = ws.d_vs.reserve(ctx, np * (5 * AVD_NPIX + 512))) return e;      // + one pad tile per pair
     }
     return 0;
 }
@@ -313,7 +264,7 @@ static int rerun_flagged(avd_ctx* ctx, const int* h_flags, int stride, int np)
     for (int i = 0; i < np; i++)
         if (h_flags[(size_t)i * stride] != 0) ws.h_rlist[m++] = i;
     if (m == 0) return 0;
-    if (int e = launch_farneback_rerun(ctx, ctx->stream, ws.h_rlist, m, 0, np)) return e < 0 ? e : -1;
+    if (int e = launch_farneback_rerun(ctx, ws.h_rlist, m, np)) return e < 0 ? e : -1;
     return m;
 }
 
@@ -342,10 +293,9 @@ static int run_flow_chunks(avd_ctx* ctx, const uint8_t* d_small, int n, float* h
     if (n < 2) return 0;
     if (int e = avd_ws_reserve_fb(ctx, n)) return e;
     const int chunk = ws.fb_cap;
-    if (h_flow_out && !ws.d_flow_il)
-        if (int e = dev_alloc(ctx, ws.d_flow_il, (size_t)chunk * AVD_NPIX * 2)) return e;
-    float* saved_il = ws.d_flow_il;
-    if (!h_flow_out) ws.d_flow_il = nullptr;
+    if (h_flow_out)
+        if (int e = ws.d_flow_il.reserve(ctx, (size_t)chunk * AVD_NPIX * 2)) return e;
+    ws.no_flow_il = !h_flow_out;                           // nobody reads the interleaved flow of these chunks
     const bool flagged_mode = ctx->fb_mode == 1 && ctx->fb_rerun;
     const bool host_wants = h_mean || h_var || h_flow_out;
     int rc = 0;
@@ -353,9 +303,9 @@ static int run_flow_chunks(avd_ctx* ctx, const uint8_t* d_small, int n, float* h
         const int np = std::min(chunk, n - 1 - p0);
         const bool last = p0 + np >= n - 1;
         const uint8_t* base = d_small + (size_t)p0 * AVD_NPIX;
-        rc = launch_farneback(ctx, ctx->stream, base, np + 1, 0, 0);
+        rc = launch_farneback(ctx, base, np + 1);
         if (rc) break;
-        rc = launch_flow_stats(ctx, ctx->stream, np + 1, 0, 0);
+        rc = launch_flow_stats(ctx, np + 1);
         if (rc) break;
         if (flagged_mode && (!last || host_wants || !into_records)) {
             std::vector<int> fl((size_t)np, 0);
@@ -371,7 +321,7 @@ static int run_flow_chunks(avd_ctx* ctx, const uint8_t* d_small, int n, float* h
         if (into_records) {
             launch_records(ctx, p0, np, fa, records_clipstart);
             if (flagged_mode && last && !host_wants) {
-                ctx->tail.active = 1; ctx->tail.p0 = p0; ctx->tail.np = np; ctx->tail.fa = fa; ctx->tail.n = n; ctx->tail.clipstart = records_clipstart;
+                ctx->tail.active = 1; ctx->tail.p0 = p0; ctx->tail.np = np; ctx->tail.fa = fa; ctx->tail.clipstart = records_clipstart;
             }
         }
         if (host_wants) {
@@ -388,7 +338,7 @@ static int run_flow_chunks(avd_ctx* ctx, const uint8_t* d_small, int n, float* h
             }
         }
     }
-    ws.d_flow_il = saved_il;
+    ws.no_flow_il = 0;
     return rc;
 }
 
@@ -398,11 +348,7 @@ static int stage_input(avd_ctx* ctx, const uint8_t* src, int mem, size_t bytes, 
     if (mem == AVD_MEM_DEVICE) { *d_out = src; return 0; }
     if (mem != AVD_MEM_HOST) { ctx->err = "mem must be AVD_MEM_HOST or AVD_MEM_DEVICE"; return AVD_ERR_ARG; }
     Workspace& ws = ctx->ws;
-    if (ws.stage_bytes < bytes) {
-        ws.stage_bytes = 0;                        // not valid again until the buffer exists
-        if (int e = dev_alloc(ctx, ws.d_stage, bytes)) return e;
-        ws.stage_bytes = bytes;
-    }
+    if (int e = ws.d_stage.reserve(ctx, bytes)) return e;
     HIP_TRY(ctx, hipMemcpyAsync(ws.d_stage, src, bytes, hipMemcpyHostToDevice, ctx->stream));
     *d_out = ws.d_stage;
     return 0;
@@ -540,7 +486,7 @@ static int impl_create(int device_id, avd_ctx** out)
         if (const char* e = std::getenv("AVD_FB_RERUN")) ctx->fb_rerun = std::atoi(e) != 0;
         if (const char* e = std::getenv("AVD_GEMM_WAVES")) ctx->gemm_waves = std::atoi(e) == 16 ? 16 : 8;
         build_fb_consts(ctx->fbc);
-        ok = hipMalloc(&ctx->d_fbc, sizeof(FbConsts)) == hipSuccess &&
+        ok = ctx->d_fbc.reserve(ctx, 1) == 0 &&
              hipMemcpy(ctx->d_fbc, &ctx->fbc, sizeof(FbConsts), hipMemcpyHostToDevice) == hipSuccess;
     }
     if (!ok) { impl_destroy(ctx); return AVD_ERR_DEVICE; }
@@ -557,8 +503,10 @@ static void impl_destroy(avd_ctx* ctx)
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
     if (ctx->counted_in_flight) { ctx->counted_in_flight = 0; g_calls_in_flight.fetch_sub(1, std::memory_order_relaxed); }
     comm_destroy(ctx);
-    free_ws(ctx->ws);
-    if (ctx->d_fbc) (void)hipFree(ctx->d_fbc);
+    // everything the context owns on the device goes here: after the drain, before its stream does
+    ctx->ws = Workspace{};
+    ctx->weights = Weights{};
+    ctx->d_fbc.reset();
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
     if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
     if (ctx->ev_in) (void)hipEventDestroy(ctx->ev_in);
@@ -570,22 +518,88 @@ static void impl_destroy(avd_ctx* ctx)
     delete ctx;
 }
 
-static int impl_preprocess_bgr(avd_ctx* ctx, const uint8_t* bgr, int mem, int n, int h, int w,
-                       int64_t row_stride, int64_t frame_stride,
-                       uint8_t* small320, uint8_t* hash1024, int64_t* lap_sum, int64_t* lap_sumsq)
+// ---- ingest: one clip = an avd_clip (BGR: uv == nullptr; NV12: data = the Y plane, uv = the interleaved chroma plane) ------------------
+static avd_clip bgr_clip(const uint8_t* bgr, int mem, int n, int h, int w, int64_t row_stride, int64_t frame_stride)
 {
-    if (!ctx) return AVD_ERR_ARG;
-    if (!bgr && n > 0) { ctx->err = "null frame pointer"; return AVD_ERR_ARG; }
-    if (int e = check_geometry(ctx, n, h, w, row_stride, frame_stride)) return e;
+    avd_clip k{};
+    k.data = bgr; k.mem = mem; k.n = n; k.h = h; k.w = w;
+    k.row_stride = row_stride; k.frame_stride = frame_stride;
+    return k;
+}
+
+static avd_clip nv12_clip(const uint8_t* y, const uint8_t* uv, int mem, int n, int h, int w, int64_t y_row, int64_t uv_row, int64_t y_frame,
+                          int64_t uv_frame)
+{
+    avd_clip k = bgr_clip(y, mem, n, h, w, y_row, y_frame);
+    k.uv = uv; k.uv_row_stride = uv_row; k.uv_frame_stride = uv_frame;
+    return k;
+}
+
+static int check_nv12(avd_ctx* ctx, const avd_clip& k)
+{
+    const int n = k.n, h = k.h, w = k.w;
+    if (n < 0 || h <= 0 || w <= 0 || h > 16384 || w > 16384) { ctx->err = "bad frame geometry"; return AVD_ERR_ARG; }
+    if ((h | w) & 1) { ctx->err = "NV12 needs even width and height"; return AVD_ERR_UNSUPPORTED; }
+    if (h < AVD_HASH || w < AVD_HASH) { ctx->err = "frame smaller than 32x32: INTER_AREA upscaling is not on the path"; return AVD_ERR_UNSUPPORTED; }
+    if ((!k.data || !k.uv) && n > 0) { ctx->err = "null plane pointer"; return AVD_ERR_ARG; }
+    if (k.row_stride < w || k.uv_row_stride < w ||
+        (n > 1 && (k.frame_stride < k.row_stride * (h - 1) + w || k.uv_frame_stride < k.uv_row_stride * (h / 2 - 1) + w))) {
+        ctx->err = "strides smaller than the planes"; return AVD_ERR_ARG;
+    }
+    return 0;
+}
+
+// Where a HOST clip lands in the staging buffer: BGR as one span; NV12 as the Y span with the chroma span on the next 256-byte
+// boundary behind it.  `total` (a multiple of 256) is what the clip occupies; a device clip is used in place and occupies nothing.
+struct ClipStage { size_t y_bytes, uv_off, uv_bytes, total; };
+
+static ClipStage clip_stage(const avd_clip& c)
+{
+    ClipStage s{};
+    if (c.mem != AVD_MEM_HOST || c.n <= 0) return s;
+    s.y_bytes = plane_span(c.frame_stride, c.n, c.row_stride, c.h, (size_t)c.w * (c.uv ? 1 : 3));
+    if (c.uv) {
+        s.uv_off = round256(s.y_bytes);
+        s.uv_bytes = plane_span(c.uv_frame_stride, c.n, c.uv_row_stride, c.h / 2, (size_t)c.w);
+    }
+    s.total = round256(c.uv ? s.uv_off + s.uv_bytes : s.y_bytes);
+    return s;
+}
+
+// Stage clip k at offset `at` of ws.d_stage (host input; reserved by the caller) and launch its fused full-resolution kernel, which
+// writes the clip's slice (ws.f0, ws.rowbuf_off, ws.lappart_off) of the per-frame buffers.  The clip's geometry is current.
+static int preprocess_clip(avd_ctx* ctx, const avd_clip& k, size_t at)
+{
+    const uint8_t *d_in = k.data, *d_uv = k.uv;
+    if (k.mem == AVD_MEM_HOST) {
+        const ClipStage s = clip_stage(k);
+        uint8_t* dst = ctx->ws.d_stage + at;
+        HIP_TRY(ctx, hipMemcpyAsync(dst, k.data, s.y_bytes, hipMemcpyHostToDevice, ctx->stream));
+        d_in = dst;
+        if (k.uv) {
+            HIP_TRY(ctx, hipMemcpyAsync(dst + s.uv_off, k.uv, s.uv_bytes, hipMemcpyHostToDevice, ctx->stream));
+            d_uv = dst + s.uv_off;
+        }
+    }
+    if (!k.uv) return launch_preprocess(ctx, d_in, k.n, k.h, k.w, k.row_stride, k.frame_stride);
+    Nv12Params nv{};
+    nv.uv = d_uv; nv.uv_row_stride = k.uv_row_stride; nv.uv_frame_stride = k.uv_frame_stride;
+    build_yuv_consts(nv.k);
+    return launch_preprocess_nv12(ctx, d_in, nv, k.n, k.h, k.w, k.row_stride, k.frame_stride);
+}
+
+// avd_preprocess_bgr / avd_preprocess_nv12 behind their argument checks: one clip at offset 0 of the buffers, results to the host
+static int preprocess_to_host(avd_ctx* ctx, const avd_clip& k, uint8_t* small320, uint8_t* hash1024, int64_t* lap_sum, int64_t* lap_sumsq)
+{
+    const int n = k.n;
     if (n == 0) return AVD_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (int e = avd_ws_reserve(ctx, n, h, w)) return e;
-    const uint8_t* d_bgr = nullptr;
-    const size_t bytes = (size_t)frame_stride * (n - 1) + (size_t)row_stride * (h - 1) + (size_t)w * 3;
-    if (int e = stage_input(ctx, bgr, mem, bytes, &d_bgr)) return e;
-    if (int e = launch_preprocess(ctx, d_bgr, n, h, w, row_stride, frame_stride)) return e;
-    if (int e = launch_hash(ctx, n)) return e;
+    if (int e = avd_ws_reserve(ctx, n, k.h, k.w)) return e;
+    if (k.mem != AVD_MEM_HOST && k.mem != AVD_MEM_DEVICE) { ctx->err = "mem must be AVD_MEM_HOST or AVD_MEM_DEVICE"; return AVD_ERR_ARG; }
     Workspace& ws = ctx->ws;
+    if (int e = ws.d_stage.reserve(ctx, clip_stage(k).total)) return e;
+    if (int e = preprocess_clip(ctx, k, 0)) return e;
+    if (int e = launch_hash(ctx, n)) return e;
     std::vector<unsigned long long> lap((size_t)n * 2);
     if (small320) HIP_TRY(ctx, hipMemcpyAsync(small320, ws.d_small, (size_t)n * AVD_NPIX, hipMemcpyDeviceToHost, ctx->stream));
     if (hash1024) HIP_TRY(ctx, hipMemcpyAsync(hash1024, ws.d_hash, (size_t)n * 1024, hipMemcpyDeviceToHost, ctx->stream));
@@ -598,6 +612,23 @@ static int impl_preprocess_bgr(avd_ctx* ctx, const uint8_t* bgr, int mem, int n,
     ctx->last_n = n;
     ctx->rec_n = 0;
     return AVD_OK;
+}
+
+static int impl_preprocess_bgr(avd_ctx* ctx, const uint8_t* bgr, int mem, int n, int h, int w,
+                       int64_t row_stride, int64_t frame_stride,
+                       uint8_t* small320, uint8_t* hash1024, int64_t* lap_sum, int64_t* lap_sumsq)
+{
+    if (!ctx) return AVD_ERR_ARG;
+    if (!bgr && n > 0) { ctx->err = "null frame pointer"; return AVD_ERR_ARG; }
+    if (int e = check_geometry(ctx, n, h, w, row_stride, frame_stride)) return e;
+    return preprocess_to_host(ctx, bgr_clip(bgr, mem, n, h, w, row_stride, frame_stride), small320, hash1024, lap_sum, lap_sumsq);
+}
+
+static int impl_preprocess_nv12(avd_ctx* ctx, const avd_clip& k, uint8_t* small320, uint8_t* hash1024, int64_t* lap_sum, int64_t* lap_sumsq)
+{
+    if (!ctx) return AVD_ERR_ARG;
+    if (int e = check_nv12(ctx, k)) return e;
+    return preprocess_to_host(ctx, k, small320, hash1024, lap_sum, lap_sumsq);
 }
 
 static int impl_farneback_pairs(avd_ctx* ctx, const uint8_t* small320, int mem, int n,
@@ -626,37 +657,6 @@ static int impl_farneback_pairs(avd_ctx* ctx, const uint8_t* small320, int mem, 
 // stage does not care where a 320 x 320 frame came from: it runs ONCE over all N - 1 consecutive pairs of the concatenation
 // (the one pair per clip boundary it computes in vain is ignored by k_records), so K short clips cost one launch sequence
 // over all their pairs instead of K sequences that each leave most of the chip idle.
-struct Nv12Arg {
-    const uint8_t *y, *uv;
-    int64_t y_row, uv_row, y_frame, uv_frame;
-};
-
-static int check_nv12(avd_ctx* ctx, const Nv12Arg& a, int n, int h, int w)
-{
-    if (n < 0 || h <= 0 || w <= 0 || h > 16384 || w > 16384) { ctx->err = "bad frame geometry"; return AVD_ERR_ARG; }
-    if ((h | w) & 1) { ctx->err = "NV12 needs even width and height"; return AVD_ERR_UNSUPPORTED; }
-    if (h < AVD_HASH || w < AVD_HASH) { ctx->err = "frame smaller than 32x32: INTER_AREA upscaling is not on the path"; return AVD_ERR_UNSUPPORTED; }
-    if ((!a.y || !a.uv) && n > 0) { ctx->err = "null plane pointer"; return AVD_ERR_ARG; }
-    if (a.y_row < w || a.uv_row < w || (n > 1 && (a.y_frame < a.y_row * (h - 1) + w || a.uv_frame < a.uv_row * (h / 2 - 1) + w))) {
-        ctx->err = "strides smaller than the planes"; return AVD_ERR_ARG;
-    }
-    return 0;
-}
-
-static size_t clip_stage_bytes(const avd_clip& c, size_t* chroma_off)
-{
-    if (c.mem != AVD_MEM_HOST || c.n <= 0) { if (chroma_off) *chroma_off = 0; return 0; }
-    if (!c.uv) {
-        if (chroma_off) *chroma_off = 0;
-        return ((size_t)c.frame_stride * (c.n - 1) + (size_t)c.row_stride * (c.h - 1) + (size_t)c.w * 3 + 255) / 256 * 256;
-    }
-    const size_t ybytes = (size_t)c.frame_stride * (c.n - 1) + (size_t)c.row_stride * (c.h - 1) + (size_t)c.w;
-    const size_t cbytes = (size_t)c.uv_frame_stride * (c.n - 1) + (size_t)c.uv_row_stride * (c.h / 2 - 1) + (size_t)c.w;
-    const size_t coff = (ybytes + 255) / 256 * 256;
-    if (chroma_off) *chroma_off = coff;
-    return (coff + cbytes + 255) / 256 * 256;
-}
-
 static int impl_analyze_batch_async(avd_ctx* ctx, const avd_clip* clips, int nclips, avd_frame_record* records)
 {
     if (!ctx) return AVD_ERR_ARG;
@@ -667,8 +667,7 @@ static int impl_analyze_batch_async(avd_ctx* ctx, const avd_clip* clips, int ncl
         if (k.mem != AVD_MEM_HOST && k.mem != AVD_MEM_DEVICE) { ctx->err = "mem must be AVD_MEM_HOST or AVD_MEM_DEVICE"; return AVD_ERR_ARG; }
         if (!k.data && k.n > 0) { ctx->err = "null frame pointer"; return AVD_ERR_ARG; }
         if (k.uv) {
-            const Nv12Arg a{k.data, k.uv, k.row_stride, k.uv_row_stride, k.frame_stride, k.uv_frame_stride};
-            if (int e = check_nv12(ctx, a, k.n, k.h, k.w)) return e;
+            if (int e = check_nv12(ctx, k)) return e;
         } else if (int e = check_geometry(ctx, k.n, k.h, k.w, k.row_stride, k.frame_stride)) return e;
         total += k.n;
     }
@@ -686,16 +685,12 @@ static int impl_analyze_batch_async(avd_ctx* ctx, const avd_clip* clips, int ncl
         if (int e = avd_ws_geometry(ctx, k.h, k.w)) return e;
         rowbuf_elems += rowbuf_elems_for(ws, k.n);
         lappart_elems += lappart_elems_for(ws, k.n);
-        stage_bytes += clip_stage_bytes(k, nullptr);
+        stage_bytes += clip_stage(k).total;
     }
     if (int e = avd_ws_reserve_frames(ctx, n, rowbuf_elems, lappart_elems)) return e;
     if (int e = avd_ws_reserve_fb(ctx, n)) return e;
-    if (ws.stage_bytes < stage_bytes) {
-        ws.stage_bytes = 0;
-        if (int e = dev_alloc(ctx, ws.d_stage, stage_bytes)) return e;
-        ws.stage_bytes = stage_bytes;
-    }
-    // pass 2: per clip, stage (host input) -> fused full-resolution kernel -> hash / Hamming, at the clip's offsets
+    if (int e = ws.d_stage.reserve(ctx, stage_bytes)) return e;
+    // pass 2: per clip, stage (host input) -> fused full-resolution kernel -> hash, at the clip's offsets
     ctx->kmark_used = 0;
     // profiling only: an empty launch in front of the first mark, so that the first region is the first kernel and not the queue's wake-up from idle as well
     if (ctx->profiling) hipLaunchKernelGGL(k_wake, dim3(1), dim3(64), 0, ctx->stream);
@@ -709,36 +704,11 @@ static int impl_analyze_batch_async(avd_ctx* ctx, const avd_clip* clips, int ncl
         ws.f0 = f0; ws.rowbuf_off = rb; ws.lappart_off = lp;
         ws.h_clipstart[f0] = 1;
         for (int i = 1; i < k.n; i++) ws.h_clipstart[f0 + i] = 0;
-        size_t coff = 0;
-        const size_t sb = clip_stage_bytes(k, &coff);
-        const uint8_t* d_in = k.data;
-        const uint8_t* d_uv = k.uv;
         kmark(ctx, AVD_K_PREPROCESS);
-        if (k.mem == AVD_MEM_HOST) {
-            uint8_t* dst = ws.d_stage + st;
-            if (!k.uv) {
-                const size_t bytes = (size_t)k.frame_stride * (k.n - 1) + (size_t)k.row_stride * (k.h - 1) + (size_t)k.w * 3;
-                HIP_TRY(ctx, hipMemcpyAsync(dst, k.data, bytes, hipMemcpyHostToDevice, ctx->stream));
-            } else {
-                const size_t ybytes = (size_t)k.frame_stride * (k.n - 1) + (size_t)k.row_stride * (k.h - 1) + (size_t)k.w;
-                const size_t cbytes = (size_t)k.uv_frame_stride * (k.n - 1) + (size_t)k.uv_row_stride * (k.h / 2 - 1) + (size_t)k.w;
-                HIP_TRY(ctx, hipMemcpyAsync(dst, k.data, ybytes, hipMemcpyHostToDevice, ctx->stream));
-                HIP_TRY(ctx, hipMemcpyAsync(dst + coff, k.uv, cbytes, hipMemcpyHostToDevice, ctx->stream));
-                d_uv = dst + coff;
-            }
-            d_in = dst;
-            st += sb;
-        }
-        if (!k.uv) {
-            if (int e = launch_preprocess(ctx, d_in, k.n, k.h, k.w, k.row_stride, k.frame_stride)) return e;
-        } else {
-            Nv12Params nv{};
-            nv.uv = d_uv; nv.uv_row_stride = k.uv_row_stride; nv.uv_frame_stride = k.uv_frame_stride;
-            build_yuv_consts(nv.k);
-            if (int e = launch_preprocess_nv12(ctx, d_in, nv, k.n, k.h, k.w, k.row_stride, k.frame_stride)) return e;
-        }
+        if (int e = preprocess_clip(ctx, k, st)) return e;
+        st += clip_stage(k).total;
         kmark(ctx, AVD_K_HASH);
-        if (int e = launch_hash(ctx, k.n, false)) return e;
+        if (int e = launch_hash(ctx, k.n)) return e;
         f0 += k.n;
         rb += rowbuf_elems_for(ws, k.n);
         lp += lappart_elems_for(ws, k.n);
@@ -783,71 +753,16 @@ static int impl_analyze_frames_async(avd_ctx* ctx, const uint8_t* bgr, int mem, 
 {
     if (!ctx) return AVD_ERR_ARG;
     if ((!bgr || !records) && n > 0) { ctx->err = "null pointer"; return AVD_ERR_ARG; }
-    avd_clip k{};
-    k.data = bgr; k.uv = nullptr; k.mem = mem; k.n = n; k.h = h; k.w = w;
-    k.row_stride = row_stride; k.frame_stride = frame_stride;
+    const avd_clip k = bgr_clip(bgr, mem, n, h, w, row_stride, frame_stride);
     return impl_analyze_batch_async(ctx, &k, 1, records);
 }
 
-static int impl_analyze_frames_nv12_async(avd_ctx* ctx, const Nv12Arg& a, int mem, int n, int h, int w, avd_frame_record* records)
+static int impl_analyze_frames_nv12_async(avd_ctx* ctx, const avd_clip& k, avd_frame_record* records)
 {
     if (!ctx) return AVD_ERR_ARG;
-    if (!records && n > 0) { ctx->err = "null pointer"; return AVD_ERR_ARG; }
-    if (int e = check_nv12(ctx, a, n, h, w)) return e;
-    avd_clip k{};
-    k.data = a.y; k.uv = a.uv; k.mem = mem; k.n = n; k.h = h; k.w = w;
-    k.row_stride = a.y_row; k.frame_stride = a.y_frame; k.uv_row_stride = a.uv_row; k.uv_frame_stride = a.uv_frame;
+    if (!records && k.n > 0) { ctx->err = "null pointer"; return AVD_ERR_ARG; }
+    if (int e = check_nv12(ctx, k)) return e;
     return impl_analyze_batch_async(ctx, &k, 1, records);
-}
-
-// host planes are staged back to back (the chroma plane on a 256-byte boundary); device planes are used in place
-static int stage_nv12(avd_ctx* ctx, const Nv12Arg& a, int mem, int n, int h, int w, const uint8_t** d_y, Nv12Params* nv)
-{
-    nv->uv_row_stride = a.uv_row; nv->uv_frame_stride = a.uv_frame;
-    build_yuv_consts(nv->k);
-    if (mem == AVD_MEM_DEVICE) { *d_y = a.y; nv->uv = a.uv; return 0; }
-    if (mem != AVD_MEM_HOST) { ctx->err = "mem must be AVD_MEM_HOST or AVD_MEM_DEVICE"; return AVD_ERR_ARG; }
-    const size_t ybytes = (size_t)a.y_frame * (n - 1) + (size_t)a.y_row * (h - 1) + (size_t)w;
-    const size_t cbytes = (size_t)a.uv_frame * (n - 1) + (size_t)a.uv_row * (h / 2 - 1) + (size_t)w;
-    const size_t coff = (ybytes + 255) / 256 * 256;
-    Workspace& ws = ctx->ws;
-    if (ws.stage_bytes < coff + cbytes) {
-        ws.stage_bytes = 0;
-        if (int e = dev_alloc(ctx, ws.d_stage, coff + cbytes)) return e;
-        ws.stage_bytes = coff + cbytes;
-    }
-    HIP_TRY(ctx, hipMemcpyAsync(ws.d_stage, a.y, ybytes, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(ws.d_stage + coff, a.uv, cbytes, hipMemcpyHostToDevice, ctx->stream));
-    *d_y = ws.d_stage; nv->uv = ws.d_stage + coff;
-    return 0;
-}
-
-static int impl_preprocess_nv12(avd_ctx* ctx, const Nv12Arg& a, int mem, int n, int h, int w,
-                                uint8_t* small320, uint8_t* hash1024, int64_t* lap_sum, int64_t* lap_sumsq)
-{
-    if (!ctx) return AVD_ERR_ARG;
-    if (int e = check_nv12(ctx, a, n, h, w)) return e;
-    if (n == 0) return AVD_OK;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (int e = avd_ws_reserve(ctx, n, h, w)) return e;
-    const uint8_t* d_y = nullptr;
-    Nv12Params nv{};
-    if (int e = stage_nv12(ctx, a, mem, n, h, w, &d_y, &nv)) return e;
-    if (int e = launch_preprocess_nv12(ctx, d_y, nv, n, h, w, a.y_row, a.y_frame)) return e;
-    if (int e = launch_hash(ctx, n)) return e;
-    Workspace& ws = ctx->ws;
-    std::vector<unsigned long long> lap((size_t)n * 2);
-    if (small320) HIP_TRY(ctx, hipMemcpyAsync(small320, ws.d_small, (size_t)n * AVD_NPIX, hipMemcpyDeviceToHost, ctx->stream));
-    if (hash1024) HIP_TRY(ctx, hipMemcpyAsync(hash1024, ws.d_hash, (size_t)n * 1024, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(lap.data(), ws.d_lap, sizeof(unsigned long long) * 2 * n, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    for (int f = 0; f < n; f++) {
-        if (lap_sum) lap_sum[f] = (int64_t)lap[2 * f];
-        if (lap_sumsq) lap_sumsq[f] = (int64_t)lap[2 * f + 1];
-    }
-    ctx->last_n = n;
-    ctx->rec_n = 0;
-    return AVD_OK;
 }
 
 static int impl_synchronize(avd_ctx* ctx)
@@ -895,7 +810,7 @@ static int impl_synchronize(avd_ctx* ctx)
             float ms = 0.f;
             if (hipEventElapsedTime(&ms, ctx->stage_ev[i], ctx->stage_ev[i + 1]) == hipSuccess) ctx->stage_ms[i] = ms;
         }
-        // 4 / 5: mean duration of one k_uv<320> / k_hscan<320> launch (first segment of the last chunk)
+        // 4 / 5: mean duration of one k_uv<320> / k_hscan<320> launch (the last chunk)
         float sum[2] = {0.f, 0.f}; int cnt[2] = {0, 0};
         for (int i = 0; i + 1 < ctx->kern_ev_used; i += 2) {     // recorded by blur_iteration<320> of the drained call
             float ms = 0.f;
@@ -1002,7 +917,7 @@ static int impl_release_workspace(avd_ctx* ctx)
     if (!ctx) return AVD_ERR_ARG;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (int e = impl_synchronize(ctx)) return e;
-    free_ws(ctx->ws, true);
+    ctx->ws = Workspace{};                                  // the uploaded weights (ctx->weights) are state and stay
     ctx->rec_n = 0;
     return AVD_OK;
 }
@@ -1054,6 +969,21 @@ static int impl_get_option(avd_ctx* ctx, const char* name, int* value)
     return AVD_ERR_ARG;
 }
 
+// Timing of the extensions: `reps` repetitions of `launch` between ev0 and ev1 on the context's stream; *out_ms = mean time of one
+template <typename F>
+static int time_reps(avd_ctx* ctx, int reps, F&& launch, float* out_ms)
+{
+    HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+    for (int r = 0; r < reps; r++)
+        if (int e = launch()) return e;
+    HIP_TRY(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+    HIP_TRY(ctx, hipEventSynchronize(ctx->ev1));
+    float ms = 0.f;
+    HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
+    *out_ms = ms / reps;
+    return 0;
+}
+
 // ---- CNN extension (avd_cnn.hip; never part of ai_score) ---------------------------------------------------------
 static int impl_cnn_set_weights(avd_ctx* ctx, const uint16_t* w, size_t n_w, const float* b, size_t n_b)
 {
@@ -1074,28 +1004,23 @@ static int impl_cnn_forward(avd_ctx* ctx, const uint8_t* bgr, int mem, int n, in
     if (n == 0) return AVD_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     Workspace& ws = ctx->ws;
-    if (!ws.d_cnn_w) { ctx->err = "avd_cnn_set_weights has not been called"; return AVD_ERR_ARG; }
+    if (!ctx->weights.d_cnn_w) { ctx->err = "avd_cnn_set_weights has not been called"; return AVD_ERR_ARG; }
     // frames per forward pass: bounds the activation scratch (4 x 1.6 MB per frame); avd_set_option "cnn_chunk", 1 ... 1024
     // (32-bit byte offsets inside an activation); the late stages fill the chip better with more frames per pass
     const int kChunk = ctx->cnn_chunk;
     if (int e = cnn_reserve(ctx, std::min(n, kChunk))) return e;
     const uint8_t* d_bgr = nullptr;
-    const size_t bytes = (size_t)frame_stride * (n - 1) + (size_t)row_stride * (h - 1) + (size_t)w * 3;
-    if (int e = stage_input(ctx, bgr, mem, bytes, &d_bgr)) return e;
+    if (int e = stage_input(ctx, bgr, mem, plane_span(frame_stride, n, row_stride, h, (size_t)w * 3), &d_bgr)) return e;
     float total_ms = 0.f;
     for (int f0 = 0; f0 < n; f0 += kChunk) {
         const int m = std::min(kChunk, n - f0);
         const uint8_t* src = d_bgr + (size_t)frame_stride * f0;
-        if (int e = launch_cnn_forward(ctx, src, m, h, w, row_stride, frame_stride)) return e;
+        auto forward = [&] { return launch_cnn_forward(ctx, src, m, h, w, row_stride, frame_stride); };
+        if (int e = forward()) return e;
         if (reps > 0 && forward_ms) {
-            HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-            for (int r = 0; r < reps; r++)
-                if (int e = launch_cnn_forward(ctx, src, m, h, w, row_stride, frame_stride)) return e;
-            HIP_TRY(ctx, hipEventRecord(ctx->ev1, ctx->stream));
-            HIP_TRY(ctx, hipEventSynchronize(ctx->ev1));
             float ms = 0.f;
-            HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
-            total_ms += ms / reps;
+            if (int e = time_reps(ctx, reps, forward, &ms)) return e;
+            total_ms += ms;
         }
         // the logits buffer is reused by the next chunk: the copy is ordered before it on the same stream
         HIP_TRY(ctx, hipMemcpyAsync(logits + (size_t)f0 * 1000, ws.d_cnn_logits, sizeof(float) * (size_t)m * 1000, hipMemcpyDeviceToHost, ctx->stream));
@@ -1110,15 +1035,15 @@ static int impl_vit_set_weights(avd_ctx* ctx, const uint16_t* w_bf16, const floa
 {
     if (!ctx || !w_bf16) return AVD_ERR_ARG;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    Workspace& ws = ctx->ws;
-    if (!ws.d_vit_w) if (int e = dev_alloc(ctx, ws.d_vit_w, (size_t)768 * 768)) return e;
-    if (!ws.d_vit_bias) if (int e = dev_alloc(ctx, ws.d_vit_bias, (size_t)768)) return e;
+    Weights& wt = ctx->weights;
+    if (int e = wt.d_vit_w.reserve(ctx, (size_t)768 * 768)) return e;
+    if (int e = wt.d_vit_bias.reserve(ctx, (size_t)768)) return e;
     // the GEMM reads its operands in 1-KiB blocks (avd_vit.hip): re-tile the row-major weight once, here
     std::vector<uint16_t> blocked((size_t)768 * 768);
     gemm_block_operand(w_bf16, blocked.data(), 768, 768);
-    HIP_TRY(ctx, hipMemcpyAsync(ws.d_vit_w, blocked.data(), sizeof(uint16_t) * 768 * 768, hipMemcpyHostToDevice, ctx->stream));
-    if (bias) HIP_TRY(ctx, hipMemcpyAsync(ws.d_vit_bias, bias, sizeof(float) * 768, hipMemcpyHostToDevice, ctx->stream));
-    ws.vit_has_bias = bias != nullptr;
+    HIP_TRY(ctx, hipMemcpyAsync(wt.d_vit_w, blocked.data(), sizeof(uint16_t) * 768 * 768, hipMemcpyHostToDevice, ctx->stream));
+    if (bias) HIP_TRY(ctx, hipMemcpyAsync(wt.d_vit_bias, bias, sizeof(float) * 768, hipMemcpyHostToDevice, ctx->stream));
+    wt.vit_has_bias = bias != nullptr;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return AVD_OK;
 }
@@ -1133,40 +1058,30 @@ static int impl_vit_patch_embed(avd_ctx* ctx, const uint8_t* bgr, int mem, int n
     if (n == 0) return AVD_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     Workspace& ws = ctx->ws;
-    if (!ws.d_vit_w) { ctx->err = "avd_vit_set_weights has not been called"; return AVD_ERR_ARG; }
+    const Weights& wt = ctx->weights;
+    if (!wt.d_vit_w) { ctx->err = "avd_vit_set_weights has not been called"; return AVD_ERR_ARG; }
     const size_t m = (size_t)n * 196;
     const size_t m_pad = (m + kGemmRowPad - 1) / kGemmRowPad * kGemmRowPad;   // the persistent GEMM reads whole 256-row tiles of A
-    if (ws.vit_patch_elems < m_pad * 768) {
-        ws.vit_patch_elems = 0;                               // not valid again until the buffer exists
-        if (int e = dev_alloc(ctx, ws.d_vit_patches, m_pad * 768)) return e;
-        HIP_TRY(ctx, hipMemsetAsync(ws.d_vit_patches, 0, m_pad * 768 * sizeof(uint16_t), ctx->stream));
-        ws.vit_patch_elems = m_pad * 768;
+    if (ws.d_vit_patches.cap < m_pad * 768) {
+        // a regrown buffer is zero-filled (the rows that pad the last tile are read, never written) -- or does not exist
+        if (int e = ws.d_vit_patches.reserve(ctx, m_pad * 768)) return e;
+        auto zero_fill = [&]() -> int { HIP_TRY(ctx, hipMemsetAsync(ws.d_vit_patches, 0, m_pad * 768 * sizeof(uint16_t), ctx->stream)); return 0; };
+        if (int e = zero_fill()) { ws.d_vit_patches.reset(); return e; }
     }
     void* d_tok = tokens;
     const size_t esz = tokens_bf16 ? sizeof(uint16_t) : sizeof(float);
     if (tokens_mem == AVD_MEM_HOST) {
-        if (ws.vit_token_elems < m * 768) {
-            ws.vit_token_elems = 0;
-            if (int e = dev_alloc(ctx, ws.d_vit_tokens, m * 768)) return e;
-            ws.vit_token_elems = m * 768;
-        }
+        if (int e = ws.d_vit_tokens.reserve(ctx, m * 768)) return e;
         d_tok = ws.d_vit_tokens;
     }
     const uint8_t* d_bgr = nullptr;
-    const size_t bytes = (size_t)frame_stride * (n - 1) + (size_t)row_stride * (h - 1) + (size_t)w * 3;
-    if (int e = stage_input(ctx, bgr, mem, bytes, &d_bgr)) return e;
-    const float* d_bias = ws.vit_has_bias ? ws.d_vit_bias : nullptr;
-    if (int e = launch_vit_patch_embed(ctx, d_bgr, n, h, w, row_stride, frame_stride, ws.d_vit_w, d_bias, d_tok, tokens_bf16, ws.d_vit_patches)) return e;
+    if (int e = stage_input(ctx, bgr, mem, plane_span(frame_stride, n, row_stride, h, (size_t)w * 3), &d_bgr)) return e;
+    const float* d_bias = wt.vit_has_bias ? wt.d_vit_bias : nullptr;
+    if (int e = launch_vit_patch_embed(ctx, d_bgr, n, h, w, row_stride, frame_stride, wt.d_vit_w, d_bias, d_tok, tokens_bf16, ws.d_vit_patches)) return e;
     if (reps > 0 && gemm_ms) {
-        // the GEMM alone, `reps` launches between two events on the context's stream (the patches stay resident)
-        HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-        for (int r = 0; r < reps; r++)
-            if (int e = launch_gemm_bf16_nt(ctx, ws.d_vit_patches, ws.d_vit_w, d_bias, d_tok, tokens_bf16, (int)m, 768, 768)) return e;
-        HIP_TRY(ctx, hipEventRecord(ctx->ev1, ctx->stream));
-        HIP_TRY(ctx, hipEventSynchronize(ctx->ev1));
-        float ms = 0.f;
-        HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
-        *gemm_ms = ms / reps;
+        // the GEMM alone (the patches stay resident)
+        auto gemm = [&] { return launch_gemm_bf16_nt(ctx, ws.d_vit_patches, wt.d_vit_w, d_bias, d_tok, tokens_bf16, (int)m, 768, 768); };
+        if (int e = time_reps(ctx, reps, gemm, gemm_ms)) return e;
     }
     if (tokens_mem == AVD_MEM_HOST)
         HIP_TRY(ctx, hipMemcpyAsync(tokens, d_tok, esz * m * 768, hipMemcpyDeviceToHost, ctx->stream));
@@ -1193,11 +1108,7 @@ static int impl_rowop(avd_ctx* ctx, int op, const void* x, int mem, int bf16, in
     const size_t x_bytes = (bytes + 255) / 256 * 256;
     const bool host = mem == AVD_MEM_HOST;
     const size_t want = host ? gb_f + (x_bytes + bytes + 3) / 4 : gb_f;
-    if (ws.vit_token_elems < want) {
-        ws.vit_token_elems = 0;
-        if (int e = dev_alloc(ctx, ws.d_vit_tokens, want)) return e;
-        ws.vit_token_elems = want;
-    }
+    if (int e = ws.d_vit_tokens.reserve(ctx, want)) return e;
     float* d_gb = ws.d_vit_tokens;                        // gamma | beta first (16-byte aligned), then x, then y
     char* d_x = (char*)x;
     char* d_y = (char*)y;
@@ -1215,16 +1126,8 @@ static int impl_rowop(avd_ctx* ctx, int op, const void* x, int mem, int bf16, in
                        : launch_softmax(ctx, (const float*)d_x, (float*)d_y, rows, cols);
     };
     if (int e = run()) return e;
-    if (reps > 0 && ms) {
-        HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-        for (int r = 0; r < reps; r++)
-            if (int e = run()) return e;
-        HIP_TRY(ctx, hipEventRecord(ctx->ev1, ctx->stream));
-        HIP_TRY(ctx, hipEventSynchronize(ctx->ev1));
-        float t = 0.f;
-        HIP_TRY(ctx, hipEventElapsedTime(&t, ctx->ev0, ctx->ev1));
-        *ms = t / reps;
-    }
+    if (reps > 0 && ms)
+        if (int e = time_reps(ctx, reps, run, ms)) return e;
     if (host) HIP_TRY(ctx, hipMemcpyAsync(y, d_y, bytes, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return AVD_OK;
@@ -1243,11 +1146,7 @@ static int impl_audio_features(avd_ctx* ctx, const float* wav, int mem, int64_t 
     Workspace& ws = ctx->ws;
     const uint8_t* d_wav = nullptr;
     if (int e = stage_input(ctx, reinterpret_cast<const uint8_t*>(wav), mem, (size_t)n * sizeof(float), &d_wav)) return e;
-    if (ws.audio_out_elems < (size_t)nwin) {
-        ws.audio_out_elems = 0;
-        if (int e = dev_alloc(ctx, ws.d_audio_out, (size_t)nwin)) return e;
-        ws.audio_out_elems = (size_t)nwin;
-    }
+    if (int e = ws.d_audio_out.reserve(ctx, (size_t)nwin)) return e;
     if (int e = launch_audio_features(ctx, reinterpret_cast<const float*>(d_wav), n, win, ws.d_audio_out, nwin)) return e;
     HIP_TRY(ctx, hipMemcpyAsync(windows, ws.d_audio_out, sizeof(avd_audio_window) * nwin, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -1340,25 +1239,25 @@ int avd_preprocess_nv12(avd_ctx* ctx, const uint8_t* y, const uint8_t* uv, int m
                         int64_t uv_row_stride, int64_t y_frame_stride, int64_t uv_frame_stride, uint8_t* small320,
                         uint8_t* hash1024, int64_t* lap_sum, int64_t* lap_sumsq)
 {
-    const Nv12Arg a{y, uv, y_row_stride, uv_row_stride, y_frame_stride, uv_frame_stride};
-    return guarded(ctx, [&] { return impl_preprocess_nv12(ctx, a, mem, n, h, w, small320, hash1024, lap_sum, lap_sumsq); });
+    const avd_clip k = nv12_clip(y, uv, mem, n, h, w, y_row_stride, uv_row_stride, y_frame_stride, uv_frame_stride);
+    return guarded(ctx, [&] { return impl_preprocess_nv12(ctx, k, small320, hash1024, lap_sum, lap_sumsq); });
 }
 
 int avd_analyze_frames_nv12_async(avd_ctx* ctx, const uint8_t* y, const uint8_t* uv, int mem, int n, int h, int w,
                                   int64_t y_row_stride, int64_t uv_row_stride, int64_t y_frame_stride,
                                   int64_t uv_frame_stride, avd_frame_record* records)
 {
-    const Nv12Arg a{y, uv, y_row_stride, uv_row_stride, y_frame_stride, uv_frame_stride};
-    return guarded(ctx, [&] { return impl_analyze_frames_nv12_async(ctx, a, mem, n, h, w, records); });
+    const avd_clip k = nv12_clip(y, uv, mem, n, h, w, y_row_stride, uv_row_stride, y_frame_stride, uv_frame_stride);
+    return guarded(ctx, [&] { return impl_analyze_frames_nv12_async(ctx, k, records); });
 }
 
 int avd_analyze_frames_nv12(avd_ctx* ctx, const uint8_t* y, const uint8_t* uv, int mem, int n, int h, int w,
                             int64_t y_row_stride, int64_t uv_row_stride, int64_t y_frame_stride, int64_t uv_frame_stride,
                             avd_frame_record* records)
 {
-    const Nv12Arg a{y, uv, y_row_stride, uv_row_stride, y_frame_stride, uv_frame_stride};
+    const avd_clip k = nv12_clip(y, uv, mem, n, h, w, y_row_stride, uv_row_stride, y_frame_stride, uv_frame_stride);
     return guarded(ctx, [&] {
-        const int rc = impl_analyze_frames_nv12_async(ctx, a, mem, n, h, w, records);
+        const int rc = impl_analyze_frames_nv12_async(ctx, k, records);
         return rc ? rc : impl_synchronize(ctx);
     });
 }

@@ -1007,12 +1007,12 @@ void cnn_param_counts(size_t* n_w, size_t* n_b) { *n_w = net().n_w; *n_b = net()
 int cnn_set_weights(avd_ctx* ctx, const uint16_t* w, const float* b)
 {
     const Net& nt = net();
-    Workspace& ws = ctx->ws;
+    Weights& wt = ctx->weights;
     size_t blocked_total = 0;
     for (const Layer& l : nt.convs) blocked_total += (size_t)l.cout * k_padded(l);
     std::vector<uint16_t> host(blocked_total + (size_t)1000 * 2048), tmp;
     size_t off = 0;
-    ws.cnn_w_off.clear();
+    wt.cnn_w_off.clear();
     for (const Layer& l : nt.convs) {
         const int K = k_padded(l), kin = l.ksize * l.ksize * l.cin;
         const uint16_t* src = w + l.w_off;
@@ -1025,15 +1025,15 @@ int cnn_set_weights(avd_ctx* ctx, const uint16_t* w, const float* b)
             src = tmp.data();
         }
         gemm_block_operand(src, host.data() + off, l.cout, K);
-        ws.cnn_w_off.push_back(off);
+        wt.cnn_w_off.push_back(off);
         off += (size_t)l.cout * K;
     }
-    ws.cnn_fc_off = off;
+    wt.cnn_fc_off = off;
     for (size_t i = 0; i < (size_t)1000 * 2048; i++) host[off + i] = w[nt.fc_w + i];
-    if (!ws.d_cnn_w) if (int e = dev_alloc(ctx, ws.d_cnn_w, host.size())) return e;
-    if (!ws.d_cnn_b) if (int e = dev_alloc(ctx, ws.d_cnn_b, nt.n_b)) return e;
-    HIP_TRY(ctx, hipMemcpyAsync(ws.d_cnn_w, host.data(), host.size() * sizeof(uint16_t), hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(ws.d_cnn_b, b, nt.n_b * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    if (int e = wt.d_cnn_w.reserve(ctx, host.size())) return e;
+    if (int e = wt.d_cnn_b.reserve(ctx, nt.n_b)) return e;
+    HIP_TRY(ctx, hipMemcpyAsync(wt.d_cnn_w, host.data(), host.size() * sizeof(uint16_t), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(wt.d_cnn_b, b, nt.n_b * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return AVD_OK;
 }
@@ -1046,13 +1046,13 @@ int cnn_reserve(avd_ctx* ctx, int n)
     ws.cnn_frames = 0;                                                   // not valid again until every buffer below exists
     const size_t act = act_elems((size_t)n * 112 * 112, 64);             // the largest activation (= n * 56 * 56 x 256)
     for (int i = 0; i < 4; i++) {
-        if (int e = dev_alloc(ctx, ws.d_cnn_act[i], act)) return e;
+        if (int e = ws.d_cnn_act[i].reserve(ctx, act)) return e;
         HIP_TRY(ctx, hipMemsetAsync(ws.d_cnn_act[i], 0, kZeroPage * sizeof(uint16_t), ctx->stream));
     }
-    if (int e = dev_alloc(ctx, ws.d_cnn_img, (size_t)n * kImgSide * kImgSide * 4)) return e;
+    if (int e = ws.d_cnn_img.reserve(ctx, (size_t)n * kImgSide * kImgSide * 4)) return e;
     HIP_TRY(ctx, hipMemsetAsync(ws.d_cnn_img, 0, (size_t)n * kImgSide * kImgSide * 4 * sizeof(uint16_t), ctx->stream));   // the zero border
-    if (int e = dev_alloc(ctx, ws.d_cnn_pool, (size_t)n * 2048)) return e;
-    if (int e = dev_alloc(ctx, ws.d_cnn_logits, (size_t)n * 1000)) return e;
+    if (int e = ws.d_cnn_pool.reserve(ctx, (size_t)n * 2048)) return e;
+    if (int e = ws.d_cnn_logits.reserve(ctx, (size_t)n * 1000)) return e;
     ws.cnn_frames = n;
     return AVD_OK;
 }
@@ -1062,11 +1062,12 @@ int launch_cnn_forward(avd_ctx* ctx, const uint8_t* d_bgr, int n, int h, int w, 
 {
     const Net& nt = net();
     Workspace& ws = ctx->ws;
+    const Weights& wt = ctx->weights;
     const int64_t px = (int64_t)n * kSide * kSide;
     hipLaunchKernelGGL(k_cnn_input, dim3((unsigned)((px + 255) / 256)), dim3(256), 0, ctx->stream, d_bgr, n, h, w, row_stride, frame_stride, ws.d_cnn_img);
     size_t li = 0;
-    auto wptr = [&](size_t i) { return ws.d_cnn_w + ws.cnn_w_off[i]; };
-    auto bptr = [&](size_t i) { return ws.d_cnn_b + nt.convs[i].b_off; };
+    auto wptr = [&](size_t i) { return wt.d_cnn_w + wt.cnn_w_off[i]; };
+    auto bptr = [&](size_t i) { return wt.d_cnn_b + nt.convs[i].b_off; };
     // the stem gathers straight from the bordered image (one half stage per kernel row)
     if (int e = launch_conv(ctx, ws.d_cnn_img, wptr(0), bptr(0), nullptr, ws.d_cnn_act[0], n, kSide, kSide, 3, 64, 7, 2, 1, true)) return e;
     li = 1;
@@ -1101,8 +1102,8 @@ int launch_cnn_forward(avd_ctx* ctx, const uint8_t* d_bgr, int n, int h, int w, 
         }
     }
     hipLaunchKernelGGL(k_avgpool, dim3((unsigned)((n * 256 + 255) / 256)), dim3(256), 0, ctx->stream, ws.d_cnn_act[cur], n, 49, 2048, ws.d_cnn_pool);
-    hipLaunchKernelGGL(k_linear, dim3((unsigned)(((n + 7) / 8 * 1000 + 3) / 4)), dim3(256), 0, ctx->stream, ws.d_cnn_pool, ws.d_cnn_w + ws.cnn_fc_off,
-                       ws.d_cnn_b + nt.fc_b, n, 1000, ws.d_cnn_logits);
+    hipLaunchKernelGGL(k_linear, dim3((unsigned)(((n + 7) / 8 * 1000 + 3) / 4)), dim3(256), 0, ctx->stream, ws.d_cnn_pool, wt.d_cnn_w + wt.cnn_fc_off,
+                       wt.d_cnn_b + nt.fc_b, n, 1000, ws.d_cnn_logits);
     HIP_TRY(ctx, hipGetLastError());
     return AVD_OK;
 }

@@ -83,7 +83,7 @@ void comm_destroy(avd_ctx* ctx)
 {
     std::string ignore;
     if (ctx->comm) { if (Rccl* r = rccl(ignore)) (void)r->destroy(ctx->comm); ctx->comm = nullptr; }
-    if (ctx->d_comm) { (void)hipFree(ctx->d_comm); ctx->d_comm = nullptr; ctx->comm_bytes = 0; }
+    ctx->d_comm.reset();
 }
 
 // every rank contributes `count` records; all = world * count records in rank order (host pointers)
@@ -96,13 +96,8 @@ int comm_allgather_records(avd_ctx* ctx, const avd_frame_record* local, int coun
     if (!r) return AVD_ERR_DEVICE;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const size_t mine = sizeof(avd_frame_record) * (size_t)count, total = mine * (size_t)ctx->comm_world;
-    if (ctx->comm_bytes < mine + total) {
-        if (ctx->d_comm) { (void)hipFree(ctx->d_comm); ctx->d_comm = nullptr; }
-        ctx->comm_bytes = 0;
-        if (hipMalloc(&ctx->d_comm, mine + total) != hipSuccess) { ctx->err = "hipMalloc (record exchange)"; return AVD_ERR_NOMEM; }
-        ctx->comm_bytes = mine + total;
-    }
-    char* d_send = static_cast<char*>(ctx->d_comm);
+    if (int e = ctx->d_comm.reserve(ctx, mine + total)) return e;
+    char* d_send = ctx->d_comm;
     char* d_recv = d_send + mine;
     HIP_TRY(ctx, hipMemcpyAsync(d_send, local, mine, hipMemcpyHostToDevice, ctx->stream));
     const int rc = r->allgather(d_send, d_recv, mine, /*ncclUint8*/ 1, ctx->comm, ctx->stream);
@@ -125,13 +120,8 @@ int comm_allgather_last_records(avd_ctx* ctx, int count, avd_frame_record* all)
     if (!r) return AVD_ERR_DEVICE;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const size_t mine = sizeof(avd_frame_record) * (size_t)count, total = mine * (size_t)ctx->comm_world;
-    if (ctx->comm_bytes < mine + total) {
-        if (ctx->d_comm) { (void)hipFree(ctx->d_comm); ctx->d_comm = nullptr; }
-        ctx->comm_bytes = 0;
-        if (hipMalloc(&ctx->d_comm, mine + total) != hipSuccess) { ctx->err = "hipMalloc (record exchange)"; return AVD_ERR_NOMEM; }
-        ctx->comm_bytes = mine + total;
-    }
-    char* d_recv = static_cast<char*>(ctx->d_comm) + mine;
+    if (int e = ctx->d_comm.reserve(ctx, mine + total)) return e;
+    char* d_recv = ctx->d_comm + mine;
     const int rc = r->allgather(ctx->ws.d_rec, d_recv, mine, /*ncclUint8*/ 1, ctx->comm, ctx->stream);
     if (rc) return fail(ctx, r, "ncclAllGather", rc);
     HIP_TRY(ctx, hipMemcpyAsync(all, d_recv, total, hipMemcpyDeviceToHost, ctx->stream));

@@ -1124,10 +1124,8 @@ __global__ void k_flow_interleave(const float* __restrict__ flow, float* __restr
     out[gid * 2 + 1] = flow[(p * 2 + 1) * AVD_NPIX + i];
 }
 
-// A segment = a run of consecutive pairs processed on one stream, with its own slice of the workspace
-// (frames [frame_off, ...) and pairs [pair_off, ...) of the chunk).  The library runs one segment per chunk:
-// splitting a clip over two streams did not pay (the level-0 kernels share the bandwidth, the latency-bound
-// levels are duplicated); keeping several CLIPS in flight on separate contexts is what fills the gaps.
+// The Farneback scratch as the launchers below see it: the buffers of the chunk in the workspace, on the context's stream.  The exact re-run
+// swaps in its own double intermediate (d_vs_rerun / d_vs0_rerun, indexed by position in its pair list) and never records kernel events.
 struct Seg {
     hipStream_t stream;
     const float* pyr[AVD_FB_LEVELS];
@@ -1136,30 +1134,27 @@ struct Seg {
     float* flow[AVD_FB_LEVELS];
     double *vs, *vs0;
     float *stats, *flow_il;
-    int* flags;                          // ill-posedness flags of the segment's pairs (fast mode)
+    int* flags;                          // ill-posedness flags of the chunk's pairs (fast mode)
     int* pairdiff;                       // [pair][kPairDiffTiles] "frame p differs from frame p + 1" per tile of the pyramid kernel's 160-px scale
     avd_ctx* prof;                       // non-null: record kernel events of the full-resolution blur launches
 };
 
-static Seg make_seg(avd_ctx* ctx, hipStream_t stream, int frame_off, int pair_off)
+static Seg make_seg(avd_ctx* ctx)
 {
     Workspace& ws = ctx->ws;
     Seg g{};
-    g.stream = stream;
+    g.stream = ctx->stream;
     for (int k = 0; k < AVD_FB_LEVELS; k++) {
-        const size_t plane = (size_t)(S >> k) * (S >> k);
-        g.pyr_w[k] = ws.d_pyr[k] + (size_t)frame_off * plane;
-        g.pyr[k] = g.pyr_w[k];
-        g.poly[k] = ws.d_poly[k] + (size_t)frame_off * 5 * plane;
-        g.flow[k] = ws.d_flow[k] + (size_t)pair_off * 2 * plane;
+        g.pyr[k] = g.pyr_w[k] = ws.d_pyr[k];
+        g.poly[k] = ws.d_poly[k];
+        g.flow[k] = ws.d_flow[k];
     }
-    g.prof = ctx->profiling && pair_off == 0 ? ctx : nullptr;
-    g.vs = ws.d_vs ? ws.d_vs + (size_t)pair_off * (5 * AVD_NPIX + 512) : nullptr;
-    g.vs0 = ws.d_vs0 ? ws.d_vs0 + (size_t)pair_off * 5 * S * 8 : nullptr;
-    g.stats = ws.d_stats + (size_t)pair_off * 2;
-    g.flags = ws.d_fbflags ? ws.d_fbflags + pair_off : nullptr;
-    g.pairdiff = ws.d_pairdiff ? ws.d_pairdiff + (size_t)pair_off * kPairDiffTiles : nullptr;
-    g.flow_il = ws.d_flow_il ? ws.d_flow_il + (size_t)pair_off * AVD_NPIX * 2 : nullptr;
+    g.prof = ctx->profiling ? ctx : nullptr;
+    g.vs = ws.d_vs; g.vs0 = ws.d_vs0;
+    g.stats = ws.d_stats;
+    g.flags = ws.d_fbflags;
+    g.pairdiff = ws.d_pairdiff;
+    g.flow_il = ws.no_flow_il ? nullptr : ws.d_flow_il;
     return g;
 }
 
@@ -1173,7 +1168,7 @@ inline void launch1d(void (*k)(A...), int64_t items, int block, hipStream_t s, A
 // Gaussian pyramid + polynomial expansion of n frames at all four scales: two launches
 void pyramid_and_polyexp(avd_ctx* ctx, const Seg& g, const uint8_t* d_small, int n)
 {
-    const FbConsts* C = (const FbConsts*)ctx->d_fbc;
+    const FbConsts* C = ctx->d_fbc;
     // ctx->fb_fold_blur (default 1): the 320-px scale's 3 x 3 blur is formed inside the polynomial expansion; the pyramid kernel then has no
     // 320-px tiles and pyr[0] is not written (avd_debug_copy "pyr0" is meaningful with the option off only)
     const bool fold = ctx->fb_fold_blur != 0;
@@ -1193,7 +1188,7 @@ void pyramid_and_polyexp(avd_ctx* ctx, const Seg& g, const uint8_t* d_small, int
 }
 
 // one FarnebackUpdateFlow_Blur iteration at level k: matrices from the current flow, box sums, solve
-// plist (may be null): the launches work on the pairs plist[0 .. np) of the segment; the double intermediate is indexed by position in the list
+// plist (may be null): the launches work on the pairs plist[0 .. np) of the chunk; the double intermediate is indexed by position in the list
 template <int W>
 void blur_iteration(const Seg& g, int k, int np, float* flow, const int* plist)
 {
@@ -1278,12 +1273,12 @@ int exact_level(avd_ctx* ctx, const Seg& g, int k, int np, float* flow, int fuse
 
 }  // namespace
 
-// All pairs (f, f+1), f in [0, n-1), of n resident 320x320 frames, on one stream, using the workspace
-// slice (frame_off, pair_off) of the current chunk.
-int launch_farneback(avd_ctx* ctx, hipStream_t stream, const uint8_t* d_small, int n, int frame_off, int pair_off)
+// All pairs (f, f+1), f in [0, n-1), of n resident 320x320 frames (one chunk), on the context's stream, into the Farneback scratch.
+int launch_farneback(avd_ctx* ctx, const uint8_t* d_small, int n)
 {
     if (n < 2) return 0;
-    const Seg g = make_seg(ctx, stream, frame_off, pair_off);
+    const Seg g = make_seg(ctx);
+    const hipStream_t stream = ctx->stream;
     if (g.prof) ctx->kern_ev_used = 0;
     const int np = n - 1;
     ctx->ws.mag_valid = ctx->fb_mode == 1;
@@ -1312,7 +1307,7 @@ int launch_farneback(avd_ctx* ctx, hipStream_t stream, const uint8_t* d_small, i
         if (fast) {
             // fast level kernel (avd_fbfast.hip): the flow ping-pongs between the level's two buffers, a = initial flow, results b, a, b
             float* a = g.flow[k];
-            float* b = ctx->ws.d_flow2[k] + (size_t)pair_off * 2 * plane;
+            float* b = ctx->ws.d_flow2[k];
             int* fl = ctx->fb_rerun ? g.flags : nullptr;
             const int* pd = ctx->fb_rerun ? g.pairdiff : nullptr;
             if (k == 0 && g.prof && g.prof->kern_ev_used < 12) (void)hipEventRecord(g.prof->kern_ev[g.prof->kern_ev_used++], stream);
@@ -1324,7 +1319,7 @@ int launch_farneback(avd_ctx* ctx, hipStream_t stream, const uint8_t* d_small, i
                 a = b;
             } else {
                 for (int it = 0; it < 3; it++) {
-                    float* mag = (k == 0 && it == 2) ? ctx->ws.d_mag + (size_t)pair_off * AVD_NPIX : nullptr;
+                    float* mag = (k == 0 && it == 2) ? ctx->ws.d_mag : nullptr;
                     const bool first_prev = prev_in && it == 0;
                     const int mode = !first_prev ? 0 : (fold_chain ? 1 : 2);
                     if (int e = launch_fb_fast(ctx, stream, w, g.poly[k], first_prev ? prev : a, b, a, mag, fl, pd, np, k == AVD_FB_LEVELS - 1 && it == 0, mode)) return e;
@@ -1351,23 +1346,21 @@ int launch_farneback(avd_ctx* ctx, hipStream_t stream, const uint8_t* d_small, i
 // 64-row bands: ~0.15 ms per level for one pair, where the fused kernel's single workgroup per pair takes 0.23 / 0.83 ms however few pairs there are),
 // beyond that the fused kernels (one workgroup per pair = the exact mode's own launches, its time for a clip of nothing but flagged pairs).
 // ctx->fb_rerun_fused (tuning / tests): level mask of the fused kernel for the few-pairs case, default 0xC (40 and 80 px).
-int launch_farneback_rerun(avd_ctx* ctx, hipStream_t stream, const int* h_list, int m, int pair_off, int np_chunk)
+int launch_farneback_rerun(avd_ctx* ctx, const int* h_list, int m, int np_chunk)
 {
     if (m <= 0) return 0;
     Workspace& ws = ctx->ws;
+    const hipStream_t stream = ctx->stream;
     if (m > ws.fb_cap) { ctx->err = "re-run list longer than the chunk"; return AVD_ERR_ARG; }
-    if (!ws.d_rlist) {
-        if (int e = dev_alloc(ctx, ws.d_rlist, (size_t)ws.fb_cap)) return e;
-        ws.rlist_cap = ws.fb_cap;
-    }
+    if (int e = ws.d_rlist.reserve(ctx, (size_t)ws.fb_cap)) return e;
     const bool few = m <= kRerunTwoKernelMax;
     const int fused_mask = few ? (ctx->fb_rerun_fused & 0xF) : 0xF;
-    if (fused_mask != 0xF && !ws.d_vs_rerun) {
-        if (int e = dev_alloc(ctx, ws.d_vs0_rerun, (size_t)kRerunTwoKernelMax * 5 * S * 8)) return e;
-        if (int e = dev_alloc(ctx, ws.d_vs_rerun, (size_t)kRerunTwoKernelMax * (5 * AVD_NPIX + 512))) return e;
+    if (fused_mask != 0xF) {
+        if (int e = ws.d_vs0_rerun.reserve(ctx, (size_t)kRerunTwoKernelMax * 5 * S * 8)) return e;
+        if (int e = ws.d_vs_rerun.reserve(ctx, (size_t)kRerunTwoKernelMax * (5 * AVD_NPIX + 512))) return e;
     }
     HIP_TRY(ctx, hipMemcpyAsync(ws.d_rlist, h_list, sizeof(int) * m, hipMemcpyHostToDevice, stream));
-    Seg g = make_seg(ctx, stream, 0, pair_off);
+    Seg g = make_seg(ctx);
     g.prof = nullptr;
     g.vs = ws.d_vs_rerun; g.vs0 = ws.d_vs0_rerun;         // indexed by position in the list
     const int* plist = ws.d_rlist;
@@ -1383,7 +1376,7 @@ int launch_farneback_rerun(avd_ctx* ctx, hipStream_t stream, const int* h_list, 
         }
         if (int e = exact_level(ctx, g, k, m, flow, fused_mask, plist)) return e;
     }
-    float* mg = ws.d_mag + (size_t)pair_off * AVD_NPIX;
+    float* mg = ws.d_mag;
     launch1d(k_mag, (int64_t)m * (AVD_NPIX / 4), 256, stream, (const float*)ws.flow_res[0], mg, (int64_t)m * (AVD_NPIX / 4), plist);
     hipLaunchKernelGGL(k_stats_pair, dim3(m), dim3(512), 0, stream, (const float*)mg, g.stats, plist);
     if (g.flow_il)                                        // the caller wants the dense flow (tests / debugging): interleave the chunk again
@@ -1392,13 +1385,14 @@ int launch_farneback_rerun(avd_ctx* ctx, hipStream_t stream, const int* h_list, 
     return 0;
 }
 
-int launch_flow_stats(avd_ctx* ctx, hipStream_t stream, int n, int frame_off, int pair_off)
+int launch_flow_stats(avd_ctx* ctx, int n)
 {
     if (n < 2) return 0;
-    const Seg g = make_seg(ctx, stream, frame_off, pair_off);
+    const Seg g = make_seg(ctx);
+    const hipStream_t stream = ctx->stream;
     const int np = n - 1;
     const float* fl = ctx->ws.flow_res[0] ? ctx->ws.flow_res[0] : g.flow[0];
-    float* mg = ctx->ws.d_mag + (size_t)pair_off * AVD_NPIX;
+    float* mg = ctx->ws.d_mag;
     kmark(ctx, AVD_K_STATS);
     if (!ctx->ws.mag_valid) launch1d(k_mag, (int64_t)np * (AVD_NPIX / 4), 256, stream, fl, mg, (int64_t)np * (AVD_NPIX / 4), (const int*)nullptr);
     hipLaunchKernelGGL(k_stats_pair, dim3(np), dim3(512), 0, stream, (const float*)mg, g.stats, (const int*)nullptr);

@@ -84,72 +84,108 @@ struct HashParams {
     int h;
 };
 
+// ---- owners of device and pinned host memory ------------------------------------------------
+// Move-only: pointer + capacity in elements, freed on destruction and on move-assignment.  Converts to its pointer, so
+// call sites read as they would with a raw one (ws.d_small + off, kernel arguments, null tests).
+struct avd_ctx;
+template <typename T, bool kPinned>
+struct Buf {
+    T* p = nullptr;
+    size_t cap = 0;                    // elements
+    Buf() = default;
+    Buf(const Buf&) = delete;
+    Buf& operator=(const Buf&) = delete;
+    Buf(Buf&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+    Buf& operator=(Buf&& o) noexcept
+    {
+        if (this != &o) { reset(); p = o.p; cap = o.cap; o.p = nullptr; o.cap = 0; }
+        return *this;
+    }
+    ~Buf() { reset(); }
+    void reset()
+    {
+        if (p) { if (kPinned) (void)hipHostFree(p); else (void)hipFree(p); }
+        p = nullptr; cap = 0;
+    }
+    // Grow-only: nothing happens while `count` elements fit.  Otherwise the old memory is freed and the buffer is EMPTY until the new
+    // allocation exists; a failure sets ctx->err, returns AVD_ERR_NOMEM and leaves it empty.
+    int reserve(avd_ctx* ctx, size_t count);
+    operator T*() const { return p; }
+};
+template <typename T> using DevBuf = Buf<T, false>;
+template <typename T> using PinBuf = Buf<T, true>;
+
 // Tables and band layout of one frame geometry.  A context keeps the last kGeomCache geometries (a mixed-resolution
 // stream alternates between a few sizes): switching between cached geometries allocates and frees nothing.
 constexpr int kGeomCache = 4;
 struct Geom {
     int h = 0, w = 0;
-    void* d_tables = nullptr; size_t tables_bytes = 0;
+    DevBuf<uint8_t> d_tables;
     PreParams pre{};
     HashParams hsh{};
     unsigned long long stamp = 0;      // last use (LRU eviction)
 };
 
+// Scratch of a context.  Everything here can be given back (avd_release_workspace resets the struct) and is re-reserved on demand.
 struct Workspace {
-    // geometry of the clip being enqueued (a copy of its cache entry) and the capacities of the per-frame buffers, which
-    // only ever grow: cap_n frames, rowbuf_cap floats, lappart_cap slots
-    int cap_n = 0, h = 0, w = 0;
-    size_t rowbuf_cap = 0, lappart_cap = 0;
+    // capacities of the per-frame buffers, which only ever grow: cap_n frames validates every [n] buffer below at once (0 until all exist)
+    int cap_n = 0;
     Geom geoms[kGeomCache];
     unsigned long long geom_clock = 0;
     // position of the clip being enqueued inside the buffers of the call (a batch concatenates its clips)
     int f0 = 0; size_t rowbuf_off = 0, lappart_off = 0;
-    int fb_cap = 0;                    // pairs the Farneback scratch holds
-    int* d_clipstart = nullptr; int* h_clipstart = nullptr; int clipstart_cap = 0;   // [n] 1 = first frame of a clip
+    int fb_cap = 0;                    // pairs the Farneback scratch holds (0 until every buffer of it exists)
+    DevBuf<int> d_clipstart; PinBuf<int> h_clipstart;   // [n] 1 = first frame of a clip
     // preprocess
-    uint8_t* d_stage = nullptr; size_t stage_bytes = 0;   // staged host frames
-    uint8_t* d_small = nullptr;       // [n][320*320]
-    float* d_rowbuf = nullptr;        // [n][h][32]
-    uint8_t* d_area = nullptr;        // [n][1024]
-    uint8_t* d_hash = nullptr;        // [n][1024]
-    int* d_ham = nullptr;             // [n]
-    unsigned long long* d_lap = nullptr;   // [n][2]
-    long long* d_lap_part = nullptr;       // [n][nbands][8 waves][2] per-wave partial moments
+    DevBuf<uint8_t> d_stage;          // staged host input
+    DevBuf<uint8_t> d_small;          // [n][320*320]
+    DevBuf<float> d_rowbuf;           // [n][h][32]
+    DevBuf<uint8_t> d_area;           // [n][1024]
+    DevBuf<uint8_t> d_hash;           // [n][1024]
+    DevBuf<unsigned long long> d_lap; // [n][2]
+    DevBuf<long long> d_lap_part;     // [n][nbands][8 waves][2] per-wave partial moments
     int lap_waves = 4;
-    PreParams pre{};
+    PreParams pre{};                  // geometry of the clip being enqueued (copies of its cache entry)
     HashParams hsh{};
     // farneback
-    float* d_pyr[AVD_FB_LEVELS] = {};     // [n][hL*wL]
-    float* d_poly[AVD_FB_LEVELS] = {};    // [n][hL*wL][5] interleaved polynomial coefficients
-    float* d_flow[AVD_FB_LEVELS] = {};    // [n-1][2][hL*wL]  planar
-    float* d_flow2[AVD_FB_LEVELS] = {};   // second flow buffer of a level: the fast level kernel (avd_fbfast.hip) ping-pongs
+    DevBuf<float> d_pyr[AVD_FB_LEVELS];     // [n][hL*wL]
+    DevBuf<float> d_poly[AVD_FB_LEVELS];    // [n][hL*wL][5] interleaved polynomial coefficients
+    DevBuf<float> d_flow[AVD_FB_LEVELS];    // [n-1][2][hL*wL]  planar
+    DevBuf<float> d_flow2[AVD_FB_LEVELS];   // second flow buffer of a level: the fast level kernel (avd_fbfast.hip) ping-pongs
     const float* flow_res[AVD_FB_LEVELS] = {};   // where the last call left the final flow of each level (d_flow or d_flow2)
-    float* d_mag = nullptr;               // [n-1][320*320] |flow| of the full-resolution level (written by the fast level kernel, or by k_mag in exact mode)
+    DevBuf<float> d_mag;                  // [n-1][320*320] |flow| of the full-resolution level (written by the fast level kernel, or by k_mag in exact mode)
     int mag_valid = 0;                    // d_mag holds the magnitudes of the chunk being processed
-    int* d_fbflags = nullptr;             // [n-1] ill-posedness flags of the fast level kernels (bit k: level k met the solver's criterion, bit 4 + k: the border-sign criterion); such pairs are re-run exactly
-    int* d_pairdiff = nullptr;            // [n-1][20] "frame p differs from frame p + 1" per tile of the pyramid kernel's 160-px scale (all zero: bit-identical frames)
-    int* d_rlist = nullptr; int rlist_cap = 0;                  // exact re-run: the flagged pairs of a chunk, compacted by the host
-    int* h_rlist = nullptr;                                     // pinned staging of that list
-    double* d_vs_rerun = nullptr; double* d_vs0_rerun = nullptr; // the two-kernel path's double intermediate for kRerunTwoKernelMax pairs (allocated by the first re-run)
-    double* d_vs = nullptr;               // [n-1] x 64x16 tiles of D = vsum(x+7)-vsum(x-8), double
-    double* d_vs0 = nullptr;              // [n-1][5][320][8]  vsum columns 0..6 (row init)
-    float* d_flow_il = nullptr;           // [n-1][320*320][2] interleaved (cv2 layout)
-    float* d_stats = nullptr;             // [n-1][2] mean, var
-    avd_frame_record* d_rec = nullptr;    // [n]
-    avd_frame_record* h_rec = nullptr;    // [n] pinned landing buffer of the asynchronous copy-out
-    // ViT patch-embed extension (avd_vit.hip): weights [768][768] bf16 + bias, im2col patches, token staging
-    uint16_t* d_vit_w = nullptr; float* d_vit_bias = nullptr; int vit_has_bias = 0;
-    uint16_t* d_vit_patches = nullptr; size_t vit_patch_elems = 0;
-    float* d_vit_tokens = nullptr; size_t vit_token_elems = 0;
+    DevBuf<int> d_fbflags;                // [n-1] ill-posedness flags of the fast level kernels (bit k: level k met the solver's criterion, bit 4 + k: the border-sign criterion); such pairs are re-run exactly
+    DevBuf<int> d_pairdiff;               // [n-1][20] "frame p differs from frame p + 1" per tile of the pyramid kernel's 160-px scale (all zero: bit-identical frames)
+    DevBuf<int> d_rlist;                  // exact re-run: the flagged pairs of a chunk, compacted by the host
+    PinBuf<int> h_rlist;                  // pinned staging of that list
+    DevBuf<double> d_vs_rerun, d_vs0_rerun;   // the two-kernel path's double intermediate for kRerunTwoKernelMax pairs (allocated by the first re-run)
+    DevBuf<double> d_vs;                  // [n-1] x 64x16 tiles of D = vsum(x+7)-vsum(x-8), double
+    DevBuf<double> d_vs0;                 // [n-1][5][320][8]  vsum columns 0..6 (row init)
+    DevBuf<float> d_flow_il;              // [n-1][320*320][2] interleaved (cv2 layout); allocated when a caller first asks for the dense flow
+    int no_flow_il = 0;                   // the chunks being enqueued hand no dense flow to the host: nothing is interleaved
+    DevBuf<float> d_stats;                // [n-1][2] mean, var
+    DevBuf<avd_frame_record> d_rec;       // [n]
+    PinBuf<avd_frame_record> h_rec;       // [n] pinned landing buffer of the asynchronous copy-out
+    // ViT patch-embed extension (avd_vit.hip): im2col patches, token staging (also the row operations' staging)
+    DevBuf<uint16_t> d_vit_patches;
+    DevBuf<float> d_vit_tokens;
     // audio analyzer (avd_audio.hip): tables (hanning, twiddles) for the current window lengths, scratch, records
-    double* d_audio_tab = nullptr; size_t audio_tab_elems = 0; int audio_win = 0, audio_last = 0;
-    double* d_audio_buf = nullptr; size_t audio_buf_elems = 0;
-    avd_audio_window* d_audio_out = nullptr; size_t audio_out_elems = 0;
-    // CNN extension (avd_cnn.hip): blocked conv weights + linear layer, biases, activation scratch for cnn_frames frames
-    uint16_t* d_cnn_w = nullptr; float* d_cnn_b = nullptr;
+    DevBuf<double> d_audio_tab; int audio_win = 0, audio_last = 0;
+    DevBuf<double> d_audio_buf;
+    DevBuf<avd_audio_window> d_audio_out;
+    // CNN extension (avd_cnn.hip): activation scratch for cnn_frames frames
+    DevBuf<uint16_t> d_cnn_act[4], d_cnn_img;
+    DevBuf<float> d_cnn_pool, d_cnn_logits; int cnn_frames = 0;
+};
+
+// What a caller uploaded (avd_cnn_set_weights, avd_vit_set_weights) is state, not scratch: it survives avd_release_workspace.
+struct Weights {
+    // CNN extension: blocked conv weights + linear layer, biases
+    DevBuf<uint16_t> d_cnn_w; DevBuf<float> d_cnn_b;
     std::vector<size_t> cnn_w_off; size_t cnn_fc_off = 0;
-    uint16_t* d_cnn_act[4] = {}; uint16_t* d_cnn_img = nullptr;
-    float* d_cnn_pool = nullptr; float* d_cnn_logits = nullptr; int cnn_frames = 0;
+    // ViT patch embedding: weights [768][768] bf16 + bias
+    DevBuf<uint16_t> d_vit_w; DevBuf<float> d_vit_bias; int vit_has_bias = 0;
 };
 
 struct avd_ctx {
@@ -161,7 +197,7 @@ struct avd_ctx {
     avd_frame_record* pending_out = nullptr;   // caller buffer the pinned records are handed to in avd_synchronize
     int pending_n = 0;
     hipEvent_t stage_ev[5] = {};
-    hipEvent_t kern_ev[12] = {};           // profiling: start/stop of the 3 k_uv<320> and 3 k_hscan<320> launches of a segment
+    hipEvent_t kern_ev[12] = {};           // profiling: start/stop of the 3 k_uv<320> and 3 k_hscan<320> launches of a chunk
     int kern_ev_used = 0;
     int profiling = 0;
     int stage_marks = 0;                       // stage events recorded by the call in flight (5 = all of them)
@@ -176,13 +212,14 @@ struct avd_ctx {
     float stage_ms[6] = {};
     std::string err;
     Workspace ws;
+    Weights weights;
     FbConsts fbc;
-    void* d_fbc = nullptr;          // FbConsts on device
+    DevBuf<FbConsts> d_fbc;         // FbConsts on device
     int last_n = 0;
     int rec_n = 0;                   // records the last avd_analyze_* call left in ws.d_rec (0 after any other entry point: avd_allgather_last_records checks it)
     void* comm = nullptr;            // RCCL communicator (avd_comm.cpp), bound at run time
     int comm_rank = 0, comm_world = 1;
-    void* d_comm = nullptr; size_t comm_bytes = 0;     // device staging of the record exchange
+    DevBuf<char> d_comm;             // device staging of the record exchange
     int cnn_tiles = 0;              // convolution tiling of the CNN extension: 0 = heuristic, 1 = 256-pixel tiles, 2 = 128 x 128 wherever possible
     int fb_fold_blur = 1;           // the 320-px scale's 3 x 3 pyramid blur formed inside the polynomial expansion (no effect on results); AVD_FB_FOLD_BLUR / avd_set_option
     int fb_wide160 = 2;             // fast mode: the 160-px level as one three-block strip per pair (1: fewer CU-microseconds, throughput) or as two strips (0: shorter launches, latency);
@@ -202,7 +239,7 @@ struct avd_ctx {
     int fb_rerun_fused = 0xC;       // exact re-run of FEW pairs (<= kRerunTwoKernelMax): level mask of the fused kernel (bit 3 = 40 px must be set), the other levels run the two-kernel path
     int last_rerun = 0;             // pairs re-run by the last drained call
     // the last Farneback chunk of an asynchronous call, whose flags the host has not seen yet (impl_synchronize re-runs its flagged pairs)
-    struct { int active = 0, p0 = 0, np = 0, fa = 0, n = 0; const int* clipstart = nullptr; } tail;
+    struct { int active = 0, p0 = 0, np = 0, fa = 0; const int* clipstart = nullptr; } tail;
     // A thread that waits in avd_synchronize settles the tails of OTHER contexts whose fast pass has finished meanwhile (avd_capi.hip, tail_help_others):
     // one host thread driving several contexts (avd_hip.ClipsInFlight, bench.py) would otherwise start each clip's re-run only when it reaches that clip.
     std::recursive_mutex api_mu;    // held by every entry point that takes this context; helpers only try_lock it
@@ -224,17 +261,18 @@ inline void kmark(avd_ctx* ctx, int id)
     if (hipEventRecord(e, ctx->stream) == hipSuccess) ctx->kmark_id[ctx->kmark_used++] = id;
 }
 
-template <typename T>
-inline int dev_alloc(avd_ctx* ctx, T*& p, size_t count)
+template <typename T, bool kPinned>
+int Buf<T, kPinned>::reserve(avd_ctx* ctx, size_t count)
 {
-    if (p) { (void)hipFree(p); p = nullptr; }
-    if (count == 0) return 0;
-    hipError_t e = hipMalloc((void**)&p, count * sizeof(T));
+    if (count <= cap) return 0;
+    reset();
+    const hipError_t e = kPinned ? hipHostMalloc((void**)&p, count * sizeof(T), hipHostMallocDefault) : hipMalloc((void**)&p, count * sizeof(T));
     if (e != hipSuccess) {
-        ctx->err = std::string("hipMalloc: ") + hipGetErrorString(e);
+        ctx->err = std::string(kPinned ? "hipHostMalloc: " : "hipMalloc: ") + hipGetErrorString(e);
         p = nullptr;
         return AVD_ERR_NOMEM;
     }
+    cap = count;
     return 0;
 }
 
@@ -248,10 +286,10 @@ int launch_preprocess(avd_ctx* ctx, const uint8_t* d_bgr, int n, int h, int w,
 // NV12 input: Y plane rows at d_y + f*frame_stride + y*row_stride, chroma rows at nv.uv + f*uv_frame_stride + (y/2)*uv_row_stride
 int launch_preprocess_nv12(avd_ctx* ctx, const uint8_t* d_y, const Nv12Params& nv, int n, int h, int w,
                            int64_t row_stride, int64_t frame_stride);
-int launch_hash(avd_ctx* ctx, int n, bool with_hamming = true);
+int launch_hash(avd_ctx* ctx, int n);
 int avd_calls_in_flight();      // avd_capi.hip: contexts of this process holding an enqueued, undrained avd_analyze_* call
-int launch_farneback(avd_ctx* ctx, hipStream_t stream, const uint8_t* d_small, int n, int frame_off, int pair_off);
-int launch_flow_stats(avd_ctx* ctx, hipStream_t stream, int n, int frame_off, int pair_off);
+int launch_farneback(avd_ctx* ctx, const uint8_t* d_small, int n);    // all pairs of n resident frames, into the Farneback scratch
+int launch_flow_stats(avd_ctx* ctx, int n);
 // avd_vit.hip (extension): patchify + bf16 MFMA GEMM; all pointers device
 int launch_vit_patch_embed(avd_ctx* ctx, const uint8_t* d_bgr, int n, int h, int w, int64_t row_stride, int64_t frame_stride,
                            const uint16_t* d_wt, const float* d_bias, void* d_tokens, int tokens_bf16, uint16_t* d_patches);
@@ -287,7 +325,7 @@ int launch_fb_fast(avd_ctx* ctx, hipStream_t stream, int w, const float* R, cons
 // avd_farneback.hip: exact re-run of the m flagged pairs h_list[0 .. m) (pair indices inside the chunk the workspace holds; h_list pinned) -- all four
 // levels with the exact kernels' launches from a compacted list, |flow| and the statistics of those pairs; np_chunk = pairs of the chunk
 constexpr int kRerunTwoKernelMax = 32;
-int launch_farneback_rerun(avd_ctx* ctx, hipStream_t stream, const int* h_list, int m, int pair_off, int np_chunk);
+int launch_farneback_rerun(avd_ctx* ctx, const int* h_list, int m, int np_chunk);
 // avd_norm.hip (extensions): LayerNorm over rows of 256..2048 values, softmax over rows of logits; device pointers
 int launch_layernorm(avd_ctx* ctx, const void* d_x, void* d_y, int bf16, long long rows, int cols, const float* d_gamma, const float* d_beta, float eps);
 int launch_softmax(avd_ctx* ctx, const float* d_x, float* d_y, long long rows, int cols);

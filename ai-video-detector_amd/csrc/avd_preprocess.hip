@@ -693,21 +693,6 @@ __global__ __launch_bounds__(1024) void k_hash(const float* __restrict__ rowbuf,
     }
 }
 
-// ham[f] = popcount(hash[f] ^ hash[f-1]) (video.py:38); ham[0] = -1
-__global__ __launch_bounds__(256) void k_hamming(const uint8_t* __restrict__ bits, int* __restrict__ ham)
-{
-    __shared__ int wsum[4];
-    const int f = blockIdx.x, tid = threadIdx.x;
-    if (f == 0) { if (tid == 0) ham[0] = -1; return; }
-    const unsigned a = reinterpret_cast<const unsigned*>(bits + (int64_t)f * 1024)[tid];
-    const unsigned b = reinterpret_cast<const unsigned*>(bits + (int64_t)(f - 1) * 1024)[tid];
-    int c = __popc(a ^ b);
-    c = wave_sum(c);
-    if ((tid & 63) == 0) wsum[tid >> 6] = c;
-    __syncthreads();
-    if (tid == 0) ham[f] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-}
-
 }  // namespace
 
 int launch_preprocess(avd_ctx* ctx, const uint8_t* d_bgr, int n, int h, int w,
@@ -781,16 +766,15 @@ int launch_preprocess_nv12(avd_ctx* ctx, const uint8_t* d_y, const Nv12Params& n
     return 0;
 }
 
-// with_hamming = false: the caller forms the Hamming distances itself (k_records of the analyze entries does, from the bits)
-int launch_hash(avd_ctx* ctx, int n, bool with_hamming)
+// (the Hamming distances between consecutive frames are formed from these bits by k_records of the analyze entries)
+int launch_hash(avd_ctx* ctx, int n)
 {
     Workspace& ws = ctx->ws;
-    // the clip's slice of the call's buffers: frame ws.f0 onwards (the first frame of a clip has no predecessor: ham = -1)
+    // the clip's slice of the call's buffers: frame ws.f0 onwards
     const size_t f0 = (size_t)ws.f0;
     hipLaunchKernelGGL(k_hash, dim3(n), dim3(1024), 0, ctx->stream, ws.d_rowbuf + ws.rowbuf_off, ws.hsh, ws.d_area + f0 * 1024,
                        ws.d_hash + f0 * 1024, (const long long*)(ws.d_lap_part + ws.lappart_off), ws.pre.nbands, ws.lap_waves,
                        ws.d_lap + 2 * f0);
-    if (with_hamming) hipLaunchKernelGGL(k_hamming, dim3(n), dim3(256), 0, ctx->stream, ws.d_hash + f0 * 1024, ws.d_ham + f0);
     HIP_TRY(ctx, hipGetLastError());
     return 0;
 }
