@@ -1,5 +1,5 @@
 // avd_capi.hip -- C-ABI of libavd_hip.so (include/avd.h): context, workspace, entry points.
-// Host C++; every kernel lives in avd_preprocess.hip / avd_farneback.hip.
+// Host C++; the kernels live in the other .hip files (the Farneback schedule: avd_farneback.hip).
 #include <algorithm>
 #include <cstdlib>
 #include <atomic>
@@ -180,8 +180,6 @@ int avd_ws_reserve(avd_ctx* ctx, int n, int h, int w)
     return avd_ws_reserve_frames(ctx, n, rowbuf_elems_for(ws, n), lappart_elems_for(ws, n));
 }
 
-constexpr size_t kPairDiffTilesHost = 20;     // = kPairDiffTiles of avd_fb_device.h (the pyramid kernel's 160-px tiles per frame)
-
 // Farneback scratch for min(n - 1, kFbChunkMax) pairs, at least kFbChunk; grows when a call brings more pairs
 int avd_ws_reserve_fb(avd_ctx* ctx, int n)
 {
@@ -203,7 +201,7 @@ int avd_ws_reserve_fb(avd_ctx* ctx, int n)
         if (int e = ws.d_stats.reserve(ctx, np * 2)) return e;
         if (int e = ws.d_mag.reserve(ctx, np * (size_t)AVD_NPIX)) return e;
         if (int e = ws.d_fbflags.reserve(ctx, np)) return e;
-        if (int e = ws.d_pairdiff.reserve(ctx, np * kPairDiffTilesHost)) return e;
+        if (int e = ws.d_pairdiff.reserve(ctx, np * kPairDiffTiles)) return e;
         if (int e = ws.h_rlist.reserve(ctx, np)) return e;
         // sized by the chunk, allocated by whoever first needs them
         ws.d_rlist.reset(); ws.d_vs.reset(); ws.d_vs0.reset(); ws.d_flow_il.reset();
@@ -213,9 +211,9 @@ int avd_ws_reserve_fb(avd_ctx* ctx, int n)
         if (int e = ws.d_pyr[0].reserve(ctx, ((size_t)ws.fb_cap + 2) * AVD_NPIX)) return e;
     // the double intermediate of the two-kernel fallback (4 MB per pair): only when that path is selected
     if (ctx->fb_mode == 0 && ctx->fb_fused != 0xF) {
-        const size_t np = (size_t)ws.fb_cap;
-        if (int e = ws.d_vs0.reserve(ctx, np * 5 * AVD_SMALL * 8)) return e;
-        if (int e = ws.d_vs.reserve(ctx, np * (5 * AVD_NPIX + 512))) return e;      // + one pad tile per pair
+        const FbTwoScratchSize sz = fb_two_scratch_size((size_t)ws.fb_cap);
+        if (int e = ws.d_vs0.reserve(ctx, sz.vs0)) return e;
+        if (int e = ws.d_vs.reserve(ctx, sz.vs)) return e;
     }
     return 0;
 }
@@ -452,10 +450,46 @@ static hipError_t wait_helping(avd_ctx* ctx, hipEvent_t ev)
     return ev ? hipEventSynchronize(ev) : hipStreamSynchronize(ctx->stream);
 }
 
+// ---- options (avd_set_option / avd_get_option, environment defaults read by avd_create) ----------------
+// One row per option; what an option MEANS is documented at its field in avd_ctx (avd_internal.h).  A read-only row is a counter: avd_set_option does
+// not know its name.  norm brings a value into range (false: refused with `refused`, the old value stays); env: read by avd_create through from_env and norm.
+struct Option { const char* name; int avd_ctx::*field; bool writable; bool (*norm)(int& v); const char* env; int (*from_env)(const char* text); const char* refused; };
+static bool opt_any(int&) { return true; }
+static bool opt_flag(int& v) { v = v != 0; return true; }
+template <int AND, int OR = 0> static bool opt_mask(int& v) { v = (v & AND) | OR; return true; }
+static bool opt_wide160(int& v) { v = v == 0 ? 0 : (v == 1 ? 1 : 2); return true; }
+static bool opt_gemm_waves(int& v) { v = v == 16 ? 16 : 8; return true; }
+static bool opt_cnn_fuse(int& v) { v = v < 0 ? 0 : (v > 2 ? 2 : v); return true; }
+static bool opt_cnn_chunk(int& v) { return v >= 1 && v <= 1024; }
+static int env_any_base(const char* e) { return (int)std::strtol(e, nullptr, 0); }
+static int env_fb_mode(const char* e) { return (std::strcmp(e, "exact") == 0 || std::strcmp(e, "0") == 0) ? 0 : 1; }
+static const Option kOptions[] = {
+    {"fb_fused", &avd_ctx::fb_fused, true, opt_mask<0xF>, "AVD_FB_FUSED", env_any_base},
+    {"fb_mode", &avd_ctx::fb_mode, true, opt_flag, "AVD_FB_MODE", env_fb_mode},
+    {"fb_fold_up", &avd_ctx::fb_fold_up, true, opt_mask<7>, "AVD_FB_FOLD_UP", std::atoi},
+    {"fb_rerun", &avd_ctx::fb_rerun, true, opt_flag, "AVD_FB_RERUN", std::atoi},
+    {"fb_rerun_fused", &avd_ctx::fb_rerun_fused, true, opt_mask<0xF, 8>},          // bit 3 (40 px) is always set
+    {"tail_help", &avd_ctx::tail_help, true, opt_flag},
+    {"fb_wide160", &avd_ctx::fb_wide160, true, opt_wide160, "AVD_FB_WIDE160", std::atoi},
+    {"fb_wide160_used", &avd_ctx::fb_wide160_used, false, opt_any},
+    {"fb_fold_blur", &avd_ctx::fb_fold_blur, true, opt_flag, "AVD_FB_FOLD_BLUR", std::atoi},
+    {"gemm_waves", &avd_ctx::gemm_waves, true, opt_gemm_waves, "AVD_GEMM_WAVES", std::atoi},
+    {"cnn_tiles", &avd_ctx::cnn_tiles, true, opt_any},
+    {"cnn_fuse", &avd_ctx::cnn_fuse, true, opt_cnn_fuse},
+    {"cnn_chunk", &avd_ctx::cnn_chunk, true, opt_cnn_chunk, nullptr, nullptr, "cnn_chunk: 1 ... 1024 frames per forward pass"},
+    {"rerun_pairs", &avd_ctx::last_rerun, false, opt_any},   // pairs of the last drained call that the fast level kernel flagged and the exact kernels re-ran
+};
+static const Option* find_option(avd_ctx* ctx, const char* name, bool to_write)
+{
+    for (const Option& o : kOptions)
+        if (std::strcmp(name, o.name) == 0 && (o.writable || !to_write)) return &o;
+    ctx->err = std::string("unknown option: ") + name;
+    return nullptr;
+}
+
 // ---- entry-point bodies (wrapped by the extern "C" functions at the end of the file) -----------------
 static void impl_destroy(avd_ctx* ctx);
 static int impl_synchronize(avd_ctx* ctx);
-
 
 static int impl_create(int device_id, avd_ctx** out)
 {
@@ -478,13 +512,8 @@ static int impl_create(int device_id, avd_ctx** out)
         hipDeviceProp_t prop;
         if (hipGetDeviceProperties(&prop, device_id) == hipSuccess && prop.multiProcessorCount > 0)
             ctx->num_cus = prop.multiProcessorCount;
-        if (const char* e = std::getenv("AVD_FB_FUSED")) ctx->fb_fused = (int)std::strtol(e, nullptr, 0) & 0xF;
-        if (const char* e = std::getenv("AVD_FB_FOLD_UP")) ctx->fb_fold_up = std::atoi(e) & 7;
-        if (const char* e = std::getenv("AVD_FB_WIDE160")) { const int v = std::atoi(e); ctx->fb_wide160 = v == 0 ? 0 : (v == 1 ? 1 : 2); }
-        if (const char* e = std::getenv("AVD_FB_FOLD_BLUR")) ctx->fb_fold_blur = std::atoi(e) != 0;
-        if (const char* e = std::getenv("AVD_FB_MODE")) ctx->fb_mode = (std::strcmp(e, "exact") == 0 || std::strcmp(e, "0") == 0) ? 0 : 1;
-        if (const char* e = std::getenv("AVD_FB_RERUN")) ctx->fb_rerun = std::atoi(e) != 0;
-        if (const char* e = std::getenv("AVD_GEMM_WAVES")) ctx->gemm_waves = std::atoi(e) == 16 ? 16 : 8;
+        for (const Option& o : kOptions)
+            if (const char* e = o.env && o.writable ? std::getenv(o.env) : nullptr) { int v = o.from_env(e); if (o.norm(v)) ctx->*o.field = v; }
         build_fb_consts(ctx->fbc);
         ok = ctx->d_fbc.reserve(ctx, 1) == 0 &&
              hipMemcpy(ctx->d_fbc, &ctx->fbc, sizeof(FbConsts), hipMemcpyHostToDevice) == hipSuccess;
@@ -812,7 +841,7 @@ static int impl_synchronize(avd_ctx* ctx)
         }
         // 4 / 5: mean duration of one k_uv<320> / k_hscan<320> launch (the last chunk)
         float sum[2] = {0.f, 0.f}; int cnt[2] = {0, 0};
-        for (int i = 0; i + 1 < ctx->kern_ev_used; i += 2) {     // recorded by blur_iteration<320> of the drained call
+        for (int i = 0; i + 1 < ctx->kern_ev_used; i += 2) {     // stage_mark events of the drained call
             float ms = 0.f;
             if (hipEventElapsedTime(&ms, ctx->kern_ev[i], ctx->kern_ev[i + 1]) == hipSuccess) { sum[(i >> 1) & 1] += ms; cnt[(i >> 1) & 1]++; }
         }
@@ -889,7 +918,7 @@ static int64_t impl_debug_fetch(avd_ctx* ctx, const char* name, void* out, size_
     else if ((k = level("pyr")) >= 0) { src = ws.d_pyr[k]; bytes = (size_t)std::min(n, ws.fb_cap + 1) * (AVD_NPIX >> (2 * k)) * 4; }
     else if ((k = level("poly")) >= 0) { src = ws.d_poly[k]; bytes = (size_t)std::min(n, ws.fb_cap + 1) * 5 * (AVD_NPIX >> (2 * k)) * 4; }
     else if ((k = level("flow")) >= 0) { src = ws.flow_res[k] ? ws.flow_res[k] : ws.d_flow[k]; bytes = (size_t)std::min(std::max(n - 1, 0), ws.fb_cap) * 2 * (AVD_NPIX >> (2 * k)) * 4; }
-    else if (std::strcmp(name, "vs0") == 0) { src = ws.d_vs0; bytes = (size_t)ws.fb_cap * 5 * AVD_SMALL * 8 * 8; }
+    else if (std::strcmp(name, "vs0") == 0) { src = ws.d_vs0; bytes = fb_two_scratch_size((size_t)ws.fb_cap).vs0 * sizeof(double); }
     else { ctx->err = "unknown debug buffer"; return AVD_ERR_ARG; }
     if (!src) { ctx->err = "buffer not allocated yet"; return AVD_ERR_ARG; }
     bytes = std::min(bytes, out_bytes);
@@ -922,51 +951,25 @@ static int impl_release_workspace(avd_ctx* ctx)
     return AVD_OK;
 }
 
-// Tuning / test switches.  "fb_fused": bit k set = pyramid level k (0 = 320x320) runs the fused level kernel.
+// Tuning / test switches (kOptions above).
 static int impl_set_option(avd_ctx* ctx, const char* name, int value)
 {
     if (!ctx || !name) return AVD_ERR_ARG;
-    if (std::strcmp(name, "fb_fused") == 0) { ctx->fb_fused = value & 0xF; return AVD_OK; }
-    if (std::strcmp(name, "fb_mode") == 0) { ctx->fb_mode = value ? 1 : 0; return AVD_OK; }
-    if (std::strcmp(name, "fb_fold_up") == 0) { ctx->fb_fold_up = value & 7; return AVD_OK; }
-    if (std::strcmp(name, "fb_rerun") == 0) { ctx->fb_rerun = value ? 1 : 0; return AVD_OK; }
-    if (std::strcmp(name, "fb_rerun_fused") == 0) { ctx->fb_rerun_fused = (value & 0xF) | 8; return AVD_OK; }
-    if (std::strcmp(name, "tail_help") == 0) { ctx->tail_help = value != 0; return AVD_OK; }
-    if (std::strcmp(name, "fb_wide160") == 0) { ctx->fb_wide160 = value == 0 ? 0 : (value == 1 ? 1 : 2); return AVD_OK; }
-    if (std::strcmp(name, "fb_fold_blur") == 0) { ctx->fb_fold_blur = value != 0; return AVD_OK; }
-    if (std::strcmp(name, "gemm_waves") == 0) { ctx->gemm_waves = value == 16 ? 16 : 8; return AVD_OK; }
-    if (std::strcmp(name, "cnn_tiles") == 0) { ctx->cnn_tiles = value; return AVD_OK; }
-    if (std::strcmp(name, "cnn_fuse") == 0) { ctx->cnn_fuse = value < 0 ? 0 : (value > 2 ? 2 : value); return AVD_OK; }
-    if (std::strcmp(name, "cnn_chunk") == 0) {
-        if (value < 1 || value > 1024) { ctx->err = "cnn_chunk: 1 ... 1024 frames per forward pass"; return AVD_ERR_ARG; }
-        ctx->cnn_chunk = value;
-        return AVD_OK;
-    }
-    ctx->err = std::string("unknown option: ") + name;
-    return AVD_ERR_ARG;
+    const Option* o = find_option(ctx, name, true);
+    if (!o) return AVD_ERR_ARG;
+    if (!o->norm(value)) { ctx->err = o->refused; return AVD_ERR_ARG; }
+    ctx->*o->field = value;
+    return AVD_OK;
 }
 
-// The value an option has NOW (environment defaults included), and read-only counters: "rerun_pairs" = pairs of the last
-// drained call that the fast level kernel flagged as ill-posed and the exact kernels re-ran.
+// The value an option has NOW (environment defaults included), and the read-only counters.
 static int impl_get_option(avd_ctx* ctx, const char* name, int* value)
 {
     if (!ctx || !name || !value) return AVD_ERR_ARG;
-    if (std::strcmp(name, "fb_fused") == 0) { *value = ctx->fb_fused; return AVD_OK; }
-    if (std::strcmp(name, "fb_mode") == 0) { *value = ctx->fb_mode; return AVD_OK; }
-    if (std::strcmp(name, "fb_fold_up") == 0) { *value = ctx->fb_fold_up; return AVD_OK; }
-    if (std::strcmp(name, "fb_rerun") == 0) { *value = ctx->fb_rerun; return AVD_OK; }
-    if (std::strcmp(name, "fb_rerun_fused") == 0) { *value = ctx->fb_rerun_fused; return AVD_OK; }
-    if (std::strcmp(name, "tail_help") == 0) { *value = ctx->tail_help; return AVD_OK; }
-    if (std::strcmp(name, "fb_wide160") == 0) { *value = ctx->fb_wide160; return AVD_OK; }
-    if (std::strcmp(name, "fb_wide160_used") == 0) { *value = ctx->fb_wide160_used; return AVD_OK; }
-    if (std::strcmp(name, "fb_fold_blur") == 0) { *value = ctx->fb_fold_blur; return AVD_OK; }
-    if (std::strcmp(name, "gemm_waves") == 0) { *value = ctx->gemm_waves; return AVD_OK; }
-    if (std::strcmp(name, "cnn_tiles") == 0) { *value = ctx->cnn_tiles; return AVD_OK; }
-    if (std::strcmp(name, "cnn_fuse") == 0) { *value = ctx->cnn_fuse; return AVD_OK; }
-    if (std::strcmp(name, "cnn_chunk") == 0) { *value = ctx->cnn_chunk; return AVD_OK; }
-    if (std::strcmp(name, "rerun_pairs") == 0) { *value = ctx->last_rerun; return AVD_OK; }
-    ctx->err = std::string("unknown option: ") + name;
-    return AVD_ERR_ARG;
+    const Option* o = find_option(ctx, name, false);
+    if (!o) return AVD_ERR_ARG;
+    *value = ctx->*o->field;
+    return AVD_OK;
 }
 
 // Timing of the extensions: `reps` repetitions of `launch` between ev0 and ev1 on the context's stream; *out_ms = mean time of one

@@ -1,4 +1,4 @@
-// avd_fb_device.h -- device helpers shared by the Farneback kernels (avd_farneback.hip, avd_fbfused.hip):
+// avd_fb_device.h -- device helpers shared by the Farneback kernels (avd_farneback.hip, avd_fbtwo.hip, avd_fbfused.hip, avd_fbfast.hip):
 // FarnebackUpdateMatrices for one pixel (reference site: cv2.calcOpticalFlowFarneback, app/analyzers/video.py:45),
 // split into the three steps of a software pipeline: inputs (flow, R0) -> bilinear gather of R1 at the warped
 // position -> normal equations.  Float arithmetic in OpenCV's order, no contraction.
@@ -303,7 +303,6 @@ constexpr float kFlowMax = 0.3f;
 constexpr float kTinyFlow = 1e-12f;
 constexpr float kJumpMin = 1e-6f;    // a non-zero component below kTinyFlow
 constexpr float kJumpMinZero = 0.05f; // an exactly zero one (cv2's may be +-residue): two different FLAT frames, whose zero flow is structural, stay below
-constexpr int kPairDiffTiles = 20;   // tiles per frame of the pyramid kernel's 160-px scale: each leaves "frame f differs from frame f + 1 here"
 
 // What FarnebackUpdateMatrices' two branches disagree by at a pixel whose deciding flow component is (all but) zero: "outside" takes
 // r2 = R0[0] / 2, r3 = R0[1] / 2, r4 .. r6 from R0 alone, "inside" (R0[0] - b[0]) / 2, .., (R0[2] + b[2]) / 2 .. with b the sample of R1, which is

@@ -578,55 +578,46 @@ __global__ __launch_bounds__((64 * Ge::NWAVES)) void k_fb_fast(const float* __re
     }
 }
 
-// mode: 0 = one iteration flow_in -> flow_out; 1 (320 px) = the same with the chain wave's resize of the previous level's flow; 2 = one
-// iteration behind a prologue that resizes the previous level's flow into flow_tmp; 3 = all three iterations (flow_in ignored when
-// zero_first, result in flow_out); 4 = prologue + all three iterations
+// the instantiation that L describes (launch_fb_fast has checked that it exists at this width)
 template <typename Ge>
-void launch_fast(hipStream_t stream, const float* R, const float* fin, float* fout, float* ftmp, float* mag, int* flags, const int* pairdiff, int np,
-                 int nstrips, int ow, int zero_first, int mode)
+void launch_fast(hipStream_t stream, const float* R, const FbFastLaunch& L, float* mag, int np, int nstrips, int ow)
 {
     const int grid = 8 * ((np + 7) / 8) * nstrips;
     const dim3 g(grid), t(64 * Ge::NWAVES);
+    const int zero_first = L.from == FbFlowFrom::zero;
+    auto go = [&](auto kernel, int zf) { hipLaunchKernelGGL(kernel, g, t, 0, stream, R, L.flow_in, L.flow_out, L.flow_tmp, mag, L.flags, L.pairdiff, np, nstrips, ow, zf); };
     // the chain wave's resize only exists where it pays: at 320 px it costs the launch 3.5 us and saves k_flow_up's 37; the small
     // levels are latency-bound on exactly the chain wave that would do it (160 px: 45 -> 84 us per launch against 12 saved)
-    if constexpr (Ge::W == 320) {
-        if (mode == 1) { hipLaunchKernelGGL((k_fb_fast<Ge, true>), g, t, 0, stream, R, fin, fout, ftmp, mag, flags, pairdiff, np, nstrips, ow, 0); return; }
-    }
-    if constexpr (Ge::W == 160 || Ge::W == 80) {
-        if (mode == 2) { hipLaunchKernelGGL((k_fb_fast<Ge, false, 1, true>), g, t, 0, stream, R, fin, fout, ftmp, mag, flags, pairdiff, np, nstrips, ow, 0); return; }
-    }
-    if constexpr (Ge::W == 80) {
-        if (mode == 4) { hipLaunchKernelGGL((k_fb_fast<Ge, false, 3, true>), g, t, 0, stream, R, fin, fout, ftmp, mag, flags, pairdiff, np, nstrips, ow, 0); return; }
-    }
-    if constexpr (Ge::W == 80 || Ge::W == 40) {
-        if (mode == 3) { hipLaunchKernelGGL((k_fb_fast<Ge, false, 3, false>), g, t, 0, stream, R, fin, fout, ftmp, mag, flags, pairdiff, np, nstrips, ow, zero_first); return; }
-    }
-    hipLaunchKernelGGL((k_fb_fast<Ge, false>), g, t, 0, stream, R, fin, fout, ftmp, mag, flags, pairdiff, np, nstrips, ow, zero_first);
+    const bool pro = L.from == FbFlowFrom::prologue, three = L.iterations == 3;
+    if constexpr (Ge::W == 320) { if (L.from == FbFlowFrom::chain) return go(k_fb_fast<Ge, true>, 0); }
+    if constexpr (Ge::W == 160 || Ge::W == 80) { if (pro && !three) return go(k_fb_fast<Ge, false, 1, true>, 0); }
+    if constexpr (Ge::W == 80) { if (pro && three) return go(k_fb_fast<Ge, false, 3, true>, 0); }
+    if constexpr (Ge::W == 80 || Ge::W == 40) { if (three) return go(k_fb_fast<Ge, false, 3, false>, zero_first); }
+    go(k_fb_fast<Ge, false>, zero_first);
 }
 
 }  // namespace
 
-// Blur iterations of one pyramid level for `np` pairs: R = polynomial expansions of np + 1 frames ([frame][y][x][5]), flows planar
-// [pair][2][y][x].  mode (see launch_fast): 0 one iteration flow_in -> flow_out (different buffers); 1 / 2 the same with flow_in = the
-// previous (coarser) level's final flow [pair][2][w/2][w/2], resized on the fly (1: 320 px, by the chain wave; 2: 160 / 80 px, in a
-// prologue, through flow_tmp); 3 / 4 all three iterations in one launch (80 / 40 px: a pair is one workgroup), result in flow_out,
-// flow_tmp as the second buffer (4: behind the prologue).
-// mag_out (320-px level, last iteration; else null): float[pair][320][320] receives |flow|
-// flags (may be null): int[np]; bit k of flags[p] is set when level k (0 = 320 px) of pair p met the solver's ill-posedness criterion, bit 4 + k when it met
-// the border-sign criterion; a pair whose word is already non-zero is skipped.  pairdiff (may be null): int[np][kPairDiffTiles], non-zero where frame p
+// Blur iterations of one pyramid level for `np` pairs (L: avd_internal.h): R = polynomial expansions of np + 1 frames ([frame][y][x][5]), flows planar [pair][2][y][x]
+// L.flags (may be null): int[np]; bit k of flags[p] is set when level k (0 = 320 px) of pair p met the solver's ill-posedness criterion, bit 4 + k when it met
+// the border-sign criterion; a pair whose word is already non-zero is skipped.  L.pairdiff (may be null): int[np][kPairDiffTiles], non-zero where frame p
 // differs from frame p + 1 (k_pyramid_all): bit-identical pairs are exempt from the border-sign criterion
-int launch_fb_fast(avd_ctx* ctx, hipStream_t stream, int w, const float* R, const float* flow_in, float* flow_out, float* flow_tmp, float* mag_out,
-                   int* flags, const int* pairdiff, int np, int zero_first, int mode)
+int launch_fb_fast(avd_ctx* ctx, hipStream_t stream, int w, const float* R, const FbFastLaunch& L, int np)
 {
     if (np <= 0) return 0;
-    const bool ok = mode == 0 || (mode == 1 && w == 320) || (mode == 2 && (w == 160 || w == 80)) || (mode == 3 && (w == 80 || w == 40)) || (mode == 4 && w == 80);
+    // the combinations that exist (k_fb_fast's template arguments, launch_fast)
+    const bool one = L.iterations == 1, three = L.iterations == 3;
+    const bool ok = L.from == FbFlowFrom::level || L.from == FbFlowFrom::zero ? (one || (three && (w == 80 || w == 40)))
+                  : L.from == FbFlowFrom::chain ? (one && w == 320)
+                  : (one ? (w == 160 || w == 80) : (three && w == 80));      // prologue
     if (!ok) { ctx->err = "launch_fb_fast: this mode does not exist at this level size"; return AVD_ERR_ARG; }
-    if (flow_in == flow_out || (mode >= 2 && (!flow_tmp || flow_tmp == flow_out))) { ctx->err = "launch_fb_fast: the flow is not updated in place"; return AVD_ERR_ARG; }
+    const bool uses_tmp = three || L.from == FbFlowFrom::prologue;
+    if (L.flow_in == L.flow_out || (uses_tmp && (!L.flow_tmp || L.flow_tmp == L.flow_out))) { ctx->err = "launch_fb_fast: the flow is not updated in place"; return AVD_ERR_ARG; }
     switch (w) {
     case 320:
         // (neighbour-shared gathers -- each lane loads its left pixel, the right one comes from lane + 1 by a DPP wave shift -- were built,
         // bit-identical and slower, 164 us per launch against 142: profiles/r04_experiments.md section 2; the code is in the history, commit 3e8b43a)
-        launch_fast<FGeo<320, 3, 2, 2, 1>>(stream, R, flow_in, flow_out, flow_tmp, mag_out, flags, pairdiff, np, 2, 160, zero_first, mode);
+        launch_fast<FGeo<320, 3, 2, 2, 1>>(stream, R, L, L.mag_out, np, 2, 160);
         break;
     case 160:
         // two shapes (ctx->fb_wide160; default 2 = chosen per call, see below): a pair as ONE strip of three blocks with the 320-px level's wave mix (119 workgroups of 12 waves,
@@ -636,11 +627,11 @@ int launch_fb_fast(avd_ctx* ctx, hipStream_t stream, int w, const float* R, cons
         // grouping of the solver's window sums (four columns per lane against two): bit-identical on well-posed content, like the 320-px level.
         // 2 = choose per call: this call is being enqueued and not yet counted, so > 0 means SOMEBODY ELSE's kernels will share the chip with it
         ctx->fb_wide160_used = ctx->fb_wide160 == 1 || (ctx->fb_wide160 == 2 && avd_calls_in_flight() - ctx->counted_in_flight > 0);
-        if (ctx->fb_wide160_used) launch_fast<FGeo<160, 3, 2, 2, 1>>(stream, R, flow_in, flow_out, flow_tmp, nullptr, flags, pairdiff, np, 1, 160, zero_first, mode);
-        else launch_fast<FGeo<160, 2, 1, 4, 2>>(stream, R, flow_in, flow_out, flow_tmp, nullptr, flags, pairdiff, np, 2, 80, zero_first, mode);
+        if (ctx->fb_wide160_used) launch_fast<FGeo<160, 3, 2, 2, 1>>(stream, R, L, nullptr, np, 1, 160);
+        else launch_fast<FGeo<160, 2, 1, 4, 2>>(stream, R, L, nullptr, np, 2, 80);
         break;
-    case 80: launch_fast<FGeo<80, 2, 1, 4, 2>>(stream, R, flow_in, flow_out, flow_tmp, nullptr, flags, pairdiff, np, 1, 80, zero_first, mode); break;
-    case 40: launch_fast<FGeo<40, 1, 1, 4, 2>>(stream, R, flow_in, flow_out, flow_tmp, nullptr, flags, pairdiff, np, 1, 40, zero_first, mode); break;
+    case 80: launch_fast<FGeo<80, 2, 1, 4, 2>>(stream, R, L, nullptr, np, 1, 80); break;
+    case 40: launch_fast<FGeo<40, 1, 1, 4, 2>>(stream, R, L, nullptr, np, 1, 40); break;
     default: ctx->err = "launch_fb_fast: unsupported level size"; return AVD_ERR_ARG;
     }
     HIP_TRY(ctx, hipGetLastError());

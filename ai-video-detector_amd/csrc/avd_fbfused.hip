@@ -1,7 +1,7 @@
 // avd_fbfused.hip -- FarnebackUpdateFlow_Blur (winsize 15) with ALL iterations of a pyramid level in one launch and
 // nothing but the flow leaving the chip (gfx950).
 //
-// Replaces, per level, the pair k_uv / k_uvp + k_hscan of avd_farneback.hip (reference site:
+// Replaces, per level, the pair k_uv / k_uvp + k_hscan of avd_fbtwo.hip (reference site:
 // cv2.calcOpticalFlowFarneback(prev, cur, None, 0.5, 3, 15, 3, 5, 1.2, 0), app/analyzers/video.py:45).  Those two
 // kernels exchange the exact double intermediate D = vsum(x+7) - vsum(x-8) through HBM (40 B per pixel written and
 // read again: 488 MB per iteration at 320x320 x 119 pairs, more than half of the stage's traffic), because the

@@ -4,11 +4,13 @@
 #include <stdint.h>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <vector>
 #include "../../include/avd.h"
 
-#define AVD_FB_LEVELS 4            // pyramid scales 1/8,1/4,1/2,1 of 320 (see farneback.hip)
+#define AVD_FB_LEVELS 4            // pyramid scales 1/8,1/4,1/2,1 of 320 (see avd_farneback.hip)
 #define AVD_NPIX (AVD_SMALL * AVD_SMALL)
+constexpr int kPairDiffTiles = 20;   // tiles per frame of the pyramid kernel's 160-px scale: each leaves "frame f differs from frame f + 1 here"
 
 #define HIP_TRY(ctx, expr)                                                         \
     do {                                                                           \
@@ -197,7 +199,7 @@ struct avd_ctx {
     avd_frame_record* pending_out = nullptr;   // caller buffer the pinned records are handed to in avd_synchronize
     int pending_n = 0;
     hipEvent_t stage_ev[5] = {};
-    hipEvent_t kern_ev[12] = {};           // profiling: start/stop of the 3 k_uv<320> and 3 k_hscan<320> launches of a chunk
+    hipEvent_t kern_ev[12] = {};           // profiling: stage_mark events around the 320-px level's blur launches of a chunk
     int kern_ev_used = 0;
     int profiling = 0;
     int stage_marks = 0;                       // stage events recorded by the call in flight (5 = all of them)
@@ -229,7 +231,7 @@ struct avd_ctx {
     int gemm_waves = 8;             // patch-embed GEMM: waves per workgroup (8: 8 x 4 MFMA tiles per wave, 16: 4 x 4; measured no faster), the same 256 x 256 tile; AVD_GEMM_WAVES / avd_set_option
     int cnn_chunk = 128;            // CNN extension: frames per forward pass (activation scratch = 4 x 1.6 MB per frame)
     int cnn_fuse = 2;               // CNN extension: a block's 3x3 and expanding 1x1 in one launch (stages 1, 2): 2 = with the 3x3's input slab in LDS in the stride-1 blocks (k_slab3_expand), 1 = gathering kernels only, 0 = layer by layer
-    int fb_fused = 0xF;             // bit k: pyramid level k runs the fused kernel (avd_fbfused.hip) instead of k_uv/k_uvp + k_hscan
+    int fb_fused = 0xF;             // bit k: pyramid level k runs the fused kernel (avd_fbfused.hip) instead of the two-kernel path (avd_fbtwo.hip)
     int fb_fold_up = 5;             // fast mode, bit mask (no effect on results; AVD_FB_FOLD_UP / avd_set_option): 1 the 320-px level's first launch resizes the
                                     // 160-px flow itself (no k_flow_up<320>), 2 the 160- / 80-px levels do so in a prologue, 4 the 80- / 40-px levels run their three
                                     // iterations in one launch
@@ -260,6 +262,10 @@ inline void kmark(avd_ctx* ctx, int id)
     if (!e && hipEventCreate(&e) != hipSuccess) { e = nullptr; return; }
     if (hipEventRecord(e, ctx->stream) == hipSuccess) ctx->kmark_id[ctx->kmark_used++] = id;
 }
+
+// profiling only: one of the twelve events around the 320-px level's blur launches (avd_stage_ms 4 and 5 are sums over alternate intervals,
+// impl_synchronize); `on` = the caller's launch is one of those (level 0 of a chunk's first pass, never the exact re-run)
+inline void stage_mark(avd_ctx* ctx, bool on) { if (on && ctx->profiling && ctx->kern_ev_used < 12) (void)hipEventRecord(ctx->kern_ev[ctx->kern_ev_used++], ctx->stream); }
 
 template <typename T, bool kPinned>
 int Buf<T, kPinned>::reserve(avd_ctx* ctx, size_t count)
@@ -316,14 +322,36 @@ int launch_audio_features(avd_ctx* ctx, const float* d_wav, int64_t n, int win, 
 // zero_first: the initial flow is zero whatever the buffer holds (the coarsest level: no clearing launch)
 // plist (may be null): the launch works on pairs plist[0 .. np)
 int launch_fb_level(avd_ctx* ctx, hipStream_t stream, int w, const float* R, float* flow, int np, int iterations, int zero_first, const int* plist = nullptr);
+// the width of a pyramid level (320 / 160 / 80 / 40 px) as a compile-time constant: f(std::integral_constant<int, W>{}); false = no such level
+template <int W = AVD_SMALL, typename F>
+inline bool fb_dispatch_width(int w, F&& f)
+{
+    if (w == W) return f(std::integral_constant<int, W>{}), true;
+    if constexpr (W > (AVD_SMALL >> (AVD_FB_LEVELS - 1))) return fb_dispatch_width<W / 2>(w, f);
+    return false;
+}
+// avd_fbtwo.hip: ONE blur iteration of one pyramid level as two kernels that exchange the double intermediate through `s`; which shape runs
+// (k_uvp<W, 12> + k_hscan_lat, k_uvp<W, 4>, k_uv) follows w, np and plist.  plist (may be null): the launch works on pairs plist[0 .. np), the
+// intermediate is indexed by position in the list.  marks: a 320-px iteration records four stage_mark events (on ctx->stream, which `stream` is)
+struct FbTwoScratch { double *vs, *vs0; };            // exact mode: {ws.d_vs, ws.d_vs0}; the re-run: {ws.d_vs_rerun, ws.d_vs0_rerun}
+struct FbTwoScratchSize { size_t vs, vs0; };          // doubles
+FbTwoScratchSize fb_two_scratch_size(size_t np);      // what np pairs need at any level
+int launch_fb_two(avd_ctx* ctx, hipStream_t stream, int w, const float* R, float* flow, FbTwoScratch s, int np, const int* plist, bool marks);
 // avd_fbfast.hip: blur iterations of one pyramid level, a pair spread over several workgroups (column strips), the horizontal window sums
-// formed directly in double (the vertical chain stays literal).  mode 0: one iteration flow_in -> flow_out; 1 / 2: the same with flow_in =
-// the coarser level's flow, resized on the fly (320 px: by the chain wave; 160 / 80 px: in a prologue through flow_tmp); 3 / 4: all three
-// iterations in one launch (80 / 40 px), result in flow_out, flow_tmp the second buffer (4: behind the prologue)
-int launch_fb_fast(avd_ctx* ctx, hipStream_t stream, int w, const float* R, const float* flow_in, float* flow_out, float* flow_tmp, float* mag_out,
-                   int* flags, const int* pairdiff, int np, int zero_first, int mode);
-// avd_farneback.hip: exact re-run of the m flagged pairs h_list[0 .. m) (pair indices inside the chunk the workspace holds; h_list pinned) -- all four
-// levels with the exact kernels' launches from a compacted list, |flow| and the statistics of those pairs; np_chunk = pairs of the chunk
+// formed directly in double (the vertical chain stays literal).  One launch runs `iterations` (1, or all 3 where a pair is one workgroup:
+// 80 / 40 px) from an initial flow that comes `from`:
+//   level     flow_in, a buffer of this level (every width)
+//   zero      like level, but at 40 px (the coarsest level) the flow is taken as zero whatever flow_in holds: no clearing launch
+//   chain     flow_in = the COARSER level's final flow [pair][2][w/2][w/2], resized by the chain wave on the fly (320 px, 1 iteration)
+//   prologue  the same, resized by the whole workgroup into flow_tmp first (160 / 80 px with 1 iteration, 80 px with 3)
+enum class FbFlowFrom { level, zero, chain, prologue };   // the result is in flow_out (3 iterations: flow_tmp is the second buffer); nothing is updated in place
+struct FbFastLaunch {
+    int iterations; FbFlowFrom from; const float* flow_in; float *flow_out, *flow_tmp;
+    float* mag_out;                              // 320-px level, last iteration (else null): float[pair][320][320] receives |flow|
+    int* flags; const int* pairdiff;             // may be null, see avd_fbfast.hip
+};
+int launch_fb_fast(avd_ctx* ctx, hipStream_t stream, int w, const float* R, const FbFastLaunch& L, int np);
+// avd_farneback.hip: exact re-run of the m flagged pairs h_list[0 .. m) (pair indices inside the chunk the workspace holds; h_list pinned); np_chunk = its pairs
 constexpr int kRerunTwoKernelMax = 32;
 int launch_farneback_rerun(avd_ctx* ctx, const int* h_list, int m, int np_chunk);
 // avd_norm.hip (extensions): LayerNorm over rows of 256..2048 values, softmax over rows of logits; device pointers

@@ -400,3 +400,73 @@ def test_a_waiting_thread_settles_the_other_contexts_tails():
     finally:
         for c in ctxs:
             c.close()
+
+
+# option -> [(value handed to avd_set_option, value avd_get_option reports afterwards)]: in range, out of range, negative
+_OPTION_SET_GET = {
+    "fb_fused": [(5, 5), (0x15, 5), (-1, 0xF)],                        # v & 0xF
+    "fb_mode": [(0, 0), (1, 1), (7, 1), (-3, 1)],                      # v ? 1 : 0
+    "fb_fold_up": [(3, 3), (13, 5), (-1, 7)],                          # v & 7
+    "fb_rerun": [(0, 0), (5, 1), (-1, 1)],                             # v ? 1 : 0
+    "fb_rerun_fused": [(0xC, 0xC), (0, 8), (0x13, 0xB), (-1, 0xF)],    # (v & 0xF) | 8
+    "tail_help": [(0, 0), (9, 1), (-2, 1)],                            # v != 0
+    "fb_wide160": [(0, 0), (1, 1), (2, 2), (5, 2), (-1, 2)],           # 0, 1, else 2
+    "fb_fold_blur": [(0, 0), (4, 1), (-1, 1)],                         # v != 0
+    "gemm_waves": [(16, 16), (8, 8), (12, 8), (-16, 8)],               # 16, else 8
+    "cnn_tiles": [(2, 2), (99, 99), (-5, -5)],                         # unchanged
+    "cnn_fuse": [(1, 1), (7, 2), (-3, 0)],                             # clamped to 0 ... 2
+    "cnn_chunk": [(64, 64), (1, 1), (1024, 1024)],                     # 1 ... 1024 (anything else is refused: below)
+}
+# environment variable -> (option, [(text, value a context created under it reports)])
+_OPTION_ENV = {
+    "AVD_FB_FUSED": ("fb_fused", [("5", 5), ("0x15", 5), ("012", 10), ("-1", 0xF), ("0", 0)]),       # strtol base 0, & 0xF
+    "AVD_FB_MODE": ("fb_mode", [("exact", 0), ("0", 0), ("fast", 1), ("1", 1), ("", 1), ("00", 1)]),   # "exact" / "0", else fast
+    "AVD_FB_FOLD_UP": ("fb_fold_up", [("3", 3), ("13", 5), ("-1", 7), ("x", 0)]),                      # atoi & 7
+    "AVD_FB_RERUN": ("fb_rerun", [("0", 0), ("1", 1), ("5", 1), ("-1", 1), ("no", 0)]),                # atoi != 0
+    "AVD_FB_WIDE160": ("fb_wide160", [("0", 0), ("1", 1), ("2", 2), ("7", 2), ("-1", 2)]),             # 0, 1, else 2
+    "AVD_FB_FOLD_BLUR": ("fb_fold_blur", [("0", 0), ("1", 1), ("4", 1), ("-1", 1)]),                   # atoi != 0
+    "AVD_GEMM_WAVES": ("gemm_waves", [("16", 16), ("8", 8), ("12", 8), ("-16", 8)]),                   # 16, else 8
+}
+_OPTION_DEFAULTS = {"fb_fused": 0xF, "fb_mode": 1, "fb_fold_up": 5, "fb_rerun": 1, "fb_rerun_fused": 0xC, "tail_help": 1, "fb_wide160": 2,
+                    "fb_fold_blur": 1, "gemm_waves": 8, "cnn_tiles": 0, "cnn_fuse": 2, "cnn_chunk": 128, "rerun_pairs": 0, "fb_wide160_used": 0}
+
+
+def test_option_table(monkeypatch):
+    """avd_set_option / avd_get_option / the AVD_* environment variables read by avd_create, option by option: what `set` stores for a value in
+    range, out of range and negative; the two read-only names and an unknown one refuse `set` (and an unknown one `get`) with AVD_ERR_ARG and
+    "unknown option: NAME"; cnn_chunk refuses a value outside 1 ... 1024 and keeps the old one; a context created under each environment variable
+    reports the mapped value and the defaults everywhere else."""
+    import avd_hip
+    for var in _OPTION_ENV:
+        monkeypatch.delenv(var, raising=False)
+    with avd_hip.Context(0) as c:
+        assert {k: c.get_option(k) for k in _OPTION_DEFAULTS} == _OPTION_DEFAULTS
+        for name, cases in _OPTION_SET_GET.items():
+            for value, stored in cases:
+                c.set_option(name, value)
+                assert c.get_option(name) == stored, (name, value)
+            # nothing else moved
+            others = {k: v for k, v in _OPTION_DEFAULTS.items() if k != name}
+            assert {k: c.get_option(k) for k in others} == others, name
+            c.set_option(name, _OPTION_DEFAULTS[name])
+            assert c.get_option(name) == _OPTION_DEFAULTS[name]
+        for bad in (0, -1, 1025, 2000):
+            with pytest.raises(avd_hip.AvdError, match=r"^avd status -1: cnn_chunk: 1 \.\.\. 1024 frames per forward pass$"):
+                c.set_option("cnn_chunk", bad)
+            assert c.get_option("cnn_chunk") == 128
+        for name in ("rerun_pairs", "fb_wide160_used", "no_such_option", ""):
+            with pytest.raises(avd_hip.AvdError, match=r"^avd status -1: unknown option: %s$" % name):
+                c.set_option(name, 1)
+        assert c.get_option("rerun_pairs") == 0 and c.get_option("fb_wide160_used") == 0
+        for name in ("no_such_option", "AVD_FB_MODE"):
+            with pytest.raises(avd_hip.AvdError, match=r"^avd status -1: unknown option: %s$" % name):
+                c.get_option(name)
+    for var, (name, cases) in _OPTION_ENV.items():
+        for text, want in cases:
+            monkeypatch.setenv(var, text)
+            with avd_hip.Context(0) as c:            # a fresh context per case: the variables are read by avd_create
+                got = {k: c.get_option(k) for k in _OPTION_DEFAULTS}
+            assert got == dict(_OPTION_DEFAULTS, **{name: want}), (var, text)
+        monkeypatch.delenv(var)
+    with avd_hip.Context(0) as c:
+        assert {k: c.get_option(k) for k in _OPTION_DEFAULTS} == _OPTION_DEFAULTS
