@@ -42,142 +42,271 @@ struct ConvGeom {
     int cpb;                                    // cin / 32
 };
 
-#define AVD_WAIT_VMC(n) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(n) : "memory")
-
-// MODE 0: the activation operand is a blocked activation, gathered per tap.  MODE 1 (the stem): the operand is the
-// zero-bordered 224 x 224 input image [frame][232][232][4 channels, the fourth zero]; half stage ky holds the 8 x 4 = 32
-// (kx, c) values of kernel row ky (kx = 7 and c = 3 carry zero weights), i.e. chunk j of a row = the two pixels
-// (2 ox + 2 j, 2 ox + 2 j + 1) of image row 2 oy + ky in border coordinates: 16 contiguous, 16-byte aligned bytes.
-template <int BM, int WAVES_M, int TI, int MODE, int KS>
-__global__ __launch_bounds__(512) void k_conv_bf16(const uint16_t* __restrict__ X, const uint16_t* __restrict__ Wt,
-                                                  const float* __restrict__ bias, const uint16_t* __restrict__ R,
-                                                  uint16_t* __restrict__ Y, ConvGeom g, int relu)
+// stem == true: (hin, win, cin, ksize, stride) describe the 7x7/2 convolution over the bordered input image
+ConvGeom conv_geom(int n, int hin, int win, int cin, int cout, int ksize, int stride, bool stem = false)
 {
-    constexpr int WAVES_N = 8 / WAVES_M, TJ = 4, BN = WAVES_N * 64;
-    static_assert(WAVES_M * TI * 16 == BM && (BM == 256 || BM == 128), "a workgroup covers 256 or 128 output pixels");
-    constexpr int RA = BM / 8, QA = RA / 16;               // activation rows / LDS-DMA instructions per wave and half stage
-    constexpr int RB = BN / 8;                              // weight rows a wave stages per half stage: 32, 16 or 8
-    constexpr int QB = (RB + 15) / 16;
-    constexpr int P = QA + QB;                              // LDS-DMA instructions per wave and half stage
-    constexpr int HALF_A = BM * 64, HALF_B = BN * 64, STAGE = HALF_A + HALF_B;
-    extern __shared__ __align__(16) char lds[];            // ring of four half stages [A | B]
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int wm = wave / WAVES_N, wn = wave % WAVES_N;
-    const int tiles_n = g.cout / BN, tiles_m = (g.m_out + BM - 1) / BM, total = tiles_m * tiles_n;
-    // the column tiles of one pixel block run together on one XCD (the gathered activation rows are fetched once)
-    const int per = (gridDim.x + 7) >> 3;
-    const int lid = (blockIdx.x & 7) * per + (blockIdx.x >> 3);
-    if (lid >= total) return;
-    const int m0 = (lid / tiles_n) * BM, n0 = (lid % tiles_n) * BN;
+    ConvGeom g;
+    g.hin = hin; g.win = win; g.cin = cin; g.cout = cout; g.ksize = ksize; g.stride = stride; g.pad = ksize / 2;
+    g.hout = (hin + 2 * g.pad - ksize) / stride + 1;
+    g.wout = (win + 2 * g.pad - ksize) / stride + 1;
+    g.m_out = n * g.hout * g.wout;
+    g.cpb = stem ? 1 : cin / 32;
+    g.nh = stem ? 7 : ksize * ksize * g.cpb;
+    return g;
+}
 
-    // ---- the activation rows this lane gathers per half stage (instruction q: tile row wave * RA + q * 16 + lane / 4)
-    // MODE 0 keeps per row: the pixel index of tap (0, 0) (rin0), a 9-bit mask of the taps that fall inside the image, and
-    // the chunk that belongs in this lane's LDS slot; a tap then costs one scalar offset and a dozen vector operations
-    int rin0[QA], cw[QA];
+__host__ __device__ constexpr int tiles_of(int m, int bm) { return (m + bm - 1) / bm; }
+
+// ---- one LDS plan per kernel shape: the kernel and its launcher both read it ---------------------------------------
+// A workgroup of eight waves, WAVES_M x WAVES_N, each wave TI x 4 MFMA tiles: BM pixels x BN output channels.  The ring
+// holds four half stages [A | B]; a layer with fewer than four half stages takes that many slots (more workgroups per CU).
+template <int BM_, int WAVES_M_, int TI_>
+struct ConvShape {
+    static constexpr int BM = BM_, WAVES_M = WAVES_M_, WAVES_N = 8 / WAVES_M, TI = TI_, TJ = 4, BN = WAVES_N * 64;
+    static_assert(WAVES_M * TI * 16 == BM && (BM == 256 || BM == 128), "a workgroup covers 256 or 128 output pixels");
+    static constexpr int RA = BM / 8, QA = RA / 16;         // activation rows / LDS-DMA instructions per wave and half stage
+    static constexpr int RB = BN / 8, QB = (RB + 15) / 16;  // weight rows a wave stages per half stage: 32, 16 or 8
+    static constexpr int P = QA + QB;                       // LDS-DMA instructions per wave and half stage
+    static constexpr int HALF_A = BM * 64, HALF_B = BN * 64, STAGE = HALF_A + HALF_B, RING = 4 * STAGE;
+    static constexpr size_t lds(int nh) { return (size_t)(nh < 4 ? nh : 4) * STAGE; }
+};
+
+// the expanding 1x1 behind a 3x3 whose BM x BN output tile stays on the CU (K = mid = BN), NCH chunks of BN output channels
+template <int BM, int BN, int TI, int TJ>
+struct ExpandSizes {
+    static constexpr int NCH = 4;
+    static constexpr int KS2 = BN / 32;                     // k steps of the expanding layer
+    static constexpr int A2 = BM * BN * 2, B2 = BN * BN * 2;   // bytes: the mid tile; one chunk of W3
+    static constexpr int NBLK = (BN / 16) * KS2;            // KiB blocks of one W3 chunk
+    static constexpr int NRES = TI * TJ / 2;                // residual loads (= output stores) per wave and chunk
+    static constexpr int BIAS3_BYTES = NCH * BN * 4;
+    static_assert(NBLK % 8 == 0 && NCH % 2 == 0 && NCH * BN <= 512, "a W3 block per wave, chunk pairs, one bias3 element per thread");
+};
+
+// k_conv3_expand: the expand's buffers live in the 3x3's ring.  W3 is RESIDENT when all of it fits beside the mid tile
+// (mid = 64: 32 KiB in one go, no barrier in the chunk loop); otherwise its chunks alternate between two buffers, the
+// second of which takes over the mid tile's LDS once the fragments are in registers.  W3 (its first chunk) is requested
+// during the 3x3's LAST step, into ring slots that step no longer reads: it reads slot (nh - 1) & 3 only, hence PHASE.
+//   resident (nh & 3 == 2, slot 1 live):  mid tile [0, A2) | W3 [2 STAGE, + NCH B2) | bias3 behind it
+//   otherwise (nh & 3 == 0, slot 3 live): W3 chunk c at (c & 1) B2 | mid tile [B2, B2 + A2) | bias3 behind the ring
+template <int BM_, int WAVES_M_, int TI_>
+struct FusedShape : ConvShape<BM_, WAVES_M_, TI_>, ExpandSizes<BM_, ConvShape<BM_, WAVES_M_, TI_>::BN, TI_, 4> {
+    using C = ConvShape<BM_, WAVES_M_, TI_>;
+    using E = ExpandSizes<BM_, C::BN, TI_, 4>;
+    static constexpr bool RESIDENT = E::NCH * E::B2 + E::BIAS3_BYTES <= 2 * C::STAGE && E::A2 <= 2 * C::STAGE;
+    static constexpr int W3BASE = RESIDENT ? 2 * C::STAGE : 0, A2BASE = RESIDENT ? 0 : E::B2;
+    static constexpr int BIAS3 = RESIDENT ? W3BASE + E::NCH * E::B2 : C::RING;
+    static constexpr int LDS = RESIDENT ? C::RING : C::RING + E::BIAS3_BYTES;
+    static constexpr int PHASE = RESIDENT ? 2 : 0;          // required nh & 3
+    static_assert(RESIDENT ? BIAS3 + E::BIAS3_BYTES <= C::RING : (E::B2 + E::A2 <= C::RING && 2 * E::B2 <= C::RING && E::B2 <= 2 * C::STAGE), "LDS plan");
+};
+
+// k_slab3_expand: [slab | ring of four W2 steps]; the expand takes all of it over once the slab is dead:
+//   W3 | mid tile | bias3 (mid 64, resident), else W3 chunk c at (c & 1) B2 | bias3 | ... mid tile at B2 until its fragments are read
+template <int MID>
+struct SlabShape : ConvShape<MID == 64 ? 256 : 128, MID == 64 ? 8 : 4, 2>, ExpandSizes<MID == 64 ? 256 : 128, MID, 2, 4> {
+    static_assert(MID == 64 || MID == 128, "the two early stages");
+    using C = ConvShape<MID == 64 ? 256 : 128, MID == 64 ? 8 : 4, 2>;
+    using E = ExpandSizes<C::BM, MID, 2, 4>;
+    static_assert(C::BN == MID, "one column tile");
+    static constexpr int CPB = MID / 32;                    // channel blocks of the input
+    static constexpr int HALO = MID == 64 ? 64 : 32;        // pixels in front of m0 (>= W + 1, whole pixel blocks)
+    static constexpr int NSLAB = C::BM + 2 * HALO, SLAB = NSLAB * CPB * 64;       // 384 x 128 B = 192 x 256 B = 48 KiB
+    static constexpr int KPS = MID == 64 ? 2 : 1;           // k blocks of W2 per step (a whole tap at 64 channels, a quarter tap at 128)
+    static constexpr int STEPB = MID * 64 * KPS, NSTEP = 9 * CPB / KPS;          // 8 KiB per step
+    static constexpr int LDS = SLAB + 4 * STEPB;            // ring of four: 80 KiB
+    static constexpr bool RESIDENT = E::NCH * E::B2 + E::A2 + E::BIAS3_BYTES <= LDS;
+    static constexpr int W3BASE = 0, A2BASE = RESIDENT ? E::NCH * E::B2 : E::B2, BIAS3 = RESIDENT ? A2BASE + E::A2 : 2 * E::B2;
+    static_assert(SLAB == 49152 && STEPB == 8192 && BIAS3 + E::BIAS3_BYTES <= LDS && A2BASE + E::A2 <= LDS, "LDS plan");
+};
+
+// ---- device parts shared by the three MFMA kernels -----------------------------------------------------------------
+// the column tiles of one pixel block run together on one XCD (the gathered activation rows are fetched once)
+__device__ __forceinline__ int xcd_tile()
+{
+    const int per = (gridDim.x + 7) >> 3;
+    return (blockIdx.x & 7) * per + (blockIdx.x >> 3);
+}
+
+template <int TI, int TJ>
+__device__ __forceinline__ void zero_acc(f32x4 (&acc)[TI][TJ])
+{
+#pragma unroll
+    for (int i = 0; i < TI; i++)
+#pragma unroll
+        for (int j = 0; j < TJ; j++) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+}
+
+// this lane's 16 bytes inside a KiB block of an output piece (16 pixels x 32 channels): pixel lane % 16, channels (lane / 16) * 8 ..
+__device__ __forceinline__ unsigned lane_in_block(int lane) { return (unsigned)((lane & 15) * 64 + (((lane >> 4) ^ swz((lane >> 2) & 3)) << 4)); }
+
+// ---- epilogue arithmetic: a lane's eight consecutive output channels of one pixel (accumulator tiles 2 jp, 2 jp + 1)
+struct Bias8 { f32x4 lo, hi; };
+__device__ __forceinline__ Bias8 bias8(const float* pb) { return {*reinterpret_cast<const f32x4*>(pb), *reinterpret_cast<const f32x4*>(pb + 4)}; }
+
+// bias (+ the residual: eight bf16, where there is one), ReLU, round to bf16
+__device__ __forceinline__ uint4 finish8(f32x4 lo, f32x4 hi, const Bias8& b, const uint4* residual, bool relu)
+{
+    lo += b.lo; hi += b.hi;
+    if (residual) {
+        const uint4 rv = *residual;
+        lo[0] += bf16_to_f32(rv.x & 0xFFFF); lo[1] += bf16_to_f32(rv.x >> 16);
+        lo[2] += bf16_to_f32(rv.y & 0xFFFF); lo[3] += bf16_to_f32(rv.y >> 16);
+        hi[0] += bf16_to_f32(rv.z & 0xFFFF); hi[1] += bf16_to_f32(rv.z >> 16);
+        hi[2] += bf16_to_f32(rv.w & 0xFFFF); hi[3] += bf16_to_f32(rv.w >> 16);
+    }
+    if (relu) {
+#pragma unroll
+        for (int e = 0; e < 4; e++) { lo[e] = fmaxf(lo[e], 0.f); hi[e] = fmaxf(hi[e], 0.f); }
+    }
+    uint4 pk;
+    pk.x = pack_bf16x2(lo[0], lo[1]);
+    pk.y = pack_bf16x2(lo[2], lo[3]);
+    pk.z = pack_bf16x2(hi[0], hi[1]);
+    pk.w = pack_bf16x2(hi[2], hi[3]);
+    return pk;
+}
+
+// ---- the activation operand of a gathering kernel: the BM / 8 tile rows this wave copies per half stage (instruction q:
+// tile row wave * RA + q * 16 + lane / 4).
+// MODE 0: a blocked activation, gathered per tap.  Kept per row: the pixel index of tap (0, 0) (rin0), a 9-bit mask of the
+// taps that fall inside the image, and the chunk that belongs in this lane's LDS slot; a tap then costs one scalar offset and
+// a dozen vector operations.  Half stages come in K order: tap (dy, dx), then channel block.
+// MODE 1 (the stem): the operand is the zero-bordered 224 x 224 input image [frame][232][232][4 channels, the fourth zero];
+// half stage ky holds the 8 x 4 = 32 (kx, c) values of kernel row ky (kx = 7 and c = 3 carry zero weights), i.e. chunk j of a
+// row = the two pixels (2 ox + 2 j, 2 ox + 2 j + 1) of image row 2 oy + ky in border coordinates: 16 contiguous, 16-byte
+// aligned bytes.
+template <int BM, int MODE, int KS>
+struct TapGather {
+    static constexpr int RA = BM / 8, QA = RA / 16;
+    int rin0[QA], cw[QA];                                   // filled by the kernel (k_conv_bf16 says why)
     unsigned tapmask[QA];
-    const int hw = g.hout * g.wout;
-#pragma unroll
-    for (int q = 0; q < QA; q++) {
-        const int r = wave * RA + q * 16 + (lane >> 2), m = m0 + r;
-        const bool valid = m < g.m_out;
-        const int img = m / hw, rem = m - img * hw, oy = rem / g.wout, ox = rem - oy * g.wout;
-        cw[q] = (lane & 3) ^ swz((r >> 2) & 3);             // the chunk that belongs in this lane's LDS slot
-        if (MODE == 1) {                                     // byte offset of pixel (2 oy, 2 ox + 2 chunk) of the bordered image
-            rin0[q] = valid ? ((img * kImgSide + 2 * oy) * kImgSide + 2 * ox + 2 * cw[q]) * 8 : 0;
-            tapmask[q] = 0;
-        } else {
-            const int y0 = oy * g.stride - g.pad, x0 = ox * g.stride - g.pad;
-            rin0[q] = (img * g.hin + y0) * g.win + x0;
-            unsigned mk = 0;
-#pragma unroll
-            for (int t = 0; t < KS * KS; t++) {
-                const int yi = y0 + t / KS, xi = x0 + t % KS;
-                if (valid && (unsigned)yi < (unsigned)g.hin && (unsigned)xi < (unsigned)g.win) mk |= 1u << t;
-            }
-            tapmask[q] = mk;
-        }
-    }
-    unsigned vob[QB];
-#pragma unroll
-    for (int q = 0; q < QB; q++) {
-        const int r = wave * RB + q * 16 + (lane >> 2);
-        vob[q] = (unsigned)((r >> 4) * g.nh * 1024 + (r & 15) * 64 + (lane & 3) * 16);
-    }
-    const char* xb = reinterpret_cast<const char*>(X);
-    int is_cb = 0, is_dy = 0, is_dx = 0;                    // channel block and tap of the next half stage to be issued
-    auto issue = [&](int hs) __attribute__((always_inline)) {
-        char* st = lds + (hs & 3) * STAGE;
+    int cb = 0, dy = 0, dx = 0;                             // channel block and tap of the next half stage to be issued
+
+    // half stage hs (they are issued in order) into the A half of ring slot `st`
+    __device__ __forceinline__ void issue(const ConvGeom& g, const char* xb, char* st, int hs, int wave, int lane)
+    {
 #pragma unroll
         for (int q = 0; q < QA; q++) {
             unsigned off;
             if (MODE == 1) {
                 off = (unsigned)(rin0[q] + hs * (kImgSide * 8));  // kernel row ky = hs: one image row down
             } else {
-                const int rin = rin0[q] + is_dy * g.win + is_dx;  // (the tap offset is uniform: scalar arithmetic)
-                const bool ok = (tapmask[q] >> (is_dy * KS + is_dx)) & 1u;
-                off = (unsigned)(kZeroPage * 2) + (unsigned)((rin >> 4) * g.cpb + is_cb) * 1024u + (unsigned)((rin & 15) * 64) +
+                const int rin = rin0[q] + dy * g.win + dx;        // (the tap offset is uniform: scalar arithmetic)
+                const bool ok = (tapmask[q] >> (dy * KS + dx)) & 1u;
+                off = (unsigned)(kZeroPage * 2) + (unsigned)((rin >> 4) * g.cpb + cb) * 1024u + (unsigned)((rin & 15) * 64) +
                       (unsigned)((cw[q] ^ swz((rin >> 2) & 3)) << 4);
-                off = ok ? off : (unsigned)(lane * 16);       // outside the image (or past the last pixel): the zero page
+                off = ok ? off : (unsigned)(lane * 16);           // outside the image (or past the last pixel): the zero page
             }
             __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(xb + off),
                                              (__attribute__((address_space(3))) void*)(st + (wave * RA + q * 16) * 64), 16, 0, 0);
         }
-        const char* wb = reinterpret_cast<const char*>(Wt + ((int64_t)(n0 >> 4) * g.nh + hs) * 512);
-#pragma unroll
-        for (int q = 0; q < QB; q++) {
-            char* dst = st + HALF_A + (wave * RB + q * 16) * 64;
-            if (q * 16 + 16 <= RB) {
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(wb + vob[q]),
-                                                 (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
-            } else if (lane < 32) {
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(wb + vob[q]),
-                                                 (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
-            }
+    }
+    // ... and on to the next half stage (after the weight loads of this one: the order the kernels were tuned with)
+    __device__ __forceinline__ void advance(const ConvGeom& g)
+    {
+        if (++cb == g.cpb) {
+            cb = 0;
+            if (++dx == KS) { dx = 0; ++dy; }
         }
-        if (++is_cb == g.cpb) {
-            is_cb = 0;
-            if (++is_dx == KS) { is_dx = 0; ++is_dy; }
-        }
-    };
+    }
+};
 
-    f32x4 acc[TI][TJ];
+// ---- one step of the ring of four half stages (the scheme of avd_vit.hip; K is a run-time value here).
+// The half stage about to be read must have landed; `younger` half stages (P LDS-DMAs each) were issued after it by this
+// wave.  The barrier says so for every wave, and that everyone is done with the half stage before: its slot may be refilled.
+template <int P>
+__device__ __forceinline__ void ring_wait(int younger)
+{
+    __builtin_amdgcn_sched_barrier(0);
+    if (younger >= 2) AVD_WAIT_VM(2 * P);
+    else if (younger == 1) AVD_WAIT_VM(P);
+    else AVD_WAIT_VM(0);
+    __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_sched_barrier(0);
+}
+__device__ __forceinline__ int ring_younger(int hs, int nh) { return (hs + 2 < nh - 1 ? hs + 2 : nh - 1) - hs; }
+
+// fragment reads of ring slot [A | B] and the wave's TI x TJ MFMAs (transposed product: b first)
+template <int TI, int TJ>
+__device__ __forceinline__ void ring_mfma(f32x4 (&acc)[TI][TJ], const char* a_half, const char* b_half, int wm, int wn, int lane)
+{
+    const int chunk = lane >> 4, r16 = lane & 15;
+    bf16x8 a[TI], b[TJ];
+#pragma unroll
+    for (int j = 0; j < TJ; j++) b[j] = frag(b_half, b_row_of(wn, 64, j, r16), chunk);
+#pragma unroll
+    for (int i = 0; i < TI; i++) a[i] = frag(a_half, (wm * TI + i) * 16 + r16, chunk);
 #pragma unroll
     for (int i = 0; i < TI; i++)
 #pragma unroll
-        for (int j = 0; j < TJ; j++) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-    // weight row -> MFMA row permutation of avd_vit.hip: a lane ends up with eight consecutive output channels
-    auto b_row = [&](int j, int rho) __attribute__((always_inline)) {
-        return wn * 64 + (j >> 1) * 32 + (rho >> 2) * 8 + (j & 1) * 4 + (rho & 3);
+        for (int j = 0; j < TJ; j++) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b[j], a[i], acc[i][j], 0, 0, 0);
+}
+
+// One implicit-GEMM convolution.  MODE / KS: see TapGather.
+template <int BM, int WAVES_M, int TI, int MODE, int KS>
+__global__ __launch_bounds__(512) void k_conv_bf16(const uint16_t* __restrict__ X, const uint16_t* __restrict__ Wt,
+                                                  const float* __restrict__ bias, const uint16_t* __restrict__ R,
+                                                  uint16_t* __restrict__ Y, ConvGeom g, int relu)
+{
+    using S = ConvShape<BM, WAVES_M, TI>;
+    constexpr int TJ = S::TJ, BN = S::BN;
+    extern __shared__ __align__(16) char lds[];            // ring of four half stages [A | B]
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int wm = wave / S::WAVES_N, wn = wave % S::WAVES_N;
+    const int tiles_n = g.cout / BN, total = tiles_of(g.m_out, BM) * tiles_n;
+    const int lid = xcd_tile();
+    if (lid >= total) return;
+    const int m0 = (lid / tiles_n) * BM, n0 = (lid % tiles_n) * BN;
+
+    // The per-row state is filled HERE, not in a member function: as a function of its own the tap-mask loop is compiled
+    // without branches (60-125 instructions fewer) and every 3x3 shape's scalar register count moves by 1-4.
+    TapGather<BM, MODE, KS> ga;
+    const int hw = g.hout * g.wout;
+#pragma unroll
+    for (int q = 0; q < ga.QA; q++) {
+        const int r = wave * ga.RA + q * 16 + (lane >> 2), m = m0 + r;
+        const bool valid = m < g.m_out;
+        const int img = m / hw, rem = m - img * hw, oy = rem / g.wout, ox = rem - oy * g.wout;
+        ga.cw[q] = (lane & 3) ^ swz((r >> 2) & 3);         // the chunk that belongs in this lane's LDS slot
+        if (MODE == 1) {                                 // byte offset of pixel (2 oy, 2 ox + 2 chunk) of the bordered image
+            ga.rin0[q] = valid ? ((img * kImgSide + 2 * oy) * kImgSide + 2 * ox + 2 * ga.cw[q]) * 8 : 0;
+            ga.tapmask[q] = 0;
+        } else {
+            const int y0 = oy * g.stride - g.pad, x0 = ox * g.stride - g.pad;
+            ga.rin0[q] = (img * g.hin + y0) * g.win + x0;
+            unsigned mk = 0;
+#pragma unroll
+            for (int t = 0; t < KS * KS; t++) {
+                const int yi = y0 + t / KS, xi = x0 + t % KS;
+                if (valid && (unsigned)yi < (unsigned)g.hin && (unsigned)xi < (unsigned)g.win) mk |= 1u << t;
+            }
+            ga.tapmask[q] = mk;
+        }
+    }
+    unsigned vob[S::QB];
+    stage_offsets<S::RB>(vob, g.nh, wave, lane);
+    auto issue = [&](int hs) __attribute__((always_inline)) {
+        char* st = lds + (hs & 3) * S::STAGE;
+        ga.issue(g, reinterpret_cast<const char*>(X), st, hs, wave, lane);
+        stage_rows<S::RB>(reinterpret_cast<const char*>(Wt + ((int64_t)(n0 >> 4) * g.nh + hs) * 512), vob, st + S::HALF_A, wave, lane);
+        ga.advance(g);
     };
 
+    f32x4 acc[TI][TJ];
+    zero_acc(acc);
     const int nh = g.nh;
     for (int hs = 0; hs < 3 && hs < nh; hs++) issue(hs);
     for (int hs = 0; hs < nh; hs++) {
-        // half stage hs must have landed; younger LDS-DMAs of this wave: the half stages issued after it
-        __builtin_amdgcn_sched_barrier(0);
-        const int younger = (hs + 2 < nh - 1 ? hs + 2 : nh - 1) - hs;
-        if (younger >= 2) AVD_WAIT_VMC(2 * P);
-        else if (younger == 1) AVD_WAIT_VMC(P);
-        else AVD_WAIT_VMC(0);
-        __builtin_amdgcn_s_barrier();                        // ... for every wave, and everyone is done with half stage hs - 1
-        __builtin_amdgcn_sched_barrier(0);
+        ring_wait<S::P>(ring_younger(hs, nh));
         if (hs + 3 < nh) issue(hs + 3);
-        const char* cur = lds + (hs & 3) * STAGE;
-        const int chunk = lane >> 4, r16 = lane & 15;
-        bf16x8 a[TI], b[TJ];
-#pragma unroll
-        for (int j = 0; j < TJ; j++) b[j] = frag(cur + HALF_A, b_row(j, r16), chunk);
-#pragma unroll
-        for (int i = 0; i < TI; i++) a[i] = frag(cur, (wm * TI + i) * 16 + r16, chunk);
-#pragma unroll
-        for (int i = 0; i < TI; i++)
-#pragma unroll
-            for (int j = 0; j < TJ; j++) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b[j], a[i], acc[i][j], 0, 0, 0);
+        const char* cur = lds + (hs & 3) * S::STAGE;
+        ring_mfma(acc, cur, cur + S::HALF_A, wm, wn, lane);
     }
 
     // ---- epilogue: bias (+ residual), ReLU, bf16, 16 bytes per lane into the blocked layout of the next operand
-    const unsigned loff = (unsigned)((lane & 15) * 64 + (((lane >> 4) ^ swz((lane >> 2) & 3)) << 4));
+    const unsigned loff = lane_in_block(lane);
     const int cblocks = g.cout >> 5;
 #pragma unroll
     for (int i = 0; i < TI; i++) {
@@ -185,27 +314,10 @@ __global__ __launch_bounds__(512) void k_conv_bf16(const uint16_t* __restrict__ 
 #pragma unroll
         for (int jp = 0; jp < TJ / 2; jp++) {
             const int col0 = n0 + wn * 64 + jp * 32;
-            const float* pb = bias + col0 + (lane >> 4) * 8;
-            f32x4 lo = acc[i][2 * jp] + *reinterpret_cast<const f32x4*>(pb);
-            f32x4 hi = acc[i][2 * jp + 1] + *reinterpret_cast<const f32x4*>(pb + 4);
             const int64_t boff = (int64_t)kZeroPage * 2 + ((int64_t)rblk * cblocks + (col0 >> 5)) * 1024;
-            if (R) {
-                const uint4 rv = *reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(R) + boff + loff);
-                lo[0] += bf16_to_f32(rv.x & 0xFFFF); lo[1] += bf16_to_f32(rv.x >> 16);
-                lo[2] += bf16_to_f32(rv.y & 0xFFFF); lo[3] += bf16_to_f32(rv.y >> 16);
-                hi[0] += bf16_to_f32(rv.z & 0xFFFF); hi[1] += bf16_to_f32(rv.z >> 16);
-                hi[2] += bf16_to_f32(rv.w & 0xFFFF); hi[3] += bf16_to_f32(rv.w >> 16);
-            }
-            if (relu) {
-#pragma unroll
-                for (int e = 0; e < 4; e++) { lo[e] = fmaxf(lo[e], 0.f); hi[e] = fmaxf(hi[e], 0.f); }
-            }
-            uint4 pk;
-            pk.x = pack_bf16x2(lo[0], lo[1]);
-            pk.y = pack_bf16x2(lo[2], lo[3]);
-            pk.z = pack_bf16x2(hi[0], hi[1]);
-            pk.w = pack_bf16x2(hi[2], hi[3]);
-            *reinterpret_cast<uint4*>(reinterpret_cast<char*>(Y) + boff + loff) = pk;
+            const uint4* res = R ? reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(R) + boff + loff) : nullptr;
+            *reinterpret_cast<uint4*>(reinterpret_cast<char*>(Y) + boff + loff) =
+                finish8(acc[i][2 * jp], acc[i][2 * jp + 1], bias8(bias + col0 + (lane >> 4) * 8), res, relu);
         }
     }
 }
@@ -216,299 +328,233 @@ __global__ __launch_bounds__(512) void k_conv_bf16(const uint16_t* __restrict__ 
 // (K = mid is short: they move a residual and an output four times the size of their input and multiply little:
 // 140-260 TFLOP/s); fused, their operand comes from LDS, their residual reads and output stores overlap the NEXT
 // workgroup's 3x3 on the same CU, and the mid activation's write + read (2 x 48 MB per block at 56 x 56) disappears.
-//   1. the 3x3 exactly as k_conv_bf16 (same ring, same K order: same bits), BN = mid, one column tile;
+//   1. the 3x3, BN = mid, one column tile: from the gather ring exactly as k_conv_bf16 (k_conv3_expand) or from a slab of
+//      the input in LDS (k_slab3_expand); same K order either way: same bits;
 //   2. its epilogue (bias, ReLU, bf16) goes to LDS in the operand layout (KS2 half tiles of BM rows x 64 B) and every
-//      wave takes the fragments of ITS pixel rows into registers (KS2 x TI fragments) -- the ring is free again;
+//      wave takes the fragments of ITS pixel rows into registers (KS2 x TI fragments) -- the 3x3's LDS is free again;
 //   3. the expanding 1x1 in NCH = 4 chunks of BN output channels: W3's chunk (BN x mid, one contiguous piece of the
-//      blocked weight) is copied into one of two LDS buffers by LDS-DMA while the previous chunk multiplies; epilogue
-//      = k_conv_bf16's (bias + residual + ReLU -> 16-byte stores into the blocked layout), the residual loads of a chunk
-//      are issued before its MFMAs.  Same k order as the unfused layer: the result is bit-identical to conv2 -> conv3.
+//      blocked weight) is copied into LDS by LDS-DMA (all four at once where they fit -- RESIDENT --, else into one of two
+//      buffers while the previous chunk multiplies); epilogue = k_conv_bf16's (bias + residual + ReLU -> 16-byte stores
+//      into the blocked layout).  Same k order as the unfused layer: the result is bit-identical to conv2 -> conv3.
+// Expand is steps 2 and 3, placed in LDS by the kernel's shape S (W3BASE, A2BASE, BIAS3, RESIDENT).  The kernels differ in
+// where the 3x3's A operand comes from and in when they request W3 and the first residuals.
+template <class S>
+struct Expand {
+    static constexpr int BM = S::BM, BN = S::BN, TI = S::TI, TJ = S::TJ, NCH = S::NCH, KS2 = S::KS2;
+    static constexpr bool RESIDENT = S::RESIDENT;
+    // PF: a chunk's residuals are requested one chunk ahead (two register sets); without it (the 128-channel shapes, whose
+    // fragments of the mid tile take 32 registers) at the top of their own chunk, in front of its MFMAs
+    static constexpr bool PF = RESIDENT;
+    static constexpr int cblocks = (NCH * BN) >> 5;
+    char* lds;
+    const uint16_t *W3, *R;
+    uint16_t* Y;
+    int wave, lane, wm, wn;
+    unsigned loff, obase;
+    uint4 rv0[TI][TJ / 2];                                  // with PF: the residuals of chunk 0, requested by the kernel (load_res(0, rv0))
+
+    __device__ __forceinline__ Expand(char* lds_, const uint16_t* W3_, const uint16_t* R_, uint16_t* Y_, int m0, int wave_, int lane_)
+        : lds(lds_), W3(W3_), R(R_), Y(Y_), wave(wave_), lane(lane_), wm(wave_ / S::WAVES_N), wn(wave_ % S::WAVES_N), loff(lane_in_block(lane_))
+    {
+        // byte offset of this lane's 16 bytes of output piece (chunk 0, row tile 0, column pair 0): 32-bit (an activation is < 4 GiB)
+        obase = (unsigned)(kZeroPage * 2) + (unsigned)(((m0 >> 4) + wm * TI) * cblocks + wn * 2) * 1024u + loff;
+    }
+    __device__ __forceinline__ unsigned out_off(int c, int i, int jp) const { return obase + (unsigned)((i * cblocks + c * (BN >> 5) + jp) * 1024); }
+    __device__ __forceinline__ char* w3_buf(int c) const { return lds + S::W3BASE + (RESIDENT ? c : (c & 1)) * S::B2; }
+
+    __device__ __forceinline__ void issue_w3(int c)
+    {
+        char* buf = w3_buf(c);
+        const char* src = reinterpret_cast<const char*>(W3) + (size_t)c * S::NBLK * 1024 + lane * 16;
+#pragma unroll
+        for (int t0 = 0; t0 < S::NBLK; t0 += 8) {
+            const int t = t0 + wave, rbl = t / KS2, kb = t % KS2;     // block t of the chunk: 16 weight rows x 32 k
+            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + t * 1024),
+                                             (__attribute__((address_space(3))) void*)(buf + kb * (BN * 64) + rbl * 1024), 16, 0, 0);
+        }
+    }
+    // all of W3 where it is resident, else its first chunk
+    __device__ __forceinline__ void issue_first_w3()
+    {
+        if (RESIDENT) {
+#pragma unroll
+            for (int c = 0; c < NCH; c++) issue_w3(c);
+        } else {
+            issue_w3(0);
+        }
+    }
+    __device__ __forceinline__ void load_res(int c, uint4 (&rv)[TI][TJ / 2])
+    {
+#pragma unroll
+        for (int i = 0; i < TI; i++)
+#pragma unroll
+            for (int jp = 0; jp < TJ / 2; jp++) rv[i][jp] = *reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(R) + out_off(c, i, jp));
+    }
+
+    // acc: the 3x3's sums, its last MFMAs issued.  b3v: this thread's element of bias3, fetched before the first LDS-DMA entered
+    // the in-order vector-memory queue (a load issued inside the chunk loop would make the compiler wait for everything in flight
+    // around it); it is parked in LDS here.  W3_NOW: W3 (its first chunk) is requested here, as soon as the 3x3's LDS is dead;
+    // otherwise the kernel has requested it already.  With PF the kernel has also requested the residuals of chunk 0.
+    template <bool W3_NOW>
+    __device__ __forceinline__ void run(const f32x4 (&acc2)[TI][TJ], const float* __restrict__ bias2, float b3v)
+    {
+        const int chunk = lane >> 4, r16 = lane & 15;
+        char* const a2 = lds + S::A2BASE;
+        float* const lbias3 = reinterpret_cast<float*>(lds + S::BIAS3);
+        // ---- 2. the mid tile -> LDS (operand layout) -> this wave's fragments
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();                        // every wave has read its last fragments: the 3x3's LDS is free
+        __builtin_amdgcn_sched_barrier(0);
+        // the 3x3's bias: this lane's 16 values.  (The compiler puts a vmcnt(0) in front of the LDS stores below anyway, because
+        // LDS-DMAs are in flight, so this load costs no extra wait.)
+        Bias8 b2[TJ / 2];
+#pragma unroll
+        for (int jp = 0; jp < TJ / 2; jp++) b2[jp] = bias8(bias2 + wn * 64 + jp * 32 + (lane >> 4) * 8);
+        if (W3_NOW) issue_first_w3();
+        if (threadIdx.x < NCH * BN) lbias3[threadIdx.x] = b3v;
+#pragma unroll
+        for (int i = 0; i < TI; i++)
+#pragma unroll
+            for (int jp = 0; jp < TJ / 2; jp++)
+                *reinterpret_cast<uint4*>(a2 + (wn * 2 + jp) * (BM * 64) + (wm * TI + i) * 1024 + loff) =
+                    finish8(acc2[i][2 * jp], acc2[i][2 * jp + 1], b2[jp], nullptr, true);
+        __builtin_amdgcn_sched_barrier(0);
+        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");   // this wave's part of W3 has landed, its part of the mid tile is written
+        __builtin_amdgcn_s_barrier();                        // ... and everybody else's
+        __builtin_amdgcn_sched_barrier(0);
+        bf16x8 am[KS2][TI];
+#pragma unroll
+        for (int ks = 0; ks < KS2; ks++)
+#pragma unroll
+            for (int i = 0; i < TI; i++) am[ks][i] = frag(a2 + ks * (BM * 64), (wm * TI + i) * 16 + r16, chunk);
+        if (!RESIDENT) {                                     // the second W3 buffer takes over the mid tile's LDS
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            __builtin_amdgcn_s_barrier();
+            __builtin_amdgcn_sched_barrier(0);
+        }
+
+        f32x4 acc[TI][TJ];
+        uint4 rv[PF ? 2 : 1][TI][TJ / 2];                   // residuals: the chunk being finished [and the next one, in flight]
+        if (PF) {
+#pragma unroll
+            for (int i = 0; i < TI; i++)
+#pragma unroll
+                for (int jp = 0; jp < TJ / 2; jp++) rv[0][i][jp] = rv0[i][jp];
+        }
+        // ---- 3. the expanding 1x1, BN output channels at a time.  Vector-memory queue of a wave (in order), resident W3: res(1) st(0) |
+        // res(2) st(1) | res(3) st(2) | st(3); otherwise res(c) DMA(c + 1) st(c) per chunk: the wait for DMA(c + 1) at the end of
+        // iteration c leaves the stores of chunk c in flight.  The loop is unrolled by two: the residual buffers alternate.
+#pragma unroll 1
+        for (int c2 = 0; c2 < NCH; c2 += 2)
+#pragma unroll
+        for (int cc = 0; cc < 2; cc++) {
+            const int c = c2 + cc;
+            if (!PF) load_res(c, rv[0]);
+            if (!RESIDENT && c + 1 < NCH) issue_w3(c + 1);
+            if (PF && c + 1 < NCH) load_res(c + 1, rv[PF ? (c + 1) & 1 : 0]);
+            __builtin_amdgcn_sched_barrier(0);
+            zero_acc(acc);
+            const char* buf = w3_buf(c);
+#pragma unroll
+            for (int ks = 0; ks < KS2; ks++) {
+                bf16x8 b[TJ];
+#pragma unroll
+                for (int j = 0; j < TJ; j++) b[j] = frag(buf + ks * (BN * 64), b_row_of(wn, 64, j, r16), chunk);
+#pragma unroll
+                for (int i = 0; i < TI; i++)
+#pragma unroll
+                    for (int j = 0; j < TJ; j++) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b[j], am[ks][i], acc[i][j], 0, 0, 0);
+            }
+#pragma unroll
+            for (int i = 0; i < TI; i++)
+#pragma unroll
+                for (int jp = 0; jp < TJ / 2; jp++)
+                    *reinterpret_cast<uint4*>(reinterpret_cast<char*>(Y) + out_off(c, i, jp)) =
+                        finish8(acc[i][2 * jp], acc[i][2 * jp + 1], bias8(lbias3 + c * BN + wn * 64 + jp * 32 + (lane >> 4) * 8),
+                                &rv[PF ? (c & 1) : 0][i][jp], true);
+            __builtin_amdgcn_sched_barrier(0);
+            if (!RESIDENT && c + 1 < NCH) {
+                AVD_WAIT_VM((PF ? 2 : 1) * S::NRES);         // younger than DMA(c + 1): [res(c + 1),] st(c)
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                __builtin_amdgcn_s_barrier();                // the next chunk has landed for every wave; everyone is done reading this one
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+    }
+};
+
+// The fused block with the 3x3 gathered as in k_conv_bf16 (same ring, same K order); stride 1 or 2.  W3 (its first chunk) and
+// the first residuals are requested during the 3x3's LAST step, into ring slots that step no longer reads (FusedShape).
 template <int BM, int WAVES_M, int TI>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_conv3_expand(const uint16_t* __restrict__ X, const uint16_t* __restrict__ W2,
                                                      const float* __restrict__ bias2, const uint16_t* __restrict__ W3,
                                                      const float* __restrict__ bias3, const uint16_t* __restrict__ R,
                                                      uint16_t* __restrict__ Y, ConvGeom g)
 {
-    constexpr int KS = 3, WAVES_N = 8 / WAVES_M, TJ = 4, BN = WAVES_N * 64;
-    static_assert(WAVES_M * TI * 16 == BM, "tile rows");
-    constexpr int RA = BM / 8, QA = RA / 16, RB = BN / 8, QB = (RB + 15) / 16, P = QA + QB;
-    constexpr int HALF_A = BM * 64, HALF_B = BN * 64, STAGE = HALF_A + HALF_B, RING = 4 * STAGE;
-    constexpr int KS2 = BN / 32;                            // k steps of the expanding layer (K = mid = BN)
-    constexpr int A2 = BM * BN * 2, B2 = BN * BN * 2;       // bytes: the mid tile; one chunk of W3
-    constexpr int NBLK = (BN / 16) * KS2;                   // KiB blocks of one W3 chunk
-    static_assert(A2 + B2 <= RING && 2 * B2 <= RING && NBLK % 8 == 0, "the expand's buffers live in the 3x3's ring");
-    constexpr int NCH = 4;
+    using S = FusedShape<BM, WAVES_M, TI>;
+    constexpr int TJ = S::TJ, KS = 3;
     extern __shared__ __align__(16) char lds[];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int wm = wave / WAVES_N, wn = wave % WAVES_N;
-    const int total = (g.m_out + BM - 1) / BM;
-    const int per = (gridDim.x + 7) >> 3;
-    const int lid = (blockIdx.x & 7) * per + (blockIdx.x >> 3);
-    if (lid >= total) return;
+    const int wm = wave / S::WAVES_N, wn = wave % S::WAVES_N;
+    const int lid = xcd_tile();
+    if (lid >= tiles_of(g.m_out, BM)) return;
     const int m0 = lid * BM;
-    // The expanding layer's bias is fetched NOW, before the first LDS-DMA enters the in-order vector-memory queue (one element per
-    // thread, parked in LDS after the 3x3): a load issued inside the chunk loop would make the compiler wait for everything in
-    // flight around it.
-    static_assert(NCH * BN <= 512, "one bias3 element per thread");
-    float b3v = threadIdx.x < NCH * BN ? bias3[threadIdx.x] : 0.f;
+    float b3v = threadIdx.x < S::NCH * S::BN ? bias3[threadIdx.x] : 0.f;
 
-    int rin0[QA], cw[QA];
-    unsigned tapmask[QA];
+    TapGather<BM, 0, KS> ga;                                // filled as in k_conv_bf16 (MODE 0)
     const int hw = g.hout * g.wout;
 #pragma unroll
-    for (int q = 0; q < QA; q++) {
-        const int r = wave * RA + q * 16 + (lane >> 2), m = m0 + r;
+    for (int q = 0; q < ga.QA; q++) {
+        const int r = wave * ga.RA + q * 16 + (lane >> 2), m = m0 + r;
         const bool valid = m < g.m_out;
         const int img = m / hw, rem = m - img * hw, oy = rem / g.wout, ox = rem - oy * g.wout;
-        cw[q] = (lane & 3) ^ swz((r >> 2) & 3);
+        ga.cw[q] = (lane & 3) ^ swz((r >> 2) & 3);
         const int y0 = oy * g.stride - g.pad, x0 = ox * g.stride - g.pad;
-        rin0[q] = (img * g.hin + y0) * g.win + x0;
+        ga.rin0[q] = (img * g.hin + y0) * g.win + x0;
         unsigned mk = 0;
 #pragma unroll
         for (int t = 0; t < KS * KS; t++) {
             const int yi = y0 + t / KS, xi = x0 + t % KS;
             if (valid && (unsigned)yi < (unsigned)g.hin && (unsigned)xi < (unsigned)g.win) mk |= 1u << t;
         }
-        tapmask[q] = mk;
+        ga.tapmask[q] = mk;
     }
-    unsigned vob[QB];
-#pragma unroll
-    for (int q = 0; q < QB; q++) {
-        const int r = wave * RB + q * 16 + (lane >> 2);
-        vob[q] = (unsigned)((r >> 4) * g.nh * 1024 + (r & 15) * 64 + (lane & 3) * 16);
-    }
-    const char* xb = reinterpret_cast<const char*>(X);
-    int is_cb = 0, is_dy = 0, is_dx = 0;
+    unsigned vob[S::QB];
+    stage_offsets<S::RB>(vob, g.nh, wave, lane);
     auto issue = [&](int hs) __attribute__((always_inline)) {
-        char* st = lds + (hs & 3) * STAGE;
-#pragma unroll
-        for (int q = 0; q < QA; q++) {
-            const int rin = rin0[q] + is_dy * g.win + is_dx;
-            const bool ok = (tapmask[q] >> (is_dy * KS + is_dx)) & 1u;
-            unsigned off = (unsigned)(kZeroPage * 2) + (unsigned)((rin >> 4) * g.cpb + is_cb) * 1024u + (unsigned)((rin & 15) * 64) +
-                           (unsigned)((cw[q] ^ swz((rin >> 2) & 3)) << 4);
-            off = ok ? off : (unsigned)(lane * 16);
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(xb + off),
-                                             (__attribute__((address_space(3))) void*)(st + (wave * RA + q * 16) * 64), 16, 0, 0);
-        }
-        const char* wb = reinterpret_cast<const char*>(W2 + (int64_t)hs * 512);
-#pragma unroll
-        for (int q = 0; q < QB; q++) {
-            char* dst = st + HALF_A + (wave * RB + q * 16) * 64;
-            if (q * 16 + 16 <= RB) {
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(wb + vob[q]),
-                                                 (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
-            } else if (lane < 32) {
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(wb + vob[q]),
-                                                 (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
-            }
-        }
-        if (++is_cb == g.cpb) {
-            is_cb = 0;
-            if (++is_dx == KS) { is_dx = 0; ++is_dy; }
-        }
+        char* st = lds + (hs & 3) * S::STAGE;
+        ga.issue(g, reinterpret_cast<const char*>(X), st, hs, wave, lane);
+        stage_rows<S::RB>(reinterpret_cast<const char*>(W2 + (int64_t)hs * 512), vob, st + S::HALF_A, wave, lane);
+        ga.advance(g);
     };
-
     f32x4 acc[TI][TJ];
-    auto zero_acc = [&]() __attribute__((always_inline)) {
-#pragma unroll
-        for (int i = 0; i < TI; i++)
-#pragma unroll
-            for (int j = 0; j < TJ; j++) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-    };
-    zero_acc();
-    auto b_row = [&](int j, int rho) __attribute__((always_inline)) {
-        return wn * 64 + (j >> 1) * 32 + (rho >> 2) * 8 + (j & 1) * 4 + (rho & 3);
-    };
-    const int chunk = lane >> 4, r16 = lane & 15;
-
+    zero_acc(acc);
     asm volatile("" : "+v"(b3v));                            // it has arrived (as far as the compiler is concerned too) before the queue fills
+    Expand<S> ex(lds, W3, R, Y, m0, wave, lane);
 
-    // LDS after the 3x3.  W3 is RESIDENT when all of it fits beside the mid tile (mid = 64: 32 KiB in one go, no barrier in the
-    // chunk loop); otherwise its chunks alternate between two buffers, the second of which takes over the mid tile's LDS once
-    // the fragments are in registers.  W3 (its first chunk) and the first residuals are requested during the 3x3's LAST step,
-    // into ring slots that step no longer reads: the last step reads slot (nh - 1) & 3 only (checked by the launcher).
-    //   resident (nh & 3 == 2, slot 1 live):  mid tile [0, A2) | W3 [2 STAGE, + NCH B2) | bias3 behind it
-    //   otherwise (nh & 3 == 0, slot 3 live): W3 chunk c at (c & 1) B2 | mid tile [B2, B2 + A2) | bias3 behind the ring
-    constexpr bool RESIDENT = NCH * B2 + NCH * BN * 4 <= 2 * STAGE && A2 <= 2 * STAGE;
-    static_assert(RESIDENT ? (2 * STAGE + NCH * B2 + NCH * BN * 4 <= RING) : (B2 + A2 <= RING && 2 * B2 <= RING && B2 <= 2 * STAGE), "LDS plan");
-    constexpr int W3BASE = RESIDENT ? 2 * STAGE : 0, A2BASE = RESIDENT ? 0 : B2;
-    constexpr int NRES = TI * TJ / 2;                       // residual loads (= output stores) per wave and chunk
-    char* const a2 = lds + A2BASE;
-    float* const lbias3 = reinterpret_cast<float*>(lds + (RESIDENT ? W3BASE + NCH * B2 : RING));
-    auto issue_w3 = [&](int c) __attribute__((always_inline)) {
-        char* buf = lds + W3BASE + (RESIDENT ? c : (c & 1)) * B2;
-        const char* src = reinterpret_cast<const char*>(W3) + (size_t)c * NBLK * 1024 + lane * 16;
-#pragma unroll
-        for (int t0 = 0; t0 < NBLK; t0 += 8) {
-            const int t = t0 + wave, rbl = t / KS2, kb = t % KS2;     // block t of the chunk: 16 weight rows x 32 k
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + t * 1024),
-                                             (__attribute__((address_space(3))) void*)(buf + kb * (BN * 64) + rbl * 1024), 16, 0, 0);
-        }
-    };
-    const unsigned loff = (unsigned)((lane & 15) * 64 + (((lane >> 4) ^ swz((lane >> 2) & 3)) << 4));
-    const int cblocks = (NCH * BN) >> 5;
-    uint4 rv[2][TI][TJ / 2];                                 // residuals: the chunk being finished and the next one (in flight)
-    // byte offset of this lane's 16 bytes of output piece (chunk c, row tile i, column pair jp): 32-bit (an activation is < 4 GiB)
-    const unsigned obase = (unsigned)(kZeroPage * 2) + (unsigned)(((m0 >> 4) + wm * TI) * cblocks + wn * 2) * 1024u + loff;
-    auto out_off = [&](int c, int i, int jp) __attribute__((always_inline)) {
-        return obase + (unsigned)((i * cblocks + c * (BN >> 5) + jp) * 1024);
-    };
-    // PF: a chunk's residuals are requested one chunk ahead (two register sets); without it (the 128-channel shape, whose
-    // fragments of the mid tile take 32 registers) at the top of their own chunk, in front of its MFMAs
-    constexpr bool PF = RESIDENT;
-    auto load_res = [&](int c) __attribute__((always_inline)) {
-#pragma unroll
-        for (int i = 0; i < TI; i++)
-#pragma unroll
-            for (int jp = 0; jp < TJ / 2; jp++)
-                rv[PF ? (c & 1) : 0][i][jp] = *reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(R) + out_off(c, i, jp));
-    };
-
-    // ---- 1. the 3x3 (the loop of k_conv_bf16)
+    // ---- 1. the 3x3 (the loop of k_conv_bf16; nh >= 18)
     const int nh = g.nh;
-    auto step = [&](int hs, auto last_c) __attribute__((always_inline)) {
-        constexpr bool LAST = decltype(last_c)::value;
-        __builtin_amdgcn_sched_barrier(0);
-        const int younger = (hs + 2 < nh - 1 ? hs + 2 : nh - 1) - hs;
-        if (LAST) AVD_WAIT_VMC(0);
-        else if (younger >= 2) AVD_WAIT_VMC(2 * P);
-        else if (younger == 1) AVD_WAIT_VMC(P);
-        else AVD_WAIT_VMC(0);
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
-        if (LAST) {                                          // everyone is past step nh - 2: three ring slots are free
-            if (RESIDENT) {
-#pragma unroll
-                for (int c = 0; c < NCH; c++) issue_w3(c);
-            } else {
-                issue_w3(0);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            if (PF) load_res(0);
-            __builtin_amdgcn_sched_barrier(0);
-        } else if (hs + 3 < nh) {
-            issue(hs + 3);
-        }
-        const char* cur = lds + (hs & 3) * STAGE;
-        bf16x8 a[TI], b[TJ];
-#pragma unroll
-        for (int j = 0; j < TJ; j++) b[j] = frag(cur + HALF_A, b_row(j, r16), chunk);
-#pragma unroll
-        for (int i = 0; i < TI; i++) a[i] = frag(cur, (wm * TI + i) * 16 + r16, chunk);
-#pragma unroll
-        for (int i = 0; i < TI; i++)
-#pragma unroll
-            for (int j = 0; j < TJ; j++) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b[j], a[i], acc[i][j], 0, 0, 0);
-    };
-    for (int hs = 0; hs < 3; hs++) issue(hs);                // nh >= 18
-    for (int hs = 0; hs < nh - 1; hs++) step(hs, std::false_type{});
-    step(nh - 1, std::true_type{});
+    for (int hs = 0; hs < 3; hs++) issue(hs);
+    for (int hs = 0; hs < nh - 1; hs++) {
+        ring_wait<S::P>(ring_younger(hs, nh));
+        if (hs + 3 < nh) issue(hs + 3);
+        const char* cur = lds + (hs & 3) * S::STAGE;
+        ring_mfma(acc, cur, cur + S::HALF_A, wm, wn, lane);
+    }
+    ring_wait<S::P>(0);                                      // everyone is past step nh - 2: three ring slots are free
+    ex.issue_first_w3();
+    __builtin_amdgcn_sched_barrier(0);
+    if (ex.PF) ex.load_res(0, ex.rv0);
+    __builtin_amdgcn_sched_barrier(0);
+    const char* cur = lds + ((nh - 1) & 3) * S::STAGE;
+    ring_mfma(acc, cur, cur + S::HALF_A, wm, wn, lane);
 
-    // ---- 2. the mid tile -> LDS (operand layout) -> this wave's fragments
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();                            // every wave has read its last fragments: the whole ring is free
-    __builtin_amdgcn_sched_barrier(0);
-    // the 3x3's bias: this lane's 16 values.  (The compiler puts a vmcnt(0) in front of the LDS stores below anyway, because
-    // LDS-DMAs are in flight -- W3 and the first chunk of residuals have had the last step to arrive -- so this load costs no
-    // extra wait.)
-    f32x4 b2lo[TJ / 2], b2hi[TJ / 2];
-#pragma unroll
-    for (int jp = 0; jp < TJ / 2; jp++) {
-        const float* pb = bias2 + wn * 64 + jp * 32 + (lane >> 4) * 8;
-        b2lo[jp] = *reinterpret_cast<const f32x4*>(pb);
-        b2hi[jp] = *reinterpret_cast<const f32x4*>(pb + 4);
-    }
-    if (threadIdx.x < NCH * BN) lbias3[threadIdx.x] = b3v;
-#pragma unroll
-    for (int i = 0; i < TI; i++)
-#pragma unroll
-        for (int jp = 0; jp < TJ / 2; jp++) {
-            f32x4 lo = acc[i][2 * jp] + b2lo[jp];
-            f32x4 hi = acc[i][2 * jp + 1] + b2hi[jp];
-#pragma unroll
-            for (int e = 0; e < 4; e++) { lo[e] = fmaxf(lo[e], 0.f); hi[e] = fmaxf(hi[e], 0.f); }
-            uint4 pk;
-            pk.x = pack_bf16x2(lo[0], lo[1]);
-            pk.y = pack_bf16x2(lo[2], lo[3]);
-            pk.z = pack_bf16x2(hi[0], hi[1]);
-            pk.w = pack_bf16x2(hi[2], hi[3]);
-            *reinterpret_cast<uint4*>(a2 + (wn * 2 + jp) * (BM * 64) + (wm * TI + i) * 1024 + loff) = pk;
-        }
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");   // this wave's part of W3 has landed, its part of the mid tile is written
-    __builtin_amdgcn_s_barrier();                            // ... and everybody else's
-    __builtin_amdgcn_sched_barrier(0);
-    bf16x8 am[KS2][TI];
-#pragma unroll
-    for (int ks = 0; ks < KS2; ks++)
-#pragma unroll
-        for (int i = 0; i < TI; i++) am[ks][i] = frag(a2 + ks * (BM * 64), (wm * TI + i) * 16 + r16, chunk);
-    if (!RESIDENT) {                                         // the second W3 buffer takes over the mid tile's LDS
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
-    }
-
-    // ---- 3. the expanding 1x1, BN output channels at a time.  Vector-memory queue of a wave (in order), resident W3: res(1) st(0) |
-    // res(2) st(1) | res(3) st(2) | st(3); otherwise res(c) DMA(c + 1) st(c) per chunk: the wait for DMA(c + 1) at the end of
-    // iteration c leaves the stores of chunk c in flight.
-    static_assert(NCH % 2 == 0, "the chunk loop is unrolled by two (the residual buffers alternate)");
-#pragma unroll 1
-    for (int c2 = 0; c2 < NCH; c2 += 2)
-#pragma unroll
-    for (int cc = 0; cc < 2; cc++) {
-        const int c = c2 + cc;
-        if (!PF) load_res(c);
-        if (!RESIDENT && c + 1 < NCH) issue_w3(c + 1);
-        if (PF && c + 1 < NCH) load_res(c + 1);
-        __builtin_amdgcn_sched_barrier(0);
-        zero_acc();
-        const char* buf = lds + W3BASE + (RESIDENT ? c : (c & 1)) * B2;
-#pragma unroll
-        for (int ks = 0; ks < KS2; ks++) {
-            bf16x8 b[TJ];
-#pragma unroll
-            for (int j = 0; j < TJ; j++) b[j] = frag(buf + ks * (BN * 64), b_row(j, r16), chunk);
-#pragma unroll
-            for (int i = 0; i < TI; i++)
-#pragma unroll
-                for (int j = 0; j < TJ; j++) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b[j], am[ks][i], acc[i][j], 0, 0, 0);
-        }
-#pragma unroll
-        for (int i = 0; i < TI; i++)
-#pragma unroll
-            for (int jp = 0; jp < TJ / 2; jp++) {
-                const float* pb = lbias3 + c * BN + wn * 64 + jp * 32 + (lane >> 4) * 8;
-                f32x4 lo = acc[i][2 * jp] + *reinterpret_cast<const f32x4*>(pb);
-                f32x4 hi = acc[i][2 * jp + 1] + *reinterpret_cast<const f32x4*>(pb + 4);
-                const uint4 r = rv[PF ? (c & 1) : 0][i][jp];
-                lo[0] += bf16_to_f32(r.x & 0xFFFF); lo[1] += bf16_to_f32(r.x >> 16);
-                lo[2] += bf16_to_f32(r.y & 0xFFFF); lo[3] += bf16_to_f32(r.y >> 16);
-                hi[0] += bf16_to_f32(r.z & 0xFFFF); hi[1] += bf16_to_f32(r.z >> 16);
-                hi[2] += bf16_to_f32(r.w & 0xFFFF); hi[3] += bf16_to_f32(r.w >> 16);
-#pragma unroll
-                for (int e = 0; e < 4; e++) { lo[e] = fmaxf(lo[e], 0.f); hi[e] = fmaxf(hi[e], 0.f); }
-                uint4 pk;
-                pk.x = pack_bf16x2(lo[0], lo[1]);
-                pk.y = pack_bf16x2(lo[2], lo[3]);
-                pk.z = pack_bf16x2(hi[0], hi[1]);
-                pk.w = pack_bf16x2(hi[2], hi[3]);
-                *reinterpret_cast<uint4*>(reinterpret_cast<char*>(Y) + out_off(c, i, jp)) = pk;
-            }
-        __builtin_amdgcn_sched_barrier(0);
-        if (!RESIDENT && c + 1 < NCH) {
-            AVD_WAIT_VMC((PF ? 2 : 1) * NRES);               // younger than DMA(c + 1): [res(c + 1),] st(c)
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();                    // the next chunk has landed for every wave; everyone is done reading this one
-            __builtin_amdgcn_sched_barrier(0);
-        }
-    }
+    ex.template run<false>(acc, bias2, b3v);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// The same fused block for mid = 64, stride 1 (the 56 x 56 stage) with the 3x3's input as ONE slab in LDS.  k_conv3_expand
+// The same fused block for stride 1 with the 3x3's input as ONE slab in LDS.  k_conv3_expand
 // gathers the 256 output pixels' inputs from L2 once per tap: 9 x 32 KB of its 520 KB of ingest per workgroup, on a path that
 // delivers ~37-40 GB/s per CU whatever the instruction (profiles/r04_experiments.md section 5).  Output pixels m0 .. m0 + 255 of
 // the linear pixel index see, through the nine taps, input pixels m0 - 57 .. m0 + 312: the 384 pixels m0 - 64 .. m0 + 319 are
@@ -516,8 +562,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
 // is then a fragment read at a shifted slab row -- lane (pixel r, chunk) reads row 64 + tile row + r + dy W + dx, which carries its
 // own swizzle key -- with the fragment zeroed where the tap leaves the image (a per-lane 9-bit mask).  Only the weights stream:
 // one tap (64 x 64 bf16 = 8 KB, one LDS-DMA instruction per wave) per step, ring of four, 16 MFMAs per wave between barriers.
-// Same K order (tap, then channel block) as the gathering kernels: bit-identical.  The expanding layer follows as in
-// k_conv3_expand (resident W3; it is requested after the last tap, when the slab is dead).
+// Same K order (tap, then channel block) as the gathering kernels: bit-identical.  The expanding layer follows (Expand; W3 is
+// requested after the last tap, when the slab is dead).
 // MID = 64 (56 x 56: 256-pixel tiles, a whole tap of W2 per step, W3 resident) or 128 (28 x 28: 128-pixel tiles, slab = 192 pixels x 4 channel
 // blocks -- again 48 contiguous KiB --, W2 streams in half stages of 32 input channels = 8 KiB like the gathering kernel, W3 in two alternating
 // chunk buffers).
@@ -527,30 +573,16 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
                                                      const float* __restrict__ bias3, const uint16_t* __restrict__ R,
                                                      uint16_t* __restrict__ Y, ConvGeom g, int in_blocks)
 {
-    static_assert(MID == 64 || MID == 128, "the two early stages");
-    constexpr int BN = MID, WAVES_N = BN / 64, WAVES_M = 8 / WAVES_N, TI = 2, TJ = 4, BM = WAVES_M * TI * 16;   // 256 x 64 or 128 x 128
-    constexpr int CPB = MID / 32, KS2 = CPB, NCH = 4;       // channel blocks of the input = k steps of the expanding layer
-    constexpr int HALO = MID == 64 ? 64 : 32;               // pixels in front of m0 (>= W + 1, whole pixel blocks)
-    constexpr int NSLAB = BM + 2 * HALO, SLAB = NSLAB * CPB * 64;                 // 384 x 128 B = 192 x 256 B = 48 KiB
-    constexpr int KPS = MID == 64 ? 2 : 1;                  // k blocks of W2 per step (a whole tap at 64 channels, a quarter tap at 128)
-    constexpr int STEPB = BN * 64 * KPS, NSTEP = 9 * CPB / KPS, LDS = SLAB + 4 * STEPB;   // 8 KiB per step, ring of four: 80 KiB
-    constexpr int A2 = BM * BN * 2, B2 = BN * BN * 2;
-    constexpr bool RESIDENT = NCH * B2 + A2 + NCH * BN * 4 <= LDS;               // W3 | mid tile | bias3 (mid 64); else two chunk buffers
-    constexpr int A2BASE = RESIDENT ? NCH * B2 : B2, BIAS3 = RESIDENT ? A2BASE + A2 : 2 * B2;
-    static_assert(SLAB == 49152 && STEPB == 8192 && BIAS3 + NCH * BN * 4 <= LDS && A2BASE + A2 <= LDS, "LDS plan");
-    constexpr int NBLK = (BN / 16) * KS2;                   // KiB blocks of one W3 chunk
-    constexpr int NRES = TI * TJ / 2;
+    using S = SlabShape<MID>;
+    constexpr int BN = S::BN, BM = S::BM, TI = S::TI, TJ = S::TJ, CPB = S::CPB, HALO = S::HALO, SLAB = S::SLAB, KPS = S::KPS, STEPB = S::STEPB, NSTEP = S::NSTEP;
     extern __shared__ __align__(16) char lds[];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int wm = wave / WAVES_N, wn = wave % WAVES_N;
-    const int total = (g.m_out + BM - 1) / BM;
-    const int per = (gridDim.x + 7) >> 3;
-    const int lid = (blockIdx.x & 7) * per + (blockIdx.x >> 3);
-    if (lid >= total) return;
+    const int wm = wave / S::WAVES_N, wn = wave % S::WAVES_N;
+    const int lid = xcd_tile();
+    if (lid >= tiles_of(g.m_out, BM)) return;
     const int m0 = lid * BM;
-    static_assert(NCH * BN <= 512, "one bias3 element per thread");
-    float b3v = threadIdx.x < NCH * BN ? bias3[threadIdx.x] : 0.f;
+    float b3v = threadIdx.x < S::NCH * S::BN ? bias3[threadIdx.x] : 0.f;
     asm volatile("" : "+v"(b3v));                            // arrived before the queue fills (k_conv3_expand)
     const int chunk = lane >> 4, r16 = lane & 15;
     const char* xb = reinterpret_cast<const char*>(X);
@@ -559,7 +591,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     // the activation come from the zero page (their pixels are masked in every tap: they only must not fault)
     const int blk0 = (m0 - HALO) >> 4;
 #pragma unroll
-    for (int j0 = 0; j0 < 48; j0 += 8) {
+    for (int j0 = 0; j0 < SLAB / 1024; j0 += 8) {
         const int j = j0 + wave, pb = blk0 + j / CPB;
         const bool ok = pb >= 0 && pb < in_blocks;          // wave-uniform
         const char* src = ok ? xb + kZeroPage * 2 + ((size_t)pb * CPB + j % CPB) * 1024 + lane * 16 : xb + lane * 16;
@@ -594,39 +626,16 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
         qbase[i] = HALO + pl;
     }
     f32x4 acc[TI][TJ];
-    auto zero_acc = [&]() __attribute__((always_inline)) {
-#pragma unroll
-        for (int i = 0; i < TI; i++)
-#pragma unroll
-            for (int j = 0; j < TJ; j++) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-    };
-    zero_acc();
-    auto b_row = [&](int j, int rho) __attribute__((always_inline)) { return wn * 64 + (j >> 1) * 32 + (rho >> 2) * 8 + (j & 1) * 4 + (rho & 3); };
-    const unsigned loff = (unsigned)((lane & 15) * 64 + (((lane >> 4) ^ swz((lane >> 2) & 3)) << 4));
-    constexpr int cblocks = (NCH * BN) >> 5;
-    constexpr bool PF = RESIDENT;                            // residuals one chunk ahead (two register sets) only where the registers allow
-    uint4 rv[PF ? 2 : 1][TI][TJ / 2];
-    const unsigned obase = (unsigned)(kZeroPage * 2) + (unsigned)(((m0 >> 4) + wm * TI) * cblocks + wn * 2) * 1024u + loff;
-    auto out_off = [&](int c, int i, int jp) __attribute__((always_inline)) { return obase + (unsigned)((i * cblocks + c * (BN >> 5) + jp) * 1024); };
-    auto load_res = [&](int c) __attribute__((always_inline)) {
-#pragma unroll
-        for (int i = 0; i < TI; i++)
-#pragma unroll
-            for (int jp = 0; jp < TJ / 2; jp++)
-                rv[PF ? (c & 1) : 0][i][jp] = *reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(R) + out_off(c, i, jp));
-    };
+    zero_acc(acc);
+    Expand<S> ex(lds, W3, R, Y, m0, wave, lane);
 
     // ---- 1. the nine taps (K order: tap, then channel block -- the gathering kernels' order)
 #pragma unroll
     for (int st = 0; st < NSTEP; st++) {
-        __builtin_amdgcn_sched_barrier(0);
-        if (st < NSTEP - 2) AVD_WAIT_VMC(2);                 // steps st + 1, st + 2 may still be in flight (the slab is older than step 0)
-        else if (st == NSTEP - 2) AVD_WAIT_VMC(1);
-        else AVD_WAIT_VMC(0);
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
+        // steps st + 1, st + 2 may still be in flight, one LDS-DMA each (the slab is older than step 0)
+        ring_wait<1>(NSTEP - 1 - st);
         if (st + 3 < NSTEP) issue_w2(st + 3);
-        else if (PF && st == NSTEP - 1) load_res(0);         // the first residuals, a whole step + the mid tile's epilogue ahead
+        else if (ex.PF && st == NSTEP - 1) ex.load_res(0, ex.rv0);   // the first residuals, a whole step + the mid tile's epilogue ahead
         __builtin_amdgcn_sched_barrier(0);
         const int t = st * KPS / CPB, cb0 = st * KPS % CPB;  // tap and first channel block of the step
         const int shift = (t / 3 - 1) * g.win + (t % 3 - 1);
@@ -635,7 +644,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
 #pragma unroll
         for (int kb = 0; kb < KPS; kb++) {
 #pragma unroll
-            for (int j = 0; j < TJ; j++) b[j][kb] = frag(sb + kb * (BN * 64), b_row(j, r16), chunk);
+            for (int j = 0; j < TJ; j++) b[j][kb] = frag(sb + kb * (BN * 64), b_row_of(wn, 64, j, r16), chunk);
 #pragma unroll
             for (int i = 0; i < TI; i++) {
                 const int q = qbase[i] + shift;
@@ -652,114 +661,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
                 for (int j = 0; j < TJ; j++) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b[j][kb], a[i][kb], acc[i][j], 0, 0, 0);
     }
 
-    // ---- 2. W3 (its first chunk) into the dead slab, the mid tile -> LDS -> this wave's fragments
-    char* const a2 = lds + A2BASE;
-    float* const lbias3 = reinterpret_cast<float*>(lds + BIAS3);
-    auto issue_w3 = [&](int c) __attribute__((always_inline)) {
-        char* buf = lds + (RESIDENT ? c : (c & 1)) * B2;
-        const char* src = reinterpret_cast<const char*>(W3) + (size_t)c * NBLK * 1024 + lane * 16;
-#pragma unroll
-        for (int t0 = 0; t0 < NBLK; t0 += 8) {
-            const int t = t0 + wave, rbl = t / KS2, kb = t % KS2;
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + t * 1024),
-                                             (__attribute__((address_space(3))) void*)(buf + kb * (BN * 64) + rbl * 1024), 16, 0, 0);
-        }
-    };
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();                            // every wave has read its last fragments
-    __builtin_amdgcn_sched_barrier(0);
-    f32x4 b2lo[TJ / 2], b2hi[TJ / 2];
-#pragma unroll
-    for (int jp = 0; jp < TJ / 2; jp++) {
-        const float* pb = bias2 + wn * 64 + jp * 32 + (lane >> 4) * 8;
-        b2lo[jp] = *reinterpret_cast<const f32x4*>(pb);
-        b2hi[jp] = *reinterpret_cast<const f32x4*>(pb + 4);
-    }
-    if (RESIDENT) {
-#pragma unroll
-        for (int c = 0; c < NCH; c++) issue_w3(c);
-    } else {
-        issue_w3(0);
-    }
-    if (threadIdx.x < NCH * BN) lbias3[threadIdx.x] = b3v;
-#pragma unroll
-    for (int i = 0; i < TI; i++)
-#pragma unroll
-        for (int jp = 0; jp < TJ / 2; jp++) {
-            f32x4 lo = acc[i][2 * jp] + b2lo[jp];
-            f32x4 hi = acc[i][2 * jp + 1] + b2hi[jp];
-#pragma unroll
-            for (int e = 0; e < 4; e++) { lo[e] = fmaxf(lo[e], 0.f); hi[e] = fmaxf(hi[e], 0.f); }
-            uint4 pk;
-            pk.x = pack_bf16x2(lo[0], lo[1]); pk.y = pack_bf16x2(lo[2], lo[3]);
-            pk.z = pack_bf16x2(hi[0], hi[1]); pk.w = pack_bf16x2(hi[2], hi[3]);
-            *reinterpret_cast<uint4*>(a2 + (wn * 2 + jp) * (BM * 64) + (wm * TI + i) * 1024 + loff) = pk;
-        }
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();                            // W3 (its first chunk) and the mid tile are complete for everyone
-    __builtin_amdgcn_sched_barrier(0);
-    bf16x8 am[KS2][TI];
-#pragma unroll
-    for (int ks = 0; ks < KS2; ks++)
-#pragma unroll
-        for (int i = 0; i < TI; i++) am[ks][i] = frag(a2 + ks * (BM * 64), (wm * TI + i) * 16 + r16, chunk);
-    if (!RESIDENT) {                                         // the second W3 buffer takes over the mid tile's LDS
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
-    }
-
-    // ---- 3. the expanding 1x1 (k_conv3_expand's chunk loop)
-    static_assert(NCH % 2 == 0, "unrolled by two");
-#pragma unroll 1
-    for (int c2 = 0; c2 < NCH; c2 += 2)
-#pragma unroll
-    for (int cc = 0; cc < 2; cc++) {
-        const int c = c2 + cc;
-        if (!PF) load_res(c);
-        if (!RESIDENT && c + 1 < NCH) issue_w3(c + 1);
-        if (PF && c + 1 < NCH) load_res(c + 1);
-        __builtin_amdgcn_sched_barrier(0);
-        zero_acc();
-        const char* buf = lds + (RESIDENT ? c : (c & 1)) * B2;
-#pragma unroll
-        for (int ks = 0; ks < KS2; ks++) {
-            bf16x8 b[TJ];
-#pragma unroll
-            for (int j = 0; j < TJ; j++) b[j] = frag(buf + ks * (BN * 64), b_row(j, r16), chunk);
-#pragma unroll
-            for (int i = 0; i < TI; i++)
-#pragma unroll
-                for (int j = 0; j < TJ; j++) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b[j], am[ks][i], acc[i][j], 0, 0, 0);
-        }
-#pragma unroll
-        for (int i = 0; i < TI; i++)
-#pragma unroll
-            for (int jp = 0; jp < TJ / 2; jp++) {
-                const float* pb = lbias3 + c * BN + wn * 64 + jp * 32 + (lane >> 4) * 8;
-                f32x4 lo = acc[i][2 * jp] + *reinterpret_cast<const f32x4*>(pb);
-                f32x4 hi = acc[i][2 * jp + 1] + *reinterpret_cast<const f32x4*>(pb + 4);
-                const uint4 r = rv[PF ? (c & 1) : 0][i][jp];
-                lo[0] += bf16_to_f32(r.x & 0xFFFF); lo[1] += bf16_to_f32(r.x >> 16);
-                lo[2] += bf16_to_f32(r.y & 0xFFFF); lo[3] += bf16_to_f32(r.y >> 16);
-                hi[0] += bf16_to_f32(r.z & 0xFFFF); hi[1] += bf16_to_f32(r.z >> 16);
-                hi[2] += bf16_to_f32(r.w & 0xFFFF); hi[3] += bf16_to_f32(r.w >> 16);
-#pragma unroll
-                for (int e = 0; e < 4; e++) { lo[e] = fmaxf(lo[e], 0.f); hi[e] = fmaxf(hi[e], 0.f); }
-                uint4 pk;
-                pk.x = pack_bf16x2(lo[0], lo[1]); pk.y = pack_bf16x2(lo[2], lo[3]);
-                pk.z = pack_bf16x2(hi[0], hi[1]); pk.w = pack_bf16x2(hi[2], hi[3]);
-                *reinterpret_cast<uint4*>(reinterpret_cast<char*>(Y) + out_off(c, i, jp)) = pk;
-            }
-        __builtin_amdgcn_sched_barrier(0);
-        if (!RESIDENT && c + 1 < NCH) {
-            AVD_WAIT_VMC(NRES);                              // younger than DMA(c + 1): the stores of chunk c
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();                    // the next chunk has landed for every wave; everyone is done reading this one
-            __builtin_amdgcn_sched_barrier(0);
-        }
-    }
+    // ---- 2., 3. W3 (its first chunk) into the dead slab, the mid tile, the expanding 1x1
+    ex.template run<true>(acc, bias2, b3v);
 }
 
 // BGR uint8 frame -> 224 x 224 (float bilinear taps, cv2's INTER_LINEAR centre mapping), RGB, (x / 255 - mean) / std,
@@ -907,93 +810,78 @@ const Net& net() { static const Net n; return n; }
 
 int k_padded(const Layer& l) { return l.ksize == 7 ? 7 * 8 * 4 : l.ksize * l.ksize * l.cin; }   // the stem: [7 ky][8 kx][4 c], kx = 7 and c = 3 zero
 
+// a grid of `workgroups` tiles (rounded up to whole XCD rounds: xcd_tile) of 512 threads with `lds` bytes of dynamic LDS
+template <class K, class... Args>
+int launch_tiles(avd_ctx* ctx, K kern, int workgroups, size_t lds, Args... args)
+{
+    HIP_TRY(ctx, hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(kern, dim3((workgroups + 7) / 8 * 8), dim3(512), lds, ctx->stream, args...);
+    HIP_TRY(ctx, hipGetLastError());
+    return 0;
+}
+
+template <int BM, int WAVES_M, int TI, int MODE, int KS>
+int launch_conv_shape(avd_ctx* ctx, const ConvGeom& g, const uint16_t* x, const uint16_t* w, const float* bias, const uint16_t* res, uint16_t* y, int relu)
+{
+    using S = ConvShape<BM, WAVES_M, TI>;
+    return launch_tiles(ctx, k_conv_bf16<BM, WAVES_M, TI, MODE, KS>, tiles_of(g.m_out, S::BM) * (g.cout / S::BN), S::lds(g.nh), x, w, bias, res, y, g, relu);
+}
+
 // stem == true: x is the bordered input image, (hin, win, cin, ksize, stride) describe the 7x7/2 convolution
 int launch_conv(avd_ctx* ctx, const uint16_t* x, const uint16_t* w, const float* bias, const uint16_t* res, uint16_t* y, int n, int hin,
                 int win, int cin, int cout, int ksize, int stride, int relu, bool stem = false)
 {
-    ConvGeom g;
-    g.hin = hin; g.win = win; g.cin = cin; g.cout = cout; g.ksize = ksize; g.stride = stride; g.pad = ksize / 2;
-    g.hout = (hin + 2 * g.pad - ksize) / stride + 1;
-    g.wout = (win + 2 * g.pad - ksize) / stride + 1;
-    g.m_out = n * g.hout * g.wout;
-    g.cpb = stem ? 1 : cin / 32;
-    g.nh = stem ? 7 : ksize * ksize * g.cpb;
+    const ConvGeom g = conv_geom(n, hin, win, cin, cout, ksize, stride, stem);
     if (!stem && (cin % 32 || cout % 64 || (ksize != 1 && ksize != 3))) { ctx->err = "conv: cin % 32, cout % 64, ksize 1 or 3"; return AVD_ERR_ARG; }
-    auto go = [&](auto kern, int bm, int bn) -> int {
-        const int total = ((g.m_out + bm - 1) / bm) * (cout / bn), grid = (total + 7) / 8 * 8;
-        const size_t lds = (size_t)(g.nh < 4 ? g.nh : 4) * (size_t)(bm * 64 + bn * 64);   // short K: fewer ring slots, more workgroups per CU
-        HIP_TRY(ctx, hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, ctx->stream, x, w, bias, res, y, g, relu);
-        HIP_TRY(ctx, hipGetLastError());
-        return 0;
-    };
-    if (stem) return go(k_conv_bf16<256, 8, 2, 1, 1>, 256, 64);
+    if (stem) return launch_conv_shape<256, 8, 2, 1, 1>(ctx, g, x, w, bias, res, y, relu);
     // 256-pixel tiles for the long-K layers that fill the chip.  128 x 128 tiles (74 registers, 16 KiB per ring slot: several
     // workgroups per CU) where 256-pixel tiles would leave most of the chip idle (the 14 x 14 and 7 x 7 stages), and for the
     // short-K 1x1 layers, which move bytes rather than multiply: there the time goes to load / store latency, and
     // co-resident workgroups are what hides it.
     const int force = ctx->cnn_tiles;   // avd_set_option "cnn_tiles": 1 = always 256-pixel tiles, 2 = 128 x 128 wherever possible
     const int bn_big = cout % 256 == 0 ? 256 : cout % 128 == 0 ? 128 : 64;
-    const int wgs_big = ((g.m_out + 255) / 256) * (cout / bn_big);
+    const int wgs_big = tiles_of(g.m_out, 256) * (cout / bn_big);
     const bool small_ok = cout % 128 == 0;
     // fill_pct = workgroups of the 256-pixel tiling, in percent of the CU count, below which the 128 x 128 tiling is taken;
     // short_k = largest number of half stages that counts as "short K"
     constexpr int fill_pct = 150, short_k = 8;
     const bool want_small = wgs_big * 100 < ctx->num_cus * fill_pct || g.nh <= short_k;
-    if (ksize == 3) {
-        if (small_ok && force != 1 && (want_small || force == 2)) return go(k_conv_bf16<128, 4, 2, 0, 3>, 128, 128);
-        if (bn_big == 256) return go(k_conv_bf16<256, 2, 8, 0, 3>, 256, 256);
-        if (bn_big == 128) return go(k_conv_bf16<256, 4, 4, 0, 3>, 256, 128);
-        return go(k_conv_bf16<256, 8, 2, 0, 3>, 256, 64);
-    }
-    if (small_ok && force != 1 && (want_small || force == 2)) return go(k_conv_bf16<128, 4, 2, 0, 1>, 128, 128);
-    if (bn_big == 256) return go(k_conv_bf16<256, 2, 8, 0, 1>, 256, 256);
-    if (bn_big == 128) return go(k_conv_bf16<256, 4, 4, 0, 1>, 256, 128);
-    return go(k_conv_bf16<256, 8, 2, 0, 1>, 256, 64);
+    auto tiled = [&](auto ks) -> int {
+        constexpr int KS = decltype(ks)::value;
+        if (small_ok && force != 1 && (want_small || force == 2)) return launch_conv_shape<128, 4, 2, 0, KS>(ctx, g, x, w, bias, res, y, relu);
+        if (bn_big == 256) return launch_conv_shape<256, 2, 8, 0, KS>(ctx, g, x, w, bias, res, y, relu);
+        if (bn_big == 128) return launch_conv_shape<256, 4, 4, 0, KS>(ctx, g, x, w, bias, res, y, relu);
+        return launch_conv_shape<256, 8, 2, 0, KS>(ctx, g, x, w, bias, res, y, relu);
+    };
+    return ksize == 3 ? tiled(std::integral_constant<int, 3>{}) : tiled(std::integral_constant<int, 1>{});
 }
 
 // conv2 (3x3, mid -> mid, stride s, ReLU) + conv3 (1x1, mid -> 4 mid, + residual, ReLU) of a bottleneck block in one launch
-// (k_conv3_expand); mid = 64 (256-pixel tiles) or 128 (128-pixel tiles).  y must not be the 3x3's input.
+// (k_conv3_expand, or k_slab3_expand in the stride-1 blocks with cnn_fuse = 2); mid = 64 (256-pixel tiles) or 128 (128-pixel
+// tiles).  y must not be the 3x3's input.
 bool can_fuse_expand(int mid) { return mid == 64 || mid == 128; }
 int launch_conv3_expand(avd_ctx* ctx, const uint16_t* x, const uint16_t* w2, const float* b2, const uint16_t* w3, const float* b3,
                         const uint16_t* res, uint16_t* y, int n, int hin, int win, int mid, int stride)
 {
-    ConvGeom g;
-    g.hin = hin; g.win = win; g.cin = mid; g.cout = mid; g.ksize = 3; g.stride = stride; g.pad = 1;
-    g.hout = (hin + 2 - 3) / stride + 1;
-    g.wout = (win + 2 - 3) / stride + 1;
-    g.m_out = n * g.hout * g.wout;
-    g.cpb = mid / 32;
-    g.nh = 9 * g.cpb;
+    const ConvGeom g = conv_geom(n, hin, win, mid, mid, 3, stride);
     if (!can_fuse_expand(mid) || !res || y == x) { ctx->err = "conv3_expand: mid 64 or 128, a residual, output apart from the input"; return AVD_ERR_ARG; }
-    auto go = [&](auto kern, int bm, int bn) -> int {
-        const int total = (g.m_out + bm - 1) / bm, grid = (total + 7) / 8 * 8;
-        // the ring; W3 resident (mid = 64): the expanding layer's bias fits inside it, otherwise behind it.  The kernel's LDS plan
-        // assumes which ring slot the 3x3's last step reads: nh & 3 == 2 (mid = 64: 18 half stages) or 0 (mid = 128: 36)
-        if ((g.nh & 3) != (bn == 64 ? 2 : 0)) { ctx->err = "conv3_expand: ring phase"; return AVD_ERR_ARG; }
-        const size_t lds = (size_t)4 * (size_t)(bm * 64 + bn * 64) + (bn == 64 ? 0 : (size_t)bn * 4 * sizeof(float));
-        HIP_TRY(ctx, hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, ctx->stream, x, w2, b2, w3, b3, res, y, g);
-        HIP_TRY(ctx, hipGetLastError());
-        return 0;
-    };
     if (stride == 1 && ctx->cnn_fuse == 2) {
-        // the 3x3's input as one slab in LDS (k_slab3_expand); the blocks of the input activation that exist: its rows are padded to 256
+        // the 3x3's input as one slab in LDS; the blocks of the input activation that exist: its rows are padded to 256
         const int in_blocks = (int)(((size_t)n * hin * win + 255) / 256 * 256 / 16);
-        const int bm = mid == 64 ? 256 : 128;
-        if (win + 1 > (mid == 64 ? 64 : 32)) { ctx->err = "conv3_expand: the slab's halo is sized for 56 x 56 (mid 64) and 28 x 28 (mid 128)"; return AVD_ERR_ARG; }
-        const int total = (g.m_out + bm - 1) / bm, grid = (total + 7) / 8 * 8;
-        const size_t lds = 49152 + 4 * 8192;
-        auto slab = [&](auto kern) -> int {
-            HIP_TRY(ctx, hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, ctx->stream, x, w2, b2, w3, b3, res, y, g, in_blocks);
-            HIP_TRY(ctx, hipGetLastError());
-            return 0;
+        auto slab = [&](auto shape, auto kern) -> int {
+            using S = decltype(shape);
+            if (win + 1 > S::HALO) { ctx->err = "conv3_expand: the slab's halo is sized for 56 x 56 (mid 64) and 28 x 28 (mid 128)"; return AVD_ERR_ARG; }
+            return launch_tiles(ctx, kern, tiles_of(g.m_out, S::BM), S::LDS, x, w2, b2, w3, b3, res, y, g, in_blocks);
         };
-        return mid == 64 ? slab(k_slab3_expand<64>) : slab(k_slab3_expand<128>);
+        return mid == 64 ? slab(SlabShape<64>{}, k_slab3_expand<64>) : slab(SlabShape<128>{}, k_slab3_expand<128>);
     }
-    if (mid == 64) return go(k_conv3_expand<256, 8, 2>, 256, 64);
-    return go(k_conv3_expand<128, 4, 2>, 128, 128);
+    auto gather = [&](auto shape, auto kern) -> int {
+        using S = decltype(shape);
+        // the kernel's LDS plan assumes which ring slot the 3x3's last step reads
+        if ((g.nh & 3) != S::PHASE) { ctx->err = "conv3_expand: ring phase"; return AVD_ERR_ARG; }
+        return launch_tiles(ctx, kern, tiles_of(g.m_out, S::BM), S::LDS, x, w2, b2, w3, b3, res, y, g);
+    };
+    return mid == 64 ? gather(FusedShape<256, 8, 2>{}, k_conv3_expand<256, 8, 2>) : gather(FusedShape<128, 4, 2>{}, k_conv3_expand<128, 4, 2>);
 }
 
 size_t act_elems(size_t rows, int c) { return kZeroPage + (rows + 255) / 256 * 256 * (size_t)c; }

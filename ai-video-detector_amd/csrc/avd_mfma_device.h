@@ -1,5 +1,6 @@
 // avd_mfma_device.h -- device helpers shared by the matrix-core kernels (avd_vit.hip, avd_cnn.hip): bf16 conversion, the
-// blocked + swizzled operand layout and the LDS fragment read that goes with it.
+// blocked + swizzled operand layout, the LDS fragment read that goes with it, the LDS-DMA staging of an operand half tile,
+// the counted vmcnt wait and the weight-row permutation of the transposed product.
 #pragma once
 #include <cstdint>
 #include <hip/hip_runtime.h>
@@ -52,5 +53,51 @@ __device__ __forceinline__ bf16x8 frag(const char* lds_tile, int row, int chunk)
 {
     return *reinterpret_cast<const bf16x8*>(lds_tile + row * 64 + ((chunk ^ swz((row >> 2) & 3)) << 4));
 }
+
+// STAGING an operand half tile (rows x 32 k) by LDS-DMA, R rows per wave: instruction q covers rows
+// wave * R + q * 16 + lane / 4; when R is an odd multiple of 8 the last instruction is issued for the lower 32 lanes only
+// (8 rows).  `tile` points at the tile's first block of the half stage.
+template <int R>
+__device__ __forceinline__ void stage_rows(const char* tile, const unsigned (&voff)[(R + 15) / 16], char* lds_half, int wave, int lane)
+{
+    constexpr int Q = (R + 15) / 16;
+#pragma unroll
+    for (int q = 0; q < Q; q++) {
+        char* dst = lds_half + (wave * R + q * 16) * 64;
+        if (q * 16 + 16 <= R) {
+            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(tile + voff[q]),
+                                             (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
+        } else if (lane < 32) {
+            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(tile + voff[q]),
+                                             (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
+        }
+    }
+}
+
+// per-lane byte offset, relative to the tile's first block of a half stage, of the 16 bytes a lane copies with
+// instruction q: tile row r = wave * R + q * 16 + lane / 4 lives in block r / 16 (blocks of one half stage are `kblocks`
+// = K / 32 KiB apart; a run-time value in the convolutions), at r % 16 * 64 + (lane % 4) * 16 inside it -- the swizzle is
+// already in the data
+template <int R>
+__device__ __forceinline__ void stage_offsets(unsigned (&voff)[(R + 15) / 16], int kblocks, int wave, int lane)
+{
+#pragma unroll
+    for (int q = 0; q < (R + 15) / 16; q++) {
+        const int r = wave * R + q * 16 + (lane >> 2);
+        voff[q] = (unsigned)((r >> 4) * kblocks * 1024 + (r & 15) * 64 + (lane & 3) * 16);
+    }
+}
+
+// counted wait on the wave's in-order vector-memory queue (LDS-DMAs, loads and stores alike)
+#define AVD_WAIT_VM(n) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(n) : "memory")
+
+// The product is formed transposed (mfma(b, a): rows of a 16x16 result = n, lane column = m), and which weight row feeds
+// which MFMA row is free to choose: MFMA row rho of column tile j takes column (j / 2) * 32 +
+// (rho / 4) * 8 + (j % 2) * 4 + rho % 4 of wave column wn's `wcols` columns, so that a lane (accumulator rows (lane / 16) * 4 + r of tiles 2 jp and 2 jp + 1)
+// owns EIGHT consecutive columns: one 16-byte store of bf16 per lane, 64 contiguous bytes per output row and instruction
+// (the natural order gives 8-byte stores, 32 contiguous bytes).  The fragment reads stay conflict-free: the four row
+// groups of a read have swizzle keys (0, 2, 0, 2) + j % 2, and the lane groups a ds_read_b128 is served in ({0-3, 12-15}
+// of one chunk, {4-11} of the next) still land in four distinct slots.
+__device__ __forceinline__ int b_row_of(int wn, int wcols, int j, int rho) { return wn * wcols + (j >> 1) * 32 + (rho >> 2) * 8 + (j & 1) * 4 + (rho & 3); }
 
 }  // namespace avd_mfma

@@ -102,40 +102,6 @@ struct TileShape {
     static_assert(TJ % 2 == 0 && 2 * P + TI * TJ <= 63, "column tiles pair up in the epilogue; vmcnt is six bits");
 };
 
-// R rows per wave of one operand half tile: instruction q covers rows wave * R + q * 16 + lane / 4; when R is an odd
-// multiple of 8 the last instruction is issued for the lower 32 lanes only (8 rows).
-template <int R>
-__device__ __forceinline__ void stage_rows(const char* tile, const unsigned (&voff)[(R + 15) / 16], char* lds_half, int wave, int lane)
-{
-    constexpr int Q = (R + 15) / 16;
-#pragma unroll
-    for (int q = 0; q < Q; q++) {
-        char* dst = lds_half + (wave * R + q * 16) * 64;
-        if (q * 16 + 16 <= R) {
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(tile + voff[q]),
-                                             (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
-        } else if (lane < 32) {
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(tile + voff[q]),
-                                             (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
-        }
-    }
-}
-
-// per-lane byte offset, relative to the tile's first block of a half stage, of the 16 bytes a lane copies with
-// instruction q: tile row r = wave * R + q * 16 + lane / 4 lives in block r / 16 (blocks of one half stage are K / 32 KiB
-// apart), at r % 16 * 64 + (lane % 4) * 16 inside it -- the swizzle is already in the data
-template <int R>
-__device__ __forceinline__ void stage_offsets(unsigned (&voff)[(R + 15) / 16], int K, int wave, int lane)
-{
-#pragma unroll
-    for (int q = 0; q < (R + 15) / 16; q++) {
-        const int r = wave * R + q * 16 + (lane >> 2);
-        voff[q] = (unsigned)((r >> 4) * (K >> 5) * 1024 + (r & 15) * 64 + (lane & 3) * 16);
-    }
-}
-
-#define AVD_WAIT_VM(n) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(n) : "memory")
-
 template <int K, int OUT_BF16, class T>
 __global__ __launch_bounds__(64 * T::NWAVES) void k_gemm_bf16_nt_persistent(const uint16_t* __restrict__ A, const uint16_t* __restrict__ Bt,
                                                                 const float* __restrict__ bias, void* __restrict__ Cv, int M, int N_)
@@ -164,23 +130,15 @@ __global__ __launch_bounds__(64 * T::NWAVES) void k_gemm_bf16_nt_persistent(cons
     // 32-bit byte offset that is the same for every tile and half stage.  A is padded to whole tiles by the caller, so no
     // row needs clamping.
     unsigned voa[T::QA], vob[T::QB];
-    stage_offsets<T::RA>(voa, K, wave, lane);
-    stage_offsets<T::RB>(vob, K, wave, lane);
+    stage_offsets<T::RA>(voa, K >> 5, wave, lane);
+    stage_offsets<T::RB>(vob, K >> 5, wave, lane);
     auto issue = [&](int m0, int n0, int hs, int slot) __attribute__((always_inline)) {
         char* st = lds + slot * T::STAGE;
         stage_rows<T::RA>(reinterpret_cast<const char*>(A + ((int64_t)(m0 >> 4) * (K >> 5) + hs) * 512), voa, st, wave, lane);
         stage_rows<T::RB>(reinterpret_cast<const char*>(Bt + ((int64_t)(n0 >> 4) * (K >> 5) + hs) * 512), vob, st + T::HALF_A, wave, lane);
     };
     // the product is formed transposed: rows of a 16x16 result = n (B fragment as the first operand), lane column = m
-    // Which weight row feeds which MFMA row is free to choose: MFMA row rho of column tile j takes the wave's local
-    // column (j / 2) * 32 + (rho / 4) * 8 + (j % 2) * 4 + rho % 4, so that a lane (accumulator rows (lane / 16) * 4 + r of
-    // tiles 2 jp and 2 jp + 1) owns EIGHT consecutive columns: one 16-byte store of bf16 tokens per lane, 64 contiguous
-    // bytes per output row and instruction (the natural order gives 8-byte stores, 32 contiguous bytes).  The fragment
-    // reads stay conflict-free: the four row groups of a read have swizzle keys (0, 2, 0, 2) + j % 2, and the lane groups
-    // a ds_read_b128 is served in ({0-3, 12-15} of one chunk, {4-11} of the next) still land in four distinct slots.
-    auto b_row = [&](int j, int rho) __attribute__((always_inline)) {
-        return wn * (TJ * 16) + (j >> 1) * 32 + (rho >> 2) * 8 + (j & 1) * 4 + (rho & 3);
-    };
+    auto b_row = [&](int j, int rho) __attribute__((always_inline)) { return b_row_of(wn, TJ * 16, j, rho); };
     constexpr int ESZ = OUT_BF16 ? 2 : 4;
     const unsigned coff = (unsigned)((lane & 15) * N + (lane >> 4) * 8) * ESZ;     // this lane inside a 16-row x 32-column piece
     auto store_tile = [&](int m0, int n0) __attribute__((always_inline)) {
