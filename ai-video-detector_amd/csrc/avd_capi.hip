@@ -14,22 +14,6 @@ constexpr int kFbChunk = 128;      // Farneback pairs the scratch holds at first
 constexpr int kFbChunkMax = 512;   // ... and at most (2.6 GB): a batch of short clips runs as ONE launch sequence up to here;
                                    // longer calls are processed in chunks of the reserved size with a one-frame overlap
 
-int rows_per_band_for(int w)
-{
-    // LDS tile = (rows+2) * pitch bytes, kept under 48 KiB so that >= 3 workgroups fit a CU
-    const int pitch = ((w + 32 + 15) / 16) * 16;
-    int r = (48 * 1024) / pitch - 2;
-    int cap = 14;                      // 16 tile rows + LDS tables = 37 KiB at 1080p: 4 workgroups per CU
-    if (w % 16 == 0 && w / 16 <= 256) {
-        // aligned fast path: a lane holds at most 9 row chunks (3 x 16 B each) in registers, so the
-        // tile may have at most 9 * (rows covered per pass) rows -- 7-row bands at 4K
-        const int rpp = 256 / (w / 16);
-        cap = std::min(cap, 9 * rpp - 2);
-    }
-    r = std::min(r, cap);
-    return std::max(r, 1);
-}
-
 struct TableBlob {
     std::vector<uint8_t> bytes;
     template <typename T>
@@ -71,7 +55,8 @@ static int build_geom(avd_ctx* ctx, Geom& g, int h, int w)
     build_linear_tab(h, w, AVD_SMALL, AVD_SMALL, lt);
     int rc = build_area_tab(h, w, AVD_HASH, AVD_HASH, at);
     if (rc) { ctx->err = "unsupported geometry for INTER_AREA"; return rc; }
-    const int R = rows_per_band_for(w);
+    const BandPlan plan = band_plan(w);
+    const int R = plan.rows_per_band;
     const int nbands = (h + R - 1) / R;
     std::vector<int> band_dy(nbands + 1, AVD_SMALL);
     for (int b = 0; b <= nbands; b++) {
@@ -113,7 +98,7 @@ static int build_geom(avd_ctx* ctx, Geom& g, int h, int w)
             at.x.w_last[d] != at.x.w_mid[d])
             P.area_x_uniform4 = 0;
     P.h = h; P.w = w; P.rows_per_band = R; P.nbands = nbands;
-    P.pitch = ((w + 32 + 15) / 16) * 16;
+    P.pitch = plan.pitch;
     HashParams& H = g.hsh;
     H = HashParams{};
     H.ay_begin = (const int*)(dt + o_ayb); H.ay_count = (const int*)(dt + o_ayc);
@@ -169,7 +154,7 @@ int avd_ws_reserve_frames(avd_ctx* ctx, int n, size_t rowbuf_elems, size_t lappa
 }
 
 static size_t rowbuf_elems_for(const Workspace& ws, int n) { return (size_t)n * ws.pre.h * AVD_HASH; }
-static size_t lappart_elems_for(const Workspace& ws, int n) { return (size_t)n * ws.pre.nbands * 8 * 2; }
+static size_t lappart_elems_for(const Workspace& ws, int n) { return (size_t)n * ws.pre.nbands * kLapSlots * 2; }
 
 // one clip at offset 0 of the buffers
 int avd_ws_reserve(avd_ctx* ctx, int n, int h, int w)
@@ -610,11 +595,7 @@ static int preprocess_clip(avd_ctx* ctx, const avd_clip& k, size_t at)
             d_uv = dst + s.uv_off;
         }
     }
-    if (!k.uv) return launch_preprocess(ctx, d_in, k.n, k.h, k.w, k.row_stride, k.frame_stride);
-    Nv12Params nv{};
-    nv.uv = d_uv; nv.uv_row_stride = k.uv_row_stride; nv.uv_frame_stride = k.uv_frame_stride;
-    build_yuv_consts(nv.k);
-    return launch_preprocess_nv12(ctx, d_in, nv, k.n, k.h, k.w, k.row_stride, k.frame_stride);
+    return launch_preprocess(ctx, k, d_in, d_uv);
 }
 
 // avd_preprocess_bgr / avd_preprocess_nv12 behind their argument checks: one clip at offset 0 of the buffers, results to the host

@@ -86,6 +86,12 @@ struct HashParams {
     int h;
 };
 
+// Band plan of the ingest kernels (avd_preprocess.hip): a workgroup owns rows_per_band full-width rows, its LDS tile rows are `pitch` bytes.
+// ni: the k_preprocess_vec<NI> a 16-byte aligned BGR clip of this width runs (0: odd or too wide a width, the generic kernel).
+struct BandPlan { int rows_per_band, pitch, ni; };
+BandPlan band_plan(int w);
+constexpr int kLapSlots = 8;       // per-band slots of Workspace::d_lap_part, one per wave of the workgroup (4 written)
+
 // ---- owners of device and pinned host memory ------------------------------------------------
 // Move-only: pointer + capacity in elements, freed on destruction and on move-assignment.  Converts to its pointer, so
 // call sites read as they would with a raw one (ws.d_small + off, kernel arguments, null tests).
@@ -145,8 +151,7 @@ struct Workspace {
     DevBuf<uint8_t> d_area;           // [n][1024]
     DevBuf<uint8_t> d_hash;           // [n][1024]
     DevBuf<unsigned long long> d_lap; // [n][2]
-    DevBuf<long long> d_lap_part;     // [n][nbands][8 waves][2] per-wave partial moments
-    int lap_waves = 4;
+    DevBuf<long long> d_lap_part;     // [n][nbands][kLapSlots][2] per-wave partial moments
     PreParams pre{};                  // geometry of the clip being enqueued (copies of its cache entry)
     HashParams hsh{};
     // farneback
@@ -287,11 +292,9 @@ int avd_ws_geometry(avd_ctx* ctx, int h, int w);                       // make (
 int avd_ws_reserve_frames(avd_ctx* ctx, int n, size_t rowbuf_elems, size_t lappart_elems);   // grow-only per-frame buffers
 int avd_ws_reserve(avd_ctx* ctx, int n, int h, int w);                 // both, for one clip at offset 0
 int avd_ws_reserve_fb(avd_ctx* ctx, int n);
-int launch_preprocess(avd_ctx* ctx, const uint8_t* d_bgr, int n, int h, int w,
-                      int64_t row_stride, int64_t frame_stride);
-// NV12 input: Y plane rows at d_y + f*frame_stride + y*row_stride, chroma rows at nv.uv + f*uv_frame_stride + (y/2)*uv_row_stride
-int launch_preprocess_nv12(avd_ctx* ctx, const uint8_t* d_y, const Nv12Params& nv, int n, int h, int w,
-                           int64_t row_stride, int64_t frame_stride);
+// the clip's frames, resident at d_in (BGR, d_uv null) or d_in / d_uv (NV12: Y rows at d_in + f*frame_stride + y*row_stride, chroma rows at
+// d_uv + f*uv_frame_stride + (y/2)*uv_row_stride), into the clip's slice of the per-frame buffers; the clip's geometry is current
+int launch_preprocess(avd_ctx* ctx, const avd_clip& clip, const uint8_t* d_in, const uint8_t* d_uv);
 int launch_hash(avd_ctx* ctx, int n);
 int avd_calls_in_flight();      // avd_capi.hip: contexts of this process holding an enqueued, undrained avd_analyze_* call
 int launch_farneback(avd_ctx* ctx, const uint8_t* d_small, int n);    // all pairs of n resident frames, into the Farneback scratch

@@ -28,9 +28,20 @@
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kPad = 16;     // bytes of padding left of pixel 0 in every LDS tile row
-constexpr int kLapSlots = 8; // per-band slots for per-wave Laplacian partial moments (<= 8 waves/workgroup)
+constexpr int kThreads = 256;       // workgroup size of the three ingest kernels
+constexpr int kPad = 16;            // bytes of padding left of pixel 0 in every LDS tile row
+constexpr int kMaxNI = 9;           // k_preprocess_vec: row chunks (3 x 16 B each) a lane holds in registers at most
+constexpr int kBandCap = 14;        // rows per band at most: 16 tile rows + LDS tables = 37 KiB at 1080p, 4 workgroups per CU
+constexpr int kLdsBudget = 48 * 1024;   // the tile stays under this so that >= 3 workgroups fit a CU
+static_assert(kThreads / 64 <= kLapSlots, "one moment slot per wave");
+
+// LDS plan, read by the kernels and by the launcher.  The tile is (rows_per_band + 2) rows of `pitch` bytes; behind it sit either the
+// resampling tables of k_preprocess_vec (LdsTabs, behind the FULL tile) or the three conversion tables of the NV12 table fill (behind the
+// rows the band has, rounded to 16: a short last band has them lower than the launcher reserved for).
+constexpr int kNvBias = 224, kNvTab = 704;     // NV12 conversion tables: entries, index bias (Y + offset in [-221, 475])
+__host__ __device__ constexpr size_t lds_tile_bytes(int trows, int pitch) { return (size_t)trows * pitch; }
+__host__ __device__ constexpr size_t lds_nvtab_off(int trows, int pitch) { return (lds_tile_bytes(trows, pitch) + 15) / 16 * 16; }
+constexpr size_t kNvTabBytes = 3 * sizeof(unsigned) * kNvTab;
 
 __device__ __forceinline__ int reflect101(int p, int len)
 {
@@ -82,12 +93,21 @@ __device__ __forceinline__ T wave_sum(T v)
     return v;
 }
 
-// blockIdx -> (frame, band): logical ids that are consecutive share blockIdx % 8, i.e. an XCD.
-__device__ __forceinline__ int xcd_remap(int bid, int total)
+// The band a workgroup owns.  blockIdx -> lid = (frame, band): logical ids that are consecutive share blockIdx % 8, i.e. an XCD.
+struct Band { int lid, f, band, r0, rows, trows; };      // rows [r0, r0 + rows) of frame f; tile row 0 = image row r0 - 1, trows = rows + 2
+
+// (no branch in here: the caller's early return then leaves the compiler free to sink the division under the first loads)
+__device__ __forceinline__ bool decode_band(const PreParams& P, int n, Band& b)      // false: idle tail block, b unusable
 {
+    const int total = n * P.nbands;
     const int per = (total + 7) >> 3;
-    const int lid = (bid & 7) * per + (bid >> 3);
-    return lid;      // may be >= total (idle tail block)
+    b.lid = (blockIdx.x & 7) * per + (blockIdx.x >> 3);
+    b.f = b.lid / P.nbands;
+    b.band = b.lid - b.f * P.nbands;
+    b.r0 = b.band * P.rows_per_band;
+    b.rows = min(P.rows_per_band, P.h - b.r0);
+    b.trows = b.rows + 2;
+    return b.lid < total;
 }
 
 __device__ __forceinline__ int reflect_once(int p, int len)      // valid for -len < p < 2*len-1
@@ -109,23 +129,18 @@ __device__ __forceinline__ uint4 gray16(const uint4& a, const uint4& b, const ui
 
 struct Moments { long long s, q; };
 
-// Phases 2-4 of a band whose gray rows [r0-1, r0+rows] (incl. column halo) sit in `tile`:
-// exact Laplacian moments, INTER_AREA horizontal partials, INTER_LINEAR 320x320 rows.
-// NT = workgroup size.  LTAB: the resampling tables were copied to LDS (layout LdsTabs) so that the
-// compute phases issue no global LOADS (the pipelined kernel keeps the next band's loads in flight
-// here, and vmcnt retires in order).
+// The resampling tables in LDS (k_preprocess_vec; the generic kernels read them from global memory).
 struct LdsTabs {
     LinTap lxt[AVD_SMALL], lyt[AVD_SMALL];
     int ax_begin[AVD_HASH], ax_count[AVD_HASH];
     float ax_first[AVD_HASH], ax_mid[AVD_HASH], ax_last[AVD_HASH];
 };
 
-template <int NT>
 __device__ __forceinline__ void fill_lds_tabs(LdsTabs* lt, const PreParams& P, int tid)
 {
     const uint2* sx = reinterpret_cast<const uint2*>(P.lxt);
     const uint2* sy = reinterpret_cast<const uint2*>(P.lyt);
-    for (int i = tid; i < AVD_SMALL; i += NT) {
+    for (int i = tid; i < AVD_SMALL; i += kThreads) {
         reinterpret_cast<uint2*>(lt->lxt)[i] = sx[i];
         reinterpret_cast<uint2*>(lt->lyt)[i] = sy[i];
     }
@@ -135,12 +150,15 @@ __device__ __forceinline__ void fill_lds_tabs(LdsTabs* lt, const PreParams& P, i
     }
 }
 
-template <int NT, bool LTAB>
-__device__ __forceinline__ Moments band_phases(const uint8_t* tile, const LdsTabs* lt, const PreParams& P, int f,
-                                               int band, int r0, int rows, int tid, uint8_t* __restrict__ small,
-                                               float* __restrict__ rowbuf)
+// Phases 2-4 of a band whose gray rows [r0-1, r0+rows] (incl. column halo) sit in `tile`:
+// exact Laplacian moments, INTER_AREA horizontal partials, INTER_LINEAR 320x320 rows.
+// LTAB: the resampling tables come from LDS (lt) instead of global memory: the staged kernel has its whole band's loads in
+// flight and vmcnt retires in order, so it fetches the tables ahead of them (fill_lds_tabs) and issues no global load here.
+template <bool LTAB>
+__device__ __forceinline__ Moments band_phases(const uint8_t* tile, const LdsTabs* lt, const PreParams& P, const Band& b, int tid,
+                                               uint8_t* __restrict__ small, float* __restrict__ rowbuf)
 {
-    constexpr int kThreads = NT;
+    const int f = b.f, band = b.band, r0 = b.r0, rows = b.rows;
     const int w = P.w, h = P.h, pitch = P.pitch;
     // ---- Laplacian moments, exact, from row-pair products -----------------------------------
     // lap(t,x) = T(t-1,x) + T(t+1,x) + T(t,x-1) + T(t,x+1) - 4 T(t,x) on the haloed tile T
@@ -159,7 +177,7 @@ __device__ __forceinline__ Moments band_phases(const uint8_t* tile, const LdsTab
     long long s_acc = 0, q_acc = 0;
     {
         const int quads = (w + 3) >> 2;
-        const int trows = rows + 2;
+        const int trows = rows + 2;             // formed from rows here: the one-row branch below is then known to walk <= 3 rows
         const unsigned ones = 0x01010101u;
         unsigned iA = 0, iHR = 0, iH2 = 0, iV1 = 0, iV2 = 0, iDp = 0, iDm = 0;   // products with the interior weights
         int xA = 0;                                                                // A with weight 1 (signed: also corrects 20 -> 19)
@@ -352,10 +370,89 @@ __device__ __forceinline__ Moments band_phases(const uint8_t* tile, const LdsTab
             }
         }
     }
-    Moments m;
-    m.s = s_acc;
-    m.q = q_acc;
-    return m;
+    return Moments{s_acc, q_acc};
+}
+
+// per-wave partial moments, summed per frame in k_hash (atomics on the 16 B/frame accumulators
+// serialise in L2: 65 k same-line atomics cost ~50 us per launch)
+__device__ __forceinline__ void store_moments(long long* __restrict__ lap_part, int lid, int tid, const Moments& m)
+{
+    const long long s64 = wave_sum(m.s), q64 = wave_sum(m.q);
+    if ((tid & 63) == 0) {
+        long long* slot = lap_part + ((int64_t)lid * kLapSlots + (tid >> 6)) * 2;
+        slot[0] = s64; slot[1] = q64;
+    }
+}
+
+// column halo (BORDER_REFLECT_101) of a filled tile: pixel -1 := pixel 1, pixel w := pixel w-2
+__device__ __forceinline__ void fill_column_halo(uint8_t* tile, int trows, int pitch, int w, int tid)
+{
+    __syncthreads();
+    for (int tr = tid; tr < trows; tr += kThreads) {
+        uint8_t* row = tile + tr * pitch + kPad;
+        row[-1] = row[reflect101(-1, w)];
+        row[w] = row[reflect101(w, w)];
+    }
+    __syncthreads();
+}
+
+// ---- the fills: gray rows [r0-1, r0+rows] of the band into the tile.  They are all the kernels differ in. ----
+
+// BGR, any geometry / alignment: one byte-wise pixel per work item
+__device__ __forceinline__ void fill_bgr_scalar(uint8_t* tile, const uint8_t* frame, const PreParams& P, const Band& b, int tid)
+{
+    const int w = P.w, pitch = P.pitch;
+    for (int it = tid; it < b.trows * w; it += kThreads) {
+        const int tr = it / w, x = it - tr * w;
+        const int y = reflect_once(b.r0 - 1 + tr, P.h);
+        tile[tr * pitch + kPad + x] = (uint8_t)gray1(frame + (int64_t)y * P.row_stride + x * 3);
+    }
+}
+
+// BGR, 16-byte aligned rows of w % 16 == 0 pixels: one 16-pixel chunk (3 x 16 B) per work item
+__device__ __forceinline__ void fill_bgr_vec16(uint8_t* tile, const uint8_t* frame, const PreParams& P, const Band& b, int tid)
+{
+    const int chunks = P.w >> 4, pitch = P.pitch;
+    for (int it = tid; it < b.trows * chunks; it += kThreads) {
+        const int tr = it / chunks, c = it - tr * chunks;
+        const int y = reflect_once(b.r0 - 1 + tr, P.h);
+        const uint4* src = reinterpret_cast<const uint4*>(frame + (int64_t)y * P.row_stride + c * 48);
+        *reinterpret_cast<uint4*>(tile + tr * pitch + kPad + c * 16) = gray16(src[0], src[1], src[2]);
+    }
+}
+
+// BGR, register-staged (w % 16 == 0, <= 16 * kThreads px): every lane owns one 16-pixel column chunk and issues ALL its NI
+// row loads (3 x 16 B each) before the first conversion, so a workgroup has its whole band in flight at once; conversions
+// start as the words arrive (vmcnt counts down in issue order).  The lanes that convert the first / last chunk also write
+// the reflected column halo bytes, which saves a barrier.
+template <int NI>
+__device__ __forceinline__ void fill_bgr_staged(uint8_t* tile, const uint8_t* frame, const PreParams& P, const Band& b, int tid)
+{
+    const int pitch = P.pitch;
+    const int chunks = P.w >> 4;
+    const int rpp = kThreads / chunks;               // tile rows covered per pass of the workgroup
+    const int rsub = tid / chunks, c = tid - rsub * chunks;
+    if (rsub < rpp) {
+        const uint8_t* col = frame + c * 48;
+        uint4 q[NI][3];
+#pragma unroll
+        for (int k = 0; k < NI; k++) {
+            const int t = min(rsub + k * rpp, b.trows - 1);  // surplus items re-read the last row (same bytes)
+            const int y = reflect_once(b.r0 - 1 + t, P.h);
+            const uint4* src = reinterpret_cast<const uint4*>(col + (int64_t)y * P.row_stride);
+            q[k][0] = src[0]; q[k][1] = src[1]; q[k][2] = src[2];
+        }
+        uint8_t* dst = tile + kPad + c * 16;
+#pragma unroll
+        for (int k = 0; k < NI; k++) {
+            const int t = min(rsub + k * rpp, b.trows - 1);
+            const uint4 g = gray16(q[k][0], q[k][1], q[k][2]);
+            uint8_t* d = dst + t * pitch;
+            *reinterpret_cast<uint4*>(d) = g;
+            if (c == 0) d[-1] = (uint8_t)(g.x >> 8);                 // pixel -1 := pixel 1
+            if (c == chunks - 1) d[16] = (uint8_t)(g.w >> 16);       // pixel w  := pixel w-2
+        }
+    }
 }
 
 // Generic kernel: one workgroup per band, any geometry / alignment (scalar loads if needed).
@@ -366,106 +463,33 @@ __global__ __launch_bounds__(kThreads) void k_preprocess(const uint8_t* __restri
                                                         long long* __restrict__ lap_part)
 {
     extern __shared__ __align__(16) uint8_t tile[];
-    const int total = n * P.nbands;
-    const int lid = xcd_remap(blockIdx.x, total);
-    if (lid >= total) return;
-    const int f = lid / P.nbands;
-    const int band = lid - f * P.nbands;
-    const int h = P.h, w = P.w, pitch = P.pitch;
-    const int r0 = band * P.rows_per_band;
-    const int rows = min(P.rows_per_band, h - r0);
+    Band b;
+    if (!decode_band(P, n, b)) return;
     const int tid = threadIdx.x;
-    const uint8_t* frame = bgr + (int64_t)f * P.frame_stride;
-    const int trows = rows + 2;                            // tile row 0 = image row r0-1
-    if (VEC) {
-        const int chunks = w >> 4;
-        for (int it = tid; it < trows * chunks; it += kThreads) {
-            const int tr = it / chunks, c = it - tr * chunks;
-            const int y = reflect_once(r0 - 1 + tr, h);
-            const uint4* src = reinterpret_cast<const uint4*>(frame + (int64_t)y * P.row_stride + c * 48);
-            *reinterpret_cast<uint4*>(tile + tr * pitch + kPad + c * 16) = gray16(src[0], src[1], src[2]);
-        }
-    } else {
-        for (int it = tid; it < trows * w; it += kThreads) {
-            const int tr = it / w, x = it - tr * w;
-            const int y = reflect_once(r0 - 1 + tr, h);
-            tile[tr * pitch + kPad + x] = (uint8_t)gray1(frame + (int64_t)y * P.row_stride + x * 3);
-        }
-    }
-    __syncthreads();
-    // column halo (BORDER_REFLECT_101): pixel -1 := pixel 1, pixel w := pixel w-2
-    for (int tr = tid; tr < trows; tr += kThreads) {
-        uint8_t* row = tile + tr * pitch + kPad;
-        row[-1] = row[reflect101(-1, w)];
-        row[w] = row[reflect101(w, w)];
-    }
-    __syncthreads();
-    const Moments m = band_phases<kThreads, false>(tile, nullptr, P, f, band, r0, rows, tid, small, rowbuf);
-    // per-wave partial moments, summed per frame in k_hash (atomics on the 16 B/frame accumulators
-    // serialise in L2: 65 k same-line atomics cost ~50 us per launch)
-    const long long s64 = wave_sum(m.s), q64 = wave_sum(m.q);
-    if ((tid & 63) == 0) {
-        long long* slot = lap_part + ((int64_t)lid * kLapSlots + (tid >> 6)) * 2;
-        slot[0] = s64; slot[1] = q64;
-    }
+    const uint8_t* frame = bgr + (int64_t)b.f * P.frame_stride;
+    if (VEC) fill_bgr_vec16(tile, frame, P, b, tid);
+    else fill_bgr_scalar(tile, frame, P, b, tid);
+    fill_column_halo(tile, b.trows, P.pitch, P.w, tid);
+    store_moments(lap_part, b.lid, tid, band_phases<false>(tile, nullptr, P, b, tid, small, rowbuf));
 }
 
-// Aligned fast path (w % 16 == 0, <= 4096 px): one workgroup per band like the generic kernel, but
-// every lane owns one 16-pixel column chunk and issues ALL its NI row loads (3 x 16 B each) before
-// the first conversion, so a workgroup has its whole band in flight at once; conversions start as
-// the words arrive (vmcnt counts down in issue order).  The lanes that convert the first / last
-// chunk also write the reflected halo bytes, which saves a barrier.
-template <int NI, int NT>
-__global__ __launch_bounds__(NT, 4) void k_preprocess_vec(const uint8_t* __restrict__ bgr, int n,
+// Aligned fast path: one workgroup per band like the generic kernel, the band staged in registers (fill_bgr_staged)
+// and the resampling tables in LDS.
+template <int NI>
+__global__ __launch_bounds__(kThreads, 4) void k_preprocess_vec(const uint8_t* __restrict__ bgr, int n,
                                                                PreParams P, uint8_t* __restrict__ small,
                                                                float* __restrict__ rowbuf,
                                                                long long* __restrict__ lap_part)
 {
     extern __shared__ __align__(16) uint8_t tile[];
-    const int total = n * P.nbands;
-    const int lid = xcd_remap(blockIdx.x, total);
-    if (lid >= total) return;
-    const int f = lid / P.nbands, band = lid - f * P.nbands;
-    const int h = P.h, w = P.w, pitch = P.pitch;
-    const int r0 = band * P.rows_per_band;
-    const int rows = min(P.rows_per_band, h - r0);
-    const int trows = rows + 2;
+    Band b;
+    if (!decode_band(P, n, b)) return;
     const int tid = threadIdx.x;
-    const int chunks = w >> 4;
-    const int rpp = NT / chunks;                     // tile rows covered per pass of the workgroup
-    const int rsub = tid / chunks, c = tid - rsub * chunks;
-    LdsTabs* lt = reinterpret_cast<LdsTabs*>(tile + (P.rows_per_band + 2) * pitch);
-    fill_lds_tabs<NT>(lt, P, tid);
-    if (rsub < rpp) {
-        const uint8_t* col = bgr + (int64_t)f * P.frame_stride + c * 48;
-        uint4 q[NI][3];
-#pragma unroll
-        for (int k = 0; k < NI; k++) {
-            const int t = min(rsub + k * rpp, trows - 1);  // surplus items re-read the last row (same bytes)
-            const int y = reflect_once(r0 - 1 + t, h);
-            const uint4* src = reinterpret_cast<const uint4*>(col + (int64_t)y * P.row_stride);
-            q[k][0] = src[0]; q[k][1] = src[1]; q[k][2] = src[2];
-        }
-        uint8_t* dst = tile + kPad + c * 16;
-#pragma unroll
-        for (int k = 0; k < NI; k++) {
-            const int t = min(rsub + k * rpp, trows - 1);
-            const uint4 g = gray16(q[k][0], q[k][1], q[k][2]);
-            uint8_t* d = dst + t * pitch;
-            *reinterpret_cast<uint4*>(d) = g;
-            if (c == 0) d[-1] = (uint8_t)(g.x >> 8);                 // pixel -1 := pixel 1
-            if (c == chunks - 1) d[16] = (uint8_t)(g.w >> 16);       // pixel w  := pixel w-2
-        }
-    }
+    LdsTabs* lt = reinterpret_cast<LdsTabs*>(tile + lds_tile_bytes(P.rows_per_band + 2, P.pitch));
+    fill_lds_tabs(lt, P, tid);
+    fill_bgr_staged<NI>(tile, bgr + (int64_t)b.f * P.frame_stride, P, b, tid);
     __syncthreads();
-    const Moments m = band_phases<NT, true>(tile, lt, P, f, band, r0, rows, tid, small, rowbuf);
-    // per-wave partial moments, summed per frame in k_hash (atomics on the 16 B/frame accumulators
-    // serialise in L2: 65 k same-line atomics cost ~50 us per launch)
-    const long long s64 = wave_sum(m.s), q64 = wave_sum(m.q);
-    if ((tid & 63) == 0) {
-        long long* slot = lap_part + ((int64_t)lid * kLapSlots + (tid >> 6)) * 2;
-        slot[0] = s64; slot[1] = q64;
-    }
+    store_moments(lap_part, b.lid, tid, band_phases<true>(tile, lt, P, b, tid, small, rowbuf));
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -491,7 +515,6 @@ __device__ __forceinline__ ChromaTerms chroma_terms(int U, int V, const YuvConst
 }
 
 // the table form: the three indices' chroma parts (libswscale's per-U / per-V table offsets), biased so that Y + offset >= 0
-constexpr int kNvBias = 224, kNvTab = 704;     // Y + offset in [-221, 475]
 __device__ __forceinline__ ChromaTerms chroma_offsets(int U, int V, const YuvConsts& k)
 {
     ChromaTerms t;
@@ -523,98 +546,93 @@ __device__ __forceinline__ unsigned gray4_nv12(unsigned yw, unsigned cw, const Y
            (gray_from_yuv((yw >> 16) & 0xFF, t1, k.cy) << 16) | (gray_from_yuv(yw >> 24, t1, k.cy) << 24);
 }
 
+// NV12, any geometry / alignment: one pixel per work item
+__device__ __forceinline__ void fill_nv12_scalar(uint8_t* tile, const uint8_t* yfr, const uint8_t* cfr, const Nv12Params& nv,
+                                                 const PreParams& P, const Band& b, int tid)
+{
+    const int w = P.w, pitch = P.pitch;
+    for (int it = tid; it < b.trows * w; it += kThreads) {
+        const int tr = it / w, x = it - tr * w;
+        const int y = reflect_once(b.r0 - 1 + tr, P.h);
+        const uint8_t* cp = cfr + (int64_t)(y >> 1) * nv.uv_row_stride + (x >> 1) * 2;
+        const ChromaTerms t = chroma_terms(cp[0], cp[1], nv.k);
+        tile[tr * pitch + kPad + x] = (uint8_t)gray_from_yuv(yfr[(int64_t)y * P.row_stride + x], t, nv.k.cy);
+    }
+}
+
+// NV12, 16-byte aligned planes of w % 16 == 0 pixels.
+// libswscale's converter IS a table lookup: B = T[Y + ob(U)], G = T[Y + og(U, V)], R = T[Y + or(V)] with one clip table T(i) = clip8((c0 + i cy) >> 16).
+// Three LDS tables of cv2's gray weight times T (3735 T, 19235 T + the rounding 2^14, 9798 T; 32-bit entries, index bias kNvBias), so a pixel is
+// three index additions, three ds_read_b32, one three-operand add and a shift -- instead of three multiply-adds, three shifts, three clamps and
+// three multiply-adds (12.3 -> 8.8 vector instructions per pixel; the LDS pipe does the lookups beside them).  Same integers by construction.
+__device__ __forceinline__ void fill_nv12_tables(uint8_t* tile, const uint8_t* yfr, const uint8_t* cfr, const Nv12Params& nv,
+                                                 const PreParams& P, const Band& b, int tid)
+{
+    const int h = P.h, pitch = P.pitch, r0 = b.r0, rows = b.rows, trows = b.trows;
+    unsigned* const tabB = reinterpret_cast<unsigned*>(tile + lds_nvtab_off(trows, pitch));
+    unsigned* const tabG = tabB + kNvTab;
+    unsigned* const tabR = tabG + kNvTab;
+    for (int i = tid; i < kNvTab; i += kThreads) {
+        const unsigned v = (unsigned)clip8((nv.k.c0 + (i - kNvBias) * nv.k.cy) >> 16);
+        tabB[i] = v * 3735u; tabG[i] = v * 19235u + (1u << 14); tabR[i] = v * 9798u;
+    }
+    __syncthreads();
+    // one work item = one chroma row x one 16-pixel chunk: the eight chroma-term triples are formed once and serve the
+    // two luma rows that share them (they are 8.5 of the ~27 integer operations a pixel costs otherwise)
+    const int ylo = r0 - 1, yhi = r0 + rows;              // image rows of tile rows 0 and trows - 1, before reflection
+    const int ya = max(ylo, 0), yb = min(yhi, h - 1);      // the ones that exist
+    const int p0 = ya >> 1, np = (yb >> 1) - p0 + 1;
+    const int chunks = P.w >> 4;
+    for (int it = tid; it < np * chunks; it += kThreads) {
+        const int pr = it / chunks, c = it - pr * chunks, p = p0 + pr;
+        const uint4 cc = *reinterpret_cast<const uint4*>(cfr + (int64_t)p * nv.uv_row_stride + c * 16);
+        const unsigned cw[4] = {cc.x, cc.y, cc.z, cc.w};
+        ChromaTerms t[8];
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            t[2 * j] = chroma_offsets(cw[j] & 0xFF, (cw[j] >> 8) & 0xFF, nv.k);
+            t[2 * j + 1] = chroma_offsets((cw[j] >> 16) & 0xFF, cw[j] >> 24, nv.k);
+        }
+#pragma unroll
+        for (int s2 = 0; s2 < 2; s2++) {
+            const int y = 2 * p + s2;
+            if (y < ya || y > yb) continue;
+            const uint4 yy = *reinterpret_cast<const uint4*>(yfr + (int64_t)y * P.row_stride + c * 16);
+            const unsigned yw[4] = {yy.x, yy.y, yy.z, yy.w};
+            unsigned g[4];
+#pragma unroll
+            for (int j = 0; j < 4; j++)
+                g[j] = gray_from_tables(yw[j] & 0xFF, t[2 * j], tabB, tabG, tabR) | (gray_from_tables((yw[j] >> 8) & 0xFF, t[2 * j], tabB, tabG, tabR) << 8) |
+                       (gray_from_tables((yw[j] >> 16) & 0xFF, t[2 * j + 1], tabB, tabG, tabR) << 16) | (gray_from_tables(yw[j] >> 24, t[2 * j + 1], tabB, tabG, tabR) << 24);
+            *reinterpret_cast<uint4*>(tile + (y - ylo) * pitch + kPad + c * 16) = make_uint4(g[0], g[1], g[2], g[3]);
+        }
+    }
+    __syncthreads();
+    // BORDER_REFLECT_101 rows: image row -1 is row 1, row h is row h - 2 (both already in the tile)
+    if (ylo < 0)
+        for (int c = tid; c < chunks; c += kThreads)
+            *reinterpret_cast<uint4*>(tile + kPad + c * 16) = *reinterpret_cast<const uint4*>(tile + 2 * pitch + kPad + c * 16);
+    if (yhi > h - 1)
+        for (int c = tid; c < chunks; c += kThreads)
+            *reinterpret_cast<uint4*>(tile + (trows - 1) * pitch + kPad + c * 16) =
+                *reinterpret_cast<const uint4*>(tile + (trows - 3) * pitch + kPad + c * 16);
+}
+
 template <bool VEC>
 __global__ __launch_bounds__(kThreads) void k_preprocess_nv12(const uint8_t* __restrict__ yplane, Nv12Params nv, int n,
                                                              PreParams P, uint8_t* __restrict__ small,
                                                              float* __restrict__ rowbuf, long long* __restrict__ lap_part)
 {
     extern __shared__ __align__(16) uint8_t tile[];
-    const int total = n * P.nbands;
-    const int lid = xcd_remap(blockIdx.x, total);
-    if (lid >= total) return;
-    const int f = lid / P.nbands;
-    const int band = lid - f * P.nbands;
-    const int h = P.h, w = P.w, pitch = P.pitch;
-    const int r0 = band * P.rows_per_band;
-    const int rows = min(P.rows_per_band, h - r0);
+    Band b;
+    if (!decode_band(P, n, b)) return;
     const int tid = threadIdx.x;
-    const uint8_t* yfr = yplane + (int64_t)f * P.frame_stride;
-    const uint8_t* cfr = nv.uv + (int64_t)f * nv.uv_frame_stride;
-    const int trows = rows + 2;                            // tile row 0 = image row r0-1
-    if (VEC) {
-        // libswscale's converter IS a table lookup: B = T[Y + ob(U)], G = T[Y + og(U, V)], R = T[Y + or(V)] with one clip table T(i) = clip8((c0 + i cy) >> 16).
-        // Round 5: three LDS tables of cv2's gray weight times T (3735 T, 19235 T + the rounding 2^14, 9798 T; 32-bit entries, index bias kNvBias), so a pixel is
-        // three index additions, three ds_read_b32, one three-operand add and a shift -- instead of three multiply-adds, three shifts, three clamps and
-        // three multiply-adds (12.3 -> 8.8 vector instructions per pixel; the LDS pipe does the lookups beside them).  Same integers by construction.
-        unsigned* const tabB = reinterpret_cast<unsigned*>(tile + ((size_t)trows * pitch + 15) / 16 * 16);
-        unsigned* const tabG = tabB + kNvTab;
-        unsigned* const tabR = tabG + kNvTab;
-        for (int i = tid; i < kNvTab; i += kThreads) {
-            const unsigned v = (unsigned)clip8((nv.k.c0 + (i - kNvBias) * nv.k.cy) >> 16);
-            tabB[i] = v * 3735u; tabG[i] = v * 19235u + (1u << 14); tabR[i] = v * 9798u;
-        }
-        __syncthreads();
-        // one work item = one chroma row x one 16-pixel chunk: the eight chroma-term triples are formed once and serve the
-        // two luma rows that share them (they are 8.5 of the ~27 integer operations a pixel costs otherwise)
-        const int ylo = r0 - 1, yhi = r0 + rows;              // image rows of tile rows 0 and trows - 1, before reflection
-        const int ya = max(ylo, 0), yb = min(yhi, h - 1);      // the ones that exist
-        const int p0 = ya >> 1, np = (yb >> 1) - p0 + 1;
-        const int chunks = w >> 4;
-        for (int it = tid; it < np * chunks; it += kThreads) {
-            const int pr = it / chunks, c = it - pr * chunks, p = p0 + pr;
-            const uint4 cc = *reinterpret_cast<const uint4*>(cfr + (int64_t)p * nv.uv_row_stride + c * 16);
-            const unsigned cw[4] = {cc.x, cc.y, cc.z, cc.w};
-            ChromaTerms t[8];
-#pragma unroll
-            for (int j = 0; j < 4; j++) {
-                t[2 * j] = chroma_offsets(cw[j] & 0xFF, (cw[j] >> 8) & 0xFF, nv.k);
-                t[2 * j + 1] = chroma_offsets((cw[j] >> 16) & 0xFF, cw[j] >> 24, nv.k);
-            }
-#pragma unroll
-            for (int s2 = 0; s2 < 2; s2++) {
-                const int y = 2 * p + s2;
-                if (y < ya || y > yb) continue;
-                const uint4 yy = *reinterpret_cast<const uint4*>(yfr + (int64_t)y * P.row_stride + c * 16);
-                const unsigned yw[4] = {yy.x, yy.y, yy.z, yy.w};
-                unsigned g[4];
-#pragma unroll
-                for (int j = 0; j < 4; j++)
-                    g[j] = gray_from_tables(yw[j] & 0xFF, t[2 * j], tabB, tabG, tabR) | (gray_from_tables((yw[j] >> 8) & 0xFF, t[2 * j], tabB, tabG, tabR) << 8) |
-                           (gray_from_tables((yw[j] >> 16) & 0xFF, t[2 * j + 1], tabB, tabG, tabR) << 16) | (gray_from_tables(yw[j] >> 24, t[2 * j + 1], tabB, tabG, tabR) << 24);
-                *reinterpret_cast<uint4*>(tile + (y - ylo) * pitch + kPad + c * 16) = make_uint4(g[0], g[1], g[2], g[3]);
-            }
-        }
-        __syncthreads();
-        // BORDER_REFLECT_101 rows: image row -1 is row 1, row h is row h - 2 (both already in the tile)
-        if (ylo < 0)
-            for (int c = tid; c < chunks; c += kThreads)
-                *reinterpret_cast<uint4*>(tile + kPad + c * 16) = *reinterpret_cast<const uint4*>(tile + 2 * pitch + kPad + c * 16);
-        if (yhi > h - 1)
-            for (int c = tid; c < chunks; c += kThreads)
-                *reinterpret_cast<uint4*>(tile + (trows - 1) * pitch + kPad + c * 16) =
-                    *reinterpret_cast<const uint4*>(tile + (trows - 3) * pitch + kPad + c * 16);
-    } else {
-        for (int it = tid; it < trows * w; it += kThreads) {
-            const int tr = it / w, x = it - tr * w;
-            const int y = reflect_once(r0 - 1 + tr, h);
-            const uint8_t* cp = cfr + (int64_t)(y >> 1) * nv.uv_row_stride + (x >> 1) * 2;
-            const ChromaTerms t = chroma_terms(cp[0], cp[1], nv.k);
-            tile[tr * pitch + kPad + x] = (uint8_t)gray_from_yuv(yfr[(int64_t)y * P.row_stride + x], t, nv.k.cy);
-        }
-    }
-    __syncthreads();
-    for (int tr = tid; tr < trows; tr += kThreads) {      // column halo (BORDER_REFLECT_101)
-        uint8_t* row = tile + tr * pitch + kPad;
-        row[-1] = row[reflect101(-1, w)];
-        row[w] = row[reflect101(w, w)];
-    }
-    __syncthreads();
-    const Moments m = band_phases<kThreads, false>(tile, nullptr, P, f, band, r0, rows, tid, small, rowbuf);
-    const long long s64 = wave_sum(m.s), q64 = wave_sum(m.q);
-    if ((tid & 63) == 0) {
-        long long* slot = lap_part + ((int64_t)lid * kLapSlots + (tid >> 6)) * 2;
-        slot[0] = s64; slot[1] = q64;
-    }
+    const uint8_t* yfr = yplane + (int64_t)b.f * P.frame_stride;
+    const uint8_t* cfr = nv.uv + (int64_t)b.f * nv.uv_frame_stride;
+    if (VEC) fill_nv12_tables(tile, yfr, cfr, nv, P, b, tid);
+    else fill_nv12_scalar(tile, yfr, cfr, nv, P, b, tid);
+    fill_column_halo(tile, b.trows, P.pitch, P.w, tid);
+    store_moments(lap_part, b.lid, tid, band_phases<false>(tile, nullptr, P, b, tid, small, rowbuf));
 }
 
 // 32x32 INTER_AREA cells from the per-row partials (vertical accumulation in cv2's row
@@ -695,73 +713,64 @@ __global__ __launch_bounds__(1024) void k_hash(const float* __restrict__ rowbuf,
 
 }  // namespace
 
-int launch_preprocess(avd_ctx* ctx, const uint8_t* d_bgr, int n, int h, int w,
-                      int64_t row_stride, int64_t frame_stride)
+// The band plan of width w: how the host cuts frames into bands, and which kernel shape that allows.
+BandPlan band_plan(int w)
 {
-    Workspace& ws = ctx->ws;
-    PreParams P = ws.pre;
-    P.row_stride = row_stride;
-    P.frame_stride = frame_stride;
-    const int total = n * P.nbands;
-    const bool vec = (w % 16 == 0) && (row_stride % 16 == 0) && (frame_stride % 16 == 0) &&
-                     (reinterpret_cast<uintptr_t>(d_bgr) % 16 == 0);
-    const int chunks = w >> 4;
-    const size_t lds1 = (size_t)(P.rows_per_band + 2) * P.pitch;
-    const size_t lds_vec = lds1 + sizeof(LdsTabs);
-    const int grid1 = ((total + 7) / 8) * 8;
-    const int ni_nt = (vec && chunks <= kThreads) ? (P.rows_per_band + 2 + kThreads / chunks - 1) / (kThreads / chunks) : 0;
-    ws.lap_waves = kThreads / 64;
-    if (ni_nt > 0 && ni_nt <= 9) {
-#define AVD_VEC_CASE(N)                                                                                                     \
-    hipLaunchKernelGGL((k_preprocess_vec<N, kThreads>), dim3(grid1), dim3(kThreads), lds_vec, ctx->stream, d_bgr, n, P,   \
-                       ws.d_small + (size_t)ws.f0 * AVD_NPIX, ws.d_rowbuf + ws.rowbuf_off, ws.d_lap_part + ws.lappart_off)
-        switch (ni_nt) {
-        case 1: case 2: case 3: AVD_VEC_CASE(3); break;
-        case 4: AVD_VEC_CASE(4); break;
-        case 5: AVD_VEC_CASE(5); break;
-        case 6: AVD_VEC_CASE(6); break;
-        case 7: AVD_VEC_CASE(7); break;
-        case 8: AVD_VEC_CASE(8); break;
-        default: AVD_VEC_CASE(9); break;
-        }
-#undef AVD_VEC_CASE
-    } else {
-        const int grid = ((total + 7) / 8) * 8;
-        const size_t lds = (size_t)(P.rows_per_band + 2) * P.pitch;
-        if (vec)
-            hipLaunchKernelGGL(k_preprocess<true>, dim3(grid), dim3(kThreads), lds, ctx->stream,
-                               d_bgr, n, P, ws.d_small + (size_t)ws.f0 * AVD_NPIX, ws.d_rowbuf + ws.rowbuf_off, ws.d_lap_part + ws.lappart_off);
-        else
-            hipLaunchKernelGGL(k_preprocess<false>, dim3(grid), dim3(kThreads), lds, ctx->stream,
-                               d_bgr, n, P, ws.d_small + (size_t)ws.f0 * AVD_NPIX, ws.d_rowbuf + ws.rowbuf_off, ws.d_lap_part + ws.lappart_off);
-    }
-    HIP_TRY(ctx, hipGetLastError());
-    return 0;
+    BandPlan p{};
+    p.pitch = ((w + 2 * kPad + 15) / 16) * 16;
+    int r = kLdsBudget / p.pitch - 2;                  // LDS tile = (rows + 2) * pitch bytes
+    int cap = kBandCap;
+    const int chunks = w / 16;
+    const bool staged = w % 16 == 0 && chunks <= kThreads;
+    const int rpp = staged ? kThreads / chunks : 0;    // tile rows one pass of the staged kernel's workgroup covers
+    // a lane of the staged kernel holds at most kMaxNI row chunks, so the tile may have at most kMaxNI * rpp rows -- 7-row bands at 4K
+    if (staged) cap = std::min(cap, kMaxNI * rpp - 2);
+    p.rows_per_band = std::max(std::min(r, cap), 1);
+    // every width up to 16 * kThreads lands on one of 3, 4, 6, 8, 9 (narrow frames need fewer than 3 passes: surplus passes re-read the last row)
+    if (staged) p.ni = std::max(3, (p.rows_per_band + 2 + rpp - 1) / rpp);
+    return p;
 }
 
-int launch_preprocess_nv12(avd_ctx* ctx, const uint8_t* d_y, const Nv12Params& nv, int n, int h, int w,
-                           int64_t row_stride, int64_t frame_stride)
+static bool aligned16(const void* p, int64_t row_stride, int64_t frame_stride)
+{
+    return reinterpret_cast<uintptr_t>(p) % 16 == 0 && row_stride % 16 == 0 && frame_stride % 16 == 0;
+}
+
+int launch_preprocess(avd_ctx* ctx, const avd_clip& clip, const uint8_t* d_in, const uint8_t* d_uv)
 {
     Workspace& ws = ctx->ws;
     PreParams P = ws.pre;
-    P.row_stride = row_stride;
-    P.frame_stride = frame_stride;
-    const int total = n * P.nbands;
-    const bool vec = (w % 16 == 0) && (row_stride % 16 == 0) && (frame_stride % 16 == 0) && (nv.uv_row_stride % 16 == 0) &&
-                     (nv.uv_frame_stride % 16 == 0) && (reinterpret_cast<uintptr_t>(d_y) % 16 == 0) &&
-                     (reinterpret_cast<uintptr_t>(nv.uv) % 16 == 0);
-    const int grid = ((total + 7) / 8) * 8;
-    size_t lds = (size_t)(P.rows_per_band + 2) * P.pitch;
-    if (vec) lds = (lds + 15) / 16 * 16 + 3 * sizeof(unsigned) * 704;     // the three conversion tables behind the tile (k_preprocess_nv12, kNvTab)
-    // (a register-staged variant in the style of k_preprocess_vec measured no faster: the kernel is bound by the
-    // conversion's integer arithmetic, not by how its loads are issued -- profiles/r02_experiments.md)
-    ws.lap_waves = kThreads / 64;
-    if (vec)
-        hipLaunchKernelGGL(k_preprocess_nv12<true>, dim3(grid), dim3(kThreads), lds, ctx->stream, d_y, nv, n, P, ws.d_small + (size_t)ws.f0 * AVD_NPIX,
+    P.row_stride = clip.row_stride;
+    P.frame_stride = clip.frame_stride;
+    const int n = clip.n;
+    const int grid = (n * P.nbands + 7) / 8 * 8;
+    const size_t tile = lds_tile_bytes(P.rows_per_band + 2, P.pitch);
+    const bool vec = P.w % 16 == 0 && aligned16(d_in, clip.row_stride, clip.frame_stride) &&
+                     (!d_uv || aligned16(d_uv, clip.uv_row_stride, clip.uv_frame_stride));
+    auto launch = [&](auto kernel, size_t lds, auto... source) {
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(kThreads), lds, ctx->stream, source..., n, P, ws.d_small + (size_t)ws.f0 * AVD_NPIX,
                            ws.d_rowbuf + ws.rowbuf_off, ws.d_lap_part + ws.lappart_off);
-    else
-        hipLaunchKernelGGL(k_preprocess_nv12<false>, dim3(grid), dim3(kThreads), lds, ctx->stream, d_y, nv, n, P, ws.d_small + (size_t)ws.f0 * AVD_NPIX,
-                           ws.d_rowbuf + ws.rowbuf_off, ws.d_lap_part + ws.lappart_off);
+    };
+    if (d_uv) {
+        Nv12Params nv{};
+        nv.uv = d_uv; nv.uv_row_stride = clip.uv_row_stride; nv.uv_frame_stride = clip.uv_frame_stride;
+        build_yuv_consts(nv.k);
+        // (a register-staged variant in the style of k_preprocess_vec measured no faster: the kernel is bound by the
+        // conversion's integer arithmetic, not by how its loads are issued -- profiles/r02_experiments.md)
+        if (vec) launch(k_preprocess_nv12<true>, lds_nvtab_off(P.rows_per_band + 2, P.pitch) + kNvTabBytes, d_in, nv);
+        else launch(k_preprocess_nv12<false>, tile, d_in, nv);
+    } else if (const int ni = vec ? band_plan(P.w).ni : 0) {
+        const size_t lds = tile + sizeof(LdsTabs);
+        switch (ni) {
+        case 3: launch(k_preprocess_vec<3>, lds, d_in); break;
+        case 4: launch(k_preprocess_vec<4>, lds, d_in); break;
+        case 6: launch(k_preprocess_vec<6>, lds, d_in); break;
+        case 8: launch(k_preprocess_vec<8>, lds, d_in); break;
+        case 9: launch(k_preprocess_vec<9>, lds, d_in); break;
+        default: ctx->err = "internal error: the band plan asks for a k_preprocess_vec that is not built"; return AVD_ERR_DEVICE;
+        }
+    } else if (vec) launch(k_preprocess<true>, tile, d_in);
+    else launch(k_preprocess<false>, tile, d_in);
     HIP_TRY(ctx, hipGetLastError());
     return 0;
 }
@@ -773,7 +782,7 @@ int launch_hash(avd_ctx* ctx, int n)
     // the clip's slice of the call's buffers: frame ws.f0 onwards
     const size_t f0 = (size_t)ws.f0;
     hipLaunchKernelGGL(k_hash, dim3(n), dim3(1024), 0, ctx->stream, ws.d_rowbuf + ws.rowbuf_off, ws.hsh, ws.d_area + f0 * 1024,
-                       ws.d_hash + f0 * 1024, (const long long*)(ws.d_lap_part + ws.lappart_off), ws.pre.nbands, ws.lap_waves,
+                       ws.d_hash + f0 * 1024, (const long long*)(ws.d_lap_part + ws.lappart_off), ws.pre.nbands, kThreads / 64,
                        ws.d_lap + 2 * f0);
     HIP_TRY(ctx, hipGetLastError());
     return 0;

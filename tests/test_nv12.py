@@ -59,7 +59,8 @@ def test_roundtrip_through_the_synthetic_encoder(oracle):
 
 
 # ---- GPU: the ingest kernel --------------------------------------------------------------------
-NV12_GEOMS = [(2, 1080, 1920), (2, 720, 1280), (1, 2160, 3840), (3, 66, 102), (2, 360, 640), (2, 34, 48)]
+NV12_GEOMS = [(2, 1080, 1920), (2, 720, 1280), (1, 2160, 3840), (3, 66, 102), (2, 360, 640), (2, 34, 48),
+              (1, 46, 4112)]      # vector fill with a one-row bottom band: tile row 2 is reflected from tile row 0
 
 
 @pytest.mark.gpu
