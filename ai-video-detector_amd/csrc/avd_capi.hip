@@ -892,6 +892,12 @@ static int64_t impl_debug_fetch(avd_ctx* ctx, const char* name, void* out, size_
         return -1;
     };
     int k;
+    if (std::strcmp(name, "ingest_plan") == 0) {       // host state, not a device buffer: what launch_preprocess ran last
+        if (!ctx->ingest_plan_valid) { ctx->err = "ingest_plan not recorded yet: no ingest kernel was launched on this context"; return AVD_ERR_ARG; }
+        bytes = std::min(sizeof(IngestPlan), out_bytes);
+        std::memcpy(out, &ctx->ingest_plan, bytes);
+        return (int64_t)bytes;
+    }
     if (std::strcmp(name, "area") == 0) { src = ws.d_area; bytes = (size_t)n * 1024; }
     else if (std::strcmp(name, "small") == 0) { src = ws.d_small; bytes = (size_t)n * AVD_NPIX; }
     // the Farneback scratch holds ONE chunk (kFbChunk pairs): for longer clips these are the last chunk's buffers

@@ -90,6 +90,10 @@ struct HashParams {
 // ni: the k_preprocess_vec<NI> a 16-byte aligned BGR clip of this width runs (0: odd or too wide a width, the generic kernel).
 struct BandPlan { int rows_per_band, pitch, ni; };
 BandPlan band_plan(int w);
+// What launch_preprocess ran last on a context: read by tests through avd_debug_fetch "ingest_plan" (eight int32 in this order).
+enum IngestKernel { kIngestBgrScalar = 0, kIngestBgrVec16, kIngestBgrStaged, kIngestNv12Scalar, kIngestNv12Tables };
+struct IngestPlan { int h, w, rows_per_band, nbands, pitch, ni, lds_bytes, kernel; };
+static_assert(sizeof(IngestPlan) == 8 * sizeof(int), "avd_debug_fetch hands the struct out as int32[8]");
 constexpr int kLapSlots = 8;       // per-band slots of Workspace::d_lap_part, one per wave of the workgroup (4 written)
 
 // ---- owners of device and pinned host memory ------------------------------------------------
@@ -223,6 +227,8 @@ struct avd_ctx {
     FbConsts fbc;
     DevBuf<FbConsts> d_fbc;         // FbConsts on device
     int last_n = 0;
+    IngestPlan ingest_plan{};        // the last launch_preprocess of this context (debug buffer "ingest_plan")
+    int ingest_plan_valid = 0;       // 0 until the first ingest launch
     int rec_n = 0;                   // records the last avd_analyze_* call left in ws.d_rec (0 after any other entry point: avd_allgather_last_records checks it)
     void* comm = nullptr;            // RCCL communicator (avd_comm.cpp), bound at run time
     int comm_rank = 0, comm_world = 1;

@@ -747,7 +747,10 @@ int launch_preprocess(avd_ctx* ctx, const avd_clip& clip, const uint8_t* d_in, c
     const size_t tile = lds_tile_bytes(P.rows_per_band + 2, P.pitch);
     const bool vec = P.w % 16 == 0 && aligned16(d_in, clip.row_stride, clip.frame_stride) &&
                      (!d_uv || aligned16(d_uv, clip.uv_row_stride, clip.uv_frame_stride));
-    auto launch = [&](auto kernel, size_t lds, auto... source) {
+    const int ni = vec && !d_uv ? band_plan(P.w).ni : 0;
+    auto launch = [&](IngestKernel id, auto kernel, size_t lds, auto... source) {
+        ctx->ingest_plan = IngestPlan{P.h, P.w, P.rows_per_band, P.nbands, P.pitch, ni, (int)lds, id};
+        ctx->ingest_plan_valid = 1;
         hipLaunchKernelGGL(kernel, dim3(grid), dim3(kThreads), lds, ctx->stream, source..., n, P, ws.d_small + (size_t)ws.f0 * AVD_NPIX,
                            ws.d_rowbuf + ws.rowbuf_off, ws.d_lap_part + ws.lappart_off);
     };
@@ -757,20 +760,20 @@ int launch_preprocess(avd_ctx* ctx, const avd_clip& clip, const uint8_t* d_in, c
         build_yuv_consts(nv.k);
         // (a register-staged variant in the style of k_preprocess_vec measured no faster: the kernel is bound by the
         // conversion's integer arithmetic, not by how its loads are issued -- profiles/r02_experiments.md)
-        if (vec) launch(k_preprocess_nv12<true>, lds_nvtab_off(P.rows_per_band + 2, P.pitch) + kNvTabBytes, d_in, nv);
-        else launch(k_preprocess_nv12<false>, tile, d_in, nv);
-    } else if (const int ni = vec ? band_plan(P.w).ni : 0) {
+        if (vec) launch(kIngestNv12Tables, k_preprocess_nv12<true>, lds_nvtab_off(P.rows_per_band + 2, P.pitch) + kNvTabBytes, d_in, nv);
+        else launch(kIngestNv12Scalar, k_preprocess_nv12<false>, tile, d_in, nv);
+    } else if (ni) {
         const size_t lds = tile + sizeof(LdsTabs);
         switch (ni) {
-        case 3: launch(k_preprocess_vec<3>, lds, d_in); break;
-        case 4: launch(k_preprocess_vec<4>, lds, d_in); break;
-        case 6: launch(k_preprocess_vec<6>, lds, d_in); break;
-        case 8: launch(k_preprocess_vec<8>, lds, d_in); break;
-        case 9: launch(k_preprocess_vec<9>, lds, d_in); break;
+        case 3: launch(kIngestBgrStaged, k_preprocess_vec<3>, lds, d_in); break;
+        case 4: launch(kIngestBgrStaged, k_preprocess_vec<4>, lds, d_in); break;
+        case 6: launch(kIngestBgrStaged, k_preprocess_vec<6>, lds, d_in); break;
+        case 8: launch(kIngestBgrStaged, k_preprocess_vec<8>, lds, d_in); break;
+        case 9: launch(kIngestBgrStaged, k_preprocess_vec<9>, lds, d_in); break;
         default: ctx->err = "internal error: the band plan asks for a k_preprocess_vec that is not built"; return AVD_ERR_DEVICE;
         }
-    } else if (vec) launch(k_preprocess<true>, tile, d_in);
-    else launch(k_preprocess<false>, tile, d_in);
+    } else if (vec) launch(kIngestBgrVec16, k_preprocess<true>, tile, d_in);
+    else launch(kIngestBgrScalar, k_preprocess<false>, tile, d_in);
     HIP_TRY(ctx, hipGetLastError());
     return 0;
 }

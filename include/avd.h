@@ -338,6 +338,9 @@ int avd_kernel_ms(avd_ctx* ctx, int kernel_id, float* ms);
 /* Test hook: copy an internal device buffer of the last call to host.
  * name: "area" uint8[n][1024]; "pyr<L>" float[n][hL][wL]; "poly<L>" float[n][hL][wL][5];
  * "flow<L>" float[n-1][2][hL][wL] (planar, after the last iteration at level L).
+ * "ingest_plan" int32[8], host state rather than a device buffer: what the last ingest launch of the context ran --
+ * h, w, rows_per_band, nbands, LDS tile pitch, NI of k_preprocess_vec (0: another kernel), dynamic LDS bytes requested,
+ * kernel (0 bgr_scalar, 1 bgr_vec16, 2 bgr_staged, 3 nv12_scalar, 4 nv12_tables); an error before any ingest launch.
  * Returns the number of bytes copied (>=0) or a negative status. */
 int64_t avd_debug_fetch(avd_ctx* ctx, const char* name, void* out, size_t out_bytes);
 
