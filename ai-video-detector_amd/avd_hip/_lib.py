@@ -418,6 +418,38 @@ class Context:
                                          int(bool(relu)), None if rb is None else rb.ctypes.data, y.ctypes.data))
         return bf16_bits_to_f32(y)
 
+    @staticmethod
+    def cnn_tap_shape(point: int, n: int):
+        """-> (shape, dtype) of debug buffer "cnn_tap" after a forward of n frames under option cnn_tap = point: 1 the zero-bordered
+        input image, 2 + i the output of convolution i (avd_cnn_set_weights order), 55 the max pool's output, 56 the pooled features."""
+        if point == 1:
+            return (n, 232, 232, 4), np.uint16
+        if point == 55:
+            return (n, 56, 56, 64), np.uint16
+        if point == 56:
+            return (n, 2048), np.float32
+        outs = [(112, 64)]                                   # (side, channels) of every convolution's output, the stem first
+        side = 56
+        for st, depth in enumerate((3, 4, 6, 3)):
+            mid = 64 << st
+            for b in range(depth):
+                so = side // 2 if (b == 0 and st > 0) else side
+                outs += [(side, mid), (so, mid), (so, 4 * mid)] + ([(so, 4 * mid)] if b == 0 else [])
+                side = so
+        if not 2 <= point < 2 + len(outs):
+            raise ValueError(f"cnn_tap point {point}")
+        s, c = outs[point - 2]
+        return (n, s, s, c), np.uint16
+
+    def cnn_tap(self, n: int) -> np.ndarray:
+        """What the last cnn_forward (of n frames) copied aside under option cnn_tap: bf16 bits (uint16) in NHWC, or float32 [n,2048]."""
+        shape, dtype = self.cnn_tap_shape(self.get_option("cnn_tap"), n)
+        return self.debug_fetch("cnn_tap", shape, dtype)
+
+    def cnn_plan(self) -> np.ndarray:
+        """int32[53]: the kernel shape each convolution of the last cnn_forward ran as (codes: avd.h, avd_debug_fetch "cnn_plan")."""
+        return self.debug_fetch("cnn_plan", (53,), np.int32)
+
     # -- audio analyzer (reference app/analyzers/audio.py:40-61 for all windows at once) -----------------------
     def audio_features(self, wav, win: int) -> np.ndarray:
         """wav: mono float32 samples (numpy or torch-ROCm tensor) -> structured array (AUDIO_WINDOW_DTYPE) per window."""

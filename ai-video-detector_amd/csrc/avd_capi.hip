@@ -446,6 +446,7 @@ static bool opt_wide160(int& v) { v = v == 0 ? 0 : (v == 1 ? 1 : 2); return true
 static bool opt_gemm_waves(int& v) { v = v == 16 ? 16 : 8; return true; }
 static bool opt_cnn_fuse(int& v) { v = v < 0 ? 0 : (v > 2 ? 2 : v); return true; }
 static bool opt_cnn_chunk(int& v) { return v >= 1 && v <= 1024; }
+static bool opt_cnn_tap(int& v) { return v >= 0 && v <= kCnnTapPooled; }
 static int env_any_base(const char* e) { return (int)std::strtol(e, nullptr, 0); }
 static int env_fb_mode(const char* e) { return (std::strcmp(e, "exact") == 0 || std::strcmp(e, "0") == 0) ? 0 : 1; }
 static const Option kOptions[] = {
@@ -462,6 +463,7 @@ static const Option kOptions[] = {
     {"cnn_tiles", &avd_ctx::cnn_tiles, true, opt_any},
     {"cnn_fuse", &avd_ctx::cnn_fuse, true, opt_cnn_fuse},
     {"cnn_chunk", &avd_ctx::cnn_chunk, true, opt_cnn_chunk, nullptr, nullptr, "cnn_chunk: 1 ... 1024 frames per forward pass"},
+    {"cnn_tap", &avd_ctx::cnn_tap, true, opt_cnn_tap, nullptr, nullptr, "cnn_tap: 0 (off), 1 input image, 2 ... 54 convolution 0 ... 52, 55 max pool, 56 pooled features"},
     {"rerun_pairs", &avd_ctx::last_rerun, false, opt_any},   // pairs of the last drained call that the fast level kernel flagged and the exact kernels re-ran
 };
 static const Option* find_option(avd_ctx* ctx, const char* name, bool to_write)
@@ -898,6 +900,16 @@ static int64_t impl_debug_fetch(avd_ctx* ctx, const char* name, void* out, size_
         std::memcpy(out, &ctx->ingest_plan, bytes);
         return (int64_t)bytes;
     }
+    if (std::strcmp(name, "cnn_plan") == 0) {          // host state: the kernel shape (CnnShape) of each convolution of the last CNN forward
+        if (!ctx->cnn_plan_valid) { ctx->err = "cnn_plan not recorded yet: no CNN forward has run on this context"; return AVD_ERR_ARG; }
+        bytes = std::min(sizeof(ctx->cnn_plan), out_bytes);
+        std::memcpy(out, ctx->cnn_plan, bytes);
+        return (int64_t)bytes;
+    }
+    if (std::strcmp(name, "cnn_tap") == 0) {           // what option "cnn_tap" made the last CNN forward copy aside
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        return cnn_tap_fetch(ctx, out, out_bytes);
+    }
     if (std::strcmp(name, "area") == 0) { src = ws.d_area; bytes = (size_t)n * 1024; }
     else if (std::strcmp(name, "small") == 0) { src = ws.d_small; bytes = (size_t)n * AVD_NPIX; }
     // the Farneback scratch holds ONE chunk (kFbChunk pairs): for longer clips these are the last chunk's buffers
@@ -998,6 +1010,7 @@ static int impl_cnn_forward(avd_ctx* ctx, const uint8_t* bgr, int mem, int n, in
     // frames per forward pass: bounds the activation scratch (4 x 1.6 MB per frame); avd_set_option "cnn_chunk", 1 ... 1024
     // (32-bit byte offsets inside an activation); the late stages fill the chip better with more frames per pass
     const int kChunk = ctx->cnn_chunk;
+    if (ctx->cnn_tap && (n > kChunk || reps > 0)) { ctx->err = "avd_cnn_forward: with option cnn_tap set, one pass (n <= cnn_chunk) and no timing repetitions"; return AVD_ERR_ARG; }
     if (int e = cnn_reserve(ctx, std::min(n, kChunk))) return e;
     const uint8_t* d_bgr = nullptr;
     if (int e = stage_input(ctx, bgr, mem, plane_span(frame_stride, n, row_stride, h, (size_t)w * 3), &d_bgr)) return e;

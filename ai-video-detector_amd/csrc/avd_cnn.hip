@@ -21,7 +21,9 @@
 //    per lane straight into the blocked layout of the NEXT layer's operand.
 // Tile: 256 pixels x (64 | 128 | 256) output channels per 512-thread workgroup, K in half stages of 32, ring of four half
 // stages with counted vmcnt + raw s_barrier (the scheme of avd_vit.hip; K is a run-time value here).
+#include <algorithm>
 #include <cstdlib>
+#include <string>
 #include <type_traits>
 #include <vector>
 #include "avd_internal.h"
@@ -833,7 +835,7 @@ int launch_conv(avd_ctx* ctx, const uint16_t* x, const uint16_t* w, const float*
 {
     const ConvGeom g = conv_geom(n, hin, win, cin, cout, ksize, stride, stem);
     if (!stem && (cin % 32 || cout % 64 || (ksize != 1 && ksize != 3))) { ctx->err = "conv: cin % 32, cout % 64, ksize 1 or 3"; return AVD_ERR_ARG; }
-    if (stem) return launch_conv_shape<256, 8, 2, 1, 1>(ctx, g, x, w, bias, res, y, relu);
+    if (stem) { ctx->cnn_shape = kCnnStem; return launch_conv_shape<256, 8, 2, 1, 1>(ctx, g, x, w, bias, res, y, relu); }
     // 256-pixel tiles for the long-K layers that fill the chip.  128 x 128 tiles (74 registers, 16 KiB per ring slot: several
     // workgroups per CU) where 256-pixel tiles would leave most of the chip idle (the 14 x 14 and 7 x 7 stages), and for the
     // short-K 1x1 layers, which move bytes rather than multiply: there the time goes to load / store latency, and
@@ -848,9 +850,10 @@ int launch_conv(avd_ctx* ctx, const uint16_t* x, const uint16_t* w, const float*
     const bool want_small = wgs_big * 100 < ctx->num_cus * fill_pct || g.nh <= short_k;
     auto tiled = [&](auto ks) -> int {
         constexpr int KS = decltype(ks)::value;
-        if (small_ok && force != 1 && (want_small || force == 2)) return launch_conv_shape<128, 4, 2, 0, KS>(ctx, g, x, w, bias, res, y, relu);
-        if (bn_big == 256) return launch_conv_shape<256, 2, 8, 0, KS>(ctx, g, x, w, bias, res, y, relu);
-        if (bn_big == 128) return launch_conv_shape<256, 4, 4, 0, KS>(ctx, g, x, w, bias, res, y, relu);
+        if (small_ok && force != 1 && (want_small || force == 2)) { ctx->cnn_shape = kCnn128x128; return launch_conv_shape<128, 4, 2, 0, KS>(ctx, g, x, w, bias, res, y, relu); }
+        if (bn_big == 256) { ctx->cnn_shape = kCnn256x256; return launch_conv_shape<256, 2, 8, 0, KS>(ctx, g, x, w, bias, res, y, relu); }
+        if (bn_big == 128) { ctx->cnn_shape = kCnn256x128; return launch_conv_shape<256, 4, 4, 0, KS>(ctx, g, x, w, bias, res, y, relu); }
+        ctx->cnn_shape = kCnn256x64;
         return launch_conv_shape<256, 8, 2, 0, KS>(ctx, g, x, w, bias, res, y, relu);
     };
     return ksize == 3 ? tiled(std::integral_constant<int, 3>{}) : tiled(std::integral_constant<int, 1>{});
@@ -871,6 +874,7 @@ int launch_conv3_expand(avd_ctx* ctx, const uint16_t* x, const uint16_t* w2, con
         auto slab = [&](auto shape, auto kern) -> int {
             using S = decltype(shape);
             if (win + 1 > S::HALO) { ctx->err = "conv3_expand: the slab's halo is sized for 56 x 56 (mid 64) and 28 x 28 (mid 128)"; return AVD_ERR_ARG; }
+            ctx->cnn_shape = kCnnSlab3Expand;
             return launch_tiles(ctx, kern, tiles_of(g.m_out, S::BM), S::LDS, x, w2, b2, w3, b3, res, y, g, in_blocks);
         };
         return mid == 64 ? slab(SlabShape<64>{}, k_slab3_expand<64>) : slab(SlabShape<128>{}, k_slab3_expand<128>);
@@ -879,6 +883,7 @@ int launch_conv3_expand(avd_ctx* ctx, const uint16_t* x, const uint16_t* w2, con
         using S = decltype(shape);
         // the kernel's LDS plan assumes which ring slot the 3x3's last step reads
         if ((g.nh & 3) != S::PHASE) { ctx->err = "conv3_expand: ring phase"; return AVD_ERR_ARG; }
+        ctx->cnn_shape = kCnnConv3Expand;
         return launch_tiles(ctx, kern, tiles_of(g.m_out, S::BM), S::LDS, x, w2, b2, w3, b3, res, y, g);
     };
     return mid == 64 ? gather(FusedShape<256, 8, 2>{}, k_conv3_expand<256, 8, 2>) : gather(FusedShape<128, 4, 2>{}, k_conv3_expand<128, 4, 2>);
@@ -932,7 +937,9 @@ int cnn_reserve(avd_ctx* ctx, int n)
     Workspace& ws = ctx->ws;
     if (n <= ws.cnn_frames) return AVD_OK;
     ws.cnn_frames = 0;                                                   // not valid again until every buffer below exists
-    const size_t act = act_elems((size_t)n * 112 * 112, 64);             // the largest activation (= n * 56 * 56 x 256)
+    // the largest activation: the stem's, or a 56 x 56 x 256 one, whose rows pad further (n * 3136 is a multiple of 256 only when n % 4 == 0) --
+    // every tile stores all its rows, so the padding rows must exist
+    const size_t act = std::max(act_elems((size_t)n * 112 * 112, 64), act_elems((size_t)n * 56 * 56, 256));
     for (int i = 0; i < 4; i++) {
         if (int e = ws.d_cnn_act[i].reserve(ctx, act)) return e;
         HIP_TRY(ctx, hipMemsetAsync(ws.d_cnn_act[i], 0, kZeroPage * sizeof(uint16_t), ctx->stream));
@@ -945,22 +952,51 @@ int cnn_reserve(avd_ctx* ctx, int n)
     return AVD_OK;
 }
 
-// frames (device BGR) -> logits (device f32 [n][1000]); everything on ctx->stream
+// frames (device BGR) -> logits (device f32 [n][1000]); everything on ctx->stream.  Option "cnn_tap" (tests): the one intermediate it names is
+// copied into ws.d_cnn_tap right after the launch that produces it; with the option at 0 nothing is enqueued for it.
 int launch_cnn_forward(avd_ctx* ctx, const uint8_t* d_bgr, int n, int h, int w, int64_t row_stride, int64_t frame_stride)
 {
     const Net& nt = net();
     Workspace& ws = ctx->ws;
     const Weights& wt = ctx->weights;
-    const int64_t px = (int64_t)n * kSide * kSide;
-    hipLaunchKernelGGL(k_cnn_input, dim3((unsigned)((px + 255) / 256)), dim3(256), 0, ctx->stream, d_bgr, n, h, w, row_stride, frame_stride, ws.d_cnn_img);
-    size_t li = 0;
+    if (nt.convs.size() != (size_t)kCnnConvs) { ctx->err = "cnn: kCnnConvs"; return AVD_ERR_ARG; }
+    int plan[kCnnConvs] = {};                                // kCnnFolded unless a launch of its own is recorded below
+    ws.cnn_tap_asked = ctx->cnn_tap;
+    ws.cnn_tap_point = 0;                                    // whatever an earlier forward left is no longer "the last forward's"
+    // a tile stores ALL its rows, a tail tile's padding rows too: [rows][c] padded to whole tiles must lie inside a scratch buffer
+    auto fits = [&](size_t rows, int c) -> int {
+        if (act_elems(rows, c) <= ws.d_cnn_act[0].cap) return 0;
+        ctx->err = "cnn: an activation of " + std::to_string(rows) + " x " + std::to_string(c) + ", padded to whole tiles, is larger than the scratch buffers";
+        return AVD_ERR_NOMEM;
+    };
+    // c != 0: the blocked activation [rows][c] at src (its zero page and padding rows included); c == 0: `bytes` plain bytes
+    auto tap = [&](int point, const void* src, size_t rows, int c, size_t bytes = 0) -> int {
+        if (ctx->cnn_tap != point) return 0;
+        if (c) bytes = act_elems(rows, c) * sizeof(uint16_t);
+        if (int e = ws.d_cnn_tap.reserve(ctx, (bytes + 1) / 2)) return e;
+        HIP_TRY(ctx, hipMemcpyAsync(ws.d_cnn_tap, src, bytes, hipMemcpyDeviceToDevice, ctx->stream));
+        ws.cnn_tap_point = point; ws.cnn_tap_rows = rows; ws.cnn_tap_c = c; ws.cnn_tap_bytes = bytes;
+        return 0;
+    };
     auto wptr = [&](size_t i) { return wt.d_cnn_w + wt.cnn_w_off[i]; };
     auto bptr = [&](size_t i) { return wt.d_cnn_b + nt.convs[i].b_off; };
+    // convolution i of the network (hin x hin input, even): launched, recorded in the plan, tapped
+    auto conv = [&](size_t i, const uint16_t* x, const uint16_t* res, uint16_t* y, int hin, int ci, int co, int ksize, int s, int relu, bool stem = false) -> int {
+        const size_t rows = (size_t)n * (hin / s) * (hin / s);
+        if (int e = fits(rows, co)) return e;
+        if (int e = launch_conv(ctx, x, wptr(i), bptr(i), res, y, n, hin, hin, ci, co, ksize, s, relu, stem)) return e;
+        plan[i] = ctx->cnn_shape;
+        return tap(kCnnTapConv0 + (int)i, y, rows, co);
+    };
+    const int64_t px = (int64_t)n * kSide * kSide;
+    hipLaunchKernelGGL(k_cnn_input, dim3((unsigned)((px + 255) / 256)), dim3(256), 0, ctx->stream, d_bgr, n, h, w, row_stride, frame_stride, ws.d_cnn_img);
+    if (int e = tap(kCnnTapImage, ws.d_cnn_img, 0, 0, (size_t)n * kImgSide * kImgSide * 4 * sizeof(uint16_t))) return e;
     // the stem gathers straight from the bordered image (one half stage per kernel row)
-    if (int e = launch_conv(ctx, ws.d_cnn_img, wptr(0), bptr(0), nullptr, ws.d_cnn_act[0], n, kSide, kSide, 3, 64, 7, 2, 1, true)) return e;
-    li = 1;
+    if (int e = conv(0, ws.d_cnn_img, nullptr, ws.d_cnn_act[0], kSide, 3, 64, 7, 2, 1, true)) return e;
+    size_t li = 1;
     const int64_t pooled = (int64_t)n * 56 * 56 * 8;
     hipLaunchKernelGGL(k_maxpool3, dim3((unsigned)((pooled + 255) / 256)), dim3(256), 0, ctx->stream, ws.d_cnn_act[0], n, 112, 112, 64, ws.d_cnn_act[1]);
+    if (int e = tap(kCnnTapMaxPool, ws.d_cnn_act[1], (size_t)n * 56 * 56, 64)) return e;
     int cur = 1, hgt = 56;                                   // index of the block input among the four rotating buffers
     const int depth[4] = {3, 4, 6, 3};
     int cin = 64;
@@ -970,19 +1006,23 @@ int launch_cnn_forward(avd_ctx* ctx, const uint8_t* d_bgr, int n, int h, int w, 
             const int s = (b == 0 && st > 0) ? 2 : 1;
             const int t1 = (cur + 1) & 3, t2 = (cur + 2) & 3, sc = (cur + 3) & 3;
             uint16_t *x = ws.d_cnn_act[cur], *a1 = ws.d_cnn_act[t1], *a2 = ws.d_cnn_act[t2], *a3 = ws.d_cnn_act[sc];
-            if (int e = launch_conv(ctx, x, wptr(li), bptr(li), nullptr, a1, n, hgt, hgt, cin, mid, 1, 1, 1)) return e;
+            if (int e = conv(li, x, nullptr, a1, hgt, cin, mid, 1, 1, 1)) return e;
             const int ho = hgt / s;
             const uint16_t* res = x;
             if (b == 0) {                                    // projection shortcut into a3
-                if (int e = launch_conv(ctx, x, wptr(li + 3), bptr(li + 3), nullptr, a3, n, hgt, hgt, cin, out, 1, s, 0)) return e;
+                if (int e = conv(li + 3, x, nullptr, a3, hgt, cin, out, 1, s, 0)) return e;
                 res = a3;
             }
             if (ctx->cnn_fuse && can_fuse_expand(mid)) {     // conv2 + conv3 in one launch: a1 -> a2 (other workgroups still read a1's halo)
+                const size_t rows = (size_t)n * ho * ho;
+                if (int e = fits(rows, out)) return e;
                 if (int e = launch_conv3_expand(ctx, a1, wptr(li + 1), bptr(li + 1), wptr(li + 2), bptr(li + 2), res, a2, n, hgt, hgt, mid, s)) return e;
+                plan[li + 1] = ctx->cnn_shape;               // recorded at the 3x3, whose output never leaves the CU: nothing to tap there
+                if (int e = tap(kCnnTapConv0 + (int)li + 2, a2, rows, out)) return e;
                 cur = t2;
             } else {                                         // conv3 writes over a1
-                if (int e = launch_conv(ctx, a1, wptr(li + 1), bptr(li + 1), nullptr, a2, n, hgt, hgt, mid, mid, 3, s, 1)) return e;
-                if (int e = launch_conv(ctx, a2, wptr(li + 2), bptr(li + 2), res, a1, n, ho, ho, mid, out, 1, 1, 1)) return e;
+                if (int e = conv(li + 1, a1, nullptr, a2, hgt, mid, mid, 3, s, 1)) return e;
+                if (int e = conv(li + 2, a2, res, a1, ho, mid, out, 1, 1, 1)) return e;
                 cur = t1;
             }
             li += b == 0 ? 4 : 3;
@@ -990,10 +1030,38 @@ int launch_cnn_forward(avd_ctx* ctx, const uint8_t* d_bgr, int n, int h, int w, 
         }
     }
     hipLaunchKernelGGL(k_avgpool, dim3((unsigned)((n * 256 + 255) / 256)), dim3(256), 0, ctx->stream, ws.d_cnn_act[cur], n, 49, 2048, ws.d_cnn_pool);
+    if (int e = tap(kCnnTapPooled, ws.d_cnn_pool, 0, 0, (size_t)n * 2048 * sizeof(float))) return e;
     hipLaunchKernelGGL(k_linear, dim3((unsigned)(((n + 7) / 8 * 1000 + 3) / 4)), dim3(256), 0, ctx->stream, ws.d_cnn_pool, wt.d_cnn_w + wt.cnn_fc_off,
                        wt.d_cnn_b + nt.fc_b, n, 1000, ws.d_cnn_logits);
     HIP_TRY(ctx, hipGetLastError());
+    for (int i = 0; i < kCnnConvs; i++) ctx->cnn_plan[i] = plan[i];
+    ctx->cnn_plan_valid = 1;
     return AVD_OK;
+}
+
+// avd_debug_fetch "cnn_tap": what the last forward copied aside, an activation de-blocked to plain NHWC (out_bytes must be the tap's size)
+int64_t cnn_tap_fetch(avd_ctx* ctx, void* out, size_t out_bytes)
+{
+    Workspace& ws = ctx->ws;
+    if (!ws.cnn_tap_point || !ws.d_cnn_tap) {
+        ctx->err = ws.cnn_tap_asked ? "cnn_tap: no launch of the last forward had that output (a fused block's 3x3 has none of its own while cnn_fuse != 0)"
+                                    : "cnn_tap: the last forward copied nothing (option cnn_tap was 0, or no forward has run since the workspace was released)";
+        return AVD_ERR_ARG;
+    }
+    const int c = ws.cnn_tap_c;
+    const size_t want = c ? ws.cnn_tap_rows * c * sizeof(uint16_t) : ws.cnn_tap_bytes;
+    if (out_bytes != want) { ctx->err = "cnn_tap: tap " + std::to_string(ws.cnn_tap_point) + " holds " + std::to_string(want) + " bytes"; return AVD_ERR_ARG; }
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (!c) {
+        HIP_TRY(ctx, hipMemcpy(out, ws.d_cnn_tap, want, hipMemcpyDeviceToHost));
+        return (int64_t)want;
+    }
+    std::vector<uint16_t> blocked(ws.cnn_tap_bytes / sizeof(uint16_t));
+    HIP_TRY(ctx, hipMemcpy(blocked.data(), ws.d_cnn_tap, ws.cnn_tap_bytes, hipMemcpyDeviceToHost));
+    uint16_t* y = static_cast<uint16_t*>(out);
+    for (size_t m = 0; m < ws.cnn_tap_rows; m++)
+        for (int k = 0; k < c; k++) y[m * c + k] = blocked[kZeroPage + blocked_index((int)m, k, c)];
+    return (int64_t)want;
 }
 
 // ONE convolution on host tensors in NHWC order (test entry: the blocked layout stays an internal matter)

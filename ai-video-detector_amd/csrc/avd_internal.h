@@ -94,6 +94,12 @@ BandPlan band_plan(int w);
 enum IngestKernel { kIngestBgrScalar = 0, kIngestBgrVec16, kIngestBgrStaged, kIngestNv12Scalar, kIngestNv12Tables };
 struct IngestPlan { int h, w, rows_per_band, nbands, pitch, ni, lds_bytes, kernel; };
 static_assert(sizeof(IngestPlan) == 8 * sizeof(int), "avd_debug_fetch hands the struct out as int32[8]");
+// Kernel shape of a CNN convolution launch (avd_cnn.hip), as avd_debug_fetch "cnn_plan" hands it out per convolution: kCnnFolded = no launch
+// of its own (the expanding 1x1 of a fused block; the fused launch is recorded at the block's 3x3)
+enum CnnShape { kCnnFolded = 0, kCnn128x128, kCnn256x64, kCnn256x128, kCnn256x256, kCnnStem, kCnnConv3Expand, kCnnSlab3Expand };
+constexpr int kCnnConvs = 53;      // convolutions of the network, in avd_cnn_set_weights order
+// option "cnn_tap": which intermediate avd_cnn_forward copies aside (0 = none); kCnnTapConv0 + i = the output of convolution i
+constexpr int kCnnTapImage = 1, kCnnTapConv0 = 2, kCnnTapMaxPool = kCnnTapConv0 + kCnnConvs, kCnnTapPooled = kCnnTapMaxPool + 1;
 constexpr int kLapSlots = 8;       // per-band slots of Workspace::d_lap_part, one per wave of the workgroup (4 written)
 
 // ---- owners of device and pinned host memory ------------------------------------------------
@@ -188,6 +194,11 @@ struct Workspace {
     // CNN extension (avd_cnn.hip): activation scratch for cnn_frames frames
     DevBuf<uint16_t> d_cnn_act[4], d_cnn_img;
     DevBuf<float> d_cnn_pool, d_cnn_logits; int cnn_frames = 0;
+    // test hook (option "cnn_tap"): the one intermediate the last forward copied aside; reserved only by a tapped forward
+    DevBuf<uint16_t> d_cnn_tap;
+    int cnn_tap_asked = 0, cnn_tap_point = 0;     // what the last forward was asked for / what it copied (0: nothing, d_cnn_tap is not to be read)
+    size_t cnn_tap_rows = 0, cnn_tap_bytes = 0;   // a blocked activation of cnn_tap_rows pixels x cnn_tap_c channels, or (cnn_tap_c == 0) cnn_tap_bytes plain bytes
+    int cnn_tap_c = 0;
 };
 
 // What a caller uploaded (avd_cnn_set_weights, avd_vit_set_weights) is state, not scratch: it survives avd_release_workspace.
@@ -240,6 +251,11 @@ struct avd_ctx {
     int counted_in_flight = 0;      // this context's enqueued call is counted in avd_calls_in_flight()
     int fb_wide160_used = 0;        // the shape the last call's 160-px launches took (read-only option "fb_wide160_used")
     int gemm_waves = 8;             // patch-embed GEMM: waves per workgroup (8: 8 x 4 MFMA tiles per wave, 16: 4 x 4; measured no faster), the same 256 x 256 tile; AVD_GEMM_WAVES / avd_set_option
+    int cnn_tap = 0;                // CNN extension, tests: the forward copies one intermediate aside for avd_debug_fetch "cnn_tap" (0 = off, 1 = bordered input image,
+                                    // 2 + i = output of convolution i, 55 = max pool, 56 = pooled features); one pass, no timing repetitions
+    int cnn_plan[kCnnConvs] = {};   // the kernel shape (CnnShape) each convolution of the last forward ran as (debug buffer "cnn_plan")
+    int cnn_plan_valid = 0;         // 0 until the first forward
+    int cnn_shape = 0;              // the shape the last convolution launch took
     int cnn_chunk = 128;            // CNN extension: frames per forward pass (activation scratch = 4 x 1.6 MB per frame)
     int cnn_fuse = 2;               // CNN extension: a block's 3x3 and expanding 1x1 in one launch (stages 1, 2): 2 = with the 3x3's input slab in LDS in the stride-1 blocks (k_slab3_expand), 1 = gathering kernels only, 0 = layer by layer
     int fb_fused = 0xF;             // bit k: pyramid level k runs the fused kernel (avd_fbfused.hip) instead of the two-kernel path (avd_fbtwo.hip)
@@ -317,6 +333,7 @@ void cnn_param_counts(size_t* n_weights, size_t* n_biases);
 int cnn_set_weights(avd_ctx* ctx, const uint16_t* weights, const float* biases);
 int cnn_reserve(avd_ctx* ctx, int n);
 int launch_cnn_forward(avd_ctx* ctx, const uint8_t* d_bgr, int n, int h, int w, int64_t row_stride, int64_t frame_stride);
+int64_t cnn_tap_fetch(avd_ctx* ctx, void* out, size_t out_bytes);   // avd_debug_fetch "cnn_tap": activations de-blocked to NHWC
 int cnn_conv_host(avd_ctx* ctx, const uint16_t* x, int n, int hin, int win, int cin, const uint16_t* w, const float* bias, int cout, int ksize,
                   int stride, int relu, const uint16_t* residual, uint16_t* y);
 // avd_comm.cpp: RCCL all-gather of the per-frame records (dlopen, no link-time dependency)

@@ -313,6 +313,10 @@ int avd_set_profiling(avd_ctx* ctx, int enable);
  * (the mid activation stays in LDS; bit-identical to the two layers); 2 = in their stride-1 blocks the 3x3 also reads its nine taps from one
  * copy of its input in LDS instead of gathering them tap by tap; 1 = gathering form everywhere; 0 = layer by layer.  "cnn_chunk" (default 128, 1 ... 1024):
  * frames per forward pass of avd_cnn_forward (activation scratch: 4 x 1.6 MB per frame).
+ * "cnn_tap" (tests; default 0 = off, 0 ... 56, anything else is refused): avd_cnn_forward copies ONE intermediate aside, device to device on the
+ * context's stream right after the launch that produces it, for avd_debug_fetch "cnn_tap": 1 = the zero-bordered input image, 2 + i = the output of
+ * convolution i (avd_cnn_set_weights order, 0 = stem ... 52), 55 = the max pool's output, 56 = the pooled features.  While it is set, a call with more
+ * frames than one pass ("cnn_chunk") or with timing_reps > 0 is refused (AVD_ERR_ARG); at 0 the forward enqueues nothing for it.
  * avd_get_option returns the value an option has now (environment defaults included) and the read-only "rerun_pairs". */
 int avd_set_option(avd_ctx* ctx, const char* name, int value);
 int avd_get_option(avd_ctx* ctx, const char* name, int* value);
@@ -341,6 +345,12 @@ int avd_kernel_ms(avd_ctx* ctx, int kernel_id, float* ms);
  * "ingest_plan" int32[8], host state rather than a device buffer: what the last ingest launch of the context ran --
  * h, w, rows_per_band, nbands, LDS tile pitch, NI of k_preprocess_vec (0: another kernel), dynamic LDS bytes requested,
  * kernel (0 bgr_scalar, 1 bgr_vec16, 2 bgr_staged, 3 nv12_scalar, 4 nv12_tables); an error before any ingest launch.
+ * "cnn_tap": what option "cnn_tap" made the last avd_cnn_forward copy aside -- 1: uint16[n][232][232][4] bf16 bits; 2 + i and 55: the activation as
+ * plain NHWC bf16 bits, uint16[n][H][W][C]; 56: float[n][2048].  out_bytes must be exactly the tap's size.  An error, never stale bytes, when the last
+ * forward was not tapped, when none of its launches has that output (the 3x3 of a fused block while "cnn_fuse" != 0), or when the size differs.
+ * "cnn_plan" int32[53], host state: the kernel shape each convolution of the last avd_cnn_forward ran as -- 0 no launch of its own (the expanding 1x1
+ * of a fused block), 1 128 x 128 tiles, 2 256 x 64, 3 256 x 128, 4 256 x 256, 5 the stem, 6 k_conv3_expand, 7 k_slab3_expand (the fused launches are
+ * recorded at the block's 3x3); an error before any forward.
  * Returns the number of bytes copied (>=0) or a negative status. */
 int64_t avd_debug_fetch(avd_ctx* ctx, const char* name, void* out, size_t out_bytes);
 

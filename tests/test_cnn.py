@@ -5,7 +5,17 @@ where the HIP path stores it, accumulation in float32.  Tolerances (stated here;
 own outputs): one layer -- the two float32 accumulation orders can land on opposite sides of a bf16 rounding boundary, so
 |error| <= 2^-7 |ref| + 2e-3 (one bf16 ulp); the whole network (53 layers of such roundings) -- logits within 0.8 % of the
 largest |logit| (budget derived in test_forward_against_float32, with a negative control: a missing residual in the last
-block is 5x outside it) and a correlation above 0.9999."""
+block is 5x outside it) and a correlation above 0.9999.
+
+The forward is also checked STAGE BY STAGE (option "cnn_tap", debug buffers "cnn_tap" / "cnn_plan"): each stage alone against a CPU reference
+computed from the GPU's own taps of its producers, so a stage's tolerance is that of one layer.  Input image and max pool: bit for bit.  Each of
+the 53 convolutions: the per-layer tolerance above on every element, more than 98 % of the elements bit-identical.  Pooled features:
+|err| <= 64 * 2^-24 * ref (a sequential float32 sum of 49 non-negative terms and one multiply).  Logits: |err| <= 64 * 2^-24 * (|pooled| @ |W|.T + |b|)
+(32 FMAs per lane, six shuffle adds, the bias).  Recorded on an MI355X (two 360 x 640 frames, seeded_parameters(0); "[cnn-stages]" lines of
+-m gpu -s): over the 53 convolutions the worst |err| / tolerance is 0.803 (conv 27, 512 -> 1024 1x1 / 2; the stem 0.678) -- a single bf16 ulp
+where the two accumulation orders round apart -- and the smallest bit-identical share 0.99986 (conv 47, 2048 -> 512 1x1); pooled features 0.024
+of their bound, logits 0.005 of theirs.  CPU negative controls restate five kernel bugs that the end-to-end comparison cannot see (a stem that pads by
+replication or drops kernel column 6, a wrapped right-border tap, an unstored tail tile, a dropped bias channel): the stage criterion rejects each."""
 import numpy as np
 import pytest
 
@@ -54,16 +64,25 @@ def bf16(t):
     return t.to(torch.bfloat16).to(torch.float32)          # round to nearest even, as the kernels do
 
 
-def conv_reference(x_nhwc, w, bias, stride, relu, residual=None):
-    """float32 NHWC in / out; x, w, residual are rounded to bf16 first; output rounded to bf16."""
+def conv_preactivation(x_nhwc, w, bias, stride, padding=None):
+    """float32 NHWC x and [cout][k][k][cin] w, both rounded to bf16 first -> the float32 sums + bias, NCHW (torch)."""
     x = bf16(torch.from_numpy(np.ascontiguousarray(x_nhwc))).permute(0, 3, 1, 2)
     wt = bf16(torch.from_numpy(np.ascontiguousarray(w))).permute(0, 3, 1, 2)
-    y = F.conv2d(x, wt, torch.from_numpy(bias), stride=stride, padding=w.shape[1] // 2)
+    return F.conv2d(x, wt, torch.from_numpy(bias), stride=stride, padding=w.shape[1] // 2 if padding is None else padding)
+
+
+def conv_finish(y, relu, residual=None):
+    """+ residual (NHWC, rounded to bf16 first), ReLU, rounded to bf16 -> float32 NHWC (numpy)."""
     if residual is not None:
         y = y + bf16(torch.from_numpy(np.ascontiguousarray(residual))).permute(0, 3, 1, 2)
     if relu:
         y = torch.relu(y)
     return bf16(y).permute(0, 2, 3, 1).contiguous().numpy()
+
+
+def conv_reference(x_nhwc, w, bias, stride, relu, residual=None):
+    """float32 NHWC in / out; x, w, residual are rounded to bf16 first; output rounded to bf16."""
+    return conv_finish(conv_preactivation(x_nhwc, w, bias, stride), relu, residual)
 
 
 def input_reference(frames):
@@ -137,7 +156,28 @@ CONV_CASES = [
     (3, 7, 7, 512, 2048, 1, 1, True, True),          # last stage: 147 rows, eight column tiles, residual + ReLU
     (1, 28, 28, 160, 64, 1, 1, True, False),         # the stem's im2col shape: K = 160 (five half stages)
     (1, 9, 11, 96, 192, 3, 1, True, False),          # odd geometry, channel counts that are not powers of two
+    (1, 8, 8, 32, 64, 1, 1, True, False),            # one half stage: a ring of one slot
+    (1, 8, 8, 96, 128, 1, 1, False, False),          # three half stages
+    (1, 1, 1, 32, 64, 3, 1, True, False),            # a single pixel: eight of nine taps on the zero page
+    (5, 3, 3, 32, 64, 3, 1, True, True),             # tiny frames: neighbouring frames adjoin in the pixel index and a tap must not cross
+    (1, 33, 31, 256, 512, 3, 2, True, False),        # odd geometry under stride 2
+    (2, 7, 7, 2048, 512, 1, 1, True, False),         # 64 half stages
+    (1, 7, 7, 512, 512, 3, 1, True, True),           # K = 4608
+    (2, 14, 14, 1024, 2048, 1, 2, False, False),     # the last projection shortcut
 ]
+
+
+def layer_figures(got, want):
+    """The per-layer criterion's two figures: the worst |error| / tolerance (tolerance 2^-7 |ref| + 2e-3; <= 1 passes) and the
+    share of bit-identical elements (> 0.98 passes)."""
+    err = np.abs(got - want)
+    tol = np.abs(want) * 2.0 ** -7 + 2e-3
+    return float((err / tol).max()), float(np.mean(got == want))
+
+
+def layer_ok(got, want):
+    worst, same = layer_figures(got, want)
+    return got.shape == want.shape and worst <= 1.0 and same > 0.98
 
 
 @pytest.mark.gpu
@@ -151,13 +191,18 @@ def test_one_convolution_against_float32(ctx, case):
     pad = k // 2
     ho, wo = (h + 2 * pad - k) // stride + 1, (w + 2 * pad - k) // stride + 1
     res = rng.standard_normal((n, ho, wo, cout)).astype(np.float32) if with_res else None
-    got = ctx.cnn_conv(x, wt, b, stride=stride, relu=relu, residual=res)
     want = conv_reference(x, wt, b, stride, relu, res)
-    assert got.shape == want.shape
-    err = np.abs(got - want)
-    tol = np.abs(want) * 2.0 ** -7 + 2e-3
-    assert np.all(err <= tol), (float(err.max()), int((err > tol).sum()))
-    assert np.mean(got == want) > 0.98               # all but the rare rounding-boundary cases are bit-identical
+    try:
+        for policy in (0, 1, 2):                     # the heuristic, the 256-pixel bodies, 128 x 128 wherever cout allows
+            ctx.set_option("cnn_tiles", policy)
+            got = ctx.cnn_conv(x, wt, b, stride=stride, relu=relu, residual=res)
+            assert got.shape == want.shape
+            err = np.abs(got - want)
+            tol = np.abs(want) * 2.0 ** -7 + 2e-3
+            assert np.all(err <= tol), (policy, float(err.max()), int((err > tol).sum()))
+            assert np.mean(got == want) > 0.98, policy   # all but the rare rounding-boundary cases are bit-identical
+    finally:
+        ctx.set_option("cnn_tiles", 0)
 
 
 @pytest.mark.gpu
@@ -267,3 +312,407 @@ def test_forward_needs_weights_and_checks_counts():
     with pytest.raises(_lib.AvdError):
         c.cnn_set_weights(np.zeros(10, np.float32), np.zeros(10, np.float32))
     c.close()
+
+
+# ---- the forward stage by stage ---------------------------------------------------------------------------------------
+# Option "cnn_tap" makes a forward copy ONE intermediate aside (debug buffer "cnn_tap"); "cnn_plan" tells which kernel shape ran
+# each convolution.  Every stage is checked alone and teacher-forced: its reference is computed on the CPU from the GPU's own
+# taps of its producers, so the tolerance is that of one layer, never of a chain.
+TAP_IMAGE, TAP_CONV0, TAP_MAXPOOL, TAP_POOLED = 1, 2, 55, 56
+PLAN_FOLDED, PLAN_128X128, PLAN_256X64, PLAN_256X128, PLAN_256X256, PLAN_STEM, PLAN_CONV3_EXPAND, PLAN_SLAB3_EXPAND = range(8)
+
+
+def wiring():
+    """{conv i (1 ... 52): (tap of its input, tap of its residual or None, relu)} and [(conv1 index, stage, stride)] per block."""
+    wires, blocks = {}, []
+    li, xin = 1, TAP_MAXPOOL
+    for st, depth in enumerate(DEPTH):
+        for b in range(depth):
+            blocks.append((li, st, 2 if (b == 0 and st > 0) else 1))
+            wires[li] = (xin, None, True)
+            wires[li + 1] = (TAP_CONV0 + li, None, True)
+            wires[li + 2] = (TAP_CONV0 + li + 1, TAP_CONV0 + li + 3 if b == 0 else xin, True)
+            if b == 0:
+                wires[li + 3] = (xin, None, False)
+            xin = TAP_CONV0 + li + 2
+            li += 4 if b == 0 else 3
+    return wires, blocks
+
+
+def conv_parameters(weights, biases):
+    """[(w float32 [cout][k][k][cin], bias, stride)] per convolution, then (wfc [1000][2048], bfc)."""
+    out, wo, bo = [], 0, 0
+    for cin, cout, k, s in topology():
+        out.append((weights[wo:wo + cout * k * k * cin].reshape(cout, k, k, cin), biases[bo:bo + cout], s))
+        wo += cout * k * k * cin
+        bo += cout
+    return out, (weights[wo:wo + 1000 * 2048].reshape(1000, 2048), biases[bo:bo + 1000])
+
+
+def stage_frames():
+    """Two frames: every stage ends in a partial tile (6272 rows / 256, 1568 / 128, 392, 98)."""
+    return np.concatenate([synth.make_clip(1, 360, 640, seed=5), synth.random_frames(1, 360, 640, seed=6)])
+
+
+def stage_reference(point, tap, convs, mutate=None):
+    """Reference of tap `point` (2 ... 55) from the taps of its producers: tap(p) -> float32 NHWC (p = 1: the 224 x 224 x 3 interior).
+    mutate (negative controls): applied to the float32 sums before the residual, the ReLU and the rounding."""
+    if point == TAP_MAXPOOL:
+        x = torch.from_numpy(tap(TAP_CONV0)).permute(0, 3, 1, 2)
+        return F.max_pool2d(x, 3, 2, 1).permute(0, 2, 3, 1).contiguous().numpy()
+    i = point - TAP_CONV0
+    w, b, stride = convs[i]
+    src, res, relu = (TAP_IMAGE, None, True) if i == 0 else wiring()[0][i]
+    y = conv_preactivation(tap(src), w, b, stride)
+    if mutate is not None:
+        y = mutate(y)
+    return conv_finish(y, relu, None if res is None else tap(res))
+
+
+class Taps:
+    """The GPU's taps of one forward configuration: bf16 bits as fetched; [p] widens to float32 (the image tap: its interior)."""
+
+    def __init__(self):
+        self.bits, self.logits, self.plan = {}, None, None
+
+    def __call__(self, p):
+        a = self.bits[p]
+        if p == TAP_POOLED:
+            return a
+        return _lib.bf16_bits_to_f32(a[:, 3:227, 3:227, :3] if p == TAP_IMAGE else a)
+
+
+def run_tapped(ctx, frames, point):
+    """One forward with the tap at `point` -> (tap, logits, plan); the option is back at 0 afterwards."""
+    ctx.set_option("cnn_tap", point)
+    try:
+        logits, _ = ctx.cnn_forward(frames)
+        return ctx.cnn_tap(frames.shape[0]), logits, ctx.cnn_plan()
+    finally:
+        ctx.set_option("cnn_tap", 0)
+
+
+@pytest.fixture(scope="module")
+def stage_params():
+    weights, biases = seeded_parameters(0)
+    return weights, biases, conv_parameters(weights, biases)
+
+
+@pytest.fixture(scope="module")
+def gpu_taps(ctx, stage_params):
+    """57 short forwards layer by layer (cnn_fuse = 0, default tiling), one per tap point."""
+    weights, biases, _ = stage_params
+    ctx.cnn_set_weights(weights, biases)
+    frames = stage_frames()
+    fuse = ctx.get_option("cnn_fuse")
+    t = Taps()
+    try:
+        ctx.set_option("cnn_fuse", 0)
+        for p in range(1, 57):
+            t.bits[p], logits, plan = run_tapped(ctx, frames, p)
+            if t.logits is None:
+                t.logits, t.plan = logits, plan
+            assert np.array_equal(logits, t.logits) and np.array_equal(plan, t.plan)   # a tap changes nothing downstream
+    finally:
+        ctx.set_option("cnn_fuse", fuse)
+    return t
+
+
+def image_is_right(img_bits, frames):
+    want = input_reference(frames).transpose(0, 2, 3, 1)                             # [n,224,224,3] RGB
+    assert np.array_equal(_lib.bf16_bits_to_f32(img_bits[:, 3:227, 3:227, :3]), want)
+    border = img_bits.copy()
+    border[:, 3:227, 3:227, :3] = 0
+    assert not border.any()                                                          # every border element, the fourth channel
+
+
+@pytest.mark.gpu
+def test_stage_input_image(ctx, gpu_taps, stage_params):
+    frames = stage_frames()
+    assert gpu_taps.bits[TAP_IMAGE].shape == (2, 232, 232, 4)
+    image_is_right(gpu_taps.bits[TAP_IMAGE], frames)
+    # another geometry and more frames in between: no stale pixel, an untouched border
+    ctx.cnn_forward(synth.random_frames(5, 96, 128, seed=21))
+    again, _, _ = run_tapped(ctx, frames, TAP_IMAGE)
+    image_is_right(again, frames)
+
+
+def report(name, got, want):
+    worst, same = layer_figures(got, want)
+    print(f"[cnn-stages] {name}: worst err/tol {worst:.3f}, identical {same:.5f}")
+    assert got.shape == want.shape
+    assert worst <= 1.0, name
+    assert same > 0.98, name
+
+
+@pytest.mark.gpu
+def test_stage_stem(gpu_taps, stage_params):
+    assert gpu_taps.plan[0] == PLAN_STEM
+    report("conv 0 (stem)", gpu_taps(TAP_CONV0), stage_reference(TAP_CONV0, gpu_taps, stage_params[2][0]))
+
+
+@pytest.mark.gpu
+def test_stage_max_pool(gpu_taps, stage_params):
+    """A maximum of bf16 values has no rounding: equal."""
+    assert np.array_equal(gpu_taps(TAP_MAXPOOL), stage_reference(TAP_MAXPOOL, gpu_taps, stage_params[2][0]))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("i", range(1, 53))
+def test_stage_convolution(gpu_taps, stage_params, i):
+    """Convolution i of the forward, from the GPU's taps of its input and its residual: the real geometry, the buffer rotation, its weight
+    and bias offsets."""
+    assert gpu_taps.plan[i] in (PLAN_128X128, PLAN_256X64, PLAN_256X128, PLAN_256X256)
+    cin, cout, k, s = topology()[i]
+    report(f"conv {i} ({cin} -> {cout}, {k}x{k}/{s})", gpu_taps(TAP_CONV0 + i), stage_reference(TAP_CONV0 + i, gpu_taps, stage_params[2][0]))
+
+
+@pytest.mark.gpu
+def test_stage_pooled_features(gpu_taps):
+    """k_avgpool: a sequential float32 sum of 49 non-negative terms, then one multiply by 1.f / 49 -- 50 roundings, and the reciprocal's."""
+    x = gpu_taps(TAP_CONV0 + 52).astype(np.float64)
+    assert x.shape == (2, 7, 7, 2048) and x.min() >= 0
+    want = x.reshape(2, 49, 2048).mean(axis=1)
+    got = gpu_taps(TAP_POOLED)
+    assert got.shape == want.shape and got.dtype == np.float32
+    err = np.abs(got - want)
+    print(f"[cnn-stages] pooled features: worst err/tol {float((err / np.maximum(64 * 2.0 ** -24 * want, 1e-300)).max()):.3f}")
+    assert np.all(err <= 64 * 2.0 ** -24 * want)
+
+
+@pytest.mark.gpu
+def test_stage_logits(gpu_taps, stage_params):
+    """k_linear: 32 FMAs per lane, six shuffle adds and the bias."""
+    wfc, bfc = stage_params[2][1]
+    wq = _lib.bf16_bits_to_f32(_lib.f32_to_bf16_bits(wfc)).astype(np.float64)
+    pooled = gpu_taps(TAP_POOLED).astype(np.float64)
+    want = pooled @ wq.T + bfc
+    bound = 64 * 2.0 ** -24 * (np.abs(pooled) @ np.abs(wq).T + np.abs(bfc))
+    err = np.abs(gpu_taps.logits - want)
+    print(f"[cnn-stages] logits: worst err/tol {float((err / bound).max()):.3f}")
+    assert gpu_taps.logits.shape == (2, 1000) and np.all(err <= bound)
+
+
+# ---- negative controls (CPU only): the stage criterion must reject each restated kernel bug ------------------------------
+@pytest.fixture(scope="module")
+def cpu_taps(stage_params):
+    """The float32 reference network on the stage frames, every tap kept (the controls need a stage's true inputs)."""
+    convs = stage_params[2][0]
+    taps = {TAP_IMAGE: np.ascontiguousarray(input_reference(stage_frames()).transpose(0, 2, 3, 1))}
+    get = taps.__getitem__
+    taps[TAP_CONV0] = stage_reference(TAP_CONV0, get, convs)
+    taps[TAP_MAXPOOL] = stage_reference(TAP_MAXPOOL, get, convs)
+    for li, st, s in wiring()[1]:
+        first = wiring()[0][li + 2][1] == TAP_CONV0 + li + 3                        # a stage's first block: the shortcut before conv3
+        for i in ([li, li + 3, li + 1, li + 2] if first else [li, li + 1, li + 2]):
+            taps[TAP_CONV0 + i] = stage_reference(TAP_CONV0 + i, get, convs)
+    return taps
+
+
+def wrapped_right_border(x_nhwc, w):
+    """Mutation of a 3x3 / 1: at the right border the dx = 2 tap reads the NEXT ROW'S FIRST pixel (the next linear pixel index) instead of the
+    zero page -- what a gather that checks only the row would do."""
+    x0 = bf16(torch.from_numpy(np.ascontiguousarray(x_nhwc[:, :, 0, :])))             # [n][H][c]: the first pixel of every row
+    wq = bf16(torch.from_numpy(np.ascontiguousarray(w)))
+    H = x_nhwc.shape[1]
+
+    def mutate(y):
+        y = y.clone()
+        for dy in range(3):                                                           # tap row oy - 1 + dy inside the image, and so the row after it
+            oy = [o for o in range(H) if 0 <= o - 1 + dy and o + dy < H]
+            y[:, :, oy, -1] += torch.einsum("nhc,oc->noh", x0[:, [o + dy for o in oy], :], wq[:, dy, 2, :])
+        return y
+    return mutate
+
+
+def block_conv(block, which):
+    """Index of convolution `which` (0 conv1, 1 the 3x3, 2 the expanding 1x1) of block `block` (0 ... 15)."""
+    return wiring()[1][block][0] + which
+
+
+def test_control_stem_ignores_kernel_column_6(cpu_taps, stage_params):
+    w, b, s = stage_params[2][0][0]
+    wm = w.copy()
+    wm[:, :, 6, :] = 0
+    wrong = conv_reference(cpu_taps[TAP_IMAGE], wm, b, s, True)
+    assert not layer_ok(wrong, cpu_taps[TAP_CONV0])
+
+
+def test_control_stem_pads_by_replication(cpu_taps, stage_params):
+    w, b, s = stage_params[2][0][0]
+    x = np.pad(cpu_taps[TAP_IMAGE], ((0, 0), (3, 3), (3, 3), (0, 0)), mode="edge")
+    wrong = conv_finish(conv_preactivation(x, w, b, s, padding=0), True)
+    assert wrong.shape == cpu_taps[TAP_CONV0].shape and not layer_ok(wrong, cpu_taps[TAP_CONV0])
+
+
+def test_control_wrapped_right_border_tap_in_block_6(cpu_taps, stage_params):
+    convs = stage_params[2][0]
+    i = block_conv(6, 1)
+    assert topology()[i] == (128, 128, 3, 1)
+    x = cpu_taps[wiring()[0][i][0]]
+    wrong = stage_reference(TAP_CONV0 + i, cpu_taps.__getitem__, convs, mutate=wrapped_right_border(x, convs[i][0]))
+    assert not layer_ok(wrong, cpu_taps[TAP_CONV0 + i])
+    # ... and the mutation is the border's alone
+    assert np.array_equal(wrong[:, :, :-1], cpu_taps[TAP_CONV0 + i][:, :, :-1])
+
+
+def test_control_tail_tile_of_block_12_not_stored(cpu_taps):
+    right = cpu_taps[TAP_CONV0 + block_conv(12, 2)]
+    assert right.shape == (2, 14, 14, 1024)
+    wrong = right.copy()
+    wrong[-1].reshape(-1, 1024)[-3:] = 0                                              # the last three pixels of the last frame
+    assert not layer_ok(wrong, right)
+
+
+def test_control_one_bias_channel_dropped_in_conv_52(cpu_taps, stage_params):
+    convs = stage_params[2][0]
+    w, b, s = convs[52]
+    ch = int(np.argsort(np.abs(b))[b.size // 2])                                       # a channel with the median |bias|: neither the easiest nor a bias of ~ 0
+
+    def mutate(y):
+        y = y.clone()
+        y[:, ch] -= float(b[ch])
+        return y
+    wrong = stage_reference(TAP_CONV0 + 52, cpu_taps.__getitem__, convs, mutate=mutate)
+    right = cpu_taps[TAP_CONV0 + 52]
+    assert not layer_ok(wrong, right)
+    others = np.arange(b.size) != ch
+    assert np.array_equal(wrong[..., others], right[..., others])
+
+
+def test_controls_pass_unmutated(cpu_taps, stage_params):
+    """The criterion accepts the reference itself and a different float32 accumulation order of it (float64 sums): the controls above are
+    rejected for their mutation, not for the way the criterion is applied."""
+    convs = stage_params[2][0]
+    for i in (0, block_conv(6, 1), 52):
+        w, b, s = convs[i]
+        src, res, relu = (TAP_IMAGE, None, True) if i == 0 else wiring()[0][i]
+        x = torch.from_numpy(cpu_taps[src]).permute(0, 3, 1, 2).double()
+        wq = bf16(torch.from_numpy(np.ascontiguousarray(w))).permute(0, 3, 1, 2).double()
+        y = F.conv2d(x, wq, torch.from_numpy(b).double(), stride=s, padding=w.shape[1] // 2)
+        if res is not None:
+            y = y + torch.from_numpy(cpu_taps[res]).permute(0, 3, 1, 2).double()
+        y64 = bf16((torch.relu(y) if relu else y).float()).permute(0, 2, 3, 1).contiguous().numpy()
+        assert layer_ok(y64, cpu_taps[TAP_CONV0 + i]), i
+
+
+# ---- fused kernels and tilings inside the forward: bit comparisons with the layer-by-layer taps ---------------------------
+@pytest.mark.gpu
+@pytest.mark.parametrize("fuse", [1, 2])
+def test_fused_blocks_tap_by_tap(ctx, gpu_taps, fuse):
+    """Every block output of the two fused stages, and the two convolutions that read the last of them from the rotated buffer, hold the bits
+    of the layer-by-layer forward; cnn_plan proves which kernel ran."""
+    frames = stage_frames()
+    blocks = wiring()[1]
+    fused = [(li, s) for li, st, s in blocks if st < 2]
+    assert len(fused) == 7
+    nxt = blocks[7][0]
+    points = [TAP_CONV0 + li + 2 for li, s in fused] + [TAP_CONV0 + nxt, TAP_CONV0 + nxt + 3]
+    default = ctx.get_option("cnn_fuse")
+    try:
+        ctx.set_option("cnn_fuse", fuse)
+        for p in points:
+            tap, logits, plan = run_tapped(ctx, frames, p)
+            assert np.array_equal(tap, gpu_taps.bits[p]), p
+            assert np.array_equal(logits, gpu_taps.logits)
+        for li, s in fused:
+            assert plan[li + 1] == (PLAN_SLAB3_EXPAND if fuse == 2 and s == 1 else PLAN_CONV3_EXPAND), li
+            assert plan[li + 2] == PLAN_FOLDED, li
+        unfused = [i for i in range(53) if not any(i in (li + 1, li + 2) for li, s in fused)]
+        assert np.array_equal(plan[unfused], gpu_taps.plan[unfused])
+        # the 3x3 of a fused block has no output of its own: an error, not the bytes of an earlier tap
+        ctx.set_option("cnn_tap", TAP_CONV0 + fused[0][0] + 1)
+        ctx.cnn_forward(frames)
+        with pytest.raises(_lib.AvdError, match="cnn_tap"):
+            ctx.cnn_tap(2)
+    finally:
+        ctx.set_option("cnn_tap", 0)
+        ctx.set_option("cnn_fuse", default)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("policy", [1, 2])
+def test_tilings_through_the_whole_forward(ctx, gpu_taps, policy):
+    """All 53 real geometries under the 256-pixel bodies (policy 1) and the 128 x 128 body (policy 2): logits and three taps hold the bits of the
+    default tiling, and cnn_plan proves that the bodies ran."""
+    frames = stage_frames()
+    convs = topology()
+    fuse = ctx.get_option("cnn_fuse")
+    try:
+        ctx.set_option("cnn_fuse", 0)
+        ctx.set_option("cnn_tiles", policy)
+        for p in (54, 46, 24):
+            tap, logits, plan = run_tapped(ctx, frames, p)
+            assert np.array_equal(tap, gpu_taps.bits[p]), p
+            assert np.array_equal(logits, gpu_taps.logits)
+    finally:
+        ctx.set_option("cnn_tiles", 0)
+        ctx.set_option("cnn_fuse", fuse)
+    assert plan[0] == PLAN_STEM
+    for i in range(1, 53):
+        cout = convs[i][1]
+        if cout % 128:
+            assert cout == 64 and plan[i] == PLAN_256X64, i
+        elif policy == 1:
+            assert plan[i] == (PLAN_256X256 if cout % 256 == 0 else PLAN_256X128), i
+        else:
+            assert plan[i] == PLAN_128X128, i
+    seen = set(plan.tolist())
+    assert seen == ({PLAN_STEM, PLAN_256X64, PLAN_256X128, PLAN_256X256} if policy == 1 else {PLAN_STEM, PLAN_256X64, PLAN_128X128})
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n", [1, 2, 3])
+def test_activation_scratch_holds_the_padded_tail_tile(stage_params, n):
+    """Regression: every tile stores all 256 (128) of its rows, so an activation's rows are padded to whole tiles.  The scratch buffers were
+    sized by the stem's output (n x 12544 rows x 64, always whole tiles), but the 56 x 56 x 256 activations pad further unless n % 4 == 0: their
+    tail tile wrote up to 96 KiB past the end of its buffer.  The forward now refuses an activation that does not fit, and a tap copies the
+    padded activation whole: on a fresh context (exactly n frames of scratch) the 56 x 56 x 256 outputs are there and right."""
+    weights, biases, (convs, _) = stage_params
+    frames = stage_frames()[[0, 1, 0][:n]]
+    with _lib.Context(0) as c:
+        c.cnn_set_weights(weights, biases)
+        c.set_option("cnn_fuse", 0)
+        taps = Taps()
+        for p in (TAP_MAXPOOL, TAP_CONV0 + 1, TAP_CONV0 + 2, TAP_CONV0 + 3, TAP_CONV0 + 4):
+            taps.bits[p], _, _ = run_tapped(c, frames, p)
+        for p in (TAP_CONV0 + 3, TAP_CONV0 + 4):                                       # conv3 and the shortcut of the first block
+            assert taps.bits[p].shape == (n, 56, 56, 256)
+            assert layer_ok(taps(p), stage_reference(p, taps, convs)), p
+
+
+@pytest.mark.gpu
+def test_tap_and_plan_refusals(stage_params):
+    """cnn_tap / cnn_plan on a fresh context: errors before any forward; a tapped forward refuses more than one pass and timing repetitions;
+    an untapped forward, a wrong size and a released workspace leave nothing to fetch."""
+    weights, biases, _ = stage_params
+    frames = synth.random_frames(3, 96, 128, seed=9)
+    with _lib.Context(0) as c:
+        c.cnn_set_weights(weights, biases)
+        with pytest.raises(_lib.AvdError, match="cnn_plan"):
+            c.cnn_plan()
+        with pytest.raises(_lib.AvdError, match="cnn_tap"):
+            c.debug_fetch("cnn_tap", (3, 2048), np.float32)
+        c.set_option("cnn_tap", TAP_POOLED)
+        with pytest.raises(_lib.AvdError, match="cnn_tap"):
+            c.cnn_forward(frames, timing_reps=1)
+        c.set_option("cnn_chunk", 2)
+        with pytest.raises(_lib.AvdError, match="cnn_tap"):
+            c.cnn_forward(frames)
+        c.set_option("cnn_chunk", 128)
+        logits, _ = c.cnn_forward(frames)
+        pooled = c.cnn_tap(3)
+        assert pooled.shape == (3, 2048) and np.isfinite(pooled).all() and pooled.max() > 0
+        with pytest.raises(_lib.AvdError, match="cnn_tap"):
+            c.debug_fetch("cnn_tap", (2, 2048), np.float32)                            # not the tap's size
+        c.release_workspace()
+        with pytest.raises(_lib.AvdError, match="cnn_tap"):
+            c.cnn_tap(3)
+        c.cnn_forward(frames)
+        assert np.array_equal(c.cnn_tap(3), pooled)
+        c.set_option("cnn_tap", 0)
+        plain, _ = c.cnn_forward(frames)
+        assert np.array_equal(plain, logits)
+        with pytest.raises(_lib.AvdError, match="cnn_tap"):                            # the LAST forward was not tapped
+            c.debug_fetch("cnn_tap", (3, 2048), np.float32)
+        assert c.cnn_plan()[0] == PLAN_STEM

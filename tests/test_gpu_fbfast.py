@@ -416,6 +416,7 @@ _OPTION_SET_GET = {
     "cnn_tiles": [(2, 2), (99, 99), (-5, -5)],                         # unchanged
     "cnn_fuse": [(1, 1), (7, 2), (-3, 0)],                             # clamped to 0 ... 2
     "cnn_chunk": [(64, 64), (1, 1), (1024, 1024)],                     # 1 ... 1024 (anything else is refused: below)
+    "cnn_tap": [(1, 1), (56, 56), (30, 30), (0, 0)],                   # 0 ... 56 (anything else is refused: below)
 }
 # environment variable -> (option, [(text, value a context created under it reports)])
 _OPTION_ENV = {
@@ -428,13 +429,13 @@ _OPTION_ENV = {
     "AVD_GEMM_WAVES": ("gemm_waves", [("16", 16), ("8", 8), ("12", 8), ("-16", 8)]),                   # 16, else 8
 }
 _OPTION_DEFAULTS = {"fb_fused": 0xF, "fb_mode": 1, "fb_fold_up": 5, "fb_rerun": 1, "fb_rerun_fused": 0xC, "tail_help": 1, "fb_wide160": 2,
-                    "fb_fold_blur": 1, "gemm_waves": 8, "cnn_tiles": 0, "cnn_fuse": 2, "cnn_chunk": 128, "rerun_pairs": 0, "fb_wide160_used": 0}
+                    "fb_fold_blur": 1, "gemm_waves": 8, "cnn_tiles": 0, "cnn_fuse": 2, "cnn_chunk": 128, "cnn_tap": 0, "rerun_pairs": 0, "fb_wide160_used": 0}
 
 
 def test_option_table(monkeypatch):
     """avd_set_option / avd_get_option / the AVD_* environment variables read by avd_create, option by option: what `set` stores for a value in
     range, out of range and negative; the two read-only names and an unknown one refuse `set` (and an unknown one `get`) with AVD_ERR_ARG and
-    "unknown option: NAME"; cnn_chunk refuses a value outside 1 ... 1024 and keeps the old one; a context created under each environment variable
+    "unknown option: NAME"; cnn_chunk refuses a value outside 1 ... 1024 and cnn_tap one outside 0 ... 56, and both keep the old one; a context created under each environment variable
     reports the mapped value and the defaults everywhere else."""
     import avd_hip
     for var in _OPTION_ENV:
@@ -454,6 +455,12 @@ def test_option_table(monkeypatch):
             with pytest.raises(avd_hip.AvdError, match=r"^avd status -1: cnn_chunk: 1 \.\.\. 1024 frames per forward pass$"):
                 c.set_option("cnn_chunk", bad)
             assert c.get_option("cnn_chunk") == 128
+        c.set_option("cnn_tap", 7)
+        for bad in (-1, 57, 100, -56):
+            with pytest.raises(avd_hip.AvdError, match=r"^avd status -1: cnn_tap: 0 \(off\), 1 input image, 2 \.\.\. 54 convolution 0 \.\.\. 52, 55 max pool, 56 pooled features$"):
+                c.set_option("cnn_tap", bad)
+            assert c.get_option("cnn_tap") == 7
+        c.set_option("cnn_tap", 0)
         for name in ("rerun_pairs", "fb_wide160_used", "no_such_option", ""):
             with pytest.raises(avd_hip.AvdError, match=r"^avd status -1: unknown option: %s$" % name):
                 c.set_option(name, 1)
