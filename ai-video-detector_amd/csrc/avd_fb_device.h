@@ -19,7 +19,6 @@ __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? l
 __device__ __forceinline__ int floor_f(float v) { int i = (int)v; return i - (i > v); }
 
 struct NeIn { float dx, dy, r0[5]; };
-struct NeG { float top[10], bot[10]; };            // (y1,x1..x1+1) and (y1+1,x1..x1+1), 5 coefficients each
 
 struct __attribute__((packed, aligned(4))) F4 { float a, b, c, d; };
 struct __attribute__((packed, aligned(4))) F2 { float a, b; };
@@ -90,62 +89,6 @@ __device__ __forceinline__ void ne_load_r0(const float* __restrict__ R, unsigned
     in.r0[0] = v.a; in.r0[1] = v.b; in.r0[2] = v.c; in.r0[3] = v.d; in.r0[4] = ld_off_i<float, 16>(R, pb);
 }
 
-// gather the four bilinear neighbours of the warped position (clamped address when outside:
-// the values are discarded by ne_finish, exactly as cv2 takes the "else" branch there)
-__device__ __forceinline__ void ne_gather(const float* __restrict__ R, unsigned r1base, const NeIn& in, int x, int y,
-                                          int w, int h, int plane, NeG& g)
-{
-    const float fx = x + in.dx, fy = y + in.dy;
-    const int x1 = clampi(floor_f(fx), 0, w - 2), y1 = clampi(floor_f(fy), 0, h - 2);
-    const unsigned pb = (r1base + (unsigned)(y1 * w + x1) * 5u) * 4u, qb = pb + (unsigned)w * 20u;
-    const F4 t0 = ld_off<F4>(R, pb), t1 = ld_off_i<F4, 16>(R, pb);
-    const F2 t2 = ld_off_i<F2, 32>(R, pb);
-    const F4 b0 = ld_off<F4>(R, qb), b1 = ld_off_i<F4, 16>(R, qb);
-    const F2 b2 = ld_off_i<F2, 32>(R, qb);
-    g.top[0] = t0.a; g.top[1] = t0.b; g.top[2] = t0.c; g.top[3] = t0.d; g.top[4] = t1.a;
-    g.top[5] = t1.b; g.top[6] = t1.c; g.top[7] = t1.d; g.top[8] = t2.a; g.top[9] = t2.b;
-    g.bot[0] = b0.a; g.bot[1] = b0.b; g.bot[2] = b0.c; g.bot[3] = b0.d; g.bot[4] = b1.a;
-    g.bot[5] = b1.b; g.bot[6] = b1.c; g.bot[7] = b1.d; g.bot[8] = b2.a; g.bot[9] = b2.b;
-}
-
-__device__ __forceinline__ void ne_finish(const NeIn& in, const NeG& g, int x, int y, int w, int h, float (&M)[5])
-{
-    // Branch-free on purpose (selects, multiplication by an exact 1.0f): a conditional block here lets the
-    // compiler sink the gathered loads into it, right in front of their use, and makes its vmcnt counts
-    // conservative at the join -- either way the software pipeline of k_uv / k_uvp collapses.
-    const float dx = in.dx, dy = in.dy;
-    float fx = x + dx, fy = y + dy;
-    const int x1 = floor_f(fx), y1 = floor_f(fy);
-    fx -= x1; fy -= y1;
-    const bool inside = (unsigned)x1 < (unsigned)(w - 1) && (unsigned)y1 < (unsigned)(h - 1);
-    const float a00 = (1.f - fx) * (1.f - fy), a01 = fx * (1.f - fy), a10 = (1.f - fx) * fy, a11 = fx * fy;
-    const float b2 = a00 * g.top[0] + a01 * g.top[5] + a10 * g.bot[0] + a11 * g.bot[5];
-    const float b3 = a00 * g.top[1] + a01 * g.top[6] + a10 * g.bot[1] + a11 * g.bot[6];
-    const float b4 = a00 * g.top[2] + a01 * g.top[7] + a10 * g.bot[2] + a11 * g.bot[7];
-    const float b5 = a00 * g.top[3] + a01 * g.top[8] + a10 * g.bot[3] + a11 * g.bot[8];
-    const float b6 = a00 * g.top[4] + a01 * g.top[9] + a10 * g.bot[4] + a11 * g.bot[9];
-    float r2 = inside ? b2 : 0.f, r3 = inside ? b3 : 0.f;
-    float r4 = inside ? (in.r0[2] + b4) * 0.5f : in.r0[2];
-    float r5 = inside ? (in.r0[3] + b5) * 0.5f : in.r0[3];
-    float r6 = inside ? (in.r0[4] + b6) * 0.25f : in.r0[4] * 0.5f;
-    r2 = (in.r0[0] - r2) * 0.5f;
-    r3 = (in.r0[1] - r3) * 0.5f;
-    r2 += r4 * dy + r6 * dx;
-    r3 += r6 * dy + r5 * dx;
-    {
-        auto border = [](int d) { return d < 2 ? 0.14f : 0.4472f; };      // {.14,.14,.4472,.4472,.4472}
-        const bool edge = (unsigned)(x - 5) >= (unsigned)(w - 10) || (unsigned)(y - 5) >= (unsigned)(h - 10);
-        const float sc = (x < 5 ? border(x) : 1.f) * (x >= w - 5 ? border(w - x - 1) : 1.f) *
-                         (y < 5 ? border(y) : 1.f) * (y >= h - 5 ? border(h - y - 1) : 1.f);
-        const float scale = edge ? sc : 1.f;             // interior: x * 1.0f == x exactly
-        r2 *= scale; r3 *= scale; r4 *= scale; r5 *= scale; r6 *= scale;
-    }
-    M[0] = r4 * r4 + r6 * r6;
-    M[1] = (r4 + r5) * r6;
-    M[2] = r5 * r5 + r6 * r6;
-    M[3] = r4 * r2 + r6 * r3;
-    M[4] = r6 * r2 + r5 * r3;
-}
 // cv2.resize(prev, (W, W), INTER_LINEAR) * 2 (the initial flow of a pyramid level from the coarser level's result), four consecutive
 // outputs dx = 4 q .. 4 q + 3 of row dy of one component plane: k_flow_up's arithmetic (avd_farneback.hip), shared by the kernels that fold
 // that resize into themselves.  The destination is exactly twice the source, so the source coordinate d / 2 - 0.25 is exact in float:
@@ -179,23 +122,23 @@ __device__ __forceinline__ void flow_up_chunk(const float* __restrict__ src, int
     }
 }
 
-// ---- leaner forms for the fused level kernel (avd_fbfused.hip): same arithmetic, fewer instructions per row ----------
+// ---- gather and normal equations ------------------------------------------------------------------------------------
 // * the warped integer position is computed once (in the gather step) and carried to the finish step;
-// * the 5-pixel border attenuation (x < 5 ? b[x] : 1) * (x >= w-5 ? b[w-x-1] : 1) * (y < 5 ? ...) * (y >= h-5 ? ...) is split
-//   into a per-lane factor sx (constant for the whole kernel) and a per-row factor sy (wave-uniform).  For images of at
-//   least 10 pixels at most one x factor and one y factor differ from 1, so cv2's left-to-right product equals sx * sy
-//   bit for bit (multiplications by 1.0f are exact), and interior pixels multiply by exactly 1.
+// * the 5-pixel border attenuation (x < 5 ? b[x] : 1) * (x >= w-5 ? b[w-x-1] : 1) * (y < 5 ? ...) * (y >= h-5 ? ...), b = {.14, .14,
+//   .4472, .4472, .4472}, is split into a per-lane factor sx (constant for the whole kernel) and a per-row factor sy (wave-uniform).
+//   For images of at least 10 pixels at most one x factor and one y factor differ from 1, so cv2's left-to-right product equals
+//   sx * sy bit for bit (multiplications by 1.0f are exact), and interior pixels multiply by exactly 1.
 typedef float fv2 __attribute__((ext_vector_type(2)));
 typedef float fv4 __attribute__((ext_vector_type(4)));
 // the gathered rows as the three loads of a row deliver them: t0 = px0 c0..c3, t1 = (px0 c4, px1 c0, px1 c1, px1 c2), t2 = (px1 c3, px1 c4)
 // fx, fy: fractional parts of the warped position; inside: cv2's test (unsigned)x1 < w - 1 && (unsigned)y1 < h - 1
-struct NeG2 { fv4 t0, t1; fv2 t2; fv4 b0, b1; fv2 b2; float fx, fy; bool inside; };
+struct NeG { fv4 t0, t1; fv2 t2; fv4 b0, b1; fv2 b2; float fx, fy; bool inside; };
 
 // The bilinear sample of the five coefficients, cv2's operation order per channel -- ((a00 p00 + a01 p01) + a10 p10) + a11 p11 -- with the
 // TEN products of a row formed as five packed multiplies on the register pairs the loads delivered (px1's coefficients start at an odd
 // register: pairing by channel across the two pixels, or by pixel across channels, both need a move per pair -- 116 of the 585 VALU
 // instructions of the N waves' loop were v_mov); the sums are scalar adds, which read any register.  Same IEEE operations: bit-identical.
-__device__ __forceinline__ void ne_bilinear(const NeG2& g, float a00, float a01, float a10, float a11, float (&b)[5])
+__device__ __forceinline__ void ne_bilinear(const NeG& g, float a00, float a01, float a10, float a11, float (&b)[5])
 {
     const fv2 w00 = {a00, a00}, w0x = {a00, a01}, w01 = {a01, a01};
     const fv2 w10 = {a10, a10}, w1x = {a10, a11}, w11 = {a11, a11};
@@ -214,10 +157,12 @@ __device__ __forceinline__ float border_factor(int p, int len)
     return (p < 5 ? lo : 1.f) * (p >= len - 5 ? hi : 1.f);
 }
 
+// gather the four bilinear neighbours of the warped position (clamped address when outside: the values are discarded by ne_finish_r,
+// exactly as cv2 takes the "else" branch there)
 // zf (wave-uniform): the flow is known to be zero (first iteration of the coarsest level): whatever the flow buffer holds is
 // ignored, which saves clearing it
-__device__ __forceinline__ void ne_gather2(const float* __restrict__ R, unsigned r1base, const NeIn& in, int x, int y,
-                                           int w, int h, NeG2& g, bool zf = false)
+__device__ __forceinline__ void ne_gather(const float* __restrict__ R, unsigned r1base, const NeIn& in, int x, int y,
+                                          int w, int h, NeG& g, bool zf = false)
 {
     // cvFloor and "fx -= x1" through v_floor_f32: floorf(v) IS (float)cvFloor(v) for |v| < 2^24 (and the same value beyond), three
     // instructions per coordinate (floor, convert, subtract) instead of six (truncate, convert back, compare, borrow, convert, subtract)
@@ -233,38 +178,14 @@ __device__ __forceinline__ void ne_gather2(const float* __restrict__ R, unsigned
     g.b2 = __builtin_bit_cast(fv2, ld_off_i<F2, 32>(R, qb));
 }
 
-__device__ __forceinline__ void ne_finish2(const NeIn& in, const NeG2& g, int x, int y, int w, int h, float sx, float sy,
-                                           float (&M)[5], bool zf = false)
+// The evaluation in two steps, because the fast level kernel (avd_fbfast.hip) runs them in different waves: its normal-equation wave
+// stops at r2 .. r6 (before the border attenuation), its chain wave -- which has issue slots to spare -- applies the attenuation and
+// forms the five products.  ne_finish is the two in one wave.
+__device__ __forceinline__ void ne_finish_r(const NeIn& in, const NeG& g, float (&r)[5], bool zf = false)
 {
-    const float dx = zf ? 0.f : in.dx, dy = zf ? 0.f : in.dy;
-    const float fx = g.fx, fy = g.fy;
-    const bool inside = g.inside;
-    const float a00 = (1.f - fx) * (1.f - fy), a01 = fx * (1.f - fy), a10 = (1.f - fx) * fy, a11 = fx * fy;
-    float bb[5];
-    ne_bilinear(g, a00, a01, a10, a11, bb);
-    const float b2 = bb[0], b3 = bb[1], b4 = bb[2], b5 = bb[3], b6 = bb[4];
-    float r2 = inside ? b2 : 0.f, r3 = inside ? b3 : 0.f;
-    float r4 = inside ? (in.r0[2] + b4) * 0.5f : in.r0[2];
-    float r5 = inside ? (in.r0[3] + b5) * 0.5f : in.r0[3];
-    float r6 = inside ? (in.r0[4] + b6) * 0.25f : in.r0[4] * 0.5f;
-    r2 = (in.r0[0] - r2) * 0.5f;
-    r3 = (in.r0[1] - r3) * 0.5f;
-    r2 += r4 * dy + r6 * dx;
-    r3 += r6 * dy + r5 * dx;
-    const float scale = sx * sy;
-    r2 *= scale; r3 *= scale; r4 *= scale; r5 *= scale; r6 *= scale;
-    M[0] = r4 * r4 + r6 * r6;
-    M[1] = (r4 + r5) * r6;
-    M[2] = r5 * r5 + r6 * r6;
-    M[3] = r4 * r2 + r6 * r3;
-    M[4] = r6 * r2 + r5 * r3;
-}
-
-// ---- the same split in two for the fast level kernel (avd_fbfast.hip): the normal-equation wave stops at r2 .. r6 (before
-// the border attenuation), the chain wave -- which has issue slots to spare -- applies the attenuation and forms the five
-// products.  Same operations in the same order as ne_finish2: bit-identical.
-__device__ __forceinline__ void ne_finish_r(const NeIn& in, const NeG2& g, int x, int y, int w, int h, float (&r)[5], bool zf = false)
-{
+    // Branch-free on purpose (selects, multiplication by an exact 1.0f): a conditional block here lets the
+    // compiler sink the gathered loads into it, right in front of their use, and makes its vmcnt counts
+    // conservative at the join -- either way the software pipeline of k_uv / k_uvp collapses.
     const float dx = zf ? 0.f : in.dx, dy = zf ? 0.f : in.dy;
     const float fx = g.fx, fy = g.fy;
     const bool inside = g.inside;
@@ -293,6 +214,26 @@ __device__ __forceinline__ void ne_products(const float (&r)[5], float scale, fl
     M[4] = r6 * r2 + r5 * r3;
 }
 
+__device__ __forceinline__ void ne_finish(const NeIn& in, const NeG& g, float sx, float sy, float (&M)[5], bool zf = false)
+{
+    float r[5];
+    ne_finish_r(in, g, r, zf);
+    ne_products(r, sx * sy, M);
+}
+
+// cv2's 2 x 2 solve of a pixel, literally: the five window sums g scaled by 1 / 225, 1e-3 added to the determinant, IEEE division, in that
+// order.  For k_hscan and k_hscan_lat; role_solve of the fused kernel has the same lines written out (see there).  The fast level
+// kernel's solver is a different computation: see recip_newton2.
+__device__ __forceinline__ void fb_solve_exact(const double (&g)[5], float& fx, float& fy)
+{
+    const double scale = 1. / (15 * 15);
+    const double g11 = g[0] * scale, g12 = g[1] * scale, g22 = g[2] * scale;
+    const double h1 = g[3] * scale, h2 = g[4] * scale;
+    const double idet = 1. / (g11 * g22 - g12 * g12 + 1e-3);
+    fx = (float)((g11 * h2 - g12 * h1) * idet);
+    fy = (float)((g22 * h1 - g12 * h2) * idet);
+}
+
 // ---- shared by the fast level kernels (avd_fbfast.hip) -------------------------------------------------------------
 // thresholds of the ill-posedness criteria (see role_solve and role_ne in avd_fbfast.hip)
 constexpr double kCondMax = 2000.;
@@ -308,7 +249,7 @@ constexpr float kJumpMinZero = 0.05f; // an exactly zero one (cv2's may be +-res
 // r2 = R0[0] / 2, r3 = R0[1] / 2, r4 .. r6 from R0 alone, "inside" (R0[0] - b[0]) / 2, .., (R0[2] + b[2]) / 2 .. with b the sample of R1, which is
 // the top-left gathered pixel there -> max(|b0|, |b1|, |R0[2] - b2|, |R0[3] - b3|, |R0[4] - b4|).  Cold path of role_ne; the same definition in
 // tools/experiments/fb_illposed_exp.c (border_ind).
-__device__ __forceinline__ float ne_branch_jump(const NeIn& in, const NeG2& g)
+__device__ __forceinline__ float ne_branch_jump(const NeIn& in, const NeG& g)
 {
     float j = fmaxf(fabsf(g.t0.x), fabsf(g.t0.y));
     j = fmaxf(j, fabsf(in.r0[2] - g.t0.z));

@@ -144,11 +144,11 @@ __device__ __forceinline__ bool role_ne(const float* __restrict__ R, const float
     auto ent = [&](int i) { return 4 * (i / EPS) + EPS * k + (i % EPS); };  // this wave's i-th entry
     auto row_of = [](int e) { return e < H - 1 ? e : H - 1; };
     NeIn in[NIS];
-    NeG2 g[NGS];
+    NeG g[NGS];
     const bool xz = x == 0;                                // this lane's column decides inside / outside by the sign of dx
     const bool chkx = chk && __builtin_amdgcn_ballot_w64(xz) != 0;   // wave-uniform: only the first block of the first strip holds column 0
     bool ill = false;
-    auto gather = [&](const NeIn& s, int row, NeG2& gs) __attribute__((always_inline)) { ne_gather2(R, r1base, s, x, row, W, H, gs, zf); };
+    auto gather = [&](const NeIn& s, int row, NeG& gs) __attribute__((always_inline)) { ne_gather(R, r1base, s, x, row, W, H, gs, zf); };
     auto flow_of = [&](int row, NeIn& s) { const float* f = fring + (row & 15) * Ge::F_SLOT + lane; s.dx = f[0]; s.dy = f[64]; };
     auto load_in = [&](int row, NeIn& s) {
         if (UP) ne_load_r0(R, r0base, x, row, W, s);
@@ -180,7 +180,7 @@ __device__ __forceinline__ bool role_ne(const float* __restrict__ R, const float
             if (UP) flow_of(row_of(ent(i + GD + 1)), in[(ii + GD + 1) % NIS]);   // for the gather issued with the next entry
             __builtin_amdgcn_sched_barrier(0);
             float a[5];                                                      // r2 .. r6: the chain wave attenuates and multiplies (PN: done here)
-            ne_finish_r(in[ii % NIS], g[ii % NGS], x, e, W, H, a, zf);
+            ne_finish_r(in[ii % NIS], g[ii % NGS], a, zf);
             if constexpr (!ZF) {                                             // (ZF: the coarsest level's first flow is zero in cv2 as well)
                 if (chkx || (chk && e == 0)) {
                     const NeIn& s = in[ii % NIS];

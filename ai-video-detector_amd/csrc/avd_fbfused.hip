@@ -107,14 +107,14 @@ __device__ __forceinline__ void role_vertical(const float* __restrict__ R, const
     auto row_of = [](int e) { return e < H - 1 ? e : H - 1; };
 
     NeIn in[4];
-    NeG2 g[2];
+    NeG g[2];
     const float sx = border_factor(x, W);                 // x part of the border attenuation: a per-lane constant
     float ring[16][5];                                  // ring[e & 15] = normal-equation row of entry e
     double vs[5] = {0., 0., 0., 0., 0.};
     unsigned goff = 0;                                  // group buffer being filled (offset in doubles)
 #pragma unroll
     for (int k = 0; k < 3; k++) ne_load(R, flow, r0base, flbase, x, row_of(k), W, plane, in[k]);
-    ne_gather2(R, r1base, in[0], x, row_of(0), W, H, g[0], zf);
+    ne_gather(R, r1base, in[0], x, row_of(0), W, H, g[0], zf);
 
     // one entry: evaluate, refill the prefetch slots, update the running sums, publish the vsum row
     auto step = [&](int e, int kk, bool first, bool refill_g, bool refill_in) __attribute__((always_inline)) {
@@ -122,11 +122,11 @@ __device__ __forceinline__ void role_vertical(const float* __restrict__ R, const
         // the other one) and the inputs three entries ahead into the slot of entry e - 1, so nothing this entry still
         // needs is overwritten -- and the gather gets a whole row of lead instead of the tail of one (issued after the
         // arithmetic it had ~300 cycles before its use at the top of the next step: less than an L2 round trip).
-        if (refill_g) ne_gather2(R, r1base, in[(kk + 1) & 3], x, row_of(e + 1), W, H, g[(kk + 1) & 1], zf);
+        if (refill_g) ne_gather(R, r1base, in[(kk + 1) & 3], x, row_of(e + 1), W, H, g[(kk + 1) & 1], zf);
         if (refill_in) ne_load(R, flow, r0base, flbase, x, row_of(e + 3), W, plane, in[(kk + 3) & 3]);
         __builtin_amdgcn_sched_barrier(0);
         float a[5];
-        ne_finish2(in[kk & 3], g[kk & 1], x, row_of(e), W, H, sx, border_factor(row_of(e), H), a, zf);
+        ne_finish(in[kk & 3], g[kk & 1], sx, border_factor(row_of(e), H), a, zf);
         if (first && kk == 0) {
 #pragma unroll
             for (int c = 0; c < 5; c++) vs[c] = (double)(a[c] * (float)(kM + 2));
@@ -354,6 +354,8 @@ __device__ __forceinline__ void role_solve(const float* __restrict__ R, const do
                 const int x = b * 64 + lane;
                 if (x < W) {
                     const double* q = buf + goff + (unsigned)(r * 5) * Ge::P + (unsigned)x;
+                    // fb_solve_exact (avd_fb_device.h) written out: called as a function it is the same instructions in another order
+                    // in three of the four kernels, and this file's text is held equal to what has been measured
                     const double g11 = q[0] * scale, g12 = q[Ge::P] * scale, g22 = q[2 * Ge::P] * scale;
                     const double h1 = q[3 * Ge::P] * scale, h2 = q[4 * Ge::P] * scale;
                     const double idet = 1. / (g11 * g22 - g12 * g12 + 1e-3);

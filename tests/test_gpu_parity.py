@@ -172,6 +172,40 @@ def test_fused_and_two_kernel_paths_agree(oracle):
             c.set_option("no_such_option", 1)
 
 
+@pytest.fixture(scope="module")
+def cycled_clip(oracle):
+    """111 frames of 320 x 320 cycled from 8 base frames (four smooth, two white noise, one constant, one saturated step) with stride 3:
+    pair k is (base[3k % 8], base[(3k + 3) % 8]), one of 8 types -> (frames, index of each frame's base, the 8 oracle flows and their (mean, variance) by first base)."""
+    rng = np.random.default_rng(17)
+    step = np.zeros((320, 320), np.uint8)
+    step[:, 160:] = 255
+    clip = synth.make_clip(4, 360, 640, seed=17, dup_every=0)
+    smooth = [oracle.resize_linear(oracle.bgr2gray(f), 320, 320) for f in clip]
+    base = np.stack(smooth + [rng.integers(0, 256, (320, 320), dtype=np.uint8) for _ in range(2)] + [np.full((320, 320), 200, np.uint8), step])
+    idx = (3 * np.arange(111)) % 8
+    flows = {a: oracle.farneback(base[a], base[(a + 3) % 8]) for a in range(8)}
+    return base[idx], idx, flows, {a: oracle.flow_stats(f) for a, f in flows.items()}
+
+
+@pytest.mark.parametrize("nframes", [111, 110])
+@pytest.mark.parametrize("fused", [0xE, 0x0])
+def test_two_kernel_path_on_both_sides_of_the_residency_limit(cycled_clip, fused, nframes):
+    """The 320-px level of the two-kernel path (bit 0 of fb_fused clear, exact mode) takes the streaming shape k_uv from 110 pairs in a
+    chunk (7 strips each: more than 3 x 256 workgroups) and the producer / consumer shape k_uvp<320, 4> up to 109.  Both give the oracle's
+    flow bit for bit; with 110 pairs the XCD dealing (14 pairs per XCD) leaves idle blocks."""
+    import avd_hip
+    frames, idx, flows, stats = cycled_clip
+    with avd_hip.Context(0) as c:
+        c.set_option("fb_mode", 0)
+        c.set_option("fb_fused", fused)
+        fm, fv, flow = c.farneback_pairs(frames[:nframes], want_flow=True)
+    assert len(flow) == nframes - 1
+    for p in range(nframes - 1):
+        want = flows[int(idx[p])]
+        assert np.array_equal(flow[p], want), f"pair {p} (type {idx[p]}): {np.count_nonzero(flow[p] != want)} values differ"
+        assert (fm[p], fv[p]) == stats[int(idx[p])], p
+
+
 def test_flow_stats_match_numpy(ctx, oracle):
     small = _smalls(oracle, 4, seed=12)
     fm, fv, flow = ctx.farneback_pairs(small, want_flow=True)
