@@ -26,6 +26,7 @@ EXPORTS = (
     "avd_analyze_frames_async", "avd_synchronize", "avd_analyze_batch", "avd_analyze_batch_async",
     "avd_wait_stream", "avd_release_workspace",
     "avd_preprocess_nv12", "avd_analyze_frames_nv12", "avd_analyze_frames_nv12_async",
+    "avd_preprocess_i420", "avd_analyze_frames_i420", "avd_analyze_frames_i420_async",
     "avd_vit_set_weights", "avd_vit_patch_embed", "avd_audio_features", "avd_layernorm", "avd_softmax",
     "avd_cnn_param_counts", "avd_cnn_set_weights", "avd_cnn_forward", "avd_cnn_conv",
     "avd_comm_unique_id", "avd_comm_init", "avd_allgather_records", "avd_allgather_last_records",
@@ -121,6 +122,10 @@ def load() -> C.CDLL:
     L.avd_preprocess_nv12.argtypes = nv12 + [u8p, u8p, i64p, i64p]
     L.avd_analyze_frames_nv12.argtypes = nv12 + [vp]
     L.avd_analyze_frames_nv12_async.argtypes = nv12 + [vp]
+    i420 = [vp, u8p, u8p, u8p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int64]
+    L.avd_preprocess_i420.argtypes = i420 + [u8p, u8p, i64p, i64p]
+    L.avd_analyze_frames_i420.argtypes = i420 + [vp]
+    L.avd_analyze_frames_i420_async.argtypes = i420 + [vp]
     L.avd_vit_set_weights.argtypes = [vp, vp, vp]
     L.avd_vit_patch_embed.argtypes = [vp, u8p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, vp, C.c_int, C.c_int, C.c_int,
                                       C.POINTER(C.c_float)]
@@ -309,6 +314,65 @@ class Context:
         assert rec.dtype == RECORD_DTYPE and rec.size >= n and rec.flags.c_contiguous
         self._check(self._L.avd_analyze_frames_nv12_async(self._h, yp, cp, mem, n, h, w, yr, cr, yf, cf, rec.ctypes.data))
         return keep
+
+    # -- I420 (planar 4:2:0, software decoders): y uint8[N,H,W], u and v uint8[N,H/2,W/2]; YV12 = the same calls with u and v exchanged ------
+    def _i420_ptrs(self, y, u, v):
+        """-> (yptr, uptr, vptr, mem, n, h, w, y_row, c_row, y_frame, c_frame, keepalive).  Strided views are passed as they are (a decoder's
+        pitch, planes cut out of one buffer per clip); U and V must share their strides (the C-ABI has one pair for both)."""
+        planes = (y, u, v)
+        torch_in = [_is_torch_tensor(p) for p in planes]
+        if any(torch_in) != all(torch_in):
+            raise ValueError("the three planes must all be numpy arrays or all torch tensors")
+        if all(torch_in):
+            if any(p.dim() != 3 or str(p.dtype) != "torch.uint8" or p.is_cuda != y.is_cuda for p in planes):
+                raise ValueError("planes must be uint8[N,H,W], uint8[N,H/2,W/2] and uint8[N,H/2,W/2] on the same device")
+            ok = lambda t: t.stride(2) == 1 and t.stride(1) >= t.shape[2] and (t.shape[0] == 1 or t.stride(0) >= t.stride(1) * t.shape[1])
+            y, u, v = (p if ok(p) else p.contiguous() for p in planes)
+            st = lambda t: (t.stride(1), t.stride(0) if t.shape[0] > 1 else t.shape[1] * t.stride(1))
+            ptr, cuda = (lambda t: t.data_ptr()), y.is_cuda
+        else:
+            y, u, v = (np.asarray(p) for p in planes)
+            if any(p.ndim != 3 or p.dtype != np.uint8 for p in (y, u, v)):
+                raise ValueError("planes must be uint8[N,H,W], uint8[N,H/2,W/2] and uint8[N,H/2,W/2]")
+            ok = lambda a: a.strides[2] == 1 and a.strides[1] >= a.shape[2] and (a.shape[0] == 1 or a.strides[0] >= a.strides[1] * a.shape[1])
+            y, u, v = (p if ok(p) else np.ascontiguousarray(p) for p in (y, u, v))
+            st = lambda a: (a.strides[1], a.strides[0] if a.shape[0] > 1 else a.shape[1] * a.strides[1])
+            ptr, cuda = (lambda a: a.ctypes.data), False
+        n, h, w = (int(d) for d in y.shape)
+        if tuple(u.shape) != (n, h // 2, w // 2) or tuple(v.shape) != (n, h // 2, w // 2):
+            raise ValueError(f"chroma planes must be uint8[{n},{h // 2},{w // 2}] each, got {tuple(u.shape)} and {tuple(v.shape)}")
+        if st(u) != st(v):
+            raise ValueError(f"the U and V planes must have the same row and frame strides, got {st(u)} and {st(v)}")
+        if cuda:
+            self._after_torch_stream(y)
+        (yr, yf), (cr, cf) = st(y), st(u)
+        return ptr(y), ptr(u), ptr(v), (AVD_MEM_DEVICE if cuda else AVD_MEM_HOST), n, h, w, yr, cr, yf, cf, (y, u, v)
+
+    def preprocess_i420(self, y, u, v):
+        yp, up, vp, mem, n, h, w, yr, cr, yf, cf, keep = self._i420_ptrs(y, u, v)
+        small = np.empty((n, SMALL, SMALL), np.uint8)
+        hsh = np.empty((n, HASH * HASH), np.uint8)
+        s = np.empty(n, np.int64)
+        q = np.empty(n, np.int64)
+        self._check(self._L.avd_preprocess_i420(self._h, yp, up, vp, mem, n, h, w, yr, cr, yf, cf, small.ctypes.data,
+                                                hsh.ctypes.data, s.ctypes.data, q.ctypes.data))
+        return small, hsh, s, q
+
+    def analyze_frames_i420(self, y, u, v) -> np.ndarray:
+        yp, up, vp, mem, n, h, w, yr, cr, yf, cf, keep = self._i420_ptrs(y, u, v)
+        rec = np.zeros(n, RECORD_DTYPE)
+        self._check(self._L.avd_analyze_frames_i420(self._h, yp, up, vp, mem, n, h, w, yr, cr, yf, cf, rec.ctypes.data))
+        return rec
+
+    def analyze_frames_i420_async(self, y, u, v, rec: np.ndarray):
+        yp, up, vp, mem, n, h, w, yr, cr, yf, cf, keep = self._i420_ptrs(y, u, v)
+        assert rec.dtype == RECORD_DTYPE and rec.size >= n and rec.flags.c_contiguous
+        self._check(self._L.avd_analyze_frames_i420_async(self._h, yp, up, vp, mem, n, h, w, yr, cr, yf, cf, rec.ctypes.data))
+        return keep
+
+    def stage_bytes(self) -> int:
+        """Bytes the last ingest call of this context copied from host memory (0: device input); avd_debug_fetch "stage_bytes"."""
+        return int(self.debug_fetch("stage_bytes", (1,), np.int64)[0])
 
     # -- LayerNorm / softmax (extensions) -------------------------------------------------------------------------
     def layernorm(self, x, gamma, beta, eps: float = 1e-5, timing_reps: int = 0, out=None):

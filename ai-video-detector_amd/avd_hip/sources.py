@@ -11,7 +11,9 @@ capture properties the reference falls back to when ffprobe metadata is missing
   1. ``*.npy``  raw decoded stack uint8[T,H,W,3] (memory-mapped) -- used by tests / tools;
   2. ``*.y4m``  YUV4MPEG2, 8-bit 4:2:0 (what ``ffmpeg -i in.mp4 out.y4m`` writes, i.e. a decoder's pictures BEFORE the colour
      conversion): memory-mapped, handed over as NV12 surfaces to ``avd_analyze_frames_nv12`` -- the YUV->BGR step of
-     ``cap.retrieve()`` happens in the HIP kernel (SURVEY.md section 8f, row N1), no BGR frame ever exists;
+     ``cap.retrieve()`` happens in the HIP kernel, no BGR frame ever exists.  With
+     ``planar=True`` (or ``AVD_Y4M_SURFACE=i420``) the file's own planar pictures go to ``avd_analyze_frames_i420`` as views of
+     the map, without the host-side interleave;
   3. ``cv2.VideoCapture`` if OpenCV is importable (identical decode to the reference);
   4. ``ffmpeg``/``ffprobe`` CLIs if on PATH (rawvideo bgr24 pipe).
 If nothing can open the file the analyzer returns the reference's "capture not opened"
@@ -20,6 +22,7 @@ result (video.py:12-13).
 from __future__ import annotations
 
 import json
+import os
 import shutil
 import subprocess
 from typing import Iterator, Optional
@@ -28,7 +31,8 @@ import numpy as np
 
 
 class FrameSource:
-    surface: str = "bgr"        # what sampled() yields: "bgr" = uint8[H,W,3]; "nv12" = (y uint8[H,W], uv uint8[H/2,W] interleaved U,V)
+    # what sampled() yields: "bgr" = uint8[H,W,3]; "nv12" = (y uint8[H,W], uv uint8[H/2,W] interleaved U,V); "i420" = (y uint8[H,W], u uint8[H/2,W/2], v likewise)
+    surface: str = "bgr"
     fps: float = 0.0
     width: int = 0
     height: int = 0
@@ -57,10 +61,12 @@ class NpySource(FrameSource):
 class Y4mSource(FrameSource):
     """YUV4MPEG2 file with 8-bit 4:2:0 pictures (C420, C420jpeg, C420mpeg2, C420paleo -- chroma siting does not enter
     libswscale's unscaled yuv420p -> bgr24 conversion, which takes the nearest chroma sample).  Frames are read through a
-    memory map; ``sampled`` yields NV12 surfaces (the U and V planes interleaved on the host: 0.5 byte per pixel)."""
+    memory map; ``sampled`` yields NV12 surfaces (the U and V planes interleaved on the host: 0.5 byte per pixel), or with
+    ``planar=True`` the file's own I420 planes as three views of the map (no copy, no interleave)."""
     surface = "nv12"
 
-    def __init__(self, path: str):
+    def __init__(self, path: str, planar: bool = False):
+        self.surface = "i420" if planar else "nv12"
         with open(path, "rb") as f:
             header = f.readline(4096)
         if not header.startswith(b"YUV4MPEG2 ") or not header.endswith(b"\n"):
@@ -113,6 +119,9 @@ class Y4mSource(FrameSource):
             y = np.asarray(self._map[o:o + self._luma]).reshape(h, w)
             u = self._map[o + self._luma:o + self._luma + self._chroma].reshape(h // 2, w // 2)
             v = self._map[o + self._luma + self._chroma:o + self._frame_bytes].reshape(h // 2, w // 2)
+            if self.surface == "i420":
+                yield self._map[o:o + self._luma].reshape(h, w), u, v
+                continue
             uv = np.empty((h // 2, w), np.uint8)
             uv[:, 0::2] = u
             uv[:, 1::2] = v
@@ -194,8 +203,12 @@ class FfmpegSource(FrameSource):
             self._proc.wait()
 
 
-def open_source(path: str) -> Optional[FrameSource]:
-    """First source that can open ``path``; None if none can (== capture not opened)."""
+def open_source(path: str, planar: Optional[bool] = None) -> Optional[FrameSource]:
+    """First source that can open ``path``; None if none can (== capture not opened).  ``planar`` selects what a ``.y4m`` file yields:
+    True = its own I420 planes, False = NV12; None reads the environment variable AVD_Y4M_SURFACE (``i420`` = planar, anything else or
+    unset = NV12)."""
+    if planar is None:
+        planar = os.getenv("AVD_Y4M_SURFACE", "") == "i420"
     if str(path).endswith(".npy"):
         try:
             return NpySource(path)
@@ -203,7 +216,7 @@ def open_source(path: str) -> Optional[FrameSource]:
             return None
     if str(path).endswith(".y4m"):
         try:
-            return Y4mSource(path)
+            return Y4mSource(path, planar=bool(planar))
         except (OSError, ValueError):
             return None
     try:

@@ -68,3 +68,17 @@ def bgr_to_nv12(frames: np.ndarray):
     uv[..., 0::2] = np.clip(np.rint(sub(u)), 0, 255).astype(np.uint8)
     uv[..., 1::2] = np.clip(np.rint(sub(v)), 0, 255).astype(np.uint8)
     return np.clip(np.rint(y), 0, 255).astype(np.uint8), uv
+
+
+def nv12_to_i420(y: np.ndarray, uv: np.ndarray):
+    """NV12 surfaces (y uint8[...,H,W], uv uint8[...,H/2,W] interleaved U,V) -> planar I420 (y, u, v): u and v uint8[...,H/2,W/2],
+    contiguous copies of the even and odd chroma bytes.  For tests and tools; i420_to_nv12 is the inverse."""
+    return y, np.ascontiguousarray(uv[..., 0::2]), np.ascontiguousarray(uv[..., 1::2])
+
+
+def i420_to_nv12(y: np.ndarray, u: np.ndarray, v: np.ndarray):
+    """Planar I420 -> NV12: the U and V planes interleaved (what Y4mSource does per frame by default)."""
+    uv = np.empty(u.shape[:-1] + (2 * u.shape[-1],), np.uint8)
+    uv[..., 0::2] = u
+    uv[..., 1::2] = v
+    return y, uv

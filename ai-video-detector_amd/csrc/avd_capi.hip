@@ -534,20 +534,29 @@ static void impl_destroy(avd_ctx* ctx)
     delete ctx;
 }
 
-// ---- ingest: one clip = an avd_clip (BGR: uv == nullptr; NV12: data = the Y plane, uv = the interleaved chroma plane) ------------------
-static avd_clip bgr_clip(const uint8_t* bgr, int mem, int n, int h, int w, int64_t row_stride, int64_t frame_stride)
+// ---- ingest: one clip = an IngestClip (BGR: uv == nullptr; NV12: data = the Y plane, uv = the interleaved chroma plane; I420: data = Y,
+// uv = the U plane, v = the V plane) ------------------
+static IngestClip bgr_clip(const uint8_t* bgr, int mem, int n, int h, int w, int64_t row_stride, int64_t frame_stride)
 {
-    avd_clip k{};
+    IngestClip k{};
     k.data = bgr; k.mem = mem; k.n = n; k.h = h; k.w = w;
     k.row_stride = row_stride; k.frame_stride = frame_stride;
     return k;
 }
 
-static avd_clip nv12_clip(const uint8_t* y, const uint8_t* uv, int mem, int n, int h, int w, int64_t y_row, int64_t uv_row, int64_t y_frame,
-                          int64_t uv_frame)
+static IngestClip nv12_clip(const uint8_t* y, const uint8_t* uv, int mem, int n, int h, int w, int64_t y_row, int64_t uv_row, int64_t y_frame,
+                            int64_t uv_frame)
 {
-    avd_clip k = bgr_clip(y, mem, n, h, w, y_row, y_frame);
+    IngestClip k = bgr_clip(y, mem, n, h, w, y_row, y_frame);
     k.uv = uv; k.uv_row_stride = uv_row; k.uv_frame_stride = uv_frame;
+    return k;
+}
+
+static IngestClip i420_clip(const uint8_t* y, const uint8_t* u, const uint8_t* v, int mem, int n, int h, int w, int64_t y_row, int64_t c_row,
+                            int64_t y_frame, int64_t c_frame)
+{
+    IngestClip k = nv12_clip(y, u, mem, n, h, w, y_row, c_row, y_frame, c_frame);
+    k.v = v;
     return k;
 }
 
@@ -565,43 +574,74 @@ static int check_nv12(avd_ctx* ctx, const avd_clip& k)
     return 0;
 }
 
-// Where a HOST clip lands in the staging buffer: BGR as one span; NV12 as the Y span with the chroma span on the next 256-byte
-// boundary behind it.  `total` (a multiple of 256) is what the clip occupies; a device clip is used in place and occupies nothing.
-struct ClipStage { size_t y_bytes, uv_off, uv_bytes, total; };
+static int check_i420(avd_ctx* ctx, const IngestClip& k)
+{
+    const int n = k.n, h = k.h, w = k.w;
+    if (n < 0 || h <= 0 || w <= 0 || h > 16384 || w > 16384) { ctx->err = "bad frame geometry"; return AVD_ERR_ARG; }
+    if ((h | w) & 1) { ctx->err = "I420 needs even width and height"; return AVD_ERR_UNSUPPORTED; }
+    if (h < AVD_HASH || w < AVD_HASH) { ctx->err = "frame smaller than 32x32: INTER_AREA upscaling is not on the path"; return AVD_ERR_UNSUPPORTED; }
+    if ((!k.data || !k.uv || !k.v) && n > 0) { ctx->err = "null I420 plane pointer"; return AVD_ERR_ARG; }
+    if (k.row_stride < w || k.uv_row_stride < w / 2 ||
+        (n > 1 && (k.frame_stride < k.row_stride * (h - 1) + w || k.uv_frame_stride < k.uv_row_stride * (h / 2 - 1) + w / 2))) {
+        ctx->err = "strides smaller than the I420 planes"; return AVD_ERR_ARG;
+    }
+    return 0;
+}
 
-static ClipStage clip_stage(const avd_clip& c)
+// Where a HOST clip lands in the staging buffer: BGR as one span; NV12 as the Y span with the chroma span on the next 256-byte boundary
+// behind it.  The three planes of I420 usually come out of ONE buffer per clip (a y4m map, a rawvideo pipe: Y, U, V of a frame adjacent), where
+// the per-plane spans overlap almost entirely: spans that overlap or touch are merged and copied once, so no host byte crosses the link twice, and
+// a plane sits at its own offset inside the merged span; separately allocated planes stay three spans.  `total` (a multiple of 256) is what
+// the clip occupies, `copied` the bytes that cross the link; a device clip is used in place and occupies nothing.
+struct StageSpan { const uint8_t* src; size_t bytes, off; };       // off: from the clip's place in the staging buffer, a multiple of 256
+struct ClipStage { StageSpan span[3]; int nspans; size_t plane_off[3], total, copied; };      // plane_off: data, uv, v
+
+static ClipStage clip_stage(const IngestClip& c)
 {
     ClipStage s{};
     if (c.mem != AVD_MEM_HOST || c.n <= 0) return s;
-    s.y_bytes = plane_span(c.frame_stride, c.n, c.row_stride, c.h, (size_t)c.w * (c.uv ? 1 : 3));
-    if (c.uv) {
-        s.uv_off = round256(s.y_bytes);
-        s.uv_bytes = plane_span(c.uv_frame_stride, c.n, c.uv_row_stride, c.h / 2, (size_t)c.w);
+    const uint8_t* src[3] = {c.data, c.uv, c.v};
+    const int planes = c.v ? 3 : (c.uv ? 2 : 1);
+    size_t len[3] = {plane_span(c.frame_stride, c.n, c.row_stride, c.h, (size_t)c.w * (c.uv ? 1 : 3)), 0, 0};
+    if (c.uv) len[1] = len[2] = plane_span(c.uv_frame_stride, c.n, c.uv_row_stride, c.h / 2, (size_t)(c.v ? c.w / 2 : c.w));
+    int order[3] = {0, 1, 2};
+    if (c.v) std::sort(order, order + 3, [&](int a, int b) { return (uintptr_t)src[a] < (uintptr_t)src[b]; });
+    for (int i = 0; i < planes; i++) {
+        const int p = order[i];
+        StageSpan* last = s.nspans ? &s.span[s.nspans - 1] : nullptr;
+        if (c.v && last && (uintptr_t)src[p] <= (uintptr_t)last->src + last->bytes)
+            last->bytes = std::max(last->bytes, (size_t)(src[p] - last->src) + len[p]);
+        else {
+            s.span[s.nspans] = StageSpan{src[p], len[p], last ? round256(last->off + last->bytes) : 0};
+            last = &s.span[s.nspans++];
+        }
+        s.plane_off[p] = last->off + (size_t)(src[p] - last->src);
     }
-    s.total = round256(c.uv ? s.uv_off + s.uv_bytes : s.y_bytes);
+    for (int i = 0; i < s.nspans; i++) s.copied += s.span[i].bytes;
+    s.total = round256(s.span[s.nspans - 1].off + s.span[s.nspans - 1].bytes);
     return s;
 }
 
 // Stage clip k at offset `at` of ws.d_stage (host input; reserved by the caller) and launch its fused full-resolution kernel, which
 // writes the clip's slice (ws.f0, ws.rowbuf_off, ws.lappart_off) of the per-frame buffers.  The clip's geometry is current.
-static int preprocess_clip(avd_ctx* ctx, const avd_clip& k, size_t at)
+static int preprocess_clip(avd_ctx* ctx, const IngestClip& k, size_t at)
 {
-    const uint8_t *d_in = k.data, *d_uv = k.uv;
+    const uint8_t *d_in = k.data, *d_uv = k.uv, *d_v = k.v;
     if (k.mem == AVD_MEM_HOST) {
         const ClipStage s = clip_stage(k);
         uint8_t* dst = ctx->ws.d_stage + at;
-        HIP_TRY(ctx, hipMemcpyAsync(dst, k.data, s.y_bytes, hipMemcpyHostToDevice, ctx->stream));
-        d_in = dst;
-        if (k.uv) {
-            HIP_TRY(ctx, hipMemcpyAsync(dst + s.uv_off, k.uv, s.uv_bytes, hipMemcpyHostToDevice, ctx->stream));
-            d_uv = dst + s.uv_off;
-        }
+        for (int i = 0; i < s.nspans; i++)
+            HIP_TRY(ctx, hipMemcpyAsync(dst + s.span[i].off, s.span[i].src, s.span[i].bytes, hipMemcpyHostToDevice, ctx->stream));
+        ctx->stage_bytes += (int64_t)s.copied;
+        d_in = dst + s.plane_off[0];
+        if (k.uv) d_uv = dst + s.plane_off[1];
+        if (k.v) d_v = dst + s.plane_off[2];
     }
-    return launch_preprocess(ctx, k, d_in, d_uv);
+    return launch_preprocess(ctx, k, d_in, d_uv, d_v);
 }
 
-// avd_preprocess_bgr / avd_preprocess_nv12 behind their argument checks: one clip at offset 0 of the buffers, results to the host
-static int preprocess_to_host(avd_ctx* ctx, const avd_clip& k, uint8_t* small320, uint8_t* hash1024, int64_t* lap_sum, int64_t* lap_sumsq)
+// avd_preprocess_bgr / _nv12 / _i420 behind their argument checks: one clip at offset 0 of the buffers, results to the host
+static int preprocess_to_host(avd_ctx* ctx, const IngestClip& k, uint8_t* small320, uint8_t* hash1024, int64_t* lap_sum, int64_t* lap_sumsq)
 {
     const int n = k.n;
     if (n == 0) return AVD_OK;
@@ -610,6 +650,7 @@ static int preprocess_to_host(avd_ctx* ctx, const avd_clip& k, uint8_t* small320
     if (k.mem != AVD_MEM_HOST && k.mem != AVD_MEM_DEVICE) { ctx->err = "mem must be AVD_MEM_HOST or AVD_MEM_DEVICE"; return AVD_ERR_ARG; }
     Workspace& ws = ctx->ws;
     if (int e = ws.d_stage.reserve(ctx, clip_stage(k).total)) return e;
+    ctx->stage_bytes = 0;
     if (int e = preprocess_clip(ctx, k, 0)) return e;
     if (int e = launch_hash(ctx, n)) return e;
     std::vector<unsigned long long> lap((size_t)n * 2);
@@ -636,10 +677,17 @@ static int impl_preprocess_bgr(avd_ctx* ctx, const uint8_t* bgr, int mem, int n,
     return preprocess_to_host(ctx, bgr_clip(bgr, mem, n, h, w, row_stride, frame_stride), small320, hash1024, lap_sum, lap_sumsq);
 }
 
-static int impl_preprocess_nv12(avd_ctx* ctx, const avd_clip& k, uint8_t* small320, uint8_t* hash1024, int64_t* lap_sum, int64_t* lap_sumsq)
+static int impl_preprocess_nv12(avd_ctx* ctx, const IngestClip& k, uint8_t* small320, uint8_t* hash1024, int64_t* lap_sum, int64_t* lap_sumsq)
 {
     if (!ctx) return AVD_ERR_ARG;
     if (int e = check_nv12(ctx, k)) return e;
+    return preprocess_to_host(ctx, k, small320, hash1024, lap_sum, lap_sumsq);
+}
+
+static int impl_preprocess_i420(avd_ctx* ctx, const IngestClip& k, uint8_t* small320, uint8_t* hash1024, int64_t* lap_sum, int64_t* lap_sumsq)
+{
+    if (!ctx) return AVD_ERR_ARG;
+    if (int e = check_i420(ctx, k)) return e;
     return preprocess_to_host(ctx, k, small320, hash1024, lap_sum, lap_sumsq);
 }
 
@@ -669,16 +717,18 @@ static int impl_farneback_pairs(avd_ctx* ctx, const uint8_t* small320, int mem, 
 // stage does not care where a 320 x 320 frame came from: it runs ONCE over all N - 1 consecutive pairs of the concatenation
 // (the one pair per clip boundary it computes in vain is ignored by k_records), so K short clips cost one launch sequence
 // over all their pairs instead of K sequences that each leave most of the chip idle.
-static int impl_analyze_batch_async(avd_ctx* ctx, const avd_clip* clips, int nclips, avd_frame_record* records)
+static int impl_analyze_batch_async(avd_ctx* ctx, const IngestClip* clips, int nclips, avd_frame_record* records)
 {
     if (!ctx) return AVD_ERR_ARG;
     if (nclips < 0 || (nclips > 0 && !clips)) { ctx->err = "bad clip list"; return AVD_ERR_ARG; }
     int64_t total = 0;
     for (int c = 0; c < nclips; c++) {
-        const avd_clip& k = clips[c];
+        const IngestClip& k = clips[c];
         if (k.mem != AVD_MEM_HOST && k.mem != AVD_MEM_DEVICE) { ctx->err = "mem must be AVD_MEM_HOST or AVD_MEM_DEVICE"; return AVD_ERR_ARG; }
         if (!k.data && k.n > 0) { ctx->err = "null frame pointer"; return AVD_ERR_ARG; }
-        if (k.uv) {
+        if (k.v) {
+            if (int e = check_i420(ctx, k)) return e;
+        } else if (k.uv) {
             if (int e = check_nv12(ctx, k)) return e;
         } else if (int e = check_geometry(ctx, k.n, k.h, k.w, k.row_stride, k.frame_stride)) return e;
         total += k.n;
@@ -692,7 +742,7 @@ static int impl_analyze_batch_async(avd_ctx* ctx, const avd_clip* clips, int ncl
     // pass 1: geometry tables (cached) and sizes -- everything is reserved before the first launch of the call
     size_t rowbuf_elems = 0, lappart_elems = 0, stage_bytes = 0;
     for (int c = 0; c < nclips; c++) {
-        const avd_clip& k = clips[c];
+        const IngestClip& k = clips[c];
         if (k.n == 0) continue;
         if (int e = avd_ws_geometry(ctx, k.h, k.w)) return e;
         rowbuf_elems += rowbuf_elems_for(ws, k.n);
@@ -704,13 +754,14 @@ static int impl_analyze_batch_async(avd_ctx* ctx, const avd_clip* clips, int ncl
     if (int e = ws.d_stage.reserve(ctx, stage_bytes)) return e;
     // pass 2: per clip, stage (host input) -> fused full-resolution kernel -> hash, at the clip's offsets
     ctx->kmark_used = 0;
+    ctx->stage_bytes = 0;
     // profiling only: an empty launch in front of the first mark, so that the first region is the first kernel and not the queue's wake-up from idle as well
     if (ctx->profiling) hipLaunchKernelGGL(k_wake, dim3(1), dim3(64), 0, ctx->stream);
     stage_mark(ctx, 0);
     int f0 = 0;
     size_t rb = 0, lp = 0, st = 0;
     for (int c = 0; c < nclips; c++) {
-        const avd_clip& k = clips[c];
+        const IngestClip& k = clips[c];
         if (k.n == 0) continue;
         if (int e = avd_ws_geometry(ctx, k.h, k.w)) return e;       // a cache hit (pass 1 built it) unless > kGeomCache geometries
         ws.f0 = f0; ws.rowbuf_off = rb; ws.lappart_off = lp;
@@ -765,16 +816,34 @@ static int impl_analyze_frames_async(avd_ctx* ctx, const uint8_t* bgr, int mem, 
 {
     if (!ctx) return AVD_ERR_ARG;
     if ((!bgr || !records) && n > 0) { ctx->err = "null pointer"; return AVD_ERR_ARG; }
-    const avd_clip k = bgr_clip(bgr, mem, n, h, w, row_stride, frame_stride);
+    const IngestClip k = bgr_clip(bgr, mem, n, h, w, row_stride, frame_stride);
     return impl_analyze_batch_async(ctx, &k, 1, records);
 }
 
-static int impl_analyze_frames_nv12_async(avd_ctx* ctx, const avd_clip& k, avd_frame_record* records)
+static int impl_analyze_frames_nv12_async(avd_ctx* ctx, const IngestClip& k, avd_frame_record* records)
 {
     if (!ctx) return AVD_ERR_ARG;
     if (!records && k.n > 0) { ctx->err = "null pointer"; return AVD_ERR_ARG; }
     if (int e = check_nv12(ctx, k)) return e;
     return impl_analyze_batch_async(ctx, &k, 1, records);
+}
+
+static int impl_analyze_frames_i420_async(avd_ctx* ctx, const IngestClip& k, avd_frame_record* records)
+{
+    if (!ctx) return AVD_ERR_ARG;
+    if (!records && k.n > 0) { ctx->err = "null pointer"; return AVD_ERR_ARG; }
+    if (int e = check_i420(ctx, k)) return e;
+    return impl_analyze_batch_async(ctx, &k, 1, records);
+}
+
+// The public batch: avd_clip is frozen at ABI 3, so its clips are BGR or NV12; the ingest code takes them as IngestClips without a third plane.
+static int impl_analyze_clips_async(avd_ctx* ctx, const avd_clip* clips, int nclips, avd_frame_record* records)
+{
+    if (!ctx) return AVD_ERR_ARG;
+    if (nclips < 0 || (nclips > 0 && !clips)) { ctx->err = "bad clip list"; return AVD_ERR_ARG; }
+    std::vector<IngestClip> ks((size_t)nclips);
+    for (int c = 0; c < nclips; c++) ks[c] = IngestClip{clips[c], nullptr};
+    return impl_analyze_batch_async(ctx, ks.data(), nclips, records);
 }
 
 static int impl_synchronize(avd_ctx* ctx)
@@ -899,6 +968,12 @@ static int64_t impl_debug_fetch(avd_ctx* ctx, const char* name, void* out, size_
         bytes = std::min(sizeof(IngestPlan), out_bytes);
         std::memcpy(out, &ctx->ingest_plan, bytes);
         return (int64_t)bytes;
+    }
+    if (std::strcmp(name, "stage_bytes") == 0) {       // host state: bytes the last ingest call copied from host memory (0: device input)
+        if (ctx->stage_bytes < 0) { ctx->err = "stage_bytes not recorded yet: no ingest call has run on this context"; return AVD_ERR_ARG; }
+        if (out_bytes < sizeof(int64_t)) { ctx->err = "stage_bytes is int64[1]"; return AVD_ERR_ARG; }
+        std::memcpy(out, &ctx->stage_bytes, sizeof(int64_t));
+        return (int64_t)sizeof(int64_t);
     }
     if (std::strcmp(name, "cnn_plan") == 0) {          // host state: the kernel shape (CnnShape) of each convolution of the last CNN forward
         if (!ctx->cnn_plan_valid) { ctx->err = "cnn_plan not recorded yet: no CNN forward has run on this context"; return AVD_ERR_ARG; }
@@ -1227,13 +1302,13 @@ int avd_synchronize(avd_ctx* ctx) { return guarded(ctx, [&] { return impl_synchr
 
 int avd_analyze_batch_async(avd_ctx* ctx, const avd_clip* clips, int nclips, avd_frame_record* records)
 {
-    return guarded(ctx, [&] { return impl_analyze_batch_async(ctx, clips, nclips, records); });
+    return guarded(ctx, [&] { return impl_analyze_clips_async(ctx, clips, nclips, records); });
 }
 
 int avd_analyze_batch(avd_ctx* ctx, const avd_clip* clips, int nclips, avd_frame_record* records)
 {
     return guarded(ctx, [&] {
-        const int rc = impl_analyze_batch_async(ctx, clips, nclips, records);
+        const int rc = impl_analyze_clips_async(ctx, clips, nclips, records);
         return rc ? rc : impl_synchronize(ctx);
     });
 }
@@ -1242,7 +1317,7 @@ int avd_preprocess_nv12(avd_ctx* ctx, const uint8_t* y, const uint8_t* uv, int m
                         int64_t uv_row_stride, int64_t y_frame_stride, int64_t uv_frame_stride, uint8_t* small320,
                         uint8_t* hash1024, int64_t* lap_sum, int64_t* lap_sumsq)
 {
-    const avd_clip k = nv12_clip(y, uv, mem, n, h, w, y_row_stride, uv_row_stride, y_frame_stride, uv_frame_stride);
+    const IngestClip k = nv12_clip(y, uv, mem, n, h, w, y_row_stride, uv_row_stride, y_frame_stride, uv_frame_stride);
     return guarded(ctx, [&] { return impl_preprocess_nv12(ctx, k, small320, hash1024, lap_sum, lap_sumsq); });
 }
 
@@ -1250,7 +1325,7 @@ int avd_analyze_frames_nv12_async(avd_ctx* ctx, const uint8_t* y, const uint8_t*
                                   int64_t y_row_stride, int64_t uv_row_stride, int64_t y_frame_stride,
                                   int64_t uv_frame_stride, avd_frame_record* records)
 {
-    const avd_clip k = nv12_clip(y, uv, mem, n, h, w, y_row_stride, uv_row_stride, y_frame_stride, uv_frame_stride);
+    const IngestClip k = nv12_clip(y, uv, mem, n, h, w, y_row_stride, uv_row_stride, y_frame_stride, uv_frame_stride);
     return guarded(ctx, [&] { return impl_analyze_frames_nv12_async(ctx, k, records); });
 }
 
@@ -1258,9 +1333,36 @@ int avd_analyze_frames_nv12(avd_ctx* ctx, const uint8_t* y, const uint8_t* uv, i
                             int64_t y_row_stride, int64_t uv_row_stride, int64_t y_frame_stride, int64_t uv_frame_stride,
                             avd_frame_record* records)
 {
-    const avd_clip k = nv12_clip(y, uv, mem, n, h, w, y_row_stride, uv_row_stride, y_frame_stride, uv_frame_stride);
+    const IngestClip k = nv12_clip(y, uv, mem, n, h, w, y_row_stride, uv_row_stride, y_frame_stride, uv_frame_stride);
     return guarded(ctx, [&] {
         const int rc = impl_analyze_frames_nv12_async(ctx, k, records);
+        return rc ? rc : impl_synchronize(ctx);
+    });
+}
+
+int avd_preprocess_i420(avd_ctx* ctx, const uint8_t* y, const uint8_t* u, const uint8_t* v, int mem, int n, int h, int w, int64_t y_row_stride,
+                        int64_t c_row_stride, int64_t y_frame_stride, int64_t c_frame_stride, uint8_t* small320, uint8_t* hash1024,
+                        int64_t* lap_sum, int64_t* lap_sumsq)
+{
+    const IngestClip k = i420_clip(y, u, v, mem, n, h, w, y_row_stride, c_row_stride, y_frame_stride, c_frame_stride);
+    return guarded(ctx, [&] { return impl_preprocess_i420(ctx, k, small320, hash1024, lap_sum, lap_sumsq); });
+}
+
+int avd_analyze_frames_i420_async(avd_ctx* ctx, const uint8_t* y, const uint8_t* u, const uint8_t* v, int mem, int n, int h, int w,
+                                  int64_t y_row_stride, int64_t c_row_stride, int64_t y_frame_stride, int64_t c_frame_stride,
+                                  avd_frame_record* records)
+{
+    const IngestClip k = i420_clip(y, u, v, mem, n, h, w, y_row_stride, c_row_stride, y_frame_stride, c_frame_stride);
+    return guarded(ctx, [&] { return impl_analyze_frames_i420_async(ctx, k, records); });
+}
+
+int avd_analyze_frames_i420(avd_ctx* ctx, const uint8_t* y, const uint8_t* u, const uint8_t* v, int mem, int n, int h, int w,
+                            int64_t y_row_stride, int64_t c_row_stride, int64_t y_frame_stride, int64_t c_frame_stride,
+                            avd_frame_record* records)
+{
+    const IngestClip k = i420_clip(y, u, v, mem, n, h, w, y_row_stride, c_row_stride, y_frame_stride, c_frame_stride);
+    return guarded(ctx, [&] {
+        const int rc = impl_analyze_frames_i420_async(ctx, k, records);
         return rc ? rc : impl_synchronize(ctx);
     });
 }

@@ -63,6 +63,16 @@ struct Nv12Params {
     YuvConsts k;
 };
 
+struct I420Params {
+    const uint8_t *u, *v;              // planar U and V of frame 0, uint8[h/2][w/2] each (YV12: the caller passes them exchanged)
+    int64_t c_row_stride, c_frame_stride;   // shared by the two planes
+    YuvConsts k;
+};
+
+// One clip as the ingest code sees it: the public avd_clip (frozen at ABI 3: BGR, or NV12 with uv set) plus the third plane of planar
+// 4:2:0 input.  v != nullptr: I420 -- data = Y, uv = the U plane, v = the V plane; uv_row_stride / uv_frame_stride hold for both.
+struct IngestClip : avd_clip { const uint8_t* v; };
+
 // ---- device-side parameter blocks ------------------------------------------------
 struct LinTap { short i0, i1, w0, w1; };   // two source indices + 11-bit weights of one output row/column
 
@@ -91,7 +101,7 @@ struct HashParams {
 struct BandPlan { int rows_per_band, pitch, ni; };
 BandPlan band_plan(int w);
 // What launch_preprocess ran last on a context: read by tests through avd_debug_fetch "ingest_plan" (eight int32 in this order).
-enum IngestKernel { kIngestBgrScalar = 0, kIngestBgrVec16, kIngestBgrStaged, kIngestNv12Scalar, kIngestNv12Tables };
+enum IngestKernel { kIngestBgrScalar = 0, kIngestBgrVec16, kIngestBgrStaged, kIngestNv12Scalar, kIngestNv12Tables, kIngestI420Scalar, kIngestI420Tables };
 struct IngestPlan { int h, w, rows_per_band, nbands, pitch, ni, lds_bytes, kernel; };
 static_assert(sizeof(IngestPlan) == 8 * sizeof(int), "avd_debug_fetch hands the struct out as int32[8]");
 // Kernel shape of a CNN convolution launch (avd_cnn.hip), as avd_debug_fetch "cnn_plan" hands it out per convolution: kCnnFolded = no launch
@@ -240,6 +250,7 @@ struct avd_ctx {
     int last_n = 0;
     IngestPlan ingest_plan{};        // the last launch_preprocess of this context (debug buffer "ingest_plan")
     int ingest_plan_valid = 0;       // 0 until the first ingest launch
+    int64_t stage_bytes = -1;        // bytes the last ingest call copied from host memory (debug buffer "stage_bytes"; 0: device input); -1 until the first one
     int rec_n = 0;                   // records the last avd_analyze_* call left in ws.d_rec (0 after any other entry point: avd_allgather_last_records checks it)
     void* comm = nullptr;            // RCCL communicator (avd_comm.cpp), bound at run time
     int comm_rank = 0, comm_world = 1;
@@ -315,8 +326,9 @@ int avd_ws_reserve_frames(avd_ctx* ctx, int n, size_t rowbuf_elems, size_t lappa
 int avd_ws_reserve(avd_ctx* ctx, int n, int h, int w);                 // both, for one clip at offset 0
 int avd_ws_reserve_fb(avd_ctx* ctx, int n);
 // the clip's frames, resident at d_in (BGR, d_uv null) or d_in / d_uv (NV12: Y rows at d_in + f*frame_stride + y*row_stride, chroma rows at
-// d_uv + f*uv_frame_stride + (y/2)*uv_row_stride), into the clip's slice of the per-frame buffers; the clip's geometry is current
-int launch_preprocess(avd_ctx* ctx, const avd_clip& clip, const uint8_t* d_in, const uint8_t* d_uv);
+// d_uv + f*uv_frame_stride + (y/2)*uv_row_stride) or d_in / d_uv / d_v (I420: d_uv is the U plane, both chroma planes with the uv strides),
+// into the clip's slice of the per-frame buffers; the clip's geometry is current
+int launch_preprocess(avd_ctx* ctx, const IngestClip& clip, const uint8_t* d_in, const uint8_t* d_uv, const uint8_t* d_v);
 int launch_hash(avd_ctx* ctx, int n);
 int avd_calls_in_flight();      // avd_capi.hip: contexts of this process holding an enqueued, undrained avd_analyze_* call
 int launch_farneback(avd_ctx* ctx, const uint8_t* d_small, int n);    // all pairs of n resident frames, into the Farneback scratch

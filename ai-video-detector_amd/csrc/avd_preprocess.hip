@@ -546,18 +546,41 @@ __device__ __forceinline__ unsigned gray4_nv12(unsigned yw, unsigned cw, const Y
            (gray_from_yuv((yw >> 16) & 0xFF, t1, k.cy) << 16) | (gray_from_yuv(yw >> 24, t1, k.cy) << 24);
 }
 
-// NV12, any geometry / alignment: one pixel per work item
-__device__ __forceinline__ void fill_nv12_scalar(uint8_t* tile, const uint8_t* yfr, const uint8_t* cfr, const Nv12Params& nv,
-                                                 const PreParams& P, const Band& b, int tid)
+// 4:2:0, any geometry / alignment: one pixel per work item.  chroma(y >> 1, x >> 1, U, V) fetches the pixel's chroma sample: the surface
+// kinds differ in nothing else.
+template <typename ChromaAt>
+__device__ __forceinline__ void fill_yuv420_scalar(uint8_t* tile, const uint8_t* yfr, const YuvConsts& k, const PreParams& P, const Band& b, int tid,
+                                                   ChromaAt chroma)
 {
     const int w = P.w, pitch = P.pitch;
     for (int it = tid; it < b.trows * w; it += kThreads) {
         const int tr = it / w, x = it - tr * w;
         const int y = reflect_once(b.r0 - 1 + tr, P.h);
-        const uint8_t* cp = cfr + (int64_t)(y >> 1) * nv.uv_row_stride + (x >> 1) * 2;
-        const ChromaTerms t = chroma_terms(cp[0], cp[1], nv.k);
-        tile[tr * pitch + kPad + x] = (uint8_t)gray_from_yuv(yfr[(int64_t)y * P.row_stride + x], t, nv.k.cy);
+        int U, V;
+        chroma(y >> 1, x >> 1, U, V);
+        const ChromaTerms t = chroma_terms(U, V, k);
+        tile[tr * pitch + kPad + x] = (uint8_t)gray_from_yuv(yfr[(int64_t)y * P.row_stride + x], t, k.cy);
     }
+}
+
+// NV12: U, V interleaved in one plane
+__device__ __forceinline__ void fill_nv12_scalar(uint8_t* tile, const uint8_t* yfr, const uint8_t* cfr, const Nv12Params& nv,
+                                                 const PreParams& P, const Band& b, int tid)
+{
+    fill_yuv420_scalar(tile, yfr, nv.k, P, b, tid, [&](int cy, int cx, int& U, int& V) {
+        const uint8_t* cp = cfr + (int64_t)cy * nv.uv_row_stride + cx * 2;
+        U = cp[0]; V = cp[1];
+    });
+}
+
+// I420: U from u + (y>>1)*c_row_stride + (x>>1), V likewise
+__device__ __forceinline__ void fill_i420_scalar(uint8_t* tile, const uint8_t* yfr, const uint8_t* ufr, const uint8_t* vfr, const I420Params& ip,
+                                                 const PreParams& P, const Band& b, int tid)
+{
+    fill_yuv420_scalar(tile, yfr, ip.k, P, b, tid, [&](int cy, int cx, int& U, int& V) {
+        const int64_t o = (int64_t)cy * ip.c_row_stride + cx;
+        U = ufr[o]; V = vfr[o];
+    });
 }
 
 // NV12, 16-byte aligned planes of w % 16 == 0 pixels.
@@ -565,15 +588,17 @@ __device__ __forceinline__ void fill_nv12_scalar(uint8_t* tile, const uint8_t* y
 // Three LDS tables of cv2's gray weight times T (3735 T, 19235 T + the rounding 2^14, 9798 T; 32-bit entries, index bias kNvBias), so a pixel is
 // three index additions, three ds_read_b32, one three-operand add and a shift -- instead of three multiply-adds, three shifts, three clamps and
 // three multiply-adds (12.3 -> 8.8 vector instructions per pixel; the LDS pipe does the lookups beside them).  Same integers by construction.
-__device__ __forceinline__ void fill_nv12_tables(uint8_t* tile, const uint8_t* yfr, const uint8_t* cfr, const Nv12Params& nv,
-                                                 const PreParams& P, const Band& b, int tid)
+// chroma8(p, c, t) forms the eight chroma-term triples of chroma row p, 16-pixel chunk c: the surface kinds differ in nothing else.
+template <typename Chroma8>
+__device__ __forceinline__ void fill_yuv420_tables(uint8_t* tile, const uint8_t* yfr, const YuvConsts& k, const PreParams& P, const Band& b, int tid,
+                                                   Chroma8 chroma8)
 {
     const int h = P.h, pitch = P.pitch, r0 = b.r0, rows = b.rows, trows = b.trows;
     unsigned* const tabB = reinterpret_cast<unsigned*>(tile + lds_nvtab_off(trows, pitch));
     unsigned* const tabG = tabB + kNvTab;
     unsigned* const tabR = tabG + kNvTab;
     for (int i = tid; i < kNvTab; i += kThreads) {
-        const unsigned v = (unsigned)clip8((nv.k.c0 + (i - kNvBias) * nv.k.cy) >> 16);
+        const unsigned v = (unsigned)clip8((k.c0 + (i - kNvBias) * k.cy) >> 16);
         tabB[i] = v * 3735u; tabG[i] = v * 19235u + (1u << 14); tabR[i] = v * 9798u;
     }
     __syncthreads();
@@ -585,14 +610,8 @@ __device__ __forceinline__ void fill_nv12_tables(uint8_t* tile, const uint8_t* y
     const int chunks = P.w >> 4;
     for (int it = tid; it < np * chunks; it += kThreads) {
         const int pr = it / chunks, c = it - pr * chunks, p = p0 + pr;
-        const uint4 cc = *reinterpret_cast<const uint4*>(cfr + (int64_t)p * nv.uv_row_stride + c * 16);
-        const unsigned cw[4] = {cc.x, cc.y, cc.z, cc.w};
         ChromaTerms t[8];
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            t[2 * j] = chroma_offsets(cw[j] & 0xFF, (cw[j] >> 8) & 0xFF, nv.k);
-            t[2 * j + 1] = chroma_offsets((cw[j] >> 16) & 0xFF, cw[j] >> 24, nv.k);
-        }
+        chroma8(p, c, t);
 #pragma unroll
         for (int s2 = 0; s2 < 2; s2++) {
             const int y = 2 * p + s2;
@@ -618,6 +637,36 @@ __device__ __forceinline__ void fill_nv12_tables(uint8_t* tile, const uint8_t* y
                 *reinterpret_cast<const uint4*>(tile + (trows - 3) * pitch + kPad + c * 16);
 }
 
+// NV12: the 16 chroma bytes of a chunk are one 16-byte load, pair j = bytes 2j (U) and 2j + 1 (V)
+__device__ __forceinline__ void fill_nv12_tables(uint8_t* tile, const uint8_t* yfr, const uint8_t* cfr, const Nv12Params& nv,
+                                                 const PreParams& P, const Band& b, int tid)
+{
+    fill_yuv420_tables(tile, yfr, nv.k, P, b, tid, [&](int p, int c, ChromaTerms (&t)[8]) {
+        const uint4 cc = *reinterpret_cast<const uint4*>(cfr + (int64_t)p * nv.uv_row_stride + c * 16);
+        const unsigned cw[4] = {cc.x, cc.y, cc.z, cc.w};
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            t[2 * j] = chroma_offsets(cw[j] & 0xFF, (cw[j] >> 8) & 0xFF, nv.k);
+            t[2 * j + 1] = chroma_offsets((cw[j] >> 16) & 0xFF, cw[j] >> 24, nv.k);
+        }
+    });
+}
+
+// I420, Y plane 16-byte aligned, U and V planes 8-byte aligned: the 16 chroma bytes of a chunk are two 8-byte loads, 8 U and 8 V; pair j = U byte j
+// and V byte j.  (A contiguous frame has its V plane at 5wh/4, which w % 16 == 0 makes a multiple of 8 but not of 16.)
+__device__ __forceinline__ void fill_i420_tables(uint8_t* tile, const uint8_t* yfr, const uint8_t* ufr, const uint8_t* vfr, const I420Params& ip,
+                                                 const PreParams& P, const Band& b, int tid)
+{
+    fill_yuv420_tables(tile, yfr, ip.k, P, b, tid, [&](int p, int c, ChromaTerms (&t)[8]) {
+        const int64_t o = (int64_t)p * ip.c_row_stride + c * 8;
+        const uint2 uu = *reinterpret_cast<const uint2*>(ufr + o), vv = *reinterpret_cast<const uint2*>(vfr + o);
+        const unsigned uw[2] = {uu.x, uu.y}, vw[2] = {vv.x, vv.y};
+#pragma unroll
+        for (int j = 0; j < 8; j++)
+            t[j] = chroma_offsets((uw[j >> 2] >> (8 * (j & 3))) & 0xFF, (vw[j >> 2] >> (8 * (j & 3))) & 0xFF, ip.k);
+    });
+}
+
 template <bool VEC>
 __global__ __launch_bounds__(kThreads) void k_preprocess_nv12(const uint8_t* __restrict__ yplane, Nv12Params nv, int n,
                                                              PreParams P, uint8_t* __restrict__ small,
@@ -631,6 +680,25 @@ __global__ __launch_bounds__(kThreads) void k_preprocess_nv12(const uint8_t* __r
     const uint8_t* cfr = nv.uv + (int64_t)b.f * nv.uv_frame_stride;
     if (VEC) fill_nv12_tables(tile, yfr, cfr, nv, P, b, tid);
     else fill_nv12_scalar(tile, yfr, cfr, nv, P, b, tid);
+    fill_column_halo(tile, b.trows, P.pitch, P.w, tid);
+    store_moments(lap_part, b.lid, tid, band_phases<false>(tile, nullptr, P, b, tid, small, rowbuf));
+}
+
+// Planar 4:2:0 (I420; YV12 with the chroma pointers exchanged): k_preprocess_nv12 with the chroma fetched from two planes
+template <bool VEC>
+__global__ __launch_bounds__(kThreads) void k_preprocess_i420(const uint8_t* __restrict__ yplane, I420Params ip, int n,
+                                                             PreParams P, uint8_t* __restrict__ small,
+                                                             float* __restrict__ rowbuf, long long* __restrict__ lap_part)
+{
+    extern __shared__ __align__(16) uint8_t tile[];
+    Band b;
+    if (!decode_band(P, n, b)) return;
+    const int tid = threadIdx.x;
+    const uint8_t* yfr = yplane + (int64_t)b.f * P.frame_stride;
+    const uint8_t* ufr = ip.u + (int64_t)b.f * ip.c_frame_stride;
+    const uint8_t* vfr = ip.v + (int64_t)b.f * ip.c_frame_stride;
+    if (VEC) fill_i420_tables(tile, yfr, ufr, vfr, ip, P, b, tid);
+    else fill_i420_scalar(tile, yfr, ufr, vfr, ip, P, b, tid);
     fill_column_halo(tile, b.trows, P.pitch, P.w, tid);
     store_moments(lap_part, b.lid, tid, band_phases<false>(tile, nullptr, P, b, tid, small, rowbuf));
 }
@@ -731,12 +799,13 @@ BandPlan band_plan(int w)
     return p;
 }
 
-static bool aligned16(const void* p, int64_t row_stride, int64_t frame_stride)
+static bool aligned_to(int a, const void* p, int64_t row_stride, int64_t frame_stride)
 {
-    return reinterpret_cast<uintptr_t>(p) % 16 == 0 && row_stride % 16 == 0 && frame_stride % 16 == 0;
+    return reinterpret_cast<uintptr_t>(p) % a == 0 && row_stride % a == 0 && frame_stride % a == 0;
 }
+static bool aligned16(const void* p, int64_t row_stride, int64_t frame_stride) { return aligned_to(16, p, row_stride, frame_stride); }
 
-int launch_preprocess(avd_ctx* ctx, const avd_clip& clip, const uint8_t* d_in, const uint8_t* d_uv)
+int launch_preprocess(avd_ctx* ctx, const IngestClip& clip, const uint8_t* d_in, const uint8_t* d_uv, const uint8_t* d_v)
 {
     Workspace& ws = ctx->ws;
     PreParams P = ws.pre;
@@ -745,8 +814,10 @@ int launch_preprocess(avd_ctx* ctx, const avd_clip& clip, const uint8_t* d_in, c
     const int n = clip.n;
     const int grid = (n * P.nbands + 7) / 8 * 8;
     const size_t tile = lds_tile_bytes(P.rows_per_band + 2, P.pitch);
-    const bool vec = P.w % 16 == 0 && aligned16(d_in, clip.row_stride, clip.frame_stride) &&
-                     (!d_uv || aligned16(d_uv, clip.uv_row_stride, clip.uv_frame_stride));
+    // the planar chroma planes are read 8 bytes at a time (fill_i420_tables), every other plane 16
+    const bool chroma_ok = d_v ? aligned_to(8, d_uv, clip.uv_row_stride, clip.uv_frame_stride) && aligned_to(8, d_v, clip.uv_row_stride, clip.uv_frame_stride)
+                               : !d_uv || aligned16(d_uv, clip.uv_row_stride, clip.uv_frame_stride);
+    const bool vec = P.w % 16 == 0 && aligned16(d_in, clip.row_stride, clip.frame_stride) && chroma_ok;
     const int ni = vec && !d_uv ? band_plan(P.w).ni : 0;
     auto launch = [&](IngestKernel id, auto kernel, size_t lds, auto... source) {
         ctx->ingest_plan = IngestPlan{P.h, P.w, P.rows_per_band, P.nbands, P.pitch, ni, (int)lds, id};
@@ -754,7 +825,13 @@ int launch_preprocess(avd_ctx* ctx, const avd_clip& clip, const uint8_t* d_in, c
         hipLaunchKernelGGL(kernel, dim3(grid), dim3(kThreads), lds, ctx->stream, source..., n, P, ws.d_small + (size_t)ws.f0 * AVD_NPIX,
                            ws.d_rowbuf + ws.rowbuf_off, ws.d_lap_part + ws.lappart_off);
     };
-    if (d_uv) {
+    if (d_v) {
+        I420Params ip{};
+        ip.u = d_uv; ip.v = d_v; ip.c_row_stride = clip.uv_row_stride; ip.c_frame_stride = clip.uv_frame_stride;
+        build_yuv_consts(ip.k);
+        if (vec) launch(kIngestI420Tables, k_preprocess_i420<true>, lds_nvtab_off(P.rows_per_band + 2, P.pitch) + kNvTabBytes, d_in, ip);
+        else launch(kIngestI420Scalar, k_preprocess_i420<false>, tile, d_in, ip);
+    } else if (d_uv) {
         Nv12Params nv{};
         nv.uv = d_uv; nv.uv_row_stride = clip.uv_row_stride; nv.uv_frame_stride = clip.uv_frame_stride;
         build_yuv_consts(nv.k);

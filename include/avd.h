@@ -105,7 +105,9 @@ int avd_analyze_frames(avd_ctx* ctx, const uint8_t* bgr, int mem, int n, int h, 
  * keep clips in flight on one GPU.  One call may be outstanding per context: any
  * other call on the context first completes it -- its records buffer is filled and
  * the re-run of its flagged pairs (fb_mode 1) is settled -- and returns its error
- * instead of running if it failed.  Exempt: avd_synchronize, avd_destroy,
+ * instead of running if it failed.  The same holds for avd_analyze_frames_nv12_async,
+ * avd_analyze_frames_i420_async and avd_analyze_batch_async: whichever of them is
+ * outstanding is drained by any other call, these included.  Exempt: avd_synchronize, avd_destroy,
  * avd_last_error, avd_get_option, avd_stage_ms, avd_kernel_ms, avd_timer_start /
  * avd_timer_stop and avd_wait_stream.  An option set while a call is pending applies
  * to the calls submitted after it; "rerun_pairs" reports the last call that ran the
@@ -126,7 +128,8 @@ int avd_synchronize(avd_ctx* ctx);
  * A clip is BGR (uv == NULL: data = frames, row_stride / frame_stride in bytes) or NV12 (data = Y plane, uv = interleaved
  * chroma plane, the four strides as for avd_analyze_frames_nv12).  records: host, sum of clips[i].n entries, clip after
  * clip; the first record of every clip has ham = -1 and flow 0 (video.py:37-41, 55).  Results are identical to calling
- * avd_analyze_frames per clip. */
+ * avd_analyze_frames per clip.  avd_clip is frozen at ABI 3 and has no room for a third plane: a batch holds BGR and NV12
+ * clips only; planar I420 clips (avd_analyze_frames_i420) wait for the next ABI revision. */
 typedef struct avd_clip {
     const uint8_t* data;
     const uint8_t* uv;
@@ -155,6 +158,26 @@ int avd_analyze_frames_nv12(avd_ctx* ctx, const uint8_t* y, const uint8_t* uv, i
 int avd_analyze_frames_nv12_async(avd_ctx* ctx, const uint8_t* y, const uint8_t* uv, int mem, int n, int h, int w,
                                   int64_t y_row_stride, int64_t uv_row_stride, int64_t y_frame_stride,
                                   int64_t uv_frame_stride, avd_frame_record* records);
+
+/* Planar 4:2:0 input (I420, ffmpeg's yuv420p): what SOFTWARE decoders hand over -- libavcodec behind cv2.VideoCapture (the reference's
+ * own source), a .y4m file, an `ffmpeg -f rawvideo -pix_fmt yuv420p` pipe, PyAV frames.  A Y plane uint8[h][w] and separate U and V planes
+ * uint8[h/2][w/2], per frame at y + f*y_frame_stride + row*y_row_stride, u + f*c_frame_stride + (row/2)*c_row_stride and v likewise (the
+ * two chroma planes share their strides).  YV12 (V stored before U) is the same call with the u and v pointers exchanged.  The arithmetic
+ * is the NV12 entry points': results equal avd_*_nv12 on the interleaved form of the same planes bit for bit, hence avd_analyze_frames on
+ * avdo_nv12_to_bgr24's BGR frames.  Width and height must be even (AVD_ERR_UNSUPPORTED otherwise, as for frames below 32 x 32); null
+ * planes, strides smaller than the planes and sizes above 16384 are AVD_ERR_ARG.  With AVD_MEM_HOST input the three per-plane spans are
+ * merged where they overlap or touch before they are staged: planes that come out of one buffer per clip (Y, U, V of a frame adjacent)
+ * cross the link once, as ONE copy; separately allocated planes are three copies (avd_debug_fetch "stage_bytes").
+ * avd_analyze_frames_i420_async follows avd_analyze_frames_async: one call outstanding per context, drained by any other call. */
+int avd_preprocess_i420(avd_ctx* ctx, const uint8_t* y, const uint8_t* u, const uint8_t* v, int mem, int n, int h, int w,
+                        int64_t y_row_stride, int64_t c_row_stride, int64_t y_frame_stride, int64_t c_frame_stride,
+                        uint8_t* small320, uint8_t* hash1024, int64_t* lap_sum, int64_t* lap_sumsq);
+int avd_analyze_frames_i420(avd_ctx* ctx, const uint8_t* y, const uint8_t* u, const uint8_t* v, int mem, int n, int h, int w,
+                            int64_t y_row_stride, int64_t c_row_stride, int64_t y_frame_stride, int64_t c_frame_stride,
+                            avd_frame_record* records);
+int avd_analyze_frames_i420_async(avd_ctx* ctx, const uint8_t* y, const uint8_t* u, const uint8_t* v, int mem, int n, int h, int w,
+                                  int64_t y_row_stride, int64_t c_row_stride, int64_t y_frame_stride, int64_t c_frame_stride,
+                                  avd_frame_record* records);
 
 /* ViT-B/16 patch embedding on the matrix cores -- a BUILD-DEFINED EXTENSION.  The reference
  * contains no learned model (its per-frame "model" is the closed form of app/analyzers/video.py:54-56); BASELINE.json's
@@ -326,7 +349,7 @@ int avd_stage_ms(avd_ctx* ctx, int stage, float* ms);
  * iteration).  bench.py's roofline.kernels is built from these, with clips run alone.  A call with more kernel regions than the library
  * records (96: ~40 clips in one batch) makes avd_kernel_ms fail rather than report partial sums. */
 enum avd_kernel_id {
-    AVD_K_PREPROCESS = 0,  /* k_preprocess_vec / k_preprocess_nv12 (+ staging copies of host input) */
+    AVD_K_PREPROCESS = 0,  /* k_preprocess_vec / k_preprocess_nv12 / k_preprocess_i420 (+ staging copies of host input) */
     AVD_K_HASH,            /* k_hash: 32 x 32 INTER_AREA cells, mean threshold, moment reduction */
     AVD_K_PYRAMID,         /* k_pyramid_all: Gaussian blur + decimation, four scales */
     AVD_K_POLYEXP,         /* k_polyexp_all: polynomial expansion, four scales */
@@ -344,7 +367,10 @@ int avd_kernel_ms(avd_ctx* ctx, int kernel_id, float* ms);
  * "flow<L>" float[n-1][2][hL][wL] (planar, after the last iteration at level L).
  * "ingest_plan" int32[8], host state rather than a device buffer: what the last ingest launch of the context ran --
  * h, w, rows_per_band, nbands, LDS tile pitch, NI of k_preprocess_vec (0: another kernel), dynamic LDS bytes requested,
- * kernel (0 bgr_scalar, 1 bgr_vec16, 2 bgr_staged, 3 nv12_scalar, 4 nv12_tables); an error before any ingest launch.
+ * kernel (0 bgr_scalar, 1 bgr_vec16, 2 bgr_staged, 3 nv12_scalar, 4 nv12_tables, 5 i420_scalar, 6 i420_tables); an error before any
+ * ingest launch.
+ * "stage_bytes" int64[1], host state: the bytes the last ingest call of the context (avd_preprocess_*, avd_analyze_*) copied from host
+ * memory into its staging buffer -- 0 for device input, the sum over the clips of a batch; an error before any ingest call.
  * "cnn_tap": what option "cnn_tap" made the last avd_cnn_forward copy aside -- 1: uint16[n][232][232][4] bf16 bits; 2 + i and 55: the activation as
  * plain NHWC bf16 bits, uint16[n][H][W][C]; 56: float[n][2048].  out_bytes must be exactly the tap's size.  An error, never stale bytes, when the last
  * forward was not tapped, when none of its launches has that output (the 3x3 of a fused block while "cnn_fuse" != 0), or when the size differs.
