@@ -42,6 +42,8 @@ def analyze(path: str, meta: dict):
         seen = {}
 
         surface = getattr(src, "surface", "bgr")             # "nv12" / "i420": decoder pictures, the colour conversion happens on the GPU
+        # stored pictures with a display rotation (src.width / src.height are the displayed picture's): the turn happens on the GPU too
+        turn = {"rotate": int(src.rotate)} if getattr(src, "rotate", 0) else {}
 
         def frames():
             for fr in src.sampled(step):
@@ -53,9 +55,9 @@ def analyze(path: str, meta: dict):
         with _analyzer.default_pool().borrow(device) as ctx:
             fa = _analyzer.FrameAnalyzer(chunk=chunk, ctx=ctx)
             if surface == "nv12":
-                rec = fa.records_stream_nv12(frames())
+                rec = fa.records_stream_nv12(frames(), **turn)
             elif surface == "i420":
-                rec = fa.records_stream_i420(frames())
+                rec = fa.records_stream_i420(frames(), **turn)
             else:
                 rec = fa.records_stream(frames())
     finally:

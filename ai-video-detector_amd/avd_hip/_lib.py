@@ -27,6 +27,7 @@ EXPORTS = (
     "avd_wait_stream", "avd_release_workspace",
     "avd_preprocess_nv12", "avd_analyze_frames_nv12", "avd_analyze_frames_nv12_async",
     "avd_preprocess_i420", "avd_analyze_frames_i420", "avd_analyze_frames_i420_async",
+    "avd_preprocess_picture", "avd_analyze_pictures", "avd_analyze_pictures_async",
     "avd_vit_set_weights", "avd_vit_patch_embed", "avd_audio_features", "avd_layernorm", "avd_softmax",
     "avd_cnn_param_counts", "avd_cnn_set_weights", "avd_cnn_forward", "avd_cnn_conv",
     "avd_comm_unique_id", "avd_comm_init", "avd_allgather_records", "avd_allgather_last_records",
@@ -57,6 +58,17 @@ class AvdClip(C.Structure):
     """struct avd_clip (include/avd.h): one clip of a batch, BGR (uv = NULL) or NV12."""
     _fields_ = [("data", C.c_void_p), ("uv", C.c_void_p), ("mem", C.c_int), ("n", C.c_int), ("h", C.c_int), ("w", C.c_int),
                 ("row_stride", C.c_int64), ("frame_stride", C.c_int64), ("uv_row_stride", C.c_int64), ("uv_frame_stride", C.c_int64)]
+
+
+AVD_FMT_BGR24, AVD_FMT_NV12, AVD_FMT_I420 = 0, 1, 2
+
+
+class AvdPicture(C.Structure):
+    """struct avd_picture (include/avd.h): one clip by descriptor -- BGR, NV12 or I420 planes of the STORED picture and the quarter turns
+    (clockwise) that make it the displayed one."""
+    _fields_ = [("struct_size", C.c_uint32), ("format", C.c_int32), ("plane", C.c_void_p * 3), ("row_stride", C.c_int64 * 3),
+                ("frame_stride", C.c_int64 * 3), ("mem", C.c_int32), ("n", C.c_int32), ("h", C.c_int32), ("w", C.c_int32),
+                ("rotate", C.c_int32), ("reserved", C.c_int32)]
 
 
 class AvdError(RuntimeError):
@@ -126,6 +138,9 @@ def load() -> C.CDLL:
     L.avd_preprocess_i420.argtypes = i420 + [u8p, u8p, i64p, i64p]
     L.avd_analyze_frames_i420.argtypes = i420 + [vp]
     L.avd_analyze_frames_i420_async.argtypes = i420 + [vp]
+    L.avd_preprocess_picture.argtypes = [vp, vp, u8p, u8p, i64p, i64p]
+    L.avd_analyze_pictures.argtypes = [vp, vp, C.c_int, vp]
+    L.avd_analyze_pictures_async.argtypes = [vp, vp, C.c_int, vp]
     L.avd_vit_set_weights.argtypes = [vp, vp, vp]
     L.avd_vit_patch_embed.argtypes = [vp, u8p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, vp, C.c_int, C.c_int, C.c_int,
                                       C.POINTER(C.c_float)]
@@ -293,7 +308,10 @@ class Context:
             raise ValueError(f"chroma plane must be uint8[{n},{h // 2},{w}] (interleaved U,V), got {tuple(uv.shape)}")
         return ptrs + (mem, n, h, w) + strides + ((y, uv),)
 
-    def preprocess_nv12(self, y, uv):
+    def preprocess_nv12(self, y, uv, rotate: int = 0):
+        """rotate: quarter turns clockwise from the stored planes to the displayed picture (avd_picture); 0 = today's call."""
+        if rotate:
+            return self.preprocess_picture((y, uv), rotate)
         yp, cp, mem, n, h, w, yr, cr, yf, cf, keep = self._nv12_ptrs(y, uv)
         small = np.empty((n, SMALL, SMALL), np.uint8)
         hsh = np.empty((n, HASH * HASH), np.uint8)
@@ -303,13 +321,17 @@ class Context:
                                                 hsh.ctypes.data, s.ctypes.data, q.ctypes.data))
         return small, hsh, s, q
 
-    def analyze_frames_nv12(self, y, uv) -> np.ndarray:
+    def analyze_frames_nv12(self, y, uv, rotate: int = 0) -> np.ndarray:
+        if rotate:
+            return self.analyze_pictures([(y, uv)], [rotate])[0]
         yp, cp, mem, n, h, w, yr, cr, yf, cf, keep = self._nv12_ptrs(y, uv)
         rec = np.zeros(n, RECORD_DTYPE)
         self._check(self._L.avd_analyze_frames_nv12(self._h, yp, cp, mem, n, h, w, yr, cr, yf, cf, rec.ctypes.data))
         return rec
 
-    def analyze_frames_nv12_async(self, y, uv, rec: np.ndarray):
+    def analyze_frames_nv12_async(self, y, uv, rec: np.ndarray, rotate: int = 0):
+        if rotate:
+            return self.analyze_pictures_async([(y, uv)], rec, [rotate])[0][0]
         yp, cp, mem, n, h, w, yr, cr, yf, cf, keep = self._nv12_ptrs(y, uv)
         assert rec.dtype == RECORD_DTYPE and rec.size >= n and rec.flags.c_contiguous
         self._check(self._L.avd_analyze_frames_nv12_async(self._h, yp, cp, mem, n, h, w, yr, cr, yf, cf, rec.ctypes.data))
@@ -348,7 +370,9 @@ class Context:
         (yr, yf), (cr, cf) = st(y), st(u)
         return ptr(y), ptr(u), ptr(v), (AVD_MEM_DEVICE if cuda else AVD_MEM_HOST), n, h, w, yr, cr, yf, cf, (y, u, v)
 
-    def preprocess_i420(self, y, u, v):
+    def preprocess_i420(self, y, u, v, rotate: int = 0):
+        if rotate:
+            return self.preprocess_picture((y, u, v), rotate)
         yp, up, vp, mem, n, h, w, yr, cr, yf, cf, keep = self._i420_ptrs(y, u, v)
         small = np.empty((n, SMALL, SMALL), np.uint8)
         hsh = np.empty((n, HASH * HASH), np.uint8)
@@ -358,17 +382,87 @@ class Context:
                                                 hsh.ctypes.data, s.ctypes.data, q.ctypes.data))
         return small, hsh, s, q
 
-    def analyze_frames_i420(self, y, u, v) -> np.ndarray:
+    def analyze_frames_i420(self, y, u, v, rotate: int = 0) -> np.ndarray:
+        if rotate:
+            return self.analyze_pictures([(y, u, v)], [rotate])[0]
         yp, up, vp, mem, n, h, w, yr, cr, yf, cf, keep = self._i420_ptrs(y, u, v)
         rec = np.zeros(n, RECORD_DTYPE)
         self._check(self._L.avd_analyze_frames_i420(self._h, yp, up, vp, mem, n, h, w, yr, cr, yf, cf, rec.ctypes.data))
         return rec
 
-    def analyze_frames_i420_async(self, y, u, v, rec: np.ndarray):
+    def analyze_frames_i420_async(self, y, u, v, rec: np.ndarray, rotate: int = 0):
+        if rotate:
+            return self.analyze_pictures_async([(y, u, v)], rec, [rotate])[0][0]
         yp, up, vp, mem, n, h, w, yr, cr, yf, cf, keep = self._i420_ptrs(y, u, v)
         assert rec.dtype == RECORD_DTYPE and rec.size >= n and rec.flags.c_contiguous
         self._check(self._L.avd_analyze_frames_i420_async(self._h, yp, up, vp, mem, n, h, w, yr, cr, yf, cf, rec.ctypes.data))
         return keep
+
+    # -- pictures by descriptor (include/avd.h: avd_picture): any format, with a display rotation -------------------------------------------
+    def _picture(self, clip, rotate: int = 0):
+        """clip: a BGR frame stack uint8[N,H,W,3], an NV12 pair (y, uv) or an I420 triple (y, u, v) of the STORED picture; numpy or torch.
+        -> (AvdPicture, frame count, keepalive).  The binding's own checks (the rotation, U and V of equal strides, planes all numpy or all
+        torch) are made before the library is touched."""
+        if isinstance(rotate, bool) or not isinstance(rotate, (int, np.integer)) or not 0 <= rotate <= 3:
+            raise ValueError(f"rotate must be 0, 1, 2 or 3 quarter turns (clockwise, stored to displayed picture), got {rotate!r}")
+        p = AvdPicture()
+        p.struct_size, p.rotate, p.reserved = C.sizeof(AvdPicture), int(rotate), 0
+        if isinstance(clip, tuple) and len(clip) == 3:
+            yp, up, vp, mem, n, h, w, yr, cr, yf, cf, keep = self._i420_ptrs(*clip)
+            p.format, planes, rows, frames = AVD_FMT_I420, (yp, up, vp), (yr, cr, cr), (yf, cf, cf)
+        elif isinstance(clip, tuple) and len(clip) == 2:
+            yp, cp, mem, n, h, w, yr, cr, yf, cf, keep = self._nv12_ptrs(*clip)
+            p.format, planes, rows, frames = AVD_FMT_NV12, (yp, cp, None), (yr, cr, 0), (yf, cf, 0)
+        elif isinstance(clip, tuple):
+            raise ValueError("a clip is a BGR frame stack, an NV12 pair (y, uv) or an I420 triple (y, u, v)")
+        else:
+            ptr, mem, n, h, w, rs, fs, keep = self._frames_ptr(clip)
+            p.format, planes, rows, frames = AVD_FMT_BGR24, (ptr, None, None), (rs, 0, 0), (fs, 0, 0)
+        for i in range(3):
+            p.plane[i], p.row_stride[i], p.frame_stride[i] = planes[i], rows[i], frames[i]
+        p.mem, p.n, p.h, p.w = mem, n, h, w
+        return p, int(n), keep
+
+    def preprocess_picture(self, clip, rotate: int = 0):
+        """-> (small320, hash1024, lap_sum, lap_sumsq) of the DISPLAYED picture, as preprocess_bgr / _nv12 / _i420 on the turned planes."""
+        p, n, keep = self._picture(clip, rotate)
+        small = np.empty((n, SMALL, SMALL), np.uint8)
+        hsh = np.empty((n, HASH * HASH), np.uint8)
+        s = np.empty(n, np.int64)
+        q = np.empty(n, np.int64)
+        self._check(self._L.avd_preprocess_picture(self._h, C.byref(p), small.ctypes.data, hsh.ctypes.data, s.ctypes.data, q.ctypes.data))
+        return small, hsh, s, q
+
+    def _picture_array(self, clips, rotates):
+        rotates = [0] * len(clips) if rotates is None else list(rotates)
+        if len(rotates) != len(clips):
+            raise ValueError("one rotation per clip")
+        arr = (AvdPicture * len(clips))()
+        keep, counts = [], []
+        for i, (c, r) in enumerate(zip(clips, rotates)):
+            arr[i], n, k = self._picture(c, r)
+            keep.append(k)
+            counts.append(n)
+        return arr, counts, keep
+
+    def analyze_pictures(self, clips, rotates=None):
+        """A batch by descriptor: BGR stacks, NV12 pairs and I420 triples in any mix, each with its rotation (default 0).
+        -> list of record arrays, one per clip, identical to one call per clip."""
+        arr, counts, keep = self._picture_array(clips, rotates)
+        rec = np.zeros(sum(counts), RECORD_DTYPE)
+        self._check(self._L.avd_analyze_pictures(self._h, arr, len(clips), rec.ctypes.data))
+        return list(np.split(rec, np.cumsum(counts)[:-1])) if counts else []
+
+    def analyze_pictures_async(self, clips, rec: np.ndarray, rotates=None):
+        """Enqueue only; rec (RECORD_DTYPE, sum of the clips' frames) is filled by synchronize().  Returns (keepalive, frame counts)."""
+        arr, counts, keep = self._picture_array(clips, rotates)
+        assert rec.dtype == RECORD_DTYPE and rec.size >= sum(counts) and rec.flags.c_contiguous
+        self._check(self._L.avd_analyze_pictures_async(self._h, arr, len(clips), rec.ctypes.data))
+        return keep, counts
+
+    def ingest_rotate(self) -> int:
+        """The rotation the last ingest launch of this context ran with; avd_debug_fetch "ingest_rotate"."""
+        return int(self.debug_fetch("ingest_rotate", (1,), np.int32)[0])
 
     def stage_bytes(self) -> int:
         """Bytes the last ingest call of this context copied from host memory (0: device input); avd_debug_fetch "stage_bytes"."""

@@ -204,41 +204,42 @@ class FrameAnalyzer:
         return rec[1:] if carry is not None else rec
 
     # -- the same for decoder surfaces: an iterable of (y uint8[H,W], uv uint8[H/2,W]) pairs ----------------
-    def records_stream_nv12(self, surfaces) -> np.ndarray:
+    # rotate: quarter turns clockwise from the stored pictures to the displayed one (a container's display rotation; include/avd.h, avd_picture)
+    def records_stream_nv12(self, surfaces, rotate: int = 0) -> np.ndarray:
         out = []
         buf = []
         carry = None
         for sf in surfaces:
             buf.append(sf)
             if len(buf) >= self.chunk:
-                out.append(self._flush_nv12(buf, carry))
+                out.append(self._flush_nv12(buf, carry, rotate))
                 carry, buf = buf[-1], []
         if buf:
-            out.append(self._flush_nv12(buf, carry))
+            out.append(self._flush_nv12(buf, carry, rotate))
         return np.concatenate(out) if out else np.zeros(0, _lib.RECORD_DTYPE)
 
-    def _flush_nv12(self, buf, carry):
+    def _flush_nv12(self, buf, carry, rotate=0):
         items = ([carry] if carry is not None else []) + buf
-        rec = self.ctx.analyze_frames_nv12(np.stack([y for y, _ in items]), np.stack([uv for _, uv in items]))
+        rec = self.ctx.analyze_frames_nv12(np.stack([y for y, _ in items]), np.stack([uv for _, uv in items]), rotate=rotate)
         return rec[1:] if carry is not None else rec
 
     # -- and for planar pictures (software decoders, .y4m): an iterable of (y uint8[H,W], u uint8[H/2,W/2], v uint8[H/2,W/2]) triples ----
-    def records_stream_i420(self, surfaces) -> np.ndarray:
+    def records_stream_i420(self, surfaces, rotate: int = 0) -> np.ndarray:
         out = []
         buf = []
         carry = None
         for sf in surfaces:
             buf.append(sf)
             if len(buf) >= self.chunk:
-                out.append(self._flush_i420(buf, carry))
+                out.append(self._flush_i420(buf, carry, rotate))
                 carry, buf = buf[-1], []
         if buf:
-            out.append(self._flush_i420(buf, carry))
+            out.append(self._flush_i420(buf, carry, rotate))
         return np.concatenate(out) if out else np.zeros(0, _lib.RECORD_DTYPE)
 
-    def _flush_i420(self, buf, carry):
+    def _flush_i420(self, buf, carry, rotate=0):
         items = ([carry] if carry is not None else []) + buf
-        rec = self.ctx.analyze_frames_i420(*(np.stack([sf[k] for sf in items]) for k in range(3)))
+        rec = self.ctx.analyze_frames_i420(*(np.stack([sf[k] for sf in items]) for k in range(3)), rotate=rotate)
         return rec[1:] if carry is not None else rec
 
 

@@ -37,6 +37,9 @@ class FrameSource:
     width: int = 0
     height: int = 0
     frame_count: int = 0
+    # quarter turns clockwise from the pictures sampled() yields (the STORED ones) to the displayed picture; width / height are the displayed
+    # picture's, as cv2's capture properties are (orientation-auto)
+    rotate: int = 0
 
     def sampled(self, step: int) -> Iterator[np.ndarray]:
         raise NotImplementedError
@@ -62,7 +65,10 @@ class Y4mSource(FrameSource):
     """YUV4MPEG2 file with 8-bit 4:2:0 pictures (C420, C420jpeg, C420mpeg2, C420paleo -- chroma siting does not enter
     libswscale's unscaled yuv420p -> bgr24 conversion, which takes the nearest chroma sample).  Frames are read through a
     memory map; ``sampled`` yields NV12 surfaces (the U and V planes interleaved on the host: 0.5 byte per pixel), or with
-    ``planar=True`` the file's own I420 planes as three views of the map (no copy, no interleave)."""
+    ``planar=True`` the file's own I420 planes as three views of the map (no copy, no interleave).
+    A header token ``XAVD_ROTATE=<0|90|180|270>`` (YUV4MPEG2 ``X`` tokens are application comments that other readers ignore) carries a
+    container's display rotation, clockwise: ``rotate`` is its quarter turns, ``width`` / ``height`` are the DISPLAYED picture's, the planes
+    yielded are the stored ones."""
     surface = "nv12"
 
     def __init__(self, path: str, planar: bool = False):
@@ -85,11 +91,17 @@ class Y4mSource(FrameSource):
                 num, den = int(a), int(b or 1)
             elif tag == b"C":
                 chroma = val
+            elif tag == b"X" and val.startswith("AVD_ROTATE="):
+                deg = val[len("AVD_ROTATE="):]
+                if deg not in ("0", "90", "180", "270"):
+                    raise ValueError("XAVD_ROTATE must be 0, 90, 180 or 270")
+                self.rotate = int(deg) // 90
         if w <= 0 or h <= 0 or (w | h) & 1:
             raise ValueError("bad or odd picture size")
         if not chroma.startswith("420") or "p1" in chroma:          # 420p10 / p12 / p16: more than 8 bits
             raise ValueError("only 8-bit 4:2:0 is supported")
-        self.width, self.height = w, h
+        self._w, self._h = w, h                                      # the stored picture
+        self.width, self.height = (h, w) if self.rotate & 1 else (w, h)
         self.fps = num / den if den else 0.0
         self._luma, self._chroma = w * h, (w // 2) * (h // 2)
         self._frame_bytes = self._luma + 2 * self._chroma
@@ -113,7 +125,7 @@ class Y4mSource(FrameSource):
         self.frame_count = len(self._offsets)
 
     def sampled(self, step):
-        h, w = self.height, self.width
+        h, w = self._h, self._w
         for i in range(0, self.frame_count, step):
             o = self._offsets[i]
             y = np.asarray(self._map[o:o + self._luma]).reshape(h, w)
@@ -131,11 +143,12 @@ class Y4mSource(FrameSource):
         self._map = None
 
 
-def write_y4m(path: str, y: np.ndarray, uv: np.ndarray, fps=(30, 1)) -> None:
-    """NV12 surfaces (y uint8[N,H,W], uv uint8[N,H/2,W] interleaved) -> a YUV4MPEG2 file (tests, tools)."""
+def write_y4m(path: str, y: np.ndarray, uv: np.ndarray, fps=(30, 1), rotate: int = 0) -> None:
+    """NV12 surfaces (y uint8[N,H,W], uv uint8[N,H/2,W] interleaved) -> a YUV4MPEG2 file (tests, tools).  rotate: display rotation in
+    DEGREES clockwise, written as the XAVD_ROTATE token when non-zero (Y4mSource)."""
     n, h, w = y.shape
     with open(path, "wb") as f:
-        f.write(b"YUV4MPEG2 W%d H%d F%d:%d Ip A1:1 C420jpeg\n" % (w, h, fps[0], fps[1]))
+        f.write(b"YUV4MPEG2 W%d H%d F%d:%d Ip A1:1 C420jpeg%s\n" % (w, h, fps[0], fps[1], b" XAVD_ROTATE=%d" % rotate if rotate else b""))
         for i in range(n):
             f.write(b"FRAME\n")
             f.write(np.ascontiguousarray(y[i]).tobytes())

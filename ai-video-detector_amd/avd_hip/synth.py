@@ -82,3 +82,16 @@ def i420_to_nv12(y: np.ndarray, u: np.ndarray, v: np.ndarray):
     uv[..., 0::2] = u
     uv[..., 1::2] = v
     return y, uv
+
+
+def rotate_planes(planes, k: int):
+    """The planes of the picture DISPLAYED after k quarter turns clockwise: np.rot90(S, -k) over the picture axes of every plane of an NV12
+    pair (y, uv) or an I420 triple (y, u, v), with or without the leading frame axis.  Chroma turns as an (h/2, w/2) image of U,V samples:
+    an interleaved plane is turned pair by pair, U,V order kept.  For tests and tools (the library turns nothing in memory)."""
+    turn = lambda p: np.ascontiguousarray(np.rot90(p, -k, axes=(p.ndim - 2, p.ndim - 1)))
+    if len(planes) == 3:
+        return tuple(turn(p) for p in planes)
+    y, uv = planes
+    pairs = uv.reshape(uv.shape[:-1] + (uv.shape[-1] // 2, 2))                     # [..., h/2, w/2, (U, V)]
+    turned = np.rot90(pairs, -k, axes=(pairs.ndim - 3, pairs.ndim - 2))
+    return turn(y), np.ascontiguousarray(turned).reshape(turned.shape[:-2] + (2 * turned.shape[-2],))

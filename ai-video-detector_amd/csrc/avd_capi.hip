@@ -646,7 +646,7 @@ static int preprocess_to_host(avd_ctx* ctx, const IngestClip& k, uint8_t* small3
     const int n = k.n;
     if (n == 0) return AVD_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (int e = avd_ws_reserve(ctx, n, k.h, k.w)) return e;
+    if (int e = avd_ws_reserve(ctx, n, k.disp_h(), k.disp_w())) return e;
     if (k.mem != AVD_MEM_HOST && k.mem != AVD_MEM_DEVICE) { ctx->err = "mem must be AVD_MEM_HOST or AVD_MEM_DEVICE"; return AVD_ERR_ARG; }
     Workspace& ws = ctx->ws;
     if (int e = ws.d_stage.reserve(ctx, clip_stage(k).total)) return e;
@@ -744,7 +744,7 @@ static int impl_analyze_batch_async(avd_ctx* ctx, const IngestClip* clips, int n
     for (int c = 0; c < nclips; c++) {
         const IngestClip& k = clips[c];
         if (k.n == 0) continue;
-        if (int e = avd_ws_geometry(ctx, k.h, k.w)) return e;
+        if (int e = avd_ws_geometry(ctx, k.disp_h(), k.disp_w())) return e;
         rowbuf_elems += rowbuf_elems_for(ws, k.n);
         lappart_elems += lappart_elems_for(ws, k.n);
         stage_bytes += clip_stage(k).total;
@@ -763,7 +763,7 @@ static int impl_analyze_batch_async(avd_ctx* ctx, const IngestClip* clips, int n
     for (int c = 0; c < nclips; c++) {
         const IngestClip& k = clips[c];
         if (k.n == 0) continue;
-        if (int e = avd_ws_geometry(ctx, k.h, k.w)) return e;       // a cache hit (pass 1 built it) unless > kGeomCache geometries
+        if (int e = avd_ws_geometry(ctx, k.disp_h(), k.disp_w())) return e;       // a cache hit (pass 1 built it) unless > kGeomCache geometries
         ws.f0 = f0; ws.rowbuf_off = rb; ws.lappart_off = lp;
         ws.h_clipstart[f0] = 1;
         for (int i = 1; i < k.n; i++) ws.h_clipstart[f0 + i] = 0;
@@ -843,6 +843,52 @@ static int impl_analyze_clips_async(avd_ctx* ctx, const avd_clip* clips, int ncl
     if (nclips < 0 || (nclips > 0 && !clips)) { ctx->err = "bad clip list"; return AVD_ERR_ARG; }
     std::vector<IngestClip> ks((size_t)nclips);
     for (int c = 0; c < nclips; c++) ks[c] = IngestClip{clips[c], nullptr};
+    return impl_analyze_batch_async(ctx, ks.data(), nclips, records);
+}
+
+// The descriptor family: an avd_picture is an IngestClip with its format spelled out.  Everything the descriptor alone can get wrong is refused
+// here; the plane, stride and size checks of the format are the ones of its own entry points (check_geometry, check_nv12, check_i420).
+static int picture_clip(avd_ctx* ctx, const avd_picture& p, IngestClip& k)
+{
+    if (p.struct_size != sizeof(avd_picture)) { ctx->err = "avd_picture.struct_size is not sizeof(avd_picture)"; return AVD_ERR_ARG; }
+    if (p.format != AVD_FMT_BGR24 && p.format != AVD_FMT_NV12 && p.format != AVD_FMT_I420) { ctx->err = "bad avd_picture.format"; return AVD_ERR_ARG; }
+    if (p.rotate < 0 || p.rotate > 3) { ctx->err = "avd_picture.rotate must be 0 .. 3 quarter turns"; return AVD_ERR_ARG; }
+    if (p.reserved != 0) { ctx->err = "avd_picture.reserved must be 0"; return AVD_ERR_ARG; }
+    if (p.format == AVD_FMT_BGR24) {
+        if (p.rotate) { ctx->err = "a turned BGR picture is not on the path: cv2 hands BGR over already rotated"; return AVD_ERR_UNSUPPORTED; }
+        k = bgr_clip(p.plane[0], p.mem, p.n, p.h, p.w, p.row_stride[0], p.frame_stride[0]);
+    } else if (p.format == AVD_FMT_NV12) {
+        k = nv12_clip(p.plane[0], p.plane[1], p.mem, p.n, p.h, p.w, p.row_stride[0], p.row_stride[1], p.frame_stride[0], p.frame_stride[1]);
+        if (!k.uv && p.n > 0) { ctx->err = "null plane pointer"; return AVD_ERR_ARG; }         // (a null uv would read as BGR further down)
+    } else {
+        if (p.row_stride[1] != p.row_stride[2] || p.frame_stride[1] != p.frame_stride[2]) {
+            ctx->err = "the U and V planes of an I420 picture share their strides"; return AVD_ERR_ARG;
+        }
+        k = i420_clip(p.plane[0], p.plane[1], p.plane[2], p.mem, p.n, p.h, p.w, p.row_stride[0], p.row_stride[1], p.frame_stride[0], p.frame_stride[1]);
+        if ((!k.uv || !k.v) && p.n > 0) { ctx->err = "null I420 plane pointer"; return AVD_ERR_ARG; }
+    }
+    k.rotate = p.rotate;
+    return 0;
+}
+
+static int impl_preprocess_picture(avd_ctx* ctx, const avd_picture* pic, uint8_t* small320, uint8_t* hash1024, int64_t* lap_sum, int64_t* lap_sumsq)
+{
+    if (!ctx) return AVD_ERR_ARG;
+    if (!pic) { ctx->err = "null picture"; return AVD_ERR_ARG; }
+    IngestClip k{};
+    if (int e = picture_clip(ctx, *pic, k)) return e;
+    if (k.v) return impl_preprocess_i420(ctx, k, small320, hash1024, lap_sum, lap_sumsq);
+    if (k.uv) return impl_preprocess_nv12(ctx, k, small320, hash1024, lap_sum, lap_sumsq);
+    return impl_preprocess_bgr(ctx, k.data, k.mem, k.n, k.h, k.w, k.row_stride, k.frame_stride, small320, hash1024, lap_sum, lap_sumsq);
+}
+
+static int impl_analyze_pictures_async(avd_ctx* ctx, const avd_picture* clips, int nclips, avd_frame_record* records)
+{
+    if (!ctx) return AVD_ERR_ARG;
+    if (nclips < 0 || (nclips > 0 && !clips)) { ctx->err = "bad clip list"; return AVD_ERR_ARG; }
+    std::vector<IngestClip> ks((size_t)nclips);
+    for (int c = 0; c < nclips; c++)
+        if (int e = picture_clip(ctx, clips[c], ks[c])) return e;
     return impl_analyze_batch_async(ctx, ks.data(), nclips, records);
 }
 
@@ -968,6 +1014,13 @@ static int64_t impl_debug_fetch(avd_ctx* ctx, const char* name, void* out, size_
         bytes = std::min(sizeof(IngestPlan), out_bytes);
         std::memcpy(out, &ctx->ingest_plan, bytes);
         return (int64_t)bytes;
+    }
+    if (std::strcmp(name, "ingest_rotate") == 0) {     // host state: the rotation (quarter turns) that launch ran with
+        if (!ctx->ingest_plan_valid) { ctx->err = "ingest_rotate not recorded yet: no ingest kernel was launched on this context"; return AVD_ERR_ARG; }
+        if (out_bytes < sizeof(int32_t)) { ctx->err = "ingest_rotate is int32[1]"; return AVD_ERR_ARG; }
+        const int32_t r = ctx->ingest_rotate;
+        std::memcpy(out, &r, sizeof r);
+        return (int64_t)sizeof r;
     }
     if (std::strcmp(name, "stage_bytes") == 0) {       // host state: bytes the last ingest call copied from host memory (0: device input)
         if (ctx->stage_bytes < 0) { ctx->err = "stage_bytes not recorded yet: no ingest call has run on this context"; return AVD_ERR_ARG; }
@@ -1309,6 +1362,24 @@ int avd_analyze_batch(avd_ctx* ctx, const avd_clip* clips, int nclips, avd_frame
 {
     return guarded(ctx, [&] {
         const int rc = impl_analyze_clips_async(ctx, clips, nclips, records);
+        return rc ? rc : impl_synchronize(ctx);
+    });
+}
+
+int avd_preprocess_picture(avd_ctx* ctx, const avd_picture* picture, uint8_t* small320, uint8_t* hash1024, int64_t* lap_sum, int64_t* lap_sumsq)
+{
+    return guarded(ctx, [&] { return impl_preprocess_picture(ctx, picture, small320, hash1024, lap_sum, lap_sumsq); });
+}
+
+int avd_analyze_pictures_async(avd_ctx* ctx, const avd_picture* clips, int nclips, avd_frame_record* records)
+{
+    return guarded(ctx, [&] { return impl_analyze_pictures_async(ctx, clips, nclips, records); });
+}
+
+int avd_analyze_pictures(avd_ctx* ctx, const avd_picture* clips, int nclips, avd_frame_record* records)
+{
+    return guarded(ctx, [&] {
+        const int rc = impl_analyze_pictures_async(ctx, clips, nclips, records);
         return rc ? rc : impl_synchronize(ctx);
     });
 }

@@ -70,8 +70,15 @@ struct I420Params {
 };
 
 // One clip as the ingest code sees it: the public avd_clip (frozen at ABI 3: BGR, or NV12 with uv set) plus the third plane of planar
-// 4:2:0 input.  v != nullptr: I420 -- data = Y, uv = the U plane, v = the V plane; uv_row_stride / uv_frame_stride hold for both.
-struct IngestClip : avd_clip { const uint8_t* v; };
+// 4:2:0 input and the display rotation of avd_picture.  v != nullptr: I420 -- data = Y, uv = the U plane, v = the V plane; uv_row_stride /
+// uv_frame_stride hold for both.  rotate: quarter turns clockwise from the stored picture (h, w, the planes and strides: always the STORED one)
+// to the displayed picture, whose size the geometry tables, the band plan and every result follow (4:2:0 clips only).
+struct IngestClip : avd_clip {
+    const uint8_t* v;
+    int rotate;
+    int disp_h() const { return rotate & 1 ? w : h; }
+    int disp_w() const { return rotate & 1 ? h : w; }
+};
 
 // ---- device-side parameter blocks ------------------------------------------------
 struct LinTap { short i0, i1, w0, w1; };   // two source indices + 11-bit weights of one output row/column
@@ -101,7 +108,8 @@ struct HashParams {
 struct BandPlan { int rows_per_band, pitch, ni; };
 BandPlan band_plan(int w);
 // What launch_preprocess ran last on a context: read by tests through avd_debug_fetch "ingest_plan" (eight int32 in this order).
-enum IngestKernel { kIngestBgrScalar = 0, kIngestBgrVec16, kIngestBgrStaged, kIngestNv12Scalar, kIngestNv12Tables, kIngestI420Scalar, kIngestI420Tables };
+enum IngestKernel { kIngestBgrScalar = 0, kIngestBgrVec16, kIngestBgrStaged, kIngestNv12Scalar, kIngestNv12Tables, kIngestI420Scalar, kIngestI420Tables,
+                    kIngestNv12Strip, kIngestI420Strip };
 struct IngestPlan { int h, w, rows_per_band, nbands, pitch, ni, lds_bytes, kernel; };
 static_assert(sizeof(IngestPlan) == 8 * sizeof(int), "avd_debug_fetch hands the struct out as int32[8]");
 // Kernel shape of a CNN convolution launch (avd_cnn.hip), as avd_debug_fetch "cnn_plan" hands it out per convolution: kCnnFolded = no launch
@@ -250,6 +258,7 @@ struct avd_ctx {
     int last_n = 0;
     IngestPlan ingest_plan{};        // the last launch_preprocess of this context (debug buffer "ingest_plan")
     int ingest_plan_valid = 0;       // 0 until the first ingest launch
+    int ingest_rotate = 0;           // the rotation that launch ran with (debug buffer "ingest_rotate")
     int64_t stage_bytes = -1;        // bytes the last ingest call copied from host memory (debug buffer "stage_bytes"; 0: device input); -1 until the first one
     int rec_n = 0;                   // records the last avd_analyze_* call left in ws.d_rec (0 after any other entry point: avd_allgather_last_records checks it)
     void* comm = nullptr;            // RCCL communicator (avd_comm.cpp), bound at run time

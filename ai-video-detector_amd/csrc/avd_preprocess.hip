@@ -547,8 +547,9 @@ __device__ __forceinline__ unsigned gray4_nv12(unsigned yw, unsigned cw, const Y
 }
 
 // 4:2:0, any geometry / alignment: one pixel per work item.  chroma(y >> 1, x >> 1, U, V) fetches the pixel's chroma sample: the surface
-// kinds differ in nothing else.
-template <typename ChromaAt>
+// kinds differ in nothing else.  FLIP: the stored picture is the displayed one turned by 180 degrees -- displayed (y, x) is stored
+// (h - 1 - y, w - 1 - x), and with even h and w its chroma sample is the mirrored one.
+template <bool FLIP, typename ChromaAt>
 __device__ __forceinline__ void fill_yuv420_scalar(uint8_t* tile, const uint8_t* yfr, const YuvConsts& k, const PreParams& P, const Band& b, int tid,
                                                    ChromaAt chroma)
 {
@@ -556,44 +557,39 @@ __device__ __forceinline__ void fill_yuv420_scalar(uint8_t* tile, const uint8_t*
     for (int it = tid; it < b.trows * w; it += kThreads) {
         const int tr = it / w, x = it - tr * w;
         const int y = reflect_once(b.r0 - 1 + tr, P.h);
+        const int sy = FLIP ? P.h - 1 - y : y, sx = FLIP ? w - 1 - x : x;
         int U, V;
-        chroma(y >> 1, x >> 1, U, V);
+        chroma(sy >> 1, sx >> 1, U, V);
         const ChromaTerms t = chroma_terms(U, V, k);
-        tile[tr * pitch + kPad + x] = (uint8_t)gray_from_yuv(yfr[(int64_t)y * P.row_stride + x], t, k.cy);
+        tile[tr * pitch + kPad + x] = (uint8_t)gray_from_yuv(yfr[(int64_t)sy * P.row_stride + sx], t, k.cy);
     }
 }
 
 // NV12: U, V interleaved in one plane
+template <bool FLIP>
 __device__ __forceinline__ void fill_nv12_scalar(uint8_t* tile, const uint8_t* yfr, const uint8_t* cfr, const Nv12Params& nv,
                                                  const PreParams& P, const Band& b, int tid)
 {
-    fill_yuv420_scalar(tile, yfr, nv.k, P, b, tid, [&](int cy, int cx, int& U, int& V) {
+    fill_yuv420_scalar<FLIP>(tile, yfr, nv.k, P, b, tid, [&](int cy, int cx, int& U, int& V) {
         const uint8_t* cp = cfr + (int64_t)cy * nv.uv_row_stride + cx * 2;
         U = cp[0]; V = cp[1];
     });
 }
 
 // I420: U from u + (y>>1)*c_row_stride + (x>>1), V likewise
+template <bool FLIP>
 __device__ __forceinline__ void fill_i420_scalar(uint8_t* tile, const uint8_t* yfr, const uint8_t* ufr, const uint8_t* vfr, const I420Params& ip,
                                                  const PreParams& P, const Band& b, int tid)
 {
-    fill_yuv420_scalar(tile, yfr, ip.k, P, b, tid, [&](int cy, int cx, int& U, int& V) {
+    fill_yuv420_scalar<FLIP>(tile, yfr, ip.k, P, b, tid, [&](int cy, int cx, int& U, int& V) {
         const int64_t o = (int64_t)cy * ip.c_row_stride + cx;
         U = ufr[o]; V = vfr[o];
     });
 }
 
-// NV12, 16-byte aligned planes of w % 16 == 0 pixels.
-// libswscale's converter IS a table lookup: B = T[Y + ob(U)], G = T[Y + og(U, V)], R = T[Y + or(V)] with one clip table T(i) = clip8((c0 + i cy) >> 16).
-// Three LDS tables of cv2's gray weight times T (3735 T, 19235 T + the rounding 2^14, 9798 T; 32-bit entries, index bias kNvBias), so a pixel is
-// three index additions, three ds_read_b32, one three-operand add and a shift -- instead of three multiply-adds, three shifts, three clamps and
-// three multiply-adds (12.3 -> 8.8 vector instructions per pixel; the LDS pipe does the lookups beside them).  Same integers by construction.
-// chroma8(p, c, t) forms the eight chroma-term triples of chroma row p, 16-pixel chunk c: the surface kinds differ in nothing else.
-template <typename Chroma8>
-__device__ __forceinline__ void fill_yuv420_tables(uint8_t* tile, const uint8_t* yfr, const YuvConsts& k, const PreParams& P, const Band& b, int tid,
-                                                   Chroma8 chroma8)
+// the three gray tables behind a tile of trows rows (B, G, R: kNvTab entries each); returns the first
+__device__ __forceinline__ unsigned* build_gray_tables(uint8_t* tile, int trows, int pitch, const YuvConsts& k, int tid)
 {
-    const int h = P.h, pitch = P.pitch, r0 = b.r0, rows = b.rows, trows = b.trows;
     unsigned* const tabB = reinterpret_cast<unsigned*>(tile + lds_nvtab_off(trows, pitch));
     unsigned* const tabG = tabB + kNvTab;
     unsigned* const tabR = tabG + kNvTab;
@@ -602,6 +598,26 @@ __device__ __forceinline__ void fill_yuv420_tables(uint8_t* tile, const uint8_t*
         tabB[i] = v * 3735u; tabG[i] = v * 19235u + (1u << 14); tabR[i] = v * 9798u;
     }
     __syncthreads();
+    return tabB;
+}
+
+// NV12, 16-byte aligned planes of w % 16 == 0 pixels.
+// libswscale's converter IS a table lookup: B = T[Y + ob(U)], G = T[Y + og(U, V)], R = T[Y + or(V)] with one clip table T(i) = clip8((c0 + i cy) >> 16).
+// Three LDS tables of cv2's gray weight times T (3735 T, 19235 T + the rounding 2^14, 9798 T; 32-bit entries, index bias kNvBias), so a pixel is
+// three index additions, three ds_read_b32, one three-operand add and a shift -- instead of three multiply-adds, three shifts, three clamps and
+// three multiply-adds (12.3 -> 8.8 vector instructions per pixel; the LDS pipe does the lookups beside them).  Same integers by construction.
+// chroma8(p, c, t) forms the eight chroma-term triples of chroma row p, 16-pixel chunk c: the surface kinds differ in nothing else.
+// FLIP (half turn): the work item of displayed chroma row p, chunk c reads the MIRRORED stored chunk -- chroma row h/2 - 1 - p, chunk
+// chunks - 1 - c, luma rows h - 1 - y -- with the same 16-byte loads, and reverses the bytes in registers: displayed byte i of the chunk is
+// stored byte 15 - i, whose chroma pair is 7 - (i >> 1).
+template <bool FLIP, typename Chroma8>
+__device__ __forceinline__ void fill_yuv420_tables(uint8_t* tile, const uint8_t* yfr, const YuvConsts& k, const PreParams& P, const Band& b, int tid,
+                                                   Chroma8 chroma8)
+{
+    const int h = P.h, pitch = P.pitch, r0 = b.r0, rows = b.rows, trows = b.trows;
+    unsigned* const tabB = build_gray_tables(tile, trows, pitch, k, tid);
+    unsigned* const tabG = tabB + kNvTab;
+    unsigned* const tabR = tabG + kNvTab;
     // one work item = one chroma row x one 16-pixel chunk: the eight chroma-term triples are formed once and serve the
     // two luma rows that share them (they are 8.5 of the ~27 integer operations a pixel costs otherwise)
     const int ylo = r0 - 1, yhi = r0 + rows;              // image rows of tile rows 0 and trows - 1, before reflection
@@ -610,19 +626,24 @@ __device__ __forceinline__ void fill_yuv420_tables(uint8_t* tile, const uint8_t*
     const int chunks = P.w >> 4;
     for (int it = tid; it < np * chunks; it += kThreads) {
         const int pr = it / chunks, c = it - pr * chunks, p = p0 + pr;
-        ChromaTerms t[8];
-        chroma8(p, c, t);
+        const int cs = FLIP ? chunks - 1 - c : c;            // the stored chunk
+        ChromaTerms ts[8];
+        chroma8(FLIP ? (h >> 1) - 1 - p : p, cs, ts);
+        const auto t = [&](int j) -> const ChromaTerms& { return ts[FLIP ? 7 - j : j]; };      // pair j of the displayed chunk
 #pragma unroll
         for (int s2 = 0; s2 < 2; s2++) {
             const int y = 2 * p + s2;
             if (y < ya || y > yb) continue;
-            const uint4 yy = *reinterpret_cast<const uint4*>(yfr + (int64_t)y * P.row_stride + c * 16);
-            const unsigned yw[4] = {yy.x, yy.y, yy.z, yy.w};
+            const uint4 yy = *reinterpret_cast<const uint4*>(yfr + (int64_t)(FLIP ? h - 1 - y : y) * P.row_stride + cs * 16);
+            unsigned yw[4] = {yy.x, yy.y, yy.z, yy.w};
+            if (FLIP) {
+                yw[0] = __builtin_bswap32(yy.w); yw[1] = __builtin_bswap32(yy.z); yw[2] = __builtin_bswap32(yy.y); yw[3] = __builtin_bswap32(yy.x);
+            }
             unsigned g[4];
 #pragma unroll
             for (int j = 0; j < 4; j++)
-                g[j] = gray_from_tables(yw[j] & 0xFF, t[2 * j], tabB, tabG, tabR) | (gray_from_tables((yw[j] >> 8) & 0xFF, t[2 * j], tabB, tabG, tabR) << 8) |
-                       (gray_from_tables((yw[j] >> 16) & 0xFF, t[2 * j + 1], tabB, tabG, tabR) << 16) | (gray_from_tables(yw[j] >> 24, t[2 * j + 1], tabB, tabG, tabR) << 24);
+                g[j] = gray_from_tables(yw[j] & 0xFF, t(2 * j), tabB, tabG, tabR) | (gray_from_tables((yw[j] >> 8) & 0xFF, t(2 * j), tabB, tabG, tabR) << 8) |
+                       (gray_from_tables((yw[j] >> 16) & 0xFF, t(2 * j + 1), tabB, tabG, tabR) << 16) | (gray_from_tables(yw[j] >> 24, t(2 * j + 1), tabB, tabG, tabR) << 24);
             *reinterpret_cast<uint4*>(tile + (y - ylo) * pitch + kPad + c * 16) = make_uint4(g[0], g[1], g[2], g[3]);
         }
     }
@@ -638,10 +659,11 @@ __device__ __forceinline__ void fill_yuv420_tables(uint8_t* tile, const uint8_t*
 }
 
 // NV12: the 16 chroma bytes of a chunk are one 16-byte load, pair j = bytes 2j (U) and 2j + 1 (V)
+template <bool FLIP>
 __device__ __forceinline__ void fill_nv12_tables(uint8_t* tile, const uint8_t* yfr, const uint8_t* cfr, const Nv12Params& nv,
                                                  const PreParams& P, const Band& b, int tid)
 {
-    fill_yuv420_tables(tile, yfr, nv.k, P, b, tid, [&](int p, int c, ChromaTerms (&t)[8]) {
+    fill_yuv420_tables<FLIP>(tile, yfr, nv.k, P, b, tid, [&](int p, int c, ChromaTerms (&t)[8]) {
         const uint4 cc = *reinterpret_cast<const uint4*>(cfr + (int64_t)p * nv.uv_row_stride + c * 16);
         const unsigned cw[4] = {cc.x, cc.y, cc.z, cc.w};
 #pragma unroll
@@ -654,10 +676,11 @@ __device__ __forceinline__ void fill_nv12_tables(uint8_t* tile, const uint8_t* y
 
 // I420, Y plane 16-byte aligned, U and V planes 8-byte aligned: the 16 chroma bytes of a chunk are two 8-byte loads, 8 U and 8 V; pair j = U byte j
 // and V byte j.  (A contiguous frame has its V plane at 5wh/4, which w % 16 == 0 makes a multiple of 8 but not of 16.)
+template <bool FLIP>
 __device__ __forceinline__ void fill_i420_tables(uint8_t* tile, const uint8_t* yfr, const uint8_t* ufr, const uint8_t* vfr, const I420Params& ip,
                                                  const PreParams& P, const Band& b, int tid)
 {
-    fill_yuv420_tables(tile, yfr, ip.k, P, b, tid, [&](int p, int c, ChromaTerms (&t)[8]) {
+    fill_yuv420_tables<FLIP>(tile, yfr, ip.k, P, b, tid, [&](int p, int c, ChromaTerms (&t)[8]) {
         const int64_t o = (int64_t)p * ip.c_row_stride + c * 8;
         const uint2 uu = *reinterpret_cast<const uint2*>(ufr + o), vv = *reinterpret_cast<const uint2*>(vfr + o);
         const unsigned uw[2] = {uu.x, uu.y}, vw[2] = {vv.x, vv.y};
@@ -667,7 +690,121 @@ __device__ __forceinline__ void fill_i420_tables(uint8_t* tile, const uint8_t* y
     });
 }
 
-template <bool VEC>
+// ---- quarter turns: the strip fills ----------------------------------------------------------------------------------------------------
+// The stored picture S (Hs = P.w rows of Ws = P.h columns) is the displayed one D turned by a quarter: ROT = 1  D[r][c] = S[Hs-1-c][r],
+// ROT = 3  D[r][c] = S[c][Ws-1-r].  A band's tile rows are therefore stored COLUMNS: of every stored row the band needs one span of at most
+// kBandCap + 2 = 16 contiguous luma bytes (the displayed rows [r0-1, r0+rows] that exist) and the chroma samples under them.  One work item =
+// one stored row = one displayed column: it loads the span, forms the chroma terms once per chroma sample (a sample serves the two adjacent
+// luma columns of the span), converts through the gray tables and writes one byte into every tile row; the lanes of a wave hold consecutive
+// displayed columns, so these are consecutive LDS bytes.  The span starts at stored column r0 - 1 (or ends there), so it has no alignment to
+// speak of: the loads are 4-byte copies the compiler may issue at any address (the target guarantees unaligned access to global memory) and
+// single bytes for what is left, never a byte outside the span -- one fill serves every geometry, base address and stride.
+
+// the first `len` (<= 4 * NW) bytes at p, little-endian into NW words; the rest of the words is zero
+template <int NW>
+__device__ __forceinline__ void load_span(const uint8_t* p, int len, unsigned (&wd)[NW])
+{
+#pragma unroll
+    for (int k = 0; k < NW; k++) {
+        unsigned v = 0;
+        if (4 * k + 4 <= len) __builtin_memcpy(&v, p + 4 * k, 4);
+        else {
+#pragma unroll
+            for (int j = 0; j < 3; j++)
+                if (4 * k + j < len) v |= (unsigned)p[4 * k + j] << (8 * j);
+        }
+        wd[k] = v;
+    }
+}
+
+__device__ __forceinline__ unsigned span_byte(const unsigned* wd, int i) { return (wd[i >> 2] >> (8 * (i & 3))) & 0xFF; }
+
+constexpr int kStripSpan = kBandCap + 2;               // luma bytes of a span at most
+constexpr int kStripChroma = kStripSpan / 2 + 1;       // chroma samples under them at most (a span that starts on an odd column)
+static_assert(kStripSpan == 16, "load_span<4> holds the luma span");
+
+// chroma9(cy, q0, nq, t): the chroma-term triples of samples [q0, q0 + nq) of stored chroma row cy.  The surface kinds differ in nothing else.
+template <int ROT, typename Chroma9>
+__device__ __forceinline__ void fill_yuv420_strip(uint8_t* tile, const uint8_t* yfr, const YuvConsts& k, const PreParams& P, const Band& b, int tid,
+                                                  Chroma9 chroma9)
+{
+    static_assert(ROT == 1 || ROT == 3, "quarter turns");
+    const int h = P.h, w = P.w, pitch = P.pitch, trows = b.trows;
+    const unsigned* const tabB = build_gray_tables(tile, trows, pitch, k, tid);
+    const unsigned* const tabG = tabB + kNvTab;
+    const unsigned* const tabR = tabG + kNvTab;
+    const int ylo = b.r0 - 1, yhi = b.r0 + b.rows;           // displayed rows of tile rows 0 and trows - 1, before reflection
+    const int ya = max(ylo, 0), yb = min(yhi, h - 1);         // the ones that exist
+    const int len = yb - ya + 1;                              // <= kStripSpan
+    const int s0 = ROT == 1 ? ya : h - 1 - yb;                // first stored column of the span
+    const int odd = s0 & 1;                                   // the span's first byte is the SECOND luma column of its chroma sample
+    const int q0 = s0 >> 1, nq = ((s0 + len - 1) >> 1) - q0 + 1;
+    // span byte i is displayed row ya + i (ROT 1) or yb - i (ROT 3)
+    uint8_t* const dst0 = tile + kPad + (ROT == 1 ? ya - ylo : yb - ylo) * pitch;
+    const int dstep = ROT == 1 ? pitch : -pitch;
+    auto walk = [&](auto odd_tag) {
+        constexpr int ODD = decltype(odd_tag)::value;
+        for (int c = tid; c < w; c += kThreads) {
+            const int sr = ROT == 1 ? w - 1 - c : c;          // the stored row of displayed column c
+            unsigned yw[4];
+            load_span<4>(yfr + (int64_t)sr * P.row_stride + s0, len, yw);
+            ChromaTerms t[kStripChroma];
+            chroma9(sr >> 1, q0, nq, t);
+            uint8_t* d = dst0 + c;
+#pragma unroll
+            for (int i = 0; i < kStripSpan; i++) {
+                if (i < len) *d = (uint8_t)gray_from_tables(span_byte(yw, i), t[(i + ODD) >> 1], tabB, tabG, tabR);
+                d += dstep;
+            }
+        }
+    };
+    if (odd) walk(std::integral_constant<int, 1>{}); else walk(std::integral_constant<int, 0>{});
+    __syncthreads();
+    // BORDER_REFLECT_101 rows: displayed row -1 is row 1, row h is row h - 2 (both already in the tile); whole 16-byte words, the last of
+    // which may end in the tile row's padding
+    const int words = (w + 15) >> 4;
+    if (ylo < 0)
+        for (int c = tid; c < words; c += kThreads)
+            *reinterpret_cast<uint4*>(tile + kPad + c * 16) = *reinterpret_cast<const uint4*>(tile + 2 * pitch + kPad + c * 16);
+    if (yhi > h - 1)
+        for (int c = tid; c < words; c += kThreads)
+            *reinterpret_cast<uint4*>(tile + (trows - 1) * pitch + kPad + c * 16) =
+                *reinterpret_cast<const uint4*>(tile + (trows - 3) * pitch + kPad + c * 16);
+}
+
+// NV12: sample q of a chroma row is the byte pair at 2q
+template <int ROT>
+__device__ __forceinline__ void fill_nv12_strip(uint8_t* tile, const uint8_t* yfr, const uint8_t* cfr, const Nv12Params& nv,
+                                                const PreParams& P, const Band& b, int tid)
+{
+    fill_yuv420_strip<ROT>(tile, yfr, nv.k, P, b, tid, [&](int cy, int q0, int nq, ChromaTerms (&t)[kStripChroma]) {
+        unsigned cw[(kStripChroma + 1) / 2];
+        load_span(cfr + (int64_t)cy * nv.uv_row_stride + q0 * 2, nq * 2, cw);
+#pragma unroll
+        for (int j = 0; j < kStripChroma; j++)
+            if (j < nq) t[j] = chroma_offsets(span_byte(cw, 2 * j), span_byte(cw, 2 * j + 1), nv.k);
+    });
+}
+
+// I420: sample q is byte q of the U row and of the V row
+template <int ROT>
+__device__ __forceinline__ void fill_i420_strip(uint8_t* tile, const uint8_t* yfr, const uint8_t* ufr, const uint8_t* vfr, const I420Params& ip,
+                                                const PreParams& P, const Band& b, int tid)
+{
+    fill_yuv420_strip<ROT>(tile, yfr, ip.k, P, b, tid, [&](int cy, int q0, int nq, ChromaTerms (&t)[kStripChroma]) {
+        const int64_t o = (int64_t)cy * ip.c_row_stride + q0;
+        unsigned uw[(kStripChroma + 3) / 4], vw[(kStripChroma + 3) / 4];
+        load_span(ufr + o, nq, uw);
+        load_span(vfr + o, nq, vw);
+#pragma unroll
+        for (int j = 0; j < kStripChroma; j++)
+            if (j < nq) t[j] = chroma_offsets(span_byte(uw, j), span_byte(vw, j), ip.k);
+    });
+}
+
+// ROT: quarter turns clockwise from the stored to the displayed picture.  0: the stored picture is the displayed one; 2: the flipped
+// instantiations of the same fills; 1, 3: the strip fill (VEC unused).  P describes the DISPLAYED picture throughout.
+template <bool VEC, int ROT>
 __global__ __launch_bounds__(kThreads) void k_preprocess_nv12(const uint8_t* __restrict__ yplane, Nv12Params nv, int n,
                                                              PreParams P, uint8_t* __restrict__ small,
                                                              float* __restrict__ rowbuf, long long* __restrict__ lap_part)
@@ -678,14 +815,15 @@ __global__ __launch_bounds__(kThreads) void k_preprocess_nv12(const uint8_t* __r
     const int tid = threadIdx.x;
     const uint8_t* yfr = yplane + (int64_t)b.f * P.frame_stride;
     const uint8_t* cfr = nv.uv + (int64_t)b.f * nv.uv_frame_stride;
-    if (VEC) fill_nv12_tables(tile, yfr, cfr, nv, P, b, tid);
-    else fill_nv12_scalar(tile, yfr, cfr, nv, P, b, tid);
+    if constexpr (ROT & 1) fill_nv12_strip<ROT>(tile, yfr, cfr, nv, P, b, tid);
+    else if (VEC) fill_nv12_tables<ROT == 2>(tile, yfr, cfr, nv, P, b, tid);
+    else fill_nv12_scalar<ROT == 2>(tile, yfr, cfr, nv, P, b, tid);
     fill_column_halo(tile, b.trows, P.pitch, P.w, tid);
     store_moments(lap_part, b.lid, tid, band_phases<false>(tile, nullptr, P, b, tid, small, rowbuf));
 }
 
 // Planar 4:2:0 (I420; YV12 with the chroma pointers exchanged): k_preprocess_nv12 with the chroma fetched from two planes
-template <bool VEC>
+template <bool VEC, int ROT>
 __global__ __launch_bounds__(kThreads) void k_preprocess_i420(const uint8_t* __restrict__ yplane, I420Params ip, int n,
                                                              PreParams P, uint8_t* __restrict__ small,
                                                              float* __restrict__ rowbuf, long long* __restrict__ lap_part)
@@ -697,8 +835,9 @@ __global__ __launch_bounds__(kThreads) void k_preprocess_i420(const uint8_t* __r
     const uint8_t* yfr = yplane + (int64_t)b.f * P.frame_stride;
     const uint8_t* ufr = ip.u + (int64_t)b.f * ip.c_frame_stride;
     const uint8_t* vfr = ip.v + (int64_t)b.f * ip.c_frame_stride;
-    if (VEC) fill_i420_tables(tile, yfr, ufr, vfr, ip, P, b, tid);
-    else fill_i420_scalar(tile, yfr, ufr, vfr, ip, P, b, tid);
+    if constexpr (ROT & 1) fill_i420_strip<ROT>(tile, yfr, ufr, vfr, ip, P, b, tid);
+    else if (VEC) fill_i420_tables<ROT == 2>(tile, yfr, ufr, vfr, ip, P, b, tid);
+    else fill_i420_scalar<ROT == 2>(tile, yfr, ufr, vfr, ip, P, b, tid);
     fill_column_halo(tile, b.trows, P.pitch, P.w, tid);
     store_moments(lap_part, b.lid, tid, band_phases<false>(tile, nullptr, P, b, tid, small, rowbuf));
 }
@@ -822,23 +961,35 @@ int launch_preprocess(avd_ctx* ctx, const IngestClip& clip, const uint8_t* d_in,
     auto launch = [&](IngestKernel id, auto kernel, size_t lds, auto... source) {
         ctx->ingest_plan = IngestPlan{P.h, P.w, P.rows_per_band, P.nbands, P.pitch, ni, (int)lds, id};
         ctx->ingest_plan_valid = 1;
+        ctx->ingest_rotate = clip.rotate;
         hipLaunchKernelGGL(kernel, dim3(grid), dim3(kThreads), lds, ctx->stream, source..., n, P, ws.d_small + (size_t)ws.f0 * AVD_NPIX,
                            ws.d_rowbuf + ws.rowbuf_off, ws.d_lap_part + ws.lappart_off);
     };
+    const size_t tabs = lds_nvtab_off(P.rows_per_band + 2, P.pitch) + kNvTabBytes;      // tile + the three gray tables
+    const int rot = clip.rotate;
+    if (rot && !d_uv) { ctx->err = "internal error: a turned BGR clip reached the ingest launch"; return AVD_ERR_DEVICE; }
     if (d_v) {
         I420Params ip{};
         ip.u = d_uv; ip.v = d_v; ip.c_row_stride = clip.uv_row_stride; ip.c_frame_stride = clip.uv_frame_stride;
         build_yuv_consts(ip.k);
-        if (vec) launch(kIngestI420Tables, k_preprocess_i420<true>, lds_nvtab_off(P.rows_per_band + 2, P.pitch) + kNvTabBytes, d_in, ip);
-        else launch(kIngestI420Scalar, k_preprocess_i420<false>, tile, d_in, ip);
+        if (rot == 1) launch(kIngestI420Strip, k_preprocess_i420<false, 1>, tabs, d_in, ip);
+        else if (rot == 3) launch(kIngestI420Strip, k_preprocess_i420<false, 3>, tabs, d_in, ip);
+        else if (rot == 2 && vec) launch(kIngestI420Tables, k_preprocess_i420<true, 2>, tabs, d_in, ip);
+        else if (rot == 2) launch(kIngestI420Scalar, k_preprocess_i420<false, 2>, tile, d_in, ip);
+        else if (vec) launch(kIngestI420Tables, k_preprocess_i420<true, 0>, tabs, d_in, ip);
+        else launch(kIngestI420Scalar, k_preprocess_i420<false, 0>, tile, d_in, ip);
     } else if (d_uv) {
         Nv12Params nv{};
         nv.uv = d_uv; nv.uv_row_stride = clip.uv_row_stride; nv.uv_frame_stride = clip.uv_frame_stride;
         build_yuv_consts(nv.k);
         // (a register-staged variant in the style of k_preprocess_vec measured no faster: the kernel is bound by the
         // conversion's integer arithmetic, not by how its loads are issued -- profiles/r02_experiments.md)
-        if (vec) launch(kIngestNv12Tables, k_preprocess_nv12<true>, lds_nvtab_off(P.rows_per_band + 2, P.pitch) + kNvTabBytes, d_in, nv);
-        else launch(kIngestNv12Scalar, k_preprocess_nv12<false>, tile, d_in, nv);
+        if (rot == 1) launch(kIngestNv12Strip, k_preprocess_nv12<false, 1>, tabs, d_in, nv);
+        else if (rot == 3) launch(kIngestNv12Strip, k_preprocess_nv12<false, 3>, tabs, d_in, nv);
+        else if (rot == 2 && vec) launch(kIngestNv12Tables, k_preprocess_nv12<true, 2>, tabs, d_in, nv);
+        else if (rot == 2) launch(kIngestNv12Scalar, k_preprocess_nv12<false, 2>, tile, d_in, nv);
+        else if (vec) launch(kIngestNv12Tables, k_preprocess_nv12<true, 0>, tabs, d_in, nv);
+        else launch(kIngestNv12Scalar, k_preprocess_nv12<false, 0>, tile, d_in, nv);
     } else if (ni) {
         const size_t lds = tile + sizeof(LdsTabs);
         switch (ni) {

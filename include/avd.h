@@ -106,7 +106,7 @@ int avd_analyze_frames(avd_ctx* ctx, const uint8_t* bgr, int mem, int n, int h, 
  * other call on the context first completes it -- its records buffer is filled and
  * the re-run of its flagged pairs (fb_mode 1) is settled -- and returns its error
  * instead of running if it failed.  The same holds for avd_analyze_frames_nv12_async,
- * avd_analyze_frames_i420_async and avd_analyze_batch_async: whichever of them is
+ * avd_analyze_frames_i420_async, avd_analyze_batch_async and avd_analyze_pictures_async: whichever of them is
  * outstanding is drained by any other call, these included.  Exempt: avd_synchronize, avd_destroy,
  * avd_last_error, avd_get_option, avd_stage_ms, avd_kernel_ms, avd_timer_start /
  * avd_timer_stop and avd_wait_stream.  An option set while a call is pending applies
@@ -129,7 +129,9 @@ int avd_synchronize(avd_ctx* ctx);
  * chroma plane, the four strides as for avd_analyze_frames_nv12).  records: host, sum of clips[i].n entries, clip after
  * clip; the first record of every clip has ham = -1 and flow 0 (video.py:37-41, 55).  Results are identical to calling
  * avd_analyze_frames per clip.  avd_clip is frozen at ABI 3 and has no room for a third plane: a batch holds BGR and NV12
- * clips only; planar I420 clips (avd_analyze_frames_i420) wait for the next ABI revision. */
+ * clips only; planar I420 clips (avd_analyze_frames_i420) wait for the next ABI revision.  They do not have to wait for a batch, though: the
+ * descriptor family below (avd_picture, avd_analyze_pictures) is additive at ABI 3, carries three planes and a display rotation, and batches
+ * any mix of formats. */
 typedef struct avd_clip {
     const uint8_t* data;
     const uint8_t* uv;
@@ -178,6 +180,42 @@ int avd_analyze_frames_i420(avd_ctx* ctx, const uint8_t* y, const uint8_t* u, co
 int avd_analyze_frames_i420_async(avd_ctx* ctx, const uint8_t* y, const uint8_t* u, const uint8_t* v, int mem, int n, int h, int w,
                                   int64_t y_row_stride, int64_t c_row_stride, int64_t y_frame_stride, int64_t c_frame_stride,
                                   avd_frame_record* records);
+
+/* Pictures by descriptor, with a display rotation (additive at ABI 3; avd_clip and every entry point above are unchanged).  A decoder hands over
+ * the STORED picture; a container may carry a display rotation (every portrait clip a phone records is stored 1920 x 1080 with a 90 degree
+ * display matrix), and cv2.VideoCapture applies it before the reference sees a frame (orientation-auto), so the reference's records are those of
+ * the DISPLAYED picture.  avd_picture describes the stored planes and says how they turn:
+ *   D = np.rot90(S, -rotate) over the picture axes of every plane (chroma planes turn as (h/2, w/2) images of U,V samples)
+ * and every output of a call with rotate = k equals, bit for bit, the output of the format's own entry point above on D's planes, in both
+ * fb_modes.  (libswscale's nearest-chroma conversion commutes with quarter turns of even-sized pictures, so this is also the rotated BGR frame's
+ * result.)  For odd `rotate` the displayed size is w x h; the 32 x 32 minimum, the resampling tables and avd_debug_fetch "ingest_plan" follow the
+ * displayed size, the host staging ("stage_bytes") the stored planes.  The turn happens inside the fused pass, where the gray tile is filled: a
+ * half turn reads the mirrored rows and chunks of the same kernels, a quarter turn reads of every stored row the 16-byte span a band needs (the
+ * strip fill); no turned picture exists in memory.
+ *   struct_size  sizeof(avd_picture) of the caller's header; anything else is AVD_ERR_ARG
+ *   plane        BGR: [0]; NV12: Y, interleaved UV; I420: Y, U, V (YV12: exchange [1] and [2])
+ *   row_stride, frame_stride   bytes, per plane; I420: [1] == [2] (AVD_ERR_ARG otherwise)
+ *   h, w         the stored picture;  rotate  quarter turns clockwise from the stored to the displayed picture, 0 .. 3;  reserved  0
+ * Refused without a launch: rotate outside 0 .. 3, a non-zero reserved, a bad format or struct_size (AVD_ERR_ARG); what the format's own entry
+ * point refuses, with its status; AVD_FMT_BGR24 with rotate != 0 (AVD_ERR_UNSUPPORTED: cv2 hands BGR over already rotated, stored-orientation
+ * BGR does not arise).  Mirrored display matrices are not covered.
+ * avd_preprocess_picture: outputs as avd_preprocess_bgr.  avd_analyze_pictures: the batch of avd_analyze_batch with descriptors -- any mix of
+ * formats, geometries and rotations, I420 included; records clip after clip, identical to one call per clip; ONE Farneback launch sequence over
+ * all clips; nclips = 1 is the single-clip call.  avd_analyze_pictures_async follows avd_analyze_batch_async exactly: one call outstanding per
+ * context, drained by any other call, with the same exemptions. */
+enum avd_format { AVD_FMT_BGR24 = 0, AVD_FMT_NV12 = 1, AVD_FMT_I420 = 2 };
+typedef struct avd_picture {
+    uint32_t struct_size;
+    int32_t  format;
+    const uint8_t* plane[3];
+    int64_t  row_stride[3], frame_stride[3];
+    int32_t  mem, n, h, w;
+    int32_t  rotate;
+    int32_t  reserved;
+} avd_picture;
+int avd_preprocess_picture(avd_ctx* ctx, const avd_picture* picture, uint8_t* small320, uint8_t* hash1024, int64_t* lap_sum, int64_t* lap_sumsq);
+int avd_analyze_pictures(avd_ctx* ctx, const avd_picture* clips, int nclips, avd_frame_record* records);
+int avd_analyze_pictures_async(avd_ctx* ctx, const avd_picture* clips, int nclips, avd_frame_record* records);
 
 /* ViT-B/16 patch embedding on the matrix cores -- a BUILD-DEFINED EXTENSION.  The reference
  * contains no learned model (its per-frame "model" is the closed form of app/analyzers/video.py:54-56); BASELINE.json's
@@ -367,8 +405,9 @@ int avd_kernel_ms(avd_ctx* ctx, int kernel_id, float* ms);
  * "flow<L>" float[n-1][2][hL][wL] (planar, after the last iteration at level L).
  * "ingest_plan" int32[8], host state rather than a device buffer: what the last ingest launch of the context ran --
  * h, w, rows_per_band, nbands, LDS tile pitch, NI of k_preprocess_vec (0: another kernel), dynamic LDS bytes requested,
- * kernel (0 bgr_scalar, 1 bgr_vec16, 2 bgr_staged, 3 nv12_scalar, 4 nv12_tables, 5 i420_scalar, 6 i420_tables); an error before any
- * ingest launch.
+ * kernel (0 bgr_scalar, 1 bgr_vec16, 2 bgr_staged, 3 nv12_scalar, 4 nv12_tables, 5 i420_scalar, 6 i420_tables, 7 nv12_strip, 8 i420_strip; a half turn runs the
+ * flipped instantiations of 3 .. 6 under the same ids); h, w are the displayed picture's; an error before any ingest launch.
+ * "ingest_rotate" int32[1], host state: the rotation (quarter turns) that launch ran with; an error before any ingest launch.
  * "stage_bytes" int64[1], host state: the bytes the last ingest call of the context (avd_preprocess_*, avd_analyze_*) copied from host
  * memory into its staging buffer -- 0 for device input, the sum over the clips of a batch; an error before any ingest call.
  * "cnn_tap": what option "cnn_tap" made the last avd_cnn_forward copy aside -- 1: uint16[n][232][232][4] bf16 bits; 2 + i and 55: the activation as
