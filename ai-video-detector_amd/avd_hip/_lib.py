@@ -10,6 +10,7 @@ import ctypes as C
 import os
 import subprocess
 import sys
+import typing
 
 import numpy as np
 
@@ -74,6 +75,24 @@ class AvdPicture(C.Structure):
 class AvdError(RuntimeError):
     """Non-zero status from the C-ABI (the analyzer may raise; reference api.py:134-140
     turns any exception into the neutral 0.5 timeline)."""
+
+
+class _Clip(typing.NamedTuple):
+    """One clip as the binding hands it to the library: planes are base pointers (BGR one, NV12 two, I420 three), rows / frames the byte
+    strides, one per plane; keep is what the caller holds while the library reads the planes."""
+    format: int
+    planes: tuple
+    mem: int
+    n: int
+    h: int
+    w: int
+    rows: tuple
+    frames: tuple
+    keep: object
+
+    def args(self):
+        """the leading arguments of the format's own C entry points (U and V of I420 share one pair of strides there)"""
+        return self.planes + (self.mem, self.n, self.h, self.w) + self.rows[:2] + self.frames[:2]
 
 
 def build(force: bool = False) -> str:
@@ -180,6 +199,11 @@ def _is_torch_tensor(x) -> bool:
     return type(x).__module__.startswith("torch") and hasattr(x, "data_ptr")
 
 
+# what Context._plane_ptrs asks of a plane, whichever kind it is: (byte strides, base pointer, a dense copy)
+_NUMPY_PLANE = (lambda a: a.strides, lambda a: a.ctypes.data, np.ascontiguousarray)
+_TORCH_PLANE = (lambda t: t.stride(), lambda t: t.data_ptr(), lambda t: t.contiguous())
+
+
 class Context:
     """One avd_ctx: one device, one HIP stream, one workspace.  Not re-entrant -- use one
     Context per thread (ctypes releases the GIL for the duration of each call)."""
@@ -247,14 +271,7 @@ class Context:
         return a.ctypes.data, AVD_MEM_HOST, n, h, w, a.strides[1], fs, a
 
     def preprocess_bgr(self, frames):
-        ptr, mem, n, h, w, rs, fs, keep = self._frames_ptr(frames)
-        small = np.empty((n, SMALL, SMALL), np.uint8)
-        hsh = np.empty((n, HASH * HASH), np.uint8)
-        s = np.empty(n, np.int64)
-        q = np.empty(n, np.int64)
-        self._check(self._L.avd_preprocess_bgr(self._h, ptr, mem, n, h, w, rs, fs, small.ctypes.data,
-                                               hsh.ctypes.data, s.ctypes.data, q.ctypes.data))
-        return small, hsh, s, q
+        return self._preprocess("avd_preprocess_bgr", self._bgr(frames))
 
     def farneback_pairs(self, small, want_flow: bool = False):
         if _is_torch_tensor(small):
@@ -275,128 +292,121 @@ class Context:
 
     def analyze_frames(self, frames) -> np.ndarray:
         """-> structured array (RECORD_DTYPE) with one record per frame."""
-        ptr, mem, n, h, w, rs, fs, keep = self._frames_ptr(frames)
-        rec = np.zeros(n, RECORD_DTYPE)
-        self._check(self._L.avd_analyze_frames(self._h, ptr, mem, n, h, w, rs, fs, rec.ctypes.data))
-        return rec
+        return self._analyze("avd_analyze_frames", self._bgr(frames))
 
-    # -- NV12 (decoder surfaces): y uint8[N,H,W], uv uint8[N,H/2,W] with U,V interleaved ----------------------
+    # -- 4:2:0 planes.  NV12 (decoder surfaces): y uint8[N,H,W], uv uint8[N,H/2,W] with U,V interleaved.  I420 (planar, software decoders):
+    # y uint8[N,H,W], u and v uint8[N,H/2,W/2]; YV12 = the same calls with u and v exchanged -------------------------------------------
+    def _plane_ptrs(self, planes):
+        """planes: an NV12 pair (y, uv) or an I420 triple (y, u, v), numpy or torch -> _Clip.  Strided views are passed
+        as they are (a decoder's pitch, planes cut out of one buffer per clip); U and V must share their strides (the C-ABI has one pair for both)."""
+        nv12 = len(planes) == 2
+        layout = "uint8[N,H,W] and uint8[N,H/2,W]" if nv12 else "uint8[N,H,W], uint8[N,H/2,W/2] and uint8[N,H/2,W/2]"
+        torch_in = [_is_torch_tensor(p) for p in planes]
+        if any(torch_in) != all(torch_in):
+            raise ValueError("both planes must be numpy arrays or both torch tensors" if nv12 else
+                             "the three planes must all be numpy arrays or all torch tensors")
+        if all(torch_in):
+            cuda = planes[0].is_cuda
+            if any(p.dim() != 3 or str(p.dtype) != "torch.uint8" or p.is_cuda != cuda for p in planes):
+                raise ValueError(f"planes must be {layout} on the same device")
+            strides, ptr, dense = _TORCH_PLANE                 # uint8: torch's element strides are bytes
+        else:
+            planes, cuda = tuple(np.asarray(p) for p in planes), False
+            if any(p.ndim != 3 or p.dtype != np.uint8 for p in planes):
+                raise ValueError(f"planes must be {layout}")
+            strides, ptr, dense = _NUMPY_PLANE
+        st = []                                                # per plane: (row stride, frame stride) as the library takes them
+        for i, p in enumerate(planes):
+            f, r, e = strides(p)
+            if e != 1 or r < p.shape[2] or (p.shape[0] != 1 and f < r * p.shape[1]):
+                p = dense(p)
+                planes = planes[:i] + (p,) + planes[i + 1:]
+                f, r, e = strides(p)
+            st.append((r, f if p.shape[0] > 1 else p.shape[1] * r))
+        n, h, w = (int(d) for d in planes[0].shape)
+        got = [tuple(p.shape) for p in planes[1:]]
+        if nv12 and got != [(n, h // 2, w)]:
+            raise ValueError(f"chroma plane must be uint8[{n},{h // 2},{w}] (interleaved U,V), got {got[0]}")
+        if not nv12 and got != [(n, h // 2, w // 2)] * 2:
+            raise ValueError(f"chroma planes must be uint8[{n},{h // 2},{w // 2}] each, got {got[0]} and {got[1]}")
+        if not nv12 and st[1] != st[2]:
+            raise ValueError(f"the U and V planes must have the same row and frame strides, got {st[1]} and {st[2]}")
+        if cuda:
+            self._after_torch_stream(planes[0])
+        return _Clip(AVD_FMT_NV12 if nv12 else AVD_FMT_I420, tuple(ptr(p) for p in planes), AVD_MEM_DEVICE if cuda else AVD_MEM_HOST, n, h, w,
+                     tuple(r for r, _ in st), tuple(f for _, f in st), planes)
+
     def _nv12_ptrs(self, y, uv):
         """-> (yptr, uvptr, mem, n, h, w, y_row, uv_row, y_frame, uv_frame, keepalive)"""
-        if _is_torch_tensor(y) != _is_torch_tensor(uv):
-            raise ValueError("both planes must be numpy arrays or both torch tensors")
-        if _is_torch_tensor(y):
-            if y.dim() != 3 or uv.dim() != 3 or str(y.dtype) != "torch.uint8" or str(uv.dtype) != "torch.uint8" or y.is_cuda != uv.is_cuda:
-                raise ValueError("planes must be uint8[N,H,W] and uint8[N,H/2,W] on the same device")
-            ok = lambda t: t.stride(2) == 1 and t.stride(1) >= t.shape[2] and (t.shape[0] == 1 or t.stride(0) >= t.stride(1) * t.shape[1])
-            y, uv = (y if ok(y) else y.contiguous()), (uv if ok(uv) else uv.contiguous())
-            if y.is_cuda:
-                self._after_torch_stream(y)
-            n, h, w = y.shape
-            strides = (y.stride(1), uv.stride(1), y.stride(0) if n > 1 else h * y.stride(1), uv.stride(0) if n > 1 else (h // 2) * uv.stride(1))
-            ptrs, mem = (y.data_ptr(), uv.data_ptr()), (AVD_MEM_DEVICE if y.is_cuda else AVD_MEM_HOST)
-        else:
-            y, uv = np.asarray(y), np.asarray(uv)
-            if y.ndim != 3 or uv.ndim != 3 or y.dtype != np.uint8 or uv.dtype != np.uint8:
-                raise ValueError("planes must be uint8[N,H,W] and uint8[N,H/2,W]")
-            ok = lambda a: a.strides[2] == 1 and a.strides[1] >= a.shape[2] and (a.shape[0] == 1 or a.strides[0] >= a.strides[1] * a.shape[1])
-            y, uv = (y if ok(y) else np.ascontiguousarray(y)), (uv if ok(uv) else np.ascontiguousarray(uv))
-            n, h, w = y.shape
-            strides = (y.strides[1], uv.strides[1], y.strides[0] if n > 1 else h * y.strides[1], uv.strides[0] if n > 1 else (h // 2) * uv.strides[1])
-            ptrs, mem = (y.ctypes.data, uv.ctypes.data), AVD_MEM_HOST
-        if tuple(uv.shape) != (n, h // 2, w):
-            raise ValueError(f"chroma plane must be uint8[{n},{h // 2},{w}] (interleaved U,V), got {tuple(uv.shape)}")
-        return ptrs + (mem, n, h, w) + strides + ((y, uv),)
+        c = self._plane_ptrs((y, uv))
+        return c.args() + (c.keep,)
 
-    def preprocess_nv12(self, y, uv, rotate: int = 0):
-        """rotate: quarter turns clockwise from the stored planes to the displayed picture (avd_picture); 0 = today's call."""
-        if rotate:
-            return self.preprocess_picture((y, uv), rotate)
-        yp, cp, mem, n, h, w, yr, cr, yf, cf, keep = self._nv12_ptrs(y, uv)
+    def _i420_ptrs(self, y, u, v):
+        """-> (yptr, uptr, vptr, mem, n, h, w, y_row, c_row, y_frame, c_frame, keepalive)"""
+        c = self._plane_ptrs((y, u, v))
+        return c.args() + (c.keep,)
+
+    def _bgr(self, frames):
+        ptr, mem, n, h, w, rs, fs, keep = self._frames_ptr(frames)
+        return _Clip(AVD_FMT_BGR24, (ptr,), mem, int(n), int(h), int(w), (rs,), (fs,), keep)
+
+    def _clip(self, clip):
+        """clip: a BGR frame stack uint8[N,H,W,3], an NV12 pair (y, uv) or an I420 triple (y, u, v); numpy or torch -> _Clip"""
+        if not isinstance(clip, tuple):
+            return self._bgr(clip)
+        if len(clip) not in (2, 3):
+            raise ValueError("a clip is a BGR frame stack, an NV12 pair (y, uv) or an I420 triple (y, u, v)")
+        return self._plane_ptrs(clip)
+
+    def _outputs_call(self, symbol, args, n):
+        """An avd_preprocess_* call: the four host outputs of n frames behind `args`."""
         small = np.empty((n, SMALL, SMALL), np.uint8)
         hsh = np.empty((n, HASH * HASH), np.uint8)
         s = np.empty(n, np.int64)
         q = np.empty(n, np.int64)
-        self._check(self._L.avd_preprocess_nv12(self._h, yp, cp, mem, n, h, w, yr, cr, yf, cf, small.ctypes.data,
-                                                hsh.ctypes.data, s.ctypes.data, q.ctypes.data))
+        self._check(getattr(self._L, symbol)(self._h, *args, small.ctypes.data, hsh.ctypes.data, s.ctypes.data, q.ctypes.data))
         return small, hsh, s, q
 
-    def analyze_frames_nv12(self, y, uv, rotate: int = 0) -> np.ndarray:
-        if rotate:
-            return self.analyze_pictures([(y, uv)], [rotate])[0]
-        yp, cp, mem, n, h, w, yr, cr, yf, cf, keep = self._nv12_ptrs(y, uv)
-        rec = np.zeros(n, RECORD_DTYPE)
-        self._check(self._L.avd_analyze_frames_nv12(self._h, yp, cp, mem, n, h, w, yr, cr, yf, cf, rec.ctypes.data))
+    def _records_call(self, symbol, args, n, rec=None):
+        """An avd_analyze_* call of n frames: blocking (rec None: a fresh record array is filled and returned) or asynchronous (the caller's
+        rec is checked and handed over; synchronize() fills it)."""
+        if rec is None:
+            rec = np.zeros(n, RECORD_DTYPE)
+        else:
+            assert rec.dtype == RECORD_DTYPE and rec.size >= n and rec.flags.c_contiguous
+        self._check(getattr(self._L, symbol)(self._h, *args, rec.ctypes.data))
         return rec
+
+    def _preprocess(self, symbol, c):
+        return self._outputs_call(symbol, c.args(), c.n)
+
+    def _analyze(self, symbol, c, rec=None):
+        """-> the records (blocking), or the buffers the kernels read (asynchronous: the caller holds them until synchronize())"""
+        out = self._records_call(symbol, c.args(), c.n, rec)
+        return out if rec is None else c.keep
+
+    def preprocess_nv12(self, y, uv, rotate: int = 0):
+        """rotate: quarter turns clockwise from the stored planes to the displayed picture (avd_picture); 0 = the format's own entry point."""
+        return self.preprocess_picture((y, uv), rotate) if rotate else self._preprocess("avd_preprocess_nv12", self._plane_ptrs((y, uv)))
+
+    def analyze_frames_nv12(self, y, uv, rotate: int = 0) -> np.ndarray:
+        return self.analyze_pictures([(y, uv)], [rotate])[0] if rotate else self._analyze("avd_analyze_frames_nv12", self._plane_ptrs((y, uv)))
 
     def analyze_frames_nv12_async(self, y, uv, rec: np.ndarray, rotate: int = 0):
         if rotate:
             return self.analyze_pictures_async([(y, uv)], rec, [rotate])[0][0]
-        yp, cp, mem, n, h, w, yr, cr, yf, cf, keep = self._nv12_ptrs(y, uv)
-        assert rec.dtype == RECORD_DTYPE and rec.size >= n and rec.flags.c_contiguous
-        self._check(self._L.avd_analyze_frames_nv12_async(self._h, yp, cp, mem, n, h, w, yr, cr, yf, cf, rec.ctypes.data))
-        return keep
-
-    # -- I420 (planar 4:2:0, software decoders): y uint8[N,H,W], u and v uint8[N,H/2,W/2]; YV12 = the same calls with u and v exchanged ------
-    def _i420_ptrs(self, y, u, v):
-        """-> (yptr, uptr, vptr, mem, n, h, w, y_row, c_row, y_frame, c_frame, keepalive).  Strided views are passed as they are (a decoder's
-        pitch, planes cut out of one buffer per clip); U and V must share their strides (the C-ABI has one pair for both)."""
-        planes = (y, u, v)
-        torch_in = [_is_torch_tensor(p) for p in planes]
-        if any(torch_in) != all(torch_in):
-            raise ValueError("the three planes must all be numpy arrays or all torch tensors")
-        if all(torch_in):
-            if any(p.dim() != 3 or str(p.dtype) != "torch.uint8" or p.is_cuda != y.is_cuda for p in planes):
-                raise ValueError("planes must be uint8[N,H,W], uint8[N,H/2,W/2] and uint8[N,H/2,W/2] on the same device")
-            ok = lambda t: t.stride(2) == 1 and t.stride(1) >= t.shape[2] and (t.shape[0] == 1 or t.stride(0) >= t.stride(1) * t.shape[1])
-            y, u, v = (p if ok(p) else p.contiguous() for p in planes)
-            st = lambda t: (t.stride(1), t.stride(0) if t.shape[0] > 1 else t.shape[1] * t.stride(1))
-            ptr, cuda = (lambda t: t.data_ptr()), y.is_cuda
-        else:
-            y, u, v = (np.asarray(p) for p in planes)
-            if any(p.ndim != 3 or p.dtype != np.uint8 for p in (y, u, v)):
-                raise ValueError("planes must be uint8[N,H,W], uint8[N,H/2,W/2] and uint8[N,H/2,W/2]")
-            ok = lambda a: a.strides[2] == 1 and a.strides[1] >= a.shape[2] and (a.shape[0] == 1 or a.strides[0] >= a.strides[1] * a.shape[1])
-            y, u, v = (p if ok(p) else np.ascontiguousarray(p) for p in (y, u, v))
-            st = lambda a: (a.strides[1], a.strides[0] if a.shape[0] > 1 else a.shape[1] * a.strides[1])
-            ptr, cuda = (lambda a: a.ctypes.data), False
-        n, h, w = (int(d) for d in y.shape)
-        if tuple(u.shape) != (n, h // 2, w // 2) or tuple(v.shape) != (n, h // 2, w // 2):
-            raise ValueError(f"chroma planes must be uint8[{n},{h // 2},{w // 2}] each, got {tuple(u.shape)} and {tuple(v.shape)}")
-        if st(u) != st(v):
-            raise ValueError(f"the U and V planes must have the same row and frame strides, got {st(u)} and {st(v)}")
-        if cuda:
-            self._after_torch_stream(y)
-        (yr, yf), (cr, cf) = st(y), st(u)
-        return ptr(y), ptr(u), ptr(v), (AVD_MEM_DEVICE if cuda else AVD_MEM_HOST), n, h, w, yr, cr, yf, cf, (y, u, v)
+        return self._analyze("avd_analyze_frames_nv12_async", self._plane_ptrs((y, uv)), rec)
 
     def preprocess_i420(self, y, u, v, rotate: int = 0):
-        if rotate:
-            return self.preprocess_picture((y, u, v), rotate)
-        yp, up, vp, mem, n, h, w, yr, cr, yf, cf, keep = self._i420_ptrs(y, u, v)
-        small = np.empty((n, SMALL, SMALL), np.uint8)
-        hsh = np.empty((n, HASH * HASH), np.uint8)
-        s = np.empty(n, np.int64)
-        q = np.empty(n, np.int64)
-        self._check(self._L.avd_preprocess_i420(self._h, yp, up, vp, mem, n, h, w, yr, cr, yf, cf, small.ctypes.data,
-                                                hsh.ctypes.data, s.ctypes.data, q.ctypes.data))
-        return small, hsh, s, q
+        return self.preprocess_picture((y, u, v), rotate) if rotate else self._preprocess("avd_preprocess_i420", self._plane_ptrs((y, u, v)))
 
     def analyze_frames_i420(self, y, u, v, rotate: int = 0) -> np.ndarray:
-        if rotate:
-            return self.analyze_pictures([(y, u, v)], [rotate])[0]
-        yp, up, vp, mem, n, h, w, yr, cr, yf, cf, keep = self._i420_ptrs(y, u, v)
-        rec = np.zeros(n, RECORD_DTYPE)
-        self._check(self._L.avd_analyze_frames_i420(self._h, yp, up, vp, mem, n, h, w, yr, cr, yf, cf, rec.ctypes.data))
-        return rec
+        return self.analyze_pictures([(y, u, v)], [rotate])[0] if rotate else self._analyze("avd_analyze_frames_i420", self._plane_ptrs((y, u, v)))
 
     def analyze_frames_i420_async(self, y, u, v, rec: np.ndarray, rotate: int = 0):
         if rotate:
             return self.analyze_pictures_async([(y, u, v)], rec, [rotate])[0][0]
-        yp, up, vp, mem, n, h, w, yr, cr, yf, cf, keep = self._i420_ptrs(y, u, v)
-        assert rec.dtype == RECORD_DTYPE and rec.size >= n and rec.flags.c_contiguous
-        self._check(self._L.avd_analyze_frames_i420_async(self._h, yp, up, vp, mem, n, h, w, yr, cr, yf, cf, rec.ctypes.data))
-        return keep
+        return self._analyze("avd_analyze_frames_i420_async", self._plane_ptrs((y, u, v)), rec)
 
     # -- pictures by descriptor (include/avd.h: avd_picture): any format, with a display rotation -------------------------------------------
     def _picture(self, clip, rotate: int = 0):
@@ -407,31 +417,16 @@ class Context:
             raise ValueError(f"rotate must be 0, 1, 2 or 3 quarter turns (clockwise, stored to displayed picture), got {rotate!r}")
         p = AvdPicture()
         p.struct_size, p.rotate, p.reserved = C.sizeof(AvdPicture), int(rotate), 0
-        if isinstance(clip, tuple) and len(clip) == 3:
-            yp, up, vp, mem, n, h, w, yr, cr, yf, cf, keep = self._i420_ptrs(*clip)
-            p.format, planes, rows, frames = AVD_FMT_I420, (yp, up, vp), (yr, cr, cr), (yf, cf, cf)
-        elif isinstance(clip, tuple) and len(clip) == 2:
-            yp, cp, mem, n, h, w, yr, cr, yf, cf, keep = self._nv12_ptrs(*clip)
-            p.format, planes, rows, frames = AVD_FMT_NV12, (yp, cp, None), (yr, cr, 0), (yf, cf, 0)
-        elif isinstance(clip, tuple):
-            raise ValueError("a clip is a BGR frame stack, an NV12 pair (y, uv) or an I420 triple (y, u, v)")
-        else:
-            ptr, mem, n, h, w, rs, fs, keep = self._frames_ptr(clip)
-            p.format, planes, rows, frames = AVD_FMT_BGR24, (ptr, None, None), (rs, 0, 0), (fs, 0, 0)
-        for i in range(3):
-            p.plane[i], p.row_stride[i], p.frame_stride[i] = planes[i], rows[i], frames[i]
-        p.mem, p.n, p.h, p.w = mem, n, h, w
-        return p, int(n), keep
+        c = self._clip(clip)
+        p.format, p.mem, p.n, p.h, p.w = c.format, c.mem, c.n, c.h, c.w
+        for i, plane in enumerate(c.planes):
+            p.plane[i], p.row_stride[i], p.frame_stride[i] = plane, c.rows[i], c.frames[i]
+        return p, c.n, c.keep
 
     def preprocess_picture(self, clip, rotate: int = 0):
         """-> (small320, hash1024, lap_sum, lap_sumsq) of the DISPLAYED picture, as preprocess_bgr / _nv12 / _i420 on the turned planes."""
         p, n, keep = self._picture(clip, rotate)
-        small = np.empty((n, SMALL, SMALL), np.uint8)
-        hsh = np.empty((n, HASH * HASH), np.uint8)
-        s = np.empty(n, np.int64)
-        q = np.empty(n, np.int64)
-        self._check(self._L.avd_preprocess_picture(self._h, C.byref(p), small.ctypes.data, hsh.ctypes.data, s.ctypes.data, q.ctypes.data))
-        return small, hsh, s, q
+        return self._outputs_call("avd_preprocess_picture", (C.byref(p),), n)
 
     def _picture_array(self, clips, rotates):
         rotates = [0] * len(clips) if rotates is None else list(rotates)
@@ -449,15 +444,13 @@ class Context:
         """A batch by descriptor: BGR stacks, NV12 pairs and I420 triples in any mix, each with its rotation (default 0).
         -> list of record arrays, one per clip, identical to one call per clip."""
         arr, counts, keep = self._picture_array(clips, rotates)
-        rec = np.zeros(sum(counts), RECORD_DTYPE)
-        self._check(self._L.avd_analyze_pictures(self._h, arr, len(clips), rec.ctypes.data))
+        rec = self._records_call("avd_analyze_pictures", (arr, len(clips)), sum(counts))
         return list(np.split(rec, np.cumsum(counts)[:-1])) if counts else []
 
     def analyze_pictures_async(self, clips, rec: np.ndarray, rotates=None):
         """Enqueue only; rec (RECORD_DTYPE, sum of the clips' frames) is filled by synchronize().  Returns (keepalive, frame counts)."""
         arr, counts, keep = self._picture_array(clips, rotates)
-        assert rec.dtype == RECORD_DTYPE and rec.size >= sum(counts) and rec.flags.c_contiguous
-        self._check(self._L.avd_analyze_pictures_async(self._h, arr, len(clips), rec.ctypes.data))
+        self._records_call("avd_analyze_pictures_async", (arr, len(clips)), sum(counts), rec)
         return keep, counts
 
     def ingest_rotate(self) -> int:
@@ -657,10 +650,7 @@ class Context:
         return out
 
     def analyze_frames_async(self, frames, rec: np.ndarray):
-        ptr, mem, n, h, w, rs, fs, keep = self._frames_ptr(frames)
-        assert rec.dtype == RECORD_DTYPE and rec.size >= n and rec.flags.c_contiguous
-        self._check(self._L.avd_analyze_frames_async(self._h, ptr, mem, n, h, w, rs, fs, rec.ctypes.data))
-        return keep          # the buffer the kernels read: the caller holds it until synchronize()
+        return self._analyze("avd_analyze_frames_async", self._bgr(frames), rec)          # the buffer the kernels read: the caller holds it until synchronize()
 
     def synchronize(self):
         self._check(self._L.avd_synchronize(self._h))
@@ -685,16 +675,14 @@ class Context:
     def analyze_batch(self, clips):
         """-> list of record arrays, one per clip (identical to analyze_frames / analyze_frames_nv12 per clip)."""
         arr, counts, keep = self._clip_array(clips)
-        rec = np.zeros(sum(counts), RECORD_DTYPE)
-        self._check(self._L.avd_analyze_batch(self._h, arr, len(clips), rec.ctypes.data))
+        rec = self._records_call("avd_analyze_batch", (arr, len(clips)), sum(counts))
         return list(np.split(rec, np.cumsum(counts)[:-1])) if counts else []
 
     def analyze_batch_async(self, clips, rec: np.ndarray):
         """Enqueue only; rec (RECORD_DTYPE, sum of the clips' frames) is filled by synchronize().  Returns what the caller
         must keep alive until then."""
         arr, counts, keep = self._clip_array(clips)
-        assert rec.dtype == RECORD_DTYPE and rec.size >= sum(counts) and rec.flags.c_contiguous
-        self._check(self._L.avd_analyze_batch_async(self._h, arr, len(clips), rec.ctypes.data))
+        self._records_call("avd_analyze_batch_async", (arr, len(clips)), sum(counts), rec)
         return keep, counts
 
     def wait_stream(self, stream_handle: int = 0):

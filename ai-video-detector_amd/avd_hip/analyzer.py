@@ -185,62 +185,35 @@ class FrameAnalyzer:
         return out
 
     # -- streaming: bounded host memory, one-frame halo between chunks ----------------------
-    def records_stream(self, frames: Iterable[np.ndarray]) -> np.ndarray:
+    def _stream(self, items, flush) -> np.ndarray:
+        """items: frames or surfaces in order; flush(list of items) -> their records (the format's own call).  Chunks of self.chunk items, each
+        analysed behind the last item of the chunk before it (the flow / hash predecessor), whose record is dropped."""
+        def records(buf, carry):
+            return flush(buf) if carry is None else flush([carry] + buf)[1:]
+
         out = []
         buf = []
-        carry = None                   # last frame of the previous chunk (flow / hash predecessor)
-        for fr in frames:
-            buf.append(fr)
+        carry = None
+        for it in items:
+            buf.append(it)
             if len(buf) >= self.chunk:
-                out.append(self._flush(buf, carry))
+                out.append(records(buf, carry))
                 carry, buf = buf[-1], []
         if buf:
-            out.append(self._flush(buf, carry))
+            out.append(records(buf, carry))
         return np.concatenate(out) if out else np.zeros(0, _lib.RECORD_DTYPE)
 
-    def _flush(self, buf, carry):
-        stack = np.stack(([carry] if carry is not None else []) + buf)
-        rec = self.ctx.analyze_frames(stack)
-        return rec[1:] if carry is not None else rec
+    def records_stream(self, frames: Iterable[np.ndarray]) -> np.ndarray:
+        return self._stream(frames, lambda items: self.ctx.analyze_frames(np.stack(items)))
 
     # -- the same for decoder surfaces: an iterable of (y uint8[H,W], uv uint8[H/2,W]) pairs ----------------
     # rotate: quarter turns clockwise from the stored pictures to the displayed one (a container's display rotation; include/avd.h, avd_picture)
     def records_stream_nv12(self, surfaces, rotate: int = 0) -> np.ndarray:
-        out = []
-        buf = []
-        carry = None
-        for sf in surfaces:
-            buf.append(sf)
-            if len(buf) >= self.chunk:
-                out.append(self._flush_nv12(buf, carry, rotate))
-                carry, buf = buf[-1], []
-        if buf:
-            out.append(self._flush_nv12(buf, carry, rotate))
-        return np.concatenate(out) if out else np.zeros(0, _lib.RECORD_DTYPE)
-
-    def _flush_nv12(self, buf, carry, rotate=0):
-        items = ([carry] if carry is not None else []) + buf
-        rec = self.ctx.analyze_frames_nv12(np.stack([y for y, _ in items]), np.stack([uv for _, uv in items]), rotate=rotate)
-        return rec[1:] if carry is not None else rec
+        return self._stream(surfaces, lambda items: self.ctx.analyze_frames_nv12(*(np.stack([sf[k] for sf in items]) for k in range(2)), rotate=rotate))
 
     # -- and for planar pictures (software decoders, .y4m): an iterable of (y uint8[H,W], u uint8[H/2,W/2], v uint8[H/2,W/2]) triples ----
     def records_stream_i420(self, surfaces, rotate: int = 0) -> np.ndarray:
-        out = []
-        buf = []
-        carry = None
-        for sf in surfaces:
-            buf.append(sf)
-            if len(buf) >= self.chunk:
-                out.append(self._flush_i420(buf, carry, rotate))
-                carry, buf = buf[-1], []
-        if buf:
-            out.append(self._flush_i420(buf, carry, rotate))
-        return np.concatenate(out) if out else np.zeros(0, _lib.RECORD_DTYPE)
-
-    def _flush_i420(self, buf, carry, rotate=0):
-        items = ([carry] if carry is not None else []) + buf
-        rec = self.ctx.analyze_frames_i420(*(np.stack([sf[k] for sf in items]) for k in range(3)), rotate=rotate)
-        return rec[1:] if carry is not None else rec
+        return self._stream(surfaces, lambda items: self.ctx.analyze_frames_i420(*(np.stack([sf[k] for sf in items]) for k in range(3)), rotate=rotate))
 
 
 class ClipsInFlight:

@@ -26,24 +26,6 @@ struct TableBlob {
     }
 };
 
-// bytes spanned by n frames of `rows` rows of `row_bytes` bytes each, with the given strides
-size_t plane_span(int64_t frame_stride, int n, int64_t row_stride, int rows, size_t row_bytes)
-{
-    return (size_t)frame_stride * (n - 1) + (size_t)row_stride * (rows - 1) + row_bytes;
-}
-
-size_t round256(size_t v) { return (v + 255) / 256 * 256; }
-
-int check_geometry(avd_ctx* ctx, int n, int h, int w, int64_t row_stride, int64_t frame_stride)
-{
-    if (n < 0 || h <= 0 || w <= 0 || h > 16384 || w > 16384) { ctx->err = "bad frame geometry"; return AVD_ERR_ARG; }
-    if (row_stride < (int64_t)w * 3 || (n > 1 && frame_stride < row_stride * (h - 1) + (int64_t)w * 3)) {
-        ctx->err = "strides smaller than the frame"; return AVD_ERR_ARG;
-    }
-    if (h < AVD_HASH || w < AVD_HASH) { ctx->err = "frame smaller than 32x32: INTER_AREA upscaling is not on the path"; return AVD_ERR_UNSUPPORTED; }
-    return 0;
-}
-
 }  // namespace
 
 // ---- workspace -----------------------------------------------------------------------
@@ -534,92 +516,11 @@ static void impl_destroy(avd_ctx* ctx)
     delete ctx;
 }
 
-// ---- ingest: one clip = an IngestClip (BGR: uv == nullptr; NV12: data = the Y plane, uv = the interleaved chroma plane; I420: data = Y,
-// uv = the U plane, v = the V plane) ------------------
-static IngestClip bgr_clip(const uint8_t* bgr, int mem, int n, int h, int w, int64_t row_stride, int64_t frame_stride)
+// ---- ingest: one clip = an IngestClip (avd_ingest_clip.h: its format, its argument check, its staging plan) ------------------
+static int refuse(avd_ctx* ctx, const Refusal& r)
 {
-    IngestClip k{};
-    k.data = bgr; k.mem = mem; k.n = n; k.h = h; k.w = w;
-    k.row_stride = row_stride; k.frame_stride = frame_stride;
-    return k;
-}
-
-static IngestClip nv12_clip(const uint8_t* y, const uint8_t* uv, int mem, int n, int h, int w, int64_t y_row, int64_t uv_row, int64_t y_frame,
-                            int64_t uv_frame)
-{
-    IngestClip k = bgr_clip(y, mem, n, h, w, y_row, y_frame);
-    k.uv = uv; k.uv_row_stride = uv_row; k.uv_frame_stride = uv_frame;
-    return k;
-}
-
-static IngestClip i420_clip(const uint8_t* y, const uint8_t* u, const uint8_t* v, int mem, int n, int h, int w, int64_t y_row, int64_t c_row,
-                            int64_t y_frame, int64_t c_frame)
-{
-    IngestClip k = nv12_clip(y, u, mem, n, h, w, y_row, c_row, y_frame, c_frame);
-    k.v = v;
-    return k;
-}
-
-static int check_nv12(avd_ctx* ctx, const avd_clip& k)
-{
-    const int n = k.n, h = k.h, w = k.w;
-    if (n < 0 || h <= 0 || w <= 0 || h > 16384 || w > 16384) { ctx->err = "bad frame geometry"; return AVD_ERR_ARG; }
-    if ((h | w) & 1) { ctx->err = "NV12 needs even width and height"; return AVD_ERR_UNSUPPORTED; }
-    if (h < AVD_HASH || w < AVD_HASH) { ctx->err = "frame smaller than 32x32: INTER_AREA upscaling is not on the path"; return AVD_ERR_UNSUPPORTED; }
-    if ((!k.data || !k.uv) && n > 0) { ctx->err = "null plane pointer"; return AVD_ERR_ARG; }
-    if (k.row_stride < w || k.uv_row_stride < w ||
-        (n > 1 && (k.frame_stride < k.row_stride * (h - 1) + w || k.uv_frame_stride < k.uv_row_stride * (h / 2 - 1) + w))) {
-        ctx->err = "strides smaller than the planes"; return AVD_ERR_ARG;
-    }
-    return 0;
-}
-
-static int check_i420(avd_ctx* ctx, const IngestClip& k)
-{
-    const int n = k.n, h = k.h, w = k.w;
-    if (n < 0 || h <= 0 || w <= 0 || h > 16384 || w > 16384) { ctx->err = "bad frame geometry"; return AVD_ERR_ARG; }
-    if ((h | w) & 1) { ctx->err = "I420 needs even width and height"; return AVD_ERR_UNSUPPORTED; }
-    if (h < AVD_HASH || w < AVD_HASH) { ctx->err = "frame smaller than 32x32: INTER_AREA upscaling is not on the path"; return AVD_ERR_UNSUPPORTED; }
-    if ((!k.data || !k.uv || !k.v) && n > 0) { ctx->err = "null I420 plane pointer"; return AVD_ERR_ARG; }
-    if (k.row_stride < w || k.uv_row_stride < w / 2 ||
-        (n > 1 && (k.frame_stride < k.row_stride * (h - 1) + w || k.uv_frame_stride < k.uv_row_stride * (h / 2 - 1) + w / 2))) {
-        ctx->err = "strides smaller than the I420 planes"; return AVD_ERR_ARG;
-    }
-    return 0;
-}
-
-// Where a HOST clip lands in the staging buffer: BGR as one span; NV12 as the Y span with the chroma span on the next 256-byte boundary
-// behind it.  The three planes of I420 usually come out of ONE buffer per clip (a y4m map, a rawvideo pipe: Y, U, V of a frame adjacent), where
-// the per-plane spans overlap almost entirely: spans that overlap or touch are merged and copied once, so no host byte crosses the link twice, and
-// a plane sits at its own offset inside the merged span; separately allocated planes stay three spans.  `total` (a multiple of 256) is what
-// the clip occupies, `copied` the bytes that cross the link; a device clip is used in place and occupies nothing.
-struct StageSpan { const uint8_t* src; size_t bytes, off; };       // off: from the clip's place in the staging buffer, a multiple of 256
-struct ClipStage { StageSpan span[3]; int nspans; size_t plane_off[3], total, copied; };      // plane_off: data, uv, v
-
-static ClipStage clip_stage(const IngestClip& c)
-{
-    ClipStage s{};
-    if (c.mem != AVD_MEM_HOST || c.n <= 0) return s;
-    const uint8_t* src[3] = {c.data, c.uv, c.v};
-    const int planes = c.v ? 3 : (c.uv ? 2 : 1);
-    size_t len[3] = {plane_span(c.frame_stride, c.n, c.row_stride, c.h, (size_t)c.w * (c.uv ? 1 : 3)), 0, 0};
-    if (c.uv) len[1] = len[2] = plane_span(c.uv_frame_stride, c.n, c.uv_row_stride, c.h / 2, (size_t)(c.v ? c.w / 2 : c.w));
-    int order[3] = {0, 1, 2};
-    if (c.v) std::sort(order, order + 3, [&](int a, int b) { return (uintptr_t)src[a] < (uintptr_t)src[b]; });
-    for (int i = 0; i < planes; i++) {
-        const int p = order[i];
-        StageSpan* last = s.nspans ? &s.span[s.nspans - 1] : nullptr;
-        if (c.v && last && (uintptr_t)src[p] <= (uintptr_t)last->src + last->bytes)
-            last->bytes = std::max(last->bytes, (size_t)(src[p] - last->src) + len[p]);
-        else {
-            s.span[s.nspans] = StageSpan{src[p], len[p], last ? round256(last->off + last->bytes) : 0};
-            last = &s.span[s.nspans++];
-        }
-        s.plane_off[p] = last->off + (size_t)(src[p] - last->src);
-    }
-    for (int i = 0; i < s.nspans; i++) s.copied += s.span[i].bytes;
-    s.total = round256(s.span[s.nspans - 1].off + s.span[s.nspans - 1].bytes);
-    return s;
+    if (r.status) ctx->err = r.why;
+    return r.status;
 }
 
 // Stage clip k at offset `at` of ws.d_stage (host input; reserved by the caller) and launch its fused full-resolution kernel, which
@@ -634,20 +535,21 @@ static int preprocess_clip(avd_ctx* ctx, const IngestClip& k, size_t at)
             HIP_TRY(ctx, hipMemcpyAsync(dst + s.span[i].off, s.span[i].src, s.span[i].bytes, hipMemcpyHostToDevice, ctx->stream));
         ctx->stage_bytes += (int64_t)s.copied;
         d_in = dst + s.plane_off[0];
-        if (k.uv) d_uv = dst + s.plane_off[1];
-        if (k.v) d_v = dst + s.plane_off[2];
+        if (k.format != AVD_FMT_BGR24) d_uv = dst + s.plane_off[1];
+        if (k.format == AVD_FMT_I420) d_v = dst + s.plane_off[2];
     }
     return launch_preprocess(ctx, k, d_in, d_uv, d_v);
 }
 
-// avd_preprocess_bgr / _nv12 / _i420 behind their argument checks: one clip at offset 0 of the buffers, results to the host
-static int preprocess_to_host(avd_ctx* ctx, const IngestClip& k, uint8_t* small320, uint8_t* hash1024, int64_t* lap_sum, int64_t* lap_sumsq)
+// Every avd_preprocess_* entry: one clip at offset 0 of the buffers, results to the host
+static int impl_preprocess(avd_ctx* ctx, const IngestClip& k, uint8_t* small320, uint8_t* hash1024, int64_t* lap_sum, int64_t* lap_sumsq)
 {
+    if (!ctx) return AVD_ERR_ARG;
+    if (int e = refuse(ctx, check_clip(k))) return e;
     const int n = k.n;
     if (n == 0) return AVD_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (int e = avd_ws_reserve(ctx, n, k.disp_h(), k.disp_w())) return e;
-    if (k.mem != AVD_MEM_HOST && k.mem != AVD_MEM_DEVICE) { ctx->err = "mem must be AVD_MEM_HOST or AVD_MEM_DEVICE"; return AVD_ERR_ARG; }
     Workspace& ws = ctx->ws;
     if (int e = ws.d_stage.reserve(ctx, clip_stage(k).total)) return e;
     ctx->stage_bytes = 0;
@@ -667,28 +569,14 @@ static int preprocess_to_host(avd_ctx* ctx, const IngestClip& k, uint8_t* small3
     return AVD_OK;
 }
 
-static int impl_preprocess_bgr(avd_ctx* ctx, const uint8_t* bgr, int mem, int n, int h, int w,
-                       int64_t row_stride, int64_t frame_stride,
-                       uint8_t* small320, uint8_t* hash1024, int64_t* lap_sum, int64_t* lap_sumsq)
+// avd_preprocess_picture: the descriptor becomes a clip (from_picture), then the one body
+static int impl_preprocess_one_picture(avd_ctx* ctx, const avd_picture* pic, uint8_t* small320, uint8_t* hash1024, int64_t* lap_sum, int64_t* lap_sumsq)
 {
     if (!ctx) return AVD_ERR_ARG;
-    if (!bgr && n > 0) { ctx->err = "null frame pointer"; return AVD_ERR_ARG; }
-    if (int e = check_geometry(ctx, n, h, w, row_stride, frame_stride)) return e;
-    return preprocess_to_host(ctx, bgr_clip(bgr, mem, n, h, w, row_stride, frame_stride), small320, hash1024, lap_sum, lap_sumsq);
-}
-
-static int impl_preprocess_nv12(avd_ctx* ctx, const IngestClip& k, uint8_t* small320, uint8_t* hash1024, int64_t* lap_sum, int64_t* lap_sumsq)
-{
-    if (!ctx) return AVD_ERR_ARG;
-    if (int e = check_nv12(ctx, k)) return e;
-    return preprocess_to_host(ctx, k, small320, hash1024, lap_sum, lap_sumsq);
-}
-
-static int impl_preprocess_i420(avd_ctx* ctx, const IngestClip& k, uint8_t* small320, uint8_t* hash1024, int64_t* lap_sum, int64_t* lap_sumsq)
-{
-    if (!ctx) return AVD_ERR_ARG;
-    if (int e = check_i420(ctx, k)) return e;
-    return preprocess_to_host(ctx, k, small320, hash1024, lap_sum, lap_sumsq);
+    if (!pic) { ctx->err = "null picture"; return AVD_ERR_ARG; }
+    IngestClip k{};
+    if (int e = refuse(ctx, from_picture(*pic, k))) return e;
+    return impl_preprocess(ctx, k, small320, hash1024, lap_sum, lap_sumsq);
 }
 
 static int impl_farneback_pairs(avd_ctx* ctx, const uint8_t* small320, int mem, int n,
@@ -711,27 +599,20 @@ static int impl_farneback_pairs(avd_ctx* ctx, const uint8_t* small320, int mem, 
     return AVD_OK;
 }
 
-// ---- the whole per-frame path for a BATCH of clips ------------------------------------------------------------------------
+// ---- the whole per-frame path for a BATCH of clips (every avd_analyze_* entry; a single clip is a batch of one) --------
 // Frames of all clips are concatenated in the per-frame buffers (small320, hashes, moments, records): clip c occupies frames
 // [f0_c, f0_c + n_c).  Preprocess / hash / Hamming run per clip with that clip's geometry (cached tables); the Farneback
 // stage does not care where a 320 x 320 frame came from: it runs ONCE over all N - 1 consecutive pairs of the concatenation
 // (the one pair per clip boundary it computes in vain is ignored by k_records), so K short clips cost one launch sequence
 // over all their pairs instead of K sequences that each leave most of the chip idle.
-static int impl_analyze_batch_async(avd_ctx* ctx, const IngestClip* clips, int nclips, avd_frame_record* records)
+static int impl_analyze_async(avd_ctx* ctx, const IngestClip* clips, int nclips, avd_frame_record* records)
 {
     if (!ctx) return AVD_ERR_ARG;
     if (nclips < 0 || (nclips > 0 && !clips)) { ctx->err = "bad clip list"; return AVD_ERR_ARG; }
     int64_t total = 0;
     for (int c = 0; c < nclips; c++) {
-        const IngestClip& k = clips[c];
-        if (k.mem != AVD_MEM_HOST && k.mem != AVD_MEM_DEVICE) { ctx->err = "mem must be AVD_MEM_HOST or AVD_MEM_DEVICE"; return AVD_ERR_ARG; }
-        if (!k.data && k.n > 0) { ctx->err = "null frame pointer"; return AVD_ERR_ARG; }
-        if (k.v) {
-            if (int e = check_i420(ctx, k)) return e;
-        } else if (k.uv) {
-            if (int e = check_nv12(ctx, k)) return e;
-        } else if (int e = check_geometry(ctx, k.n, k.h, k.w, k.row_stride, k.frame_stride)) return e;
-        total += k.n;
+        if (int e = refuse(ctx, check_clip(clips[c]))) return e;
+        total += clips[c].n;
     }
     if (total > (1 << 24)) { ctx->err = "too many frames in one call"; return AVD_ERR_ARG; }
     if (total == 0) return AVD_OK;
@@ -811,86 +692,18 @@ static int impl_analyze_batch_async(avd_ctx* ctx, const IngestClip* clips, int n
     return AVD_OK;
 }
 
-static int impl_analyze_frames_async(avd_ctx* ctx, const uint8_t* bgr, int mem, int n, int h, int w,
-                             int64_t row_stride, int64_t frame_stride, avd_frame_record* records)
+// The two list entries: every avd_clip (from_public) or avd_picture (from_picture) becomes an IngestClip, the first refusal ends the call.
+template <typename Public, typename Convert>
+static int impl_analyze_list_async(avd_ctx* ctx, const Public* list, int nclips, avd_frame_record* records, Convert&& convert)
 {
     if (!ctx) return AVD_ERR_ARG;
-    if ((!bgr || !records) && n > 0) { ctx->err = "null pointer"; return AVD_ERR_ARG; }
-    const IngestClip k = bgr_clip(bgr, mem, n, h, w, row_stride, frame_stride);
-    return impl_analyze_batch_async(ctx, &k, 1, records);
-}
-
-static int impl_analyze_frames_nv12_async(avd_ctx* ctx, const IngestClip& k, avd_frame_record* records)
-{
-    if (!ctx) return AVD_ERR_ARG;
-    if (!records && k.n > 0) { ctx->err = "null pointer"; return AVD_ERR_ARG; }
-    if (int e = check_nv12(ctx, k)) return e;
-    return impl_analyze_batch_async(ctx, &k, 1, records);
-}
-
-static int impl_analyze_frames_i420_async(avd_ctx* ctx, const IngestClip& k, avd_frame_record* records)
-{
-    if (!ctx) return AVD_ERR_ARG;
-    if (!records && k.n > 0) { ctx->err = "null pointer"; return AVD_ERR_ARG; }
-    if (int e = check_i420(ctx, k)) return e;
-    return impl_analyze_batch_async(ctx, &k, 1, records);
-}
-
-// The public batch: avd_clip is frozen at ABI 3, so its clips are BGR or NV12; the ingest code takes them as IngestClips without a third plane.
-static int impl_analyze_clips_async(avd_ctx* ctx, const avd_clip* clips, int nclips, avd_frame_record* records)
-{
-    if (!ctx) return AVD_ERR_ARG;
-    if (nclips < 0 || (nclips > 0 && !clips)) { ctx->err = "bad clip list"; return AVD_ERR_ARG; }
-    std::vector<IngestClip> ks((size_t)nclips);
-    for (int c = 0; c < nclips; c++) ks[c] = IngestClip{clips[c], nullptr};
-    return impl_analyze_batch_async(ctx, ks.data(), nclips, records);
-}
-
-// The descriptor family: an avd_picture is an IngestClip with its format spelled out.  Everything the descriptor alone can get wrong is refused
-// here; the plane, stride and size checks of the format are the ones of its own entry points (check_geometry, check_nv12, check_i420).
-static int picture_clip(avd_ctx* ctx, const avd_picture& p, IngestClip& k)
-{
-    if (p.struct_size != sizeof(avd_picture)) { ctx->err = "avd_picture.struct_size is not sizeof(avd_picture)"; return AVD_ERR_ARG; }
-    if (p.format != AVD_FMT_BGR24 && p.format != AVD_FMT_NV12 && p.format != AVD_FMT_I420) { ctx->err = "bad avd_picture.format"; return AVD_ERR_ARG; }
-    if (p.rotate < 0 || p.rotate > 3) { ctx->err = "avd_picture.rotate must be 0 .. 3 quarter turns"; return AVD_ERR_ARG; }
-    if (p.reserved != 0) { ctx->err = "avd_picture.reserved must be 0"; return AVD_ERR_ARG; }
-    if (p.format == AVD_FMT_BGR24) {
-        if (p.rotate) { ctx->err = "a turned BGR picture is not on the path: cv2 hands BGR over already rotated"; return AVD_ERR_UNSUPPORTED; }
-        k = bgr_clip(p.plane[0], p.mem, p.n, p.h, p.w, p.row_stride[0], p.frame_stride[0]);
-    } else if (p.format == AVD_FMT_NV12) {
-        k = nv12_clip(p.plane[0], p.plane[1], p.mem, p.n, p.h, p.w, p.row_stride[0], p.row_stride[1], p.frame_stride[0], p.frame_stride[1]);
-        if (!k.uv && p.n > 0) { ctx->err = "null plane pointer"; return AVD_ERR_ARG; }         // (a null uv would read as BGR further down)
-    } else {
-        if (p.row_stride[1] != p.row_stride[2] || p.frame_stride[1] != p.frame_stride[2]) {
-            ctx->err = "the U and V planes of an I420 picture share their strides"; return AVD_ERR_ARG;
-        }
-        k = i420_clip(p.plane[0], p.plane[1], p.plane[2], p.mem, p.n, p.h, p.w, p.row_stride[0], p.row_stride[1], p.frame_stride[0], p.frame_stride[1]);
-        if ((!k.uv || !k.v) && p.n > 0) { ctx->err = "null I420 plane pointer"; return AVD_ERR_ARG; }
-    }
-    k.rotate = p.rotate;
-    return 0;
-}
-
-static int impl_preprocess_picture(avd_ctx* ctx, const avd_picture* pic, uint8_t* small320, uint8_t* hash1024, int64_t* lap_sum, int64_t* lap_sumsq)
-{
-    if (!ctx) return AVD_ERR_ARG;
-    if (!pic) { ctx->err = "null picture"; return AVD_ERR_ARG; }
-    IngestClip k{};
-    if (int e = picture_clip(ctx, *pic, k)) return e;
-    if (k.v) return impl_preprocess_i420(ctx, k, small320, hash1024, lap_sum, lap_sumsq);
-    if (k.uv) return impl_preprocess_nv12(ctx, k, small320, hash1024, lap_sum, lap_sumsq);
-    return impl_preprocess_bgr(ctx, k.data, k.mem, k.n, k.h, k.w, k.row_stride, k.frame_stride, small320, hash1024, lap_sum, lap_sumsq);
-}
-
-static int impl_analyze_pictures_async(avd_ctx* ctx, const avd_picture* clips, int nclips, avd_frame_record* records)
-{
-    if (!ctx) return AVD_ERR_ARG;
-    if (nclips < 0 || (nclips > 0 && !clips)) { ctx->err = "bad clip list"; return AVD_ERR_ARG; }
+    if (nclips < 0 || (nclips > 0 && !list)) { ctx->err = "bad clip list"; return AVD_ERR_ARG; }
     std::vector<IngestClip> ks((size_t)nclips);
     for (int c = 0; c < nclips; c++)
-        if (int e = picture_clip(ctx, clips[c], ks[c])) return e;
-    return impl_analyze_batch_async(ctx, ks.data(), nclips, records);
+        if (int e = refuse(ctx, convert(list[c], ks[c]))) return e;
+    return impl_analyze_async(ctx, ks.data(), nclips, records);
 }
+static Refusal clip_from_public(const avd_clip& c, IngestClip& k) { k = from_public(c); return {0, nullptr}; }
 
 static int impl_synchronize(avd_ctx* ctx)
 {
@@ -947,14 +760,6 @@ static int impl_synchronize(avd_ctx* ctx)
         ctx->stage_marks = 0;                       // the events belong to the call that was just drained
     }
     return AVD_OK;
-}
-
-static int impl_analyze_frames(avd_ctx* ctx, const uint8_t* bgr, int mem, int n, int h, int w,
-                       int64_t row_stride, int64_t frame_stride, avd_frame_record* records)
-{
-    int rc = impl_analyze_frames_async(ctx, bgr, mem, n, h, w, row_stride, frame_stride, records);
-    if (rc) return rc;
-    return impl_synchronize(ctx);
 }
 
 static int impl_timer_start(avd_ctx* ctx)
@@ -1317,6 +1122,29 @@ static int guarded(avd_ctx* ctx, F&& f, Pending pending = Pending::drain) noexce
     }
 }
 
+// Every avd_analyze_* entry point is ONE guarded call: the asynchronous body and, in the blocking variants, the drain behind it.
+enum class Wait { no, yes };
+template <typename F>
+static int analyze_entry(avd_ctx* ctx, Wait wait, F&& enqueue) noexcept
+{
+    return guarded(ctx, [&] {
+        const int rc = enqueue();
+        return rc || wait == Wait::no ? rc : impl_synchronize(ctx);
+    });
+}
+static int analyze_clip(avd_ctx* ctx, const IngestClip& k, avd_frame_record* records, Wait wait) noexcept
+{
+    return analyze_entry(ctx, wait, [&] { return impl_analyze_async(ctx, &k, 1, records); });
+}
+static int analyze_clips(avd_ctx* ctx, const avd_clip* clips, int nclips, avd_frame_record* records, Wait wait) noexcept
+{
+    return analyze_entry(ctx, wait, [&] { return impl_analyze_list_async(ctx, clips, nclips, records, clip_from_public); });
+}
+static int analyze_pictures(avd_ctx* ctx, const avd_picture* clips, int nclips, avd_frame_record* records, Wait wait) noexcept
+{
+    return analyze_entry(ctx, wait, [&] { return impl_analyze_list_async(ctx, clips, nclips, records, from_picture); });
+}
+
 // ---- C-ABI ------------------------------------------------------------------------------
 extern "C" {
 
@@ -1337,7 +1165,8 @@ void avd_destroy(avd_ctx* ctx)
 int avd_preprocess_bgr(avd_ctx* ctx, const uint8_t* bgr, int mem, int n, int h, int w, int64_t row_stride,
                        int64_t frame_stride, uint8_t* small320, uint8_t* hash1024, int64_t* lap_sum, int64_t* lap_sumsq)
 {
-    return guarded(ctx, [&] { return impl_preprocess_bgr(ctx, bgr, mem, n, h, w, row_stride, frame_stride, small320, hash1024, lap_sum, lap_sumsq); });
+    const IngestClip k = bgr_clip(bgr, mem, n, h, w, row_stride, frame_stride);
+    return guarded(ctx, [&] { return impl_preprocess(ctx, k, small320, hash1024, lap_sum, lap_sumsq); });
 }
 
 int avd_farneback_pairs(avd_ctx* ctx, const uint8_t* small320, int mem, int n, float* flow_mean, float* flow_var, float* flow_out)
@@ -1348,40 +1177,34 @@ int avd_farneback_pairs(avd_ctx* ctx, const uint8_t* small320, int mem, int n, f
 int avd_analyze_frames_async(avd_ctx* ctx, const uint8_t* bgr, int mem, int n, int h, int w, int64_t row_stride,
                              int64_t frame_stride, avd_frame_record* records)
 {
-    return guarded(ctx, [&] { return impl_analyze_frames_async(ctx, bgr, mem, n, h, w, row_stride, frame_stride, records); });
+    return analyze_clip(ctx, bgr_clip(bgr, mem, n, h, w, row_stride, frame_stride), records, Wait::no);
 }
 
 int avd_synchronize(avd_ctx* ctx) { return guarded(ctx, [&] { return impl_synchronize(ctx); }, Pending::keep); }
 
 int avd_analyze_batch_async(avd_ctx* ctx, const avd_clip* clips, int nclips, avd_frame_record* records)
 {
-    return guarded(ctx, [&] { return impl_analyze_clips_async(ctx, clips, nclips, records); });
+    return analyze_clips(ctx, clips, nclips, records, Wait::no);
 }
 
 int avd_analyze_batch(avd_ctx* ctx, const avd_clip* clips, int nclips, avd_frame_record* records)
 {
-    return guarded(ctx, [&] {
-        const int rc = impl_analyze_clips_async(ctx, clips, nclips, records);
-        return rc ? rc : impl_synchronize(ctx);
-    });
+    return analyze_clips(ctx, clips, nclips, records, Wait::yes);
 }
 
 int avd_preprocess_picture(avd_ctx* ctx, const avd_picture* picture, uint8_t* small320, uint8_t* hash1024, int64_t* lap_sum, int64_t* lap_sumsq)
 {
-    return guarded(ctx, [&] { return impl_preprocess_picture(ctx, picture, small320, hash1024, lap_sum, lap_sumsq); });
+    return guarded(ctx, [&] { return impl_preprocess_one_picture(ctx, picture, small320, hash1024, lap_sum, lap_sumsq); });
 }
 
 int avd_analyze_pictures_async(avd_ctx* ctx, const avd_picture* clips, int nclips, avd_frame_record* records)
 {
-    return guarded(ctx, [&] { return impl_analyze_pictures_async(ctx, clips, nclips, records); });
+    return analyze_pictures(ctx, clips, nclips, records, Wait::no);
 }
 
 int avd_analyze_pictures(avd_ctx* ctx, const avd_picture* clips, int nclips, avd_frame_record* records)
 {
-    return guarded(ctx, [&] {
-        const int rc = impl_analyze_pictures_async(ctx, clips, nclips, records);
-        return rc ? rc : impl_synchronize(ctx);
-    });
+    return analyze_pictures(ctx, clips, nclips, records, Wait::yes);
 }
 
 int avd_preprocess_nv12(avd_ctx* ctx, const uint8_t* y, const uint8_t* uv, int mem, int n, int h, int w, int64_t y_row_stride,
@@ -1389,7 +1212,7 @@ int avd_preprocess_nv12(avd_ctx* ctx, const uint8_t* y, const uint8_t* uv, int m
                         uint8_t* hash1024, int64_t* lap_sum, int64_t* lap_sumsq)
 {
     const IngestClip k = nv12_clip(y, uv, mem, n, h, w, y_row_stride, uv_row_stride, y_frame_stride, uv_frame_stride);
-    return guarded(ctx, [&] { return impl_preprocess_nv12(ctx, k, small320, hash1024, lap_sum, lap_sumsq); });
+    return guarded(ctx, [&] { return impl_preprocess(ctx, k, small320, hash1024, lap_sum, lap_sumsq); });
 }
 
 int avd_analyze_frames_nv12_async(avd_ctx* ctx, const uint8_t* y, const uint8_t* uv, int mem, int n, int h, int w,
@@ -1397,7 +1220,7 @@ int avd_analyze_frames_nv12_async(avd_ctx* ctx, const uint8_t* y, const uint8_t*
                                   int64_t uv_frame_stride, avd_frame_record* records)
 {
     const IngestClip k = nv12_clip(y, uv, mem, n, h, w, y_row_stride, uv_row_stride, y_frame_stride, uv_frame_stride);
-    return guarded(ctx, [&] { return impl_analyze_frames_nv12_async(ctx, k, records); });
+    return analyze_clip(ctx, k, records, Wait::no);
 }
 
 int avd_analyze_frames_nv12(avd_ctx* ctx, const uint8_t* y, const uint8_t* uv, int mem, int n, int h, int w,
@@ -1405,10 +1228,7 @@ int avd_analyze_frames_nv12(avd_ctx* ctx, const uint8_t* y, const uint8_t* uv, i
                             avd_frame_record* records)
 {
     const IngestClip k = nv12_clip(y, uv, mem, n, h, w, y_row_stride, uv_row_stride, y_frame_stride, uv_frame_stride);
-    return guarded(ctx, [&] {
-        const int rc = impl_analyze_frames_nv12_async(ctx, k, records);
-        return rc ? rc : impl_synchronize(ctx);
-    });
+    return analyze_clip(ctx, k, records, Wait::yes);
 }
 
 int avd_preprocess_i420(avd_ctx* ctx, const uint8_t* y, const uint8_t* u, const uint8_t* v, int mem, int n, int h, int w, int64_t y_row_stride,
@@ -1416,7 +1236,7 @@ int avd_preprocess_i420(avd_ctx* ctx, const uint8_t* y, const uint8_t* u, const 
                         int64_t* lap_sum, int64_t* lap_sumsq)
 {
     const IngestClip k = i420_clip(y, u, v, mem, n, h, w, y_row_stride, c_row_stride, y_frame_stride, c_frame_stride);
-    return guarded(ctx, [&] { return impl_preprocess_i420(ctx, k, small320, hash1024, lap_sum, lap_sumsq); });
+    return guarded(ctx, [&] { return impl_preprocess(ctx, k, small320, hash1024, lap_sum, lap_sumsq); });
 }
 
 int avd_analyze_frames_i420_async(avd_ctx* ctx, const uint8_t* y, const uint8_t* u, const uint8_t* v, int mem, int n, int h, int w,
@@ -1424,7 +1244,7 @@ int avd_analyze_frames_i420_async(avd_ctx* ctx, const uint8_t* y, const uint8_t*
                                   avd_frame_record* records)
 {
     const IngestClip k = i420_clip(y, u, v, mem, n, h, w, y_row_stride, c_row_stride, y_frame_stride, c_frame_stride);
-    return guarded(ctx, [&] { return impl_analyze_frames_i420_async(ctx, k, records); });
+    return analyze_clip(ctx, k, records, Wait::no);
 }
 
 int avd_analyze_frames_i420(avd_ctx* ctx, const uint8_t* y, const uint8_t* u, const uint8_t* v, int mem, int n, int h, int w,
@@ -1432,16 +1252,13 @@ int avd_analyze_frames_i420(avd_ctx* ctx, const uint8_t* y, const uint8_t* u, co
                             avd_frame_record* records)
 {
     const IngestClip k = i420_clip(y, u, v, mem, n, h, w, y_row_stride, c_row_stride, y_frame_stride, c_frame_stride);
-    return guarded(ctx, [&] {
-        const int rc = impl_analyze_frames_i420_async(ctx, k, records);
-        return rc ? rc : impl_synchronize(ctx);
-    });
+    return analyze_clip(ctx, k, records, Wait::yes);
 }
 
 int avd_analyze_frames(avd_ctx* ctx, const uint8_t* bgr, int mem, int n, int h, int w, int64_t row_stride,
                        int64_t frame_stride, avd_frame_record* records)
 {
-    return guarded(ctx, [&] { return impl_analyze_frames(ctx, bgr, mem, n, h, w, row_stride, frame_stride, records); });
+    return analyze_clip(ctx, bgr_clip(bgr, mem, n, h, w, row_stride, frame_stride), records, Wait::yes);
 }
 
 int avd_cnn_param_counts(size_t* n_weights, size_t* n_biases)

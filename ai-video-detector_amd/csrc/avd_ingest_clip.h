@@ -1,0 +1,149 @@
+// avd_ingest_clip.h -- one clip as the ingest host path sees it: what it is, whether it is acceptable, where it lands in the staging buffer.
+// Pure host C++ (include/avd.h and the standard library; no HIP type, no avd_ctx), so a stand-alone program can include it
+// (tests/ingest_clip_check.cpp).
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+#include <algorithm>
+#include "../../include/avd.h"
+
+// format says what the planes are -- nothing downstream looks at which pointers are null to find out:
+//   AVD_FMT_BGR24  data = the interleaved frames (row_stride / frame_stride)
+//   AVD_FMT_NV12   data = the Y plane, uv = the interleaved chroma plane (uv_row_stride / uv_frame_stride)
+//   AVD_FMT_I420   data = Y, uv = the U plane, v = the V plane; the uv strides hold for both chroma planes
+// rotate: quarter turns clockwise from the stored picture (h, w, the planes and strides: always the STORED one) to the displayed picture, whose
+// size the geometry tables, the band plan and every result follow (4:2:0 clips only).
+// A clip is made by bgr_clip / nv12_clip / i420_clip (the entry points that name their format), from_public (avd_clip) or from_picture
+// (avd_picture), and by nothing else.
+struct IngestClip {
+    int format;
+    const uint8_t *data, *uv, *v;
+    int mem, n, h, w;
+    int64_t row_stride, frame_stride, uv_row_stride, uv_frame_stride;
+    int rotate;
+    int disp_h() const { return rotate & 1 ? w : h; }
+    int disp_w() const { return rotate & 1 ? h : w; }
+};
+
+// status 0: accepted; otherwise an avd_status and the text avd_last_error reports
+struct Refusal { int status; const char* why; };
+
+inline IngestClip bgr_clip(const uint8_t* bgr, int mem, int n, int h, int w, int64_t row_stride, int64_t frame_stride)
+{
+    IngestClip k{};
+    k.format = AVD_FMT_BGR24;
+    k.data = bgr; k.mem = mem; k.n = n; k.h = h; k.w = w;
+    k.row_stride = row_stride; k.frame_stride = frame_stride;
+    return k;
+}
+
+inline IngestClip nv12_clip(const uint8_t* y, const uint8_t* uv, int mem, int n, int h, int w, int64_t y_row, int64_t uv_row, int64_t y_frame,
+                            int64_t uv_frame)
+{
+    IngestClip k = bgr_clip(y, mem, n, h, w, y_row, y_frame);
+    k.format = AVD_FMT_NV12;
+    k.uv = uv; k.uv_row_stride = uv_row; k.uv_frame_stride = uv_frame;
+    return k;
+}
+
+inline IngestClip i420_clip(const uint8_t* y, const uint8_t* u, const uint8_t* v, int mem, int n, int h, int w, int64_t y_row, int64_t c_row,
+                            int64_t y_frame, int64_t c_frame)
+{
+    IngestClip k = nv12_clip(y, u, mem, n, h, w, y_row, c_row, y_frame, c_frame);
+    k.format = AVD_FMT_I420;
+    k.v = v;
+    return k;
+}
+
+// avd_clip is frozen at ABI 3 and has no format field: a clip with uv set is NV12, any other is BGR.  The ONE place where a format is inferred
+// from a pointer.
+inline IngestClip from_public(const avd_clip& c)
+{
+    if (c.uv) return nv12_clip(c.data, c.uv, c.mem, c.n, c.h, c.w, c.row_stride, c.uv_row_stride, c.frame_stride, c.uv_frame_stride);
+    return bgr_clip(c.data, c.mem, c.n, c.h, c.w, c.row_stride, c.frame_stride);
+}
+
+// avd_picture spells its format out.  Refused here: what the descriptor alone can get wrong; the planes, strides and sizes are check_clip's.
+inline Refusal from_picture(const avd_picture& p, IngestClip& k)
+{
+    if (p.struct_size != sizeof(avd_picture)) return {AVD_ERR_ARG, "avd_picture.struct_size is not sizeof(avd_picture)"};
+    if (p.format != AVD_FMT_BGR24 && p.format != AVD_FMT_NV12 && p.format != AVD_FMT_I420) return {AVD_ERR_ARG, "bad avd_picture.format"};
+    if (p.rotate < 0 || p.rotate > 3) return {AVD_ERR_ARG, "avd_picture.rotate must be 0 .. 3 quarter turns"};
+    if (p.reserved != 0) return {AVD_ERR_ARG, "avd_picture.reserved must be 0"};
+    if (p.format == AVD_FMT_BGR24) {
+        if (p.rotate) return {AVD_ERR_UNSUPPORTED, "a turned BGR picture is not on the path: cv2 hands BGR over already rotated"};
+        k = bgr_clip(p.plane[0], p.mem, p.n, p.h, p.w, p.row_stride[0], p.frame_stride[0]);
+    } else if (p.format == AVD_FMT_NV12) {
+        k = nv12_clip(p.plane[0], p.plane[1], p.mem, p.n, p.h, p.w, p.row_stride[0], p.row_stride[1], p.frame_stride[0], p.frame_stride[1]);
+    } else {
+        if (p.row_stride[1] != p.row_stride[2] || p.frame_stride[1] != p.frame_stride[2])
+            return {AVD_ERR_ARG, "the U and V planes of an I420 picture share their strides"};
+        k = i420_clip(p.plane[0], p.plane[1], p.plane[2], p.mem, p.n, p.h, p.w, p.row_stride[0], p.row_stride[1], p.frame_stride[0], p.frame_stride[1]);
+    }
+    k.rotate = p.rotate;
+    return {0, nullptr};
+}
+
+// The one argument check of every ingest entry point.  A clip with several faults is refused for the FIRST of, in this order (include/avd.h):
+// mem; the size range; even width and height (4:2:0); the 32 x 32 minimum (of the displayed picture: a quarter turn exchanges h and w, which
+// this test does not notice); null planes of a clip that has frames; strides.
+inline Refusal check_clip(const IngestClip& k)
+{
+    const bool bgr = k.format == AVD_FMT_BGR24, planar = k.format == AVD_FMT_I420;
+    const int n = k.n, h = k.h, w = k.w;
+    if (k.mem != AVD_MEM_HOST && k.mem != AVD_MEM_DEVICE) return {AVD_ERR_ARG, "mem must be AVD_MEM_HOST or AVD_MEM_DEVICE"};
+    if (n < 0 || h <= 0 || w <= 0 || h > 16384 || w > 16384) return {AVD_ERR_ARG, "bad frame geometry"};
+    if (!bgr && ((h | w) & 1)) return {AVD_ERR_UNSUPPORTED, planar ? "I420 needs even width and height" : "NV12 needs even width and height"};
+    if (h < AVD_HASH || w < AVD_HASH) return {AVD_ERR_UNSUPPORTED, "frame smaller than 32x32: INTER_AREA upscaling is not on the path"};
+    if (n > 0 && (!k.data || (!bgr && !k.uv) || (planar && !k.v)))
+        return {AVD_ERR_ARG, bgr ? "null frame pointer" : (planar ? "null I420 plane pointer" : "null plane pointer")};
+    const int64_t row = bgr ? (int64_t)w * 3 : w, crow = planar ? w / 2 : w;      // bytes of a luma (BGR: frame) row and of a chroma row
+    bool small = k.row_stride < row || (n > 1 && k.frame_stride < k.row_stride * (h - 1) + row);
+    if (!bgr) small = small || k.uv_row_stride < crow || (n > 1 && k.uv_frame_stride < k.uv_row_stride * (h / 2 - 1) + crow);
+    if (small) return {AVD_ERR_ARG, bgr ? "strides smaller than the frame" : (planar ? "strides smaller than the I420 planes" : "strides smaller than the planes")};
+    return {0, nullptr};
+}
+
+// ---- staging plan of a HOST clip --------------------------------------------------------------------------------------------------------
+// bytes spanned by n frames of `rows` rows of `row_bytes` bytes each, with the given strides
+inline size_t plane_span(int64_t frame_stride, int n, int64_t row_stride, int rows, size_t row_bytes)
+{
+    return (size_t)frame_stride * (n - 1) + (size_t)row_stride * (rows - 1) + row_bytes;
+}
+
+inline size_t round256(size_t v) { return (v + 255) / 256 * 256; }
+
+// Where a HOST clip lands in the staging buffer: BGR as one span; NV12 as the Y span with the chroma span on the next 256-byte boundary
+// behind it.  The three planes of I420 usually come out of ONE buffer per clip (a y4m map, a rawvideo pipe: Y, U, V of a frame adjacent), where
+// the per-plane spans overlap almost entirely: spans that overlap or touch are merged and copied once, so no host byte crosses the link twice, and
+// a plane sits at its own offset inside the merged span; separately allocated planes stay three spans.  `total` (a multiple of 256) is what
+// the clip occupies, `copied` the bytes that cross the link; a device clip is used in place and occupies nothing.
+struct StageSpan { const uint8_t* src; size_t bytes, off; };       // off: from the clip's place in the staging buffer, a multiple of 256
+struct ClipStage { StageSpan span[3]; int nspans; size_t plane_off[3], total, copied; };      // plane_off: data, uv, v
+
+inline ClipStage clip_stage(const IngestClip& c)
+{
+    ClipStage s{};
+    if (c.mem != AVD_MEM_HOST || c.n <= 0) return s;
+    const bool bgr = c.format == AVD_FMT_BGR24, planar = c.format == AVD_FMT_I420;
+    const uint8_t* src[3] = {c.data, c.uv, c.v};
+    const int planes = bgr ? 1 : (planar ? 3 : 2);
+    size_t len[3] = {plane_span(c.frame_stride, c.n, c.row_stride, c.h, (size_t)c.w * (bgr ? 3 : 1)), 0, 0};
+    if (!bgr) len[1] = len[2] = plane_span(c.uv_frame_stride, c.n, c.uv_row_stride, c.h / 2, (size_t)(planar ? c.w / 2 : c.w));
+    int order[3] = {0, 1, 2};
+    if (planar) std::sort(order, order + 3, [&](int a, int b) { return (uintptr_t)src[a] < (uintptr_t)src[b]; });
+    for (int i = 0; i < planes; i++) {
+        const int p = order[i];
+        StageSpan* last = s.nspans ? &s.span[s.nspans - 1] : nullptr;
+        if (planar && last && (uintptr_t)src[p] <= (uintptr_t)last->src + last->bytes)
+            last->bytes = std::max(last->bytes, (size_t)(src[p] - last->src) + len[p]);
+        else {
+            s.span[s.nspans] = StageSpan{src[p], len[p], last ? round256(last->off + last->bytes) : 0};
+            last = &s.span[s.nspans++];
+        }
+        s.plane_off[p] = last->off + (size_t)(src[p] - last->src);
+    }
+    for (int i = 0; i < s.nspans; i++) s.copied += s.span[i].bytes;
+    s.total = round256(s.span[s.nspans - 1].off + s.span[s.nspans - 1].bytes);
+    return s;
+}

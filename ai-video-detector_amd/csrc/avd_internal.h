@@ -7,6 +7,7 @@
 #include <type_traits>
 #include <vector>
 #include "../../include/avd.h"
+#include "avd_ingest_clip.h"      // IngestClip: one clip of an ingest call, its argument check and its staging plan (host only)
 
 #define AVD_FB_LEVELS 4            // pyramid scales 1/8,1/4,1/2,1 of 320 (see avd_farneback.hip)
 #define AVD_NPIX (AVD_SMALL * AVD_SMALL)
@@ -67,17 +68,6 @@ struct I420Params {
     const uint8_t *u, *v;              // planar U and V of frame 0, uint8[h/2][w/2] each (YV12: the caller passes them exchanged)
     int64_t c_row_stride, c_frame_stride;   // shared by the two planes
     YuvConsts k;
-};
-
-// One clip as the ingest code sees it: the public avd_clip (frozen at ABI 3: BGR, or NV12 with uv set) plus the third plane of planar
-// 4:2:0 input and the display rotation of avd_picture.  v != nullptr: I420 -- data = Y, uv = the U plane, v = the V plane; uv_row_stride /
-// uv_frame_stride hold for both.  rotate: quarter turns clockwise from the stored picture (h, w, the planes and strides: always the STORED one)
-// to the displayed picture, whose size the geometry tables, the band plan and every result follow (4:2:0 clips only).
-struct IngestClip : avd_clip {
-    const uint8_t* v;
-    int rotate;
-    int disp_h() const { return rotate & 1 ? w : h; }
-    int disp_w() const { return rotate & 1 ? h : w; }
 };
 
 // ---- device-side parameter blocks ------------------------------------------------
@@ -334,9 +324,9 @@ int avd_ws_geometry(avd_ctx* ctx, int h, int w);                       // make (
 int avd_ws_reserve_frames(avd_ctx* ctx, int n, size_t rowbuf_elems, size_t lappart_elems);   // grow-only per-frame buffers
 int avd_ws_reserve(avd_ctx* ctx, int n, int h, int w);                 // both, for one clip at offset 0
 int avd_ws_reserve_fb(avd_ctx* ctx, int n);
-// the clip's frames, resident at d_in (BGR, d_uv null) or d_in / d_uv (NV12: Y rows at d_in + f*frame_stride + y*row_stride, chroma rows at
+// the clip's frames, resident at d_in (BGR) or d_in / d_uv (NV12: Y rows at d_in + f*frame_stride + y*row_stride, chroma rows at
 // d_uv + f*uv_frame_stride + (y/2)*uv_row_stride) or d_in / d_uv / d_v (I420: d_uv is the U plane, both chroma planes with the uv strides),
-// into the clip's slice of the per-frame buffers; the clip's geometry is current
+// into the clip's slice of the per-frame buffers; which of the three it is says clip.format; the clip's geometry is current
 int launch_preprocess(avd_ctx* ctx, const IngestClip& clip, const uint8_t* d_in, const uint8_t* d_uv, const uint8_t* d_v);
 int launch_hash(avd_ctx* ctx, int n);
 int avd_calls_in_flight();      // avd_capi.hip: contexts of this process holding an enqueued, undrained avd_analyze_* call

@@ -953,11 +953,12 @@ int launch_preprocess(avd_ctx* ctx, const IngestClip& clip, const uint8_t* d_in,
     const int n = clip.n;
     const int grid = (n * P.nbands + 7) / 8 * 8;
     const size_t tile = lds_tile_bytes(P.rows_per_band + 2, P.pitch);
+    const bool bgr = clip.format == AVD_FMT_BGR24, planar = clip.format == AVD_FMT_I420;
     // the planar chroma planes are read 8 bytes at a time (fill_i420_tables), every other plane 16
-    const bool chroma_ok = d_v ? aligned_to(8, d_uv, clip.uv_row_stride, clip.uv_frame_stride) && aligned_to(8, d_v, clip.uv_row_stride, clip.uv_frame_stride)
-                               : !d_uv || aligned16(d_uv, clip.uv_row_stride, clip.uv_frame_stride);
+    const bool chroma_ok = planar ? aligned_to(8, d_uv, clip.uv_row_stride, clip.uv_frame_stride) && aligned_to(8, d_v, clip.uv_row_stride, clip.uv_frame_stride)
+                                  : bgr || aligned16(d_uv, clip.uv_row_stride, clip.uv_frame_stride);
     const bool vec = P.w % 16 == 0 && aligned16(d_in, clip.row_stride, clip.frame_stride) && chroma_ok;
-    const int ni = vec && !d_uv ? band_plan(P.w).ni : 0;
+    const int ni = vec && bgr ? band_plan(P.w).ni : 0;
     auto launch = [&](IngestKernel id, auto kernel, size_t lds, auto... source) {
         ctx->ingest_plan = IngestPlan{P.h, P.w, P.rows_per_band, P.nbands, P.pitch, ni, (int)lds, id};
         ctx->ingest_plan_valid = 1;
@@ -967,8 +968,8 @@ int launch_preprocess(avd_ctx* ctx, const IngestClip& clip, const uint8_t* d_in,
     };
     const size_t tabs = lds_nvtab_off(P.rows_per_band + 2, P.pitch) + kNvTabBytes;      // tile + the three gray tables
     const int rot = clip.rotate;
-    if (rot && !d_uv) { ctx->err = "internal error: a turned BGR clip reached the ingest launch"; return AVD_ERR_DEVICE; }
-    if (d_v) {
+    if (rot && bgr) { ctx->err = "internal error: a turned BGR clip reached the ingest launch"; return AVD_ERR_DEVICE; }
+    if (planar) {
         I420Params ip{};
         ip.u = d_uv; ip.v = d_v; ip.c_row_stride = clip.uv_row_stride; ip.c_frame_stride = clip.uv_frame_stride;
         build_yuv_consts(ip.k);
@@ -978,7 +979,7 @@ int launch_preprocess(avd_ctx* ctx, const IngestClip& clip, const uint8_t* d_in,
         else if (rot == 2) launch(kIngestI420Scalar, k_preprocess_i420<false, 2>, tile, d_in, ip);
         else if (vec) launch(kIngestI420Tables, k_preprocess_i420<true, 0>, tabs, d_in, ip);
         else launch(kIngestI420Scalar, k_preprocess_i420<false, 0>, tile, d_in, ip);
-    } else if (d_uv) {
+    } else if (!bgr) {
         Nv12Params nv{};
         nv.uv = d_uv; nv.uv_row_stride = clip.uv_row_stride; nv.uv_frame_stride = clip.uv_frame_stride;
         build_yuv_consts(nv.k);

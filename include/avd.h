@@ -24,6 +24,14 @@
  *     A thread that waits in avd_synchronize may enqueue the exact re-run of another
  *     ctx's flagged pairs meanwhile (option "tail_help"); that ctx's results and
  *     errors still come out of its own avd_synchronize.
+ *   - every ingest entry point (avd_preprocess_*, avd_analyze_*) checks its clips the same way, before anything is
+ *     launched.  A clip with several faults is refused for the FIRST of, in this order: mem that is neither
+ *     AVD_MEM_HOST nor AVD_MEM_DEVICE (AVD_ERR_ARG); a size out of range -- n < 0, h or w outside 1 .. 16384
+ *     (AVD_ERR_ARG); an odd width or height of 4:2:0 input (AVD_ERR_UNSUPPORTED); a picture below 32 x 32
+ *     (AVD_ERR_UNSUPPORTED); a null plane of a clip with n > 0 (AVD_ERR_ARG); strides smaller than the planes
+ *     (AVD_ERR_ARG).  What an avd_picture alone can get wrong (struct_size, format, rotate, reserved, BGR with a
+ *     rotation, U and V strides that differ) is refused before any of these; a records pointer that is null while
+ *     there are frames to write, after all of them.  The clips of a batch are checked in order.
  *   - if no HIP device is usable avd_create fails (AVD_ERR_DEVICE): there is no
  *     CPU fallback in this library.
  */
