@@ -44,6 +44,9 @@ def analyze(path: str, meta: dict):
         surface = getattr(src, "surface", "bgr")             # "nv12" / "i420": decoder pictures, the colour conversion happens on the GPU
         # stored pictures with a display rotation (src.width / src.height are the displayed picture's): the turn happens on the GPU too
         turn = {"rotate": int(src.rotate)} if getattr(src, "rotate", 0) else {}
+        # full-range pictures (yuvj420p): converted with libswscale's full-range tables, on the GPU too; a source that yields BGR has none
+        if surface != "bgr" and getattr(src, "full_range", False):
+            turn["full_range"] = True
 
         def frames():
             for fr in src.sampled(step):

@@ -62,6 +62,7 @@ class AvdClip(C.Structure):
 
 
 AVD_FMT_BGR24, AVD_FMT_NV12, AVD_FMT_I420 = 0, 1, 2
+AVD_FMT_FULL_RANGE = 0x100      # flag OR-ed into a 4:2:0 layout: the samples use 0 .. 255 (ffmpeg's yuvj420p)
 
 
 class AvdPicture(C.Structure):
@@ -385,32 +386,42 @@ class Context:
         out = self._records_call(symbol, c.args(), c.n, rec)
         return out if rec is None else c.keep
 
-    def preprocess_nv12(self, y, uv, rotate: int = 0):
-        """rotate: quarter turns clockwise from the stored planes to the displayed picture (avd_picture); 0 = the format's own entry point."""
-        return self.preprocess_picture((y, uv), rotate) if rotate else self._preprocess("avd_preprocess_nv12", self._plane_ptrs((y, uv)))
+    def preprocess_nv12(self, y, uv, rotate: int = 0, full_range: bool = False):
+        """rotate: quarter turns clockwise from the stored planes to the displayed picture; full_range: the samples use 0 .. 255 (ffmpeg's J
+        formats).  Either goes through the descriptor (avd_picture); without them this is the format's own entry point."""
+        if rotate or full_range:
+            return self.preprocess_picture((y, uv), rotate, full_range)
+        return self._preprocess("avd_preprocess_nv12", self._plane_ptrs((y, uv)))
 
-    def analyze_frames_nv12(self, y, uv, rotate: int = 0) -> np.ndarray:
-        return self.analyze_pictures([(y, uv)], [rotate])[0] if rotate else self._analyze("avd_analyze_frames_nv12", self._plane_ptrs((y, uv)))
+    def analyze_frames_nv12(self, y, uv, rotate: int = 0, full_range: bool = False) -> np.ndarray:
+        if rotate or full_range:
+            return self.analyze_pictures([(y, uv)], [rotate], [full_range])[0]
+        return self._analyze("avd_analyze_frames_nv12", self._plane_ptrs((y, uv)))
 
-    def analyze_frames_nv12_async(self, y, uv, rec: np.ndarray, rotate: int = 0):
-        if rotate:
-            return self.analyze_pictures_async([(y, uv)], rec, [rotate])[0][0]
+    def analyze_frames_nv12_async(self, y, uv, rec: np.ndarray, rotate: int = 0, full_range: bool = False):
+        if rotate or full_range:
+            return self.analyze_pictures_async([(y, uv)], rec, [rotate], [full_range])[0][0]
         return self._analyze("avd_analyze_frames_nv12_async", self._plane_ptrs((y, uv)), rec)
 
-    def preprocess_i420(self, y, u, v, rotate: int = 0):
-        return self.preprocess_picture((y, u, v), rotate) if rotate else self._preprocess("avd_preprocess_i420", self._plane_ptrs((y, u, v)))
+    def preprocess_i420(self, y, u, v, rotate: int = 0, full_range: bool = False):
+        if rotate or full_range:
+            return self.preprocess_picture((y, u, v), rotate, full_range)
+        return self._preprocess("avd_preprocess_i420", self._plane_ptrs((y, u, v)))
 
-    def analyze_frames_i420(self, y, u, v, rotate: int = 0) -> np.ndarray:
-        return self.analyze_pictures([(y, u, v)], [rotate])[0] if rotate else self._analyze("avd_analyze_frames_i420", self._plane_ptrs((y, u, v)))
+    def analyze_frames_i420(self, y, u, v, rotate: int = 0, full_range: bool = False) -> np.ndarray:
+        if rotate or full_range:
+            return self.analyze_pictures([(y, u, v)], [rotate], [full_range])[0]
+        return self._analyze("avd_analyze_frames_i420", self._plane_ptrs((y, u, v)))
 
-    def analyze_frames_i420_async(self, y, u, v, rec: np.ndarray, rotate: int = 0):
-        if rotate:
-            return self.analyze_pictures_async([(y, u, v)], rec, [rotate])[0][0]
+    def analyze_frames_i420_async(self, y, u, v, rec: np.ndarray, rotate: int = 0, full_range: bool = False):
+        if rotate or full_range:
+            return self.analyze_pictures_async([(y, u, v)], rec, [rotate], [full_range])[0][0]
         return self._analyze("avd_analyze_frames_i420_async", self._plane_ptrs((y, u, v)), rec)
 
     # -- pictures by descriptor (include/avd.h: avd_picture): any format, with a display rotation -------------------------------------------
-    def _picture(self, clip, rotate: int = 0):
+    def _picture(self, clip, rotate: int = 0, full_range: bool = False):
         """clip: a BGR frame stack uint8[N,H,W,3], an NV12 pair (y, uv) or an I420 triple (y, u, v) of the STORED picture; numpy or torch.
+        full_range: AVD_FMT_FULL_RANGE is OR-ed into the format (the library refuses it on BGR).
         -> (AvdPicture, frame count, keepalive).  The binding's own checks (the rotation, U and V of equal strides, planes all numpy or all
         torch) are made before the library is touched."""
         if isinstance(rotate, bool) or not isinstance(rotate, (int, np.integer)) or not 0 <= rotate <= 3:
@@ -418,44 +429,52 @@ class Context:
         p = AvdPicture()
         p.struct_size, p.rotate, p.reserved = C.sizeof(AvdPicture), int(rotate), 0
         c = self._clip(clip)
-        p.format, p.mem, p.n, p.h, p.w = c.format, c.mem, c.n, c.h, c.w
+        p.format, p.mem, p.n, p.h, p.w = c.format | (AVD_FMT_FULL_RANGE if full_range else 0), c.mem, c.n, c.h, c.w
         for i, plane in enumerate(c.planes):
             p.plane[i], p.row_stride[i], p.frame_stride[i] = plane, c.rows[i], c.frames[i]
         return p, c.n, c.keep
 
-    def preprocess_picture(self, clip, rotate: int = 0):
-        """-> (small320, hash1024, lap_sum, lap_sumsq) of the DISPLAYED picture, as preprocess_bgr / _nv12 / _i420 on the turned planes."""
-        p, n, keep = self._picture(clip, rotate)
+    def preprocess_picture(self, clip, rotate: int = 0, full_range: bool = False):
+        """-> (small320, hash1024, lap_sum, lap_sumsq) of the DISPLAYED picture, as preprocess_bgr / _nv12 / _i420 on the turned planes;
+        full_range: the 4:2:0 samples use 0 .. 255 and are converted as libswscale converts yuvj420p."""
+        p, n, keep = self._picture(clip, rotate, full_range)
         return self._outputs_call("avd_preprocess_picture", (C.byref(p),), n)
 
-    def _picture_array(self, clips, rotates):
+    def _picture_array(self, clips, rotates, full_ranges=None):
         rotates = [0] * len(clips) if rotates is None else list(rotates)
         if len(rotates) != len(clips):
             raise ValueError("one rotation per clip")
+        full_ranges = [False] * len(clips) if full_ranges is None else list(full_ranges)
+        if len(full_ranges) != len(clips):
+            raise ValueError("one range per clip")
         arr = (AvdPicture * len(clips))()
         keep, counts = [], []
-        for i, (c, r) in enumerate(zip(clips, rotates)):
-            arr[i], n, k = self._picture(c, r)
+        for i, (c, r, fr) in enumerate(zip(clips, rotates, full_ranges)):
+            arr[i], n, k = self._picture(c, r, fr)
             keep.append(k)
             counts.append(n)
         return arr, counts, keep
 
-    def analyze_pictures(self, clips, rotates=None):
-        """A batch by descriptor: BGR stacks, NV12 pairs and I420 triples in any mix, each with its rotation (default 0).
-        -> list of record arrays, one per clip, identical to one call per clip."""
-        arr, counts, keep = self._picture_array(clips, rotates)
+    def analyze_pictures(self, clips, rotates=None, full_ranges=None):
+        """A batch by descriptor: BGR stacks, NV12 pairs and I420 triples in any mix, each with its rotation (default 0) and its range
+        (default limited; True = full range, 4:2:0 clips only).  -> list of record arrays, one per clip, identical to one call per clip."""
+        arr, counts, keep = self._picture_array(clips, rotates, full_ranges)
         rec = self._records_call("avd_analyze_pictures", (arr, len(clips)), sum(counts))
         return list(np.split(rec, np.cumsum(counts)[:-1])) if counts else []
 
-    def analyze_pictures_async(self, clips, rec: np.ndarray, rotates=None):
+    def analyze_pictures_async(self, clips, rec: np.ndarray, rotates=None, full_ranges=None):
         """Enqueue only; rec (RECORD_DTYPE, sum of the clips' frames) is filled by synchronize().  Returns (keepalive, frame counts)."""
-        arr, counts, keep = self._picture_array(clips, rotates)
+        arr, counts, keep = self._picture_array(clips, rotates, full_ranges)
         self._records_call("avd_analyze_pictures_async", (arr, len(clips)), sum(counts), rec)
         return keep, counts
 
     def ingest_rotate(self) -> int:
         """The rotation the last ingest launch of this context ran with; avd_debug_fetch "ingest_rotate"."""
         return int(self.debug_fetch("ingest_rotate", (1,), np.int32)[0])
+
+    def ingest_range(self) -> int:
+        """1 if the last ingest launch of this context ran with full-range conversion constants, else 0; avd_debug_fetch "ingest_range"."""
+        return int(self.debug_fetch("ingest_range", (1,), np.int32)[0])
 
     def stage_bytes(self) -> int:
         """Bytes the last ingest call of this context copied from host memory (0: device input); avd_debug_fetch "stage_bytes"."""

@@ -208,12 +208,15 @@ class FrameAnalyzer:
 
     # -- the same for decoder surfaces: an iterable of (y uint8[H,W], uv uint8[H/2,W]) pairs ----------------
     # rotate: quarter turns clockwise from the stored pictures to the displayed one (a container's display rotation; include/avd.h, avd_picture)
-    def records_stream_nv12(self, surfaces, rotate: int = 0) -> np.ndarray:
-        return self._stream(surfaces, lambda items: self.ctx.analyze_frames_nv12(*(np.stack([sf[k] for sf in items]) for k in range(2)), rotate=rotate))
+    # full_range: the samples use 0 .. 255 (ffmpeg's J formats; AVD_FMT_FULL_RANGE)
+    def records_stream_nv12(self, surfaces, rotate: int = 0, full_range: bool = False) -> np.ndarray:
+        return self._stream(surfaces, lambda items: self.ctx.analyze_frames_nv12(*(np.stack([sf[k] for sf in items]) for k in range(2)), rotate=rotate,
+                                                                                 full_range=full_range))
 
     # -- and for planar pictures (software decoders, .y4m): an iterable of (y uint8[H,W], u uint8[H/2,W/2], v uint8[H/2,W/2]) triples ----
-    def records_stream_i420(self, surfaces, rotate: int = 0) -> np.ndarray:
-        return self._stream(surfaces, lambda items: self.ctx.analyze_frames_i420(*(np.stack([sf[k] for sf in items]) for k in range(3)), rotate=rotate))
+    def records_stream_i420(self, surfaces, rotate: int = 0, full_range: bool = False) -> np.ndarray:
+        return self._stream(surfaces, lambda items: self.ctx.analyze_frames_i420(*(np.stack([sf[k] for sf in items]) for k in range(3)), rotate=rotate,
+                                                                                 full_range=full_range))
 
 
 class ClipsInFlight:

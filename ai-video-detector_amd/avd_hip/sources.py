@@ -40,6 +40,8 @@ class FrameSource:
     # quarter turns clockwise from the pictures sampled() yields (the STORED ones) to the displayed picture; width / height are the displayed
     # picture's, as cv2's capture properties are (orientation-auto)
     rotate: int = 0
+    # the 4:2:0 pictures sampled() yields are full range (0 .. 255: ffmpeg's yuvj420p); means nothing for a source that yields BGR
+    full_range: bool = False
 
     def sampled(self, step: int) -> Iterator[np.ndarray]:
         raise NotImplementedError
@@ -68,7 +70,8 @@ class Y4mSource(FrameSource):
     ``planar=True`` the file's own I420 planes as three views of the map (no copy, no interleave).
     A header token ``XAVD_ROTATE=<0|90|180|270>`` (YUV4MPEG2 ``X`` tokens are application comments that other readers ignore) carries a
     container's display rotation, clockwise: ``rotate`` is its quarter turns, ``width`` / ``height`` are the DISPLAYED picture's, the planes
-    yielded are the stored ones."""
+    yielded are the stored ones.  ``XCOLORRANGE=FULL`` (what ffmpeg's y4m muxer writes for yuvj420p) sets ``full_range``; ``XCOLORRANGE=LIMITED``
+    and no token mean limited range."""
     surface = "nv12"
 
     def __init__(self, path: str, planar: bool = False):
@@ -96,6 +99,11 @@ class Y4mSource(FrameSource):
                 if deg not in ("0", "90", "180", "270"):
                     raise ValueError("XAVD_ROTATE must be 0, 90, 180 or 270")
                 self.rotate = int(deg) // 90
+            elif tag == b"X" and val.startswith("COLORRANGE="):
+                rng = val[len("COLORRANGE="):]
+                if rng not in ("FULL", "LIMITED"):
+                    raise ValueError("XCOLORRANGE must be FULL or LIMITED")
+                self.full_range = rng == "FULL"
         if w <= 0 or h <= 0 or (w | h) & 1:
             raise ValueError("bad or odd picture size")
         if not chroma.startswith("420") or "p1" in chroma:          # 420p10 / p12 / p16: more than 8 bits
@@ -143,12 +151,14 @@ class Y4mSource(FrameSource):
         self._map = None
 
 
-def write_y4m(path: str, y: np.ndarray, uv: np.ndarray, fps=(30, 1), rotate: int = 0) -> None:
+def write_y4m(path: str, y: np.ndarray, uv: np.ndarray, fps=(30, 1), rotate: int = 0, full_range: bool = False) -> None:
     """NV12 surfaces (y uint8[N,H,W], uv uint8[N,H/2,W] interleaved) -> a YUV4MPEG2 file (tests, tools).  rotate: display rotation in
-    DEGREES clockwise, written as the XAVD_ROTATE token when non-zero (Y4mSource)."""
+    DEGREES clockwise, written as the XAVD_ROTATE token when non-zero (Y4mSource); full_range: the XCOLORRANGE=FULL token, written only
+    when true."""
     n, h, w = y.shape
     with open(path, "wb") as f:
-        f.write(b"YUV4MPEG2 W%d H%d F%d:%d Ip A1:1 C420jpeg%s\n" % (w, h, fps[0], fps[1], b" XAVD_ROTATE=%d" % rotate if rotate else b""))
+        f.write(b"YUV4MPEG2 W%d H%d F%d:%d Ip A1:1 C420jpeg%s%s\n" % (w, h, fps[0], fps[1], b" XAVD_ROTATE=%d" % rotate if rotate else b"",
+                                                                   b" XCOLORRANGE=FULL" if full_range else b""))
         for i in range(n):
             f.write(b"FRAME\n")
             f.write(np.ascontiguousarray(y[i]).tobytes())

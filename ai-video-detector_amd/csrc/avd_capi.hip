@@ -827,6 +827,13 @@ static int64_t impl_debug_fetch(avd_ctx* ctx, const char* name, void* out, size_
         std::memcpy(out, &r, sizeof r);
         return (int64_t)sizeof r;
     }
+    if (std::strcmp(name, "ingest_range") == 0) {      // host state: 1 if that launch ran with full-range conversion constants
+        if (!ctx->ingest_plan_valid) { ctx->err = "ingest_range not recorded yet: no ingest kernel was launched on this context"; return AVD_ERR_ARG; }
+        if (out_bytes < sizeof(int32_t)) { ctx->err = "ingest_range is int32[1]"; return AVD_ERR_ARG; }
+        const int32_t r = ctx->ingest_range;
+        std::memcpy(out, &r, sizeof r);
+        return (int64_t)sizeof r;
+    }
     if (std::strcmp(name, "stage_bytes") == 0) {       // host state: bytes the last ingest call copied from host memory (0: device input)
         if (ctx->stage_bytes < 0) { ctx->err = "stage_bytes not recorded yet: no ingest call has run on this context"; return AVD_ERR_ARG; }
         if (out_bytes < sizeof(int64_t)) { ctx->err = "stage_bytes is int64[1]"; return AVD_ERR_ARG; }

@@ -13,6 +13,7 @@
 //   AVD_FMT_I420   data = Y, uv = the U plane, v = the V plane; the uv strides hold for both chroma planes
 // rotate: quarter turns clockwise from the stored picture (h, w, the planes and strides: always the STORED one) to the displayed picture, whose
 // size the geometry tables, the band plan and every result follow (4:2:0 clips only).
+// full_range: AVD_FMT_FULL_RANGE of the descriptor, taken out of `format`, which stays the plain layout.
 // A clip is made by bgr_clip / nv12_clip / i420_clip (the entry points that name their format), from_public (avd_clip) or from_picture
 // (avd_picture), and by nothing else.
 struct IngestClip {
@@ -21,6 +22,7 @@ struct IngestClip {
     int mem, n, h, w;
     int64_t row_stride, frame_stride, uv_row_stride, uv_frame_stride;
     int rotate;
+    int full_range;       // 4:2:0 clips: the samples use 0 .. 255 (ffmpeg's J formats), not 16 .. 235 / 240; 0 from every entry point but from_picture
     int disp_h() const { return rotate & 1 ? w : h; }
     int disp_w() const { return rotate & 1 ? h : w; }
 };
@@ -63,17 +65,21 @@ inline IngestClip from_public(const avd_clip& c)
     return bgr_clip(c.data, c.mem, c.n, c.h, c.w, c.row_stride, c.frame_stride);
 }
 
-// avd_picture spells its format out.  Refused here: what the descriptor alone can get wrong; the planes, strides and sizes are check_clip's.
+// avd_picture spells its format out: the layout in the low byte, AVD_FMT_FULL_RANGE above it.  Refused here: what the descriptor alone can get
+// wrong, in the order of the lines below; the planes, strides and sizes are check_clip's.
 inline Refusal from_picture(const avd_picture& p, IngestClip& k)
 {
     if (p.struct_size != sizeof(avd_picture)) return {AVD_ERR_ARG, "avd_picture.struct_size is not sizeof(avd_picture)"};
-    if (p.format != AVD_FMT_BGR24 && p.format != AVD_FMT_NV12 && p.format != AVD_FMT_I420) return {AVD_ERR_ARG, "bad avd_picture.format"};
+    const int layout = p.format & 0xFF, full_range = (p.format & AVD_FMT_FULL_RANGE) != 0;
+    if ((p.format & ~(0xFF | AVD_FMT_FULL_RANGE)) || (layout != AVD_FMT_BGR24 && layout != AVD_FMT_NV12 && layout != AVD_FMT_I420))
+        return {AVD_ERR_ARG, "bad avd_picture.format"};
+    if (full_range && layout == AVD_FMT_BGR24) return {AVD_ERR_ARG, "AVD_FMT_FULL_RANGE describes 4:2:0 samples: a BGR picture has no range"};
     if (p.rotate < 0 || p.rotate > 3) return {AVD_ERR_ARG, "avd_picture.rotate must be 0 .. 3 quarter turns"};
     if (p.reserved != 0) return {AVD_ERR_ARG, "avd_picture.reserved must be 0"};
-    if (p.format == AVD_FMT_BGR24) {
+    if (layout == AVD_FMT_BGR24) {
         if (p.rotate) return {AVD_ERR_UNSUPPORTED, "a turned BGR picture is not on the path: cv2 hands BGR over already rotated"};
         k = bgr_clip(p.plane[0], p.mem, p.n, p.h, p.w, p.row_stride[0], p.frame_stride[0]);
-    } else if (p.format == AVD_FMT_NV12) {
+    } else if (layout == AVD_FMT_NV12) {
         k = nv12_clip(p.plane[0], p.plane[1], p.mem, p.n, p.h, p.w, p.row_stride[0], p.row_stride[1], p.frame_stride[0], p.frame_stride[1]);
     } else {
         if (p.row_stride[1] != p.row_stride[2] || p.frame_stride[1] != p.frame_stride[2])
@@ -81,6 +87,7 @@ inline Refusal from_picture(const avd_picture& p, IngestClip& k)
         k = i420_clip(p.plane[0], p.plane[1], p.plane[2], p.mem, p.n, p.h, p.w, p.row_stride[0], p.row_stride[1], p.frame_stride[0], p.frame_stride[1]);
     }
     k.rotate = p.rotate;
+    k.full_range = full_range;
     return {0, nullptr};
 }
 

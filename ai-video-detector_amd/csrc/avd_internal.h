@@ -52,11 +52,13 @@ struct FbConsts {
 };
 void build_fb_consts(FbConsts& c);
 
-// libswscale's C yuv420 -> BGR24 conversion in integer form (avd_tables.cpp, yuv2rgb.c semantics, BT.601 limited):
+// libswscale's C yuv420 -> BGR24 conversion in integer form (avd_tables.cpp, yuv2rgb.c semantics, BT.601, limited or full range):
 //   value = clip8((c0 + (Y + off) * cy) >> 16),  off_r = ((V*crv)>>16) - (crv>>9),  off_b likewise with U and cbu,
 //   off_g = ((U*cgu)>>16) - (cgu>>9) + ((V*cgv)>>16) - (cgv>>9)   (arithmetic shifts: cgu, cgv are negative)
-struct YuvConsts { int cy, crv, cbu, cgu, cgv, c0, kr, kb, kg; };   // kr = -(crv>>9), kb = -(cbu>>9), kg = -(cgu>>9) - (cgv>>9)
-void build_yuv_consts(YuvConsts& c);
+// bias, ntab: the gray tables of the table fills (avd_preprocess.hip) hold entry Y + off at index Y + off + bias of ntab entries
+struct YuvConsts { int cy, crv, cbu, cgu, cgv, c0, kr, kb, kg, bias, ntab; };   // kr = -(crv>>9), kb = -(cbu>>9), kg = -(cgu>>9) - (cgv>>9)
+void build_yuv_consts(YuvConsts& c, bool full_range);
+void yuv_index_window(const YuvConsts& c, int& lo, int& hi);      // min and max of Y + off over Y, U, V in 0 .. 255
 
 struct Nv12Params {
     const uint8_t* uv;                 // interleaved U,V plane of frame 0 (the Y plane is the kernel's frame pointer)
@@ -249,6 +251,7 @@ struct avd_ctx {
     IngestPlan ingest_plan{};        // the last launch_preprocess of this context (debug buffer "ingest_plan")
     int ingest_plan_valid = 0;       // 0 until the first ingest launch
     int ingest_rotate = 0;           // the rotation that launch ran with (debug buffer "ingest_rotate")
+    int ingest_range = 0;            // 1: that launch ran with full-range conversion constants (debug buffer "ingest_range")
     int64_t stage_bytes = -1;        // bytes the last ingest call copied from host memory (debug buffer "stage_bytes"; 0: device input); -1 until the first one
     int rec_n = 0;                   // records the last avd_analyze_* call left in ws.d_rec (0 after any other entry point: avd_allgather_last_records checks it)
     void* comm = nullptr;            // RCCL communicator (avd_comm.cpp), bound at run time

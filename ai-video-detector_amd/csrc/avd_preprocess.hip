@@ -36,12 +36,13 @@ constexpr int kLdsBudget = 48 * 1024;   // the tile stays under this so that >= 
 static_assert(kThreads / 64 <= kLapSlots, "one moment slot per wave");
 
 // LDS plan, read by the kernels and by the launcher.  The tile is (rows_per_band + 2) rows of `pitch` bytes; behind it sit either the
-// resampling tables of k_preprocess_vec (LdsTabs, behind the FULL tile) or the three conversion tables of the NV12 table fill (behind the
-// rows the band has, rounded to 16: a short last band has them lower than the launcher reserved for).
-constexpr int kNvBias = 224, kNvTab = 704;     // NV12 conversion tables: entries, index bias (Y + offset in [-221, 475])
+// resampling tables of k_preprocess_vec (LdsTabs, behind the FULL tile) or the three conversion tables of the 4:2:0 table fills (behind the
+// rows the band has, rounded to 16: a short last band has them lower than the launcher reserved for).  Their length and index bias travel
+// with the conversion constants (YuvConsts::ntab, ::bias): the window of Y + offset follows the constants -- [-221, 475] limited range,
+// [-226, 480] full range -- and launch_preprocess refuses constants whose window leaves the table.
 __host__ __device__ constexpr size_t lds_tile_bytes(int trows, int pitch) { return (size_t)trows * pitch; }
 __host__ __device__ constexpr size_t lds_nvtab_off(int trows, int pitch) { return (lds_tile_bytes(trows, pitch) + 15) / 16 * 16; }
-constexpr size_t kNvTabBytes = 3 * sizeof(unsigned) * kNvTab;
+__host__ __device__ constexpr size_t lds_nvtab_bytes(int ntab) { return 3 * sizeof(unsigned) * (size_t)ntab; }
 
 __device__ __forceinline__ int reflect101(int p, int len)
 {
@@ -503,7 +504,8 @@ __device__ __forceinline__ int clip8(int v) { return min(max(v, 0), 255); }
 
 // chroma part of the three table lookups of one U,V pair: c0 + off * cy per channel
 struct ChromaTerms { int r, g, b; };
-// every product below has operands inside 24 bits (8-bit samples, 17-bit coefficients, table indices of a few hundred):
+// every product below has operands inside 24 bits (8-bit samples, 17-bit coefficients of either range -- the largest is cbu = 132201 limited,
+// 116129 full, both below 2^17 --, table indices of a few hundred):
 // __mul24 / __umul24 are full-rate instructions where a 32-bit multiply is quarter rate
 __device__ __forceinline__ ChromaTerms chroma_terms(int U, int V, const YuvConsts& k)
 {
@@ -518,9 +520,9 @@ __device__ __forceinline__ ChromaTerms chroma_terms(int U, int V, const YuvConst
 __device__ __forceinline__ ChromaTerms chroma_offsets(int U, int V, const YuvConsts& k)
 {
     ChromaTerms t;
-    t.r = (__mul24(V, k.crv) >> 16) + (k.kr + kNvBias);
-    t.b = (__mul24(U, k.cbu) >> 16) + (k.kb + kNvBias);
-    t.g = (__mul24(U, k.cgu) >> 16) + (__mul24(V, k.cgv) >> 16) + (k.kg + kNvBias);
+    t.r = (__mul24(V, k.crv) >> 16) + (k.kr + k.bias);       // the sums in parentheses are uniform: one scalar add per launch, as with a literal bias
+    t.b = (__mul24(U, k.cbu) >> 16) + (k.kb + k.bias);
+    t.g = (__mul24(U, k.cgu) >> 16) + (__mul24(V, k.cgv) >> 16) + (k.kg + k.bias);
     return t;
 }
 
@@ -587,14 +589,14 @@ __device__ __forceinline__ void fill_i420_scalar(uint8_t* tile, const uint8_t* y
     });
 }
 
-// the three gray tables behind a tile of trows rows (B, G, R: kNvTab entries each); returns the first
+// the three gray tables behind a tile of trows rows (B, G, R: k.ntab entries each); returns the first
 __device__ __forceinline__ unsigned* build_gray_tables(uint8_t* tile, int trows, int pitch, const YuvConsts& k, int tid)
 {
     unsigned* const tabB = reinterpret_cast<unsigned*>(tile + lds_nvtab_off(trows, pitch));
-    unsigned* const tabG = tabB + kNvTab;
-    unsigned* const tabR = tabG + kNvTab;
-    for (int i = tid; i < kNvTab; i += kThreads) {
-        const unsigned v = (unsigned)clip8((k.c0 + (i - kNvBias) * k.cy) >> 16);
+    unsigned* const tabG = tabB + k.ntab;
+    unsigned* const tabR = tabG + k.ntab;
+    for (int i = tid; i < k.ntab; i += kThreads) {
+        const unsigned v = (unsigned)clip8((k.c0 + (i - k.bias) * k.cy) >> 16);
         tabB[i] = v * 3735u; tabG[i] = v * 19235u + (1u << 14); tabR[i] = v * 9798u;
     }
     __syncthreads();
@@ -603,7 +605,7 @@ __device__ __forceinline__ unsigned* build_gray_tables(uint8_t* tile, int trows,
 
 // NV12, 16-byte aligned planes of w % 16 == 0 pixels.
 // libswscale's converter IS a table lookup: B = T[Y + ob(U)], G = T[Y + og(U, V)], R = T[Y + or(V)] with one clip table T(i) = clip8((c0 + i cy) >> 16).
-// Three LDS tables of cv2's gray weight times T (3735 T, 19235 T + the rounding 2^14, 9798 T; 32-bit entries, index bias kNvBias), so a pixel is
+// Three LDS tables of cv2's gray weight times T (3735 T, 19235 T + the rounding 2^14, 9798 T; 32-bit entries, index bias k.bias), so a pixel is
 // three index additions, three ds_read_b32, one three-operand add and a shift -- instead of three multiply-adds, three shifts, three clamps and
 // three multiply-adds (12.3 -> 8.8 vector instructions per pixel; the LDS pipe does the lookups beside them).  Same integers by construction.
 // chroma8(p, c, t) forms the eight chroma-term triples of chroma row p, 16-pixel chunk c: the surface kinds differ in nothing else.
@@ -616,8 +618,8 @@ __device__ __forceinline__ void fill_yuv420_tables(uint8_t* tile, const uint8_t*
 {
     const int h = P.h, pitch = P.pitch, r0 = b.r0, rows = b.rows, trows = b.trows;
     unsigned* const tabB = build_gray_tables(tile, trows, pitch, k, tid);
-    unsigned* const tabG = tabB + kNvTab;
-    unsigned* const tabR = tabG + kNvTab;
+    unsigned* const tabG = tabB + k.ntab;
+    unsigned* const tabR = tabG + k.ntab;
     // one work item = one chroma row x one 16-pixel chunk: the eight chroma-term triples are formed once and serve the
     // two luma rows that share them (they are 8.5 of the ~27 integer operations a pixel costs otherwise)
     const int ylo = r0 - 1, yhi = r0 + rows;              // image rows of tile rows 0 and trows - 1, before reflection
@@ -731,8 +733,8 @@ __device__ __forceinline__ void fill_yuv420_strip(uint8_t* tile, const uint8_t* 
     static_assert(ROT == 1 || ROT == 3, "quarter turns");
     const int h = P.h, w = P.w, pitch = P.pitch, trows = b.trows;
     const unsigned* const tabB = build_gray_tables(tile, trows, pitch, k, tid);
-    const unsigned* const tabG = tabB + kNvTab;
-    const unsigned* const tabR = tabG + kNvTab;
+    const unsigned* const tabG = tabB + k.ntab;
+    const unsigned* const tabR = tabG + k.ntab;
     const int ylo = b.r0 - 1, yhi = b.r0 + b.rows;           // displayed rows of tile rows 0 and trows - 1, before reflection
     const int ya = max(ylo, 0), yb = min(yhi, h - 1);         // the ones that exist
     const int len = yb - ya + 1;                              // <= kStripSpan
@@ -963,16 +965,30 @@ int launch_preprocess(avd_ctx* ctx, const IngestClip& clip, const uint8_t* d_in,
         ctx->ingest_plan = IngestPlan{P.h, P.w, P.rows_per_band, P.nbands, P.pitch, ni, (int)lds, id};
         ctx->ingest_plan_valid = 1;
         ctx->ingest_rotate = clip.rotate;
+        ctx->ingest_range = !bgr && clip.full_range;
         hipLaunchKernelGGL(kernel, dim3(grid), dim3(kThreads), lds, ctx->stream, source..., n, P, ws.d_small + (size_t)ws.f0 * AVD_NPIX,
                            ws.d_rowbuf + ws.rowbuf_off, ws.d_lap_part + ws.lappart_off);
     };
-    const size_t tabs = lds_nvtab_off(P.rows_per_band + 2, P.pitch) + kNvTabBytes;      // tile + the three gray tables
     const int rot = clip.rotate;
     if (rot && bgr) { ctx->err = "internal error: a turned BGR clip reached the ingest launch"; return AVD_ERR_DEVICE; }
+    if (clip.full_range && bgr) { ctx->err = "internal error: a full-range BGR clip reached the ingest launch"; return AVD_ERR_DEVICE; }
+    YuvConsts yc{};
+    size_t tabs = 0;                                   // tile + the three gray tables
+    if (!bgr) {
+        build_yuv_consts(yc, clip.full_range != 0);
+        // every index the table fills can form, Y + offset + bias, must lie inside the tables these constants dimension
+        int lo, hi;
+        yuv_index_window(yc, lo, hi);
+        if (lo + yc.bias < 0 || hi + yc.bias >= yc.ntab) {
+            ctx->err = "internal error: the conversion constants index outside the gray tables";
+            return AVD_ERR_DEVICE;
+        }
+        tabs = lds_nvtab_off(P.rows_per_band + 2, P.pitch) + lds_nvtab_bytes(yc.ntab);
+    }
     if (planar) {
         I420Params ip{};
         ip.u = d_uv; ip.v = d_v; ip.c_row_stride = clip.uv_row_stride; ip.c_frame_stride = clip.uv_frame_stride;
-        build_yuv_consts(ip.k);
+        ip.k = yc;
         if (rot == 1) launch(kIngestI420Strip, k_preprocess_i420<false, 1>, tabs, d_in, ip);
         else if (rot == 3) launch(kIngestI420Strip, k_preprocess_i420<false, 3>, tabs, d_in, ip);
         else if (rot == 2 && vec) launch(kIngestI420Tables, k_preprocess_i420<true, 2>, tabs, d_in, ip);
@@ -982,7 +998,7 @@ int launch_preprocess(avd_ctx* ctx, const IngestClip& clip, const uint8_t* d_in,
     } else if (!bgr) {
         Nv12Params nv{};
         nv.uv = d_uv; nv.uv_row_stride = clip.uv_row_stride; nv.uv_frame_stride = clip.uv_frame_stride;
-        build_yuv_consts(nv.k);
+        nv.k = yc;
         // (a register-staged variant in the style of k_preprocess_vec measured no faster: the kernel is bound by the
         // conversion's integer arithmetic, not by how its loads are issued -- profiles/r02_experiments.md)
         if (rot == 1) launch(kIngestNv12Strip, k_preprocess_nv12<false, 1>, tabs, d_in, nv);

@@ -8,6 +8,7 @@
 // :45 (calcOpticalFlowFarneback: pyramid Gaussian taps, poly_n=5 / poly_sigma=1.2).
 // Compiled with -ffp-contract=off.
 #include <cfloat>
+#include <climits>
 #include <cmath>
 #include <cstring>
 #include "avd_internal.h"
@@ -190,22 +191,46 @@ void build_fb_consts(FbConsts& c)
     }
 }
 
-// ---- NV12 ingest: libswscale's yuv2rgb.c table construction reduced to its integer constants ------------------
-// (ff_yuv2rgb_c_init_tables for a 24-bit destination, SWS_CS_DEFAULT = BT.601, limited range, neutral brightness /
-// contrast / saturation).  The tables themselves are not materialised: every entry is
-// clip_uint8((yb0 + i*cy + 0x8000) >> 16) and every chroma table is an index offset, so the kernel evaluates
-// value = clip8((c0 + (Y + off)*cy) >> 16) directly (the oracle keeps the literal tables and the two are compared).
-void build_yuv_consts(YuvConsts& c)
+// ---- 4:2:0 ingest: libswscale's yuv2rgb.c table construction reduced to its integer constants ------------------
+// (ff_yuv2rgb_c_init_tables for a 24-bit destination, SWS_CS_DEFAULT = BT.601, neutral brightness / contrast /
+// saturation; limited range, or fullRange = 1 for ffmpeg's J formats).  The tables themselves are not materialised:
+// every entry is clip_uint8((yb0 + i*cy + 0x8000) >> 16) and every chroma table is an index offset, so the kernel
+// evaluates value = clip8((c0 + (Y + off)*cy) >> 16) directly (the oracle keeps the literal tables of the limited case
+// and the two are compared; tests/yuv_tables_reference.py restates both).
+// Full range: the luma gain is 1 and its offset 0, the chroma coefficients shrink by 224/255 (their excursion is the
+// limited one's 224 levels spread over 255), and the table base moves from 326 to 384 so that c0 is the rounding alone.
+void build_yuv_consts(YuvConsts& c, bool full_range)
 {
     const long long one = 1ll << 16;
-    const long long cy = one * 255 / 219;                    // luma gain of a limited-range source
-    const long long oy = 16ll << 16;
+    const long long cy = full_range ? one : one * 255 / 219;   // luma gain (limited: 219 levels spread over 255)
+    const long long oy = full_range ? 0 : 16ll << 16;
+    auto ranged = [&](long long inc) { return full_range ? inc * 224 / 255 : inc; };
     auto rescale = [&](long long inc) { return (inc * one + 0x8000) / cy; };      // "scale coefficients by cy"
-    const long long crv = rescale(104597), cbu = rescale(132201), cgu = rescale(-25675), cgv = rescale(-53279);
+    const long long crv = rescale(ranged(104597)), cbu = rescale(ranged(132201)), cgu = rescale(ranged(-25675)), cgv = rescale(ranged(-53279));
     auto fl = [](long long v, int s) { return v >= 0 ? v >> s : -((-v + (1ll << s) - 1) >> s); };   // floor shift
     c.cy = (int)cy; c.crv = (int)crv; c.cbu = (int)cbu; c.cgu = (int)cgu; c.cgv = (int)cgv;
-    c.c0 = (int)(-(384ll << 16) - oy + 326 * cy + 0x8000);   // table bias, luma offset of the limited-range tables, rounding
+    c.c0 = (int)(-(384ll << 16) - oy + (full_range ? 384 : 326) * cy + 0x8000);   // table bias, luma offset of the tables, rounding
     c.kr = (int)-fl(crv, 9);
     c.kb = (int)-fl(cbu, 9);
     c.kg = (int)(-fl(cgu, 9) - fl(cgv, 9));
+    // the gray tables of the table fills: Y + offset lies in [-221, 475] (limited) or [-226, 480] (full); launch_preprocess checks
+    // whatever it is about to pass against yuv_index_window
+    c.bias = full_range ? 228 : 224;
+    c.ntab = full_range ? 712 : 704;
+}
+
+// The true range of the table index Y + offset over Y, U, V in 0 .. 255, with the kernels' own expressions (chroma_offsets: arithmetic
+// shifts of the products).  R depends on V alone, B on U alone; G is a sum of a U term and a V term, so its extremes are sums of theirs.
+void yuv_index_window(const YuvConsts& c, int& lo, int& hi)
+{
+    auto term = [](int s, int coef) { return (int)(((long long)s * coef) >> 16); };
+    int rmin = INT_MAX, rmax = INT_MIN, bmin = INT_MAX, bmax = INT_MIN, gumin = INT_MAX, gumax = INT_MIN, gvmin = INT_MAX, gvmax = INT_MIN;
+    for (int s = 0; s < 256; s++) {
+        rmin = std::min(rmin, term(s, c.crv)); rmax = std::max(rmax, term(s, c.crv));
+        bmin = std::min(bmin, term(s, c.cbu)); bmax = std::max(bmax, term(s, c.cbu));
+        gumin = std::min(gumin, term(s, c.cgu)); gumax = std::max(gumax, term(s, c.cgu));
+        gvmin = std::min(gvmin, term(s, c.cgv)); gvmax = std::max(gvmax, term(s, c.cgv));
+    }
+    lo = std::min({rmin + c.kr, bmin + c.kb, gumin + gvmin + c.kg});
+    hi = std::max({rmax + c.kr, bmax + c.kb, gumax + gvmax + c.kg}) + 255;
 }

@@ -29,8 +29,10 @@
  *     AVD_MEM_HOST nor AVD_MEM_DEVICE (AVD_ERR_ARG); a size out of range -- n < 0, h or w outside 1 .. 16384
  *     (AVD_ERR_ARG); an odd width or height of 4:2:0 input (AVD_ERR_UNSUPPORTED); a picture below 32 x 32
  *     (AVD_ERR_UNSUPPORTED); a null plane of a clip with n > 0 (AVD_ERR_ARG); strides smaller than the planes
- *     (AVD_ERR_ARG).  What an avd_picture alone can get wrong (struct_size, format, rotate, reserved, BGR with a
- *     rotation, U and V strides that differ) is refused before any of these; a records pointer that is null while
+ *     (AVD_ERR_ARG).  What an avd_picture alone can get wrong is refused before any of these, in this order:
+ *     struct_size; format (an unknown layout in the low byte, or a bit above it other than AVD_FMT_FULL_RANGE);
+ *     AVD_FMT_FULL_RANGE on a BGR picture; rotate; reserved; BGR with a rotation; U and V strides that differ.
+ *     A records pointer that is null while
  *     there are frames to write, after all of them.  The clips of a batch are checked in order.
  *   - if no HIP device is usable avd_create fails (AVD_ERR_DEVICE): there is no
  *     CPU fallback in this library.
@@ -158,7 +160,9 @@ int avd_analyze_batch_async(avd_ctx* ctx, const avd_clip* clips, int nclips, avd
  * range, nearest chroma) before cv2's BGR2GRAY: 1.5 bytes per pixel cross PCIe / HBM instead of 3, and no BGR frame
  * exists anywhere.  Results equal avd_analyze_frames on the BGR frames of oracle/avd_oracle.c's avdo_nv12_to_bgr24
  * bit for bit; parity with a real libswscale is UNPINNED (restated from memory, x86 builds also dispatch to SIMD
- * code that differs by +-1).  Width and height must be even.  Outputs as for the BGR entry points. */
+ * code that differs by +-1).  Width and height must be even.  Outputs as for the BGR entry points.
+ * These entry points, the I420 ones below and the NV12 clips of avd_clip are LIMITED range (Y 16 .. 235, chroma 16 .. 240); full-range
+ * pictures (ffmpeg's yuvj420p) go through avd_picture with AVD_FMT_FULL_RANGE. */
 int avd_preprocess_nv12(avd_ctx* ctx, const uint8_t* y, const uint8_t* uv, int mem, int n, int h, int w,
                         int64_t y_row_stride, int64_t uv_row_stride, int64_t y_frame_stride, int64_t uv_frame_stride,
                         uint8_t* small320, uint8_t* hash1024, int64_t* lap_sum, int64_t* lap_sumsq);
@@ -204,14 +208,23 @@ int avd_analyze_frames_i420_async(avd_ctx* ctx, const uint8_t* y, const uint8_t*
  *   plane        BGR: [0]; NV12: Y, interleaved UV; I420: Y, U, V (YV12: exchange [1] and [2])
  *   row_stride, frame_stride   bytes, per plane; I420: [1] == [2] (AVD_ERR_ARG otherwise)
  *   h, w         the stored picture;  rotate  quarter turns clockwise from the stored to the displayed picture, 0 .. 3;  reserved  0
+ *   format       the layout (AVD_FMT_BGR24 / _NV12 / _I420), for the 4:2:0 layouts optionally OR-ed with AVD_FMT_FULL_RANGE
  * Refused without a launch: rotate outside 0 .. 3, a non-zero reserved, a bad format or struct_size (AVD_ERR_ARG); what the format's own entry
  * point refuses, with its status; AVD_FMT_BGR24 with rotate != 0 (AVD_ERR_UNSUPPORTED: cv2 hands BGR over already rotated, stored-orientation
  * BGR does not arise).  Mirrored display matrices are not covered.
+ * AVD_FMT_FULL_RANGE: the samples use 0 .. 255 -- ffmpeg's yuvj420p (AVD_FMT_I420 | AVD_FMT_FULL_RANGE) and its semi-planar form
+ * (AVD_FMT_NV12 | AVD_FMT_FULL_RANGE): every MJPEG clip, the H.264 of many phones and screen recorders.  cv2.VideoCapture.retrieve() converts
+ * those with the same table-driven yuv2rgb.c, its tables built for fullRange = 1 (luma gain 1, chroma coefficients times 224/255), and so does
+ * the fused pass: results equal the BGR entry points on that conversion's frames bit for bit (tests/yuv_tables_reference.py restates it; parity
+ * with a real libswscale is UNPINNED exactly as in the limited case).  Without the flag a 4:2:0 picture is limited range, as everywhere above.
+ * The flag is per clip: a batch may mix ranges.  AVD_FMT_BGR24 | AVD_FMT_FULL_RANGE (BGR has no range), any other bit above the low byte and an
+ * unknown layout in the low byte are AVD_ERR_ARG.
  * avd_preprocess_picture: outputs as avd_preprocess_bgr.  avd_analyze_pictures: the batch of avd_analyze_batch with descriptors -- any mix of
  * formats, geometries and rotations, I420 included; records clip after clip, identical to one call per clip; ONE Farneback launch sequence over
  * all clips; nclips = 1 is the single-clip call.  avd_analyze_pictures_async follows avd_analyze_batch_async exactly: one call outstanding per
  * context, drained by any other call, with the same exemptions. */
 enum avd_format { AVD_FMT_BGR24 = 0, AVD_FMT_NV12 = 1, AVD_FMT_I420 = 2 };
+#define AVD_FMT_FULL_RANGE 0x100      /* a flag OR-ed into the layout in avd_picture.format; the layout is the low byte */
 typedef struct avd_picture {
     uint32_t struct_size;
     int32_t  format;
@@ -265,9 +278,9 @@ int avd_cnn_conv(avd_ctx* ctx, const uint16_t* x, int n, int hin, int win, int c
  * held in registers, wave-level shuffle reductions, one pass over HBM.
  * avd_layernorm: y = (x - mean) / sqrt(var + eps) * gamma + beta over the last dimension (biased variance, float32
  * statistics: torch.nn.functional.layer_norm); x / y [rows][cols] float32 (bf16 = 0) or bf16 bit patterns (bf16 = 1), both
- * host or both device (mem); cols in {256, 512, 768, 1024, 2048} (768 = the ViT-B/16 token width); gamma / beta host
- * float[cols].  avd_softmax: y = exp(x - max) / sum over rows of cols float32 logits (cols % 4 == 0, <= 4096; 1000 = the
- * CNN's classes).  If timing_reps > 0 and ms != NULL the kernel alone is launched timing_reps more times between two HIP
+ * host or both device (mem); any cols >= 1 -- 256, 512, 768, 1024 and 2048 (768 = the ViT-B/16 token width) run the
+ * register-resident kernel, every other width a general one; gamma / beta host float[cols].  avd_softmax: y = exp(x - max) / sum
+ * over rows of cols float32 logits, any cols >= 1 (whole float4s up to 4096 stay in registers; 1000 = the CNN's classes).  If timing_reps > 0 and ms != NULL the kernel alone is launched timing_reps more times between two HIP
  * events and its mean duration is returned (bench hook). */
 int avd_layernorm(avd_ctx* ctx, const void* x, int mem, int bf16, int64_t rows, int cols, const float* gamma, const float* beta,
                   float eps, void* y, int timing_reps, float* ms);
@@ -416,6 +429,8 @@ int avd_kernel_ms(avd_ctx* ctx, int kernel_id, float* ms);
  * kernel (0 bgr_scalar, 1 bgr_vec16, 2 bgr_staged, 3 nv12_scalar, 4 nv12_tables, 5 i420_scalar, 6 i420_tables, 7 nv12_strip, 8 i420_strip; a half turn runs the
  * flipped instantiations of 3 .. 6 under the same ids); h, w are the displayed picture's; an error before any ingest launch.
  * "ingest_rotate" int32[1], host state: the rotation (quarter turns) that launch ran with; an error before any ingest launch.
+ * "ingest_range" int32[1], host state: 1 if that launch ran with full-range conversion constants (AVD_FMT_FULL_RANGE), else 0; an error before
+ * any ingest launch.
  * "stage_bytes" int64[1], host state: the bytes the last ingest call of the context (avd_preprocess_*, avd_analyze_*) copied from host
  * memory into its staging buffer -- 0 for device input, the sum over the clips of a batch; an error before any ingest call.
  * "cnn_tap": what option "cnn_tap" made the last avd_cnn_forward copy aside -- 1: uint16[n][232][232][4] bf16 bits; 2 + i and 55: the activation as
