@@ -36,6 +36,9 @@ EXPORTS = (
     "avd_set_profiling", "avd_stage_ms", "avd_kernel_ms", "avd_debug_fetch",
 )
 
+# the frame-list family (include/avd_frame_list.h, which avd.h includes): additive at ABI 3, declared and listed apart from the entry points of avd.h
+LIST_EXPORTS = ("avd_preprocess_frame_list", "avd_analyze_frame_lists", "avd_analyze_frame_lists_async")
+
 # numpy view of struct avd_audio_window (48 bytes)
 AUDIO_WINDOW_DTYPE = np.dtype([("sumsq", "<f8"), ("sum_log", "<f8"), ("sum_mag", "<f8"), ("sum_fmag", "<f8"),
                                ("zero_cross", "<i4"), ("length", "<i4"), ("rolloff_index", "<i4"), ("nbins", "<i4")])
@@ -73,6 +76,13 @@ class AvdPicture(C.Structure):
                 ("rotate", C.c_int32), ("reserved", C.c_int32)]
 
 
+class AvdFrameList(C.Structure):
+    """struct avd_frame_list (include/avd_frame_list.h): one clip as a list of separately allocated frames -- per plane an array of n plane pointers (host
+    memory, read during the call only) in place of avd_picture's base + f * frame_stride."""
+    _fields_ = [("struct_size", C.c_uint32), ("format", C.c_int32), ("plane", C.c_void_p * 3), ("row_stride", C.c_int64 * 3),
+                ("mem", C.c_int32), ("n", C.c_int32), ("h", C.c_int32), ("w", C.c_int32), ("rotate", C.c_int32), ("reserved", C.c_int32)]
+
+
 class AvdError(RuntimeError):
     """Non-zero status from the C-ABI (the analyzer may raise; reference api.py:134-140
     turns any exception into the neutral 0.5 timeline)."""
@@ -99,7 +109,7 @@ class _Clip(typing.NamedTuple):
 def build(force: bool = False) -> str:
     """Compile the HIP extension for gfx950 with hipcc (cross-compiles without a GPU)."""
     srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".cpp", ".h"))]
-    srcs.append(os.path.join(os.path.dirname(_PKG), "include", "avd.h"))
+    srcs += [os.path.join(os.path.dirname(_PKG), "include", h) for h in ("avd.h", "avd_frame_list.h")]
     stale = (not os.path.exists(SO_PATH)) or any(os.path.getmtime(s) > os.path.getmtime(SO_PATH) for s in srcs)
     if force or stale:
         subprocess.run(["make", "-C", CSRC] + (["-B"] if force else []), check=True, stdout=sys.stderr)   # keep stdout clean (bench.py prints one JSON line)
@@ -161,6 +171,9 @@ def load() -> C.CDLL:
     L.avd_preprocess_picture.argtypes = [vp, vp, u8p, u8p, i64p, i64p]
     L.avd_analyze_pictures.argtypes = [vp, vp, C.c_int, vp]
     L.avd_analyze_pictures_async.argtypes = [vp, vp, C.c_int, vp]
+    L.avd_preprocess_frame_list.argtypes = [vp, vp, u8p, u8p, i64p, i64p]
+    L.avd_analyze_frame_lists.argtypes = [vp, vp, C.c_int, vp]
+    L.avd_analyze_frame_lists_async.argtypes = [vp, vp, C.c_int, vp]
     L.avd_vit_set_weights.argtypes = [vp, vp, vp]
     L.avd_vit_patch_embed.argtypes = [vp, u8p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, vp, C.c_int, C.c_int, C.c_int,
                                       C.POINTER(C.c_float)]
@@ -189,7 +202,7 @@ def load() -> C.CDLL:
     L.avd_kernel_ms.argtypes = [vp, C.c_int, C.POINTER(C.c_float)]
     L.avd_debug_fetch.argtypes = [vp, C.c_char_p, vp, C.c_size_t]
     L.avd_debug_fetch.restype = C.c_int64
-    for name in EXPORTS:
+    for name in EXPORTS + LIST_EXPORTS:
         if name not in ("avd_destroy", "avd_last_error", "avd_debug_fetch"):
             getattr(L, name).restype = C.c_int
     _lib = L
@@ -218,6 +231,7 @@ class Context:
                            "(the HIP path has no CPU fallback)")
         self._h = h
         self.device = int(device)
+        self._list_keep = None          # the frames of a pending analyze_frame_lists_async, held until synchronize()
 
     def close(self):
         if getattr(self, "_h", None):
@@ -468,6 +482,109 @@ class Context:
         self._records_call("avd_analyze_pictures_async", (arr, len(clips)), sum(counts), rec)
         return keep, counts
 
+    # -- clips as lists of separately allocated frames (include/avd_frame_list.h) ---------------------------------------------------------
+    def _frame_list(self, frames, fmt: int, rotate: int = 0, full_range: bool = False):
+        """frames: a sequence of per-frame arrays -- BGR uint8[H,W,3], NV12 pairs (y uint8[H,W], uv uint8[H/2,W]) or I420 triples (y, u, v) -- all
+        numpy arrays (host) or all torch tensors on one device; every frame where it lies, nothing is gathered.  A plane's rows must be dense
+        and all frames of the list share the row stride of each plane: anything else raises ValueError (there is no silent copy).
+        -> (AvdFrameList, frame count, what the library reads: the pointer arrays during the call, the frames until it is drained)"""
+        if isinstance(rotate, bool) or not isinstance(rotate, (int, np.integer)) or not 0 <= rotate <= 3:
+            raise ValueError(f"rotate must be 0, 1, 2 or 3 quarter turns (clockwise, stored to displayed picture), got {rotate!r}")
+        if fmt not in (AVD_FMT_BGR24, AVD_FMT_NV12, AVD_FMT_I420):
+            raise ValueError(f"fmt must be AVD_FMT_BGR24, AVD_FMT_NV12 or AVD_FMT_I420, got {fmt!r}")
+        nplanes = {AVD_FMT_BGR24: 1, AVD_FMT_NV12: 2, AVD_FMT_I420: 3}[fmt]
+        frames = [(f,) if fmt == AVD_FMT_BGR24 else tuple(f) for f in frames]
+        if any(len(f) != nplanes for f in frames):
+            raise ValueError(f"every frame of the list has {nplanes} plane(s)")
+        L = AvdFrameList()
+        L.struct_size, L.format, L.rotate, L.reserved = C.sizeof(AvdFrameList), fmt | (AVD_FMT_FULL_RANGE if full_range else 0), int(rotate), 0
+        L.n, L.mem = len(frames), AVD_MEM_HOST
+        if not frames:                                         # an empty list has no picture to take a size from: any valid one
+            L.h = L.w = HASH
+            for p in range(nplanes):
+                L.row_stride[p] = HASH * 3 if fmt == AVD_FMT_BGR24 else (HASH // 2 if fmt == AVD_FMT_I420 and p else HASH)
+            return L, 0, ()
+        torch_in = [_is_torch_tensor(p) for f in frames for p in f]
+        if any(torch_in) != all(torch_in):
+            raise ValueError("the frames of a list are all numpy arrays or all torch tensors")
+        if all(torch_in):
+            first = frames[0][0]
+            if any(str(p.dtype) != "torch.uint8" or p.device != first.device for f in frames for p in f):
+                raise ValueError("the frames of a list are uint8 tensors on one device")
+            strides, ptr, _ = _TORCH_PLANE
+            if first.is_cuda:
+                L.mem = AVD_MEM_DEVICE
+                self._after_torch_stream(first)
+        else:
+            frames = [tuple(np.asarray(p) for p in f) for f in frames]
+            if any(p.dtype != np.uint8 for f in frames for p in f):
+                raise ValueError("the frames of a list are uint8 arrays")
+            strides, ptr, _ = _NUMPY_PLANE
+        h, w = int(frames[0][0].shape[0]), int(frames[0][0].shape[1])
+        shapes = {AVD_FMT_BGR24: [(h, w, 3)], AVD_FMT_NV12: [(h, w), (h // 2, w)], AVD_FMT_I420: [(h, w), (h // 2, w // 2), (h // 2, w // 2)]}[fmt]
+        arrays = []
+        for p in range(nplanes):
+            dense = (3, 1) if fmt == AVD_FMT_BGR24 else (1,)
+            for i, f in enumerate(frames):
+                if tuple(f[p].shape) != shapes[p]:
+                    raise ValueError(f"frame {i}: plane {p} must be uint8{list(shapes[p])}, got {list(f[p].shape)}")
+                st = tuple(strides(f[p]))
+                if st[1:] != dense:
+                    raise ValueError(f"frame {i}: the rows of plane {p} are not dense (element strides {st[1:]})")
+                if st[0] != strides(frames[0][p])[0]:
+                    raise ValueError(f"frame {i}: plane {p} has row stride {st[0]}, frame 0 has {strides(frames[0][p])[0]}: the frames of a list share "
+                                     "their row strides")
+            L.row_stride[p] = int(strides(frames[0][p])[0])
+            arrays.append((C.c_void_p * len(frames))(*[ptr(f[p]) for f in frames]))
+            L.plane[p] = C.cast(arrays[-1], C.c_void_p)
+        L.h, L.w = h, w
+        return L, len(frames), (arrays, frames)
+
+    def preprocess_frame_list(self, frames, fmt: int, rotate: int = 0, full_range: bool = False):
+        """-> (small320, hash1024, lap_sum, lap_sumsq), as the format's own preprocess call on np.stack of the same frames."""
+        L, n, keep = self._frame_list(frames, fmt, rotate, full_range)
+        return self._outputs_call("avd_preprocess_frame_list", (C.byref(L),), n)
+
+    def _frame_list_array(self, lists, rotates, full_ranges):
+        rotates = [0] * len(lists) if rotates is None else list(rotates)
+        full_ranges = [False] * len(lists) if full_ranges is None else list(full_ranges)
+        if len(rotates) != len(lists) or len(full_ranges) != len(lists):
+            raise ValueError("one rotation and one range per list")
+        arr = (AvdFrameList * len(lists))()
+        keep, counts = [], []
+        for i, ((frames, fmt), r, fr) in enumerate(zip(lists, rotates, full_ranges)):
+            arr[i], n, k = self._frame_list(frames, fmt, r, fr)
+            keep.append(k)
+            counts.append(n)
+        return arr, counts, keep
+
+    def analyze_frame_lists(self, lists, rotates=None, full_ranges=None):
+        """lists: a sequence of (frames, fmt) -- frames as for preprocess_frame_list, any mix of formats and geometries, empty lists included --
+        each with its rotation (default 0) and range (default limited).  -> list of record arrays, one per list, identical to the strided call
+        on the stacked frames."""
+        arr, counts, keep = self._frame_list_array(lists, rotates, full_ranges)
+        rec = self._records_call("avd_analyze_frame_lists", (arr, len(lists)), sum(counts))
+        self._list_keep = None                                 # a blocking call drains whatever was pending before it returns
+        return list(np.split(rec, np.cumsum(counts)[:-1])) if counts else []
+
+    def analyze_frame_lists_async(self, lists, rec: np.ndarray, rotates=None, full_ranges=None):
+        """Enqueue only; rec (RECORD_DTYPE, sum of the lists' frames) is filled by synchronize().  Returns (keepalive, frame counts); the context
+        itself also holds the frames until synchronize()."""
+        arr, counts, keep = self._frame_list_array(lists, rotates, full_ranges)
+        self._records_call("avd_analyze_frame_lists_async", (arr, len(lists)), sum(counts), rec)
+        # only now: the C call above first drained a still-pending call, whose frames the context held until then
+        self._list_keep = keep
+        return keep, counts
+
+    def ingest_list(self):
+        """(1, frames) if the last ingest launch of this context took its frame bases from a table of plane pointers, else (0, 0);
+        avd_debug_fetch "ingest_list"."""
+        return tuple(int(v) for v in self.debug_fetch("ingest_list", (2,), np.int32))
+
+    def stage_copies(self) -> int:
+        """Host-to-device staging copies the last ingest call of this context issued; avd_debug_fetch "stage_copies"."""
+        return int(self.debug_fetch("stage_copies", (1,), np.int64)[0])
+
     def ingest_rotate(self) -> int:
         """The rotation the last ingest launch of this context ran with; avd_debug_fetch "ingest_rotate"."""
         return int(self.debug_fetch("ingest_rotate", (1,), np.int32)[0])
@@ -673,6 +790,7 @@ class Context:
 
     def synchronize(self):
         self._check(self._L.avd_synchronize(self._h))
+        self._list_keep = None
 
     # -- a batch of clips in one call (include/avd.h: avd_analyze_batch) -----------------------------------------
     def _clip_array(self, clips):

@@ -203,20 +203,32 @@ class FrameAnalyzer:
             out.append(records(buf, carry))
         return np.concatenate(out) if out else np.zeros(0, _lib.RECORD_DTYPE)
 
+    # A chunk goes to the library as a LIST of frames (avd_frame_list): every frame is staged from where the decoder left it, nothing is
+    # stacked first.  The carry frame between chunks is simply the first entry of the next list.
+    def _flush_list(self, items, fmt, rotate=0, full_range=False) -> np.ndarray:
+        frames = [(np.asarray(it),) if fmt == _lib.AVD_FMT_BGR24 else tuple(np.asarray(p) for p in it) for it in items]
+        # Frames go through as they lie -- row-padded decoder frames included -- while plane by plane their rows are dense and all frames share
+        # one row stride, which is what a list takes.  Only a chunk that breaks that rule is copied (every plane to tight rows).
+        tail = (3, 1) if fmt == _lib.AVD_FMT_BGR24 else (1,)
+        agree = all(p.ndim == len(tail) + 1 and p.strides[1:] == tail and p.strides[0] == q.strides[0] for f in frames for p, q in zip(f, frames[0]))
+        if not agree:
+            frames = [tuple(np.ascontiguousarray(p) for p in f) for f in frames]
+        if fmt == _lib.AVD_FMT_BGR24:
+            frames = [f[0] for f in frames]
+        return self.ctx.analyze_frame_lists([(frames, fmt)], [rotate], [full_range])[0]
+
     def records_stream(self, frames: Iterable[np.ndarray]) -> np.ndarray:
-        return self._stream(frames, lambda items: self.ctx.analyze_frames(np.stack(items)))
+        return self._stream(frames, lambda items: self._flush_list(items, _lib.AVD_FMT_BGR24))
 
     # -- the same for decoder surfaces: an iterable of (y uint8[H,W], uv uint8[H/2,W]) pairs ----------------
     # rotate: quarter turns clockwise from the stored pictures to the displayed one (a container's display rotation; include/avd.h, avd_picture)
     # full_range: the samples use 0 .. 255 (ffmpeg's J formats; AVD_FMT_FULL_RANGE)
     def records_stream_nv12(self, surfaces, rotate: int = 0, full_range: bool = False) -> np.ndarray:
-        return self._stream(surfaces, lambda items: self.ctx.analyze_frames_nv12(*(np.stack([sf[k] for sf in items]) for k in range(2)), rotate=rotate,
-                                                                                 full_range=full_range))
+        return self._stream(surfaces, lambda items: self._flush_list(items, _lib.AVD_FMT_NV12, rotate, full_range))
 
     # -- and for planar pictures (software decoders, .y4m): an iterable of (y uint8[H,W], u uint8[H/2,W/2], v uint8[H/2,W/2]) triples ----
     def records_stream_i420(self, surfaces, rotate: int = 0, full_range: bool = False) -> np.ndarray:
-        return self._stream(surfaces, lambda items: self.ctx.analyze_frames_i420(*(np.stack([sf[k] for sf in items]) for k in range(3)), rotate=rotate,
-                                                                                 full_range=full_range))
+        return self._stream(surfaces, lambda items: self._flush_list(items, _lib.AVD_FMT_I420, rotate, full_range))
 
 
 class ClipsInFlight:

@@ -523,17 +523,82 @@ static int refuse(avd_ctx* ctx, const Refusal& r)
     return r.status;
 }
 
-// Stage clip k at offset `at` of ws.d_stage (host input; reserved by the caller) and launch its fused full-resolution kernel, which
-// writes the clip's slice (ws.f0, ws.rowbuf_off, ws.lappart_off) of the per-frame buffers.  The clip's geometry is current.
-static int preprocess_clip(avd_ctx* ctx, const IngestClip& k, size_t at)
+// The frame lists of one call (IngestClip::is_list): the staging plan of each and its place in the table of plane pointers.  The table -- per
+// list [plane][frame] device addresses: the caller's planes, or where list_stage puts them in the staging buffer, so that host and device
+// lists run the same path -- is filled in the pinned mirror and uploaded once, ahead of the first clip.
+struct CallLists {
+    std::vector<ListStage> stage;      // per clip; empty for a strided clip
+    std::vector<size_t> at;            // per clip: its first entry in the table
+    size_t entries = 0;
+    size_t total(const IngestClip& k, int c) const { return k.is_list ? stage[c].total : clip_stage(k).total; }      // bytes of ws.d_stage clip c occupies
+};
+
+static void plan_lists(const IngestClip* clips, int nclips, CallLists& L)
 {
+    L.stage.resize((size_t)nclips);
+    L.at.assign((size_t)nclips, 0);
+    for (int c = 0; c < nclips; c++) {
+        const IngestClip& k = clips[c];
+        if (!k.is_list || k.n <= 0) continue;
+        L.stage[c] = list_stage(k);
+        L.at[c] = L.entries;
+        L.entries += (size_t)k.planes() * k.n;
+    }
+}
+
+// the table and its pinned mirror, grow-only; with every other reservation of the call, before its first launch
+static int reserve_lists(avd_ctx* ctx, const CallLists& L)
+{
+    if (int e = ctx->ws.d_ftab.reserve(ctx, L.entries)) return e;
+    return ctx->ws.h_ftab.reserve(ctx, L.entries);
+}
+
+// ws.d_stage and the table are reserved: the table can be filled.  One upload for all lists of the call.
+static int upload_lists(avd_ctx* ctx, const IngestClip* clips, int nclips, const CallLists& L)
+{
+    if (!L.entries) return 0;
+    Workspace& ws = ctx->ws;
+    size_t st = 0;
+    for (int c = 0; c < nclips; c++) {
+        const IngestClip& k = clips[c];
+        if (k.is_list && k.n > 0) {
+            const uint8_t** tab = ws.h_ftab + L.at[c];
+            for (int p = 0; p < k.planes(); p++)
+                for (int f = 0; f < k.n; f++) {
+                    const size_t i = (size_t)p * k.n + f;
+                    tab[i] = k.mem == AVD_MEM_HOST ? ws.d_stage + st + L.stage[c].plane_off[i] : k.list[p][f];
+                }
+        }
+        if (k.n > 0) st += L.total(k, c);
+    }
+    HIP_TRY(ctx, hipMemcpyAsync(ws.d_ftab, ws.h_ftab, sizeof(const uint8_t*) * L.entries, hipMemcpyHostToDevice, ctx->stream));
+    return 0;
+}
+
+// Stage clip c of the call at offset `at` of ws.d_stage (host input; reserved by the caller) and launch its fused full-resolution kernel, which
+// writes the clip's slice (ws.f0, ws.rowbuf_off, ws.lappart_off) of the per-frame buffers.  The clip's geometry is current.
+static int preprocess_clip(avd_ctx* ctx, const IngestClip& k, size_t at, const CallLists& L, int c)
+{
+    uint8_t* dst = ctx->ws.d_stage + at;
+    if (k.is_list) {
+        const ListStage& s = L.stage[c];
+        for (const StageSpan& sp : s.span)
+            HIP_TRY(ctx, hipMemcpyAsync(dst + sp.off, sp.src, sp.bytes, hipMemcpyHostToDevice, ctx->stream));
+        ctx->stage_bytes += (int64_t)s.copied;
+        ctx->stage_copies += (int64_t)s.span.size();
+        const uint8_t* const* h_tab = ctx->ws.h_ftab + L.at[c];
+        const uint8_t* const* d_tab = ctx->ws.d_ftab + L.at[c];
+        const FrameTable ft{list_vec_eligible(k, h_tab)};
+        auto plane = [&](int p) { return p < k.planes() ? reinterpret_cast<const uint8_t*>(d_tab + (size_t)p * k.n) : nullptr; };
+        return launch_preprocess(ctx, k, plane(0), plane(1), plane(2), &ft);
+    }
     const uint8_t *d_in = k.data, *d_uv = k.uv, *d_v = k.v;
     if (k.mem == AVD_MEM_HOST) {
         const ClipStage s = clip_stage(k);
-        uint8_t* dst = ctx->ws.d_stage + at;
         for (int i = 0; i < s.nspans; i++)
             HIP_TRY(ctx, hipMemcpyAsync(dst + s.span[i].off, s.span[i].src, s.span[i].bytes, hipMemcpyHostToDevice, ctx->stream));
         ctx->stage_bytes += (int64_t)s.copied;
+        ctx->stage_copies += s.nspans;
         d_in = dst + s.plane_off[0];
         if (k.format != AVD_FMT_BGR24) d_uv = dst + s.plane_off[1];
         if (k.format == AVD_FMT_I420) d_v = dst + s.plane_off[2];
@@ -551,9 +616,14 @@ static int impl_preprocess(avd_ctx* ctx, const IngestClip& k, uint8_t* small320,
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (int e = avd_ws_reserve(ctx, n, k.disp_h(), k.disp_w())) return e;
     Workspace& ws = ctx->ws;
-    if (int e = ws.d_stage.reserve(ctx, clip_stage(k).total)) return e;
+    CallLists lists;
+    plan_lists(&k, 1, lists);
+    if (int e = ws.d_stage.reserve(ctx, lists.total(k, 0))) return e;
+    if (int e = reserve_lists(ctx, lists)) return e;
     ctx->stage_bytes = 0;
-    if (int e = preprocess_clip(ctx, k, 0)) return e;
+    ctx->stage_copies = 0;
+    if (int e = upload_lists(ctx, &k, 1, lists)) return e;
+    if (int e = preprocess_clip(ctx, k, 0, lists, 0)) return e;
     if (int e = launch_hash(ctx, n)) return e;
     std::vector<unsigned long long> lap((size_t)n * 2);
     if (small320) HIP_TRY(ctx, hipMemcpyAsync(small320, ws.d_small, (size_t)n * AVD_NPIX, hipMemcpyDeviceToHost, ctx->stream));
@@ -576,6 +646,16 @@ static int impl_preprocess_one_picture(avd_ctx* ctx, const avd_picture* pic, uin
     if (!pic) { ctx->err = "null picture"; return AVD_ERR_ARG; }
     IngestClip k{};
     if (int e = refuse(ctx, from_picture(*pic, k))) return e;
+    return impl_preprocess(ctx, k, small320, hash1024, lap_sum, lap_sumsq);
+}
+
+// avd_preprocess_frame_list: the same with from_frame_list
+static int impl_preprocess_one_list(avd_ctx* ctx, const avd_frame_list* list, uint8_t* small320, uint8_t* hash1024, int64_t* lap_sum, int64_t* lap_sumsq)
+{
+    if (!ctx) return AVD_ERR_ARG;
+    if (!list) { ctx->err = "null frame list"; return AVD_ERR_ARG; }
+    IngestClip k{};
+    if (int e = refuse(ctx, from_frame_list(*list, k))) return e;
     return impl_preprocess(ctx, k, small320, hash1024, lap_sum, lap_sumsq);
 }
 
@@ -622,23 +702,28 @@ static int impl_analyze_async(avd_ctx* ctx, const IngestClip* clips, int nclips,
     Workspace& ws = ctx->ws;
     // pass 1: geometry tables (cached) and sizes -- everything is reserved before the first launch of the call
     size_t rowbuf_elems = 0, lappart_elems = 0, stage_bytes = 0;
+    CallLists lists;
+    plan_lists(clips, nclips, lists);
     for (int c = 0; c < nclips; c++) {
         const IngestClip& k = clips[c];
         if (k.n == 0) continue;
         if (int e = avd_ws_geometry(ctx, k.disp_h(), k.disp_w())) return e;
         rowbuf_elems += rowbuf_elems_for(ws, k.n);
         lappart_elems += lappart_elems_for(ws, k.n);
-        stage_bytes += clip_stage(k).total;
+        stage_bytes += lists.total(k, c);
     }
     if (int e = avd_ws_reserve_frames(ctx, n, rowbuf_elems, lappart_elems)) return e;
     if (int e = avd_ws_reserve_fb(ctx, n)) return e;
     if (int e = ws.d_stage.reserve(ctx, stage_bytes)) return e;
+    if (int e = reserve_lists(ctx, lists)) return e;
     // pass 2: per clip, stage (host input) -> fused full-resolution kernel -> hash, at the clip's offsets
     ctx->kmark_used = 0;
     ctx->stage_bytes = 0;
+    ctx->stage_copies = 0;
     // profiling only: an empty launch in front of the first mark, so that the first region is the first kernel and not the queue's wake-up from idle as well
     if (ctx->profiling) hipLaunchKernelGGL(k_wake, dim3(1), dim3(64), 0, ctx->stream);
     stage_mark(ctx, 0);
+    if (int e = upload_lists(ctx, clips, nclips, lists)) return e;
     int f0 = 0;
     size_t rb = 0, lp = 0, st = 0;
     for (int c = 0; c < nclips; c++) {
@@ -649,8 +734,8 @@ static int impl_analyze_async(avd_ctx* ctx, const IngestClip* clips, int nclips,
         ws.h_clipstart[f0] = 1;
         for (int i = 1; i < k.n; i++) ws.h_clipstart[f0 + i] = 0;
         kmark(ctx, AVD_K_PREPROCESS);
-        if (int e = preprocess_clip(ctx, k, st)) return e;
-        st += clip_stage(k).total;
+        if (int e = preprocess_clip(ctx, k, st, lists, c)) return e;
+        st += lists.total(k, c);
         kmark(ctx, AVD_K_HASH);
         if (int e = launch_hash(ctx, k.n)) return e;
         f0 += k.n;
@@ -833,6 +918,18 @@ static int64_t impl_debug_fetch(avd_ctx* ctx, const char* name, void* out, size_
         const int32_t r = ctx->ingest_range;
         std::memcpy(out, &r, sizeof r);
         return (int64_t)sizeof r;
+    }
+    if (std::strcmp(name, "ingest_list") == 0) {       // host state: did that launch take its frame bases from a table, and of how many frames
+        if (!ctx->ingest_plan_valid) { ctx->err = "ingest_list not recorded yet: no ingest kernel was launched on this context"; return AVD_ERR_ARG; }
+        if (out_bytes < sizeof(ctx->ingest_list)) { ctx->err = "ingest_list is int32[2]"; return AVD_ERR_ARG; }
+        std::memcpy(out, ctx->ingest_list, sizeof(ctx->ingest_list));
+        return (int64_t)sizeof(ctx->ingest_list);
+    }
+    if (std::strcmp(name, "stage_copies") == 0) {      // host state: staging copies the last ingest call issued
+        if (ctx->stage_copies < 0) { ctx->err = "stage_copies not recorded yet: no ingest call has run on this context"; return AVD_ERR_ARG; }
+        if (out_bytes < sizeof(int64_t)) { ctx->err = "stage_copies is int64[1]"; return AVD_ERR_ARG; }
+        std::memcpy(out, &ctx->stage_copies, sizeof(int64_t));
+        return (int64_t)sizeof(int64_t);
     }
     if (std::strcmp(name, "stage_bytes") == 0) {       // host state: bytes the last ingest call copied from host memory (0: device input)
         if (ctx->stage_bytes < 0) { ctx->err = "stage_bytes not recorded yet: no ingest call has run on this context"; return AVD_ERR_ARG; }
@@ -1151,6 +1248,10 @@ static int analyze_pictures(avd_ctx* ctx, const avd_picture* clips, int nclips, 
 {
     return analyze_entry(ctx, wait, [&] { return impl_analyze_list_async(ctx, clips, nclips, records, from_picture); });
 }
+static int analyze_frame_lists(avd_ctx* ctx, const avd_frame_list* lists, int nlists, avd_frame_record* records, Wait wait) noexcept
+{
+    return analyze_entry(ctx, wait, [&] { return impl_analyze_list_async(ctx, lists, nlists, records, from_frame_list); });
+}
 
 // ---- C-ABI ------------------------------------------------------------------------------
 extern "C" {
@@ -1212,6 +1313,21 @@ int avd_analyze_pictures_async(avd_ctx* ctx, const avd_picture* clips, int nclip
 int avd_analyze_pictures(avd_ctx* ctx, const avd_picture* clips, int nclips, avd_frame_record* records)
 {
     return analyze_pictures(ctx, clips, nclips, records, Wait::yes);
+}
+
+int avd_preprocess_frame_list(avd_ctx* ctx, const avd_frame_list* list, uint8_t* small320, uint8_t* hash1024, int64_t* lap_sum, int64_t* lap_sumsq)
+{
+    return guarded(ctx, [&] { return impl_preprocess_one_list(ctx, list, small320, hash1024, lap_sum, lap_sumsq); });
+}
+
+int avd_analyze_frame_lists_async(avd_ctx* ctx, const avd_frame_list* lists, int nlists, avd_frame_record* records)
+{
+    return analyze_frame_lists(ctx, lists, nlists, records, Wait::no);
+}
+
+int avd_analyze_frame_lists(avd_ctx* ctx, const avd_frame_list* lists, int nlists, avd_frame_record* records)
+{
+    return analyze_frame_lists(ctx, lists, nlists, records, Wait::yes);
 }
 
 int avd_preprocess_nv12(avd_ctx* ctx, const uint8_t* y, const uint8_t* uv, int mem, int n, int h, int w, int64_t y_row_stride,

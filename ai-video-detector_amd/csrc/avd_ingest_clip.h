@@ -5,6 +5,7 @@
 #include <stddef.h>
 #include <stdint.h>
 #include <algorithm>
+#include <vector>
 #include "../../include/avd.h"
 
 // format says what the planes are -- nothing downstream looks at which pointers are null to find out:
@@ -14,11 +15,17 @@
 // rotate: quarter turns clockwise from the stored picture (h, w, the planes and strides: always the STORED one) to the displayed picture, whose
 // size the geometry tables, the band plan and every result follow (4:2:0 clips only).
 // full_range: AVD_FMT_FULL_RANGE of the descriptor, taken out of `format`, which stays the plain layout.
-// A clip is made by bgr_clip / nv12_clip / i420_clip (the entry points that name their format), from_public (avd_clip) or from_picture
-// (avd_picture), and by nothing else.
+// list: the frames do not lie at a fixed distance from each other but where a table says -- list[p][f] = plane p of frame f (avd_frame_list;
+// p as data, uv, v).  The arrays are the CALLER's host memory, read while the call runs and never kept.  data / uv / v and the frame strides
+// of such a clip are unused (null, 0); everything else means what it means for a strided clip.
+// A clip is made by bgr_clip / nv12_clip / i420_clip (the entry points that name their format), from_public (avd_clip), from_picture
+// (avd_picture) or from_frame_list (avd_frame_list), and by nothing else.
 struct IngestClip {
     int format;
     const uint8_t *data, *uv, *v;
+    const uint8_t* const* list[3];
+    bool is_list;         // from_frame_list made it (the arrays may still be null: check_clip refuses that)
+    int planes() const { return format == AVD_FMT_BGR24 ? 1 : (format == AVD_FMT_I420 ? 3 : 2); }
     int mem, n, h, w;
     int64_t row_stride, frame_stride, uv_row_stride, uv_frame_stride;
     int rotate;
@@ -91,9 +98,36 @@ inline Refusal from_picture(const avd_picture& p, IngestClip& k)
     return {0, nullptr};
 }
 
+// avd_frame_list: avd_picture with a table of plane pointers per frame in place of base + f * frame_stride.  The same refusals in the same order.
+inline Refusal from_frame_list(const avd_frame_list& p, IngestClip& k)
+{
+    if (p.struct_size != sizeof(avd_frame_list)) return {AVD_ERR_ARG, "avd_frame_list.struct_size is not sizeof(avd_frame_list)"};
+    const int layout = p.format & 0xFF, full_range = (p.format & AVD_FMT_FULL_RANGE) != 0;
+    if ((p.format & ~(0xFF | AVD_FMT_FULL_RANGE)) || (layout != AVD_FMT_BGR24 && layout != AVD_FMT_NV12 && layout != AVD_FMT_I420))
+        return {AVD_ERR_ARG, "bad avd_frame_list.format"};
+    if (full_range && layout == AVD_FMT_BGR24) return {AVD_ERR_ARG, "AVD_FMT_FULL_RANGE describes 4:2:0 samples: a BGR picture has no range"};
+    if (p.rotate < 0 || p.rotate > 3) return {AVD_ERR_ARG, "avd_frame_list.rotate must be 0 .. 3 quarter turns"};
+    if (p.reserved != 0) return {AVD_ERR_ARG, "avd_frame_list.reserved must be 0"};
+    if (layout == AVD_FMT_BGR24) {
+        if (p.rotate) return {AVD_ERR_UNSUPPORTED, "a turned BGR picture is not on the path: cv2 hands BGR over already rotated"};
+        k = bgr_clip(nullptr, p.mem, p.n, p.h, p.w, p.row_stride[0], 0);
+    } else if (layout == AVD_FMT_NV12) {
+        k = nv12_clip(nullptr, nullptr, p.mem, p.n, p.h, p.w, p.row_stride[0], p.row_stride[1], 0, 0);
+    } else {
+        if (p.row_stride[1] != p.row_stride[2]) return {AVD_ERR_ARG, "the U and V planes of an I420 picture share their strides"};
+        k = i420_clip(nullptr, nullptr, nullptr, p.mem, p.n, p.h, p.w, p.row_stride[0], p.row_stride[1], 0, 0);
+    }
+    k.is_list = true;
+    for (int i = 0; i < k.planes(); i++) k.list[i] = p.plane[i];
+    k.rotate = p.rotate;
+    k.full_range = full_range;
+    return {0, nullptr};
+}
+
 // The one argument check of every ingest entry point.  A clip with several faults is refused for the FIRST of, in this order (include/avd.h):
 // mem; the size range; even width and height (4:2:0); the 32 x 32 minimum (of the displayed picture: a quarter turn exchanges h and w, which
-// this test does not notice); null planes of a clip that has frames; strides.
+// this test does not notice); null planes of a clip that has frames -- of a list: a null array, then a null entry of one; strides (a list
+// has no frame strides to check: its frames may lie anywhere, in any order, and may repeat).
 inline Refusal check_clip(const IngestClip& k)
 {
     const bool bgr = k.format == AVD_FMT_BGR24, planar = k.format == AVD_FMT_I420;
@@ -102,11 +136,20 @@ inline Refusal check_clip(const IngestClip& k)
     if (n < 0 || h <= 0 || w <= 0 || h > 16384 || w > 16384) return {AVD_ERR_ARG, "bad frame geometry"};
     if (!bgr && ((h | w) & 1)) return {AVD_ERR_UNSUPPORTED, planar ? "I420 needs even width and height" : "NV12 needs even width and height"};
     if (h < AVD_HASH || w < AVD_HASH) return {AVD_ERR_UNSUPPORTED, "frame smaller than 32x32: INTER_AREA upscaling is not on the path"};
-    if (n > 0 && (!k.data || (!bgr && !k.uv) || (planar && !k.v)))
+    if (k.is_list) {
+        if (n > 0) {
+            for (int p = 0; p < k.planes(); p++)
+                if (!k.list[p]) return {AVD_ERR_ARG, "null plane array of a frame list"};
+            for (int p = 0; p < k.planes(); p++)
+                for (int f = 0; f < n; f++)
+                    if (!k.list[p][f]) return {AVD_ERR_ARG, "null plane pointer in a frame list"};
+        }
+    } else if (n > 0 && (!k.data || (!bgr && !k.uv) || (planar && !k.v)))
         return {AVD_ERR_ARG, bgr ? "null frame pointer" : (planar ? "null I420 plane pointer" : "null plane pointer")};
     const int64_t row = bgr ? (int64_t)w * 3 : w, crow = planar ? w / 2 : w;      // bytes of a luma (BGR: frame) row and of a chroma row
-    bool small = k.row_stride < row || (n > 1 && k.frame_stride < k.row_stride * (h - 1) + row);
-    if (!bgr) small = small || k.uv_row_stride < crow || (n > 1 && k.uv_frame_stride < k.uv_row_stride * (h / 2 - 1) + crow);
+    const bool strided = !k.is_list && n > 1;
+    bool small = k.row_stride < row || (strided && k.frame_stride < k.row_stride * (h - 1) + row);
+    if (!bgr) small = small || k.uv_row_stride < crow || (strided && k.uv_frame_stride < k.uv_row_stride * (h / 2 - 1) + crow);
     if (small) return {AVD_ERR_ARG, bgr ? "strides smaller than the frame" : (planar ? "strides smaller than the I420 planes" : "strides smaller than the planes")};
     return {0, nullptr};
 }
@@ -131,7 +174,7 @@ struct ClipStage { StageSpan span[3]; int nspans; size_t plane_off[3], total, co
 inline ClipStage clip_stage(const IngestClip& c)
 {
     ClipStage s{};
-    if (c.mem != AVD_MEM_HOST || c.n <= 0) return s;
+    if (c.mem != AVD_MEM_HOST || c.n <= 0 || c.is_list) return s;      // a list has its own plan: list_stage
     const bool bgr = c.format == AVD_FMT_BGR24, planar = c.format == AVD_FMT_I420;
     const uint8_t* src[3] = {c.data, c.uv, c.v};
     const int planes = bgr ? 1 : (planar ? 3 : 2);
@@ -153,4 +196,61 @@ inline ClipStage clip_stage(const IngestClip& c)
     for (int i = 0; i < s.nspans; i++) s.copied += s.span[i].bytes;
     s.total = round256(s.span[s.nspans - 1].off + s.span[s.nspans - 1].bytes);
     return s;
+}
+
+// ---- a list of frames (IngestClip::is_list) ----------------------------------------------------------------------------------------------
+// The rule of clip_stage for any number of planes: the spans of all (frame, plane) pairs, in address order, merged where they overlap or touch;
+// every merged span on a 256-byte boundary, every plane at its own offset inside its span.  Frames that are views of one stacked array stage as
+// the strided clip does (the same bytes, ONE copy where the stack is dense); separately allocated frames are n x planes copies; a frame that
+// is listed twice crosses the link once; no host byte is copied twice.  Spans that a gap separates are not merged, however small the gap.
+// plane_off[p * n + f]: where plane p of frame f lands.  Only the pointer VALUES are used: nothing is read through them.
+struct ListStage { std::vector<StageSpan> span; std::vector<size_t> plane_off; size_t total = 0, copied = 0; };
+
+// bytes of plane p of one frame, first to last
+inline size_t list_plane_bytes(const IngestClip& c, int p)
+{
+    const bool bgr = c.format == AVD_FMT_BGR24, planar = c.format == AVD_FMT_I420;
+    if (p == 0) return plane_span(0, 1, c.row_stride, c.h, (size_t)c.w * (bgr ? 3 : 1));
+    return plane_span(0, 1, c.uv_row_stride, c.h / 2, (size_t)(planar ? c.w / 2 : c.w));
+}
+
+inline ListStage list_stage(const IngestClip& c)
+{
+    ListStage s;
+    if (!c.is_list || c.mem != AVD_MEM_HOST || c.n <= 0) return s;
+    const int planes = c.planes(), n = c.n;
+    struct Item { const uint8_t* src; size_t bytes; int slot; };
+    std::vector<Item> items;
+    items.reserve((size_t)planes * n);
+    for (int p = 0; p < planes; p++)
+        for (int f = 0; f < n; f++) items.push_back(Item{c.list[p][f], list_plane_bytes(c, p), p * n + f});
+    std::sort(items.begin(), items.end(), [](const Item& a, const Item& b) { return (uintptr_t)a.src < (uintptr_t)b.src; });
+    s.plane_off.resize(items.size());
+    for (const Item& it : items) {
+        StageSpan* last = s.span.empty() ? nullptr : &s.span.back();
+        if (last && (uintptr_t)it.src <= (uintptr_t)last->src + last->bytes)
+            last->bytes = std::max(last->bytes, (size_t)((uintptr_t)it.src - (uintptr_t)last->src) + it.bytes);
+        else {
+            s.span.push_back(StageSpan{it.src, it.bytes, last ? round256(last->off + last->bytes) : 0});
+            last = &s.span.back();
+        }
+        s.plane_off[it.slot] = last->off + (size_t)((uintptr_t)it.src - (uintptr_t)last->src);
+    }
+    for (const StageSpan& sp : s.span) s.copied += sp.bytes;
+    s.total = round256(s.span.back().off + s.span.back().bytes);
+    return s;
+}
+
+// May a list run the vector fills?  Their rule (launch_preprocess: w % 16 == 0, 16-byte aligned planes and row strides, 8 bytes for the
+// chroma planes of I420) must hold for EVERY frame; one frame that fails sends the whole list through the scalar fill, with the same results.
+// tab[p * n + f]: where the kernel will find plane p of frame f (device addresses: the caller's planes, or their places in the staging buffer).
+inline bool list_vec_eligible(const IngestClip& c, const uint8_t* const* tab)
+{
+    const bool bgr = c.format == AVD_FMT_BGR24, planar = c.format == AVD_FMT_I420;
+    const int ca = planar ? 8 : 16;
+    if (c.w % 16 != 0 || c.row_stride % 16 != 0 || (!bgr && c.uv_row_stride % ca != 0)) return false;
+    for (int p = 0; p < c.planes(); p++)
+        for (int f = 0; f < c.n; f++)
+            if ((uintptr_t)tab[(size_t)p * c.n + f] % (p == 0 ? 16 : ca) != 0) return false;
+    return true;
 }

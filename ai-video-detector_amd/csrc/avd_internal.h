@@ -166,6 +166,9 @@ struct Workspace {
     DevBuf<int> d_clipstart; PinBuf<int> h_clipstart;   // [n] 1 = first frame of a clip
     // preprocess
     DevBuf<uint8_t> d_stage;          // staged host input
+    // frame lists (avd_frame_list): the plane pointers of every list of the call, per list [plane][frame] -- device addresses (the caller's
+    // planes, or their places in d_stage); filled in the pinned mirror and uploaded ONCE per call, so an asynchronous call owns its copy
+    DevBuf<const uint8_t*> d_ftab; PinBuf<const uint8_t*> h_ftab;
     DevBuf<uint8_t> d_small;          // [n][320*320]
     DevBuf<float> d_rowbuf;           // [n][h][32]
     DevBuf<uint8_t> d_area;           // [n][1024]
@@ -252,6 +255,8 @@ struct avd_ctx {
     int ingest_plan_valid = 0;       // 0 until the first ingest launch
     int ingest_rotate = 0;           // the rotation that launch ran with (debug buffer "ingest_rotate")
     int ingest_range = 0;            // 1: that launch ran with full-range conversion constants (debug buffer "ingest_range")
+    int ingest_list[2] = {0, 0};     // that launch took its frame bases from a table of plane pointers / the frames the table held (debug buffer "ingest_list")
+    int64_t stage_copies = -1;       // host-to-device staging copies of the last ingest call (debug buffer "stage_copies"); -1 until the first one
     int64_t stage_bytes = -1;        // bytes the last ingest call copied from host memory (debug buffer "stage_bytes"; 0: device input); -1 until the first one
     int rec_n = 0;                   // records the last avd_analyze_* call left in ws.d_rec (0 after any other entry point: avd_allgather_last_records checks it)
     void* comm = nullptr;            // RCCL communicator (avd_comm.cpp), bound at run time
@@ -330,7 +335,10 @@ int avd_ws_reserve_fb(avd_ctx* ctx, int n);
 // the clip's frames, resident at d_in (BGR) or d_in / d_uv (NV12: Y rows at d_in + f*frame_stride + y*row_stride, chroma rows at
 // d_uv + f*uv_frame_stride + (y/2)*uv_row_stride) or d_in / d_uv / d_v (I420: d_uv is the U plane, both chroma planes with the uv strides),
 // into the clip's slice of the per-frame buffers; which of the three it is says clip.format; the clip's geometry is current
-int launch_preprocess(avd_ctx* ctx, const IngestClip& clip, const uint8_t* d_in, const uint8_t* d_uv, const uint8_t* d_v);
+// list (null: strided): the frames come from a device table of plane pointers (avd_frame_list) -- d_in / d_uv / d_v are then the addresses of the
+// table's per-plane arrays, n entries each, and the clip's frame strides are unused
+struct FrameTable { bool aligned; };      // aligned: every frame of the list allows the 16-byte fills (list_vec_eligible)
+int launch_preprocess(avd_ctx* ctx, const IngestClip& clip, const uint8_t* d_in, const uint8_t* d_uv, const uint8_t* d_v, const FrameTable* list = nullptr);
 int launch_hash(avd_ctx* ctx, int n);
 int avd_calls_in_flight();      // avd_capi.hip: contexts of this process holding an enqueued, undrained avd_analyze_* call
 int launch_farneback(avd_ctx* ctx, const uint8_t* d_small, int n);    // all pairs of n resident frames, into the Farneback scratch

@@ -111,6 +111,22 @@ __device__ __forceinline__ bool decode_band(const PreParams& P, int n, Band& b) 
     return b.lid < total;
 }
 
+// Where the planes of frame f start.  strided: at a fixed distance from frame 0's.  listed: where a device table of plane pointers says
+// (avd_frame_list) -- the kernel's plane argument then IS that table, entry f of it the plane of frame f, and the frame stride is unused.  f is
+// uniform over the workgroup and nothing the kernel stores aliases the table, so the base arrives by one scalar load per plane and workgroup,
+// ahead of the fill.  The entry is read as a pointer into GLOBAL memory (address space 1; what a kernel argument is known to be and a pointer
+// that comes out of memory is not): the fills below then issue the same global_load instructions as in the strided kernels -- a generic pointer
+// would make them flat loads, which also count against lgkmcnt beside the LDS traffic of the tile.
+// A template parameter of the kernels: the strided instantiations contain no trace of the table.
+enum class Frames { strided, listed };
+using GlobalPlane = const __attribute__((address_space(1))) uint8_t*;
+template <Frames FR>
+__device__ __forceinline__ const uint8_t* frame_base(const uint8_t* plane, int f, int64_t frame_stride)
+{
+    if constexpr (FR == Frames::listed) return (const uint8_t*)reinterpret_cast<const GlobalPlane*>(plane)[f];
+    else return plane + (int64_t)f * frame_stride;
+}
+
 __device__ __forceinline__ int reflect_once(int p, int len)      // valid for -len < p < 2*len-1
 {
     p = p < 0 ? -p : p;
@@ -457,7 +473,7 @@ __device__ __forceinline__ void fill_bgr_staged(uint8_t* tile, const uint8_t* fr
 }
 
 // Generic kernel: one workgroup per band, any geometry / alignment (scalar loads if needed).
-template <bool VEC>
+template <bool VEC, Frames FR>
 __global__ __launch_bounds__(kThreads) void k_preprocess(const uint8_t* __restrict__ bgr, int n,
                                                         PreParams P, uint8_t* __restrict__ small,
                                                         float* __restrict__ rowbuf,
@@ -467,7 +483,7 @@ __global__ __launch_bounds__(kThreads) void k_preprocess(const uint8_t* __restri
     Band b;
     if (!decode_band(P, n, b)) return;
     const int tid = threadIdx.x;
-    const uint8_t* frame = bgr + (int64_t)b.f * P.frame_stride;
+    const uint8_t* frame = frame_base<FR>(bgr, b.f, P.frame_stride);
     if (VEC) fill_bgr_vec16(tile, frame, P, b, tid);
     else fill_bgr_scalar(tile, frame, P, b, tid);
     fill_column_halo(tile, b.trows, P.pitch, P.w, tid);
@@ -476,7 +492,7 @@ __global__ __launch_bounds__(kThreads) void k_preprocess(const uint8_t* __restri
 
 // Aligned fast path: one workgroup per band like the generic kernel, the band staged in registers (fill_bgr_staged)
 // and the resampling tables in LDS.
-template <int NI>
+template <int NI, Frames FR>
 __global__ __launch_bounds__(kThreads, 4) void k_preprocess_vec(const uint8_t* __restrict__ bgr, int n,
                                                                PreParams P, uint8_t* __restrict__ small,
                                                                float* __restrict__ rowbuf,
@@ -488,7 +504,7 @@ __global__ __launch_bounds__(kThreads, 4) void k_preprocess_vec(const uint8_t* _
     const int tid = threadIdx.x;
     LdsTabs* lt = reinterpret_cast<LdsTabs*>(tile + lds_tile_bytes(P.rows_per_band + 2, P.pitch));
     fill_lds_tabs(lt, P, tid);
-    fill_bgr_staged<NI>(tile, bgr + (int64_t)b.f * P.frame_stride, P, b, tid);
+    fill_bgr_staged<NI>(tile, frame_base<FR>(bgr, b.f, P.frame_stride), P, b, tid);
     __syncthreads();
     store_moments(lap_part, b.lid, tid, band_phases<true>(tile, lt, P, b, tid, small, rowbuf));
 }
@@ -806,7 +822,7 @@ __device__ __forceinline__ void fill_i420_strip(uint8_t* tile, const uint8_t* yf
 
 // ROT: quarter turns clockwise from the stored to the displayed picture.  0: the stored picture is the displayed one; 2: the flipped
 // instantiations of the same fills; 1, 3: the strip fill (VEC unused).  P describes the DISPLAYED picture throughout.
-template <bool VEC, int ROT>
+template <bool VEC, int ROT, Frames FR>
 __global__ __launch_bounds__(kThreads) void k_preprocess_nv12(const uint8_t* __restrict__ yplane, Nv12Params nv, int n,
                                                              PreParams P, uint8_t* __restrict__ small,
                                                              float* __restrict__ rowbuf, long long* __restrict__ lap_part)
@@ -815,8 +831,8 @@ __global__ __launch_bounds__(kThreads) void k_preprocess_nv12(const uint8_t* __r
     Band b;
     if (!decode_band(P, n, b)) return;
     const int tid = threadIdx.x;
-    const uint8_t* yfr = yplane + (int64_t)b.f * P.frame_stride;
-    const uint8_t* cfr = nv.uv + (int64_t)b.f * nv.uv_frame_stride;
+    const uint8_t* yfr = frame_base<FR>(yplane, b.f, P.frame_stride);
+    const uint8_t* cfr = frame_base<FR>(nv.uv, b.f, nv.uv_frame_stride);
     if constexpr (ROT & 1) fill_nv12_strip<ROT>(tile, yfr, cfr, nv, P, b, tid);
     else if (VEC) fill_nv12_tables<ROT == 2>(tile, yfr, cfr, nv, P, b, tid);
     else fill_nv12_scalar<ROT == 2>(tile, yfr, cfr, nv, P, b, tid);
@@ -825,7 +841,7 @@ __global__ __launch_bounds__(kThreads) void k_preprocess_nv12(const uint8_t* __r
 }
 
 // Planar 4:2:0 (I420; YV12 with the chroma pointers exchanged): k_preprocess_nv12 with the chroma fetched from two planes
-template <bool VEC, int ROT>
+template <bool VEC, int ROT, Frames FR>
 __global__ __launch_bounds__(kThreads) void k_preprocess_i420(const uint8_t* __restrict__ yplane, I420Params ip, int n,
                                                              PreParams P, uint8_t* __restrict__ small,
                                                              float* __restrict__ rowbuf, long long* __restrict__ lap_part)
@@ -834,9 +850,9 @@ __global__ __launch_bounds__(kThreads) void k_preprocess_i420(const uint8_t* __r
     Band b;
     if (!decode_band(P, n, b)) return;
     const int tid = threadIdx.x;
-    const uint8_t* yfr = yplane + (int64_t)b.f * P.frame_stride;
-    const uint8_t* ufr = ip.u + (int64_t)b.f * ip.c_frame_stride;
-    const uint8_t* vfr = ip.v + (int64_t)b.f * ip.c_frame_stride;
+    const uint8_t* yfr = frame_base<FR>(yplane, b.f, P.frame_stride);
+    const uint8_t* ufr = frame_base<FR>(ip.u, b.f, ip.c_frame_stride);
+    const uint8_t* vfr = frame_base<FR>(ip.v, b.f, ip.c_frame_stride);
     if constexpr (ROT & 1) fill_i420_strip<ROT>(tile, yfr, ufr, vfr, ip, P, b, tid);
     else if (VEC) fill_i420_tables<ROT == 2>(tile, yfr, ufr, vfr, ip, P, b, tid);
     else fill_i420_scalar<ROT == 2>(tile, yfr, ufr, vfr, ip, P, b, tid);
@@ -946,7 +962,9 @@ static bool aligned_to(int a, const void* p, int64_t row_stride, int64_t frame_s
 }
 static bool aligned16(const void* p, int64_t row_stride, int64_t frame_stride) { return aligned_to(16, p, row_stride, frame_stride); }
 
-int launch_preprocess(avd_ctx* ctx, const IngestClip& clip, const uint8_t* d_in, const uint8_t* d_uv, const uint8_t* d_v)
+// list (null: a strided clip): the clip's frames come from a device table of plane pointers -- d_in / d_uv / d_v are then the addresses of the
+// table's per-plane arrays (n entries each), and list->aligned says whether every frame allows the 16-byte fills (list_vec_eligible).
+int launch_preprocess(avd_ctx* ctx, const IngestClip& clip, const uint8_t* d_in, const uint8_t* d_uv, const uint8_t* d_v, const FrameTable* list)
 {
     Workspace& ws = ctx->ws;
     PreParams P = ws.pre;
@@ -959,13 +977,15 @@ int launch_preprocess(avd_ctx* ctx, const IngestClip& clip, const uint8_t* d_in,
     // the planar chroma planes are read 8 bytes at a time (fill_i420_tables), every other plane 16
     const bool chroma_ok = planar ? aligned_to(8, d_uv, clip.uv_row_stride, clip.uv_frame_stride) && aligned_to(8, d_v, clip.uv_row_stride, clip.uv_frame_stride)
                                   : bgr || aligned16(d_uv, clip.uv_row_stride, clip.uv_frame_stride);
-    const bool vec = P.w % 16 == 0 && aligned16(d_in, clip.row_stride, clip.frame_stride) && chroma_ok;
+    const bool vec = list ? list->aligned : P.w % 16 == 0 && aligned16(d_in, clip.row_stride, clip.frame_stride) && chroma_ok;
     const int ni = vec && bgr ? band_plan(P.w).ni : 0;
     auto launch = [&](IngestKernel id, auto kernel, size_t lds, auto... source) {
         ctx->ingest_plan = IngestPlan{P.h, P.w, P.rows_per_band, P.nbands, P.pitch, ni, (int)lds, id};
         ctx->ingest_plan_valid = 1;
         ctx->ingest_rotate = clip.rotate;
         ctx->ingest_range = !bgr && clip.full_range;
+        ctx->ingest_list[0] = list != nullptr;
+        ctx->ingest_list[1] = list ? n : 0;
         hipLaunchKernelGGL(kernel, dim3(grid), dim3(kThreads), lds, ctx->stream, source..., n, P, ws.d_small + (size_t)ws.f0 * AVD_NPIX,
                            ws.d_rowbuf + ws.rowbuf_off, ws.d_lap_part + ws.lappart_off);
     };
@@ -985,40 +1005,46 @@ int launch_preprocess(avd_ctx* ctx, const IngestClip& clip, const uint8_t* d_in,
         }
         tabs = lds_nvtab_off(P.rows_per_band + 2, P.pitch) + lds_nvtab_bytes(yc.ntab);
     }
-    if (planar) {
-        I420Params ip{};
-        ip.u = d_uv; ip.v = d_v; ip.c_row_stride = clip.uv_row_stride; ip.c_frame_stride = clip.uv_frame_stride;
-        ip.k = yc;
-        if (rot == 1) launch(kIngestI420Strip, k_preprocess_i420<false, 1>, tabs, d_in, ip);
-        else if (rot == 3) launch(kIngestI420Strip, k_preprocess_i420<false, 3>, tabs, d_in, ip);
-        else if (rot == 2 && vec) launch(kIngestI420Tables, k_preprocess_i420<true, 2>, tabs, d_in, ip);
-        else if (rot == 2) launch(kIngestI420Scalar, k_preprocess_i420<false, 2>, tile, d_in, ip);
-        else if (vec) launch(kIngestI420Tables, k_preprocess_i420<true, 0>, tabs, d_in, ip);
-        else launch(kIngestI420Scalar, k_preprocess_i420<false, 0>, tile, d_in, ip);
-    } else if (!bgr) {
-        Nv12Params nv{};
-        nv.uv = d_uv; nv.uv_row_stride = clip.uv_row_stride; nv.uv_frame_stride = clip.uv_frame_stride;
-        nv.k = yc;
-        // (a register-staged variant in the style of k_preprocess_vec measured no faster: the kernel is bound by the
-        // conversion's integer arithmetic, not by how its loads are issued -- profiles/r02_experiments.md)
-        if (rot == 1) launch(kIngestNv12Strip, k_preprocess_nv12<false, 1>, tabs, d_in, nv);
-        else if (rot == 3) launch(kIngestNv12Strip, k_preprocess_nv12<false, 3>, tabs, d_in, nv);
-        else if (rot == 2 && vec) launch(kIngestNv12Tables, k_preprocess_nv12<true, 2>, tabs, d_in, nv);
-        else if (rot == 2) launch(kIngestNv12Scalar, k_preprocess_nv12<false, 2>, tile, d_in, nv);
-        else if (vec) launch(kIngestNv12Tables, k_preprocess_nv12<true, 0>, tabs, d_in, nv);
-        else launch(kIngestNv12Scalar, k_preprocess_nv12<false, 0>, tile, d_in, nv);
-    } else if (ni) {
-        const size_t lds = tile + sizeof(LdsTabs);
-        switch (ni) {
-        case 3: launch(kIngestBgrStaged, k_preprocess_vec<3>, lds, d_in); break;
-        case 4: launch(kIngestBgrStaged, k_preprocess_vec<4>, lds, d_in); break;
-        case 6: launch(kIngestBgrStaged, k_preprocess_vec<6>, lds, d_in); break;
-        case 8: launch(kIngestBgrStaged, k_preprocess_vec<8>, lds, d_in); break;
-        case 9: launch(kIngestBgrStaged, k_preprocess_vec<9>, lds, d_in); break;
-        default: ctx->err = "internal error: the band plan asks for a k_preprocess_vec that is not built"; return AVD_ERR_DEVICE;
-        }
-    } else if (vec) launch(kIngestBgrVec16, k_preprocess<true>, tile, d_in);
-    else launch(kIngestBgrScalar, k_preprocess<false>, tile, d_in);
+    // one selection for both sources of the frame base: the same fills under the same ids
+    auto select = [&](auto frames_tag) -> int {
+        constexpr Frames FR = decltype(frames_tag)::value;
+        if (planar) {
+            I420Params ip{};
+            ip.u = d_uv; ip.v = d_v; ip.c_row_stride = clip.uv_row_stride; ip.c_frame_stride = clip.uv_frame_stride;
+            ip.k = yc;
+            if (rot == 1) launch(kIngestI420Strip, k_preprocess_i420<false, 1, FR>, tabs, d_in, ip);
+            else if (rot == 3) launch(kIngestI420Strip, k_preprocess_i420<false, 3, FR>, tabs, d_in, ip);
+            else if (rot == 2 && vec) launch(kIngestI420Tables, k_preprocess_i420<true, 2, FR>, tabs, d_in, ip);
+            else if (rot == 2) launch(kIngestI420Scalar, k_preprocess_i420<false, 2, FR>, tile, d_in, ip);
+            else if (vec) launch(kIngestI420Tables, k_preprocess_i420<true, 0, FR>, tabs, d_in, ip);
+            else launch(kIngestI420Scalar, k_preprocess_i420<false, 0, FR>, tile, d_in, ip);
+        } else if (!bgr) {
+            Nv12Params nv{};
+            nv.uv = d_uv; nv.uv_row_stride = clip.uv_row_stride; nv.uv_frame_stride = clip.uv_frame_stride;
+            nv.k = yc;
+            // (a register-staged variant in the style of k_preprocess_vec measured no faster: the kernel is bound by the
+            // conversion's integer arithmetic, not by how its loads are issued -- profiles/r02_experiments.md)
+            if (rot == 1) launch(kIngestNv12Strip, k_preprocess_nv12<false, 1, FR>, tabs, d_in, nv);
+            else if (rot == 3) launch(kIngestNv12Strip, k_preprocess_nv12<false, 3, FR>, tabs, d_in, nv);
+            else if (rot == 2 && vec) launch(kIngestNv12Tables, k_preprocess_nv12<true, 2, FR>, tabs, d_in, nv);
+            else if (rot == 2) launch(kIngestNv12Scalar, k_preprocess_nv12<false, 2, FR>, tile, d_in, nv);
+            else if (vec) launch(kIngestNv12Tables, k_preprocess_nv12<true, 0, FR>, tabs, d_in, nv);
+            else launch(kIngestNv12Scalar, k_preprocess_nv12<false, 0, FR>, tile, d_in, nv);
+        } else if (ni) {
+            const size_t lds = tile + sizeof(LdsTabs);
+            switch (ni) {
+            case 3: launch(kIngestBgrStaged, k_preprocess_vec<3, FR>, lds, d_in); break;
+            case 4: launch(kIngestBgrStaged, k_preprocess_vec<4, FR>, lds, d_in); break;
+            case 6: launch(kIngestBgrStaged, k_preprocess_vec<6, FR>, lds, d_in); break;
+            case 8: launch(kIngestBgrStaged, k_preprocess_vec<8, FR>, lds, d_in); break;
+            case 9: launch(kIngestBgrStaged, k_preprocess_vec<9, FR>, lds, d_in); break;
+            default: ctx->err = "internal error: the band plan asks for a k_preprocess_vec that is not built"; return AVD_ERR_DEVICE;
+            }
+        } else if (vec) launch(kIngestBgrVec16, k_preprocess<true, FR>, tile, d_in);
+        else launch(kIngestBgrScalar, k_preprocess<false, FR>, tile, d_in);
+        return 0;
+    };
+    if (int e = list ? select(std::integral_constant<Frames, Frames::listed>{}) : select(std::integral_constant<Frames, Frames::strided>{})) return e;
     HIP_TRY(ctx, hipGetLastError());
     return 0;
 }

@@ -32,7 +32,8 @@
  *     (AVD_ERR_ARG).  What an avd_picture alone can get wrong is refused before any of these, in this order:
  *     struct_size; format (an unknown layout in the low byte, or a bit above it other than AVD_FMT_FULL_RANGE);
  *     AVD_FMT_FULL_RANGE on a BGR picture; rotate; reserved; BGR with a rotation; U and V strides that differ.
- *     A records pointer that is null while
+ *     An avd_frame_list is refused for the same things in the same order (it has no frame strides; a null array of plane pointers, then a
+ *     null entry of one, stand where the null plane stands).  A records pointer that is null while
  *     there are frames to write, after all of them.  The clips of a batch are checked in order.
  *   - if no HIP device is usable avd_create fails (AVD_ERR_DEVICE): there is no
  *     CPU fallback in this library.
@@ -116,7 +117,7 @@ int avd_analyze_frames(avd_ctx* ctx, const uint8_t* bgr, int mem, int n, int h, 
  * other call on the context first completes it -- its records buffer is filled and
  * the re-run of its flagged pairs (fb_mode 1) is settled -- and returns its error
  * instead of running if it failed.  The same holds for avd_analyze_frames_nv12_async,
- * avd_analyze_frames_i420_async, avd_analyze_batch_async and avd_analyze_pictures_async: whichever of them is
+ * avd_analyze_frames_i420_async, avd_analyze_batch_async, avd_analyze_pictures_async and avd_analyze_frame_lists_async: whichever of them is
  * outstanding is drained by any other call, these included.  Exempt: avd_synchronize, avd_destroy,
  * avd_last_error, avd_get_option, avd_stage_ms, avd_kernel_ms, avd_timer_start /
  * avd_timer_stop and avd_wait_stream.  An option set while a call is pending applies
@@ -237,6 +238,10 @@ typedef struct avd_picture {
 int avd_preprocess_picture(avd_ctx* ctx, const avd_picture* picture, uint8_t* small320, uint8_t* hash1024, int64_t* lap_sum, int64_t* lap_sumsq);
 int avd_analyze_pictures(avd_ctx* ctx, const avd_picture* clips, int nclips, avd_frame_record* records);
 int avd_analyze_pictures_async(avd_ctx* ctx, const avd_picture* clips, int nclips, avd_frame_record* records);
+
+/* Clips as LISTS of separately allocated frames -- avd_frame_list, avd_preprocess_frame_list, avd_analyze_frame_lists(_async): additive at
+ * ABI 3 like avd_picture.  The family is declared in a header of its own, which this one includes: nothing else is needed to use it. */
+#include "avd_frame_list.h"
 
 /* ViT-B/16 patch embedding on the matrix cores -- a BUILD-DEFINED EXTENSION.  The reference
  * contains no learned model (its per-frame "model" is the closed form of app/analyzers/video.py:54-56); BASELINE.json's
@@ -433,6 +438,10 @@ int avd_kernel_ms(avd_ctx* ctx, int kernel_id, float* ms);
  * any ingest launch.
  * "stage_bytes" int64[1], host state: the bytes the last ingest call of the context (avd_preprocess_*, avd_analyze_*) copied from host
  * memory into its staging buffer -- 0 for device input, the sum over the clips of a batch; an error before any ingest call.
+ * "stage_copies" int64[1], host state: the host-to-device staging copies that call issued, summed over its clips (a strided clip: its merged
+ * spans, 1 to 3; a frame list: one per merged span, n x planes for separately allocated frames); an error before any ingest call.
+ * "ingest_list" int32[2], host state: 1 if the last ingest launch took its frame bases from a table of plane pointers (avd_frame_list) and
+ * the frames that table held, else 0, 0; an error before any ingest launch.
  * "cnn_tap": what option "cnn_tap" made the last avd_cnn_forward copy aside -- 1: uint16[n][232][232][4] bf16 bits; 2 + i and 55: the activation as
  * plain NHWC bf16 bits, uint16[n][H][W][C]; 56: float[n][2048].  out_bytes must be exactly the tap's size.  An error, never stale bytes, when the last
  * forward was not tapped, when none of its launches has that output (the 3x3 of a fused block while "cnn_fuse" != 0), or when the size differs.
