@@ -13,9 +13,14 @@ from __future__ import annotations
 
 import os
 
+from avd_hip import _lib
 from avd_hip import analyzer as _analyzer
 from avd_hip import sources as _sources
 from avd_hip.timeline import records_to_result, sample_step
+
+# FrameSource.surface of the sources that yield one RGB-family array per frame -> the layout records_stream takes
+_RGB_SURFACES = {"rgb24": _lib.AVD_FMT_RGB24, "bgra32": _lib.AVD_FMT_BGRA32, "rgba32": _lib.AVD_FMT_RGBA32, "rgbp": _lib.AVD_FMT_RGBP}
+
 
 def _settings():
     """Environment knobs, read per call (a service may be reconfigured without a restart; tests set them per case):
@@ -45,13 +50,16 @@ def analyze(path: str, meta: dict):
         # stored pictures with a display rotation (src.width / src.height are the displayed picture's): the turn happens on the GPU too
         turn = {"rotate": int(src.rotate)} if getattr(src, "rotate", 0) else {}
         # full-range pictures (yuvj420p): converted with libswscale's full-range tables, on the GPU too; a source that yields BGR has none
-        if surface != "bgr" and getattr(src, "full_range", False):
+        if surface in ("nv12", "i420") and getattr(src, "full_range", False):
             turn["full_range"] = True
 
         def frames():
             for fr in src.sampled(step):
-                plane = fr if surface == "bgr" else fr[0]
-                seen.setdefault("npix", int(plane.shape[0]) * int(plane.shape[1]))
+                if surface == "rgbp":                        # channels first: [3,H,W]
+                    hw = fr.shape[1:3]
+                else:
+                    hw = (fr if surface == "bgr" or surface in _RGB_SURFACES else fr[0]).shape[:2]
+                seen.setdefault("npix", int(hw[0]) * int(hw[1]))
                 yield fr
 
         # one pooled context for the duration of the request (bounded pool: api.py:133 runs this on worker threads)
@@ -61,6 +69,8 @@ def analyze(path: str, meta: dict):
                 rec = fa.records_stream_nv12(frames(), **turn)
             elif surface == "i420":
                 rec = fa.records_stream_i420(frames(), **turn)
+            elif surface in _RGB_SURFACES:
+                rec = fa.records_stream(frames(), _RGB_SURFACES[surface])
             else:
                 rec = fa.records_stream(frames())
     finally:

@@ -8,6 +8,7 @@
   sources   runtime-probed frame sources (decoders are optional host plumbing)
   dist      frame-parallel sharding across ranks + record all-gather (RCCL / gloo)
 """
-from ._lib import AvdError, Context, RECORD_DTYPE, build, load  # noqa: F401
+from ._lib import AvdError, Context, Pixels, RECORD_DTYPE, build, load  # noqa: F401
+from ._lib import AVD_FMT_BGR24, AVD_FMT_BGRA32, AVD_FMT_I420, AVD_FMT_NV12, AVD_FMT_RGB24, AVD_FMT_RGBA32, AVD_FMT_RGBP  # noqa: F401
 from .analyzer import ClipsInFlight, ContextPool, FrameAnalyzer, analyze_frames, default_pool  # noqa: F401
 from .timeline import records_to_result, sample_step  # noqa: F401

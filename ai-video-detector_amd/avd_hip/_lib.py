@@ -66,6 +66,23 @@ class AvdClip(C.Structure):
 
 AVD_FMT_BGR24, AVD_FMT_NV12, AVD_FMT_I420 = 0, 1, 2
 AVD_FMT_FULL_RANGE = 0x100      # flag OR-ed into a 4:2:0 layout: the samples use 0 .. 255 (ffmpeg's yuvj420p)
+# what RGB producers hand over (include/avd.h): R,G,B interleaved; B,G,R,x and R,G,B,x with an ignored fourth byte; three planes R, G, B
+AVD_FMT_RGB24, AVD_FMT_BGRA32, AVD_FMT_RGBA32, AVD_FMT_RGBP = 0x10, 0x11, 0x12, 0x13
+_PACKED = {AVD_FMT_BGR24: 3, AVD_FMT_RGB24: 3, AVD_FMT_BGRA32: 4, AVD_FMT_RGBA32: 4}      # one interleaved plane: bytes per pixel
+_FMT_PLANES = {AVD_FMT_BGR24: 1, AVD_FMT_NV12: 2, AVD_FMT_I420: 3, AVD_FMT_RGB24: 1, AVD_FMT_BGRA32: 1, AVD_FMT_RGBA32: 1, AVD_FMT_RGBP: 3}
+
+
+class Pixels:
+    """A clip tagged with its layout, accepted wherever a clip is (preprocess_picture, analyze_pictures, analyze_pictures_async):
+    data uint8[N,H,W,3] for AVD_FMT_RGB24 (and AVD_FMT_BGR24), uint8[N,H,W,4] for AVD_FMT_BGRA32 / AVD_FMT_RGBA32, uint8[N,3,H,W] for
+    AVD_FMT_RGBP (channels first, R,G,B: what torchcodec and torchvision.io decode to); numpy or torch, host or device.  An untagged array
+    remains BGR, tuples remain NV12 / I420."""
+    __slots__ = ("data", "fmt")
+
+    def __init__(self, data, fmt: int):
+        if fmt not in _PACKED and fmt != AVD_FMT_RGBP:
+            raise ValueError(f"fmt must be AVD_FMT_BGR24, AVD_FMT_RGB24, AVD_FMT_BGRA32, AVD_FMT_RGBA32 or AVD_FMT_RGBP, got {fmt!r}")
+        self.data, self.fmt = data, fmt
 
 
 class AvdPicture(C.Structure):
@@ -365,8 +382,43 @@ class Context:
         ptr, mem, n, h, w, rs, fs, keep = self._frames_ptr(frames)
         return _Clip(AVD_FMT_BGR24, (ptr,), mem, int(n), int(h), int(w), (rs,), (fs,), keep)
 
+    def _pixels(self, px):
+        """A tagged clip (Pixels) -> _Clip.  A strided view goes through as it lies while its rows are dense (and, channels first, whatever the
+        distance between the planes: they share their row and frame strides by construction); anything else is copied once, as _frames_ptr does."""
+        fmt = px.fmt
+        if fmt == AVD_FMT_BGR24:
+            return self._bgr(px.data)
+        torch_in = _is_torch_tensor(px.data)
+        a = px.data if torch_in else np.asarray(px.data)
+        strides, ptr, dense = _TORCH_PLANE if torch_in else _NUMPY_PLANE
+        planar = fmt == AVD_FMT_RGBP
+        want = "uint8[N,3,H,W] (R,G,B planes)" if planar else f"uint8[N,H,W,{_PACKED[fmt]}]"
+        shape = tuple(int(d) for d in a.shape)
+        if len(shape) != 4 or shape[1 if planar else 3] != (3 if planar else _PACKED[fmt]) or str(a.dtype) not in ("torch.uint8", "uint8"):
+            raise ValueError(f"frames must be {want}, got {str(a.dtype)}{list(shape)}")
+        n, h, w = (shape[0], shape[2], shape[3]) if planar else shape[:3]
+
+        def lies_well(st):
+            if planar:
+                f, _, r, e = st
+                return e == 1 and r >= w and (n <= 1 or f >= r * (h - 1) + w)
+            f, r, p, e = st
+            return e == 1 and p == _PACKED[fmt] and r >= _PACKED[fmt] * w and (n <= 1 or f >= r * h)
+        if not lies_well(tuple(strides(a))):
+            a = dense(a)
+        st = tuple(int(v) for v in strides(a))
+        row = st[2] if planar else st[1]
+        frame = st[0] if n > 1 else h * row
+        planes = tuple(ptr(a) + c * st[1] for c in range(3)) if planar else (ptr(a),)
+        cuda = torch_in and a.is_cuda
+        if cuda:
+            self._after_torch_stream(a)
+        return _Clip(fmt, planes, AVD_MEM_DEVICE if cuda else AVD_MEM_HOST, n, h, w, (row,) * len(planes), (frame,) * len(planes), a)
+
     def _clip(self, clip):
-        """clip: a BGR frame stack uint8[N,H,W,3], an NV12 pair (y, uv) or an I420 triple (y, u, v); numpy or torch -> _Clip"""
+        """clip: a BGR frame stack uint8[N,H,W,3], an NV12 pair (y, uv), an I420 triple (y, u, v) or a tagged clip (Pixels); numpy or torch -> _Clip"""
+        if isinstance(clip, Pixels):
+            return self._pixels(clip)
         if not isinstance(clip, tuple):
             return self._bgr(clip)
         if len(clip) not in (2, 3):
@@ -434,7 +486,8 @@ class Context:
 
     # -- pictures by descriptor (include/avd.h: avd_picture): any format, with a display rotation -------------------------------------------
     def _picture(self, clip, rotate: int = 0, full_range: bool = False):
-        """clip: a BGR frame stack uint8[N,H,W,3], an NV12 pair (y, uv) or an I420 triple (y, u, v) of the STORED picture; numpy or torch.
+        """clip: a BGR frame stack uint8[N,H,W,3], an NV12 pair (y, uv) or an I420 triple (y, u, v) of the STORED picture, or a tagged clip
+        (Pixels: RGB, BGRA, RGBA, planar RGB); numpy or torch.
         full_range: AVD_FMT_FULL_RANGE is OR-ed into the format (the library refuses it on BGR).
         -> (AvdPicture, frame count, keepalive).  The binding's own checks (the rotation, U and V of equal strides, planes all numpy or all
         torch) are made before the library is touched."""
@@ -484,16 +537,26 @@ class Context:
 
     # -- clips as lists of separately allocated frames (include/avd_frame_list.h) ---------------------------------------------------------
     def _frame_list(self, frames, fmt: int, rotate: int = 0, full_range: bool = False):
-        """frames: a sequence of per-frame arrays -- BGR uint8[H,W,3], NV12 pairs (y uint8[H,W], uv uint8[H/2,W]) or I420 triples (y, u, v) -- all
+        """frames: a sequence of per-frame arrays -- BGR or RGB uint8[H,W,3], BGRA / RGBA uint8[H,W,4], planar RGB uint8[3,H,W], NV12 pairs
+        (y uint8[H,W], uv uint8[H/2,W]) or I420 triples (y, u, v) -- all
         numpy arrays (host) or all torch tensors on one device; every frame where it lies, nothing is gathered.  A plane's rows must be dense
         and all frames of the list share the row stride of each plane: anything else raises ValueError (there is no silent copy).
         -> (AvdFrameList, frame count, what the library reads: the pointer arrays during the call, the frames until it is drained)"""
         if isinstance(rotate, bool) or not isinstance(rotate, (int, np.integer)) or not 0 <= rotate <= 3:
             raise ValueError(f"rotate must be 0, 1, 2 or 3 quarter turns (clockwise, stored to displayed picture), got {rotate!r}")
-        if fmt not in (AVD_FMT_BGR24, AVD_FMT_NV12, AVD_FMT_I420):
-            raise ValueError(f"fmt must be AVD_FMT_BGR24, AVD_FMT_NV12 or AVD_FMT_I420, got {fmt!r}")
-        nplanes = {AVD_FMT_BGR24: 1, AVD_FMT_NV12: 2, AVD_FMT_I420: 3}[fmt]
-        frames = [(f,) if fmt == AVD_FMT_BGR24 else tuple(f) for f in frames]
+        if fmt not in _FMT_PLANES:
+            raise ValueError("fmt must be AVD_FMT_BGR24, AVD_FMT_NV12, AVD_FMT_I420, AVD_FMT_RGB24, AVD_FMT_BGRA32, AVD_FMT_RGBA32 or AVD_FMT_RGBP, "
+                             f"got {fmt!r}")
+        nplanes = _FMT_PLANES[fmt]
+        px = _PACKED.get(fmt, 1)                               # bytes per pixel of plane 0
+        if fmt == AVD_FMT_RGBP:                                # a [3,H,W] frame contributes its three channel views as planes
+            frames = list(frames)
+            for i, f in enumerate(frames):
+                if len(getattr(f, "shape", ())) != 3 or int(f.shape[0]) != 3:
+                    raise ValueError(f"frame {i}: an AVD_FMT_RGBP frame is uint8[3,H,W], got {list(getattr(f, 'shape', ()))}")
+            frames = [(f[0], f[1], f[2]) for f in frames]
+        else:
+            frames = [(f,) if fmt in _PACKED else tuple(f) for f in frames]
         if any(len(f) != nplanes for f in frames):
             raise ValueError(f"every frame of the list has {nplanes} plane(s)")
         L = AvdFrameList()
@@ -502,7 +565,7 @@ class Context:
         if not frames:                                         # an empty list has no picture to take a size from: any valid one
             L.h = L.w = HASH
             for p in range(nplanes):
-                L.row_stride[p] = HASH * 3 if fmt == AVD_FMT_BGR24 else (HASH // 2 if fmt == AVD_FMT_I420 and p else HASH)
+                L.row_stride[p] = HASH * px if p == 0 else (HASH // 2 if fmt == AVD_FMT_I420 else HASH)
             return L, 0, ()
         torch_in = [_is_torch_tensor(p) for f in frames for p in f]
         if any(torch_in) != all(torch_in):
@@ -521,10 +584,11 @@ class Context:
                 raise ValueError("the frames of a list are uint8 arrays")
             strides, ptr, _ = _NUMPY_PLANE
         h, w = int(frames[0][0].shape[0]), int(frames[0][0].shape[1])
-        shapes = {AVD_FMT_BGR24: [(h, w, 3)], AVD_FMT_NV12: [(h, w), (h // 2, w)], AVD_FMT_I420: [(h, w), (h // 2, w // 2), (h // 2, w // 2)]}[fmt]
+        shapes = {AVD_FMT_NV12: [(h, w), (h // 2, w)], AVD_FMT_I420: [(h, w), (h // 2, w // 2), (h // 2, w // 2)],
+                  AVD_FMT_RGBP: [(h, w)] * 3}.get(fmt, [(h, w, px)])
         arrays = []
         for p in range(nplanes):
-            dense = (3, 1) if fmt == AVD_FMT_BGR24 else (1,)
+            dense = (px, 1) if fmt in _PACKED else (1,)
             for i, f in enumerate(frames):
                 if tuple(f[p].shape) != shapes[p]:
                     raise ValueError(f"frame {i}: plane {p} must be uint8{list(shapes[p])}, got {list(f[p].shape)}")
@@ -584,6 +648,10 @@ class Context:
     def stage_copies(self) -> int:
         """Host-to-device staging copies the last ingest call of this context issued; avd_debug_fetch "stage_copies"."""
         return int(self.debug_fetch("stage_copies", (1,), np.int64)[0])
+
+    def ingest_format(self) -> int:
+        """The layout (AVD_FMT_*) of the last ingest launch of this context; avd_debug_fetch "ingest_format"."""
+        return int(self.debug_fetch("ingest_format", (1,), np.int32)[0])
 
     def ingest_rotate(self) -> int:
         """The rotation the last ingest launch of this context ran with; avd_debug_fetch "ingest_rotate"."""

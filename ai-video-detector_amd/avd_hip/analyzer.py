@@ -206,19 +206,26 @@ class FrameAnalyzer:
     # A chunk goes to the library as a LIST of frames (avd_frame_list): every frame is staged from where the decoder left it, nothing is
     # stacked first.  The carry frame between chunks is simply the first entry of the next list.
     def _flush_list(self, items, fmt, rotate=0, full_range=False) -> np.ndarray:
-        frames = [(np.asarray(it),) if fmt == _lib.AVD_FMT_BGR24 else tuple(np.asarray(p) for p in it) for it in items]
+        single = fmt in _lib._PACKED or fmt == _lib.AVD_FMT_RGBP          # one array per frame: interleaved [H,W,C], or channels first [3,H,W]
+        lead = 1 if fmt == _lib.AVD_FMT_RGBP else 0                       # axes in front of the rows
+        frames = [(np.asarray(it),) if single else tuple(np.asarray(p) for p in it) for it in items]
         # Frames go through as they lie -- row-padded decoder frames included -- while plane by plane their rows are dense and all frames share
         # one row stride, which is what a list takes.  Only a chunk that breaks that rule is copied (every plane to tight rows).
-        tail = (3, 1) if fmt == _lib.AVD_FMT_BGR24 else (1,)
-        agree = all(p.ndim == len(tail) + 1 and p.strides[1:] == tail and p.strides[0] == q.strides[0] for f in frames for p, q in zip(f, frames[0]))
+        tail = (_lib._PACKED[fmt], 1) if fmt in _lib._PACKED else (1,)
+        agree = all(p.ndim == lead + len(tail) + 1 and p.strides[lead + 1:] == tail and p.strides[lead] == q.strides[lead]
+                    for f in frames for p, q in zip(f, frames[0]))
         if not agree:
             frames = [tuple(np.ascontiguousarray(p) for p in f) for f in frames]
-        if fmt == _lib.AVD_FMT_BGR24:
+        if single:
             frames = [f[0] for f in frames]
         return self.ctx.analyze_frame_lists([(frames, fmt)], [rotate], [full_range])[0]
 
-    def records_stream(self, frames: Iterable[np.ndarray]) -> np.ndarray:
-        return self._stream(frames, lambda items: self._flush_list(items, _lib.AVD_FMT_BGR24))
+    def records_stream(self, frames: Iterable[np.ndarray], fmt: int = _lib.AVD_FMT_BGR24) -> np.ndarray:
+        """fmt: the layout of the frames -- AVD_FMT_BGR24 (default) or AVD_FMT_RGB24 uint8[H,W,3], AVD_FMT_BGRA32 / AVD_FMT_RGBA32 uint8[H,W,4],
+        AVD_FMT_RGBP uint8[3,H,W]."""
+        if fmt not in _lib._PACKED and fmt != _lib.AVD_FMT_RGBP:
+            raise ValueError(f"records_stream takes one array per frame: a packed layout or AVD_FMT_RGBP, got fmt {fmt!r}")
+        return self._stream(frames, lambda items: self._flush_list(items, fmt))
 
     # -- the same for decoder surfaces: an iterable of (y uint8[H,W], uv uint8[H/2,W]) pairs ----------------
     # rotate: quarter turns clockwise from the stored pictures to the displayed one (a container's display rotation; include/avd.h, avd_picture)

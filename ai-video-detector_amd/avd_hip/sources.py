@@ -31,7 +31,8 @@ import numpy as np
 
 
 class FrameSource:
-    # what sampled() yields: "bgr" = uint8[H,W,3]; "nv12" = (y uint8[H,W], uv uint8[H/2,W] interleaved U,V); "i420" = (y uint8[H,W], u uint8[H/2,W/2], v likewise)
+    # what sampled() yields: "bgr" = uint8[H,W,3]; "nv12" = (y uint8[H,W], uv uint8[H/2,W] interleaved U,V); "i420" = (y uint8[H,W], u uint8[H/2,W/2], v likewise);
+    # "rgb24" = uint8[H,W,3] R,G,B; "bgra32" / "rgba32" = uint8[H,W,4], fourth byte ignored; "rgbp" = uint8[3,H,W] R,G,B planes (channels first)
     surface: str = "bgr"
     fps: float = 0.0
     width: int = 0

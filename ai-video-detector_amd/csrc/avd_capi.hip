@@ -600,8 +600,8 @@ static int preprocess_clip(avd_ctx* ctx, const IngestClip& k, size_t at, const C
         ctx->stage_bytes += (int64_t)s.copied;
         ctx->stage_copies += s.nspans;
         d_in = dst + s.plane_off[0];
-        if (k.format != AVD_FMT_BGR24) d_uv = dst + s.plane_off[1];
-        if (k.format == AVD_FMT_I420) d_v = dst + s.plane_off[2];
+        if (k.planes() >= 2) d_uv = dst + s.plane_off[1];
+        if (k.planes() == 3) d_v = dst + s.plane_off[2];
     }
     return launch_preprocess(ctx, k, d_in, d_uv, d_v);
 }
@@ -918,6 +918,13 @@ static int64_t impl_debug_fetch(avd_ctx* ctx, const char* name, void* out, size_
         const int32_t r = ctx->ingest_range;
         std::memcpy(out, &r, sizeof r);
         return (int64_t)sizeof r;
+    }
+    if (std::strcmp(name, "ingest_format") == 0) {     // host state: the layout (AVD_FMT_*) of that launch
+        if (!ctx->ingest_plan_valid) { ctx->err = "ingest_format not recorded yet: no ingest kernel was launched on this context"; return AVD_ERR_ARG; }
+        if (out_bytes < sizeof(int32_t)) { ctx->err = "ingest_format is int32[1]"; return AVD_ERR_ARG; }
+        const int32_t r = ctx->ingest_format;
+        std::memcpy(out, &r, sizeof(r));
+        return (int64_t)sizeof(r);
     }
     if (std::strcmp(name, "ingest_list") == 0) {       // host state: did that launch take its frame bases from a table, and of how many frames
         if (!ctx->ingest_plan_valid) { ctx->err = "ingest_list not recorded yet: no ingest kernel was launched on this context"; return AVD_ERR_ARG; }

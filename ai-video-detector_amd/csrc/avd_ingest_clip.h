@@ -12,20 +12,28 @@
 //   AVD_FMT_BGR24  data = the interleaved frames (row_stride / frame_stride)
 //   AVD_FMT_NV12   data = the Y plane, uv = the interleaved chroma plane (uv_row_stride / uv_frame_stride)
 //   AVD_FMT_I420   data = Y, uv = the U plane, v = the V plane; the uv strides hold for both chroma planes
+//   AVD_FMT_RGB24 / _BGRA32 / _RGBA32   data = the interleaved frames, 3 / 4 / 4 bytes per pixel, as BGR24
+//   AVD_FMT_RGBP   data = R, uv = the G plane, v = the B plane, each h x w; row_stride == uv_row_stride and frame_stride == uv_frame_stride
 // rotate: quarter turns clockwise from the stored picture (h, w, the planes and strides: always the STORED one) to the displayed picture, whose
 // size the geometry tables, the band plan and every result follow (4:2:0 clips only).
 // full_range: AVD_FMT_FULL_RANGE of the descriptor, taken out of `format`, which stays the plain layout.
 // list: the frames do not lie at a fixed distance from each other but where a table says -- list[p][f] = plane p of frame f (avd_frame_list;
 // p as data, uv, v).  The arrays are the CALLER's host memory, read while the call runs and never kept.  data / uv / v and the frame strides
 // of such a clip are unused (null, 0); everything else means what it means for a strided clip.
-// A clip is made by bgr_clip / nv12_clip / i420_clip (the entry points that name their format), from_public (avd_clip), from_picture
+// A clip is made by bgr_clip / nv12_clip / i420_clip (the entry points that name their format), rgb_clip (descriptors only), from_public (avd_clip), from_picture
 // (avd_picture) or from_frame_list (avd_frame_list), and by nothing else.
 struct IngestClip {
     int format;
     const uint8_t *data, *uv, *v;
     const uint8_t* const* list[3];
     bool is_list;         // from_frame_list made it (the arrays may still be null: check_clip refuses that)
-    int planes() const { return format == AVD_FMT_BGR24 ? 1 : (format == AVD_FMT_I420 ? 3 : 2); }
+    int planes() const { return format == AVD_FMT_NV12 ? 2 : (format == AVD_FMT_I420 || format == AVD_FMT_RGBP ? 3 : 1); }
+    bool is_420() const { return format == AVD_FMT_NV12 || format == AVD_FMT_I420; }
+    bool is_rgb() const { return format >= AVD_FMT_RGB24 && format <= AVD_FMT_RGBP; }      // the four layouts of RGB producers
+    int px_bytes() const { return format == AVD_FMT_BGR24 || format == AVD_FMT_RGB24 ? 3 : (format == AVD_FMT_BGRA32 || format == AVD_FMT_RGBA32 ? 4 : 1); }      // of plane 0
+    // planes 1 and 2: the chroma planes of 4:2:0 (h/2 rows of w bytes interleaved, w/2 planar), the G and B planes of RGBP (the size of plane 0)
+    int sub_rows() const { return is_420() ? h / 2 : h; }
+    int sub_row_bytes() const { return format == AVD_FMT_I420 ? w / 2 : w; }
     int mem, n, h, w;
     int64_t row_stride, frame_stride, uv_row_stride, uv_frame_stride;
     int rotate;
@@ -64,6 +72,20 @@ inline IngestClip i420_clip(const uint8_t* y, const uint8_t* u, const uint8_t* v
     return k;
 }
 
+// the four layouts of RGB producers: packed (g, b null) or planar (AVD_FMT_RGBP: r, g, b share row / frame)
+inline IngestClip rgb_clip(int format, const uint8_t* r, const uint8_t* g, const uint8_t* b, int mem, int n, int h, int w, int64_t row, int64_t frame)
+{
+    IngestClip k = bgr_clip(r, mem, n, h, w, row, frame);
+    k.format = format;
+    if (format == AVD_FMT_RGBP) { k.uv = g; k.v = b; k.uv_row_stride = row; k.uv_frame_stride = frame; }
+    return k;
+}
+
+inline bool known_layout(int layout)
+{
+    return layout == AVD_FMT_BGR24 || layout == AVD_FMT_NV12 || layout == AVD_FMT_I420 || (layout >= AVD_FMT_RGB24 && layout <= AVD_FMT_RGBP);
+}
+
 // avd_clip is frozen at ABI 3 and has no format field: a clip with uv set is NV12, any other is BGR.  The ONE place where a format is inferred
 // from a pointer.
 inline IngestClip from_public(const avd_clip& c)
@@ -78,14 +100,22 @@ inline Refusal from_picture(const avd_picture& p, IngestClip& k)
 {
     if (p.struct_size != sizeof(avd_picture)) return {AVD_ERR_ARG, "avd_picture.struct_size is not sizeof(avd_picture)"};
     const int layout = p.format & 0xFF, full_range = (p.format & AVD_FMT_FULL_RANGE) != 0;
-    if ((p.format & ~(0xFF | AVD_FMT_FULL_RANGE)) || (layout != AVD_FMT_BGR24 && layout != AVD_FMT_NV12 && layout != AVD_FMT_I420))
+    if ((p.format & ~(0xFF | AVD_FMT_FULL_RANGE)) || !known_layout(layout))
         return {AVD_ERR_ARG, "bad avd_picture.format"};
+    const bool rgb = layout >= AVD_FMT_RGB24 && layout <= AVD_FMT_RGBP;
     if (full_range && layout == AVD_FMT_BGR24) return {AVD_ERR_ARG, "AVD_FMT_FULL_RANGE describes 4:2:0 samples: a BGR picture has no range"};
+    if (full_range && rgb) return {AVD_ERR_ARG, "AVD_FMT_FULL_RANGE describes 4:2:0 samples: an RGB picture has no range"};
     if (p.rotate < 0 || p.rotate > 3) return {AVD_ERR_ARG, "avd_picture.rotate must be 0 .. 3 quarter turns"};
     if (p.reserved != 0) return {AVD_ERR_ARG, "avd_picture.reserved must be 0"};
     if (layout == AVD_FMT_BGR24) {
         if (p.rotate) return {AVD_ERR_UNSUPPORTED, "a turned BGR picture is not on the path: cv2 hands BGR over already rotated"};
         k = bgr_clip(p.plane[0], p.mem, p.n, p.h, p.w, p.row_stride[0], p.frame_stride[0]);
+    } else if (rgb) {
+        if (p.rotate) return {AVD_ERR_UNSUPPORTED, "a turned RGB picture is not on the path: producers of RGB hand it over already rotated"};
+        if (layout == AVD_FMT_RGBP && (p.row_stride[0] != p.row_stride[1] || p.row_stride[1] != p.row_stride[2] || p.frame_stride[0] != p.frame_stride[1] ||
+                                       p.frame_stride[1] != p.frame_stride[2]))
+            return {AVD_ERR_ARG, "the R, G and B planes of an RGBP picture share their strides"};
+        k = rgb_clip(layout, p.plane[0], p.plane[1], p.plane[2], p.mem, p.n, p.h, p.w, p.row_stride[0], p.frame_stride[0]);
     } else if (layout == AVD_FMT_NV12) {
         k = nv12_clip(p.plane[0], p.plane[1], p.mem, p.n, p.h, p.w, p.row_stride[0], p.row_stride[1], p.frame_stride[0], p.frame_stride[1]);
     } else {
@@ -103,14 +133,21 @@ inline Refusal from_frame_list(const avd_frame_list& p, IngestClip& k)
 {
     if (p.struct_size != sizeof(avd_frame_list)) return {AVD_ERR_ARG, "avd_frame_list.struct_size is not sizeof(avd_frame_list)"};
     const int layout = p.format & 0xFF, full_range = (p.format & AVD_FMT_FULL_RANGE) != 0;
-    if ((p.format & ~(0xFF | AVD_FMT_FULL_RANGE)) || (layout != AVD_FMT_BGR24 && layout != AVD_FMT_NV12 && layout != AVD_FMT_I420))
+    if ((p.format & ~(0xFF | AVD_FMT_FULL_RANGE)) || !known_layout(layout))
         return {AVD_ERR_ARG, "bad avd_frame_list.format"};
+    const bool rgb = layout >= AVD_FMT_RGB24 && layout <= AVD_FMT_RGBP;
     if (full_range && layout == AVD_FMT_BGR24) return {AVD_ERR_ARG, "AVD_FMT_FULL_RANGE describes 4:2:0 samples: a BGR picture has no range"};
+    if (full_range && rgb) return {AVD_ERR_ARG, "AVD_FMT_FULL_RANGE describes 4:2:0 samples: an RGB picture has no range"};
     if (p.rotate < 0 || p.rotate > 3) return {AVD_ERR_ARG, "avd_frame_list.rotate must be 0 .. 3 quarter turns"};
     if (p.reserved != 0) return {AVD_ERR_ARG, "avd_frame_list.reserved must be 0"};
     if (layout == AVD_FMT_BGR24) {
         if (p.rotate) return {AVD_ERR_UNSUPPORTED, "a turned BGR picture is not on the path: cv2 hands BGR over already rotated"};
         k = bgr_clip(nullptr, p.mem, p.n, p.h, p.w, p.row_stride[0], 0);
+    } else if (rgb) {
+        if (p.rotate) return {AVD_ERR_UNSUPPORTED, "a turned RGB picture is not on the path: producers of RGB hand it over already rotated"};
+        if (layout == AVD_FMT_RGBP && (p.row_stride[0] != p.row_stride[1] || p.row_stride[1] != p.row_stride[2]))
+            return {AVD_ERR_ARG, "the R, G and B planes of an RGBP picture share their strides"};
+        k = rgb_clip(layout, nullptr, nullptr, nullptr, p.mem, p.n, p.h, p.w, p.row_stride[0], 0);
     } else if (layout == AVD_FMT_NV12) {
         k = nv12_clip(nullptr, nullptr, p.mem, p.n, p.h, p.w, p.row_stride[0], p.row_stride[1], 0, 0);
     } else {
@@ -130,11 +167,12 @@ inline Refusal from_frame_list(const avd_frame_list& p, IngestClip& k)
 // has no frame strides to check: its frames may lie anywhere, in any order, and may repeat).
 inline Refusal check_clip(const IngestClip& k)
 {
-    const bool bgr = k.format == AVD_FMT_BGR24, planar = k.format == AVD_FMT_I420;
+    // bgr: ONE packed plane (BGR24 and the packed RGB layouts: their refusals read alike); planar: I420; rgbp: three full-size planes
+    const bool bgr = k.planes() == 1, planar = k.format == AVD_FMT_I420, rgbp = k.format == AVD_FMT_RGBP;
     const int n = k.n, h = k.h, w = k.w;
     if (k.mem != AVD_MEM_HOST && k.mem != AVD_MEM_DEVICE) return {AVD_ERR_ARG, "mem must be AVD_MEM_HOST or AVD_MEM_DEVICE"};
     if (n < 0 || h <= 0 || w <= 0 || h > 16384 || w > 16384) return {AVD_ERR_ARG, "bad frame geometry"};
-    if (!bgr && ((h | w) & 1)) return {AVD_ERR_UNSUPPORTED, planar ? "I420 needs even width and height" : "NV12 needs even width and height"};
+    if (k.is_420() && ((h | w) & 1)) return {AVD_ERR_UNSUPPORTED, planar ? "I420 needs even width and height" : "NV12 needs even width and height"};
     if (h < AVD_HASH || w < AVD_HASH) return {AVD_ERR_UNSUPPORTED, "frame smaller than 32x32: INTER_AREA upscaling is not on the path"};
     if (k.is_list) {
         if (n > 0) {
@@ -144,13 +182,15 @@ inline Refusal check_clip(const IngestClip& k)
                 for (int f = 0; f < n; f++)
                     if (!k.list[p][f]) return {AVD_ERR_ARG, "null plane pointer in a frame list"};
         }
-    } else if (n > 0 && (!k.data || (!bgr && !k.uv) || (planar && !k.v)))
-        return {AVD_ERR_ARG, bgr ? "null frame pointer" : (planar ? "null I420 plane pointer" : "null plane pointer")};
-    const int64_t row = bgr ? (int64_t)w * 3 : w, crow = planar ? w / 2 : w;      // bytes of a luma (BGR: frame) row and of a chroma row
+    } else if (n > 0 && (!k.data || (!bgr && !k.uv) || (k.planes() == 3 && !k.v)))
+        return {AVD_ERR_ARG, bgr ? "null frame pointer" : (planar ? "null I420 plane pointer" : (rgbp ? "null RGBP plane pointer" : "null plane pointer"))};
+    const int64_t row = (int64_t)w * k.px_bytes(), crow = k.sub_row_bytes();      // bytes of a row of plane 0 and of the planes behind it
     const bool strided = !k.is_list && n > 1;
     bool small = k.row_stride < row || (strided && k.frame_stride < k.row_stride * (h - 1) + row);
-    if (!bgr) small = small || k.uv_row_stride < crow || (strided && k.uv_frame_stride < k.uv_row_stride * (h / 2 - 1) + crow);
-    if (small) return {AVD_ERR_ARG, bgr ? "strides smaller than the frame" : (planar ? "strides smaller than the I420 planes" : "strides smaller than the planes")};
+    if (!bgr) small = small || k.uv_row_stride < crow || (strided && k.uv_frame_stride < k.uv_row_stride * (k.sub_rows() - 1) + crow);
+    if (small)
+        return {AVD_ERR_ARG, bgr ? "strides smaller than the frame"
+                                 : (planar ? "strides smaller than the I420 planes" : (rgbp ? "strides smaller than the RGBP planes" : "strides smaller than the planes"))};
     return {0, nullptr};
 }
 
@@ -163,7 +203,7 @@ inline size_t plane_span(int64_t frame_stride, int n, int64_t row_stride, int ro
 
 inline size_t round256(size_t v) { return (v + 255) / 256 * 256; }
 
-// Where a HOST clip lands in the staging buffer: BGR as one span; NV12 as the Y span with the chroma span on the next 256-byte boundary
+// Where a HOST clip lands in the staging buffer: BGR and the packed RGB layouts as one span; RGBP as I420 (a dense [N,3,H,W] stack is one span); NV12 as the Y span with the chroma span on the next 256-byte boundary
 // behind it.  The three planes of I420 usually come out of ONE buffer per clip (a y4m map, a rawvideo pipe: Y, U, V of a frame adjacent), where
 // the per-plane spans overlap almost entirely: spans that overlap or touch are merged and copied once, so no host byte crosses the link twice, and
 // a plane sits at its own offset inside the merged span; separately allocated planes stay three spans.  `total` (a multiple of 256) is what
@@ -175,11 +215,11 @@ inline ClipStage clip_stage(const IngestClip& c)
 {
     ClipStage s{};
     if (c.mem != AVD_MEM_HOST || c.n <= 0 || c.is_list) return s;      // a list has its own plan: list_stage
-    const bool bgr = c.format == AVD_FMT_BGR24, planar = c.format == AVD_FMT_I420;
+    const int planes = c.planes();
+    const bool bgr = planes == 1, planar = planes == 3;      // planar: I420 and RGBP, whose three planes usually come out of one buffer
     const uint8_t* src[3] = {c.data, c.uv, c.v};
-    const int planes = bgr ? 1 : (planar ? 3 : 2);
-    size_t len[3] = {plane_span(c.frame_stride, c.n, c.row_stride, c.h, (size_t)c.w * (bgr ? 3 : 1)), 0, 0};
-    if (!bgr) len[1] = len[2] = plane_span(c.uv_frame_stride, c.n, c.uv_row_stride, c.h / 2, (size_t)(planar ? c.w / 2 : c.w));
+    size_t len[3] = {plane_span(c.frame_stride, c.n, c.row_stride, c.h, (size_t)c.w * c.px_bytes()), 0, 0};
+    if (!bgr) len[1] = len[2] = plane_span(c.uv_frame_stride, c.n, c.uv_row_stride, c.sub_rows(), (size_t)c.sub_row_bytes());
     int order[3] = {0, 1, 2};
     if (planar) std::sort(order, order + 3, [&](int a, int b) { return (uintptr_t)src[a] < (uintptr_t)src[b]; });
     for (int i = 0; i < planes; i++) {
@@ -209,9 +249,8 @@ struct ListStage { std::vector<StageSpan> span; std::vector<size_t> plane_off; s
 // bytes of plane p of one frame, first to last
 inline size_t list_plane_bytes(const IngestClip& c, int p)
 {
-    const bool bgr = c.format == AVD_FMT_BGR24, planar = c.format == AVD_FMT_I420;
-    if (p == 0) return plane_span(0, 1, c.row_stride, c.h, (size_t)c.w * (bgr ? 3 : 1));
-    return plane_span(0, 1, c.uv_row_stride, c.h / 2, (size_t)(planar ? c.w / 2 : c.w));
+    if (p == 0) return plane_span(0, 1, c.row_stride, c.h, (size_t)c.w * c.px_bytes());
+    return plane_span(0, 1, c.uv_row_stride, c.sub_rows(), (size_t)c.sub_row_bytes());
 }
 
 inline ListStage list_stage(const IngestClip& c)
@@ -242,12 +281,12 @@ inline ListStage list_stage(const IngestClip& c)
 }
 
 // May a list run the vector fills?  Their rule (launch_preprocess: w % 16 == 0, 16-byte aligned planes and row strides, 8 bytes for the
-// chroma planes of I420) must hold for EVERY frame; one frame that fails sends the whole list through the scalar fill, with the same results.
+// chroma planes of I420; 16 for every plane of RGBP and for the packed RGB layouts) must hold for EVERY frame; one frame that fails sends the whole list through the scalar fill, with the same results.
 // tab[p * n + f]: where the kernel will find plane p of frame f (device addresses: the caller's planes, or their places in the staging buffer).
 inline bool list_vec_eligible(const IngestClip& c, const uint8_t* const* tab)
 {
-    const bool bgr = c.format == AVD_FMT_BGR24, planar = c.format == AVD_FMT_I420;
-    const int ca = planar ? 8 : 16;
+    const bool bgr = c.planes() == 1;
+    const int ca = c.format == AVD_FMT_I420 ? 8 : 16;
     if (c.w % 16 != 0 || c.row_stride % 16 != 0 || (!bgr && c.uv_row_stride % ca != 0)) return false;
     for (int p = 0; p < c.planes(); p++)
         for (int f = 0; f < c.n; f++)

@@ -66,6 +66,10 @@ struct Nv12Params {
     YuvConsts k;
 };
 
+struct RgbpParams {
+    const uint8_t *g, *b;              // the G and B planes of frame 0 (the R plane is the kernel's frame pointer); all three share PreParams' strides
+};
+
 struct I420Params {
     const uint8_t *u, *v;              // planar U and V of frame 0, uint8[h/2][w/2] each (YV12: the caller passes them exchanged)
     int64_t c_row_stride, c_frame_stride;   // shared by the two planes
@@ -101,7 +105,7 @@ struct BandPlan { int rows_per_band, pitch, ni; };
 BandPlan band_plan(int w);
 // What launch_preprocess ran last on a context: read by tests through avd_debug_fetch "ingest_plan" (eight int32 in this order).
 enum IngestKernel { kIngestBgrScalar = 0, kIngestBgrVec16, kIngestBgrStaged, kIngestNv12Scalar, kIngestNv12Tables, kIngestI420Scalar, kIngestI420Tables,
-                    kIngestNv12Strip, kIngestI420Strip };
+                    kIngestNv12Strip, kIngestI420Strip, kIngestPx32Scalar, kIngestPx32Vec16, kIngestRgbpScalar, kIngestRgbpVec16, kIngestRgbpStaged };
 struct IngestPlan { int h, w, rows_per_band, nbands, pitch, ni, lds_bytes, kernel; };
 static_assert(sizeof(IngestPlan) == 8 * sizeof(int), "avd_debug_fetch hands the struct out as int32[8]");
 // Kernel shape of a CNN convolution launch (avd_cnn.hip), as avd_debug_fetch "cnn_plan" hands it out per convolution: kCnnFolded = no launch
@@ -254,6 +258,7 @@ struct avd_ctx {
     IngestPlan ingest_plan{};        // the last launch_preprocess of this context (debug buffer "ingest_plan")
     int ingest_plan_valid = 0;       // 0 until the first ingest launch
     int ingest_rotate = 0;           // the rotation that launch ran with (debug buffer "ingest_rotate")
+    int ingest_format = 0;           // the layout (AVD_FMT_*) of that launch (debug buffer "ingest_format")
     int ingest_range = 0;            // 1: that launch ran with full-range conversion constants (debug buffer "ingest_range")
     int ingest_list[2] = {0, 0};     // that launch took its frame bases from a table of plane pointers / the frames the table held (debug buffer "ingest_list")
     int64_t stage_copies = -1;       // host-to-device staging copies of the last ingest call (debug buffer "stage_copies"); -1 until the first one
@@ -334,7 +339,8 @@ int avd_ws_reserve(avd_ctx* ctx, int n, int h, int w);                 // both, 
 int avd_ws_reserve_fb(avd_ctx* ctx, int n);
 // the clip's frames, resident at d_in (BGR) or d_in / d_uv (NV12: Y rows at d_in + f*frame_stride + y*row_stride, chroma rows at
 // d_uv + f*uv_frame_stride + (y/2)*uv_row_stride) or d_in / d_uv / d_v (I420: d_uv is the U plane, both chroma planes with the uv strides),
-// into the clip's slice of the per-frame buffers; which of the three it is says clip.format; the clip's geometry is current
+// or d_in alone (the packed RGB layouts, as BGR with 3 or 4 bytes per pixel) or d_in / d_uv / d_v (RGBP: R, G, B, all with the clip's row_stride / frame_stride),
+// into the clip's slice of the per-frame buffers; which it is says clip.format; the clip's geometry is current
 // list (null: strided): the frames come from a device table of plane pointers (avd_frame_list) -- d_in / d_uv / d_v are then the addresses of the
 // table's per-plane arrays, n entries each, and the clip's frame strides are unused
 struct FrameTable { bool aligned; };      // aligned: every frame of the list allows the 16-byte fills (list_vec_eligible)

@@ -1,6 +1,6 @@
-// avd_preprocess.hip -- fused full-resolution pass over decoded BGR frames (gfx950).
+// avd_preprocess.hip -- fused full-resolution pass over decoded frames (gfx950): BGR, RGB in four layouts, NV12, I420.
 //
-// One read of each BGR frame from HBM produces everything the reference derives
+// One read of each frame from HBM produces everything the reference derives
 // from full-resolution pixels (reference app/analyzers/video.py):
 //   :5,:43,:51  cv2.cvtColor(BGR2GRAY) x3   -> gray lives only in LDS
 //   :6          cv2.resize(32x32, INTER_AREA) -> per-row partial sums (float, cv2's order)
@@ -59,6 +59,13 @@ __device__ __forceinline__ int reflect101(int p, int len)
 // quad are packed by two v_perm picking byte 1 of each.
 constexpr unsigned kHi2 = 28u | (150u << 8) | (76u << 16);
 constexpr unsigned kLo = 151u | (35u << 8) | (70u << 16);
+// The same for pixels stored R, G, B (AVD_FMT_RGB24, AVD_FMT_RGBA32, the pixel words gathered from AVD_FMT_RGBP): bytes 0 and 2 exchanged.  The
+// channel order is a constant of the fill -- the template parameter RGB of everything below -- and nothing else knows it.  Byte 3 of either
+// constant is zero: a 32-bit pixel's fourth byte (AVD_FMT_BGRA32 / _RGBA32) drops out of both dot products.
+constexpr unsigned kHi2Rgb = 76u | (150u << 8) | (28u << 16);
+constexpr unsigned kLoRgb = 70u | (35u << 8) | (151u << 16);
+template <bool RGB> constexpr unsigned hi2_of() { return RGB ? kHi2Rgb : kHi2; }
+template <bool RGB> constexpr unsigned lo_of() { return RGB ? kLoRgb : kLo; }
 
 __device__ __forceinline__ unsigned gray_v(unsigned px, unsigned hi2, unsigned lo)
 {
@@ -66,24 +73,57 @@ __device__ __forceinline__ unsigned gray_v(unsigned px, unsigned hi2, unsigned l
     return __builtin_amdgcn_udot4(px, hi2, l >> 7, false);       // gray in bits 8..15
 }
 
-// 12 bytes (4 BGR pixels) -> 4 gray bytes packed little-endian
+// 12 bytes (4 BGR or RGB pixels) -> 4 gray bytes packed little-endian
+template <bool RGB>
 __device__ __forceinline__ unsigned gray4(unsigned w0, unsigned w1, unsigned w2)
 {
+    constexpr unsigned hi2 = hi2_of<RGB>(), lo = lo_of<RGB>();
     const unsigned p1 = __builtin_amdgcn_alignbyte(w1, w0, 3);
     const unsigned p2 = __builtin_amdgcn_alignbyte(w2, w1, 2);
-    const unsigned v0 = gray_v(w0, kHi2, kLo);
-    const unsigned v1 = gray_v(p1, kHi2, kLo);
-    const unsigned v2 = gray_v(p2, kHi2, kLo);
-    const unsigned v3 = gray_v(w2, kHi2 << 8, kLo << 8);
+    const unsigned v0 = gray_v(w0, hi2, lo);
+    const unsigned v1 = gray_v(p1, hi2, lo);
+    const unsigned v2 = gray_v(p2, hi2, lo);
+    const unsigned v3 = gray_v(w2, hi2 << 8, lo << 8);
     // v_perm_b32(hi, lo, sel): byte k of the result = byte sel[k] of {hi:lo} (0..3 = lo, 4..7 = hi)
     const unsigned g01 = __builtin_amdgcn_perm(v1, v0, 0x0c0c0501u);     // [v0.b1, v1.b1, 0, 0]
     const unsigned g23 = __builtin_amdgcn_perm(v3, v2, 0x05010c0cu);     // [0, 0, v2.b1, v3.b1]
     return g01 | g23;
 }
 
+template <bool RGB>
 __device__ __forceinline__ unsigned gray1(const uint8_t* p)
 {
-    return (p[0] * 3735u + p[1] * 19235u + p[2] * 9798u + (1u << 14)) >> 15;
+    return (p[RGB ? 2 : 0] * 3735u + p[1] * 19235u + p[RGB ? 0 : 2] * 9798u + (1u << 14)) >> 15;
+}
+
+// four pixels of one dword each (channel c in byte c; byte 3 anything: its coefficient is zero) -> 4 gray bytes.  No alignbyte: the pixels
+// arrive aligned.  8 dot4, 4 shifts, 2 perm, 1 or = 15 vector instructions per 4 pixels (gray4: 17).
+template <bool RGB>
+__device__ __forceinline__ unsigned gray4_px(unsigned p0, unsigned p1, unsigned p2, unsigned p3)
+{
+    constexpr unsigned hi2 = hi2_of<RGB>(), lo = lo_of<RGB>();
+    const unsigned v0 = gray_v(p0, hi2, lo);
+    const unsigned v1 = gray_v(p1, hi2, lo);
+    const unsigned v2 = gray_v(p2, hi2, lo);
+    const unsigned v3 = gray_v(p3, hi2, lo);
+    const unsigned g01 = __builtin_amdgcn_perm(v1, v0, 0x0c0c0501u);     // [v0.b1, v1.b1, 0, 0]
+    const unsigned g23 = __builtin_amdgcn_perm(v3, v2, 0x05010c0cu);     // [0, 0, v2.b1, v3.b1]
+    return g01 | g23;
+}
+
+// 4 R, 4 G and 4 B bytes of the same four pixels (AVD_FMT_RGBP) -> 4 gray bytes.  The byte lanes are gathered into pixel words [R, G, B, 0]
+// by v_perm: two interleave R with G ([r0 g0 r1 g1], [r2 g2 r3 g3]), four put a B byte behind each pair -- 6 perm + gray4_px's 15 = 21
+// vector instructions per 4 pixels.  (Per-plane byte extraction with v_mad_u32_u24 is 12 extractions + 12 multiply-adds + 4 shifts + 3 to
+// pack = 31: DESIGN.md section 4.1.)
+__device__ __forceinline__ unsigned gray4_planar(unsigned r, unsigned g, unsigned b)
+{
+    const unsigned rg01 = __builtin_amdgcn_perm(g, r, 0x05010400u);      // [r0, g0, r1, g1]
+    const unsigned rg23 = __builtin_amdgcn_perm(g, r, 0x07030602u);      // [r2, g2, r3, g3]
+    const unsigned p0 = __builtin_amdgcn_perm(b, rg01, 0x0c040100u);     // [r0, g0, b0, 0]
+    const unsigned p1 = __builtin_amdgcn_perm(b, rg01, 0x0c050302u);     // [r1, g1, b1, 0]
+    const unsigned p2 = __builtin_amdgcn_perm(b, rg23, 0x0c060100u);
+    const unsigned p3 = __builtin_amdgcn_perm(b, rg23, 0x0c070302u);
+    return gray4_px<true>(p0, p1, p2, p3);
 }
 
 template <typename T>
@@ -133,14 +173,15 @@ __device__ __forceinline__ int reflect_once(int p, int len)      // valid for -l
     return p >= len ? 2 * len - 2 - p : p;
 }
 
-// 16 BGR pixels (three 16-byte words) -> 16 gray bytes
+// 16 BGR or RGB pixels (three 16-byte words) -> 16 gray bytes
+template <bool RGB>
 __device__ __forceinline__ uint4 gray16(const uint4& a, const uint4& b, const uint4& d)
 {
     uint4 g;
-    g.x = gray4(a.x, a.y, a.z);
-    g.y = gray4(a.w, b.x, b.y);
-    g.z = gray4(b.z, b.w, d.x);
-    g.w = gray4(d.y, d.z, d.w);
+    g.x = gray4<RGB>(a.x, a.y, a.z);
+    g.y = gray4<RGB>(a.w, b.x, b.y);
+    g.z = gray4<RGB>(b.z, b.w, d.x);
+    g.w = gray4<RGB>(d.y, d.z, d.w);
     return g;
 }
 
@@ -415,18 +456,21 @@ __device__ __forceinline__ void fill_column_halo(uint8_t* tile, int trows, int p
 
 // ---- the fills: gray rows [r0-1, r0+rows] of the band into the tile.  They are all the kernels differ in. ----
 
+// The BGR fills serve AVD_FMT_RGB24 as well (RGB: the coefficient constants with bytes 0 and 2 exchanged, the same instruction stream).
 // BGR, any geometry / alignment: one byte-wise pixel per work item
+template <bool RGB>
 __device__ __forceinline__ void fill_bgr_scalar(uint8_t* tile, const uint8_t* frame, const PreParams& P, const Band& b, int tid)
 {
     const int w = P.w, pitch = P.pitch;
     for (int it = tid; it < b.trows * w; it += kThreads) {
         const int tr = it / w, x = it - tr * w;
         const int y = reflect_once(b.r0 - 1 + tr, P.h);
-        tile[tr * pitch + kPad + x] = (uint8_t)gray1(frame + (int64_t)y * P.row_stride + x * 3);
+        tile[tr * pitch + kPad + x] = (uint8_t)gray1<RGB>(frame + (int64_t)y * P.row_stride + x * 3);
     }
 }
 
 // BGR, 16-byte aligned rows of w % 16 == 0 pixels: one 16-pixel chunk (3 x 16 B) per work item
+template <bool RGB>
 __device__ __forceinline__ void fill_bgr_vec16(uint8_t* tile, const uint8_t* frame, const PreParams& P, const Band& b, int tid)
 {
     const int chunks = P.w >> 4, pitch = P.pitch;
@@ -434,7 +478,7 @@ __device__ __forceinline__ void fill_bgr_vec16(uint8_t* tile, const uint8_t* fra
         const int tr = it / chunks, c = it - tr * chunks;
         const int y = reflect_once(b.r0 - 1 + tr, P.h);
         const uint4* src = reinterpret_cast<const uint4*>(frame + (int64_t)y * P.row_stride + c * 48);
-        *reinterpret_cast<uint4*>(tile + tr * pitch + kPad + c * 16) = gray16(src[0], src[1], src[2]);
+        *reinterpret_cast<uint4*>(tile + tr * pitch + kPad + c * 16) = gray16<RGB>(src[0], src[1], src[2]);
     }
 }
 
@@ -442,7 +486,7 @@ __device__ __forceinline__ void fill_bgr_vec16(uint8_t* tile, const uint8_t* fra
 // row loads (3 x 16 B each) before the first conversion, so a workgroup has its whole band in flight at once; conversions
 // start as the words arrive (vmcnt counts down in issue order).  The lanes that convert the first / last chunk also write
 // the reflected column halo bytes, which saves a barrier.
-template <int NI>
+template <int NI, bool RGB>
 __device__ __forceinline__ void fill_bgr_staged(uint8_t* tile, const uint8_t* frame, const PreParams& P, const Band& b, int tid)
 {
     const int pitch = P.pitch;
@@ -463,7 +507,7 @@ __device__ __forceinline__ void fill_bgr_staged(uint8_t* tile, const uint8_t* fr
 #pragma unroll
         for (int k = 0; k < NI; k++) {
             const int t = min(rsub + k * rpp, b.trows - 1);
-            const uint4 g = gray16(q[k][0], q[k][1], q[k][2]);
+            const uint4 g = gray16<RGB>(q[k][0], q[k][1], q[k][2]);
             uint8_t* d = dst + t * pitch;
             *reinterpret_cast<uint4*>(d) = g;
             if (c == 0) d[-1] = (uint8_t)(g.x >> 8);                 // pixel -1 := pixel 1
@@ -472,8 +516,101 @@ __device__ __forceinline__ void fill_bgr_staged(uint8_t* tile, const uint8_t* fr
     }
 }
 
-// Generic kernel: one workgroup per band, any geometry / alignment (scalar loads if needed).
-template <bool VEC, Frames FR>
+// 32-bit pixels (AVD_FMT_BGRA32, AVD_FMT_RGBA32: RGB), any geometry / alignment: one byte-wise pixel per work item; the fourth byte is not read
+template <bool RGB>
+__device__ __forceinline__ void fill_px32_scalar(uint8_t* tile, const uint8_t* frame, const PreParams& P, const Band& b, int tid)
+{
+    const int w = P.w, pitch = P.pitch;
+    for (int it = tid; it < b.trows * w; it += kThreads) {
+        const int tr = it / w, x = it - tr * w;
+        const int y = reflect_once(b.r0 - 1 + tr, P.h);
+        tile[tr * pitch + kPad + x] = (uint8_t)gray1<RGB>(frame + (int64_t)y * P.row_stride + x * 4);
+    }
+}
+
+// 32-bit pixels, 16-byte aligned rows of w % 16 == 0 pixels: one 16-pixel chunk (4 x 16 B, a pixel per dword) per work item
+template <bool RGB>
+__device__ __forceinline__ void fill_px32_vec16(uint8_t* tile, const uint8_t* frame, const PreParams& P, const Band& b, int tid)
+{
+    const int chunks = P.w >> 4, pitch = P.pitch;
+    for (int it = tid; it < b.trows * chunks; it += kThreads) {
+        const int tr = it / chunks, c = it - tr * chunks;
+        const int y = reflect_once(b.r0 - 1 + tr, P.h);
+        const uint4* src = reinterpret_cast<const uint4*>(frame + (int64_t)y * P.row_stride + c * 64);
+        const uint4 s0 = src[0], s1 = src[1], s2 = src[2], s3 = src[3];
+        uint4 g;
+        g.x = gray4_px<RGB>(s0.x, s0.y, s0.z, s0.w);
+        g.y = gray4_px<RGB>(s1.x, s1.y, s1.z, s1.w);
+        g.z = gray4_px<RGB>(s2.x, s2.y, s2.z, s2.w);
+        g.w = gray4_px<RGB>(s3.x, s3.y, s3.z, s3.w);
+        *reinterpret_cast<uint4*>(tile + tr * pitch + kPad + c * 16) = g;
+    }
+}
+
+// Planar RGB (AVD_FMT_RGBP: three h x w planes that share P.row_stride), any geometry / alignment: one pixel per work item
+__device__ __forceinline__ void fill_rgbp_scalar(uint8_t* tile, const uint8_t* rfr, const uint8_t* gfr, const uint8_t* bfr, const PreParams& P,
+                                                 const Band& b, int tid)
+{
+    const int w = P.w, pitch = P.pitch;
+    for (int it = tid; it < b.trows * w; it += kThreads) {
+        const int tr = it / w, x = it - tr * w;
+        const int64_t o = (int64_t)reflect_once(b.r0 - 1 + tr, P.h) * P.row_stride + x;
+        tile[tr * pitch + kPad + x] = (uint8_t)((bfr[o] * 3735u + gfr[o] * 19235u + rfr[o] * 9798u + (1u << 14)) >> 15);
+    }
+}
+
+// Planar RGB, 16-byte aligned planes of w % 16 == 0 pixels: one 16-pixel chunk (one 16-byte load from each plane) per work item
+__device__ __forceinline__ void fill_rgbp_vec16(uint8_t* tile, const uint8_t* rfr, const uint8_t* gfr, const uint8_t* bfr, const PreParams& P,
+                                                const Band& b, int tid)
+{
+    const int chunks = P.w >> 4, pitch = P.pitch;
+    for (int it = tid; it < b.trows * chunks; it += kThreads) {
+        const int tr = it / chunks, c = it - tr * chunks;
+        const int64_t o = (int64_t)reflect_once(b.r0 - 1 + tr, P.h) * P.row_stride + c * 16;
+        const uint4 r = *reinterpret_cast<const uint4*>(rfr + o), g = *reinterpret_cast<const uint4*>(gfr + o),
+                    bl = *reinterpret_cast<const uint4*>(bfr + o);
+        *reinterpret_cast<uint4*>(tile + tr * pitch + kPad + c * 16) =
+            make_uint4(gray4_planar(r.x, g.x, bl.x), gray4_planar(r.y, g.y, bl.y), gray4_planar(r.z, g.z, bl.z), gray4_planar(r.w, g.w, bl.w));
+    }
+}
+
+// Planar RGB, register-staged: fill_bgr_staged with the three 16-byte words of a chunk coming from the three planes -- the same register
+// footprint, so BGR's band plan and NI classes carry over (up to NI = 8: launch_preprocess)
+template <int NI>
+__device__ __forceinline__ void fill_rgbp_staged(uint8_t* tile, const uint8_t* rfr, const uint8_t* gfr, const uint8_t* bfr, const PreParams& P,
+                                                 const Band& b, int tid)
+{
+    const int pitch = P.pitch;
+    const int chunks = P.w >> 4;
+    const int rpp = kThreads / chunks;               // tile rows covered per pass of the workgroup
+    const int rsub = tid / chunks, c = tid - rsub * chunks;
+    if (rsub < rpp) {
+        uint4 q[NI][3];
+#pragma unroll
+        for (int k = 0; k < NI; k++) {
+            const int t = min(rsub + k * rpp, b.trows - 1);  // surplus items re-read the last row (same bytes)
+            const int64_t o = (int64_t)reflect_once(b.r0 - 1 + t, P.h) * P.row_stride + c * 16;
+            q[k][0] = *reinterpret_cast<const uint4*>(rfr + o);
+            q[k][1] = *reinterpret_cast<const uint4*>(gfr + o);
+            q[k][2] = *reinterpret_cast<const uint4*>(bfr + o);
+        }
+        uint8_t* dst = tile + kPad + c * 16;
+#pragma unroll
+        for (int k = 0; k < NI; k++) {
+            const int t = min(rsub + k * rpp, b.trows - 1);
+            const uint4 g = make_uint4(gray4_planar(q[k][0].x, q[k][1].x, q[k][2].x), gray4_planar(q[k][0].y, q[k][1].y, q[k][2].y),
+                                       gray4_planar(q[k][0].z, q[k][1].z, q[k][2].z), gray4_planar(q[k][0].w, q[k][1].w, q[k][2].w));
+            uint8_t* d = dst + t * pitch;
+            *reinterpret_cast<uint4*>(d) = g;
+            if (c == 0) d[-1] = (uint8_t)(g.x >> 8);                 // pixel -1 := pixel 1
+            if (c == chunks - 1) d[16] = (uint8_t)(g.w >> 16);       // pixel w  := pixel w-2
+        }
+    }
+}
+
+// Generic kernel: one workgroup per band, any geometry / alignment (scalar loads if needed).  FMT: the packed layout -- AVD_FMT_BGR24,
+// AVD_FMT_RGB24, AVD_FMT_BGRA32 or AVD_FMT_RGBA32; it selects the fill and nothing else.
+template <bool VEC, int FMT, Frames FR>
 __global__ __launch_bounds__(kThreads) void k_preprocess(const uint8_t* __restrict__ bgr, int n,
                                                         PreParams P, uint8_t* __restrict__ small,
                                                         float* __restrict__ rowbuf,
@@ -484,15 +621,58 @@ __global__ __launch_bounds__(kThreads) void k_preprocess(const uint8_t* __restri
     if (!decode_band(P, n, b)) return;
     const int tid = threadIdx.x;
     const uint8_t* frame = frame_base<FR>(bgr, b.f, P.frame_stride);
-    if (VEC) fill_bgr_vec16(tile, frame, P, b, tid);
-    else fill_bgr_scalar(tile, frame, P, b, tid);
+    constexpr bool RGB = FMT == AVD_FMT_RGB24 || FMT == AVD_FMT_RGBA32;
+    if constexpr (FMT == AVD_FMT_BGRA32 || FMT == AVD_FMT_RGBA32) {
+        if (VEC) fill_px32_vec16<RGB>(tile, frame, P, b, tid);
+        else fill_px32_scalar<RGB>(tile, frame, P, b, tid);
+    } else {
+        if (VEC) fill_bgr_vec16<RGB>(tile, frame, P, b, tid);
+        else fill_bgr_scalar<RGB>(tile, frame, P, b, tid);
+    }
     fill_column_halo(tile, b.trows, P.pitch, P.w, tid);
     store_moments(lap_part, b.lid, tid, band_phases<false>(tile, nullptr, P, b, tid, small, rowbuf));
 }
 
-// Aligned fast path: one workgroup per band like the generic kernel, the band staged in registers (fill_bgr_staged)
-// and the resampling tables in LDS.
+// Planar RGB: the generic kernel with the pixel gathered from three planes
+template <bool VEC, Frames FR>
+__global__ __launch_bounds__(kThreads) void k_preprocess_rgbp(const uint8_t* __restrict__ rplane, RgbpParams rp, int n,
+                                                             PreParams P, uint8_t* __restrict__ small,
+                                                             float* __restrict__ rowbuf, long long* __restrict__ lap_part)
+{
+    extern __shared__ __align__(16) uint8_t tile[];
+    Band b;
+    if (!decode_band(P, n, b)) return;
+    const int tid = threadIdx.x;
+    const uint8_t* rfr = frame_base<FR>(rplane, b.f, P.frame_stride);
+    const uint8_t* gfr = frame_base<FR>(rp.g, b.f, P.frame_stride);
+    const uint8_t* bfr = frame_base<FR>(rp.b, b.f, P.frame_stride);
+    if (VEC) fill_rgbp_vec16(tile, rfr, gfr, bfr, P, b, tid);
+    else fill_rgbp_scalar(tile, rfr, gfr, bfr, P, b, tid);
+    fill_column_halo(tile, b.trows, P.pitch, P.w, tid);
+    store_moments(lap_part, b.lid, tid, band_phases<false>(tile, nullptr, P, b, tid, small, rowbuf));
+}
+
+// Planar RGB, aligned fast path: k_preprocess_vec with the band staged from three planes
 template <int NI, Frames FR>
+__global__ __launch_bounds__(kThreads, 4) void k_preprocess_rgbp_vec(const uint8_t* __restrict__ rplane, RgbpParams rp, int n,
+                                                                    PreParams P, uint8_t* __restrict__ small,
+                                                                    float* __restrict__ rowbuf, long long* __restrict__ lap_part)
+{
+    extern __shared__ __align__(16) uint8_t tile[];
+    Band b;
+    if (!decode_band(P, n, b)) return;
+    const int tid = threadIdx.x;
+    LdsTabs* lt = reinterpret_cast<LdsTabs*>(tile + lds_tile_bytes(P.rows_per_band + 2, P.pitch));
+    fill_lds_tabs(lt, P, tid);
+    fill_rgbp_staged<NI>(tile, frame_base<FR>(rplane, b.f, P.frame_stride), frame_base<FR>(rp.g, b.f, P.frame_stride),
+                         frame_base<FR>(rp.b, b.f, P.frame_stride), P, b, tid);
+    __syncthreads();
+    store_moments(lap_part, b.lid, tid, band_phases<true>(tile, lt, P, b, tid, small, rowbuf));
+}
+
+// Aligned fast path: one workgroup per band like the generic kernel, the band staged in registers (fill_bgr_staged)
+// and the resampling tables in LDS.  RGB: AVD_FMT_RGB24, the same kernel with the other coefficient constants.
+template <int NI, bool RGB, Frames FR>
 __global__ __launch_bounds__(kThreads, 4) void k_preprocess_vec(const uint8_t* __restrict__ bgr, int n,
                                                                PreParams P, uint8_t* __restrict__ small,
                                                                float* __restrict__ rowbuf,
@@ -504,7 +684,7 @@ __global__ __launch_bounds__(kThreads, 4) void k_preprocess_vec(const uint8_t* _
     const int tid = threadIdx.x;
     LdsTabs* lt = reinterpret_cast<LdsTabs*>(tile + lds_tile_bytes(P.rows_per_band + 2, P.pitch));
     fill_lds_tabs(lt, P, tid);
-    fill_bgr_staged<NI>(tile, frame_base<FR>(bgr, b.f, P.frame_stride), P, b, tid);
+    fill_bgr_staged<NI, RGB>(tile, frame_base<FR>(bgr, b.f, P.frame_stride), P, b, tid);
     __syncthreads();
     store_moments(lap_part, b.lid, tid, band_phases<true>(tile, lt, P, b, tid, small, rowbuf));
 }
@@ -973,16 +1153,24 @@ int launch_preprocess(avd_ctx* ctx, const IngestClip& clip, const uint8_t* d_in,
     const int n = clip.n;
     const int grid = (n * P.nbands + 7) / 8 * 8;
     const size_t tile = lds_tile_bytes(P.rows_per_band + 2, P.pitch);
-    const bool bgr = clip.format == AVD_FMT_BGR24, planar = clip.format == AVD_FMT_I420;
+    // bgr: no conversion constants -- BGR24 and the four layouts of RGB producers; planar: I420
+    const bool bgr = !clip.is_420(), planar = clip.format == AVD_FMT_I420;
+    const bool rgbp = clip.format == AVD_FMT_RGBP, px32 = clip.format == AVD_FMT_BGRA32 || clip.format == AVD_FMT_RGBA32;
+    const bool rgb24 = clip.format == AVD_FMT_RGB24;
     // the planar chroma planes are read 8 bytes at a time (fill_i420_tables), every other plane 16
     const bool chroma_ok = planar ? aligned_to(8, d_uv, clip.uv_row_stride, clip.uv_frame_stride) && aligned_to(8, d_v, clip.uv_row_stride, clip.uv_frame_stride)
+                           : rgbp ? aligned16(d_uv, clip.uv_row_stride, clip.uv_frame_stride) && aligned16(d_v, clip.uv_row_stride, clip.uv_frame_stride)
                                   : bgr || aligned16(d_uv, clip.uv_row_stride, clip.uv_frame_stride);
     const bool vec = list ? list->aligned : P.w % 16 == 0 && aligned16(d_in, clip.row_stride, clip.frame_stride) && chroma_ok;
-    const int ni = vec && bgr ? band_plan(P.w).ni : 0;
+    int ni = vec && (clip.format == AVD_FMT_BGR24 || rgb24 || rgbp) ? band_plan(P.w).ni : 0;
+    // planar RGB: the byte gather needs a few registers more than BGR's alignbyte, and NI = 9 (2048 < w <= 4096) no longer fits the 128 VGPRs of
+    // __launch_bounds__(256, 4) without spilling: those widths run the 16-byte fill
+    if (rgbp && ni > 8) ni = 0;
     auto launch = [&](IngestKernel id, auto kernel, size_t lds, auto... source) {
         ctx->ingest_plan = IngestPlan{P.h, P.w, P.rows_per_band, P.nbands, P.pitch, ni, (int)lds, id};
         ctx->ingest_plan_valid = 1;
         ctx->ingest_rotate = clip.rotate;
+        ctx->ingest_format = clip.format;
         ctx->ingest_range = !bgr && clip.full_range;
         ctx->ingest_list[0] = list != nullptr;
         ctx->ingest_list[1] = list ? n : 0;
@@ -1030,18 +1218,48 @@ int launch_preprocess(avd_ctx* ctx, const IngestClip& clip, const uint8_t* d_in,
             else if (rot == 2) launch(kIngestNv12Scalar, k_preprocess_nv12<false, 2, FR>, tile, d_in, nv);
             else if (vec) launch(kIngestNv12Tables, k_preprocess_nv12<true, 0, FR>, tabs, d_in, nv);
             else launch(kIngestNv12Scalar, k_preprocess_nv12<false, 0, FR>, tile, d_in, nv);
+        } else if (rgbp) {
+            RgbpParams rp{};
+            rp.g = d_uv; rp.b = d_v;
+            const size_t lds = tile + sizeof(LdsTabs);
+            switch (ni) {                              // BGR's band plan and NI classes: the chunk has the same register footprint
+            case 3: launch(kIngestRgbpStaged, k_preprocess_rgbp_vec<3, FR>, lds, d_in, rp); return 0;
+            case 4: launch(kIngestRgbpStaged, k_preprocess_rgbp_vec<4, FR>, lds, d_in, rp); return 0;
+            case 6: launch(kIngestRgbpStaged, k_preprocess_rgbp_vec<6, FR>, lds, d_in, rp); return 0;
+            case 8: launch(kIngestRgbpStaged, k_preprocess_rgbp_vec<8, FR>, lds, d_in, rp); return 0;
+            case 0: break;
+            default: ctx->err = "internal error: the band plan asks for a k_preprocess_rgbp_vec that is not built"; return AVD_ERR_DEVICE;
+            }
+            if (vec) launch(kIngestRgbpVec16, k_preprocess_rgbp<true, FR>, tile, d_in, rp);
+            else launch(kIngestRgbpScalar, k_preprocess_rgbp<false, FR>, tile, d_in, rp);
+        } else if (px32) {
+            const bool rgba = clip.format == AVD_FMT_RGBA32;
+            if (vec && rgba) launch(kIngestPx32Vec16, k_preprocess<true, AVD_FMT_RGBA32, FR>, tile, d_in);
+            else if (vec) launch(kIngestPx32Vec16, k_preprocess<true, AVD_FMT_BGRA32, FR>, tile, d_in);
+            else if (rgba) launch(kIngestPx32Scalar, k_preprocess<false, AVD_FMT_RGBA32, FR>, tile, d_in);
+            else launch(kIngestPx32Scalar, k_preprocess<false, AVD_FMT_BGRA32, FR>, tile, d_in);
         } else if (ni) {
             const size_t lds = tile + sizeof(LdsTabs);
-            switch (ni) {
-            case 3: launch(kIngestBgrStaged, k_preprocess_vec<3, FR>, lds, d_in); break;
-            case 4: launch(kIngestBgrStaged, k_preprocess_vec<4, FR>, lds, d_in); break;
-            case 6: launch(kIngestBgrStaged, k_preprocess_vec<6, FR>, lds, d_in); break;
-            case 8: launch(kIngestBgrStaged, k_preprocess_vec<8, FR>, lds, d_in); break;
-            case 9: launch(kIngestBgrStaged, k_preprocess_vec<9, FR>, lds, d_in); break;
-            default: ctx->err = "internal error: the band plan asks for a k_preprocess_vec that is not built"; return AVD_ERR_DEVICE;
+            // BGR24 and RGB24: the same band plan, the same NI, the same ids
+            auto staged = [&](auto rgb_tag) -> bool {
+                constexpr bool RGB = decltype(rgb_tag)::value;
+                switch (ni) {
+                case 3: launch(kIngestBgrStaged, k_preprocess_vec<3, RGB, FR>, lds, d_in); return true;
+                case 4: launch(kIngestBgrStaged, k_preprocess_vec<4, RGB, FR>, lds, d_in); return true;
+                case 6: launch(kIngestBgrStaged, k_preprocess_vec<6, RGB, FR>, lds, d_in); return true;
+                case 8: launch(kIngestBgrStaged, k_preprocess_vec<8, RGB, FR>, lds, d_in); return true;
+                case 9: launch(kIngestBgrStaged, k_preprocess_vec<9, RGB, FR>, lds, d_in); return true;
+                default: return false;
+                }
+            };
+            if (!(rgb24 ? staged(std::true_type{}) : staged(std::false_type{}))) {
+                ctx->err = "internal error: the band plan asks for a k_preprocess_vec that is not built";
+                return AVD_ERR_DEVICE;
             }
-        } else if (vec) launch(kIngestBgrVec16, k_preprocess<true, FR>, tile, d_in);
-        else launch(kIngestBgrScalar, k_preprocess<false, FR>, tile, d_in);
+        } else if (vec && rgb24) launch(kIngestBgrVec16, k_preprocess<true, AVD_FMT_RGB24, FR>, tile, d_in);
+        else if (vec) launch(kIngestBgrVec16, k_preprocess<true, AVD_FMT_BGR24, FR>, tile, d_in);
+        else if (rgb24) launch(kIngestBgrScalar, k_preprocess<false, AVD_FMT_RGB24, FR>, tile, d_in);
+        else launch(kIngestBgrScalar, k_preprocess<false, AVD_FMT_BGR24, FR>, tile, d_in);
         return 0;
     };
     if (int e = list ? select(std::integral_constant<Frames, Frames::listed>{}) : select(std::integral_constant<Frames, Frames::strided>{})) return e;

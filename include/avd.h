@@ -31,7 +31,8 @@
  *     (AVD_ERR_UNSUPPORTED); a null plane of a clip with n > 0 (AVD_ERR_ARG); strides smaller than the planes
  *     (AVD_ERR_ARG).  What an avd_picture alone can get wrong is refused before any of these, in this order:
  *     struct_size; format (an unknown layout in the low byte, or a bit above it other than AVD_FMT_FULL_RANGE);
- *     AVD_FMT_FULL_RANGE on a BGR picture; rotate; reserved; BGR with a rotation; U and V strides that differ.
+ *     AVD_FMT_FULL_RANGE on a BGR or RGB picture; rotate; reserved; BGR or RGB with a rotation; U and V (RGBP: R, G and B)
+ *     strides that differ.
  *     An avd_frame_list is refused for the same things in the same order (it has no frame strides; a null array of plane pointers, then a
  *     null entry of one, stand where the null plane stands).  A records pointer that is null while
  *     there are frames to write, after all of them.  The clips of a batch are checked in order.
@@ -206,10 +207,10 @@ int avd_analyze_frames_i420_async(avd_ctx* ctx, const uint8_t* y, const uint8_t*
  * half turn reads the mirrored rows and chunks of the same kernels, a quarter turn reads of every stored row the 16-byte span a band needs (the
  * strip fill); no turned picture exists in memory.
  *   struct_size  sizeof(avd_picture) of the caller's header; anything else is AVD_ERR_ARG
- *   plane        BGR: [0]; NV12: Y, interleaved UV; I420: Y, U, V (YV12: exchange [1] and [2])
- *   row_stride, frame_stride   bytes, per plane; I420: [1] == [2] (AVD_ERR_ARG otherwise)
+ *   plane        BGR: [0]; NV12: Y, interleaved UV; I420: Y, U, V (YV12: exchange [1] and [2]); the RGB layouts: below the struct's format enum
+ *   row_stride, frame_stride   bytes, per plane; I420: [1] == [2] (AVD_ERR_ARG otherwise); RGBP: [0] == [1] == [2]
  *   h, w         the stored picture;  rotate  quarter turns clockwise from the stored to the displayed picture, 0 .. 3;  reserved  0
- *   format       the layout (AVD_FMT_BGR24 / _NV12 / _I420), for the 4:2:0 layouts optionally OR-ed with AVD_FMT_FULL_RANGE
+ *   format       the layout (AVD_FMT_BGR24 / _NV12 / _I420 / _RGB24 / _BGRA32 / _RGBA32 / _RGBP), for the 4:2:0 layouts optionally OR-ed with AVD_FMT_FULL_RANGE
  * Refused without a launch: rotate outside 0 .. 3, a non-zero reserved, a bad format or struct_size (AVD_ERR_ARG); what the format's own entry
  * point refuses, with its status; AVD_FMT_BGR24 with rotate != 0 (AVD_ERR_UNSUPPORTED: cv2 hands BGR over already rotated, stored-orientation
  * BGR does not arise).  Mirrored display matrices are not covered.
@@ -226,6 +227,31 @@ int avd_analyze_frames_i420_async(avd_ctx* ctx, const uint8_t* y, const uint8_t*
  * context, drained by any other call, with the same exemptions. */
 enum avd_format { AVD_FMT_BGR24 = 0, AVD_FMT_NV12 = 1, AVD_FMT_I420 = 2 };
 #define AVD_FMT_FULL_RANGE 0x100      /* a flag OR-ed into the layout in avd_picture.format; the layout is the low byte */
+/* RGB producers (additive at ABI 3; avd_picture / avd_frame_list only -- avd_clip and the entry points that name their format are unchanged).
+ * Everything that hands over RGB rather than BGR: torchcodec / torchvision.io (uint8[N,3,H,W], channels first), decord, PyAV rgb24, imageio,
+ * PIL (uint8[H,W,3]), screen capture, compositors and rocDecode's colour-conversion helpers (BGRA / RGBA), ffmpeg's gbrp.  The gray conversion
+ * is the first thing the fused pass does, so the channel order is a constant of the fill: no rearranged copy exists anywhere.
+ *   AVD_FMT_RGB24   1 plane   R,G,B interleaved, 3 bytes per pixel
+ *   AVD_FMT_BGRA32  1 plane   B,G,R,x, 4 bytes per pixel; the fourth byte is ignored
+ *   AVD_FMT_RGBA32  1 plane   R,G,B,x, 4 bytes per pixel; the fourth byte is ignored
+ *   AVD_FMT_RGBP    3 planes  plane[0] = R, [1] = G, [2] = B, each uint8[h][w]; the three planes share their row and frame strides
+ * A torch uint8[N,3,H,W] tensor is AVD_FMT_RGBP with plane[c] = base + c*H*W and frame stride 3*H*W.  ffmpeg's gbrp (planes stored G, B, R) is
+ * the same layout with its three plane pointers handed over in R, G, B order: plane[0] = data[2], plane[1] = data[0], plane[2] = data[1].
+ * ARGB and ABGR (alpha first) are not covered, nor 16-bit or float RGB, nor GRAY8.
+ * Results: if B is the BGR24 arrangement of the same pixels (alpha dropped), every output equals the BGR entry point's on B bit for bit -- cv2's
+ * own RGB2GRAY / BGRA2GRAY use the same three coefficients in other positions.
+ * Refused in avd_picture's / avd_frame_list's order, where the BGR and I420 equivalents stand: AVD_FMT_FULL_RANGE on any of the four
+ * (AVD_ERR_ARG: RGB has no range); rotate != 0 (AVD_ERR_UNSUPPORTED: producers of RGB hand it over already turned); AVD_FMT_RGBP planes whose
+ * row or frame strides differ (AVD_ERR_ARG).  No evenness rule applies; the 32 x 32 minimum, the 16384 limits, null planes and short strides
+ * are checked as for every clip, with rows of 3w, 4w and w bytes.  Layouts 3 .. 0x0F and 0x14 .. 0xFF stay AVD_ERR_ARG.
+ * AVD_MEM_HOST: the three planes of AVD_FMT_RGBP are staged as the planes of I420 are -- spans merged where they overlap or touch, so a dense
+ * [N,3,H,W] stack crosses the link as ONE copy and separately allocated planes as three; the packed layouts are one span.
+ * The 16-byte fills need w % 16 == 0 and every plane base, row stride and frame stride 16-byte aligned (a list: every frame); anything else
+ * runs the scalar fill with identical results. */
+#define AVD_FMT_RGB24  0x10
+#define AVD_FMT_BGRA32 0x11
+#define AVD_FMT_RGBA32 0x12
+#define AVD_FMT_RGBP   0x13
 typedef struct avd_picture {
     uint32_t struct_size;
     int32_t  format;
@@ -430,12 +456,14 @@ int avd_kernel_ms(avd_ctx* ctx, int kernel_id, float* ms);
  * name: "area" uint8[n][1024]; "pyr<L>" float[n][hL][wL]; "poly<L>" float[n][hL][wL][5];
  * "flow<L>" float[n-1][2][hL][wL] (planar, after the last iteration at level L).
  * "ingest_plan" int32[8], host state rather than a device buffer: what the last ingest launch of the context ran --
- * h, w, rows_per_band, nbands, LDS tile pitch, NI of k_preprocess_vec (0: another kernel), dynamic LDS bytes requested,
- * kernel (0 bgr_scalar, 1 bgr_vec16, 2 bgr_staged, 3 nv12_scalar, 4 nv12_tables, 5 i420_scalar, 6 i420_tables, 7 nv12_strip, 8 i420_strip; a half turn runs the
- * flipped instantiations of 3 .. 6 under the same ids); h, w are the displayed picture's; an error before any ingest launch.
+ * h, w, rows_per_band, nbands, LDS tile pitch, NI of k_preprocess_vec / k_preprocess_rgbp_vec (0: another kernel), dynamic LDS bytes requested,
+ * kernel (0 bgr_scalar, 1 bgr_vec16, 2 bgr_staged, 3 nv12_scalar, 4 nv12_tables, 5 i420_scalar, 6 i420_tables, 7 nv12_strip, 8 i420_strip, 9 px32_scalar, 10 px32_vec16, 11 rgbp_scalar, 12 rgbp_vec16, 13 rgbp_staged;
+ * a half turn runs the flipped instantiations of 3 .. 6 under the same ids; AVD_FMT_RGB24 runs 0 .. 2 with its own coefficient constants, BGRA32 and
+ * RGBA32 share 9 and 10: "ingest_format" tells them apart); h, w are the displayed picture's; an error before any ingest launch.
  * "ingest_rotate" int32[1], host state: the rotation (quarter turns) that launch ran with; an error before any ingest launch.
  * "ingest_range" int32[1], host state: 1 if that launch ran with full-range conversion constants (AVD_FMT_FULL_RANGE), else 0; an error before
  * any ingest launch.
+ * "ingest_format" int32[1], host state: the layout (AVD_FMT_*, without AVD_FMT_FULL_RANGE) of that launch; an error before any ingest launch.
  * "stage_bytes" int64[1], host state: the bytes the last ingest call of the context (avd_preprocess_*, avd_analyze_*) copied from host
  * memory into its staging buffer -- 0 for device input, the sum over the clips of a batch; an error before any ingest call.
  * "stage_copies" int64[1], host state: the host-to-device staging copies that call issued, summed over its clips (a strided clip: its merged
