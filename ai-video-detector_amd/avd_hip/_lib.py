@@ -820,10 +820,27 @@ class Context:
             if a.ndim != 1:
                 raise ValueError("wav must be float32[n]")
             ptr, mem, n, keep = a.ctypes.data, AVD_MEM_HOST, int(a.size), a
-        nwin = (n + win - 1) // win if n else 0
+        nwin = (n + win - 1) // win if n and win > 0 else 0          # win < 1 or > 8192: the library refuses (AvdError)
         out = np.zeros(nwin, AUDIO_WINDOW_DTYPE)
         self._check(self._L.avd_audio_features(self._h, ptr, mem, n, int(win), out.ctypes.data, nwin))
         return out
+
+    def audio_plan(self):
+        """(nwin, win, last, nfull) of the last audio_features call: windows, window length, length of the last window, windows that
+        took the 80 x 100 transform (the rest took the direct sum); avd_debug_fetch "audio_plan"."""
+        return tuple(int(v) for v in self.debug_fetch("audio_plan", (4,), np.int32))
+
+    def audio_xw(self) -> np.ndarray:
+        """float64[nwin, win]: the windowed samples of the last audio_features call (a short last window fills only its first
+        ``last`` entries); avd_debug_fetch "audio_xw"."""
+        nwin, win, _, _ = self.audio_plan()
+        return self.debug_fetch("audio_xw", (nwin, win), np.float64)
+
+    def audio_mag(self) -> np.ndarray:
+        """float64[nwin, win // 2 + 1]: |rfft| + 1e-9 per window of the last audio_features call (a short last window: its first
+        ``last // 2 + 1`` entries); avd_debug_fetch "audio_mag"."""
+        nwin, win, _, _ = self.audio_plan()
+        return self.debug_fetch("audio_mag", (nwin, win // 2 + 1), np.float64)
 
     # -- record exchange across ranks (RCCL, bound at run time) --------------------------------------------------
     @staticmethod

@@ -954,7 +954,22 @@ static int64_t impl_debug_fetch(avd_ctx* ctx, const char* name, void* out, size_
         HIP_TRY(ctx, hipSetDevice(ctx->device));
         return cnn_tap_fetch(ctx, out, out_bytes);
     }
-    if (std::strcmp(name, "area") == 0) { src = ws.d_area; bytes = (size_t)n * 1024; }
+    if (std::strncmp(name, "audio_", 6) == 0) {        // the last avd_audio_features of this context: its window plan (host state) and its two scratch arrays
+        const bool plan = std::strcmp(name + 6, "plan") == 0, xw = std::strcmp(name + 6, "xw") == 0, mag = std::strcmp(name + 6, "mag") == 0;
+        if (!plan && !xw && !mag) { ctx->err = "unknown debug buffer"; return AVD_ERR_ARG; }
+        if (!ctx->audio_plan_valid) { ctx->err = "audio_plan / audio_xw / audio_mag not recorded yet: no avd_audio_features call has run on this context"; return AVD_ERR_ARG; }
+        if (plan) {
+            if (out_bytes < sizeof(ctx->audio_plan)) { ctx->err = "audio_plan is int32[4]"; return AVD_ERR_ARG; }
+            std::memcpy(out, ctx->audio_plan, sizeof(ctx->audio_plan));
+            return (int64_t)sizeof(ctx->audio_plan);
+        }
+        // launch_audio_features lays ws.d_audio_buf out as xw [nwin][win] | mag [nwin][win / 2 + 1] | the FFT path's intermediate
+        const size_t nwin = (size_t)ctx->audio_plan[0], win = (size_t)ctx->audio_plan[1];
+        if (!ws.d_audio_buf) { ctx->err = "buffer not allocated yet"; return AVD_ERR_ARG; }   // avd_release_workspace since that call
+        src = xw ? ws.d_audio_buf.p : ws.d_audio_buf.p + nwin * win;
+        bytes = (xw ? nwin * win : nwin * (win / 2 + 1)) * sizeof(double);
+    }
+    else if (std::strcmp(name, "area") == 0) { src = ws.d_area; bytes = (size_t)n * 1024; }
     else if (std::strcmp(name, "small") == 0) { src = ws.d_small; bytes = (size_t)n * AVD_NPIX; }
     // the Farneback scratch holds ONE chunk (kFbChunk pairs): for longer clips these are the last chunk's buffers
     else if ((k = level("pyr")) >= 0 && k == 0 && ctx->fb_fold_blur) { ctx->err = "pyr0 does not exist while fb_fold_blur is on (the polynomial expansion forms the 320-px blur itself)"; return AVD_ERR_ARG; }
@@ -1184,7 +1199,8 @@ static int impl_rowop(avd_ctx* ctx, int op, const void* x, int mem, int bf16, in
 static int impl_audio_features(avd_ctx* ctx, const float* wav, int mem, int64_t n, int win, avd_audio_window* windows, int max_windows)
 {
     if (!ctx) return AVD_ERR_ARG;
-    if (n < 0 || win < 1 || (n > 0 && (!wav || !windows))) { ctx->err = "bad arguments"; return AVD_ERR_ARG; }
+    if (win < 1 || win > 8192) { ctx->err = "audio window must be 1..8192 samples"; return AVD_ERR_ARG; }   // also for n = 0: a bad window is never "nothing to do"
+    if (n < 0 || (n > 0 && (!wav || !windows))) { ctx->err = "bad arguments"; return AVD_ERR_ARG; }
     if (n == 0) return AVD_OK;
     const int64_t nw64 = (n + win - 1) / win;
     if (nw64 > max_windows || nw64 > (1 << 24)) { ctx->err = "windows array too small"; return AVD_ERR_ARG; }

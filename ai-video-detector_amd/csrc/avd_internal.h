@@ -278,6 +278,8 @@ struct avd_ctx {
                                     // 2 + i = output of convolution i, 55 = max pool, 56 = pooled features); one pass, no timing repetitions
     int cnn_plan[kCnnConvs] = {};   // the kernel shape (CnnShape) each convolution of the last forward ran as (debug buffer "cnn_plan")
     int cnn_plan_valid = 0;         // 0 until the first forward
+    int audio_plan[4] = {};         // nwin, win, last, nfull (windows on the 80 x 100 path) of the last avd_audio_features (debug buffer "audio_plan")
+    int audio_plan_valid = 0;       // 0 until the first one, and while a later one has not enqueued all its launches
     int cnn_shape = 0;              // the shape the last convolution launch took
     int cnn_chunk = 128;            // CNN extension: frames per forward pass (activation scratch = 4 x 1.6 MB per frame)
     int cnn_fuse = 2;               // CNN extension: a block's 3x3 and expanding 1x1 in one launch (stages 1, 2): 2 = with the 3x3's input slab in LDS in the stride-1 blocks (k_slab3_expand), 1 = gathering kernels only, 0 = layer by layer

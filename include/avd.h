@@ -320,7 +320,8 @@ int avd_softmax(avd_ctx* ctx, const float* x, int mem, int64_t rows, int cols, f
 /* Audio analyzer: the per-window loop of reference app/analyzers/audio.py:40-61 for every window of a
  * mono float32 waveform at once.  wav: n samples (host or device); win: samples per window (the reference uses
  * int(sr * 0.5) = 8000 at 16 kHz; at most 8192); windows: host array of ceil(n / win) records, filled in order (the
- * last window may be shorter).  From a record the reference's per-window values follow as
+ * last window may be shorter).  n = 0 is AVD_OK and writes nothing; win outside 1 ... 8192 (whatever n is), n < 0, a null wav or windows with n > 0
+ * and max_windows < ceil(n / win) are AVD_ERR_ARG, and the context takes the next call as if the refused one had not been made.  From a record the reference's per-window values follow as
  *   rms = sqrt(sumsq / length); zcr = float32(zero_cross) / float32(length - 1) / 2;
  *   flatness = exp(sum_log / nbins) / (sum_mag / nbins); rolloff = rolloff_index / max(1, nbins);
  *   centroid = sum_fmag / sum_mag          (mag = |rfft(seg * hanning)| + 1e-9, all sums in double)
@@ -476,6 +477,11 @@ int avd_kernel_ms(avd_ctx* ctx, int kernel_id, float* ms);
  * "cnn_plan" int32[53], host state: the kernel shape each convolution of the last avd_cnn_forward ran as -- 0 no launch of its own (the expanding 1x1
  * of a fused block), 1 128 x 128 tiles, 2 256 x 64, 3 256 x 128, 4 256 x 256, 5 the stem, 6 k_conv3_expand, 7 k_slab3_expand (the fused launches are
  * recorded at the block's 3x3); an error before any forward.
+ * "audio_plan" int32[4], host state: nwin, win, last (the length of the last window) and nfull (the windows that took the 80 x 100 transform;
+ * the others took the direct sum) of the last avd_audio_features call of the context; an error before any such call.
+ * "audio_xw" double[nwin][win]: the windowed samples seg * hanning of that call (a short last window fills only its first `last` entries).
+ * "audio_mag" double[nwin][win / 2 + 1]: the magnitudes |rfft| + 1e-9 its sums were taken over (a short last window: its first last / 2 + 1
+ * entries).  Both are an error before any such call and after avd_release_workspace.
  * Returns the number of bytes copied (>=0) or a negative status. */
 int64_t avd_debug_fetch(avd_ctx* ctx, const char* name, void* out, size_t out_bytes);
 

@@ -27,7 +27,7 @@ def golden():
 def _wave_of(case):
     if "seed" in case:
         return audio_oracle.synth_wave(case["seconds"], case["seed"])
-    return {"silence": np.zeros(16000 * 2, np.float32), "dc": np.full(16000 * 2 + 123, 0.25, np.float32)}[case["named"]]
+    return audio_oracle.named_wave(case["named"])
 
 
 def _close(a, b, tol):
@@ -39,6 +39,14 @@ def _close(a, b, tol):
 
 
 # ---- CPU ----------------------------------------------------------------------------------------
+def test_golden_file_holds_every_named_wave(golden):
+    have = {c["named"] for c in golden if "named" in c}
+    assert have == set(audio_oracle.NAMED_WAVES) | {"extract_fails"}
+    for case in golden:
+        if "samples" in case:
+            assert len(_wave_of(case)) == case["samples"]
+
+
 def test_oracle_equals_the_reference_outputs(golden):
     for case in golden:
         if case.get("named") == "extract_fails":
@@ -48,7 +56,7 @@ def test_oracle_equals_the_reference_outputs(golden):
 
 def test_host_tail_equals_oracle_tail(golden):
     for case in golden:
-        if "seed" not in case:
+        if case.get("named") == "extract_fails":
             continue
         wav = _wave_of(case)
         vals = audio_oracle.window_features(wav, 16000)
