@@ -263,6 +263,9 @@ static int run_flow_chunks(avd_ctx* ctx, const uint8_t* d_small, int n, float* h
     ws.no_flow_il = !h_flow_out;                           // nobody reads the interleaved flow of these chunks
     const bool flagged_mode = ctx->fb_mode == 1 && ctx->fb_rerun;
     const bool host_wants = h_mean || h_var || h_flow_out;
+    // fast mode: the shape of the 160-px level, once for all chunks and launches of this call.  fb_wide160 = 2 chooses by what is in flight: this call is
+    // being enqueued and not yet counted, so > 0 means SOMEBODY ELSE's kernels will share the chip with it
+    if (ctx->fb_mode == 1) ctx->fb_wide160_used = ctx->fb_wide160 == 1 || (ctx->fb_wide160 == 2 && avd_calls_in_flight() - ctx->counted_in_flight > 0);
     int rc = 0;
     for (int p0 = 0; p0 < n - 1 && rc == 0; p0 += chunk) {
         const int np = std::min(chunk, n - 1 - p0);
@@ -435,6 +438,7 @@ static const Option kOptions[] = {
     {"fb_fused", &avd_ctx::fb_fused, true, opt_mask<0xF>, "AVD_FB_FUSED", env_any_base},
     {"fb_mode", &avd_ctx::fb_mode, true, opt_flag, "AVD_FB_MODE", env_fb_mode},
     {"fb_fold_up", &avd_ctx::fb_fold_up, true, opt_mask<7>, "AVD_FB_FOLD_UP", std::atoi},
+    {"fb_fold_up160", &avd_ctx::fb_fold_up160, true, opt_flag, "AVD_FB_FOLD_UP160", std::atoi},
     {"fb_rerun", &avd_ctx::fb_rerun, true, opt_flag, "AVD_FB_RERUN", std::atoi},
     {"fb_rerun_fused", &avd_ctx::fb_rerun_fused, true, opt_mask<0xF, 8>},          // bit 3 (40 px) is always set
     {"tail_help", &avd_ctx::tail_help, true, opt_flag},

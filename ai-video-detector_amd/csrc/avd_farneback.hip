@@ -46,6 +46,26 @@ struct PyrGeo {
     static constexpr int SRC_BYTES = SROWS * PS, LDS_BYTES = SRC_BYTES + SROWS * NC * 4;
 };
 constexpr int cmax(int a, int b) { return a > b ? a : b; }
+constexpr int cgcd(int a, int b) { return b == 0 ? a : cgcd(b, a % b); }
+
+// The items it = tid, tid + 256, ... of a 256-thread workgroup as (row, column) = (it / PR, it % PR), without a division: the first by comparisons,
+// the following ones by a constant step with one wrap.  The columns a lane meets repeat after PER items, which are SG rows further down.
+template <int PR>
+struct PyrWalk {
+    static constexpr int PER = PR / cgcd(256, PR), SG = 256 / cgcd(256, PR);
+    __device__ static __forceinline__ void first(int tid, int& r, int& c)
+    {
+        r = 0; c = tid;
+#pragma unroll
+        for (int q = 1; q * PR < 256; q++)
+            if (tid >= q * PR) { r = q; c = tid - q * PR; }
+    }
+    __device__ static __forceinline__ void next(int& r, int& c)
+    {
+        r += 256 / PR; c += 256 % PR;
+        if (c >= PR) { c -= PR; r++; }
+    }
+};
 constexpr int kPyrLds = cmax(cmax(PyrGeo<3>::LDS_BYTES, PyrGeo<2>::LDS_BYTES), cmax(PyrGeo<1>::LDS_BYTES, PyrGeo<0>::LDS_BYTES));   // 29 KB
 
 // blk = frame * TILES + tile of this scale
@@ -88,71 +108,113 @@ __device__ __forceinline__ void pyramid_body(char* lds, int blk, const uint8_t* 
         if (tid == 0) pairdiff[f * tiles + t] = any;
     } else
         __syncthreads();
-    const float* kx = C->gk[K];
+    // The two passes below are item loops "for (it = tid; it < rows * PR; it += 256)" over (row, column) = (it / PR, it % PR), PR items per row.
+    // The columns a lane meets repeat after W::PER items = W::SG rows (PyrWalk), so a lane OWNS up to PER columns and walks down the rows in steps of SG:
+    // the column, the window's word base and byte shift, the LDS addresses and the tap weights are formed once in front of the loop, and no division
+    // is left in it (round-5 counters: 2.4 x the VALU instructions of the filters themselves, the difference was this index work per item).
+    float kw[KS];                                        // the tap weights (uniform: scalar registers)
+#pragma unroll
+    for (int q = 0; q < KS; q++) kw[q] = C->gk[K][q];
     if (KS == 3) {
         // every column is filtered at these scales (x = j): a lane does four of them from three aligned words
         static_assert(KS != 3 || NC == S, "the 3-tap scales filter whole rows");
-        for (int it = tid; it < SROWS * (S / 4); it += 256) {
-            const int r = it / (S / 4), x0 = (it - r * (S / 4)) * 4;
-            const unsigned* wp = reinterpret_cast<const unsigned*>(src[r] + PADX + x0);
-            const unsigned pw = wp[-1], cwd = wp[0], nw = wp[1];
-            const float b[6] = {(float)(pw >> 24), (float)(cwd & 0xFFu), (float)((cwd >> 8) & 0xFFu), (float)((cwd >> 16) & 0xFFu),
-                                (float)(cwd >> 24), (float)(nw & 0xFFu)};
-            typedef float f4 __attribute__((ext_vector_type(4)));
-            f4 o;
+        using W = PyrWalk<S / 4>;
+        typedef float f4 __attribute__((ext_vector_type(4)));
+        const unsigned* wp0[W::PER]; f4* dst0[W::PER]; int r0[W::PER];
+        {
+            int r, c4;
+            W::first(tid, r, c4);
 #pragma unroll
-            for (int e = 0; e < 4; e++) o[e] = __builtin_fmaf(b[e + 1], kx[1], (b[e] + b[e + 2]) * kx[0]);
-            *reinterpret_cast<f4*>(&rowf[r][x0]) = o;
-        }
-    } else
-    for (int it = tid; it < SROWS * NC; it += 256) {
-        const int r = it / NC, j = it - r * NC;
-        const int x = K == 0 ? j : ((j >> 1) << K) + OFF + (j & 1);
-        const uint8_t* row = src[r] + PADX;
-        float v;
-        if (KS == 3) {
-            const float l = (float)row[x - 1], c = (float)row[x], rr = (float)row[x + 1];
-            v = __builtin_fmaf(c, kx[1], (l + rr) * kx[0]);
-        } else {
-            // the KS source bytes x - HALF .. x + HALF: aligned 32-bit LDS reads, one byte alignment of the window
-            // (v_alignbyte), then one v_cvt_f32_ubyteN per tap -- instead of a byte read and a reflected index per tap
-            constexpr int NW = (KS + 3) / 4;                         // aligned words of the window
-            const int base = PADX + x - HALF, sh = base & 3;
-            const unsigned* wp = reinterpret_cast<const unsigned*>(src[r] + (base & ~3));
-            unsigned d[NW + 1];
-#pragma unroll
-            for (int q = 0; q <= NW; q++) d[q] = wp[q];
-            v = 0.f;
-#pragma unroll
-            for (int q = 0; q < NW; q++) {
-                const unsigned wv = __builtin_amdgcn_alignbyte(d[q + 1], d[q], sh);
-#pragma unroll
-                for (int e = 0; e < 4; e++)
-                    if (q * 4 + e < KS) v = __builtin_fmaf((float)((wv >> (8 * e)) & 0xFFu), kx[q * 4 + e], v);
+            for (int i = 0; i < W::PER; i++) {
+                r0[i] = r;
+                wp0[i] = reinterpret_cast<const unsigned*>(src[r] + PADX + 4 * c4);
+                dst0[i] = reinterpret_cast<f4*>(&rowf[r][4 * c4]);
+                W::next(r, c4);
             }
         }
-        rowf[r][j] = v;
+        for (int sb = 0; sb < SROWS; sb += W::SG) {
+#pragma unroll
+            for (int i = 0; i < W::PER; i++) {
+                if (256 * i >= SROWS * (S / 4) || r0[i] + sb >= SROWS) continue;
+                const unsigned* wp = wp0[i] + sb * (PS / 4);
+                const unsigned pw = wp[-1], cwd = wp[0], nw = wp[1];
+                const float b[6] = {(float)(pw >> 24), (float)(cwd & 0xFFu), (float)((cwd >> 8) & 0xFFu), (float)((cwd >> 16) & 0xFFu),
+                                    (float)(cwd >> 24), (float)(nw & 0xFFu)};
+                f4 o;
+#pragma unroll
+                for (int e = 0; e < 4; e++) o[e] = __builtin_fmaf(b[e + 1], kw[1], (b[e] + b[e + 2]) * kw[0]);
+                dst0[i][sb * (NC / 4)] = o;
+            }
+        }
+    } else {
+        // the KS source bytes x - HALF .. x + HALF: aligned 32-bit LDS reads, one byte alignment of the window
+        // (v_alignbyte), then one v_cvt_f32_ubyteN per tap -- instead of a byte read and a reflected index per tap
+        using W = PyrWalk<NC>;
+        constexpr int NW = (KS + 3) / 4;                 // aligned words of the window
+        const unsigned* wp0[W::PER]; float* dst0[W::PER]; int r0[W::PER], sh0[W::PER];
+        {
+            int r, j;
+            W::first(tid, r, j);
+#pragma unroll
+            for (int i = 0; i < W::PER; i++) {
+                const int x = K == 0 ? j : ((j >> 1) << K) + OFF + (j & 1);
+                const int base = PADX + x - HALF;
+                r0[i] = r; sh0[i] = base & 3;
+                wp0[i] = reinterpret_cast<const unsigned*>(src[r] + (base & ~3));
+                dst0[i] = &rowf[r][j];
+                W::next(r, j);
+            }
+        }
+        for (int sb = 0; sb < SROWS; sb += W::SG) {
+#pragma unroll
+            for (int i = 0; i < W::PER; i++) {
+                if (256 * i >= SROWS * NC || r0[i] + sb >= SROWS) continue;
+                const unsigned* wp = wp0[i] + sb * (PS / 4);
+                unsigned d[NW + 1];
+#pragma unroll
+                for (int q = 0; q <= NW; q++) d[q] = wp[q];
+                float v = 0.f;
+#pragma unroll
+                for (int q = 0; q < NW; q++) {
+                    const unsigned wv = __builtin_amdgcn_alignbyte(d[q + 1], d[q], sh0[i]);
+#pragma unroll
+                    for (int e = 0; e < 4; e++)
+                        if (q * 4 + e < KS) v = __builtin_fmaf((float)((wv >> (8 * e)) & 0xFFu), kw[q * 4 + e], v);
+                }
+                dst0[i][sb * NC] = v;
+            }
+        }
     }
     __syncthreads();
-    const float* kc = kx + HALF;
-    auto colf = [&](int rc, int j) {                     // rc = LDS row of the centre tap
-        float sacc = __builtin_fmaf(rowf[rc][j], kc[0], 0.f);
+    auto colf = [&](const float* c) {                    // c = the centre tap's row, this column
+        float sacc = __builtin_fmaf(c[0], kw[HALF], 0.f);
 #pragma unroll
-        for (int k = 1; k <= HALF; k++) sacc = __builtin_fmaf(rowf[rc + k][j] + rowf[rc - k][j], kc[k], sacc);
+        for (int k = 1; k <= HALF; k++) sacc = __builtin_fmaf(c[k * NC] + c[-k * NC], kw[HALF + k], sacc);
         return sacc;
     };
-    for (int it = tid; it < TR * WL; it += 256) {
-        const int dyl = it / WL, dx = it - dyl * WL;
-        float out;
-        if (K == 0) {
-            out = colf(dyl + HALF, dx);
-        } else {
-            const int rc = (dyl << K) + HALF;            // LDS row of source row (dy<<K)+OFF
-            const float p00 = colf(rc, 2 * dx), p01 = colf(rc, 2 * dx + 1);
-            const float p10 = colf(rc + 1, 2 * dx), p11 = colf(rc + 1, 2 * dx + 1);
-            out = ((p00 + p01) + (p10 + p11)) * 0.25f;
+    {
+        using W = PyrWalk<WL>;
+        float* out = I + ((int64_t)f * WL + dy0) * WL;
+        int dyl, dx;
+        W::first(tid, dyl, dx);
+#pragma unroll
+        for (int i = 0; i < W::PER; i++) {
+            if (256 * i < TR * WL) {
+                for (int y = dyl; y < TR; y += W::SG) {              // (one turn wherever SG >= TR: every scale but the 320-px one)
+                    float o;
+                    if (K == 0) {
+                        o = colf(&rowf[y + HALF][dx]);
+                    } else {
+                        const float* c = &rowf[(y << K) + HALF][2 * dx];   // LDS row of source row (dy << K) + OFF
+                        const float p00 = colf(c), p01 = colf(c + 1);
+                        const float p10 = colf(c + NC), p11 = colf(c + NC + 1);
+                        o = ((p00 + p01) + (p10 + p11)) * 0.25f;
+                    }
+                    out[y * WL + dx] = o;
+                }
+            }
+            W::next(dyl, dx);
         }
-        I[((int64_t)f * WL + dy0 + dyl) * WL + dx] = out;
     }
 }
 
@@ -611,7 +673,8 @@ int exact_levels(avd_ctx* ctx, int np, int fused_mask, FbTwoScratch scratch, con
 }
 
 // Levels 3 -> 0 with the fast level kernel (avd_fbfast.hip), fb_mode = 1: three iterations per level, the flow ping-pongs between the level's two
-// buffers (a = initial flow, results b, a, b), the last launch writes |flow| to d_mag; ctx->fb_fold_up (avd_internal.h) says what the launches fold in.
+// buffers (a = initial flow, results b, a, b), the last launch writes |flow| to d_mag; ctx->fb_fold_up and ctx->fb_fold_up160 (avd_internal.h) say what the
+// launches fold in.
 // Pairs the kernels flag as ill-posed are re-run by the exact kernels once the HOST has seen the flags (launch_farneback_rerun).
 int fast_levels(avd_ctx* ctx, int np)
 {
@@ -626,7 +689,9 @@ int fast_levels(avd_ctx* ctx, int np)
         float *a = ws.d_flow[k], *b = ws.d_flow2[k];
         // the initial flow: zero at the coarsest level, else the coarser level's final flow, resized by the first launch itself or by k_flow_up into a
         const float* prev = coarsest ? nullptr : ws.flow_res[k + 1];
-        const FbFlowFrom from = coarsest ? FbFlowFrom::zero : (k == 0 && (fold & 1)) ? FbFlowFrom::chain
+        // (160 px: the chain wave resizes in the one-strip shape only, which the call has chosen or not before it got here)
+        const bool chain = (k == 0 && (fold & 1)) || (k == 1 && ctx->fb_fold_up160 && ctx->fb_wide160_used);
+        const FbFlowFrom from = coarsest ? FbFlowFrom::zero : chain ? FbFlowFrom::chain
                                 : ((k == 1 || k == 2) && (fold & 2)) ? FbFlowFrom::prologue : FbFlowFrom::level;
         if (from == FbFlowFrom::level) {
             kmark(ctx, kFlowUpId[k]);

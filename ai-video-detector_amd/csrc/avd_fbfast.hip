@@ -28,6 +28,9 @@
 //           columns per step
 // (No touch / prefetch loads: the N waves' own three-entry lead covers the latency, and touching the next rows one dword
 // per line from a fourth wave cost 0.16 ms per level: it is the texture-addresser / L1 path that limits this kernel.)
+// The first launch of the 320-px level, and of the 160-px level where a pair is one strip of this same wave mix, has no input flow of its own size: its chain wave forms it from
+// the coarser level's flow a few rows ahead of the N waves (UP, role_chain), which saves k_flow_up's full-chip pass (320 px: 37 us for +3.5; 160 px: 12 us alone, 50 us among three
+// clips in flight, for +9 us on 119 CUs -- profiles/fold160_pyramid_ab.txt).
 // One workgroup barrier per step of 4 rows; N works on group t, C on group t-1, X on group t-2.  A launch is one blur
 // iteration: the flow is read from one buffer and written to another (strips of a pair read each other's columns), and the
 // next iteration is the next launch.
@@ -480,7 +483,7 @@ __device__ __forceinline__ void phase_sync()
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
 }
 
-// UP  (320 px): flow_in is the PREVIOUS level's flow ([pair][2][H/2][W/2]); the chain wave forms the launch's input flow from it on the
+// UP  (320 px, and 160 px as one strip per pair): flow_in is the PREVIOUS level's flow ([pair][2][H/2][W/2]); the chain wave forms the launch's input flow from it on the
 //     fly, a few rows ahead of the normal-equation waves (LDS ring).
 // PRO (160 / 80 px): flow_in is the previous level's flow as well, but the whole workgroup resizes it in a PROLOGUE into flow_tmp (the
 //     columns its own lanes read; strips of one pair write identical values where they overlap) -- at these sizes the chain wave is the
@@ -494,7 +497,7 @@ __global__ __launch_bounds__((64 * Ge::NWAVES)) void k_fb_fast(const float* __re
 {
     constexpr int W = Ge::W, NB = Ge::NB;
     static_assert(IT == 1 || IT == 3, "one iteration per launch, or all three");
-    static_assert(!(UP && (PRO || IT > 1)), "the chain wave's resize is the 320-px launch's");
+    static_assert(!(UP && (PRO || IT > 1 || Ge::PN)), "the chain wave's resize belongs to one-iteration launches of the throughput shape");
     __shared__ __align__(16) double lds[Ge::LDS_DOUBLES + (UP ? Ge::F_FLOATS / 2 : 0)];
     double* vsring = lds;
     float* mrings = reinterpret_cast<float*>(lds + Ge::VS_DOUBLES);
@@ -586,10 +589,11 @@ void launch_fast(hipStream_t stream, const float* R, const FbFastLaunch& L, floa
     const dim3 g(grid), t(64 * Ge::NWAVES);
     const int zero_first = L.from == FbFlowFrom::zero;
     auto go = [&](auto kernel, int zf) { hipLaunchKernelGGL(kernel, g, t, 0, stream, R, L.flow_in, L.flow_out, L.flow_tmp, mag, L.flags, L.pairdiff, np, nstrips, ow, zf); };
-    // the chain wave's resize only exists where it pays: at 320 px it costs the launch 3.5 us and saves k_flow_up's 37; the small
-    // levels are latency-bound on exactly the chain wave that would do it (160 px: 45 -> 84 us per launch against 12 saved)
+    // the chain wave's resize only exists where it pays: in the throughput shape (2 + 1 + 1 waves per block: the chain wave has issue slots to
+    // spare).  At 320 px it costs the launch 3.5 us and saves k_flow_up's 37; the 160-px level's one-strip shape is the same wave mix.  The
+    // latency shapes are bound by exactly the chain wave that would do it (160 px, two strips: 45 -> 84 us per launch against 12 saved)
     const bool pro = L.from == FbFlowFrom::prologue, three = L.iterations == 3;
-    if constexpr (Ge::W == 320) { if (L.from == FbFlowFrom::chain) return go(k_fb_fast<Ge, true>, 0); }
+    if constexpr (Ge::W == 320 || (Ge::W == 160 && !Ge::PN)) { if (L.from == FbFlowFrom::chain) return go(k_fb_fast<Ge, true>, 0); }
     if constexpr (Ge::W == 160 || Ge::W == 80) { if (pro && !three) return go(k_fb_fast<Ge, false, 1, true>, 0); }
     if constexpr (Ge::W == 80) { if (pro && three) return go(k_fb_fast<Ge, false, 3, true>, 0); }
     if constexpr (Ge::W == 80 || Ge::W == 40) { if (three) return go(k_fb_fast<Ge, false, 3, false>, zero_first); }
@@ -608,7 +612,7 @@ int launch_fb_fast(avd_ctx* ctx, hipStream_t stream, int w, const float* R, cons
     // the combinations that exist (k_fb_fast's template arguments, launch_fast)
     const bool one = L.iterations == 1, three = L.iterations == 3;
     const bool ok = L.from == FbFlowFrom::level || L.from == FbFlowFrom::zero ? (one || (three && (w == 80 || w == 40)))
-                  : L.from == FbFlowFrom::chain ? (one && w == 320)
+                  : L.from == FbFlowFrom::chain ? (one && (w == 320 || (w == 160 && ctx->fb_wide160_used)))      // 160 px: the one-strip shape only
                   : (one ? (w == 160 || w == 80) : (three && w == 80));      // prologue
     if (!ok) { ctx->err = "launch_fb_fast: this mode does not exist at this level size"; return AVD_ERR_ARG; }
     const bool uses_tmp = three || L.from == FbFlowFrom::prologue;
@@ -625,8 +629,8 @@ int launch_fb_fast(avd_ctx* ctx, hipStream_t stream, int w, const float* R, cons
         // (one clip alone: -25 us); the wide one costs fewer CU-microseconds (119 x 58 against 238 x 48: lanes 91 % instead of 73 % on image
         // columns, 14 halo columns per pair instead of 28) and that is what counts with clips in flight: +2.4 % frames/s.  The two differ in the
         // grouping of the solver's window sums (four columns per lane against two): bit-identical on well-posed content, like the 320-px level.
-        // 2 = choose per call: this call is being enqueued and not yet counted, so > 0 means SOMEBODY ELSE's kernels will share the chip with it
-        ctx->fb_wide160_used = ctx->fb_wide160 == 1 || (ctx->fb_wide160 == 2 && avd_calls_in_flight() - ctx->counted_in_flight > 0);
+        // Which of the two a call takes is decided once, when the call is enqueued (ctx->fb_wide160_used, avd_capi.hip): all launches of the call,
+        // and the schedule that chooses where the first one's flow comes from (fast_levels), read the same answer.
         if (ctx->fb_wide160_used) launch_fast<FGeo<160, 3, 2, 2, 1>>(stream, R, L, nullptr, np, 1, 160);
         else launch_fast<FGeo<160, 2, 1, 4, 2>>(stream, R, L, nullptr, np, 2, 80);
         break;

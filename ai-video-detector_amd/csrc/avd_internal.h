@@ -272,7 +272,8 @@ struct avd_ctx {
     int fb_wide160 = 2;             // fast mode: the 160-px level as one three-block strip per pair (1: fewer CU-microseconds, throughput) or as two strips (0: shorter launches, latency);
                                     // 2 (default) = by what is in flight when the call is enqueued: one strip if another context of the process holds an undrained call, two if this clip is alone; AVD_FB_WIDE160 / avd_set_option
     int counted_in_flight = 0;      // this context's enqueued call is counted in avd_calls_in_flight()
-    int fb_wide160_used = 0;        // the shape the last call's 160-px launches took (read-only option "fb_wide160_used")
+    int fb_wide160_used = 0;        // the shape of the 160-px launches, decided ONCE per call when it is enqueued (run_flow_chunks) and read by the schedule and by
+                                    // every launch of the call (read-only option "fb_wide160_used")
     int gemm_waves = 8;             // patch-embed GEMM: waves per workgroup (8: 8 x 4 MFMA tiles per wave, 16: 4 x 4; measured no faster), the same 256 x 256 tile; AVD_GEMM_WAVES / avd_set_option
     int cnn_tap = 0;                // CNN extension, tests: the forward copies one intermediate aside for avd_debug_fetch "cnn_tap" (0 = off, 1 = bordered input image,
                                     // 2 + i = output of convolution i, 55 = max pool, 56 = pooled features); one pass, no timing repetitions
@@ -287,6 +288,10 @@ struct avd_ctx {
     int fb_fold_up = 5;             // fast mode, bit mask (no effect on results; AVD_FB_FOLD_UP / avd_set_option): 1 the 320-px level's first launch resizes the
                                     // 160-px flow itself (no k_flow_up<320>), 2 the 160- / 80-px levels do so in a prologue, 4 the 80- / 40-px levels run their three
                                     // iterations in one launch
+    int fb_fold_up160 = 1;          // fast mode (no effect on results; AVD_FB_FOLD_UP160 / avd_set_option): the 160-px level's first launch resizes the 80-px flow
+                                    // itself in its chain wave, as bit 1 of fb_fold_up does at 320 px (no k_flow_up<160>) -- in the one-strip shape only (fb_wide160_used),
+                                    // whose wave mix is the 320-px strip's; with two strips per pair the chain wave is the pole and fb_fold_up decides.  An option of
+                                    // its own, not a fourth bit of fb_fold_up: that option is a 3-bit mask with default 5 by its published contract (avd.h, ABI 3)
     int fb_mode = 1;                // 1 = fast level kernel (avd_fbfast.hip: literal vertical chain, direct horizontal window sums; flow within
                                     // 1e-5 px of the oracle, in practice identical), 0 = exact (avd_fbfused.hip / two-kernel path: bit-identical)
     int fb_rerun = 1;               // fast mode: pairs the level kernels flag as ill-posed are re-run by the exact kernels (launch_farneback_rerun); 0 = A/B, tests
@@ -398,7 +403,8 @@ int launch_fb_two(avd_ctx* ctx, hipStream_t stream, int w, const float* R, float
 // 80 / 40 px) from an initial flow that comes `from`:
 //   level     flow_in, a buffer of this level (every width)
 //   zero      like level, but at 40 px (the coarsest level) the flow is taken as zero whatever flow_in holds: no clearing launch
-//   chain     flow_in = the COARSER level's final flow [pair][2][w/2][w/2], resized by the chain wave on the fly (320 px, 1 iteration)
+//   chain     flow_in = the COARSER level's final flow [pair][2][w/2][w/2], resized by the chain wave on the fly (320 px, and 160 px in the one-strip
+//             shape: ctx->fb_wide160_used; 1 iteration)
 //   prologue  the same, resized by the whole workgroup into flow_tmp first (160 / 80 px with 1 iteration, 80 px with 3)
 enum class FbFlowFrom { level, zero, chain, prologue };   // the result is in flow_out (3 iterations: flow_tmp is the second buffer); nothing is updated in place
 struct FbFastLaunch {

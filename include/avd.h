@@ -410,12 +410,15 @@ int avd_set_profiling(avd_ctx* ctx, int enable);
  * "fb_fold_up" (fast mode, bit mask, default 5, environment AVD_FB_FOLD_UP; no effect on results): 1 = the first launch of the 320-px level
  * resizes the 160-px level's flow itself instead of reading the output of a separate resize launch; 2 = the 160- and 80-px levels do so in a
  * prologue of their first launch; 4 = the 80- and 40-px levels (a pair is one workgroup there) run their three iterations in one launch.
+ * "fb_fold_up160" (fast mode, default 1, environment AVD_FB_FOLD_UP160; no effect on results): the first launch of the 160-px level resizes the
+ * 80-px level's flow itself, as bit 1 of "fb_fold_up" does at 320 px, whenever the call runs that level as one strip per pair ("fb_wide160");
+ * with two strips per pair it changes nothing and "fb_fold_up" decides.
  * "fb_fold_blur" (default 1, environment AVD_FB_FOLD_BLUR; no effect on results): the 3 x 3 Gaussian of the 320-px pyramid scale is formed inside
  * the polynomial expansion (same two float passes, same operation order) instead of being written by the pyramid kernel and read back;
  * avd_debug_fetch "pyr0" exists with the option off only (an error otherwise: the buffer is not even allocated).
  * "fb_wide160" (fast mode, environment AVD_FB_WIDE160): 1 = the 160-px level runs a pair as ONE strip of three 64-column blocks
  * (119 workgroups, fewer CU-microseconds: +2.4 % frames/s with clips in flight), 0 = as two 80-column strips (238 workgroups, each
- * launch 10 us shorter: one clip alone finishes ~25 us sooner), 2 (default) = chosen when the call is enqueued: one strip if another context of the
+ * launch 10 us shorter: one clip alone finishes ~25 us sooner), 2 (default) = chosen ONCE when the call is enqueued, for all its launches: one strip if another context of the
  * process holds an undrained avd_analyze_* call, two strips if this clip has the chip to itself.  Same guarantee; the two shapes group the solver's
  * window sums differently (bit-identical on well-posed content, tests/test_gpu_fbfast.py).
  * "fb_fused" (exact mode only, no effect on results): bit k set = pyramid level k (0 = 320x320 .. 3 = 40x40)
