@@ -100,3 +100,62 @@ def test_host_softmax_on_a_fresh_context(rows, cols):
         assert np.array_equal(got, got2)
         odd = (rng.standard_normal((2, 33)) * 3).astype(np.float32)   # a width the register-resident kernel does not take: the general one does
         np.testing.assert_allclose(c.softmax(odd)[0], torch.softmax(torch.from_numpy(odd), dim=1).numpy(), rtol=2e-6, atol=1e-9)
+
+
+# ---- every instantiation of the row kernels, against float64 ---------------------------------------------------------------------------
+# The cases above leave k_layernorm<2, *> (cols = 512), the bf16 variants of k_layernorm<1>, <2>, <4>, <8> and k_softmax<8> (cols % 4 == 0,
+# 1028 <= cols <= 2048) unlaunched, and their reference is float32 torch, which shares the kernels' roundings.  The references here are
+# float64 numpy on the same float32 (or bf16-rounded) inputs, the tolerances are the ones above; tests/test_norm_host.py shows on the CPU
+# that float32 arithmetic in the kernels' lane order meets them.
+from tests.test_norm_host import layernorm_f64, layernorm_inputs, softmax_f64, softmax_inputs
+
+
+@pytest.mark.parametrize("rows", [1, 2, 3, 4, 6])                  # four rows per workgroup: three, two, one, no and two idle waves in the last one
+def test_layernorm_512_f32_against_float64(ctx, rows):
+    cols = 512                                                     # k_layernorm<2, false>
+    x, g, b = layernorm_inputs(rows, cols, 100 + rows)
+    want = layernorm_f64(x, g, b)
+    canary = torch.full((rows + 1, cols), float("nan"), dtype=torch.float32, device="cuda:0")
+    dev, _ = ctx.layernorm(torch.from_numpy(x).to("cuda:0"), g, b, 1e-5, out=canary[:rows])
+    got, _ = ctx.layernorm(x, g, b, 1e-5)
+    assert got.dtype == np.float32 and got.shape == (rows, cols)
+    np.testing.assert_allclose(got, want, rtol=0, atol=2e-6 * max(1.0, float(np.abs(want).max())))
+    assert np.array_equal(dev.cpu().numpy().view(np.uint32), got.view(np.uint32))     # host-staged and device-resident operands: the same bits
+    assert bool(torch.isnan(canary[rows]).all())                   # an idle wave of the last workgroup writes no row
+
+
+@pytest.mark.parametrize("cols", [256, 512, 1024, 2048])           # k_layernorm<1>, <2>, <4>, <8> with bf16 tokens
+def test_layernorm_bf16_tokens_against_float64(ctx, cols):
+    rows = 5
+    rng = np.random.default_rng(cols)
+    x = torch.from_numpy((rng.standard_normal((rows, cols)) * 3 + rng.standard_normal((rows, 1)) * 5).astype(np.float32)).to(torch.bfloat16)
+    x[3] = 1.25                                                    # a constant row: exactly beta, rounded to bf16
+    g = rng.standard_normal(cols).astype(np.float32)
+    b = rng.standard_normal(cols).astype(np.float32)
+    want = torch.from_numpy(layernorm_f64(x.float().numpy(), g, b))            # float64, from the bf16-rounded inputs
+    canary = torch.full((rows + 1, cols), float("nan"), dtype=torch.bfloat16, device="cuda:0")
+    got, _ = ctx.layernorm(x.to("cuda:0"), g, b, 1e-5, out=canary[:rows])
+    assert got.dtype == torch.bfloat16
+    got = got.cpu().double()
+    ulp = torch.maximum(want.abs(), torch.tensor(2.0 ** -126, dtype=torch.float64)) * 2.0 ** -7
+    assert torch.all((got - want).abs() <= ulp + 1e-6), float(((got - want).abs() / (ulp + 1e-6)).max())
+    assert torch.equal(got[3], torch.from_numpy(b).to(torch.bfloat16).double())
+    assert bool(torch.isnan(canary[rows]).all())
+
+
+@pytest.mark.parametrize("cols", [1024, 1028, 1500, 2048, 2052, 4092, 4096, 4100])
+def test_softmax_dispatch_edges_against_float64(ctx, cols):
+    """Both sides of every edge of launch_softmax: 1024 (k_softmax<4>) | 1028, 1500, 2048 (<8>) | 2052, 4092 -- the last piece of lane 63 is
+    padding --, 4096 (<16>) | 4100 (the general kernel).  Row 0 carries the large-logit head, row 1 equal logits (1 / cols), row 2 its
+    maximum in the last valid piece; six rows are two workgroups, the second with two idle waves."""
+    rows = 6
+    x = softmax_inputs(rows, cols, cols)
+    want = softmax_f64(x)
+    got, _ = ctx.softmax(x)
+    assert got.dtype == np.float32 and got.shape == (rows, cols)
+    np.testing.assert_allclose(got, want, rtol=2e-6, atol=1e-9)
+    np.testing.assert_allclose(got.sum(axis=1), 1.0, atol=1e-6)
+    np.testing.assert_allclose(got[1], 1.0 / cols, rtol=2e-6, atol=1e-9)
+    assert got[2].argmax() == cols - 2 and got[0].argmax() == 0
+    dev, _ = ctx.softmax(torch.from_numpy(x).to("cuda:0"))
+    assert np.array_equal(dev.cpu().numpy().view(np.uint32), got.view(np.uint32))
