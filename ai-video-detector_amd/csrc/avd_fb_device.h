@@ -238,10 +238,13 @@ __device__ __forceinline__ void fb_solve_exact(const double (&g)[5], float& fx, 
 // thresholds of the ill-posedness criteria (see role_solve and role_ne in avd_fbfast.hip)
 constexpr double kCondMax = 2000.;
 constexpr float kFlowMax = 0.3f;
-// border-sign criterion (round 5, role_ne): a flow component below kTinyFlow in magnitude is of the size of cv2's own running-sum residue
-// (<= ~1e-13 px), so its SIGN -- which decides "inside" / "outside" at the top / left border -- is not reproducible; kJumpMin: how much the
-// two branches must differ at that pixel for the flip to matter
-constexpr float kTinyFlow = 1e-12f;
+// border-sign criterion (round 5, role_ne): a flow component below kTinyFlow in magnitude is of the size of cv2's own running-sum residue,
+// so its SIGN -- which decides "inside" / "outside" at the top / left border -- is not reproducible; kJumpMin: how much the
+// two branches must differ at that pixel for the flip to matter.  The residue is 1e-17 px and less on almost every pair, but it scales with the
+// window sums it is left over from: in a flat corner next to a 160-grey-level edge the hold-out fuzz (profiles/holdout_fuzz.txt) met
+// +1.3e-12 .. +5.5e-12 px in cv2's arithmetic against -1.8e-12 .. -3.1e-12 px in this kernel's, above the 1e-12 this threshold was first set to.
+// 1e-10: eighteen times that, and still a hundred thousand times below any component of a flow that is motion (1e-5 px is the dense tolerance)
+constexpr float kTinyFlow = 1e-10f;
 constexpr float kJumpMin = 1e-6f;    // a non-zero component below kTinyFlow
 constexpr float kJumpMinZero = 0.05f; // an exactly zero one (cv2's may be +-residue): two different FLAT frames, whose zero flow is structural, stay below
 

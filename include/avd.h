@@ -389,7 +389,7 @@ int avd_set_profiling(avd_ctx* ctx, int enable);
  * profiles/r05_experiments.md section 1; tools/experiments/fb_illposed_run.py):
  *   solver      the 2 x 2 normal equations are singular over whole regions -- determinant cancellation above 2000, or a displacement
  *               above 0.3 of the level width: the reference's own flow is chaotic there (ramps, stripes, isolated straight edges);
- *   border sign a flow component at the top / left image border is smaller than 1e-12 px (the size of the rounding residue of cv2's own
+ *   border sign a flow component at the top / left image border is smaller than 1e-10 px (the size of the rounding residue of cv2's own
  *               running sums) while cv2's warp decides "inside the image" / "outside" by its SIGN and the two branches differ there:
  *               exactly periodic or static content whose true flow is zero (checkerboards; bit-identical frames but for a small patch).
  *               A pair of bit-identical frames is exempt (its zero flow is structural in cv2 too).

@@ -9,7 +9,8 @@ constant, steps, gradients) and adversarial (ramps, stripes, checkerboards of an
 Asserted for EVERY pair, no family excepted: flow_mean / flow_var within rel 1e-6 (abs 1e-7) of the oracle and |delta ai_susp| <= 1e-6
 for the texture value that makes ai_susp most sensitive to the flow (tex -> infinity: ai_susp = 1 - (1 + mot), so |delta ai_susp| =
 |delta flow_mean|); fb_mode = exact bit-identical.  The CPU experiment behind the two flag criteria
-(tools/experiments/fb_illposed_run.py, 3 120 pairs) is the same generator.
+(tools/experiments/fb_illposed_run.py, 3 120 pairs) is the same generator, so this soak is in-sample; its out-of-sample counterpart is
+tests/test_gpu_holdout.py (sixteen hold-out families of tests/holdout_families.py, 1 023 pairs each, refereed by fb_mode = exact on the GPU).
 
 Round 4 kept a carve-out here for exactly periodic checkerboards, keyed on the family's name.  Round 5 found the mechanism (cv2's
 warp takes "inside" or "outside" at the top / left border by the SIGN of a flow component that is pure rounding residue of its

@@ -26,7 +26,7 @@ static double* g_ind;          /* 8 doubles of the level being processed, or NUL
 /* i = 6 / i = 5 (round 5): the SIGN of a tiny flow at the top / left border.  cv2's warp (FarnebackUpdateMatrices) is discontinuous there: at x = 0,
  * dx = -tiny gives x1 = -1, "outside" (R0 alone), dx = +tiny gives x1 = 0, "inside" (average with R1); likewise dy at y = 0.  Where both frames are
  * flat at the border the two branches agree, so the indicator is the jump: max over border pixels whose deciding component is
- * below 1e-12 of max(|R1[0]|, |R1[1]|, |R0[c] - R1[c]| c = 2..4) (cv2's own running-sum residue can reach ~1e-13 px there, with either sign);
+ * below 1e-10 of max(|R1[0]|, |R1[1]|, |R0[c] - R1[c]| c = 2..4) (cv2's own running-sum residue has been met at 5.5e-12 px there, with either sign: 1e-12 was too low);
  * i = 5: nonzero components (criterion: jump > 1e-6), i = 6: exactly zero ones, where cv2's may be +-residue (criterion: jump > 0.05 -- two
  * different flat frames, whose zero flow is structural, stay below that).  Called on the flow every matrix update reads. */
 static void border_ind(const float* R0, const float* R1, const float* flow, int h, int w)
@@ -39,7 +39,7 @@ static void border_ind(const float* R0, const float* R1, const float* flow, int 
             double d = 1e30;
             if (x == 0) d = fmin(d, fabs((double)f[0]));
             if (y == 0) d = fmin(d, fabs((double)f[1]));
-            if (d >= 1e-12) continue;
+            if (d >= 1e-10) continue;      /* kTinyFlow */
             double nf = 0;
             /* what the two branches disagree by: outside takes r2 = R0[0] / 2, r3 = R0[1] / 2, r4.. = R0[2..]; inside (R0[0] - b[0]) / 2, .., (R0[2] + b[2]) / 2 ..
              * with b the sample of R1 = (for an all-but-zero deciding component) the top-left pixel of the warped position, clamped as the kernel gathers it */
@@ -48,7 +48,7 @@ static void border_ind(const float* R0, const float* R1, const float* flow, int 
             nf = fmax(fabs((double)b[0]), fabs((double)b[1]));
             for (int c = 2; c < 5; c++) nf = fmax(nf, fabs((double)a[c] - (double)b[c]));
             if (d == 0 && nf > g_ind[6]) g_ind[6] = nf;     /* exactly zero: cv2's may be +-residue */
-            if (d != 0 && nf > g_ind[5]) g_ind[5] = nf;     /* nonzero, below 1e-12 */
+            if (d != 0 && nf > g_ind[5]) g_ind[5] = nf;     /* nonzero, below 1e-10 */
         }
 }
 
