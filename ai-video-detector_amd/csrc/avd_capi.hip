@@ -588,8 +588,8 @@ static int preprocess_clip(avd_ctx* ctx, const IngestClip& k, size_t at, const C
         const ListStage& s = L.stage[c];
         for (const StageSpan& sp : s.span)
             HIP_TRY(ctx, hipMemcpyAsync(dst + sp.off, sp.src, sp.bytes, hipMemcpyHostToDevice, ctx->stream));
-        ctx->stage_bytes += (int64_t)s.copied;
-        ctx->stage_copies += (int64_t)s.span.size();
+        ctx->ingest.stage_bytes += (int64_t)s.copied;
+        ctx->ingest.stage_copies += (int64_t)s.span.size();
         const uint8_t* const* h_tab = ctx->ws.h_ftab + L.at[c];
         const uint8_t* const* d_tab = ctx->ws.d_ftab + L.at[c];
         const FrameTable ft{list_vec_eligible(k, h_tab)};
@@ -601,8 +601,8 @@ static int preprocess_clip(avd_ctx* ctx, const IngestClip& k, size_t at, const C
         const ClipStage s = clip_stage(k);
         for (int i = 0; i < s.nspans; i++)
             HIP_TRY(ctx, hipMemcpyAsync(dst + s.span[i].off, s.span[i].src, s.span[i].bytes, hipMemcpyHostToDevice, ctx->stream));
-        ctx->stage_bytes += (int64_t)s.copied;
-        ctx->stage_copies += s.nspans;
+        ctx->ingest.stage_bytes += (int64_t)s.copied;
+        ctx->ingest.stage_copies += s.nspans;
         d_in = dst + s.plane_off[0];
         if (k.planes() >= 2) d_uv = dst + s.plane_off[1];
         if (k.planes() == 3) d_v = dst + s.plane_off[2];
@@ -624,8 +624,8 @@ static int impl_preprocess(avd_ctx* ctx, const IngestClip& k, uint8_t* small320,
     plan_lists(&k, 1, lists);
     if (int e = ws.d_stage.reserve(ctx, lists.total(k, 0))) return e;
     if (int e = reserve_lists(ctx, lists)) return e;
-    ctx->stage_bytes = 0;
-    ctx->stage_copies = 0;
+    ctx->ingest.stage_bytes = 0;
+    ctx->ingest.stage_copies = 0;
     if (int e = upload_lists(ctx, &k, 1, lists)) return e;
     if (int e = preprocess_clip(ctx, k, 0, lists, 0)) return e;
     if (int e = launch_hash(ctx, n)) return e;
@@ -722,8 +722,8 @@ static int impl_analyze_async(avd_ctx* ctx, const IngestClip* clips, int nclips,
     if (int e = reserve_lists(ctx, lists)) return e;
     // pass 2: per clip, stage (host input) -> fused full-resolution kernel -> hash, at the clip's offsets
     ctx->kmark_used = 0;
-    ctx->stage_bytes = 0;
-    ctx->stage_copies = 0;
+    ctx->ingest.stage_bytes = 0;
+    ctx->ingest.stage_copies = 0;
     // profiling only: an empty launch in front of the first mark, so that the first region is the first kernel and not the queue's wake-up from idle as well
     if (ctx->profiling) hipLaunchKernelGGL(k_wake, dim3(1), dim3(64), 0, ctx->stream);
     stage_mark(ctx, 0);
@@ -903,50 +903,28 @@ static int64_t impl_debug_fetch(avd_ctx* ctx, const char* name, void* out, size_
         return -1;
     };
     int k;
-    if (std::strcmp(name, "ingest_plan") == 0) {       // host state, not a device buffer: what launch_preprocess ran last
-        if (!ctx->ingest_plan_valid) { ctx->err = "ingest_plan not recorded yet: no ingest kernel was launched on this context"; return AVD_ERR_ARG; }
-        bytes = std::min(sizeof(IngestPlan), out_bytes);
-        std::memcpy(out, &ctx->ingest_plan, bytes);
-        return (int64_t)bytes;
-    }
-    if (std::strcmp(name, "ingest_rotate") == 0) {     // host state: the rotation (quarter turns) that launch ran with
-        if (!ctx->ingest_plan_valid) { ctx->err = "ingest_rotate not recorded yet: no ingest kernel was launched on this context"; return AVD_ERR_ARG; }
-        if (out_bytes < sizeof(int32_t)) { ctx->err = "ingest_rotate is int32[1]"; return AVD_ERR_ARG; }
-        const int32_t r = ctx->ingest_rotate;
-        std::memcpy(out, &r, sizeof r);
-        return (int64_t)sizeof r;
-    }
-    if (std::strcmp(name, "ingest_range") == 0) {      // host state: 1 if that launch ran with full-range conversion constants
-        if (!ctx->ingest_plan_valid) { ctx->err = "ingest_range not recorded yet: no ingest kernel was launched on this context"; return AVD_ERR_ARG; }
-        if (out_bytes < sizeof(int32_t)) { ctx->err = "ingest_range is int32[1]"; return AVD_ERR_ARG; }
-        const int32_t r = ctx->ingest_range;
-        std::memcpy(out, &r, sizeof r);
-        return (int64_t)sizeof r;
-    }
-    if (std::strcmp(name, "ingest_format") == 0) {     // host state: the layout (AVD_FMT_*) of that launch
-        if (!ctx->ingest_plan_valid) { ctx->err = "ingest_format not recorded yet: no ingest kernel was launched on this context"; return AVD_ERR_ARG; }
-        if (out_bytes < sizeof(int32_t)) { ctx->err = "ingest_format is int32[1]"; return AVD_ERR_ARG; }
-        const int32_t r = ctx->ingest_format;
-        std::memcpy(out, &r, sizeof(r));
-        return (int64_t)sizeof(r);
-    }
-    if (std::strcmp(name, "ingest_list") == 0) {       // host state: did that launch take its frame bases from a table, and of how many frames
-        if (!ctx->ingest_plan_valid) { ctx->err = "ingest_list not recorded yet: no ingest kernel was launched on this context"; return AVD_ERR_ARG; }
-        if (out_bytes < sizeof(ctx->ingest_list)) { ctx->err = "ingest_list is int32[2]"; return AVD_ERR_ARG; }
-        std::memcpy(out, ctx->ingest_list, sizeof(ctx->ingest_list));
-        return (int64_t)sizeof(ctx->ingest_list);
-    }
-    if (std::strcmp(name, "stage_copies") == 0) {      // host state: staging copies the last ingest call issued
-        if (ctx->stage_copies < 0) { ctx->err = "stage_copies not recorded yet: no ingest call has run on this context"; return AVD_ERR_ARG; }
-        if (out_bytes < sizeof(int64_t)) { ctx->err = "stage_copies is int64[1]"; return AVD_ERR_ARG; }
-        std::memcpy(out, &ctx->stage_copies, sizeof(int64_t));
-        return (int64_t)sizeof(int64_t);
-    }
-    if (std::strcmp(name, "stage_bytes") == 0) {       // host state: bytes the last ingest call copied from host memory (0: device input)
-        if (ctx->stage_bytes < 0) { ctx->err = "stage_bytes not recorded yet: no ingest call has run on this context"; return AVD_ERR_ARG; }
-        if (out_bytes < sizeof(int64_t)) { ctx->err = "stage_bytes is int64[1]"; return AVD_ERR_ARG; }
-        std::memcpy(out, &ctx->stage_bytes, sizeof(int64_t));
-        return (int64_t)sizeof(int64_t);
+    {   // host state, not device buffers: what the last ingest launch / the last ingest call of the context did (IngestRecord)
+        const IngestRecord& in = ctx->ingest;
+        const char* const no_launch = "no ingest kernel was launched on this context";
+        const char* const no_call = "no ingest call has run on this context";
+        // type null: a short `out` gets the first out_bytes; otherwise it is refused with the type's name
+        const struct { const char* name; const void* p; size_t bytes; bool recorded; const char* missing; const char* type; } host_state[] = {
+            {"ingest_plan", &in.plan, sizeof in.plan, in.launched != 0, no_launch, nullptr},
+            {"ingest_rotate", &in.rotate, sizeof in.rotate, in.launched != 0, no_launch, "int32[1]"},
+            {"ingest_range", &in.range, sizeof in.range, in.launched != 0, no_launch, "int32[1]"},
+            {"ingest_format", &in.format, sizeof in.format, in.launched != 0, no_launch, "int32[1]"},
+            {"ingest_list", in.list, sizeof in.list, in.launched != 0, no_launch, "int32[2]"},
+            {"stage_copies", &in.stage_copies, sizeof in.stage_copies, in.stage_copies >= 0, no_call, "int64[1]"},
+            {"stage_bytes", &in.stage_bytes, sizeof in.stage_bytes, in.stage_bytes >= 0, no_call, "int64[1]"},
+        };
+        for (const auto& e : host_state) {
+            if (std::strcmp(name, e.name) != 0) continue;
+            if (!e.recorded) { ctx->err = std::string(e.name) + " not recorded yet: " + e.missing; return AVD_ERR_ARG; }
+            if (e.type && out_bytes < e.bytes) { ctx->err = std::string(e.name) + " is " + e.type; return AVD_ERR_ARG; }
+            bytes = std::min(e.bytes, out_bytes);
+            std::memcpy(out, e.p, bytes);
+            return (int64_t)bytes;
+        }
     }
     if (std::strcmp(name, "cnn_plan") == 0) {          // host state: the kernel shape (CnnShape) of each convolution of the last CNN forward
         if (!ctx->cnn_plan_valid) { ctx->err = "cnn_plan not recorded yet: no CNN forward has run on this context"; return AVD_ERR_ARG; }

@@ -60,22 +60,6 @@ struct YuvConsts { int cy, crv, cbu, cgu, cgv, c0, kr, kb, kg, bias, ntab; };   
 void build_yuv_consts(YuvConsts& c, bool full_range);
 void yuv_index_window(const YuvConsts& c, int& lo, int& hi);      // min and max of Y + off over Y, U, V in 0 .. 255
 
-struct Nv12Params {
-    const uint8_t* uv;                 // interleaved U,V plane of frame 0 (the Y plane is the kernel's frame pointer)
-    int64_t uv_row_stride, uv_frame_stride;
-    YuvConsts k;
-};
-
-struct RgbpParams {
-    const uint8_t *g, *b;              // the G and B planes of frame 0 (the R plane is the kernel's frame pointer); all three share PreParams' strides
-};
-
-struct I420Params {
-    const uint8_t *u, *v;              // planar U and V of frame 0, uint8[h/2][w/2] each (YV12: the caller passes them exchanged)
-    int64_t c_row_stride, c_frame_stride;   // shared by the two planes
-    YuvConsts k;
-};
-
 // ---- device-side parameter blocks ------------------------------------------------
 struct LinTap { short i0, i1, w0, w1; };   // two source indices + 11-bit weights of one output row/column
 
@@ -100,7 +84,7 @@ struct HashParams {
 };
 
 // Band plan of the ingest kernels (avd_preprocess.hip): a workgroup owns rows_per_band full-width rows, its LDS tile rows are `pitch` bytes.
-// ni: the k_preprocess_vec<NI> a 16-byte aligned BGR clip of this width runs (0: odd or too wide a width, the generic kernel).
+// ni: the NI of the staged kernel (k_preprocess_vec) a 16-byte aligned BGR clip of this width runs (0: odd or too wide a width, the generic kernel).
 struct BandPlan { int rows_per_band, pitch, ni; };
 BandPlan band_plan(int w);
 // What launch_preprocess ran last on a context: read by tests through avd_debug_fetch "ingest_plan" (eight int32 in this order).
@@ -108,6 +92,18 @@ enum IngestKernel { kIngestBgrScalar = 0, kIngestBgrVec16, kIngestBgrStaged, kIn
                     kIngestNv12Strip, kIngestI420Strip, kIngestPx32Scalar, kIngestPx32Vec16, kIngestRgbpScalar, kIngestRgbpVec16, kIngestRgbpStaged };
 struct IngestPlan { int h, w, rows_per_band, nbands, pitch, ni, lds_bytes, kernel; };
 static_assert(sizeof(IngestPlan) == 8 * sizeof(int), "avd_debug_fetch hands the struct out as int32[8]");
+// What the last ingest of a context did; avd_debug_fetch hands each member out under the name beside it.  launch_preprocess records the launch,
+// the ingest entries (avd_capi.hip) count the staging of the call.
+struct IngestRecord {
+    IngestPlan plan{};               // "ingest_plan": the last launch_preprocess
+    int launched = 0;                // 0 until the first ingest launch
+    int32_t rotate = 0;              // "ingest_rotate": the rotation that launch ran with
+    int32_t range = 0;               // "ingest_range": 1 if it ran with full-range conversion constants
+    int32_t format = 0;              // "ingest_format": its layout (AVD_FMT_*)
+    int32_t list[2] = {0, 0};        // "ingest_list": it took its frame bases from a table of plane pointers / the frames the table held
+    int64_t stage_copies = -1;       // "stage_copies": host-to-device staging copies of the last ingest call; -1 until the first one
+    int64_t stage_bytes = -1;        // "stage_bytes": bytes that call copied from host memory (0: device input); -1 until the first one
+};
 // Kernel shape of a CNN convolution launch (avd_cnn.hip), as avd_debug_fetch "cnn_plan" hands it out per convolution: kCnnFolded = no launch
 // of its own (the expanding 1x1 of a fused block; the fused launch is recorded at the block's 3x3)
 enum CnnShape { kCnnFolded = 0, kCnn128x128, kCnn256x64, kCnn256x128, kCnn256x256, kCnnStem, kCnnConv3Expand, kCnnSlab3Expand };
@@ -255,14 +251,7 @@ struct avd_ctx {
     FbConsts fbc;
     DevBuf<FbConsts> d_fbc;         // FbConsts on device
     int last_n = 0;
-    IngestPlan ingest_plan{};        // the last launch_preprocess of this context (debug buffer "ingest_plan")
-    int ingest_plan_valid = 0;       // 0 until the first ingest launch
-    int ingest_rotate = 0;           // the rotation that launch ran with (debug buffer "ingest_rotate")
-    int ingest_format = 0;           // the layout (AVD_FMT_*) of that launch (debug buffer "ingest_format")
-    int ingest_range = 0;            // 1: that launch ran with full-range conversion constants (debug buffer "ingest_range")
-    int ingest_list[2] = {0, 0};     // that launch took its frame bases from a table of plane pointers / the frames the table held (debug buffer "ingest_list")
-    int64_t stage_copies = -1;       // host-to-device staging copies of the last ingest call (debug buffer "stage_copies"); -1 until the first one
-    int64_t stage_bytes = -1;        // bytes the last ingest call copied from host memory (debug buffer "stage_bytes"; 0: device input); -1 until the first one
+    IngestRecord ingest;             // what the last ingest of this context did
     int rec_n = 0;                   // records the last avd_analyze_* call left in ws.d_rec (0 after any other entry point: avd_allgather_last_records checks it)
     void* comm = nullptr;            // RCCL communicator (avd_comm.cpp), bound at run time
     int comm_rank = 0, comm_world = 1;

@@ -28,12 +28,28 @@
 
 namespace {
 
-constexpr int kThreads = 256;       // workgroup size of the three ingest kernels
+constexpr int kThreads = 256;       // workgroup size of the ingest kernels
 constexpr int kPad = 16;            // bytes of padding left of pixel 0 in every LDS tile row
 constexpr int kMaxNI = 9;           // k_preprocess_vec: row chunks (3 x 16 B each) a lane holds in registers at most
 constexpr int kBandCap = 14;        // rows per band at most: 16 tile rows + LDS tables = 37 KiB at 1080p, 4 workgroups per CU
 constexpr int kLdsBudget = 48 * 1024;   // the tile stays under this so that >= 3 workgroups fit a CU
 static_assert(kThreads / 64 <= kLapSlots, "one moment slot per wave");
+
+// What a layout's kernels take besides plane 0 (the kernel's first argument) and PreParams: its other planes, frame 0's (or, for a listed clip,
+// the tables of their per-frame pointers), and what only this layout needs.  Packed layouts take nothing.
+struct Nv12Params {
+    const uint8_t* uv;                 // interleaved U,V plane
+    int64_t uv_row_stride, uv_frame_stride;
+    YuvConsts k;
+};
+struct I420Params {
+    const uint8_t *u, *v;              // planar U and V, uint8[h/2][w/2] each (YV12: the caller passes them exchanged)
+    int64_t c_row_stride, c_frame_stride;   // shared by the two planes
+    YuvConsts k;
+};
+struct RgbpParams {
+    const uint8_t *g, *b;              // the G and B planes (plane 0 is R); all three share PreParams' strides
+};
 
 // LDS plan, read by the kernels and by the launcher.  The tile is (rows_per_band + 2) rows of `pitch` bytes; behind it sit either the
 // resampling tables of k_preprocess_vec (LdsTabs, behind the FULL tile) or the three conversion tables of the 4:2:0 table fills (behind the
@@ -455,238 +471,64 @@ __device__ __forceinline__ void fill_column_halo(uint8_t* tile, int trows, int p
 }
 
 // ---- the fills: gray rows [r0-1, r0+rows] of the band into the tile.  They are all the kernels differ in. ----
+// The packed and the planar RGB layouts share three loops; a layout (the policies further down) hands a loop the callable that fetches and
+// converts, the way the 4:2:0 fills take their chroma callable.  `row` is the byte offset of the (reflected) image row in a plane.
 
-// The BGR fills serve AVD_FMT_RGB24 as well (RGB: the coefficient constants with bytes 0 and 2 exchanged, the same instruction stream).
-// BGR, any geometry / alignment: one byte-wise pixel per work item
-template <bool RGB>
-__device__ __forceinline__ void fill_bgr_scalar(uint8_t* tile, const uint8_t* frame, const PreParams& P, const Band& b, int tid)
+// any geometry / alignment: one byte-wise pixel per work item.  gray(row, x): the gray value of pixel x of that row
+template <typename Gray>
+__device__ __forceinline__ void fill_scalar(uint8_t* tile, const PreParams& P, const Band& b, int tid, Gray gray)
 {
     const int w = P.w, pitch = P.pitch;
     for (int it = tid; it < b.trows * w; it += kThreads) {
         const int tr = it / w, x = it - tr * w;
         const int y = reflect_once(b.r0 - 1 + tr, P.h);
-        tile[tr * pitch + kPad + x] = (uint8_t)gray1<RGB>(frame + (int64_t)y * P.row_stride + x * 3);
+        tile[tr * pitch + kPad + x] = (uint8_t)gray((int64_t)y * P.row_stride, x);
     }
 }
 
-// BGR, 16-byte aligned rows of w % 16 == 0 pixels: one 16-pixel chunk (3 x 16 B) per work item
-template <bool RGB>
-__device__ __forceinline__ void fill_bgr_vec16(uint8_t* tile, const uint8_t* frame, const PreParams& P, const Band& b, int tid)
+// 16-byte aligned rows of w % 16 == 0 pixels: one 16-pixel chunk per work item.  gray16_of(row, c): the 16 gray bytes of chunk c of that row
+template <typename Gray16>
+__device__ __forceinline__ void fill_vec16(uint8_t* tile, const PreParams& P, const Band& b, int tid, Gray16 gray16_of)
 {
     const int chunks = P.w >> 4, pitch = P.pitch;
     for (int it = tid; it < b.trows * chunks; it += kThreads) {
         const int tr = it / chunks, c = it - tr * chunks;
         const int y = reflect_once(b.r0 - 1 + tr, P.h);
-        const uint4* src = reinterpret_cast<const uint4*>(frame + (int64_t)y * P.row_stride + c * 48);
-        *reinterpret_cast<uint4*>(tile + tr * pitch + kPad + c * 16) = gray16<RGB>(src[0], src[1], src[2]);
+        *reinterpret_cast<uint4*>(tile + tr * pitch + kPad + c * 16) = gray16_of((int64_t)y * P.row_stride, c);
     }
 }
 
-// BGR, register-staged (w % 16 == 0, <= 16 * kThreads px): every lane owns one 16-pixel column chunk and issues ALL its NI
-// row loads (3 x 16 B each) before the first conversion, so a workgroup has its whole band in flight at once; conversions
-// start as the words arrive (vmcnt counts down in issue order).  The lanes that convert the first / last chunk also write
+// register-staged (w % 16 == 0, <= 16 * kThreads px): every lane owns one 16-pixel column chunk c and issues ALL its NI row loads (loader(c)
+// gives the lane's load(row, q): three 16-byte words each) before the first conversion (convert(q): their 16 gray bytes), so a workgroup has
+// its whole band in flight at once; conversions start as the words arrive (vmcnt counts down in issue order).  The lanes that convert the first / last chunk also write
 // the reflected column halo bytes, which saves a barrier.
-template <int NI, bool RGB>
-__device__ __forceinline__ void fill_bgr_staged(uint8_t* tile, const uint8_t* frame, const PreParams& P, const Band& b, int tid)
+template <int NI, typename Loader, typename Convert>
+__device__ __forceinline__ void fill_staged(uint8_t* tile, const PreParams& P, const Band& b, int tid, Loader loader, Convert convert)
 {
     const int pitch = P.pitch;
     const int chunks = P.w >> 4;
     const int rpp = kThreads / chunks;               // tile rows covered per pass of the workgroup
     const int rsub = tid / chunks, c = tid - rsub * chunks;
     if (rsub < rpp) {
-        const uint8_t* col = frame + c * 48;
+        const auto load = loader(c);
         uint4 q[NI][3];
 #pragma unroll
         for (int k = 0; k < NI; k++) {
             const int t = min(rsub + k * rpp, b.trows - 1);  // surplus items re-read the last row (same bytes)
             const int y = reflect_once(b.r0 - 1 + t, P.h);
-            const uint4* src = reinterpret_cast<const uint4*>(col + (int64_t)y * P.row_stride);
-            q[k][0] = src[0]; q[k][1] = src[1]; q[k][2] = src[2];
+            load((int64_t)y * P.row_stride, q[k]);
         }
         uint8_t* dst = tile + kPad + c * 16;
 #pragma unroll
         for (int k = 0; k < NI; k++) {
             const int t = min(rsub + k * rpp, b.trows - 1);
-            const uint4 g = gray16<RGB>(q[k][0], q[k][1], q[k][2]);
+            const uint4 g = convert(q[k]);
             uint8_t* d = dst + t * pitch;
             *reinterpret_cast<uint4*>(d) = g;
             if (c == 0) d[-1] = (uint8_t)(g.x >> 8);                 // pixel -1 := pixel 1
             if (c == chunks - 1) d[16] = (uint8_t)(g.w >> 16);       // pixel w  := pixel w-2
         }
     }
-}
-
-// 32-bit pixels (AVD_FMT_BGRA32, AVD_FMT_RGBA32: RGB), any geometry / alignment: one byte-wise pixel per work item; the fourth byte is not read
-template <bool RGB>
-__device__ __forceinline__ void fill_px32_scalar(uint8_t* tile, const uint8_t* frame, const PreParams& P, const Band& b, int tid)
-{
-    const int w = P.w, pitch = P.pitch;
-    for (int it = tid; it < b.trows * w; it += kThreads) {
-        const int tr = it / w, x = it - tr * w;
-        const int y = reflect_once(b.r0 - 1 + tr, P.h);
-        tile[tr * pitch + kPad + x] = (uint8_t)gray1<RGB>(frame + (int64_t)y * P.row_stride + x * 4);
-    }
-}
-
-// 32-bit pixels, 16-byte aligned rows of w % 16 == 0 pixels: one 16-pixel chunk (4 x 16 B, a pixel per dword) per work item
-template <bool RGB>
-__device__ __forceinline__ void fill_px32_vec16(uint8_t* tile, const uint8_t* frame, const PreParams& P, const Band& b, int tid)
-{
-    const int chunks = P.w >> 4, pitch = P.pitch;
-    for (int it = tid; it < b.trows * chunks; it += kThreads) {
-        const int tr = it / chunks, c = it - tr * chunks;
-        const int y = reflect_once(b.r0 - 1 + tr, P.h);
-        const uint4* src = reinterpret_cast<const uint4*>(frame + (int64_t)y * P.row_stride + c * 64);
-        const uint4 s0 = src[0], s1 = src[1], s2 = src[2], s3 = src[3];
-        uint4 g;
-        g.x = gray4_px<RGB>(s0.x, s0.y, s0.z, s0.w);
-        g.y = gray4_px<RGB>(s1.x, s1.y, s1.z, s1.w);
-        g.z = gray4_px<RGB>(s2.x, s2.y, s2.z, s2.w);
-        g.w = gray4_px<RGB>(s3.x, s3.y, s3.z, s3.w);
-        *reinterpret_cast<uint4*>(tile + tr * pitch + kPad + c * 16) = g;
-    }
-}
-
-// Planar RGB (AVD_FMT_RGBP: three h x w planes that share P.row_stride), any geometry / alignment: one pixel per work item
-__device__ __forceinline__ void fill_rgbp_scalar(uint8_t* tile, const uint8_t* rfr, const uint8_t* gfr, const uint8_t* bfr, const PreParams& P,
-                                                 const Band& b, int tid)
-{
-    const int w = P.w, pitch = P.pitch;
-    for (int it = tid; it < b.trows * w; it += kThreads) {
-        const int tr = it / w, x = it - tr * w;
-        const int64_t o = (int64_t)reflect_once(b.r0 - 1 + tr, P.h) * P.row_stride + x;
-        tile[tr * pitch + kPad + x] = (uint8_t)((bfr[o] * 3735u + gfr[o] * 19235u + rfr[o] * 9798u + (1u << 14)) >> 15);
-    }
-}
-
-// Planar RGB, 16-byte aligned planes of w % 16 == 0 pixels: one 16-pixel chunk (one 16-byte load from each plane) per work item
-__device__ __forceinline__ void fill_rgbp_vec16(uint8_t* tile, const uint8_t* rfr, const uint8_t* gfr, const uint8_t* bfr, const PreParams& P,
-                                                const Band& b, int tid)
-{
-    const int chunks = P.w >> 4, pitch = P.pitch;
-    for (int it = tid; it < b.trows * chunks; it += kThreads) {
-        const int tr = it / chunks, c = it - tr * chunks;
-        const int64_t o = (int64_t)reflect_once(b.r0 - 1 + tr, P.h) * P.row_stride + c * 16;
-        const uint4 r = *reinterpret_cast<const uint4*>(rfr + o), g = *reinterpret_cast<const uint4*>(gfr + o),
-                    bl = *reinterpret_cast<const uint4*>(bfr + o);
-        *reinterpret_cast<uint4*>(tile + tr * pitch + kPad + c * 16) =
-            make_uint4(gray4_planar(r.x, g.x, bl.x), gray4_planar(r.y, g.y, bl.y), gray4_planar(r.z, g.z, bl.z), gray4_planar(r.w, g.w, bl.w));
-    }
-}
-
-// Planar RGB, register-staged: fill_bgr_staged with the three 16-byte words of a chunk coming from the three planes -- the same register
-// footprint, so BGR's band plan and NI classes carry over (up to NI = 8: launch_preprocess)
-template <int NI>
-__device__ __forceinline__ void fill_rgbp_staged(uint8_t* tile, const uint8_t* rfr, const uint8_t* gfr, const uint8_t* bfr, const PreParams& P,
-                                                 const Band& b, int tid)
-{
-    const int pitch = P.pitch;
-    const int chunks = P.w >> 4;
-    const int rpp = kThreads / chunks;               // tile rows covered per pass of the workgroup
-    const int rsub = tid / chunks, c = tid - rsub * chunks;
-    if (rsub < rpp) {
-        uint4 q[NI][3];
-#pragma unroll
-        for (int k = 0; k < NI; k++) {
-            const int t = min(rsub + k * rpp, b.trows - 1);  // surplus items re-read the last row (same bytes)
-            const int64_t o = (int64_t)reflect_once(b.r0 - 1 + t, P.h) * P.row_stride + c * 16;
-            q[k][0] = *reinterpret_cast<const uint4*>(rfr + o);
-            q[k][1] = *reinterpret_cast<const uint4*>(gfr + o);
-            q[k][2] = *reinterpret_cast<const uint4*>(bfr + o);
-        }
-        uint8_t* dst = tile + kPad + c * 16;
-#pragma unroll
-        for (int k = 0; k < NI; k++) {
-            const int t = min(rsub + k * rpp, b.trows - 1);
-            const uint4 g = make_uint4(gray4_planar(q[k][0].x, q[k][1].x, q[k][2].x), gray4_planar(q[k][0].y, q[k][1].y, q[k][2].y),
-                                       gray4_planar(q[k][0].z, q[k][1].z, q[k][2].z), gray4_planar(q[k][0].w, q[k][1].w, q[k][2].w));
-            uint8_t* d = dst + t * pitch;
-            *reinterpret_cast<uint4*>(d) = g;
-            if (c == 0) d[-1] = (uint8_t)(g.x >> 8);                 // pixel -1 := pixel 1
-            if (c == chunks - 1) d[16] = (uint8_t)(g.w >> 16);       // pixel w  := pixel w-2
-        }
-    }
-}
-
-// Generic kernel: one workgroup per band, any geometry / alignment (scalar loads if needed).  FMT: the packed layout -- AVD_FMT_BGR24,
-// AVD_FMT_RGB24, AVD_FMT_BGRA32 or AVD_FMT_RGBA32; it selects the fill and nothing else.
-template <bool VEC, int FMT, Frames FR>
-__global__ __launch_bounds__(kThreads) void k_preprocess(const uint8_t* __restrict__ bgr, int n,
-                                                        PreParams P, uint8_t* __restrict__ small,
-                                                        float* __restrict__ rowbuf,
-                                                        long long* __restrict__ lap_part)
-{
-    extern __shared__ __align__(16) uint8_t tile[];
-    Band b;
-    if (!decode_band(P, n, b)) return;
-    const int tid = threadIdx.x;
-    const uint8_t* frame = frame_base<FR>(bgr, b.f, P.frame_stride);
-    constexpr bool RGB = FMT == AVD_FMT_RGB24 || FMT == AVD_FMT_RGBA32;
-    if constexpr (FMT == AVD_FMT_BGRA32 || FMT == AVD_FMT_RGBA32) {
-        if (VEC) fill_px32_vec16<RGB>(tile, frame, P, b, tid);
-        else fill_px32_scalar<RGB>(tile, frame, P, b, tid);
-    } else {
-        if (VEC) fill_bgr_vec16<RGB>(tile, frame, P, b, tid);
-        else fill_bgr_scalar<RGB>(tile, frame, P, b, tid);
-    }
-    fill_column_halo(tile, b.trows, P.pitch, P.w, tid);
-    store_moments(lap_part, b.lid, tid, band_phases<false>(tile, nullptr, P, b, tid, small, rowbuf));
-}
-
-// Planar RGB: the generic kernel with the pixel gathered from three planes
-template <bool VEC, Frames FR>
-__global__ __launch_bounds__(kThreads) void k_preprocess_rgbp(const uint8_t* __restrict__ rplane, RgbpParams rp, int n,
-                                                             PreParams P, uint8_t* __restrict__ small,
-                                                             float* __restrict__ rowbuf, long long* __restrict__ lap_part)
-{
-    extern __shared__ __align__(16) uint8_t tile[];
-    Band b;
-    if (!decode_band(P, n, b)) return;
-    const int tid = threadIdx.x;
-    const uint8_t* rfr = frame_base<FR>(rplane, b.f, P.frame_stride);
-    const uint8_t* gfr = frame_base<FR>(rp.g, b.f, P.frame_stride);
-    const uint8_t* bfr = frame_base<FR>(rp.b, b.f, P.frame_stride);
-    if (VEC) fill_rgbp_vec16(tile, rfr, gfr, bfr, P, b, tid);
-    else fill_rgbp_scalar(tile, rfr, gfr, bfr, P, b, tid);
-    fill_column_halo(tile, b.trows, P.pitch, P.w, tid);
-    store_moments(lap_part, b.lid, tid, band_phases<false>(tile, nullptr, P, b, tid, small, rowbuf));
-}
-
-// Planar RGB, aligned fast path: k_preprocess_vec with the band staged from three planes
-template <int NI, Frames FR>
-__global__ __launch_bounds__(kThreads, 4) void k_preprocess_rgbp_vec(const uint8_t* __restrict__ rplane, RgbpParams rp, int n,
-                                                                    PreParams P, uint8_t* __restrict__ small,
-                                                                    float* __restrict__ rowbuf, long long* __restrict__ lap_part)
-{
-    extern __shared__ __align__(16) uint8_t tile[];
-    Band b;
-    if (!decode_band(P, n, b)) return;
-    const int tid = threadIdx.x;
-    LdsTabs* lt = reinterpret_cast<LdsTabs*>(tile + lds_tile_bytes(P.rows_per_band + 2, P.pitch));
-    fill_lds_tabs(lt, P, tid);
-    fill_rgbp_staged<NI>(tile, frame_base<FR>(rplane, b.f, P.frame_stride), frame_base<FR>(rp.g, b.f, P.frame_stride),
-                         frame_base<FR>(rp.b, b.f, P.frame_stride), P, b, tid);
-    __syncthreads();
-    store_moments(lap_part, b.lid, tid, band_phases<true>(tile, lt, P, b, tid, small, rowbuf));
-}
-
-// Aligned fast path: one workgroup per band like the generic kernel, the band staged in registers (fill_bgr_staged)
-// and the resampling tables in LDS.  RGB: AVD_FMT_RGB24, the same kernel with the other coefficient constants.
-template <int NI, bool RGB, Frames FR>
-__global__ __launch_bounds__(kThreads, 4) void k_preprocess_vec(const uint8_t* __restrict__ bgr, int n,
-                                                               PreParams P, uint8_t* __restrict__ small,
-                                                               float* __restrict__ rowbuf,
-                                                               long long* __restrict__ lap_part)
-{
-    extern __shared__ __align__(16) uint8_t tile[];
-    Band b;
-    if (!decode_band(P, n, b)) return;
-    const int tid = threadIdx.x;
-    LdsTabs* lt = reinterpret_cast<LdsTabs*>(tile + lds_tile_bytes(P.rows_per_band + 2, P.pitch));
-    fill_lds_tabs(lt, P, tid);
-    fill_bgr_staged<NI, RGB>(tile, frame_base<FR>(bgr, b.f, P.frame_stride), P, b, tid);
-    __syncthreads();
-    store_moments(lap_part, b.lid, tid, band_phases<true>(tile, lt, P, b, tid, small, rowbuf));
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -763,26 +605,17 @@ __device__ __forceinline__ void fill_yuv420_scalar(uint8_t* tile, const uint8_t*
     }
 }
 
-// NV12: U, V interleaved in one plane
-template <bool FLIP>
-__device__ __forceinline__ void fill_nv12_scalar(uint8_t* tile, const uint8_t* yfr, const uint8_t* cfr, const Nv12Params& nv,
-                                                 const PreParams& P, const Band& b, int tid)
+// BORDER_REFLECT_101 rows of a tile whose image rows are filled (and a barrier passed): image row -1 (tile row 0, if `top`) is row 1, image row h (the last tile row,
+// if `bottom`) is row h - 2 -- both already in the tile.  Copied as `words` 16-byte words per row.
+__device__ __forceinline__ void reflect_tile_rows(uint8_t* tile, int trows, int pitch, int words, bool top, bool bottom, int tid)
 {
-    fill_yuv420_scalar<FLIP>(tile, yfr, nv.k, P, b, tid, [&](int cy, int cx, int& U, int& V) {
-        const uint8_t* cp = cfr + (int64_t)cy * nv.uv_row_stride + cx * 2;
-        U = cp[0]; V = cp[1];
-    });
-}
-
-// I420: U from u + (y>>1)*c_row_stride + (x>>1), V likewise
-template <bool FLIP>
-__device__ __forceinline__ void fill_i420_scalar(uint8_t* tile, const uint8_t* yfr, const uint8_t* ufr, const uint8_t* vfr, const I420Params& ip,
-                                                 const PreParams& P, const Band& b, int tid)
-{
-    fill_yuv420_scalar<FLIP>(tile, yfr, ip.k, P, b, tid, [&](int cy, int cx, int& U, int& V) {
-        const int64_t o = (int64_t)cy * ip.c_row_stride + cx;
-        U = ufr[o]; V = vfr[o];
-    });
+    if (top)
+        for (int c = tid; c < words; c += kThreads)
+            *reinterpret_cast<uint4*>(tile + kPad + c * 16) = *reinterpret_cast<const uint4*>(tile + 2 * pitch + kPad + c * 16);
+    if (bottom)
+        for (int c = tid; c < words; c += kThreads)
+            *reinterpret_cast<uint4*>(tile + (trows - 1) * pitch + kPad + c * 16) =
+                *reinterpret_cast<const uint4*>(tile + (trows - 3) * pitch + kPad + c * 16);
 }
 
 // the three gray tables behind a tile of trows rows (B, G, R: k.ntab entries each); returns the first
@@ -846,46 +679,7 @@ __device__ __forceinline__ void fill_yuv420_tables(uint8_t* tile, const uint8_t*
         }
     }
     __syncthreads();
-    // BORDER_REFLECT_101 rows: image row -1 is row 1, row h is row h - 2 (both already in the tile)
-    if (ylo < 0)
-        for (int c = tid; c < chunks; c += kThreads)
-            *reinterpret_cast<uint4*>(tile + kPad + c * 16) = *reinterpret_cast<const uint4*>(tile + 2 * pitch + kPad + c * 16);
-    if (yhi > h - 1)
-        for (int c = tid; c < chunks; c += kThreads)
-            *reinterpret_cast<uint4*>(tile + (trows - 1) * pitch + kPad + c * 16) =
-                *reinterpret_cast<const uint4*>(tile + (trows - 3) * pitch + kPad + c * 16);
-}
-
-// NV12: the 16 chroma bytes of a chunk are one 16-byte load, pair j = bytes 2j (U) and 2j + 1 (V)
-template <bool FLIP>
-__device__ __forceinline__ void fill_nv12_tables(uint8_t* tile, const uint8_t* yfr, const uint8_t* cfr, const Nv12Params& nv,
-                                                 const PreParams& P, const Band& b, int tid)
-{
-    fill_yuv420_tables<FLIP>(tile, yfr, nv.k, P, b, tid, [&](int p, int c, ChromaTerms (&t)[8]) {
-        const uint4 cc = *reinterpret_cast<const uint4*>(cfr + (int64_t)p * nv.uv_row_stride + c * 16);
-        const unsigned cw[4] = {cc.x, cc.y, cc.z, cc.w};
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            t[2 * j] = chroma_offsets(cw[j] & 0xFF, (cw[j] >> 8) & 0xFF, nv.k);
-            t[2 * j + 1] = chroma_offsets((cw[j] >> 16) & 0xFF, cw[j] >> 24, nv.k);
-        }
-    });
-}
-
-// I420, Y plane 16-byte aligned, U and V planes 8-byte aligned: the 16 chroma bytes of a chunk are two 8-byte loads, 8 U and 8 V; pair j = U byte j
-// and V byte j.  (A contiguous frame has its V plane at 5wh/4, which w % 16 == 0 makes a multiple of 8 but not of 16.)
-template <bool FLIP>
-__device__ __forceinline__ void fill_i420_tables(uint8_t* tile, const uint8_t* yfr, const uint8_t* ufr, const uint8_t* vfr, const I420Params& ip,
-                                                 const PreParams& P, const Band& b, int tid)
-{
-    fill_yuv420_tables<FLIP>(tile, yfr, ip.k, P, b, tid, [&](int p, int c, ChromaTerms (&t)[8]) {
-        const int64_t o = (int64_t)p * ip.c_row_stride + c * 8;
-        const uint2 uu = *reinterpret_cast<const uint2*>(ufr + o), vv = *reinterpret_cast<const uint2*>(vfr + o);
-        const unsigned uw[2] = {uu.x, uu.y}, vw[2] = {vv.x, vv.y};
-#pragma unroll
-        for (int j = 0; j < 8; j++)
-            t[j] = chroma_offsets((uw[j >> 2] >> (8 * (j & 3))) & 0xFF, (vw[j >> 2] >> (8 * (j & 3))) & 0xFF, ip.k);
-    });
+    reflect_tile_rows(tile, trows, pitch, chunks, ylo < 0, yhi > h - 1, tid);
 }
 
 // ---- quarter turns: the strip fills ----------------------------------------------------------------------------------------------------
@@ -958,86 +752,229 @@ __device__ __forceinline__ void fill_yuv420_strip(uint8_t* tile, const uint8_t* 
     };
     if (odd) walk(std::integral_constant<int, 1>{}); else walk(std::integral_constant<int, 0>{});
     __syncthreads();
-    // BORDER_REFLECT_101 rows: displayed row -1 is row 1, row h is row h - 2 (both already in the tile); whole 16-byte words, the last of
-    // which may end in the tile row's padding
-    const int words = (w + 15) >> 4;
-    if (ylo < 0)
-        for (int c = tid; c < words; c += kThreads)
-            *reinterpret_cast<uint4*>(tile + kPad + c * 16) = *reinterpret_cast<const uint4*>(tile + 2 * pitch + kPad + c * 16);
-    if (yhi > h - 1)
-        for (int c = tid; c < words; c += kThreads)
-            *reinterpret_cast<uint4*>(tile + (trows - 1) * pitch + kPad + c * 16) =
-                *reinterpret_cast<const uint4*>(tile + (trows - 3) * pitch + kPad + c * 16);
+    reflect_tile_rows(tile, trows, pitch, (w + 15) >> 4, ylo < 0, yhi > h - 1, tid);      // the last word may end in the tile row's padding
 }
 
-// NV12: sample q of a chroma row is the byte pair at 2q
-template <int ROT>
-__device__ __forceinline__ void fill_nv12_strip(uint8_t* tile, const uint8_t* yfr, const uint8_t* cfr, const Nv12Params& nv,
-                                                const PreParams& P, const Band& b, int tid)
+// ---- the layouts ----------------------------------------------------------------------------------------------------------------------
+// A fill policy is what a layout contributes to a kernel: planes<FR>() forms the frame bases of its N planes (frame_base<FR>) from plane 0 and
+// the layout's extra block, fill() chooses the fill and hands it the layout's callable, id is what the launch is recorded under.
+template <int N> struct PlaneSet { const uint8_t* p[N]; };
+struct PackedPlanes {                  // one plane of packed pixels
+    template <Frames FR>
+    static __device__ __forceinline__ PlaneSet<1> planes(const uint8_t* plane, const PreParams& P, int f) { return {{frame_base<FR>(plane, f, P.frame_stride)}}; }
+};
+struct RgbpPlanes {                    // R, G, B planes at the same strides
+    template <Frames FR>
+    static __device__ __forceinline__ PlaneSet<3> planes(const uint8_t* rplane, const RgbpParams& rp, const PreParams& P, int f)
+    {
+        return {{frame_base<FR>(rplane, f, P.frame_stride), frame_base<FR>(rp.g, f, P.frame_stride), frame_base<FR>(rp.b, f, P.frame_stride)}};
+    }
+};
+
+// Packed pixels of BPP bytes -- 3: AVD_FMT_BGR24 / _RGB24, 4: AVD_FMT_BGRA32 / _RGBA32, whose fourth byte is not read (scalar) or drops out of
+// the dot products (vec16) -- in either channel order (RGB: the coefficient constants with bytes 0 and 2 exchanged, the same instruction stream).
+// vec16: a chunk is BPP 16-byte loads; 32-bit pixels arrive one per dword and need no alignbyte.
+template <bool VEC, bool RGB, int BPP>
+struct Packed : PackedPlanes {
+    static constexpr IngestKernel id = BPP == 4 ? (VEC ? kIngestPx32Vec16 : kIngestPx32Scalar) : (VEC ? kIngestBgrVec16 : kIngestBgrScalar);
+    static __device__ __forceinline__ void fill(uint8_t* tile, const PlaneSet<1>& fr, const PreParams& P, const Band& b, int tid)
+    {
+        const uint8_t* frame = fr.p[0];
+        if (VEC)
+            fill_vec16(tile, P, b, tid, [&](int64_t row, int c) {
+                const uint4* src = reinterpret_cast<const uint4*>(frame + row + c * (16 * BPP));
+                if constexpr (BPP == 4) {
+                    const uint4 s0 = src[0], s1 = src[1], s2 = src[2], s3 = src[3];
+                    return make_uint4(gray4_px<RGB>(s0.x, s0.y, s0.z, s0.w), gray4_px<RGB>(s1.x, s1.y, s1.z, s1.w),
+                                      gray4_px<RGB>(s2.x, s2.y, s2.z, s2.w), gray4_px<RGB>(s3.x, s3.y, s3.z, s3.w));
+                } else return gray16<RGB>(src[0], src[1], src[2]);
+            });
+        else fill_scalar(tile, P, b, tid, [&](int64_t row, int x) { return gray1<RGB>(frame + row + x * BPP); });
+    }
+};
+
+// BGR24 / RGB24, the aligned fast path: a chunk's three 16-byte words are 48 consecutive bytes
+template <int NI, bool RGB>
+struct PackedStaged : PackedPlanes {
+    static constexpr IngestKernel id = kIngestBgrStaged;
+    static __device__ __forceinline__ void fill(uint8_t* tile, const PlaneSet<1>& fr, const PreParams& P, const Band& b, int tid)
+    {
+        const uint8_t* frame = fr.p[0];
+        fill_staged<NI>(tile, P, b, tid,
+                        [&](int c) {
+                            return [col = frame + c * 48](int64_t row, uint4 (&q)[3]) {
+                                const uint4* src = reinterpret_cast<const uint4*>(col + row);
+                                q[0] = src[0]; q[1] = src[1]; q[2] = src[2];
+                            };
+                        },
+                        [](const uint4 (&q)[3]) { return gray16<RGB>(q[0], q[1], q[2]); });
+    }
+};
+
+// the 16 gray bytes of 16 R, 16 G and 16 B bytes
+__device__ __forceinline__ uint4 gray16_planar(const uint4& r, const uint4& g, const uint4& b)
 {
-    fill_yuv420_strip<ROT>(tile, yfr, nv.k, P, b, tid, [&](int cy, int q0, int nq, ChromaTerms (&t)[kStripChroma]) {
-        unsigned cw[(kStripChroma + 1) / 2];
-        load_span(cfr + (int64_t)cy * nv.uv_row_stride + q0 * 2, nq * 2, cw);
-#pragma unroll
-        for (int j = 0; j < kStripChroma; j++)
-            if (j < nq) t[j] = chroma_offsets(span_byte(cw, 2 * j), span_byte(cw, 2 * j + 1), nv.k);
-    });
+    return make_uint4(gray4_planar(r.x, g.x, b.x), gray4_planar(r.y, g.y, b.y), gray4_planar(r.z, g.z, b.z), gray4_planar(r.w, g.w, b.w));
 }
 
-// I420: sample q is byte q of the U row and of the V row
-template <int ROT>
-__device__ __forceinline__ void fill_i420_strip(uint8_t* tile, const uint8_t* yfr, const uint8_t* ufr, const uint8_t* vfr, const I420Params& ip,
-                                                const PreParams& P, const Band& b, int tid)
-{
-    fill_yuv420_strip<ROT>(tile, yfr, ip.k, P, b, tid, [&](int cy, int q0, int nq, ChromaTerms (&t)[kStripChroma]) {
-        const int64_t o = (int64_t)cy * ip.c_row_stride + q0;
-        unsigned uw[(kStripChroma + 3) / 4], vw[(kStripChroma + 3) / 4];
-        load_span(ufr + o, nq, uw);
-        load_span(vfr + o, nq, vw);
-#pragma unroll
-        for (int j = 0; j < kStripChroma; j++)
-            if (j < nq) t[j] = chroma_offsets(span_byte(uw, j), span_byte(vw, j), ip.k);
-    });
-}
+// Planar RGB (AVD_FMT_RGBP: three h x w planes that share P.row_stride): a pixel or a chunk (one 16-byte load per plane) gathered from the planes
+template <bool VEC>
+struct Rgbp : RgbpPlanes {
+    static constexpr IngestKernel id = VEC ? kIngestRgbpVec16 : kIngestRgbpScalar;
+    static __device__ __forceinline__ void fill(uint8_t* tile, const PlaneSet<3>& fr, const RgbpParams&, const PreParams& P, const Band& b, int tid)
+    {
+        const uint8_t *rfr = fr.p[0], *gfr = fr.p[1], *bfr = fr.p[2];
+        if (VEC)
+            fill_vec16(tile, P, b, tid, [&](int64_t row, int c) {
+                const int64_t o = row + c * 16;
+                return gray16_planar(*reinterpret_cast<const uint4*>(rfr + o), *reinterpret_cast<const uint4*>(gfr + o),
+                                     *reinterpret_cast<const uint4*>(bfr + o));
+            });
+        else
+            fill_scalar(tile, P, b, tid, [&](int64_t row, int x) {
+                const int64_t o = row + x;
+                return (bfr[o] * 3735u + gfr[o] * 19235u + rfr[o] * 9798u + (1u << 14)) >> 15;
+            });
+    }
+};
 
-// ROT: quarter turns clockwise from the stored to the displayed picture.  0: the stored picture is the displayed one; 2: the flipped
+// Planar RGB, the aligned fast path: the three 16-byte words of a chunk come from the three planes -- PackedStaged's register footprint, so
+// BGR's band plan and NI classes carry over (up to NI = 8: launch_preprocess)
+template <int NI>
+struct RgbpStaged : RgbpPlanes {
+    static constexpr IngestKernel id = kIngestRgbpStaged;
+    static __device__ __forceinline__ void fill(uint8_t* tile, const PlaneSet<3>& fr, const RgbpParams&, const PreParams& P, const Band& b, int tid)
+    {
+        const uint8_t *rfr = fr.p[0], *gfr = fr.p[1], *bfr = fr.p[2];
+        fill_staged<NI>(tile, P, b, tid,
+                        [&](int c) {
+                            return [=](int64_t row, uint4 (&q)[3]) {
+                                const int64_t o = row + c * 16;
+                                q[0] = *reinterpret_cast<const uint4*>(rfr + o);
+                                q[1] = *reinterpret_cast<const uint4*>(gfr + o);
+                                q[2] = *reinterpret_cast<const uint4*>(bfr + o);
+                            };
+                        },
+                        [](const uint4 (&q)[3]) { return gray16_planar(q[0], q[1], q[2]); });
+    }
+};
+
+// 4:2:0.  ROT: quarter turns clockwise from the stored to the displayed picture.  0: the stored picture is the displayed one; 2: the flipped
 // instantiations of the same fills; 1, 3: the strip fill (VEC unused).  P describes the DISPLAYED picture throughout.
-template <bool VEC, int ROT, Frames FR>
-__global__ __launch_bounds__(kThreads) void k_preprocess_nv12(const uint8_t* __restrict__ yplane, Nv12Params nv, int n,
-                                                             PreParams P, uint8_t* __restrict__ small,
-                                                             float* __restrict__ rowbuf, long long* __restrict__ lap_part)
+// NV12: U, V interleaved in one plane
+template <bool VEC, int ROT>
+struct Nv12 {
+    static constexpr IngestKernel id = (ROT & 1) ? kIngestNv12Strip : VEC ? kIngestNv12Tables : kIngestNv12Scalar;
+    template <Frames FR>
+    static __device__ __forceinline__ PlaneSet<2> planes(const uint8_t* yplane, const Nv12Params& nv, const PreParams& P, int f)
+    {
+        return {{frame_base<FR>(yplane, f, P.frame_stride), frame_base<FR>(nv.uv, f, nv.uv_frame_stride)}};
+    }
+    static __device__ __forceinline__ void fill(uint8_t* tile, const PlaneSet<2>& fr, const Nv12Params& nv, const PreParams& P, const Band& b, int tid)
+    {
+        const uint8_t *yfr = fr.p[0], *cfr = fr.p[1];
+        if constexpr (ROT & 1)             // sample q of a chroma row is the byte pair at 2q
+            fill_yuv420_strip<ROT>(tile, yfr, nv.k, P, b, tid, [&](int cy, int q0, int nq, ChromaTerms (&t)[kStripChroma]) {
+                unsigned cw[(kStripChroma + 1) / 2];
+                load_span(cfr + (int64_t)cy * nv.uv_row_stride + q0 * 2, nq * 2, cw);
+#pragma unroll
+                for (int j = 0; j < kStripChroma; j++)
+                    if (j < nq) t[j] = chroma_offsets(span_byte(cw, 2 * j), span_byte(cw, 2 * j + 1), nv.k);
+            });
+        else if (VEC)                      // the 16 chroma bytes of a chunk are one 16-byte load, pair j = bytes 2j (U) and 2j + 1 (V)
+            fill_yuv420_tables<ROT == 2>(tile, yfr, nv.k, P, b, tid, [&](int p, int c, ChromaTerms (&t)[8]) {
+                const uint4 cc = *reinterpret_cast<const uint4*>(cfr + (int64_t)p * nv.uv_row_stride + c * 16);
+                const unsigned cw[4] = {cc.x, cc.y, cc.z, cc.w};
+#pragma unroll
+                for (int j = 0; j < 4; j++) {
+                    t[2 * j] = chroma_offsets(cw[j] & 0xFF, (cw[j] >> 8) & 0xFF, nv.k);
+                    t[2 * j + 1] = chroma_offsets((cw[j] >> 16) & 0xFF, cw[j] >> 24, nv.k);
+                }
+            });
+        else
+            fill_yuv420_scalar<ROT == 2>(tile, yfr, nv.k, P, b, tid, [&](int cy, int cx, int& U, int& V) {
+                const uint8_t* cp = cfr + (int64_t)cy * nv.uv_row_stride + cx * 2;
+                U = cp[0]; V = cp[1];
+            });
+    }
+};
+
+// Planar 4:2:0 (I420; YV12 with the chroma pointers exchanged): the chroma fetched from two planes
+template <bool VEC, int ROT>
+struct I420 {
+    static constexpr IngestKernel id = (ROT & 1) ? kIngestI420Strip : VEC ? kIngestI420Tables : kIngestI420Scalar;
+    template <Frames FR>
+    static __device__ __forceinline__ PlaneSet<3> planes(const uint8_t* yplane, const I420Params& ip, const PreParams& P, int f)
+    {
+        return {{frame_base<FR>(yplane, f, P.frame_stride), frame_base<FR>(ip.u, f, ip.c_frame_stride), frame_base<FR>(ip.v, f, ip.c_frame_stride)}};
+    }
+    static __device__ __forceinline__ void fill(uint8_t* tile, const PlaneSet<3>& fr, const I420Params& ip, const PreParams& P, const Band& b, int tid)
+    {
+        const uint8_t *yfr = fr.p[0], *ufr = fr.p[1], *vfr = fr.p[2];
+        if constexpr (ROT & 1)             // sample q is byte q of the U row and of the V row
+            fill_yuv420_strip<ROT>(tile, yfr, ip.k, P, b, tid, [&](int cy, int q0, int nq, ChromaTerms (&t)[kStripChroma]) {
+                const int64_t o = (int64_t)cy * ip.c_row_stride + q0;
+                unsigned uw[(kStripChroma + 3) / 4], vw[(kStripChroma + 3) / 4];
+                load_span(ufr + o, nq, uw);
+                load_span(vfr + o, nq, vw);
+#pragma unroll
+                for (int j = 0; j < kStripChroma; j++)
+                    if (j < nq) t[j] = chroma_offsets(span_byte(uw, j), span_byte(vw, j), ip.k);
+            });
+        // Y plane 16-byte aligned, U and V planes 8-byte aligned: the 16 chroma bytes of a chunk are two 8-byte loads, 8 U and 8 V; pair j = U byte
+        // j and V byte j.  (A contiguous frame has its V plane at 5wh/4, which w % 16 == 0 makes a multiple of 8 but not of 16.)
+        else if (VEC)
+            fill_yuv420_tables<ROT == 2>(tile, yfr, ip.k, P, b, tid, [&](int p, int c, ChromaTerms (&t)[8]) {
+                const int64_t o = (int64_t)p * ip.c_row_stride + c * 8;
+                const uint2 uu = *reinterpret_cast<const uint2*>(ufr + o), vv = *reinterpret_cast<const uint2*>(vfr + o);
+                const unsigned uw[2] = {uu.x, uu.y}, vw[2] = {vv.x, vv.y};
+#pragma unroll
+                for (int j = 0; j < 8; j++)
+                    t[j] = chroma_offsets((uw[j >> 2] >> (8 * (j & 3))) & 0xFF, (vw[j >> 2] >> (8 * (j & 3))) & 0xFF, ip.k);
+            });
+        else
+            fill_yuv420_scalar<ROT == 2>(tile, yfr, ip.k, P, b, tid, [&](int cy, int cx, int& U, int& V) {
+                const int64_t o = (int64_t)cy * ip.c_row_stride + cx;
+                U = ufr[o]; V = vfr[o];
+            });
+    }
+};
+
+// ---- the two kernels: one workgroup per band; POL fills the tile from plane 0 and the layout's extra block, the rest is written once ----
+
+// Generic kernel: any geometry / alignment that POL's fill takes; the resampling tables are read from global memory.
+template <typename POL, Frames FR, typename... Extra>
+__global__ __launch_bounds__(kThreads) void k_preprocess(const uint8_t* __restrict__ plane0, Extra... extra, int n,
+                                                        PreParams P, uint8_t* __restrict__ small,
+                                                        float* __restrict__ rowbuf,
+                                                        long long* __restrict__ lap_part)
 {
     extern __shared__ __align__(16) uint8_t tile[];
     Band b;
     if (!decode_band(P, n, b)) return;
     const int tid = threadIdx.x;
-    const uint8_t* yfr = frame_base<FR>(yplane, b.f, P.frame_stride);
-    const uint8_t* cfr = frame_base<FR>(nv.uv, b.f, nv.uv_frame_stride);
-    if constexpr (ROT & 1) fill_nv12_strip<ROT>(tile, yfr, cfr, nv, P, b, tid);
-    else if (VEC) fill_nv12_tables<ROT == 2>(tile, yfr, cfr, nv, P, b, tid);
-    else fill_nv12_scalar<ROT == 2>(tile, yfr, cfr, nv, P, b, tid);
+    POL::fill(tile, POL::template planes<FR>(plane0, extra..., P, b.f), extra..., P, b, tid);
     fill_column_halo(tile, b.trows, P.pitch, P.w, tid);
     store_moments(lap_part, b.lid, tid, band_phases<false>(tile, nullptr, P, b, tid, small, rowbuf));
 }
 
-// Planar 4:2:0 (I420; YV12 with the chroma pointers exchanged): k_preprocess_nv12 with the chroma fetched from two planes
-template <bool VEC, int ROT, Frames FR>
-__global__ __launch_bounds__(kThreads) void k_preprocess_i420(const uint8_t* __restrict__ yplane, I420Params ip, int n,
-                                                             PreParams P, uint8_t* __restrict__ small,
-                                                             float* __restrict__ rowbuf, long long* __restrict__ lap_part)
+// Aligned fast path: the band staged in registers (fill_staged, which also writes the column halo) and the resampling tables in LDS, fetched
+// ahead of the band's loads.
+template <typename POL, Frames FR, typename... Extra>
+__global__ __launch_bounds__(kThreads, 4) void k_preprocess_vec(const uint8_t* __restrict__ plane0, Extra... extra, int n,
+                                                               PreParams P, uint8_t* __restrict__ small,
+                                                               float* __restrict__ rowbuf,
+                                                               long long* __restrict__ lap_part)
 {
     extern __shared__ __align__(16) uint8_t tile[];
     Band b;
     if (!decode_band(P, n, b)) return;
     const int tid = threadIdx.x;
-    const uint8_t* yfr = frame_base<FR>(yplane, b.f, P.frame_stride);
-    const uint8_t* ufr = frame_base<FR>(ip.u, b.f, ip.c_frame_stride);
-    const uint8_t* vfr = frame_base<FR>(ip.v, b.f, ip.c_frame_stride);
-    if constexpr (ROT & 1) fill_i420_strip<ROT>(tile, yfr, ufr, vfr, ip, P, b, tid);
-    else if (VEC) fill_i420_tables<ROT == 2>(tile, yfr, ufr, vfr, ip, P, b, tid);
-    else fill_i420_scalar<ROT == 2>(tile, yfr, ufr, vfr, ip, P, b, tid);
-    fill_column_halo(tile, b.trows, P.pitch, P.w, tid);
-    store_moments(lap_part, b.lid, tid, band_phases<false>(tile, nullptr, P, b, tid, small, rowbuf));
+    LdsTabs* lt = reinterpret_cast<LdsTabs*>(tile + lds_tile_bytes(P.rows_per_band + 2, P.pitch));
+    fill_lds_tabs(lt, P, tid);
+    POL::fill(tile, POL::template planes<FR>(plane0, extra..., P, b.f), extra..., P, b, tid);
+    __syncthreads();
+    store_moments(lap_part, b.lid, tid, band_phases<true>(tile, lt, P, b, tid, small, rowbuf));
 }
 
 // 32x32 INTER_AREA cells from the per-row partials (vertical accumulation in cv2's row
@@ -1142,6 +1079,43 @@ static bool aligned_to(int a, const void* p, int64_t row_stride, int64_t frame_s
 }
 static bool aligned16(const void* p, int64_t row_stride, int64_t frame_stride) { return aligned_to(16, p, row_stride, frame_stride); }
 
+// ---- runtime values as template arguments (in the style of fb_dispatch_width): f receives std::integral_constant objects ----
+template <typename F>
+static auto dispatch_bool(bool v, F&& f) { return v ? f(std::true_type{}) : f(std::false_type{}); }
+
+// the NI classes band_plan yields, up to CAP: false = no staged kernel of that NI is built
+template <int CAP, int NI = 3, typename F>
+static bool dispatch_ni(int ni, F&& f)
+{
+    if (ni == NI) return f(std::integral_constant<int, NI>{}), true;
+    constexpr int next = NI == 3 ? 4 : NI == 4 ? 6 : NI == 6 ? 8 : 9;
+    if constexpr (next > NI && next <= CAP) return dispatch_ni<CAP, next>(ni, f);
+    return false;
+}
+
+// 4:2:0: f(VEC, ROT) for the six fills that are built -- a quarter turn has one fill whatever the alignment
+template <typename F>
+static void dispatch_turn(bool vec, int rot, F&& f)
+{
+    if (rot == 1) f(std::false_type{}, std::integral_constant<int, 1>{});
+    else if (rot == 3) f(std::false_type{}, std::integral_constant<int, 3>{});
+    else dispatch_bool(vec, [&](auto v) { rot == 2 ? f(v, std::integral_constant<int, 2>{}) : f(v, std::integral_constant<int, 0>{}); });
+}
+
+static constexpr bool is_staged(IngestKernel id) { return id == kIngestBgrStaged || id == kIngestRgbpStaged; }
+static constexpr bool has_gray_tables(IngestKernel id)
+{
+    return id == kIngestNv12Tables || id == kIngestNv12Strip || id == kIngestI420Tables || id == kIngestI420Strip;
+}
+
+// POL's kernel: the staged body for the staged fills, the generic one for every other
+template <typename POL, Frames FR, typename... Extra>
+static constexpr auto ingest_kernel()
+{
+    if constexpr (is_staged(POL::id)) return k_preprocess_vec<POL, FR, Extra...>;
+    else return k_preprocess<POL, FR, Extra...>;
+}
+
 // list (null: a strided clip): the clip's frames come from a device table of plane pointers -- d_in / d_uv / d_v are then the addresses of the
 // table's per-plane arrays (n entries each), and list->aligned says whether every frame allows the 16-byte fills (list_vec_eligible).
 int launch_preprocess(avd_ctx* ctx, const IngestClip& clip, const uint8_t* d_in, const uint8_t* d_uv, const uint8_t* d_v, const FrameTable* list)
@@ -1156,27 +1130,16 @@ int launch_preprocess(avd_ctx* ctx, const IngestClip& clip, const uint8_t* d_in,
     // bgr: no conversion constants -- BGR24 and the four layouts of RGB producers; planar: I420
     const bool bgr = !clip.is_420(), planar = clip.format == AVD_FMT_I420;
     const bool rgbp = clip.format == AVD_FMT_RGBP, px32 = clip.format == AVD_FMT_BGRA32 || clip.format == AVD_FMT_RGBA32;
-    const bool rgb24 = clip.format == AVD_FMT_RGB24;
-    // the planar chroma planes are read 8 bytes at a time (fill_i420_tables), every other plane 16
+    const bool rgb = clip.format == AVD_FMT_RGB24 || clip.format == AVD_FMT_RGBA32;     // packed pixels stored R, G, B
+    // the planar chroma planes are read 8 bytes at a time (I420's table fill), every other plane 16
     const bool chroma_ok = planar ? aligned_to(8, d_uv, clip.uv_row_stride, clip.uv_frame_stride) && aligned_to(8, d_v, clip.uv_row_stride, clip.uv_frame_stride)
                            : rgbp ? aligned16(d_uv, clip.uv_row_stride, clip.uv_frame_stride) && aligned16(d_v, clip.uv_row_stride, clip.uv_frame_stride)
                                   : bgr || aligned16(d_uv, clip.uv_row_stride, clip.uv_frame_stride);
     const bool vec = list ? list->aligned : P.w % 16 == 0 && aligned16(d_in, clip.row_stride, clip.frame_stride) && chroma_ok;
-    int ni = vec && (clip.format == AVD_FMT_BGR24 || rgb24 || rgbp) ? band_plan(P.w).ni : 0;
+    int ni = vec && bgr && !px32 ? band_plan(P.w).ni : 0;       // the layouts with a staged fill: BGR24, RGB24, RGBP
     // planar RGB: the byte gather needs a few registers more than BGR's alignbyte, and NI = 9 (2048 < w <= 4096) no longer fits the 128 VGPRs of
     // __launch_bounds__(256, 4) without spilling: those widths run the 16-byte fill
     if (rgbp && ni > 8) ni = 0;
-    auto launch = [&](IngestKernel id, auto kernel, size_t lds, auto... source) {
-        ctx->ingest_plan = IngestPlan{P.h, P.w, P.rows_per_band, P.nbands, P.pitch, ni, (int)lds, id};
-        ctx->ingest_plan_valid = 1;
-        ctx->ingest_rotate = clip.rotate;
-        ctx->ingest_format = clip.format;
-        ctx->ingest_range = !bgr && clip.full_range;
-        ctx->ingest_list[0] = list != nullptr;
-        ctx->ingest_list[1] = list ? n : 0;
-        hipLaunchKernelGGL(kernel, dim3(grid), dim3(kThreads), lds, ctx->stream, source..., n, P, ws.d_small + (size_t)ws.f0 * AVD_NPIX,
-                           ws.d_rowbuf + ws.rowbuf_off, ws.d_lap_part + ws.lappart_off);
-    };
     const int rot = clip.rotate;
     if (rot && bgr) { ctx->err = "internal error: a turned BGR clip reached the ingest launch"; return AVD_ERR_DEVICE; }
     if (clip.full_range && bgr) { ctx->err = "internal error: a full-range BGR clip reached the ingest launch"; return AVD_ERR_DEVICE; }
@@ -1193,76 +1156,51 @@ int launch_preprocess(avd_ctx* ctx, const IngestClip& clip, const uint8_t* d_in,
         }
         tabs = lds_nvtab_off(P.rows_per_band + 2, P.pitch) + lds_nvtab_bytes(yc.ntab);
     }
-    // one selection for both sources of the frame base: the same fills under the same ids
-    auto select = [&](auto frames_tag) -> int {
-        constexpr Frames FR = decltype(frames_tag)::value;
-        if (planar) {
-            I420Params ip{};
-            ip.u = d_uv; ip.v = d_v; ip.c_row_stride = clip.uv_row_stride; ip.c_frame_stride = clip.uv_frame_stride;
-            ip.k = yc;
-            if (rot == 1) launch(kIngestI420Strip, k_preprocess_i420<false, 1, FR>, tabs, d_in, ip);
-            else if (rot == 3) launch(kIngestI420Strip, k_preprocess_i420<false, 3, FR>, tabs, d_in, ip);
-            else if (rot == 2 && vec) launch(kIngestI420Tables, k_preprocess_i420<true, 2, FR>, tabs, d_in, ip);
-            else if (rot == 2) launch(kIngestI420Scalar, k_preprocess_i420<false, 2, FR>, tile, d_in, ip);
-            else if (vec) launch(kIngestI420Tables, k_preprocess_i420<true, 0, FR>, tabs, d_in, ip);
-            else launch(kIngestI420Scalar, k_preprocess_i420<false, 0, FR>, tile, d_in, ip);
-        } else if (!bgr) {
-            Nv12Params nv{};
-            nv.uv = d_uv; nv.uv_row_stride = clip.uv_row_stride; nv.uv_frame_stride = clip.uv_frame_stride;
-            nv.k = yc;
-            // (a register-staged variant in the style of k_preprocess_vec measured no faster: the kernel is bound by the
-            // conversion's integer arithmetic, not by how its loads are issued -- profiles/r02_experiments.md)
-            if (rot == 1) launch(kIngestNv12Strip, k_preprocess_nv12<false, 1, FR>, tabs, d_in, nv);
-            else if (rot == 3) launch(kIngestNv12Strip, k_preprocess_nv12<false, 3, FR>, tabs, d_in, nv);
-            else if (rot == 2 && vec) launch(kIngestNv12Tables, k_preprocess_nv12<true, 2, FR>, tabs, d_in, nv);
-            else if (rot == 2) launch(kIngestNv12Scalar, k_preprocess_nv12<false, 2, FR>, tile, d_in, nv);
-            else if (vec) launch(kIngestNv12Tables, k_preprocess_nv12<true, 0, FR>, tabs, d_in, nv);
-            else launch(kIngestNv12Scalar, k_preprocess_nv12<false, 0, FR>, tile, d_in, nv);
-        } else if (rgbp) {
-            RgbpParams rp{};
-            rp.g = d_uv; rp.b = d_v;
-            const size_t lds = tile + sizeof(LdsTabs);
-            switch (ni) {                              // BGR's band plan and NI classes: the chunk has the same register footprint
-            case 3: launch(kIngestRgbpStaged, k_preprocess_rgbp_vec<3, FR>, lds, d_in, rp); return 0;
-            case 4: launch(kIngestRgbpStaged, k_preprocess_rgbp_vec<4, FR>, lds, d_in, rp); return 0;
-            case 6: launch(kIngestRgbpStaged, k_preprocess_rgbp_vec<6, FR>, lds, d_in, rp); return 0;
-            case 8: launch(kIngestRgbpStaged, k_preprocess_rgbp_vec<8, FR>, lds, d_in, rp); return 0;
-            case 0: break;
-            default: ctx->err = "internal error: the band plan asks for a k_preprocess_rgbp_vec that is not built"; return AVD_ERR_DEVICE;
-            }
-            if (vec) launch(kIngestRgbpVec16, k_preprocess_rgbp<true, FR>, tile, d_in, rp);
-            else launch(kIngestRgbpScalar, k_preprocess_rgbp<false, FR>, tile, d_in, rp);
-        } else if (px32) {
-            const bool rgba = clip.format == AVD_FMT_RGBA32;
-            if (vec && rgba) launch(kIngestPx32Vec16, k_preprocess<true, AVD_FMT_RGBA32, FR>, tile, d_in);
-            else if (vec) launch(kIngestPx32Vec16, k_preprocess<true, AVD_FMT_BGRA32, FR>, tile, d_in);
-            else if (rgba) launch(kIngestPx32Scalar, k_preprocess<false, AVD_FMT_RGBA32, FR>, tile, d_in);
-            else launch(kIngestPx32Scalar, k_preprocess<false, AVD_FMT_BGRA32, FR>, tile, d_in);
-        } else if (ni) {
-            const size_t lds = tile + sizeof(LdsTabs);
-            // BGR24 and RGB24: the same band plan, the same NI, the same ids
-            auto staged = [&](auto rgb_tag) -> bool {
-                constexpr bool RGB = decltype(rgb_tag)::value;
-                switch (ni) {
-                case 3: launch(kIngestBgrStaged, k_preprocess_vec<3, RGB, FR>, lds, d_in); return true;
-                case 4: launch(kIngestBgrStaged, k_preprocess_vec<4, RGB, FR>, lds, d_in); return true;
-                case 6: launch(kIngestBgrStaged, k_preprocess_vec<6, RGB, FR>, lds, d_in); return true;
-                case 8: launch(kIngestBgrStaged, k_preprocess_vec<8, RGB, FR>, lds, d_in); return true;
-                case 9: launch(kIngestBgrStaged, k_preprocess_vec<9, RGB, FR>, lds, d_in); return true;
-                default: return false;
-                }
-            };
-            if (!(rgb24 ? staged(std::true_type{}) : staged(std::false_type{}))) {
-                ctx->err = "internal error: the band plan asks for a k_preprocess_vec that is not built";
-                return AVD_ERR_DEVICE;
-            }
-        } else if (vec && rgb24) launch(kIngestBgrVec16, k_preprocess<true, AVD_FMT_RGB24, FR>, tile, d_in);
-        else if (vec) launch(kIngestBgrVec16, k_preprocess<true, AVD_FMT_BGR24, FR>, tile, d_in);
-        else if (rgb24) launch(kIngestBgrScalar, k_preprocess<false, AVD_FMT_RGB24, FR>, tile, d_in);
-        else launch(kIngestBgrScalar, k_preprocess<false, AVD_FMT_BGR24, FR>, tile, d_in);
-        return 0;
+    // the launch of policy POL: its kernel body and LDS follow its id, the source of the frame bases follows `list`
+    auto launch = [&](auto pol, auto... extra) {
+        using POL = decltype(pol);
+        const size_t lds = is_staged(POL::id) ? tile + sizeof(LdsTabs) : has_gray_tables(POL::id) ? tabs : tile;
+        IngestRecord& rec = ctx->ingest;
+        rec.plan = IngestPlan{P.h, P.w, P.rows_per_band, P.nbands, P.pitch, ni, (int)lds, POL::id};
+        rec.launched = 1;
+        rec.rotate = clip.rotate;
+        rec.format = clip.format;
+        rec.range = !bgr && clip.full_range;
+        rec.list[0] = list != nullptr;
+        rec.list[1] = list ? n : 0;
+        dispatch_bool(list != nullptr, [&](auto listed) {
+            constexpr Frames FR = decltype(listed)::value ? Frames::listed : Frames::strided;
+            auto kernel = ingest_kernel<POL, FR, decltype(extra)...>();
+            hipLaunchKernelGGL(kernel, dim3(grid), dim3(kThreads), lds, ctx->stream, d_in, extra..., n, P, ws.d_small + (size_t)ws.f0 * AVD_NPIX,
+                               ws.d_rowbuf + ws.rowbuf_off, ws.d_lap_part + ws.lappart_off);
+        });
     };
-    if (int e = list ? select(std::integral_constant<Frames, Frames::listed>{}) : select(std::integral_constant<Frames, Frames::strided>{})) return e;
+    bool built = true;                                 // false: the band plan's NI has no staged kernel
+    if (planar) {
+        const I420Params ip{d_uv, d_v, clip.uv_row_stride, clip.uv_frame_stride, yc};
+        dispatch_turn(vec, rot, [&](auto v, auto r) { launch(I420<decltype(v)::value, decltype(r)::value>{}, ip); });
+    } else if (!bgr) {
+        // (a register-staged variant in the style of k_preprocess_vec measured no faster: the kernel is bound by the
+        // conversion's integer arithmetic, not by how its loads are issued -- profiles/r02_experiments.md)
+        const Nv12Params nv{d_uv, clip.uv_row_stride, clip.uv_frame_stride, yc};
+        dispatch_turn(vec, rot, [&](auto v, auto r) { launch(Nv12<decltype(v)::value, decltype(r)::value>{}, nv); });
+    } else if (rgbp) {
+        const RgbpParams rp{d_uv, d_v};
+        // BGR's band plan and NI classes: the chunk has the same register footprint
+        if (ni) built = dispatch_ni<8>(ni, [&](auto k) { launch(RgbpStaged<decltype(k)::value>{}, rp); });
+        else dispatch_bool(vec, [&](auto v) { launch(Rgbp<decltype(v)::value>{}, rp); });
+        if (!built) ctx->err = "internal error: the band plan asks for a k_preprocess_rgbp_vec that is not built";
+    } else if (ni) {                                   // BGR24 and RGB24: the same band plan, the same NI, the same ids
+        built = dispatch_bool(rgb, [&](auto o) { return dispatch_ni<kMaxNI>(ni, [&](auto k) { launch(PackedStaged<decltype(k)::value, decltype(o)::value>{}); }); });
+        if (!built) ctx->err = "internal error: the band plan asks for a k_preprocess_vec that is not built";
+    } else
+        dispatch_bool(vec, [&](auto v) {
+            dispatch_bool(rgb, [&](auto o) {
+                if (px32) launch(Packed<decltype(v)::value, decltype(o)::value, 4>{});
+                else launch(Packed<decltype(v)::value, decltype(o)::value, 3>{});
+            });
+        });
+    if (!built) return AVD_ERR_DEVICE;
     HIP_TRY(ctx, hipGetLastError());
     return 0;
 }

@@ -443,7 +443,7 @@ int avd_stage_ms(avd_ctx* ctx, int stage, float* ms);
  * iteration).  bench.py's roofline.kernels is built from these, with clips run alone.  A call with more kernel regions than the library
  * records (96: ~40 clips in one batch) makes avd_kernel_ms fail rather than report partial sums. */
 enum avd_kernel_id {
-    AVD_K_PREPROCESS = 0,  /* k_preprocess_vec / k_preprocess_nv12 / k_preprocess_i420 (+ staging copies of host input) */
+    AVD_K_PREPROCESS = 0,  /* k_preprocess_vec / k_preprocess, whatever the layout (+ staging copies of host input) */
     AVD_K_HASH,            /* k_hash: 32 x 32 INTER_AREA cells, mean threshold, moment reduction */
     AVD_K_PYRAMID,         /* k_pyramid_all: Gaussian blur + decimation, four scales */
     AVD_K_POLYEXP,         /* k_polyexp_all: polynomial expansion, four scales */
@@ -460,7 +460,7 @@ int avd_kernel_ms(avd_ctx* ctx, int kernel_id, float* ms);
  * name: "area" uint8[n][1024]; "pyr<L>" float[n][hL][wL]; "poly<L>" float[n][hL][wL][5];
  * "flow<L>" float[n-1][2][hL][wL] (planar, after the last iteration at level L).
  * "ingest_plan" int32[8], host state rather than a device buffer: what the last ingest launch of the context ran --
- * h, w, rows_per_band, nbands, LDS tile pitch, NI of k_preprocess_vec / k_preprocess_rgbp_vec (0: another kernel), dynamic LDS bytes requested,
+ * h, w, rows_per_band, nbands, LDS tile pitch, NI of k_preprocess_vec, the staged kernel of BGR24 / RGB24 / RGBP (0: the generic kernel), dynamic LDS bytes requested,
  * kernel (0 bgr_scalar, 1 bgr_vec16, 2 bgr_staged, 3 nv12_scalar, 4 nv12_tables, 5 i420_scalar, 6 i420_tables, 7 nv12_strip, 8 i420_strip, 9 px32_scalar, 10 px32_vec16, 11 rgbp_scalar, 12 rgbp_vec16, 13 rgbp_staged;
  * a half turn runs the flipped instantiations of 3 .. 6 under the same ids; AVD_FMT_RGB24 runs 0 .. 2 with its own coefficient constants, BGRA32 and
  * RGBA32 share 9 and 10: "ingest_format" tells them apart); h, w are the displayed picture's; an error before any ingest launch.

@@ -1,4 +1,4 @@
-"""Planar 4:2:0 (I420) ingest: k_preprocess_i420 and the avd_*_i420 entry points (include/avd.h).
+"""Planar 4:2:0 (I420) ingest: k_preprocess with the I420 fill policy and the avd_*_i420 entry points (include/avd.h).
 
 The arithmetic is the NV12 kernels' -- swscale's tables, nearest chroma, cv2's gray -- so every result is compared BIT FOR BIT: with the
 CPU oracle (NV12 -> BGR, then the BGR oracle) on the interleaved form of the same planes, and with the NV12 entry points.  There is no

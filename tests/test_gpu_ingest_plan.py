@@ -1,7 +1,7 @@
 """The ingest kernels (avd_preprocess.hip) over every class of the band plan and every alignment the launcher tells apart.
 
-k_preprocess, k_preprocess_vec<NI> and k_preprocess_nv12 share decode_band, the fills, band_phases and store_moments; which fill
-runs and how many rows a band has follow from the width alone (band_plan) and from the 16-byte alignment of the input
+The generic kernel k_preprocess and the staged kernel k_preprocess_vec (NI row chunks per lane) are written once and templated on a
+fill policy per layout; which fill runs and how many rows a band has follow from the width alone (band_plan) and from the 16-byte alignment of the input
 (launch_preprocess).  Every case here names the kernel and the rows per band it was written for and reads both back from the
 "ingest_plan" debug buffer, so a sweep that silently took another kernel fails instead of passing.
 
@@ -228,8 +228,8 @@ def _sweep_draws():
 
 @pytest.mark.parametrize("n,h,w", _sweep_draws())
 def test_vector_paths_random_geometries(ctx, oracle, n, h, w):
-    """Widths that are multiples of 16 (the existing random sweep draws none): the staged kernel up to 4096 px, k_preprocess<true>
-    above, and the NV12 table fill on the draws of even height."""
+    """Widths that are multiples of 16 (the existing random sweep draws none): the staged kernel up to 4096 px, the generic kernel's 16-byte
+    fill above, and the NV12 table fill on the draws of even height."""
     frames = synth.random_frames(n, h, w, seed=h * 1000 + w)
     got = ctx.preprocess_bgr(frames)
     assert _plan(ctx)[P_KERNEL] == (BGR_STAGED if w <= 4096 else BGR_VEC16), (h, w)

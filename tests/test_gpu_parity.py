@@ -21,8 +21,8 @@ GEOMS = [
     (2, 64, 64),        # 2x2 area-fast for the hash as well
     (2, 96, 128),       # integer scales 3x4 -> area-fast general
     (2, 240, 426),      # upscaling in y for the 320x320 resize
-    (2, 45, 832),       # k_preprocess_vec<4>: 4 tile rows per pass, bands 14/14/14/3
-    (1, 37, 4112),      # aligned but wider than the staged kernel: k_preprocess<true>, 9-row bands, a one-row last band
+    (2, 45, 832),       # k_preprocess_vec, NI = 4: 4 tile rows per pass, bands 14/14/14/3
+    (1, 37, 4112),      # aligned but wider than the staged kernel: k_preprocess with the 16-byte fill, 9-row bands, a one-row last band
 ]
 
 

@@ -329,6 +329,28 @@ def test_device_lists(ctx, oracle, fmt, misalign):
     assert ctx.stage_bytes() == 0 and ctx.stage_copies() == 0
 
 
+# The listed instantiations of the plan classes that no other case of the suite launches (the lists above and those of
+# tests/test_gpu_framelist.py are 64 px wide or BGR's first width per fill): layout, kernel, NI, width, rows per band.  Two frames of the
+# smallest height above the minimum, the first width of the class (RGB24_PLANS / RGBP_PLANS).
+LISTED_PLANS = [
+    (BGR, BGR_STAGED, 4, 688, 14), (BGR, BGR_STAGED, 8, 1376, 14),
+    (RGB24, BGR_STAGED, 4, 688, 14), (RGB24, BGR_STAGED, 6, 1040, 14), (RGB24, BGR_STAGED, 8, 1376, 14), (RGB24, BGR_STAGED, 9, 2064, 7),
+    (RGB24, BGR_VEC16, 0, 4112, 9),
+    (RGBP, RGBP_STAGED, 4, 688, 14), (RGBP, RGBP_STAGED, 6, 1040, 14), (RGBP, RGBP_STAGED, 8, 1376, 14), (RGBP, RGBP_VEC16, 0, 4112, 9),
+]
+
+
+@pytest.mark.parametrize("fmt,kernel,ni,w,rows", LISTED_PLANS, ids=[f"{NAMES[c[0]]}-k{c[1]}-ni{c[2]}-w{c[3]}" for c in LISTED_PLANS])
+def test_host_lists_plan_classes(ctx, oracle, fmt, kernel, ni, w, rows):
+    h = 33
+    B = synth.random_frames(2, h, w, seed=h * 7 + w + fmt)
+    frames = [np.ascontiguousarray(f) for f in arrange(B, fmt)]
+    got = ctx.preprocess_frame_list(frames, fmt)
+    assert ctx.ingest_list() == (1, 2)
+    _check_plan(ctx, fmt, h, w, kernel, rows, ni)
+    _check_outputs(ctx, oracle, got, B, (NAMES[fmt], "host list", w))
+
+
 # ---- batches ---------------------------------------------------------------------------------------------------------------------------------
 def _mixed_clips():
     """BGR, NV12, I420 and the four new layouts at two geometries, with B of each RGB-family clip"""

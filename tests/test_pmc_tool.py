@@ -43,3 +43,21 @@ def test_summary_of_separate_passes(tmp_path):
     # per clip: the pyramid kernel runs exactly once per clip
     assert res["farneback_stage"]["clips_in_trace"] == 1
     assert abs(res["farneback_stage"]["hbm_bytes"] - (2 * k[name_plain]["hbm_bytes"] + up_bytes + 2 * 1024 * 100 + 1024 * 50)) < 1e-6
+
+
+def test_nv12_short_name_in_both_spellings(tmp_path):
+    """The key bench.py reads, k_preprocess_nv12, collects the NV12 ingest under the kernel template it once had and as the generic kernel
+    with the Nv12 fill policy; another layout's instantiation of the generic kernel stays out of it."""
+    old = "void (anonymous namespace)::k_preprocess_nv12<true, 0, (anonymous namespace)::Frames::strided>(unsigned char const*, Nv12Params, int)"
+    new = ("void (anonymous namespace)::k_preprocess<(anonymous namespace)::Nv12<true, 0>, (anonymous namespace)::Frames::strided, "
+           "(anonymous namespace)::Nv12Params>(unsigned char const*, (anonymous namespace)::Nv12Params, int)")
+    other = ("void (anonymous namespace)::k_preprocess<(anonymous namespace)::I420<true, 0>, (anonymous namespace)::Frames::strided, "
+             "(anonymous namespace)::I420Params>(unsigned char const*, (anonymous namespace)::I420Params, int)")
+    for case, name in (("old", old), ("new", new)):
+        rows = [(name, "FETCH_SIZE", 3000), (name, "WRITE_SIZE", 20), (other, "FETCH_SIZE", 7000), (other, "WRITE_SIZE", 70)]
+        _write_pass(str(tmp_path / case / "x"), rows)
+        out = str(tmp_path / (case + ".json"))
+        subprocess.run([sys.executable, os.path.join(ROOT, "tools", "pmc_to_json.py"), out, "test", str(tmp_path / case)], check=True, capture_output=True)
+        res = json.load(open(out))
+        assert res["k_preprocess_nv12"]["hbm_bytes"] == 2 * 1024 * 3000 + 1024 * 20 and res["k_preprocess_nv12"]["launches"] == 1, case
+        assert "k_preprocess_vec" not in res, case
