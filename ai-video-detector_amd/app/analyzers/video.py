@@ -50,7 +50,7 @@ def analyze(path: str, meta: dict):
         # stored pictures with a display rotation (src.width / src.height are the displayed picture's): the turn happens on the GPU too
         turn = {"rotate": int(src.rotate)} if getattr(src, "rotate", 0) else {}
         # full-range pictures (yuvj420p): converted with libswscale's full-range tables, on the GPU too; a source that yields BGR has none
-        if surface in ("nv12", "i420") and getattr(src, "full_range", False):
+        if surface in ("nv12", "i420", "i422") and getattr(src, "full_range", False):
             turn["full_range"] = True
 
         def frames():
@@ -69,6 +69,8 @@ def analyze(path: str, meta: dict):
                 rec = fa.records_stream_nv12(frames(), **turn)
             elif surface == "i420":
                 rec = fa.records_stream_i420(frames(), **turn)
+            elif surface == "i422":                          # (a turned 4:2:2 picture is refused by the library)
+                rec = fa.records_stream_i422(frames(), **turn)
             elif surface in _RGB_SURFACES:
                 rec = fa.records_stream(frames(), _RGB_SURFACES[surface])
             else:

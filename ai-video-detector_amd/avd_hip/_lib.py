@@ -68,20 +68,38 @@ AVD_FMT_BGR24, AVD_FMT_NV12, AVD_FMT_I420 = 0, 1, 2
 AVD_FMT_FULL_RANGE = 0x100      # flag OR-ed into a 4:2:0 layout: the samples use 0 .. 255 (ffmpeg's yuvj420p)
 # what RGB producers hand over (include/avd.h): R,G,B interleaved; B,G,R,x and R,G,B,x with an ignored fourth byte; three planes R, G, B
 AVD_FMT_RGB24, AVD_FMT_BGRA32, AVD_FMT_RGBA32, AVD_FMT_RGBP = 0x10, 0x11, 0x12, 0x13
-_PACKED = {AVD_FMT_BGR24: 3, AVD_FMT_RGB24: 3, AVD_FMT_BGRA32: 4, AVD_FMT_RGBA32: 4}      # one interleaved plane: bytes per pixel
-_FMT_PLANES = {AVD_FMT_BGR24: 1, AVD_FMT_NV12: 2, AVD_FMT_I420: 3, AVD_FMT_RGB24: 1, AVD_FMT_BGRA32: 1, AVD_FMT_RGBA32: 1, AVD_FMT_RGBP: 3}
+# 4:2:2 (include/avd.h): Y0 U Y1 V and U Y0 V Y1 packed, 2 bytes per pixel; planar Y, U, V with chroma planes [H][W/2]; Y and interleaved U,V [H][W]
+AVD_FMT_YUYV422, AVD_FMT_UYVY422, AVD_FMT_I422, AVD_FMT_NV16 = 0x20, 0x21, 0x22, 0x23
+# one interleaved plane: bytes per pixel
+_PACKED = {AVD_FMT_BGR24: 3, AVD_FMT_RGB24: 3, AVD_FMT_BGRA32: 4, AVD_FMT_RGBA32: 4, AVD_FMT_YUYV422: 2, AVD_FMT_UYVY422: 2}
+_FMT_PLANES = {AVD_FMT_BGR24: 1, AVD_FMT_NV12: 2, AVD_FMT_I420: 3, AVD_FMT_RGB24: 1, AVD_FMT_BGRA32: 1, AVD_FMT_RGBA32: 1, AVD_FMT_RGBP: 3,
+               AVD_FMT_YUYV422: 1, AVD_FMT_UYVY422: 1, AVD_FMT_I422: 3, AVD_FMT_NV16: 2}
+_YUV_PLANES = (AVD_FMT_NV12, AVD_FMT_I420, AVD_FMT_I422, AVD_FMT_NV16)      # clips handed over as a tuple of planes
+_FMT_NAMES = ("AVD_FMT_BGR24, AVD_FMT_NV12, AVD_FMT_I420, AVD_FMT_RGB24, AVD_FMT_BGRA32, AVD_FMT_RGBA32, AVD_FMT_RGBP, AVD_FMT_YUYV422, "
+              "AVD_FMT_UYVY422, AVD_FMT_I422 or AVD_FMT_NV16")
+
+
+def _chroma_shape(fmt: int, h: int, w: int):
+    """rows and bytes per row of a chroma plane: 4:2:0 halves the rows, the planar layouts halve the row"""
+    return (h if fmt in (AVD_FMT_I422, AVD_FMT_NV16) else h // 2, w // 2 if fmt in (AVD_FMT_I420, AVD_FMT_I422) else w)
 
 
 class Pixels:
     """A clip tagged with its layout, accepted wherever a clip is (preprocess_picture, analyze_pictures, analyze_pictures_async):
     data uint8[N,H,W,3] for AVD_FMT_RGB24 (and AVD_FMT_BGR24), uint8[N,H,W,4] for AVD_FMT_BGRA32 / AVD_FMT_RGBA32, uint8[N,3,H,W] for
-    AVD_FMT_RGBP (channels first, R,G,B: what torchcodec and torchvision.io decode to); numpy or torch, host or device.  An untagged array
-    remains BGR, tuples remain NV12 / I420."""
+    AVD_FMT_RGBP (channels first, R,G,B: what torchcodec and torchvision.io decode to), uint8[N,H,W,2] for the packed 4:2:2 layouts
+    AVD_FMT_YUYV422 / AVD_FMT_UYVY422; a tuple of planes for AVD_FMT_I422 (y uint8[N,H,W], u and v uint8[N,H,W/2]) and AVD_FMT_NV16
+    (y, uv uint8[N,H,W]); numpy or torch, host or device.  An untagged array remains BGR, untagged tuples remain NV12 / I420."""
     __slots__ = ("data", "fmt")
 
     def __init__(self, data, fmt: int):
-        if fmt not in _PACKED and fmt != AVD_FMT_RGBP:
-            raise ValueError(f"fmt must be AVD_FMT_BGR24, AVD_FMT_RGB24, AVD_FMT_BGRA32, AVD_FMT_RGBA32 or AVD_FMT_RGBP, got {fmt!r}")
+        if fmt not in _PACKED and fmt not in (AVD_FMT_RGBP, AVD_FMT_I422, AVD_FMT_NV16):
+            raise ValueError("fmt must be AVD_FMT_BGR24, AVD_FMT_RGB24, AVD_FMT_BGRA32, AVD_FMT_RGBA32, AVD_FMT_RGBP, AVD_FMT_YUYV422, AVD_FMT_UYVY422, "
+                             f"AVD_FMT_I422 or AVD_FMT_NV16, got {fmt!r}")
+        if fmt in (AVD_FMT_I422, AVD_FMT_NV16):
+            data = tuple(data)
+            if len(data) != _FMT_PLANES[fmt]:
+                raise ValueError(f"an {'AVD_FMT_I422' if fmt == AVD_FMT_I422 else 'AVD_FMT_NV16'} clip is a tuple of {_FMT_PLANES[fmt]} planes")
         self.data, self.fmt = data, fmt
 
 
@@ -328,11 +346,15 @@ class Context:
 
     # -- 4:2:0 planes.  NV12 (decoder surfaces): y uint8[N,H,W], uv uint8[N,H/2,W] with U,V interleaved.  I420 (planar, software decoders):
     # y uint8[N,H,W], u and v uint8[N,H/2,W/2]; YV12 = the same calls with u and v exchanged -------------------------------------------
-    def _plane_ptrs(self, planes):
-        """planes: an NV12 pair (y, uv) or an I420 triple (y, u, v), numpy or torch -> _Clip.  Strided views are passed
+    def _plane_ptrs(self, planes, fmt=None):
+        """planes: an NV12 pair (y, uv) or an I420 triple (y, u, v), numpy or torch -> _Clip; fmt AVD_FMT_NV16 / AVD_FMT_I422: the same with
+        chroma planes of H rows.  Strided views are passed
         as they are (a decoder's pitch, planes cut out of one buffer per clip); U and V must share their strides (the C-ABI has one pair for both)."""
         nv12 = len(planes) == 2
-        layout = "uint8[N,H,W] and uint8[N,H/2,W]" if nv12 else "uint8[N,H,W], uint8[N,H/2,W/2] and uint8[N,H/2,W/2]"
+        if fmt is None:
+            fmt = AVD_FMT_NV12 if nv12 else AVD_FMT_I420
+        ch = "H/2" if fmt in (AVD_FMT_NV12, AVD_FMT_I420) else "H"
+        layout = f"uint8[N,H,W] and uint8[N,{ch},W]" if nv12 else f"uint8[N,H,W], uint8[N,{ch},W/2] and uint8[N,{ch},W/2]"
         torch_in = [_is_torch_tensor(p) for p in planes]
         if any(torch_in) != all(torch_in):
             raise ValueError("both planes must be numpy arrays or both torch tensors" if nv12 else
@@ -357,15 +379,16 @@ class Context:
             st.append((r, f if p.shape[0] > 1 else p.shape[1] * r))
         n, h, w = (int(d) for d in planes[0].shape)
         got = [tuple(p.shape) for p in planes[1:]]
-        if nv12 and got != [(n, h // 2, w)]:
-            raise ValueError(f"chroma plane must be uint8[{n},{h // 2},{w}] (interleaved U,V), got {got[0]}")
-        if not nv12 and got != [(n, h // 2, w // 2)] * 2:
-            raise ValueError(f"chroma planes must be uint8[{n},{h // 2},{w // 2}] each, got {got[0]} and {got[1]}")
+        crows, cbytes = _chroma_shape(fmt, h, w)
+        if nv12 and got != [(n, crows, cbytes)]:
+            raise ValueError(f"chroma plane must be uint8[{n},{crows},{cbytes}] (interleaved U,V), got {got[0]}")
+        if not nv12 and got != [(n, crows, cbytes)] * 2:
+            raise ValueError(f"chroma planes must be uint8[{n},{crows},{cbytes}] each, got {got[0]} and {got[1]}")
         if not nv12 and st[1] != st[2]:
             raise ValueError(f"the U and V planes must have the same row and frame strides, got {st[1]} and {st[2]}")
         if cuda:
             self._after_torch_stream(planes[0])
-        return _Clip(AVD_FMT_NV12 if nv12 else AVD_FMT_I420, tuple(ptr(p) for p in planes), AVD_MEM_DEVICE if cuda else AVD_MEM_HOST, n, h, w,
+        return _Clip(fmt, tuple(ptr(p) for p in planes), AVD_MEM_DEVICE if cuda else AVD_MEM_HOST, n, h, w,
                      tuple(r for r, _ in st), tuple(f for _, f in st), planes)
 
     def _nv12_ptrs(self, y, uv):
@@ -388,6 +411,8 @@ class Context:
         fmt = px.fmt
         if fmt == AVD_FMT_BGR24:
             return self._bgr(px.data)
+        if fmt in (AVD_FMT_I422, AVD_FMT_NV16):
+            return self._plane_ptrs(px.data, fmt)
         torch_in = _is_torch_tensor(px.data)
         a = px.data if torch_in else np.asarray(px.data)
         strides, ptr, dense = _TORCH_PLANE if torch_in else _NUMPY_PLANE
@@ -487,8 +512,8 @@ class Context:
     # -- pictures by descriptor (include/avd.h: avd_picture): any format, with a display rotation -------------------------------------------
     def _picture(self, clip, rotate: int = 0, full_range: bool = False):
         """clip: a BGR frame stack uint8[N,H,W,3], an NV12 pair (y, uv) or an I420 triple (y, u, v) of the STORED picture, or a tagged clip
-        (Pixels: RGB, BGRA, RGBA, planar RGB); numpy or torch.
-        full_range: AVD_FMT_FULL_RANGE is OR-ed into the format (the library refuses it on BGR).
+        (Pixels: RGB, BGRA, RGBA, planar RGB, the four 4:2:2 layouts); numpy or torch.
+        full_range: AVD_FMT_FULL_RANGE is OR-ed into the format (the library refuses it on BGR and RGB).
         -> (AvdPicture, frame count, keepalive).  The binding's own checks (the rotation, U and V of equal strides, planes all numpy or all
         torch) are made before the library is touched."""
         if isinstance(rotate, bool) or not isinstance(rotate, (int, np.integer)) or not 0 <= rotate <= 3:
@@ -503,7 +528,7 @@ class Context:
 
     def preprocess_picture(self, clip, rotate: int = 0, full_range: bool = False):
         """-> (small320, hash1024, lap_sum, lap_sumsq) of the DISPLAYED picture, as preprocess_bgr / _nv12 / _i420 on the turned planes;
-        full_range: the 4:2:0 samples use 0 .. 255 and are converted as libswscale converts yuvj420p."""
+        full_range: the 4:2:0 / 4:2:2 samples use 0 .. 255 and are converted as libswscale converts yuvj420p."""
         p, n, keep = self._picture(clip, rotate, full_range)
         return self._outputs_call("avd_preprocess_picture", (C.byref(p),), n)
 
@@ -524,7 +549,7 @@ class Context:
 
     def analyze_pictures(self, clips, rotates=None, full_ranges=None):
         """A batch by descriptor: BGR stacks, NV12 pairs and I420 triples in any mix, each with its rotation (default 0) and its range
-        (default limited; True = full range, 4:2:0 clips only).  -> list of record arrays, one per clip, identical to one call per clip."""
+        (default limited; True = full range, 4:2:0 and 4:2:2 clips only).  -> list of record arrays, one per clip, identical to one call per clip."""
         arr, counts, keep = self._picture_array(clips, rotates, full_ranges)
         rec = self._records_call("avd_analyze_pictures", (arr, len(clips)), sum(counts))
         return list(np.split(rec, np.cumsum(counts)[:-1])) if counts else []
@@ -538,15 +563,15 @@ class Context:
     # -- clips as lists of separately allocated frames (include/avd_frame_list.h) ---------------------------------------------------------
     def _frame_list(self, frames, fmt: int, rotate: int = 0, full_range: bool = False):
         """frames: a sequence of per-frame arrays -- BGR or RGB uint8[H,W,3], BGRA / RGBA uint8[H,W,4], planar RGB uint8[3,H,W], NV12 pairs
-        (y uint8[H,W], uv uint8[H/2,W]) or I420 triples (y, u, v) -- all
+        (y uint8[H,W], uv uint8[H/2,W]) or I420 triples (y, u, v), packed 4:2:2 uint8[H,W,2], I422 triples (y, u and v uint8[H,W/2]) or NV16
+        pairs (y, uv uint8[H,W]) -- all
         numpy arrays (host) or all torch tensors on one device; every frame where it lies, nothing is gathered.  A plane's rows must be dense
         and all frames of the list share the row stride of each plane: anything else raises ValueError (there is no silent copy).
         -> (AvdFrameList, frame count, what the library reads: the pointer arrays during the call, the frames until it is drained)"""
         if isinstance(rotate, bool) or not isinstance(rotate, (int, np.integer)) or not 0 <= rotate <= 3:
             raise ValueError(f"rotate must be 0, 1, 2 or 3 quarter turns (clockwise, stored to displayed picture), got {rotate!r}")
         if fmt not in _FMT_PLANES:
-            raise ValueError("fmt must be AVD_FMT_BGR24, AVD_FMT_NV12, AVD_FMT_I420, AVD_FMT_RGB24, AVD_FMT_BGRA32, AVD_FMT_RGBA32 or AVD_FMT_RGBP, "
-                             f"got {fmt!r}")
+            raise ValueError(f"fmt must be {_FMT_NAMES}, got {fmt!r}")
         nplanes = _FMT_PLANES[fmt]
         px = _PACKED.get(fmt, 1)                               # bytes per pixel of plane 0
         if fmt == AVD_FMT_RGBP:                                # a [3,H,W] frame contributes its three channel views as planes
@@ -565,7 +590,7 @@ class Context:
         if not frames:                                         # an empty list has no picture to take a size from: any valid one
             L.h = L.w = HASH
             for p in range(nplanes):
-                L.row_stride[p] = HASH * px if p == 0 else (HASH // 2 if fmt == AVD_FMT_I420 else HASH)
+                L.row_stride[p] = HASH * px if p == 0 else _chroma_shape(fmt, HASH, HASH)[1]
             return L, 0, ()
         torch_in = [_is_torch_tensor(p) for f in frames for p in f]
         if any(torch_in) != all(torch_in):
@@ -584,8 +609,10 @@ class Context:
                 raise ValueError("the frames of a list are uint8 arrays")
             strides, ptr, _ = _NUMPY_PLANE
         h, w = int(frames[0][0].shape[0]), int(frames[0][0].shape[1])
-        shapes = {AVD_FMT_NV12: [(h, w), (h // 2, w)], AVD_FMT_I420: [(h, w), (h // 2, w // 2), (h // 2, w // 2)],
-                  AVD_FMT_RGBP: [(h, w)] * 3}.get(fmt, [(h, w, px)])
+        if fmt in _YUV_PLANES:
+            shapes = [(h, w)] + [_chroma_shape(fmt, h, w)] * (nplanes - 1)
+        else:
+            shapes = [(h, w)] * 3 if fmt == AVD_FMT_RGBP else [(h, w, px)]
         arrays = []
         for p in range(nplanes):
             dense = (px, 1) if fmt in _PACKED else (1,)

@@ -222,7 +222,7 @@ class FrameAnalyzer:
 
     def records_stream(self, frames: Iterable[np.ndarray], fmt: int = _lib.AVD_FMT_BGR24) -> np.ndarray:
         """fmt: the layout of the frames -- AVD_FMT_BGR24 (default) or AVD_FMT_RGB24 uint8[H,W,3], AVD_FMT_BGRA32 / AVD_FMT_RGBA32 uint8[H,W,4],
-        AVD_FMT_RGBP uint8[3,H,W]."""
+        AVD_FMT_RGBP uint8[3,H,W], AVD_FMT_YUYV422 / AVD_FMT_UYVY422 uint8[H,W,2] (limited range)."""
         if fmt not in _lib._PACKED and fmt != _lib.AVD_FMT_RGBP:
             raise ValueError(f"records_stream takes one array per frame: a packed layout or AVD_FMT_RGBP, got fmt {fmt!r}")
         return self._stream(frames, lambda items: self._flush_list(items, fmt))
@@ -236,6 +236,11 @@ class FrameAnalyzer:
     # -- and for planar pictures (software decoders, .y4m): an iterable of (y uint8[H,W], u uint8[H/2,W/2], v uint8[H/2,W/2]) triples ----
     def records_stream_i420(self, surfaces, rotate: int = 0, full_range: bool = False) -> np.ndarray:
         return self._stream(surfaces, lambda items: self._flush_list(items, _lib.AVD_FMT_I420, rotate, full_range))
+
+    # -- 4:2:2 planar pictures (MJPEG, a C422 .y4m): an iterable of (y uint8[H,W], u uint8[H,W/2], v uint8[H,W/2]) triples; H may be odd.
+    # A turned 4:2:2 picture is not on the path: the library refuses rotate != 0 (include/avd.h)
+    def records_stream_i422(self, surfaces, rotate: int = 0, full_range: bool = False) -> np.ndarray:
+        return self._stream(surfaces, lambda items: self._flush_list(items, _lib.AVD_FMT_I422, rotate, full_range))
 
 
 class ClipsInFlight:

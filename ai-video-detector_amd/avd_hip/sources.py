@@ -9,7 +9,7 @@ capture properties the reference falls back to when ffprobe metadata is missing
 (video.py:14-17).  Probed in this order:
 
   1. ``*.npy``  raw decoded stack uint8[T,H,W,3] (memory-mapped) -- used by tests / tools;
-  2. ``*.y4m``  YUV4MPEG2, 8-bit 4:2:0 (what ``ffmpeg -i in.mp4 out.y4m`` writes, i.e. a decoder's pictures BEFORE the colour
+  2. ``*.y4m``  YUV4MPEG2, 8-bit 4:2:0 or 4:2:2 (a ``C422`` file goes, as the file's own planes, through the 4:2:2 ingest; what ``ffmpeg -i in.mp4 out.y4m`` writes, i.e. a decoder's pictures BEFORE the colour
      conversion): memory-mapped, handed over as NV12 surfaces to ``avd_analyze_frames_nv12`` -- the YUV->BGR step of
      ``cap.retrieve()`` happens in the HIP kernel, no BGR frame ever exists.  With
      ``planar=True`` (or ``AVD_Y4M_SURFACE=i420``) the file's own planar pictures go to ``avd_analyze_frames_i420`` as views of
@@ -32,6 +32,7 @@ import numpy as np
 
 class FrameSource:
     # what sampled() yields: "bgr" = uint8[H,W,3]; "nv12" = (y uint8[H,W], uv uint8[H/2,W] interleaved U,V); "i420" = (y uint8[H,W], u uint8[H/2,W/2], v likewise);
+    # "i422" = (y uint8[H,W], u uint8[H,W/2], v likewise), H even or odd;
     # "rgb24" = uint8[H,W,3] R,G,B; "bgra32" / "rgba32" = uint8[H,W,4], fourth byte ignored; "rgbp" = uint8[3,H,W] R,G,B planes (channels first)
     surface: str = "bgr"
     fps: float = 0.0
@@ -41,7 +42,7 @@ class FrameSource:
     # quarter turns clockwise from the pictures sampled() yields (the STORED ones) to the displayed picture; width / height are the displayed
     # picture's, as cv2's capture properties are (orientation-auto)
     rotate: int = 0
-    # the 4:2:0 pictures sampled() yields are full range (0 .. 255: ffmpeg's yuvj420p); means nothing for a source that yields BGR
+    # the 4:2:0 / 4:2:2 pictures sampled() yields are full range (0 .. 255: ffmpeg's yuvj420p); means nothing for a source that yields BGR
     full_range: bool = False
 
     def sampled(self, step: int) -> Iterator[np.ndarray]:
@@ -72,7 +73,10 @@ class Y4mSource(FrameSource):
     A header token ``XAVD_ROTATE=<0|90|180|270>`` (YUV4MPEG2 ``X`` tokens are application comments that other readers ignore) carries a
     container's display rotation, clockwise: ``rotate`` is its quarter turns, ``width`` / ``height`` are the DISPLAYED picture's, the planes
     yielded are the stored ones.  ``XCOLORRANGE=FULL`` (what ffmpeg's y4m muxer writes for yuvj420p) sets ``full_range``; ``XCOLORRANGE=LIMITED``
-    and no token mean limited range."""
+    and no token mean limited range.
+    ``C422`` (8-bit 4:2:2: what ffmpeg writes for yuv422p / yuvj422p, i.e. for MJPEG, webcam and capture-card sources): the chroma planes
+    have H rows of W/2 samples, a frame is 2WH bytes, H may be odd; ``sampled`` always yields the file's own three planes as views of the
+    map and ``surface`` is "i422", whatever ``planar`` says."""
     surface = "nv12"
 
     def __init__(self, path: str, planar: bool = False):
@@ -105,14 +109,18 @@ class Y4mSource(FrameSource):
                 if rng not in ("FULL", "LIMITED"):
                     raise ValueError("XCOLORRANGE must be FULL or LIMITED")
                 self.full_range = rng == "FULL"
-        if w <= 0 or h <= 0 or (w | h) & 1:
+        c422 = chroma == "422"
+        if w <= 0 or h <= 0 or w & 1 or (h & 1 and not c422):        # 4:2:2 subsamples nothing vertically: its height may be odd
             raise ValueError("bad or odd picture size")
-        if not chroma.startswith("420") or "p1" in chroma:          # 420p10 / p12 / p16: more than 8 bits
-            raise ValueError("only 8-bit 4:2:0 is supported")
+        if not c422 and (not chroma.startswith("420") or "p1" in chroma):      # 420p10 / p12 / p16, 422p10 ...: more than 8 bits
+            raise ValueError("only 8-bit 4:2:0 and 4:2:2 are supported")
+        if c422:
+            self.surface = "i422"
         self._w, self._h = w, h                                      # the stored picture
         self.width, self.height = (h, w) if self.rotate & 1 else (w, h)
         self.fps = num / den if den else 0.0
-        self._luma, self._chroma = w * h, (w // 2) * (h // 2)
+        self._crows = h if c422 else h // 2
+        self._luma, self._chroma = w * h, (w // 2) * self._crows
         self._frame_bytes = self._luma + 2 * self._chroma
         self._map = np.memmap(path, dtype=np.uint8, mode="r")
         # every picture is preceded by "FRAME" [parameters] "\n"; the marker length is constant in files written by ffmpeg,
@@ -138,9 +146,9 @@ class Y4mSource(FrameSource):
         for i in range(0, self.frame_count, step):
             o = self._offsets[i]
             y = np.asarray(self._map[o:o + self._luma]).reshape(h, w)
-            u = self._map[o + self._luma:o + self._luma + self._chroma].reshape(h // 2, w // 2)
-            v = self._map[o + self._luma + self._chroma:o + self._frame_bytes].reshape(h // 2, w // 2)
-            if self.surface == "i420":
+            u = self._map[o + self._luma:o + self._luma + self._chroma].reshape(self._crows, w // 2)
+            v = self._map[o + self._luma + self._chroma:o + self._frame_bytes].reshape(self._crows, w // 2)
+            if self.surface in ("i420", "i422"):
                 yield self._map[o:o + self._luma].reshape(h, w), u, v
                 continue
             uv = np.empty((h // 2, w), np.uint8)
@@ -155,11 +163,12 @@ class Y4mSource(FrameSource):
 def write_y4m(path: str, y: np.ndarray, uv: np.ndarray, fps=(30, 1), rotate: int = 0, full_range: bool = False) -> None:
     """NV12 surfaces (y uint8[N,H,W], uv uint8[N,H/2,W] interleaved) -> a YUV4MPEG2 file (tests, tools).  rotate: display rotation in
     DEGREES clockwise, written as the XAVD_ROTATE token when non-zero (Y4mSource); full_range: the XCOLORRANGE=FULL token, written only
-    when true."""
+    when true.  A uv of H rows (NV16: uint8[N,H,W]) is written as C422."""
     n, h, w = y.shape
+    tag = b"C422" if uv.shape[1] == h else b"C420jpeg"
     with open(path, "wb") as f:
-        f.write(b"YUV4MPEG2 W%d H%d F%d:%d Ip A1:1 C420jpeg%s%s\n" % (w, h, fps[0], fps[1], b" XAVD_ROTATE=%d" % rotate if rotate else b"",
-                                                                   b" XCOLORRANGE=FULL" if full_range else b""))
+        f.write(b"YUV4MPEG2 W%d H%d F%d:%d Ip A1:1 %s%s%s\n" % (w, h, fps[0], fps[1], tag, b" XAVD_ROTATE=%d" % rotate if rotate else b"",
+                                                              b" XCOLORRANGE=FULL" if full_range else b""))
         for i in range(n):
             f.write(b"FRAME\n")
             f.write(np.ascontiguousarray(y[i]).tobytes())

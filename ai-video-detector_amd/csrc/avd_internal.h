@@ -89,7 +89,8 @@ struct BandPlan { int rows_per_band, pitch, ni; };
 BandPlan band_plan(int w);
 // What launch_preprocess ran last on a context: read by tests through avd_debug_fetch "ingest_plan" (eight int32 in this order).
 enum IngestKernel { kIngestBgrScalar = 0, kIngestBgrVec16, kIngestBgrStaged, kIngestNv12Scalar, kIngestNv12Tables, kIngestI420Scalar, kIngestI420Tables,
-                    kIngestNv12Strip, kIngestI420Strip, kIngestPx32Scalar, kIngestPx32Vec16, kIngestRgbpScalar, kIngestRgbpVec16, kIngestRgbpStaged };
+                    kIngestNv12Strip, kIngestI420Strip, kIngestPx32Scalar, kIngestPx32Vec16, kIngestRgbpScalar, kIngestRgbpVec16, kIngestRgbpStaged,
+                    kIngestYuyvScalar, kIngestYuyvTables, kIngestI422Scalar, kIngestI422Tables, kIngestNv16Scalar, kIngestNv16Tables };
 struct IngestPlan { int h, w, rows_per_band, nbands, pitch, ni, lds_bytes, kernel; };
 static_assert(sizeof(IngestPlan) == 8 * sizeof(int), "avd_debug_fetch hands the struct out as int32[8]");
 // What the last ingest of a context did; avd_debug_fetch hands each member out under the name beside it.  launch_preprocess records the launch,

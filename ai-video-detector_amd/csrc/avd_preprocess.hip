@@ -1,4 +1,4 @@
-// avd_preprocess.hip -- fused full-resolution pass over decoded frames (gfx950): BGR, RGB in four layouts, NV12, I420.
+// avd_preprocess.hip -- fused full-resolution pass over decoded frames (gfx950): BGR, RGB in four layouts, NV12, I420, 4:2:2 in four layouts.
 //
 // One read of each frame from HBM produces everything the reference derives
 // from full-resolution pixels (reference app/analyzers/video.py):
@@ -38,13 +38,16 @@ static_assert(kThreads / 64 <= kLapSlots, "one moment slot per wave");
 // What a layout's kernels take besides plane 0 (the kernel's first argument) and PreParams: its other planes, frame 0's (or, for a listed clip,
 // the tables of their per-frame pointers), and what only this layout needs.  Packed layouts take nothing.
 struct Nv12Params {
-    const uint8_t* uv;                 // interleaved U,V plane
+    const uint8_t* uv;                 // interleaved U,V plane (NV12: h/2 rows; NV16: h rows)
     int64_t uv_row_stride, uv_frame_stride;
     YuvConsts k;
 };
 struct I420Params {
-    const uint8_t *u, *v;              // planar U and V, uint8[h/2][w/2] each (YV12: the caller passes them exchanged)
+    const uint8_t *u, *v;              // planar U and V, uint8[h/2][w/2] each (I422: [h][w/2]; YV12 / YV16: the caller passes them exchanged)
     int64_t c_row_stride, c_frame_stride;   // shared by the two planes
+    YuvConsts k;
+};
+struct YuyvParams {                    // packed 4:2:2: one plane, only the constants
     YuvConsts k;
 };
 struct RgbpParams {
@@ -52,7 +55,7 @@ struct RgbpParams {
 };
 
 // LDS plan, read by the kernels and by the launcher.  The tile is (rows_per_band + 2) rows of `pitch` bytes; behind it sit either the
-// resampling tables of k_preprocess_vec (LdsTabs, behind the FULL tile) or the three conversion tables of the 4:2:0 table fills (behind the
+// resampling tables of k_preprocess_vec (LdsTabs, behind the FULL tile) or the three conversion tables of the 4:2:0 and 4:2:2 table fills (behind the
 // rows the band has, rounded to 16: a short last band has them lower than the launcher reserved for).  Their length and index bias travel
 // with the conversion constants (YuvConsts::ntab, ::bias): the window of Y + offset follows the constants -- [-221, 475] limited range,
 // [-226, 480] full range -- and launch_preprocess refuses constants whose window leaves the table.
@@ -564,6 +567,25 @@ __device__ __forceinline__ ChromaTerms chroma_offsets(int U, int V, const YuvCon
     return t;
 }
 
+// the eight chroma-offset triples of a 16-pixel chunk.  Interleaved (NV12, NV16): one 16-byte word, pair j = bytes 2j (U) and 2j + 1 (V)
+__device__ __forceinline__ void chroma8_interleaved(const uint4& cc, const YuvConsts& k, ChromaTerms (&t)[8])
+{
+    const unsigned cw[4] = {cc.x, cc.y, cc.z, cc.w};
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        t[2 * j] = chroma_offsets(cw[j] & 0xFF, (cw[j] >> 8) & 0xFF, k);
+        t[2 * j + 1] = chroma_offsets((cw[j] >> 16) & 0xFF, cw[j] >> 24, k);
+    }
+}
+// planar (I420, I422): 8 U and 8 V bytes, pair j = U byte j and V byte j
+__device__ __forceinline__ void chroma8_planar(const uint2& uu, const uint2& vv, const YuvConsts& k, ChromaTerms (&t)[8])
+{
+    const unsigned uw[2] = {uu.x, uu.y}, vw[2] = {vv.x, vv.y};
+#pragma unroll
+    for (int j = 0; j < 8; j++)
+        t[j] = chroma_offsets((uw[j >> 2] >> (8 * (j & 3))) & 0xFF, (vw[j >> 2] >> (8 * (j & 3))) & 0xFF, k);
+}
+
 __device__ __forceinline__ unsigned gray_from_tables(int Y, const ChromaTerms& t, const unsigned* tabB, const unsigned* tabG, const unsigned* tabR)
 {
     return (tabB[Y + t.b] + tabG[Y + t.g] + tabR[Y + t.r]) >> 15;
@@ -677,6 +699,54 @@ __device__ __forceinline__ void fill_yuv420_tables(uint8_t* tile, const uint8_t*
                        (gray_from_tables((yw[j] >> 16) & 0xFF, t(2 * j + 1), tabB, tabG, tabR) << 16) | (gray_from_tables(yw[j] >> 24, t(2 * j + 1), tabB, tabG, tabR) << 24);
             *reinterpret_cast<uint4*>(tile + (y - ylo) * pitch + kPad + c * 16) = make_uint4(g[0], g[1], g[2], g[3]);
         }
+    }
+    __syncthreads();
+    reflect_tile_rows(tile, trows, pitch, chunks, ylo < 0, yhi > h - 1, tid);
+}
+
+// ---- 4:2:2: chroma subsampled horizontally only.  Pixel (y, x) takes the chroma sample (y, x >> 1) of its own row, so the work item of the
+// 4:2:0 fills -- one chroma row serving two luma rows -- does not exist here: a work item is one luma row, the height may be odd, a band may
+// begin and end on any row, and no chroma row is ever shared between workgroups.  The arithmetic per pixel is the 4:2:0 fills'.
+
+// any geometry / alignment: one pixel per work item.  fetch(y, x, Y, U, V): the samples of stored pixel (y, x)
+template <typename Fetch>
+__device__ __forceinline__ void fill_yuv422_scalar(uint8_t* tile, const YuvConsts& k, const PreParams& P, const Band& b, int tid, Fetch fetch)
+{
+    const int w = P.w, pitch = P.pitch;
+    for (int it = tid; it < b.trows * w; it += kThreads) {
+        const int tr = it / w, x = it - tr * w;
+        const int y = reflect_once(b.r0 - 1 + tr, P.h);
+        int Y, U, V;
+        fetch(y, x, Y, U, V);
+        tile[tr * pitch + kPad + x] = (uint8_t)gray_from_yuv(Y, chroma_terms(U, V, k), k.cy);
+    }
+}
+
+// aligned planes of w % 16 == 0 pixels: one work item = one luma row x one 16-pixel chunk, through the three gray tables of the 4:2:0 table
+// fill.  chunk16(y, c, yy, t): the 16 luma bytes of chunk c of row y and its eight chroma-offset triples (pair j serves pixels 2j, 2j + 1).
+// The offsets are formed per row, not per two rows: about 50 vector instructions more per 16-pixel row than fill_yuv420_tables.
+template <typename Chunk16>
+__device__ __forceinline__ void fill_yuv422_tables(uint8_t* tile, const YuvConsts& k, const PreParams& P, const Band& b, int tid, Chunk16 chunk16)
+{
+    const int h = P.h, pitch = P.pitch, trows = b.trows;
+    unsigned* const tabB = build_gray_tables(tile, trows, pitch, k, tid);
+    unsigned* const tabG = tabB + k.ntab;
+    unsigned* const tabR = tabG + k.ntab;
+    const int ylo = b.r0 - 1, yhi = b.r0 + b.rows;        // image rows of tile rows 0 and trows - 1, before reflection
+    const int ya = max(ylo, 0), yb = min(yhi, h - 1);      // the ones that exist
+    const int chunks = P.w >> 4;
+    for (int it = tid; it < (yb - ya + 1) * chunks; it += kThreads) {
+        const int yr = it / chunks, c = it - yr * chunks, y = ya + yr;
+        uint4 yy;
+        ChromaTerms t[8];
+        chunk16(y, c, yy, t);
+        const unsigned yw[4] = {yy.x, yy.y, yy.z, yy.w};
+        unsigned g[4];
+#pragma unroll
+        for (int j = 0; j < 4; j++)
+            g[j] = gray_from_tables(yw[j] & 0xFF, t[2 * j], tabB, tabG, tabR) | (gray_from_tables((yw[j] >> 8) & 0xFF, t[2 * j], tabB, tabG, tabR) << 8) |
+                   (gray_from_tables((yw[j] >> 16) & 0xFF, t[2 * j + 1], tabB, tabG, tabR) << 16) | (gray_from_tables(yw[j] >> 24, t[2 * j + 1], tabB, tabG, tabR) << 24);
+        *reinterpret_cast<uint4*>(tile + (y - ylo) * pitch + kPad + c * 16) = make_uint4(g[0], g[1], g[2], g[3]);
     }
     __syncthreads();
     reflect_tile_rows(tile, trows, pitch, chunks, ylo < 0, yhi > h - 1, tid);
@@ -883,13 +953,7 @@ struct Nv12 {
             });
         else if (VEC)                      // the 16 chroma bytes of a chunk are one 16-byte load, pair j = bytes 2j (U) and 2j + 1 (V)
             fill_yuv420_tables<ROT == 2>(tile, yfr, nv.k, P, b, tid, [&](int p, int c, ChromaTerms (&t)[8]) {
-                const uint4 cc = *reinterpret_cast<const uint4*>(cfr + (int64_t)p * nv.uv_row_stride + c * 16);
-                const unsigned cw[4] = {cc.x, cc.y, cc.z, cc.w};
-#pragma unroll
-                for (int j = 0; j < 4; j++) {
-                    t[2 * j] = chroma_offsets(cw[j] & 0xFF, (cw[j] >> 8) & 0xFF, nv.k);
-                    t[2 * j + 1] = chroma_offsets((cw[j] >> 16) & 0xFF, cw[j] >> 24, nv.k);
-                }
+                chroma8_interleaved(*reinterpret_cast<const uint4*>(cfr + (int64_t)p * nv.uv_row_stride + c * 16), nv.k, t);
             });
         else
             fill_yuv420_scalar<ROT == 2>(tile, yfr, nv.k, P, b, tid, [&](int cy, int cx, int& U, int& V) {
@@ -926,16 +990,99 @@ struct I420 {
         else if (VEC)
             fill_yuv420_tables<ROT == 2>(tile, yfr, ip.k, P, b, tid, [&](int p, int c, ChromaTerms (&t)[8]) {
                 const int64_t o = (int64_t)p * ip.c_row_stride + c * 8;
-                const uint2 uu = *reinterpret_cast<const uint2*>(ufr + o), vv = *reinterpret_cast<const uint2*>(vfr + o);
-                const unsigned uw[2] = {uu.x, uu.y}, vw[2] = {vv.x, vv.y};
-#pragma unroll
-                for (int j = 0; j < 8; j++)
-                    t[j] = chroma_offsets((uw[j >> 2] >> (8 * (j & 3))) & 0xFF, (vw[j >> 2] >> (8 * (j & 3))) & 0xFF, ip.k);
+                chroma8_planar(*reinterpret_cast<const uint2*>(ufr + o), *reinterpret_cast<const uint2*>(vfr + o), ip.k, t);
             });
         else
             fill_yuv420_scalar<ROT == 2>(tile, yfr, ip.k, P, b, tid, [&](int cy, int cx, int& U, int& V) {
                 const int64_t o = (int64_t)cy * ip.c_row_stride + cx;
                 U = ufr[o]; V = vfr[o];
+            });
+    }
+};
+
+// 4:2:2.  The stored picture is the displayed one (a turned 4:2:2 picture is refused: avd_ingest_clip.h).
+// Packed (AVD_FMT_YUYV422: Y0 U Y1 V; UYVY: U Y0 V Y1): every dword is a pixel pair with its own U and V.  Tables: a chunk is two 16-byte loads;
+// a v_perm per luma word picks the four luma bytes of two dwords, the chroma bytes are taken where they lie -- no byte gather.
+template <bool VEC, bool UYVY>
+struct Yuyv {
+    static constexpr IngestKernel id = VEC ? kIngestYuyvTables : kIngestYuyvScalar;
+    template <Frames FR>
+    static __device__ __forceinline__ PlaneSet<1> planes(const uint8_t* plane, const YuyvParams&, const PreParams& P, int f)
+    {
+        return {{frame_base<FR>(plane, f, P.frame_stride)}};
+    }
+    static __device__ __forceinline__ void fill(uint8_t* tile, const PlaneSet<1>& fr, const YuyvParams& yp, const PreParams& P, const Band& b, int tid)
+    {
+        const uint8_t* frame = fr.p[0];
+        if (VEC)
+            fill_yuv422_tables(tile, yp.k, P, b, tid, [&](int y, int c, uint4& yy, ChromaTerms (&t)[8]) {
+                const uint4* src = reinterpret_cast<const uint4*>(frame + (int64_t)y * P.row_stride + c * 32);
+                const uint4 s0 = src[0], s1 = src[1];
+                const unsigned d[8] = {s0.x, s0.y, s0.z, s0.w, s1.x, s1.y, s1.z, s1.w};
+                constexpr unsigned luma = UYVY ? 0x07050301u : 0x06040200u;      // bytes 1, 3 (UYVY) or 0, 2 of the low, then of the high dword
+                yy = make_uint4(__builtin_amdgcn_perm(d[1], d[0], luma), __builtin_amdgcn_perm(d[3], d[2], luma),
+                                __builtin_amdgcn_perm(d[5], d[4], luma), __builtin_amdgcn_perm(d[7], d[6], luma));
+#pragma unroll
+                for (int j = 0; j < 8; j++)
+                    t[j] = UYVY ? chroma_offsets(d[j] & 0xFF, (d[j] >> 16) & 0xFF, yp.k) : chroma_offsets((d[j] >> 8) & 0xFF, d[j] >> 24, yp.k);
+            });
+        else
+            fill_yuv422_scalar(tile, yp.k, P, b, tid, [&](int y, int x, int& Y, int& U, int& V) {
+                const uint8_t* p = frame + (int64_t)y * P.row_stride + (x >> 1) * 4;
+                Y = p[2 * (x & 1) + (UYVY ? 1 : 0)]; U = p[UYVY ? 0 : 1]; V = p[UYVY ? 2 : 3];
+            });
+    }
+};
+
+// Planar 4:2:2 (I422; YV16 with the chroma pointers exchanged): I420's fetches with one chroma row per luma row -- a 16-byte Y load and two
+// 8-byte chroma loads per chunk, hence I420's alignment rule (Y on 16, U and V on 8: a contiguous frame has its V plane at 3wh/2, a multiple
+// of 8 but, for odd h, not of 16)
+template <bool VEC>
+struct I422 {
+    static constexpr IngestKernel id = VEC ? kIngestI422Tables : kIngestI422Scalar;
+    template <Frames FR>
+    static __device__ __forceinline__ PlaneSet<3> planes(const uint8_t* yplane, const I420Params& ip, const PreParams& P, int f)
+    {
+        return I420<VEC, 0>::template planes<FR>(yplane, ip, P, f);
+    }
+    static __device__ __forceinline__ void fill(uint8_t* tile, const PlaneSet<3>& fr, const I420Params& ip, const PreParams& P, const Band& b, int tid)
+    {
+        const uint8_t *yfr = fr.p[0], *ufr = fr.p[1], *vfr = fr.p[2];
+        if (VEC)
+            fill_yuv422_tables(tile, ip.k, P, b, tid, [&](int y, int c, uint4& yy, ChromaTerms (&t)[8]) {
+                yy = *reinterpret_cast<const uint4*>(yfr + (int64_t)y * P.row_stride + c * 16);
+                const int64_t o = (int64_t)y * ip.c_row_stride + c * 8;
+                chroma8_planar(*reinterpret_cast<const uint2*>(ufr + o), *reinterpret_cast<const uint2*>(vfr + o), ip.k, t);
+            });
+        else
+            fill_yuv422_scalar(tile, ip.k, P, b, tid, [&](int y, int x, int& Y, int& U, int& V) {
+                const int64_t o = (int64_t)y * ip.c_row_stride + (x >> 1);
+                Y = yfr[(int64_t)y * P.row_stride + x]; U = ufr[o]; V = vfr[o];
+            });
+    }
+};
+
+// NV16: NV12's planes with one chroma row per luma row -- two 16-byte loads per chunk
+template <bool VEC>
+struct Nv16 {
+    static constexpr IngestKernel id = VEC ? kIngestNv16Tables : kIngestNv16Scalar;
+    template <Frames FR>
+    static __device__ __forceinline__ PlaneSet<2> planes(const uint8_t* yplane, const Nv12Params& nv, const PreParams& P, int f)
+    {
+        return Nv12<VEC, 0>::template planes<FR>(yplane, nv, P, f);
+    }
+    static __device__ __forceinline__ void fill(uint8_t* tile, const PlaneSet<2>& fr, const Nv12Params& nv, const PreParams& P, const Band& b, int tid)
+    {
+        const uint8_t *yfr = fr.p[0], *cfr = fr.p[1];
+        if (VEC)
+            fill_yuv422_tables(tile, nv.k, P, b, tid, [&](int y, int c, uint4& yy, ChromaTerms (&t)[8]) {
+                yy = *reinterpret_cast<const uint4*>(yfr + (int64_t)y * P.row_stride + c * 16);
+                chroma8_interleaved(*reinterpret_cast<const uint4*>(cfr + (int64_t)y * nv.uv_row_stride + c * 16), nv.k, t);
+            });
+        else
+            fill_yuv422_scalar(tile, nv.k, P, b, tid, [&](int y, int x, int& Y, int& U, int& V) {
+                const uint8_t* cp = cfr + (int64_t)y * nv.uv_row_stride + (x >> 1) * 2;
+                Y = yfr[(int64_t)y * P.row_stride + x]; U = cp[0]; V = cp[1];
             });
     }
 };
@@ -1105,7 +1252,8 @@ static void dispatch_turn(bool vec, int rot, F&& f)
 static constexpr bool is_staged(IngestKernel id) { return id == kIngestBgrStaged || id == kIngestRgbpStaged; }
 static constexpr bool has_gray_tables(IngestKernel id)
 {
-    return id == kIngestNv12Tables || id == kIngestNv12Strip || id == kIngestI420Tables || id == kIngestI420Strip;
+    return id == kIngestNv12Tables || id == kIngestNv12Strip || id == kIngestI420Tables || id == kIngestI420Strip || id == kIngestYuyvTables ||
+           id == kIngestI422Tables || id == kIngestNv16Tables;
 }
 
 // POL's kernel: the staged body for the staged fills, the generic one for every other
@@ -1128,13 +1276,13 @@ int launch_preprocess(avd_ctx* ctx, const IngestClip& clip, const uint8_t* d_in,
     const int grid = (n * P.nbands + 7) / 8 * 8;
     const size_t tile = lds_tile_bytes(P.rows_per_band + 2, P.pitch);
     // bgr: no conversion constants -- BGR24 and the four layouts of RGB producers; planar: I420
-    const bool bgr = !clip.is_420(), planar = clip.format == AVD_FMT_I420;
+    const bool bgr = !clip.is_yuv(), planar = clip.planar_yuv(), yuv422 = clip.is_422();
     const bool rgbp = clip.format == AVD_FMT_RGBP, px32 = clip.format == AVD_FMT_BGRA32 || clip.format == AVD_FMT_RGBA32;
     const bool rgb = clip.format == AVD_FMT_RGB24 || clip.format == AVD_FMT_RGBA32;     // packed pixels stored R, G, B
-    // the planar chroma planes are read 8 bytes at a time (I420's table fill), every other plane 16
+    // the planar chroma planes are read 8 bytes at a time (I420's and I422's table fills), every other plane 16; packed 4:2:2 has no other plane
     const bool chroma_ok = planar ? aligned_to(8, d_uv, clip.uv_row_stride, clip.uv_frame_stride) && aligned_to(8, d_v, clip.uv_row_stride, clip.uv_frame_stride)
                            : rgbp ? aligned16(d_uv, clip.uv_row_stride, clip.uv_frame_stride) && aligned16(d_v, clip.uv_row_stride, clip.uv_frame_stride)
-                                  : bgr || aligned16(d_uv, clip.uv_row_stride, clip.uv_frame_stride);
+                                  : bgr || clip.planes() == 1 || aligned16(d_uv, clip.uv_row_stride, clip.uv_frame_stride);
     const bool vec = list ? list->aligned : P.w % 16 == 0 && aligned16(d_in, clip.row_stride, clip.frame_stride) && chroma_ok;
     int ni = vec && bgr && !px32 ? band_plan(P.w).ni : 0;       // the layouts with a staged fill: BGR24, RGB24, RGBP
     // planar RGB: the byte gather needs a few registers more than BGR's alignbyte, and NI = 9 (2048 < w <= 4096) no longer fits the 128 VGPRs of
@@ -1176,7 +1324,16 @@ int launch_preprocess(avd_ctx* ctx, const IngestClip& clip, const uint8_t* d_in,
         });
     };
     bool built = true;                                 // false: the band plan's NI has no staged kernel
-    if (planar) {
+    if (yuv422) {                                      // one table and one scalar fill per layout, no turn
+        if (rot) { ctx->err = "internal error: a turned 4:2:2 clip reached the ingest launch"; return AVD_ERR_DEVICE; }
+        dispatch_bool(vec, [&](auto v) {
+            constexpr bool V = decltype(v)::value;
+            if (clip.format == AVD_FMT_I422) launch(I422<V>{}, I420Params{d_uv, d_v, clip.uv_row_stride, clip.uv_frame_stride, yc});
+            else if (clip.format == AVD_FMT_NV16) launch(Nv16<V>{}, Nv12Params{d_uv, clip.uv_row_stride, clip.uv_frame_stride, yc});
+            else if (clip.format == AVD_FMT_UYVY422) launch(Yuyv<V, true>{}, YuyvParams{yc});
+            else launch(Yuyv<V, false>{}, YuyvParams{yc});
+        });
+    } else if (planar) {
         const I420Params ip{d_uv, d_v, clip.uv_row_stride, clip.uv_frame_stride, yc};
         dispatch_turn(vec, rot, [&](auto v, auto r) { launch(I420<decltype(v)::value, decltype(r)::value>{}, ip); });
     } else if (!bgr) {

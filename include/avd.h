@@ -207,10 +207,11 @@ int avd_analyze_frames_i420_async(avd_ctx* ctx, const uint8_t* y, const uint8_t*
  * half turn reads the mirrored rows and chunks of the same kernels, a quarter turn reads of every stored row the 16-byte span a band needs (the
  * strip fill); no turned picture exists in memory.
  *   struct_size  sizeof(avd_picture) of the caller's header; anything else is AVD_ERR_ARG
- *   plane        BGR: [0]; NV12: Y, interleaved UV; I420: Y, U, V (YV12: exchange [1] and [2]); the RGB layouts: below the struct's format enum
- *   row_stride, frame_stride   bytes, per plane; I420: [1] == [2] (AVD_ERR_ARG otherwise); RGBP: [0] == [1] == [2]
+ *   plane        BGR: [0]; NV12: Y, interleaved UV; I420: Y, U, V (YV12: exchange [1] and [2]); the RGB and 4:2:2 layouts: below the struct's format enum
+ *   row_stride, frame_stride   bytes, per plane; I420 and I422: [1] == [2] (AVD_ERR_ARG otherwise); RGBP: [0] == [1] == [2]
  *   h, w         the stored picture;  rotate  quarter turns clockwise from the stored to the displayed picture, 0 .. 3;  reserved  0
- *   format       the layout (AVD_FMT_BGR24 / _NV12 / _I420 / _RGB24 / _BGRA32 / _RGBA32 / _RGBP), for the 4:2:0 layouts optionally OR-ed with AVD_FMT_FULL_RANGE
+ *   format       the layout (AVD_FMT_BGR24 / _NV12 / _I420 / _RGB24 / _BGRA32 / _RGBA32 / _RGBP / _YUYV422 / _UYVY422 / _I422 / _NV16), for the 4:2:0 and 4:2:2
+ *                layouts optionally OR-ed with AVD_FMT_FULL_RANGE
  * Refused without a launch: rotate outside 0 .. 3, a non-zero reserved, a bad format or struct_size (AVD_ERR_ARG); what the format's own entry
  * point refuses, with its status; AVD_FMT_BGR24 with rotate != 0 (AVD_ERR_UNSUPPORTED: cv2 hands BGR over already rotated, stored-orientation
  * BGR does not arise).  Mirrored display matrices are not covered.
@@ -243,7 +244,7 @@ enum avd_format { AVD_FMT_BGR24 = 0, AVD_FMT_NV12 = 1, AVD_FMT_I420 = 2 };
  * Refused in avd_picture's / avd_frame_list's order, where the BGR and I420 equivalents stand: AVD_FMT_FULL_RANGE on any of the four
  * (AVD_ERR_ARG: RGB has no range); rotate != 0 (AVD_ERR_UNSUPPORTED: producers of RGB hand it over already turned); AVD_FMT_RGBP planes whose
  * row or frame strides differ (AVD_ERR_ARG).  No evenness rule applies; the 32 x 32 minimum, the 16384 limits, null planes and short strides
- * are checked as for every clip, with rows of 3w, 4w and w bytes.  Layouts 3 .. 0x0F and 0x14 .. 0xFF stay AVD_ERR_ARG.
+ * are checked as for every clip, with rows of 3w, 4w and w bytes.  Layouts 3 .. 0x0F, 0x14 .. 0x1F and 0x24 .. 0xFF stay AVD_ERR_ARG (0x20 .. 0x23: the 4:2:2 layouts below).
  * AVD_MEM_HOST: the three planes of AVD_FMT_RGBP are staged as the planes of I420 are -- spans merged where they overlap or touch, so a dense
  * [N,3,H,W] stack crosses the link as ONE copy and separately allocated planes as three; the packed layouts are one span.
  * The 16-byte fills need w % 16 == 0 and every plane base, row stride and frame stride 16-byte aligned (a list: every frame); anything else
@@ -252,6 +253,43 @@ enum avd_format { AVD_FMT_BGR24 = 0, AVD_FMT_NV12 = 1, AVD_FMT_I420 = 2 };
 #define AVD_FMT_BGRA32 0x11
 #define AVD_FMT_RGBA32 0x12
 #define AVD_FMT_RGBP   0x13
+/* 4:2:2 pictures -- chroma subsampled horizontally only (additive at ABI 3; avd_picture / avd_frame_list only -- avd_clip and the entry points that
+ * name their format are unchanged).  MJPEG from cameras, webcams and capture boxes (ffmpeg's yuvj422p: AVD_FMT_I422 | AVD_FMT_FULL_RANGE), raw
+ * webcam and capture-card frames and V4L2 / DeckLink / AVFoundation pipes (yuyv422, uyvy422), hardware JPEG and capture paths (NV16), a .y4m file
+ * with C422.
+ *   value  name               planes                                                                row bytes
+ *   0x20   AVD_FMT_YUYV422    1: Y0 U Y1 V, a pixel pair per 4 bytes                                 2w
+ *   0x21   AVD_FMT_UYVY422    1: U Y0 V Y1                                                           2w
+ *   0x22   AVD_FMT_I422       3: Y [h][w], U and V [h][w/2] (YV16: exchange [1] and [2])             w, w/2, w/2
+ *   0x23   AVD_FMT_NV16       2: Y [h][w], interleaved U,V [h][w]                                    w, w
+ * The conversion: pixel (y, x) has luma Y[y][x] and the chroma sample U[y][x >> 1], V[y][x >> 1] of its OWN row, and its BGR triple is the one
+ * libswscale's table converter (yuv2rgb.c) gives -- B = T[Y + ob(U)], G = T[Y + og(U, V)], R = T[Y + or(V)] with the very tables and constants
+ * of the 4:2:0 path, limited range by default and full range with AVD_FMT_FULL_RANGE (allowed on all four, per clip of a batch).  Every output
+ * of a call equals, bit for bit and in both fb_modes, the BGR entry point's on those BGR frames.  Two equivalent statements: an NV12 picture of
+ * height 2h whose luma rows 2y and 2y + 1 are both Y[y] and whose chroma row y is this picture's chroma row y converts (avdo_nv12_to_bgr24,
+ * tests/yuv_tables_reference.py) to this picture's BGR frame in its even rows; and a 4:2:2 picture of even height whose chroma rows 2k and
+ * 2k + 1 are equal gives exactly the I420 / NV12 result on chroma rows k (tests/yuv422_reference.py restates the definition).
+ * Parity with a real libswscale is UNPINNED, and nothing here can check it.  For the packed layouts and NV16 libswscale takes its general path
+ * at equal size; as far as it can be restated that path has one-tap filters and (x + 64) >> 7 of a value shifted left by 7, then the same
+ * tables: the definition above with every chroma row used.  For planar yuv422p / yuvj422p FFmpeg up to 7.0 takes the unscaled special
+ * converter, which doubles the chroma stride and therefore uses only the EVEN chroma rows; later versions use every row.  Both are available:
+ * every row is AVD_FMT_I422; even rows only is the AVD_FMT_I420 call on the same planes with the chroma row stride doubled (and an even h).
+ * Which FFmpeg the reference's OpenCV wheel bundles could not be determined.
+ * Refused in avd_picture's / avd_frame_list's order, where the RGB and I420 equivalents stand: rotate != 0 (AVD_ERR_UNSUPPORTED: the conversion
+ * does not commute with quarter turns when only one axis is subsampled, and a turned 4:2:2 fill is not built); AVD_FMT_I422 chroma planes whose
+ * row or frame strides differ (AVD_ERR_ARG); an odd width (AVD_ERR_UNSUPPORTED).  The height may be ODD: nothing is subsampled vertically.
+ * The 32 x 32 minimum, the 16384 limits, null planes and short strides are checked as for every clip, with the row bytes above.  Layouts
+ * 0x14 .. 0x1F and 0x24 .. 0xFF stay AVD_ERR_ARG.
+ * AVD_MEM_HOST: the packed layouts are one span of 2w-byte rows; the three planes of I422 are staged as I420's (merged where they overlap or
+ * touch: a .y4m map is ONE copy, separately allocated planes three); NV16 as NV12, two spans.
+ * The table fills need w % 16 == 0 and every plane base, row stride and frame stride 16-byte aligned (8 for the chroma planes of I422; a list:
+ * every frame); anything else runs the scalar fill with identical results.
+ * Not covered: turned 4:2:2 pictures; 4:4:4 and 10-bit surfaces (libswscale's filtered general path, which is not restatable here); NV21, GRAY8
+ * and mirrored display matrices.  avd_clip is unchanged. */
+#define AVD_FMT_YUYV422 0x20
+#define AVD_FMT_UYVY422 0x21
+#define AVD_FMT_I422    0x22
+#define AVD_FMT_NV16    0x23
 typedef struct avd_picture {
     uint32_t struct_size;
     int32_t  format;
@@ -461,9 +499,10 @@ int avd_kernel_ms(avd_ctx* ctx, int kernel_id, float* ms);
  * "flow<L>" float[n-1][2][hL][wL] (planar, after the last iteration at level L).
  * "ingest_plan" int32[8], host state rather than a device buffer: what the last ingest launch of the context ran --
  * h, w, rows_per_band, nbands, LDS tile pitch, NI of k_preprocess_vec, the staged kernel of BGR24 / RGB24 / RGBP (0: the generic kernel), dynamic LDS bytes requested,
- * kernel (0 bgr_scalar, 1 bgr_vec16, 2 bgr_staged, 3 nv12_scalar, 4 nv12_tables, 5 i420_scalar, 6 i420_tables, 7 nv12_strip, 8 i420_strip, 9 px32_scalar, 10 px32_vec16, 11 rgbp_scalar, 12 rgbp_vec16, 13 rgbp_staged;
+ * kernel (0 bgr_scalar, 1 bgr_vec16, 2 bgr_staged, 3 nv12_scalar, 4 nv12_tables, 5 i420_scalar, 6 i420_tables, 7 nv12_strip, 8 i420_strip, 9 px32_scalar, 10 px32_vec16, 11 rgbp_scalar, 12 rgbp_vec16, 13 rgbp_staged,
+ * 14 yuyv_scalar, 15 yuyv_tables, 16 i422_scalar, 17 i422_tables, 18 nv16_scalar, 19 nv16_tables;
  * a half turn runs the flipped instantiations of 3 .. 6 under the same ids; AVD_FMT_RGB24 runs 0 .. 2 with its own coefficient constants, BGRA32 and
- * RGBA32 share 9 and 10: "ingest_format" tells them apart); h, w are the displayed picture's; an error before any ingest launch.
+ * RGBA32 share 9 and 10, YUYV422 and UYVY422 share 14 and 15: "ingest_format" tells them apart); h, w are the displayed picture's; an error before any ingest launch.
  * "ingest_rotate" int32[1], host state: the rotation (quarter turns) that launch ran with; an error before any ingest launch.
  * "ingest_range" int32[1], host state: 1 if that launch ran with full-range conversion constants (AVD_FMT_FULL_RANGE), else 0; an error before
  * any ingest launch.
