@@ -61,8 +61,9 @@ def _pattern(n, nbase):
 
 
 def test_cfg3_4k_dense_sampling_through_video_analyze(ctx, oracle, monkeypatch):
-    """240 sampled 4K frames (4K30, 8 analysed frames per second -> step 4) in ONE HIP call of 241 > 129 frames,
-    so the Farneback stage runs in two workspace chunks that overlap by one frame.  The whole result of
+    """240 sampled 4K frames (4K30, 8 analysed frames per second -> step 4) in ONE HIP call.  Its 239 pairs are more than the 128 the
+    Farneback scratch holds at first, so the scratch grows for the call; it runs as ONE chunk (a call is split only above 512 pairs:
+    tests/test_gpu_history.py compares that boundary with the oracle).  The whole result of
     ``video.analyze`` is compared with the oracle run on the same 240 frames, and the device-resident form of
     the same clip (built on the GPU from the six base frames) with the streamed one."""
     torch = pytest.importorskip("torch")
@@ -74,7 +75,7 @@ def test_cfg3_4k_dense_sampling_through_video_analyze(ctx, oracle, monkeypatch):
     src = _Synthetic4KSource(base, pattern)
     monkeypatch.setattr(sources, "open_source", lambda path: src)
     monkeypatch.setenv("AVD_SAMPLES_PER_SECOND", "8")
-    monkeypatch.setenv("AVD_CHUNK_FRAMES", "256")                 # one HIP call: the clip crosses the 128-pair chunk inside it
+    monkeypatch.setenv("AVD_CHUNK_FRAMES", "256")                 # one HIP call of 239 pairs: the Farneback scratch grows past its first 128 pairs
     meta = {"width": w, "height": h, "fps": 30.0, "duration": 120.0}
     got = video.analyze("synthetic-4k30.mp4", meta)
     assert src.steps_seen == [4] and src.closed

@@ -230,8 +230,9 @@ def test_analyze_frames_end_to_end(ctx, oracle):
 
 
 def test_long_clip_crosses_farneback_chunk_boundary(ctx, oracle):
-    """The Farneback workspace holds 128 pairs; longer clips are processed in chunks that overlap by
-    one frame.  131 frames -> pairs 127|128 straddle the boundary: records there must equal the oracle."""
+    """The Farneback workspace holds 128 pairs at first and grows with the call up to 512: the 130 pairs of these 131 frames make it grow
+    and run as ONE chunk, so nothing is split here any more (the name is from when 128 was the chunk).  Records on both sides of pair 128,
+    the first beyond the initial capacity, must equal the oracle.  The split above 512 pairs against the oracle: tests/test_gpu_history.py."""
     base = synth.make_clip(8, 64, 96, seed=31, dup_every=0)
     idx = np.arange(131) % 8
     clip = base[idx]                                        # cheap long clip (8 distinct frames cycled)
@@ -241,7 +242,7 @@ def test_long_clip_crosses_farneback_chunk_boundary(ctx, oracle):
         a, b = idx[p], idx[p + 1]
         m, v = oracle.flow_stats(oracle.farneback(small[a], small[b]))
         assert rec["flow_mean"][p + 1] == m and rec["flow_var"][p + 1] == v, p
-    # the cycle repeats every 8 frames: equal pairs must give equal records on both sides of the boundary
+    # the cycle repeats every 8 frames: equal pairs must give equal records on both sides of pair 128
     assert rec["flow_mean"][120 + 1] == rec["flow_mean"][128 + 1] and rec["flow_var"][121 + 1] == rec["flow_var"][129 + 1]
     assert rec["ham"][0] == -1 and np.all(rec["ham"][1:] >= 0)
 
