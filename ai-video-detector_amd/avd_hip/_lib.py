@@ -70,18 +70,27 @@ AVD_FMT_FULL_RANGE = 0x100      # flag OR-ed into a 4:2:0 layout: the samples us
 AVD_FMT_RGB24, AVD_FMT_BGRA32, AVD_FMT_RGBA32, AVD_FMT_RGBP = 0x10, 0x11, 0x12, 0x13
 # 4:2:2 (include/avd.h): Y0 U Y1 V and U Y0 V Y1 packed, 2 bytes per pixel; planar Y, U, V with chroma planes [H][W/2]; Y and interleaved U,V [H][W]
 AVD_FMT_YUYV422, AVD_FMT_UYVY422, AVD_FMT_I422, AVD_FMT_NV16 = 0x20, 0x21, 0x22, 0x23
+# 10-bit 4:2:0 in little-endian 16-bit words (include/avd.h): P010 = NV12's planes with the 10 bits in the high bits, I010 = I420's with them in the low bits
+AVD_FMT_P010, AVD_FMT_I010 = 0x30, 0x31
+_WIDE = (AVD_FMT_P010, AVD_FMT_I010)        # planes of uint16 (torch: uint16, or int16 read as the same bits); every stride handed on is in bytes
 # one interleaved plane: bytes per pixel
 _PACKED = {AVD_FMT_BGR24: 3, AVD_FMT_RGB24: 3, AVD_FMT_BGRA32: 4, AVD_FMT_RGBA32: 4, AVD_FMT_YUYV422: 2, AVD_FMT_UYVY422: 2}
 _FMT_PLANES = {AVD_FMT_BGR24: 1, AVD_FMT_NV12: 2, AVD_FMT_I420: 3, AVD_FMT_RGB24: 1, AVD_FMT_BGRA32: 1, AVD_FMT_RGBA32: 1, AVD_FMT_RGBP: 3,
-               AVD_FMT_YUYV422: 1, AVD_FMT_UYVY422: 1, AVD_FMT_I422: 3, AVD_FMT_NV16: 2}
-_YUV_PLANES = (AVD_FMT_NV12, AVD_FMT_I420, AVD_FMT_I422, AVD_FMT_NV16)      # clips handed over as a tuple of planes
+               AVD_FMT_YUYV422: 1, AVD_FMT_UYVY422: 1, AVD_FMT_I422: 3, AVD_FMT_NV16: 2, AVD_FMT_P010: 2, AVD_FMT_I010: 3}
+_YUV_PLANES = (AVD_FMT_NV12, AVD_FMT_I420, AVD_FMT_I422, AVD_FMT_NV16, AVD_FMT_P010, AVD_FMT_I010)      # clips handed over as a tuple of planes
+_TAGGED_PLANES = {AVD_FMT_I422: "AVD_FMT_I422", AVD_FMT_NV16: "AVD_FMT_NV16", AVD_FMT_P010: "AVD_FMT_P010", AVD_FMT_I010: "AVD_FMT_I010"}      # ... through Pixels
 _FMT_NAMES = ("AVD_FMT_BGR24, AVD_FMT_NV12, AVD_FMT_I420, AVD_FMT_RGB24, AVD_FMT_BGRA32, AVD_FMT_RGBA32, AVD_FMT_RGBP, AVD_FMT_YUYV422, "
-              "AVD_FMT_UYVY422, AVD_FMT_I422 or AVD_FMT_NV16")
+              "AVD_FMT_UYVY422, AVD_FMT_I422, AVD_FMT_NV16, AVD_FMT_P010 or AVD_FMT_I010")
+
+
+def _wide_dtype(p) -> bool:
+    """is p a plane of 16-bit words: numpy uint16, torch uint16 or int16 (the same bits)"""
+    return str(getattr(p, "dtype", None)) in ("uint16", "torch.uint16", "torch.int16")
 
 
 def _chroma_shape(fmt: int, h: int, w: int):
-    """rows and bytes per row of a chroma plane: 4:2:0 halves the rows, the planar layouts halve the row"""
-    return (h if fmt in (AVD_FMT_I422, AVD_FMT_NV16) else h // 2, w // 2 if fmt in (AVD_FMT_I420, AVD_FMT_I422) else w)
+    """rows and samples per row of a chroma plane: 4:2:0 halves the rows, the planar layouts halve the row"""
+    return (h if fmt in (AVD_FMT_I422, AVD_FMT_NV16) else h // 2, w // 2 if fmt in (AVD_FMT_I420, AVD_FMT_I422, AVD_FMT_I010) else w)
 
 
 class Pixels:
@@ -89,17 +98,21 @@ class Pixels:
     data uint8[N,H,W,3] for AVD_FMT_RGB24 (and AVD_FMT_BGR24), uint8[N,H,W,4] for AVD_FMT_BGRA32 / AVD_FMT_RGBA32, uint8[N,3,H,W] for
     AVD_FMT_RGBP (channels first, R,G,B: what torchcodec and torchvision.io decode to), uint8[N,H,W,2] for the packed 4:2:2 layouts
     AVD_FMT_YUYV422 / AVD_FMT_UYVY422; a tuple of planes for AVD_FMT_I422 (y uint8[N,H,W], u and v uint8[N,H,W/2]) and AVD_FMT_NV16
-    (y, uv uint8[N,H,W]); numpy or torch, host or device.  An untagged array remains BGR, untagged tuples remain NV12 / I420."""
+    (y, uv uint8[N,H,W]); a tuple of uint16 planes for the 10-bit layouts AVD_FMT_P010 (y uint16[N,H,W], uv uint16[N,H/2,W]: the 10 bits in the
+    high bits) and AVD_FMT_I010 (y, u and v uint16[N,H/2,W/2]: in the low bits; a torch int16 tensor is read as the same bits); numpy or torch,
+    host or device.  An untagged array remains BGR, untagged tuples remain NV12 / I420."""
     __slots__ = ("data", "fmt")
 
     def __init__(self, data, fmt: int):
-        if fmt not in _PACKED and fmt not in (AVD_FMT_RGBP, AVD_FMT_I422, AVD_FMT_NV16):
+        if fmt not in _PACKED and fmt != AVD_FMT_RGBP and fmt not in _TAGGED_PLANES:
             raise ValueError("fmt must be AVD_FMT_BGR24, AVD_FMT_RGB24, AVD_FMT_BGRA32, AVD_FMT_RGBA32, AVD_FMT_RGBP, AVD_FMT_YUYV422, AVD_FMT_UYVY422, "
-                             f"AVD_FMT_I422 or AVD_FMT_NV16, got {fmt!r}")
-        if fmt in (AVD_FMT_I422, AVD_FMT_NV16):
+                             f"AVD_FMT_I422, AVD_FMT_NV16, AVD_FMT_P010 or AVD_FMT_I010, got {fmt!r}")
+        if fmt in _TAGGED_PLANES:
             data = tuple(data)
             if len(data) != _FMT_PLANES[fmt]:
-                raise ValueError(f"an {'AVD_FMT_I422' if fmt == AVD_FMT_I422 else 'AVD_FMT_NV16'} clip is a tuple of {_FMT_PLANES[fmt]} planes")
+                raise ValueError(f"an {_TAGGED_PLANES[fmt]} clip is a tuple of {_FMT_PLANES[fmt]} planes")
+            if fmt in _WIDE and not all(_wide_dtype(p) for p in data):
+                raise ValueError(f"the planes of an {_TAGGED_PLANES[fmt]} clip are uint16 (torch: uint16 or int16), got {[str(getattr(p, 'dtype', type(p).__name__)) for p in data]}")
         self.data, self.fmt = data, fmt
 
 
@@ -353,26 +366,29 @@ class Context:
         nv12 = len(planes) == 2
         if fmt is None:
             fmt = AVD_FMT_NV12 if nv12 else AVD_FMT_I420
-        ch = "H/2" if fmt in (AVD_FMT_NV12, AVD_FMT_I420) else "H"
-        layout = f"uint8[N,H,W] and uint8[N,{ch},W]" if nv12 else f"uint8[N,H,W], uint8[N,{ch},W/2] and uint8[N,{ch},W/2]"
+        ch = "H" if fmt in (AVD_FMT_I422, AVD_FMT_NV16) else "H/2"
+        wide = fmt in _WIDE                                    # 16-bit words: the shapes count samples, the strides handed on are bytes
+        ty, item = ("uint16", 2) if wide else ("uint8", 1)
+        layout = f"{ty}[N,H,W] and {ty}[N,{ch},W]" if nv12 else f"{ty}[N,H,W], {ty}[N,{ch},W/2] and {ty}[N,{ch},W/2]"
         torch_in = [_is_torch_tensor(p) for p in planes]
         if any(torch_in) != all(torch_in):
             raise ValueError("both planes must be numpy arrays or both torch tensors" if nv12 else
                              "the three planes must all be numpy arrays or all torch tensors")
         if all(torch_in):
             cuda = planes[0].is_cuda
-            if any(p.dim() != 3 or str(p.dtype) != "torch.uint8" or p.is_cuda != cuda for p in planes):
+            if any(p.dim() != 3 or (not _wide_dtype(p) if wide else str(p.dtype) != "torch.uint8") or p.is_cuda != cuda for p in planes):
                 raise ValueError(f"planes must be {layout} on the same device")
-            strides, ptr, dense = _TORCH_PLANE                 # uint8: torch's element strides are bytes
+            _, ptr, dense = _TORCH_PLANE                       # torch's strides count elements
+            strides = lambda t: tuple(v * item for v in t.stride())
         else:
             planes, cuda = tuple(np.asarray(p) for p in planes), False
-            if any(p.ndim != 3 or p.dtype != np.uint8 for p in planes):
+            if any(p.ndim != 3 or p.dtype != (np.uint16 if wide else np.uint8) for p in planes):
                 raise ValueError(f"planes must be {layout}")
             strides, ptr, dense = _NUMPY_PLANE
-        st = []                                                # per plane: (row stride, frame stride) as the library takes them
+        st = []                                                # per plane: (row stride, frame stride) in bytes, as the library takes them
         for i, p in enumerate(planes):
             f, r, e = strides(p)
-            if e != 1 or r < p.shape[2] or (p.shape[0] != 1 and f < r * p.shape[1]):
+            if e != item or r < p.shape[2] * item or (p.shape[0] != 1 and f < r * p.shape[1]):
                 p = dense(p)
                 planes = planes[:i] + (p,) + planes[i + 1:]
                 f, r, e = strides(p)
@@ -381,9 +397,9 @@ class Context:
         got = [tuple(p.shape) for p in planes[1:]]
         crows, cbytes = _chroma_shape(fmt, h, w)
         if nv12 and got != [(n, crows, cbytes)]:
-            raise ValueError(f"chroma plane must be uint8[{n},{crows},{cbytes}] (interleaved U,V), got {got[0]}")
+            raise ValueError(f"chroma plane must be {ty}[{n},{crows},{cbytes}] (interleaved U,V), got {got[0]}")
         if not nv12 and got != [(n, crows, cbytes)] * 2:
-            raise ValueError(f"chroma planes must be uint8[{n},{crows},{cbytes}] each, got {got[0]} and {got[1]}")
+            raise ValueError(f"chroma planes must be {ty}[{n},{crows},{cbytes}] each, got {got[0]} and {got[1]}")
         if not nv12 and st[1] != st[2]:
             raise ValueError(f"the U and V planes must have the same row and frame strides, got {st[1]} and {st[2]}")
         if cuda:
@@ -411,7 +427,7 @@ class Context:
         fmt = px.fmt
         if fmt == AVD_FMT_BGR24:
             return self._bgr(px.data)
-        if fmt in (AVD_FMT_I422, AVD_FMT_NV16):
+        if fmt in _TAGGED_PLANES:
             return self._plane_ptrs(px.data, fmt)
         torch_in = _is_torch_tensor(px.data)
         a = px.data if torch_in else np.asarray(px.data)
@@ -573,7 +589,9 @@ class Context:
         if fmt not in _FMT_PLANES:
             raise ValueError(f"fmt must be {_FMT_NAMES}, got {fmt!r}")
         nplanes = _FMT_PLANES[fmt]
-        px = _PACKED.get(fmt, 1)                               # bytes per pixel of plane 0
+        wide = fmt in _WIDE
+        ty, item = ("uint16", 2) if wide else ("uint8", 1)
+        px = _PACKED.get(fmt, item)                            # bytes per pixel of plane 0
         if fmt == AVD_FMT_RGBP:                                # a [3,H,W] frame contributes its three channel views as planes
             frames = list(frames)
             for i, f in enumerate(frames):
@@ -590,23 +608,24 @@ class Context:
         if not frames:                                         # an empty list has no picture to take a size from: any valid one
             L.h = L.w = HASH
             for p in range(nplanes):
-                L.row_stride[p] = HASH * px if p == 0 else _chroma_shape(fmt, HASH, HASH)[1]
+                L.row_stride[p] = HASH * px if p == 0 else _chroma_shape(fmt, HASH, HASH)[1] * item
             return L, 0, ()
         torch_in = [_is_torch_tensor(p) for f in frames for p in f]
         if any(torch_in) != all(torch_in):
             raise ValueError("the frames of a list are all numpy arrays or all torch tensors")
         if all(torch_in):
             first = frames[0][0]
-            if any(str(p.dtype) != "torch.uint8" or p.device != first.device for f in frames for p in f):
-                raise ValueError("the frames of a list are uint8 tensors on one device")
-            strides, ptr, _ = _TORCH_PLANE
+            if any((not _wide_dtype(p) if wide else str(p.dtype) != "torch.uint8") or p.device != first.device for f in frames for p in f):
+                raise ValueError(f"the frames of a list are {ty} tensors on one device")
+            _, ptr, _ = _TORCH_PLANE
+            strides = lambda t: tuple(v * item for v in t.stride())      # torch counts elements, the library bytes
             if first.is_cuda:
                 L.mem = AVD_MEM_DEVICE
                 self._after_torch_stream(first)
         else:
             frames = [tuple(np.asarray(p) for p in f) for f in frames]
-            if any(p.dtype != np.uint8 for f in frames for p in f):
-                raise ValueError("the frames of a list are uint8 arrays")
+            if any(p.dtype != (np.uint16 if wide else np.uint8) for f in frames for p in f):
+                raise ValueError(f"the frames of a list are {ty} arrays")
             strides, ptr, _ = _NUMPY_PLANE
         h, w = int(frames[0][0].shape[0]), int(frames[0][0].shape[1])
         if fmt in _YUV_PLANES:
@@ -615,10 +634,10 @@ class Context:
             shapes = [(h, w)] * 3 if fmt == AVD_FMT_RGBP else [(h, w, px)]
         arrays = []
         for p in range(nplanes):
-            dense = (px, 1) if fmt in _PACKED else (1,)
+            dense = (px, 1) if fmt in _PACKED else (item,)
             for i, f in enumerate(frames):
                 if tuple(f[p].shape) != shapes[p]:
-                    raise ValueError(f"frame {i}: plane {p} must be uint8{list(shapes[p])}, got {list(f[p].shape)}")
+                    raise ValueError(f"frame {i}: plane {p} must be {ty}{list(shapes[p])}, got {list(f[p].shape)}")
                 st = tuple(strides(f[p]))
                 if st[1:] != dense:
                     raise ValueError(f"frame {i}: the rows of plane {p} are not dense (element strides {st[1:]})")

@@ -211,7 +211,7 @@ class FrameAnalyzer:
         frames = [(np.asarray(it),) if single else tuple(np.asarray(p) for p in it) for it in items]
         # Frames go through as they lie -- row-padded decoder frames included -- while plane by plane their rows are dense and all frames share
         # one row stride, which is what a list takes.  Only a chunk that breaks that rule is copied (every plane to tight rows).
-        tail = (_lib._PACKED[fmt], 1) if fmt in _lib._PACKED else (1,)
+        tail = (_lib._PACKED[fmt], 1) if fmt in _lib._PACKED else (2 if fmt in _lib._WIDE else 1,)      # byte strides behind the rows
         agree = all(p.ndim == lead + len(tail) + 1 and p.strides[lead + 1:] == tail and p.strides[lead] == q.strides[lead]
                     for f in frames for p, q in zip(f, frames[0]))
         if not agree:
@@ -241,6 +241,15 @@ class FrameAnalyzer:
     # A turned 4:2:2 picture is not on the path: the library refuses rotate != 0 (include/avd.h)
     def records_stream_i422(self, surfaces, rotate: int = 0, full_range: bool = False) -> np.ndarray:
         return self._stream(surfaces, lambda items: self._flush_list(items, _lib.AVD_FMT_I422, rotate, full_range))
+
+    # -- 10-bit 4:2:0 in 16-bit words (include/avd.h): P010 surfaces (VCN / rocDecode), an iterable of (y uint16[H,W], uv uint16[H/2,W]) pairs with
+    # the 10 bits in the high bits; yuv420p10le pictures (libavcodec), (y uint16[H,W], u uint16[H/2,W/2], v likewise) triples with them in the low
+    # bits.  The words are narrowed where the fused pass loads them: neither a stacked nor a narrowed copy exists anywhere
+    def records_stream_p010(self, surfaces, rotate: int = 0, full_range: bool = False) -> np.ndarray:
+        return self._stream(surfaces, lambda items: self._flush_list(items, _lib.AVD_FMT_P010, rotate, full_range))
+
+    def records_stream_i010(self, surfaces, rotate: int = 0, full_range: bool = False) -> np.ndarray:
+        return self._stream(surfaces, lambda items: self._flush_list(items, _lib.AVD_FMT_I010, rotate, full_range))
 
 
 class ClipsInFlight:

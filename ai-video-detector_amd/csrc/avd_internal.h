@@ -90,7 +90,9 @@ BandPlan band_plan(int w);
 // What launch_preprocess ran last on a context: read by tests through avd_debug_fetch "ingest_plan" (eight int32 in this order).
 enum IngestKernel { kIngestBgrScalar = 0, kIngestBgrVec16, kIngestBgrStaged, kIngestNv12Scalar, kIngestNv12Tables, kIngestI420Scalar, kIngestI420Tables,
                     kIngestNv12Strip, kIngestI420Strip, kIngestPx32Scalar, kIngestPx32Vec16, kIngestRgbpScalar, kIngestRgbpVec16, kIngestRgbpStaged,
-                    kIngestYuyvScalar, kIngestYuyvTables, kIngestI422Scalar, kIngestI422Tables, kIngestNv16Scalar, kIngestNv16Tables };
+                    kIngestYuyvScalar, kIngestYuyvTables, kIngestI422Scalar, kIngestI422Tables, kIngestNv16Scalar, kIngestNv16Tables,
+                    kIngestP010Scalar, kIngestP010Tables, kIngestI010Scalar, kIngestI010Tables, kIngestP010Strip, kIngestI010Strip };
+static_assert(kIngestP010Scalar == 20 && kIngestI010Strip == 25, "the ids include/avd.h lists");
 struct IngestPlan { int h, w, rows_per_band, nbands, pitch, ni, lds_bytes, kernel; };
 static_assert(sizeof(IngestPlan) == 8 * sizeof(int), "avd_debug_fetch hands the struct out as int32[8]");
 // What the last ingest of a context did; avd_debug_fetch hands each member out under the name beside it.  launch_preprocess records the launch,

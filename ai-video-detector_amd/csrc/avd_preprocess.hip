@@ -1,4 +1,4 @@
-// avd_preprocess.hip -- fused full-resolution pass over decoded frames (gfx950): BGR, RGB in four layouts, NV12, I420, 4:2:2 in four layouts.
+// avd_preprocess.hip -- fused full-resolution pass over decoded frames (gfx950): BGR, RGB in four layouts, NV12, I420, 4:2:2 in four layouts, 10-bit 4:2:0 in two.
 //
 // One read of each frame from HBM produces everything the reference derives
 // from full-resolution pixels (reference app/analyzers/video.py):
@@ -608,10 +608,10 @@ __device__ __forceinline__ unsigned gray4_nv12(unsigned yw, unsigned cw, const Y
            (gray_from_yuv((yw >> 16) & 0xFF, t1, k.cy) << 16) | (gray_from_yuv(yw >> 24, t1, k.cy) << 24);
 }
 
-// 4:2:0, any geometry / alignment: one pixel per work item.  chroma(y >> 1, x >> 1, U, V) fetches the pixel's chroma sample: the surface
-// kinds differ in nothing else.  FLIP: the stored picture is the displayed one turned by 180 degrees -- displayed (y, x) is stored
+// 4:2:0, any geometry / alignment: one pixel per work item.  Luma::at(row, x) fetches the pixel's luma sample from its stored row, chroma(y >> 1, x >> 1, U, V) its
+// chroma sample (8-bit values: a 16-bit layout narrows them): the surface kinds differ in nothing else.  FLIP: the stored picture is the displayed one turned by 180 degrees -- displayed (y, x) is stored
 // (h - 1 - y, w - 1 - x), and with even h and w its chroma sample is the mirrored one.
-template <bool FLIP, typename ChromaAt>
+template <bool FLIP, typename Luma, typename ChromaAt>
 __device__ __forceinline__ void fill_yuv420_scalar(uint8_t* tile, const uint8_t* yfr, const YuvConsts& k, const PreParams& P, const Band& b, int tid,
                                                    ChromaAt chroma)
 {
@@ -623,7 +623,7 @@ __device__ __forceinline__ void fill_yuv420_scalar(uint8_t* tile, const uint8_t*
         int U, V;
         chroma(sy >> 1, sx >> 1, U, V);
         const ChromaTerms t = chroma_terms(U, V, k);
-        tile[tr * pitch + kPad + x] = (uint8_t)gray_from_yuv(yfr[(int64_t)sy * P.row_stride + sx], t, k.cy);
+        tile[tr * pitch + kPad + x] = (uint8_t)gray_from_yuv(Luma::at(yfr + (int64_t)sy * P.row_stride, sx), t, k.cy);
     }
 }
 
@@ -659,11 +659,12 @@ __device__ __forceinline__ unsigned* build_gray_tables(uint8_t* tile, int trows,
 // Three LDS tables of cv2's gray weight times T (3735 T, 19235 T + the rounding 2^14, 9798 T; 32-bit entries, index bias k.bias), so a pixel is
 // three index additions, three ds_read_b32, one three-operand add and a shift -- instead of three multiply-adds, three shifts, three clamps and
 // three multiply-adds (12.3 -> 8.8 vector instructions per pixel; the LDS pipe does the lookups beside them).  Same integers by construction.
-// chroma8(p, c, t) forms the eight chroma-term triples of chroma row p, 16-pixel chunk c: the surface kinds differ in nothing else.
+// Luma::chunk(row, c): the 16 luma bytes of 16-pixel chunk c of a stored row; chroma8(p, c, t) forms the eight chroma-term triples of chroma row p, chunk c:
+// the surface kinds differ in nothing else.
 // FLIP (half turn): the work item of displayed chroma row p, chunk c reads the MIRRORED stored chunk -- chroma row h/2 - 1 - p, chunk
 // chunks - 1 - c, luma rows h - 1 - y -- with the same 16-byte loads, and reverses the bytes in registers: displayed byte i of the chunk is
 // stored byte 15 - i, whose chroma pair is 7 - (i >> 1).
-template <bool FLIP, typename Chroma8>
+template <bool FLIP, typename Luma, typename Chroma8>
 __device__ __forceinline__ void fill_yuv420_tables(uint8_t* tile, const uint8_t* yfr, const YuvConsts& k, const PreParams& P, const Band& b, int tid,
                                                    Chroma8 chroma8)
 {
@@ -687,7 +688,7 @@ __device__ __forceinline__ void fill_yuv420_tables(uint8_t* tile, const uint8_t*
         for (int s2 = 0; s2 < 2; s2++) {
             const int y = 2 * p + s2;
             if (y < ya || y > yb) continue;
-            const uint4 yy = *reinterpret_cast<const uint4*>(yfr + (int64_t)(FLIP ? h - 1 - y : y) * P.row_stride + cs * 16);
+            const uint4 yy = Luma::chunk(yfr + (int64_t)(FLIP ? h - 1 - y : y) * P.row_stride, cs);
             unsigned yw[4] = {yy.x, yy.y, yy.z, yy.w};
             if (FLIP) {
                 yw[0] = __builtin_bswap32(yy.w); yw[1] = __builtin_bswap32(yy.z); yw[2] = __builtin_bswap32(yy.y); yw[3] = __builtin_bswap32(yy.x);
@@ -779,14 +780,33 @@ __device__ __forceinline__ void load_span(const uint8_t* p, int len, unsigned (&
     }
 }
 
+// the same for the 16-bit layouts, whose spans are twice as long: a span of at least 16 * FULL bytes -- the common case, every band but a clip's
+// first and last has all 16 rows -- takes them as FULL 16-byte copies (the address is only 2-byte aligned: unaligned global access again) and
+// load_span's pieces for what is left; `full` is uniform over the workgroup
+template <int FULL, int NW>
+__device__ __forceinline__ void load_span_wide(const uint8_t* p, int len, unsigned (&wd)[NW])
+{
+    static_assert(4 * FULL <= NW, "the 16-byte copies fit the words");
+    if (len >= 16 * FULL) {
+        __builtin_memcpy(&wd[0], p, 16 * FULL);
+        if constexpr (NW > 4 * FULL) {
+            unsigned rest[NW - 4 * FULL];
+            load_span(p + 16 * FULL, len - 16 * FULL, rest);
+#pragma unroll
+            for (int k = 0; k < NW - 4 * FULL; k++) wd[4 * FULL + k] = rest[k];
+        }
+    } else load_span(p, len, wd);
+}
+
 __device__ __forceinline__ unsigned span_byte(const unsigned* wd, int i) { return (wd[i >> 2] >> (8 * (i & 3))) & 0xFF; }
 
 constexpr int kStripSpan = kBandCap + 2;               // luma bytes of a span at most
 constexpr int kStripChroma = kStripSpan / 2 + 1;       // chroma samples under them at most (a span that starts on an odd column)
 static_assert(kStripSpan == 16, "load_span<4> holds the luma span");
 
-// chroma9(cy, q0, nq, t): the chroma-term triples of samples [q0, q0 + nq) of stored chroma row cy.  The surface kinds differ in nothing else.
-template <int ROT, typename Chroma9>
+// Luma::span(row, s0, len, yw): the `len` luma bytes from column s0 of a stored row, little-endian into four words; chroma9(cy, q0, nq, t): the
+// chroma-term triples of samples [q0, q0 + nq) of stored chroma row cy.  The surface kinds differ in nothing else.
+template <int ROT, typename Luma, typename Chroma9>
 __device__ __forceinline__ void fill_yuv420_strip(uint8_t* tile, const uint8_t* yfr, const YuvConsts& k, const PreParams& P, const Band& b, int tid,
                                                   Chroma9 chroma9)
 {
@@ -809,7 +829,7 @@ __device__ __forceinline__ void fill_yuv420_strip(uint8_t* tile, const uint8_t* 
         for (int c = tid; c < w; c += kThreads) {
             const int sr = ROT == 1 ? w - 1 - c : c;          // the stored row of displayed column c
             unsigned yw[4];
-            load_span<4>(yfr + (int64_t)sr * P.row_stride + s0, len, yw);
+            Luma::span(yfr + (int64_t)sr * P.row_stride, s0, len, yw);
             ChromaTerms t[kStripChroma];
             chroma9(sr >> 1, q0, nq, t);
             uint8_t* d = dst0 + c;
@@ -824,6 +844,66 @@ __device__ __forceinline__ void fill_yuv420_strip(uint8_t* tile, const uint8_t* 
     __syncthreads();
     reflect_tile_rows(tile, trows, pitch, (w + 15) >> 4, ylo < 0, yhi > h - 1, tid);      // the last word may end in the tile row's padding
 }
+
+// ---- luma of the 4:2:0 fills: 8-bit planes (NV12, I420) load it as it lies ----
+struct Luma8 {
+    static __device__ __forceinline__ int at(const uint8_t* row, int x) { return row[x]; }
+    static __device__ __forceinline__ uint4 chunk(const uint8_t* row, int c) { return *reinterpret_cast<const uint4*>(row + c * 16); }
+    static __device__ __forceinline__ void span(const uint8_t* row, int s0, int len, unsigned (&yw)[4]) { load_span<4>(row + s0, len, yw); }
+};
+
+// ---- 16-bit samples (little-endian words).  HIGH: the 10 bits sit in the high bits (AVD_FMT_P010; P016 reads the same way), else in the low
+// bits (AVD_FMT_I010).  Every word s narrows to s8 = min(255, (s + 128) >> 8) resp. min(255, (s + 2) >> 2) -- total over all 65536 words --
+// and from there on the picture is the 8-bit one: the words below are exactly what the 8-bit fills hold after their loads.
+template <bool HIGH>
+__device__ __forceinline__ int narrow1(unsigned s)          // s: one word, 0 .. 65535
+{
+    return (int)(HIGH ? min(255u, (s + 128u) >> 8) : min(255u, (s + 2u) >> 2));
+}
+__device__ __forceinline__ unsigned load_u16(const uint8_t* p) { return *reinterpret_cast<const uint16_t*>(p); }      // planes and strides are 2-byte aligned (check_clip)
+
+// two words in the 16-bit lanes of a dword, narrowed in place.  HIGH: one saturating packed add (v_pk_add_u16 clamp: a word from 0xFF80 up stays
+// 0xFFFF, so the min is free), s8 is the lane's HIGH byte; else a saturating packed add, a packed shift and a packed min, s8 is the lane's LOW byte
+using u16x2 = unsigned short __attribute__((ext_vector_type(2)));
+template <bool HIGH>
+__device__ __forceinline__ unsigned narrow_pk(unsigned w)
+{
+    u16x2 v = __builtin_bit_cast(u16x2, w);
+    if (HIGH) v = __builtin_elementwise_add_sat(v, (u16x2)(128));
+    else v = __builtin_elementwise_min(__builtin_elementwise_add_sat(v, (u16x2)(2)) >> (u16x2)(2), (u16x2)(255));
+    return __builtin_bit_cast(unsigned, v);
+}
+template <bool HIGH> __device__ __forceinline__ unsigned pk_lo(unsigned pk) { return HIGH ? (pk >> 8) & 0xFF : pk & 0xFF; }      // s8 of the first word
+template <bool HIGH> __device__ __forceinline__ unsigned pk_hi(unsigned pk) { return HIGH ? pk >> 24 : (pk >> 16) & 0xFF; }       // of the second
+// four words (two dwords) -> their four s8 bytes, in order: one v_perm picks them
+template <bool HIGH>
+__device__ __forceinline__ unsigned narrow4(unsigned a, unsigned b)
+{
+    return __builtin_amdgcn_perm(narrow_pk<HIGH>(b), narrow_pk<HIGH>(a), HIGH ? 0x07050301u : 0x06040200u);
+}
+template <bool HIGH> __device__ __forceinline__ uint2 narrow8(const uint4& a) { return make_uint2(narrow4<HIGH>(a.x, a.y), narrow4<HIGH>(a.z, a.w)); }
+// sixteen words at p (two 16-byte loads) -> their 16 s8 bytes
+template <bool HIGH>
+__device__ __forceinline__ uint4 load_narrow16(const uint8_t* p)
+{
+    const uint4* src = reinterpret_cast<const uint4*>(p);
+    const uint2 lo = narrow8<HIGH>(src[0]), hi = narrow8<HIGH>(src[1]);
+    return make_uint4(lo.x, lo.y, hi.x, hi.y);
+}
+
+template <bool HIGH>
+struct Luma16 {
+    static __device__ __forceinline__ int at(const uint8_t* row, int x) { return narrow1<HIGH>(load_u16(row + 2 * x)); }
+    static __device__ __forceinline__ uint4 chunk(const uint8_t* row, int c) { return load_narrow16<HIGH>(row + c * 32); }
+    // the span is 2 * len <= 32 bytes at a 2-byte aligned address; words beyond it are zero and narrow to bytes nobody reads
+    static __device__ __forceinline__ void span(const uint8_t* row, int s0, int len, unsigned (&yw)[4])
+    {
+        unsigned wd[8];
+        load_span_wide<2>(row + 2 * s0, 2 * len, wd);
+#pragma unroll
+        for (int j = 0; j < 4; j++) yw[j] = narrow4<HIGH>(wd[2 * j], wd[2 * j + 1]);
+    }
+};
 
 // ---- the layouts ----------------------------------------------------------------------------------------------------------------------
 // A fill policy is what a layout contributes to a kernel: planes<FR>() forms the frame bases of its N planes (frame_base<FR>) from plane 0 and
@@ -944,7 +1024,7 @@ struct Nv12 {
     {
         const uint8_t *yfr = fr.p[0], *cfr = fr.p[1];
         if constexpr (ROT & 1)             // sample q of a chroma row is the byte pair at 2q
-            fill_yuv420_strip<ROT>(tile, yfr, nv.k, P, b, tid, [&](int cy, int q0, int nq, ChromaTerms (&t)[kStripChroma]) {
+            fill_yuv420_strip<ROT, Luma8>(tile, yfr, nv.k, P, b, tid, [&](int cy, int q0, int nq, ChromaTerms (&t)[kStripChroma]) {
                 unsigned cw[(kStripChroma + 1) / 2];
                 load_span(cfr + (int64_t)cy * nv.uv_row_stride + q0 * 2, nq * 2, cw);
 #pragma unroll
@@ -952,11 +1032,11 @@ struct Nv12 {
                     if (j < nq) t[j] = chroma_offsets(span_byte(cw, 2 * j), span_byte(cw, 2 * j + 1), nv.k);
             });
         else if (VEC)                      // the 16 chroma bytes of a chunk are one 16-byte load, pair j = bytes 2j (U) and 2j + 1 (V)
-            fill_yuv420_tables<ROT == 2>(tile, yfr, nv.k, P, b, tid, [&](int p, int c, ChromaTerms (&t)[8]) {
+            fill_yuv420_tables<ROT == 2, Luma8>(tile, yfr, nv.k, P, b, tid, [&](int p, int c, ChromaTerms (&t)[8]) {
                 chroma8_interleaved(*reinterpret_cast<const uint4*>(cfr + (int64_t)p * nv.uv_row_stride + c * 16), nv.k, t);
             });
         else
-            fill_yuv420_scalar<ROT == 2>(tile, yfr, nv.k, P, b, tid, [&](int cy, int cx, int& U, int& V) {
+            fill_yuv420_scalar<ROT == 2, Luma8>(tile, yfr, nv.k, P, b, tid, [&](int cy, int cx, int& U, int& V) {
                 const uint8_t* cp = cfr + (int64_t)cy * nv.uv_row_stride + cx * 2;
                 U = cp[0]; V = cp[1];
             });
@@ -976,7 +1056,7 @@ struct I420 {
     {
         const uint8_t *yfr = fr.p[0], *ufr = fr.p[1], *vfr = fr.p[2];
         if constexpr (ROT & 1)             // sample q is byte q of the U row and of the V row
-            fill_yuv420_strip<ROT>(tile, yfr, ip.k, P, b, tid, [&](int cy, int q0, int nq, ChromaTerms (&t)[kStripChroma]) {
+            fill_yuv420_strip<ROT, Luma8>(tile, yfr, ip.k, P, b, tid, [&](int cy, int q0, int nq, ChromaTerms (&t)[kStripChroma]) {
                 const int64_t o = (int64_t)cy * ip.c_row_stride + q0;
                 unsigned uw[(kStripChroma + 3) / 4], vw[(kStripChroma + 3) / 4];
                 load_span(ufr + o, nq, uw);
@@ -988,14 +1068,93 @@ struct I420 {
         // Y plane 16-byte aligned, U and V planes 8-byte aligned: the 16 chroma bytes of a chunk are two 8-byte loads, 8 U and 8 V; pair j = U byte
         // j and V byte j.  (A contiguous frame has its V plane at 5wh/4, which w % 16 == 0 makes a multiple of 8 but not of 16.)
         else if (VEC)
-            fill_yuv420_tables<ROT == 2>(tile, yfr, ip.k, P, b, tid, [&](int p, int c, ChromaTerms (&t)[8]) {
+            fill_yuv420_tables<ROT == 2, Luma8>(tile, yfr, ip.k, P, b, tid, [&](int p, int c, ChromaTerms (&t)[8]) {
                 const int64_t o = (int64_t)p * ip.c_row_stride + c * 8;
                 chroma8_planar(*reinterpret_cast<const uint2*>(ufr + o), *reinterpret_cast<const uint2*>(vfr + o), ip.k, t);
             });
         else
-            fill_yuv420_scalar<ROT == 2>(tile, yfr, ip.k, P, b, tid, [&](int cy, int cx, int& U, int& V) {
+            fill_yuv420_scalar<ROT == 2, Luma8>(tile, yfr, ip.k, P, b, tid, [&](int cy, int cx, int& U, int& V) {
                 const int64_t o = (int64_t)cy * ip.c_row_stride + cx;
                 U = ufr[o]; V = vfr[o];
+            });
+    }
+};
+
+// ---- 10-bit 4:2:0 in 16-bit words (AVD_FMT_P010, AVD_FMT_I010): every sample is narrowed to 8 bits where it is loaded (narrow1 / narrow_pk) and
+// the fills above run on what NV12 / I420 would have loaded.  Strides stay in BYTES; a luma row has 2w bytes.
+// P010: NV12's planes, the 10 bits in the high bits of each word.  A chroma row has w words, sample q is the word pair at 4q
+template <bool VEC, int ROT>
+struct P010 {
+    static constexpr IngestKernel id = (ROT & 1) ? kIngestP010Strip : VEC ? kIngestP010Tables : kIngestP010Scalar;
+    template <Frames FR>
+    static __device__ __forceinline__ PlaneSet<2> planes(const uint8_t* yplane, const Nv12Params& nv, const PreParams& P, int f)
+    {
+        return Nv12<VEC, ROT>::template planes<FR>(yplane, nv, P, f);
+    }
+    static __device__ __forceinline__ void fill(uint8_t* tile, const PlaneSet<2>& fr, const Nv12Params& nv, const PreParams& P, const Band& b, int tid)
+    {
+        const uint8_t *yfr = fr.p[0], *cfr = fr.p[1];
+        using Luma = Luma16<true>;
+        if constexpr (ROT & 1)             // nq <= kStripChroma samples = that many dwords, U in the low and V in the high lane
+            fill_yuv420_strip<ROT, Luma>(tile, yfr, nv.k, P, b, tid, [&](int cy, int q0, int nq, ChromaTerms (&t)[kStripChroma]) {
+                unsigned cw[kStripChroma];
+                load_span_wide<2>(cfr + (int64_t)cy * nv.uv_row_stride + q0 * 4, nq * 4, cw);
+#pragma unroll
+                for (int j = 0; j < kStripChroma; j++)
+                    if (j < nq) {
+                        const unsigned pk = narrow_pk<true>(cw[j]);
+                        t[j] = chroma_offsets(pk_lo<true>(pk), pk_hi<true>(pk), nv.k);
+                    }
+            });
+        else if (VEC)                      // the 16 chroma words of a chunk are two 16-byte loads; narrowed they are NV12's 16 chroma bytes
+            fill_yuv420_tables<ROT == 2, Luma>(tile, yfr, nv.k, P, b, tid, [&](int p, int c, ChromaTerms (&t)[8]) {
+                chroma8_interleaved(load_narrow16<true>(cfr + (int64_t)p * nv.uv_row_stride + c * 32), nv.k, t);
+            });
+        else
+            fill_yuv420_scalar<ROT == 2, Luma>(tile, yfr, nv.k, P, b, tid, [&](int cy, int cx, int& U, int& V) {
+                const uint8_t* cp = cfr + (int64_t)cy * nv.uv_row_stride + cx * 4;
+                U = narrow1<true>(load_u16(cp)); V = narrow1<true>(load_u16(cp + 2));
+            });
+    }
+};
+
+// I010 (yuv420p10le; V-first with the chroma pointers exchanged): I420's planes, the 10 bits in the low bits of each word.  A chroma row has
+// w / 2 words per plane, sample q is word q of the U row and of the V row
+template <bool VEC, int ROT>
+struct I010 {
+    static constexpr IngestKernel id = (ROT & 1) ? kIngestI010Strip : VEC ? kIngestI010Tables : kIngestI010Scalar;
+    template <Frames FR>
+    static __device__ __forceinline__ PlaneSet<3> planes(const uint8_t* yplane, const I420Params& ip, const PreParams& P, int f)
+    {
+        return I420<VEC, ROT>::template planes<FR>(yplane, ip, P, f);
+    }
+    static __device__ __forceinline__ void fill(uint8_t* tile, const PlaneSet<3>& fr, const I420Params& ip, const PreParams& P, const Band& b, int tid)
+    {
+        const uint8_t *yfr = fr.p[0], *ufr = fr.p[1], *vfr = fr.p[2];
+        using Luma = Luma16<false>;
+        if constexpr (ROT & 1)             // nq <= kStripChroma words per plane, two to a dword
+            fill_yuv420_strip<ROT, Luma>(tile, yfr, ip.k, P, b, tid, [&](int cy, int q0, int nq, ChromaTerms (&t)[kStripChroma]) {
+                const int64_t o = (int64_t)cy * ip.c_row_stride + q0 * 2;
+                unsigned uw[(kStripChroma + 1) / 2], vw[(kStripChroma + 1) / 2];
+                load_span_wide<1>(ufr + o, nq * 2, uw);
+                load_span_wide<1>(vfr + o, nq * 2, vw);
+#pragma unroll
+                for (int i = 0; i < (kStripChroma + 1) / 2; i++) { uw[i] = narrow_pk<false>(uw[i]); vw[i] = narrow_pk<false>(vw[i]); }
+#pragma unroll
+                for (int j = 0; j < kStripChroma; j++)
+                    if (j < nq) t[j] = chroma_offsets(span_byte(uw, 2 * j), span_byte(vw, 2 * j), ip.k);      // the low byte of lane j
+            });
+        // every plane 16-byte aligned: the 8 U and the 8 V words of a chunk are one 16-byte load each; narrowed they are I420's 8 + 8 chroma bytes.
+        // (A contiguous frame has its V plane at 5wh/2 bytes, which w % 16 == 0 and an even h make a multiple of 16.)
+        else if (VEC)
+            fill_yuv420_tables<ROT == 2, Luma>(tile, yfr, ip.k, P, b, tid, [&](int p, int c, ChromaTerms (&t)[8]) {
+                const int64_t o = (int64_t)p * ip.c_row_stride + c * 16;
+                chroma8_planar(narrow8<false>(*reinterpret_cast<const uint4*>(ufr + o)), narrow8<false>(*reinterpret_cast<const uint4*>(vfr + o)), ip.k, t);
+            });
+        else
+            fill_yuv420_scalar<ROT == 2, Luma>(tile, yfr, ip.k, P, b, tid, [&](int cy, int cx, int& U, int& V) {
+                const int64_t o = (int64_t)cy * ip.c_row_stride + cx * 2;
+                U = narrow1<false>(load_u16(ufr + o)); V = narrow1<false>(load_u16(vfr + o));
             });
     }
 };
@@ -1253,7 +1412,8 @@ static constexpr bool is_staged(IngestKernel id) { return id == kIngestBgrStaged
 static constexpr bool has_gray_tables(IngestKernel id)
 {
     return id == kIngestNv12Tables || id == kIngestNv12Strip || id == kIngestI420Tables || id == kIngestI420Strip || id == kIngestYuyvTables ||
-           id == kIngestI422Tables || id == kIngestNv16Tables;
+           id == kIngestI422Tables || id == kIngestNv16Tables || id == kIngestP010Tables || id == kIngestI010Tables || id == kIngestP010Strip ||
+           id == kIngestI010Strip;
 }
 
 // POL's kernel: the staged body for the staged fills, the generic one for every other
@@ -1279,8 +1439,10 @@ int launch_preprocess(avd_ctx* ctx, const IngestClip& clip, const uint8_t* d_in,
     const bool bgr = !clip.is_yuv(), planar = clip.planar_yuv(), yuv422 = clip.is_422();
     const bool rgbp = clip.format == AVD_FMT_RGBP, px32 = clip.format == AVD_FMT_BGRA32 || clip.format == AVD_FMT_RGBA32;
     const bool rgb = clip.format == AVD_FMT_RGB24 || clip.format == AVD_FMT_RGBA32;     // packed pixels stored R, G, B
-    // the planar chroma planes are read 8 bytes at a time (I420's and I422's table fills), every other plane 16; packed 4:2:2 has no other plane
-    const bool chroma_ok = planar ? aligned_to(8, d_uv, clip.uv_row_stride, clip.uv_frame_stride) && aligned_to(8, d_v, clip.uv_row_stride, clip.uv_frame_stride)
+    const bool wide = clip.is_16bit();                 // P010 (with NV12's planes) and I010 (with I420's)
+    // the planar chroma planes are read 8 bytes at a time (I420's and I422's table fills; I010's 16), every other plane 16; packed 4:2:2 has no other plane
+    const int ca = wide ? 16 : 8;
+    const bool chroma_ok = planar ? aligned_to(ca, d_uv, clip.uv_row_stride, clip.uv_frame_stride) && aligned_to(ca, d_v, clip.uv_row_stride, clip.uv_frame_stride)
                            : rgbp ? aligned16(d_uv, clip.uv_row_stride, clip.uv_frame_stride) && aligned16(d_v, clip.uv_row_stride, clip.uv_frame_stride)
                                   : bgr || clip.planes() == 1 || aligned16(d_uv, clip.uv_row_stride, clip.uv_frame_stride);
     const bool vec = list ? list->aligned : P.w % 16 == 0 && aligned16(d_in, clip.row_stride, clip.frame_stride) && chroma_ok;
@@ -1335,12 +1497,18 @@ int launch_preprocess(avd_ctx* ctx, const IngestClip& clip, const uint8_t* d_in,
         });
     } else if (planar) {
         const I420Params ip{d_uv, d_v, clip.uv_row_stride, clip.uv_frame_stride, yc};
-        dispatch_turn(vec, rot, [&](auto v, auto r) { launch(I420<decltype(v)::value, decltype(r)::value>{}, ip); });
+        dispatch_turn(vec, rot, [&](auto v, auto r) {
+            if (wide) launch(I010<decltype(v)::value, decltype(r)::value>{}, ip);
+            else launch(I420<decltype(v)::value, decltype(r)::value>{}, ip);
+        });
     } else if (!bgr) {
         // (a register-staged variant in the style of k_preprocess_vec measured no faster: the kernel is bound by the
         // conversion's integer arithmetic, not by how its loads are issued -- profiles/r02_experiments.md)
         const Nv12Params nv{d_uv, clip.uv_row_stride, clip.uv_frame_stride, yc};
-        dispatch_turn(vec, rot, [&](auto v, auto r) { launch(Nv12<decltype(v)::value, decltype(r)::value>{}, nv); });
+        dispatch_turn(vec, rot, [&](auto v, auto r) {
+            if (wide) launch(P010<decltype(v)::value, decltype(r)::value>{}, nv);
+            else launch(Nv12<decltype(v)::value, decltype(r)::value>{}, nv);
+        });
     } else if (rgbp) {
         const RgbpParams rp{d_uv, d_v};
         // BGR's band plan and NI classes: the chunk has the same register footprint

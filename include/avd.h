@@ -29,7 +29,8 @@
  *     AVD_MEM_HOST nor AVD_MEM_DEVICE (AVD_ERR_ARG); a size out of range -- n < 0, h or w outside 1 .. 16384
  *     (AVD_ERR_ARG); an odd width or height of 4:2:0 input (AVD_ERR_UNSUPPORTED); a picture below 32 x 32
  *     (AVD_ERR_UNSUPPORTED); a null plane of a clip with n > 0 (AVD_ERR_ARG); strides smaller than the planes
- *     (AVD_ERR_ARG).  What an avd_picture alone can get wrong is refused before any of these, in this order:
+ *     (AVD_ERR_ARG); of a picture in 16-bit words (AVD_FMT_P010 / _I010), a plane base, row stride or frame stride that is odd (AVD_ERR_ARG).
+ *     What an avd_picture alone can get wrong is refused before any of these, in this order:
  *     struct_size; format (an unknown layout in the low byte, or a bit above it other than AVD_FMT_FULL_RANGE);
  *     AVD_FMT_FULL_RANGE on a BGR or RGB picture; rotate; reserved; BGR or RGB with a rotation; U and V (RGBP: R, G and B)
  *     strides that differ.
@@ -207,10 +208,10 @@ int avd_analyze_frames_i420_async(avd_ctx* ctx, const uint8_t* y, const uint8_t*
  * half turn reads the mirrored rows and chunks of the same kernels, a quarter turn reads of every stored row the 16-byte span a band needs (the
  * strip fill); no turned picture exists in memory.
  *   struct_size  sizeof(avd_picture) of the caller's header; anything else is AVD_ERR_ARG
- *   plane        BGR: [0]; NV12: Y, interleaved UV; I420: Y, U, V (YV12: exchange [1] and [2]); the RGB and 4:2:2 layouts: below the struct's format enum
- *   row_stride, frame_stride   bytes, per plane; I420 and I422: [1] == [2] (AVD_ERR_ARG otherwise); RGBP: [0] == [1] == [2]
+ *   plane        BGR: [0]; NV12: Y, interleaved UV; I420: Y, U, V (YV12: exchange [1] and [2]); the RGB, 4:2:2 and 10-bit layouts: below the struct's format enum
+ *   row_stride, frame_stride   bytes, per plane; I420, I422 and I010: [1] == [2] (AVD_ERR_ARG otherwise); RGBP: [0] == [1] == [2]
  *   h, w         the stored picture;  rotate  quarter turns clockwise from the stored to the displayed picture, 0 .. 3;  reserved  0
- *   format       the layout (AVD_FMT_BGR24 / _NV12 / _I420 / _RGB24 / _BGRA32 / _RGBA32 / _RGBP / _YUYV422 / _UYVY422 / _I422 / _NV16), for the 4:2:0 and 4:2:2
+ *   format       the layout (AVD_FMT_BGR24 / _NV12 / _I420 / _RGB24 / _BGRA32 / _RGBA32 / _RGBP / _YUYV422 / _UYVY422 / _I422 / _NV16 / _P010 / _I010), for the 4:2:0 and 4:2:2
  *                layouts optionally OR-ed with AVD_FMT_FULL_RANGE
  * Refused without a launch: rotate outside 0 .. 3, a non-zero reserved, a bad format or struct_size (AVD_ERR_ARG); what the format's own entry
  * point refuses, with its status; AVD_FMT_BGR24 with rotate != 0 (AVD_ERR_UNSUPPORTED: cv2 hands BGR over already rotated, stored-orientation
@@ -244,7 +245,7 @@ enum avd_format { AVD_FMT_BGR24 = 0, AVD_FMT_NV12 = 1, AVD_FMT_I420 = 2 };
  * Refused in avd_picture's / avd_frame_list's order, where the BGR and I420 equivalents stand: AVD_FMT_FULL_RANGE on any of the four
  * (AVD_ERR_ARG: RGB has no range); rotate != 0 (AVD_ERR_UNSUPPORTED: producers of RGB hand it over already turned); AVD_FMT_RGBP planes whose
  * row or frame strides differ (AVD_ERR_ARG).  No evenness rule applies; the 32 x 32 minimum, the 16384 limits, null planes and short strides
- * are checked as for every clip, with rows of 3w, 4w and w bytes.  Layouts 3 .. 0x0F, 0x14 .. 0x1F and 0x24 .. 0xFF stay AVD_ERR_ARG (0x20 .. 0x23: the 4:2:2 layouts below).
+ * are checked as for every clip, with rows of 3w, 4w and w bytes.  Layouts 3 .. 0x0F, 0x14 .. 0x1F, 0x24 .. 0x2F and 0x32 .. 0xFF stay AVD_ERR_ARG (0x20 .. 0x23: the 4:2:2 layouts below; 0x30, 0x31: the 10-bit layouts below them).
  * AVD_MEM_HOST: the three planes of AVD_FMT_RGBP are staged as the planes of I420 are -- spans merged where they overlap or touch, so a dense
  * [N,3,H,W] stack crosses the link as ONE copy and separately allocated planes as three; the packed layouts are one span.
  * The 16-byte fills need w % 16 == 0 and every plane base, row stride and frame stride 16-byte aligned (a list: every frame); anything else
@@ -279,17 +280,50 @@ enum avd_format { AVD_FMT_BGR24 = 0, AVD_FMT_NV12 = 1, AVD_FMT_I420 = 2 };
  * does not commute with quarter turns when only one axis is subsampled, and a turned 4:2:2 fill is not built); AVD_FMT_I422 chroma planes whose
  * row or frame strides differ (AVD_ERR_ARG); an odd width (AVD_ERR_UNSUPPORTED).  The height may be ODD: nothing is subsampled vertically.
  * The 32 x 32 minimum, the 16384 limits, null planes and short strides are checked as for every clip, with the row bytes above.  Layouts
- * 0x14 .. 0x1F and 0x24 .. 0xFF stay AVD_ERR_ARG.
+ * 0x14 .. 0x1F, 0x24 .. 0x2F and 0x32 .. 0xFF stay AVD_ERR_ARG.
  * AVD_MEM_HOST: the packed layouts are one span of 2w-byte rows; the three planes of I422 are staged as I420's (merged where they overlap or
  * touch: a .y4m map is ONE copy, separately allocated planes three); NV16 as NV12, two spans.
  * The table fills need w % 16 == 0 and every plane base, row stride and frame stride 16-byte aligned (8 for the chroma planes of I422; a list:
  * every frame); anything else runs the scalar fill with identical results.
- * Not covered: turned 4:2:2 pictures; 4:4:4 and 10-bit surfaces (libswscale's filtered general path, which is not restatable here); NV21, GRAY8
+ * Not covered: turned 4:2:2 pictures; 4:4:4 and 10-bit 4:2:2 surfaces (libswscale's filtered general path, which is not restatable here; 10-bit
+ * 4:2:0 is settled by definition, below); NV21, GRAY8
  * and mirrored display matrices.  avd_clip is unchanged. */
 #define AVD_FMT_YUYV422 0x20
 #define AVD_FMT_UYVY422 0x21
 #define AVD_FMT_I422    0x22
 #define AVD_FMT_NV16    0x23
+/* 10-bit 4:2:0 pictures in 16-bit words (additive at ABI 3; avd_picture / avd_frame_list only -- avd_clip and the entry points that name their
+ * format are unchanged).  HEVC Main10 as phones record it (libavcodec's yuv420p10le: AVD_FMT_I010), the same streams and 10-bit AV1 / VP9 from
+ * VCN / rocDecode (P010 surfaces: AVD_FMT_P010).  The plane pointers stay const uint8_t* and every stride stays in BYTES; the words are
+ * little-endian.
+ *   value  name            planes                                                                                          row bytes
+ *   0x30   AVD_FMT_P010    2: Y [h][w], interleaved U,V [h/2][w]; the 10 bits in the HIGH bits of each word (p010le; a       2w, 2w
+ *                          P016 surface reads the same way)
+ *   0x31   AVD_FMT_I010    3: Y [h][w], U and V [h/2][w/2]; the 10 bits in the LOW bits (yuv420p10le); U and V share their    2w, w, w
+ *                          strides; exchange [1] and [2] for V-first
+ * The definition, total over all 65536 words so that no input is undefined: a P010 word s becomes s8 = min(255, (s + 128) >> 8), formed without
+ * 16-bit overflow -- with the low six bits zero that is min(255, (v10 + 2) >> 2), and non-zero low bits never change it --, an I010 word s
+ * becomes s8 = min(255, (s + 2) >> 2).  The 8-bit NV12 / I420 picture of those samples, pushed through the format's own 8-bit path, gives every
+ * output of the call: bit for bit, in both fb_modes, for rotate 0 .. 3, limited range by default and full range with AVD_FMT_FULL_RANGE (allowed,
+ * per clip of a batch).  tests/yuv10_reference.py restates it.  No narrowed picture exists in memory: the samples are narrowed in registers
+ * where the fused pass loads them, and everything behind the load is NV12's / I420's at the same displayed geometry.
+ * Where the rounding comes from (restated from memory; parity with a real libswscale is UNPINNED, and nothing here can check it):
+ * cv2.VideoCapture.retrieve() has libswscale convert the 10-bit picture to bgr24; its hScale16To15 takes a 10-bit sample v to v << 5 and the
+ * one-tap vertical output takes that to (v * 32 + 64) >> 7 = (v + 2) >> 2 before the yuv2rgb tables.  Two known deviations: super-white samples
+ * (v10 >= 1022) are clipped to 255 BEFORE the table, where libswscale would index the table at 256; and the vertical chroma interpolation of
+ * libswscale's general path is not restated -- the NV12 deviation (nearest chroma), unchanged.
+ * Refused in avd_picture's / avd_frame_list's order, where the NV12 / I420 equivalents stand: AVD_FMT_I010 chroma planes whose row or frame
+ * strides differ (AVD_ERR_ARG); an odd width or height (AVD_ERR_UNSUPPORTED); the 32 x 32 minimum, the 16384 limits, null planes and short
+ * strides as for every clip, with the row bytes above; and LAST a plane base (of a list: any entry), a row stride or a frame stride that is odd
+ * (AVD_ERR_ARG: 16-bit samples need 2-byte aligned planes and strides).  Layouts 0x24 .. 0x2F and 0x32 .. 0xFF stay AVD_ERR_ARG.
+ * AVD_MEM_HOST: P010 is staged as NV12, two spans; I010 as I420 -- spans merged where they overlap or touch, so a dense yuv420p10le frame stack
+ * is ONE copy and separately allocated planes three.
+ * The table fills need w % 16 == 0 and every plane base, row stride and frame stride 16-byte aligned, the chroma planes of I010 included (a
+ * contiguous I010 frame has its V plane at 5wh/2 bytes, a multiple of 16; a list: every frame); anything else runs the scalar fill with
+ * identical results.  A quarter turn runs the strip fill whatever the alignment.
+ * Not covered: 10-bit 4:2:2 and 4:4:4, 12-bit and big-endian layouts. */
+#define AVD_FMT_P010    0x30
+#define AVD_FMT_I010    0x31
 typedef struct avd_picture {
     uint32_t struct_size;
     int32_t  format;
@@ -500,8 +534,9 @@ int avd_kernel_ms(avd_ctx* ctx, int kernel_id, float* ms);
  * "ingest_plan" int32[8], host state rather than a device buffer: what the last ingest launch of the context ran --
  * h, w, rows_per_band, nbands, LDS tile pitch, NI of k_preprocess_vec, the staged kernel of BGR24 / RGB24 / RGBP (0: the generic kernel), dynamic LDS bytes requested,
  * kernel (0 bgr_scalar, 1 bgr_vec16, 2 bgr_staged, 3 nv12_scalar, 4 nv12_tables, 5 i420_scalar, 6 i420_tables, 7 nv12_strip, 8 i420_strip, 9 px32_scalar, 10 px32_vec16, 11 rgbp_scalar, 12 rgbp_vec16, 13 rgbp_staged,
- * 14 yuyv_scalar, 15 yuyv_tables, 16 i422_scalar, 17 i422_tables, 18 nv16_scalar, 19 nv16_tables;
- * a half turn runs the flipped instantiations of 3 .. 6 under the same ids; AVD_FMT_RGB24 runs 0 .. 2 with its own coefficient constants, BGRA32 and
+ * 14 yuyv_scalar, 15 yuyv_tables, 16 i422_scalar, 17 i422_tables, 18 nv16_scalar, 19 nv16_tables, 20 p010_scalar, 21 p010_tables, 22 i010_scalar,
+ * 23 i010_tables, 24 p010_strip, 25 i010_strip;
+ * a half turn runs the flipped instantiations of 3 .. 6 and 20 .. 23 under the same ids; AVD_FMT_RGB24 runs 0 .. 2 with its own coefficient constants, BGRA32 and
  * RGBA32 share 9 and 10, YUYV422 and UYVY422 share 14 and 15: "ingest_format" tells them apart); h, w are the displayed picture's; an error before any ingest launch.
  * "ingest_rotate" int32[1], host state: the rotation (quarter turns) that launch ran with; an error before any ingest launch.
  * "ingest_range" int32[1], host state: 1 if that launch ran with full-range conversion constants (AVD_FMT_FULL_RANGE), else 0; an error before

@@ -17,8 +17,9 @@
  *   format       exactly as avd_picture.format: the layout in the low byte, AVD_FMT_FULL_RANGE above it
  *   plane        plane[p][f] = plane p of frame f, n entries each.  BGR: [0]; NV12: Y, interleaved UV; I420: Y, U, V; AVD_FMT_RGB24 / _BGRA32 /
  *                _RGBA32: [0]; AVD_FMT_RGBP: R, G, B (a torch uint8[3,H,W] frame: its three channel views; gbrp: data[2], data[0], data[1]);
- *                AVD_FMT_YUYV422 / _UYVY422: [0]; AVD_FMT_I422: Y, U, V; AVD_FMT_NV16: Y, interleaved UV
- *   row_stride   bytes, per plane, shared by all frames of the list; I420 and I422: [1] == [2], RGBP: [0] == [1] == [2] (AVD_ERR_ARG otherwise)
+ *                AVD_FMT_YUYV422 / _UYVY422: [0]; AVD_FMT_I422: Y, U, V; AVD_FMT_NV16: Y, interleaved UV;
+ *                AVD_FMT_P010: Y, interleaved UV; AVD_FMT_I010: Y, U, V (16-bit words behind byte pointers, include/avd.h)
+ *   row_stride   bytes, per plane, shared by all frames of the list; I420, I422 and I010: [1] == [2], RGBP: [0] == [1] == [2] (AVD_ERR_ARG otherwise)
  *   mem          where the PLANES live;  h, w  the stored picture;  rotate, reserved  as avd_picture
  * Pointer arrays: the arrays plane[p] are always HOST memory, whatever `mem` says.  They are read during the call and never retained: after
  * avd_analyze_frame_lists_async returns the caller may free or overwrite them.  The planes themselves stay alive until avd_synchronize (or the
@@ -38,8 +39,8 @@
  * strided clip is trivially a list).  avd_analyze_frame_lists_async follows avd_analyze_pictures_async exactly: one call outstanding per context,
  * drained by any other call, with the same exemptions.
  * Refused before anything is staged or launched, the first of: struct_size; format; AVD_FMT_FULL_RANGE on BGR or an RGB layout; rotate; reserved; BGR or an
- * RGB or 4:2:2 layout with a rotation; I420 / I422 chroma (RGBP: plane) row strides that differ; then mem; the size range; even size (4:2:0), even width (4:2:2); 32 x 32; a null plane[p] array or a null entry in
- * one while n > 0 (AVD_ERR_ARG); row strides smaller than a row; last, a null records pointer while there are frames.  Statuses as above. */
+ * RGB or 4:2:2 layout with a rotation; I420 / I422 / I010 chroma (RGBP: plane) row strides that differ; then mem; the size range; even size (4:2:0), even width (4:2:2); 32 x 32; a null plane[p] array or a null entry in
+ * one while n > 0 (AVD_ERR_ARG); row strides smaller than a row; P010 / I010: an odd plane address or row stride; last, a null records pointer while there are frames.  Statuses as above. */
 typedef struct avd_frame_list {
     uint32_t struct_size;            /* sizeof(avd_frame_list); anything else AVD_ERR_ARG */
     int32_t  format;                 /* exactly as avd_picture.format: layout in the low byte, AVD_FMT_FULL_RANGE above it */
