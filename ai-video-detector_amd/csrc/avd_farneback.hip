@@ -239,32 +239,90 @@ __global__ __launch_bounds__(256) void k_pyramid_all(const uint8_t* __restrict__
 }
 
 // ---------------------------------------------------------------------------------------
-// FarnebackPolyExp (poly_n = 5), all four scales in ONE launch.  A 320-thread workgroup owns 320 / w consecutive image
-// rows of one frame (one row at 320 px, eight at 40 px: every lane has a pixel at every scale).  Vertical 11-tap pass in
-// float into LDS (3 moment planes, replicate border), horizontal pass with double accumulators, 5 interleaved
+// FarnebackPolyExp (poly_n = 5), all four scales in ONE launch.  A 320-thread workgroup works on 320 / w consecutive image
+// rows of one frame at a time (one row at 320 px, eight at 40 px: every lane has a pixel at every scale).  Vertical 11-tap pass in
+// float into LDS (the 3 moments of a column as one quad, replicate border), horizontal pass with double accumulators, 5 interleaved
 // coefficients R[y][x][c] (cv2's own layout: the level kernel gathers a pixel's five coefficients and its right-hand
 // neighbour's as ten consecutive floats).  The workgroup's output is ONE contiguous span of 1600 floats: it is staged in
 // LDS and stored as 16-byte pieces (a lane's own five floats are 20 bytes apart from its neighbour's).
 // ---------------------------------------------------------------------------------------
 struct PolyPtrs { const float* I[AVD_FB_LEVELS]; float* R[AVD_FB_LEVELS]; const uint8_t* small; };   // small != null: the 320-px scale is blurred here
 
-constexpr int kPolyRows = 16;                            // image rows per workgroup of the full-resolution scale
+constexpr int kPolyRows = 16;                            // image rows per workgroup (a band) of the 320-, 160- and 80-px scales
+constexpr int kPolyQuads = 4 * (S / 4 + 10);             // quads of one LDS row buffer: the 80-px scale's four sub-rows of w + 10 (330 / 340 / 360)
+static_assert(AVD_FB_LEVELS == 4, "three walking scales and the one-row form of the coarsest");
+// workgroups per frame at scale k: bands of kPolyRows rows, at the coarsest scale single steps of 2^k rows (20 / 10 / 5 / 5)
+__host__ __device__ constexpr int poly_wgs(int k) { return k < AVD_FB_LEVELS - 1 ? (S >> k) / kPolyRows : S >> (2 * k); }
 
-// The 320-px scale (three quarters of the stage's pixels): a workgroup walks kPolyRows consecutive rows.  A lane keeps the
-// eleven rows of its column that the vertical pass reads in registers and slides them (one new load per row instead of
-// eleven, 18 / 8 loads per row with the halo), the two LDS buffers alternate, so a row costs ONE workgroup barrier, and the
-// coalesced 16-byte stores of row i - 1 are issued while row i is in its horizontal pass.  Same arithmetic per pixel as
-// the one-row form below (which still serves the three small scales): bit-identical.
+// The vertical pass leaves a column's three moments in LDS as ONE 16-byte quad {t0, t1, t1, t2}: a single 128-bit read then hands the
+// horizontal pass (t0, t1) and (t1, t2) as two aligned register pairs, which is what its packed sums, differences and products take as
+// operands -- from three separate moment rows every pair had to be put together with register moves first.
+typedef float pf4 __attribute__((ext_vector_type(4)));
+typedef float pf2 __attribute__((ext_vector_type(2)));
+
+// quad of column x of a w-wide row (rowq: the row's w + 10 quads); the two edge lanes also write the five replicated quads of their side
+__device__ __forceinline__ void polyexp_put(pf4* __restrict__ rowq, int x, int w, float t0, float t1, float t2)
+{
+    const pf4 t = {t0, t1, t1, t2};
+    rowq[x + 5] = t;
+    if (x == 0)
+        for (int q = 0; q < 5; q++) rowq[q] = t;
+    if (x == w - 1)
+        for (int q = 0; q < 5; q++) rowq[w + 5 + q] = t;
+}
+
+// Horizontal pass of one pixel (rq: its own quad; rq[-5 .. 5] are read) -> its five coefficients o[0 .. 4].  Per tap: (s0, s1) and (d0, d1)
+// from the low pairs, (s1, s2) from the high pairs, (d0, d1) * xg and (s1, s2) * g -- five two-component operations (v_pk_add_f32 /
+// v_pk_mul_f32: each half is the IEEE single operation of the scalar form on the same operands), then cv2's double accumulations in cv2's order.
+__device__ __forceinline__ void polyexp_hpass(const pf4* __restrict__ rq, const float (&g)[6], const float (&xg)[6], const double (&gd)[6],
+                                              const double (&xxgd)[6], double ig11, double ig03, double ig33, double ig55, float* __restrict__ o)
+{
+    const pf4 c = rq[0];
+    double b1 = (double)(c.x * g[0]), b2 = 0, b3 = (double)(c.y * g[0]), b4 = 0, b5 = (double)(c.w * g[0]), b6 = 0;
+#pragma unroll
+    for (int q = 1; q <= 5; q++) {
+        const pf4 p = rq[q], m = rq[-q];
+        const pf2 s01 = p.xy + m.xy, d01 = p.xy - m.xy, s12 = p.zw + m.zw;
+        const pf2 dx = d01 * pf2{xg[q], xg[q]};          // (r0p - r0m) * xg, (r1p - r1m) * xg
+        const pf2 sg = s12 * pf2{g[q], g[q]};            // (r1p + r1m) * g, (r2p + r2m) * g
+        // tg and the taps are float VALUES held in doubles: their product has at most 48 significant bits, i.e. it is exact in
+        // double, so cv2's "b += tg * g" (a rounded product, then a rounded sum) IS the fused multiply-add, bit for bit -- one
+        // double instruction instead of two on the pass that bounds this kernel
+        const double tg = (double)s01.x;
+        b1 = __builtin_fma(tg, gd[q], b1);
+        b4 = __builtin_fma(tg, xxgd[q], b4);
+        b2 += (double)dx.x;
+        b3 += (double)sg.x;
+        b6 += (double)dx.y;
+        b5 += (double)sg.y;
+    }
+    o[0] = (float)(b3 * ig11);
+    o[1] = (float)(b2 * ig11);
+    o[2] = (float)(b1 * ig03 + b5 * ig33);
+    o[3] = (float)(b1 * ig03 + b4 * ig33);
+    o[4] = (float)(b6 * ig55);
+}
+
+// The 320-, 160- and 80-px scales (K = 0, 1, 2): a workgroup walks a band of kPolyRows consecutive image rows in steps of R = 2^K rows
+// (lane = (sub-row, column): every lane has a pixel in every step).  A lane keeps the eleven rows of its column that the vertical pass
+// reads in registers and slides them by R rows per step (R new loads per step instead of eleven, (10 + kPolyRows) / kPolyRows loads per
+// pixel with the band's halo), the two LDS buffers alternate, so a step costs ONE workgroup barrier, and the coalesced 16-byte stores
+// of step i - 1 are issued while step i is in its horizontal pass.  Same arithmetic per pixel as the one-row form below (which still
+// serves the 40-px scale: eight rows per step, nothing to slide): bit-identical.
 // FOLD: the scale's input is not the pyramid kernel's blurred float image but the 320 x 320 gray bytes themselves; the 3 x 3 Gaussian of
 // pyramid_body<0> (BORDER_REFLECT_101, the same two float passes in the same operation order: bit-identical) is formed on the way into the
 // register window -- one 4-byte load per new row instead of one float load, a rolling window of three horizontally filtered rows.  Saves the
 // 320-px tiles of the pyramid kernel and 49 MB written + read per 120 frames.
-template <bool FOLD>
-__device__ __forceinline__ void polyexp_rows320(const float* __restrict__ img, const uint8_t* __restrict__ small, float* __restrict__ out, int y0,
-                                                const FbConsts* __restrict__ C, float (*rowb)[3][S + 80], float (*outb)[S * 5])
+template <int K, bool FOLD>
+__device__ __forceinline__ void polyexp_rows(const float* __restrict__ img, const uint8_t* __restrict__ small, float* __restrict__ out, int y0,
+                                             const FbConsts* __restrict__ C, pf4 (*rowb)[kPolyQuads], float (*outb)[S * 5])
 {
-    constexpr int w = S, h = S;
-    const int x = threadIdx.x;
+    static_assert(!FOLD || K == 0, "only the 320-px scale forms its own blur");
+    constexpr int w = S >> K, h = w, R = 1 << K, STEPS = kPolyRows / R;
+    static_assert(R * (w + 10) <= kPolyQuads && h % kPolyRows == 0 && kPolyRows % R == 0, "a step's R rows fit one LDS buffer; whole bands");
+    const int tid = threadIdx.x;
+    const int sr = K == 0 ? 0 : tid / w, x = tid - sr * w;   // sub-row of this lane within a step, column
+    const int yb = y0 + sr;                                  // this lane's row in step 0
     // FOLD: bytes x - 1, x, x + 1 of a row (reflected at the image edge) out of ONE 4-byte load at xs = clamp(x - 1, 0, w - 4)
     const int xs = x - 1 < 0 ? 0 : (x - 1 > w - 4 ? w - 4 : x - 1);
     const int shl = ((x == 0 ? 1 : x - 1) - xs) * 8, shc = (x - xs) * 8, shr = ((x == w - 1 ? w - 2 : x + 1) - xs) * 8;
@@ -295,114 +353,91 @@ __device__ __forceinline__ void polyexp_rows320(const float* __restrict__ img, c
     float g[6], xg[6], xxg[6];
     double gd[6], xxgd[6];
 #pragma unroll
-    for (int q = 0; q <= 5; q++) { g[q] = C->g[5 + q]; xg[q] = C->xg[5 + q]; xxg[q] = C->xxg[5 + q]; gd[q] = (double)g[q]; xxgd[q] = (double)xxg[q]; }
+    for (int q = 0; q <= 5; q++) { g[q] = C->g[5 + q]; xg[q] = C->xg[5 + q]; xxg[q] = C->xxg[5 + q]; gd[q] = C->gd[q]; xxgd[q] = C->xxgd[q]; }
     const double ig11 = C->ig11, ig03 = C->ig03, ig33 = C->ig33, ig55 = C->ig55;
-    float win[11 + kPolyRows];                           // rows y0 - 5 .. y0 + kPolyRows + 4 of this column (clamped: replicate border)
+    float win[11 + kPolyRows - R];                       // win[j] = row yb - 5 + j of this column (clamped: replicate border); step i reads win[R i .. R i + 10]
 #pragma unroll
-    for (int q = 0; q < 10; q++) win[q] = pixel(min(max(y0 - 5 + q, 0), h - 1));
+    for (int q = 0; q < 10; q++) win[q] = pixel(min(max(yb - 5 + q, 0), h - 1));
+    pf4* rowq[2] = {rowb[0] + sr * (w + 10), rowb[1] + sr * (w + 10)};
 #pragma unroll
-    for (int i = 0; i < kPolyRows; i++) {                // fully unrolled: the window is a static slice win[i .. i + 10]
-        const int y = y0 + i, par = i & 1;
-        win[i + 10] = pixel(min(y + 5, h - 1));
+    for (int i = 0; i < STEPS; i++) {                    // fully unrolled: the window is a static slice
+        const int par = i & 1, o = R * i;
+#pragma unroll
+        for (int j = o + 11 - R; j <= o + 10; j++)       // the rows this step is the first to read (one in step 0: the others were loaded above)
+            if (j >= 10) win[j] = pixel(min(yb - 5 + j, h - 1));
         {
-            f2 t02 = f2{win[i + 5] * g[0], 0.f};
+            f2 t02 = f2{win[o + 5] * g[0], 0.f};
             float t1 = 0.f;
 #pragma unroll
             for (int q = 1; q <= 5; q++) {
-                const float a = win[i + 5 - q], bb = win[i + 5 + q];
+                const float a = win[o + 5 - q], bb = win[o + 5 + q];
                 const float p = a + bb;
                 t02 = t02 + f2{g[q], xxg[q]} * f2{p, p};  // t0 = t0 + g[q] * p;  t2 = t2 + xxg[q] * p
                 t1 = t1 + xg[q] * (bb - a);
             }
-            float* r0s = rowb[par][0]; float* r1s = rowb[par][1]; float* r2s = rowb[par][2];
-            const float t0 = t02.x, t2 = t02.y;
-            r0s[x + 5] = t0; r1s[x + 5] = t1; r2s[x + 5] = t2;
-            if (x == 0)
-                for (int q = 0; q < 5; q++) { r0s[q] = t0; r1s[q] = t1; r2s[q] = t2; }
-            if (x == w - 1)
-                for (int q = 0; q < 5; q++) { r0s[w + 5 + q] = t0; r1s[w + 5 + q] = t1; r2s[w + 5 + q] = t2; }
+            polyexp_put(rowq[par], x, w, t02.x, t1, t02.y);
         }
         __syncthreads();
-        if (i > 0) {                                     // row i - 1 is complete in outb[par ^ 1]: 1600 floats = 400 16-byte pieces
-            f4* dst = reinterpret_cast<f4*>(out + (int64_t)(y - 1) * w * 5);
+        if (i > 0) {                                     // step i - 1 is complete in outb[par ^ 1]: R rows = 1600 floats = 400 16-byte pieces
+            f4* dst = reinterpret_cast<f4*>(out + (int64_t)(y0 + o - R) * w * 5);
             const f4* srcv = reinterpret_cast<const f4*>(outb[par ^ 1]);
-            __builtin_nontemporal_store(srcv[x], dst + x);
-            if (x < S * 5 / 4 - 320) __builtin_nontemporal_store(srcv[x + 320], dst + x + 320);
+            __builtin_nontemporal_store(srcv[tid], dst + tid);
+            if (tid < S * 5 / 4 - 320) __builtin_nontemporal_store(srcv[tid + 320], dst + tid + 320);
         }
-        const float* r0 = rowb[par][0] + x + 5; const float* r1 = rowb[par][1] + x + 5; const float* r2 = rowb[par][2] + x + 5;
-        double b1 = (double)(r0[0] * g[0]), b2 = 0, b3 = (double)(r1[0] * g[0]), b4 = 0, b5 = (double)(r2[0] * g[0]), b6 = 0;
-#pragma unroll
-        for (int q = 1; q <= 5; q++) {
-            // scalar float operations on purpose: formed as two-component vectors ((r0, r1) differences, (r1, r2) sums) every pair had to
-            // be assembled with register moves first -- 40 of the 208 VALU instructions of a row -- which cost more than the packing saved
-            const float r0p = r0[q], r0m = r0[-q], r1p = r1[q], r1m = r1[-q], r2p = r2[q], r2m = r2[-q];
-            // tg and the taps are float VALUES held in doubles: their product has at most 48 significant bits, i.e. it is exact in
-            // double, so cv2's "b += tg * g" (a rounded product, then a rounded sum) IS the fused multiply-add, bit for bit -- one
-            // double instruction instead of two on the pass that bounds this kernel
-            const double tg = (double)(r0p + r0m);
-            b1 = __builtin_fma(tg, gd[q], b1);
-            b4 = __builtin_fma(tg, xxgd[q], b4);
-            b2 += (double)((r0p - r0m) * xg[q]);
-            b3 += (double)((r1p + r1m) * g[q]);
-            b6 += (double)((r1p - r1m) * xg[q]);
-            b5 += (double)((r2p + r2m) * g[q]);
-        }
-        float* o = outb[par] + x * 5;
-        o[0] = (float)(b3 * ig11);
-        o[1] = (float)(b2 * ig11);
-        o[2] = (float)(b1 * ig03 + b5 * ig33);
-        o[3] = (float)(b1 * ig03 + b4 * ig33);
-        o[4] = (float)(b6 * ig55);
+        polyexp_hpass(rowq[par] + x + 5, g, xg, gd, xxgd, ig11, ig03, ig33, ig55, outb[par] + tid * 5);   // (sub-row, x) order = memory order
     }
     __syncthreads();
     {
-        f4* dst = reinterpret_cast<f4*>(out + (int64_t)(y0 + kPolyRows - 1) * w * 5);
-        const f4* srcv = reinterpret_cast<const f4*>(outb[(kPolyRows - 1) & 1]);
-        __builtin_nontemporal_store(srcv[x], dst + x);
-        if (x < S * 5 / 4 - 320) __builtin_nontemporal_store(srcv[x + 320], dst + x + 320);
+        f4* dst = reinterpret_cast<f4*>(out + (int64_t)(y0 + kPolyRows - R) * w * 5);
+        const f4* srcv = reinterpret_cast<const f4*>(outb[(STEPS - 1) & 1]);
+        __builtin_nontemporal_store(srcv[tid], dst + tid);
+        if (tid < S * 5 / 4 - 320) __builtin_nontemporal_store(srcv[tid + 320], dst + tid + 320);
     }
 }
 
 __global__ __launch_bounds__(320) void k_polyexp_all(PolyPtrs P, int n, const FbConsts* __restrict__ C)
 {
-    __shared__ float rowb[2][3][S + 80];                 // per sub-row: w + 10 entries (5 replicated on either side); two buffers
+    __shared__ pf4 rowb[2][kPolyQuads];                  // per sub-row: w + 10 quads (5 replicated on either side); two buffers
     __shared__ __align__(16) float outbb[2][S * 5];
-    float (*row)[S + 80] = rowb[0];
+    pf4* row = rowb[0];                                  // the one-row form: eight sub-rows of w + 10 quads, 400 of the 720
+    static_assert(8 * (S / 8 + 10) <= 2 * kPolyQuads, "the eight sub-rows of the coarsest scale fit");
     float* outb = outbb[0];
-    // the 320-px scale first: n * 320 / kPolyRows workgroups of kPolyRows rows (consecutive row bands of a frame share an XCD)
-    {
-        const int wgs0 = n * (S / kPolyRows), cnt0 = ((wgs0 + 7) >> 3) << 3;
-        if ((int)blockIdx.x < cnt0) {
-            const int per = cnt0 >> 3, lid = ((int)blockIdx.x & 7) * per + ((int)blockIdx.x >> 3);
-            if (lid >= wgs0) return;
-            const int f = lid / (S / kPolyRows), y0 = (lid - f * (S / kPolyRows)) * kPolyRows;
-            if (P.small) polyexp_rows320<true>(nullptr, P.small + (int64_t)f * S * S, P.R[0] + (int64_t)f * S * S * 5, y0, C, rowb, outbb);
-            else polyexp_rows320<false>(P.I[0] + (int64_t)f * S * S, nullptr, P.R[0] + (int64_t)f * S * S * 5, y0, C, rowb, outbb);
-            return;
-        }
-    }
-    // scale k >= 1: w = 320 >> k, rows per workgroup 1 << k, workgroups n * 320 / 4^k (padded to a multiple of 8: within a
-    // scale consecutive workgroups -- overlapping 11-row windows -- share an XCD)
-    int b = (int)blockIdx.x - ((((n * (S / kPolyRows)) + 7) >> 3) << 3), k = 1;
+    // scale k: n * poly_wgs(k) workgroups, padded to a multiple of 8: within a scale consecutive workgroups -- row bands of a frame, whose
+    // 11-row windows overlap -- share an XCD
+    int b = (int)blockIdx.x, k = 0, wgs = 0;
     for (; k < AVD_FB_LEVELS; k++) {
-        const int cnt = ((n * (S >> (2 * k)) + 7) >> 3) << 3;
+        wgs = n * poly_wgs(k);
+        const int cnt = ((wgs + 7) >> 3) << 3;
         if (b < cnt) break;
         b -= cnt;
     }
     if (k >= AVD_FB_LEVELS) return;
-    const int wgs = n * (S >> (2 * k));
-    const int per = ((wgs + 7) >> 3), lid = (b & 7) * per + (b >> 3);
+    const int per = (wgs + 7) >> 3, lid = (b & 7) * per + (b >> 3);
     if (lid >= wgs) return;
     const int w = S >> k, h = w;
-    const int wgs_per_frame = h >> k;
-    const int f = lid / wgs_per_frame, y0 = (lid - f * wgs_per_frame) << k;
+    int f = 0;
+#pragma unroll
+    for (int kk = 0; kk < AVD_FB_LEVELS; kk++)
+        if (k == kk) f = lid / poly_wgs(kk);             // (divisions by constants)
+    const int t = lid - f * poly_wgs(k);
+    float* R = P.R[k] + (int64_t)f * w * h * 5;
+    if (k == 0) {
+        if (P.small) polyexp_rows<0, true>(nullptr, P.small + (int64_t)f * S * S, R, t * kPolyRows, C, rowb, outbb);
+        else polyexp_rows<0, false>(P.I[0] + (int64_t)f * S * S, nullptr, R, t * kPolyRows, C, rowb, outbb);
+        return;
+    }
+    if (k == 1) { polyexp_rows<1, false>(P.I[1] + (int64_t)f * w * h, nullptr, R, t * kPolyRows, C, rowb, outbb); return; }
+    if (k == 2) { polyexp_rows<2, false>(P.I[2] + (int64_t)f * w * h, nullptr, R, t * kPolyRows, C, rowb, outbb); return; }
+    const int y0 = t << k;
     const int tid = threadIdx.x;
     const int sr = tid / w, x = tid - sr * w;            // sub-row of this lane, column
     const int y = y0 + sr;
     const float* img = P.I[k] + (int64_t)f * w * h;
-    const float* g = C->g + 5; const float* xg = C->xg + 5; const float* xxg = C->xxg + 5;
-    const int pitch = w + 10;
-    float* r0s = row[0] + sr * pitch; float* r1s = row[1] + sr * pitch; float* r2s = row[2] + sr * pitch;
+    float g[6], xg[6], xxg[6];                            // uniform: scalar registers, as are the taps as doubles
+    double gd[6], xxgd[6];
+#pragma unroll
+    for (int q = 0; q <= 5; q++) { g[q] = C->g[5 + q]; xg[q] = C->xg[5 + q]; xxg[q] = C->xxg[5 + q]; gd[q] = C->gd[q]; xxgd[q] = C->xxgd[q]; }
+    pf4* rowq = row + sr * (w + 10);
     {
         float t0 = img[y * w + x] * g[0], t1 = 0.f, t2 = 0.f;
 #pragma unroll
@@ -413,35 +448,13 @@ __global__ __launch_bounds__(320) void k_polyexp_all(PolyPtrs P, int n, const Fb
             t1 = t1 + xg[q] * (bb - a);
             t2 = t2 + xxg[q] * p;
         }
-        r0s[x + 5] = t0; r1s[x + 5] = t1; r2s[x + 5] = t2;
-        if (x == 0)
-            for (int q = 0; q < 5; q++) { r0s[q] = t0; r1s[q] = t1; r2s[q] = t2; }
-        if (x == w - 1)
-            for (int q = 0; q < 5; q++) { r0s[w + 5 + q] = t0; r1s[w + 5 + q] = t1; r2s[w + 5 + q] = t2; }
+        polyexp_put(rowq, x, w, t0, t1, t2);
     }
     __syncthreads();
-    const float* r0 = r0s + x + 5; const float* r1 = r1s + x + 5; const float* r2 = r2s + x + 5;
-    double b1 = (double)(r0[0] * g[0]), b2 = 0, b3 = (double)(r1[0] * g[0]), b4 = 0,
-           b5 = (double)(r2[0] * g[0]), b6 = 0;
-#pragma unroll
-    for (int q = 1; q <= 5; q++) {
-        const double tg = (double)(r0[q] + r0[-q]);
-        b1 = __builtin_fma(tg, (double)g[q], b1);          // exact products (two float values): the fma IS cv2's multiply, then add
-        b4 = __builtin_fma(tg, (double)xxg[q], b4);
-        b2 += (double)((r0[q] - r0[-q]) * xg[q]);
-        b3 += (double)((r1[q] + r1[-q]) * g[q]);
-        b6 += (double)((r1[q] - r1[-q]) * xg[q]);
-        b5 += (double)((r2[q] + r2[-q]) * g[q]);
-    }
-    float* o = outb + tid * 5;                           // (sub-row, x) order = memory order of the workgroup's rows
-    o[0] = (float)(b3 * C->ig11);
-    o[1] = (float)(b2 * C->ig11);
-    o[2] = (float)(b1 * C->ig03 + b5 * C->ig33);
-    o[3] = (float)(b1 * C->ig03 + b4 * C->ig33);
-    o[4] = (float)(b6 * C->ig55);
+    polyexp_hpass(rowq + x + 5, g, xg, gd, xxgd, C->ig11, C->ig03, C->ig33, C->ig55, outb + tid * 5);   // (sub-row, x) order = memory order of the workgroup's rows
     __syncthreads();
     typedef float f4 __attribute__((ext_vector_type(4)));
-    f4* dst = reinterpret_cast<f4*>(P.R[k] + ((int64_t)f * w * h + (int64_t)y0 * w) * 5);
+    f4* dst = reinterpret_cast<f4*>(R + (int64_t)y0 * w * 5);
     const f4* srcv = reinterpret_cast<const f4*>(outb);
     __builtin_nontemporal_store(srcv[tid], dst + tid);
     if (tid < S * 5 / 4 - 320) __builtin_nontemporal_store(srcv[tid + 320], dst + tid + 320);
@@ -617,10 +630,10 @@ void pyramid_and_polyexp(avd_ctx* ctx, const uint8_t* d_small, int n)
                        ws.d_pyr[3].p, ws.d_fbflags.p, ws.d_pairdiff.p);
     PolyPtrs P;
     P.small = fold ? d_small : nullptr;
-    int grid = ((n * (S / kPolyRows) + 7) >> 3) << 3;      // the 320-px scale: kPolyRows rows per workgroup
+    int grid = 0;
     for (int k = 0; k < AVD_FB_LEVELS; k++) {
         P.I[k] = ws.d_pyr[k]; P.R[k] = ws.d_poly[k];
-        if (k > 0) grid += ((n * (S >> (2 * k)) + 7) >> 3) << 3;
+        grid += ((n * poly_wgs(k) + 7) >> 3) << 3;
     }
     kmark(ctx, AVD_K_POLYEXP);
     hipLaunchKernelGGL(k_polyexp_all, dim3(grid), dim3(320), 0, ctx->stream, P, n, C);

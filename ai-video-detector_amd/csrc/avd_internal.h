@@ -49,6 +49,7 @@ struct FbConsts {
     double ig11, ig03, ig33, ig55;
     float gk[AVD_FB_LEVELS][19];       // per-level Gaussian taps, level index = pyramid k
     int gksize[AVD_FB_LEVELS];
+    double gd[6], xxgd[6];             // g[5 + q], xxg[5 + q] as doubles (the same values): scalar operands of the expansion's double multiply-adds
 };
 void build_fb_consts(FbConsts& c);
 

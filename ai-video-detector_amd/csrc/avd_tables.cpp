@@ -163,6 +163,7 @@ void build_fb_consts(FbConsts& c)
         xg[x] = (float)(x * g[x]);
         xxg[x] = (float)(x * x * g[x]);
     }
+    for (int q = 0; q <= n; q++) { c.gd[q] = (double)g[q]; c.xxgd[q] = (double)xxg[q]; }
     double G[6][6] = {}, inv[6][6] = {};
     for (int y = -n; y <= n; y++)
         for (int x = -n; x <= n; x++) {
