@@ -6,6 +6,7 @@ missing, or no HIP device is usable, loading / context creation raises.
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 import os
 import subprocess
@@ -72,15 +73,38 @@ AVD_FMT_RGB24, AVD_FMT_BGRA32, AVD_FMT_RGBA32, AVD_FMT_RGBP = 0x10, 0x11, 0x12, 
 AVD_FMT_YUYV422, AVD_FMT_UYVY422, AVD_FMT_I422, AVD_FMT_NV16 = 0x20, 0x21, 0x22, 0x23
 # 10-bit 4:2:0 in little-endian 16-bit words (include/avd.h): P010 = NV12's planes with the 10 bits in the high bits, I010 = I420's with them in the low bits
 AVD_FMT_P010, AVD_FMT_I010 = 0x30, 0x31
-_WIDE = (AVD_FMT_P010, AVD_FMT_I010)        # planes of uint16 (torch: uint16, or int16 read as the same bits); every stride handed on is in bytes
-# one interleaved plane: bytes per pixel
-_PACKED = {AVD_FMT_BGR24: 3, AVD_FMT_RGB24: 3, AVD_FMT_BGRA32: 4, AVD_FMT_RGBA32: 4, AVD_FMT_YUYV422: 2, AVD_FMT_UYVY422: 2}
-_FMT_PLANES = {AVD_FMT_BGR24: 1, AVD_FMT_NV12: 2, AVD_FMT_I420: 3, AVD_FMT_RGB24: 1, AVD_FMT_BGRA32: 1, AVD_FMT_RGBA32: 1, AVD_FMT_RGBP: 3,
-               AVD_FMT_YUYV422: 1, AVD_FMT_UYVY422: 1, AVD_FMT_I422: 3, AVD_FMT_NV16: 2, AVD_FMT_P010: 2, AVD_FMT_I010: 3}
-_YUV_PLANES = (AVD_FMT_NV12, AVD_FMT_I420, AVD_FMT_I422, AVD_FMT_NV16, AVD_FMT_P010, AVD_FMT_I010)      # clips handed over as a tuple of planes
-_TAGGED_PLANES = {AVD_FMT_I422: "AVD_FMT_I422", AVD_FMT_NV16: "AVD_FMT_NV16", AVD_FMT_P010: "AVD_FMT_P010", AVD_FMT_I010: "AVD_FMT_I010"}      # ... through Pixels
-_FMT_NAMES = ("AVD_FMT_BGR24, AVD_FMT_NV12, AVD_FMT_I420, AVD_FMT_RGB24, AVD_FMT_BGRA32, AVD_FMT_RGBA32, AVD_FMT_RGBP, AVD_FMT_YUYV422, "
-              "AVD_FMT_UYVY422, AVD_FMT_I422, AVD_FMT_NV16, AVD_FMT_P010 or AVD_FMT_I010")
+# One record per layout (csrc/avd_ingest_clip.h has the library's row; tests/test_ingest_layouts.py holds the two against include/avd.h).
+#   px: bytes per pixel of plane 0; item: bytes per sample (2: planes of uint16 -- torch: uint16, or int16 read as the same bits; every stride
+#   handed on is in bytes); planes 1 and 2 have H // ydiv rows of W // xdiv samples
+#   handed: how a clip is handed over -- "stack": one interleaved array [N,H,W,px]; "channels": one array [N,3,H,W]; "planes": a tuple of planes
+#   pixels: the clip goes through Pixels (an untagged array remains BGR24, untagged tuples remain NV12 / I420)
+_Layout = collections.namedtuple("_Layout", "value name planes px item ydiv xdiv handed pixels")
+LAYOUTS = (
+    _Layout(AVD_FMT_BGR24, "AVD_FMT_BGR24", 1, 3, 1, 1, 1, "stack", True),
+    _Layout(AVD_FMT_NV12, "AVD_FMT_NV12", 2, 1, 1, 2, 1, "planes", False),
+    _Layout(AVD_FMT_I420, "AVD_FMT_I420", 3, 1, 1, 2, 2, "planes", False),
+    _Layout(AVD_FMT_RGB24, "AVD_FMT_RGB24", 1, 3, 1, 1, 1, "stack", True),
+    _Layout(AVD_FMT_BGRA32, "AVD_FMT_BGRA32", 1, 4, 1, 1, 1, "stack", True),
+    _Layout(AVD_FMT_RGBA32, "AVD_FMT_RGBA32", 1, 4, 1, 1, 1, "stack", True),
+    _Layout(AVD_FMT_RGBP, "AVD_FMT_RGBP", 3, 1, 1, 1, 1, "channels", True),
+    _Layout(AVD_FMT_YUYV422, "AVD_FMT_YUYV422", 1, 2, 1, 1, 1, "stack", True),
+    _Layout(AVD_FMT_UYVY422, "AVD_FMT_UYVY422", 1, 2, 1, 1, 1, "stack", True),
+    _Layout(AVD_FMT_I422, "AVD_FMT_I422", 3, 1, 1, 1, 2, "planes", True),
+    _Layout(AVD_FMT_NV16, "AVD_FMT_NV16", 2, 1, 1, 1, 1, "planes", True),
+    _Layout(AVD_FMT_P010, "AVD_FMT_P010", 2, 2, 2, 2, 1, "planes", True),
+    _Layout(AVD_FMT_I010, "AVD_FMT_I010", 3, 2, 2, 2, 2, "planes", True),
+)
+LAYOUT = {l.value: l for l in LAYOUTS}
+_PACKED = {l.value: l.px for l in LAYOUTS if l.handed == "stack"}      # one interleaved plane: bytes per pixel
+_WIDE = tuple(l.value for l in LAYOUTS if l.item == 2)
+
+
+def _names(layouts) -> str:
+    names = [l.name for l in layouts]
+    return ", ".join(names[:-1]) + " or " + names[-1]
+
+
+_FMT_NAMES = _names(LAYOUTS)
 
 
 def _wide_dtype(p) -> bool:
@@ -88,9 +112,9 @@ def _wide_dtype(p) -> bool:
     return str(getattr(p, "dtype", None)) in ("uint16", "torch.uint16", "torch.int16")
 
 
-def _chroma_shape(fmt: int, h: int, w: int):
-    """rows and samples per row of a chroma plane: 4:2:0 halves the rows, the planar layouts halve the row"""
-    return (h if fmt in (AVD_FMT_I422, AVD_FMT_NV16) else h // 2, w // 2 if fmt in (AVD_FMT_I420, AVD_FMT_I422, AVD_FMT_I010) else w)
+def _chroma_shape(l: _Layout, h: int, w: int):
+    """rows and samples per row of a plane behind plane 0: 4:2:0 halves the rows, the planar YUV layouts halve the row"""
+    return (h // l.ydiv, w // l.xdiv)
 
 
 class Pixels:
@@ -104,15 +128,15 @@ class Pixels:
     __slots__ = ("data", "fmt")
 
     def __init__(self, data, fmt: int):
-        if fmt not in _PACKED and fmt != AVD_FMT_RGBP and fmt not in _TAGGED_PLANES:
-            raise ValueError("fmt must be AVD_FMT_BGR24, AVD_FMT_RGB24, AVD_FMT_BGRA32, AVD_FMT_RGBA32, AVD_FMT_RGBP, AVD_FMT_YUYV422, AVD_FMT_UYVY422, "
-                             f"AVD_FMT_I422, AVD_FMT_NV16, AVD_FMT_P010 or AVD_FMT_I010, got {fmt!r}")
-        if fmt in _TAGGED_PLANES:
+        l = LAYOUT.get(fmt)
+        if l is None or not l.pixels:
+            raise ValueError(f"fmt must be {_names([l for l in LAYOUTS if l.pixels])}, got {fmt!r}")
+        if l.handed == "planes":
             data = tuple(data)
-            if len(data) != _FMT_PLANES[fmt]:
-                raise ValueError(f"an {_TAGGED_PLANES[fmt]} clip is a tuple of {_FMT_PLANES[fmt]} planes")
-            if fmt in _WIDE and not all(_wide_dtype(p) for p in data):
-                raise ValueError(f"the planes of an {_TAGGED_PLANES[fmt]} clip are uint16 (torch: uint16 or int16), got {[str(getattr(p, 'dtype', type(p).__name__)) for p in data]}")
+            if len(data) != l.planes:
+                raise ValueError(f"an {l.name} clip is a tuple of {l.planes} planes")
+            if l.item == 2 and not all(_wide_dtype(p) for p in data):
+                raise ValueError(f"the planes of an {l.name} clip are uint16 (torch: uint16 or int16), got {[str(getattr(p, 'dtype', type(p).__name__)) for p in data]}")
         self.data, self.fmt = data, fmt
 
 
@@ -366,9 +390,10 @@ class Context:
         nv12 = len(planes) == 2
         if fmt is None:
             fmt = AVD_FMT_NV12 if nv12 else AVD_FMT_I420
-        ch = "H" if fmt in (AVD_FMT_I422, AVD_FMT_NV16) else "H/2"
-        wide = fmt in _WIDE                                    # 16-bit words: the shapes count samples, the strides handed on are bytes
-        ty, item = ("uint16", 2) if wide else ("uint8", 1)
+        l = LAYOUT[fmt]
+        ch = "H" if l.ydiv == 1 else "H/2"
+        wide, item = l.item == 2, l.item                       # 16-bit words: the shapes count samples, the strides handed on are bytes
+        ty = "uint16" if wide else "uint8"
         layout = f"{ty}[N,H,W] and {ty}[N,{ch},W]" if nv12 else f"{ty}[N,H,W], {ty}[N,{ch},W/2] and {ty}[N,{ch},W/2]"
         torch_in = [_is_torch_tensor(p) for p in planes]
         if any(torch_in) != all(torch_in):
@@ -395,7 +420,7 @@ class Context:
             st.append((r, f if p.shape[0] > 1 else p.shape[1] * r))
         n, h, w = (int(d) for d in planes[0].shape)
         got = [tuple(p.shape) for p in planes[1:]]
-        crows, cbytes = _chroma_shape(fmt, h, w)
+        crows, cbytes = _chroma_shape(l, h, w)
         if nv12 and got != [(n, crows, cbytes)]:
             raise ValueError(f"chroma plane must be {ty}[{n},{crows},{cbytes}] (interleaved U,V), got {got[0]}")
         if not nv12 and got != [(n, crows, cbytes)] * 2:
@@ -424,18 +449,18 @@ class Context:
     def _pixels(self, px):
         """A tagged clip (Pixels) -> _Clip.  A strided view goes through as it lies while its rows are dense (and, channels first, whatever the
         distance between the planes: they share their row and frame strides by construction); anything else is copied once, as _frames_ptr does."""
-        fmt = px.fmt
+        fmt, l = px.fmt, LAYOUT[px.fmt]
         if fmt == AVD_FMT_BGR24:
             return self._bgr(px.data)
-        if fmt in _TAGGED_PLANES:
+        if l.handed == "planes":
             return self._plane_ptrs(px.data, fmt)
         torch_in = _is_torch_tensor(px.data)
         a = px.data if torch_in else np.asarray(px.data)
         strides, ptr, dense = _TORCH_PLANE if torch_in else _NUMPY_PLANE
-        planar = fmt == AVD_FMT_RGBP
-        want = "uint8[N,3,H,W] (R,G,B planes)" if planar else f"uint8[N,H,W,{_PACKED[fmt]}]"
+        planar = l.handed == "channels"
+        want = "uint8[N,3,H,W] (R,G,B planes)" if planar else f"uint8[N,H,W,{l.px}]"
         shape = tuple(int(d) for d in a.shape)
-        if len(shape) != 4 or shape[1 if planar else 3] != (3 if planar else _PACKED[fmt]) or str(a.dtype) not in ("torch.uint8", "uint8"):
+        if len(shape) != 4 or shape[1 if planar else 3] != (3 if planar else l.px) or str(a.dtype) not in ("torch.uint8", "uint8"):
             raise ValueError(f"frames must be {want}, got {str(a.dtype)}{list(shape)}")
         n, h, w = (shape[0], shape[2], shape[3]) if planar else shape[:3]
 
@@ -444,7 +469,7 @@ class Context:
                 f, _, r, e = st
                 return e == 1 and r >= w and (n <= 1 or f >= r * (h - 1) + w)
             f, r, p, e = st
-            return e == 1 and p == _PACKED[fmt] and r >= _PACKED[fmt] * w and (n <= 1 or f >= r * h)
+            return e == 1 and p == l.px and r >= l.px * w and (n <= 1 or f >= r * h)
         if not lies_well(tuple(strides(a))):
             a = dense(a)
         st = tuple(int(v) for v in strides(a))
@@ -586,20 +611,19 @@ class Context:
         -> (AvdFrameList, frame count, what the library reads: the pointer arrays during the call, the frames until it is drained)"""
         if isinstance(rotate, bool) or not isinstance(rotate, (int, np.integer)) or not 0 <= rotate <= 3:
             raise ValueError(f"rotate must be 0, 1, 2 or 3 quarter turns (clockwise, stored to displayed picture), got {rotate!r}")
-        if fmt not in _FMT_PLANES:
+        l = LAYOUT.get(fmt)
+        if l is None:
             raise ValueError(f"fmt must be {_FMT_NAMES}, got {fmt!r}")
-        nplanes = _FMT_PLANES[fmt]
-        wide = fmt in _WIDE
-        ty, item = ("uint16", 2) if wide else ("uint8", 1)
-        px = _PACKED.get(fmt, item)                            # bytes per pixel of plane 0
-        if fmt == AVD_FMT_RGBP:                                # a [3,H,W] frame contributes its three channel views as planes
+        nplanes, px, item, wide = l.planes, l.px, l.item, l.item == 2
+        ty = "uint16" if wide else "uint8"
+        if l.handed == "channels":                             # a [3,H,W] frame contributes its three channel views as planes
             frames = list(frames)
             for i, f in enumerate(frames):
                 if len(getattr(f, "shape", ())) != 3 or int(f.shape[0]) != 3:
                     raise ValueError(f"frame {i}: an AVD_FMT_RGBP frame is uint8[3,H,W], got {list(getattr(f, 'shape', ()))}")
             frames = [(f[0], f[1], f[2]) for f in frames]
         else:
-            frames = [(f,) if fmt in _PACKED else tuple(f) for f in frames]
+            frames = [(f,) if l.handed == "stack" else tuple(f) for f in frames]
         if any(len(f) != nplanes for f in frames):
             raise ValueError(f"every frame of the list has {nplanes} plane(s)")
         L = AvdFrameList()
@@ -608,7 +632,7 @@ class Context:
         if not frames:                                         # an empty list has no picture to take a size from: any valid one
             L.h = L.w = HASH
             for p in range(nplanes):
-                L.row_stride[p] = HASH * px if p == 0 else _chroma_shape(fmt, HASH, HASH)[1] * item
+                L.row_stride[p] = HASH * px if p == 0 else _chroma_shape(l, HASH, HASH)[1] * item
             return L, 0, ()
         torch_in = [_is_torch_tensor(p) for f in frames for p in f]
         if any(torch_in) != all(torch_in):
@@ -628,13 +652,10 @@ class Context:
                 raise ValueError(f"the frames of a list are {ty} arrays")
             strides, ptr, _ = _NUMPY_PLANE
         h, w = int(frames[0][0].shape[0]), int(frames[0][0].shape[1])
-        if fmt in _YUV_PLANES:
-            shapes = [(h, w)] + [_chroma_shape(fmt, h, w)] * (nplanes - 1)
-        else:
-            shapes = [(h, w)] * 3 if fmt == AVD_FMT_RGBP else [(h, w, px)]
+        shapes = [(h, w, px)] if l.handed == "stack" else [(h, w)] + [_chroma_shape(l, h, w)] * (nplanes - 1)
         arrays = []
         for p in range(nplanes):
-            dense = (px, 1) if fmt in _PACKED else (item,)
+            dense = (px, 1) if l.handed == "stack" else (item,)
             for i, f in enumerate(frames):
                 if tuple(f[p].shape) != shapes[p]:
                     raise ValueError(f"frame {i}: plane {p} must be {ty}{list(shapes[p])}, got {list(f[p].shape)}")

@@ -1,6 +1,9 @@
 // avd_ingest_clip.h -- one clip as the ingest host path sees it: what it is, whether it is acceptable, where it lands in the staging buffer.
 // Pure host C++ (include/avd.h and the standard library; no HIP type, no avd_ctx), so a stand-alone program can include it
-// (tests/ingest_clip_check.cpp).
+// (tests/ingest_check.cpp).
+//
+// Everything that depends on the layout is ONE row of kIngestLayouts: a new layout is a new row (and a fill policy, a dispatch branch, a record
+// in the binding: DESIGN.md, "adding a layout").  No function below asks "which format is this": it reads the clip's row.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -8,55 +11,103 @@
 #include <vector>
 #include "../../include/avd.h"
 
+// ---- the layouts ---------------------------------------------------------------------------------------------------------------------------
+enum class LayoutFamily { packed_rgb, planar_rgb, yuv420, yuv422 };      // packed_rgb: BGR24 and the packed layouts of RGB producers
+
+// planes behind plane 0 (the chroma planes of 4:2:0 and 4:2:2, the G and B planes of RGBP): h / sub_ydiv rows of w / sub_xdiv samples.
+// The texts are whole literals: what include/avd.h documents can be found here by searching.  They are irregular on purpose (NV12 and the
+// one-plane layouts were first and say "the planes" / "the frame"; the range and turn texts say "picture" of a frame list too).
+struct IngestLayout {
+    int value;
+    const char* name;         // AVD_FMT_<name>
+    int planes, px_bytes;     // px_bytes: of plane 0
+    int sample_bytes;         // 2: 16-bit little-endian words, narrowed to 8 bits as they are loaded; pointers stay byte pointers, strides bytes
+    int sub_ydiv, sub_xdiv;
+    LayoutFamily family;
+    bool even_h, even_w;      // what the subsampling needs even
+    int shared_from;          // planes shared_from .. 2 share their strides (3: none do)
+    int chroma_align;         // bytes the vector fills read of planes 1 and 2 at a time; plane 0 is always read 16 at a time
+    const char *no_range, *no_turn;      // why AVD_FMT_FULL_RANGE / a quarter turn is refused; null: allowed
+    const char *shared, *even, *null_plane, *small_strides;
+};
+
+// the long texts that several rows share
+inline constexpr char kNoRangeRgb[] = "AVD_FMT_FULL_RANGE describes 4:2:0 samples: an RGB picture has no range";
+inline constexpr char kNoTurnRgb[] = "a turned RGB picture is not on the path: producers of RGB hand it over already rotated";
+inline constexpr char kNoTurn422[] = "a turned 4:2:2 picture is not on the path: the conversion does not commute with quarter turns";
+constexpr IngestLayout kIngestLayouts[] = {
+    // value, name, planes, px, sample, ydiv, xdiv, family, even h, w, shared, align, no_range, no_turn, shared, even, null, small
+    {AVD_FMT_BGR24, "BGR24", 1, 3, 1, 1, 1, LayoutFamily::packed_rgb, false, false, 3, 16,
+     "AVD_FMT_FULL_RANGE describes 4:2:0 samples: a BGR picture has no range", "a turned BGR picture is not on the path: cv2 hands BGR over already rotated",
+     nullptr, nullptr, "null frame pointer", "strides smaller than the frame"},
+    {AVD_FMT_NV12, "NV12", 2, 1, 1, 2, 1, LayoutFamily::yuv420, true, true, 3, 16, nullptr, nullptr,
+     nullptr, "NV12 needs even width and height", "null plane pointer", "strides smaller than the planes"},
+    {AVD_FMT_I420, "I420", 3, 1, 1, 2, 2, LayoutFamily::yuv420, true, true, 1, 8, nullptr, nullptr,
+     "the U and V planes of an I420 picture share their strides", "I420 needs even width and height", "null I420 plane pointer", "strides smaller than the I420 planes"},
+    {AVD_FMT_RGB24, "RGB24", 1, 3, 1, 1, 1, LayoutFamily::packed_rgb, false, false, 3, 16, kNoRangeRgb, kNoTurnRgb,
+     nullptr, nullptr, "null frame pointer", "strides smaller than the frame"},
+    {AVD_FMT_BGRA32, "BGRA32", 1, 4, 1, 1, 1, LayoutFamily::packed_rgb, false, false, 3, 16, kNoRangeRgb, kNoTurnRgb,
+     nullptr, nullptr, "null frame pointer", "strides smaller than the frame"},
+    {AVD_FMT_RGBA32, "RGBA32", 1, 4, 1, 1, 1, LayoutFamily::packed_rgb, false, false, 3, 16, kNoRangeRgb, kNoTurnRgb,
+     nullptr, nullptr, "null frame pointer", "strides smaller than the frame"},
+    {AVD_FMT_RGBP, "RGBP", 3, 1, 1, 1, 1, LayoutFamily::planar_rgb, false, false, 0, 16, kNoRangeRgb, kNoTurnRgb,
+     "the R, G and B planes of an RGBP picture share their strides", nullptr, "null RGBP plane pointer", "strides smaller than the RGBP planes"},
+    {AVD_FMT_YUYV422, "YUYV422", 1, 2, 1, 1, 1, LayoutFamily::yuv422, false, true, 3, 16, nullptr, kNoTurn422,
+     nullptr, "YUYV422 needs even width", "null frame pointer", "strides smaller than the frame"},
+    {AVD_FMT_UYVY422, "UYVY422", 1, 2, 1, 1, 1, LayoutFamily::yuv422, false, true, 3, 16, nullptr, kNoTurn422,
+     nullptr, "UYVY422 needs even width", "null frame pointer", "strides smaller than the frame"},
+    {AVD_FMT_I422, "I422", 3, 1, 1, 1, 2, LayoutFamily::yuv422, false, true, 1, 8, nullptr, kNoTurn422,
+     "the U and V planes of an I422 picture share their strides", "I422 needs even width", "null I422 plane pointer", "strides smaller than the I422 planes"},
+    {AVD_FMT_NV16, "NV16", 2, 1, 1, 1, 1, LayoutFamily::yuv422, false, true, 3, 16, nullptr, kNoTurn422,
+     nullptr, "NV16 needs even width", "null NV16 plane pointer", "strides smaller than the NV16 planes"},
+    {AVD_FMT_P010, "P010", 2, 2, 2, 2, 1, LayoutFamily::yuv420, true, true, 3, 16, nullptr, nullptr,
+     nullptr, "P010 needs even width and height", "null P010 plane pointer", "strides smaller than the P010 planes"},
+    {AVD_FMT_I010, "I010", 3, 2, 2, 2, 2, LayoutFamily::yuv420, true, true, 1, 16, nullptr, nullptr,
+     "the U and V planes of an I010 picture share their strides", "I010 needs even width and height", "null I010 plane pointer", "strides smaller than the I010 planes"},
+};
+
+// the row of a layout value; null: the value is not a layout (what include/avd.h says stays refused)
+constexpr const IngestLayout* ingest_layout(int value)
+{
+    for (const IngestLayout& r : kIngestLayouts)
+        if (r.value == value) return &r;
+    return nullptr;
+}
+inline bool known_layout(int layout) { return ingest_layout(layout) != nullptr; }
+
+// ---- the clip ------------------------------------------------------------------------------------------------------------------------------
 // format says what the planes are -- nothing downstream looks at which pointers are null to find out:
-//   AVD_FMT_BGR24  data = the interleaved frames (row_stride / frame_stride)
-//   AVD_FMT_NV12   data = the Y plane, uv = the interleaved chroma plane (uv_row_stride / uv_frame_stride)
-//   AVD_FMT_I420   data = Y, uv = the U plane, v = the V plane; the uv strides hold for both chroma planes
-//   AVD_FMT_RGB24 / _BGRA32 / _RGBA32   data = the interleaved frames, 3 / 4 / 4 bytes per pixel, as BGR24
-//   AVD_FMT_RGBP   data = R, uv = the G plane, v = the B plane, each h x w; row_stride == uv_row_stride and frame_stride == uv_frame_stride
-//   AVD_FMT_YUYV422 / _UYVY422   data = the packed frames, 2 bytes per pixel (a pixel pair per dword), as BGR24
-//   AVD_FMT_I422   as I420, the chroma planes h rows of w / 2 bytes;  AVD_FMT_NV16   as NV12, the chroma plane h rows of w bytes
-//   AVD_FMT_P010   as NV12, AVD_FMT_I010 as I420, every sample a little-endian 16-bit word: rows of 2w (Y), 2w (P010 UV) and w (I010 U, V) bytes;
-//                  the pointers stay byte pointers and the strides bytes
+//   one plane     data = the interleaved frames (row_stride / frame_stride)
+//   two planes    data = the Y plane, uv = the interleaved chroma plane (uv_row_stride / uv_frame_stride)
+//   three planes  data = Y, uv = the U plane, v = the V plane; the uv strides hold for both (RGBP: R, G, B, and all four strides hold for all)
 // rotate: quarter turns clockwise from the stored picture (h, w, the planes and strides: always the STORED one) to the displayed picture, whose
 // size the geometry tables, the band plan and every result follow (4:2:0 clips only).
 // full_range: AVD_FMT_FULL_RANGE of the descriptor, taken out of `format`, which stays the plain layout.
 // list: the frames do not lie at a fixed distance from each other but where a table says -- list[p][f] = plane p of frame f (avd_frame_list;
 // p as data, uv, v).  The arrays are the CALLER's host memory, read while the call runs and never kept.  data / uv / v and the frame strides
 // of such a clip are unused (null, 0); everything else means what it means for a strided clip.
-// A clip is made by bgr_clip / nv12_clip / i420_clip (the entry points that name their format), rgb_clip / yuv422_clip / yuv10_clip (descriptors only), from_public (avd_clip), from_picture
-// (avd_picture) or from_frame_list (avd_frame_list), and by nothing else.
+// A clip is made by make_clip: through bgr_clip / nv12_clip / i420_clip (the entry points that name their format), from_public (avd_clip),
+// from_picture (avd_picture) or from_frame_list (avd_frame_list), and by nothing else.
 struct IngestClip {
     int format;
     const uint8_t *data, *uv, *v;
     const uint8_t* const* list[3];
     bool is_list;         // from_frame_list made it (the arrays may still be null: check_clip refuses that)
-    int planes() const
-    {
-        if (format == AVD_FMT_P010) return 2;
-        if (format == AVD_FMT_I010) return 3;
-        return format == AVD_FMT_NV12 || format == AVD_FMT_NV16 ? 2 : (format == AVD_FMT_I420 || format == AVD_FMT_RGBP || format == AVD_FMT_I422 ? 3 : 1);
-    }
-    bool is_16bit() const { return format == AVD_FMT_P010 || format == AVD_FMT_I010; }      // 10-bit 4:2:0: the samples are 16-bit words, narrowed to 8 bits as they are loaded
-    bool is_420() const { return format == AVD_FMT_NV12 || format == AVD_FMT_I420 || is_16bit(); }
-    bool is_422() const { return format >= AVD_FMT_YUYV422 && format <= AVD_FMT_NV16; }     // chroma subsampled horizontally only: one chroma row per luma row
-    bool is_yuv() const { return is_420() || is_422(); }                                     // converted through the yuv2rgb tables; has a range
-    bool planar_yuv() const { return format == AVD_FMT_I420 || format == AVD_FMT_I422 || format == AVD_FMT_I010; }     // separate U and V planes of w / 2 samples a row, at shared strides
-    bool is_rgb() const { return format >= AVD_FMT_RGB24 && format <= AVD_FMT_RGBP; }      // the four layouts of RGB producers
-    int px_bytes() const      // of plane 0
-    {
-        if (format == AVD_FMT_BGR24 || format == AVD_FMT_RGB24) return 3;
-        if (format == AVD_FMT_BGRA32 || format == AVD_FMT_RGBA32) return 4;
-        return format == AVD_FMT_YUYV422 || format == AVD_FMT_UYVY422 || is_16bit() ? 2 : 1;
-    }
-    // planes 1 and 2: the chroma planes of 4:2:0 (h/2 rows) and of 4:2:2 (h rows) -- w bytes interleaved, w/2 planar; twice that in 16-bit
-    // words: 2w for P010, w for I010 --, the G and B planes of RGBP (the size of plane 0)
-    int sub_rows() const { return is_420() ? h / 2 : h; }
-    int sub_row_bytes() const { return (planar_yuv() ? w / 2 : w) * (is_16bit() ? 2 : 1); }
+    const IngestLayout& row() const { return *ingest_layout(format); }
+    int planes() const { return row().planes; }
+    bool is_16bit() const { return row().sample_bytes == 2; }
+    bool is_420() const { return row().family == LayoutFamily::yuv420; }
+    bool is_422() const { return row().family == LayoutFamily::yuv422; }      // chroma subsampled horizontally only: one chroma row per luma row
+    bool is_yuv() const { return is_420() || is_422(); }                      // converted through the yuv2rgb tables; has a range
+    bool planar_yuv() const { return is_yuv() && planes() == 3; }             // separate U and V planes of w / 2 samples a row, at shared strides
+    bool is_rgb() const { return !is_yuv() && format != AVD_FMT_BGR24; }      // the four layouts of RGB producers
+    int px_bytes() const { return row().px_bytes; }
+    int sub_rows() const { return h / row().sub_ydiv; }
+    int sub_row_bytes() const { return w / row().sub_xdiv * row().sample_bytes; }
     int mem, n, h, w;
     int64_t row_stride, frame_stride, uv_row_stride, uv_frame_stride;
     int rotate;
-    int full_range;       // 4:2:0 and 4:2:2 clips: the samples use 0 .. 255 (ffmpeg's J formats), not 16 .. 235 / 240; 0 from every entry point but from_picture
+    int full_range;       // 4:2:0 and 4:2:2 clips: the samples use 0 .. 255 (ffmpeg's J formats), not 16 .. 235 / 240; 0 from every entry point but the descriptors
     int disp_h() const { return rotate & 1 ? w : h; }
     int disp_w() const { return rotate & 1 ? h : w; }
 };
@@ -64,67 +115,39 @@ struct IngestClip {
 // status 0: accepted; otherwise an avd_status and the text avd_last_error reports
 struct Refusal { int status; const char* why; };
 
-inline IngestClip bgr_clip(const uint8_t* bgr, int mem, int n, int h, int w, int64_t row_stride, int64_t frame_stride)
+// The one constructor: the planes the row has, the strides of planes 0 and 1 (whatever lies behind is not looked at)
+inline IngestClip make_clip(const IngestLayout& L, const uint8_t* const plane[3], const int64_t row[3], const int64_t frame[3], int mem, int n, int h, int w)
 {
     IngestClip k{};
-    k.format = AVD_FMT_BGR24;
-    k.data = bgr; k.mem = mem; k.n = n; k.h = h; k.w = w;
-    k.row_stride = row_stride; k.frame_stride = frame_stride;
+    k.format = L.value;
+    k.mem = mem; k.n = n; k.h = h; k.w = w;
+    k.data = plane[0]; k.row_stride = row[0]; k.frame_stride = frame[0];
+    if (L.planes >= 2) { k.uv = plane[1]; k.uv_row_stride = row[1]; k.uv_frame_stride = frame[1]; }
+    if (L.planes == 3) k.v = plane[2];
     return k;
 }
 
+// the entry points that name their format: one pair of strides for plane 0, one for whatever lies behind it
+inline IngestClip named_clip(int format, const uint8_t* p0, const uint8_t* p1, const uint8_t* p2, int mem, int n, int h, int w, int64_t row0, int64_t row1,
+                             int64_t frame0, int64_t frame1)
+{
+    const uint8_t* const plane[3] = {p0, p1, p2};
+    const int64_t row[3] = {row0, row1, row1}, frame[3] = {frame0, frame1, frame1};
+    return make_clip(*ingest_layout(format), plane, row, frame, mem, n, h, w);
+}
+inline IngestClip bgr_clip(const uint8_t* bgr, int mem, int n, int h, int w, int64_t row_stride, int64_t frame_stride)
+{
+    return named_clip(AVD_FMT_BGR24, bgr, nullptr, nullptr, mem, n, h, w, row_stride, 0, frame_stride, 0);
+}
 inline IngestClip nv12_clip(const uint8_t* y, const uint8_t* uv, int mem, int n, int h, int w, int64_t y_row, int64_t uv_row, int64_t y_frame,
                             int64_t uv_frame)
 {
-    IngestClip k = bgr_clip(y, mem, n, h, w, y_row, y_frame);
-    k.format = AVD_FMT_NV12;
-    k.uv = uv; k.uv_row_stride = uv_row; k.uv_frame_stride = uv_frame;
-    return k;
+    return named_clip(AVD_FMT_NV12, y, uv, nullptr, mem, n, h, w, y_row, uv_row, y_frame, uv_frame);
 }
-
 inline IngestClip i420_clip(const uint8_t* y, const uint8_t* u, const uint8_t* v, int mem, int n, int h, int w, int64_t y_row, int64_t c_row,
                             int64_t y_frame, int64_t c_frame)
 {
-    IngestClip k = nv12_clip(y, u, mem, n, h, w, y_row, c_row, y_frame, c_frame);
-    k.format = AVD_FMT_I420;
-    k.v = v;
-    return k;
-}
-
-// the four 4:2:2 layouts: packed (c1, c2 null), NV16 (c1 = the interleaved chroma plane) or I422 (c1 = U, c2 = V at shared strides)
-inline IngestClip yuv422_clip(int format, const uint8_t* y, const uint8_t* c1, const uint8_t* c2, int mem, int n, int h, int w, int64_t y_row, int64_t c_row,
-                              int64_t y_frame, int64_t c_frame)
-{
-    IngestClip k = bgr_clip(y, mem, n, h, w, y_row, y_frame);
-    k.format = format;
-    if (format == AVD_FMT_I422 || format == AVD_FMT_NV16) { k.uv = c1; k.uv_row_stride = c_row; k.uv_frame_stride = c_frame; }
-    if (format == AVD_FMT_I422) k.v = c2;
-    return k;
-}
-
-// the two 10-bit 4:2:0 layouts in 16-bit words: P010 (c1 = the interleaved chroma plane) or I010 (c1 = U, c2 = V at shared strides); strides in bytes
-inline IngestClip yuv10_clip(int format, const uint8_t* y, const uint8_t* c1, const uint8_t* c2, int mem, int n, int h, int w, int64_t y_row, int64_t c_row,
-                             int64_t y_frame, int64_t c_frame)
-{
-    IngestClip k = nv12_clip(y, c1, mem, n, h, w, y_row, c_row, y_frame, c_frame);
-    k.format = format;
-    if (format == AVD_FMT_I010) k.v = c2;
-    return k;
-}
-
-// the four layouts of RGB producers: packed (g, b null) or planar (AVD_FMT_RGBP: r, g, b share row / frame)
-inline IngestClip rgb_clip(int format, const uint8_t* r, const uint8_t* g, const uint8_t* b, int mem, int n, int h, int w, int64_t row, int64_t frame)
-{
-    IngestClip k = bgr_clip(r, mem, n, h, w, row, frame);
-    k.format = format;
-    if (format == AVD_FMT_RGBP) { k.uv = g; k.v = b; k.uv_row_stride = row; k.uv_frame_stride = frame; }
-    return k;
-}
-
-inline bool known_layout(int layout)
-{
-    return layout == AVD_FMT_BGR24 || layout == AVD_FMT_NV12 || layout == AVD_FMT_I420 || (layout >= AVD_FMT_RGB24 && layout <= AVD_FMT_RGBP) ||
-           (layout >= AVD_FMT_YUYV422 && layout <= AVD_FMT_NV16) || layout == AVD_FMT_P010 || layout == AVD_FMT_I010;
+    return named_clip(AVD_FMT_I420, y, u, v, mem, n, h, w, y_row, c_row, y_frame, c_frame);
 }
 
 // avd_clip is frozen at ABI 3 and has no format field: a clip with uv set is NV12, any other is BGR.  The ONE place where a format is inferred
@@ -135,86 +158,49 @@ inline IngestClip from_public(const avd_clip& c)
     return bgr_clip(c.data, c.mem, c.n, c.h, c.w, c.row_stride, c.frame_stride);
 }
 
-// avd_picture spells its format out: the layout in the low byte, AVD_FMT_FULL_RANGE above it.  Refused here: what the descriptor alone can get
-// wrong, in the order of the lines below; the planes, strides and sizes are check_clip's.
-inline Refusal from_picture(const avd_picture& p, IngestClip& k)
+// ---- the two descriptors -------------------------------------------------------------------------------------------------------------------
+// The descriptors spell their format out: the layout in the low byte, AVD_FMT_FULL_RANGE above it.  Refused here: what the descriptor alone can
+// get wrong, in the order of the lines below (include/avd.h); the planes, strides and sizes are check_clip's.  `k` is written only on success.
+struct DescriptorTexts { const char *size, *format, *rotate, *reserved; };      // the four texts that name the struct
+
+inline Refusal from_descriptor(const DescriptorTexts& t, bool size_ok, int format, int rotate, int reserved, const uint8_t* const plane[3],
+                               const int64_t row[3], const int64_t frame[3], int mem, int n, int h, int w, IngestClip& k)
 {
-    if (p.struct_size != sizeof(avd_picture)) return {AVD_ERR_ARG, "avd_picture.struct_size is not sizeof(avd_picture)"};
-    const int layout = p.format & 0xFF, full_range = (p.format & AVD_FMT_FULL_RANGE) != 0;
-    if ((p.format & ~(0xFF | AVD_FMT_FULL_RANGE)) || !known_layout(layout))
-        return {AVD_ERR_ARG, "bad avd_picture.format"};
-    const bool rgb = layout >= AVD_FMT_RGB24 && layout <= AVD_FMT_RGBP, yuv422 = layout >= AVD_FMT_YUYV422 && layout <= AVD_FMT_NV16;
-    if (full_range && layout == AVD_FMT_BGR24) return {AVD_ERR_ARG, "AVD_FMT_FULL_RANGE describes 4:2:0 samples: a BGR picture has no range"};
-    if (full_range && rgb) return {AVD_ERR_ARG, "AVD_FMT_FULL_RANGE describes 4:2:0 samples: an RGB picture has no range"};
-    if (p.rotate < 0 || p.rotate > 3) return {AVD_ERR_ARG, "avd_picture.rotate must be 0 .. 3 quarter turns"};
-    if (p.reserved != 0) return {AVD_ERR_ARG, "avd_picture.reserved must be 0"};
-    if (layout == AVD_FMT_BGR24) {
-        if (p.rotate) return {AVD_ERR_UNSUPPORTED, "a turned BGR picture is not on the path: cv2 hands BGR over already rotated"};
-        k = bgr_clip(p.plane[0], p.mem, p.n, p.h, p.w, p.row_stride[0], p.frame_stride[0]);
-    } else if (rgb) {
-        if (p.rotate) return {AVD_ERR_UNSUPPORTED, "a turned RGB picture is not on the path: producers of RGB hand it over already rotated"};
-        if (layout == AVD_FMT_RGBP && (p.row_stride[0] != p.row_stride[1] || p.row_stride[1] != p.row_stride[2] || p.frame_stride[0] != p.frame_stride[1] ||
-                                       p.frame_stride[1] != p.frame_stride[2]))
-            return {AVD_ERR_ARG, "the R, G and B planes of an RGBP picture share their strides"};
-        k = rgb_clip(layout, p.plane[0], p.plane[1], p.plane[2], p.mem, p.n, p.h, p.w, p.row_stride[0], p.frame_stride[0]);
-    } else if (yuv422) {
-        if (p.rotate) return {AVD_ERR_UNSUPPORTED, "a turned 4:2:2 picture is not on the path: the conversion does not commute with quarter turns"};
-        if (layout == AVD_FMT_I422 && (p.row_stride[1] != p.row_stride[2] || p.frame_stride[1] != p.frame_stride[2]))
-            return {AVD_ERR_ARG, "the U and V planes of an I422 picture share their strides"};
-        k = yuv422_clip(layout, p.plane[0], p.plane[1], p.plane[2], p.mem, p.n, p.h, p.w, p.row_stride[0], p.row_stride[1], p.frame_stride[0], p.frame_stride[1]);
-    } else if (layout == AVD_FMT_NV12) {
-        k = nv12_clip(p.plane[0], p.plane[1], p.mem, p.n, p.h, p.w, p.row_stride[0], p.row_stride[1], p.frame_stride[0], p.frame_stride[1]);
-    } else if (layout == AVD_FMT_P010 || layout == AVD_FMT_I010) {
-        if (layout == AVD_FMT_I010 && (p.row_stride[1] != p.row_stride[2] || p.frame_stride[1] != p.frame_stride[2]))
-            return {AVD_ERR_ARG, "the U and V planes of an I010 picture share their strides"};
-        k = yuv10_clip(layout, p.plane[0], p.plane[1], p.plane[2], p.mem, p.n, p.h, p.w, p.row_stride[0], p.row_stride[1], p.frame_stride[0], p.frame_stride[1]);
-    } else {
-        if (p.row_stride[1] != p.row_stride[2] || p.frame_stride[1] != p.frame_stride[2])
-            return {AVD_ERR_ARG, "the U and V planes of an I420 picture share their strides"};
-        k = i420_clip(p.plane[0], p.plane[1], p.plane[2], p.mem, p.n, p.h, p.w, p.row_stride[0], p.row_stride[1], p.frame_stride[0], p.frame_stride[1]);
-    }
-    k.rotate = p.rotate;
+    if (!size_ok) return {AVD_ERR_ARG, t.size};
+    const IngestLayout* L = ingest_layout(format & 0xFF);
+    const int full_range = (format & AVD_FMT_FULL_RANGE) != 0;
+    if ((format & ~(0xFF | AVD_FMT_FULL_RANGE)) || !L) return {AVD_ERR_ARG, t.format};
+    if (full_range && L->no_range) return {AVD_ERR_ARG, L->no_range};
+    if (rotate < 0 || rotate > 3) return {AVD_ERR_ARG, t.rotate};
+    if (reserved != 0) return {AVD_ERR_ARG, t.reserved};
+    if (rotate && L->no_turn) return {AVD_ERR_UNSUPPORTED, L->no_turn};
+    for (int p = L->shared_from; p < 2; p++)
+        if (row[p] != row[p + 1] || frame[p] != frame[p + 1]) return {AVD_ERR_ARG, L->shared};
+    k = make_clip(*L, plane, row, frame, mem, n, h, w);
+    k.rotate = rotate;
     k.full_range = full_range;
     return {0, nullptr};
 }
 
-// avd_frame_list: avd_picture with a table of plane pointers per frame in place of base + f * frame_stride.  The same refusals in the same order.
+inline Refusal from_picture(const avd_picture& p, IngestClip& k)
+{
+    static constexpr DescriptorTexts t{"avd_picture.struct_size is not sizeof(avd_picture)", "bad avd_picture.format",
+                                       "avd_picture.rotate must be 0 .. 3 quarter turns", "avd_picture.reserved must be 0"};
+    return from_descriptor(t, p.struct_size == sizeof(avd_picture), p.format, p.rotate, p.reserved, p.plane, p.row_stride, p.frame_stride, p.mem, p.n, p.h, p.w, k);
+}
+
+// avd_frame_list: avd_picture with a table of plane pointers per frame in place of base + f * frame_stride.  A list has no frame strides: zeros
+// share whatever must be shared.
 inline Refusal from_frame_list(const avd_frame_list& p, IngestClip& k)
 {
-    if (p.struct_size != sizeof(avd_frame_list)) return {AVD_ERR_ARG, "avd_frame_list.struct_size is not sizeof(avd_frame_list)"};
-    const int layout = p.format & 0xFF, full_range = (p.format & AVD_FMT_FULL_RANGE) != 0;
-    if ((p.format & ~(0xFF | AVD_FMT_FULL_RANGE)) || !known_layout(layout))
-        return {AVD_ERR_ARG, "bad avd_frame_list.format"};
-    const bool rgb = layout >= AVD_FMT_RGB24 && layout <= AVD_FMT_RGBP, yuv422 = layout >= AVD_FMT_YUYV422 && layout <= AVD_FMT_NV16;
-    if (full_range && layout == AVD_FMT_BGR24) return {AVD_ERR_ARG, "AVD_FMT_FULL_RANGE describes 4:2:0 samples: a BGR picture has no range"};
-    if (full_range && rgb) return {AVD_ERR_ARG, "AVD_FMT_FULL_RANGE describes 4:2:0 samples: an RGB picture has no range"};
-    if (p.rotate < 0 || p.rotate > 3) return {AVD_ERR_ARG, "avd_frame_list.rotate must be 0 .. 3 quarter turns"};
-    if (p.reserved != 0) return {AVD_ERR_ARG, "avd_frame_list.reserved must be 0"};
-    if (layout == AVD_FMT_BGR24) {
-        if (p.rotate) return {AVD_ERR_UNSUPPORTED, "a turned BGR picture is not on the path: cv2 hands BGR over already rotated"};
-        k = bgr_clip(nullptr, p.mem, p.n, p.h, p.w, p.row_stride[0], 0);
-    } else if (rgb) {
-        if (p.rotate) return {AVD_ERR_UNSUPPORTED, "a turned RGB picture is not on the path: producers of RGB hand it over already rotated"};
-        if (layout == AVD_FMT_RGBP && (p.row_stride[0] != p.row_stride[1] || p.row_stride[1] != p.row_stride[2]))
-            return {AVD_ERR_ARG, "the R, G and B planes of an RGBP picture share their strides"};
-        k = rgb_clip(layout, nullptr, nullptr, nullptr, p.mem, p.n, p.h, p.w, p.row_stride[0], 0);
-    } else if (yuv422) {
-        if (p.rotate) return {AVD_ERR_UNSUPPORTED, "a turned 4:2:2 picture is not on the path: the conversion does not commute with quarter turns"};
-        if (layout == AVD_FMT_I422 && p.row_stride[1] != p.row_stride[2]) return {AVD_ERR_ARG, "the U and V planes of an I422 picture share their strides"};
-        k = yuv422_clip(layout, nullptr, nullptr, nullptr, p.mem, p.n, p.h, p.w, p.row_stride[0], p.row_stride[1], 0, 0);
-    } else if (layout == AVD_FMT_NV12) {
-        k = nv12_clip(nullptr, nullptr, p.mem, p.n, p.h, p.w, p.row_stride[0], p.row_stride[1], 0, 0);
-    } else if (layout == AVD_FMT_P010 || layout == AVD_FMT_I010) {
-        if (layout == AVD_FMT_I010 && p.row_stride[1] != p.row_stride[2]) return {AVD_ERR_ARG, "the U and V planes of an I010 picture share their strides"};
-        k = yuv10_clip(layout, nullptr, nullptr, nullptr, p.mem, p.n, p.h, p.w, p.row_stride[0], p.row_stride[1], 0, 0);
-    } else {
-        if (p.row_stride[1] != p.row_stride[2]) return {AVD_ERR_ARG, "the U and V planes of an I420 picture share their strides"};
-        k = i420_clip(nullptr, nullptr, nullptr, p.mem, p.n, p.h, p.w, p.row_stride[0], p.row_stride[1], 0, 0);
-    }
+    static constexpr DescriptorTexts t{"avd_frame_list.struct_size is not sizeof(avd_frame_list)", "bad avd_frame_list.format",
+                                       "avd_frame_list.rotate must be 0 .. 3 quarter turns", "avd_frame_list.reserved must be 0"};
+    const uint8_t* const none[3] = {nullptr, nullptr, nullptr};
+    const int64_t zero[3] = {0, 0, 0};
+    const Refusal r = from_descriptor(t, p.struct_size == sizeof(avd_frame_list), p.format, p.rotate, p.reserved, none, p.row_stride, zero, p.mem, p.n, p.h, p.w, k);
+    if (r.status) return r;
     k.is_list = true;
     for (int i = 0; i < k.planes(); i++) k.list[i] = p.plane[i];
-    k.rotate = p.rotate;
-    k.full_range = full_range;
     return {0, nullptr};
 }
 
@@ -225,47 +211,32 @@ inline Refusal from_frame_list(const avd_frame_list& p, IngestClip& k)
 // entry), a row stride or -- where frame strides are looked at: a strided clip of several frames -- a frame stride that is odd.
 inline Refusal check_clip(const IngestClip& k)
 {
-    // bgr: ONE packed plane (BGR24 and the packed RGB layouts: their refusals read alike); planar: I420; rgbp: three full-size planes
-    // (the packed 4:2:2 layouts are one plane too; I422 and NV16 have texts of their own)
-    const bool bgr = k.planes() == 1, planar = k.format == AVD_FMT_I420, rgbp = k.format == AVD_FMT_RGBP;
-    const bool i422 = k.format == AVD_FMT_I422, nv16 = k.format == AVD_FMT_NV16, p010 = k.format == AVD_FMT_P010, i010 = k.format == AVD_FMT_I010;
+    const IngestLayout& L = k.row();
     const int n = k.n, h = k.h, w = k.w;
     if (k.mem != AVD_MEM_HOST && k.mem != AVD_MEM_DEVICE) return {AVD_ERR_ARG, "mem must be AVD_MEM_HOST or AVD_MEM_DEVICE"};
     if (n < 0 || h <= 0 || w <= 0 || h > 16384 || w > 16384) return {AVD_ERR_ARG, "bad frame geometry"};
-    if (k.is_420() && ((h | w) & 1))
-        return {AVD_ERR_UNSUPPORTED, planar ? "I420 needs even width and height"
-                                            : (p010 ? "P010 needs even width and height" : (i010 ? "I010 needs even width and height" : "NV12 needs even width and height"))};
-    if (k.is_422() && (w & 1))      // the height may be odd: nothing is subsampled vertically
-        return {AVD_ERR_UNSUPPORTED, i422 ? "I422 needs even width" : (nv16 ? "NV16 needs even width" : (k.format == AVD_FMT_YUYV422 ? "YUYV422 needs even width" : "UYVY422 needs even width"))};
+    if ((L.even_h && (h & 1)) || (L.even_w && (w & 1))) return {AVD_ERR_UNSUPPORTED, L.even};      // 4:2:2: the height may be odd, nothing is subsampled vertically
     if (h < AVD_HASH || w < AVD_HASH) return {AVD_ERR_UNSUPPORTED, "frame smaller than 32x32: INTER_AREA upscaling is not on the path"};
+    const uint8_t* const base[3] = {k.data, k.uv, k.v};
     if (k.is_list) {
         if (n > 0) {
-            for (int p = 0; p < k.planes(); p++)
+            for (int p = 0; p < L.planes; p++)
                 if (!k.list[p]) return {AVD_ERR_ARG, "null plane array of a frame list"};
-            for (int p = 0; p < k.planes(); p++)
+            for (int p = 0; p < L.planes; p++)
                 for (int f = 0; f < n; f++)
                     if (!k.list[p][f]) return {AVD_ERR_ARG, "null plane pointer in a frame list"};
         }
-    } else if (n > 0 && (!k.data || (!bgr && !k.uv) || (k.planes() == 3 && !k.v)))
-        return {AVD_ERR_ARG, bgr ? "null frame pointer"
-                                 : (planar ? "null I420 plane pointer"
-                                           : (rgbp ? "null RGBP plane pointer" : (i422 ? "null I422 plane pointer" : (nv16 ? "null NV16 plane pointer" : (p010 ? "null P010 plane pointer" : (i010 ? "null I010 plane pointer" : "null plane pointer"))))))};
-    const int64_t row = (int64_t)w * k.px_bytes(), crow = k.sub_row_bytes();      // bytes of a row of plane 0 and of the planes behind it
+    } else
+        for (int p = 0; p < L.planes && n > 0; p++)
+            if (!base[p]) return {AVD_ERR_ARG, L.null_plane};
+    const int64_t row = (int64_t)w * L.px_bytes, crow = k.sub_row_bytes();      // bytes of a row of plane 0 and of the planes behind it
     const bool strided = !k.is_list && n > 1;
     bool small = k.row_stride < row || (strided && k.frame_stride < k.row_stride * (h - 1) + row);
-    if (!bgr) small = small || k.uv_row_stride < crow || (strided && k.uv_frame_stride < k.uv_row_stride * (k.sub_rows() - 1) + crow);
-    if (small)
-        return {AVD_ERR_ARG, bgr ? "strides smaller than the frame"
-                                 : (planar ? "strides smaller than the I420 planes"
-                                           : (rgbp ? "strides smaller than the RGBP planes"
-                                                   : (i422 ? "strides smaller than the I422 planes"
-                                                           : (nv16 ? "strides smaller than the NV16 planes"
-                                                                   : (p010 ? "strides smaller than the P010 planes"
-                                                                           : (i010 ? "strides smaller than the I010 planes" : "strides smaller than the planes"))))))};
-    if (k.is_16bit()) {
+    if (L.planes > 1) small = small || k.uv_row_stride < crow || (strided && k.uv_frame_stride < k.uv_row_stride * (k.sub_rows() - 1) + crow);
+    if (small) return {AVD_ERR_ARG, L.small_strides};
+    if (L.sample_bytes == 2) {
         bool odd = ((k.row_stride | k.uv_row_stride) & 1) || (strided && ((k.frame_stride | k.uv_frame_stride) & 1));
-        const uint8_t* const base[3] = {k.data, k.uv, k.v};
-        for (int p = 0; p < k.planes() && n > 0; p++) {
+        for (int p = 0; p < L.planes && n > 0; p++) {
             if (!k.is_list) odd = odd || ((uintptr_t)base[p] & 1);
             else
                 for (int f = 0; f < n; f++) odd = odd || ((uintptr_t)k.list[p][f] & 1);
@@ -362,16 +333,33 @@ inline ListStage list_stage(const IngestClip& c)
     return s;
 }
 
-// May a list run the vector fills?  Their rule (launch_preprocess: w % 16 == 0, 16-byte aligned planes and row strides, 8 bytes for the
-// chroma planes of I420 and I422; 16 for every plane of RGBP, of P010 and I010 and for the packed RGB layouts) must hold for EVERY frame; one frame that fails sends the whole list through the scalar fill, with the same results.
-// tab[p * n + f]: where the kernel will find plane p of frame f (device addresses: the caller's planes, or their places in the staging buffer).
+// ---- may a clip run the 16-byte fills? ------------------------------------------------------------------------------------------------------
+// The ONE rule, for lists and strided clips: w % 16 == 0; plane 0 and its row stride 16-byte aligned; the planes behind it and their row stride
+// aligned to the row's chroma_align (8 for the chroma planes of I420 and I422, which the table fills read 8 bytes at a time; 16 for every
+// other, RGBP's G and B included).  It must hold at EVERY address a frame's plane can have: addr(p, i), i < count, names them.  A clip that
+// fails runs the scalar fill, with the same results.  (w is the stored width: where a quarter turn makes it differ from the displayed one,
+// the turned fill is chosen whatever this says.)
+template <typename Addr>
+inline bool vec_eligible(const IngestClip& c, int count, Addr addr)
+{
+    const IngestLayout& L = c.row();
+    if (c.w % 16 != 0 || c.row_stride % 16 != 0 || (L.planes > 1 && c.uv_row_stride % L.chroma_align != 0)) return false;
+    for (int p = 0; p < L.planes; p++)
+        for (int i = 0; i < count; i++)
+            if (addr(p, i) % (p == 0 ? 16 : L.chroma_align) != 0) return false;
+    return true;
+}
+
+// a list: every frame of every plane.  tab[p * n + f]: where the kernel will find plane p of frame f (device addresses: the caller's planes, or
+// their places in the staging buffer); one frame that fails sends the whole list through the scalar fill.
 inline bool list_vec_eligible(const IngestClip& c, const uint8_t* const* tab)
 {
-    const bool bgr = c.planes() == 1;
-    const int ca = c.planar_yuv() && !c.is_16bit() ? 8 : 16;
-    if (c.w % 16 != 0 || c.row_stride % 16 != 0 || (!bgr && c.uv_row_stride % ca != 0)) return false;
-    for (int p = 0; p < c.planes(); p++)
-        for (int f = 0; f < c.n; f++)
-            if ((uintptr_t)tab[(size_t)p * c.n + f] % (p == 0 ? 16 : ca) != 0) return false;
-    return true;
+    return vec_eligible(c, c.n, [&](int p, int f) { return (uintptr_t)tab[(size_t)p * c.n + f]; });
+}
+
+// a strided clip: each plane's base and the base plus its frame stride (the stride is looked at whatever n is)
+inline bool strided_vec_eligible(const IngestClip& c, const uint8_t* d_in, const uint8_t* d_uv, const uint8_t* d_v)
+{
+    const uintptr_t base[3] = {(uintptr_t)d_in, (uintptr_t)d_uv, (uintptr_t)d_v};
+    return vec_eligible(c, 2, [&](int p, int i) { return base[p] + (uintptr_t)i * (uintptr_t)(p == 0 ? c.frame_stride : c.uv_frame_stride); });
 }

@@ -1379,12 +1379,6 @@ BandPlan band_plan(int w)
     return p;
 }
 
-static bool aligned_to(int a, const void* p, int64_t row_stride, int64_t frame_stride)
-{
-    return reinterpret_cast<uintptr_t>(p) % a == 0 && row_stride % a == 0 && frame_stride % a == 0;
-}
-static bool aligned16(const void* p, int64_t row_stride, int64_t frame_stride) { return aligned_to(16, p, row_stride, frame_stride); }
-
 // ---- runtime values as template arguments (in the style of fb_dispatch_width): f receives std::integral_constant objects ----
 template <typename F>
 static auto dispatch_bool(bool v, F&& f) { return v ? f(std::true_type{}) : f(std::false_type{}); }
@@ -1440,12 +1434,7 @@ int launch_preprocess(avd_ctx* ctx, const IngestClip& clip, const uint8_t* d_in,
     const bool rgbp = clip.format == AVD_FMT_RGBP, px32 = clip.format == AVD_FMT_BGRA32 || clip.format == AVD_FMT_RGBA32;
     const bool rgb = clip.format == AVD_FMT_RGB24 || clip.format == AVD_FMT_RGBA32;     // packed pixels stored R, G, B
     const bool wide = clip.is_16bit();                 // P010 (with NV12's planes) and I010 (with I420's)
-    // the planar chroma planes are read 8 bytes at a time (I420's and I422's table fills; I010's 16), every other plane 16; packed 4:2:2 has no other plane
-    const int ca = wide ? 16 : 8;
-    const bool chroma_ok = planar ? aligned_to(ca, d_uv, clip.uv_row_stride, clip.uv_frame_stride) && aligned_to(ca, d_v, clip.uv_row_stride, clip.uv_frame_stride)
-                           : rgbp ? aligned16(d_uv, clip.uv_row_stride, clip.uv_frame_stride) && aligned16(d_v, clip.uv_row_stride, clip.uv_frame_stride)
-                                  : bgr || clip.planes() == 1 || aligned16(d_uv, clip.uv_row_stride, clip.uv_frame_stride);
-    const bool vec = list ? list->aligned : P.w % 16 == 0 && aligned16(d_in, clip.row_stride, clip.frame_stride) && chroma_ok;
+    const bool vec = list ? list->aligned : strided_vec_eligible(clip, d_in, d_uv, d_v);      // the one rule of avd_ingest_clip.h
     int ni = vec && bgr && !px32 ? band_plan(P.w).ni : 0;       // the layouts with a staged fill: BGR24, RGB24, RGBP
     // planar RGB: the byte gather needs a few registers more than BGR's alignbyte, and NI = 9 (2048 < w <= 4096) no longer fits the 128 VGPRs of
     // __launch_bounds__(256, 4) without spilling: those widths run the 16-byte fill

@@ -1,6 +1,6 @@
 """Clips as lists of separately allocated frames (include/avd_frame_list.h), the part that needs no GPU: the descriptor's presence in header,
 library and binding, and the host logic of csrc/avd_ingest_clip.h -- from_frame_list's and check_clip's refusals in their documented order, the
-staging plan of a host list (list_stage) and the vector-fill eligibility (list_vec_eligible).  tests/framelist_check.cpp is compiled with the
+staging plan of a host list (list_stage) and the vector-fill eligibility (list_vec_eligible).  tests/ingest_check.cpp is compiled with the
 host C++ compiler and the address / undefined-behaviour sanitizers and run as its own process; nothing sanitized is loaded into Python.
 
 The staging rule, restated here and computed independently in `plan`: the spans of all (frame, plane) pairs in address order, merged where they
@@ -9,36 +9,20 @@ overlap or touch; every merged span on a 256-byte boundary; a plane at span offs
 import ctypes
 import os
 import re
-import shutil
-import subprocess
 
 import pytest
 
 from avd_hip import _lib
+from tests.ingest_host_kit import (ARG, BGR, DEVICE, FULL, HOST, I420, NV12, OK, PLANES, ROOT, T_GEOM, T_MEM, T_NULL_ARRAY, T_NULL_ENTRY, UNSUPPORTED,  # noqa: F401
+                                   frame_list, parse, picture, program, r256, t_format, t_reserved, t_rotate, t_size)
+from tests.ingest_host_kit import T_SMALL as T_32
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BGR, NV12, I420, FULL = 0, 1, 2, 0x100
-PLANES = {BGR: 1, NV12: 2, I420: 3}
-HOST, DEVICE = 0, 1
-OK, ARG, UNSUPPORTED = 0, -1, -4
-T_SIZE = "avd_frame_list.struct_size is not sizeof(avd_frame_list)"
-T_FORMAT = "bad avd_frame_list.format"
+T_SIZE, T_FORMAT, T_ROTATE, T_RESERVED = (t("frame_list") for t in (t_size, t_format, t_rotate, t_reserved))
 T_RANGE = "AVD_FMT_FULL_RANGE describes 4:2:0 samples: a BGR picture has no range"
-T_ROTATE = "avd_frame_list.rotate must be 0 .. 3 quarter turns"
-T_RESERVED = "avd_frame_list.reserved must be 0"
 T_BGR_TURN = "a turned BGR picture is not on the path: cv2 hands BGR over already rotated"
 T_UV = "the U and V planes of an I420 picture share their strides"
-T_MEM = "mem must be AVD_MEM_HOST or AVD_MEM_DEVICE"
-T_GEOM = "bad frame geometry"
 T_EVEN = {NV12: "NV12 needs even width and height", I420: "I420 needs even width and height"}
-T_32 = "frame smaller than 32x32: INTER_AREA upscaling is not on the path"
-T_NULL_ARRAY = "null plane array of a frame list"
-T_NULL_ENTRY = "null plane pointer in a frame list"
 T_STRIDES = {BGR: "strides smaller than the frame", NV12: "strides smaller than the planes", I420: "strides smaller than the I420 planes"}
-
-
-def r256(v):
-    return (v + 255) // 256 * 256
 
 
 def plane_bytes(fmt, h, w, rows):
@@ -78,42 +62,17 @@ def plan(c):
                 total=r256(spans[-1][2] + spans[-1][1]), copied=sum(s[1] for s in spans))
 
 
-@pytest.fixture(scope="module")
-def program(tmp_path_factory):
-    cxx = os.environ.get("CXX") or shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
-    assert cxx, "no host C++ compiler"
-    exe = str(tmp_path_factory.mktemp("framelist") / "framelist_check")
-    subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                    "-o", exe, os.path.join(ROOT, "tests", "framelist_check.cpp")], check=True)
-
-    def run(lines):
-        r = subprocess.run([exe], input="\n".join(lines) + "\n", capture_output=True, text=True)
-        assert r.returncode == 0 and not r.stderr, (r.returncode, r.stderr)       # a sanitizer report ends the program with a non-zero status
-        out = r.stdout.splitlines()
-        assert len(out) == len(lines)
-        return out
-    return run
-
-
 def run_lists(program, cases):
-    lines = []
-    for c in cases:
-        m = max(c["n"], 0)
-        flat = [a for p in range(3) for a in (c["addrs"][p] + [0] * m)[:m]]
-        lines.append(" ".join(str(v) for v in ["L", c["fmt"], c["mem"], c["n"], c["h"], c["w"], c["rotate"], c["reserved"], c["size_delta"], *c["rows"],
-                                               c["null_arrays"], *flat]))
-    out = []
-    ints = lambda s: [int(v) for v in s.split(",")] if s else []
-    for line in program(lines):
-        status, why, nspans, off, nbytes, plane_off, total, copied, given, staged = line.split("|")
-        out.append(dict(status=int(status), why=why, nspans=int(nspans), off=ints(off), bytes=ints(nbytes), plane_off=ints(plane_off), total=int(total),
-                        copied=int(copied), given=int(given), staged=int(staged)))
-    return out
+    lines = [frame_list(c["fmt"], c["addrs"], mem=c["mem"], h=c["h"], w=c["w"], rotate=c["rotate"], reserved=c["reserved"], rs=c["rows"],
+                        null_arrays=c["null_arrays"], size_delta=c["size_delta"], n=c["n"]) for c in cases]
+    return [parse(g) for g in program(lines)]
 
 
 def run_strided(program, fmt, n, h, w, bases, rows, frames):
-    nspans, total, copied = program([" ".join(str(v) for v in ["S", fmt, n, h, w, *bases, *rows, *frames])])[0].split("|")
-    return dict(nspans=int(nspans), total=int(total), copied=int(copied))
+    """-> the staging plan of the STRIDED host clip (from_picture, clip_stage)"""
+    g = parse(program([picture(fmt, n=n, h=h, w=w, planes=bases, rs=rows, fs=frames)])[0])
+    assert g["status"] == OK, g
+    return {k: g[k] for k in ("nspans", "total", "copied")}
 
 
 # ---- ABI presence ----------------------------------------------------------------------------------------------------------------------------
@@ -128,10 +87,10 @@ def test_descriptor_is_the_same_in_header_binding_and_compiler(program):
             names += [re.sub(r"\[\d+\]", "", v.strip().split()[-1].lstrip("*")) for v in decl.split(",")]
     assert names == ["struct_size", "format", "plane", "row_stride", "mem", "n", "h", "w", "rotate", "reserved"]
     assert names == [f[0] for f in _lib.AvdFrameList._fields_]
-    size, picture, offsets = program(["A"])[0].split("|")
-    assert int(size) == ctypes.sizeof(_lib.AvdFrameList) == 80
-    assert [int(v) for v in offsets.split(",")] == [getattr(_lib.AvdFrameList, f).offset for f in names[1:]]
-    assert int(picture) == ctypes.sizeof(_lib.AvdPicture) == 104                 # avd_picture is untouched
+    a = parse(program(["A"])[0])
+    assert a["list_size"] == ctypes.sizeof(_lib.AvdFrameList) == 80
+    assert a["list_offsets"] == [getattr(_lib.AvdFrameList, f).offset for f in names[1:]]
+    assert a["picture_size"] == ctypes.sizeof(_lib.AvdPicture) == 104            # avd_picture is untouched
 
 
 def test_the_three_symbols_are_declared_bound_and_exported():

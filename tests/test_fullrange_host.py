@@ -5,27 +5,24 @@ tests/yuv_tables_reference.py restates libswscale's table converter literally, w
 against what the construction must give: the gray axis is the identity, the integers are the ones written out below, the table index
 Y + offset spans [-226, 480] -- five entries lower and five higher than the limited window [-221, 475] the ingest kernels' tables were
 once dimensioned for.  Then the binding's constant and struct, the .y4m range token, and the descriptor's refusals through a stand-alone
-program (tests/fullrange_clip_check.cpp, built with the address and undefined-behaviour sanitizers)."""
+program (tests/ingest_check.cpp, built with the address and undefined-behaviour sanitizers by tests/ingest_host_kit.py, which also
+holds the case writers, the answer reader and the texts every layout shares)."""
 import ctypes
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 from avd_hip import _lib, sources
 from tests import yuv_tables_reference as ref
+from tests.ingest_host_kit import ARG, BGR, FULL, I420, NV12, OK, ROOT, T_MEM, UNSUPPORTED, parse, picture  # noqa: F401
+from tests.ingest_host_kit import program as _lines  # noqa: F401
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BGR, NV12, I420, FULL = 0, 1, 2, 0x100
-OK, ARG, UNSUPPORTED = 0, -1, -4
 T_FORMAT = "bad avd_picture.format"
 T_BGR_RANGE = "AVD_FMT_FULL_RANGE describes 4:2:0 samples: a BGR picture has no range"
 T_ROTATE = "avd_picture.rotate must be 0 .. 3 quarter turns"
 T_RESERVED = "avd_picture.reserved must be 0"
-T_MEM = "mem must be AVD_MEM_HOST or AVD_MEM_DEVICE"
 
 
 # ---- the restatement -----------------------------------------------------------------------------------------------------------------------
@@ -139,23 +136,12 @@ def test_y4m_range_token_round_trip(tmp_path):
 
 # ---- the descriptor, host side ----------------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
-def program(tmp_path_factory):
-    cxx = os.environ.get("CXX") or shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
-    assert cxx, "no host C++ compiler"
-    exe = str(tmp_path_factory.mktemp("fullrange_clip") / "fullrange_clip_check")
-    subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                    "-o", exe, os.path.join(ROOT, "tests", "fullrange_clip_check.cpp")], check=True)
-
+def program(_lines):
     def run(cases):
-        """cases: [(format, rotate, reserved, mem)] -> [(status, why, format, full_range, rotate)]"""
-        r = subprocess.run([exe], input="".join("%d %d %d %d\n" % c for c in cases), capture_output=True, text=True)
-        assert r.returncode == 0 and not r.stderr, (r.returncode, r.stderr)       # a sanitizer report ends the program with a non-zero status
-        out = []
-        for line in r.stdout.splitlines():
-            status, why, fmt, full, rot = line.split("|")
-            out.append((int(status), why, int(fmt), int(full), int(rot)))
-        assert len(out) == len(cases)
-        return out
+        """cases: [(format, rotate, reserved, mem)] of an otherwise valid picture (2 frames of 64 x 64, tight strides) ->
+        [(status, why, format, full_range, rotate)], the last three as the IngestClip carries them (zeros where from_picture refused)"""
+        got = [parse(g) for g in _lines([picture(fmt, mem=mem, n=2, h=64, w=64, rotate=rotate, reserved=reserved) for fmt, rotate, reserved, mem in cases])]
+        return [(g["status"], g["why"], g["format"], g["full"], g["rotate"]) for g in got]
     return run
 
 

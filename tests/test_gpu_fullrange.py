@@ -18,26 +18,23 @@ pytestmark = pytest.mark.gpu
 import avd_hip  # noqa: E402
 from avd_hip import AvdError, _lib, synth  # noqa: E402
 from tests import yuv_tables_reference as ref  # noqa: E402
+from tests.ingest_gpu_kit import P_LDS, P_PITCH, check_plan  # noqa: E402
 from tests.test_gpu_i420 import _device_view  # noqa: E402
 
-P_H, P_W, P_ROWS, P_NBANDS, P_PITCH, P_NI, P_LDS, P_KERNEL = range(8)
 KERNEL_NAMES = ("bgr_scalar", "bgr_vec16", "bgr_staged", "nv12_scalar", "nv12_tables", "i420_scalar", "i420_tables", "nv12_strip", "i420_strip")
 SCALAR, TABLES, STRIP = {"nv12": 3, "i420": 5}, {"nv12": 4, "i420": 6}, {"nv12": 7, "i420": 8}
 
 
 def _check_plan(ctx, h, w, kernel, rows, rotate, full):
     """h, w: the DISPLAYED picture"""
-    p = ctx.debug_fetch("ingest_plan", (8,), np.int32)
-    tag = (h, w, rotate, full, [int(v) for v in p])
-    assert KERNEL_NAMES[p[P_KERNEL]] == KERNEL_NAMES[kernel], tag
-    assert (p[P_H], p[P_W], p[P_ROWS], p[P_NBANDS], p[P_NI]) == (h, w, rows, -(-h // rows), 0), tag
+    p = check_plan(ctx, h, w, kernel, rows, rotate=rotate, full_range=full)
+    tag = (h, w, rotate, full, p)
     if kernel not in SCALAR.values():
         # the three gray tables behind the tile: 704 entries each hold the limited window [-221, 475], the full one [-226, 480] needs 707 at least
         assert p[P_LDS] >= (rows + 2) * p[P_PITCH] + 3 * 4 * (707 if full else 704), tag
         if not full:
             assert p[P_LDS] == ((rows + 2) * p[P_PITCH] + 15) // 16 * 16 + 3 * 4 * 704, tag      # as it was before there was a range
         assert p[P_LDS] <= 64 * 1024, tag
-    assert ctx.ingest_rotate() == rotate and ctx.ingest_range() == int(full), tag
 
 
 # ---- the displayed pictures and what is expected of them, formed once and left unchanged ---------------------------------------------------

@@ -16,50 +16,19 @@ pytestmark = pytest.mark.gpu
 
 import avd_hip  # noqa: E402
 from avd_hip import AvdError, synth  # noqa: E402
+from tests.ingest_gpu_kit import check_outputs as _check_outputs  # noqa: E402
+from tests.ingest_gpu_kit import check_plan as _check_plan  # noqa: E402
+from tests.ingest_gpu_kit import heights_even as _heights  # noqa: E402
+from tests.ingest_gpu_kit import reference  # noqa: E402
 from tests.test_nv12 import _planes  # noqa: E402
 
-# "ingest_plan" (include/avd.h): h, w, rows_per_band, nbands, pitch, NI, dynamic LDS bytes, kernel
-P_H, P_W, P_ROWS, P_NBANDS, P_PITCH, P_NI, P_LDS, P_KERNEL = range(8)
 KERNEL_NAMES = ("bgr_scalar", "bgr_vec16", "bgr_staged", "nv12_scalar", "nv12_tables", "i420_scalar", "i420_tables")
 I420_SCALAR, I420_TABLES = 5, 6
 
 
-def _check_plan(ctx, h, w, kernel, rows, lds=None):
-    p = ctx.debug_fetch("ingest_plan", (8,), np.int32)
-    tag = (h, w, [int(v) for v in p])
-    assert KERNEL_NAMES[p[P_KERNEL]] == KERNEL_NAMES[kernel], tag
-    assert p[P_ROWS] == rows, tag
-    assert (p[P_H], p[P_W]) == (h, w) and p[P_NBANDS] == -(-h // rows) and p[P_NI] == 0, tag
-    assert p[P_PITCH] % 16 == 0 and p[P_PITCH] >= w + 17, tag
-    assert p[P_LDS] >= (rows + 2) * p[P_PITCH], tag
-    if lds is not None:
-        assert p[P_LDS] == lds, tag
-
-
 def _reference(oracle, y, uv):
-    """(small320, hash, lap_sum, lap_sumsq, area) of the oracle on swscale's BGR of the NV12 form"""
-    bgr = oracle.nv12_to_bgr(y, uv)
-    area = np.stack([oracle.resize_area(oracle.bgr2gray(f), 32, 32) for f in bgr])
-    return tuple(oracle.preprocess_bgr(bgr)) + (area,)
-
-
-def _check_outputs(ctx, got, want, tag):
-    """got = what preprocess_i420 just returned on ctx; want = _reference(...)"""
-    n = len(want[4])
-    area = ctx.debug_fetch("area", (n, 32, 32), np.uint8)
-    for name, a, b in zip(("lap_sum", "lap_sumsq", "area", "small320", "hash"), (got[2], got[3], area, got[0], got[1]),
-                          (want[2], want[3], want[4], want[0], want[1])):
-        assert np.array_equal(a, b), (tag, name, int(np.count_nonzero(np.asarray(a) != np.asarray(b))))
-
-
-def _heights(rows):
-    """Even heights above the 32-row minimum: plans of an odd number of rows get a one-row and a full last band, even plans a two-row
-    and a full one (the rule of the NV12 sweep)."""
-    first = lambda rem: next(h for h in range(34, 34 + 2 * rows, 2) if h % rows == rem % rows)
-    return tuple(dict.fromkeys(first(rem) for rem in ((1, 0) if rows % 2 else (2, 0))))
-
-
-assert [_heights(r) for r in (14, 9, 7, 5, 3, 1)] == [(44, 42), (46, 36), (36, 42), (36, 40), (34, 36), (34,)]
+    """the oracle on swscale's BGR of the NV12 form"""
+    return reference(oracle, oracle.nv12_to_bgr(y, uv))
 
 
 def _cases(kernel, widths_rows):
@@ -78,7 +47,7 @@ def test_i420_plan_classes(ctx, oracle, kernel, w, rows, h):
     y, uv = _planes(2, h, w, seed=h + w)
     got = ctx.preprocess_i420(*synth.nv12_to_i420(y, uv))
     lds = 57696 if (kernel, w) == (I420_TABLES, 16384) else None          # 3 * 16416 + 3 * 4 * 704, as NV12
-    _check_plan(ctx, h, w, kernel, rows, lds)
+    _check_plan(ctx, h, w, kernel, rows, lds=lds)
     _check_outputs(ctx, got, _reference(oracle, y, uv), (h, w))
     assert ctx.stage_bytes() == y.nbytes + uv.nbytes                      # three separately allocated planes: three spans
 

@@ -18,63 +18,21 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 from avd_hip import synth  # noqa: E402
+from tests.ingest_gpu_kit import P_KERNEL, P_NBANDS, check_outputs, reference  # noqa: E402
+from tests.ingest_gpu_kit import check_plan as _check_plan  # noqa: E402
+from tests.ingest_gpu_kit import heights as _heights  # noqa: E402
+from tests.ingest_gpu_kit import heights_even as _heights_nv12  # noqa: E402
+from tests.ingest_gpu_kit import plan as _plan  # noqa: E402
 from tests.test_nv12 import _planes  # noqa: E402
 
 # enum IngestKernel (avd_internal.h) and the layout of "ingest_plan" (include/avd.h)
 BGR_SCALAR, BGR_VEC16, BGR_STAGED, NV12_SCALAR, NV12_TABLES = range(5)
 KERNEL_NAMES = ("bgr_scalar", "bgr_vec16", "bgr_staged", "nv12_scalar", "nv12_tables")
-P_H, P_W, P_ROWS, P_NBANDS, P_PITCH, P_NI, P_LDS, P_KERNEL = range(8)
-
-
-def _plan(ctx):
-    return ctx.debug_fetch("ingest_plan", (8,), np.int32)
-
-
-def _check_plan(ctx, h, w, kernel, rows, ni=0, lds=None):
-    p = _plan(ctx)
-    tag = (h, w, [int(v) for v in p])
-    assert KERNEL_NAMES[p[P_KERNEL]] == KERNEL_NAMES[kernel], tag
-    assert p[P_ROWS] == rows, tag
-    assert (p[P_H], p[P_W]) == (h, w) and p[P_NBANDS] == -(-h // rows), tag
-    assert p[P_NI] == ni, tag
-    assert p[P_PITCH] % 16 == 0 and p[P_PITCH] >= w + 17, tag            # 16 B left of pixel 0, the halo byte right of pixel w - 1
-    assert p[P_LDS] >= (rows + 2) * p[P_PITCH], tag
-    if lds is not None:
-        assert p[P_LDS] == lds, tag
-
-
-def _oracle_area(oracle, frames):
-    return np.stack([oracle.resize_area(oracle.bgr2gray(f), 32, 32) for f in frames])
 
 
 def _check_outputs(ctx, oracle, got, ref_bgr, tag):
     """got = (small320, hash, lap_sum, lap_sumsq) of the call that just ran on ctx; ref_bgr = the frames the oracle sees."""
-    n = len(ref_bgr)
-    area = ctx.debug_fetch("area", (n, 32, 32), np.uint8)
-    want = oracle.preprocess_bgr(ref_bgr)
-    o_area = _oracle_area(oracle, ref_bgr)
-    for name, a, b in zip(("lap_sum", "lap_sumsq"), got[2:], want[2:]):
-        assert np.array_equal(a, b), (tag, name, a.tolist(), b.tolist())
-    assert np.array_equal(area, o_area), (tag, "area", np.argwhere(area != o_area)[:5].tolist())
-    assert np.array_equal(got[0], want[0]), (tag, "small320", int(np.count_nonzero(got[0] != want[0])))
-    assert np.array_equal(got[1], want[1]), (tag, "hash")
-
-
-def _heights(rows):
-    """The smallest frames (above the 32-row minimum) in which a plan of `rows` rows per band has a one-row last band, a two-row last
-    band (plans of more than two rows) and a full one."""
-    first = lambda rem: next(h for h in range(33, 33 + rows) if h % rows == rem % rows)
-    return tuple(dict.fromkeys(first(rem) for rem in ((1, 2, 0) if rows > 2 else (1, 0))))
-
-
-def _heights_nv12(rows):
-    """NV12 needs even heights: odd plans get a one-row and a full last band, even plans a two-row and a full one."""
-    first = lambda rem: next(h for h in range(34, 34 + 2 * rows, 2) if h % rows == rem % rows)
-    return tuple(dict.fromkeys(first(rem) for rem in ((1, 0) if rows % 2 else (2, 0))))
-
-
-assert [_heights(r) for r in (14, 9, 3, 2, 1)] == [(43, 44, 42), (37, 38, 36), (34, 35, 33), (33, 34), (33,)]
-assert [_heights_nv12(r) for r in (14, 9, 8, 7, 5, 3, 2, 1)] == [(44, 42), (46, 36), (34, 40), (36, 42), (36, 40), (34, 36), (34,), (34,)]
+    check_outputs(ctx, got, reference(oracle, ref_bgr), tag)
 
 
 def _expand(table, heights):
@@ -199,7 +157,7 @@ def align_inputs(oracle):
         else:
             planes = _planes(n, h, w, seed=h + w)
             bgr = oracle.nv12_to_bgr(*planes)
-        out[name] = (planes, oracle.preprocess_bgr(bgr), _oracle_area(oracle, bgr))
+        out[name] = (planes, oracle.preprocess_bgr(bgr), reference(oracle, bgr)[4])
     return out
 
 

@@ -10,7 +10,6 @@ AVD_FMT_RGB24 runs BGR's plan under BGR's ids (the staged kernel with NI = 3 / 4
 generic kernel with a 16-byte fill (ids 10 and 12) or a scalar fill (9 and 11) on the band plan of the width: 14 rows up to 2048 px, 7 rows
 up to 4096, then 9 at 4112; 13 rows at 3041.  AVD_FMT_RGBP also has a staged kernel (id 13) with BGR's NI classes up to NI = 8, that is up to
 2048 px; from 2064 px on it runs its 16-byte fill."""
-import ctypes
 
 import numpy as np
 import pytest
@@ -20,6 +19,10 @@ pytestmark = pytest.mark.gpu
 import avd_hip  # noqa: E402
 from avd_hip import _lib, synth  # noqa: E402
 from avd_hip import Pixels  # noqa: E402
+from tests.ingest_gpu_kit import P_KERNEL, check_outputs, check_plan, reference  # noqa: E402
+from tests.ingest_gpu_kit import heights as _heights  # noqa: E402
+from tests.ingest_gpu_kit import raw_picture_at as _raw_picture  # noqa: E402
+from tests.ingest_gpu_kit import same_records as _same_records  # noqa: E402
 
 BGR, NV12, I420, RGB24, BGRA32, RGBA32, RGBP, FULL = 0, 1, 2, 0x10, 0x11, 0x12, 0x13, 0x100
 NEW = (RGB24, BGRA32, RGBA32, RGBP)
@@ -27,11 +30,19 @@ NAMES = {BGR: "bgr24", RGB24: "rgb24", BGRA32: "bgra32", RGBA32: "rgba32", RGBP:
 # enum IngestKernel (avd_internal.h) and the layout of "ingest_plan" (include/avd.h)
 BGR_SCALAR, BGR_VEC16, BGR_STAGED = 0, 1, 2
 PX32_SCALAR, PX32_VEC16, RGBP_SCALAR, RGBP_VEC16, RGBP_STAGED = 9, 10, 11, 12, 13
-P_H, P_W, P_ROWS, P_NBANDS, P_PITCH, P_NI, P_LDS, P_KERNEL = range(8)
 SCALAR = {RGB24: BGR_SCALAR, BGRA32: PX32_SCALAR, RGBA32: PX32_SCALAR, RGBP: RGBP_SCALAR}
 VEC16 = {RGB24: BGR_VEC16, BGRA32: PX32_VEC16, RGBA32: PX32_VEC16, RGBP: RGBP_VEC16}
 # (kernel, NI) of an aligned clip up to 672 px wide
 ALIGNED = {RGB24: (BGR_STAGED, 3), BGRA32: (PX32_VEC16, 0), RGBA32: (PX32_VEC16, 0), RGBP: (RGBP_STAGED, 3)}
+
+
+def _check_plan(ctx, fmt, h, w, kernel, rows, ni=0):
+    check_plan(ctx, h, w, kernel, rows, ni, fmt=fmt, rotate=0, full_range=False)
+
+
+def _check_outputs(ctx, oracle, got, ref_bgr, tag):
+    """got = (small320, hash, lap_sum, lap_sumsq) of the call that just ran on ctx; ref_bgr = B, the frames the oracle sees."""
+    check_outputs(ctx, got, reference(oracle, ref_bgr), tag)
 
 
 def arrange(bgr, fmt, alpha=None):
@@ -45,50 +56,6 @@ def arrange(bgr, fmt, alpha=None):
     a = (np.random.default_rng(bgr.shape[1] * 31 + bgr.shape[2]).integers(0, 256, bgr.shape[:3] + (1,), dtype=np.uint8) if alpha is None
          else np.full(bgr.shape[:3] + (1,), alpha, np.uint8))
     return np.concatenate([bgr if fmt == BGRA32 else bgr[..., ::-1], a], axis=-1)
-
-
-def _check_plan(ctx, fmt, h, w, kernel, rows, ni=0):
-    p = ctx.debug_fetch("ingest_plan", (8,), np.int32)
-    tag = (NAMES[fmt], h, w, [int(v) for v in p])
-    assert ctx.ingest_format() == fmt, tag
-    assert p[P_KERNEL] == kernel, tag
-    assert p[P_ROWS] == rows, tag
-    assert (p[P_H], p[P_W]) == (h, w) and p[P_NBANDS] == -(-h // rows), tag
-    assert p[P_NI] == ni, tag
-    assert p[P_PITCH] % 16 == 0 and p[P_PITCH] >= w + 17 and p[P_LDS] >= (rows + 2) * p[P_PITCH], tag
-    assert ctx.ingest_rotate() == 0 and ctx.ingest_range() == 0, tag
-
-
-def _check_outputs(ctx, oracle, got, ref_bgr, tag):
-    """got = (small320, hash, lap_sum, lap_sumsq) of the call that just ran on ctx; ref_bgr = B, the frames the oracle sees."""
-    n = len(ref_bgr)
-    area = ctx.debug_fetch("area", (n, 32, 32), np.uint8)
-    want = oracle.preprocess_bgr(ref_bgr)
-    o_area = np.stack([oracle.resize_area(oracle.bgr2gray(f), 32, 32) for f in ref_bgr])
-    for name, a, b in zip(("lap_sum", "lap_sumsq"), got[2:], want[2:]):
-        assert np.array_equal(a, b), (tag, name, a.tolist(), b.tolist())
-    assert np.array_equal(area, o_area), (tag, "area", np.argwhere(area != o_area)[:5].tolist())
-    assert np.array_equal(got[0], want[0]), (tag, "small320", int(np.count_nonzero(got[0] != want[0])))
-    assert np.array_equal(got[1], want[1]), (tag, "hash")
-
-
-def _heights(rows):
-    """The smallest frames (above the 32-row minimum) in which a plan of `rows` rows per band has a one-row last band, a two-row last
-    band (plans of more than two rows) and a full one."""
-    first = lambda rem: next(h for h in range(33, 33 + rows) if h % rows == rem % rows)
-    return tuple(dict.fromkeys(first(rem) for rem in ((1, 2, 0) if rows > 2 else (1, 0))))
-
-
-assert [_heights(r) for r in (14, 13, 9, 7)] == [(43, 44, 42), (40, 41, 39), (37, 38, 36), (36, 37, 35)]
-
-
-def _raw_picture(ctx, fmt, planes, mem, n, h, w, rows, frames, rotate=0):
-    """avd_preprocess_picture on a descriptor written out by hand: plane addresses and strides exactly as given"""
-    p = _lib.AvdPicture()
-    p.struct_size, p.format, p.mem, p.n, p.h, p.w, p.rotate, p.reserved = ctypes.sizeof(p), fmt, mem, n, h, w, rotate, 0
-    for i, a in enumerate(planes):
-        p.plane[i], p.row_stride[i], p.frame_stride[i] = a, rows[i], frames[i]
-    return ctx._outputs_call("avd_preprocess_picture", (ctypes.byref(p),), n)
 
 
 # ---- RGB24: BGR's plan, BGR's kernels, the other coefficient constants ---------------------------------------------------------------------
@@ -371,11 +338,6 @@ def _mixed_clips():
         clips.append(c)
         twins.append(c)
     return clips, twins
-
-
-def _same_records(a, b, tag):
-    for key in ("lap_sum", "lap_sumsq", "ham", "flow_mean", "flow_var"):
-        assert np.array_equal(a[key], b[key]), (tag, key, a[key].tolist(), b[key].tolist())
 
 
 def test_mixed_batches(ctx):

@@ -18,27 +18,16 @@ pytestmark = pytest.mark.gpu
 import avd_hip  # noqa: E402
 from avd_hip import AvdError, _lib, synth  # noqa: E402
 from tests.test_gpu_i420 import VIEWS, _check_outputs, _device_view, _heights, _reference  # noqa: E402
+from tests.ingest_gpu_kit import GRAY_TABLES, check_plan  # noqa: E402
 from tests.test_nv12 import _planes  # noqa: E402
 
-P_H, P_W, P_ROWS, P_NBANDS, P_PITCH, P_NI, P_LDS, P_KERNEL = range(8)
 KERNEL_NAMES = ("bgr_scalar", "bgr_vec16", "bgr_staged", "nv12_scalar", "nv12_tables", "i420_scalar", "i420_tables", "nv12_strip", "i420_strip")
 NV12_SCALAR, NV12_TABLES, I420_SCALAR, I420_TABLES, NV12_STRIP, I420_STRIP = 3, 4, 5, 6, 7, 8
-GRAY_TABLES = 3 * 4 * 704                      # the three conversion tables behind the tile (table fills and the strip fill)
 
 
 def _check_plan(ctx, h, w, kernel, rows, rotate, lds=None):
     """h, w: the DISPLAYED picture"""
-    p = ctx.debug_fetch("ingest_plan", (8,), np.int32)
-    tag = (h, w, rotate, [int(v) for v in p])
-    assert KERNEL_NAMES[p[P_KERNEL]] == KERNEL_NAMES[kernel], tag
-    assert p[P_ROWS] == rows, tag
-    assert (p[P_H], p[P_W]) == (h, w) and p[P_NBANDS] == -(-h // rows) and p[P_NI] == 0, tag
-    assert p[P_PITCH] % 16 == 0 and p[P_PITCH] >= w + 17, tag
-    tables = 0 if kernel in (NV12_SCALAR, I420_SCALAR) else GRAY_TABLES
-    assert p[P_LDS] >= (rows + 2) * p[P_PITCH] + tables, tag
-    if lds is not None:
-        assert p[P_LDS] == lds, tag
-    assert ctx.ingest_rotate() == rotate, tag
+    check_plan(ctx, h, w, kernel, rows, 0, lds, lds_behind_tile=0 if kernel in (NV12_SCALAR, I420_SCALAR) else GRAY_TABLES, rotate=rotate)
 
 
 _displayed = {}

@@ -8,7 +8,6 @@ on those frames, and against the NV12 / I420 call on the narrowed planes.
 Every case reads "ingest_plan" (kernel id, rows per band, and the dynamic LDS bytes, which must be NV12's at that displayed geometry),
 "ingest_format", "ingest_range" and "ingest_rotate" back, so a case that silently took another fill fails.  Kernel ids: 20 p010_scalar,
 21 p010_tables, 22 i010_scalar, 23 i010_tables, 24 p010_strip, 25 i010_strip; a half turn runs under 20 .. 23."""
-import ctypes
 
 import numpy as np
 import pytest
@@ -19,6 +18,12 @@ import avd_hip  # noqa: E402
 from avd_hip import Pixels, _lib, synth  # noqa: E402
 from tests import yuv10_reference as ref  # noqa: E402
 from tests import yuv_tables_reference as ytr  # noqa: E402
+from tests.ingest_gpu_kit import P_KERNEL, P_LDS, check_plan  # noqa: E402
+from tests.ingest_gpu_kit import check_outputs as _check_outputs  # noqa: E402
+from tests.ingest_gpu_kit import plan as _plan  # noqa: E402
+from tests.ingest_gpu_kit import raw_picture as _raw_picture  # noqa: E402
+from tests.ingest_gpu_kit import reference as _reference  # noqa: E402
+from tests.ingest_gpu_kit import same_records as _same_records  # noqa: E402
 from tests.test_gpu_i420 import _device_view, _heights  # noqa: E402
 
 BGR, NV12, I420, FULL = 0, 1, 2, 0x100
@@ -30,38 +35,11 @@ TABLES = {P010: 21, I010: 23}
 STRIP = {P010: 24, I010: 25}
 PLANES = {P010: 2, I010: 3}
 NV12_SCALAR, NV12_TABLES, NV12_STRIP = 3, 4, 7
-P_H, P_W, P_ROWS, P_NBANDS, P_PITCH, P_NI, P_LDS, P_KERNEL = range(8)
-
-
-def _plan(ctx):
-    return [int(v) for v in ctx.debug_fetch("ingest_plan", (8,), np.int32)]
 
 
 def _check_plan(ctx, fmt, h, w, kernel, rows, nv12_lds, rotate=0, full_range=False):
     """h, w: the DISPLAYED picture; nv12_lds: the LDS bytes the NV12 launch of the same displayed geometry and fill shape asked for"""
-    p = _plan(ctx)
-    tag = (NAMES[fmt], h, w, rotate, p)
-    assert ctx.ingest_format() == fmt, tag
-    assert p[P_KERNEL] == kernel, tag
-    assert p[P_ROWS] == rows, tag
-    assert (p[P_H], p[P_W]) == (h, w) and p[P_NBANDS] == -(-h // rows) and p[P_NI] == 0, tag
-    assert p[P_PITCH] % 16 == 0 and p[P_PITCH] >= w + 17, tag
-    assert p[P_LDS] == nv12_lds, tag
-    assert ctx.ingest_rotate() == rotate and ctx.ingest_range() == int(full_range), tag
-
-
-def _reference(oracle, bgr):
-    """(small320, hash, lap_sum, lap_sumsq, area) of the oracle on the definition's BGR frames"""
-    area = np.stack([oracle.resize_area(oracle.bgr2gray(f), 32, 32) for f in bgr])
-    return tuple(oracle.preprocess_bgr(bgr)) + (area,)
-
-
-def _check_outputs(ctx, got, want, tag):
-    n = len(want[4])
-    area = ctx.debug_fetch("area", (n, 32, 32), np.uint8)
-    for name, a, b in zip(("lap_sum", "lap_sumsq", "area", "small320", "hash"), (got[2], got[3], area, got[0], got[1]),
-                          (want[2], want[3], want[4], want[0], want[1])):
-        assert np.array_equal(a, b), (tag, name, int(np.count_nonzero(np.asarray(a) != np.asarray(b))))
+    check_plan(ctx, h, w, kernel, rows, 0, nv12_lds, fmt=fmt, rotate=rotate, full_range=full_range)
 
 
 def _same(got, other, tag):
@@ -197,15 +175,6 @@ def test_words_above_the_samples_are_defined(ctx, oracle, w, kind, rotate):
 A_N, A_H, A_W = 2, 34, 48
 
 
-def _raw_picture(ctx, fmt, views, n, h, w, rotate=0):
-    """avd_preprocess_picture on a descriptor written out by hand from uint8 device views: plane addresses and BYTE strides exactly as they are"""
-    p = _lib.AvdPicture()
-    p.struct_size, p.format, p.mem, p.n, p.h, p.w, p.rotate, p.reserved = ctypes.sizeof(p), fmt, 1, n, h, w, rotate, 0
-    for i, t in enumerate(views):
-        p.plane[i], p.row_stride[i], p.frame_stride[i] = t.data_ptr(), t.stride(1), t.stride(0)
-    return ctx._outputs_call("avd_preprocess_picture", (ctypes.byref(p),), n)
-
-
 @pytest.fixture(scope="module")
 def align_input(oracle):
     """The samples, their oracle results and the LDS bytes of NV12's two fills at this geometry; formed once and left unchanged."""
@@ -330,11 +299,6 @@ def test_device_lists(ctx, oracle, fmt, misalign):
 
 
 # ---- 7, 8: batches, the asynchronous form -------------------------------------------------------------------------------------------------------
-def _same_records(a, b, tag):
-    for key in ("lap_sum", "lap_sumsq", "ham", "flow_mean", "flow_var"):
-        assert np.array_equal(a[key], b[key]), (tag, key, a[key].tolist(), b[key].tolist())
-
-
 def _mixed_clips():
     """P010 and I010 clips with NV12 and BGR clips and a rotated, full-range one; two geometries
     -> (clips, rotations, ranges, the BGR twin of every 10-bit clip or None)"""

@@ -9,7 +9,6 @@ Every case reads the kernel and the rows per band it was written for back from "
 that silently took the other fill fails.  Kernel ids: 14 yuyv_scalar, 15 yuyv_tables (both packed layouts), 16 i422_scalar, 17 i422_tables,
 18 nv16_scalar, 19 nv16_tables.  The band plan is the generic kernel's, keyed by the width as for 4:2:0; the heights may be odd here, and a
 band begins on any row.  One case runs the four layouts on the same samples, so the reference is formed once per geometry."""
-import ctypes
 
 import numpy as np
 import pytest
@@ -19,6 +18,11 @@ pytestmark = pytest.mark.gpu
 import avd_hip  # noqa: E402
 from avd_hip import Pixels, _lib, synth  # noqa: E402
 from tests import yuv422_reference as ref  # noqa: E402
+from tests.ingest_gpu_kit import check_plan  # noqa: E402
+from tests.ingest_gpu_kit import check_outputs as _check_outputs  # noqa: E402
+from tests.ingest_gpu_kit import raw_picture as _raw_picture  # noqa: E402
+from tests.ingest_gpu_kit import reference as _reference  # noqa: E402
+from tests.ingest_gpu_kit import same_records as _same_records  # noqa: E402
 from tests.test_gpu_i420 import _device_view  # noqa: E402
 
 BGR, NV12, I420, RGBP, FULL = 0, 1, 2, 0x13, 0x100
@@ -28,34 +32,10 @@ NAMES = ref.NAMES
 SCALAR = {YUYV: 14, UYVY: 14, I422: 16, NV16: 18}
 TABLES = {YUYV: 15, UYVY: 15, I422: 17, NV16: 19}
 PLANES = {YUYV: 1, UYVY: 1, I422: 3, NV16: 2}
-P_H, P_W, P_ROWS, P_NBANDS, P_PITCH, P_NI, P_LDS, P_KERNEL = range(8)
 
 
 def _check_plan(ctx, fmt, h, w, kernel, rows, full_range=False, lds=None):
-    p = ctx.debug_fetch("ingest_plan", (8,), np.int32)
-    tag = (NAMES[fmt], h, w, [int(v) for v in p])
-    assert ctx.ingest_format() == fmt, tag
-    assert p[P_KERNEL] == kernel, tag
-    assert p[P_ROWS] == rows, tag
-    assert (p[P_H], p[P_W]) == (h, w) and p[P_NBANDS] == -(-h // rows) and p[P_NI] == 0, tag
-    assert p[P_PITCH] % 16 == 0 and p[P_PITCH] >= w + 17 and p[P_LDS] >= (rows + 2) * p[P_PITCH], tag
-    if lds is not None:
-        assert p[P_LDS] == lds, tag
-    assert ctx.ingest_rotate() == 0 and ctx.ingest_range() == int(full_range), tag
-
-
-def _reference(oracle, bgr):
-    """(small320, hash, lap_sum, lap_sumsq, area) of the oracle on the definition's BGR frames"""
-    area = np.stack([oracle.resize_area(oracle.bgr2gray(f), 32, 32) for f in bgr])
-    return tuple(oracle.preprocess_bgr(bgr)) + (area,)
-
-
-def _check_outputs(ctx, got, want, tag):
-    n = len(want[4])
-    area = ctx.debug_fetch("area", (n, 32, 32), np.uint8)
-    for name, a, b in zip(("lap_sum", "lap_sumsq", "area", "small320", "hash"), (got[2], got[3], area, got[0], got[1]),
-                          (want[2], want[3], want[4], want[0], want[1])):
-        assert np.array_equal(a, b), (tag, name, int(np.count_nonzero(np.asarray(a) != np.asarray(b))))
+    check_plan(ctx, h, w, kernel, rows, 0, lds, fmt=fmt, rotate=0, full_range=full_range)
 
 
 def _clip(fmt, y, u, v):
@@ -112,15 +92,6 @@ def test_yv16_is_i422_with_the_chroma_pointers_exchanged(ctx, oracle):
 
 
 # ---- alignment dispatch on device views ---------------------------------------------------------------------------------------------------
-def _raw_picture(ctx, fmt, views, n, h, w, rotate=0, rows=None):
-    """avd_preprocess_picture on a descriptor written out by hand from device views: plane addresses and strides exactly as they are"""
-    p = _lib.AvdPicture()
-    p.struct_size, p.format, p.mem, p.n, p.h, p.w, p.rotate, p.reserved = ctypes.sizeof(p), fmt, 1, n, h, w, rotate, 0
-    for i, t in enumerate(views):
-        p.plane[i], p.row_stride[i], p.frame_stride[i] = t.data_ptr(), (rows[i] if rows else t.stride(1)), t.stride(0)
-    return ctx._outputs_call("avd_preprocess_picture", (ctypes.byref(p),), n)
-
-
 A_N, A_H, A_W = 2, 33, 48
 # view -> (tables?, per plane (base offset from a 16-byte boundary, row padding, odd frame stride)); planes a layout lacks are not used.
 # Every misalignment the launcher tells apart, on plane 0 (all layouts) and on the chroma planes (NV16: 16 bytes; I422: 8).
@@ -250,11 +221,6 @@ def test_device_lists(ctx, oracle, fmt, misalign):
 
 
 # ---- batches, the asynchronous form -----------------------------------------------------------------------------------------------------------
-def _same_records(a, b, tag):
-    for key in ("lap_sum", "lap_sumsq", "ham", "flow_mean", "flow_var"):
-        assert np.array_equal(a[key], b[key]), (tag, key, a[key].tolist(), b[key].tolist())
-
-
 def _mixed_clips():
     """the four layouts with NV12, I420, BGR and RGBP clips, two geometries (one of odd height), mixed ranges
     -> (clips, ranges, the BGR twin of every 4:2:2 clip or None)"""

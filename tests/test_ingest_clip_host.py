@@ -1,6 +1,6 @@
-"""The ingest host path's one clip type (csrc/avd_ingest_clip.h), without a GPU and without the library: tests/ingest_clip_check.cpp is compiled
-with the host C++ compiler and the address / undefined-behaviour sanitizers, fed one line per clip, and its answers are compared with what is
-written out here.
+"""The ingest host path's one clip type (csrc/avd_ingest_clip.h), without a GPU and without the library: tests/ingest_check.cpp (built with the
+address / undefined-behaviour sanitizers by tests/ingest_host_kit.py) is fed one line per clip through each of the three named constructors,
+from_public and from_picture, and its answers are compared with what is written out here.
 
 The refusal table (`single_faults`, `MULTI_FAULTS`, `PICTURE_FAULTS`) is the documented check order of include/avd.h: mem, the size range, even
 width and height (4:2:0), the 32 x 32 minimum, null planes of a clip that has frames, strides.  Status and text of every row are the library's
@@ -9,22 +9,15 @@ The staging plan is computed here from its rule: BGR one span; NV12 the chroma s
 I420 spans in address order, merged where they overlap or touch, a span that is not merged on the next 256-byte boundary; `copied` the sum of
 the spans' bytes, `total` the end of the last span rounded up to 256."""
 import copy
-import os
-import shutil
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BGR, NV12, I420 = 0, 1, 2
+from tests.ingest_host_kit import ARG, BGR, DEVICE, HOST, I420, NV12, OK, PLANES, T_GEOM, T_MEM, UNSUPPORTED, parse, t_size
+from tests.ingest_host_kit import T_SMALL as T_32
+from tests.ingest_host_kit import program as _lines
+
 NAMES = {BGR: "bgr", NV12: "nv12", I420: "i420"}
-PLANES = {BGR: 1, NV12: 2, I420: 3}
-HOST, DEVICE = 0, 1
-OK, ARG, UNSUPPORTED = 0, -1, -4
-T_MEM = "mem must be AVD_MEM_HOST or AVD_MEM_DEVICE"
-T_GEOM = "bad frame geometry"
 T_EVEN = {NV12: "NV12 needs even width and height", I420: "I420 needs even width and height"}
-T_32 = "frame smaller than 32x32: INTER_AREA upscaling is not on the path"
 T_NULL = {BGR: "null frame pointer", NV12: "null plane pointer", I420: "null I420 plane pointer"}
 T_STRIDES = {BGR: "strides smaller than the frame", NV12: "strides smaller than the planes", I420: "strides smaller than the I420 planes"}
 ADDR = (0x10000000, 0x20000000, 0x30000000)            # stand-ins for plane pointers: the header never reads through them
@@ -93,8 +86,8 @@ MULTI_FAULTS = [
 
 # What the descriptor alone gets wrong (from_picture), before any of the above is looked at.
 PICTURE_FAULTS = [
-    ("struct-size-minus-8", NV12, _set(size_delta=-8), (ARG, "avd_picture.struct_size is not sizeof(avd_picture)")),
-    ("struct-size-plus-8", I420, _set(size_delta=8), (ARG, "avd_picture.struct_size is not sizeof(avd_picture)")),
+    ("struct-size-minus-8", NV12, _set(size_delta=-8), (ARG, t_size("picture"))),
+    ("struct-size-plus-8", I420, _set(size_delta=8), (ARG, t_size("picture"))),
     ("format-3", NV12, _set(fmt=3), (ARG, "bad avd_picture.format")),
     ("rotate-minus-1", NV12, _set(rotate=-1), (ARG, "avd_picture.rotate must be 0 .. 3 quarter turns")),
     ("rotate-4", I420, _set(rotate=4), (ARG, "avd_picture.rotate must be 0 .. 3 quarter turns")),
@@ -118,28 +111,21 @@ def edited(fmt, edit):
 
 # ---- the program ---------------------------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
-def program(tmp_path_factory):
-    cxx = os.environ.get("CXX") or shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
-    assert cxx, "no host C++ compiler"
-    exe = str(tmp_path_factory.mktemp("ingest_clip") / "ingest_clip_check")
-    subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                    "-o", exe, os.path.join(ROOT, "tests", "ingest_clip_check.cpp")], check=True)
-
+def program(_lines):
     def run(cases):
-        """cases: [(via, clip dict)] -> [dict(status, why, format, nspans, off, bytes, plane_off, total, copied)]"""
+        """cases: [(via, clip dict)] -> [dict(status, why, format, nspans, off, bytes, plane_off, total, copied)], the lists padded to three entries"""
         lines = []
         for via, c in cases:
-            lines.append(" ".join(str(v) for v in [via, c["fmt"], c["mem"], c["n"], c["h"], c["w"], c["rotate"], *c["planes"], *c["rows"], *c["frames"],
-                                                   c["size_delta"], c["reserved"]]))
-        r = subprocess.run([exe], input="\n".join(lines) + "\n", capture_output=True, text=True)
-        assert r.returncode == 0 and not r.stderr, (r.returncode, r.stderr)       # a sanitizer report ends the program with a non-zero status
-        out = []
-        for line in r.stdout.splitlines():
-            status, why, fmt, nspans, off, nbytes, plane_off, total, copied = line.split("|")
-            ints = lambda s: [int(v) for v in s.split(",")]
-            out.append(dict(status=int(status), why=why, format=int(fmt), nspans=int(nspans), off=ints(off), bytes=ints(nbytes),
-                            plane_off=ints(plane_off), total=int(total), copied=int(copied)))
-        assert len(out) == len(cases)
+            if via == "direct":
+                lines.append(["D", c["fmt"], c["mem"], c["n"], c["h"], c["w"], *c["planes"], *c["rows"][:2], *c["frames"][:2]])
+            elif via == "public":
+                lines.append(["C", c["mem"], c["n"], c["h"], c["w"], *c["planes"][:2], *c["rows"][:2], *c["frames"][:2]])
+            else:
+                lines.append(["P", c["fmt"], c["mem"], c["n"], c["h"], c["w"], c["rotate"], c["reserved"], c["size_delta"], *c["planes"], *c["rows"], *c["frames"]])
+        out = [parse(g) for g in _lines([" ".join(str(v) for v in l) for l in lines])]
+        for g in out:
+            for key in ("off", "bytes", "plane_off"):
+                g[key] = (g[key] + [0, 0, 0])[:3]
         return out
     return run
 

@@ -2,44 +2,25 @@
 header and binding; the refusals of from_picture / from_frame_list / check_clip in their documented order; the staging plan of host clips
 (a dense [N,3,H,W] stack is ONE span, separately allocated planes three, a 32-bit clip one span of 4w-byte rows, a frame listed twice crosses
 once); the vector-fill eligibility of lists; and the descriptors the binding builds from Pixels and per-frame arrays.  The host logic runs in a
-stand-alone program (tests/rgb_clip_check.cpp, built with the address and undefined-behaviour sanitizers)."""
+stand-alone program (tests/ingest_check.cpp, built with the address and undefined-behaviour sanitizers by tests/ingest_host_kit.py, which also
+holds the case writers, the answer reader and the texts every layout shares)."""
 import ctypes
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 import avd_hip
 from avd_hip import _lib
+from tests.ingest_host_kit import (ARG, BASE, BGR, DEVICE, FULL, HOST, I420, NV12, OK, PLANES, PX, ROOT, T_GEOM, T_MEM, T_SMALL, UNSUPPORTED,  # noqa: F401
+                                   binding, frame_list, list_addrs, parse, picture, program, t_format, t_reserved, t_rotate)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BGR, NV12, I420, RGB24, BGRA32, RGBA32, RGBP, FULL = 0, 1, 2, 0x10, 0x11, 0x12, 0x13, 0x100
-NEW = (RGB24, BGRA32, RGBA32, RGBP)
-PX = {RGB24: 3, BGRA32: 4, RGBA32: 4, RGBP: 1}
-PLANES = {RGB24: 1, BGRA32: 1, RGBA32: 1, RGBP: 3}
-OK, ARG, UNSUPPORTED = 0, -1, -4
-HOST, DEVICE = 0, 1
+RGB24, BGRA32, RGBA32, RGBP = NEW = (0x10, 0x11, 0x12, 0x13)
 T_RANGE = "AVD_FMT_FULL_RANGE describes 4:2:0 samples: an RGB picture has no range"
 T_TURNED = "a turned RGB picture is not on the path: producers of RGB hand it over already rotated"
 T_SHARE = "the R, G and B planes of an RGBP picture share their strides"
-T_MEM = "mem must be AVD_MEM_HOST or AVD_MEM_DEVICE"
-T_GEOM = "bad frame geometry"
-T_SMALL = "frame smaller than 32x32: INTER_AREA upscaling is not on the path"
-
-
-def t_format(kind):
-    return "bad avd_%s.format" % kind
-
-
-def t_rotate(kind):
-    return "avd_%s.rotate must be 0 .. 3 quarter turns" % kind
-
-
-def t_reserved(kind):
-    return "avd_%s.reserved must be 0" % kind
+parse_p = parse_l = parse
 
 
 def t_null(fmt, kind):
@@ -52,64 +33,6 @@ def t_strides(fmt):
     return "strides smaller than the RGBP planes" if fmt == RGBP else "strides smaller than the frame"
 
 
-@pytest.fixture(scope="module")
-def program(tmp_path_factory):
-    cxx = os.environ.get("CXX") or shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
-    assert cxx, "no host C++ compiler"
-    exe = str(tmp_path_factory.mktemp("rgb_clip") / "rgb_clip_check")
-    subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                    "-o", exe, os.path.join(ROOT, "tests", "rgb_clip_check.cpp")], check=True)
-
-    def run(lines):
-        r = subprocess.run([exe], input="".join(l + "\n" for l in lines), capture_output=True, text=True)
-        assert r.returncode == 0 and not r.stderr, (r.returncode, r.stderr)       # a sanitizer report ends the program with a non-zero status
-        out = r.stdout.splitlines()
-        assert len(out) == len(lines)
-        return out
-    return run
-
-
-def ints(s):
-    return [int(v) for v in s.split(",")] if s else []
-
-
-# ---- a picture / a list through the program ------------------------------------------------------------------------------------------------
-BASE = (0x10000000, 0x20000000, 0x30000000)
-
-
-def picture(fmt, mem=HOST, n=2, h=48, w=64, rotate=0, reserved=0, planes=BASE, rs=None, fs=None):
-    """-> the P line of a valid picture of layout fmt (low byte), with whatever the keywords change"""
-    px = PX.get(fmt & 0xFF, 1)
-    rs = [w * px] * 3 if rs is None else list(rs)
-    fs = [rs[0] * h] * 3 if fs is None else list(fs)
-    return "P %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d" % (fmt, mem, n, h, w, rotate, reserved, *planes, *rs, *fs)
-
-
-def parse_p(line):
-    status, why, fmt, planes, px, nspans, off, nbytes, poff, total, copied = line.split("|")
-    return dict(status=int(status), why=why, format=int(fmt), planes=int(planes), px=int(px), nspans=int(nspans), off=ints(off), bytes=ints(nbytes),
-                plane_off=ints(poff), total=int(total), copied=int(copied))
-
-
-def frame_list(fmt, addrs, mem=HOST, h=48, w=64, rotate=0, reserved=0, rs=None, null_arrays=0):
-    """addrs: [plane][frame] addresses (missing planes: zeros) -> the L line"""
-    px = PX.get(fmt & 0xFF, 1)
-    n = len(addrs[0])
-    rs = [w * px] * 3 if rs is None else list(rs)
-    full = [list(addrs[p]) if p < len(addrs) else [0] * n for p in range(3)]
-    return "L %d %d %d %d %d %d %d %d %d %d %d %s" % (fmt, mem, n, h, w, rotate, reserved, *rs, null_arrays, " ".join(str(a) for pl in full for a in pl))
-
-
-def parse_l(line):
-    status, why, fmt, planes, px, nspans, off, nbytes, poff, total, copied, given, staged = line.split("|")
-    return dict(status=int(status), why=why, format=int(fmt), planes=int(planes), px=int(px), nspans=int(nspans), off=ints(off), bytes=ints(nbytes),
-                plane_off=ints(poff), total=int(total), copied=int(copied), given=int(given), staged=int(staged))
-
-
-def list_addrs(fmt, n=2, step=0x100000):
-    return [[BASE[p] + f * step for f in range(n)] for p in range(PLANES[fmt])]
-
-
 # ---- the values -----------------------------------------------------------------------------------------------------------------------------
 def test_header_library_and_binding_agree_on_the_four_values(program):
     hdr = open(os.path.join(ROOT, "include", "avd.h")).read()
@@ -119,28 +42,12 @@ def test_header_library_and_binding_agree_on_the_four_values(program):
         assert getattr(_lib, name) == value == getattr(avd_hip, name)
     # the enum of the first three layouts stays as it was
     assert "enum avd_format { AVD_FMT_BGR24 = 0, AVD_FMT_NV12 = 1, AVD_FMT_I420 = 2 };" in hdr
-    picture_size, list_size, values = program(["A"])[0].split("|")
-    assert int(picture_size) == ctypes.sizeof(_lib.AvdPicture) == 104
-    assert int(list_size) == ctypes.sizeof(_lib.AvdFrameList) == 80
-    assert tuple(ints(values)) == NEW
+    a = parse(program(["A"])[0])
+    assert a["picture_size"] == ctypes.sizeof(_lib.AvdPicture) == 104
+    assert a["list_size"] == ctypes.sizeof(_lib.AvdFrameList) == 80
+    assert tuple(a[name] for name in names) == NEW
     for text in ("ARGB and ABGR", "gbrp", '"ingest_format" int32[1]', "9 px32_scalar, 10 px32_vec16, 11 rgbp_scalar, 12 rgbp_vec16, 13 rgbp_staged"):
         assert text in hdr, text
-
-
-def test_the_exported_symbol_set_is_unchanged():
-    """the feature adds layouts, not functions: what the headers declare is what the binding lists, and the library exports exactly that"""
-    hdr = open(os.path.join(ROOT, "include", "avd.h")).read()
-    own = open(os.path.join(ROOT, "include", "avd_frame_list.h")).read()
-    assert set(re.findall(r"^\s*(?:int|void|int64_t|const char\*)\s+(avd_\w+)\s*\(", hdr, re.M)) == set(_lib.EXPORTS)
-    assert set(re.findall(r"^int (avd_\w+)\(", own, re.M)) == set(_lib.LIST_EXPORTS)
-    assert len(_lib.EXPORTS) == 43 and len(_lib.LIST_EXPORTS) == 3
-    nm = shutil.which("nm")
-    assert nm, "no nm"
-    so = _lib.build()
-    out = subprocess.run([nm, "-D", "--defined-only", so], check=True, capture_output=True, text=True).stdout
-    exported = {line.split()[-1] for line in out.splitlines() if re.search(r" T avd_\w+$", line)}
-    assert exported == set(_lib.EXPORTS) | set(_lib.LIST_EXPORTS), exported ^ (set(_lib.EXPORTS) | set(_lib.LIST_EXPORTS))
-    assert callable(_lib.Context.ingest_format)
 
 
 # ---- refusals -------------------------------------------------------------------------------------------------------------------------------
@@ -338,11 +245,6 @@ def test_list_vec_eligible(program, fmt):
 
 
 # ---- the binding's descriptors ----------------------------------------------------------------------------------------------------------------
-@pytest.fixture()
-def binding():
-    return object.__new__(_lib.Context)                       # no context, no device: what is checked is the binding's own
-
-
 def test_pixels_is_exported_and_tagged():
     assert avd_hip.Pixels is _lib.Pixels
     a = np.zeros((1, 32, 32, 3), np.uint8)

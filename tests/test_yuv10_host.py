@@ -2,12 +2,11 @@
 binding; the definition (tests/yuv10_reference.py) over all 65536 words and tied to the pinned 8-bit converter; the refusals of from_picture /
 from_frame_list / check_clip in their documented order, the 2-byte alignment check last; the staging plan of host clips; the table-fill
 eligibility of lists; the descriptors the binding builds and the dtypes it refuses.  The host logic runs in a stand-alone program
-(tests/yuv10_clip_check.cpp, built with the address and undefined-behaviour sanitizers)."""
+(tests/ingest_check.cpp, built with the address and undefined-behaviour sanitizers by tests/ingest_host_kit.py, which also
+holds the case writers, the answer reader and the texts every layout shares)."""
 import ctypes
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
@@ -16,97 +15,16 @@ import avd_hip
 from avd_hip import _lib
 from tests import yuv10_reference as ref
 from tests import yuv_tables_reference as ytr
+from tests.ingest_host_kit import (ARG, BASE, DEVICE, FULL, HOST, I420, NV12, OK, PLANES, ROOT, T_GEOM, T_MEM, T_ODD, T_SMALL, UNSUPPORTED,  # noqa: F401
+                                   binding, frame_list, list_addrs, parse, picture, program, r256, row_bytes, t_format, t_reserved, t_rotate)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BGR, NV12, I420, FULL = 0, 1, 2, 0x100
 P010, I010 = ref.LAYOUTS
 NEW = ref.LAYOUTS
-PLANES = {P010: 2, I010: 3}
-OK, ARG, UNSUPPORTED = 0, -1, -4
-HOST, DEVICE = 0, 1
 T_SHARE = "the U and V planes of an I010 picture share their strides"
-T_MEM = "mem must be AVD_MEM_HOST or AVD_MEM_DEVICE"
-T_GEOM = "bad frame geometry"
-T_SMALL = "frame smaller than 32x32: INTER_AREA upscaling is not on the path"
 T_EVEN = {P010: "P010 needs even width and height", I010: "I010 needs even width and height"}
 T_NULL = {P010: "null P010 plane pointer", I010: "null I010 plane pointer"}
 T_STRIDES = {P010: "strides smaller than the P010 planes", I010: "strides smaller than the I010 planes"}
-T_ODD = "16-bit samples need 2-byte aligned planes and strides"
-
-
-def t_format(kind):
-    return "bad avd_%s.format" % kind
-
-
-def t_rotate(kind):
-    return "avd_%s.rotate must be 0 .. 3 quarter turns" % kind
-
-
-def t_reserved(kind):
-    return "avd_%s.reserved must be 0" % kind
-
-
-@pytest.fixture(scope="module")
-def program(tmp_path_factory):
-    cxx = os.environ.get("CXX") or shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
-    assert cxx, "no host C++ compiler"
-    exe = str(tmp_path_factory.mktemp("yuv10_clip") / "yuv10_clip_check")
-    subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                    "-o", exe, os.path.join(ROOT, "tests", "yuv10_clip_check.cpp")], check=True)
-
-    def run(lines):
-        r = subprocess.run([exe], input="".join(l + "\n" for l in lines), capture_output=True, text=True)
-        assert r.returncode == 0 and not r.stderr, (r.returncode, r.stderr)       # a sanitizer report ends the program with a non-zero status
-        out = r.stdout.splitlines()
-        assert len(out) == len(lines)
-        return out
-    return run
-
-
-def ints(s):
-    return [int(v) for v in s.split(",")] if s else []
-
-
-# ---- a picture / a list through the program ------------------------------------------------------------------------------------------------
-BASE = (0x10000000, 0x20000000, 0x30000000)
-
-
-def row_bytes(fmt, w):
-    """bytes of a row of planes 0, 1, 2 (the interface table of include/avd.h)"""
-    c = w if fmt & 0xFF == I010 else 2 * w
-    return [2 * w, c, c]
-
-
-def picture(fmt, mem=HOST, n=2, h=48, w=64, rotate=0, reserved=0, planes=BASE, rs=None, fs=None):
-    """-> the P line of a valid picture of layout fmt (low byte), with whatever the keywords change"""
-    rs = row_bytes(fmt, w) if rs is None else list(rs)
-    fs = [rs[0] * h, rs[1] * (h // 2), rs[2] * (h // 2)] if fs is None else list(fs)
-    return "P %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d" % (fmt, mem, n, h, w, rotate, reserved, *planes, *rs, *fs)
-
-
-def parse_p(line):
-    status, why, fmt, planes, px, nspans, off, nbytes, poff, total, copied, sub_rows, sub_row, full = line.split("|")
-    return dict(status=int(status), why=why, format=int(fmt), planes=int(planes), px=int(px), nspans=int(nspans), off=ints(off), bytes=ints(nbytes),
-                plane_off=ints(poff), total=int(total), copied=int(copied), sub_rows=int(sub_rows), sub_row=int(sub_row), full=int(full))
-
-
-def frame_list(fmt, addrs, mem=HOST, h=48, w=64, rotate=0, reserved=0, rs=None, null_arrays=0):
-    """addrs: [plane][frame] addresses (missing planes: zeros) -> the L line"""
-    n = len(addrs[0])
-    rs = row_bytes(fmt, w) if rs is None else list(rs)
-    full = [list(addrs[p]) if p < len(addrs) else [0] * n for p in range(3)]
-    return "L %d %d %d %d %d %d %d %d %d %d %d %s" % (fmt, mem, n, h, w, rotate, reserved, *rs, null_arrays, " ".join(str(a) for pl in full for a in pl))
-
-
-def parse_l(line):
-    status, why, fmt, planes, px, nspans, off, nbytes, poff, total, copied, given, staged, sub_rows, sub_row, full = line.split("|")
-    return dict(status=int(status), why=why, format=int(fmt), planes=int(planes), px=int(px), nspans=int(nspans), off=ints(off), bytes=ints(nbytes),
-                plane_off=ints(poff), total=int(total), copied=int(copied), given=int(given), staged=int(staged), sub_rows=int(sub_rows),
-                sub_row=int(sub_row), full=int(full))
-
-
-def list_addrs(fmt, n=2, step=0x100000):
-    return [[BASE[p] + f * step for f in range(n)] for p in range(PLANES[fmt])]
+parse_p = parse_l = parse
 
 
 # ---- the values -----------------------------------------------------------------------------------------------------------------------------
@@ -115,34 +33,17 @@ def test_header_library_and_binding_agree_on_the_two_values(program):
     for name, value in zip(("AVD_FMT_P010", "AVD_FMT_I010"), (0x30, 0x31)):
         assert int(re.search(r"^#define %s\s+(0x[0-9a-fA-F]+)\s*$" % name, hdr, re.M).group(1), 16) == value
         assert getattr(_lib, name) == value == getattr(avd_hip, name)
-        assert _lib._FMT_PLANES[value] == PLANES[value] and value in _lib._YUV_PLANES
-    picture_size, list_size, values = program(["A"])[0].split("|")
-    assert int(picture_size) == ctypes.sizeof(_lib.AvdPicture) == 104
-    assert int(list_size) == ctypes.sizeof(_lib.AvdFrameList) == 80
-    assert tuple(ints(values)) == NEW == (0x30, 0x31)
+        assert _lib.LAYOUT[value].planes == PLANES[value] and _lib.LAYOUT[value].handed == "planes"
+    a = parse(program(["A"])[0])
+    assert a["picture_size"] == ctypes.sizeof(_lib.AvdPicture) == 104
+    assert a["list_size"] == ctypes.sizeof(_lib.AvdFrameList) == 80
+    assert (a["AVD_FMT_P010"], a["AVD_FMT_I010"]) == NEW == (0x30, 0x31)
     assert re.search(r"^#define AVD_ABI_VERSION 3\b", hdr, re.M)
     for text in ("20 p010_scalar, 21 p010_tables, 22 i010_scalar", "23 i010_tables, 24 p010_strip, 25 i010_strip", "UNPINNED", "yuv420p10le",
                  "min(255, (s + 128) >> 8)", "min(255, (s + 2) >> 2)", "index the table at 256", "0x24 .. 0x2F and 0x32 .. 0xFF stay AVD_ERR_ARG",
                  "4:4:4 and 10-bit 4:2:2", T_ODD[:40]):
         assert text in hdr, text
     assert _lib._FMT_NAMES.endswith("AVD_FMT_P010 or AVD_FMT_I010")
-
-
-def test_the_exported_symbol_set_is_unchanged():
-    """two layouts, no function: what the headers declare is what the binding lists, and the library exports exactly that"""
-    hdr = open(os.path.join(ROOT, "include", "avd.h")).read()
-    own = open(os.path.join(ROOT, "include", "avd_frame_list.h")).read()
-    assert set(re.findall(r"^\s*(?:int|void|int64_t|const char\*)\s+(avd_\w+)\s*\(", hdr, re.M)) == set(_lib.EXPORTS)
-    assert set(re.findall(r"^int (avd_\w+)\(", own, re.M)) == set(_lib.LIST_EXPORTS)
-    assert len(_lib.EXPORTS) == 43 and len(_lib.LIST_EXPORTS) == 3
-    nm = shutil.which("nm")
-    assert nm, "no nm"
-    so = _lib.build()
-    out = subprocess.run([nm, "-D", "--defined-only", so], check=True, capture_output=True, text=True).stdout
-    exported = {line.split()[-1] for line in out.splitlines() if re.search(r" T avd_\w+$", line)}
-    assert exported == set(_lib.EXPORTS) | set(_lib.LIST_EXPORTS), exported ^ (set(_lib.EXPORTS) | set(_lib.LIST_EXPORTS))
-    assert _lib.load().avd_abi_version() == 3
-    assert callable(avd_hip.FrameAnalyzer.records_stream_p010) and callable(avd_hip.FrameAnalyzer.records_stream_i010)
 
 
 # ---- the definition -------------------------------------------------------------------------------------------------------------------------
@@ -349,9 +250,6 @@ def test_neighbouring_layout_values_stay_refused(program):
 
 
 # ---- staging --------------------------------------------------------------------------------------------------------------------------------
-r256 = lambda v: (v + 255) // 256 * 256
-
-
 def test_p010_is_two_spans(program):
     n, h, w = 2, 34, 48
     ys, cs = n * h * w * 2, n * (h // 2) * w * 2
@@ -427,11 +325,6 @@ def test_list_vec_eligible(program, fmt):
 
 
 # ---- the binding's descriptors ----------------------------------------------------------------------------------------------------------------
-@pytest.fixture()
-def binding():
-    return object.__new__(_lib.Context)                       # no context, no device: what is checked is the binding's own
-
-
 def _clips(n, h, w, seed):
     y, u, v = ref.random_planes10(n, h, w, seed)
     return {fmt: ref.pack(fmt, y, u, v) for fmt in NEW}

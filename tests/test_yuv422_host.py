@@ -2,12 +2,11 @@
 binding; the definition (tests/yuv422_reference.py) tied to the pinned 4:2:0 converters through the row-doubling and the chroma-row-pairs
 identities; the refusals of from_picture / from_frame_list / check_clip in their documented order; the staging plan of host clips; the
 table-fill eligibility of lists; the descriptors the binding builds; a C422 .y4m written and read back.  The host logic runs in a stand-alone
-program (tests/yuv422_clip_check.cpp, built with the address and undefined-behaviour sanitizers)."""
+program (tests/ingest_check.cpp, built with the address and undefined-behaviour sanitizers by tests/ingest_host_kit.py, which also
+holds the case writers, the answer reader and the texts every layout shares)."""
 import ctypes
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
@@ -16,99 +15,18 @@ import avd_hip
 from avd_hip import _lib, sources
 from tests import yuv422_reference as ref
 from tests import yuv_tables_reference as ytr
+from tests.ingest_host_kit import (ARG, BASE, BGR, DEVICE, FULL, HOST, I420, NV12, OK, PLANES, PX, ROOT, T_GEOM, T_MEM, T_SMALL, UNSUPPORTED,  # noqa: F401
+                                   binding, frame_list, list_addrs, parse, picture, program, r256, row_bytes, t_format, t_reserved, t_rotate)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BGR, NV12, I420, FULL = 0, 1, 2, 0x100
 YUYV, UYVY, I422, NV16 = ref.LAYOUTS
 NEW = ref.LAYOUTS
-PX = {YUYV: 2, UYVY: 2, I422: 1, NV16: 1}
-PLANES = {YUYV: 1, UYVY: 1, I422: 3, NV16: 2}
-OK, ARG, UNSUPPORTED = 0, -1, -4
-HOST, DEVICE = 0, 1
 T_TURNED = "a turned 4:2:2 picture is not on the path: the conversion does not commute with quarter turns"
 T_SHARE = "the U and V planes of an I422 picture share their strides"
-T_MEM = "mem must be AVD_MEM_HOST or AVD_MEM_DEVICE"
-T_GEOM = "bad frame geometry"
-T_SMALL = "frame smaller than 32x32: INTER_AREA upscaling is not on the path"
 T_EVEN = {YUYV: "YUYV422 needs even width", UYVY: "UYVY422 needs even width", I422: "I422 needs even width", NV16: "NV16 needs even width"}
 T_NULL = {YUYV: "null frame pointer", UYVY: "null frame pointer", I422: "null I422 plane pointer", NV16: "null NV16 plane pointer"}
 T_STRIDES = {YUYV: "strides smaller than the frame", UYVY: "strides smaller than the frame", I422: "strides smaller than the I422 planes",
              NV16: "strides smaller than the NV16 planes"}
-
-
-def t_format(kind):
-    return "bad avd_%s.format" % kind
-
-
-def t_rotate(kind):
-    return "avd_%s.rotate must be 0 .. 3 quarter turns" % kind
-
-
-def t_reserved(kind):
-    return "avd_%s.reserved must be 0" % kind
-
-
-@pytest.fixture(scope="module")
-def program(tmp_path_factory):
-    cxx = os.environ.get("CXX") or shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
-    assert cxx, "no host C++ compiler"
-    exe = str(tmp_path_factory.mktemp("yuv422_clip") / "yuv422_clip_check")
-    subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                    "-o", exe, os.path.join(ROOT, "tests", "yuv422_clip_check.cpp")], check=True)
-
-    def run(lines):
-        r = subprocess.run([exe], input="".join(l + "\n" for l in lines), capture_output=True, text=True)
-        assert r.returncode == 0 and not r.stderr, (r.returncode, r.stderr)       # a sanitizer report ends the program with a non-zero status
-        out = r.stdout.splitlines()
-        assert len(out) == len(lines)
-        return out
-    return run
-
-
-def ints(s):
-    return [int(v) for v in s.split(",")] if s else []
-
-
-# ---- a picture / a list through the program ------------------------------------------------------------------------------------------------
-BASE = (0x10000000, 0x20000000, 0x30000000)
-
-
-def row_bytes(fmt, w):
-    """bytes of a row of planes 0, 1, 2 (the interface table of include/avd.h)"""
-    lay = fmt & 0xFF
-    return [w * PX.get(lay, 1), w // 2 if lay == I422 else w, w // 2 if lay == I422 else w]
-
-
-def picture(fmt, mem=HOST, n=2, h=48, w=64, rotate=0, reserved=0, planes=BASE, rs=None, fs=None):
-    """-> the P line of a valid picture of layout fmt (low byte), with whatever the keywords change"""
-    rs = row_bytes(fmt, w) if rs is None else list(rs)
-    fs = [r * h for r in rs] if fs is None else list(fs)
-    return "P %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d" % (fmt, mem, n, h, w, rotate, reserved, *planes, *rs, *fs)
-
-
-def parse_p(line):
-    status, why, fmt, planes, px, nspans, off, nbytes, poff, total, copied, sub_rows, sub_row, full = line.split("|")
-    return dict(status=int(status), why=why, format=int(fmt), planes=int(planes), px=int(px), nspans=int(nspans), off=ints(off), bytes=ints(nbytes),
-                plane_off=ints(poff), total=int(total), copied=int(copied), sub_rows=int(sub_rows), sub_row=int(sub_row), full=int(full))
-
-
-def frame_list(fmt, addrs, mem=HOST, h=48, w=64, rotate=0, reserved=0, rs=None, null_arrays=0):
-    """addrs: [plane][frame] addresses (missing planes: zeros) -> the L line"""
-    n = len(addrs[0])
-    rs = row_bytes(fmt, w) if rs is None else list(rs)
-    full = [list(addrs[p]) if p < len(addrs) else [0] * n for p in range(3)]
-    return "L %d %d %d %d %d %d %d %d %d %d %d %s" % (fmt, mem, n, h, w, rotate, reserved, *rs, null_arrays, " ".join(str(a) for pl in full for a in pl))
-
-
-def parse_l(line):
-    status, why, fmt, planes, px, nspans, off, nbytes, poff, total, copied, given, staged, sub_rows, sub_row, full = line.split("|")
-    return dict(status=int(status), why=why, format=int(fmt), planes=int(planes), px=int(px), nspans=int(nspans), off=ints(off), bytes=ints(nbytes),
-                plane_off=ints(poff), total=int(total), copied=int(copied), given=int(given), staged=int(staged), sub_rows=int(sub_rows),
-                sub_row=int(sub_row), full=int(full))
-
-
-def list_addrs(fmt, n=2, step=0x100000):
-    return [[BASE[p] + f * step for f in range(n)] for p in range(PLANES[fmt])]
+parse_p = parse_l = parse
 
 
 # ---- the values -----------------------------------------------------------------------------------------------------------------------------
@@ -118,33 +36,16 @@ def test_header_library_and_binding_agree_on_the_four_values(program):
     for name, value in zip(names, (0x20, 0x21, 0x22, 0x23)):
         assert int(re.search(r"^#define %s\s+(0x[0-9a-fA-F]+)\s*$" % name, hdr, re.M).group(1), 16) == value
         assert getattr(_lib, name) == value == getattr(avd_hip, name)
-        assert _lib._FMT_PLANES[value] == PLANES[value]
-    picture_size, list_size, values = program(["A"])[0].split("|")
-    assert int(picture_size) == ctypes.sizeof(_lib.AvdPicture) == 104
-    assert int(list_size) == ctypes.sizeof(_lib.AvdFrameList) == 80
-    assert tuple(ints(values)) == NEW == (0x20, 0x21, 0x22, 0x23)
+        assert _lib.LAYOUT[value].planes == PLANES[value]
+    a = parse(program(["A"])[0])
+    assert a["picture_size"] == ctypes.sizeof(_lib.AvdPicture) == 104
+    assert a["list_size"] == ctypes.sizeof(_lib.AvdFrameList) == 80
+    assert tuple(a[name] for name in names) == NEW == (0x20, 0x21, 0x22, 0x23)
     for text in ("14 yuyv_scalar, 15 yuyv_tables, 16 i422_scalar, 17 i422_tables, 18 nv16_scalar, 19 nv16_tables", "UNPINNED", "YV16",
                  "FFmpeg up to 7.0", "could not be determined", "4:4:4 and 10-bit"):
         assert text in hdr, text
     own = open(os.path.join(ROOT, "include", "avd_frame_list.h")).read()
     assert "AVD_FMT_I422: Y, U, V; AVD_FMT_NV16: Y, interleaved UV" in own
-
-
-def test_the_exported_symbol_set_is_unchanged():
-    """four layouts, no function: what the headers declare is what the binding lists, and the library exports exactly that"""
-    hdr = open(os.path.join(ROOT, "include", "avd.h")).read()
-    own = open(os.path.join(ROOT, "include", "avd_frame_list.h")).read()
-    assert set(re.findall(r"^\s*(?:int|void|int64_t|const char\*)\s+(avd_\w+)\s*\(", hdr, re.M)) == set(_lib.EXPORTS)
-    assert set(re.findall(r"^int (avd_\w+)\(", own, re.M)) == set(_lib.LIST_EXPORTS)
-    assert len(_lib.EXPORTS) == 43 and len(_lib.LIST_EXPORTS) == 3
-    nm = shutil.which("nm")
-    assert nm, "no nm"
-    so = _lib.build()
-    out = subprocess.run([nm, "-D", "--defined-only", so], check=True, capture_output=True, text=True).stdout
-    exported = {line.split()[-1] for line in out.splitlines() if re.search(r" T avd_\w+$", line)}
-    assert exported == set(_lib.EXPORTS) | set(_lib.LIST_EXPORTS), exported ^ (set(_lib.EXPORTS) | set(_lib.LIST_EXPORTS))
-    assert _lib.load().avd_abi_version() == 3
-    assert callable(avd_hip.FrameAnalyzer.records_stream_i422)
 
 
 # ---- the definition -------------------------------------------------------------------------------------------------------------------------
@@ -347,7 +248,6 @@ def test_a_dense_i422_frame_stack_is_one_span(program):
 def test_separate_i422_planes_are_three_spans_and_nv16_two(program):
     n, h, w = 2, 33, 34
     ys, cs = n * h * w, n * h * (w // 2)
-    r256 = lambda v: (v + 255) // 256 * 256
     p = parse_p(program([picture(I422, n=n, h=h, w=w)])[0])
     assert (p["status"], p["nspans"], p["bytes"]) == (OK, 3, [ys, cs, cs])
     assert p["off"] == [0, r256(ys), r256(ys) + r256(cs)] == p["plane_off"] and p["copied"] == ys + 2 * cs
@@ -400,11 +300,6 @@ def test_list_vec_eligible(program, fmt):
 
 
 # ---- the binding's descriptors ----------------------------------------------------------------------------------------------------------------
-@pytest.fixture()
-def binding():
-    return object.__new__(_lib.Context)                       # no context, no device: what is checked is the binding's own
-
-
 def test_pixels_takes_the_four_layouts():
     y, u, v = ref.random_planes(2, 33, 48, 5)
     for fmt in NEW:
