@@ -93,9 +93,9 @@ static int build_geom(avd_ctx* ctx, Geom& g, int h, int w)
     return 0;
 }
 
-// Make (h, w) the current geometry: ws.pre / ws.hsh are copies of its cache entry.  A hit costs nothing; a miss builds the
+// The geometry (h, w) for one clip: slot.pre / slot.hsh become copies of its cache entry.  A hit costs nothing; a miss builds the
 // tables in a free entry, or in the least recently used one.
-int avd_ws_geometry(avd_ctx* ctx, int h, int w)
+static int avd_ws_geometry(avd_ctx* ctx, int h, int w, ClipSlot& slot)
 {
     Workspace& ws = ctx->ws;
     Geom* hit = nullptr;
@@ -109,13 +109,13 @@ int avd_ws_geometry(avd_ctx* ctx, int h, int w)
         hit = victim;
     }
     hit->stamp = ++ws.geom_clock;
-    ws.pre = hit->pre; ws.hsh = hit->hsh;
+    slot.pre = hit->pre; slot.hsh = hit->hsh;
     return 0;
 }
 
 // Per-frame buffers for n frames (all clips of a call), `rowbuf_elems` floats of INTER_AREA row partials and `lappart_elems`
 // long longs of Laplacian partial moments.  Grow-only: in steady state nothing is allocated or freed.
-int avd_ws_reserve_frames(avd_ctx* ctx, int n, size_t rowbuf_elems, size_t lappart_elems)
+static int avd_ws_reserve_frames(avd_ctx* ctx, int n, size_t rowbuf_elems, size_t lappart_elems)
 {
     Workspace& ws = ctx->ws;
     if (n > ws.cap_n) {
@@ -135,26 +135,19 @@ int avd_ws_reserve_frames(avd_ctx* ctx, int n, size_t rowbuf_elems, size_t lappa
     return ws.d_lap_part.reserve(ctx, lappart_elems);
 }
 
-static size_t rowbuf_elems_for(const Workspace& ws, int n) { return (size_t)n * ws.pre.h * AVD_HASH; }
-static size_t lappart_elems_for(const Workspace& ws, int n) { return (size_t)n * ws.pre.nbands * kLapSlots * 2; }
-
-// one clip at offset 0 of the buffers
-int avd_ws_reserve(avd_ctx* ctx, int n, int h, int w)
-{
-    if (int e = avd_ws_geometry(ctx, h, w)) return e;
-    Workspace& ws = ctx->ws;
-    ws.f0 = 0; ws.rowbuf_off = 0; ws.lappart_off = 0;
-    return avd_ws_reserve_frames(ctx, n, rowbuf_elems_for(ws, n), lappart_elems_for(ws, n));
-}
+// what n frames of a geometry take of d_rowbuf / d_lap_part
+static size_t rowbuf_elems_for(const PreParams& pre, int n) { return (size_t)n * pre.h * AVD_HASH; }
+static size_t lappart_elems_for(const PreParams& pre, int n) { return (size_t)n * pre.nbands * kLapSlots * 2; }
 
 // Farneback scratch for min(n - 1, kFbChunkMax) pairs, at least kFbChunk; grows when a call brings more pairs
-int avd_ws_reserve_fb(avd_ctx* ctx, int n)
+static int avd_ws_reserve_fb(avd_ctx* ctx, int n)
 {
     Workspace& ws = ctx->ws;
     const int want = std::max(kFbChunk, std::min(std::max(n - 1, 0), kFbChunkMax));
     if (want > ws.fb_cap) {
         const size_t nf = (size_t)want + 2, np = (size_t)want;       // frames = pairs + 1, and one spare
         ws.fb_cap = 0;                                 // not valid again until every buffer below exists
+        ws.fb_holds = FbChunk{};
         for (int k = 0; k < AVD_FB_LEVELS; k++) {
             const size_t plane = (size_t)(AVD_SMALL >> k) * (AVD_SMALL >> k);
             // the 320-px scale of the pyramid exists only with fb_fold_blur off (the polynomial expansion forms that blur itself): 49 MB per 120 frames
@@ -163,7 +156,6 @@ int avd_ws_reserve_fb(avd_ctx* ctx, int n)
             if (int e = ws.d_poly[k].reserve(ctx, nf * 5 * plane)) return e;
             if (int e = ws.d_flow[k].reserve(ctx, np * 2 * plane)) return e;
             if (int e = ws.d_flow2[k].reserve(ctx, np * 2 * plane)) return e;
-            ws.flow_res[k] = nullptr;
         }
         if (int e = ws.d_stats.reserve(ctx, np * 2)) return e;
         if (int e = ws.d_mag.reserve(ctx, np * (size_t)AVD_NPIX)) return e;
@@ -222,26 +214,28 @@ __global__ __launch_bounds__(256) void k_records(const unsigned long long* __res
 
 // Fast mode: the pairs of the chunk in the workspace whose flag word is set (h_flags[0 .. np), as the host has just read them) go through the
 // exact kernels again (launch_farneback_rerun: enqueued, not drained).  Returns the number of such pairs, or a negative status.
-static int rerun_flagged(avd_ctx* ctx, const int* h_flags, int stride, int np)
+static int rerun_flagged(avd_ctx* ctx, const FlowCall& call, const int* h_flags, int stride, int np)
 {
     Workspace& ws = ctx->ws;
     int m = 0;
     for (int i = 0; i < np; i++)
         if (h_flags[(size_t)i * stride] != 0) ws.h_rlist[m++] = i;
     if (m == 0) return 0;
-    if (int e = launch_farneback_rerun(ctx, ws.h_rlist, m, np)) return e < 0 ? e : -1;
+    if (int e = launch_farneback_rerun(ctx, call, ws.h_rlist, m, np)) return e < 0 ? e : -1;
     return m;
 }
 
 __global__ void k_wake() {}
 
+// the records of frames fa .. p0 + np: the chunk of pairs p0 .. p0 + np - 1 is in the Farneback scratch.  np == 0: a call of one frame, which has no pair
 static void launch_records(avd_ctx* ctx, int p0, int np, int fa, const int* clipstart)
 {
     Workspace& ws = ctx->ws;
+    const int with_flow = np > 0;
     kmark(ctx, AVD_K_RECORDS);
     hipLaunchKernelGGL(k_records, dim3(p0 + np + 1 - fa), dim3(256), 0, ctx->stream, (const unsigned long long*)ws.d_lap,
-                       (const uint8_t*)ws.d_hash, (const float*)ws.d_stats,
-                       (const int*)(ctx->fb_mode == 1 && ctx->fb_rerun ? ws.d_fbflags : nullptr), p0, ws.d_rec, fa, clipstart, 1);
+                       (const uint8_t*)ws.d_hash, (const float*)(with_flow ? ws.d_stats.p : nullptr),
+                       (const int*)(with_flow && ctx->fb_mode == 1 && ctx->fb_rerun ? ws.d_fbflags.p : nullptr), p0, ws.d_rec, fa, clipstart, with_flow);
 }
 
 // Farneback + stats over all n-1 pairs in chunks; pair p = (frame p, frame p+1).
@@ -260,27 +254,29 @@ static int run_flow_chunks(avd_ctx* ctx, const uint8_t* d_small, int n, float* h
     const int chunk = ws.fb_cap;
     if (h_flow_out)
         if (int e = ws.d_flow_il.reserve(ctx, (size_t)chunk * AVD_NPIX * 2)) return e;
-    ws.no_flow_il = !h_flow_out;                           // nobody reads the interleaved flow of these chunks
     const bool flagged_mode = ctx->fb_mode == 1 && ctx->fb_rerun;
     const bool host_wants = h_mean || h_var || h_flow_out;
-    // fast mode: the shape of the 160-px level, once for all chunks and launches of this call.  fb_wide160 = 2 chooses by what is in flight: this call is
-    // being enqueued and not yet counted, so > 0 means SOMEBODY ELSE's kernels will share the chip with it
-    if (ctx->fb_mode == 1) ctx->fb_wide160_used = ctx->fb_wide160 == 1 || (ctx->fb_wide160 == 2 && avd_calls_in_flight() - ctx->counted_in_flight > 0);
+    // The plan of this call, handed to every launch of it.  Fast mode: the shape of the 160-px level, once for all chunks.  fb_wide160 = 2 chooses by what is
+    // in flight: this call is being enqueued and not yet counted, so > 0 means SOMEBODY ELSE's kernels will share the chip with it.
+    // The interleaved flow is formed only for a caller who fetches it.
+    const FlowCall call{ctx->fb_wide160 == 1 || (ctx->fb_wide160 == 2 && avd_calls_in_flight() - ctx->counted_in_flight > 0), h_flow_out != nullptr};
+    if (ctx->fb_mode == 1) ctx->fb_wide160_used = call.wide160;      // the record behind the read-only option
     int rc = 0;
     for (int p0 = 0; p0 < n - 1 && rc == 0; p0 += chunk) {
         const int np = std::min(chunk, n - 1 - p0);
         const bool last = p0 + np >= n - 1;
         const uint8_t* base = d_small + (size_t)p0 * AVD_NPIX;
-        rc = launch_farneback(ctx, base, np + 1);
+        FbChunk left;
+        rc = launch_farneback(ctx, call, base, np + 1, &left);
         if (rc) break;
-        rc = launch_flow_stats(ctx, np + 1);
+        rc = launch_flow_stats(ctx, call, left, np + 1);
         if (rc) break;
         if (flagged_mode && (!last || host_wants || !into_records)) {
             std::vector<int> fl((size_t)np, 0);
             hipError_t e = hipMemcpyAsync(fl.data(), ws.d_fbflags, sizeof(int) * np, hipMemcpyDeviceToHost, ctx->stream);
             if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
             if (e != hipSuccess) { ctx->err = hipGetErrorString(e); rc = AVD_ERR_DEVICE; break; }
-            const int m = rerun_flagged(ctx, fl.data(), 1, np);
+            const int m = rerun_flagged(ctx, call, fl.data(), 1, np);
             if (m < 0) { rc = m; break; }
             if (!into_records) ctx->last_rerun += m;
         }
@@ -289,7 +285,8 @@ static int run_flow_chunks(avd_ctx* ctx, const uint8_t* d_small, int n, float* h
         if (into_records) {
             launch_records(ctx, p0, np, fa, records_clipstart);
             if (flagged_mode && last && !host_wants) {
-                ctx->tail.active = 1; ctx->tail.p0 = p0; ctx->tail.np = np; ctx->tail.fa = fa; ctx->tail.clipstart = records_clipstart;
+                // (the records path asked for no dense flow, so the deferred re-run forms none)
+                ctx->tail.active = 1; ctx->tail.p0 = p0; ctx->tail.np = np; ctx->tail.fa = fa; ctx->tail.clipstart = records_clipstart; ctx->tail.call = call;
             }
         }
         if (host_wants) {
@@ -306,7 +303,6 @@ static int run_flow_chunks(avd_ctx* ctx, const uint8_t* d_small, int n, float* h
             }
         }
     }
-    ws.no_flow_il = 0;
     return rc;
 }
 
@@ -369,7 +365,7 @@ static int tail_settle(avd_ctx* ctx)
     ctx->tail.active = 0;
     Workspace& ws = ctx->ws;
     const int p0 = ctx->tail.p0, np = ctx->tail.np, fa = ctx->tail.fa;
-    const int m = rerun_flagged(ctx, &ws.h_rec[p0 + 1].reserved, (int)(sizeof(avd_frame_record) / sizeof(int)), np);
+    const int m = rerun_flagged(ctx, ctx->tail.call, &ws.h_rec[p0 + 1].reserved, (int)(sizeof(avd_frame_record) / sizeof(int)), np);
     if (m < 0) return m;
     if (m > 0) {
         launch_records(ctx, p0, np, fa, ctx->tail.clipstart);
@@ -580,8 +576,8 @@ static int upload_lists(avd_ctx* ctx, const IngestClip* clips, int nclips, const
 }
 
 // Stage clip c of the call at offset `at` of ws.d_stage (host input; reserved by the caller) and launch its fused full-resolution kernel, which
-// writes the clip's slice (ws.f0, ws.rowbuf_off, ws.lappart_off) of the per-frame buffers.  The clip's geometry is current.
-static int preprocess_clip(avd_ctx* ctx, const IngestClip& k, size_t at, const CallLists& L, int c)
+// writes the clip's slice of the per-frame buffers with the clip's geometry (slot).
+static int preprocess_clip(avd_ctx* ctx, const ClipSlot& slot, const IngestClip& k, size_t at, const CallLists& L, int c)
 {
     uint8_t* dst = ctx->ws.d_stage + at;
     if (k.is_list) {
@@ -594,7 +590,7 @@ static int preprocess_clip(avd_ctx* ctx, const IngestClip& k, size_t at, const C
         const uint8_t* const* d_tab = ctx->ws.d_ftab + L.at[c];
         const FrameTable ft{list_vec_eligible(k, h_tab)};
         auto plane = [&](int p) { return p < k.planes() ? reinterpret_cast<const uint8_t*>(d_tab + (size_t)p * k.n) : nullptr; };
-        return launch_preprocess(ctx, k, plane(0), plane(1), plane(2), &ft);
+        return launch_preprocess(ctx, slot, k, plane(0), plane(1), plane(2), &ft);
     }
     const uint8_t *d_in = k.data, *d_uv = k.uv, *d_v = k.v;
     if (k.mem == AVD_MEM_HOST) {
@@ -607,7 +603,7 @@ static int preprocess_clip(avd_ctx* ctx, const IngestClip& k, size_t at, const C
         if (k.planes() >= 2) d_uv = dst + s.plane_off[1];
         if (k.planes() == 3) d_v = dst + s.plane_off[2];
     }
-    return launch_preprocess(ctx, k, d_in, d_uv, d_v);
+    return launch_preprocess(ctx, slot, k, d_in, d_uv, d_v);
 }
 
 // Every avd_preprocess_* entry: one clip at offset 0 of the buffers, results to the host
@@ -618,7 +614,9 @@ static int impl_preprocess(avd_ctx* ctx, const IngestClip& k, uint8_t* small320,
     const int n = k.n;
     if (n == 0) return AVD_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (int e = avd_ws_reserve(ctx, n, k.disp_h(), k.disp_w())) return e;
+    ClipSlot slot;                                         // the one clip starts every buffer
+    if (int e = avd_ws_geometry(ctx, k.disp_h(), k.disp_w(), slot)) return e;
+    if (int e = avd_ws_reserve_frames(ctx, n, rowbuf_elems_for(slot.pre, n), lappart_elems_for(slot.pre, n))) return e;
     Workspace& ws = ctx->ws;
     CallLists lists;
     plan_lists(&k, 1, lists);
@@ -627,8 +625,8 @@ static int impl_preprocess(avd_ctx* ctx, const IngestClip& k, uint8_t* small320,
     ctx->ingest.stage_bytes = 0;
     ctx->ingest.stage_copies = 0;
     if (int e = upload_lists(ctx, &k, 1, lists)) return e;
-    if (int e = preprocess_clip(ctx, k, 0, lists, 0)) return e;
-    if (int e = launch_hash(ctx, n)) return e;
+    if (int e = preprocess_clip(ctx, slot, k, 0, lists, 0)) return e;
+    if (int e = launch_hash(ctx, slot, n)) return e;
     std::vector<unsigned long long> lap((size_t)n * 2);
     if (small320) HIP_TRY(ctx, hipMemcpyAsync(small320, ws.d_small, (size_t)n * AVD_NPIX, hipMemcpyDeviceToHost, ctx->stream));
     if (hash1024) HIP_TRY(ctx, hipMemcpyAsync(hash1024, ws.d_hash, (size_t)n * 1024, hipMemcpyDeviceToHost, ctx->stream));
@@ -704,23 +702,30 @@ static int impl_analyze_async(avd_ctx* ctx, const IngestClip* clips, int nclips,
     const int n = (int)total;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     Workspace& ws = ctx->ws;
-    // pass 1: geometry tables (cached) and sizes -- everything is reserved before the first launch of the call
+    // pass 1: geometry tables (cached), each clip's place in the buffers and their sizes -- everything is reserved before the first launch of the call
+    int frames = 0;
     size_t rowbuf_elems = 0, lappart_elems = 0, stage_bytes = 0;
     CallLists lists;
     plan_lists(clips, nclips, lists);
+    std::vector<ClipSlot> slots((size_t)nclips);
+    std::vector<size_t> stage_at((size_t)nclips, 0);       // the clip's first byte of ws.d_stage
     for (int c = 0; c < nclips; c++) {
         const IngestClip& k = clips[c];
         if (k.n == 0) continue;
-        if (int e = avd_ws_geometry(ctx, k.disp_h(), k.disp_w())) return e;
-        rowbuf_elems += rowbuf_elems_for(ws, k.n);
-        lappart_elems += lappart_elems_for(ws, k.n);
+        ClipSlot& slot = slots[c];
+        if (int e = avd_ws_geometry(ctx, k.disp_h(), k.disp_w(), slot)) return e;
+        slot.f0 = frames; slot.rowbuf_off = rowbuf_elems; slot.lappart_off = lappart_elems;
+        stage_at[c] = stage_bytes;
+        frames += k.n;
+        rowbuf_elems += rowbuf_elems_for(slot.pre, k.n);
+        lappart_elems += lappart_elems_for(slot.pre, k.n);
         stage_bytes += lists.total(k, c);
     }
     if (int e = avd_ws_reserve_frames(ctx, n, rowbuf_elems, lappart_elems)) return e;
     if (int e = avd_ws_reserve_fb(ctx, n)) return e;
     if (int e = ws.d_stage.reserve(ctx, stage_bytes)) return e;
     if (int e = reserve_lists(ctx, lists)) return e;
-    // pass 2: per clip, stage (host input) -> fused full-resolution kernel -> hash, at the clip's offsets
+    // pass 2: per clip, stage (host input) -> fused full-resolution kernel -> hash, in the clip's slot
     ctx->kmark_used = 0;
     ctx->ingest.stage_bytes = 0;
     ctx->ingest.stage_copies = 0;
@@ -728,25 +733,20 @@ static int impl_analyze_async(avd_ctx* ctx, const IngestClip* clips, int nclips,
     if (ctx->profiling) hipLaunchKernelGGL(k_wake, dim3(1), dim3(64), 0, ctx->stream);
     stage_mark(ctx, 0);
     if (int e = upload_lists(ctx, clips, nclips, lists)) return e;
-    int f0 = 0;
-    size_t rb = 0, lp = 0, st = 0;
     for (int c = 0; c < nclips; c++) {
         const IngestClip& k = clips[c];
         if (k.n == 0) continue;
-        if (int e = avd_ws_geometry(ctx, k.disp_h(), k.disp_w())) return e;       // a cache hit (pass 1 built it) unless > kGeomCache geometries
-        ws.f0 = f0; ws.rowbuf_off = rb; ws.lappart_off = lp;
-        ws.h_clipstart[f0] = 1;
-        for (int i = 1; i < k.n; i++) ws.h_clipstart[f0 + i] = 0;
+        ClipSlot& slot = slots[c];
+        // the tables again: a cache hit (pass 1 built them) unless the call has > kGeomCache geometries -- then pass 1 has evicted this one since,
+        // the slot's copies point into freed tables, and they are rebuilt here (same geometry, same sizes: the offsets hold)
+        if (int e = avd_ws_geometry(ctx, k.disp_h(), k.disp_w(), slot)) return e;
+        ws.h_clipstart[slot.f0] = 1;
+        for (int i = 1; i < k.n; i++) ws.h_clipstart[slot.f0 + i] = 0;
         kmark(ctx, AVD_K_PREPROCESS);
-        if (int e = preprocess_clip(ctx, k, st, lists, c)) return e;
-        st += lists.total(k, c);
+        if (int e = preprocess_clip(ctx, slot, k, stage_at[c], lists, c)) return e;
         kmark(ctx, AVD_K_HASH);
-        if (int e = launch_hash(ctx, k.n)) return e;
-        f0 += k.n;
-        rb += rowbuf_elems_for(ws, k.n);
-        lp += lappart_elems_for(ws, k.n);
+        if (int e = launch_hash(ctx, slot, k.n)) return e;
     }
-    ws.f0 = 0; ws.rowbuf_off = 0; ws.lappart_off = 0;
     kmark(ctx, AVD_K_OTHER);
     stage_mark(ctx, 1);
     const int* clipstart = nullptr;                        // one clip: frame 0 is the only one without a predecessor
@@ -761,9 +761,7 @@ static int impl_analyze_async(avd_ctx* ctx, const IngestClip* clips, int nclips,
         bool ok = false;
         ~TailOnError() { if (!ok) c->tail.active = 0; }
     } tail_on_error{ctx};
-    if (n < 2)
-        hipLaunchKernelGGL(k_records, dim3(n), dim3(256), 0, ctx->stream, (const unsigned long long*)ws.d_lap, (const uint8_t*)ws.d_hash,
-                           (const float*)nullptr, (const int*)nullptr, 0, ws.d_rec, 0, clipstart, 0);
+    if (n < 2) launch_records(ctx, 0, 0, 0, clipstart);     // one frame: no pair, no flow
     else if (int e = run_flow_chunks(ctx, ws.d_small, n, nullptr, nullptr, nullptr, true, clipstart)) return e;
     kmark(ctx, AVD_K_OTHER);
     stage_mark(ctx, 3);
@@ -841,7 +839,7 @@ static int impl_synchronize(avd_ctx* ctx)
         }
         // 4 / 5: mean duration of one k_uv<320> / k_hscan<320> launch (the last chunk)
         float sum[2] = {0.f, 0.f}; int cnt[2] = {0, 0};
-        for (int i = 0; i + 1 < ctx->kern_ev_used; i += 2) {     // stage_mark events of the drained call
+        for (int i = 0; i + 1 < ctx->kern_ev_used; i += 2) {     // level320_mark events of the drained call
             float ms = 0.f;
             if (hipEventElapsedTime(&ms, ctx->kern_ev[i], ctx->kern_ev[i + 1]) == hipSuccess) { sum[(i >> 1) & 1] += ms; cnt[(i >> 1) & 1]++; }
         }
@@ -957,7 +955,7 @@ static int64_t impl_debug_fetch(avd_ctx* ctx, const char* name, void* out, size_
     else if ((k = level("pyr")) >= 0 && k == 0 && ctx->fb_fold_blur) { ctx->err = "pyr0 does not exist while fb_fold_blur is on (the polynomial expansion forms the 320-px blur itself)"; return AVD_ERR_ARG; }
     else if ((k = level("pyr")) >= 0) { src = ws.d_pyr[k]; bytes = (size_t)std::min(n, ws.fb_cap + 1) * (AVD_NPIX >> (2 * k)) * 4; }
     else if ((k = level("poly")) >= 0) { src = ws.d_poly[k]; bytes = (size_t)std::min(n, ws.fb_cap + 1) * 5 * (AVD_NPIX >> (2 * k)) * 4; }
-    else if ((k = level("flow")) >= 0) { src = ws.flow_res[k] ? ws.flow_res[k] : ws.d_flow[k]; bytes = (size_t)std::min(std::max(n - 1, 0), ws.fb_cap) * 2 * (AVD_NPIX >> (2 * k)) * 4; }
+    else if ((k = level("flow")) >= 0) { src = ws.fb_holds.flow[k] ? ws.fb_holds.flow[k] : ws.d_flow[k]; bytes = (size_t)std::min(std::max(n - 1, 0), ws.fb_cap) * 2 * (AVD_NPIX >> (2 * k)) * 4; }
     else if (std::strcmp(name, "vs0") == 0) { src = ws.d_vs0; bytes = fb_two_scratch_size((size_t)ws.fb_cap).vs0 * sizeof(double); }
     else { ctx->err = "unknown debug buffer"; return AVD_ERR_ARG; }
     if (!src) { ctx->err = "buffer not allocated yet"; return AVD_ERR_ARG; }

@@ -829,13 +829,13 @@ int launch_conv_shape(avd_ctx* ctx, const ConvGeom& g, const uint16_t* x, const 
     return launch_tiles(ctx, k_conv_bf16<BM, WAVES_M, TI, MODE, KS>, tiles_of(g.m_out, S::BM) * (g.cout / S::BN), S::lds(g.nh), x, w, bias, res, y, g, relu);
 }
 
-// stem == true: x is the bordered input image, (hin, win, cin, ksize, stride) describe the 7x7/2 convolution
-int launch_conv(avd_ctx* ctx, const uint16_t* x, const uint16_t* w, const float* bias, const uint16_t* res, uint16_t* y, int n, int hin,
+// stem == true: x is the bordered input image, (hin, win, cin, ksize, stride) describe the 7x7/2 convolution.  *ran = the kernel shape it launched
+int launch_conv(avd_ctx* ctx, CnnShape* ran, const uint16_t* x, const uint16_t* w, const float* bias, const uint16_t* res, uint16_t* y, int n, int hin,
                 int win, int cin, int cout, int ksize, int stride, int relu, bool stem = false)
 {
     const ConvGeom g = conv_geom(n, hin, win, cin, cout, ksize, stride, stem);
     if (!stem && (cin % 32 || cout % 64 || (ksize != 1 && ksize != 3))) { ctx->err = "conv: cin % 32, cout % 64, ksize 1 or 3"; return AVD_ERR_ARG; }
-    if (stem) { ctx->cnn_shape = kCnnStem; return launch_conv_shape<256, 8, 2, 1, 1>(ctx, g, x, w, bias, res, y, relu); }
+    if (stem) { *ran = kCnnStem; return launch_conv_shape<256, 8, 2, 1, 1>(ctx, g, x, w, bias, res, y, relu); }
     // 256-pixel tiles for the long-K layers that fill the chip.  128 x 128 tiles (74 registers, 16 KiB per ring slot: several
     // workgroups per CU) where 256-pixel tiles would leave most of the chip idle (the 14 x 14 and 7 x 7 stages), and for the
     // short-K 1x1 layers, which move bytes rather than multiply: there the time goes to load / store latency, and
@@ -850,10 +850,10 @@ int launch_conv(avd_ctx* ctx, const uint16_t* x, const uint16_t* w, const float*
     const bool want_small = wgs_big * 100 < ctx->num_cus * fill_pct || g.nh <= short_k;
     auto tiled = [&](auto ks) -> int {
         constexpr int KS = decltype(ks)::value;
-        if (small_ok && force != 1 && (want_small || force == 2)) { ctx->cnn_shape = kCnn128x128; return launch_conv_shape<128, 4, 2, 0, KS>(ctx, g, x, w, bias, res, y, relu); }
-        if (bn_big == 256) { ctx->cnn_shape = kCnn256x256; return launch_conv_shape<256, 2, 8, 0, KS>(ctx, g, x, w, bias, res, y, relu); }
-        if (bn_big == 128) { ctx->cnn_shape = kCnn256x128; return launch_conv_shape<256, 4, 4, 0, KS>(ctx, g, x, w, bias, res, y, relu); }
-        ctx->cnn_shape = kCnn256x64;
+        if (small_ok && force != 1 && (want_small || force == 2)) { *ran = kCnn128x128; return launch_conv_shape<128, 4, 2, 0, KS>(ctx, g, x, w, bias, res, y, relu); }
+        if (bn_big == 256) { *ran = kCnn256x256; return launch_conv_shape<256, 2, 8, 0, KS>(ctx, g, x, w, bias, res, y, relu); }
+        if (bn_big == 128) { *ran = kCnn256x128; return launch_conv_shape<256, 4, 4, 0, KS>(ctx, g, x, w, bias, res, y, relu); }
+        *ran = kCnn256x64;
         return launch_conv_shape<256, 8, 2, 0, KS>(ctx, g, x, w, bias, res, y, relu);
     };
     return ksize == 3 ? tiled(std::integral_constant<int, 3>{}) : tiled(std::integral_constant<int, 1>{});
@@ -861,9 +861,9 @@ int launch_conv(avd_ctx* ctx, const uint16_t* x, const uint16_t* w, const float*
 
 // conv2 (3x3, mid -> mid, stride s, ReLU) + conv3 (1x1, mid -> 4 mid, + residual, ReLU) of a bottleneck block in one launch
 // (k_conv3_expand, or k_slab3_expand in the stride-1 blocks with cnn_fuse = 2); mid = 64 (256-pixel tiles) or 128 (128-pixel
-// tiles).  y must not be the 3x3's input.
+// tiles).  y must not be the 3x3's input.  *ran = which of the two it launched
 bool can_fuse_expand(int mid) { return mid == 64 || mid == 128; }
-int launch_conv3_expand(avd_ctx* ctx, const uint16_t* x, const uint16_t* w2, const float* b2, const uint16_t* w3, const float* b3,
+int launch_conv3_expand(avd_ctx* ctx, CnnShape* ran, const uint16_t* x, const uint16_t* w2, const float* b2, const uint16_t* w3, const float* b3,
                         const uint16_t* res, uint16_t* y, int n, int hin, int win, int mid, int stride)
 {
     const ConvGeom g = conv_geom(n, hin, win, mid, mid, 3, stride);
@@ -874,7 +874,7 @@ int launch_conv3_expand(avd_ctx* ctx, const uint16_t* x, const uint16_t* w2, con
         auto slab = [&](auto shape, auto kern) -> int {
             using S = decltype(shape);
             if (win + 1 > S::HALO) { ctx->err = "conv3_expand: the slab's halo is sized for 56 x 56 (mid 64) and 28 x 28 (mid 128)"; return AVD_ERR_ARG; }
-            ctx->cnn_shape = kCnnSlab3Expand;
+            *ran = kCnnSlab3Expand;
             return launch_tiles(ctx, kern, tiles_of(g.m_out, S::BM), S::LDS, x, w2, b2, w3, b3, res, y, g, in_blocks);
         };
         return mid == 64 ? slab(SlabShape<64>{}, k_slab3_expand<64>) : slab(SlabShape<128>{}, k_slab3_expand<128>);
@@ -883,7 +883,7 @@ int launch_conv3_expand(avd_ctx* ctx, const uint16_t* x, const uint16_t* w2, con
         using S = decltype(shape);
         // the kernel's LDS plan assumes which ring slot the 3x3's last step reads
         if ((g.nh & 3) != S::PHASE) { ctx->err = "conv3_expand: ring phase"; return AVD_ERR_ARG; }
-        ctx->cnn_shape = kCnnConv3Expand;
+        *ran = kCnnConv3Expand;
         return launch_tiles(ctx, kern, tiles_of(g.m_out, S::BM), S::LDS, x, w2, b2, w3, b3, res, y, g);
     };
     return mid == 64 ? gather(FusedShape<256, 8, 2>{}, k_conv3_expand<256, 8, 2>) : gather(FusedShape<128, 4, 2>{}, k_conv3_expand<128, 4, 2>);
@@ -984,8 +984,9 @@ int launch_cnn_forward(avd_ctx* ctx, const uint8_t* d_bgr, int n, int h, int w, 
     auto conv = [&](size_t i, const uint16_t* x, const uint16_t* res, uint16_t* y, int hin, int ci, int co, int ksize, int s, int relu, bool stem = false) -> int {
         const size_t rows = (size_t)n * (hin / s) * (hin / s);
         if (int e = fits(rows, co)) return e;
-        if (int e = launch_conv(ctx, x, wptr(i), bptr(i), res, y, n, hin, hin, ci, co, ksize, s, relu, stem)) return e;
-        plan[i] = ctx->cnn_shape;
+        CnnShape ran;
+        if (int e = launch_conv(ctx, &ran, x, wptr(i), bptr(i), res, y, n, hin, hin, ci, co, ksize, s, relu, stem)) return e;
+        plan[i] = ran;
         return tap(kCnnTapConv0 + (int)i, y, rows, co);
     };
     const int64_t px = (int64_t)n * kSide * kSide;
@@ -1016,8 +1017,9 @@ int launch_cnn_forward(avd_ctx* ctx, const uint8_t* d_bgr, int n, int h, int w, 
             if (ctx->cnn_fuse && can_fuse_expand(mid)) {     // conv2 + conv3 in one launch: a1 -> a2 (other workgroups still read a1's halo)
                 const size_t rows = (size_t)n * ho * ho;
                 if (int e = fits(rows, out)) return e;
-                if (int e = launch_conv3_expand(ctx, a1, wptr(li + 1), bptr(li + 1), wptr(li + 2), bptr(li + 2), res, a2, n, hgt, hgt, mid, s)) return e;
-                plan[li + 1] = ctx->cnn_shape;               // recorded at the 3x3, whose output never leaves the CU: nothing to tap there
+                CnnShape ran;
+                if (int e = launch_conv3_expand(ctx, &ran, a1, wptr(li + 1), bptr(li + 1), wptr(li + 2), bptr(li + 2), res, a2, n, hgt, hgt, mid, s)) return e;
+                plan[li + 1] = ran;                          // recorded at the 3x3, whose output never leaves the CU: nothing to tap there
                 if (int e = tap(kCnnTapConv0 + (int)li + 2, a2, rows, out)) return e;
                 cur = t2;
             } else {                                         // conv3 writes over a1
@@ -1097,7 +1099,8 @@ int cnn_conv_host(avd_ctx* ctx, const uint16_t* x, int n, int hin, int win, int 
     CNN_TRY(hipMemcpyAsync(db, bias, cout * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
     CNN_TRY(hipMemsetAsync(dy, 0, hy.size() * 2, ctx->stream));
     if (residual) CNN_TRY(hipMemcpyAsync(dr, hr.data(), hr.size() * 2, hipMemcpyHostToDevice, ctx->stream));
-    rc = launch_conv(ctx, dx, dw, db, dr, dy, n, hin, win, cin, cout, ksize, stride, relu);
+    CnnShape ran;                                            // nobody asks for it here
+    rc = launch_conv(ctx, &ran, dx, dw, db, dr, dy, n, hin, win, cin, cout, ksize, stride, relu);
     if (rc == AVD_OK) {
         CNN_TRY(hipMemcpyAsync(hy.data(), dy, hy.size() * 2, hipMemcpyDeviceToHost, ctx->stream));
         CNN_TRY(hipStreamSynchronize(ctx->stream));

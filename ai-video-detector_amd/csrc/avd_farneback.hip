@@ -651,13 +651,14 @@ void flow_up_level(hipStream_t stream, int k, const float* prev, float* flow, in
 // Levels 3 -> 0 with the EXACT kernels (bit-identical to the oracle), a level's three iterations in place in its flow buffer: the fused kernel
 // (avd_fbfused.hip) where bit k of fused_mask is set, else the two-kernel path (avd_fbtwo.hip) through `scratch`.  plist == null: exact mode, all np
 // pairs of the chunk; plist != null: the re-run of the flagged pairs plist[0 .. np).  The two differ in four things, (1) .. (4), and in nothing else.
-int exact_levels(avd_ctx* ctx, int np, int fused_mask, FbTwoScratch scratch, const int* plist)
+// chunk: exact mode fills in where it leaves each level's flow; the re-run reads where the fast kernels left the 320-px one.
+int exact_levels(avd_ctx* ctx, int np, int fused_mask, FbTwoScratch scratch, const int* plist, FbChunk& chunk)
 {
     Workspace& ws = ctx->ws;
     const hipStream_t stream = ctx->stream;
     const bool rerun = plist != nullptr;
     // (1) level 0 works in its first flow buffer; the re-run in the one the fast kernels left their final flow in (the caller may read it back)
-    float* const flow0 = rerun ? const_cast<float*>(ws.flow_res[0]) : ws.d_flow[0].p;
+    float* const flow0 = rerun ? const_cast<float*>(chunk.flow[0]) : ws.d_flow[0].p;
     if (rerun) kmark(ctx, AVD_K_RERUN);                  // (3) avd_kernel_ms: exact mode records the per-level regions, the re-run is one region
     for (int k = AVD_FB_LEVELS - 1; k >= 0; k--) {
         const int w = S >> k;
@@ -671,12 +672,12 @@ int exact_levels(avd_ctx* ctx, int np, int fused_mask, FbTwoScratch scratch, con
             if (!rerun) kmark(ctx, kFlowUpId[k]);
             flow_up_level(stream, k, ws.d_flow[k + 1], flow, np, plist);
         }
-        if (!rerun) { ws.flow_res[k] = flow; kmark(ctx, kLevelId[k]); }
+        if (!rerun) { chunk.flow[k] = flow; kmark(ctx, kLevelId[k]); }
         const bool marks = !rerun && k == 0;             // (4) the events of avd_stage_ms 4 / 5 belong to the 320-px level of exact mode
         if (fused) {
-            stage_mark(ctx, marks);
+            level320_mark(ctx, marks);
             if (int e = launch_fb_level(ctx, stream, w, ws.d_poly[k], flow, np, 3, coarsest, plist)) return e;
-            stage_mark(ctx, marks);
+            level320_mark(ctx, marks);
         } else {
             for (int it = 0; it < 3; it++)
                 if (int e = launch_fb_two(ctx, stream, w, ws.d_poly[k], flow, scratch, np, plist, marks)) return e;
@@ -689,7 +690,7 @@ int exact_levels(avd_ctx* ctx, int np, int fused_mask, FbTwoScratch scratch, con
 // buffers (a = initial flow, results b, a, b), the last launch writes |flow| to d_mag; ctx->fb_fold_up and ctx->fb_fold_up160 (avd_internal.h) say what the
 // launches fold in.
 // Pairs the kernels flag as ill-posed are re-run by the exact kernels once the HOST has seen the flags (launch_farneback_rerun).
-int fast_levels(avd_ctx* ctx, int np)
+int fast_levels(avd_ctx* ctx, const FlowCall& call, int np, FbChunk& chunk)
 {
     Workspace& ws = ctx->ws;
     const hipStream_t stream = ctx->stream;
@@ -701,9 +702,9 @@ int fast_levels(avd_ctx* ctx, int np)
         const bool coarsest = k == AVD_FB_LEVELS - 1, three = (k == 2 || k == 3) && (fold & 4);
         float *a = ws.d_flow[k], *b = ws.d_flow2[k];
         // the initial flow: zero at the coarsest level, else the coarser level's final flow, resized by the first launch itself or by k_flow_up into a
-        const float* prev = coarsest ? nullptr : ws.flow_res[k + 1];
+        const float* prev = coarsest ? nullptr : chunk.flow[k + 1];
         // (160 px: the chain wave resizes in the one-strip shape only, which the call has chosen or not before it got here)
-        const bool chain = (k == 0 && (fold & 1)) || (k == 1 && ctx->fb_fold_up160 && ctx->fb_wide160_used);
+        const bool chain = (k == 0 && (fold & 1)) || (k == 1 && ctx->fb_fold_up160 && call.wide160);
         const FbFlowFrom from = coarsest ? FbFlowFrom::zero : chain ? FbFlowFrom::chain
                                 : ((k == 1 || k == 2) && (fold & 2)) ? FbFlowFrom::prologue : FbFlowFrom::level;
         if (from == FbFlowFrom::level) {
@@ -712,50 +713,52 @@ int fast_levels(avd_ctx* ctx, int np)
         }
         const bool from_prev = from == FbFlowFrom::chain || from == FbFlowFrom::prologue;
         kmark(ctx, kLevelId[k]);
-        stage_mark(ctx, k == 0);
+        level320_mark(ctx, k == 0);
         if (three) {                                     // (prologue: prev -> a,) a -> b -> a -> b
-            const FbFastLaunch L{3, from, from_prev ? prev : a, b, a, nullptr, flags, pairdiff};
+            const FbFastLaunch L{call.wide160, 3, from, from_prev ? prev : a, b, a, nullptr, flags, pairdiff};
             if (int e = launch_fb_fast(ctx, stream, w, ws.d_poly[k], L, np)) return e;
             a = b;
         } else {
             for (int it = 0; it < 3; it++) {
                 float* mag = (k == 0 && it == 2) ? ws.d_mag.p : nullptr;
-                const FbFastLaunch L{1, it == 0 ? from : FbFlowFrom::level, it == 0 && from_prev ? prev : a, b, a, mag, flags, pairdiff};
+                const FbFastLaunch L{call.wide160, 1, it == 0 ? from : FbFlowFrom::level, it == 0 && from_prev ? prev : a, b, a, mag, flags, pairdiff};
                 if (int e = launch_fb_fast(ctx, stream, w, ws.d_poly[k], L, np)) return e;
                 float* t = a; a = b; b = t;
             }
         }
-        stage_mark(ctx, k == 0);
-        ws.flow_res[k] = a;                            // the buffer written last
+        level320_mark(ctx, k == 0);
+        chunk.flow[k] = a;                             // the buffer written last
     }
     return 0;
 }
 
 // What follows the levels: |flow| (with_mag; the fast kernels write it themselves) and the two statistics of m pairs -- plist[0 .. m), or the first m
-// with plist null -- and, when the caller wants the dense flow (tests / debugging), cv2's interleaved layout of the whole chunk (np_chunk pairs).
-void flow_tail(avd_ctx* ctx, const float* flow, bool with_mag, int m, const int* plist, int np_chunk)
+// with plist null -- and, when the call wants the dense flow (tests / debugging), cv2's interleaved layout of the whole chunk (np_chunk pairs).
+void flow_tail(avd_ctx* ctx, const FlowCall& call, const float* flow, bool with_mag, int m, const int* plist, int np_chunk)
 {
     Workspace& ws = ctx->ws;
     const hipStream_t stream = ctx->stream;
     if (with_mag) launch1d(k_mag, (int64_t)m * (AVD_NPIX / 4), 256, stream, flow, ws.d_mag.p, (int64_t)m * (AVD_NPIX / 4), plist);
     hipLaunchKernelGGL(k_stats_pair, dim3(m), dim3(512), 0, stream, (const float*)ws.d_mag, ws.d_stats.p, plist);
-    if (!ws.no_flow_il && ws.d_flow_il)
+    if (call.dense_flow && ws.d_flow_il)
         launch1d(k_flow_interleave, (int64_t)np_chunk * AVD_NPIX, 256, stream, flow, ws.d_flow_il.p, (int64_t)np_chunk * AVD_NPIX);
 }
 
 }  // namespace
 
 // All pairs (f, f+1), f in [0, n-1), of n resident 320x320 frames (one chunk), on the context's stream, into the Farneback scratch
-int launch_farneback(avd_ctx* ctx, const uint8_t* d_small, int n)
+int launch_farneback(avd_ctx* ctx, const FlowCall& call, const uint8_t* d_small, int n, FbChunk* left)
 {
     if (n < 2) return 0;
     Workspace& ws = ctx->ws;
     if (ctx->profiling) ctx->kern_ev_used = 0;
     const bool fast = ctx->fb_mode == 1;
-    ws.mag_valid = fast;
+    FbChunk& chunk = ws.fb_holds;                      // level by level: a launch sequence that fails half way has overwritten those levels
+    chunk.mag_valid = fast;
     pyramid_and_polyexp(ctx, d_small, n);
-    if (int e = fast ? fast_levels(ctx, n - 1) : exact_levels(ctx, n - 1, ctx->fb_fused, {ws.d_vs, ws.d_vs0}, nullptr)) return e;
+    if (int e = fast ? fast_levels(ctx, call, n - 1, chunk) : exact_levels(ctx, n - 1, ctx->fb_fused, {ws.d_vs, ws.d_vs0}, nullptr, chunk)) return e;
     HIP_TRY(ctx, hipGetLastError());
+    *left = chunk;
     return 0;
 }
 
@@ -766,7 +769,7 @@ int launch_farneback(avd_ctx* ctx, const uint8_t* d_small, int n)
 // 64-row bands: ~0.15 ms per level for one pair, where the fused kernel's single workgroup per pair takes 0.23 / 0.83 ms however few pairs there are),
 // beyond that the fused kernels (one workgroup per pair = the exact mode's own launches, its time for a clip of nothing but flagged pairs).
 // ctx->fb_rerun_fused (tuning / tests): level mask of the fused kernel for the few-pairs case, default 0xC (40 and 80 px).
-int launch_farneback_rerun(avd_ctx* ctx, const int* h_list, int m, int np_chunk)
+int launch_farneback_rerun(avd_ctx* ctx, const FlowCall& call, const int* h_list, int m, int np_chunk)
 {
     if (m <= 0) return 0;
     Workspace& ws = ctx->ws;
@@ -779,18 +782,17 @@ int launch_farneback_rerun(avd_ctx* ctx, const int* h_list, int m, int np_chunk)
         if (int e = ws.d_vs_rerun.reserve(ctx, sz.vs)) return e;
     }
     HIP_TRY(ctx, hipMemcpyAsync(ws.d_rlist, h_list, sizeof(int) * m, hipMemcpyHostToDevice, ctx->stream));
-    if (int e = exact_levels(ctx, m, fused_mask, {ws.d_vs_rerun, ws.d_vs0_rerun}, ws.d_rlist)) return e;   // the scratch is indexed by position in the list
-    flow_tail(ctx, ws.flow_res[0], true, m, ws.d_rlist, np_chunk);
+    if (int e = exact_levels(ctx, m, fused_mask, {ws.d_vs_rerun, ws.d_vs0_rerun}, ws.d_rlist, ws.fb_holds)) return e;   // the scratch is indexed by position in the list
+    flow_tail(ctx, call, ws.fb_holds.flow[0], true, m, ws.d_rlist, np_chunk);
     HIP_TRY(ctx, hipGetLastError());
     return 0;
 }
 
-int launch_flow_stats(avd_ctx* ctx, int n)
+int launch_flow_stats(avd_ctx* ctx, const FlowCall& call, const FbChunk& chunk, int n)
 {
     if (n < 2) return 0;
-    Workspace& ws = ctx->ws;
     kmark(ctx, AVD_K_STATS);
-    flow_tail(ctx, ws.flow_res[0] ? ws.flow_res[0] : ws.d_flow[0].p, !ws.mag_valid, n - 1, nullptr, n - 1);
+    flow_tail(ctx, call, chunk.flow[0], !chunk.mag_valid, n - 1, nullptr, n - 1);
     HIP_TRY(ctx, hipGetLastError());
     return 0;
 }

@@ -612,7 +612,7 @@ int launch_fb_fast(avd_ctx* ctx, hipStream_t stream, int w, const float* R, cons
     // the combinations that exist (k_fb_fast's template arguments, launch_fast)
     const bool one = L.iterations == 1, three = L.iterations == 3;
     const bool ok = L.from == FbFlowFrom::level || L.from == FbFlowFrom::zero ? (one || (three && (w == 80 || w == 40)))
-                  : L.from == FbFlowFrom::chain ? (one && (w == 320 || (w == 160 && ctx->fb_wide160_used)))      // 160 px: the one-strip shape only
+                  : L.from == FbFlowFrom::chain ? (one && (w == 320 || (w == 160 && L.wide160)))      // 160 px: the one-strip shape only
                   : (one ? (w == 160 || w == 80) : (three && w == 80));      // prologue
     if (!ok) { ctx->err = "launch_fb_fast: this mode does not exist at this level size"; return AVD_ERR_ARG; }
     const bool uses_tmp = three || L.from == FbFlowFrom::prologue;
@@ -629,9 +629,9 @@ int launch_fb_fast(avd_ctx* ctx, hipStream_t stream, int w, const float* R, cons
         // (one clip alone: -25 us); the wide one costs fewer CU-microseconds (119 x 58 against 238 x 48: lanes 91 % instead of 73 % on image
         // columns, 14 halo columns per pair instead of 28) and that is what counts with clips in flight: +2.4 % frames/s.  The two differ in the
         // grouping of the solver's window sums (four columns per lane against two): bit-identical on well-posed content, like the 320-px level.
-        // Which of the two a call takes is decided once, when the call is enqueued (ctx->fb_wide160_used, avd_capi.hip): all launches of the call,
+        // Which of the two a call takes is decided once, when the call is enqueued (FlowCall::wide160, avd_capi.hip): all launches of the call,
         // and the schedule that chooses where the first one's flow comes from (fast_levels), read the same answer.
-        if (ctx->fb_wide160_used) launch_fast<FGeo<160, 3, 2, 2, 1>>(stream, R, L, nullptr, np, 1, 160);
+        if (L.wide160) launch_fast<FGeo<160, 3, 2, 2, 1>>(stream, R, L, nullptr, np, 1, 160);
         else launch_fast<FGeo<160, 2, 1, 4, 2>>(stream, R, L, nullptr, np, 2, 80);
         break;
     case 80: launch_fast<FGeo<80, 2, 1, 4, 2>>(stream, R, L, nullptr, np, 1, 80); break;

@@ -658,7 +658,7 @@ template <int W>
 void blur_iteration(avd_ctx* ctx, hipStream_t stream, const float* R, float* flow, FbTwoScratch s, int np, const int* plist, bool marks)
 {
     // profiling: HIP events around the two full-resolution kernels (avd_stage_ms 4 and 5)
-    auto mark = [&](void) { stage_mark(ctx, marks && W == S); };
+    auto mark = [&](void) { level320_mark(ctx, marks && W == S); };
     const Shape shape = choose_shape(W, np, plist != nullptr);
     const dim3 grid(8 * ((np + 7) / 8) * strips_of(W));  // (XCD, pair-in-XCD, strip); pairs >= np exit at once
     const float* fin = flow;

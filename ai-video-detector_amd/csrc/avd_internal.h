@@ -158,14 +158,32 @@ struct Geom {
     unsigned long long stamp = 0;      // last use (LRU eviction)
 };
 
+// One clip of an ingest call, as its launches see it: the geometry it runs with and its slice of the per-frame buffers (a batch concatenates its
+// clips).  pre / hsh are COPIES of the geometry's cache entry, not pointers into it: a call with more than kGeomCache geometries evicts entries as it goes.
+struct ClipSlot {
+    PreParams pre{};
+    HashParams hsh{};
+    int f0 = 0;                        // first frame of the clip in the [n] buffers
+    size_t rowbuf_off = 0, lappart_off = 0;   // its first element of d_rowbuf / d_lap_part
+};
+
+// What one Farneback call (all its chunks, and the deferred exact re-run of its last one) runs as: decided once, where the call is enqueued (run_flow_chunks)
+struct FlowCall {
+    bool wide160;                      // fast mode: the 160-px level as one three-block strip per pair (see avd_ctx::fb_wide160)
+    bool dense_flow;                   // the caller fetches the interleaved flow (ws.d_flow_il, reserved): the chunks' flow_tail interleaves it
+};
+// What launch_farneback left in the Farneback scratch
+struct FbChunk {
+    const float* flow[AVD_FB_LEVELS] = {};   // the final flow of each level (d_flow or d_flow2)
+    bool mag_valid = false;                  // d_mag holds |flow| of the chunk already (the fast level kernel wrote it)
+};
+
 // Scratch of a context.  Everything here can be given back (avd_release_workspace resets the struct) and is re-reserved on demand.
 struct Workspace {
     // capacities of the per-frame buffers, which only ever grow: cap_n frames validates every [n] buffer below at once (0 until all exist)
     int cap_n = 0;
     Geom geoms[kGeomCache];
     unsigned long long geom_clock = 0;
-    // position of the clip being enqueued inside the buffers of the call (a batch concatenates its clips)
-    int f0 = 0; size_t rowbuf_off = 0, lappart_off = 0;
     int fb_cap = 0;                    // pairs the Farneback scratch holds (0 until every buffer of it exists)
     DevBuf<int> d_clipstart; PinBuf<int> h_clipstart;   // [n] 1 = first frame of a clip
     // preprocess
@@ -179,16 +197,13 @@ struct Workspace {
     DevBuf<uint8_t> d_hash;           // [n][1024]
     DevBuf<unsigned long long> d_lap; // [n][2]
     DevBuf<long long> d_lap_part;     // [n][nbands][kLapSlots][2] per-wave partial moments
-    PreParams pre{};                  // geometry of the clip being enqueued (copies of its cache entry)
-    HashParams hsh{};
     // farneback
     DevBuf<float> d_pyr[AVD_FB_LEVELS];     // [n][hL*wL]
     DevBuf<float> d_poly[AVD_FB_LEVELS];    // [n][hL*wL][5] interleaved polynomial coefficients
     DevBuf<float> d_flow[AVD_FB_LEVELS];    // [n-1][2][hL*wL]  planar
     DevBuf<float> d_flow2[AVD_FB_LEVELS];   // second flow buffer of a level: the fast level kernel (avd_fbfast.hip) ping-pongs
-    const float* flow_res[AVD_FB_LEVELS] = {};   // where the last call left the final flow of each level (d_flow or d_flow2)
+    FbChunk fb_holds{};                   // what the scratch holds: launch_farneback's report of the last chunk; the deferred re-run and avd_debug_fetch "flowK" read it
     DevBuf<float> d_mag;                  // [n-1][320*320] |flow| of the full-resolution level (written by the fast level kernel, or by k_mag in exact mode)
-    int mag_valid = 0;                    // d_mag holds the magnitudes of the chunk being processed
     DevBuf<int> d_fbflags;                // [n-1] ill-posedness flags of the fast level kernels (bit k: level k met the solver's criterion, bit 4 + k: the border-sign criterion); such pairs are re-run exactly
     DevBuf<int> d_pairdiff;               // [n-1][20] "frame p differs from frame p + 1" per tile of the pyramid kernel's 160-px scale (all zero: bit-identical frames)
     DevBuf<int> d_rlist;                  // exact re-run: the flagged pairs of a chunk, compacted by the host
@@ -197,7 +212,6 @@ struct Workspace {
     DevBuf<double> d_vs;                  // [n-1] x 64x16 tiles of D = vsum(x+7)-vsum(x-8), double
     DevBuf<double> d_vs0;                 // [n-1][5][320][8]  vsum columns 0..6 (row init)
     DevBuf<float> d_flow_il;              // [n-1][320*320][2] interleaved (cv2 layout); allocated when a caller first asks for the dense flow
-    int no_flow_il = 0;                   // the chunks being enqueued hand no dense flow to the host: nothing is interleaved
     DevBuf<float> d_stats;                // [n-1][2] mean, var
     DevBuf<avd_frame_record> d_rec;       // [n]
     PinBuf<avd_frame_record> h_rec;       // [n] pinned landing buffer of the asynchronous copy-out
@@ -236,7 +250,7 @@ struct avd_ctx {
     avd_frame_record* pending_out = nullptr;   // caller buffer the pinned records are handed to in avd_synchronize
     int pending_n = 0;
     hipEvent_t stage_ev[5] = {};
-    hipEvent_t kern_ev[12] = {};           // profiling: stage_mark events around the 320-px level's blur launches of a chunk
+    hipEvent_t kern_ev[12] = {};           // profiling: level320_mark events around the 320-px level's blur launches of a chunk
     int kern_ev_used = 0;
     int profiling = 0;
     int stage_marks = 0;                       // stage events recorded by the call in flight (5 = all of them)
@@ -265,8 +279,7 @@ struct avd_ctx {
     int fb_wide160 = 2;             // fast mode: the 160-px level as one three-block strip per pair (1: fewer CU-microseconds, throughput) or as two strips (0: shorter launches, latency);
                                     // 2 (default) = by what is in flight when the call is enqueued: one strip if another context of the process holds an undrained call, two if this clip is alone; AVD_FB_WIDE160 / avd_set_option
     int counted_in_flight = 0;      // this context's enqueued call is counted in avd_calls_in_flight()
-    int fb_wide160_used = 0;        // the shape of the 160-px launches, decided ONCE per call when it is enqueued (run_flow_chunks) and read by the schedule and by
-                                    // every launch of the call (read-only option "fb_wide160_used")
+    int fb_wide160_used = 0;        // read-only option "fb_wide160_used": FlowCall::wide160 of the last fast-mode call, written when it is enqueued; no launcher reads it
     int gemm_waves = 8;             // patch-embed GEMM: waves per workgroup (8: 8 x 4 MFMA tiles per wave, 16: 4 x 4; measured no faster), the same 256 x 256 tile; AVD_GEMM_WAVES / avd_set_option
     int cnn_tap = 0;                // CNN extension, tests: the forward copies one intermediate aside for avd_debug_fetch "cnn_tap" (0 = off, 1 = bordered input image,
                                     // 2 + i = output of convolution i, 55 = max pool, 56 = pooled features); one pass, no timing repetitions
@@ -274,7 +287,6 @@ struct avd_ctx {
     int cnn_plan_valid = 0;         // 0 until the first forward
     int audio_plan[4] = {};         // nwin, win, last, nfull (windows on the 80 x 100 path) of the last avd_audio_features (debug buffer "audio_plan")
     int audio_plan_valid = 0;       // 0 until the first one, and while a later one has not enqueued all its launches
-    int cnn_shape = 0;              // the shape the last convolution launch took
     int cnn_chunk = 128;            // CNN extension: frames per forward pass (activation scratch = 4 x 1.6 MB per frame)
     int cnn_fuse = 2;               // CNN extension: a block's 3x3 and expanding 1x1 in one launch (stages 1, 2): 2 = with the 3x3's input slab in LDS in the stride-1 blocks (k_slab3_expand), 1 = gathering kernels only, 0 = layer by layer
     int fb_fused = 0xF;             // bit k: pyramid level k runs the fused kernel (avd_fbfused.hip) instead of the two-kernel path (avd_fbtwo.hip)
@@ -282,7 +294,7 @@ struct avd_ctx {
                                     // 160-px flow itself (no k_flow_up<320>), 2 the 160- / 80-px levels do so in a prologue, 4 the 80- / 40-px levels run their three
                                     // iterations in one launch
     int fb_fold_up160 = 1;          // fast mode (no effect on results; AVD_FB_FOLD_UP160 / avd_set_option): the 160-px level's first launch resizes the 80-px flow
-                                    // itself in its chain wave, as bit 1 of fb_fold_up does at 320 px (no k_flow_up<160>) -- in the one-strip shape only (fb_wide160_used),
+                                    // itself in its chain wave, as bit 1 of fb_fold_up does at 320 px (no k_flow_up<160>) -- in the one-strip shape only (FlowCall::wide160),
                                     // whose wave mix is the 320-px strip's; with two strips per pair the chain wave is the pole and fb_fold_up decides.  An option of
                                     // its own, not a fourth bit of fb_fold_up: that option is a 3-bit mask with default 5 by its published contract (avd.h, ABI 3)
     int fb_mode = 1;                // 1 = fast level kernel (avd_fbfast.hip: literal vertical chain, direct horizontal window sums; flow within
@@ -290,8 +302,8 @@ struct avd_ctx {
     int fb_rerun = 1;               // fast mode: pairs the level kernels flag as ill-posed are re-run by the exact kernels (launch_farneback_rerun); 0 = A/B, tests
     int fb_rerun_fused = 0xC;       // exact re-run of FEW pairs (<= kRerunTwoKernelMax): level mask of the fused kernel (bit 3 = 40 px must be set), the other levels run the two-kernel path
     int last_rerun = 0;             // pairs re-run by the last drained call
-    // the last Farneback chunk of an asynchronous call, whose flags the host has not seen yet (impl_synchronize re-runs its flagged pairs)
-    struct { int active = 0, p0 = 0, np = 0, fa = 0; const int* clipstart = nullptr; } tail;
+    // the last Farneback chunk of an asynchronous call, whose flags the host has not seen yet (impl_synchronize re-runs its flagged pairs, as `call` says)
+    struct { int active = 0, p0 = 0, np = 0, fa = 0; const int* clipstart = nullptr; FlowCall call{}; } tail;
     // A thread that waits in avd_synchronize settles the tails of OTHER contexts whose fast pass has finished meanwhile (avd_capi.hip, tail_help_others):
     // one host thread driving several contexts (avd_hip.ClipsInFlight, bench.py) would otherwise start each clip's re-run only when it reaches that clip.
     std::recursive_mutex api_mu;    // held by every entry point that takes this context; helpers only try_lock it
@@ -315,7 +327,7 @@ inline void kmark(avd_ctx* ctx, int id)
 
 // profiling only: one of the twelve events around the 320-px level's blur launches (avd_stage_ms 4 and 5 are sums over alternate intervals,
 // impl_synchronize); `on` = the caller's launch is one of those (level 0 of a chunk's first pass, never the exact re-run)
-inline void stage_mark(avd_ctx* ctx, bool on) { if (on && ctx->profiling && ctx->kern_ev_used < 12) (void)hipEventRecord(ctx->kern_ev[ctx->kern_ev_used++], ctx->stream); }
+inline void level320_mark(avd_ctx* ctx, bool on) { if (on && ctx->profiling && ctx->kern_ev_used < 12) (void)hipEventRecord(ctx->kern_ev[ctx->kern_ev_used++], ctx->stream); }
 
 template <typename T, bool kPinned>
 int Buf<T, kPinned>::reserve(avd_ctx* ctx, size_t count)
@@ -333,22 +345,20 @@ int Buf<T, kPinned>::reserve(avd_ctx* ctx, size_t count)
 }
 
 // ---- stage launchers (each enqueues on ctx->stream) --------------------------------
-int avd_ws_geometry(avd_ctx* ctx, int h, int w);                       // make (h, w) the current geometry (cached tables)
-int avd_ws_reserve_frames(avd_ctx* ctx, int n, size_t rowbuf_elems, size_t lappart_elems);   // grow-only per-frame buffers
-int avd_ws_reserve(avd_ctx* ctx, int n, int h, int w);                 // both, for one clip at offset 0
-int avd_ws_reserve_fb(avd_ctx* ctx, int n);
 // the clip's frames, resident at d_in (BGR) or d_in / d_uv (NV12: Y rows at d_in + f*frame_stride + y*row_stride, chroma rows at
 // d_uv + f*uv_frame_stride + (y/2)*uv_row_stride) or d_in / d_uv / d_v (I420: d_uv is the U plane, both chroma planes with the uv strides),
 // or d_in alone (the packed RGB layouts, as BGR with 3 or 4 bytes per pixel) or d_in / d_uv / d_v (RGBP: R, G, B, all with the clip's row_stride / frame_stride),
-// into the clip's slice of the per-frame buffers; which it is says clip.format; the clip's geometry is current
+// into the clip's slice of the per-frame buffers, with the clip's geometry (slot); which it is says clip.format
 // list (null: strided): the frames come from a device table of plane pointers (avd_frame_list) -- d_in / d_uv / d_v are then the addresses of the
 // table's per-plane arrays, n entries each, and the clip's frame strides are unused
 struct FrameTable { bool aligned; };      // aligned: every frame of the list allows the 16-byte fills (list_vec_eligible)
-int launch_preprocess(avd_ctx* ctx, const IngestClip& clip, const uint8_t* d_in, const uint8_t* d_uv, const uint8_t* d_v, const FrameTable* list = nullptr);
-int launch_hash(avd_ctx* ctx, int n);
+int launch_preprocess(avd_ctx* ctx, const ClipSlot& slot, const IngestClip& clip, const uint8_t* d_in, const uint8_t* d_uv, const uint8_t* d_v,
+                      const FrameTable* list = nullptr);
+int launch_hash(avd_ctx* ctx, const ClipSlot& slot, int n);       // the clip's n frames
 int avd_calls_in_flight();      // avd_capi.hip: contexts of this process holding an enqueued, undrained avd_analyze_* call
-int launch_farneback(avd_ctx* ctx, const uint8_t* d_small, int n);    // all pairs of n resident frames, into the Farneback scratch
-int launch_flow_stats(avd_ctx* ctx, int n);
+// all pairs of n resident frames, into the Farneback scratch; *left (and ws.fb_holds) = what it holds then
+int launch_farneback(avd_ctx* ctx, const FlowCall& call, const uint8_t* d_small, int n, FbChunk* left);
+int launch_flow_stats(avd_ctx* ctx, const FlowCall& call, const FbChunk& chunk, int n);
 // avd_vit.hip (extension): patchify + bf16 MFMA GEMM; all pointers device
 int launch_vit_patch_embed(avd_ctx* ctx, const uint8_t* d_bgr, int n, int h, int w, int64_t row_stride, int64_t frame_stride,
                            const uint16_t* d_wt, const float* d_bias, void* d_tokens, int tokens_bf16, uint16_t* d_patches);
@@ -386,7 +396,7 @@ inline bool fb_dispatch_width(int w, F&& f)
 }
 // avd_fbtwo.hip: ONE blur iteration of one pyramid level as two kernels that exchange the double intermediate through `s`; which shape runs
 // (k_uvp<W, 12> + k_hscan_lat, k_uvp<W, 4>, k_uv) follows w, np and plist.  plist (may be null): the launch works on pairs plist[0 .. np), the
-// intermediate is indexed by position in the list.  marks: a 320-px iteration records four stage_mark events (on ctx->stream, which `stream` is)
+// intermediate is indexed by position in the list.  marks: a 320-px iteration records four level320_mark events (on ctx->stream, which `stream` is)
 struct FbTwoScratch { double *vs, *vs0; };            // exact mode: {ws.d_vs, ws.d_vs0}; the re-run: {ws.d_vs_rerun, ws.d_vs0_rerun}
 struct FbTwoScratchSize { size_t vs, vs0; };          // doubles
 FbTwoScratchSize fb_two_scratch_size(size_t np);      // what np pairs need at any level
@@ -397,10 +407,11 @@ int launch_fb_two(avd_ctx* ctx, hipStream_t stream, int w, const float* R, float
 //   level     flow_in, a buffer of this level (every width)
 //   zero      like level, but at 40 px (the coarsest level) the flow is taken as zero whatever flow_in holds: no clearing launch
 //   chain     flow_in = the COARSER level's final flow [pair][2][w/2][w/2], resized by the chain wave on the fly (320 px, and 160 px in the one-strip
-//             shape: ctx->fb_wide160_used; 1 iteration)
+//             shape: wide160; 1 iteration)
 //   prologue  the same, resized by the whole workgroup into flow_tmp first (160 / 80 px with 1 iteration, 80 px with 3)
 enum class FbFlowFrom { level, zero, chain, prologue };   // the result is in flow_out (3 iterations: flow_tmp is the second buffer); nothing is updated in place
 struct FbFastLaunch {
+    bool wide160;                                // the 160-px shape of the call (FlowCall::wide160); no other level reads it
     int iterations; FbFlowFrom from; const float* flow_in; float *flow_out, *flow_tmp;
     float* mag_out;                              // 320-px level, last iteration (else null): float[pair][320][320] receives |flow|
     int* flags; const int* pairdiff;             // may be null, see avd_fbfast.hip
@@ -408,7 +419,7 @@ struct FbFastLaunch {
 int launch_fb_fast(avd_ctx* ctx, hipStream_t stream, int w, const float* R, const FbFastLaunch& L, int np);
 // avd_farneback.hip: exact re-run of the m flagged pairs h_list[0 .. m) (pair indices inside the chunk the workspace holds; h_list pinned); np_chunk = its pairs
 constexpr int kRerunTwoKernelMax = 32;
-int launch_farneback_rerun(avd_ctx* ctx, const int* h_list, int m, int np_chunk);
+int launch_farneback_rerun(avd_ctx* ctx, const FlowCall& call, const int* h_list, int m, int np_chunk);
 // avd_norm.hip (extensions): LayerNorm over rows of 256..2048 values, softmax over rows of logits; device pointers
 int launch_layernorm(avd_ctx* ctx, const void* d_x, void* d_y, int bf16, long long rows, int cols, const float* d_gamma, const float* d_beta, float eps);
 int launch_softmax(avd_ctx* ctx, const float* d_x, float* d_y, long long rows, int cols);

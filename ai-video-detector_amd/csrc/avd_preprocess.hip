@@ -1420,10 +1420,11 @@ static constexpr auto ingest_kernel()
 
 // list (null: a strided clip): the clip's frames come from a device table of plane pointers -- d_in / d_uv / d_v are then the addresses of the
 // table's per-plane arrays (n entries each), and list->aligned says whether every frame allows the 16-byte fills (list_vec_eligible).
-int launch_preprocess(avd_ctx* ctx, const IngestClip& clip, const uint8_t* d_in, const uint8_t* d_uv, const uint8_t* d_v, const FrameTable* list)
+int launch_preprocess(avd_ctx* ctx, const ClipSlot& slot, const IngestClip& clip, const uint8_t* d_in, const uint8_t* d_uv, const uint8_t* d_v,
+                      const FrameTable* list)
 {
     Workspace& ws = ctx->ws;
-    PreParams P = ws.pre;
+    PreParams P = slot.pre;
     P.row_stride = clip.row_stride;
     P.frame_stride = clip.frame_stride;
     const int n = clip.n;
@@ -1470,8 +1471,8 @@ int launch_preprocess(avd_ctx* ctx, const IngestClip& clip, const uint8_t* d_in,
         dispatch_bool(list != nullptr, [&](auto listed) {
             constexpr Frames FR = decltype(listed)::value ? Frames::listed : Frames::strided;
             auto kernel = ingest_kernel<POL, FR, decltype(extra)...>();
-            hipLaunchKernelGGL(kernel, dim3(grid), dim3(kThreads), lds, ctx->stream, d_in, extra..., n, P, ws.d_small + (size_t)ws.f0 * AVD_NPIX,
-                               ws.d_rowbuf + ws.rowbuf_off, ws.d_lap_part + ws.lappart_off);
+            hipLaunchKernelGGL(kernel, dim3(grid), dim3(kThreads), lds, ctx->stream, d_in, extra..., n, P, ws.d_small + (size_t)slot.f0 * AVD_NPIX,
+                               ws.d_rowbuf + slot.rowbuf_off, ws.d_lap_part + slot.lappart_off);
         });
     };
     bool built = true;                                 // false: the band plan's NI has no staged kernel
@@ -1520,13 +1521,13 @@ int launch_preprocess(avd_ctx* ctx, const IngestClip& clip, const uint8_t* d_in,
 }
 
 // (the Hamming distances between consecutive frames are formed from these bits by k_records of the analyze entries)
-int launch_hash(avd_ctx* ctx, int n)
+int launch_hash(avd_ctx* ctx, const ClipSlot& slot, int n)
 {
     Workspace& ws = ctx->ws;
-    // the clip's slice of the call's buffers: frame ws.f0 onwards
-    const size_t f0 = (size_t)ws.f0;
-    hipLaunchKernelGGL(k_hash, dim3(n), dim3(1024), 0, ctx->stream, ws.d_rowbuf + ws.rowbuf_off, ws.hsh, ws.d_area + f0 * 1024,
-                       ws.d_hash + f0 * 1024, (const long long*)(ws.d_lap_part + ws.lappart_off), ws.pre.nbands, kThreads / 64,
+    // the clip's slice of the call's buffers: frame slot.f0 onwards
+    const size_t f0 = (size_t)slot.f0;
+    hipLaunchKernelGGL(k_hash, dim3(n), dim3(1024), 0, ctx->stream, ws.d_rowbuf + slot.rowbuf_off, slot.hsh, ws.d_area + f0 * 1024,
+                       ws.d_hash + f0 * 1024, (const long long*)(ws.d_lap_part + slot.lappart_off), slot.pre.nbands, kThreads / 64,
                        ws.d_lap + 2 * f0);
     HIP_TRY(ctx, hipGetLastError());
     return 0;
