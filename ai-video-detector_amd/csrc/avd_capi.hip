@@ -227,12 +227,14 @@ static int rerun_flagged(avd_ctx* ctx, const FlowCall& call, const int* h_flags,
 
 __global__ void k_wake() {}
 
-// the records of frames fa .. p0 + np: the chunk of pairs p0 .. p0 + np - 1 is in the Farneback scratch.  np == 0: a call of one frame, which has no pair
-static void launch_records(avd_ctx* ctx, int p0, int np, int fa, const int* clipstart)
+// the records of frames fa .. p0 + np: the chunk of pairs p0 .. p0 + np - 1 is in the Farneback scratch.  np == 0: a call of one frame, which has no pair.
+// again: the deferred re-run assembles its chunk's records a second time; that launch stays in the re-run's region (AVD_K_RERUN), it is not the
+// call's record kernel
+static void launch_records(avd_ctx* ctx, int p0, int np, int fa, const int* clipstart, bool again = false)
 {
     Workspace& ws = ctx->ws;
     const int with_flow = np > 0;
-    kmark(ctx, AVD_K_RECORDS);
+    if (!again) kmark(ctx, AVD_K_RECORDS);
     hipLaunchKernelGGL(k_records, dim3(p0 + np + 1 - fa), dim3(256), 0, ctx->stream, (const unsigned long long*)ws.d_lap,
                        (const uint8_t*)ws.d_hash, (const float*)(with_flow ? ws.d_stats.p : nullptr),
                        (const int*)(with_flow && ctx->fb_mode == 1 && ctx->fb_rerun ? ws.d_fbflags.p : nullptr), p0, ws.d_rec, fa, clipstart, with_flow);
@@ -318,11 +320,14 @@ static int stage_input(avd_ctx* ctx, const uint8_t* src, int mem, size_t bytes, 
     return 0;
 }
 
-static void stage_mark(avd_ctx* ctx, int i)
+// -> the event, for the kernel region that begins at the same place (kmark's `shared`); null with profiling off or when it was not recorded
+static hipEvent_t stage_mark(avd_ctx* ctx, int i)
 {
-    if (!ctx->profiling) return;
+    if (!ctx->profiling) return nullptr;
     if (i == 0) ctx->stage_marks = 0;
-    if (hipEventRecord(ctx->stage_ev[i], ctx->stream) == hipSuccess) ctx->stage_marks++;
+    if (hipEventRecord(ctx->stage_ev[i], ctx->stream) != hipSuccess) return nullptr;
+    ctx->stage_marks++;
+    return ctx->stage_ev[i];
 }
 
 // contexts of this process (any device) that hold an enqueued, not yet drained avd_analyze_* call: what "fb_wide160" = 2 decides by
@@ -368,7 +373,7 @@ static int tail_settle(avd_ctx* ctx)
     const int m = rerun_flagged(ctx, ctx->tail.call, &ws.h_rec[p0 + 1].reserved, (int)(sizeof(avd_frame_record) / sizeof(int)), np);
     if (m < 0) return m;
     if (m > 0) {
-        launch_records(ctx, p0, np, fa, ctx->tail.clipstart);
+        launch_records(ctx, p0, np, fa, ctx->tail.clipstart, true);
         HIP_TRY(ctx, hipMemcpyAsync(ws.h_rec + fa, ws.d_rec + fa, sizeof(avd_frame_record) * (size_t)(p0 + np + 1 - fa), hipMemcpyDeviceToHost, ctx->stream));
         if (ctx->profiling && ctx->kmark_used > 0) kmark(ctx, AVD_K_COUNT);     // close the re-run's region
     }
@@ -671,11 +676,14 @@ static int impl_farneback_pairs(avd_ctx* ctx, const uint8_t* small320, int mem, 
     const uint8_t* d_small = nullptr;
     if (int e = stage_input(ctx, small320, mem, (size_t)n * AVD_NPIX, &d_small)) return e;
     ctx->last_rerun = 0;
-    ctx->kmark_used = 0;
+    kmark_reset(ctx);
     std::vector<float> fm_tmp;
     if (!flow_mean && !flow_var && !flow_out) { fm_tmp.resize((size_t)n - 1); flow_mean = fm_tmp.data(); }   // the chunks are drained either way
     if (int e = run_flow_chunks(ctx, d_small, n, flow_mean, flow_var, flow_out, false)) return e;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    // with profiling on the launchers have recorded marks, but avd_kernel_ms reports avd_analyze_* calls only: these feed no figure (an error
+    // return above leaves them behind unclosed, which impl_synchronize does not read either)
+    kmark_reset(ctx);
     ctx->last_n = std::min(n, ctx->ws.fb_cap + 1);
     ctx->rec_n = 0;
     return AVD_OK;
@@ -726,12 +734,16 @@ static int impl_analyze_async(avd_ctx* ctx, const IngestClip* clips, int nclips,
     if (int e = ws.d_stage.reserve(ctx, stage_bytes)) return e;
     if (int e = reserve_lists(ctx, lists)) return e;
     // pass 2: per clip, stage (host input) -> fused full-resolution kernel -> hash, in the clip's slot
-    ctx->kmark_used = 0;
+    kmark_reset(ctx);
     ctx->ingest.stage_bytes = 0;
     ctx->ingest.stage_copies = 0;
     // profiling only: an empty launch in front of the first mark, so that the first region is the first kernel and not the queue's wake-up from idle as well
     if (ctx->profiling) hipLaunchKernelGGL(k_wake, dim3(1), dim3(64), 0, ctx->stream);
-    stage_mark(ctx, 0);
+    // A stage boundary and the kernel region that begins there are ONE event (kmark's `shared`), here and below: stages 0 .. 3 and the regions
+    // recorded at enqueue are two partitions of the same interval.  The first region is the first clip's ingest, the upload of the list table
+    // (host input staged for it) included.
+    kmark(ctx, AVD_K_PREPROCESS, stage_mark(ctx, 0));
+    bool first_clip = true;
     if (int e = upload_lists(ctx, clips, nclips, lists)) return e;
     for (int c = 0; c < nclips; c++) {
         const IngestClip& k = clips[c];
@@ -742,19 +754,19 @@ static int impl_analyze_async(avd_ctx* ctx, const IngestClip* clips, int nclips,
         if (int e = avd_ws_geometry(ctx, k.disp_h(), k.disp_w(), slot)) return e;
         ws.h_clipstart[slot.f0] = 1;
         for (int i = 1; i < k.n; i++) ws.h_clipstart[slot.f0 + i] = 0;
-        kmark(ctx, AVD_K_PREPROCESS);
+        if (!first_clip) kmark(ctx, AVD_K_PREPROCESS);
+        first_clip = false;
         if (int e = preprocess_clip(ctx, slot, k, stage_at[c], lists, c)) return e;
         kmark(ctx, AVD_K_HASH);
         if (int e = launch_hash(ctx, slot, k.n)) return e;
     }
-    kmark(ctx, AVD_K_OTHER);
-    stage_mark(ctx, 1);
+    kmark(ctx, AVD_K_OTHER, stage_mark(ctx, 1));
     const int* clipstart = nullptr;                        // one clip: frame 0 is the only one without a predecessor
     if (nclips > 1) {
         HIP_TRY(ctx, hipMemcpyAsync(ws.d_clipstart, ws.h_clipstart, sizeof(int) * n, hipMemcpyHostToDevice, ctx->stream));
         clipstart = ws.d_clipstart;
     }
-    stage_mark(ctx, 2);
+    kmark(ctx, n < 2 ? AVD_K_RECORDS : AVD_K_PYRAMID, stage_mark(ctx, 2));     // stage 2 opens with that kernel; its launcher marks the same id again
     // from here on an error return must not leave a tail behind: a later avd_synchronize would settle it from a stale h_rec
     struct TailOnError {
         avd_ctx* c;
@@ -763,8 +775,7 @@ static int impl_analyze_async(avd_ctx* ctx, const IngestClip* clips, int nclips,
     } tail_on_error{ctx};
     if (n < 2) launch_records(ctx, 0, 0, 0, clipstart);     // one frame: no pair, no flow
     else if (int e = run_flow_chunks(ctx, ws.d_small, n, nullptr, nullptr, nullptr, true, clipstart)) return e;
-    kmark(ctx, AVD_K_OTHER);
-    stage_mark(ctx, 3);
+    kmark(ctx, AVD_K_OTHER, stage_mark(ctx, 3));
     // into PINNED memory: a device-to-host copy into the caller's pageable buffer would block this thread until
     // the whole call is done and it would not be asynchronous at all; avd_synchronize hands the records over
     HIP_TRY(ctx, hipMemcpyAsync(ws.h_rec, ws.d_rec, sizeof(avd_frame_record) * n, hipMemcpyDeviceToHost, ctx->stream));
@@ -772,8 +783,7 @@ static int impl_analyze_async(avd_ctx* ctx, const IngestClip* clips, int nclips,
     ctx->pending_out = records; ctx->pending_n = n;
     if (ctx->tail.active) tail_register(ctx);              // from here on a waiting thread may settle this call's tail
     if (!ctx->counted_in_flight) { ctx->counted_in_flight = 1; g_calls_in_flight.fetch_add(1, std::memory_order_relaxed); }
-    kmark(ctx, AVD_K_COUNT);                               // end of the last region
-    stage_mark(ctx, 4);
+    kmark(ctx, AVD_K_COUNT, stage_mark(ctx, 4));           // end of the last region
     ctx->last_n = n;
     ctx->rec_n = n;
     return AVD_OK;
@@ -820,24 +830,27 @@ static int impl_synchronize(avd_ctx* ctx)
         for (int i = 0; i < ctx->pending_n; i++) ctx->last_rerun += ctx->ws.h_rec[i].reserved != 0;
         ctx->pending_out = nullptr; ctx->pending_n = 0;
     }
-    if (ctx->profiling && ctx->kmark_used > 1) {
+    // only a mark list that an avd_analyze_* call closed (its last mark is AVD_K_COUNT: impl_analyze_async, tail_settle) is a call's timeline;
+    // anything else -- marks of a call that failed half way -- would drop its last region and replace the figures of the last drained call
+    if (ctx->profiling && ctx->kmark_used > 1 && ctx->kmark_id[ctx->kmark_used - 1] == AVD_K_COUNT) {
         for (float& v : ctx->kernel_ms) v = 0.f;
         for (int i = 0; i + 1 < ctx->kmark_used; i++) {
             float ms = 0.f;
-            if (ctx->kmark_id[i] < AVD_K_COUNT && hipEventElapsedTime(&ms, ctx->kmark_ev[i], ctx->kmark_ev[i + 1]) == hipSuccess)
+            if (ctx->kmark_id[i] < AVD_K_COUNT && hipEventElapsedTime(&ms, ctx->kmark_at[i], ctx->kmark_at[i + 1]) == hipSuccess)
                 ctx->kernel_ms[ctx->kmark_id[i]] += ms;
         }
         ctx->kmark_incomplete = ctx->kmark_overflow;
     }
-    ctx->kmark_used = 0;
-    ctx->kmark_overflow = 0;
+    kmark_reset(ctx);
     if (ctx->profiling && ctx->stage_marks == 5) {
-        // stages: 0 preprocess, 1 hash+hamming+records, 2 farneback+stats (3 reported as copy-out)
+        // stages as in include/avd.h (avd_set_profiling): 0 staging copies + preprocess + aHash of every clip, 1 upload of the clip-start table,
+        // 2 Farneback + flow statistics + the record kernel, 3 records copy-out
         for (int i = 0; i < 4; i++) {
             float ms = 0.f;
             if (hipEventElapsedTime(&ms, ctx->stage_ev[i], ctx->stage_ev[i + 1]) == hipSuccess) ctx->stage_ms[i] = ms;
         }
-        // 4 / 5: mean duration of one k_uv<320> / k_hscan<320> launch (the last chunk)
+        // 4 / 5, of the call's last chunk.  One event pair (fast mode, and the fused 320-px kernel of exact mode): 4 = the 320-px level, 5 = 0.
+        // Twelve events (the two-kernel path of exact mode): 4 / 5 = mean duration of one k_uv<320> / k_hscan<320> launch
         float sum[2] = {0.f, 0.f}; int cnt[2] = {0, 0};
         for (int i = 0; i + 1 < ctx->kern_ev_used; i += 2) {     // level320_mark events of the drained call
             float ms = 0.f;

@@ -257,6 +257,7 @@ struct avd_ctx {
     // per-kernel profiling (avd_kernel_ms): an event in front of every kernel (group) of the path, labelled with the avd_kernel_id of the
     // region that starts there; elapsed times between consecutive events are summed per id when the call is drained
     hipEvent_t kmark_ev[96] = {};
+    hipEvent_t kmark_at[96] = {};              // the event that opens region i: kmark_ev[i], or the stage event recorded at the same place (kmark's `shared`)
     int kmark_id[96] = {};
     int kmark_used = 0;
     int kmark_incomplete = 0;                  // the same for the call whose times kernel_ms holds
@@ -313,17 +314,24 @@ struct avd_ctx {
     int tail_help = 1;              // option "tail_help": 0 = never settle other contexts' tails, wait with hipStreamSynchronize (A/B, tests)
 };
 
-// profiling only (avd_set_profiling): the region that starts here on the context's stream is kernel `id`
-inline void kmark(avd_ctx* ctx, int id)
+// profiling only (avd_set_profiling): the region that starts here on the context's stream is kernel `id` (AVD_K_COUNT: nobody's -- the end of
+// the call).  shared: an event that was recorded at this very place (a stage event of avd_stage_ms); the region is bounded by it instead of by
+// an event of its own, so that the stage and the region begin at ONE timestamp and neither decomposition of the call contains a gap between
+// two event packets that the other lacks.
+inline void kmark(avd_ctx* ctx, int id, hipEvent_t shared = nullptr)
 {
     // the last slot is kept for the closing mark (AVD_K_COUNT): a call with more regions than slots loses its LATER regions' split (they are
     // accounted to the region of mark 94), never the end of the timeline; kmark_overflow says so (avd_kernel_ms fails then)
     if (!ctx->profiling) return;
     if (ctx->kmark_used >= 96 || (ctx->kmark_used == 95 && id != AVD_K_COUNT)) { ctx->kmark_overflow = 1; return; }
+    if (shared) { ctx->kmark_at[ctx->kmark_used] = shared; ctx->kmark_id[ctx->kmark_used++] = id; return; }
     hipEvent_t& e = ctx->kmark_ev[ctx->kmark_used];
     if (!e && hipEventCreate(&e) != hipSuccess) { e = nullptr; return; }
-    if (hipEventRecord(e, ctx->stream) == hipSuccess) ctx->kmark_id[ctx->kmark_used++] = id;
+    if (hipEventRecord(e, ctx->stream) == hipSuccess) { ctx->kmark_at[ctx->kmark_used] = e; ctx->kmark_id[ctx->kmark_used++] = id; }
 }
+
+// the marks of a call begin: whatever an earlier call left behind -- marks it never closed, an overflow nobody drained -- is not this call's
+inline void kmark_reset(avd_ctx* ctx) { ctx->kmark_used = 0; ctx->kmark_overflow = 0; }
 
 // profiling only: one of the twelve events around the 320-px level's blur launches (avd_stage_ms 4 and 5 are sums over alternate intervals,
 // impl_synchronize); `on` = the caller's launch is one of those (level 0 of a chunk's first pass, never the exact re-run)

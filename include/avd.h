@@ -448,10 +448,18 @@ int avd_timer_stop(avd_ctx* ctx, float* elapsed_ms);
  * call when profiling was enabled with avd_set_profiling(ctx, 1): stage 0 = staging copies, fused
  * preprocess kernel (+ the 2 KB moment memset) and aHash kernel of every clip of the call, 1 = upload of the clip-start
  * table (calls with several clips; otherwise empty), 2 = Farneback (pyramid .. flow) + flow statistics + the record kernel
- * (Hamming distances, record assembly), 3 = records copy-out; 4 = duration of the fused level kernel at
- * 320x320 (all iterations of pyramid level 0 in one launch, events around the launch; with the two-kernel path selected
- * by AVD_FB_FUSED: mean duration of one k_uv launch), 5 = mean duration of one k_hscan<320> launch (two-kernel path only,
- * otherwise 0). */
+ * (Hamming distances, record assembly), 3 = records copy-out; 4 = the 320-px pyramid level of the call's LAST Farneback chunk
+ * (a call of more than 513 frames has several), between events of its own inside stage 2 -- by mode:
+ *   fb_mode 1 (fast)                      the level's THREE launches, one per blur iteration, between one pair of events;
+ *   fb_mode 0, bit 0 of "fb_fused" set    the fused level kernel: all three iterations in ONE launch, events around it;
+ *   fb_mode 0, bit 0 of "fb_fused" clear  the two-kernel path: the MEAN duration of one k_uv launch (three of them, one per iteration);
+ * 5 = the mean duration of one k_hscan<320> launch in the last of these three cases, and 0 in the other two.
+ * The LAST call is the last DRAINED one: an asynchronous call changes nothing before avd_synchronize.
+ * Stages 0 .. 3 tile the call: each ends at the event the next begins at.  The kernel regions of avd_kernel_ms that were recorded when the call
+ * was enqueued tile the same interval, and the region that opens a stage is bounded by the stage's OWN event: the regions inside a stage sum
+ * to that stage (0: AVD_K_PREPROCESS + AVD_K_HASH; 1 + 3: AVD_K_OTHER; 2: the Farneback, statistics and record ids), up to float rounding.
+ * All six are 0 until a profiled call has been drained, and keep the values of the last such call: a call made with profiling off, or any
+ * other entry point, leaves them alone. */
 int avd_set_profiling(avd_ctx* ctx, int enable);
 /* Tuning / test switches.  "fb_mode": 1 (default; environment AVD_FB_MODE=fast) = the fast Farneback level kernel
  * (csrc/avd_fbfast.hip: a pair is spread over several workgroups; cv2's vertical running sums are kept literally, the
@@ -513,14 +521,19 @@ int avd_stage_ms(avd_ctx* ctx, int stage, float* ms);
 /* Per-kernel device time (ms) of the LAST drained avd_analyze_* call with profiling on: HIP events on the context's stream in
  * front of every kernel (group) of the path; a level's figure is the sum of its launches (fast mode: three, one per blur
  * iteration).  bench.py's roofline.kernels is built from these, with clips run alone.  A call with more kernel regions than the library
- * records (96: ~40 clips in one batch) makes avd_kernel_ms fail rather than report partial sums. */
+ * records (96: ~40 clips in one batch) makes avd_kernel_ms fail rather than report partial sums -- for THAT call: the next profiled call
+ * reports normally.  Only avd_analyze_* calls count: avd_farneback_pairs, avd_preprocess_* and the extensions run the same launchers but
+ * change no figure, nor does an avd_synchronize with nothing pending.  An id whose kernel the call did not launch is exactly 0 (the
+ * k_flow_up ids a fold option absorbs, AVD_K_RERUN with nothing flagged, every Farneback id of a one-frame call). */
 enum avd_kernel_id {
     AVD_K_PREPROCESS = 0,  /* k_preprocess_vec / k_preprocess, whatever the layout (+ staging copies of host input) */
     AVD_K_HASH,            /* k_hash: 32 x 32 INTER_AREA cells, mean threshold, moment reduction */
     AVD_K_PYRAMID,         /* k_pyramid_all: Gaussian blur + decimation, four scales */
     AVD_K_POLYEXP,         /* k_polyexp_all: polynomial expansion, four scales */
     AVD_K_LEVEL40, AVD_K_FLOWUP80, AVD_K_LEVEL80, AVD_K_FLOWUP160, AVD_K_LEVEL160, AVD_K_FLOWUP320, AVD_K_LEVEL320,
-    AVD_K_RERUN,           /* exact re-run of the pairs the fast level kernels flagged (launched when the call is drained; 0 when none was) */
+    AVD_K_RERUN,           /* exact re-run of the pairs the fast level kernels flagged; 0 when none was.  The flagged pairs of a call's LAST chunk are re-run when
+                            * the call is drained, behind stage 3: that region holds the exact kernels, the second assembly of the chunk's records and their
+                            * second copy-out, and lies outside every stage.  Earlier chunks (calls of more than 513 frames) are re-run inside stage 2. */
     AVD_K_STATS,           /* k_stats_pair (exact mode: + k_mag) */
     AVD_K_RECORDS,         /* k_records: Hamming distances, record assembly */
     AVD_K_OTHER,           /* clip-table upload, records copy-out */
