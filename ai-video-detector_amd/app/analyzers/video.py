@@ -27,7 +27,8 @@ def _settings():
     AVD_DEVICE            HIP device index (default 0)
     AVD_CHUNK_FRAMES      sampled frames per HIP call (bounds host memory; default 64)
     AVD_SAMPLES_PER_SECOND  extension knob, 2 = the reference's hard-coded sampling (video.py:19); 8 = the dense
-                          sampling of BASELINE.json configs[3]"""
+                          sampling of BASELINE.json configs[3]
+    AVD_STREAM_CARRY      "resident": chunks continue each other through a stream slot (read in analyze)"""
     return (int(os.getenv("AVD_DEVICE", "0")), int(os.getenv("AVD_CHUNK_FRAMES", "64")),
             float(os.getenv("AVD_SAMPLES_PER_SECOND", "2")))
 
@@ -62,9 +63,12 @@ def analyze(path: str, meta: dict):
                 seen.setdefault("npix", int(hw[0]) * int(hw[1]))
                 yield fr
 
+        # AVD_STREAM_CARRY=resident: the frame between two chunks stays on the device (a stream slot of the context, include/avd.h) instead of
+        # being staged and ingested again with the next chunk; unset: the analyzer's default
+        carry = {"resident_carry": True} if os.getenv("AVD_STREAM_CARRY", "") == "resident" else {}
         # one pooled context for the duration of the request (bounded pool: api.py:133 runs this on worker threads)
         with _analyzer.default_pool().borrow(device) as ctx:
-            fa = _analyzer.FrameAnalyzer(chunk=chunk, ctx=ctx)
+            fa = _analyzer.FrameAnalyzer(chunk=chunk, ctx=ctx, **carry)
             if surface == "nv12":
                 rec = fa.records_stream_nv12(frames(), **turn)
             elif surface == "i420":

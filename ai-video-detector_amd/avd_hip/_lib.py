@@ -999,6 +999,20 @@ class Context:
         self._check(self._L.avd_get_option(self._h, name.encode(), C.byref(v)))
         return int(v.value)
 
+    # -- stream slots (include/avd.h, options "stream_slot" / "stream_reset" / "stream_frames"): calls that continue one clip ----------------
+    def stream_slot(self, slot: int = 0):
+        """Select slot 1 ... 8: every analyze_* call of ONE clip then continues the clip whose last frame the slot holds (its first record is
+        that of the pair across the call boundary) and leaves its own last frame there.  0 (default): every call starts a new clip."""
+        self.set_option("stream_slot", slot)
+
+    def stream_reset(self, slot: int = 0):
+        """Empty slot 1 ... 8, or with 0 all of them: the next call on it starts a clip."""
+        self.set_option("stream_reset", slot)
+
+    def stream_frames(self) -> int:
+        """Frames the selected slot has absorbed since it was last emptied (0: it is empty, or no slot is selected)."""
+        return self.get_option("stream_frames")
+
     def set_profiling(self, on: bool):
         self._check(self._L.avd_set_profiling(self._h, int(bool(on))))
 

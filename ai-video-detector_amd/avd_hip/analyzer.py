@@ -10,6 +10,7 @@ import logging
 
 import collections
 import contextlib
+import itertools
 import os
 import threading
 from typing import Iterable, Iterator, Optional, Tuple
@@ -141,10 +142,14 @@ class FrameAnalyzer:
     (``with default_pool().borrow(device) as ctx: FrameAnalyzer(ctx=ctx)...``), which is what the drop-in
     ``app.analyzers.video.analyze`` does per request."""
 
-    def __init__(self, device: int = 0, chunk: int = 64, ctx: Optional["_lib.Context"] = None):
+    def __init__(self, device: int = 0, chunk: int = 64, ctx: Optional["_lib.Context"] = None, slot: int = 1, resident_carry: bool = False):
+        """slot, resident_carry: the defaults of the records_stream* methods (see _stream_resident)"""
         self._own = ctx is None
         self.ctx = ctx or _lib.Context(device)
         self.chunk = max(2, int(chunk))
+        self.resident_chunk = max(1, int(chunk))      # with the carry frame on the device a chunk of ONE frame has a predecessor too
+        self.slot = int(slot)
+        self.resident_carry = bool(resident_carry)
 
     def close(self):
         if self._own and self.ctx is not None:
@@ -203,9 +208,51 @@ class FrameAnalyzer:
             out.append(records(buf, carry))
         return np.concatenate(out) if out else np.zeros(0, _lib.RECORD_DTYPE)
 
+    def _stream_resident(self, items, submit, slot: int) -> np.ndarray:
+        """The same stream with the carry frame RESIDENT: stream slot `slot` of the context (include/avd.h, option "stream_slot") keeps the last
+        frame of every chunk on the device, so no chunk carries a prepended frame -- nothing is staged, ingested or hashed twice and the
+        caller's frame is free once its chunk is drained.  submit(list of items, rec) enqueues one chunk (its records land in rec when the
+        context is drained) and returns what the library reads; the next chunk is pulled from `items` -- decoded -- while that one runs."""
+        ctx = self.ctx
+        out = []
+        ctx.stream_reset(slot)
+        ctx.stream_slot(slot)
+        try:
+            it = iter(items)
+            buf = list(itertools.islice(it, self.resident_chunk))
+            while buf:
+                rec = np.zeros(len(buf), _lib.RECORD_DTYPE)
+                keep = submit(buf, rec)                    # the chunk's arrays stay referenced (buf, keep) until it is drained
+                nxt = list(itertools.islice(it, self.resident_chunk))
+                ctx.synchronize()
+                out.append(rec)
+                del keep
+                buf = nxt
+        finally:
+            # an exception of the iterator finds a chunk in flight: buf, keep and rec are alive up to here, and it is drained first
+            try:
+                ctx.synchronize()
+            finally:
+                ctx.stream_slot(0)
+        return np.concatenate(out) if out else np.zeros(0, _lib.RECORD_DTYPE)
+
+    def _stream_list(self, items, fmt, rotate=0, full_range=False, slot=None, resident_carry=None) -> np.ndarray:
+        """records_stream* behind their argument checks: the default stream (_stream), or with resident_carry the resident one"""
+        if not (self.resident_carry if resident_carry is None else resident_carry):
+            return self._stream(items, lambda chunk: self._flush_list(chunk, fmt, rotate, full_range))
+        return self._stream_resident(items, lambda chunk, rec: self._submit_list(chunk, rec, fmt, rotate, full_range),
+                                     self.slot if slot is None else int(slot))
+
     # A chunk goes to the library as a LIST of frames (avd_frame_list): every frame is staged from where the decoder left it, nothing is
     # stacked first.  The carry frame between chunks is simply the first entry of the next list.
     def _flush_list(self, items, fmt, rotate=0, full_range=False) -> np.ndarray:
+        return self.ctx.analyze_frame_lists([(self._list_frames(items, fmt), fmt)], [rotate], [full_range])[0]
+
+    def _submit_list(self, items, rec, fmt, rotate=0, full_range=False):
+        """_flush_list without the wait: enqueue only (analyze_frame_lists_async); -> what the library reads until the context is drained"""
+        return self.ctx.analyze_frame_lists_async([(self._list_frames(items, fmt), fmt)], rec, [rotate], [full_range])[0]
+
+    def _list_frames(self, items, fmt) -> list:
         single = fmt in _lib._PACKED or fmt == _lib.AVD_FMT_RGBP          # one array per frame: interleaved [H,W,C], or channels first [3,H,W]
         lead = 1 if fmt == _lib.AVD_FMT_RGBP else 0                       # axes in front of the rows
         frames = [(np.asarray(it),) if single else tuple(np.asarray(p) for p in it) for it in items]
@@ -218,38 +265,46 @@ class FrameAnalyzer:
             frames = [tuple(np.ascontiguousarray(p) for p in f) for f in frames]
         if single:
             frames = [f[0] for f in frames]
-        return self.ctx.analyze_frame_lists([(frames, fmt)], [rotate], [full_range])[0]
+        return frames
 
-    def records_stream(self, frames: Iterable[np.ndarray], fmt: int = _lib.AVD_FMT_BGR24) -> np.ndarray:
+    # slot, resident_carry (every records_stream* method; None: the analyzer's): resident_carry keeps the frame between two chunks on the device,
+    # in stream slot `slot` of the context, instead of prepending it to the next chunk (_stream_resident); the records are the same
+    def records_stream(self, frames: Iterable[np.ndarray], fmt: int = _lib.AVD_FMT_BGR24, slot: Optional[int] = None,
+                       resident_carry: Optional[bool] = None) -> np.ndarray:
         """fmt: the layout of the frames -- AVD_FMT_BGR24 (default) or AVD_FMT_RGB24 uint8[H,W,3], AVD_FMT_BGRA32 / AVD_FMT_RGBA32 uint8[H,W,4],
         AVD_FMT_RGBP uint8[3,H,W], AVD_FMT_YUYV422 / AVD_FMT_UYVY422 uint8[H,W,2] (limited range)."""
         if fmt not in _lib._PACKED and fmt != _lib.AVD_FMT_RGBP:
             raise ValueError(f"records_stream takes one array per frame: a packed layout or AVD_FMT_RGBP, got fmt {fmt!r}")
-        return self._stream(frames, lambda items: self._flush_list(items, fmt))
+        return self._stream_list(frames, fmt, slot=slot, resident_carry=resident_carry)
 
     # -- the same for decoder surfaces: an iterable of (y uint8[H,W], uv uint8[H/2,W]) pairs ----------------
     # rotate: quarter turns clockwise from the stored pictures to the displayed one (a container's display rotation; include/avd.h, avd_picture)
     # full_range: the samples use 0 .. 255 (ffmpeg's J formats; AVD_FMT_FULL_RANGE)
-    def records_stream_nv12(self, surfaces, rotate: int = 0, full_range: bool = False) -> np.ndarray:
-        return self._stream(surfaces, lambda items: self._flush_list(items, _lib.AVD_FMT_NV12, rotate, full_range))
+    def records_stream_nv12(self, surfaces, rotate: int = 0, full_range: bool = False, slot: Optional[int] = None,
+                            resident_carry: Optional[bool] = None) -> np.ndarray:
+        return self._stream_list(surfaces, _lib.AVD_FMT_NV12, rotate, full_range, slot, resident_carry)
 
     # -- and for planar pictures (software decoders, .y4m): an iterable of (y uint8[H,W], u uint8[H/2,W/2], v uint8[H/2,W/2]) triples ----
-    def records_stream_i420(self, surfaces, rotate: int = 0, full_range: bool = False) -> np.ndarray:
-        return self._stream(surfaces, lambda items: self._flush_list(items, _lib.AVD_FMT_I420, rotate, full_range))
+    def records_stream_i420(self, surfaces, rotate: int = 0, full_range: bool = False, slot: Optional[int] = None,
+                            resident_carry: Optional[bool] = None) -> np.ndarray:
+        return self._stream_list(surfaces, _lib.AVD_FMT_I420, rotate, full_range, slot, resident_carry)
 
     # -- 4:2:2 planar pictures (MJPEG, a C422 .y4m): an iterable of (y uint8[H,W], u uint8[H,W/2], v uint8[H,W/2]) triples; H may be odd.
     # A turned 4:2:2 picture is not on the path: the library refuses rotate != 0 (include/avd.h)
-    def records_stream_i422(self, surfaces, rotate: int = 0, full_range: bool = False) -> np.ndarray:
-        return self._stream(surfaces, lambda items: self._flush_list(items, _lib.AVD_FMT_I422, rotate, full_range))
+    def records_stream_i422(self, surfaces, rotate: int = 0, full_range: bool = False, slot: Optional[int] = None,
+                            resident_carry: Optional[bool] = None) -> np.ndarray:
+        return self._stream_list(surfaces, _lib.AVD_FMT_I422, rotate, full_range, slot, resident_carry)
 
     # -- 10-bit 4:2:0 in 16-bit words (include/avd.h): P010 surfaces (VCN / rocDecode), an iterable of (y uint16[H,W], uv uint16[H/2,W]) pairs with
     # the 10 bits in the high bits; yuv420p10le pictures (libavcodec), (y uint16[H,W], u uint16[H/2,W/2], v likewise) triples with them in the low
     # bits.  The words are narrowed where the fused pass loads them: neither a stacked nor a narrowed copy exists anywhere
-    def records_stream_p010(self, surfaces, rotate: int = 0, full_range: bool = False) -> np.ndarray:
-        return self._stream(surfaces, lambda items: self._flush_list(items, _lib.AVD_FMT_P010, rotate, full_range))
+    def records_stream_p010(self, surfaces, rotate: int = 0, full_range: bool = False, slot: Optional[int] = None,
+                            resident_carry: Optional[bool] = None) -> np.ndarray:
+        return self._stream_list(surfaces, _lib.AVD_FMT_P010, rotate, full_range, slot, resident_carry)
 
-    def records_stream_i010(self, surfaces, rotate: int = 0, full_range: bool = False) -> np.ndarray:
-        return self._stream(surfaces, lambda items: self._flush_list(items, _lib.AVD_FMT_I010, rotate, full_range))
+    def records_stream_i010(self, surfaces, rotate: int = 0, full_range: bool = False, slot: Optional[int] = None,
+                            resident_carry: Optional[bool] = None) -> np.ndarray:
+        return self._stream_list(surfaces, _lib.AVD_FMT_I010, rotate, full_range, slot, resident_carry)
 
 
 class ClipsInFlight:

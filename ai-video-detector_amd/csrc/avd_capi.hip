@@ -424,7 +424,9 @@ static hipError_t wait_helping(avd_ctx* ctx, hipEvent_t ev)
 // ---- options (avd_set_option / avd_get_option, environment defaults read by avd_create) ----------------
 // One row per option; what an option MEANS is documented at its field in avd_ctx (avd_internal.h).  A read-only row is a counter: avd_set_option does
 // not know its name.  norm brings a value into range (false: refused with `refused`, the old value stays); env: read by avd_create through from_env and norm.
-struct Option { const char* name; int avd_ctx::*field; bool writable; bool (*norm)(int& v); const char* env; int (*from_env)(const char* text); const char* refused; };
+// act / read (the stream options): the option is not a plain field -- avd_set_option calls act with the accepted value, avd_get_option returns read's.
+struct Option { const char* name; int avd_ctx::*field; bool writable; bool (*norm)(int& v); const char* env; int (*from_env)(const char* text); const char* refused;
+                void (*act)(avd_ctx* ctx, int v); int (*read)(const avd_ctx* ctx); };
 static bool opt_any(int&) { return true; }
 static bool opt_flag(int& v) { v = v != 0; return true; }
 template <int AND, int OR = 0> static bool opt_mask(int& v) { v = (v & AND) | OR; return true; }
@@ -433,6 +435,16 @@ static bool opt_gemm_waves(int& v) { v = v == 16 ? 16 : 8; return true; }
 static bool opt_cnn_fuse(int& v) { v = v < 0 ? 0 : (v > 2 ? 2 : v); return true; }
 static bool opt_cnn_chunk(int& v) { return v >= 1 && v <= 1024; }
 static bool opt_cnn_tap(int& v) { return v >= 0 && v <= kCnnTapPooled; }
+static bool opt_stream(int& v) { return v >= 0 && v <= kStreamSlots; }
+// "stream_reset": k empties slot k, 0 all of them (the memory stays: 103 KB a slot); it reads back as 0.  avd_set_option has drained the context.
+static void stream_reset(avd_ctx* ctx, int v)
+{
+    for (int k = 1; k <= kStreamSlots; k++)
+        if (v == 0 || v == k) ctx->streams[k - 1].frames = 0;
+}
+static int stream_reset_read(const avd_ctx*) { return 0; }
+// "stream_frames": what the SELECTED slot has absorbed since it was last emptied
+static int stream_frames(const avd_ctx* ctx) { return ctx->stream_slot ? ctx->streams[ctx->stream_slot - 1].frames : 0; }
 static int env_any_base(const char* e) { return (int)std::strtol(e, nullptr, 0); }
 static int env_fb_mode(const char* e) { return (std::strcmp(e, "exact") == 0 || std::strcmp(e, "0") == 0) ? 0 : 1; }
 static const Option kOptions[] = {
@@ -452,6 +464,9 @@ static const Option kOptions[] = {
     {"cnn_chunk", &avd_ctx::cnn_chunk, true, opt_cnn_chunk, nullptr, nullptr, "cnn_chunk: 1 ... 1024 frames per forward pass"},
     {"cnn_tap", &avd_ctx::cnn_tap, true, opt_cnn_tap, nullptr, nullptr, "cnn_tap: 0 (off), 1 input image, 2 ... 54 convolution 0 ... 52, 55 max pool, 56 pooled features"},
     {"rerun_pairs", &avd_ctx::last_rerun, false, opt_any},   // pairs of the last drained call that the fast level kernel flagged and the exact kernels re-ran
+    {"stream_slot", &avd_ctx::stream_slot, true, opt_stream, nullptr, nullptr, "stream_slot: 0 (every call starts a new clip) or slot 1 ... 8"},
+    {"stream_reset", nullptr, true, opt_stream, nullptr, nullptr, "stream_reset: 0 (every slot) or slot 1 ... 8", stream_reset, stream_reset_read},
+    {"stream_frames", nullptr, false, opt_any, nullptr, nullptr, nullptr, nullptr, stream_frames},
 };
 static const Option* find_option(avd_ctx* ctx, const char* name, bool to_write)
 {
@@ -509,6 +524,7 @@ static void impl_destroy(avd_ctx* ctx)
     // everything the context owns on the device goes here: after the drain, before its stream does
     ctx->ws = Workspace{};
     ctx->weights = Weights{};
+    for (StreamSlot& s : ctx->streams) s.d_prev.reset();
     ctx->d_fbc.reset();
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
     if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
@@ -689,6 +705,32 @@ static int impl_farneback_pairs(avd_ctx* ctx, const uint8_t* small320, int mem, 
     return AVD_OK;
 }
 
+// A stream slot's frame <-> one frame of the per-frame buffers: what the Farneback stage and k_records read of a frame (its rows of small,
+// hash and lap), 103 KB in kStreamWords 16-byte words, which the slot keeps back to back.  ONE launch per direction: three copies through the
+// runtime cost a 1080p call more than ingesting the frame again did.
+constexpr int kStreamSmallWords = AVD_NPIX / 16, kStreamHashWords = 1024 / 16, kStreamWords = kStreamSmallWords + kStreamHashWords + 1;
+static_assert(kStreamHashAt == (size_t)kStreamSmallWords * 16 && kStreamLapAt == (size_t)(kStreamSmallWords + kStreamHashWords) * 16 &&
+              kStreamPrevBytes == (size_t)kStreamWords * 16, "the slot's layout in 16-byte words");
+__global__ __launch_bounds__(256) void k_stream_copy(uint4* __restrict__ small, uint4* __restrict__ hash, uint4* __restrict__ lap,
+                                                    uint4* __restrict__ kept, int save)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= kStreamWords) return;
+    uint4* const frame = i < kStreamSmallWords ? small + i : (i < kStreamSmallWords + kStreamHashWords ? hash + (i - kStreamSmallWords) : lap);
+    if (save) kept[i] = *frame;
+    else *frame = kept[i];
+}
+
+// save: frame f of the buffers -> slot; else slot -> frame f.  (A frame's rows are 16-byte aligned: 102 400, 1 024 and 16 bytes a frame.)
+static hipError_t stream_copy(avd_ctx* ctx, StreamSlot& s, int f, bool save)
+{
+    Workspace& ws = ctx->ws;
+    hipLaunchKernelGGL(k_stream_copy, dim3((kStreamWords + 255) / 256), dim3(256), 0, ctx->stream, reinterpret_cast<uint4*>(ws.d_small + (size_t)f * AVD_NPIX),
+                       reinterpret_cast<uint4*>(ws.d_hash + (size_t)f * 1024), reinterpret_cast<uint4*>(ws.d_lap + 2 * (size_t)f),
+                       reinterpret_cast<uint4*>(s.d_prev.p), save ? 1 : 0);
+    return hipGetLastError();
+}
+
 // ---- the whole per-frame path for a BATCH of clips (every avd_analyze_* entry; a single clip is a batch of one) --------
 // Frames of all clips are concatenated in the per-frame buffers (small320, hashes, moments, records): clip c occupies frames
 // [f0_c, f0_c + n_c).  Preprocess / hash / Hamming run per clip with that clip's geometry (cached tables); the Farneback
@@ -700,18 +742,27 @@ static int impl_analyze_async(avd_ctx* ctx, const IngestClip* clips, int nclips,
     if (!ctx) return AVD_ERR_ARG;
     if (nclips < 0 || (nclips > 0 && !clips)) { ctx->err = "bad clip list"; return AVD_ERR_ARG; }
     int64_t total = 0;
+    int live = 0;                                          // clips that bring frames
     for (int c = 0; c < nclips; c++) {
         if (int e = refuse(ctx, check_clip(clips[c]))) return e;
         total += clips[c].n;
+        live += clips[c].n > 0;
     }
-    if (total > (1 << 24)) { ctx->err = "too many frames in one call"; return AVD_ERR_ARG; }
+    // Option "stream_slot": the call continues the clip whose last frame the slot holds.  That frame (pred = 1) goes in front of the call's own
+    // frames in the per-frame buffers, the one clip starts at frame 1, and everything behind the ingest -- Farneback chunks, flags, the exact
+    // re-run, the record kernel -- runs over n + 1 frames as it would for a call that had been handed the frame again; records 1 .. n go out.
+    StreamSlot* const stream = ctx->stream_slot ? &ctx->streams[ctx->stream_slot - 1] : nullptr;
+    if (stream && live > 1) { ctx->err = "stream_slot: one clip per call"; return AVD_ERR_ARG; }
+    const int pred = stream && stream->frames > 0 ? 1 : 0;
+    if (total + pred > (1 << 24)) { ctx->err = "too many frames in one call"; return AVD_ERR_ARG; }
     if (total == 0) return AVD_OK;
     if (!records) { ctx->err = "null pointer"; return AVD_ERR_ARG; }
-    const int n = (int)total;
+    const int own = (int)total;                            // the caller's frames = the records that go out
+    const int n = own + pred;                              // frames in the buffers
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     Workspace& ws = ctx->ws;
     // pass 1: geometry tables (cached), each clip's place in the buffers and their sizes -- everything is reserved before the first launch of the call
-    int frames = 0;
+    int frames = pred;
     size_t rowbuf_elems = 0, lappart_elems = 0, stage_bytes = 0;
     CallLists lists;
     plan_lists(clips, nclips, lists);
@@ -733,6 +784,8 @@ static int impl_analyze_async(avd_ctx* ctx, const IngestClip* clips, int nclips,
     if (int e = avd_ws_reserve_fb(ctx, n)) return e;
     if (int e = ws.d_stage.reserve(ctx, stage_bytes)) return e;
     if (int e = reserve_lists(ctx, lists)) return e;
+    if (stream)
+        if (int e = stream->d_prev.reserve(ctx, kStreamPrevBytes)) return e;     // an empty slot's first call (frames = 0: still empty if the call fails)
     // pass 2: per clip, stage (host input) -> fused full-resolution kernel -> hash, in the clip's slot
     kmark_reset(ctx);
     ctx->ingest.stage_bytes = 0;
@@ -744,6 +797,8 @@ static int impl_analyze_async(avd_ctx* ctx, const IngestClip* clips, int nclips,
     // (host input staged for it) included.
     kmark(ctx, AVD_K_PREPROCESS, stage_mark(ctx, 0));
     bool first_clip = true;
+    // the slot's frame becomes frame 0 (device to device, ordered on the stream like everything else; inside the first region)
+    if (pred) HIP_TRY(ctx, stream_copy(ctx, *stream, 0, false));
     if (int e = upload_lists(ctx, clips, nclips, lists)) return e;
     for (int c = 0; c < nclips; c++) {
         const IngestClip& k = clips[c];
@@ -762,7 +817,7 @@ static int impl_analyze_async(avd_ctx* ctx, const IngestClip* clips, int nclips,
     }
     kmark(ctx, AVD_K_OTHER, stage_mark(ctx, 1));
     const int* clipstart = nullptr;                        // one clip: frame 0 is the only one without a predecessor
-    if (nclips > 1) {
+    if (nclips > 1 && !pred) {                             // (a continued clip is one clip behind the slot's frame, whatever empty clips the call lists)
         HIP_TRY(ctx, hipMemcpyAsync(ws.d_clipstart, ws.h_clipstart, sizeof(int) * n, hipMemcpyHostToDevice, ctx->stream));
         clipstart = ws.d_clipstart;
     }
@@ -776,16 +831,21 @@ static int impl_analyze_async(avd_ctx* ctx, const IngestClip* clips, int nclips,
     if (n < 2) launch_records(ctx, 0, 0, 0, clipstart);     // one frame: no pair, no flow
     else if (int e = run_flow_chunks(ctx, ws.d_small, n, nullptr, nullptr, nullptr, true, clipstart)) return e;
     kmark(ctx, AVD_K_OTHER, stage_mark(ctx, 3));
+    // the call's last frame becomes the slot's: only here, behind everything that can refuse or fail for want of memory (nothing has written
+    // d_small, d_hash or d_lap since the ingest), so that such a call leaves the slot as it was
+    if (stream) HIP_TRY(ctx, stream_copy(ctx, *stream, n - 1, true));
     // into PINNED memory: a device-to-host copy into the caller's pageable buffer would block this thread until
     // the whole call is done and it would not be asynchronous at all; avd_synchronize hands the records over
+    // (all n of them, the slot's frame included: the deferred re-run finds its chunk's flag words where it always does)
     HIP_TRY(ctx, hipMemcpyAsync(ws.h_rec, ws.d_rec, sizeof(avd_frame_record) * n, hipMemcpyDeviceToHost, ctx->stream));
     tail_on_error.ok = true;
-    ctx->pending_out = records; ctx->pending_n = n;
+    if (stream) stream->frames = (int)std::min<int64_t>((int64_t)stream->frames + own, INT32_MAX);
+    ctx->pending_out = records; ctx->pending_n = own; ctx->pending_off = pred;
     if (ctx->tail.active) tail_register(ctx);              // from here on a waiting thread may settle this call's tail
     if (!ctx->counted_in_flight) { ctx->counted_in_flight = 1; g_calls_in_flight.fetch_add(1, std::memory_order_relaxed); }
     kmark(ctx, AVD_K_COUNT, stage_mark(ctx, 4));           // end of the last region
     ctx->last_n = n;
-    ctx->rec_n = n;
+    ctx->rec_n = own; ctx->rec_off = pred;
     return AVD_OK;
 }
 
@@ -825,9 +885,10 @@ static int impl_synchronize(avd_ctx* ctx)
     }
     HIP_TRY(ctx, wait_helping(ctx, nullptr));
     if (ctx->pending_out) {
-        std::memcpy(ctx->pending_out, ctx->ws.h_rec, sizeof(avd_frame_record) * ctx->pending_n);
+        const avd_frame_record* const got = ctx->ws.h_rec + ctx->pending_off;
+        std::memcpy(ctx->pending_out, got, sizeof(avd_frame_record) * ctx->pending_n);
         ctx->last_rerun = 0;
-        for (int i = 0; i < ctx->pending_n; i++) ctx->last_rerun += ctx->ws.h_rec[i].reserved != 0;
+        for (int i = 0; i < ctx->pending_n; i++) ctx->last_rerun += got[i].reserved != 0;
         ctx->pending_out = nullptr; ctx->pending_n = 0;
     }
     // only a mark list that an avd_analyze_* call closed (its last mark is AVD_K_COUNT: impl_analyze_async, tail_settle) is a call's timeline;
@@ -1009,7 +1070,8 @@ static int impl_set_option(avd_ctx* ctx, const char* name, int value)
     const Option* o = find_option(ctx, name, true);
     if (!o) return AVD_ERR_ARG;
     if (!o->norm(value)) { ctx->err = o->refused; return AVD_ERR_ARG; }
-    ctx->*o->field = value;
+    if (o->act) o->act(ctx, value);
+    else ctx->*o->field = value;
     return AVD_OK;
 }
 
@@ -1019,7 +1081,7 @@ static int impl_get_option(avd_ctx* ctx, const char* name, int* value)
     if (!ctx || !name || !value) return AVD_ERR_ARG;
     const Option* o = find_option(ctx, name, false);
     if (!o) return AVD_ERR_ARG;
-    *value = ctx->*o->field;
+    *value = o->read ? o->read(ctx) : ctx->*o->field;
     return AVD_OK;
 }
 

@@ -122,7 +122,7 @@ int comm_allgather_last_records(avd_ctx* ctx, int count, avd_frame_record* all)
     const size_t mine = sizeof(avd_frame_record) * (size_t)count, total = mine * (size_t)ctx->comm_world;
     if (int e = ctx->d_comm.reserve(ctx, mine + total)) return e;
     char* d_recv = ctx->d_comm + mine;
-    const int rc = r->allgather(ctx->ws.d_rec, d_recv, mine, /*ncclUint8*/ 1, ctx->comm, ctx->stream);
+    const int rc = r->allgather(ctx->ws.d_rec + ctx->rec_off, d_recv, mine, /*ncclUint8*/ 1, ctx->comm, ctx->stream);
     if (rc) return fail(ctx, r, "ncclAllGather", rc);
     HIP_TRY(ctx, hipMemcpyAsync(all, d_recv, total, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));

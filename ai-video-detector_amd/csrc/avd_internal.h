@@ -241,6 +241,17 @@ struct Weights {
     DevBuf<uint16_t> d_vit_w; DevBuf<float> d_vit_bias; int vit_has_bias = 0;
 };
 
+// A stream slot (option "stream_slot") is state too: what the pair (previous, current) reads of the last frame the slot absorbed -- its 320 x 320
+// gray image, its 1024 hash bits (one per byte) and its two Laplacian moments, in this order.  An avd_analyze_* call with a slot selected puts
+// them in front of its own frames (ClipSlot::f0 = 1) and leaves its last frame here; frames = 0: the slot is empty, whatever d_prev holds.
+constexpr int kStreamSlots = 8;
+constexpr size_t kStreamHashAt = AVD_NPIX, kStreamLapAt = AVD_NPIX + 1024, kStreamPrevBytes = kStreamLapAt + 2 * sizeof(unsigned long long);
+static_assert(kStreamLapAt % sizeof(unsigned long long) == 0, "the moments are copied as two 64-bit words");
+struct StreamSlot {
+    DevBuf<uint8_t> d_prev;          // [kStreamPrevBytes]
+    int frames = 0;                  // frames absorbed since the slot was last emptied ("stream_frames")
+};
+
 struct avd_ctx {
     int device = 0;
     int num_cus = 256;
@@ -249,6 +260,7 @@ struct avd_ctx {
     hipEvent_t ev_in = nullptr;                // avd_wait_stream: recorded on the caller's stream, waited for by ours
     avd_frame_record* pending_out = nullptr;   // caller buffer the pinned records are handed to in avd_synchronize
     int pending_n = 0;
+    int pending_off = 0;                       // the first of them in ws.h_rec (1: the call continued a stream slot, record 0 is the slot's frame)
     hipEvent_t stage_ev[5] = {};
     hipEvent_t kern_ev[12] = {};           // profiling: level320_mark events around the 320-px level's blur launches of a chunk
     int kern_ev_used = 0;
@@ -272,6 +284,9 @@ struct avd_ctx {
     int last_n = 0;
     IngestRecord ingest;             // what the last ingest of this context did
     int rec_n = 0;                   // records the last avd_analyze_* call left in ws.d_rec (0 after any other entry point: avd_allgather_last_records checks it)
+    int rec_off = 0;                 // ... from this entry on (1: the call continued a stream slot)
+    StreamSlot streams[kStreamSlots];   // option "stream_slot" = k selects streams[k - 1]
+    int stream_slot = 0;             // 0 = every avd_analyze_* call starts a new clip; k = the call continues the clip slot k holds (one clip per call)
     void* comm = nullptr;            // RCCL communicator (avd_comm.cpp), bound at run time
     int comm_rank = 0, comm_world = 1;
     DevBuf<char> d_comm;             // device staging of the record exchange

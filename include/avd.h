@@ -514,7 +514,23 @@ int avd_set_profiling(avd_ctx* ctx, int enable);
  * context's stream right after the launch that produces it, for avd_debug_fetch "cnn_tap": 1 = the zero-bordered input image, 2 + i = the output of
  * convolution i (avd_cnn_set_weights order, 0 = stem ... 52), 55 = the max pool's output, 56 = the pooled features.  While it is set, a call with more
  * frames than one pass ("cnn_chunk") or with timing_reps > 0 is refused (AVD_ERR_ARG); at 0 the forward enqueues nothing for it.
- * avd_get_option returns the value an option has now (environment defaults included) and the read-only "rerun_pairs". */
+ * Stream slots: calls that continue ONE clip (a decoder that hands out 4 to 16 surfaces per call, a live stream of one or two frames per call).
+ * "stream_slot" (default 0; 0 ... 8, anything else is refused with AVD_ERR_ARG and the old value stays): 0 = every avd_analyze_* call starts a new clip
+ * (first record: ham = -1, flow 0).  With slot k = 1 ... 8 selected, a call of any avd_analyze_* entry (avd_analyze_frames / _nv12 / _i420, avd_analyze_batch,
+ * avd_analyze_pictures, avd_analyze_frame_lists and their _async forms) that carries exactly one non-empty clip CONTINUES the clip of slot k: on an empty slot
+ * its records are what they are without the option; on a filled one its n records are, bit for bit and in both "fb_mode"s, records [1:] of the same call
+ * made on the slot's frame followed by the n frames -- record 0 carries the Hamming distance and the flow statistics of the pair (slot frame, frame 0),
+ * with the fast mode's flag word, exact re-run and bit-identical-pair exemption as for any other pair.  After the call the slot holds the call's last frame
+ * (its 320 x 320 gray image, 1024 hash bits and Laplacian moments: 103 KB on the device, kept and restored by copies ordered on the context's stream -- no
+ * host round trip, no synchronisation; the caller's frame is free once its call is drained).  One clip per call: more than one non-empty clip while a slot is
+ * selected is refused (AVD_ERR_ARG, "stream_slot: one clip per call") before anything is staged.  A refused call, a call that fails before it is
+ * enqueued and a call without frames leave the slot as it was.  The layout, geometry, rotation and range may change from call to call.  A slot is state,
+ * not scratch: it survives avd_release_workspace and every call in between (other slots, slot-0 analyses, avd_preprocess_*, avd_farneback_pairs -- which
+ * ignore the option -- audio, the extensions); avd_destroy frees it.  One context has eight slots and so serves up to eight streams in turn.
+ * avd_debug_fetch "small" of a call that continued a filled slot begins with the slot's frame ("area": with an entry that is not defined).
+ * "stream_reset": setting k = 1 ... 8 empties slot k, 0 empties all eight (other values are refused); it reads back as 0.
+ * "stream_frames" (read-only): frames the selected slot has absorbed since it was last emptied; 0 for an empty slot and with slot 0 selected.
+ * avd_get_option returns the value an option has now (environment defaults included) and the read-only "rerun_pairs" and "stream_frames". */
 int avd_set_option(avd_ctx* ctx, const char* name, int value);
 int avd_get_option(avd_ctx* ctx, const char* name, int* value);
 int avd_stage_ms(avd_ctx* ctx, int stage, float* ms);
