@@ -1030,6 +1030,7 @@ static int64_t impl_debug_fetch(avd_ctx* ctx, const char* name, void* out, size_
     else if ((k = level("pyr")) >= 0) { src = ws.d_pyr[k]; bytes = (size_t)std::min(n, ws.fb_cap + 1) * (AVD_NPIX >> (2 * k)) * 4; }
     else if ((k = level("poly")) >= 0) { src = ws.d_poly[k]; bytes = (size_t)std::min(n, ws.fb_cap + 1) * 5 * (AVD_NPIX >> (2 * k)) * 4; }
     else if ((k = level("flow")) >= 0) { src = ws.fb_holds.flow[k] ? ws.fb_holds.flow[k] : ws.d_flow[k]; bytes = (size_t)std::min(std::max(n - 1, 0), ws.fb_cap) * 2 * (AVD_NPIX >> (2 * k)) * 4; }
+    else if (std::strcmp(name, "pairdiff") == 0) { src = ws.d_pairdiff; bytes = (size_t)std::min(std::max(n - 1, 0), ws.fb_cap) * kPairDiffTiles * sizeof(int); }
     else if (std::strcmp(name, "vs0") == 0) { src = ws.d_vs0; bytes = fb_two_scratch_size((size_t)ws.fb_cap).vs0 * sizeof(double); }
     else { ctx->err = "unknown debug buffer"; return AVD_ERR_ARG; }
     if (!src) { ctx->err = "buffer not allocated yet"; return AVD_ERR_ARG; }

@@ -27,23 +27,37 @@ constexpr int S = AVD_SMALL;
 // Gaussian pyramid level K (scale 2^-K): GaussianBlur(full-res, ksize, sigma) then the
 // INTER_LINEAR decimation, which at these exact power-of-two scales is the 2x2 mean
 // ((p00+p01)+(p10+p11))*0.25 of the two centre pixels.  Only the columns/rows the
-// decimation reads are filtered.  One workgroup = TR output rows of one frame:
+// decimation reads are filtered.  One workgroup = one BAND of one frame, BAND = STEPS x TR output rows, walked in steps of TR rows:
 //   source rows (uint8, reflect-101) -> LDS;  row pass (FMA chain, cv2's RowVec_32f order)
 //   -> LDS float [rows][NC];  column pass (SymmColumnVec_32f order) + 2x2 mean -> I[f][dy][dx].
+// A step's TR output rows read SROWS row-filtered source rows, of which the last KEEP = SROWS - NEW are also the first KEEP of the next step
+// (NEW = TR 2^K: how far the window moves).  A later step of a band therefore moves those KEEP float rows to the top of the LDS array and loads,
+// converts and row-filters only its NEW rows: the LDS plan stays that of ONE step (29 KB -- the 76 rows that eight 40-px output rows need at
+// once are 50 KB and held a CU to three workgroups), while a source row is filtered (SROWS + (STEPS - 1) NEW) / (STEPS NEW) times per frame
+// instead of SROWS / NEW times.  The bands are kept short -- a workgroup's steps are a serial chain -- and the 160-px scale, whose 3-tap
+// filter overlaps by two rows in sixteen, is not walked at all.  (The kernel's 104 registers, not its LDS, hold a CU to four workgroups;
+// a build capped at 96 registers keeps five, spills twelve of them and is 0.4 us of 25 faster: not kept, profiles/pyramid_bands_ab.txt.)
 // ---------------------------------------------------------------------------------------
 template <int K>
 struct PyrGeo {
     static constexpr int WL = S >> K;
     static constexpr int NC = K == 0 ? S : 2 * WL;              // filtered columns per row
     static constexpr int OFF = K == 0 ? 0 : (1 << K) / 2 - 1;
-    // output rows per workgroup: four at the two coarse scales -- their long filters need (TR - 1) 2^K + 2 + 2 HALF source rows,
-    // and the 40-px scale's 76 rows (50 KB of LDS for every workgroup of the launch) held a CU to three workgroups
+    // output rows per step: four at the two coarse scales -- their long filters need (TR - 1) 2^K + 2 + 2 HALF source rows
     static constexpr int TR = K >= 2 ? 4 : 8;                   // (2 / 4 / 4 / 8 rows -- 22 KB, seven workgroups per CU -- is slower: 57 vs 52 us)
-    static constexpr int TILES = WL / TR;                       // workgroups per frame
+    static constexpr int STEPS = K >= 2 ? 2 : 1, BAND = STEPS * TR;   // a band: eight output rows at every scale
+    static constexpr int TILES = WL / BAND;                     // workgroups per frame
     static constexpr int KS = K == 3 ? 19 : (K == 2 ? 9 : 3), HALF = KS / 2;
-    static constexpr int SROWS = K == 0 ? TR + 2 * HALF : ((TR - 1) << K) + 2 + 2 * HALF;   // source rows needed
+    static constexpr int SROWS = K == 0 ? TR + 2 * HALF : ((TR - 1) << K) + 2 + 2 * HALF;   // source rows a step reads
+    static constexpr int NEW = K == 0 ? TR : TR << K, KEEP = SROWS - NEW;                   // rows a later step adds / takes over
     static constexpr int PADX = 12, PS = S + 2 * PADX;          // source rows carry their reflected borders (HALF <= 9 < PADX, PADX % 4 == 0)
     static constexpr int SRC_BYTES = SROWS * PS, LDS_BYTES = SRC_BYTES + SROWS * NC * 4;
+    // source rows loaded, converted and row-filtered per frame, against the frame's S rows, in percent: 112 / 118 / 118 at 160 / 80 / 40 px
+    // (unwalked: 112 / 137 / 137; the 320-px scale, which runs with fb_fold_blur off only, is at 125)
+    static constexpr int FILTERED_PCT = TILES * (SROWS + (STEPS - 1) * NEW) * 100 / S;
+    static_assert(WL % BAND == 0 && (K == 0 || FILTERED_PCT <= 120), "whole bands; a source row is filtered at most 1.2 times per frame");
+    static_assert(STEPS == 1 || (KEEP * NC <= 4 * 256 && SRC_BYTES % 16 == 0 && (NEW * NC) % 4 == 0 && (KEEP * NC) % 4 == 0),
+                  "the rows a step takes over move as one 16-byte piece per lane");
 };
 constexpr int cmax(int a, int b) { return a > b ? a : b; }
 constexpr int cgcd(int a, int b) { return b == 0 ? a : cgcd(b, a % b); }
@@ -68,59 +82,88 @@ struct PyrWalk {
 };
 constexpr int kPyrLds = cmax(cmax(PyrGeo<3>::LDS_BYTES, PyrGeo<2>::LDS_BYTES), cmax(PyrGeo<1>::LDS_BYTES, PyrGeo<0>::LDS_BYTES));   // 29 KB
 
-// blk = frame * TILES + tile of this scale
-// pairdiff (K == 1 only, may be null): the tile also compares its source rows with the same rows of the NEXT frame and leaves "they differ" in
-// pairdiff[f * TILES + t] -- the 20 tiles of the 160-px scale read every row of the frame (with overlap), so their OR says whether pair (f, f + 1)
-// is a pair of bit-identical frames (which the fast level kernels exempt from the border-sign criterion, avd_fbfast.hip)
+typedef float pyr_f4 __attribute__((ext_vector_type(4)));
+typedef float pyr_f2 __attribute__((ext_vector_type(2)));
+
+// One step of a band: the TR output rows out[0 .. TR)[WL] of frame img, whose first row-filtered source row, LDS row 0, is image row y_first
+// (may be < 0: reflected).  LDS rows [0, rb) are taken over from the step before (rb = 0 in a band's first step, KEEP in the others: this lane's
+// piece of them arrives in `kept`), rows [rb, SROWS) are loaded and filtered here; `more`: another step follows, its piece is left in `kept`.
+// diffword (K == 1 only, may be null): the tile also compares its source rows with the same rows of the NEXT frame and leaves "they differ" in
+// *diffword = pairdiff[f * TILES + t] -- the 20 tiles of the 160-px scale read every row of the frame (with overlap), so their OR says whether pair
+// (f, f + 1) is a pair of bit-identical frames (which the fast level kernels exempt from the border-sign criterion, avd_fbfast.hip)
 template <int K>
-__device__ __forceinline__ void pyramid_body(char* lds, int blk, const uint8_t* __restrict__ small, const FbConsts* __restrict__ C,
-                                             float* __restrict__ I, int n = 0, int* __restrict__ pairdiff = nullptr)
+__device__ __forceinline__ void pyramid_step(char* lds, const uint8_t* __restrict__ img, const float (&kw)[PyrGeo<K>::KS], float* __restrict__ out,
+                                             int y_first, int rb, pyr_f4& kept, bool more, int* __restrict__ diffword)
 {
     using G = PyrGeo<K>;
     constexpr int WL = G::WL, NC = G::NC, OFF = G::OFF, TR = G::TR, KS = G::KS, HALF = G::HALF, SROWS = G::SROWS;
     constexpr int PADX = G::PADX, PS = G::PS;
     uint8_t (*src)[PS] = reinterpret_cast<uint8_t (*)[PS]>(lds);
     float (*rowf)[NC] = reinterpret_cast<float (*)[NC]>(lds + G::SRC_BYTES);
-    const int tiles = WL / TR;
-    const int f = blk / tiles, t = blk - f * tiles;
     const int tid = threadIdx.x;
-    const int dy0 = t * TR;
-    const int y_first = (K == 0 ? dy0 : (dy0 << K) + OFF) - HALF;        // first source row (may be < 0)
-    const uint8_t* img = small + (int64_t)f * AVD_NPIX;
-    const bool cmp = K == 1 && pairdiff != nullptr && f + 1 < n;       // workgroup-uniform
+    const bool cmp = K == 1 && diffword != nullptr;      // workgroup-uniform
+    static_assert(K != 1 || G::STEPS == 1, "the pair-identity word is formed by a tile that loads all its source rows in one step");
+    // Source rows -> LDS.  A lane's loads are issued in batches, a whole batch before the first of them is waited for and written (the item loops
+    // are unrolled over registers, the row's reflection is a select): as "load, wait, write" per item the up to fourteen loads of a lane each
+    // paid the memory latency, one after the other, and that chain was most of a workgroup's time.
+    static_assert(HALF + 1 < S, "a source row is reflected at most once");
+    // byte offset of LDS row r's image row (BORDER_REFLECT_101) in the frame: unsigned, so that a load is "uniform base + 32-bit lane offset"
+    auto row_at = [&](int r) -> unsigned { const int y = y_first + r; return (unsigned)(y < 0 ? -y : (y >= S ? 2 * S - 2 - y : y)) * S; };
+    constexpr int NLD = (SROWS * (S / 4) + 255) / 256, NBD = (SROWS * 2 * HALF + 255) / 256;
+    const int nld = (SROWS - rb) * (S / 4), nbd = (SROWS - rb) * 2 * HALF;
+    constexpr int NBATCH = 8;                            // loads of a lane in flight at a time: two batches where a lane has up to fourteen
     int differs = 0;
-    for (int it = tid; it < SROWS * (S / 4); it += 256) {
-        const int r = it / (S / 4), c4 = it - r * (S / 4);
-        const int y = reflect101(y_first + r, S);
-        const unsigned v = reinterpret_cast<const unsigned*>(img + y * S)[c4];
-        reinterpret_cast<unsigned*>(src[r] + PADX)[c4] = v;
-        if (K == 1 && cmp) differs |= v != reinterpret_cast<const unsigned*>(img + AVD_NPIX + y * S)[c4];
-    }
-    // BORDER_REFLECT_101 columns, so that the taps below need no index arithmetic: x = -1 - i is x = 1 + i, x = S + i is S - 2 - i
-    for (int it = tid; it < SROWS * 2 * HALF; it += 256) {
-        const int r = it / (2 * HALF), i = it - r * (2 * HALF);
-        const uint8_t* g = img + reflect101(y_first + r, S) * S;
-        if (i < HALF) src[r][PADX - 1 - i] = g[1 + i];
-        else src[r][PADX + S + (i - HALF)] = g[S - 2 - (i - HALF)];
+#pragma unroll
+    for (int e0 = 0; e0 < NLD; e0 += NBATCH) {
+        const bool last = e0 + NBATCH >= NLD;            // the reflected columns' bytes travel with the last batch
+        unsigned v[NBATCH], vn[K == 1 ? NBATCH : 1];
+        uint8_t bv[NBD];
+#pragma unroll
+        for (int e = e0; e < NLD && e < e0 + NBATCH; e++) {
+            const int it = tid + 256 * e, q = it / (S / 4), c4 = it - q * (S / 4);
+            if (it >= nld) continue;
+            const unsigned at = row_at(rb + q) + 4u * c4;
+            v[e - e0] = *reinterpret_cast<const unsigned*>(img + at);
+            if (K == 1 && cmp) vn[e - e0] = *reinterpret_cast<const unsigned*>(img + (at + AVD_NPIX));
+        }
+        // the reflected columns, so that the taps below need no index arithmetic: x = -1 - i is x = 1 + i, x = S + i is S - 2 - i
+#pragma unroll
+        for (int e = 0; e < NBD; e++) {
+            const int it = tid + 256 * e, q = it / (2 * HALF), i = it - q * (2 * HALF);
+            if (!last || it >= nbd) continue;
+            bv[e] = img[row_at(rb + q) + (unsigned)(i < HALF ? 1 + i : S - 2 - (i - HALF))];
+        }
+#pragma unroll
+        for (int e = e0; e < NLD && e < e0 + NBATCH; e++) {
+            const int it = tid + 256 * e, q = it / (S / 4), c4 = it - q * (S / 4);
+            if (it >= nld) continue;
+            reinterpret_cast<unsigned*>(src[rb + q] + PADX)[c4] = v[e - e0];
+            if (K == 1 && cmp) differs |= v[e - e0] != vn[e - e0];
+        }
+#pragma unroll
+        for (int e = 0; e < NBD; e++) {
+            const int it = tid + 256 * e, q = it / (2 * HALF), i = it - q * (2 * HALF);
+            if (!last || it >= nbd) continue;
+            src[rb + q][i < HALF ? PADX - 1 - i : PADX + S + (i - HALF)] = bv[e];
+        }
+        __builtin_amdgcn_sched_barrier(0);               // (the next batch's loads stay behind this batch's writes)
     }
     if (K == 1 && cmp) {
         const int any = __syncthreads_or(differs);
-        if (tid == 0) pairdiff[f * tiles + t] = any;
+        if (tid == 0) *diffword = any;
     } else
-        __syncthreads();
-    // The two passes below are item loops "for (it = tid; it < rows * PR; it += 256)" over (row, column) = (it / PR, it % PR), PR items per row.
+        __syncthreads();                                 // (a later step: the column pass of the step before has read the rows written below)
+    if (G::STEPS > 1 && rb && tid < G::KEEP * NC / 4) reinterpret_cast<pyr_f4*>(&rowf[0][0])[tid] = kept;
+    // The two passes below are item loops "for (it = tid; it < rows * PR; it += 256)" over (row, column) = (it / PR, it % PR), PR items per row,
+    // the row pass over LDS rows [rb, SROWS).
     // The columns a lane meets repeat after W::PER items = W::SG rows (PyrWalk), so a lane OWNS up to PER columns and walks down the rows in steps of SG:
-    // the column, the window's word base and byte shift, the LDS addresses and the tap weights are formed once in front of the loop, and no division
+    // the column, the window's word base, the LDS addresses and the tap weights are formed once in front of the loop, and no division
     // is left in it (round-5 counters: 2.4 x the VALU instructions of the filters themselves, the difference was this index work per item).
-    float kw[KS];                                        // the tap weights (uniform: scalar registers)
-#pragma unroll
-    for (int q = 0; q < KS; q++) kw[q] = C->gk[K][q];
     if (KS == 3) {
         // every column is filtered at these scales (x = j): a lane does four of them from three aligned words
         static_assert(KS != 3 || NC == S, "the 3-tap scales filter whole rows");
         using W = PyrWalk<S / 4>;
-        typedef float f4 __attribute__((ext_vector_type(4)));
-        const unsigned* wp0[W::PER]; f4* dst0[W::PER]; int r0[W::PER];
+        const unsigned* wp0[W::PER]; pyr_f4* dst0[W::PER]; int r0[W::PER];
         {
             int r, c4;
             W::first(tid, r, c4);
@@ -128,11 +171,11 @@ __device__ __forceinline__ void pyramid_body(char* lds, int blk, const uint8_t* 
             for (int i = 0; i < W::PER; i++) {
                 r0[i] = r;
                 wp0[i] = reinterpret_cast<const unsigned*>(src[r] + PADX + 4 * c4);
-                dst0[i] = reinterpret_cast<f4*>(&rowf[r][4 * c4]);
+                dst0[i] = reinterpret_cast<pyr_f4*>(&rowf[r][4 * c4]);
                 W::next(r, c4);
             }
         }
-        for (int sb = 0; sb < SROWS; sb += W::SG) {
+        for (int sb = rb; sb < SROWS; sb += W::SG) {
 #pragma unroll
             for (int i = 0; i < W::PER; i++) {
                 if (256 * i >= SROWS * (S / 4) || r0[i] + sb >= SROWS) continue;
@@ -140,48 +183,50 @@ __device__ __forceinline__ void pyramid_body(char* lds, int blk, const uint8_t* 
                 const unsigned pw = wp[-1], cwd = wp[0], nw = wp[1];
                 const float b[6] = {(float)(pw >> 24), (float)(cwd & 0xFFu), (float)((cwd >> 8) & 0xFFu), (float)((cwd >> 16) & 0xFFu),
                                     (float)(cwd >> 24), (float)(nw & 0xFFu)};
-                f4 o;
+                pyr_f4 o;
 #pragma unroll
                 for (int e = 0; e < 4; e++) o[e] = __builtin_fmaf(b[e + 1], kw[1], (b[e] + b[e + 2]) * kw[0]);
                 dst0[i][sb * (NC / 4)] = o;
             }
         }
     } else {
-        // the KS source bytes x - HALF .. x + HALF: aligned 32-bit LDS reads, one byte alignment of the window
-        // (v_alignbyte), then one v_cvt_f32_ubyteN per tap -- instead of a byte read and a reflected index per tap
-        using W = PyrWalk<NC>;
-        constexpr int NW = (KS + 3) / 4;                 // aligned words of the window
-        const unsigned* wp0[W::PER]; float* dst0[W::PER]; int r0[W::PER], sh0[W::PER];
+        // The filtered columns come in adjacent pairs x0 = (jp << K) + OFF and x0 + 1, whose windows share KS - 1 of their KS + 1 source bytes: an
+        // item is a PAIR.  Its window x0 - HALF .. x0 + HALF + 1 begins B0 + (jp << K) bytes into the LDS row, at the same byte of a word for every
+        // pair (2^K is a multiple of four): aligned 32-bit LDS reads, ONE v_cvt_f32_ubyteN per distinct byte with a constant byte number (no
+        // alignment of the window), the two FMA chains of the pair on the same converted bytes, and one 8-byte write of the two results.
+        static_assert(KS == 3 || (K >= 2 && NC == 2 * WL), "the long filters run at the decimated scales, where the columns are pairs");
+        using W = PyrWalk<WL>;
+        constexpr int B0 = PADX + OFF - HALF, SH = B0 & 3, NW = (SH + KS + 1 + 3) / 4;   // window of pair 0: first byte, its place in a word, aligned words
+        const unsigned* wp0[W::PER]; pyr_f2* dst0[W::PER]; int r0[W::PER];
         {
-            int r, j;
-            W::first(tid, r, j);
+            int r, jp;
+            W::first(tid, r, jp);
 #pragma unroll
             for (int i = 0; i < W::PER; i++) {
-                const int x = K == 0 ? j : ((j >> 1) << K) + OFF + (j & 1);
-                const int base = PADX + x - HALF;
-                r0[i] = r; sh0[i] = base & 3;
-                wp0[i] = reinterpret_cast<const unsigned*>(src[r] + (base & ~3));
-                dst0[i] = &rowf[r][j];
-                W::next(r, j);
+                r0[i] = r;
+                wp0[i] = reinterpret_cast<const unsigned*>(src[r] + (B0 & ~3) + (jp << K));
+                dst0[i] = reinterpret_cast<pyr_f2*>(&rowf[r][2 * jp]);
+                W::next(r, jp);
             }
         }
-        for (int sb = 0; sb < SROWS; sb += W::SG) {
+        for (int sb = rb; sb < SROWS; sb += W::SG) {
 #pragma unroll
             for (int i = 0; i < W::PER; i++) {
-                if (256 * i >= SROWS * NC || r0[i] + sb >= SROWS) continue;
+                if (256 * i >= SROWS * WL || r0[i] + sb >= SROWS) continue;
                 const unsigned* wp = wp0[i] + sb * (PS / 4);
-                unsigned d[NW + 1];
+                unsigned d[NW];
 #pragma unroll
-                for (int q = 0; q <= NW; q++) d[q] = wp[q];
-                float v = 0.f;
+                for (int q = 0; q < NW; q++) d[q] = wp[q];
+                float b[KS + 1];
 #pragma unroll
-                for (int q = 0; q < NW; q++) {
-                    const unsigned wv = __builtin_amdgcn_alignbyte(d[q + 1], d[q], sh0[i]);
+                for (int q = 0; q <= KS; q++) b[q] = (float)((d[(SH + q) >> 2] >> (8 * ((SH + q) & 3))) & 0xFFu);
+                float v0 = 0.f, v1 = 0.f;
 #pragma unroll
-                    for (int e = 0; e < 4; e++)
-                        if (q * 4 + e < KS) v = __builtin_fmaf((float)((wv >> (8 * e)) & 0xFFu), kw[q * 4 + e], v);
+                for (int q = 0; q < KS; q++) {
+                    v0 = __builtin_fmaf(b[q], kw[q], v0);
+                    v1 = __builtin_fmaf(b[q + 1], kw[q], v1);
                 }
-                dst0[i][sb * NC] = v;
+                dst0[i][sb * (NC / 2)] = pyr_f2{v0, v1};
             }
         }
     }
@@ -194,7 +239,6 @@ __device__ __forceinline__ void pyramid_body(char* lds, int blk, const uint8_t* 
     };
     {
         using W = PyrWalk<WL>;
-        float* out = I + ((int64_t)f * WL + dy0) * WL;
         int dyl, dx;
         W::first(tid, dyl, dx);
 #pragma unroll
@@ -205,10 +249,26 @@ __device__ __forceinline__ void pyramid_body(char* lds, int blk, const uint8_t* 
                     if (K == 0) {
                         o = colf(&rowf[y + HALF][dx]);
                     } else {
-                        const float* c = &rowf[(y << K) + HALF][2 * dx];   // LDS row of source row (dy << K) + OFF
-                        const float p00 = colf(c), p01 = colf(c + 1);
-                        const float p10 = colf(c + NC), p11 = colf(c + NC + 1);
-                        o = ((p00 + p01) + (p10 + p11)) * 0.25f;
+                        // the output's 2 x 2 block: centre taps in LDS rows (y << K) + HALF (source row (dy << K) + OFF) and the one below, columns
+                        // 2 dx and 2 dx + 1.  The four windows cover 2 HALF + 2 rows of that column pair: each is read ONCE, as 8 bytes
+                        const pyr_f2* c = reinterpret_cast<const pyr_f2*>(&rowf[y << K][2 * dx]);
+                        float w[2][2 * HALF + 2];
+#pragma unroll
+                        for (int q = 0; q < 2 * HALF + 2; q++) {
+                            const pyr_f2 v = c[q * (NC / 2)];
+                            w[0][q] = v.x; w[1][q] = v.y;
+                        }
+                        float p[2][2];                                     // [row of the block][column]
+#pragma unroll
+                        for (int a = 0; a < 2; a++)
+#pragma unroll
+                            for (int e = 0; e < 2; e++) {
+                                float sacc = __builtin_fmaf(w[e][HALF + a], kw[HALF], 0.f);
+#pragma unroll
+                                for (int k = 1; k <= HALF; k++) sacc = __builtin_fmaf(w[e][HALF + a + k] + w[e][HALF + a - k], kw[HALF + k], sacc);
+                                p[a][e] = sacc;
+                            }
+                        o = ((p[0][0] + p[0][1]) + (p[1][0] + p[1][1])) * 0.25f;
                     }
                     out[y * WL + dx] = o;
                 }
@@ -216,7 +276,31 @@ __device__ __forceinline__ void pyramid_body(char* lds, int blk, const uint8_t* 
             W::next(dyl, dx);
         }
     }
+    // the rows the next step takes over, LDS rows [NEW, SROWS): read before that step's barrier, written to rows [0, KEEP) behind it
+    if (G::STEPS > 1 && more && tid < G::KEEP * NC / 4) kept = reinterpret_cast<const pyr_f4*>(&rowf[G::NEW][0])[tid];
 }
+
+// blk = frame * TILES + band of this scale: the band's steps, top to bottom.  pairdiff: see pyramid_step
+template <int K>
+__device__ __forceinline__ void pyramid_body(char* lds, int blk, const uint8_t* __restrict__ small, const FbConsts* __restrict__ C,
+                                             float* __restrict__ I, int n = 0, int* __restrict__ pairdiff = nullptr)
+{
+    using G = PyrGeo<K>;
+    constexpr int WL = G::WL;
+    const int f = blk / G::TILES, t = blk - f * G::TILES;
+    const int dy0 = t * G::BAND;                         // the band's first output row
+    const uint8_t* img = small + (int64_t)f * AVD_NPIX;
+    float* out = I + ((int64_t)f * WL + dy0) * WL;
+    int* diffword = K == 1 && pairdiff != nullptr && f + 1 < n ? pairdiff + blk : nullptr;
+    float kw[G::KS];                                     // the tap weights (uniform: scalar registers)
+#pragma unroll
+    for (int q = 0; q < G::KS; q++) kw[q] = C->gk[K][q];
+    const int y_first = (K == 0 ? dy0 : (dy0 << K) + G::OFF) - G::HALF;
+    pyr_f4 kept = {0.f, 0.f, 0.f, 0.f};
+    for (int step = 0; step < G::STEPS; step++)
+        pyramid_step<K>(lds, img, kw, out + step * G::TR * WL, y_first + step * G::NEW, step ? G::KEEP : 0, kept, step + 1 < G::STEPS, diffword);
+}
+
 
 // the four scales of every frame in ONE launch (coarsest first: its workgroups do the most work): the small scales
 // alone cannot fill the chip (600 workgroups at 40 px for a 120-frame clip) and used to run one after the other

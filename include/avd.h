@@ -560,6 +560,8 @@ int avd_kernel_ms(avd_ctx* ctx, int kernel_id, float* ms);
 /* Test hook: copy an internal device buffer of the last call to host.
  * name: "area" uint8[n][1024]; "pyr<L>" float[n][hL][wL]; "poly<L>" float[n][hL][wL][5];
  * "flow<L>" float[n-1][2][hL][wL] (planar, after the last iteration at level L).
+ * "pairdiff" int32[n-1][20]: per pair (f, f + 1) and tile of the pyramid kernel's 160-px scale (16 source rows and one on either side), non-zero where
+ * the two frames differ in the tile's rows; a pair of bit-identical frames is all zero.
  * "ingest_plan" int32[8], host state rather than a device buffer: what the last ingest launch of the context ran --
  * h, w, rows_per_band, nbands, LDS tile pitch, NI of k_preprocess_vec, the staged kernel of BGR24 / RGB24 / RGBP (0: the generic kernel), dynamic LDS bytes requested,
  * kernel (0 bgr_scalar, 1 bgr_vec16, 2 bgr_staged, 3 nv12_scalar, 4 nv12_tables, 5 i420_scalar, 6 i420_tables, 7 nv12_strip, 8 i420_strip, 9 px32_scalar, 10 px32_vec16, 11 rgbp_scalar, 12 rgbp_vec16, 13 rgbp_staged,
