@@ -40,13 +40,8 @@ static int build_geom(avd_ctx* ctx, Geom& g, int h, int w)
     const BandPlan plan = band_plan(w);
     const int R = plan.rows_per_band;
     const int nbands = (h + R - 1) / R;
-    std::vector<int> band_dy(nbands + 1, AVD_SMALL);
-    for (int b = 0; b <= nbands; b++) {
-        int d = 0;
-        while (d < AVD_SMALL && lt.y0[d] < b * R) d++;
-        band_dy[b] = d;
-    }
-    band_dy[nbands] = AVD_SMALL;
+    std::vector<int> band_dy;
+    build_band_dy(lt, h, R, band_dy);
     TableBlob tb;
     std::vector<LinTap> lxt(AVD_SMALL), lyt(AVD_SMALL);
     for (int d = 0; d < AVD_SMALL; d++) {

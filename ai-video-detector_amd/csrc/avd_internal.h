@@ -29,6 +29,8 @@ struct LinearTab {
     std::vector<short> a0, a1, b0, b1;        // 11-bit fixed-point weights
 };
 void build_linear_tab(int src_h, int src_w, int dst_h, int dst_w, LinearTab& t);
+// the output rows each band of rows_per_band source rows forms: [band_dy[b], band_dy[b + 1]), nbands + 1 entries, the last one dst_h
+void build_band_dy(const LinearTab& t, int src_h, int rows_per_band, std::vector<int>& band_dy);
 
 // INTER_AREA uint8 -> 32x32 (reference video.py:6): per destination index a run of
 // consecutive source indices with (first, middle, last) float weights.

@@ -81,6 +81,20 @@ void build_linear_tab(int src_h, int src_w, int dst_h, int dst_w, LinearTab& t)
     linear_axis(src_h, dst_h, false, t.y0, t.y1, t.b0, t.b1);
 }
 
+// band_dy[b] = the first output row whose upper source row y0 lies in band b or below it, band_dy[nbands] = dst_h: band b of rows_per_band
+// source rows forms the output rows [band_dy[b], band_dy[b + 1]).  One walk: y0 does not decrease.
+void build_band_dy(const LinearTab& t, int src_h, int rows_per_band, std::vector<int>& band_dy)
+{
+    const int dst_h = (int)t.y0.size();
+    const int nbands = (src_h + rows_per_band - 1) / rows_per_band;
+    band_dy.assign(nbands + 1, dst_h);
+    int d = 0;
+    for (int b = 0; b < nbands; b++) {
+        while (d < dst_h && t.y0[d] < b * rows_per_band) d++;
+        band_dy[b] = d;
+    }
+}
+
 int build_area_tab(int src_h, int src_w, int dst_h, int dst_w, AreaTab& t)
 {
     const double sx = 1. / ((double)dst_w / src_w), sy = 1. / ((double)dst_h / src_h);
