@@ -1013,6 +1013,31 @@ class Context:
         """Frames the selected slot has absorbed since it was last emptied (0: it is empty, or no slot is selected)."""
         return self.get_option("stream_frames")
 
+    # -- several clips of ONE call continue a slot each (include/avd.h, option "stream_map") -------------------------------------------------
+    def stream_map(self, mapping=None):
+        """mapping: {clip position 0 ... 63: slot 1 ... 8} -- the clip at that position of every following analyze_* call continues that slot,
+        every other clip starts a new one.  The map is replaced by `mapping`; None or {} clears it.  A refused entry leaves the map empty."""
+        self.set_option("stream_map", -1)
+        try:
+            for position, slot in sorted((mapping or {}).items()):
+                position, slot = int(position), int(slot)
+                if not 0 <= position <= 63 or not 1 <= slot <= 8:
+                    raise ValueError(f"stream_map: position 0 ... 63 -> slot 1 ... 8, got {position} -> {slot}")
+                self.set_option("stream_map", (position << 4) | slot)
+        except Exception:
+            self.set_option("stream_map", -1)
+            raise
+
+    def stream_state(self) -> np.ndarray:
+        """int32[8][2]: per slot the frames it has absorbed since it was last emptied and the clip position mapped to it (-1: none);
+        avd_debug_fetch "stream_state"."""
+        return self.debug_fetch("stream_state", (8, 2), np.int32)
+
+    def stream_call(self) -> np.ndarray:
+        """int32[4] of the last analyze_* call: clips that continued a filled slot, restore launches, save launches, frames in the per-frame
+        buffers (restored frames included); avd_debug_fetch "stream_call"."""
+        return self.debug_fetch("stream_call", (4,), np.int32)
+
     def set_profiling(self, on: bool):
         self._check(self._L.avd_set_profiling(self._h, int(bool(on))))
 

@@ -252,7 +252,8 @@ class FrameAnalyzer:
         """_flush_list without the wait: enqueue only (analyze_frame_lists_async); -> what the library reads until the context is drained"""
         return self.ctx.analyze_frame_lists_async([(self._list_frames(items, fmt), fmt)], rec, [rotate], [full_range])[0]
 
-    def _list_frames(self, items, fmt) -> list:
+    @staticmethod
+    def _list_frames(items, fmt) -> list:
         single = fmt in _lib._PACKED or fmt == _lib.AVD_FMT_RGBP          # one array per frame: interleaved [H,W,C], or channels first [3,H,W]
         lead = 1 if fmt == _lib.AVD_FMT_RGBP else 0                       # axes in front of the rows
         frames = [(np.asarray(it),) if single else tuple(np.asarray(p) for p in it) for it in items]
@@ -305,6 +306,84 @@ class FrameAnalyzer:
     def records_stream_i010(self, surfaces, rotate: int = 0, full_range: bool = False, slot: Optional[int] = None,
                             resident_carry: Optional[bool] = None) -> np.ndarray:
         return self._stream_list(surfaces, _lib.AVD_FMT_I010, rotate, full_range, slot, resident_carry)
+
+
+class StreamMux:
+    """Several live streams on ONE context, one call per round: stream i is clip position i of every call and continues stream slot i + 1
+    (include/avd.h, option "stream_map"), so a round of K short chunks costs one Farneback launch sequence instead of K -- calls of 1 to 8
+    frames are bound by their launches, not by pixels.  The records of each stream are those of its frames analysed as
+    one clip.
+
+        mux = StreamMux(chunk=4)
+        per_stream = mux.run([(decoder_a, AVD_FMT_NV12), (decoder_b, AVD_FMT_I420, 1), (camera, AVD_FMT_BGR24)])
+    """
+
+    MAX_STREAMS = 8                                   # the context's stream slots
+
+    def __init__(self, ctx: Optional["_lib.Context"] = None, chunk: int = 8, device: int = 0):
+        self._own = ctx is None
+        self.ctx = ctx or _lib.Context(device)
+        self.chunk = max(1, int(chunk))
+
+    def close(self):
+        if self._own and self.ctx is not None:
+            self.ctx.close()
+        self.ctx = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def run(self, streams) -> list:
+        """streams: up to eight (items, fmt[, rotate[, full_range]]) -- items an iterable of frames (a packed layout or AVD_FMT_RGBP: one array
+        per frame) or of plane tuples, as the records_stream* methods of FrameAnalyzer take them.  -> one record array per stream.
+        Each round pulls up to `chunk` items from every stream that still has some and submits them as ONE asynchronous call; the next round is
+        pulled -- decoded -- while that one runs.  A stream with nothing to give keeps its position as an empty list.  The slots used are
+        emptied first and the map is cleared at the end, also when an iterator raises (then after the round in flight has been drained)."""
+        specs = []
+        for s in streams:
+            s = tuple(s)
+            if not 2 <= len(s) <= 4:
+                raise ValueError("a stream is (items, fmt[, rotate[, full_range]])")
+            specs.append((iter(s[0]), s[1], s[2] if len(s) > 2 else 0, bool(s[3]) if len(s) > 3 else False))
+        if len(specs) > self.MAX_STREAMS:
+            raise ValueError(f"at most {self.MAX_STREAMS} streams: a context has {self.MAX_STREAMS} stream slots")
+        if not specs:
+            return []
+        ctx = self.ctx
+        fmts, rotates, ranges = [s[1] for s in specs], [s[2] for s in specs], [s[3] for s in specs]
+        out = [[] for _ in specs]
+
+        def pull():
+            return [list(itertools.islice(s[0], self.chunk)) for s in specs]
+
+        for i in range(len(specs)):
+            ctx.stream_reset(i + 1)
+        ctx.stream_map({i: i + 1 for i in range(len(specs))})
+        try:
+            bufs = pull()
+            while any(bufs):
+                rec = np.zeros(sum(len(b) for b in bufs), _lib.RECORD_DTYPE)
+                lists = [(FrameAnalyzer._list_frames(b, f), f) for b, f in zip(bufs, fmts)]
+                keep = ctx.analyze_frame_lists_async(lists, rec, rotates, ranges)      # the round's arrays stay referenced (bufs, keep) until it is drained
+                nxt = pull()
+                ctx.synchronize()
+                at = 0
+                for o, b in zip(out, bufs):
+                    if b:
+                        o.append(rec[at:at + len(b)])
+                    at += len(b)
+                del keep
+                bufs = nxt
+        finally:
+            # an exception of an iterator finds a round in flight: bufs, keep and rec are alive up to here, and it is drained first
+            try:
+                ctx.synchronize()
+            finally:
+                ctx.stream_map(None)
+        return [np.concatenate(o) if o else np.zeros(0, _lib.RECORD_DTYPE) for o in out]
 
 
 class ClipsInFlight:

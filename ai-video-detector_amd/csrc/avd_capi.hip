@@ -420,8 +420,9 @@ static hipError_t wait_helping(avd_ctx* ctx, hipEvent_t ev)
 // One row per option; what an option MEANS is documented at its field in avd_ctx (avd_internal.h).  A read-only row is a counter: avd_set_option does
 // not know its name.  norm brings a value into range (false: refused with `refused`, the old value stays); env: read by avd_create through from_env and norm.
 // act / read (the stream options): the option is not a plain field -- avd_set_option calls act with the accepted value, avd_get_option returns read's.
+// check (the stream options): what the context's state refuses of a value that norm accepted -- the message, or null.
 struct Option { const char* name; int avd_ctx::*field; bool writable; bool (*norm)(int& v); const char* env; int (*from_env)(const char* text); const char* refused;
-                void (*act)(avd_ctx* ctx, int v); int (*read)(const avd_ctx* ctx); };
+                void (*act)(avd_ctx* ctx, int v); int (*read)(const avd_ctx* ctx); const char* (*check)(const avd_ctx* ctx, int v); };
 static bool opt_any(int&) { return true; }
 static bool opt_flag(int& v) { v = v != 0; return true; }
 template <int AND, int OR = 0> static bool opt_mask(int& v) { v = (v & AND) | OR; return true; }
@@ -440,6 +441,31 @@ static void stream_reset(avd_ctx* ctx, int v)
 static int stream_reset_read(const avd_ctx*) { return 0; }
 // "stream_frames": what the SELECTED slot has absorbed since it was last emptied
 static int stream_frames(const avd_ctx* ctx) { return ctx->stream_slot ? ctx->streams[ctx->stream_slot - 1].frames : 0; }
+// "stream_slot" and "stream_map" never hold at once: selecting a slot is refused while a position is mapped, mapping one while a slot is selected
+static const char* stream_slot_check(const avd_ctx* ctx, int v)
+{
+    return v != 0 && ctx->stream_mapped > 0 ? "stream_slot: refused while \"stream_map\" maps a position (clear the map first: \"stream_map\" = -1)" : nullptr;
+}
+// "stream_map": (position << 4) | slot -- position 0 ... 63, slot 1 ... 8 maps it, slot 0 unmaps it; -1 clears the map.  Reads back as the number of
+// mapped positions.  avd_set_option has drained the context.
+static const char* stream_map_check(const avd_ctx* ctx, int v)
+{
+    if (v == -1) return nullptr;
+    const int pos = v >> 4, slot = v & 15;
+    if (v < 0 || pos >= kStreamMapPositions || slot > kStreamSlots) return "stream_map: (position << 4) | slot with position 0 ... 63 and slot 0 ... 8, or -1 (clear the map)";
+    if (ctx->stream_slot != 0) return "stream_map: refused while \"stream_slot\" selects a slot (set it to 0 first)";
+    for (int p = 0; slot != 0 && p < kStreamMapPositions; p++)
+        if (p != pos && ctx->stream_map[p] == slot) return "stream_map: the slot is already mapped at another position";
+    return nullptr;
+}
+static void stream_map_set(avd_ctx* ctx, int v)
+{
+    if (v == -1) for (int& s : ctx->stream_map) s = 0;
+    else ctx->stream_map[v >> 4] = v & 15;
+    ctx->stream_mapped = 0;
+    for (int s : ctx->stream_map) ctx->stream_mapped += s != 0;
+}
+static int stream_map_read(const avd_ctx* ctx) { return ctx->stream_mapped; }
 static int env_any_base(const char* e) { return (int)std::strtol(e, nullptr, 0); }
 static int env_fb_mode(const char* e) { return (std::strcmp(e, "exact") == 0 || std::strcmp(e, "0") == 0) ? 0 : 1; }
 static const Option kOptions[] = {
@@ -459,7 +485,8 @@ static const Option kOptions[] = {
     {"cnn_chunk", &avd_ctx::cnn_chunk, true, opt_cnn_chunk, nullptr, nullptr, "cnn_chunk: 1 ... 1024 frames per forward pass"},
     {"cnn_tap", &avd_ctx::cnn_tap, true, opt_cnn_tap, nullptr, nullptr, "cnn_tap: 0 (off), 1 input image, 2 ... 54 convolution 0 ... 52, 55 max pool, 56 pooled features"},
     {"rerun_pairs", &avd_ctx::last_rerun, false, opt_any},   // pairs of the last drained call that the fast level kernel flagged and the exact kernels re-ran
-    {"stream_slot", &avd_ctx::stream_slot, true, opt_stream, nullptr, nullptr, "stream_slot: 0 (every call starts a new clip) or slot 1 ... 8"},
+    {"stream_slot", &avd_ctx::stream_slot, true, opt_stream, nullptr, nullptr, "stream_slot: 0 (every call starts a new clip) or slot 1 ... 8", nullptr, nullptr, stream_slot_check},
+    {"stream_map", nullptr, true, opt_any, nullptr, nullptr, nullptr, stream_map_set, stream_map_read, stream_map_check},
     {"stream_reset", nullptr, true, opt_stream, nullptr, nullptr, "stream_reset: 0 (every slot) or slot 1 ... 8", stream_reset, stream_reset_read},
     {"stream_frames", nullptr, false, opt_any, nullptr, nullptr, nullptr, nullptr, stream_frames},
 };
@@ -653,7 +680,7 @@ static int impl_preprocess(avd_ctx* ctx, const IngestClip& k, uint8_t* small320,
         if (lap_sumsq) lap_sumsq[f] = (int64_t)lap[2 * f + 1];
     }
     ctx->last_n = n;
-    ctx->rec_n = 0;
+    ctx->rec_n = 0; ctx->rec_mapped = 0;
     return AVD_OK;
 }
 
@@ -696,7 +723,7 @@ static int impl_farneback_pairs(avd_ctx* ctx, const uint8_t* small320, int mem, 
     // return above leaves them behind unclosed, which impl_synchronize does not read either)
     kmark_reset(ctx);
     ctx->last_n = std::min(n, ctx->ws.fb_cap + 1);
-    ctx->rec_n = 0;
+    ctx->rec_n = 0; ctx->rec_mapped = 0;
     return AVD_OK;
 }
 
@@ -706,23 +733,30 @@ static int impl_farneback_pairs(avd_ctx* ctx, const uint8_t* small320, int mem, 
 constexpr int kStreamSmallWords = AVD_NPIX / 16, kStreamHashWords = 1024 / 16, kStreamWords = kStreamSmallWords + kStreamHashWords + 1;
 static_assert(kStreamHashAt == (size_t)kStreamSmallWords * 16 && kStreamLapAt == (size_t)(kStreamSmallWords + kStreamHashWords) * 16 &&
               kStreamPrevBytes == (size_t)kStreamWords * 16, "the slot's layout in 16-byte words");
+// One launch serves every slot of a call (option "stream_map": up to eight clips continue a slot each): the grid is (words of a slot frame,
+// entries of the table), and the table -- which slot buffer goes with which frame of the buffers -- is a kernel argument by value.
+struct StreamCopyEntry { uint4* kept; int frame; };
+struct StreamCopyTable { StreamCopyEntry e[kStreamSlots]; };
 __global__ __launch_bounds__(256) void k_stream_copy(uint4* __restrict__ small, uint4* __restrict__ hash, uint4* __restrict__ lap,
-                                                    uint4* __restrict__ kept, int save)
+                                                    const StreamCopyTable table, int save)
 {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= kStreamWords) return;
-    uint4* const frame = i < kStreamSmallWords ? small + i : (i < kStreamSmallWords + kStreamHashWords ? hash + (i - kStreamSmallWords) : lap);
-    if (save) kept[i] = *frame;
-    else *frame = kept[i];
+    const StreamCopyEntry e = table.e[blockIdx.y];
+    const size_t f = (size_t)e.frame;
+    uint4* const frame = i < kStreamSmallWords ? small + f * kStreamSmallWords + i
+                       : (i < kStreamSmallWords + kStreamHashWords ? hash + f * kStreamHashWords + (i - kStreamSmallWords) : lap + f);
+    if (save) e.kept[i] = *frame;
+    else *frame = e.kept[i];
 }
 
-// save: frame f of the buffers -> slot; else slot -> frame f.  (A frame's rows are 16-byte aligned: 102 400, 1 024 and 16 bytes a frame.)
-static hipError_t stream_copy(avd_ctx* ctx, StreamSlot& s, int f, bool save)
+// save: each entry's frame of the buffers -> its slot; else slot -> frame.  (A frame's rows are 16-byte aligned: 102 400, 1 024 and 16 bytes a frame.)
+// The frames lie inside the buffers the call reserved (avd_ws_reserve_frames), the slots' buffers are reserved in pass 1.
+static hipError_t stream_copy(avd_ctx* ctx, const StreamCopyTable& table, int entries, bool save)
 {
     Workspace& ws = ctx->ws;
-    hipLaunchKernelGGL(k_stream_copy, dim3((kStreamWords + 255) / 256), dim3(256), 0, ctx->stream, reinterpret_cast<uint4*>(ws.d_small + (size_t)f * AVD_NPIX),
-                       reinterpret_cast<uint4*>(ws.d_hash + (size_t)f * 1024), reinterpret_cast<uint4*>(ws.d_lap + 2 * (size_t)f),
-                       reinterpret_cast<uint4*>(s.d_prev.p), save ? 1 : 0);
+    hipLaunchKernelGGL(k_stream_copy, dim3((kStreamWords + 255) / 256, entries), dim3(256), 0, ctx->stream, reinterpret_cast<uint4*>(ws.d_small.p),
+                       reinterpret_cast<uint4*>(ws.d_hash.p), reinterpret_cast<uint4*>(ws.d_lap.p), table, save ? 1 : 0);
     return hipGetLastError();
 }
 
@@ -743,21 +777,31 @@ static int impl_analyze_async(avd_ctx* ctx, const IngestClip* clips, int nclips,
         total += clips[c].n;
         live += clips[c].n > 0;
     }
-    // Option "stream_slot": the call continues the clip whose last frame the slot holds.  That frame (pred = 1) goes in front of the call's own
+    // Option "stream_slot": the call continues the clip whose last frame the slot holds.  That frame (its carry) goes in front of the call's own
     // frames in the per-frame buffers, the one clip starts at frame 1, and everything behind the ingest -- Farneback chunks, flags, the exact
     // re-run, the record kernel -- runs over n + 1 frames as it would for a call that had been handed the frame again; records 1 .. n go out.
-    StreamSlot* const stream = ctx->stream_slot ? &ctx->streams[ctx->stream_slot - 1] : nullptr;
-    if (stream && live > 1) { ctx->err = "stream_slot: one clip per call"; return AVD_ERR_ARG; }
-    const int pred = stream && stream->frames > 0 ? 1 : 0;
-    if (total + pred > (1 << 24)) { ctx->err = "too many frames in one call"; return AVD_ERR_ARG; }
-    if (total == 0) return AVD_OK;
+    // Option "stream_map": the same for several clips of one call -- the clip at position p continues slot stream_map[p], each behind its own
+    // restored frame.  Where every clip lies, which frames have no predecessor and which records go out is the plan (avd_stream_plan.h);
+    // with "stream_slot" it is the one clip at frame 1 behind the slot's frame, without a slot the batch layout.
+    if (ctx->stream_slot && live > 1) { ctx->err = "stream_slot: one clip per call"; return AVD_ERR_ARG; }
+    const bool mapped = ctx->stream_mapped > 0;
+    std::vector<StreamSlot*> stream((size_t)nclips, nullptr);     // per clip: the slot it continues (a clip that brings frames only: an empty one leaves its slot alone)
+    std::vector<avd_stream::ClipIn> plan_in((size_t)nclips);
+    for (int c = 0; c < nclips; c++) {
+        const int k = mapped ? (c < kStreamMapPositions ? ctx->stream_map[c] : 0) : ctx->stream_slot;
+        if (k && clips[c].n > 0) stream[c] = &ctx->streams[k - 1];
+        plan_in[c] = {clips[c].n, !stream[c] ? avd_stream::kUnmapped : (stream[c]->frames > 0 ? avd_stream::kMappedFilled : avd_stream::kMappedEmpty)};
+    }
+    if (total > (1 << 24)) { ctx->err = "too many frames in one call"; return AVD_ERR_ARG; }
+    if (total == 0) { for (int& v : ctx->stream_call) v = 0; return AVD_OK; }
+    const avd_stream::Plan plan = avd_stream::plan_call(plan_in.data(), nclips);
+    if (plan.total > (1 << 24)) { ctx->err = "too many frames in one call"; return AVD_ERR_ARG; }
     if (!records) { ctx->err = "null pointer"; return AVD_ERR_ARG; }
-    const int own = (int)total;                            // the caller's frames = the records that go out
-    const int n = own + pred;                              // frames in the buffers
+    const int own = plan.own;                              // the caller's frames = the records that go out
+    const int n = plan.total;                              // frames in the buffers
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     Workspace& ws = ctx->ws;
     // pass 1: geometry tables (cached), each clip's place in the buffers and their sizes -- everything is reserved before the first launch of the call
-    int frames = pred;
     size_t rowbuf_elems = 0, lappart_elems = 0, stage_bytes = 0;
     CallLists lists;
     plan_lists(clips, nclips, lists);
@@ -768,9 +812,8 @@ static int impl_analyze_async(avd_ctx* ctx, const IngestClip* clips, int nclips,
         if (k.n == 0) continue;
         ClipSlot& slot = slots[c];
         if (int e = avd_ws_geometry(ctx, k.disp_h(), k.disp_w(), slot)) return e;
-        slot.f0 = frames; slot.rowbuf_off = rowbuf_elems; slot.lappart_off = lappart_elems;
+        slot.f0 = plan.f0[c]; slot.rowbuf_off = rowbuf_elems; slot.lappart_off = lappart_elems;
         stage_at[c] = stage_bytes;
-        frames += k.n;
         rowbuf_elems += rowbuf_elems_for(slot.pre, k.n);
         lappart_elems += lappart_elems_for(slot.pre, k.n);
         stage_bytes += lists.total(k, c);
@@ -779,8 +822,17 @@ static int impl_analyze_async(avd_ctx* ctx, const IngestClip* clips, int nclips,
     if (int e = avd_ws_reserve_fb(ctx, n)) return e;
     if (int e = ws.d_stage.reserve(ctx, stage_bytes)) return e;
     if (int e = reserve_lists(ctx, lists)) return e;
-    if (stream)
-        if (int e = stream->d_prev.reserve(ctx, kStreamPrevBytes)) return e;     // an empty slot's first call (frames = 0: still empty if the call fails)
+    // every continued slot's buffer (an empty slot's first call; frames = 0: still empty if the call fails), and the two tables of the copy kernel
+    StreamCopyTable restore{}, save{};
+    int nrestore = 0, nsave = 0;
+    for (int c = 0; c < nclips; c++) {
+        if (!stream[c]) continue;
+        if (int e = stream[c]->d_prev.reserve(ctx, kStreamPrevBytes)) return e;
+        if (nsave >= kStreamSlots) { ctx->err = "internal error: more continued clips than stream slots"; return AVD_ERR_DEVICE; }
+        uint4* const kept = reinterpret_cast<uint4*>(stream[c]->d_prev.p);
+        if (plan.carry[c] >= 0) restore.e[nrestore++] = {kept, plan.carry[c]};
+        save.e[nsave++] = {kept, plan.f0[c] + clips[c].n - 1};
+    }
     // pass 2: per clip, stage (host input) -> fused full-resolution kernel -> hash, in the clip's slot
     kmark_reset(ctx);
     ctx->ingest.stage_bytes = 0;
@@ -792,9 +844,11 @@ static int impl_analyze_async(avd_ctx* ctx, const IngestClip* clips, int nclips,
     // (host input staged for it) included.
     kmark(ctx, AVD_K_PREPROCESS, stage_mark(ctx, 0));
     bool first_clip = true;
-    // the slot's frame becomes frame 0 (device to device, ordered on the stream like everything else; inside the first region)
-    if (pred) HIP_TRY(ctx, stream_copy(ctx, *stream, 0, false));
+    // each filled slot's frame becomes its clip's carry frame (device to device, ordered on the stream like everything else; inside the first
+    // region): ONE launch for all of them
+    if (nrestore) HIP_TRY(ctx, stream_copy(ctx, restore, nrestore, false));
     if (int e = upload_lists(ctx, clips, nclips, lists)) return e;
+    std::copy(plan.clipstart.begin(), plan.clipstart.end(), ws.h_clipstart.p);
     for (int c = 0; c < nclips; c++) {
         const IngestClip& k = clips[c];
         if (k.n == 0) continue;
@@ -802,8 +856,6 @@ static int impl_analyze_async(avd_ctx* ctx, const IngestClip* clips, int nclips,
         // the tables again: a cache hit (pass 1 built them) unless the call has > kGeomCache geometries -- then pass 1 has evicted this one since,
         // the slot's copies point into freed tables, and they are rebuilt here (same geometry, same sizes: the offsets hold)
         if (int e = avd_ws_geometry(ctx, k.disp_h(), k.disp_w(), slot)) return e;
-        ws.h_clipstart[slot.f0] = 1;
-        for (int i = 1; i < k.n; i++) ws.h_clipstart[slot.f0 + i] = 0;
         if (!first_clip) kmark(ctx, AVD_K_PREPROCESS);
         first_clip = false;
         if (int e = preprocess_clip(ctx, slot, k, stage_at[c], lists, c)) return e;
@@ -811,8 +863,10 @@ static int impl_analyze_async(avd_ctx* ctx, const IngestClip* clips, int nclips,
         if (int e = launch_hash(ctx, slot, k.n)) return e;
     }
     kmark(ctx, AVD_K_OTHER, stage_mark(ctx, 1));
-    const int* clipstart = nullptr;                        // one clip: frame 0 is the only one without a predecessor
-    if (nclips > 1 && !pred) {                             // (a continued clip is one clip behind the slot's frame, whatever empty clips the call lists)
+    const int* clipstart = nullptr;                        // one segment: frame 0 is the only one without a predecessor
+    // more than one segment needs the table (plan.clipstart: 1 at every carry frame and at the first frame of a clip without one, 0 at the first
+    // own frame of a continued clip); a batch without a continued clip uploads it as it always did, whatever empty clips the call lists
+    if (plan.segments > 1 || (nclips > 1 && plan.carries == 0)) {
         HIP_TRY(ctx, hipMemcpyAsync(ws.d_clipstart, ws.h_clipstart, sizeof(int) * n, hipMemcpyHostToDevice, ctx->stream));
         clipstart = ws.d_clipstart;
     }
@@ -826,21 +880,24 @@ static int impl_analyze_async(avd_ctx* ctx, const IngestClip* clips, int nclips,
     if (n < 2) launch_records(ctx, 0, 0, 0, clipstart);     // one frame: no pair, no flow
     else if (int e = run_flow_chunks(ctx, ws.d_small, n, nullptr, nullptr, nullptr, true, clipstart)) return e;
     kmark(ctx, AVD_K_OTHER, stage_mark(ctx, 3));
-    // the call's last frame becomes the slot's: only here, behind everything that can refuse or fail for want of memory (nothing has written
-    // d_small, d_hash or d_lap since the ingest), so that such a call leaves the slot as it was
-    if (stream) HIP_TRY(ctx, stream_copy(ctx, *stream, n - 1, true));
+    // every continued clip's last frame becomes its slot's, in ONE launch: only here, behind everything that can refuse or fail for want of memory
+    // (nothing has written d_small, d_hash or d_lap since the ingest), so that such a call leaves every slot as it was
+    if (nsave) HIP_TRY(ctx, stream_copy(ctx, save, nsave, true));
     // into PINNED memory: a device-to-host copy into the caller's pageable buffer would block this thread until
     // the whole call is done and it would not be asynchronous at all; avd_synchronize hands the records over
     // (all n of them, the slot's frame included: the deferred re-run finds its chunk's flag words where it always does)
+    ctx->pending_runs = plan.runs;                         // (can throw: while an error still drops the tail, and before the counters move)
     HIP_TRY(ctx, hipMemcpyAsync(ws.h_rec, ws.d_rec, sizeof(avd_frame_record) * n, hipMemcpyDeviceToHost, ctx->stream));
     tail_on_error.ok = true;
-    if (stream) stream->frames = (int)std::min<int64_t>((int64_t)stream->frames + own, INT32_MAX);
-    ctx->pending_out = records; ctx->pending_n = own; ctx->pending_off = pred;
+    for (int c = 0; c < nclips; c++)
+        if (stream[c]) stream[c]->frames = (int)std::min<int64_t>((int64_t)stream[c]->frames + clips[c].n, INT32_MAX);
+    ctx->pending_out = records;
+    ctx->stream_call[0] = plan.carries; ctx->stream_call[1] = nrestore > 0; ctx->stream_call[2] = nsave > 0; ctx->stream_call[3] = n;
     if (ctx->tail.active) tail_register(ctx);              // from here on a waiting thread may settle this call's tail
     if (!ctx->counted_in_flight) { ctx->counted_in_flight = 1; g_calls_in_flight.fetch_add(1, std::memory_order_relaxed); }
     kmark(ctx, AVD_K_COUNT, stage_mark(ctx, 4));           // end of the last region
     ctx->last_n = n;
-    ctx->rec_n = own; ctx->rec_off = pred;
+    ctx->rec_n = own; ctx->rec_off = plan.runs.front().first; ctx->rec_mapped = mapped;
     return AVD_OK;
 }
 
@@ -870,21 +927,26 @@ static int impl_synchronize(avd_ctx* ctx)
         // was waiting for its own context has settled this one already
         const hipError_t e = ctx->tail_registered ? wait_helping(ctx, ctx->tail_ev) : hipStreamSynchronize(ctx->stream);
         tail_unregister(ctx);
-        if (e != hipSuccess) { ctx->tail.active = 0; ctx->pending_out = nullptr; ctx->pending_n = 0; ctx->err = hipGetErrorString(e); return AVD_ERR_DEVICE; }
+        if (e != hipSuccess) { ctx->tail.active = 0; ctx->pending_out = nullptr; ctx->err = hipGetErrorString(e); return AVD_ERR_DEVICE; }
         if (ctx->tail.active) ctx->tail_rc = tail_settle(ctx);
     }
     if (ctx->tail_rc) {                                     // the re-run could not be enqueued (by this thread or by a helper): the call has failed
         const int rc = ctx->tail_rc;
-        ctx->tail_rc = 0; ctx->pending_out = nullptr; ctx->pending_n = 0;
+        ctx->tail_rc = 0; ctx->pending_out = nullptr;
         return rc;
     }
     HIP_TRY(ctx, wait_helping(ctx, nullptr));
     if (ctx->pending_out) {
-        const avd_frame_record* const got = ctx->ws.h_rec + ctx->pending_off;
-        std::memcpy(ctx->pending_out, got, sizeof(avd_frame_record) * ctx->pending_n);
+        // the call's own frames, run after run (avd_stream_plan.h): the frames restored from stream slots lie between the runs and stay behind
+        avd_frame_record* out = ctx->pending_out;
         ctx->last_rerun = 0;
-        for (int i = 0; i < ctx->pending_n; i++) ctx->last_rerun += got[i].reserved != 0;
-        ctx->pending_out = nullptr; ctx->pending_n = 0;
+        for (const avd_stream::Run& r : ctx->pending_runs) {
+            const avd_frame_record* const got = ctx->ws.h_rec + r.first;
+            std::memcpy(out, got, sizeof(avd_frame_record) * (size_t)r.count);
+            for (int i = 0; i < r.count; i++) ctx->last_rerun += got[i].reserved != 0;
+            out += r.count;
+        }
+        ctx->pending_out = nullptr;
     }
     // only a mark list that an avd_analyze_* call closed (its last mark is AVD_K_COUNT: impl_analyze_async, tail_settle) is a call's timeline;
     // anything else -- marks of a call that failed half way -- would drop its last region and replace the figures of the last drained call
@@ -974,6 +1036,14 @@ static int64_t impl_debug_fetch(avd_ctx* ctx, const char* name, void* out, size_
         const IngestRecord& in = ctx->ingest;
         const char* const no_launch = "no ingest kernel was launched on this context";
         const char* const no_call = "no ingest call has run on this context";
+        // the stream slots as they are now: frames absorbed and the position "stream_map" maps to the slot (-1: none)
+        int stream_state[kStreamSlots][2];
+        for (int k = 0; k < kStreamSlots; k++) {
+            stream_state[k][0] = ctx->streams[k].frames;
+            stream_state[k][1] = -1;
+            for (int p = 0; p < kStreamMapPositions; p++)
+                if (ctx->stream_map[p] == k + 1) stream_state[k][1] = p;
+        }
         // type null: a short `out` gets the first out_bytes; otherwise it is refused with the type's name
         const struct { const char* name; const void* p; size_t bytes; bool recorded; const char* missing; const char* type; } host_state[] = {
             {"ingest_plan", &in.plan, sizeof in.plan, in.launched != 0, no_launch, nullptr},
@@ -983,6 +1053,8 @@ static int64_t impl_debug_fetch(avd_ctx* ctx, const char* name, void* out, size_
             {"ingest_list", in.list, sizeof in.list, in.launched != 0, no_launch, "int32[2]"},
             {"stage_copies", &in.stage_copies, sizeof in.stage_copies, in.stage_copies >= 0, no_call, "int64[1]"},
             {"stage_bytes", &in.stage_bytes, sizeof in.stage_bytes, in.stage_bytes >= 0, no_call, "int64[1]"},
+            {"stream_state", stream_state, sizeof stream_state, true, nullptr, "int32[8][2]"},
+            {"stream_call", ctx->stream_call, sizeof ctx->stream_call, true, nullptr, "int32[4]"},
         };
         for (const auto& e : host_state) {
             if (std::strcmp(name, e.name) != 0) continue;
@@ -1055,7 +1127,7 @@ static int impl_release_workspace(avd_ctx* ctx)
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (int e = impl_synchronize(ctx)) return e;
     ctx->ws = Workspace{};                                  // the uploaded weights (ctx->weights) are state and stay
-    ctx->rec_n = 0;
+    ctx->rec_n = 0; ctx->rec_mapped = 0;
     return AVD_OK;
 }
 
@@ -1066,6 +1138,8 @@ static int impl_set_option(avd_ctx* ctx, const char* name, int value)
     const Option* o = find_option(ctx, name, true);
     if (!o) return AVD_ERR_ARG;
     if (!o->norm(value)) { ctx->err = o->refused; return AVD_ERR_ARG; }
+    if (o->check)
+        if (const char* why = o->check(ctx, value)) { ctx->err = why; return AVD_ERR_ARG; }
     if (o->act) o->act(ctx, value);
     else ctx->*o->field = value;
     return AVD_OK;

@@ -113,6 +113,9 @@ int comm_allgather_records(avd_ctx* ctx, const avd_frame_record* local, int coun
 int comm_allgather_last_records(avd_ctx* ctx, int count, avd_frame_record* all)
 {
     if (count < 0 || (count > 0 && !all)) { ctx->err = "bad arguments"; return AVD_ERR_ARG; }
+    // a call under a non-empty "stream_map" leaves its own records in several runs of ws.d_rec, the restored frames' records between them; they
+    // are not compacted on the device.  Ahead of the communicator check: the refusal needs none
+    if (ctx->rec_mapped) { ctx->err = "avd_allgather_last_records: the last call ran under a non-empty stream_map, its records are not one run on the device (gather them with avd_allgather_records)"; return AVD_ERR_UNSUPPORTED; }
     if (!ctx->comm) { ctx->err = "avd_comm_init has not been called on this context"; return AVD_ERR_ARG; }
     if (count > ctx->rec_n || !ctx->ws.d_rec) { ctx->err = "the last call on this context left fewer records than asked for (only avd_analyze_* calls leave records)"; return AVD_ERR_ARG; }
     if (count == 0) return AVD_OK;

@@ -8,6 +8,7 @@
 #include <vector>
 #include "../../include/avd.h"
 #include "avd_ingest_clip.h"      // IngestClip: one clip of an ingest call, its argument check and its staging plan (host only)
+#include "avd_stream_plan.h"      // where the clips of a call lie when some continue a stream slot (host only)
 
 #define AVD_FB_LEVELS 4            // pyramid scales 1/8,1/4,1/2,1 of 320 (see avd_farneback.hip)
 #define AVD_NPIX (AVD_SMALL * AVD_SMALL)
@@ -247,6 +248,7 @@ struct Weights {
 // gray image, its 1024 hash bits (one per byte) and its two Laplacian moments, in this order.  An avd_analyze_* call with a slot selected puts
 // them in front of its own frames (ClipSlot::f0 = 1) and leaves its last frame here; frames = 0: the slot is empty, whatever d_prev holds.
 constexpr int kStreamSlots = 8;
+constexpr int kStreamMapPositions = 64;          // option "stream_map": the clip positions of a call that can be mapped to a slot
 constexpr size_t kStreamHashAt = AVD_NPIX, kStreamLapAt = AVD_NPIX + 1024, kStreamPrevBytes = kStreamLapAt + 2 * sizeof(unsigned long long);
 static_assert(kStreamLapAt % sizeof(unsigned long long) == 0, "the moments are copied as two 64-bit words");
 struct StreamSlot {
@@ -261,8 +263,7 @@ struct avd_ctx {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     hipEvent_t ev_in = nullptr;                // avd_wait_stream: recorded on the caller's stream, waited for by ours
     avd_frame_record* pending_out = nullptr;   // caller buffer the pinned records are handed to in avd_synchronize
-    int pending_n = 0;
-    int pending_off = 0;                       // the first of them in ws.h_rec (1: the call continued a stream slot, record 0 is the slot's frame)
+    std::vector<avd_stream::Run> pending_runs; // where they lie in ws.h_rec (avd_stream_plan.h): the call's own frames, without the frames restored from stream slots
     hipEvent_t stage_ev[5] = {};
     hipEvent_t kern_ev[12] = {};           // profiling: level320_mark events around the 320-px level's blur launches of a chunk
     int kern_ev_used = 0;
@@ -287,8 +288,14 @@ struct avd_ctx {
     IngestRecord ingest;             // what the last ingest of this context did
     int rec_n = 0;                   // records the last avd_analyze_* call left in ws.d_rec (0 after any other entry point: avd_allgather_last_records checks it)
     int rec_off = 0;                 // ... from this entry on (1: the call continued a stream slot)
+    int rec_mapped = 0;              // that call ran under a non-empty "stream_map": its own records are not one run of ws.d_rec (avd_allgather_last_records refuses)
     StreamSlot streams[kStreamSlots];   // option "stream_slot" = k selects streams[k - 1]
     int stream_slot = 0;             // 0 = every avd_analyze_* call starts a new clip; k = the call continues the clip slot k holds (one clip per call)
+    // option "stream_map": clip position p of every avd_analyze_* call continues slot stream_map[p] (0: it starts a new clip).  A slot is mapped at one
+    // position at most, and the map is empty while stream_slot != 0 (avd_set_option refuses either way): the two ways of choosing slots never hold at once
+    int stream_map[kStreamMapPositions] = {};
+    int stream_mapped = 0;           // positions mapped
+    int stream_call[4] = {};         // debug buffer "stream_call", of the last avd_analyze_* call: clips that continued a filled slot, restore launches, save launches, frames in the buffers
     void* comm = nullptr;            // RCCL communicator (avd_comm.cpp), bound at run time
     int comm_rank = 0, comm_world = 1;
     DevBuf<char> d_comm;             // device staging of the record exchange

@@ -424,7 +424,9 @@ int avd_allgather_records(avd_ctx* ctx, const avd_frame_record* local, int count
 /* The same exchange straight from the device: the first `count` records of this context's LAST avd_analyze_* call
  * (blocking or asynchronous) are gathered from where k_records left them in HBM -- the collective is enqueued on the
  * context's stream behind the analysis, one copy brings the world * count gathered records to `all` (host).  Blocks until
- * they are there; an outstanding asynchronous call is drained too (its own records buffer is filled). */
+ * they are there; an outstanding asynchronous call is drained too (its own records buffer is filled).
+ * Refused (AVD_ERR_UNSUPPORTED, before the communicator is looked at) when that call ran under a non-empty option "stream_map": its own
+ * records are then several runs in HBM with the restored frames' between them, and they are not compacted on the device. */
 int avd_allgather_last_records(avd_ctx* ctx, int count, avd_frame_record* all);
 
 /* Stream ordering for AVD_MEM_DEVICE inputs.  A context launches on its own non-blocking stream, so device memory
@@ -526,10 +528,29 @@ int avd_set_profiling(avd_ctx* ctx, int enable);
  * selected is refused (AVD_ERR_ARG, "stream_slot: one clip per call") before anything is staged.  A refused call, a call that fails before it is
  * enqueued and a call without frames leave the slot as it was.  The layout, geometry, rotation and range may change from call to call.  A slot is state,
  * not scratch: it survives avd_release_workspace and every call in between (other slots, slot-0 analyses, avd_preprocess_*, avd_farneback_pairs -- which
- * ignore the option -- audio, the extensions); avd_destroy frees it.  One context has eight slots and so serves up to eight streams in turn.
+ * ignore the option -- audio, the extensions); avd_destroy frees it.  One context has eight slots and so serves up to eight streams in turn,
+ * or with "stream_map" (below) several of them in ONE call.
  * avd_debug_fetch "small" of a call that continued a filled slot begins with the slot's frame ("area": with an entry that is not defined).
  * "stream_reset": setting k = 1 ... 8 empties slot k, 0 empties all eight (other values are refused); it reads back as 0.
  * "stream_frames" (read-only): frames the selected slot has absorbed since it was last emptied; 0 for an empty slot and with slot 0 selected.
+ * "stream_map": several clips of one call continue a slot each -- a service that watches several live streams, or drains several decoder pools, pays the
+ * Farneback launch sequence once per call instead of once per stream (calls of 1 to 8 frames are bound by their launches, not by pixels).  Durable, like
+ * "stream_slot".  The value is (position << 4) | slot with position 0 ... 63 and slot 0 ... 8: slot 1 ... 8 makes the clip at position `position` of every
+ * following avd_analyze_* call (blocking or asynchronous, whatever entry it is made through) continue that slot, slot 0 unmaps the position; -1 clears
+ * the whole map; it reads back as the number of mapped positions.  Refused with AVD_ERR_ARG, the map unchanged and a message that begins "stream_map:":
+ * any other value; a slot that is already mapped at another position; any value but -1 while "stream_slot" is not 0.  Setting "stream_slot" to k != 0
+ * while the map is not empty is refused too (AVD_ERR_ARG, the old value stays): the two ways of choosing slots never hold at once.  Positions >= 64 cannot
+ * be mapped: clips there start new clips.  With a non-empty map a clip at a mapped position continues its slot exactly as the one-clip call with
+ * "stream_slot" = k does (an empty slot: today's call; a filled one: its first record is that of the pair (slot frame, frame 0)), a clip at an unmapped
+ * position starts a new clip, and the records go out clip after clip, the callers' own frames only.  An empty clip, and a mapped position the call does not
+ * list, leave their slot untouched.  Afterwards every continued slot holds its clip's last frame and has absorbed the clip's n frames; "rerun_pairs" counts
+ * the flagged records among those handed out.  The slots' frames are restored by ONE launch ahead of the ingest (none if no continued slot is filled) and
+ * saved by ONE launch behind the Farneback stage, whatever the number of streams; the Farneback stage runs once over all frames of the call, each
+ * continued clip behind its restored frame.  A refused call, a call that fails while it is enqueued and a call without frames leave every slot as it was.
+ * avd_preprocess_* and avd_farneback_pairs ignore the map, as they ignore "stream_slot".  After a call made under a non-empty map
+ * avd_allgather_last_records is refused (AVD_ERR_UNSUPPORTED, naming stream_map): the restored frames' records lie between the clips' in HBM and
+ * compacting them on the device is left out; gather the handed-out records with avd_allgather_records.  Left out as well: each clip still has its own
+ * preprocess and hash launch, whatever geometries the clips share.
  * avd_get_option returns the value an option has now (environment defaults included) and the read-only "rerun_pairs" and "stream_frames". */
 int avd_set_option(avd_ctx* ctx, const char* name, int value);
 int avd_get_option(avd_ctx* ctx, const char* name, int* value);
@@ -590,6 +611,11 @@ int avd_kernel_ms(avd_ctx* ctx, int kernel_id, float* ms);
  * "audio_xw" double[nwin][win]: the windowed samples seg * hanning of that call (a short last window fills only its first `last` entries).
  * "audio_mag" double[nwin][win / 2 + 1]: the magnitudes |rfft| + 1e-9 its sums were taken over (a short last window: its first last / 2 + 1
  * entries).  Both are an error before any such call and after avd_release_workspace.
+ * "stream_state" int32[8][2], host state: for each stream slot 1 ... 8 the frames it has absorbed since it was last emptied and the clip position
+ * option "stream_map" maps to it (-1: none).
+ * "stream_call" int32[4], host state, of the last avd_analyze_* call that brought frames: the clips that continued a FILLED slot, the launches that restored
+ * slot frames (0 or 1), the launches that saved them (0 or 1), and the frames in the per-frame buffers, restored frames included; all 0 after a call
+ * without frames.  (A call refused or failed keeps the figures of the call before it.)
  * Returns the number of bytes copied (>=0) or a negative status. */
 int64_t avd_debug_fetch(avd_ctx* ctx, const char* name, void* out, size_t out_bytes);
 
