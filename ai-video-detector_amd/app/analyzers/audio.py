@@ -14,7 +14,7 @@ from avd_hip import audio as _audio
 
 def analyze(path: str, meta: dict):
     try:
-        wav, sr = _audio.extract_wav_16k(path)
+        wav, sr = _audio.extract_wav_16k(path, native=True)      # a 16-bit file: its int16 samples as they are, converted on the device
         with _analyzer.default_pool().borrow(int(os.getenv("AVD_DEVICE", "0"))) as ctx:
             return _audio.analyze_wave(wav, sr, ctx)
     except Exception as e:          # noqa: BLE001 -- the reference swallows everything here (audio.py:111)

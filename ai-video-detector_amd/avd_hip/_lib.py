@@ -873,24 +873,108 @@ class Context:
         return self.debug_fetch("cnn_plan", (53,), np.int32)
 
     # -- audio analyzer (reference app/analyzers/audio.py:40-61 for all windows at once) -----------------------
-    def audio_features(self, wav, win: int) -> np.ndarray:
-        """wav: mono float32 samples (numpy or torch-ROCm tensor) -> structured array (AUDIO_WINDOW_DTYPE) per window."""
+    @staticmethod
+    def _is_pcm16(wav) -> bool:
+        return str(wav.dtype) == "torch.int16" if _is_torch_tensor(wav) else getattr(wav, "dtype", None) == np.int16
+
+    def _audio_ptr(self, wav, pcm16: bool):
+        """-> (ptr, mem, n, keepalive) of mono samples: int16 PCM as it is (pcm16), anything else as float32"""
         if _is_torch_tensor(wav):
             t = wav.contiguous()
-            if str(t.dtype) != "torch.float32" or t.dim() != 1:
-                raise ValueError("wav must be float32[n]")
+            if str(t.dtype) != ("torch.int16" if pcm16 else "torch.float32") or t.dim() != 1:
+                raise ValueError("wav must be float32[n] or int16[n]")
             if t.is_cuda:
                 self._after_torch_stream(t)
-            ptr, mem, n, keep = t.data_ptr(), (AVD_MEM_DEVICE if t.is_cuda else AVD_MEM_HOST), int(t.numel()), t
-        else:
-            a = np.ascontiguousarray(wav, dtype=np.float32)
-            if a.ndim != 1:
-                raise ValueError("wav must be float32[n]")
-            ptr, mem, n, keep = a.ctypes.data, AVD_MEM_HOST, int(a.size), a
-        nwin = (n + win - 1) // win if n and win > 0 else 0          # win < 1 or > 8192: the library refuses (AvdError)
+            return t.data_ptr(), (AVD_MEM_DEVICE if t.is_cuda else AVD_MEM_HOST), int(t.numel()), t
+        a = np.ascontiguousarray(wav, dtype=np.int16 if pcm16 else np.float32)
+        if a.ndim != 1:
+            raise ValueError("wav must be float32[n] or int16[n]")
+        return a.ctypes.data, AVD_MEM_HOST, int(a.size), a
+
+    def _audio_call(self, ptr, mem, n: int, win: int, nwin: int, pcm16: bool, cuts=()) -> np.ndarray:
+        """One avd_audio_features call: option "audio_format" set for it and restored (also after an exception), its cuts set in ascending order."""
         out = np.zeros(nwin, AUDIO_WINDOW_DTYPE)
-        self._check(self._L.avd_audio_features(self._h, ptr, mem, n, int(win), out.ctypes.data, nwin))
+        want = 1 if pcm16 else 0
+        before = self.get_option("audio_format")             # a caller of the C-ABI may keep the option at 1: the samples handed over HERE decide
+        if before != want:
+            self.set_option("audio_format", want)
+        try:
+            try:
+                for c in cuts:
+                    self.set_option("audio_cut", int(c))
+            except Exception:
+                self.set_option("audio_cut", -1)
+                raise
+            self._check(self._L.avd_audio_features(self._h, ptr, mem, n, int(win), out.ctypes.data, nwin))
+        finally:
+            if before != want:
+                self.set_option("audio_format", before)
         return out
+
+    def audio_features(self, wav, win: int) -> np.ndarray:
+        """wav: mono samples, float32 or 16-bit PCM as decoded (int16: sample s counts as float32(s) * 2^-15, converted on the device), numpy or
+        torch-ROCm tensor -> structured array (AUDIO_WINDOW_DTYPE) per window."""
+        pcm16 = self._is_pcm16(wav)
+        ptr, mem, n, keep = self._audio_ptr(wav, pcm16)
+        nwin = (n + win - 1) // win if n and win > 0 else 0          # win < 1 or > 8192: the library refuses (AvdError)
+        return self._audio_call(ptr, mem, n, win, nwin, pcm16)
+
+    AUDIO_TRACKS_PER_CALL = 64
+
+    def audio_features_many(self, tracks, win: int) -> list:
+        """Several mono tracks in as few calls as possible (option "audio_cut": up to 64 tracks share one call and fill the chip together).
+        tracks: all float32 or all int16, all host arrays (numpy, host tensors) or all device tensors.  Host tracks are concatenated once, device
+        tracks go through one torch.cat.  -> one record array per track, in order: byte for byte what audio_features gives for that track alone."""
+        tracks = list(tracks)
+        if not tracks:
+            return []
+        pcm = {self._is_pcm16(t) for t in tracks}
+        if len(pcm) != 1:
+            raise ValueError("audio_features_many: the tracks must be all float32 or all int16")
+        pcm16 = pcm.pop()
+        on_device = {bool(_is_torch_tensor(t) and t.is_cuda) for t in tracks}
+        if len(on_device) != 1:
+            raise ValueError("audio_features_many: the tracks must be all host arrays or all device tensors")
+        if any(t.ndim != 1 for t in tracks):
+            raise ValueError("wav must be float32[n] or int16[n]")
+        win = int(win)
+        per = win if 1 <= win <= 8192 else 0                         # win < 1 or > 8192: the library refuses (AvdError)
+        lens =[int(t.shape[0]) for t in tracks]
+        if on_device.pop():
+            import torch
+            whole = torch.cat([t if pcm16 else t.to(torch.float32) for t in tracks])
+        else:
+            dt = np.int16 if pcm16 else np.float32
+            whole = np.concatenate([np.asarray(t.numpy() if _is_torch_tensor(t) else t, dtype=dt) for t in tracks])
+        ptr, mem, _, keep = self._audio_ptr(whole, pcm16)
+        size = 2 if pcm16 else 4
+        results = [None] * len(tracks)
+        # an empty track has no window and cannot be cut off (cuts ascend strictly): it gets its empty result here and stays out of the calls
+        live = [i for i, n in enumerate(lens) if n > 0]
+        starts = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+        for g in range(0, len(live), self.AUDIO_TRACKS_PER_CALL):
+            group = live[g:g + self.AUDIO_TRACKS_PER_CALL]
+            first, end = int(starts[group[0]]), int(starts[group[-1] + 1])
+            counts = [(lens[i] + per - 1) // per if per else 0 for i in group]
+            cuts = [int(starts[i]) - first for i in group[1:]]
+            rec = self._audio_call(ptr + first * size, mem, end - first, win, sum(counts), pcm16, cuts)
+            at = 0
+            for i, c in zip(group, counts):
+                results[i] = rec[at:at + c]
+                at += c
+        for i, n in enumerate(lens):
+            if n == 0:
+                results[i] = np.zeros(0, AUDIO_WINDOW_DTYPE)
+        return results
+
+    def audio_tracks(self) -> np.ndarray:
+        """int32[tracks, 3] of the last audio_features / audio_features_many call that ran: per track its first window, its windows and the length
+        of its last window; avd_debug_fetch "audio_tracks"."""
+        out = np.zeros((self.AUDIO_TRACKS_PER_CALL, 3), np.int32)
+        got = self._L.avd_debug_fetch(self._h, b"audio_tracks", out.ctypes.data, out.nbytes)
+        if got < 0:
+            self._check(int(got))
+        return out[:got // 12].copy()
 
     def audio_plan(self):
         """(nwin, win, last, nfull) of the last audio_features call: windows, window length, length of the last window, windows that

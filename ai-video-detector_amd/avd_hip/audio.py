@@ -36,9 +36,25 @@ def read_wav_pcm(path: str):
     return np.ascontiguousarray(a), int(sr)
 
 
-def extract_wav_16k(path: str):
-    """audio.py:7-20: ffmpeg -> 16 kHz mono wav -> float32.  Without ffmpeg (this image has none) a file that already IS a
-    16 kHz PCM wav is read directly; anything else fails the way the reference fails when ffmpeg does."""
+def read_wav_native(path: str):
+    """read_wav_pcm's sibling: a 16-bit file gives the int16 samples of channel 0 UNTOUCHED (half the bytes; the analyzer takes them as
+    float32(s) * 2^-15 on the device, bit for bit what read_wav_pcm's division gives), every other width what read_wav_pcm returns."""
+    with wave.open(path, "rb") as w:
+        nch, width, sr, n = w.getnchannels(), w.getsampwidth(), w.getframerate(), w.getnframes()
+        raw = w.readframes(n) if width == 2 else None
+    if raw is None:
+        return read_wav_pcm(path)
+    a = np.frombuffer(raw, "<i2").astype(np.int16, copy=False)
+    if nch > 1:
+        a = a.reshape(-1, nch)[:, 0]          # audio.py:34: first channel
+    return np.ascontiguousarray(a), int(sr)
+
+
+def extract_wav_16k(path: str, native: bool = False):
+    """audio.py:7-20: ffmpeg -> 16 kHz mono wav -> float32 (native: the int16 samples of the 16-bit file ffmpeg writes, as read_wav_native
+    hands them over).  Without ffmpeg (this image has none) a file that already IS a 16 kHz PCM wav is read directly; anything else fails the
+    way the reference fails when ffmpeg does."""
+    read = read_wav_native if native else read_wav_pcm
     if shutil.which("ffmpeg"):
         tmp = tempfile.NamedTemporaryFile(delete=False, suffix=".wav")
         tmp.close()
@@ -48,7 +64,7 @@ def extract_wav_16k(path: str):
             if proc.returncode != 0:
                 raise RuntimeError("ffmpeg_convert_failed")
             try:
-                return read_wav_pcm(tmp.name)
+                return read(tmp.name)
             except Exception:
                 raise RuntimeError("soundfile_read_failed")
         finally:
@@ -57,7 +73,7 @@ def extract_wav_16k(path: str):
             except OSError:
                 pass
     try:
-        wav, sr = read_wav_pcm(path)
+        wav, sr = read(path)
     except Exception:
         raise RuntimeError("ffmpeg_convert_failed")
     if sr != SAMPLE_RATE:
@@ -109,11 +125,37 @@ def features_to_result(values: dict, dur: float) -> dict:
             "timeline": line}
 
 
-def analyze_wave(wav: np.ndarray, sr: int, ctx) -> dict:
-    """audio.py:33-110 for a decoded waveform, spectral features on the GPU."""
+def _mono(wav):
+    """the first channel (audio.py:34); int16 PCM stays int16, everything else becomes float32"""
+    wav = np.asarray(wav)
     if wav.ndim > 1:
         wav = wav[:, 0]
+    return np.ascontiguousarray(wav, np.int16 if wav.dtype == np.int16 else np.float32)
+
+
+def _win_of(sr: int) -> int:
+    return max(1, int(sr * 0.5)) if sr else 1
+
+
+def analyze_wave(wav: np.ndarray, sr: int, ctx) -> dict:
+    """audio.py:33-110 for a decoded waveform (float32, or 16-bit PCM as int16), spectral features on the GPU."""
+    wav = _mono(wav)
     dur = len(wav) / sr if sr > 0 else 0.0
-    win = max(1, int(sr * 0.5)) if sr else 1
-    rec = ctx.audio_features(np.ascontiguousarray(wav, np.float32), win)
+    rec = ctx.audio_features(wav, _win_of(sr))
     return features_to_result(window_values(rec), dur)
+
+
+def analyze_waves(waves, ctx) -> list:
+    """[(wav, sr), ...] -> the list of analyze_wave's results, in input order.  Tracks of one window length (that is, one sample rate) and one
+    sample type share calls (Context.audio_features_many: up to 64 tracks per call), so that short tracks fill the chip together."""
+    waves = [(_mono(w), sr) for w, sr in waves]
+    groups = {}
+    for i, (w, sr) in enumerate(waves):
+        groups.setdefault((_win_of(sr), w.dtype == np.int16), []).append(i)
+    results = [None] * len(waves)
+    for (win, _), members in groups.items():
+        recs = ctx.audio_features_many([waves[i][0] for i in members], win)
+        for i, rec in zip(members, recs):
+            w, sr = waves[i]
+            results[i] = features_to_result(window_values(rec), len(w) / sr if sr > 0 else 0.0)
+    return results

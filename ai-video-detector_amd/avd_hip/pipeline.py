@@ -2,7 +2,8 @@
 ``api._analyze_path`` (api.py:142-170) without the HTTP layer.
 
     meta  -> hints (heuristics_v2.compute_hints)
-          -> audio result (pluggable; the audio analyzer is outside this build's scope)
+          -> audio result (pluggable; by default app.analyzers.audio.analyze, whose per-window
+             spectral features run in the HIP kernels behind avd_audio_features)
           -> video result (app.analyzers.video.analyze, HIP kernels), with the reference's
              "safe" wrapper: ANY exception becomes the neutral 0.5 timeline + hints["video_error"]
              (api.py:130-140)

@@ -18,34 +18,50 @@
 // Either way the difference to numpy's pocketfft is the order of additions: per bin at most 6.8e-16 * sum|xw| on the 80 x 100
 // path and 4.8e-15 * sum|xw| on the direct one, measured bin by bin by tests/test_gpu_audio_spectrum.py (whose docstring is
 // the record of these figures; its bound is 1e-12), far inside the 1e-4 tolerance of the path.
+//
+// One call may hold several tracks (option "audio_cut"), each windowed from its own start, as float32 or as 16-bit PCM (option "audio_format").
+// csrc/avd_audio_plan.h lays the call out; the kernels go by its window table, and every window is computed exactly as it would be if its
+// track were the only one of the call.
+#include <chrono>
 #include <cmath>
-#include <vector>
+#include <cstdint>
+#include <cstring>
 #include "avd_internal.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
+// Every pass takes its windows from the call's window table (avd_audio_plan.h): where a window begins in the staged buffer, how long it is, and
+// which tables it reads -- the full-length set (hann | cos | sin, `win` entries each, cached per win) or its own length's set in the call's arena.
+using avd_audio::Window;
+using avd_audio::kTabFull;
+
+// a sample as the float32 the reference analyses: float32 as it is; int16 PCM s is (float)s * 2^-15, exact for all 65536 values (what
+// soundfile's dtype="float32" read gives), widened in registers -- no float32 copy of an int16 track exists in memory
+__device__ __forceinline__ float audio_sample(const float* p, int64_t i) { return p[i]; }
+__device__ __forceinline__ float audio_sample(const int16_t* p, int64_t i) { return (float)p[i] * 0x1p-15f; }
+
 // ---- pass 1: time-domain sums and the windowed segment ----------------------------------------------------------
-__global__ __launch_bounds__(256) void k_audio_prepare(const float* __restrict__ wav, int64_t n, int win,
-                                                      const double* __restrict__ hann_full, const double* __restrict__ hann_last,
+template <typename T>
+__global__ __launch_bounds__(256) void k_audio_prepare(const T* __restrict__ wav, const Window* __restrict__ wt, int win,
+                                                      const double* __restrict__ tab_full, const double* __restrict__ arena,
                                                       double* __restrict__ xw, avd_audio_window* __restrict__ out)
 {
     __shared__ double ssum[4];
     __shared__ int szc[4];
     const int wdx = blockIdx.x, tid = threadIdx.x;
-    const int64_t base = (int64_t)wdx * win;
-    const int len = (int)((n - base) < win ? (n - base) : win);
-    const double* hann = len == win ? hann_full : hann_last;
-    const float* seg = wav + base;
+    const Window w = wt[wdx];
+    const int len = w.len;
+    const double* hann = w.tab == kTabFull ? tab_full : arena + w.tab;
     double sq = 0.;
     int zc = 0;
     for (int i = tid; i < len; i += 256) {
-        const float v = seg[i];
+        const float v = audio_sample(wav, w.off + i);
         sq += (double)(v * v);                              // seg**2 is float32 in the reference; summed in double here
         xw[(int64_t)wdx * win + i] = (double)v * hann[i];
         if (i + 1 < len) {
-            const float u = seg[i + 1];
+            const float u = audio_sample(wav, w.off + i + 1);
             const int sv = (v > 0.f) - (v < 0.f), su = (u > 0.f) - (u < 0.f);
             zc += abs(su - sv);                             // |diff(sign(seg))|, values 0, 1, 2
         }
@@ -63,22 +79,21 @@ __global__ __launch_bounds__(256) void k_audio_prepare(const float* __restrict__
 }
 
 // ---- pass 2: |rfft| + 1e-9 by direct evaluation -----------------------------------------------------------------
-// grid (windows, ceil(max_bins / 256)); LDS: window [L] + cosine table [L] (dynamic, 16 * L bytes)
-__global__ __launch_bounds__(256) void k_audio_dft(const double* __restrict__ xw, int64_t n, int win,
-                                                  const double* __restrict__ cos_full, const double* __restrict__ sin_full,
-                                                  const double* __restrict__ cos_last, const double* __restrict__ sin_last,
-                                                  double* __restrict__ mag, int first_window)
+// grid (windows of `list`, ceil(max_bins / 256)); LDS: window [L] + cosine table [L] (dynamic, 16 * lds_len bytes, lds_len = the longest of them)
+__global__ __launch_bounds__(256) void k_audio_dft(const double* __restrict__ xw, const Window* __restrict__ wt, const int* __restrict__ list, int win,
+                                                  int lds_len, const double* __restrict__ tab_full, const double* __restrict__ arena,
+                                                  double* __restrict__ mag)
 {
     extern __shared__ __align__(16) double lds[];
-    const int wdx = first_window + blockIdx.x, tid = threadIdx.x;   // the windows before first_window went through the FFT path
-    const int64_t base = (int64_t)wdx * win;
-    const int L = (int)((n - base) < win ? (n - base) : win);
+    const int wdx = list[blockIdx.x], tid = threadIdx.x;   // the call's windows that do not go through the FFT path
+    const Window w = wt[wdx];
+    const int L = w.len;
     const int nb = L / 2 + 1;
     if ((int)blockIdx.y * 256 >= nb) return;                // whole workgroup
-    const bool full = L == win;
-    const double* ct = full ? cos_full : cos_last;
+    const bool full = w.tab == kTabFull;
+    const double* ct = full ? tab_full + win : arena + w.tab + L;
     double* x = lds;
-    double* c = lds + win;
+    double* c = lds + lds_len;
     for (int i = tid; i < L; i += 256) { x[i] = xw[(int64_t)wdx * win + i]; c[i] = ct[i]; }
     __syncthreads();
     const int k = blockIdx.y * 256 + tid;
@@ -97,8 +112,8 @@ __global__ __launch_bounds__(256) void k_audio_dft(const double* __restrict__ xw
         }
     } else {
         // a length that is not a multiple of 4 has no quarter period in its cosine table: sines of THIS length from
-        // global memory (full windows of a caller-chosen size as well as the short last window of a stream)
-        const double* st = full ? sin_full : sin_last;
+        // global memory (full windows of a caller-chosen size as well as the short last window of a track)
+        const double* st = full ? tab_full + 2 * win : arena + w.tab + 2 * L;
         int j = 0;
         for (int i = 0; i < L; i++) {
             const double v = x[i];
@@ -118,18 +133,20 @@ __global__ __launch_bounds__(256) void k_audio_dft(const double* __restrict__ xw
 // the SAME 8000-entry cosine table the direct form uses (W_80^m = W_8000^(100 m), W_100^m = W_8000^(80 m), sines a quarter
 // period away): no approximation anywhere, the result differs from the direct sum only by the order of additions
 // (figures above).  The intermediate B[n2][k1] (16 bytes per entry, 128 KB per window) goes through global memory / L2.
-constexpr int kFftN = 8000, kN1 = 80, kN2 = 100;
+constexpr int kFftN = avd_audio::kFftLen, kN1 = 80, kN2 = 100;
+static_assert(kFftN == kN1 * kN2, "the two-step transform is written for 80 x 100");
 
-__global__ __launch_bounds__(256) void k_audio_fft_a(const double* __restrict__ xw, const double* __restrict__ cos_full,
+// Both kernels run over the compacted list of the call's full windows: workgroup b transforms window list[b], its intermediate is B[b]
+__global__ __launch_bounds__(256) void k_audio_fft_a(const double* __restrict__ xw, const int* __restrict__ list, const double* __restrict__ cos_full,
                                                     double2* __restrict__ B)
 {
     extern __shared__ __align__(16) double lds[];          // window [8000] | cosine table [8000]
     double* x = lds;
     double* c = lds + kFftN;
-    const int wdx = blockIdx.x, tid = threadIdx.x;
+    const int wdx = list[blockIdx.x], tid = threadIdx.x;
     for (int i = tid; i < kFftN; i += 256) { x[i] = xw[(int64_t)wdx * kFftN + i]; c[i] = cos_full[i]; }
     __syncthreads();
-    double2* out = B + (int64_t)wdx * kFftN;
+    double2* out = B + (int64_t)blockIdx.x * kFftN;
     for (int o = tid; o < kFftN; o += 256) {
         const int k1 = o / kN2, n2 = o - k1 * kN2;          // consecutive lanes: consecutive n2, (almost) the same k1
         double re = 0., im = 0.;
@@ -152,15 +169,15 @@ __global__ __launch_bounds__(256) void k_audio_fft_a(const double* __restrict__ 
     }
 }
 
-__global__ __launch_bounds__(256) void k_audio_fft_b(const double2* __restrict__ B, const double* __restrict__ cos_full,
+__global__ __launch_bounds__(256) void k_audio_fft_b(const double2* __restrict__ B, const int* __restrict__ list, const double* __restrict__ cos_full,
                                                     double* __restrict__ mag)
 {
     extern __shared__ __align__(16) double lds[];          // cosine table [8000]
     double* c = lds;
-    const int wdx = blockIdx.x, tid = threadIdx.x;
+    const int wdx = list[blockIdx.x], tid = threadIdx.x;
     for (int i = tid; i < kFftN; i += 256) c[i] = cos_full[i];
     __syncthreads();
-    const double2* in = B + (int64_t)wdx * kFftN;
+    const double2* in = B + (int64_t)blockIdx.x * kFftN;
     for (int k = tid; k <= kFftN / 2; k += 256) {
         const int k2 = k / kN1, k1 = k - k2 * kN1;          // consecutive lanes: consecutive k1 -> consecutive B entries
         double re = 0., im = 0.;
@@ -179,12 +196,12 @@ __global__ __launch_bounds__(256) void k_audio_fft_b(const double2* __restrict__
 }
 
 // ---- pass 3: spectral sums and the roll-off index ---------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_audio_reduce(const double* __restrict__ mag, int win, avd_audio_window* __restrict__ out)
+__global__ __launch_bounds__(256) void k_audio_reduce(const double* __restrict__ mag, const Window* __restrict__ wt, int win, avd_audio_window* __restrict__ out)
 {
     __shared__ double sl[4], sm[4], sf[4];
     __shared__ double total;
     const int wdx = blockIdx.x, tid = threadIdx.x;
-    const int nb = out[wdx].nbins;
+    const int nb = wt[wdx].len / 2 + 1;
     const double* m = mag + (int64_t)wdx * (win / 2 + 1);
     // np.linspace(0, 1, nb): k * step with step = 1 / (nb - 1), the last element exactly 1
     const double step = nb > 1 ? 1.0 / (double)(nb - 1) : 0.0;
@@ -218,62 +235,87 @@ __global__ __launch_bounds__(256) void k_audio_reduce(const double* __restrict__
 
 }  // namespace
 
-// per-window features of n float32 samples (device pointer), window length `win`; out: device array of ceil(n / win)
-int launch_audio_features(avd_ctx* ctx, const float* d_wav, int64_t n, int win, avd_audio_window* d_out, int nwin)
+// np.hanning(L), cos(2 pi j / L) and sin(2 pi j / L) at t, t + L and t + 2 L.  The one place where a table value is formed, for the full length
+// and for every short one, on the host: a track's windows read the same bits whether it is analysed alone or in a batch, which is what makes the
+// batch byte-identical to the per-track calls (device cos need not match libm's).
+static void fill_length_tables(double* t, int L)
 {
+    // np.hanning(M) = 0.5 + 0.5 cos(pi n / (M-1)) for n = 1-M, 3-M, ..., M-1 (ones for M = 1)
+    for (int i = 0; i < L; i++) t[i] = L == 1 ? 1.0 : 0.5 + 0.5 * std::cos(M_PI * (double)(2 * i + 1 - L) / (double)(L - 1));
+    for (int j = 0; j < L; j++) { t[L + j] = std::cos(2.0 * M_PI * (double)j / (double)L); t[2 * L + j] = std::sin(2.0 * M_PI * (double)j / (double)L); }
+}
+
+// per-window features of the tracks of `plan` (avd_audio_plan.h), samples at d_wav (device; format 0: float32, 1: int16 PCM); d_out: device array of
+// plan.nwin() records
+int launch_audio_features(avd_ctx* ctx, const void* d_wav, int format, const avd_audio::Plan& plan, avd_audio_window* d_out)
+{
+    const int nwin = plan.nwin(), win = plan.win, nfull = plan.nfull(), ndft = (int)plan.dft.size();
     if (nwin <= 0) return 0;
-    if (win < 1 || win > 8192) { ctx->err = "audio window must be 1..8192 samples"; return AVD_ERR_ARG; }
+    if (win < 1 || win > avd_audio::kMaxWin) { ctx->err = "audio window must be 1..8192 samples"; return AVD_ERR_ARG; }
     Workspace& ws = ctx->ws;
     ctx->audio_plan_valid = 0;                               // debug buffers "audio_*" describe this call once it is enqueued, never the one before
-    const int last = (int)(n - (int64_t)(nwin - 1) * win);
-    if (ws.audio_win != win || ws.audio_last != last) {
-        // tables: np.hanning of both window lengths, cos(2 pi j / L) (and sin for the last length)
-        std::vector<double> hf(win), hl(last), cf(win), sf(win), cl(last), sl(last);
-        // np.hanning(M) = 0.5 + 0.5 cos(pi n / (M-1)) for n = 1-M, 3-M, ..., M-1 (ones for M = 1)
-        for (int i = 0; i < win; i++) hf[i] = win == 1 ? 1.0 : 0.5 + 0.5 * std::cos(M_PI * (double)(2 * i + 1 - win) / (double)(win - 1));
-        for (int i = 0; i < last; i++) hl[i] = last == 1 ? 1.0 : 0.5 + 0.5 * std::cos(M_PI * (double)(2 * i + 1 - last) / (double)(last - 1));
-        for (int j = 0; j < win; j++) { cf[j] = std::cos(2.0 * M_PI * (double)j / (double)win); sf[j] = std::sin(2.0 * M_PI * (double)j / (double)win); }
-        for (int j = 0; j < last; j++) { cl[j] = std::cos(2.0 * M_PI * (double)j / (double)last); sl[j] = std::sin(2.0 * M_PI * (double)j / (double)last); }
-        const size_t need = (size_t)3 * win + 3 * (size_t)last;
-        ws.audio_win = ws.audio_last = 0;                     // the tables are not valid again until every copy below is enqueued
-        if (int e = ws.d_audio_tab.reserve(ctx, need)) return e;
-        double* t = ws.d_audio_tab;
-        HIP_TRY(ctx, hipMemcpyAsync(t, hf.data(), sizeof(double) * win, hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(ctx, hipMemcpyAsync(t + win, cf.data(), sizeof(double) * win, hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(ctx, hipMemcpyAsync(t + 2 * win, sf.data(), sizeof(double) * win, hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(ctx, hipMemcpyAsync(t + 3 * win, hl.data(), sizeof(double) * last, hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(ctx, hipMemcpyAsync(t + 3 * win + last, cl.data(), sizeof(double) * last, hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(ctx, hipMemcpyAsync(t + 3 * win + 2 * last, sl.data(), sizeof(double) * last, hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));   // the host vectors go out of scope
-        ws.audio_win = win; ws.audio_last = last;
+    // A call that failed between its upload and its drain may have left the copy out of the pinned staging buffer in flight
+    if (ws.audio_upload_pending) { HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); ws.audio_upload_pending = 0; }
+    // pinned staging: the per-call upload (arena | window table | the two lists), then the full-length tables when `win` changed.  Both leave in
+    // asynchronous copies; the buffer is the workspace's, so nothing waits here for host memory that goes out of scope
+    const bool new_win = ws.audio_win != win;
+    const size_t up = plan.upload_bytes() / sizeof(double), full_at = up, stage = up + (new_win ? 3 * (size_t)win : 0);
+    if (int e = ws.h_audio_call.reserve(ctx, stage)) return e;
+    if (int e = ws.d_audio_call.reserve(ctx, up)) return e;
+    double* h = ws.h_audio_call;
+    char* hb = reinterpret_cast<char*>(h);
+    const auto t0 = std::chrono::steady_clock::now();
+    for (size_t k = 0; k < plan.lengths.size(); k++) fill_length_tables(h + plan.set_at[k], plan.lengths[k]);
+    ctx->audio_host[0] = (int)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count();
+    ctx->audio_host[1] = (int)plan.lengths.size();
+    std::memcpy(hb + plan.windows_at(), plan.windows.data(), sizeof(Window) * (size_t)nwin);
+    if (nfull) std::memcpy(hb + plan.fft_at(), plan.fft.data(), sizeof(int) * (size_t)nfull);
+    if (ndft) std::memcpy(hb + plan.dft_at(), plan.dft.data(), sizeof(int) * (size_t)ndft);
+    if (new_win) {
+        fill_length_tables(h + full_at, win);
+        ws.audio_win = 0;                                    // the tables are not valid again until their copy is enqueued
+        if (int e = ws.d_audio_tab.reserve(ctx, 3 * (size_t)win)) return e;
     }
-    // full windows of 8000 samples (the reference's half second at 16 kHz) take the two-step FFT path, everything else
-    // (another window length, the short last window of a stream) the direct form
-    const int nfull = win == kFftN ? (last == win ? nwin : nwin - 1) : 0;
-    const size_t xw_need = (size_t)nwin * win, mag_need = (size_t)nwin * (win / 2 + 1), b_need = (size_t)nfull * kFftN * 2;
+    const size_t xw_need = plan.xw_size(), mag_need = plan.mag_size(), b_need = plan.b_size();
     if (int e = ws.d_audio_buf.reserve(ctx, xw_need + mag_need + b_need)) return e;
-    double* t = ws.d_audio_tab;
+    ws.audio_upload_pending = 1;
+    HIP_TRY(ctx, hipMemcpyAsync(ws.d_audio_call, h, plan.upload_bytes(), hipMemcpyHostToDevice, ctx->stream));
+    if (new_win) {
+        HIP_TRY(ctx, hipMemcpyAsync(ws.d_audio_tab, h + full_at, sizeof(double) * 3 * (size_t)win, hipMemcpyHostToDevice, ctx->stream));
+        ws.audio_win = win;
+    }
+    const char* db = reinterpret_cast<const char*>(ws.d_audio_call.p);
+    const double* arena = ws.d_audio_call;
+    const Window* wt = reinterpret_cast<const Window*>(db + plan.windows_at());
+    const int* fft_list = reinterpret_cast<const int*>(db + plan.fft_at());
+    const int* dft_list = reinterpret_cast<const int*>(db + plan.dft_at());
+    const double* t = ws.d_audio_tab;                        // hann | cos | sin of the full length
     double *xw = ws.d_audio_buf, *mag = ws.d_audio_buf + xw_need;
     double2* bbuf = reinterpret_cast<double2*>(ws.d_audio_buf + xw_need + mag_need);
-    hipLaunchKernelGGL(k_audio_prepare, dim3(nwin), dim3(256), 0, ctx->stream, d_wav, n, win, (const double*)t,
-                       (const double*)(t + 3 * win), xw, d_out);
+    if (format == 1)
+        hipLaunchKernelGGL(k_audio_prepare<int16_t>, dim3(nwin), dim3(256), 0, ctx->stream, static_cast<const int16_t*>(d_wav), wt, win, t, arena, xw, d_out);
+    else
+        hipLaunchKernelGGL(k_audio_prepare<float>, dim3(nwin), dim3(256), 0, ctx->stream, static_cast<const float*>(d_wav), wt, win, t, arena, xw, d_out);
     // per call (a function attribute belongs to the current device; a process may hold contexts on several)
     HIP_TRY(ctx, hipFuncSetAttribute((const void*)k_audio_dft, hipFuncAttributeMaxDynamicSharedMemorySize, 16 * 8192));
     HIP_TRY(ctx, hipFuncSetAttribute((const void*)k_audio_fft_a, hipFuncAttributeMaxDynamicSharedMemorySize, 16 * kFftN));
     HIP_TRY(ctx, hipFuncSetAttribute((const void*)k_audio_fft_b, hipFuncAttributeMaxDynamicSharedMemorySize, 8 * kFftN));
+    // full windows of 8000 samples (the reference's half second at 16 kHz) take the two-step FFT path, everything else
+    // (another window length, the short last window of a track) the direct form
     if (nfull > 0) {
-        hipLaunchKernelGGL(k_audio_fft_a, dim3(nfull), dim3(256), (size_t)16 * kFftN, ctx->stream, (const double*)xw, (const double*)(t + win), bbuf);
-        hipLaunchKernelGGL(k_audio_fft_b, dim3(nfull), dim3(256), (size_t)8 * kFftN, ctx->stream, (const double2*)bbuf, (const double*)(t + win), mag);
+        hipLaunchKernelGGL(k_audio_fft_a, dim3(nfull), dim3(256), (size_t)16 * kFftN, ctx->stream, (const double*)xw, fft_list, t + win, bbuf);
+        hipLaunchKernelGGL(k_audio_fft_b, dim3(nfull), dim3(256), (size_t)8 * kFftN, ctx->stream, (const double2*)bbuf, fft_list, t + win, mag);
     }
-    if (nfull < nwin) {
-        const size_t lds = (size_t)16 * win;
-        hipLaunchKernelGGL(k_audio_dft, dim3(nwin - nfull, (win / 2 + 1 + 255) / 256), dim3(256), lds, ctx->stream, (const double*)xw, n, win,
-                           (const double*)(t + win), (const double*)(t + 2 * win), (const double*)(t + 3 * win + last),
-                           (const double*)(t + 3 * win + 2 * last), mag, nfull);
+    if (ndft > 0) {
+        const int L = plan.max_dft_len;
+        hipLaunchKernelGGL(k_audio_dft, dim3(ndft, (L / 2 + 1 + 255) / 256), dim3(256), (size_t)16 * L, ctx->stream, (const double*)xw, wt, dft_list, win, L,
+                           t, arena, mag);
     }
-    hipLaunchKernelGGL(k_audio_reduce, dim3(nwin), dim3(256), 0, ctx->stream, (const double*)mag, win, d_out);
+    hipLaunchKernelGGL(k_audio_reduce, dim3(nwin), dim3(256), 0, ctx->stream, (const double*)mag, wt, win, d_out);
     HIP_TRY(ctx, hipGetLastError());
-    ctx->audio_plan[0] = nwin; ctx->audio_plan[1] = win; ctx->audio_plan[2] = last; ctx->audio_plan[3] = nfull;
+    ctx->audio_plan[0] = nwin; ctx->audio_plan[1] = win; ctx->audio_plan[2] = plan.tracks.back().last; ctx->audio_plan[3] = nfull;
+    ctx->audio_ntracks = (int)plan.tracks.size();
+    std::memcpy(ctx->audio_tracks, plan.tracks.data(), sizeof(avd_audio::Track) * plan.tracks.size());
     ctx->audio_plan_valid = 1;
     return 0;
 }

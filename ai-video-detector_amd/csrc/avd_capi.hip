@@ -466,6 +466,24 @@ static void stream_map_set(avd_ctx* ctx, int v)
     for (int s : ctx->stream_map) ctx->stream_mapped += s != 0;
 }
 static int stream_map_read(const avd_ctx* ctx) { return ctx->stream_mapped; }
+// "audio_format": 0 float32 samples, 1 little-endian int16 PCM; durable
+static bool opt_audio_format(int& v) { return v == 0 || v == 1; }
+// "audio_cut": a track of the NEXT avd_audio_features call ends, and the next one begins, at sample v of its buffer; one at a time, strictly ascending,
+// at most 63; -1 clears the list.  Reads back as the number of cuts held.  The call takes the list (impl_audio_features).
+static const char* audio_cut_check(const avd_ctx* ctx, int v)
+{
+    if (v == -1) return nullptr;
+    if (v <= 0) return "audio_cut: a sample position above 0, or -1 (clear the list)";
+    if (ctx->audio_ncuts > 0 && v <= ctx->audio_cuts[ctx->audio_ncuts - 1]) return "audio_cut: cuts are set in strictly ascending order";
+    if (ctx->audio_ncuts >= avd_audio::kMaxCuts) return "audio_cut: at most 63 cuts (64 tracks) per call";
+    return nullptr;
+}
+static void audio_cut_set(avd_ctx* ctx, int v)
+{
+    if (v == -1) ctx->audio_ncuts = 0;
+    else ctx->audio_cuts[ctx->audio_ncuts++] = v;
+}
+static int audio_cut_read(const avd_ctx* ctx) { return ctx->audio_ncuts; }
 static int env_any_base(const char* e) { return (int)std::strtol(e, nullptr, 0); }
 static int env_fb_mode(const char* e) { return (std::strcmp(e, "exact") == 0 || std::strcmp(e, "0") == 0) ? 0 : 1; }
 static const Option kOptions[] = {
@@ -489,6 +507,8 @@ static const Option kOptions[] = {
     {"stream_map", nullptr, true, opt_any, nullptr, nullptr, nullptr, stream_map_set, stream_map_read, stream_map_check},
     {"stream_reset", nullptr, true, opt_stream, nullptr, nullptr, "stream_reset: 0 (every slot) or slot 1 ... 8", stream_reset, stream_reset_read},
     {"stream_frames", nullptr, false, opt_any, nullptr, nullptr, nullptr, nullptr, stream_frames},
+    {"audio_format", &avd_ctx::audio_format, true, opt_audio_format, nullptr, nullptr, "audio_format: 0 (float32 samples) or 1 (little-endian int16 PCM)"},
+    {"audio_cut", nullptr, true, opt_any, nullptr, nullptr, nullptr, audio_cut_set, audio_cut_read, audio_cut_check},
 };
 static const Option* find_option(avd_ctx* ctx, const char* name, bool to_write)
 {
@@ -1077,8 +1097,20 @@ static int64_t impl_debug_fetch(avd_ctx* ctx, const char* name, void* out, size_
     }
     if (std::strncmp(name, "audio_", 6) == 0) {        // the last avd_audio_features of this context: its window plan (host state) and its two scratch arrays
         const bool plan = std::strcmp(name + 6, "plan") == 0, xw = std::strcmp(name + 6, "xw") == 0, mag = std::strcmp(name + 6, "mag") == 0;
-        if (!plan && !xw && !mag) { ctx->err = "unknown debug buffer"; return AVD_ERR_ARG; }
+        const bool tracks = std::strcmp(name + 6, "tracks") == 0;
+        if (!plan && !xw && !mag && !tracks && std::strcmp(name + 6, "host") != 0) { ctx->err = "unknown debug buffer"; return AVD_ERR_ARG; }
         if (!ctx->audio_plan_valid) { ctx->err = "audio_plan / audio_xw / audio_mag not recorded yet: no avd_audio_features call has run on this context"; return AVD_ERR_ARG; }
+        if (std::strcmp(name + 6, "host") == 0) {      // int32[2]: microseconds spent forming the short lengths' tables, distinct short lengths
+            if (out_bytes < sizeof(ctx->audio_host)) { ctx->err = "audio_host is int32[2]"; return AVD_ERR_ARG; }
+            std::memcpy(out, ctx->audio_host, sizeof(ctx->audio_host));
+            return (int64_t)sizeof(ctx->audio_host);
+        }
+        if (tracks) {                                  // int32[tracks][3]: first window, windows, length of the last window
+            const size_t have = sizeof(int) * 3 * (size_t)ctx->audio_ntracks;
+            if (out_bytes < have) { ctx->err = "audio_tracks is int32[tracks][3]"; return AVD_ERR_ARG; }
+            std::memcpy(out, ctx->audio_tracks, have);
+            return (int64_t)have;
+        }
         if (plan) {
             if (out_bytes < sizeof(ctx->audio_plan)) { ctx->err = "audio_plan is int32[4]"; return AVD_ERR_ARG; }
             std::memcpy(out, ctx->audio_plan, sizeof(ctx->audio_plan));
@@ -1321,23 +1353,27 @@ static int impl_rowop(avd_ctx* ctx, int op, const void* x, int mem, int bf16, in
 }
 
 // ---- audio analyzer (row N3) -------------------------------------------------------------------------------------
-static int impl_audio_features(avd_ctx* ctx, const float* wav, int mem, int64_t n, int win, avd_audio_window* windows, int max_windows)
+// cuts / ncuts: the "audio_cut" list the call took from the context (avd_audio_features: one-shot, whatever becomes of the call)
+static int impl_audio_features(avd_ctx* ctx, const void* wav, int mem, int64_t n, int win, avd_audio_window* windows, int max_windows, const int* cuts, int ncuts)
 {
-    if (!ctx) return AVD_ERR_ARG;
     if (win < 1 || win > 8192) { ctx->err = "audio window must be 1..8192 samples"; return AVD_ERR_ARG; }   // also for n = 0: a bad window is never "nothing to do"
     if (n < 0 || (n > 0 && (!wav || !windows))) { ctx->err = "bad arguments"; return AVD_ERR_ARG; }
     if (n == 0) return AVD_OK;
-    const int64_t nw64 = (n + win - 1) / win;
-    if (nw64 > max_windows || nw64 > (1 << 24)) { ctx->err = "windows array too small"; return AVD_ERR_ARG; }
-    const int nwin = (int)nw64;
+    const int format = ctx->audio_format;
+    if (format == 1 && (reinterpret_cast<uintptr_t>(wav) & 1)) { ctx->err = "audio_format 1: int16 samples need a 2-byte aligned wav"; return AVD_ERR_ARG; }
+    const avd_audio::Plan plan = avd_audio::plan_call(n, win, cuts, ncuts, max_windows);
+    if (plan.refused == avd_audio::kCutBeyond) { ctx->err = "audio_cut: beyond the buffer"; return AVD_ERR_ARG; }
+    if (plan.refused) { ctx->err = "windows array too small"; return AVD_ERR_ARG; }
+    const int nwin = plan.nwin();
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     Workspace& ws = ctx->ws;
     const uint8_t* d_wav = nullptr;
-    if (int e = stage_input(ctx, reinterpret_cast<const uint8_t*>(wav), mem, (size_t)n * sizeof(float), &d_wav)) return e;
+    if (int e = stage_input(ctx, static_cast<const uint8_t*>(wav), mem, (size_t)n * (format == 1 ? sizeof(int16_t) : sizeof(float)), &d_wav)) return e;
     if (int e = ws.d_audio_out.reserve(ctx, (size_t)nwin)) return e;
-    if (int e = launch_audio_features(ctx, reinterpret_cast<const float*>(d_wav), n, win, ws.d_audio_out, nwin)) return e;
+    if (int e = launch_audio_features(ctx, d_wav, format, plan, ws.d_audio_out)) return e;
     HIP_TRY(ctx, hipMemcpyAsync(windows, ws.d_audio_out, sizeof(avd_audio_window) * nwin, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    ws.audio_upload_pending = 0;
     return AVD_OK;
 }
 
@@ -1584,7 +1620,16 @@ int avd_softmax(avd_ctx* ctx, const float* x, int mem, int64_t rows, int cols, f
 
 int avd_audio_features(avd_ctx* ctx, const float* wav, int mem, int64_t n, int win, avd_audio_window* windows, int max_windows)
 {
-    return guarded(ctx, [&] { return impl_audio_features(ctx, wav, mem, n, win, windows, max_windows); });
+    if (!ctx) return AVD_ERR_ARG;
+    // The "audio_cut" list is taken FIRST, ahead of the drain of a pending call: it is gone whether this call succeeds, is refused or fails
+    return guarded(ctx, [&] {
+        int cuts[avd_audio::kMaxCuts];
+        const int ncuts = ctx->audio_ncuts;
+        std::copy(ctx->audio_cuts, ctx->audio_cuts + ncuts, cuts);
+        ctx->audio_ncuts = 0;
+        if (int e = drain_pending(ctx)) return e;
+        return impl_audio_features(ctx, wav, mem, n, win, windows, max_windows, cuts, ncuts);
+    }, Pending::keep);
 }
 
 int avd_comm_unique_id(void* id128)

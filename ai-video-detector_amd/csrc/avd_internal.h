@@ -9,6 +9,7 @@
 #include "../../include/avd.h"
 #include "avd_ingest_clip.h"      // IngestClip: one clip of an ingest call, its argument check and its staging plan (host only)
 #include "avd_stream_plan.h"      // where the clips of a call lie when some continue a stream slot (host only)
+#include "avd_audio_plan.h"       // the tracks, window table and table arena of one avd_audio_features call (host only)
 
 #define AVD_FB_LEVELS 4            // pyramid scales 1/8,1/4,1/2,1 of 320 (see avd_farneback.hip)
 #define AVD_NPIX (AVD_SMALL * AVD_SMALL)
@@ -222,7 +223,11 @@ struct Workspace {
     DevBuf<uint16_t> d_vit_patches;
     DevBuf<float> d_vit_tokens;
     // audio analyzer (avd_audio.hip): tables (hanning, twiddles) for the current window lengths, scratch, records
-    DevBuf<double> d_audio_tab; int audio_win = 0, audio_last = 0;
+    // d_audio_tab: hann | cos | sin of the full length audio_win, kept across calls.  d_audio_call / h_audio_call: what changes with every call
+    // (avd_audio_plan.h: the short lengths' table arena, the window table, the two window lists), filled in the pinned mirror and uploaded in one copy
+    DevBuf<double> d_audio_tab; int audio_win = 0;
+    DevBuf<double> d_audio_call; PinBuf<double> h_audio_call;
+    int audio_upload_pending = 0;         // that copy was enqueued by a call that has not drained the stream since
     DevBuf<double> d_audio_buf;
     DevBuf<avd_audio_window> d_audio_out;
     // CNN extension (avd_cnn.hip): activation scratch for cnn_frames frames
@@ -312,6 +317,14 @@ struct avd_ctx {
     int cnn_plan_valid = 0;         // 0 until the first forward
     int audio_plan[4] = {};         // nwin, win, last, nfull (windows on the 80 x 100 path) of the last avd_audio_features (debug buffer "audio_plan")
     int audio_plan_valid = 0;       // 0 until the first one, and while a later one has not enqueued all its launches
+    int audio_tracks[avd_audio::kMaxTracks][3] = {};   // per track of that call: first window, windows, length of the last window (debug buffer "audio_tracks")
+    int audio_ntracks = 0;
+    int audio_host[2] = {};         // of that call: microseconds the host spent forming the short lengths' tables, and how many distinct lengths (debug buffer "audio_host")
+    int audio_format = 0;           // option "audio_format": what `wav` of avd_audio_features points at -- 0 float32 samples, 1 little-endian int16 PCM ((float)s * 2^-15)
+    // option "audio_cut": the track boundaries of the NEXT avd_audio_features call, strictly ascending sample positions.  One-shot: that call takes
+    // the list whatever becomes of it, so a forgotten list never splits a later call and results do not depend on the context's history
+    int audio_cuts[avd_audio::kMaxCuts] = {};
+    int audio_ncuts = 0;
     int cnn_chunk = 128;            // CNN extension: frames per forward pass (activation scratch = 4 x 1.6 MB per frame)
     int cnn_fuse = 2;               // CNN extension: a block's 3x3 and expanding 1x1 in one launch (stages 1, 2): 2 = with the 3x3's input slab in LDS in the stride-1 blocks (k_slab3_expand), 1 = gathering kernels only, 0 = layer by layer
     int fb_fused = 0xF;             // bit k: pyramid level k runs the fused kernel (avd_fbfused.hip) instead of the two-kernel path (avd_fbtwo.hip)
@@ -412,8 +425,8 @@ int comm_init(avd_ctx* ctx, int rank, int world, const void* id128);
 void comm_destroy(avd_ctx* ctx);
 int comm_allgather_records(avd_ctx* ctx, const avd_frame_record* local, int count, avd_frame_record* all);
 int comm_allgather_last_records(avd_ctx* ctx, int count, avd_frame_record* all);
-// avd_audio.hip: per-window features of a mono float32 waveform (device pointers)
-int launch_audio_features(avd_ctx* ctx, const float* d_wav, int64_t n, int win, avd_audio_window* d_out, int nwin);
+// avd_audio.hip: per-window features of the mono tracks of `plan` (device pointers; format: option "audio_format")
+int launch_audio_features(avd_ctx* ctx, const void* d_wav, int format, const avd_audio::Plan& plan, avd_audio_window* d_out);
 // avd_fbfused.hip: all blur iterations of one pyramid level (w = 40 / 80 / 160 / 320) in one launch, one workgroup per pair
 // zero_first: the initial flow is zero whatever the buffer holds (the coarsest level: no clearing launch)
 // plist (may be null): the launch works on pairs plist[0 .. np)

@@ -398,7 +398,29 @@ int avd_softmax(avd_ctx* ctx, const float* x, int mem, int64_t rows, int cols, f
  *   flatness = exp(sum_log / nbins) / (sum_mag / nbins); rolloff = rolloff_index / max(1, nbins);
  *   centroid = sum_fmag / sum_mag          (mag = |rfft(seg * hanning)| + 1e-9, all sums in double)
  * and the scalar tail (audio.py:63-110) is host numpy (avd_hip/audio.py).  sumsq is accumulated in double where
- * audio.py:44 squares and averages in float32 (a deliberate deviation, inside 1e-6 of the reference's rms). */
+ * audio.py:44 squares and averages in float32 (a deliberate deviation, inside 1e-6 of the reference's rms).
+ *
+ * Two options of avd_set_option shape a call; with both at their defaults every call is what it was before they existed.  No function and no
+ * AVD_FMT_* value is added, and AVD_ABI_VERSION stays 3.
+ *   "audio_format" (durable, reads back): 0 (default) float32 samples; 1 little-endian int16 PCM -- wav then points at int16 samples, n still
+ *     counts samples, and sample s is the float32 value (float)s * 2^-15: exact for all 65536 values, and what a 16-bit file read as float32
+ *     gives (the reference's input).  The samples are widened in registers; host input is staged as 2 * n bytes.  Any other value is
+ *     AVD_ERR_ARG with a message that begins "audio_format:", and the old value stays.  With format 1 an odd wav address is AVD_ERR_ARG before
+ *     anything is staged.
+ *   "audio_cut" (one-shot, for the NEXT avd_audio_features call): a value s > 0 says that a track ends and the next one begins at sample s of that
+ *     call's buffer.  Cuts are set one at a time in strictly ascending order, at most 63 (64 tracks); -1 clears the list; the option reads back as
+ *     the number of cuts held.  A value of 0 or below other than -1, a value not above the last cut and a 64th cut are AVD_ERR_ARG with a message
+ *     that begins "audio_cut:", and the list stays as it was.  The next avd_audio_features call takes the list whether it succeeds, is refused
+ *     or fails: a forgotten list never splits a later call.
+ *     With cuts c1 < ... < ck the n samples are k + 1 tracks [0, c1), [c1, c2), ..., [ck, n), each windowed from its own start with its own short
+ *     last window; windows receives the records track after track, ceil(n_t / win) per track, and the records of a track are byte for byte those
+ *     of avd_audio_features on that track's samples alone.  Checked after the argument checks above and before anything is staged, in this order:
+ *     a cut >= n is AVD_ERR_ARG ("audio_cut: beyond the buffer"); max_windows below the sum of the tracks' window counts is AVD_ERR_ARG.  n = 0
+ *     with cuts pending is AVD_OK, writes nothing and clears the list.
+ * avd_debug_fetch, host state of the last call that ran: "audio_tracks" int32[tracks][3] -- per track its first window, its windows and the length
+ * of its last window; "audio_plan" int32[4] -- windows of all tracks, win, the LAST track's last length, windows of all tracks that took the
+ * 80 x 100 transform; "audio_host" int32[2] -- the microseconds the host spent forming the tables of the call's short window lengths, and how
+ * many distinct short lengths it had.  "audio_xw" double[windows][win] and "audio_mag" double[windows][win / 2 + 1] are indexed by the call's window number. */
 typedef struct avd_audio_window {
     double sumsq;            /* sum of seg^2                                             (audio.py:44) */
     double sum_log;          /* sum of log(mag)                                          (audio.py:50) */
@@ -551,6 +573,8 @@ int avd_set_profiling(avd_ctx* ctx, int enable);
  * avd_allgather_last_records is refused (AVD_ERR_UNSUPPORTED, naming stream_map): the restored frames' records lie between the clips' in HBM and
  * compacting them on the device is left out; gather the handed-out records with avd_allgather_records.  Left out as well: each clip still has its own
  * preprocess and hash launch, whatever geometries the clips share.
+ * "audio_format" (0 float32, 1 int16 PCM; durable) and "audio_cut" (the track boundaries of the next avd_audio_features call; one-shot) belong to the
+ * audio analyzer and are described at avd_audio_features.
  * avd_get_option returns the value an option has now (environment defaults included) and the read-only "rerun_pairs" and "stream_frames". */
 int avd_set_option(avd_ctx* ctx, const char* name, int value);
 int avd_get_option(avd_ctx* ctx, const char* name, int* value);
@@ -610,7 +634,9 @@ int avd_kernel_ms(avd_ctx* ctx, int kernel_id, float* ms);
  * the others took the direct sum) of the last avd_audio_features call of the context; an error before any such call.
  * "audio_xw" double[nwin][win]: the windowed samples seg * hanning of that call (a short last window fills only its first `last` entries).
  * "audio_mag" double[nwin][win / 2 + 1]: the magnitudes |rfft| + 1e-9 its sums were taken over (a short last window: its first last / 2 + 1
- * entries).  Both are an error before any such call and after avd_release_workspace.
+ * entries).  Both are an error before any such call and after avd_release_workspace.  A call of several tracks (option "audio_cut"): nwin and
+ * nfull count the windows of all tracks, last is the last track's, the rows are the call's windows track after track; "audio_tracks" int32[tracks][3]
+ * and "audio_host" int32[2] are described at avd_audio_features.
  * "stream_state" int32[8][2], host state: for each stream slot 1 ... 8 the frames it has absorbed since it was last emptied and the clip position
  * option "stream_map" maps to it (-1: none).
  * "stream_call" int32[4], host state, of the last avd_analyze_* call that brought frames: the clips that continued a FILLED slot, the launches that restored
