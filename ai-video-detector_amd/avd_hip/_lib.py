@@ -1122,6 +1122,18 @@ class Context:
         buffers (restored frames included); avd_debug_fetch "stream_call"."""
         return self.debug_fetch("stream_call", (4,), np.int32)
 
+    # -- option "ingest_group" (include/avd.h): the clips of a call that share a key share one ingest and one hash launch ---------------------
+    def ingest_call(self) -> np.ndarray:
+        """int32[4] of the last analyze_* call: ingest launches, hash launches, groups of more than one clip, frames ingested by grouped
+        launches; avd_debug_fetch "ingest_call"."""
+        return self.debug_fetch("ingest_call", (4,), np.int32)
+
+    def ingest_groups(self) -> np.ndarray:
+        """int32[launches][4] of that call, in launch order: first clip position, clips, frames, kernel id (as in ingest_plan);
+        avd_debug_fetch "ingest_groups"."""
+        launches = int(self.ingest_call()[0])
+        return self.debug_fetch("ingest_groups", (launches, 4), np.int32) if launches else np.zeros((0, 4), np.int32)
+
     def set_profiling(self, on: bool):
         self._check(self._L.avd_set_profiling(self._h, int(bool(on))))
 

@@ -320,10 +320,14 @@ class StreamMux:
 
     MAX_STREAMS = 8                                   # the context's stream slots
 
-    def __init__(self, ctx: Optional["_lib.Context"] = None, chunk: int = 8, device: int = 0):
+    def __init__(self, ctx: Optional["_lib.Context"] = None, chunk: int = 8, device: int = 0, group: Optional[bool] = None):
+        """group: option "ingest_group" (include/avd.h) for the rounds of run() -- True: the streams of a round that share a geometry, layout and
+        alignment are ingested by one launch instead of one each; False: a launch per stream; None (default): whatever the context is set to,
+        and no call is made for it.  The records are the same either way.  run() restores the context's value behind its drain."""
         self._own = ctx is None
         self.ctx = ctx or _lib.Context(device)
         self.chunk = max(1, int(chunk))
+        self.group = None if group is None else bool(group)
 
     def close(self):
         if self._own and self.ctx is not None:
@@ -362,7 +366,11 @@ class StreamMux:
         for i in range(len(specs)):
             ctx.stream_reset(i + 1)
         ctx.stream_map({i: i + 1 for i in range(len(specs))})
+        group_was = None
         try:
+            if self.group is not None:
+                group_was = ctx.get_option("ingest_group")
+                ctx.set_option("ingest_group", int(self.group))
             bufs = pull()
             while any(bufs):
                 rec = np.zeros(sum(len(b) for b in bufs), _lib.RECORD_DTYPE)
@@ -382,7 +390,11 @@ class StreamMux:
             try:
                 ctx.synchronize()
             finally:
-                ctx.stream_map(None)
+                try:
+                    if group_was is not None:
+                        ctx.set_option("ingest_group", group_was)
+                finally:
+                    ctx.stream_map(None)
         return [np.concatenate(o) if o else np.zeros(0, _lib.RECORD_DTYPE) for o in out]
 
 

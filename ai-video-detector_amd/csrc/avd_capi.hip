@@ -484,6 +484,8 @@ static void audio_cut_set(avd_ctx* ctx, int v)
     else ctx->audio_cuts[ctx->audio_ncuts++] = v;
 }
 static int audio_cut_read(const avd_ctx* ctx) { return ctx->audio_ncuts; }
+// "ingest_group": 0 a launch pair per clip, 1 one per group of clips that share a key (avd_ingest_group.h); durable
+static bool opt_ingest_group(int& v) { return v == 0 || v == 1; }
 static int env_any_base(const char* e) { return (int)std::strtol(e, nullptr, 0); }
 static int env_fb_mode(const char* e) { return (std::strcmp(e, "exact") == 0 || std::strcmp(e, "0") == 0) ? 0 : 1; }
 static const Option kOptions[] = {
@@ -509,6 +511,7 @@ static const Option kOptions[] = {
     {"stream_frames", nullptr, false, opt_any, nullptr, nullptr, nullptr, nullptr, stream_frames},
     {"audio_format", &avd_ctx::audio_format, true, opt_audio_format, nullptr, nullptr, "audio_format: 0 (float32 samples) or 1 (little-endian int16 PCM)"},
     {"audio_cut", nullptr, true, opt_any, nullptr, nullptr, nullptr, audio_cut_set, audio_cut_read, audio_cut_check},
+    {"ingest_group", &avd_ctx::ingest_group, true, opt_ingest_group, nullptr, nullptr, "ingest_group: 0 (an ingest and a hash launch per clip) or 1 (one of each per group of clips that share a key)"},
 };
 static const Option* find_option(avd_ctx* ctx, const char* name, bool to_write)
 {
@@ -592,6 +595,7 @@ static int refuse(avd_ctx* ctx, const Refusal& r)
 struct CallLists {
     std::vector<ListStage> stage;      // per clip; empty for a strided clip
     std::vector<size_t> at;            // per clip: its first entry in the table
+    std::vector<size_t> group_at;      // per group of the call's plan (option "ingest_group"): a grouped launch's first entry -- [plane][frames], then its output frames
     size_t entries = 0;
     size_t total(const IngestClip& k, int c) const { return k.is_list ? stage[c].total : clip_stage(k).total; }      // bytes of ws.d_stage clip c occupies
 };
@@ -616,11 +620,56 @@ static int reserve_lists(avd_ctx* ctx, const CallLists& L)
     return ctx->ws.h_ftab.reserve(ctx, L.entries);
 }
 
-// ws.d_stage and the table are reserved: the table can be filled.  One upload for all lists of the call.
-static int upload_lists(avd_ctx* ctx, const IngestClip* clips, int nclips, const CallLists& L)
+// Where the planes of clip c of a call are on the DEVICE, whatever kind of clip it is: the caller's planes, or their places in the staging buffer
+// (the clip occupies ws.d_stage from byte stage_at on, which must be reserved).  What the per-clip path hands its launch, asked per frame: a
+// grouped launch's table and a clip's group key (its 16-byte eligibility) are formed from it.
+struct DevicePlanes {
+    const IngestClip& k;
+    const uint8_t* staged;             // the clip's place in ws.d_stage
+    const ListStage* list;             // a list's staging plan
+    const uint8_t* base[3];            // a strided clip: frame 0's planes
+    DevicePlanes(const Workspace& ws, const IngestClip& clip, size_t stage_at, const ListStage* ls)
+        : k(clip), staged(ws.d_stage + stage_at), list(ls), base{clip.data, clip.uv, clip.v}
+    {
+        if (k.is_list || k.mem != AVD_MEM_HOST || k.n <= 0) return;
+        const ClipStage s = clip_stage(k);
+        for (int p = 0; p < k.planes(); p++) base[p] = staged + s.plane_off[p];
+    }
+    const uint8_t* at(int p, int f) const
+    {
+        if (k.is_list) return k.mem == AVD_MEM_HOST ? staged + list->plane_off[(size_t)p * k.n + f] : k.list[p][f];
+        return base[p] + (int64_t)f * (p == 0 ? k.frame_stride : k.uv_frame_stride);
+    }
+    // the clip's own answer, by the rule it runs under alone (avd_ingest_clip.h)
+    bool vec_eligible() const
+    {
+        if (k.is_list) return ::vec_eligible(k, k.n, [&](int p, int f) { return (uintptr_t)at(p, f); });
+        return strided_vec_eligible(k, base[0], base[1], base[2]);
+    }
+};
+
+// ws.d_stage and the table are reserved: the table can be filled.  One upload for all lists of the call, the tables of its grouped launches
+// (groups, may be null; stage_at: per clip, its first byte of ws.d_stage) included.
+static int upload_lists(avd_ctx* ctx, const IngestClip* clips, int nclips, const CallLists& L, const avd_group::Plan* groups = nullptr,
+                        const size_t* stage_at = nullptr)
 {
     if (!L.entries) return 0;
     Workspace& ws = ctx->ws;
+    for (size_t gi = 0; groups && gi < groups->groups.size(); gi++) {
+        const avd_group::Group& G = groups->groups[gi];
+        if (!G.grouped) continue;
+        const uint8_t** tab = ws.h_ftab + L.group_at[gi];
+        const int planes = clips[G.members.front().clip].planes();
+        int* out = reinterpret_cast<int*>(tab + (size_t)planes * G.frames);
+        for (const avd_group::Member& m : G.members) {
+            const DevicePlanes dp(ws, clips[m.clip], stage_at[m.clip], &L.stage[(size_t)m.clip]);
+            for (int f = 0; f < m.n; f++) {
+                for (int p = 0; p < planes; p++) tab[(size_t)p * G.frames + m.g0 + f] = dp.at(p, f);
+                out[m.g0 + f] = m.out0 + f;
+            }
+        }
+        if (G.frames & 1) out[G.frames] = 0;           // the other half of the last entry
+    }
     size_t st = 0;
     for (int c = 0; c < nclips; c++) {
         const IngestClip& k = clips[c];
@@ -640,15 +689,32 @@ static int upload_lists(avd_ctx* ctx, const IngestClip* clips, int nclips, const
 
 // Stage clip c of the call at offset `at` of ws.d_stage (host input; reserved by the caller) and launch its fused full-resolution kernel, which
 // writes the clip's slice of the per-frame buffers with the clip's geometry (slot).
-static int preprocess_clip(avd_ctx* ctx, const ClipSlot& slot, const IngestClip& k, size_t at, const CallLists& L, int c)
+// the copies alone (nothing for device input): a grouped launch has those of all its clips enqueued ahead of it
+static int stage_clip(avd_ctx* ctx, const IngestClip& k, size_t at, const CallLists& L, int c)
 {
     uint8_t* dst = ctx->ws.d_stage + at;
+    if (k.mem != AVD_MEM_HOST) return 0;
     if (k.is_list) {
         const ListStage& s = L.stage[c];
         for (const StageSpan& sp : s.span)
             HIP_TRY(ctx, hipMemcpyAsync(dst + sp.off, sp.src, sp.bytes, hipMemcpyHostToDevice, ctx->stream));
         ctx->ingest.stage_bytes += (int64_t)s.copied;
         ctx->ingest.stage_copies += (int64_t)s.span.size();
+        return 0;
+    }
+    const ClipStage s = clip_stage(k);
+    for (int i = 0; i < s.nspans; i++)
+        HIP_TRY(ctx, hipMemcpyAsync(dst + s.span[i].off, s.span[i].src, s.span[i].bytes, hipMemcpyHostToDevice, ctx->stream));
+    ctx->ingest.stage_bytes += (int64_t)s.copied;
+    ctx->ingest.stage_copies += s.nspans;
+    return 0;
+}
+
+static int preprocess_clip(avd_ctx* ctx, const ClipSlot& slot, const IngestClip& k, size_t at, const CallLists& L, int c)
+{
+    uint8_t* dst = ctx->ws.d_stage + at;
+    if (int e = stage_clip(ctx, k, at, L, c)) return e;
+    if (k.is_list) {
         const uint8_t* const* h_tab = ctx->ws.h_ftab + L.at[c];
         const uint8_t* const* d_tab = ctx->ws.d_ftab + L.at[c];
         const FrameTable ft{list_vec_eligible(k, h_tab)};
@@ -658,10 +724,6 @@ static int preprocess_clip(avd_ctx* ctx, const ClipSlot& slot, const IngestClip&
     const uint8_t *d_in = k.data, *d_uv = k.uv, *d_v = k.v;
     if (k.mem == AVD_MEM_HOST) {
         const ClipStage s = clip_stage(k);
-        for (int i = 0; i < s.nspans; i++)
-            HIP_TRY(ctx, hipMemcpyAsync(dst + s.span[i].off, s.span[i].src, s.span[i].bytes, hipMemcpyHostToDevice, ctx->stream));
-        ctx->ingest.stage_bytes += (int64_t)s.copied;
-        ctx->ingest.stage_copies += s.nspans;
         d_in = dst + s.plane_off[0];
         if (k.planes() >= 2) d_uv = dst + s.plane_off[1];
         if (k.planes() == 3) d_v = dst + s.plane_off[2];
@@ -813,7 +875,12 @@ static int impl_analyze_async(avd_ctx* ctx, const IngestClip* clips, int nclips,
         plan_in[c] = {clips[c].n, !stream[c] ? avd_stream::kUnmapped : (stream[c]->frames > 0 ? avd_stream::kMappedFilled : avd_stream::kMappedEmpty)};
     }
     if (total > (1 << 24)) { ctx->err = "too many frames in one call"; return AVD_ERR_ARG; }
-    if (total == 0) { for (int& v : ctx->stream_call) v = 0; return AVD_OK; }
+    if (total == 0) {
+        for (int& v : ctx->stream_call) v = 0;
+        for (int& v : ctx->ingest_call) v = 0;
+        ctx->ingest_groups.clear();
+        return AVD_OK;
+    }
     const avd_stream::Plan plan = avd_stream::plan_call(plan_in.data(), nclips);
     if (plan.total > (1 << 24)) { ctx->err = "too many frames in one call"; return AVD_ERR_ARG; }
     if (!records) { ctx->err = "null pointer"; return AVD_ERR_ARG; }
@@ -832,15 +899,38 @@ static int impl_analyze_async(avd_ctx* ctx, const IngestClip* clips, int nclips,
         if (k.n == 0) continue;
         ClipSlot& slot = slots[c];
         if (int e = avd_ws_geometry(ctx, k.disp_h(), k.disp_w(), slot)) return e;
-        slot.f0 = plan.f0[c]; slot.rowbuf_off = rowbuf_elems; slot.lappart_off = lappart_elems;
+        slot.f0 = plan.f0[c];
         stage_at[c] = stage_bytes;
-        rowbuf_elems += rowbuf_elems_for(slot.pre, k.n);
-        lappart_elems += lappart_elems_for(slot.pre, k.n);
         stage_bytes += lists.total(k, c);
     }
+    if (int e = ws.d_stage.reserve(ctx, stage_bytes)) return e;
+    // Which clips share their two launches (avd_ingest_group.h).  With option "ingest_group" off nobody does -- a bound of 0 bands puts every clip in
+    // a group of its own, in call order, and the row and Laplacian partials are handed out clip by clip as they always were.  A clip's key needs
+    // its planes' device addresses (its 16-byte eligibility), hence the staging buffer first.
+    const bool grouping = ctx->ingest_group != 0;
+    std::vector<avd_group::Key> keys((size_t)nclips);
+    std::vector<int> clip_n((size_t)nclips);
+    for (int c = 0; c < nclips; c++) {
+        const IngestClip& k = clips[c];
+        clip_n[c] = k.n;
+        if (k.n == 0) continue;
+        keys[c] = avd_group::key_of(k, slots[c].pre.nbands, grouping && DevicePlanes(ws, k, stage_at[c], &lists.stage[c]).vec_eligible());
+    }
+    const avd_group::Plan groups = avd_group::plan_groups(keys.data(), clip_n.data(), plan.f0.data(), nclips, grouping ? avd_group::kMaxLaunchBands : 0);
+    lists.group_at.assign(groups.groups.size(), 0);
+    for (size_t gi = 0; gi < groups.groups.size(); gi++) {
+        const avd_group::Group& G = groups.groups[gi];
+        if (G.grouped) {
+            lists.group_at[gi] = lists.entries;
+            lists.entries += avd_group::table_entries(clips[G.members.front().clip].planes(), G.frames);
+        } else {
+            ClipSlot& slot = slots[(size_t)G.members.front().clip];
+            slot.rowbuf_off = G.rowbuf_off; slot.lappart_off = G.lappart_off;
+        }
+    }
+    rowbuf_elems = groups.rowbuf_elems; lappart_elems = groups.lappart_elems;
     if (int e = avd_ws_reserve_frames(ctx, n, rowbuf_elems, lappart_elems)) return e;
     if (int e = avd_ws_reserve_fb(ctx, n)) return e;
-    if (int e = ws.d_stage.reserve(ctx, stage_bytes)) return e;
     if (int e = reserve_lists(ctx, lists)) return e;
     // every continued slot's buffer (an empty slot's first call; frames = 0: still empty if the call fails), and the two tables of the copy kernel
     StreamCopyTable restore{}, save{};
@@ -867,20 +957,42 @@ static int impl_analyze_async(avd_ctx* ctx, const IngestClip* clips, int nclips,
     // each filled slot's frame becomes its clip's carry frame (device to device, ordered on the stream like everything else; inside the first
     // region): ONE launch for all of them
     if (nrestore) HIP_TRY(ctx, stream_copy(ctx, restore, nrestore, false));
-    if (int e = upload_lists(ctx, clips, nclips, lists)) return e;
+    if (int e = upload_lists(ctx, clips, nclips, lists, &groups, stage_at.data())) return e;
     std::copy(plan.clipstart.begin(), plan.clipstart.end(), ws.h_clipstart.p);
-    for (int c = 0; c < nclips; c++) {
+    // one ingest and one hash launch per group, in the order of the groups' first clips: a clip alone in its group runs the per-clip path (with the
+    // option off every clip does), several clips run ONE listed launch over all their frames with the group's table of output frames
+    std::vector<int> launched;                             // "ingest_groups" of this call
+    int grouped_launches = 0, grouped_frames = 0;
+    for (size_t gi = 0; gi < groups.groups.size(); gi++) {
+        const avd_group::Group& G = groups.groups[gi];
+        const int c = G.members.front().clip;
         const IngestClip& k = clips[c];
-        if (k.n == 0) continue;
-        ClipSlot& slot = slots[c];
+        ClipSlot& slot = slots[c];                         // a group's launches run with its first clip's slot: the geometry is the group's
         // the tables again: a cache hit (pass 1 built them) unless the call has > kGeomCache geometries -- then pass 1 has evicted this one since,
         // the slot's copies point into freed tables, and they are rebuilt here (same geometry, same sizes: the offsets hold)
         if (int e = avd_ws_geometry(ctx, k.disp_h(), k.disp_w(), slot)) return e;
         if (!first_clip) kmark(ctx, AVD_K_PREPROCESS);
         first_clip = false;
-        if (int e = preprocess_clip(ctx, slot, k, stage_at[c], lists, c)) return e;
-        kmark(ctx, AVD_K_HASH);
-        if (int e = launch_hash(ctx, slot, k.n)) return e;
+        if (!G.grouped) {
+            if (int e = preprocess_clip(ctx, slot, k, stage_at[c], lists, c)) return e;
+            kmark(ctx, AVD_K_HASH);
+            if (int e = launch_hash(ctx, slot, k.n)) return e;
+        } else {
+            for (const avd_group::Member& m : G.members)
+                if (int e = stage_clip(ctx, clips[m.clip], stage_at[m.clip], lists, m.clip)) return e;
+            slot.rowbuf_off = G.rowbuf_off; slot.lappart_off = G.lappart_off;
+            const uint8_t* const* d_tab = ws.d_ftab + lists.group_at[gi];
+            const int* d_out = reinterpret_cast<const int*>(d_tab + (size_t)k.planes() * G.frames);
+            const FrameTable ft{G.key.vec != 0, d_out, G.frames};
+            auto plane = [&](int p) { return p < k.planes() ? reinterpret_cast<const uint8_t*>(d_tab + (size_t)p * G.frames) : nullptr; };
+            if (int e = launch_preprocess(ctx, slot, k, plane(0), plane(1), plane(2), &ft)) return e;
+            kmark(ctx, AVD_K_HASH);
+            if (int e = launch_hash(ctx, slot, G.frames, d_out)) return e;
+            grouped_launches++;
+            grouped_frames += G.frames;
+        }
+        const int row[4] = {c, (int)G.members.size(), G.frames, ctx->ingest.plan.kernel};
+        launched.insert(launched.end(), row, row + 4);
     }
     kmark(ctx, AVD_K_OTHER, stage_mark(ctx, 1));
     const int* clipstart = nullptr;                        // one segment: frame 0 is the only one without a predecessor
@@ -907,11 +1019,15 @@ static int impl_analyze_async(avd_ctx* ctx, const IngestClip* clips, int nclips,
     // the whole call is done and it would not be asynchronous at all; avd_synchronize hands the records over
     // (all n of them, the slot's frame included: the deferred re-run finds its chunk's flag words where it always does)
     ctx->pending_runs = plan.runs;                         // (can throw: while an error still drops the tail, and before the counters move)
+    ctx->ingest_groups.reserve(launched.size());           // (the same: the swap below cannot)
     HIP_TRY(ctx, hipMemcpyAsync(ws.h_rec, ws.d_rec, sizeof(avd_frame_record) * n, hipMemcpyDeviceToHost, ctx->stream));
     tail_on_error.ok = true;
     for (int c = 0; c < nclips; c++)
         if (stream[c]) stream[c]->frames = (int)std::min<int64_t>((int64_t)stream[c]->frames + clips[c].n, INT32_MAX);
     ctx->pending_out = records;
+    const int launches = (int)groups.groups.size();
+    ctx->ingest_call[0] = launches; ctx->ingest_call[1] = launches; ctx->ingest_call[2] = grouped_launches; ctx->ingest_call[3] = grouped_frames;
+    ctx->ingest_groups.swap(launched);
     ctx->stream_call[0] = plan.carries; ctx->stream_call[1] = nrestore > 0; ctx->stream_call[2] = nsave > 0; ctx->stream_call[3] = n;
     if (ctx->tail.active) tail_register(ctx);              // from here on a waiting thread may settle this call's tail
     if (!ctx->counted_in_flight) { ctx->counted_in_flight = 1; g_calls_in_flight.fetch_add(1, std::memory_order_relaxed); }
@@ -1075,13 +1191,15 @@ static int64_t impl_debug_fetch(avd_ctx* ctx, const char* name, void* out, size_
             {"stage_bytes", &in.stage_bytes, sizeof in.stage_bytes, in.stage_bytes >= 0, no_call, "int64[1]"},
             {"stream_state", stream_state, sizeof stream_state, true, nullptr, "int32[8][2]"},
             {"stream_call", ctx->stream_call, sizeof ctx->stream_call, true, nullptr, "int32[4]"},
+            {"ingest_call", ctx->ingest_call, sizeof ctx->ingest_call, true, nullptr, "int32[4]"},
+            {"ingest_groups", ctx->ingest_groups.data(), sizeof(int) * ctx->ingest_groups.size(), true, nullptr, "int32[launches][4]"},
         };
         for (const auto& e : host_state) {
             if (std::strcmp(name, e.name) != 0) continue;
             if (!e.recorded) { ctx->err = std::string(e.name) + " not recorded yet: " + e.missing; return AVD_ERR_ARG; }
             if (e.type && out_bytes < e.bytes) { ctx->err = std::string(e.name) + " is " + e.type; return AVD_ERR_ARG; }
             bytes = std::min(e.bytes, out_bytes);
-            std::memcpy(out, e.p, bytes);
+            if (bytes) std::memcpy(out, e.p, bytes);      // (no launch yet: "ingest_groups" is empty)
             return (int64_t)bytes;
         }
     }

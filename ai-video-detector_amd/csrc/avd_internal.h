@@ -10,6 +10,7 @@
 #include "avd_ingest_clip.h"      // IngestClip: one clip of an ingest call, its argument check and its staging plan (host only)
 #include "avd_stream_plan.h"      // where the clips of a call lie when some continue a stream slot (host only)
 #include "avd_audio_plan.h"       // the tracks, window table and table arena of one avd_audio_features call (host only)
+#include "avd_ingest_group.h"     // which clips of a call share an ingest launch (option "ingest_group"), and kLapSlots (host only)
 
 #define AVD_FB_LEVELS 4            // pyramid scales 1/8,1/4,1/2,1 of 320 (see avd_farneback.hip)
 #define AVD_NPIX (AVD_SMALL * AVD_SMALL)
@@ -108,7 +109,7 @@ struct IngestRecord {
     int32_t rotate = 0;              // "ingest_rotate": the rotation that launch ran with
     int32_t range = 0;               // "ingest_range": 1 if it ran with full-range conversion constants
     int32_t format = 0;              // "ingest_format": its layout (AVD_FMT_*)
-    int32_t list[2] = {0, 0};        // "ingest_list": it took its frame bases from a table of plane pointers / the frames the table held
+    int32_t list[2] = {0, 0};        // "ingest_list": it took its frame bases from a table of plane pointers (2: a grouped launch, with a table of output frames) / the frames the table held
     int64_t stage_copies = -1;       // "stage_copies": host-to-device staging copies of the last ingest call; -1 until the first one
     int64_t stage_bytes = -1;        // "stage_bytes": bytes that call copied from host memory (0: device input); -1 until the first one
 };
@@ -118,7 +119,6 @@ enum CnnShape { kCnnFolded = 0, kCnn128x128, kCnn256x64, kCnn256x128, kCnn256x25
 constexpr int kCnnConvs = 53;      // convolutions of the network, in avd_cnn_set_weights order
 // option "cnn_tap": which intermediate avd_cnn_forward copies aside (0 = none); kCnnTapConv0 + i = the output of convolution i
 constexpr int kCnnTapImage = 1, kCnnTapConv0 = 2, kCnnTapMaxPool = kCnnTapConv0 + kCnnConvs, kCnnTapPooled = kCnnTapMaxPool + 1;
-constexpr int kLapSlots = 8;       // per-band slots of Workspace::d_lap_part, one per wave of the workgroup (4 written)
 
 // ---- owners of device and pinned host memory ------------------------------------------------
 // Move-only: pointer + capacity in elements, freed on destruction and on move-assignment.  Converts to its pointer, so
@@ -300,6 +300,11 @@ struct avd_ctx {
     // position at most, and the map is empty while stream_slot != 0 (avd_set_option refuses either way): the two ways of choosing slots never hold at once
     int stream_map[kStreamMapPositions] = {};
     int stream_mapped = 0;           // positions mapped
+    // option "ingest_group": 0 = every clip of an avd_analyze_* call has an ingest launch and a k_hash launch of its own; 1 = the clips of a call that
+    // share a key (avd_ingest_group.h: geometry, layout, rotation, range, row strides, 16-byte eligibility) share ONE of each.  Durable; no effect on results
+    int ingest_group = 0;
+    int ingest_call[4] = {};         // debug buffer "ingest_call", of the last avd_analyze_* call: ingest launches, hash launches, groups of more than one clip, frames ingested by grouped launches
+    std::vector<int> ingest_groups;  // debug buffer "ingest_groups", of that call: per launch {first clip position, clips, frames, IngestKernel id}
     int stream_call[4] = {};         // debug buffer "stream_call", of the last avd_analyze_* call: clips that continued a filled slot, restore launches, save launches, frames in the buffers
     void* comm = nullptr;            // RCCL communicator (avd_comm.cpp), bound at run time
     int comm_rank = 0, comm_world = 1;
@@ -396,10 +401,14 @@ int Buf<T, kPinned>::reserve(avd_ctx* ctx, size_t count)
 // into the clip's slice of the per-frame buffers, with the clip's geometry (slot); which it is says clip.format
 // list (null: strided): the frames come from a device table of plane pointers (avd_frame_list) -- d_in / d_uv / d_v are then the addresses of the
 // table's per-plane arrays, n entries each, and the clip's frame strides are unused
-struct FrameTable { bool aligned; };      // aligned: every frame of the list allows the 16-byte fills (list_vec_eligible)
+// A grouped launch (option "ingest_group") is a listed launch over the n frames of several clips that share clip's key -- `clip` is the first of
+// them -- with a device table out_frame[n]: frame g of the launch writes its 320-px image at frame out_frame[g] of ws.d_small (slot.f0 is unused),
+// its row and Laplacian partials at g of the slot's run.
+struct FrameTable { bool aligned; const int* out_frame = nullptr; int n = 0; };      // aligned: every frame of the list allows the 16-byte fills (list_vec_eligible); out_frame / n: a grouped launch
 int launch_preprocess(avd_ctx* ctx, const ClipSlot& slot, const IngestClip& clip, const uint8_t* d_in, const uint8_t* d_uv, const uint8_t* d_v,
                       const FrameTable* list = nullptr);
-int launch_hash(avd_ctx* ctx, const ClipSlot& slot, int n);       // the clip's n frames
+// the clip's n frames; out_frame (device, may be null): a grouped launch's n frames, whose cells, bits and moments go to frame out_frame[g] of the buffers
+int launch_hash(avd_ctx* ctx, const ClipSlot& slot, int n, const int* out_frame = nullptr);
 int avd_calls_in_flight();      // avd_capi.hip: contexts of this process holding an enqueued, undrained avd_analyze_* call
 // all pairs of n resident frames, into the Farneback scratch; *left (and ws.fb_holds) = what it holds then
 int launch_farneback(avd_ctx* ctx, const FlowCall& call, const uint8_t* d_small, int n, FbChunk* left);

@@ -154,7 +154,9 @@ __device__ __forceinline__ T wave_sum(T v)
 }
 
 // The band a workgroup owns.  blockIdx -> lid = (frame, band): logical ids that are consecutive share blockIdx % 8, i.e. an XCD.
-struct Band { int lid, f, band, r0, rows, trows; };      // rows [r0, r0 + rows) of frame f; tile row 0 = image row r0 - 1, trows = rows + 2
+// of: the frame of the per-frame outputs (the 320-px image) the band writes -- f itself, except in a grouped launch (OutFrames below), whose
+// frames come from several clips; the row and Laplacian partials stay at f (lid), which only the launch's own k_hash reads
+struct Band { int lid, f, band, r0, rows, trows, of; };      // rows [r0, r0 + rows) of frame f; tile row 0 = image row r0 - 1, trows = rows + 2
 
 // (no branch in here: the caller's early return then leaves the compiler free to sink the division under the first loads)
 __device__ __forceinline__ bool decode_band(const PreParams& P, int n, Band& b)      // false: idle tail block, b unusable
@@ -185,6 +187,20 @@ __device__ __forceinline__ const uint8_t* frame_base(const uint8_t* plane, int f
     if constexpr (FR == Frames::listed) return (const uint8_t*)reinterpret_cast<const GlobalPlane*>(plane)[f];
     else return plane + (int64_t)f * frame_stride;
 }
+
+// The output frame of frame f of a launch.  strided: f, at compile time -- the argument is an empty struct and the strided instantiations contain
+// no trace of it.  listed: entry f of a device table (a grouped launch, option "ingest_group": the frames of several clips, whose places in the
+// per-frame buffers are not one run), or f where the table is null (a plain list).  f is uniform over the workgroup: like the plane pointers,
+// the entry arrives by one scalar load per workgroup.
+using GlobalInts = const __attribute__((address_space(1))) int*;
+template <Frames FR> struct OutFrames;
+template <> struct OutFrames<Frames::strided> {
+    __device__ __forceinline__ int at(int f) const { return f; }
+};
+template <> struct OutFrames<Frames::listed> {
+    const int* tab;
+    __device__ __forceinline__ int at(int f) const { return tab ? ((GlobalInts)tab)[f] : f; }
+};
 
 __device__ __forceinline__ int reflect_once(int p, int len)      // valid for -len < p < 2*len-1
 {
@@ -428,7 +444,7 @@ __device__ __forceinline__ Moments band_phases(const uint8_t* tile, const LdsTab
     // ---- INTER_LINEAR 320x320 rows whose upper source row lies in this band ----------------
     {
         const int d0 = P.band_dy[band], d1 = P.band_dy[band + 1];        // wave-uniform scalar loads
-        uint8_t* dst = small + (int64_t)f * AVD_NPIX;
+        uint8_t* dst = small + (int64_t)b.of * AVD_NPIX;
         // a lane owns output COLUMNS (its x taps are unpacked once); the rows of the band are walked with
         // wave-uniform y taps held in scalar registers
         for (int dx = tid; dx < AVD_SMALL; dx += kThreads) {
@@ -1250,7 +1266,7 @@ struct Nv16 {
 
 // Generic kernel: any geometry / alignment that POL's fill takes; the resampling tables are read from global memory.
 template <typename POL, Frames FR, typename... Extra>
-__global__ __launch_bounds__(kThreads) void k_preprocess(const uint8_t* __restrict__ plane0, Extra... extra, int n,
+__global__ __launch_bounds__(kThreads) void k_preprocess(const uint8_t* __restrict__ plane0, Extra... extra, int n, OutFrames<FR> out,
                                                         PreParams P, uint8_t* __restrict__ small,
                                                         float* __restrict__ rowbuf,
                                                         long long* __restrict__ lap_part)
@@ -1258,6 +1274,7 @@ __global__ __launch_bounds__(kThreads) void k_preprocess(const uint8_t* __restri
     extern __shared__ __align__(16) uint8_t tile[];
     Band b;
     if (!decode_band(P, n, b)) return;
+    b.of = out.at(b.f);
     const int tid = threadIdx.x;
     POL::fill(tile, POL::template planes<FR>(plane0, extra..., P, b.f), extra..., P, b, tid);
     fill_column_halo(tile, b.trows, P.pitch, P.w, tid);
@@ -1267,7 +1284,7 @@ __global__ __launch_bounds__(kThreads) void k_preprocess(const uint8_t* __restri
 // Aligned fast path: the band staged in registers (fill_staged, which also writes the column halo) and the resampling tables in LDS, fetched
 // ahead of the band's loads.
 template <typename POL, Frames FR, typename... Extra>
-__global__ __launch_bounds__(kThreads, 4) void k_preprocess_vec(const uint8_t* __restrict__ plane0, Extra... extra, int n,
+__global__ __launch_bounds__(kThreads, 4) void k_preprocess_vec(const uint8_t* __restrict__ plane0, Extra... extra, int n, OutFrames<FR> out,
                                                                PreParams P, uint8_t* __restrict__ small,
                                                                float* __restrict__ rowbuf,
                                                                long long* __restrict__ lap_part)
@@ -1275,6 +1292,7 @@ __global__ __launch_bounds__(kThreads, 4) void k_preprocess_vec(const uint8_t* _
     extern __shared__ __align__(16) uint8_t tile[];
     Band b;
     if (!decode_band(P, n, b)) return;
+    b.of = out.at(b.f);
     const int tid = threadIdx.x;
     LdsTabs* lt = reinterpret_cast<LdsTabs*>(tile + lds_tile_bytes(P.rows_per_band + 2, P.pitch));
     fill_lds_tabs(lt, P, tid);
@@ -1285,10 +1303,13 @@ __global__ __launch_bounds__(kThreads, 4) void k_preprocess_vec(const uint8_t* _
 
 // 32x32 INTER_AREA cells from the per-row partials (vertical accumulation in cv2's row
 // order), then aHash bits: g >= mean(g)  <=>  1024*g >= sum(g)   (video.py:7-8)
+// One block per frame f of the launch: it reads the row and Laplacian partials at f and writes the cells, bits and moments at the output frame --
+// f, or (GROUPED: a grouped launch, option "ingest_group") entry f of the same table the ingest launch took.
+template <bool GROUPED>
 __global__ __launch_bounds__(1024) void k_hash(const float* __restrict__ rowbuf, HashParams P,
                                               uint8_t* __restrict__ area, uint8_t* __restrict__ bits,
                                               const long long* __restrict__ lap_part, int nbands, int waves,
-                                              unsigned long long* __restrict__ lap)
+                                              unsigned long long* __restrict__ lap, const int* __restrict__ out_frame)
 {
     __shared__ int wsum[16];
     __shared__ long long lsum[2][16];
@@ -1348,14 +1369,15 @@ __global__ __launch_bounds__(1024) void k_hash(const float* __restrict__ rowbuf,
     int total = 0;
 #pragma unroll
     for (int i = 0; i < 16; i++) total += wsum[i];
-    area[(int64_t)f * 1024 + tid] = (uint8_t)cell;
-    bits[(int64_t)f * 1024 + tid] = (uint8_t)(cell * 1024 >= total);
+    const int of = GROUPED ? out_frame[f] : f;
+    area[(int64_t)of * 1024 + tid] = (uint8_t)cell;
+    bits[(int64_t)of * 1024 + tid] = (uint8_t)(cell * 1024 >= total);
     if (tid == 0) {
         long long s = 0, q = 0;
 #pragma unroll
         for (int i = 0; i < 16; i++) { s += lsum[0][i]; q += lsum[1][i]; }
-        lap[2 * f] = (unsigned long long)s;
-        lap[2 * f + 1] = (unsigned long long)q;
+        lap[2 * of] = (unsigned long long)s;
+        lap[2 * of + 1] = (unsigned long long)q;
     }
 }
 
@@ -1420,6 +1442,7 @@ static constexpr auto ingest_kernel()
 
 // list (null: a strided clip): the clip's frames come from a device table of plane pointers -- d_in / d_uv / d_v are then the addresses of the
 // table's per-plane arrays (n entries each), and list->aligned says whether every frame allows the 16-byte fills (list_vec_eligible).
+// list->out_frame: a grouped launch -- the list's n frames are those of several clips that share `clip`'s key, and each writes where the table says.
 int launch_preprocess(avd_ctx* ctx, const ClipSlot& slot, const IngestClip& clip, const uint8_t* d_in, const uint8_t* d_uv, const uint8_t* d_v,
                       const FrameTable* list)
 {
@@ -1427,8 +1450,11 @@ int launch_preprocess(avd_ctx* ctx, const ClipSlot& slot, const IngestClip& clip
     PreParams P = slot.pre;
     P.row_stride = clip.row_stride;
     P.frame_stride = clip.frame_stride;
-    const int n = clip.n;
+    const bool grouped = list && list->out_frame;
+    const int n = grouped ? list->n : clip.n;
+    if ((int64_t)n * P.nbands > avd_group::kMaxLaunchBands) { ctx->err = "too many bands in one ingest launch"; return AVD_ERR_ARG; }
     const int grid = (n * P.nbands + 7) / 8 * 8;
+    uint8_t* const small = grouped ? ws.d_small.p : ws.d_small + (size_t)slot.f0 * AVD_NPIX;      // a grouped launch's frames name their places in the whole buffer
     const size_t tile = lds_tile_bytes(P.rows_per_band + 2, P.pitch);
     // bgr: no conversion constants -- BGR24 and the four layouts of RGB producers; planar: I420
     const bool bgr = !clip.is_yuv(), planar = clip.planar_yuv(), yuv422 = clip.is_422();
@@ -1466,12 +1492,14 @@ int launch_preprocess(avd_ctx* ctx, const ClipSlot& slot, const IngestClip& clip
         rec.rotate = clip.rotate;
         rec.format = clip.format;
         rec.range = !bgr && clip.full_range;
-        rec.list[0] = list != nullptr;
+        rec.list[0] = grouped ? 2 : list != nullptr;
         rec.list[1] = list ? n : 0;
         dispatch_bool(list != nullptr, [&](auto listed) {
             constexpr Frames FR = decltype(listed)::value ? Frames::listed : Frames::strided;
             auto kernel = ingest_kernel<POL, FR, decltype(extra)...>();
-            hipLaunchKernelGGL(kernel, dim3(grid), dim3(kThreads), lds, ctx->stream, d_in, extra..., n, P, ws.d_small + (size_t)slot.f0 * AVD_NPIX,
+            OutFrames<FR> out{};
+            if constexpr (FR == Frames::listed) out.tab = list->out_frame;
+            hipLaunchKernelGGL(kernel, dim3(grid), dim3(kThreads), lds, ctx->stream, d_in, extra..., n, out, P, small,
                                ws.d_rowbuf + slot.rowbuf_off, ws.d_lap_part + slot.lappart_off);
         });
     };
@@ -1521,14 +1549,16 @@ int launch_preprocess(avd_ctx* ctx, const ClipSlot& slot, const IngestClip& clip
 }
 
 // (the Hamming distances between consecutive frames are formed from these bits by k_records of the analyze entries)
-int launch_hash(avd_ctx* ctx, const ClipSlot& slot, int n)
+int launch_hash(avd_ctx* ctx, const ClipSlot& slot, int n, const int* out_frame)
 {
     Workspace& ws = ctx->ws;
-    // the clip's slice of the call's buffers: frame slot.f0 onwards
-    const size_t f0 = (size_t)slot.f0;
-    hipLaunchKernelGGL(k_hash, dim3(n), dim3(1024), 0, ctx->stream, ws.d_rowbuf + slot.rowbuf_off, slot.hsh, ws.d_area + f0 * 1024,
-                       ws.d_hash + f0 * 1024, (const long long*)(ws.d_lap_part + slot.lappart_off), slot.pre.nbands, kThreads / 64,
-                       ws.d_lap + 2 * f0);
+    // the clip's slice of the call's buffers: frame slot.f0 onwards; a grouped launch's frames name their places in the whole buffers
+    const size_t f0 = out_frame ? 0 : (size_t)slot.f0;
+    dispatch_bool(out_frame != nullptr, [&](auto g) {
+        hipLaunchKernelGGL(k_hash<decltype(g)::value>, dim3(n), dim3(1024), 0, ctx->stream, ws.d_rowbuf + slot.rowbuf_off, slot.hsh, ws.d_area + f0 * 1024,
+                           ws.d_hash + f0 * 1024, (const long long*)(ws.d_lap_part + slot.lappart_off), slot.pre.nbands, kThreads / 64,
+                           ws.d_lap + 2 * f0, out_frame);
+    });
     HIP_TRY(ctx, hipGetLastError());
     return 0;
 }

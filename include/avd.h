@@ -571,8 +571,20 @@ int avd_set_profiling(avd_ctx* ctx, int enable);
  * continued clip behind its restored frame.  A refused call, a call that fails while it is enqueued and a call without frames leave every slot as it was.
  * avd_preprocess_* and avd_farneback_pairs ignore the map, as they ignore "stream_slot".  After a call made under a non-empty map
  * avd_allgather_last_records is refused (AVD_ERR_UNSUPPORTED, naming stream_map): the restored frames' records lie between the clips' in HBM and
- * compacting them on the device is left out; gather the handed-out records with avd_allgather_records.  Left out as well: each clip still has its own
- * preprocess and hash launch, whatever geometries the clips share.
+ * compacting them on the device is left out; gather the handed-out records with avd_allgather_records.  Each clip still has its own
+ * preprocess and hash launch unless "ingest_group" (below) is set.
+ * "ingest_group" (default 0; 0 or 1, anything else is refused with AVD_ERR_ARG, a message that begins "ingest_group:", and the old value stays; durable; no
+ * effect on results): with 1 the clips of ONE avd_analyze_* call (any entry, blocking or asynchronous, with or without "stream_map" / "stream_slot") that
+ * share a group key are ingested by ONE ingest launch and ONE k_hash launch per group instead of one of each per clip -- a round of eight one-frame
+ * streams, or a batch of short clips, is bound by its launches.  The group key: the displayed height and width, the layout, rotate, full range, the row
+ * strides of plane 0 and of the planes behind it, and whether the clip may run the 16-byte fills (decided per clip, by the rule it runs under alone):
+ * an aligned and a misaligned clip of one layout are two groups, and each group runs the kernel its clips run alone.  Strided clips, frame lists, host
+ * and device memory mix freely inside a group; a host clip's staging copies are enqueued ahead of its group's launch, and "stage_bytes" / "stage_copies"
+ * are the sums they are without the option.  Groups run in the order of their first clip.  A group of ONE clip runs today's per-clip path, so a call in
+ * which no two clips share a key enqueues the same launches under both values; with 0 every call enqueues exactly what it did before the option
+ * existed.  The records, and the debug buffers "small", "area", are bit for bit those of option 0.  avd_preprocess_* takes one clip and ignores the option.
+ * What a call did is in avd_debug_fetch "ingest_call" and "ingest_groups"; with profiling on there is one AVD_K_PREPROCESS and one AVD_K_HASH region per
+ * launch, so a grouped call has fewer.  Experimental while the default is 0.
  * "audio_format" (0 float32, 1 int16 PCM; durable) and "audio_cut" (the track boundaries of the next avd_audio_features call; one-shot) belong to the
  * audio analyzer and are described at avd_audio_features.
  * avd_get_option returns the value an option has now (environment defaults included) and the read-only "rerun_pairs" and "stream_frames". */
@@ -623,7 +635,13 @@ int avd_kernel_ms(avd_ctx* ctx, int kernel_id, float* ms);
  * "stage_copies" int64[1], host state: the host-to-device staging copies that call issued, summed over its clips (a strided clip: its merged
  * spans, 1 to 3; a frame list: one per merged span, n x planes for separately allocated frames); an error before any ingest call.
  * "ingest_list" int32[2], host state: 1 if the last ingest launch took its frame bases from a table of plane pointers (avd_frame_list) and
- * the frames that table held, else 0, 0; an error before any ingest launch.
+ * the frames that table held, else 0, 0; 2 and the group's frames for a grouped launch (option "ingest_group"); an error before any ingest launch.
+ * "ingest_call" int32[4], host state, of the last avd_analyze_* call that brought frames: its ingest launches, its hash launches, its groups of more than
+ * one clip, and the frames those grouped launches ingested -- {live clips, live clips, 0, 0} with option "ingest_group" off; all 0 after a call without
+ * frames and before the first call.  (A call refused or failed keeps the figures of the call before it.)
+ * "ingest_groups" int32[launches][4], host state, of that call, in launch order: the position of the launch's first clip, its clips, its frames and the
+ * kernel id it ran ("ingest_plan"'s last entry).  out_bytes must hold all rows.  "ingest_plan", "ingest_format", "ingest_rotate", "ingest_range" and
+ * "ingest_list" keep describing the LAST launch.
  * "cnn_tap": what option "cnn_tap" made the last avd_cnn_forward copy aside -- 1: uint16[n][232][232][4] bf16 bits; 2 + i and 55: the activation as
  * plain NHWC bf16 bits, uint16[n][H][W][C]; 56: float[n][2048].  out_bytes must be exactly the tap's size.  An error, never stale bytes, when the last
  * forward was not tapped, when none of its launches has that output (the 3x3 of a fused block while "cnn_fuse" != 0), or when the size differs.
