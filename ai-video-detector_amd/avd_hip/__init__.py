@@ -13,5 +13,6 @@ from ._lib import AvdError, Context, Pixels, RECORD_DTYPE, build, load  # noqa: 
 from ._lib import AVD_FMT_BGR24, AVD_FMT_BGRA32, AVD_FMT_I420, AVD_FMT_NV12, AVD_FMT_RGB24, AVD_FMT_RGBA32, AVD_FMT_RGBP  # noqa: F401
 from ._lib import AVD_FMT_I422, AVD_FMT_NV16, AVD_FMT_UYVY422, AVD_FMT_YUYV422  # noqa: F401
 from ._lib import AVD_FMT_I010, AVD_FMT_P010  # noqa: F401
+from ._lib import CV2_GAUSS_MULADD, CV2_RESIZE_LERP, CV2_THREE_SCALES  # noqa: F401
 from .analyzer import ClipsInFlight, ContextPool, FrameAnalyzer, StreamMux, analyze_frames, default_pool  # noqa: F401
 from .timeline import records_to_result, sample_step  # noqa: F401

@@ -73,6 +73,9 @@ AVD_FMT_RGB24, AVD_FMT_BGRA32, AVD_FMT_RGBA32, AVD_FMT_RGBP = 0x10, 0x11, 0x12, 
 AVD_FMT_YUYV422, AVD_FMT_UYVY422, AVD_FMT_I422, AVD_FMT_NV16 = 0x20, 0x21, 0x22, 0x23
 # 10-bit 4:2:0 in little-endian 16-bit words (include/avd.h): P010 = NV12's planes with the 10 bits in the high bits, I010 = I420's with them in the low bits
 AVD_FMT_P010, AVD_FMT_I010 = 0x30, 0x31
+# bits of option "cv2_model" (include/avd.h), the values of the oracle's own switches (the same numbers in its header): mul + add Gaussian taps, three pyramid
+# scales, the 32f linear resize as a + (b - a) * f
+CV2_GAUSS_MULADD, CV2_THREE_SCALES, CV2_RESIZE_LERP = 1, 8, 16
 # One record per layout (csrc/avd_ingest_clip.h has the library's row; tests/test_ingest_layouts.py holds the two against include/avd.h).
 #   px: bytes per pixel of plane 0; item: bytes per sample (2: planes of uint16 -- torch: uint16, or int16 read as the same bits; every stride
 #   handed on is in bytes); planes 1 and 2 have H // ydiv rows of W // xdiv samples
@@ -1133,6 +1136,12 @@ class Context:
         avd_debug_fetch "ingest_groups"."""
         launches = int(self.ingest_call()[0])
         return self.debug_fetch("ingest_groups", (launches, 4), np.int32) if launches else np.zeros((0, 4), np.int32)
+
+    # -- option "cv2_model" (include/avd.h): the library follows the oracle's model switches; set with set_option("cv2_model", mask) -----------
+    def fb_model(self) -> np.ndarray:
+        """int32[4] of the last call that ran the Farneback stage: the cv2_model it ran under, the scales it ran (4 or 3), the fb_fold_up mask
+        in effect, fb_fold_blur in effect; avd_debug_fetch "fb_model"."""
+        return self.debug_fetch("fb_model", (4,), np.int32)
 
     def set_profiling(self, on: bool):
         self._check(self._L.avd_set_profiling(self._h, int(bool(on))))

@@ -146,7 +146,7 @@ static int avd_ws_reserve_fb(avd_ctx* ctx, int n)
         for (int k = 0; k < AVD_FB_LEVELS; k++) {
             const size_t plane = (size_t)(AVD_SMALL >> k) * (AVD_SMALL >> k);
             // the 320-px scale of the pyramid exists only with fb_fold_blur off (the polynomial expansion forms that blur itself): 49 MB per 120 frames
-            if (k > 0 || !ctx->fb_fold_blur) { if (int e = ws.d_pyr[k].reserve(ctx, nf * plane)) return e; }
+            if (k > 0 || !fb_fold_blur_eff(ctx->fb_fold_blur, ctx->cv2_model)) { if (int e = ws.d_pyr[k].reserve(ctx, nf * plane)) return e; }
             else ws.d_pyr[0].reset();
             if (int e = ws.d_poly[k].reserve(ctx, nf * 5 * plane)) return e;
             if (int e = ws.d_flow[k].reserve(ctx, np * 2 * plane)) return e;
@@ -161,7 +161,7 @@ static int avd_ws_reserve_fb(avd_ctx* ctx, int n)
         ws.d_rlist.reset(); ws.d_vs.reset(); ws.d_vs0.reset(); ws.d_flow_il.reset();
         ws.fb_cap = want;
     }
-    if (!ctx->fb_fold_blur)
+    if (!fb_fold_blur_eff(ctx->fb_fold_blur, ctx->cv2_model))       // (a call is enqueued under the option's value of now: FlowCall::model)
         if (int e = ws.d_pyr[0].reserve(ctx, ((size_t)ws.fb_cap + 2) * AVD_NPIX)) return e;
     // the double intermediate of the two-kernel fallback (4 MB per pair): only when that path is selected
     if (ctx->fb_mode == 0 && ctx->fb_fused != 0xF) {
@@ -256,8 +256,11 @@ static int run_flow_chunks(avd_ctx* ctx, const uint8_t* d_small, int n, float* h
     // The plan of this call, handed to every launch of it.  Fast mode: the shape of the 160-px level, once for all chunks.  fb_wide160 = 2 chooses by what is
     // in flight: this call is being enqueued and not yet counted, so > 0 means SOMEBODY ELSE's kernels will share the chip with it.
     // The interleaved flow is formed only for a caller who fetches it.
-    const FlowCall call{ctx->fb_wide160 == 1 || (ctx->fb_wide160 == 2 && avd_calls_in_flight() - ctx->counted_in_flight > 0), h_flow_out != nullptr};
+    const FlowCall call{ctx->cv2_model, ctx->fb_wide160 == 1 || (ctx->fb_wide160 == 2 && avd_calls_in_flight() - ctx->counted_in_flight > 0), h_flow_out != nullptr};
     if (ctx->fb_mode == 1) ctx->fb_wide160_used = call.wide160;      // the record behind the read-only option
+    ctx->fb_model[0] = call.model; ctx->fb_model[1] = fb_coarsest(call.model) + 1;
+    ctx->fb_model[2] = fb_fold_up_eff(ctx->fb_fold_up, call.model); ctx->fb_model[3] = fb_fold_blur_eff(ctx->fb_fold_blur, call.model);
+    ctx->fb_model_valid = 1;
     int rc = 0;
     for (int p0 = 0; p0 < n - 1 && rc == 0; p0 += chunk) {
         const int np = std::min(chunk, n - 1 - p0);
@@ -486,6 +489,8 @@ static void audio_cut_set(avd_ctx* ctx, int v)
 static int audio_cut_read(const avd_ctx* ctx) { return ctx->audio_ncuts; }
 // "ingest_group": 0 a launch pair per clip, 1 one per group of clips that share a key (avd_ingest_group.h); durable
 static bool opt_ingest_group(int& v) { return v == 0 || v == 1; }
+// "cv2_model": any combination of the bits 1, 8 and 16 (the oracle's jitter switches 2 and 4 model nothing a library can follow); durable
+static bool opt_cv2_model(int& v) { return v >= 0 && (v & ~kCv2ModelMask) == 0; }
 static int env_any_base(const char* e) { return (int)std::strtol(e, nullptr, 0); }
 static int env_fb_mode(const char* e) { return (std::strcmp(e, "exact") == 0 || std::strcmp(e, "0") == 0) ? 0 : 1; }
 static const Option kOptions[] = {
@@ -512,6 +517,7 @@ static const Option kOptions[] = {
     {"audio_format", &avd_ctx::audio_format, true, opt_audio_format, nullptr, nullptr, "audio_format: 0 (float32 samples) or 1 (little-endian int16 PCM)"},
     {"audio_cut", nullptr, true, opt_any, nullptr, nullptr, nullptr, audio_cut_set, audio_cut_read, audio_cut_check},
     {"ingest_group", &avd_ctx::ingest_group, true, opt_ingest_group, nullptr, nullptr, "ingest_group: 0 (an ingest and a hash launch per clip) or 1 (one of each per group of clips that share a key)"},
+    {"cv2_model", &avd_ctx::cv2_model, true, opt_cv2_model, "AVD_CV2_MODEL", env_any_base, "cv2_model: a combination of 1 (GAUSS_MULADD), 8 (THREE_SCALES) and 16 (RESIZE_LERP), or 0 (the default model)"},
 };
 static const Option* find_option(avd_ctx* ctx, const char* name, bool to_write)
 {
@@ -1193,6 +1199,7 @@ static int64_t impl_debug_fetch(avd_ctx* ctx, const char* name, void* out, size_
             {"stream_call", ctx->stream_call, sizeof ctx->stream_call, true, nullptr, "int32[4]"},
             {"ingest_call", ctx->ingest_call, sizeof ctx->ingest_call, true, nullptr, "int32[4]"},
             {"ingest_groups", ctx->ingest_groups.data(), sizeof(int) * ctx->ingest_groups.size(), true, nullptr, "int32[launches][4]"},
+            {"fb_model", ctx->fb_model, sizeof ctx->fb_model, ctx->fb_model_valid != 0, "no call has run the Farneback stage on this context", "int32[4]"},
         };
         for (const auto& e : host_state) {
             if (std::strcmp(name, e.name) != 0) continue;
@@ -1243,7 +1250,7 @@ static int64_t impl_debug_fetch(avd_ctx* ctx, const char* name, void* out, size_
     else if (std::strcmp(name, "area") == 0) { src = ws.d_area; bytes = (size_t)n * 1024; }
     else if (std::strcmp(name, "small") == 0) { src = ws.d_small; bytes = (size_t)n * AVD_NPIX; }
     // the Farneback scratch holds ONE chunk (kFbChunk pairs): for longer clips these are the last chunk's buffers
-    else if ((k = level("pyr")) >= 0 && k == 0 && ctx->fb_fold_blur) { ctx->err = "pyr0 does not exist while fb_fold_blur is on (the polynomial expansion forms the 320-px blur itself)"; return AVD_ERR_ARG; }
+    else if ((k = level("pyr")) >= 0 && k == 0 && fb_fold_blur_eff(ctx->fb_fold_blur, ctx->cv2_model)) { ctx->err = "pyr0 does not exist while fb_fold_blur is on (the polynomial expansion forms the 320-px blur itself)"; return AVD_ERR_ARG; }
     else if ((k = level("pyr")) >= 0) { src = ws.d_pyr[k]; bytes = (size_t)std::min(n, ws.fb_cap + 1) * (AVD_NPIX >> (2 * k)) * 4; }
     else if ((k = level("poly")) >= 0) { src = ws.d_poly[k]; bytes = (size_t)std::min(n, ws.fb_cap + 1) * 5 * (AVD_NPIX >> (2 * k)) * 4; }
     else if ((k = level("flow")) >= 0) { src = ws.fb_holds.flow[k] ? ws.fb_holds.flow[k] : ws.d_flow[k]; bytes = (size_t)std::min(std::max(n - 1, 0), ws.fb_cap) * 2 * (AVD_NPIX >> (2 * k)) * 4; }

@@ -91,7 +91,18 @@ typedef float pyr_f2 __attribute__((ext_vector_type(2)));
 // diffword (K == 1 only, may be null): the tile also compares its source rows with the same rows of the NEXT frame and leaves "they differ" in
 // *diffword = pairdiff[f * TILES + t] -- the 20 tiles of the 160-px scale read every row of the frame (with overlap), so their OR says whether pair
 // (f, f + 1) is a pair of bit-identical frames (which the fast level kernels exempt from the border-sign criterion, avd_fbfast.hip)
-template <int K>
+// a * b + c of a Gaussian tap: the fused multiply-add of the default model, or (MA: bit 1 of option "cv2_model", GAUSS_MULADD) a rounded product
+// followed by a rounded sum -- the intrinsics, which the compiler never contracts
+template <bool MA>
+__device__ __forceinline__ float pyr_mac(float a, float b, float c)
+{
+    if constexpr (MA) return __fadd_rn(__fmul_rn(a, b), c);
+    else return __builtin_fmaf(a, b, c);
+}
+
+// MA: see pyr_mac.  LERP (bit 16 of "cv2_model", RESIZE_LERP): the decimation to 80 / 40 px -- the general INTER_LINEAR path with both weights 0.5 --
+// is a + (b - a) * 0.5 along x, then along y, instead of a * 0.5 + b * 0.5 (the 2 x 2 mean); the 160-px scale takes cv2's exact-2x area path and has no lerp
+template <int K, bool MA = false, bool LERP = false>
 __device__ __forceinline__ void pyramid_step(char* lds, const uint8_t* __restrict__ img, const float (&kw)[PyrGeo<K>::KS], float* __restrict__ out,
                                              int y_first, int rb, pyr_f4& kept, bool more, int* __restrict__ diffword)
 {
@@ -185,7 +196,7 @@ __device__ __forceinline__ void pyramid_step(char* lds, const uint8_t* __restric
                                     (float)(cwd >> 24), (float)(nw & 0xFFu)};
                 pyr_f4 o;
 #pragma unroll
-                for (int e = 0; e < 4; e++) o[e] = __builtin_fmaf(b[e + 1], kw[1], (b[e] + b[e + 2]) * kw[0]);
+                for (int e = 0; e < 4; e++) o[e] = pyr_mac<MA>(b[e + 1], kw[1], (b[e] + b[e + 2]) * kw[0]);
                 dst0[i][sb * (NC / 4)] = o;
             }
         }
@@ -223,8 +234,8 @@ __device__ __forceinline__ void pyramid_step(char* lds, const uint8_t* __restric
                 float v0 = 0.f, v1 = 0.f;
 #pragma unroll
                 for (int q = 0; q < KS; q++) {
-                    v0 = __builtin_fmaf(b[q], kw[q], v0);
-                    v1 = __builtin_fmaf(b[q + 1], kw[q], v1);
+                    v0 = pyr_mac<MA>(b[q], kw[q], v0);
+                    v1 = pyr_mac<MA>(b[q + 1], kw[q], v1);
                 }
                 dst0[i][sb * (NC / 2)] = pyr_f2{v0, v1};
             }
@@ -232,9 +243,9 @@ __device__ __forceinline__ void pyramid_step(char* lds, const uint8_t* __restric
     }
     __syncthreads();
     auto colf = [&](const float* c) {                    // c = the centre tap's row, this column
-        float sacc = __builtin_fmaf(c[0], kw[HALF], 0.f);
+        float sacc = pyr_mac<MA>(c[0], kw[HALF], 0.f);
 #pragma unroll
-        for (int k = 1; k <= HALF; k++) sacc = __builtin_fmaf(c[k * NC] + c[-k * NC], kw[HALF + k], sacc);
+        for (int k = 1; k <= HALF; k++) sacc = pyr_mac<MA>(c[k * NC] + c[-k * NC], kw[HALF + k], sacc);
         return sacc;
     };
     {
@@ -263,12 +274,16 @@ __device__ __forceinline__ void pyramid_step(char* lds, const uint8_t* __restric
                         for (int a = 0; a < 2; a++)
 #pragma unroll
                             for (int e = 0; e < 2; e++) {
-                                float sacc = __builtin_fmaf(w[e][HALF + a], kw[HALF], 0.f);
+                                float sacc = pyr_mac<MA>(w[e][HALF + a], kw[HALF], 0.f);
 #pragma unroll
-                                for (int k = 1; k <= HALF; k++) sacc = __builtin_fmaf(w[e][HALF + a + k] + w[e][HALF + a - k], kw[HALF + k], sacc);
+                                for (int k = 1; k <= HALF; k++) sacc = pyr_mac<MA>(w[e][HALF + a + k] + w[e][HALF + a - k], kw[HALF + k], sacc);
                                 p[a][e] = sacc;
                             }
-                        o = ((p[0][0] + p[0][1]) + (p[1][0] + p[1][1])) * 0.25f;
+                        if constexpr (LERP && K >= 2) {
+                            const float h0 = p[0][0] + (p[0][1] - p[0][0]) * 0.5f, h1 = p[1][0] + (p[1][1] - p[1][0]) * 0.5f;
+                            o = h0 + (h1 - h0) * 0.5f;
+                        } else
+                            o = ((p[0][0] + p[0][1]) + (p[1][0] + p[1][1])) * 0.25f;
                     }
                     out[y * WL + dx] = o;
                 }
@@ -281,7 +296,7 @@ __device__ __forceinline__ void pyramid_step(char* lds, const uint8_t* __restric
 }
 
 // blk = frame * TILES + band of this scale: the band's steps, top to bottom.  pairdiff: see pyramid_step
-template <int K>
+template <int K, bool MA = false, bool LERP = false>
 __device__ __forceinline__ void pyramid_body(char* lds, int blk, const uint8_t* __restrict__ small, const FbConsts* __restrict__ C,
                                              float* __restrict__ I, int n = 0, int* __restrict__ pairdiff = nullptr)
 {
@@ -298,28 +313,47 @@ __device__ __forceinline__ void pyramid_body(char* lds, int blk, const uint8_t* 
     const int y_first = (K == 0 ? dy0 : (dy0 << K) + G::OFF) - G::HALF;
     pyr_f4 kept = {0.f, 0.f, 0.f, 0.f};
     for (int step = 0; step < G::STEPS; step++)
-        pyramid_step<K>(lds, img, kw, out + step * G::TR * WL, y_first + step * G::NEW, step ? G::KEEP : 0, kept, step + 1 < G::STEPS, diffword);
+        pyramid_step<K, MA, LERP>(lds, img, kw, out + step * G::TR * WL, y_first + step * G::NEW, step ? G::KEEP : 0, kept, step + 1 < G::STEPS, diffword);
 }
 
 
 // the four scales of every frame in ONE launch (coarsest first: its workgroups do the most work): the small scales
 // alone cannot fill the chip (600 workgroups at 40 px for a 120-frame clip) and used to run one after the other
 // It also clears the per-pair ill-posedness flags of the chunk (the fast level kernels, which come later on the stream, set them).
+template <bool MA, bool LERP>
+__device__ __forceinline__ void pyramid_all(char* lds, const uint8_t* __restrict__ small, int n, const FbConsts* __restrict__ C,
+                                            float* __restrict__ I0, float* __restrict__ I1, float* __restrict__ I2,
+                                            float* __restrict__ I3, int* __restrict__ flags, int* __restrict__ pairdiff)
+{
+    static_assert(PyrGeo<1>::TILES == kPairDiffTiles, "avd_fbfast.hip reads one word per 160-px tile");
+    if (flags && (int)(blockIdx.x * 256 + threadIdx.x) < n - 1) flags[blockIdx.x * 256 + threadIdx.x] = 0;
+    const int n3 = n * PyrGeo<3>::TILES, n2 = n * PyrGeo<2>::TILES, n1 = n * PyrGeo<1>::TILES;
+    int b = blockIdx.x;
+    if (b < n3) { pyramid_body<3, MA, LERP>(lds, b, small, C, I3); return; }
+    b -= n3;
+    if (b < n2) { pyramid_body<2, MA, LERP>(lds, b, small, C, I2); return; }
+    b -= n2;
+    if (b < n1) { pyramid_body<1, MA, LERP>(lds, b, small, C, I1, n, pairdiff); return; }
+    if (I0) pyramid_body<0, MA, LERP>(lds, b - n1, small, C, I0);     // null: the polynomial expansion forms the 320-px scale's 3 x 3 blur itself (the grid ends before)
+}
+
 __global__ __launch_bounds__(256) void k_pyramid_all(const uint8_t* __restrict__ small, int n, const FbConsts* __restrict__ C,
                                                     float* __restrict__ I0, float* __restrict__ I1, float* __restrict__ I2,
                                                     float* __restrict__ I3, int* __restrict__ flags, int* __restrict__ pairdiff)
 {
-    static_assert(PyrGeo<1>::TILES == kPairDiffTiles, "avd_fbfast.hip reads one word per 160-px tile");
     __shared__ __align__(16) char lds[kPyrLds];
-    if (flags && (int)(blockIdx.x * 256 + threadIdx.x) < n - 1) flags[blockIdx.x * 256 + threadIdx.x] = 0;
-    const int n3 = n * PyrGeo<3>::TILES, n2 = n * PyrGeo<2>::TILES, n1 = n * PyrGeo<1>::TILES;
-    int b = blockIdx.x;
-    if (b < n3) { pyramid_body<3>(lds, b, small, C, I3); return; }
-    b -= n3;
-    if (b < n2) { pyramid_body<2>(lds, b, small, C, I2); return; }
-    b -= n2;
-    if (b < n1) { pyramid_body<1>(lds, b, small, C, I1, n, pairdiff); return; }
-    if (I0) pyramid_body<0>(lds, b - n1, small, C, I0);     // null: the polynomial expansion forms the 320-px scale's 3 x 3 blur itself (the grid ends before)
+    pyramid_all<false, false>(lds, small, n, C, I0, I1, I2, I3, flags, pairdiff);
+}
+
+// the same launch under a non-zero "cv2_model" (bits 1 and 16: MA, LERP); with bit 8 (three scales) the 40-px tiles still run -- their
+// workgroups are the first of the grid, and nobody reads what they write
+template <bool MA, bool LERP>
+__global__ __launch_bounds__(256) void k_pyramid_model(const uint8_t* __restrict__ small, int n, const FbConsts* __restrict__ C,
+                                                      float* __restrict__ I0, float* __restrict__ I1, float* __restrict__ I2,
+                                                      float* __restrict__ I3, int* __restrict__ flags, int* __restrict__ pairdiff)
+{
+    __shared__ __align__(16) char lds[kPyrLds];
+    pyramid_all<MA, LERP>(lds, small, n, C, I0, I1, I2, I3, flags, pairdiff);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -552,7 +586,8 @@ __global__ __launch_bounds__(320) void k_polyexp_all(PolyPtrs P, int n, const Fb
 // horizontally the weights snap to the edge pixel (f = 0) when s falls outside [0, pw-1),
 // vertically the rows are clipped and the weights kept.  A lane produces 4 consecutive outputs.
 // ---------------------------------------------------------------------------------------
-template <int W>
+// LERP (bit 16 of option "cv2_model"): a + (b - a) * f in both directions instead of a * (1 - f) + b * f; a copied edge value stays a copy
+template <int W, bool LERP = false>
 __global__ __launch_bounds__(256) void k_flow_up(const float* __restrict__ prev, float* __restrict__ flow, int npairs, const int* __restrict__ plist)
 {
     constexpr int H = W, PW = W / 2, PH = H / 2, Q = W / 4;
@@ -583,8 +618,10 @@ __global__ __launch_bounds__(256) void k_flow_up(const float* __restrict__ prev,
         const float a0 = 1.f - fx, a1 = fx;
         float d0, d1;
         if (edge) { d0 = r0[sx] * 1.f; d1 = r1[sx] * 1.f; }
+        else if constexpr (LERP) { d0 = r0[sx] + (r0[x1] - r0[sx]) * a1; d1 = r1[sx] + (r1[x1] - r1[sx]) * a1; }
         else { d0 = r0[sx] * a0 + r0[x1] * a1; d1 = r1[sx] * a0 + r1[x1] * a1; }
-        o[i] = (d0 * b0 + d1 * b1) * 2.f;
+        if constexpr (LERP) o[i] = (d0 + (d1 - d0) * b1) * 2.f;
+        else o[i] = (d0 * b0 + d1 * b1) * 2.f;
     }
     *reinterpret_cast<float4*>(flow + ((int64_t)pc * H + dy) * W + q * 4) = make_float4(o[0], o[1], o[2], o[3]);
 }
@@ -701,17 +738,26 @@ constexpr int kLevelId[AVD_FB_LEVELS] = {AVD_K_LEVEL320, AVD_K_LEVEL160, AVD_K_L
 constexpr int kFlowUpId[AVD_FB_LEVELS - 1] = {AVD_K_FLOWUP320, AVD_K_FLOWUP160, AVD_K_FLOWUP80};
 
 // Gaussian pyramid + polynomial expansion of n frames at all four scales: two launches
-void pyramid_and_polyexp(avd_ctx* ctx, const uint8_t* d_small, int n)
+void pyramid_and_polyexp(avd_ctx* ctx, const FlowCall& call, const uint8_t* d_small, int n)
 {
     Workspace& ws = ctx->ws;
     const FbConsts* C = ctx->d_fbc;
     // ctx->fb_fold_blur (default 1): the 320-px scale's 3 x 3 blur is formed inside the polynomial expansion; the pyramid kernel then has no
-    // 320-px tiles and d_pyr[0] is not written (avd_debug_copy "pyr0" is meaningful with the option off only)
-    const bool fold = ctx->fb_fold_blur != 0;
+    // 320-px tiles and d_pyr[0] is not written (avd_debug_copy "pyr0" is meaningful with the option off only).  Under bit 1 of "cv2_model" the
+    // blur is never folded (fb_fold_blur_eff): the mul + add taps exist in the pyramid kernel only
+    const bool fold = fb_fold_blur_eff(ctx->fb_fold_blur, call.model) != 0;
     const int wgs = n * ((fold ? 0 : PyrGeo<0>::TILES) + PyrGeo<1>::TILES + PyrGeo<2>::TILES + PyrGeo<3>::TILES);
     kmark(ctx, AVD_K_PYRAMID);
-    hipLaunchKernelGGL(k_pyramid_all, dim3(wgs), dim3(256), 0, ctx->stream, d_small, n, C, fold ? nullptr : ws.d_pyr[0].p, ws.d_pyr[1].p, ws.d_pyr[2].p,
-                       ws.d_pyr[3].p, ws.d_fbflags.p, ws.d_pairdiff.p);
+    auto pyramid = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(wgs), dim3(256), 0, ctx->stream, d_small, n, C, fold ? nullptr : ws.d_pyr[0].p, ws.d_pyr[1].p, ws.d_pyr[2].p,
+                           ws.d_pyr[3].p, ws.d_fbflags.p, ws.d_pairdiff.p);
+    };
+    switch (call.model & (kCv2GaussMuladd | kCv2ResizeLerp)) {
+    case 0: pyramid(k_pyramid_all); break;                 // the default model: the launch of always
+    case kCv2GaussMuladd: pyramid(k_pyramid_model<true, false>); break;
+    case kCv2ResizeLerp: pyramid(k_pyramid_model<false, true>); break;
+    default: pyramid(k_pyramid_model<true, true>); break;
+    }
     PolyPtrs P;
     P.small = fold ? d_small : nullptr;
     int grid = 0;
@@ -724,11 +770,15 @@ void pyramid_and_polyexp(avd_ctx* ctx, const uint8_t* d_small, int n)
 }
 
 // initial flow of level k = 0 .. 2 from the coarser level's final flow (no launch for any other k); plist (may be null): for the pairs plist[0 .. np) only
-void flow_up_level(hipStream_t stream, int k, const float* prev, float* flow, int np, const int* plist)
+// lerp: bit 16 of the call's "cv2_model"
+void flow_up_level(hipStream_t stream, int k, const float* prev, float* flow, int np, const int* plist, bool lerp)
 {
     fb_dispatch_width(S >> k, [&](auto wc) {
         constexpr int W = decltype(wc)::value;
-        if constexpr (W > S / 8) launch1d(k_flow_up<W>, (int64_t)np * 2 * W * (W / 4), 256, stream, prev, flow, np, plist);
+        if constexpr (W > S / 8) {
+            if (lerp) launch1d(k_flow_up<W, true>, (int64_t)np * 2 * W * (W / 4), 256, stream, prev, flow, np, plist);
+            else launch1d(k_flow_up<W>, (int64_t)np * 2 * W * (W / 4), 256, stream, prev, flow, np, plist);
+        }
     });
 }
 
@@ -736,17 +786,20 @@ void flow_up_level(hipStream_t stream, int k, const float* prev, float* flow, in
 // (avd_fbfused.hip) where bit k of fused_mask is set, else the two-kernel path (avd_fbtwo.hip) through `scratch`.  plist == null: exact mode, all np
 // pairs of the chunk; plist != null: the re-run of the flagged pairs plist[0 .. np).  The two differ in four things, (1) .. (4), and in nothing else.
 // chunk: exact mode fills in where it leaves each level's flow; the re-run reads where the fast kernels left the 320-px one.
-int exact_levels(avd_ctx* ctx, int np, int fused_mask, FbTwoScratch scratch, const int* plist, FbChunk& chunk)
+// call.model ("cv2_model"): under bit 8 the levels are 2 -> 0 -- the 80-px level is the coarsest and starts from zero flow; bit 16 selects k_flow_up's lerp form.
+int exact_levels(avd_ctx* ctx, const FlowCall& call, int np, int fused_mask, FbTwoScratch scratch, const int* plist, FbChunk& chunk)
 {
+    const int top = fb_coarsest(call.model);
+    const bool lerp = (call.model & kCv2ResizeLerp) != 0;
     Workspace& ws = ctx->ws;
     const hipStream_t stream = ctx->stream;
     const bool rerun = plist != nullptr;
     // (1) level 0 works in its first flow buffer; the re-run in the one the fast kernels left their final flow in (the caller may read it back)
     float* const flow0 = rerun ? const_cast<float*>(chunk.flow[0]) : ws.d_flow[0].p;
     if (rerun) kmark(ctx, AVD_K_RERUN);                  // (3) avd_kernel_ms: exact mode records the per-level regions, the re-run is one region
-    for (int k = AVD_FB_LEVELS - 1; k >= 0; k--) {
+    for (int k = top; k >= 0; k--) {
         const int w = S >> k;
-        const bool coarsest = k == AVD_FB_LEVELS - 1, fused = (fused_mask >> k) & 1;
+        const bool coarsest = k == top, fused = (fused_mask >> k) & 1;
         float* flow = k == 0 ? flow0 : ws.d_flow[k].p;
         if (coarsest) {
             // (2) zero initial flow: the fused kernel is told so; the two-kernel path reads a buffer that only exact mode may clear
@@ -754,7 +807,7 @@ int exact_levels(avd_ctx* ctx, int np, int fused_mask, FbTwoScratch scratch, con
             if (!fused) HIP_TRY(ctx, hipMemsetAsync(flow, 0, sizeof(float) * 2 * w * w * np, stream));
         } else {
             if (!rerun) kmark(ctx, kFlowUpId[k]);
-            flow_up_level(stream, k, ws.d_flow[k + 1], flow, np, plist);
+            flow_up_level(stream, k, ws.d_flow[k + 1], flow, np, plist, lerp);
         }
         if (!rerun) { chunk.flow[k] = flow; kmark(ctx, kLevelId[k]); }
         const bool marks = !rerun && k == 0;             // (4) the events of avd_stage_ms 4 / 5 belong to the 320-px level of exact mode
@@ -778,22 +831,33 @@ int fast_levels(avd_ctx* ctx, const FlowCall& call, int np, FbChunk& chunk)
 {
     Workspace& ws = ctx->ws;
     const hipStream_t stream = ctx->stream;
-    const int fold = ctx->fb_fold_up;
+    // under bit 16 of the call's "cv2_model" no launch resizes a flow itself (fb_fold_up_eff): the lerp form exists in k_flow_up only
+    const int fold = fb_fold_up_eff(ctx->fb_fold_up, call.model), top = fb_coarsest(call.model);
+    const bool fold160 = fb_fold_up160_eff(ctx->fb_fold_up160, call.model) != 0, lerp = (call.model & kCv2ResizeLerp) != 0;
     int* flags = ctx->fb_rerun ? ws.d_fbflags.p : nullptr;
     const int* pairdiff = ctx->fb_rerun ? ws.d_pairdiff.p : nullptr;
-    for (int k = AVD_FB_LEVELS - 1; k >= 0; k--) {
+    for (int k = top; k >= 0; k--) {
         const int w = S >> k;
-        const bool coarsest = k == AVD_FB_LEVELS - 1, three = (k == 2 || k == 3) && (fold & 4);
+        const bool coarsest = k == top, three = (k == 2 || k == 3) && (fold & 4);
         float *a = ws.d_flow[k], *b = ws.d_flow2[k];
         // the initial flow: zero at the coarsest level, else the coarser level's final flow, resized by the first launch itself or by k_flow_up into a
         const float* prev = coarsest ? nullptr : chunk.flow[k + 1];
         // (160 px: the chain wave resizes in the one-strip shape only, which the call has chosen or not before it got here)
-        const bool chain = (k == 0 && (fold & 1)) || (k == 1 && ctx->fb_fold_up160 && call.wide160);
-        const FbFlowFrom from = coarsest ? FbFlowFrom::zero : chain ? FbFlowFrom::chain
+        const bool chain = (k == 0 && (fold & 1)) || (k == 1 && fold160 && call.wide160);
+        // the kernel's zero form is compiled for the 40-px level only: an 80-px coarsest level (bit 8) reads a cleared buffer, the same arithmetic.
+        // That form also exempts its iteration from the border-sign criterion (a zero initial flow is structural in cv2 too, and "inside" in both);
+        // without the exemption nearly every pair is flagged there.  The cleared level gets it through the kernel's other exemption, the one for
+        // bit-identical frames: its first iteration runs as a launch of its own (fb_fold_up_eff drops bit 4) and is handed pair-identity words that
+        // are all zero -- the cleared flow buffer itself, which that launch only reads (2 w w >= kPairDiffTiles words per pair).  The solver's
+        // criterion does not read those words and stays.
+        const bool cleared = coarsest && k != AVD_FB_LEVELS - 1;
+        static_assert(2 * (S >> (AVD_FB_LEVELS - 2)) * (S >> (AVD_FB_LEVELS - 2)) >= kPairDiffTiles, "the cleared flow serves as the identity words");
+        if (cleared) HIP_TRY(ctx, hipMemsetAsync(a, 0, sizeof(float) * 2 * w * w * np, stream));
+        const FbFlowFrom from = cleared ? FbFlowFrom::level : coarsest ? FbFlowFrom::zero : chain ? FbFlowFrom::chain
                                 : ((k == 1 || k == 2) && (fold & 2)) ? FbFlowFrom::prologue : FbFlowFrom::level;
-        if (from == FbFlowFrom::level) {
+        if (from == FbFlowFrom::level && !coarsest) {
             kmark(ctx, kFlowUpId[k]);
-            flow_up_level(stream, k, prev, a, np, nullptr);
+            flow_up_level(stream, k, prev, a, np, nullptr, lerp);
         }
         const bool from_prev = from == FbFlowFrom::chain || from == FbFlowFrom::prologue;
         kmark(ctx, kLevelId[k]);
@@ -805,7 +869,8 @@ int fast_levels(avd_ctx* ctx, const FlowCall& call, int np, FbChunk& chunk)
         } else {
             for (int it = 0; it < 3; it++) {
                 float* mag = (k == 0 && it == 2) ? ws.d_mag.p : nullptr;
-                const FbFastLaunch L{call.wide160, 1, it == 0 ? from : FbFlowFrom::level, it == 0 && from_prev ? prev : a, b, a, mag, flags, pairdiff};
+                const int* identity = cleared && it == 0 && pairdiff ? reinterpret_cast<const int*>(a) : pairdiff;
+                const FbFastLaunch L{call.wide160, 1, it == 0 ? from : FbFlowFrom::level, it == 0 && from_prev ? prev : a, b, a, mag, flags, identity};
                 if (int e = launch_fb_fast(ctx, stream, w, ws.d_poly[k], L, np)) return e;
                 float* t = a; a = b; b = t;
             }
@@ -839,8 +904,8 @@ int launch_farneback(avd_ctx* ctx, const FlowCall& call, const uint8_t* d_small,
     const bool fast = ctx->fb_mode == 1;
     FbChunk& chunk = ws.fb_holds;                      // level by level: a launch sequence that fails half way has overwritten those levels
     chunk.mag_valid = fast;
-    pyramid_and_polyexp(ctx, d_small, n);
-    if (int e = fast ? fast_levels(ctx, call, n - 1, chunk) : exact_levels(ctx, n - 1, ctx->fb_fused, {ws.d_vs, ws.d_vs0}, nullptr, chunk)) return e;
+    pyramid_and_polyexp(ctx, call, d_small, n);
+    if (int e = fast ? fast_levels(ctx, call, n - 1, chunk) : exact_levels(ctx, call, n - 1, ctx->fb_fused, {ws.d_vs, ws.d_vs0}, nullptr, chunk)) return e;
     HIP_TRY(ctx, hipGetLastError());
     *left = chunk;
     return 0;
@@ -859,14 +924,15 @@ int launch_farneback_rerun(avd_ctx* ctx, const FlowCall& call, const int* h_list
     Workspace& ws = ctx->ws;
     if (m > ws.fb_cap) { ctx->err = "re-run list longer than the chunk"; return AVD_ERR_ARG; }
     if (int e = ws.d_rlist.reserve(ctx, (size_t)ws.fb_cap)) return e;
-    const int fused_mask = m <= kRerunTwoKernelMax ? (ctx->fb_rerun_fused & 0xF) : 0xF;
+    // the coarsest level runs the fused kernel, which needs no cleared flow: bit 3 of the option is always set, and under bit 8 of "cv2_model" bit 2 is taken as set
+    const int fused_mask = m <= kRerunTwoKernelMax ? ((ctx->fb_rerun_fused & 0xF) | (1 << fb_coarsest(call.model))) : 0xF;
     if (fused_mask != 0xF) {
         const FbTwoScratchSize sz = fb_two_scratch_size(kRerunTwoKernelMax);
         if (int e = ws.d_vs0_rerun.reserve(ctx, sz.vs0)) return e;
         if (int e = ws.d_vs_rerun.reserve(ctx, sz.vs)) return e;
     }
     HIP_TRY(ctx, hipMemcpyAsync(ws.d_rlist, h_list, sizeof(int) * m, hipMemcpyHostToDevice, ctx->stream));
-    if (int e = exact_levels(ctx, m, fused_mask, {ws.d_vs_rerun, ws.d_vs0_rerun}, ws.d_rlist, ws.fb_holds)) return e;   // the scratch is indexed by position in the list
+    if (int e = exact_levels(ctx, call, m, fused_mask, {ws.d_vs_rerun, ws.d_vs0_rerun}, ws.d_rlist, ws.fb_holds)) return e;   // the scratch is indexed by position in the list
     flow_tail(ctx, call, ws.fb_holds.flow[0], true, m, ws.d_rlist, np_chunk);
     HIP_TRY(ctx, hipGetLastError());
     return 0;

@@ -173,9 +173,20 @@ struct ClipSlot {
 
 // What one Farneback call (all its chunks, and the deferred exact re-run of its last one) runs as: decided once, where the call is enqueued (run_flow_chunks)
 struct FlowCall {
+    int model;                         // option "cv2_model" as it stood when the call was enqueued: every chunk and the deferred exact re-run follow it
     bool wide160;                      // fast mode: the 160-px level as one three-block strip per pair (see avd_ctx::fb_wide160)
     bool dense_flow;                   // the caller fetches the interleaved flow (ws.d_flow_il, reserved): the chunks' flow_tail interleaves it
 };
+// Option "cv2_model": the oracle's model switches (its header; the same bit values) that the library follows.  What each bit changes in the
+// launches is decided by the helpers below and nowhere else.
+constexpr int kCv2GaussMuladd = 1, kCv2ThreeScales = 8, kCv2ResizeLerp = 16, kCv2ModelMask = kCv2GaussMuladd | kCv2ThreeScales | kCv2ResizeLerp;
+inline int fb_coarsest(int model) { return model & kCv2ThreeScales ? AVD_FB_LEVELS - 2 : AVD_FB_LEVELS - 1; }        // pyramid index of the first level run
+// the fold options IN EFFECT (they have no effect on results, so a model whose arithmetic exists in the unfolded kernels only runs those):
+// bit 1 -> the 320-px blur comes from the pyramid kernel; bit 16 -> every initial flow comes from k_flow_up (fb_fold_up loses bits 1 and 2);
+// bit 8 -> the 80-px level, now the coarsest, runs its iterations one per launch (fb_fold_up loses bit 4: fast_levels says why)
+inline int fb_fold_blur_eff(int fold_blur, int model) { return model & kCv2GaussMuladd ? 0 : fold_blur; }
+inline int fb_fold_up_eff(int fold_up, int model) { return fold_up & (model & kCv2ResizeLerp ? 4 : 7) & (model & kCv2ThreeScales ? 3 : 7); }
+inline int fb_fold_up160_eff(int fold_up160, int model) { return model & kCv2ResizeLerp ? 0 : fold_up160; }
 // What launch_farneback left in the Farneback scratch
 struct FbChunk {
     const float* flow[AVD_FB_LEVELS] = {};   // the final flow of each level (d_flow or d_flow2)
@@ -310,6 +321,9 @@ struct avd_ctx {
     int comm_rank = 0, comm_world = 1;
     DevBuf<char> d_comm;             // device staging of the record exchange
     int cnn_tiles = 0;              // convolution tiling of the CNN extension: 0 = heuristic, 1 = 256-pixel tiles, 2 = 128 x 128 wherever possible
+    int cv2_model = 0;              // option "cv2_model" (AVD_CV2_MODEL): mask of kCv2GaussMuladd / kCv2ThreeScales / kCv2ResizeLerp, 0 = the default model; a call follows the value it was enqueued under (FlowCall::model)
+    int fb_model[4] = {};           // debug buffer "fb_model", of the last call that ran the Farneback stage: model, scales run (4 or 3), fb_fold_up in effect, fb_fold_blur in effect
+    int fb_model_valid = 0;         // 0 until the first such call
     int fb_fold_blur = 1;           // the 320-px scale's 3 x 3 pyramid blur formed inside the polynomial expansion (no effect on results); AVD_FB_FOLD_BLUR / avd_set_option
     int fb_wide160 = 2;             // fast mode: the 160-px level as one three-block strip per pair (1: fewer CU-microseconds, throughput) or as two strips (0: shorter launches, latency);
                                     // 2 (default) = by what is in flight when the call is enqueued: one strip if another context of the process holds an undrained call, two if this clip is alone; AVD_FB_WIDE160 / avd_set_option

@@ -585,6 +585,30 @@ int avd_set_profiling(avd_ctx* ctx, int enable);
  * existed.  The records, and the debug buffers "small", "area", are bit for bit those of option 0.  avd_preprocess_* takes one clip and ignores the option.
  * What a call did is in avd_debug_fetch "ingest_call" and "ingest_groups"; with profiling on there is one AVD_K_PREPROCESS and one AVD_K_HASH region per
  * launch, so a grouped call has fewer.  Experimental while the default is 0.
+ * "cv2_model" (default 0, environment AVD_CV2_MODEL read with strtol base 0; durable, survives avd_release_workspace): the library follows the CPU
+ * oracle's model switches (oracle/avd_oracle.h, avdo_set_model) -- the implementation choices of the OpenCV wheel that only golden vectors of a real
+ * cv2 settle.  The value is a mask with the oracle's own bit values, so one number means the same on both sides:
+ *    1  GAUSS_MULADD   the taps of every 32f Gaussian filter of the Farneback stage (pyramid blurs of 3 / 9 / 19 taps) are a rounded product followed
+ *                      by a rounded sum, in the order of the default model's fused multiply-add chains (a host without FMA dispatch);
+ *    8  THREE_SCALES   scales 80 / 160 / 320 only: the 80-px level is the coarsest and starts from zero flow;
+ *   16  RESIZE_LERP    every 32f INTER_LINEAR resize inside Farneback is a + (b - a) * f instead of a * (1 - f) + b * f: the decimations to 80 and
+ *                      40 px and the x2 up-sampling of the flow.  The exact-2x area path to 160 px has no lerp and stays.
+ * Any combination of 1, 8 and 16 is accepted.  Every other value -- bits 2 and 4 (the oracle's +-1 ulp jitter switches, which model nothing a library
+ * can follow), bits from 32 up, negative values -- is refused with AVD_ERR_ARG and a message that begins "cv2_model:", and the old value stays; an
+ * environment value that would be refused leaves 0.  With 0 every call enqueues exactly what it did before the option existed.  The option applies to
+ * the Farneback stage of every entry that has one: all avd_analyze_* forms (blocking and asynchronous, batches, pictures, lists, under "stream_slot" /
+ * "stream_map" / "ingest_group"), avd_farneback_pairs, both "fb_mode"s, and the exact re-run of flagged pairs -- the deferred one of avd_synchronize and
+ * the one "tail_help" runs from another thread included: a call follows the model it was ENQUEUED under.  A stream slot holds model-independent data
+ * only, so the model may change between the calls of one stream.  The stated guarantee is unchanged with "the oracle" read as "the oracle under the
+ * same flags" (oracle.model(mask)): "fb_mode" 0 bit-identical everywhere; "fb_mode" 1 flagged pairs bit for bit, the others within rel 1e-6 on
+ * flow_mean / flow_var and 1e-5 px on the dense flow.  The fold options have no effect on results, so under a non-zero model the launcher runs the
+ * unfolded forms where only those carry the model's arithmetic: under bit 1 "fb_fold_blur" is taken as 0 (avd_debug_fetch "pyr0" exists), under bit 16
+ * bits 1 and 2 of "fb_fold_up" and "fb_fold_up160" are taken as 0 (every initial flow comes from k_flow_up), under bit 8 bit 4 of "fb_fold_up" is taken
+ * as 0 (the 80-px level's first iteration is a launch of its own, exempt from the border-sign criterion as the 40-px level's is); avd_get_option keeps returning what the
+ * caller set, avd_debug_fetch "fb_model" what was in effect.  Under bit 8: AVD_K_LEVEL40 and AVD_K_FLOWUP80 are exactly 0 (neither is launched; the
+ * pyramid and polynomial-expansion launches still form the unused 40-px scale), the remaining regions still tile stage 2, bits 3 and 7 of
+ * avd_frame_record.reserved are never set, and in the few-pairs re-run bit 2 of "fb_rerun_fused" is taken as set (the coarsest level runs the fused
+ * kernel).  The fast mode's flag thresholds were fuzzed at full size under the default model only; see DESIGN.md section 2 for what was repeated.
  * "audio_format" (0 float32, 1 int16 PCM; durable) and "audio_cut" (the track boundaries of the next avd_audio_features call; one-shot) belong to the
  * audio analyzer and are described at avd_audio_features.
  * avd_get_option returns the value an option has now (environment defaults included) and the read-only "rerun_pairs" and "stream_frames". */
@@ -660,6 +684,8 @@ int avd_kernel_ms(avd_ctx* ctx, int kernel_id, float* ms);
  * "stream_call" int32[4], host state, of the last avd_analyze_* call that brought frames: the clips that continued a FILLED slot, the launches that restored
  * slot frames (0 or 1), the launches that saved them (0 or 1), and the frames in the per-frame buffers, restored frames included; all 0 after a call
  * without frames.  (A call refused or failed keeps the figures of the call before it.)
+ * "fb_model" int32[4], host state, of the last call that ran the Farneback stage (at least one pair): the "cv2_model" it ran under, the scales it ran
+ * (4, or 3 under bit 8), the "fb_fold_up" mask in effect and "fb_fold_blur" in effect; an error before any such call.
  * Returns the number of bytes copied (>=0) or a negative status. */
 int64_t avd_debug_fetch(avd_ctx* ctx, const char* name, void* out, size_t out_bytes);
 

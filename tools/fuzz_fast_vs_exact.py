@@ -10,6 +10,8 @@ and |delta flow_mean| <= 1e-6 * max(1, |m|).  tests/test_gpu_holdout.py is the f
           between them (scene cuts between unrelated content) are checked as well and reported as the row cut_between
 --seed0   seed of pair i of family j is seed0 + j * 10 ** 8 + i; at least 10 ** 7, the tests' seeds lie below
 --out     directory for the table (holdout_fuzz.txt) and every violator's two frames (.npz, with family, seed and the figures)
+--cv2-model  option "cv2_model" of BOTH contexts (a mask of 1, 8 and 16; default 0): the referee is fb_mode = exact under the same mask, and
+          violators are confirmed against the CPU oracle under oracle.model(mask)
 
 Violators, and only they, are confirmed against the CPU oracle (is the referee right about them?).  Nothing is retried: the first error of the
 library or the HIP runtime ends the run with what the table holds so far and a non-zero exit status.
@@ -38,6 +40,7 @@ def main():
     ap.add_argument("--pairs", type=int, default=10_000)
     ap.add_argument("--seed0", type=int, default=1_000_000_000)
     ap.add_argument("--out", default=os.path.join(ROOT, "out", "fuzz"))
+    ap.add_argument("--cv2-model", type=lambda t: int(t, 0), default=0, help="option cv2_model of both contexts (mask of 1, 8, 16)")
     ap.add_argument("--commit", default=None, help="the commit the tree is at, where the run has no git to ask")
     a = ap.parse_args()
     if a.seed0 < H.FUZZ_SEED_MIN:
@@ -54,6 +57,9 @@ def main():
     oracle = None
     with avd_hip.Context(0) as default, avd_hip.Context(0) as exact:
         exact.set_option("fb_mode", 0)
+        if a.cv2_model:
+            default.set_option("cv2_model", a.cv2_model)
+            exact.set_option("cv2_model", a.cv2_model)
         try:
             for c in range(chunks):
                 for j, (name, make) in enumerate(fam.items()):
@@ -79,7 +85,8 @@ def main():
                         if oracle is None:
                             from oracle import oracle as oracle
                             oracle.lib()
-                        om, ov = oracle.flow_stats(oracle.farneback(prev, nxt))          # the CPU oracle's word on the violator
+                        with oracle.model(a.cv2_model):
+                            om, ov = oracle.flow_stats(oracle.farneback(prev, nxt))      # the CPU oracle's word on the violator
                         v = dict(family=name, row=row, seed=seeds[p // 2], seed_next=seeds[(p + 1) // 2], pair_in_chunk=p, kind=kind, got=str(got), want=str(want),
                                  reserved=int(r["reserved"][p]), default=(float(r["fm"][p]), float(r["fv"][p])), exact=(float(r["xm"][p]), float(r["xv"][p])),
                                  oracle=(float(om), float(ov)), exact_is_oracle=bool(r["xm"][p] == om and r["xv"][p] == ov))
@@ -101,7 +108,7 @@ def main():
             commit = "unknown"
     total = {k: (max if k == "max_dmean" else sum)(x[k] for x in rows.values()) for k in next(iter(rows.values()))}
     lines = ["default Farneback mode (fast level kernels + exact re-run of flagged pairs) against fb_mode = exact, hold-out families of tests/holdout_families.py",
-             f"tools/fuzz_fast_vs_exact.py --pairs {a.pairs} --seed0 {a.seed0}: {chunks} chunks of {CHUNK} pairs per family; seed of pair i of family j = seed0 + j * 10 ** 8 + i",
+             f"tools/fuzz_fast_vs_exact.py --pairs {a.pairs} --seed0 {a.seed0} --cv2-model {a.cv2_model}: {chunks} chunks of {CHUNK} pairs per family; seed of pair i of family j = seed0 + j * 10 ** 8 + i",
              f"commit {commit}; bank {H.BANK_SHA256[:16]}; {time.time() - t0:.0f} s" + (f"; ENDED BY AN ERROR: {error}" if error else ""),
              "flagged = re-run exactly (solver criterion: flag word & 0x0F, border-sign criterion: & 0xF0); differ = flow_mean or flow_var not bit-identical to exact;",
              "violator = outside the guarantee (flagged: bit-identical; unflagged: rel 1e-6 / abs 1e-7 on both statistics, |delta flow_mean| <= 1e-6 * max(1, |m|))",
