@@ -3,7 +3,11 @@
 ``analyze(path, meta)`` keeps the reference's contract (audio.py:29-122): it never raises -- any failure (no ffmpeg, an
 unreadable file, a HIP error) becomes ``{"scores": {}, "flags_audio": {"error": str(e)}, "timeline": [0.5] * tlen}``
 exactly as the reference's own ``except`` does (audio.py:111-118).  The per-window spectral features run in the HIP
-kernels behind the C-ABI (``avd_audio_features``); there is no CPU fallback for them."""
+kernels behind the C-ABI (``avd_audio_features``); there is no CPU fallback for them.
+
+``AVD_AUDIO_RESAMPLE=1``: a PCM ``.wav`` at one of the converter's rates (``avd_hip.audio.RESAMPLE_RATES``) is read as it is, every channel, and
+what the reference's ffmpeg line does (downmix, 16 kHz, 16 bit) happens on the device (``analyze_decoded``); no ffmpeg runs.  Any other file takes
+the usual way.  Unset, nothing changes."""
 from __future__ import annotations
 
 import os
@@ -12,8 +16,22 @@ from avd_hip import analyzer as _analyzer
 from avd_hip import audio as _audio
 
 
+def _read_decoded(path: str):
+    """-> (frames, rate) of a PCM .wav the converter takes (one or two channels, a supported rate), else None"""
+    try:
+        frames, sr = _audio.read_wav_frames(path)
+    except Exception:          # noqa: BLE001 -- not a PCM .wav: ffmpeg's job
+        return None
+    return (frames, sr) if sr in _audio.RESAMPLE_RATES and frames.shape[1] in (1, 2) and len(frames) else None
+
+
 def analyze(path: str, meta: dict):
     try:
+        if os.getenv("AVD_AUDIO_RESAMPLE", "0") == "1":
+            decoded = _read_decoded(path)
+            if decoded is not None:
+                with _analyzer.default_pool().borrow(int(os.getenv("AVD_DEVICE", "0"))) as ctx:
+                    return _audio.analyze_decoded(decoded[0], decoded[1], ctx)
         wav, sr = _audio.extract_wav_16k(path, native=True)      # a 16-bit file: its int16 samples as they are, converted on the device
         with _analyzer.default_pool().borrow(int(os.getenv("AVD_DEVICE", "0"))) as ctx:
             return _audio.analyze_wave(wav, sr, ctx)

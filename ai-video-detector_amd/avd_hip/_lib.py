@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import collections
 import ctypes as C
+import math
 import os
 import subprocess
 import sys
@@ -894,9 +895,29 @@ class Context:
             raise ValueError("wav must be float32[n] or int16[n]")
         return a.ctypes.data, AVD_MEM_HOST, int(a.size), a
 
-    def _audio_call(self, ptr, mem, n: int, win: int, nwin: int, pcm16: bool, cuts=()) -> np.ndarray:
-        """One avd_audio_features call: option "audio_format" set for it and restored (also after an exception), its cuts set in ascending order."""
+    AUDIO_OUT_RATE = 16000
+    AUDIO_RATES = (8000, 11025, 12000, 16000, 22050, 24000, 32000, 44100, 48000, 88200, 96000, 176400, 192000)
+
+    @classmethod
+    def audio_converted_length(cls, n: int, rate: int) -> int:
+        """16 kHz output samples of a track of n frames at ``rate`` (option "audio_rate"): ceil(n * U / D)"""
+        g = math.gcd(int(rate), cls.AUDIO_OUT_RATE)
+        return -(-int(n) * (cls.AUDIO_OUT_RATE // g) // (int(rate) // g))
+
+    def _audio_call(self, ptr, mem, n: int, win: int, nwin: int, pcm16: bool, cuts=(), rate=None, channels: int = 1) -> np.ndarray:
+        """One avd_audio_features call: option "audio_format" -- and, for a track at its decoder's rate, "audio_rate" and "audio_channels" -- set for
+        it and restored (also after an exception), its cuts set in ascending order."""
         out = np.zeros(nwin, AUDIO_WINDOW_DTYPE)
+        if rate is not None:
+            # a refused value leaves the options as they were: nothing has been set yet
+            was = self.get_option("audio_rate"), self.get_option("audio_channels")
+            self.set_option("audio_rate", int(rate))
+            try:
+                self.set_option("audio_channels", int(channels))
+                return self._audio_call(ptr, mem, n, win, nwin, pcm16, cuts)
+            finally:
+                self.set_option("audio_rate", was[0])
+                self.set_option("audio_channels", was[1])
         want = 1 if pcm16 else 0
         before = self.get_option("audio_format")             # a caller of the C-ABI may keep the option at 1: the samples handed over HERE decide
         if before != want:
@@ -914,23 +935,56 @@ class Context:
                 self.set_option("audio_format", before)
         return out
 
-    def audio_features(self, wav, win: int) -> np.ndarray:
+    @staticmethod
+    def _audio_frames(wav, channels: int):
+        """-> (the interleaved samples as one flat array, channels): [n, c] names its own channel count, a flat array is n * channels samples"""
+        if wav.ndim == 2:
+            channels = int(wav.shape[1])
+            wav = (wav.contiguous() if _is_torch_tensor(wav) else np.ascontiguousarray(wav)).reshape(-1)
+        elif wav.ndim != 1:
+            raise ValueError("wav must be [n * channels] or [n, channels]")
+        if channels < 1 or int(wav.shape[0]) % channels:
+            raise ValueError("wav does not hold whole frames of %d channels" % channels)
+        return wav, channels
+
+    def audio_features(self, wav, win: int, rate=None, channels: int = 1) -> np.ndarray:
         """wav: mono samples, float32 or 16-bit PCM as decoded (int16: sample s counts as float32(s) * 2^-15, converted on the device), numpy or
-        torch-ROCm tensor -> structured array (AUDIO_WINDOW_DTYPE) per window."""
+        torch-ROCm tensor -> structured array (AUDIO_WINDOW_DTYPE) per window.
+
+        rate (one of AUDIO_RATES): wav is a track as its decoder produced it -- frames at ``rate``, [n] / [n, 1] mono or [n, 2] / flat with
+        channels = 2 interleaved stereo -- and is downmixed, resampled to 16 kHz and narrowed to 16 bit on the device first (options "audio_rate" /
+        "audio_channels", set for this call and restored); win and the records refer to the 16 kHz output."""
         pcm16 = self._is_pcm16(wav)
-        ptr, mem, n, keep = self._audio_ptr(wav, pcm16)
-        nwin = (n + win - 1) // win if n and win > 0 else 0          # win < 1 or > 8192: the library refuses (AvdError)
-        return self._audio_call(ptr, mem, n, win, nwin, pcm16)
+        if rate is None:
+            ptr, mem, n, keep = self._audio_ptr(wav, pcm16)
+            nwin = (n + win - 1) // win if n and win > 0 else 0          # win < 1 or > 8192: the library refuses (AvdError)
+            return self._audio_call(ptr, mem, n, win, nwin, pcm16)
+        wav, channels = self._audio_frames(wav, channels)
+        ptr, mem, size, keep = self._audio_ptr(wav, pcm16)
+        n = size // channels
+        n_out = self.audio_converted_length(n, rate) if rate in self.AUDIO_RATES else 0          # another rate: the library refuses (AvdError)
+        nwin = (n_out + win - 1) // win if n_out and win > 0 else 0
+        return self._audio_call(ptr, mem, n, win, nwin, pcm16, (), rate, channels)
 
     AUDIO_TRACKS_PER_CALL = 64
 
-    def audio_features_many(self, tracks, win: int) -> list:
+    def audio_features_many(self, tracks, win: int, rate=None, channels: int = 1) -> list:
         """Several mono tracks in as few calls as possible (option "audio_cut": up to 64 tracks share one call and fill the chip together).
         tracks: all float32 or all int16, all host arrays (numpy, host tensors) or all device tensors.  Host tracks are concatenated once, device
-        tracks go through one torch.cat.  -> one record array per track, in order: byte for byte what audio_features gives for that track alone."""
+        tracks go through one torch.cat.  -> one record array per track, in order: byte for byte what audio_features gives for that track alone.
+
+        rate: every track is frames at that rate with the same channel count (see audio_features); the cuts are frame positions, and each track is
+        converted from its own start."""
         tracks = list(tracks)
         if not tracks:
             return []
+        if rate is not None:
+            framed = [self._audio_frames(t, channels) for t in tracks]
+            if len({c for _, c in framed}) != 1:
+                raise ValueError("audio_features_many: the tracks must have one channel count")
+            tracks, channels = [t for t, _ in framed], framed[0][1]
+        else:
+            channels = 1
         pcm = {self._is_pcm16(t) for t in tracks}
         if len(pcm) != 1:
             raise ValueError("audio_features_many: the tracks must be all float32 or all int16")
@@ -942,7 +996,13 @@ class Context:
             raise ValueError("wav must be float32[n] or int16[n]")
         win = int(win)
         per = win if 1 <= win <= 8192 else 0                         # win < 1 or > 8192: the library refuses (AvdError)
-        lens =[int(t.shape[0]) for t in tracks]
+        lens = [int(t.shape[0]) // channels for t in tracks]          # frames
+        if rate is None:
+            analysed = lens                                           # samples the analyzer windows, per track
+        elif rate in self.AUDIO_RATES:
+            analysed = [self.audio_converted_length(n, rate) for n in lens]
+        else:
+            analysed = [0] * len(lens)                                # another rate: the library refuses (AvdError)
         if on_device.pop():
             import torch
             whole = torch.cat([t if pcm16 else t.to(torch.float32) for t in tracks])
@@ -950,7 +1010,7 @@ class Context:
             dt = np.int16 if pcm16 else np.float32
             whole = np.concatenate([np.asarray(t.numpy() if _is_torch_tensor(t) else t, dtype=dt) for t in tracks])
         ptr, mem, _, keep = self._audio_ptr(whole, pcm16)
-        size = 2 if pcm16 else 4
+        size = (2 if pcm16 else 4) * channels
         results = [None] * len(tracks)
         # an empty track has no window and cannot be cut off (cuts ascend strictly): it gets its empty result here and stays out of the calls
         live = [i for i, n in enumerate(lens) if n > 0]
@@ -958,9 +1018,9 @@ class Context:
         for g in range(0, len(live), self.AUDIO_TRACKS_PER_CALL):
             group = live[g:g + self.AUDIO_TRACKS_PER_CALL]
             first, end = int(starts[group[0]]), int(starts[group[-1] + 1])
-            counts = [(lens[i] + per - 1) // per if per else 0 for i in group]
+            counts = [(analysed[i] + per - 1) // per if per else 0 for i in group]
             cuts = [int(starts[i]) - first for i in group[1:]]
-            rec = self._audio_call(ptr + first * size, mem, end - first, win, sum(counts), pcm16, cuts)
+            rec = self._audio_call(ptr + first * size, mem, end - first, win, sum(counts), pcm16, cuts, rate, channels)
             at = 0
             for i, c in zip(group, counts):
                 results[i] = rec[at:at + c]
@@ -978,6 +1038,29 @@ class Context:
         if got < 0:
             self._check(int(got))
         return out[:got // 12].copy()
+
+    def audio_resample_plan(self):
+        """(rate, channels, U, D, T, outputs per tile, input frames, output samples) of the last audio_features call, which converted its input
+        (rate given); avd_debug_fetch "audio_rs_plan"."""
+        return tuple(int(v) for v in self.debug_fetch("audio_rs_plan", (8,), np.int32))
+
+    def audio_resample_taps(self) -> np.ndarray:
+        """int32[U, T]: the filter bank that call ran with (empty at rate 16000, which has none); avd_debug_fetch "audio_rs_taps"."""
+        _, _, U, _, T, _, _, _ = self.audio_resample_plan()
+        return self.debug_fetch("audio_rs_taps", (U, T), np.int32) if U * T else np.zeros((U, 0), np.int32)
+
+    def audio_resample_tracks(self) -> np.ndarray:
+        """int32[tracks, 2]: per track of that call its first output sample in the converted buffer and its output samples; avd_debug_fetch
+        "audio_rs_tracks"."""
+        out = np.zeros((self.AUDIO_TRACKS_PER_CALL, 2), np.int32)
+        got = self._L.avd_debug_fetch(self._h, b"audio_rs_tracks", out.ctypes.data, out.nbytes)
+        if got < 0:
+            self._check(int(got))
+        return out[:got // 8].copy()
+
+    def audio_pcm(self) -> np.ndarray:
+        """int16[output samples]: the converted tracks of that call, side by side -- what the analyzer ran over; avd_debug_fetch "audio_pcm"."""
+        return self.debug_fetch("audio_pcm", (self.audio_resample_plan()[7],), np.int16)
 
     def audio_plan(self):
         """(nwin, win, last, nfull) of the last audio_features call: windows, window length, length of the last window, windows that

@@ -50,6 +50,26 @@ def read_wav_native(path: str):
     return np.ascontiguousarray(a), int(sr)
 
 
+RESAMPLE_RATES = (8000, 11025, 12000, 16000, 22050, 24000, 32000, 44100, 48000, 88200, 96000, 176400, 192000)   # option "audio_rate" (include/avd.h)
+
+
+def read_wav_frames(path: str):
+    """-> (all channels untouched as [n, channels] -- int16 for a 16-bit file, float32 scaled like read_wav_pcm for 8 / 32 bit --, sample rate):
+    what analyze_decoded takes."""
+    with wave.open(path, "rb") as w:
+        nch, width, sr, n = w.getnchannels(), w.getsampwidth(), w.getframerate(), w.getnframes()
+        raw = w.readframes(n)
+    if width == 2:
+        a = np.frombuffer(raw, "<i2").astype(np.int16, copy=False)
+    elif width == 4:
+        a = (np.frombuffer(raw, "<i4").astype(np.float64) / 2147483648.0).astype(np.float32)
+    elif width == 1:
+        a = (np.frombuffer(raw, np.uint8).astype(np.float32) - np.float32(128.0)) / np.float32(128.0)
+    else:
+        raise RuntimeError("soundfile_read_failed")
+    return np.ascontiguousarray(a.reshape(-1, nch)), int(sr)
+
+
 def extract_wav_16k(path: str, native: bool = False):
     """audio.py:7-20: ffmpeg -> 16 kHz mono wav -> float32 (native: the int16 samples of the 16-bit file ffmpeg writes, as read_wav_native
     hands them over).  Without ffmpeg (this image has none) a file that already IS a 16 kHz PCM wav is read directly; anything else fails the
@@ -158,4 +178,41 @@ def analyze_waves(waves, ctx) -> list:
         for i, rec in zip(members, recs):
             w, sr = waves[i]
             results[i] = features_to_result(window_values(rec), len(w) / sr if sr > 0 else 0.0)
+    return results
+
+
+def _decoded(wav):
+    """a decoded track as [n, c]: int16 PCM stays int16, everything else becomes float32"""
+    wav = np.asarray(wav)
+    if wav.ndim == 1:
+        wav = wav[:, None]
+    if wav.ndim != 2 or wav.shape[1] not in (1, 2):
+        raise ValueError("a decoded track is [n] or [n, c] with c = 1 or 2 (downmix other layouts first)")
+    return np.ascontiguousarray(wav, np.int16 if wav.dtype == np.int16 else np.float32)
+
+
+def _converted_duration(n: int, sr: int, ctx) -> float:
+    return ctx.audio_converted_length(n, sr) / SAMPLE_RATE
+
+
+def analyze_decoded(wav: np.ndarray, sr: int, ctx) -> dict:
+    """audio.py:7-110 for a track as its decoder produced it -- [n] or [n, c], c = 1 or 2, int16 or float32, at one of RESAMPLE_RATES: what the
+    reference's ffmpeg line does (downmix, 16 kHz, 16 bit) happens on the device in front of the analyzer (Context.audio_features, rate=sr)."""
+    wav = _decoded(wav)
+    rec = ctx.audio_features(wav, _win_of(SAMPLE_RATE), rate=int(sr))
+    return features_to_result(window_values(rec), _converted_duration(len(wav), int(sr), ctx))
+
+
+def analyze_decoded_many(waves, ctx) -> list:
+    """[(wav, sr), ...] -> the list of analyze_decoded's results, in input order.  Tracks of one rate, one channel count and one sample type share
+    calls (Context.audio_features_many: up to 64 tracks per call)."""
+    waves = [(_decoded(w), int(sr)) for w, sr in waves]
+    groups = {}
+    for i, (w, sr) in enumerate(waves):
+        groups.setdefault((sr, w.shape[1], w.dtype == np.int16), []).append(i)
+    results = [None] * len(waves)
+    for (sr, _, _), members in groups.items():
+        recs = ctx.audio_features_many([waves[i][0] for i in members], _win_of(SAMPLE_RATE), rate=sr)
+        for i, rec in zip(members, recs):
+            results[i] = features_to_result(window_values(rec), _converted_duration(len(waves[i][0]), sr, ctx))
     return results

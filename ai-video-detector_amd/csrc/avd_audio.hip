@@ -233,7 +233,165 @@ __global__ __launch_bounds__(256) void k_audio_reduce(const double* __restrict__
     }
 }
 
+// ---- the converter in front of pass 1 (options "audio_rate" / "audio_channels"): decoder frames -> 16 kHz mono int16 ------------------------
+// One workgroup per tile of avd_audio_resample.h: a run of at most tile_outputs() output samples of one track.  LDS (laid out by the header's
+// lds_* functions): the rate's filter bank | the span's samples as narrowed | the span downmixed | the tile's results.
+//  * the span is read ONCE, with 16-byte loads where a whole 16-byte line of the buffer lies inside the track's part of the span, sample by
+//    sample in the partial line at either end (the buffer is aligned for its sample type only, and tracks begin wherever they were cut);
+//  * narrowing and downmix happen once per frame; the sums are exact integer multiply-adds -- 32 bits where 32768 * sum|q| stays below 2^31
+//    (every downsampling rate), 64 bits with 32-bit bank entries at the three upsampling rates;
+//  * lane l forms outputs l, l + 256, ...: consecutive lanes read LDS D / U frames apart (three halfwords at 48 kHz, where the bank row is the
+//    same for all lanes and broadcasts; at 44.1 kHz the gathered rows are 92 halfwords long, an odd number of banks apart);
+//  * the results leave as 16-byte rows of the converted buffer; the row a tile shares with its neighbour is written entry by entry.
+using avd_resample::Tile;
+
+// step 1 of the rule: int16 is itself; float32 x is clamp(rint(x * 32768), -32768, 32767), ties to even, NaN -> 0
+__device__ __forceinline__ int narrow_sample(int16_t s) { return s; }
+__device__ __forceinline__ int narrow_sample(float x)
+{
+    const float v = rintf(x * 32768.f);
+    return v != v ? 0 : (int)fminf(fmaxf(v, -32768.f), 32767.f);
+}
+
+template <typename S, typename Q, typename Acc>
+__global__ __launch_bounds__(256) void k_audio_resample(const S* __restrict__ wav, const Tile* __restrict__ tiles, const int* __restrict__ taps, int U, int D,
+                                                       int T, int channels, int samples_at, int mono_at, int res_at, int16_t* __restrict__ pcm)
+{
+    extern __shared__ __align__(16) unsigned char rs_lds[];
+    Q* q = reinterpret_cast<Q*>(rs_lds);
+    int16_t* smp = reinterpret_cast<int16_t*>(rs_lds + samples_at);
+    int16_t* mono = reinterpret_cast<int16_t*>(rs_lds + mono_at);
+    int16_t* res = reinterpret_cast<int16_t*>(rs_lds + res_at);
+    const Tile t = tiles[blockIdx.x];
+    const int tid = threadIdx.x;
+    for (int i = tid; i < U * T; i += 256) q[i] = (Q)taps[i];
+    const int span = T == 0 ? t.count : (t.phase + (t.count - 1) * D) / U + T;
+    // the span's frames that exist: [f_lo, f_hi) of the track; samples [s0, s1) of the buffer
+    const long long f_lo = t.in0 > t.begin ? t.in0 : t.begin, f_hi = t.in0 + span < t.end ? t.in0 + span : t.end;
+    const long long s0 = f_lo * channels, s1 = f_hi * channels;
+    constexpr int per = 16 / (int)sizeof(S);                // samples in a 16-byte line
+    const int lead = (int)((reinterpret_cast<uintptr_t>(wav + s0) & 15) / sizeof(S));   // smp[0] is the sample at the line boundary at or below s0
+    const int lines = s1 > s0 ? (lead + (int)(s1 - s0) + per - 1) / per : 0;
+    for (int c = tid; c < lines; c += 256) {
+        const long long lo = s0 - lead + (long long)c * per;
+        int16_t* dst = smp + c * per;
+        if (lo >= s0 && lo + per <= s1) {
+            const uint4 v = *reinterpret_cast<const uint4*>(wav + lo);
+            if constexpr (sizeof(S) == 2) {
+                *reinterpret_cast<uint4*>(dst) = v;
+            } else {
+                const int a = narrow_sample(__uint_as_float(v.x)), b = narrow_sample(__uint_as_float(v.y));
+                const int c2 = narrow_sample(__uint_as_float(v.z)), d = narrow_sample(__uint_as_float(v.w));
+                uint2 o;
+                o.x = (unsigned)(a & 0xffff) | ((unsigned)b << 16);
+                o.y = (unsigned)(c2 & 0xffff) | ((unsigned)d << 16);
+                *reinterpret_cast<uint2*>(dst) = o;
+            }
+        } else {
+            for (int e = 0; e < per; e++) {
+                const long long s = lo + e;
+                dst[e] = s >= s0 && s < s1 ? (int16_t)narrow_sample(wav[s]) : (int16_t)0;
+            }
+        }
+    }
+    __syncthreads();
+    // step 2: M = s, or floor((L + R + 1) / 2); 0 outside the track
+    for (int i = tid; i < span; i += 256) {
+        const long long f = t.in0 + i;
+        int m = 0;
+        if (f >= f_lo && f < f_hi) {
+            const int at = lead + (int)(f - f_lo) * channels;
+            m = channels == 2 ? ((int)smp[at] + (int)smp[at + 1] + 1) >> 1 : (int)smp[at];
+        }
+        mono[i] = (int16_t)m;
+    }
+    __syncthreads();
+    // step 4; res[e] is entry e of the converted buffer counted from the 16-byte row boundary at or below the tile's first output
+    const int shift = (int)(t.out0 & 7);
+    for (int j = tid; j < t.count; j += 256) {
+        int y;
+        if (T == 0) y = mono[j];
+        else {
+            const int pos = t.phase + j * D, idx = pos / U, phi = pos - idx * U;
+            const Q* row = q + phi * T;
+            const int16_t* x = mono + idx;
+            Acc acc = 0;
+            for (int k = 0; k < T; k++) acc += (Acc)row[k] * (Acc)x[k];
+            const Acc v = (acc + 16384) >> 15;
+            y = v < -32768 ? -32768 : v > 32767 ? 32767 : (int)v;
+        }
+        res[shift + j] = (int16_t)y;
+    }
+    __syncthreads();
+    int16_t* out = pcm + (t.out0 - shift);
+    const int last = shift + t.count;
+    for (int r = tid; r < (last + 7) / 8; r += 256) {
+        const int e0 = r * 8;
+        if (e0 >= shift && e0 + 8 <= last) *reinterpret_cast<uint4*>(out + e0) = *reinterpret_cast<const uint4*>(res + e0);
+        else
+            for (int e = e0 > shift ? e0 : shift; e < e0 + 8 && e < last; e++) out[e] = res[e];
+    }
+}
+
+template <typename S, typename Q, typename Acc>
+int launch_resample_as(avd_ctx* ctx, const void* d_in, const Tile* tiles, const int* taps, int ntiles, const avd_resample::Ratio& r, int channels, int16_t* d_pcm)
+{
+    const size_t at_s = avd_resample::lds_taps_bytes(r), at_m = at_s + avd_resample::lds_samples_bytes(r, channels), at_r = at_m + avd_resample::lds_mono_bytes(r);
+    const size_t lds = avd_resample::lds_bytes(r, channels);
+    // per call (a function attribute belongs to the current device; a process may hold contexts on several)
+    HIP_TRY(ctx, hipFuncSetAttribute((const void*)k_audio_resample<S, Q, Acc>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL((k_audio_resample<S, Q, Acc>), dim3(ntiles), dim3(256), lds, ctx->stream, static_cast<const S*>(d_in), tiles, taps, r.U, r.D, r.T, channels,
+                       (int)at_s, (int)at_m, (int)at_r, d_pcm);
+    return 0;
+}
+
 }  // namespace
+
+int launch_audio_resample(avd_ctx* ctx, const void* d_in, int format, int channels, const avd_resample::Plan& plan, int16_t* d_pcm)
+{
+    const avd_resample::Ratio& r = plan.r;
+    const int ntiles = (int)plan.tiles.size(), bank = r.U * r.T, idx = avd_resample::rate_index(r.rate);
+    if (ntiles <= 0 || idx < 0) return 0;
+    Workspace& ws = ctx->ws;
+    ctx->audio_rs_valid = 0;
+    if (ws.audio_rs_upload_pending) { HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); ws.audio_rs_upload_pending = 0; }
+    std::vector<int>& taps = ctx->audio_rs_bank[idx];
+    if (taps.empty() && bank) taps = avd_resample::build_taps(r);       // once per rate and context
+    const bool new_rate = bank && ws.audio_rs_rate != r.rate;
+    // pinned staging, in units of a tile (40 bytes): the tile table, then the bank when the rate changed
+    const size_t bank_tiles = new_rate ? (sizeof(int) * (size_t)bank + sizeof(Tile) - 1) / sizeof(Tile) : 0;
+    if (int e = ws.h_audio_rs.reserve(ctx, (size_t)ntiles + bank_tiles)) return e;
+    if (int e = ws.d_audio_rs_tiles.reserve(ctx, (size_t)ntiles)) return e;
+    std::memcpy(ws.h_audio_rs.p, plan.tiles.data(), sizeof(Tile) * (size_t)ntiles);
+    if (new_rate) {
+        std::memcpy(ws.h_audio_rs.p + ntiles, taps.data(), sizeof(int) * (size_t)bank);
+        ws.audio_rs_rate = 0;                                // the bank is not valid again until its copy is enqueued
+        if (int e = ws.d_audio_rs_taps.reserve(ctx, (size_t)bank)) return e;
+    }
+    ws.audio_rs_upload_pending = 1;
+    HIP_TRY(ctx, hipMemcpyAsync(ws.d_audio_rs_tiles, ws.h_audio_rs.p, sizeof(Tile) * (size_t)ntiles, hipMemcpyHostToDevice, ctx->stream));
+    if (new_rate) {
+        HIP_TRY(ctx, hipMemcpyAsync(ws.d_audio_rs_taps, ws.h_audio_rs.p + ntiles, sizeof(int) * (size_t)bank, hipMemcpyHostToDevice, ctx->stream));
+        ws.audio_rs_rate = r.rate;
+    }
+    const Tile* tiles = ws.d_audio_rs_tiles;
+    const int* d_taps = ws.d_audio_rs_taps;                  // null at rate 16000 before any other rate ran: T = 0 reads none
+    int e;
+    if (avd_resample::wide(r))
+        e = format == 1 ? launch_resample_as<int16_t, int, long long>(ctx, d_in, tiles, d_taps, ntiles, r, channels, d_pcm)
+                        : launch_resample_as<float, int, long long>(ctx, d_in, tiles, d_taps, ntiles, r, channels, d_pcm);
+    else
+        e = format == 1 ? launch_resample_as<int16_t, int16_t, int>(ctx, d_in, tiles, d_taps, ntiles, r, channels, d_pcm)
+                        : launch_resample_as<float, int16_t, int>(ctx, d_in, tiles, d_taps, ntiles, r, channels, d_pcm);
+    if (e) return e;
+    HIP_TRY(ctx, hipGetLastError());
+    const int rs_plan[8] = {r.rate, channels, r.U, r.D, r.T, plan.tile_out, (int)std::min<long long>(plan.n_in, 0x7fffffff), (int)plan.n_out};
+    std::memcpy(ctx->audio_rs_plan, rs_plan, sizeof rs_plan);
+    ctx->audio_rs_ntracks = (int)plan.tracks.size();
+    std::memcpy(ctx->audio_rs_tracks, plan.tracks.data(), sizeof(avd_resample::Track) * plan.tracks.size());
+    ctx->audio_rs_valid = 1;
+    return 0;
+}
 
 // np.hanning(L), cos(2 pi j / L) and sin(2 pi j / L) at t, t + L and t + 2 L.  The one place where a table value is formed, for the full length
 // and for every short one, on the host: a track's windows read the same bits whether it is analysed alone or in a batch, which is what makes the

@@ -487,6 +487,10 @@ static void audio_cut_set(avd_ctx* ctx, int v)
     else ctx->audio_cuts[ctx->audio_ncuts++] = v;
 }
 static int audio_cut_read(const avd_ctx* ctx) { return ctx->audio_ncuts; }
+// "audio_rate": 0 the samples are the 16 kHz track already; a rate of avd_audio_resample.h: frames at that rate, converted on the device; durable
+static bool opt_audio_rate(int& v) { return v == 0 || avd_resample::rate_index(v) >= 0; }
+// "audio_channels": interleaved samples per frame of a converted call, 1 or 2; durable
+static bool opt_audio_channels(int& v) { return v == 1 || v == 2; }
 // "ingest_group": 0 a launch pair per clip, 1 one per group of clips that share a key (avd_ingest_group.h); durable
 static bool opt_ingest_group(int& v) { return v == 0 || v == 1; }
 // "cv2_model": any combination of the bits 1, 8 and 16 (the oracle's jitter switches 2 and 4 model nothing a library can follow); durable
@@ -516,6 +520,8 @@ static const Option kOptions[] = {
     {"stream_frames", nullptr, false, opt_any, nullptr, nullptr, nullptr, nullptr, stream_frames},
     {"audio_format", &avd_ctx::audio_format, true, opt_audio_format, nullptr, nullptr, "audio_format: 0 (float32 samples) or 1 (little-endian int16 PCM)"},
     {"audio_cut", nullptr, true, opt_any, nullptr, nullptr, nullptr, audio_cut_set, audio_cut_read, audio_cut_check},
+    {"audio_rate", &avd_ctx::audio_rate, true, opt_audio_rate, nullptr, nullptr, "audio_rate: 0 (samples at 16 kHz already) or 8000, 11025, 12000, 16000, 22050, 24000, 32000, 44100, 48000, 88200, 96000, 176400, 192000"},
+    {"audio_channels", &avd_ctx::audio_channels, true, opt_audio_channels, nullptr, nullptr, "audio_channels: 1 or 2 interleaved samples per frame (downmix other layouts first)"},
     {"ingest_group", &avd_ctx::ingest_group, true, opt_ingest_group, nullptr, nullptr, "ingest_group: 0 (an ingest and a hash launch per clip) or 1 (one of each per group of clips that share a key)"},
     {"cv2_model", &avd_ctx::cv2_model, true, opt_cv2_model, "AVD_CV2_MODEL", env_any_base, "cv2_model: a combination of 1 (GAUSS_MULADD), 8 (THREE_SCALES) and 16 (RESIZE_LERP), or 0 (the default model)"},
 };
@@ -1220,7 +1226,26 @@ static int64_t impl_debug_fetch(avd_ctx* ctx, const char* name, void* out, size_
         HIP_TRY(ctx, hipSetDevice(ctx->device));
         return cnn_tap_fetch(ctx, out, out_bytes);
     }
-    if (std::strncmp(name, "audio_", 6) == 0) {        // the last avd_audio_features of this context: its window plan (host state) and its two scratch arrays
+    if (std::strncmp(name, "audio_rs_", 9) == 0 || std::strcmp(name, "audio_pcm") == 0) {   // the converter's part of the last avd_audio_features call (option "audio_rate")
+        const bool rs_plan = std::strcmp(name, "audio_rs_plan") == 0, rs_taps = std::strcmp(name, "audio_rs_taps") == 0, rs_tracks = std::strcmp(name, "audio_rs_tracks") == 0;
+        if (!rs_plan && !rs_taps && !rs_tracks && std::strcmp(name, "audio_pcm") != 0) { ctx->err = "unknown debug buffer"; return AVD_ERR_ARG; }
+        if (!ctx->audio_rs_valid) { ctx->err = "audio_rs_plan / audio_rs_taps / audio_rs_tracks / audio_pcm not recorded: the last avd_audio_features call on this context did not convert (option \"audio_rate\")"; return AVD_ERR_ARG; }
+        const int* rp = ctx->audio_rs_plan;
+        const void* from = nullptr;
+        size_t have = 0;
+        const char* type = nullptr;
+        if (rs_plan) { from = rp; have = sizeof(ctx->audio_rs_plan); type = "audio_rs_plan is int32[8]"; }
+        else if (rs_taps) { const std::vector<int>& b = ctx->audio_rs_bank[avd_resample::rate_index(rp[0])]; from = b.data(); have = sizeof(int) * b.size(); type = "audio_rs_taps is int32[U][T]"; }
+        else if (rs_tracks) { from = ctx->audio_rs_tracks; have = sizeof(int) * 2 * (size_t)ctx->audio_rs_ntracks; type = "audio_rs_tracks is int32[tracks][2]"; }
+        if (type) {
+            if (out_bytes < have) { ctx->err = type; return AVD_ERR_ARG; }
+            if (have) std::memcpy(out, from, have);
+            return (int64_t)have;
+        }
+        src = ws.d_audio_pcm.p;                          // null after avd_release_workspace: "buffer not allocated yet" below
+        bytes = sizeof(int16_t) * (size_t)rp[7];
+    }
+    else if (std::strncmp(name, "audio_", 6) == 0) {   // the last avd_audio_features of this context: its window plan (host state) and its two scratch arrays
         const bool plan = std::strcmp(name + 6, "plan") == 0, xw = std::strcmp(name + 6, "xw") == 0, mag = std::strcmp(name + 6, "mag") == 0;
         const bool tracks = std::strcmp(name + 6, "tracks") == 0;
         if (!plan && !xw && !mag && !tracks && std::strcmp(name + 6, "host") != 0) { ctx->err = "unknown debug buffer"; return AVD_ERR_ARG; }
@@ -1478,6 +1503,38 @@ static int impl_rowop(avd_ctx* ctx, int op, const void* x, int mem, int bf16, in
 }
 
 // ---- audio analyzer (row N3) -------------------------------------------------------------------------------------
+// Option "audio_rate" != 0: n FRAMES of audio_channels interleaved samples at that rate.  Two steps: the converter (k_audio_resample) writes the
+// 16 kHz mono int16 tracks into ws.d_audio_pcm, then the analyzer runs over that buffer and the output-side cuts exactly as it runs over a caller's
+// int16 track (format 1).  Every check comes before anything is staged, in the order include/avd.h lists: the argument checks and the int16
+// alignment (impl_audio_features), the float32 alignment, a cut beyond the buffer, the windows array against the OUTPUT's window count.
+static int convert_audio_features(avd_ctx* ctx, const void* wav, int mem, int64_t n, int win, avd_audio_window* windows, int max_windows, const int* cuts, int ncuts)
+{
+    const int format = ctx->audio_format, channels = ctx->audio_channels;
+    if (format == 0 && (reinterpret_cast<uintptr_t>(wav) & 3)) { ctx->err = "audio_rate: float32 samples need a 4-byte aligned wav"; return AVD_ERR_ARG; }
+    if (mem != AVD_MEM_HOST && mem != AVD_MEM_DEVICE) { ctx->err = "mem must be AVD_MEM_HOST or AVD_MEM_DEVICE"; return AVD_ERR_ARG; }
+    avd_resample::Ratio ratio;
+    if (!avd_resample::ratio_of(ctx->audio_rate, ratio)) { ctx->err = "audio_rate: not a supported rate"; return AVD_ERR_ARG; }   // (the option refuses such a value)
+    const avd_resample::Plan conv = avd_resample::plan_convert(n, ratio, cuts, ncuts);
+    if (conv.refused == avd_resample::kCutBeyond) { ctx->err = "audio_cut: beyond the buffer"; return AVD_ERR_ARG; }
+    if (conv.refused) { ctx->err = "audio_rate: more than 2^31 - 1 output samples"; return AVD_ERR_ARG; }
+    const avd_audio::Plan plan = avd_audio::plan_call(conv.n_out, win, conv.out_cuts.data(), ncuts, max_windows);
+    if (plan.refused) { ctx->err = "windows array too small"; return AVD_ERR_ARG; }
+    const int nwin = plan.nwin();
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    Workspace& ws = ctx->ws;
+    const uint8_t* d_in = nullptr;
+    if (int e = stage_input(ctx, static_cast<const uint8_t*>(wav), mem, (size_t)n * (size_t)channels * (format == 1 ? sizeof(int16_t) : sizeof(float)), &d_in)) return e;
+    if (int e = ws.d_audio_pcm.reserve(ctx, (size_t)conv.n_out + 8)) return e;
+    if (int e = ws.d_audio_out.reserve(ctx, (size_t)nwin)) return e;
+    if (int e = launch_audio_resample(ctx, d_in, format, channels, conv, ws.d_audio_pcm)) return e;
+    if (int e = launch_audio_features(ctx, ws.d_audio_pcm, 1, plan, ws.d_audio_out)) return e;
+    HIP_TRY(ctx, hipMemcpyAsync(windows, ws.d_audio_out, sizeof(avd_audio_window) * nwin, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    ws.audio_upload_pending = 0;
+    ws.audio_rs_upload_pending = 0;
+    return AVD_OK;
+}
+
 // cuts / ncuts: the "audio_cut" list the call took from the context (avd_audio_features: one-shot, whatever becomes of the call)
 static int impl_audio_features(avd_ctx* ctx, const void* wav, int mem, int64_t n, int win, avd_audio_window* windows, int max_windows, const int* cuts, int ncuts)
 {
@@ -1486,9 +1543,11 @@ static int impl_audio_features(avd_ctx* ctx, const void* wav, int mem, int64_t n
     if (n == 0) return AVD_OK;
     const int format = ctx->audio_format;
     if (format == 1 && (reinterpret_cast<uintptr_t>(wav) & 1)) { ctx->err = "audio_format 1: int16 samples need a 2-byte aligned wav"; return AVD_ERR_ARG; }
+    if (ctx->audio_rate != 0) return convert_audio_features(ctx, wav, mem, n, win, windows, max_windows, cuts, ncuts);
     const avd_audio::Plan plan = avd_audio::plan_call(n, win, cuts, ncuts, max_windows);
     if (plan.refused == avd_audio::kCutBeyond) { ctx->err = "audio_cut: beyond the buffer"; return AVD_ERR_ARG; }
     if (plan.refused) { ctx->err = "windows array too small"; return AVD_ERR_ARG; }
+    ctx->audio_rs_valid = 0;                                 // debug buffers "audio_rs_*" / "audio_pcm" describe the last call that ran, and only if it converted
     const int nwin = plan.nwin();
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     Workspace& ws = ctx->ws;

@@ -10,6 +10,7 @@
 #include "avd_ingest_clip.h"      // IngestClip: one clip of an ingest call, its argument check and its staging plan (host only)
 #include "avd_stream_plan.h"      // where the clips of a call lie when some continue a stream slot (host only)
 #include "avd_audio_plan.h"       // the tracks, window table and table arena of one avd_audio_features call (host only)
+#include "avd_audio_resample.h"   // the converter in front of it (option "audio_rate"): ratios, filter bank, output ranges, tile table (host only)
 #include "avd_ingest_group.h"     // which clips of a call share an ingest launch (option "ingest_group"), and kLapSlots (host only)
 
 #define AVD_FB_LEVELS 4            // pyramid scales 1/8,1/4,1/2,1 of 320 (see avd_farneback.hip)
@@ -241,6 +242,13 @@ struct Workspace {
     int audio_upload_pending = 0;         // that copy was enqueued by a call that has not drained the stream since
     DevBuf<double> d_audio_buf;
     DevBuf<avd_audio_window> d_audio_out;
+    // the converter in front of the analyzer (option "audio_rate", k_audio_resample): the converted tracks, 16 kHz mono int16, side by side (8 spare
+    // entries: its 16-byte rows); the filter bank [U][T] of rate audio_rs_rate, kept across calls; the call's tile table with its pinned mirror (which
+    // also carries the bank when the rate changed), uploaded like d_audio_call
+    DevBuf<int16_t> d_audio_pcm;
+    DevBuf<int> d_audio_rs_taps; int audio_rs_rate = 0;
+    DevBuf<avd_resample::Tile> d_audio_rs_tiles; PinBuf<avd_resample::Tile> h_audio_rs;
+    int audio_rs_upload_pending = 0;      // that copy was enqueued by a call that has not drained the stream since
     // CNN extension (avd_cnn.hip): activation scratch for cnn_frames frames
     DevBuf<uint16_t> d_cnn_act[4], d_cnn_img;
     DevBuf<float> d_cnn_pool, d_cnn_logits; int cnn_frames = 0;
@@ -344,6 +352,15 @@ struct avd_ctx {
     // the list whatever becomes of it, so a forgotten list never splits a later call and results do not depend on the context's history
     int audio_cuts[avd_audio::kMaxCuts] = {};
     int audio_ncuts = 0;
+    // options "audio_rate" / "audio_channels": wav of avd_audio_features holds n FRAMES of audio_channels interleaved samples at audio_rate, converted
+    // on the device to the 16 kHz mono int16 track the analyzer runs over (avd_audio_resample.h); audio_rate 0 = the samples are that track already
+    int audio_rate = 0;
+    int audio_channels = 1;
+    std::vector<int> audio_rs_bank[avd_resample::kNumRates];   // the filter bank of each rate a call has used, built once (avd_resample::build_taps)
+    int audio_rs_plan[8] = {};      // debug buffer "audio_rs_plan" of the last avd_audio_features call, if it converted: rate, channels, U, D, T, outputs per tile, input frames, output samples
+    int audio_rs_valid = 0;         // 0 while the last call that ran did not convert (or none ran)
+    int audio_rs_tracks[avd_audio::kMaxTracks][2] = {};   // per track of that call: first output sample, output samples (debug buffer "audio_rs_tracks")
+    int audio_rs_ntracks = 0;
     int cnn_chunk = 128;            // CNN extension: frames per forward pass (activation scratch = 4 x 1.6 MB per frame)
     int cnn_fuse = 2;               // CNN extension: a block's 3x3 and expanding 1x1 in one launch (stages 1, 2): 2 = with the 3x3's input slab in LDS in the stride-1 blocks (k_slab3_expand), 1 = gathering kernels only, 0 = layer by layer
     int fb_fused = 0xF;             // bit k: pyramid level k runs the fused kernel (avd_fbfused.hip) instead of the two-kernel path (avd_fbtwo.hip)
@@ -450,6 +467,9 @@ int comm_allgather_records(avd_ctx* ctx, const avd_frame_record* local, int coun
 int comm_allgather_last_records(avd_ctx* ctx, int count, avd_frame_record* all);
 // avd_audio.hip: per-window features of the mono tracks of `plan` (device pointers; format: option "audio_format")
 int launch_audio_features(avd_ctx* ctx, const void* d_wav, int format, const avd_audio::Plan& plan, avd_audio_window* d_out);
+// avd_audio.hip: the frames at d_in (format: option "audio_format"; channels interleaved) to the 16 kHz mono int16 tracks of `plan` at d_pcm
+// (device, plan.n_out + 8 entries, 16-byte aligned)
+int launch_audio_resample(avd_ctx* ctx, const void* d_in, int format, int channels, const avd_resample::Plan& plan, int16_t* d_pcm);
 // avd_fbfused.hip: all blur iterations of one pyramid level (w = 40 / 80 / 160 / 320) in one launch, one workgroup per pair
 // zero_first: the initial flow is zero whatever the buffer holds (the coarsest level: no clearing launch)
 // plist (may be null): the launch works on pairs plist[0 .. np)

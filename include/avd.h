@@ -417,6 +417,44 @@ int avd_softmax(avd_ctx* ctx, const float* x, int mem, int64_t rows, int cols, f
  *     of avd_audio_features on that track's samples alone.  Checked after the argument checks above and before anything is staged, in this order:
  *     a cut >= n is AVD_ERR_ARG ("audio_cut: beyond the buffer"); max_windows below the sum of the tracks' window counts is AVD_ERR_ARG.  n = 0
  *     with cuts pending is AVD_OK, writes nothing and clears the list.
+ *
+ * Tracks at the decoder's rate.  Two more durable options put a converter in front of the analyzer, on the device: what the reference's
+ * "ffmpeg -ac 1 -ar 16000 -f wav" does (audio.py:10) -- downmix to mono, resample to 16 kHz, narrow to 16 bit.  With both at their defaults
+ * every call and every record is byte for byte what it was before they existed.
+ *   "audio_rate" (durable, reads back): 0 (default) the samples are at the analysis rate already.  One of 8000, 11025, 12000, 16000, 22050,
+ *     24000, 32000, 44100, 48000, 88200, 96000, 176400, 192000: wav holds n sample FRAMES at that rate.  Any other value is AVD_ERR_ARG with a
+ *     message that begins "audio_rate:", and the old value stays.
+ *   "audio_channels" (durable, reads back; read only while "audio_rate" is not 0): 1 (default) or 2 interleaved samples per frame.  Any other
+ *     value is AVD_ERR_ARG with a message that begins "audio_channels:"; the caller downmixes other layouts first.
+ * While "audio_rate" is not 0: "audio_format" gives the sample type of the input (n * channels samples); win, max_windows and the records refer
+ * to the 16 kHz OUTPUT; "audio_cut" positions are input frames; each track is converted from its own start with zeros beyond both of its ends
+ * and has ceil(n_t * U / D) output samples, and its records are byte for byte those of the track alone.  The analyzer sees an output sample y
+ * exactly as it sees an int16 sample under "audio_format" 1: (float)y * 2^-15.  Checks, all before anything is staged, in this order: the
+ * argument checks above; alignment -- 2 bytes for int16 ("audio_format 1: ..."), 4 bytes for float32 ("audio_rate: float32 samples need a
+ * 4-byte aligned wav"); a cut >= n ("audio_cut: beyond the buffer"); more than 2^31 - 1 output samples ("audio_rate: ..."); max_windows below the
+ * OUTPUT's window count.  A refused call leaves the context as if it had not been made; the cut list remains one-shot.
+ *
+ * The conversion is a stated rule.  It is modelled on libswresample's defaults (a Kaiser-windowed sinc with beta = 9, a 32-tap base length,
+ * cutoff 0.97, a 16-bit fixed-point filter bank, a 16-bit result) and is unpinned against a real ffmpeg: no libswresample was at hand to compare
+ * with, so nothing here promises ffmpeg's bits.  After step 1 it is integer arithmetic throughout, so a restatement matches it bit for bit
+ * (tests/audio_resample_reference.py).  R the rate, g = gcd(R, 16000), U = 16000 / g, D = R / g.
+ *   1. Narrow.  An int16 sample is itself.  A float32 sample x is clamp(rint(x * 32768), -32768, 32767), ties to even; NaN is 0, +-inf clamp.
+ *   2. Downmix.  One channel: M = s.  Two: M = floor((L + R + 1) / 2).
+ *   3. Filter bank (none at R = 16000, which is steps 1 and 2 only; T is then reported as 0).  f = min(1, 0.97 U / D), T = 2 ceil(16 / f) taps
+ *      per phase (48000: U 1, D 3, T 100; 44100: U 160, D 441, T 92).  For phase p in [0, U) and tap k in [0, T): x = (k - T/2 + 1) - p / U,
+ *      h = f sinc(f x) I0(9 sqrt(1 - (2 x / T)^2)) / I0(9) with sinc(t) = sin(pi t) / (pi t), h = 0 where the root's argument is negative, all in
+ *      double; q[p][k] = rint(h / sum_k h * 32768); then 32768 - sum_k q is added to the tap with the largest h (the lowest k on a tie), so every
+ *      phase sums to exactly 32768.  Built on the host once per rate and context.
+ *   4. Output m in [0, ceil(n U / D)): i0 = floor(m D / U), p = (m D) mod U, acc = sum_k q[p][k] M[i0 - T/2 + 1 + k] with M = 0 outside the
+ *      track, y = clamp((acc + 16384) >> 15, -32768, 32767), the shift arithmetic.
+ * sum_k |q| is at most 63760 at the downsampling rates (a 32-bit accumulator is exact) and 77084, with entries up to 32768, at 8000, 11025 and
+ * 12000 (64-bit accumulator, 32-bit entries).  A 1 kHz sine of 20000 peak comes back within 5 LSB from 48000 and 44100; a 10 kHz tone at 48000
+ * leaves at most 3 LSB.
+ * avd_debug_fetch, of the last call that ran, if it converted (an error otherwise): "audio_rs_plan" int32[8] -- rate, channels, U, D, T, outputs
+ * per tile (a tile: one workgroup's run of outputs of one track), input frames, output samples; "audio_rs_taps" int32[U][T]; "audio_rs_tracks"
+ * int32[tracks][2] -- per track its first output sample and its output samples; "audio_pcm" int16[output samples] -- the converted tracks side
+ * by side (an error after avd_release_workspace).  "audio_plan", "audio_tracks", "audio_xw" and "audio_mag" then describe the analysis of that output.
+ *
  * avd_debug_fetch, host state of the last call that ran: "audio_tracks" int32[tracks][3] -- per track its first window, its windows and the length
  * of its last window; "audio_plan" int32[4] -- windows of all tracks, win, the LAST track's last length, windows of all tracks that took the
  * 80 x 100 transform; "audio_host" int32[2] -- the microseconds the host spent forming the tables of the call's short window lengths, and how
@@ -610,7 +648,8 @@ int avd_set_profiling(avd_ctx* ctx, int enable);
  * avd_frame_record.reserved are never set, and in the few-pairs re-run bit 2 of "fb_rerun_fused" is taken as set (the coarsest level runs the fused
  * kernel).  The fast mode's flag thresholds were fuzzed at full size under the default model only; see DESIGN.md section 2 for what was repeated.
  * "audio_format" (0 float32, 1 int16 PCM; durable) and "audio_cut" (the track boundaries of the next avd_audio_features call; one-shot) belong to the
- * audio analyzer and are described at avd_audio_features.
+ * audio analyzer and are described at avd_audio_features, as are "audio_rate" (0, or the decoder's rate of the frames handed over: they are converted
+ * to 16 kHz mono int16 on the device first; durable) and "audio_channels" (1 or 2 interleaved samples per frame of such a call; durable).
  * avd_get_option returns the value an option has now (environment defaults included) and the read-only "rerun_pairs" and "stream_frames". */
 int avd_set_option(avd_ctx* ctx, const char* name, int value);
 int avd_get_option(avd_ctx* ctx, const char* name, int* value);
@@ -678,7 +717,8 @@ int avd_kernel_ms(avd_ctx* ctx, int kernel_id, float* ms);
  * "audio_mag" double[nwin][win / 2 + 1]: the magnitudes |rfft| + 1e-9 its sums were taken over (a short last window: its first last / 2 + 1
  * entries).  Both are an error before any such call and after avd_release_workspace.  A call of several tracks (option "audio_cut"): nwin and
  * nfull count the windows of all tracks, last is the last track's, the rows are the call's windows track after track; "audio_tracks" int32[tracks][3]
- * and "audio_host" int32[2] are described at avd_audio_features.
+ * and "audio_host" int32[2] are described at avd_audio_features, as are the converter's "audio_rs_plan" int32[8], "audio_rs_taps" int32[U][T],
+ * "audio_rs_tracks" int32[tracks][2] and "audio_pcm" int16[output samples] (option "audio_rate").
  * "stream_state" int32[8][2], host state: for each stream slot 1 ... 8 the frames it has absorbed since it was last emptied and the clip position
  * option "stream_map" maps to it (-1: none).
  * "stream_call" int32[4], host state, of the last avd_analyze_* call that brought frames: the clips that continued a FILLED slot, the launches that restored
