@@ -7,7 +7,10 @@ kernels behind the C-ABI (``avd_audio_features``); there is no CPU fallback for 
 
 ``AVD_AUDIO_RESAMPLE=1``: a PCM ``.wav`` at one of the converter's rates (``avd_hip.audio.RESAMPLE_RATES``) is read as it is, every channel, and
 what the reference's ffmpeg line does (downmix, 16 kHz, 16 bit) happens on the device (``analyze_decoded``); no ffmpeg runs.  Any other file takes
-the usual way.  Unset, nothing changes."""
+the usual way.  Unset, nothing changes.
+
+``AVD_AUDIO_CHUNK=<frames>`` (read only with ``AVD_AUDIO_RESAMPLE=1``): such a file is read with ``readframes(<frames>)`` in a loop and continued on the
+device in an audio slot (``analyze_decoded_chunks``): the result of the whole-file read, in memory bounded by one piece.  Unset, nothing changes."""
 from __future__ import annotations
 
 import os
@@ -25,9 +28,33 @@ def _read_decoded(path: str):
     return (frames, sr) if sr in _audio.RESAMPLE_RATES and frames.shape[1] in (1, 2) and len(frames) else None
 
 
+def _chunk_frames() -> int:
+    """AVD_AUDIO_CHUNK: frames per readframes() of the AVD_AUDIO_RESAMPLE path; unset, empty, not a number or below 1: the file is read whole"""
+    try:
+        return max(0, int(os.getenv("AVD_AUDIO_CHUNK", "0") or 0))
+    except ValueError:
+        return 0
+
+
+def _chunked_rate(path: str):
+    """-> the rate of a PCM .wav the converter takes in pieces (the same files _read_decoded accepts), else None"""
+    try:
+        nch, width, sr, n = _audio.wav_info(path)
+    except Exception:          # noqa: BLE001 -- not a PCM .wav: ffmpeg's job
+        return None
+    return sr if sr in _audio.RESAMPLE_RATES and nch in (1, 2) and width in (1, 2, 4) and n else None
+
+
 def analyze(path: str, meta: dict):
     try:
-        if os.getenv("AVD_AUDIO_RESAMPLE", "0") == "1":
+        resample = os.getenv("AVD_AUDIO_RESAMPLE", "0") == "1"
+        chunk = _chunk_frames() if resample else 0
+        rate = _chunked_rate(path) if chunk else None
+        if rate:
+            # the bounded-memory decode loop: read -> analyze -> drop, the track continued on the device in an audio slot
+            with _analyzer.default_pool().borrow(int(os.getenv("AVD_DEVICE", "0"))) as ctx:
+                return _audio.analyze_decoded_chunks(_audio.read_wav_chunks(path, chunk), rate, ctx)
+        if resample:
             decoded = _read_decoded(path)
             if decoded is not None:
                 with _analyzer.default_pool().borrow(int(os.getenv("AVD_DEVICE", "0"))) as ctx:

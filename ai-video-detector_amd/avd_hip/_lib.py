@@ -904,9 +904,9 @@ class Context:
         g = math.gcd(int(rate), cls.AUDIO_OUT_RATE)
         return -(-int(n) * (cls.AUDIO_OUT_RATE // g) // (int(rate) // g))
 
-    def _audio_call(self, ptr, mem, n: int, win: int, nwin: int, pcm16: bool, cuts=(), rate=None, channels: int = 1) -> np.ndarray:
+    def _audio_call(self, ptr, mem, n: int, win: int, nwin: int, pcm16: bool, cuts=(), rate=None, channels: int = 1, last: bool = False) -> np.ndarray:
         """One avd_audio_features call: option "audio_format" -- and, for a track at its decoder's rate, "audio_rate" and "audio_channels" -- set for
-        it and restored (also after an exception), its cuts set in ascending order."""
+        it and restored (also after an exception), its cuts set in ascending order.  last: option "audio_end" is set for it (a slot call)."""
         out = np.zeros(nwin, AUDIO_WINDOW_DTYPE)
         if rate is not None:
             # a refused value leaves the options as they were: nothing has been set yet
@@ -914,7 +914,7 @@ class Context:
             self.set_option("audio_rate", int(rate))
             try:
                 self.set_option("audio_channels", int(channels))
-                return self._audio_call(ptr, mem, n, win, nwin, pcm16, cuts)
+                return self._audio_call(ptr, mem, n, win, nwin, pcm16, cuts, None, 1, last)
             finally:
                 self.set_option("audio_rate", was[0])
                 self.set_option("audio_channels", was[1])
@@ -929,6 +929,8 @@ class Context:
             except Exception:
                 self.set_option("audio_cut", -1)
                 raise
+            if last:
+                self.set_option("audio_end", 1)
             self._check(self._L.avd_audio_features(self._h, ptr, mem, n, int(win), out.ctypes.data, nwin))
         finally:
             if before != want:
@@ -947,13 +949,70 @@ class Context:
             raise ValueError("wav does not hold whole frames of %d channels" % channels)
         return wav, channels
 
-    def audio_features(self, wav, win: int, rate=None, channels: int = 1) -> np.ndarray:
+    AUDIO_SLOTS = 8
+
+    @classmethod
+    def audio_ratio(cls, rate):
+        """-> (U, D, T) of the conversion rule (include/avd.h); rate None or 0 -- a track that is not converted -- is (1, 1, 0)"""
+        if not rate:
+            return 1, 1, 0
+        g = math.gcd(int(rate), cls.AUDIO_OUT_RATE)
+        U, D = cls.AUDIO_OUT_RATE // g, int(rate) // g
+        if int(rate) == cls.AUDIO_OUT_RATE:
+            return U, D, 0
+        return U, D, 2 * math.ceil(16 / min(1.0, 0.97 * U / D))
+
+    @classmethod
+    def audio_outputs_after(cls, frames: int, rate, last: bool = False) -> int:
+        """M of the audio slots' rule: the outputs that exist once a slot has absorbed ``frames`` frames -- ceil(max(0, N - T/2) U / D), and
+        ceil(N U / D) after the last call"""
+        U, D, T = cls.audio_ratio(rate)
+        usable = int(frames) if last else max(0, int(frames) - T // 2)
+        return -(-usable * U // D)
+
+    def _audio_slot_features(self, wav, win: int, rate, channels: int, slot: int, last: bool) -> np.ndarray:
+        """audio_features with a slot: option "audio_slot" set for the call and restored, also after an exception"""
+        pcm16 = self._is_pcm16(wav)
+        if rate is not None:
+            wav, channels = self._audio_frames(wav, channels)
+        else:
+            channels = 1
+        ptr, mem, size, keep = self._audio_ptr(wav, pcm16)
+        n = size // channels
+        was = self.get_option("audio_slot")
+        self.set_option("audio_slot", int(slot))          # a refused value leaves the option as it was
+        try:
+            # the record array, from the rule: W_after - W_before.  A slot past 2^31 - 1 frames reads back saturated; then an upper bound serves
+            # (a written record has length >= 1, the array starts as zeros)
+            frames, held = self.get_option("audio_slot_frames"), self.get_option("audio_slot_held")
+            exact = frames < 0x7fffffff and 1 <= win <= 8192 and (rate is None or rate in self.AUDIO_RATES)
+            if exact:
+                fresh = self.audio_outputs_after(frames + n, rate, last) - self.audio_outputs_after(frames, rate)
+                nwin = -(-(held + fresh) // win) if last else (held + fresh) // win
+            elif 1 <= win <= 8192 and (rate is None or rate in self.AUDIO_RATES):
+                U, D, T = self.audio_ratio(rate)
+                nwin = (held + -(-(n + T) * U // D) + 1) // win + 1
+            else:
+                nwin = 0                                   # the library refuses (AvdError)
+            rec = self._audio_call(ptr, mem, n, win, nwin, pcm16, (), rate, channels, last)
+            return rec if exact else rec[:int(np.count_nonzero(rec["length"]))]
+        finally:
+            self.set_option("audio_slot", was)
+
+    def audio_features(self, wav, win: int, rate=None, channels: int = 1, slot: int = 0, last: bool = False) -> np.ndarray:
         """wav: mono samples, float32 or 16-bit PCM as decoded (int16: sample s counts as float32(s) * 2^-15, converted on the device), numpy or
         torch-ROCm tensor -> structured array (AUDIO_WINDOW_DTYPE) per window.
 
         rate (one of AUDIO_RATES): wav is a track as its decoder produced it -- frames at ``rate``, [n] / [n, 1] mono or [n, 2] / flat with
         channels = 2 interleaved stereo -- and is downmixed, resampled to 16 kHz and narrowed to 16 bit on the device first (options "audio_rate" /
-        "audio_channels", set for this call and restored); win and the records refer to the 16 kHz output."""
+        "audio_channels", set for this call and restored); win and the records refer to the 16 kHz output.
+
+        slot (1 ... AUDIO_SLOTS): the call CONTINUES the track of that audio slot (option "audio_slot", set for this call and restored, also after
+        an exception) and returns the records of the windows this call completes -- possibly none; last=True marks the track's final call
+        (option "audio_end"), which hands out the short last window and empties the slot.  wav may be empty.  The concatenated results of a
+        track's calls are byte for byte the result of one slot-0 call on the joined samples."""
+        if slot:
+            return self._audio_slot_features(wav, int(win), rate, channels, slot, bool(last))
         pcm16 = self._is_pcm16(wav)
         if rate is None:
             ptr, mem, n, keep = self._audio_ptr(wav, pcm16)
@@ -1060,7 +1119,8 @@ class Context:
 
     def audio_pcm(self) -> np.ndarray:
         """int16[output samples]: the converted tracks of that call, side by side -- what the analyzer ran over; avd_debug_fetch "audio_pcm"."""
-        return self.debug_fetch("audio_pcm", (self.audio_resample_plan()[7],), np.int16)
+        n = self.audio_resample_plan()[7]                   # a slot call: its new outputs only, possibly none
+        return self.debug_fetch("audio_pcm", (n,), np.int16) if n else np.zeros(0, np.int16)
 
     def audio_plan(self):
         """(nwin, win, last, nfull) of the last audio_features call: windows, window length, length of the last window, windows that

@@ -59,6 +59,11 @@ def read_wav_frames(path: str):
     with wave.open(path, "rb") as w:
         nch, width, sr, n = w.getnchannels(), w.getsampwidth(), w.getframerate(), w.getnframes()
         raw = w.readframes(n)
+    return _frames_of(raw, width, nch), int(sr)
+
+
+def _frames_of(raw: bytes, width: int, nch: int) -> np.ndarray:
+    """the bytes readframes() returned as [n, channels]: int16 for a 16-bit file, float32 scaled like read_wav_pcm for 8 / 32 bit"""
     if width == 2:
         a = np.frombuffer(raw, "<i2").astype(np.int16, copy=False)
     elif width == 4:
@@ -67,7 +72,25 @@ def read_wav_frames(path: str):
         a = (np.frombuffer(raw, np.uint8).astype(np.float32) - np.float32(128.0)) / np.float32(128.0)
     else:
         raise RuntimeError("soundfile_read_failed")
-    return np.ascontiguousarray(a.reshape(-1, nch)), int(sr)
+    return np.ascontiguousarray(a.reshape(-1, nch))
+
+
+def wav_info(path: str):
+    """-> (channels, bytes per sample, rate, frames) of a PCM .wav"""
+    with wave.open(path, "rb") as w:
+        return w.getnchannels(), w.getsampwidth(), w.getframerate(), w.getnframes()
+
+
+def read_wav_chunks(path: str, chunk: int):
+    """read_wav_frames in pieces: yields [<= chunk, channels] arrays read with readframes(chunk) -- what analyze_decoded_chunks takes, which
+    holds a piece back until its successor shows that it was not the last: two pieces of the file are in host memory at most, never the file."""
+    with wave.open(path, "rb") as w:
+        nch, width = w.getnchannels(), w.getsampwidth()
+        while True:
+            raw = w.readframes(int(chunk))
+            if not raw:
+                return
+            yield _frames_of(raw, width, nch)
 
 
 def extract_wav_16k(path: str, native: bool = False):
@@ -216,3 +239,40 @@ def analyze_decoded_many(waves, ctx) -> list:
         for i, rec in zip(members, recs):
             results[i] = features_to_result(window_values(rec), _converted_duration(len(waves[i][0]), sr, ctx))
     return results
+
+
+def _chunk_records(chunks, ctx, slot: int, prepare, win: int, rate=None):
+    """The decode loop read -> analyze -> drop: every chunk goes to the device once, as it comes, and only the LAST one is marked as the end of
+    the track (so a chunk is held until its successor shows that it was not the last).  -> (records of the whole track, frames seen)"""
+    recs, frames, held = [], 0, None
+    ctx.set_option("audio_slot_reset", int(slot))            # the helper owns the slot for the length of the track
+    try:
+        for chunk in chunks:
+            chunk = prepare(chunk)
+            if held is not None:
+                recs.append(ctx.audio_features(held, win, rate=rate, slot=slot))
+                frames += len(held)
+            held = chunk
+        if held is not None:
+            recs.append(ctx.audio_features(held, win, rate=rate, slot=slot, last=True))
+            frames += len(held)
+    except BaseException:
+        ctx.set_option("audio_slot_reset", int(slot))        # half a track is of no use to the next one
+        raise
+    if not recs:
+        return ctx.audio_features(np.zeros(0, np.float32), win), 0
+    return np.concatenate(recs), frames
+
+
+def analyze_wave_chunks(chunks, sr: int, ctx, slot: int = 1) -> dict:
+    """analyze_wave for a 16 kHz track that arrives in pieces: an iterator of [n] or [n, c] arrays (one sample type throughout), continued on
+    the device in audio slot ``slot`` (Context.audio_features, slot=...).  -> what analyze_wave gives for the concatenation, in bounded memory."""
+    rec, n = _chunk_records(chunks, ctx, slot, _mono, _win_of(sr))
+    return features_to_result(window_values(rec), n / sr if sr > 0 else 0.0)
+
+
+def analyze_decoded_chunks(chunks, sr: int, ctx, slot: int = 1) -> dict:
+    """analyze_decoded for a track that arrives as its decoder's packets: an iterator of [n] or [n, c] arrays at rate ``sr`` (one channel count and
+    one sample type throughout).  -> what analyze_decoded gives for the concatenation; the duration is ceil(N U / D) / 16000 of the N frames seen."""
+    rec, n = _chunk_records(chunks, ctx, slot, _decoded, _win_of(SAMPLE_RATE), int(sr))
+    return features_to_result(window_values(rec), _converted_duration(n, int(sr), ctx))

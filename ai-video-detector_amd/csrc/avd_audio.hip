@@ -243,6 +243,9 @@ __global__ __launch_bounds__(256) void k_audio_reduce(const double* __restrict__
 //  * lane l forms outputs l, l + 256, ...: consecutive lanes read LDS D / U frames apart (three halfwords at 48 kHz, where the bank row is the
 //    same for all lanes and broadcasts; at 44.1 kHz the gathered rows are 92 halfwords long, an odd number of banks apart);
 //  * the results leave as 16-byte rows of the converted buffer; the row a tile shares with its neighbour is written entry by entry.
+// A continued track (option "audio_slot", avd_audio_stream.h) has a two-part source: tiles carry positions relative to the TRACK, `wav` holds its
+// frames from `chunk0` on, and the hist_n frames below chunk0 come from the slot's history -- mono int16 already, so they go straight into
+// mono[].  Both extents are the same for every lane of the workgroup.  A whole track is chunk0 = 0 with no history.
 using avd_resample::Tile;
 
 // step 1 of the rule: int16 is itself; float32 x is clamp(rint(x * 32768), -32768, 32767), ties to even, NaN -> 0
@@ -255,7 +258,8 @@ __device__ __forceinline__ int narrow_sample(float x)
 
 template <typename S, typename Q, typename Acc>
 __global__ __launch_bounds__(256) void k_audio_resample(const S* __restrict__ wav, const Tile* __restrict__ tiles, const int* __restrict__ taps, int U, int D,
-                                                       int T, int channels, int samples_at, int mono_at, int res_at, int16_t* __restrict__ pcm)
+                                                       int T, int channels, int samples_at, int mono_at, int res_at, int16_t* __restrict__ pcm,
+                                                       long long chunk0, const int16_t* __restrict__ hist, int hist_n)
 {
     extern __shared__ __align__(16) unsigned char rs_lds[];
     Q* q = reinterpret_cast<Q*>(rs_lds);
@@ -266,9 +270,11 @@ __global__ __launch_bounds__(256) void k_audio_resample(const S* __restrict__ wa
     const int tid = threadIdx.x;
     for (int i = tid; i < U * T; i += 256) q[i] = (Q)taps[i];
     const int span = T == 0 ? t.count : (t.phase + (t.count - 1) * D) / U + T;
-    // the span's frames that exist: [f_lo, f_hi) of the track; samples [s0, s1) of the buffer
-    const long long f_lo = t.in0 > t.begin ? t.in0 : t.begin, f_hi = t.in0 + span < t.end ? t.in0 + span : t.end;
-    const long long s0 = f_lo * channels, s1 = f_hi * channels;
+    // the span's frames that `wav` holds: [f_lo, f_hi) of the track; samples [s0, s1) of the buffer
+    const long long f_min = t.begin > chunk0 ? t.begin : chunk0;
+    const long long f_lo = t.in0 > f_min ? t.in0 : f_min, f_hi = t.in0 + span < t.end ? t.in0 + span : t.end;
+    const long long s0 = (f_lo - chunk0) * channels, s1 = (f_hi - chunk0) * channels;
+    const long long h_lo = chunk0 - hist_n;                 // the history holds frames [h_lo, chunk0)
     constexpr int per = 16 / (int)sizeof(S);                // samples in a 16-byte line
     const int lead = (int)((reinterpret_cast<uintptr_t>(wav + s0) & 15) / sizeof(S));   // smp[0] is the sample at the line boundary at or below s0
     const int lines = s1 > s0 ? (lead + (int)(s1 - s0) + per - 1) / per : 0;
@@ -302,6 +308,8 @@ __global__ __launch_bounds__(256) void k_audio_resample(const S* __restrict__ wa
         if (f >= f_lo && f < f_hi) {
             const int at = lead + (int)(f - f_lo) * channels;
             m = channels == 2 ? ((int)smp[at] + (int)smp[at + 1] + 1) >> 1 : (int)smp[at];
+        } else if (f >= h_lo && f < chunk0) {
+            m = hist[f - h_lo];
         }
         mono[i] = (int16_t)m;
     }
@@ -334,26 +342,82 @@ __global__ __launch_bounds__(256) void k_audio_resample(const S* __restrict__ wa
 }
 
 template <typename S, typename Q, typename Acc>
-int launch_resample_as(avd_ctx* ctx, const void* d_in, const Tile* tiles, const int* taps, int ntiles, const avd_resample::Ratio& r, int channels, int16_t* d_pcm)
+int launch_resample_as(avd_ctx* ctx, const void* d_in, const Tile* tiles, const int* taps, int ntiles, const avd_resample::Ratio& r, int channels, int16_t* d_pcm,
+                       const AudioSource& src)
 {
     const size_t at_s = avd_resample::lds_taps_bytes(r), at_m = at_s + avd_resample::lds_samples_bytes(r, channels), at_r = at_m + avd_resample::lds_mono_bytes(r);
     const size_t lds = avd_resample::lds_bytes(r, channels);
     // per call (a function attribute belongs to the current device; a process may hold contexts on several)
     HIP_TRY(ctx, hipFuncSetAttribute((const void*)k_audio_resample<S, Q, Acc>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL((k_audio_resample<S, Q, Acc>), dim3(ntiles), dim3(256), lds, ctx->stream, static_cast<const S*>(d_in), tiles, taps, r.U, r.D, r.T, channels,
-                       (int)at_s, (int)at_m, (int)at_r, d_pcm);
+                       (int)at_s, (int)at_m, (int)at_r, d_pcm, src.chunk0, src.hist, src.hist_n);
     return 0;
+}
+
+// ---- what a call leaves in its audio slot (option "audio_slot"): ONE launch, one workgroup --------------------------------------------------
+//  * the new history: the track's last hist_new_n frames, narrowed and downmixed exactly as k_audio_resample does it -- frame r of the call's n
+//    (r >= 0) from `wav`, frame r < 0 from the old history, which a chunk shorter than T - 1 shifts.  Old and new history are two buffers
+//    (the slot alternates), so no lane reads what another writes; hist_new_n <= n + hist_old_n by the rule.
+//  * the new held remainder: held_words 16-bit words of the analyzer's buffer behind its last window (a float32 sample is two of them).
+template <typename S>
+__global__ __launch_bounds__(256) void k_audio_slot_save(const S* __restrict__ wav, long long n, int channels, const int16_t* __restrict__ hist_old, int hist_old_n,
+                                                        int16_t* __restrict__ hist_new, int hist_new_n, const int16_t* __restrict__ held_src,
+                                                        int16_t* __restrict__ held_dst, int held_words)
+{
+    const int tid = threadIdx.x;
+    for (int i = tid; i < hist_new_n; i += 256) {
+        const long long r = n - hist_new_n + i;
+        int m;
+        if (r >= 0) m = channels == 2 ? (narrow_sample(wav[2 * r]) + narrow_sample(wav[2 * r + 1]) + 1) >> 1 : narrow_sample(wav[r]);
+        else m = hist_old[hist_old_n + r];
+        hist_new[i] = (int16_t)m;
+    }
+    for (int i = tid; i < held_words; i += 256) held_dst[i] = held_src[i];
 }
 
 }  // namespace
 
-int launch_audio_resample(avd_ctx* ctx, const void* d_in, int format, int channels, const avd_resample::Plan& plan, int16_t* d_pcm)
+int launch_audio_slot_save(avd_ctx* ctx, const void* d_in, int format, long long n, int channels, const int16_t* hist_old, int hist_old_n, int16_t* hist_new,
+                           int hist_new_n, const void* held_src, int16_t* held_dst, int held_words, bool* enqueued)
+{
+    if (hist_new_n < 0 || hist_new_n > avd_resample::kMaxHistory || hist_new_n > n + hist_old_n || held_words < 0 || held_words > kAudioSlotHeldWords) {
+        ctx->err = "audio_slot: internal error (save extents)";
+        return AVD_ERR_DEVICE;
+    }
+    if (format == 1)
+        hipLaunchKernelGGL(k_audio_slot_save<int16_t>, dim3(1), dim3(256), 0, ctx->stream, static_cast<const int16_t*>(d_in), n, channels, hist_old, hist_old_n,
+                           hist_new, hist_new_n, static_cast<const int16_t*>(held_src), held_dst, held_words);
+    else
+        hipLaunchKernelGGL(k_audio_slot_save<float>, dim3(1), dim3(256), 0, ctx->stream, static_cast<const float*>(d_in), n, channels, hist_old, hist_old_n,
+                           hist_new, hist_new_n, static_cast<const int16_t*>(held_src), held_dst, held_words);
+    *enqueued = true;                                        // from here on the slot's memory may have been written
+    HIP_TRY(ctx, hipGetLastError());
+    return 0;
+}
+
+// debug buffers "audio_rs_*" / "audio_pcm": what the converter of this call ran over
+static void record_resample_plan(avd_ctx* ctx, const avd_resample::Plan& plan, int channels)
+{
+    const avd_resample::Ratio& r = plan.r;
+    const int rs_plan[8] = {r.rate, channels, r.U, r.D, r.T, plan.tile_out, (int)std::min<long long>(plan.n_in, 0x7fffffff), (int)plan.n_out};
+    std::memcpy(ctx->audio_rs_plan, rs_plan, sizeof rs_plan);
+    ctx->audio_rs_ntracks = (int)plan.tracks.size();
+    std::memcpy(ctx->audio_rs_tracks, plan.tracks.data(), sizeof(avd_resample::Track) * plan.tracks.size());
+    ctx->audio_rs_pcm_at = plan.tracks.empty() ? 0 : plan.tracks[0].first;   // above 0 only behind a slot's held samples
+    ctx->audio_rs_valid = 1;
+}
+
+int launch_audio_resample(avd_ctx* ctx, const void* d_in, int format, int channels, const avd_resample::Plan& plan, int16_t* d_pcm, const AudioSource& src)
 {
     const avd_resample::Ratio& r = plan.r;
     const int ntiles = (int)plan.tiles.size(), bank = r.U * r.T, idx = avd_resample::rate_index(r.rate);
-    if (ntiles <= 0 || idx < 0) return 0;
+    if (idx < 0 || (ntiles <= 0 && plan.tracks.empty())) return 0;
     Workspace& ws = ctx->ws;
     ctx->audio_rs_valid = 0;
+    if (ntiles <= 0) {                                       // a continued track's call that forms no output: recorded as such, nothing launched
+        record_resample_plan(ctx, plan, channels);
+        return 0;
+    }
     if (ws.audio_rs_upload_pending) { HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); ws.audio_rs_upload_pending = 0; }
     std::vector<int>& taps = ctx->audio_rs_bank[idx];
     if (taps.empty() && bank) taps = avd_resample::build_taps(r);       // once per rate and context
@@ -378,18 +442,14 @@ int launch_audio_resample(avd_ctx* ctx, const void* d_in, int format, int channe
     const int* d_taps = ws.d_audio_rs_taps;                  // null at rate 16000 before any other rate ran: T = 0 reads none
     int e;
     if (avd_resample::wide(r))
-        e = format == 1 ? launch_resample_as<int16_t, int, long long>(ctx, d_in, tiles, d_taps, ntiles, r, channels, d_pcm)
-                        : launch_resample_as<float, int, long long>(ctx, d_in, tiles, d_taps, ntiles, r, channels, d_pcm);
+        e = format == 1 ? launch_resample_as<int16_t, int, long long>(ctx, d_in, tiles, d_taps, ntiles, r, channels, d_pcm, src)
+                        : launch_resample_as<float, int, long long>(ctx, d_in, tiles, d_taps, ntiles, r, channels, d_pcm, src);
     else
-        e = format == 1 ? launch_resample_as<int16_t, int16_t, int>(ctx, d_in, tiles, d_taps, ntiles, r, channels, d_pcm)
-                        : launch_resample_as<float, int16_t, int>(ctx, d_in, tiles, d_taps, ntiles, r, channels, d_pcm);
+        e = format == 1 ? launch_resample_as<int16_t, int16_t, int>(ctx, d_in, tiles, d_taps, ntiles, r, channels, d_pcm, src)
+                        : launch_resample_as<float, int16_t, int>(ctx, d_in, tiles, d_taps, ntiles, r, channels, d_pcm, src);
     if (e) return e;
     HIP_TRY(ctx, hipGetLastError());
-    const int rs_plan[8] = {r.rate, channels, r.U, r.D, r.T, plan.tile_out, (int)std::min<long long>(plan.n_in, 0x7fffffff), (int)plan.n_out};
-    std::memcpy(ctx->audio_rs_plan, rs_plan, sizeof rs_plan);
-    ctx->audio_rs_ntracks = (int)plan.tracks.size();
-    std::memcpy(ctx->audio_rs_tracks, plan.tracks.data(), sizeof(avd_resample::Track) * plan.tracks.size());
-    ctx->audio_rs_valid = 1;
+    record_resample_plan(ctx, plan, channels);
     return 0;
 }
 

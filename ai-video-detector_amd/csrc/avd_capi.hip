@@ -491,6 +491,28 @@ static int audio_cut_read(const avd_ctx* ctx) { return ctx->audio_ncuts; }
 static bool opt_audio_rate(int& v) { return v == 0 || avd_resample::rate_index(v) >= 0; }
 // "audio_channels": interleaved samples per frame of a converted call, 1 or 2; durable
 static bool opt_audio_channels(int& v) { return v == 1 || v == 2; }
+// "audio_slot": 0 every avd_audio_features call is a whole track, k = 1 ... 8 it continues the track of audio slot k; durable.  The audio slots are
+// apart from the video stream slots: neither family of options touches the other's.
+static bool opt_audio_slot(int& v) { return v >= 0 && v <= kAudioSlots; }
+// "audio_end": one-shot, the next avd_audio_features call carries the last samples of its slot's track; the call takes it (avd_audio_features)
+static bool opt_audio_end(int& v) { return v == 1; }
+static void audio_end_set(avd_ctx* ctx, int) { ctx->audio_end = 1; }
+static int audio_end_read(const avd_ctx* ctx) { return ctx->audio_end; }
+// "audio_slot_reset": k empties audio slot k, 0 all of them (the memory stays); it reads back as 0.  avd_set_option has drained the context.
+static void audio_slot_reset(avd_ctx* ctx, int v)
+{
+    for (int k = 1; k <= kAudioSlots; k++)
+        if (v == 0 || v == k) ctx->audio_slots[k - 1].clear();
+}
+static int audio_slot_reset_read(const avd_ctx*) { return 0; }
+// read-only, of the SELECTED slot; an empty slot (frames = 0) reads 0 everywhere
+static const AudioSlot* audio_slot_selected(const avd_ctx* ctx)
+{
+    return ctx->audio_slot && ctx->audio_slots[ctx->audio_slot - 1].frames > 0 ? &ctx->audio_slots[ctx->audio_slot - 1] : nullptr;
+}
+static int audio_slot_frames(const avd_ctx* ctx) { const AudioSlot* s = audio_slot_selected(ctx); return s ? (int)std::min<long long>(s->frames, 0x7fffffff) : 0; }
+static int audio_slot_held(const avd_ctx* ctx) { const AudioSlot* s = audio_slot_selected(ctx); return s ? s->held : 0; }
+static int audio_slot_windows(const avd_ctx* ctx) { const AudioSlot* s = audio_slot_selected(ctx); return s ? s->windows : 0; }
 // "ingest_group": 0 a launch pair per clip, 1 one per group of clips that share a key (avd_ingest_group.h); durable
 static bool opt_ingest_group(int& v) { return v == 0 || v == 1; }
 // "cv2_model": any combination of the bits 1, 8 and 16 (the oracle's jitter switches 2 and 4 model nothing a library can follow); durable
@@ -522,6 +544,12 @@ static const Option kOptions[] = {
     {"audio_cut", nullptr, true, opt_any, nullptr, nullptr, nullptr, audio_cut_set, audio_cut_read, audio_cut_check},
     {"audio_rate", &avd_ctx::audio_rate, true, opt_audio_rate, nullptr, nullptr, "audio_rate: 0 (samples at 16 kHz already) or 8000, 11025, 12000, 16000, 22050, 24000, 32000, 44100, 48000, 88200, 96000, 176400, 192000"},
     {"audio_channels", &avd_ctx::audio_channels, true, opt_audio_channels, nullptr, nullptr, "audio_channels: 1 or 2 interleaved samples per frame (downmix other layouts first)"},
+    {"audio_slot", &avd_ctx::audio_slot, true, opt_audio_slot, nullptr, nullptr, "audio_slot: 0 (every call is a whole track) or audio slot 1 ... 8"},
+    {"audio_end", nullptr, true, opt_audio_end, nullptr, nullptr, "audio_end: 1 (the next avd_audio_features call carries the last samples of its slot's track)", audio_end_set, audio_end_read},
+    {"audio_slot_reset", nullptr, true, opt_audio_slot, nullptr, nullptr, "audio_slot_reset: 0 (every audio slot) or audio slot 1 ... 8", audio_slot_reset, audio_slot_reset_read},
+    {"audio_slot_frames", nullptr, false, opt_any, nullptr, nullptr, nullptr, nullptr, audio_slot_frames},
+    {"audio_slot_held", nullptr, false, opt_any, nullptr, nullptr, nullptr, nullptr, audio_slot_held},
+    {"audio_slot_windows", nullptr, false, opt_any, nullptr, nullptr, nullptr, nullptr, audio_slot_windows},
     {"ingest_group", &avd_ctx::ingest_group, true, opt_ingest_group, nullptr, nullptr, "ingest_group: 0 (an ingest and a hash launch per clip) or 1 (one of each per group of clips that share a key)"},
     {"cv2_model", &avd_ctx::cv2_model, true, opt_cv2_model, "AVD_CV2_MODEL", env_any_base, "cv2_model: a combination of 1 (GAUSS_MULADD), 8 (THREE_SCALES) and 16 (RESIZE_LERP), or 0 (the default model)"},
 };
@@ -582,6 +610,7 @@ static void impl_destroy(avd_ctx* ctx)
     ctx->ws = Workspace{};
     ctx->weights = Weights{};
     for (StreamSlot& s : ctx->streams) s.d_prev.reset();
+    for (AudioSlot& s : ctx->audio_slots) s.d_mem.reset();
     ctx->d_fbc.reset();
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
     if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
@@ -1242,7 +1271,7 @@ static int64_t impl_debug_fetch(avd_ctx* ctx, const char* name, void* out, size_
             if (have) std::memcpy(out, from, have);
             return (int64_t)have;
         }
-        src = ws.d_audio_pcm.p;                          // null after avd_release_workspace: "buffer not allocated yet" below
+        src = ws.d_audio_pcm.p ? ws.d_audio_pcm.p + ctx->audio_rs_pcm_at : nullptr;   // null after avd_release_workspace: "buffer not allocated yet" below
         bytes = sizeof(int16_t) * (size_t)rp[7];
     }
     else if (std::strncmp(name, "audio_", 6) == 0) {   // the last avd_audio_features of this context: its window plan (host state) and its two scratch arrays
@@ -1535,11 +1564,116 @@ static int convert_audio_features(avd_ctx* ctx, const void* wav, int mem, int64_
     return AVD_OK;
 }
 
-// cuts / ncuts: the "audio_cut" list the call took from the context (avd_audio_features: one-shot, whatever becomes of the call)
-static int impl_audio_features(avd_ctx* ctx, const void* wav, int mem, int64_t n, int win, avd_audio_window* windows, int max_windows, const int* cuts, int ncuts)
+// Option "audio_slot" != 0: the call continues the track of an audio slot (avd_audio_stream.h plans it; include/avd.h states the rule).  The
+// analyzer's buffer is ws.d_audio_pcm, laid out [held | new]: the slot's held samples are copied in front, the converter writes the new outputs
+// behind them (an unconverted track: the call's samples are copied there, in their own type), the analyzer runs over whole windows of it with its
+// kernels as they are, and ONE save launch leaves the new history and the new held remainder in the slot.  Everything is ordered on the context's
+// stream; the host state of the slot changes only once the call has drained.  *saved: the save launch was enqueued -- a failure from there on
+// has left the slot's memory in an unknown state.
+static int run_audio_slot(avd_ctx* ctx, AudioSlot& slot, const avd_resample::Continue& c, const avd_resample::Ratio& ratio, const void* wav, int mem, int64_t n,
+                          int win, avd_audio_window* windows, int max_windows, bool last, bool* saved)
+{
+    const int format = ctx->audio_format, channels = ratio.rate ? ctx->audio_channels : 1;
+    const bool converted = ratio.rate != 0;
+    const size_t in_size = format == 1 ? sizeof(int16_t) : sizeof(float), an_size = converted ? sizeof(int16_t) : in_size;   // bytes per input / analysed sample
+    const int an_format = converted ? 1 : format;
+    const size_t have = (size_t)c.held_before + (size_t)c.fresh();
+    avd_audio::Plan plan;
+    if (c.analysed > 0) {
+        plan = avd_audio::plan_call(c.analysed, win, nullptr, 0, max_windows);
+        if (plan.refused) { ctx->err = "audio_slot: windows array too small"; return AVD_ERR_ARG; }
+    }
+    const int nwin = plan.nwin();
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    Workspace& ws = ctx->ws;
+    if (int e = slot.d_mem.reserve(ctx, kAudioSlotWords)) return e;
+    if (int e = ws.d_audio_pcm.reserve(ctx, have * an_size / sizeof(int16_t) + 8)) return e;
+    if (int e = ws.d_audio_out.reserve(ctx, (size_t)std::max(nwin, 1))) return e;
+    char* buf = reinterpret_cast<char*>(ws.d_audio_pcm.p);
+    const uint8_t* d_in = reinterpret_cast<const uint8_t*>(slot.d_mem.p);          // n = 0: a valid address nobody reads
+    if (c.held_before) HIP_TRY(ctx, hipMemcpyAsync(buf, slot.held_at(), (size_t)c.held_before * an_size, hipMemcpyDeviceToDevice, ctx->stream));
+    ctx->audio_rs_valid = 0;
+    if (converted) {
+        if (n > 0)
+            if (int e = stage_input(ctx, static_cast<const uint8_t*>(wav), mem, (size_t)n * (size_t)channels * in_size, &d_in)) return e;
+        avd_resample::Plan conv;
+        conv.r = ratio;
+        conv.tile_out = c.tile_out;
+        conv.n_in = n;
+        conv.n_out = c.fresh();
+        conv.tracks.push_back(avd_resample::Track{c.held_before, (int)c.fresh()});
+        conv.tiles = c.tiles;
+        AudioSource src;
+        src.chunk0 = c.n_before;
+        src.hist = slot.hist(slot.hist_side);
+        src.hist_n = c.hist_before;
+        if (int e = launch_audio_resample(ctx, d_in, format, channels, conv, ws.d_audio_pcm, src)) return e;
+    } else if (n > 0) {
+        d_in = reinterpret_cast<const uint8_t*>(buf + (size_t)c.held_before * an_size);
+        HIP_TRY(ctx, hipMemcpyAsync(buf + (size_t)c.held_before * an_size, wav, (size_t)n * in_size, mem == AVD_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, ctx->stream));
+    }
+    if (nwin > 0) {
+        if (int e = launch_audio_features(ctx, buf, an_format, plan, ws.d_audio_out)) return e;
+        HIP_TRY(ctx, hipMemcpyAsync(windows, ws.d_audio_out, sizeof(avd_audio_window) * nwin, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    if (!last) {
+        if (int e = launch_audio_slot_save(ctx, d_in, converted ? format : 1, converted ? n : 0, channels, slot.hist(slot.hist_side), c.hist_before,
+                                           slot.hist(slot.hist_side ^ 1), c.hist_after, buf + (size_t)c.analysed * an_size, slot.held_at(),
+                                           (int)((size_t)c.held_after * an_size / sizeof(int16_t)), saved)) return e;
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    ws.audio_upload_pending = 0;
+    ws.audio_rs_upload_pending = 0;
+    return AVD_OK;
+}
+
+// The checks of a slot call, in the order include/avd.h lists them, all before anything is staged and with the slot untouched; then the call.
+static int slot_audio_features(avd_ctx* ctx, const void* wav, int mem, int64_t n, int win, avd_audio_window* windows, int max_windows, int ncuts, bool last)
+{
+    AudioSlot& slot = ctx->audio_slots[ctx->audio_slot - 1];
+    const int format = ctx->audio_format, rate = ctx->audio_rate, channels = rate ? ctx->audio_channels : 1;
+    if (ncuts > 0) { ctx->err = "audio_slot: one track per call (an \"audio_cut\" list was pending; it is gone)"; return AVD_ERR_ARG; }
+    if (slot.frames > 0 && (slot.win != win || slot.rate != rate || slot.channels != channels || slot.format != format)) {
+        ctx->err = "audio_slot: win, \"audio_rate\", \"audio_channels\" and \"audio_format\" must be those of the slot's first call";
+        return AVD_ERR_ARG;
+    }
+    avd_resample::Ratio ratio = avd_resample::identity_ratio();
+    if (rate != 0 && !avd_resample::ratio_of(rate, ratio)) { ctx->err = "audio_rate: not a supported rate"; return AVD_ERR_ARG; }   // (the option refuses such a value)
+    const avd_resample::Continue c = avd_resample::plan_continue(slot.frames, n, last, ratio, win);
+    if (c.refused) { ctx->err = "audio_slot: more than 2^31 - 1 output samples in the track"; return AVD_ERR_ARG; }
+    if (c.windows > max_windows || (c.windows > 0 && !windows)) { ctx->err = "audio_slot: windows array too small"; return AVD_ERR_ARG; }
+    if (n == 0 && !last) {                                   // nothing to absorb, nothing to flush: the call wrote no record
+        if (slot.frames > 0) slot.windows = 0;
+        return AVD_OK;
+    }
+    bool saved = false;
+    const int e = run_audio_slot(ctx, slot, c, ratio, wav, mem, n, win, windows, max_windows, last, &saved);
+    if (e) {
+        if (saved) { slot.clear(); ctx->err += " (audio_slot: the failure came after the slot's save launch; the slot was emptied)"; }
+        return e;
+    }
+    if (last) { slot.clear(); return AVD_OK; }
+    if (slot.frames == 0) { slot.win = win; slot.rate = rate; slot.channels = channels; slot.format = format; }
+    slot.frames = c.n_after;
+    slot.held = c.held_after;
+    slot.windows = (int)c.windows;
+    slot.hist_side ^= 1;
+    return AVD_OK;
+}
+
+// cuts / ncuts: the "audio_cut" list the call took from the context (avd_audio_features: one-shot, whatever becomes of the call); last: "audio_end" likewise
+static int impl_audio_features(avd_ctx* ctx, const void* wav, int mem, int64_t n, int win, avd_audio_window* windows, int max_windows, const int* cuts, int ncuts,
+                               bool last)
 {
     if (win < 1 || win > 8192) { ctx->err = "audio window must be 1..8192 samples"; return AVD_ERR_ARG; }   // also for n = 0: a bad window is never "nothing to do"
-    if (n < 0 || (n > 0 && (!wav || !windows))) { ctx->err = "bad arguments"; return AVD_ERR_ARG; }
+    // a slot call that completes no window needs no windows array (slot_audio_features asks for one only where records are written)
+    if (n < 0 || (n > 0 && (!wav || (!windows && ctx->audio_slot == 0)))) { ctx->err = "bad arguments"; return AVD_ERR_ARG; }
+    if (ctx->audio_slot != 0) {
+        if (n > 0 && ctx->audio_format == 1 && (reinterpret_cast<uintptr_t>(wav) & 1)) { ctx->err = "audio_format 1: int16 samples need a 2-byte aligned wav"; return AVD_ERR_ARG; }
+        if (n > 0 && ctx->audio_format == 0 && (reinterpret_cast<uintptr_t>(wav) & 3)) { ctx->err = "audio_slot: float32 samples need a 4-byte aligned wav"; return AVD_ERR_ARG; }
+        if (mem != AVD_MEM_HOST && mem != AVD_MEM_DEVICE) { ctx->err = "mem must be AVD_MEM_HOST or AVD_MEM_DEVICE"; return AVD_ERR_ARG; }
+        return slot_audio_features(ctx, wav, mem, n, win, windows, max_windows, ncuts, last);
+    }
     if (n == 0) return AVD_OK;
     const int format = ctx->audio_format;
     if (format == 1 && (reinterpret_cast<uintptr_t>(wav) & 1)) { ctx->err = "audio_format 1: int16 samples need a 2-byte aligned wav"; return AVD_ERR_ARG; }
@@ -1811,8 +1945,10 @@ int avd_audio_features(avd_ctx* ctx, const float* wav, int mem, int64_t n, int w
         const int ncuts = ctx->audio_ncuts;
         std::copy(ctx->audio_cuts, ctx->audio_cuts + ncuts, cuts);
         ctx->audio_ncuts = 0;
+        const bool last = ctx->audio_end != 0;               // "audio_end" goes the same way
+        ctx->audio_end = 0;
         if (int e = drain_pending(ctx)) return e;
-        return impl_audio_features(ctx, wav, mem, n, win, windows, max_windows, cuts, ncuts);
+        return impl_audio_features(ctx, wav, mem, n, win, windows, max_windows, cuts, ncuts, last);
     }, Pending::keep);
 }
 

@@ -11,6 +11,7 @@
 #include "avd_stream_plan.h"      // where the clips of a call lie when some continue a stream slot (host only)
 #include "avd_audio_plan.h"       // the tracks, window table and table arena of one avd_audio_features call (host only)
 #include "avd_audio_resample.h"   // the converter in front of it (option "audio_rate"): ratios, filter bank, output ranges, tile table (host only)
+#include "avd_audio_stream.h"     // a track continued across calls (option "audio_slot"): what one call of it forms, hands out and holds back (host only)
 #include "avd_ingest_group.h"     // which clips of a call share an ingest launch (option "ingest_group"), and kLapSlots (host only)
 
 #define AVD_FB_LEVELS 4            // pyramid scales 1/8,1/4,1/2,1 of 320 (see avd_farneback.hip)
@@ -280,6 +281,28 @@ struct StreamSlot {
     int frames = 0;                  // frames absorbed since the slot was last emptied ("stream_frames")
 };
 
+// An audio slot (option "audio_slot") is state as well: a track continued across avd_audio_features calls.  On the device, in one allocation:
+// two history buffers of kMaxHistory mono int16 frames (the save launch reads one and writes the other; hist_side says which one is current) and
+// the held-back analysis samples, fewer than win, in the track's analysis type (int16, or float32 for an unconverted float track).  frames = 0:
+// the slot is empty, whatever the memory holds.  The values of its first call bind the track (win, rate, channels, format).
+constexpr int kAudioSlots = 8;
+constexpr int kAudioSlotHeldWords = 2 * avd_audio::kMaxWin;          // 16-bit words: kMaxWin - 1 float32 samples at most
+constexpr size_t kAudioSlotHistAt = 0, kAudioSlotHeldAt = 2 * 1024, kAudioSlotWords = kAudioSlotHeldAt + kAudioSlotHeldWords;   // 36 KB
+static_assert(avd_resample::kMaxHistory <= 1024, "a history buffer is 1024 entries");
+struct AudioSlot {
+    DevBuf<int16_t> d_mem;           // [kAudioSlotWords]
+    long long frames = 0;            // input frames absorbed since the slot was last emptied
+    int held = 0;                    // analysis samples held back
+    int windows = 0;                 // records the last call on the slot wrote
+    int hist_side = 0;
+    int win = 0, rate = 0, channels = 0, format = 0;
+    int16_t* hist(int side) { return d_mem.p + kAudioSlotHistAt + 1024 * (size_t)side; }
+    int16_t* held_at() { return d_mem.p + kAudioSlotHeldAt; }
+    void clear() { frames = 0; held = 0; windows = 0; }
+};
+// the two-part source of a continued track's converter launch: `wav` holds the track's frames from chunk0 on, hist its hist_n frames below
+struct AudioSource { long long chunk0 = 0; const int16_t* hist = nullptr; int hist_n = 0; };
+
 struct avd_ctx {
     int device = 0;
     int num_cus = 256;
@@ -361,6 +384,12 @@ struct avd_ctx {
     int audio_rs_valid = 0;         // 0 while the last call that ran did not convert (or none ran)
     int audio_rs_tracks[avd_audio::kMaxTracks][2] = {};   // per track of that call: first output sample, output samples (debug buffer "audio_rs_tracks")
     int audio_rs_ntracks = 0;
+    int audio_rs_pcm_at = 0;        // debug buffer "audio_pcm" begins at this entry of ws.d_audio_pcm (a slot call: behind the held samples)
+    // options "audio_slot" (durable: 0 = every avd_audio_features call is a whole track, k = it continues the track of audio_slots[k - 1]) and
+    // "audio_end" (one-shot like the cut list: the next call carries the track's last samples)
+    AudioSlot audio_slots[kAudioSlots];
+    int audio_slot = 0;
+    int audio_end = 0;
     int cnn_chunk = 128;            // CNN extension: frames per forward pass (activation scratch = 4 x 1.6 MB per frame)
     int cnn_fuse = 2;               // CNN extension: a block's 3x3 and expanding 1x1 in one launch (stages 1, 2): 2 = with the 3x3's input slab in LDS in the stride-1 blocks (k_slab3_expand), 1 = gathering kernels only, 0 = layer by layer
     int fb_fused = 0xF;             // bit k: pyramid level k runs the fused kernel (avd_fbfused.hip) instead of the two-kernel path (avd_fbtwo.hip)
@@ -469,7 +498,11 @@ int comm_allgather_last_records(avd_ctx* ctx, int count, avd_frame_record* all);
 int launch_audio_features(avd_ctx* ctx, const void* d_wav, int format, const avd_audio::Plan& plan, avd_audio_window* d_out);
 // avd_audio.hip: the frames at d_in (format: option "audio_format"; channels interleaved) to the 16 kHz mono int16 tracks of `plan` at d_pcm
 // (device, plan.n_out + 8 entries, 16-byte aligned)
-int launch_audio_resample(avd_ctx* ctx, const void* d_in, int format, int channels, const avd_resample::Plan& plan, int16_t* d_pcm);
+int launch_audio_resample(avd_ctx* ctx, const void* d_in, int format, int channels, const avd_resample::Plan& plan, int16_t* d_pcm, const AudioSource& src = AudioSource{});
+// avd_audio.hip: what a call leaves in its audio slot -- the last hist_new_n frames of the track (from the call's n frames at d_in and the old
+// history) as mono int16, and held_words 16-bit words of the analyzer's buffer.  *enqueued is set once the launch has been made (not by a refusal before it)
+int launch_audio_slot_save(avd_ctx* ctx, const void* d_in, int format, long long n, int channels, const int16_t* hist_old, int hist_old_n, int16_t* hist_new,
+                           int hist_new_n, const void* held_src, int16_t* held_dst, int held_words, bool* enqueued);
 // avd_fbfused.hip: all blur iterations of one pyramid level (w = 40 / 80 / 160 / 320) in one launch, one workgroup per pair
 // zero_first: the initial flow is zero whatever the buffer holds (the coarsest level: no clearing launch)
 // plist (may be null): the launch works on pairs plist[0 .. np)

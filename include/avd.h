@@ -455,6 +455,45 @@ int avd_softmax(avd_ctx* ctx, const float* x, int mem, int64_t rows, int cols, f
  * int32[tracks][2] -- per track its first output sample and its output samples; "audio_pcm" int16[output samples] -- the converted tracks side
  * by side (an error after avd_release_workspace).  "audio_plan", "audio_tracks", "audio_xw" and "audio_mag" then describe the analysis of that output.
  *
+ * A track continued across calls (audio slots).  A decoder hands audio out in packets; four more options let a track arrive in as many
+ * avd_audio_features calls as the caller likes, in bounded memory, with the records of the whole track.  No function is added and AVD_ABI_VERSION
+ * stays 3; with these options at their defaults every call enqueues and returns exactly what it did before they existed.
+ *   "audio_slot" (durable, reads back; default 0): 0 -- every call is a whole track.  k = 1 ... 8 -- an avd_audio_features call continues the
+ *     track of audio slot k.  Any other value is AVD_ERR_ARG with a message that begins "audio_slot:", and the old value stays.  The audio slots
+ *     are apart from the video stream slots: "stream_slot", "stream_map" and "stream_reset" do not touch them, and these options do not touch those.
+ *   "audio_end" (one-shot, for the NEXT avd_audio_features call; the value is 1, any other value is AVD_ERR_ARG with a message that begins
+ *     "audio_end:"; reads back as 0 or 1): that call carries the last samples of its slot's track.  The next avd_audio_features call takes it
+ *     whether it succeeds, is refused or fails, exactly like the "audio_cut" list.  With slot 0 selected it has no effect.
+ *   "audio_slot_reset": k = 1 ... 8 empties audio slot k, 0 empties all eight; reads back as 0.
+ *   Read-only, of the selected slot; all are 0 with slot 0 selected and for an empty slot (so also after an "audio_end" call):
+ *     "audio_slot_frames" -- input frames absorbed, saturated at 2^31 - 1; "audio_slot_held" -- analysis-rate samples held back, fewer than win;
+ *     "audio_slot_windows" -- records the last call on this slot wrote.
+ * The rule.  N is the frames a slot has absorbed, the present call included.  U, D and T belong to the rate as above (T the taps per phase);
+ * with "audio_rate" 0 take U = D = 1 and T = 0.  The outputs that exist after a call that is not the last are
+ *     M(N) = ceil(max(0, N - T/2) U / D)
+ * -- exactly the outputs m whose last tap floor(m D / U) + T/2 lies at or below frame N - 1.  After the last call M = ceil(N U / D), with zeros
+ * beyond the end as in a whole-track call.  The windows handed out so far are W = floor(M / win), and ceil(M / win) after the last call.
+ *   - A call writes records W_before ... W_after - 1 of the track into windows, in order, and needs max_windows >= W_after - W_before.
+ *   - Output samples [W_after win, M) stay on the device, in the slot, as do the last min(N, T - 1) frames, already narrowed and downmixed
+ *     (steps 1 and 2 are per frame, so carrying mono int16 is exact).  A track with "audio_rate" 0 holds its samples in their own type.
+ *   - After an "audio_end" call the slot is empty.
+ *   - n = 0 is allowed: nothing happens without "audio_end" (the call wrote no record: "audio_slot_windows" then reads 0), and the track is
+ *     flushed with it; a null wav is then accepted, as for n = 0 today.  A call that writes no record accepts a null windows.
+ * Guarantee: for any split of a track into calls, the concatenated records are byte for byte the records of ONE slot-0 call on the joined
+ * samples, and the concatenated new outputs (debug buffer "audio_pcm", which after a slot call holds that call's new outputs only) equal that
+ * call's "audio_pcm" -- for float32 and int16 input, every rate, mono and stereo, host and device memory.
+ * Refusals: after the argument and alignment checks above (with a slot selected float32 samples need a 4-byte aligned wav at every rate), all
+ * before anything is staged, the slot untouched, each AVD_ERR_ARG with a message that begins "audio_slot:", in this order: a pending
+ * "audio_cut" list (one track per call); win, "audio_rate", "audio_channels" or "audio_format" other than at the slot's first call; more than
+ * 2^31 - 1 outputs for the track; max_windows too small.
+ * A slot is state, not scratch (36 KB of device memory each, allocated by the slot's first call): it survives avd_release_workspace and every
+ * other call on the context -- slot-0 audio calls, video, the extensions; avd_destroy frees it.  A call that fails before its save launch (the
+ * one launch that writes the slot) is enqueued leaves the slot as it was; a call that fails later empties the slot and says so in the error
+ * text.  A pending asynchronous analysis is drained first, as by every avd_audio_features call; no host round trip is added.
+ * "audio_rs_plan" after a slot call that converted: input frames and output samples are the call's own (its new outputs; 0 is possible), and
+ * "audio_rs_tracks" gives where the new outputs begin in the analyzer's buffer -- behind the held samples -- and their count.  A slot call
+ * that completes no window runs no analysis: "audio_plan", "audio_tracks", "audio_xw" and "audio_mag" then still describe the last call that did.
+ *
  * avd_debug_fetch, host state of the last call that ran: "audio_tracks" int32[tracks][3] -- per track its first window, its windows and the length
  * of its last window; "audio_plan" int32[4] -- windows of all tracks, win, the LAST track's last length, windows of all tracks that took the
  * 80 x 100 transform; "audio_host" int32[2] -- the microseconds the host spent forming the tables of the call's short window lengths, and how
@@ -649,7 +688,9 @@ int avd_set_profiling(avd_ctx* ctx, int enable);
  * kernel).  The fast mode's flag thresholds were fuzzed at full size under the default model only; see DESIGN.md section 2 for what was repeated.
  * "audio_format" (0 float32, 1 int16 PCM; durable) and "audio_cut" (the track boundaries of the next avd_audio_features call; one-shot) belong to the
  * audio analyzer and are described at avd_audio_features, as are "audio_rate" (0, or the decoder's rate of the frames handed over: they are converted
- * to 16 kHz mono int16 on the device first; durable) and "audio_channels" (1 or 2 interleaved samples per frame of such a call; durable).
+ * to 16 kHz mono int16 on the device first; durable) and "audio_channels" (1 or 2 interleaved samples per frame of such a call; durable), and
+ * the audio slots: "audio_slot" (0, or the slot 1 ... 8 whose track the calls continue; durable), "audio_end" (the next call ends the track;
+ * one-shot), "audio_slot_reset" and the read-only "audio_slot_frames", "audio_slot_held" and "audio_slot_windows".
  * avd_get_option returns the value an option has now (environment defaults included) and the read-only "rerun_pairs" and "stream_frames". */
 int avd_set_option(avd_ctx* ctx, const char* name, int value);
 int avd_get_option(avd_ctx* ctx, const char* name, int* value);
