@@ -1307,6 +1307,11 @@ static int64_t impl_debug_fetch(avd_ctx* ctx, const char* name, void* out, size_
     else if ((k = level("pyr")) >= 0 && k == 0 && fb_fold_blur_eff(ctx->fb_fold_blur, ctx->cv2_model)) { ctx->err = "pyr0 does not exist while fb_fold_blur is on (the polynomial expansion forms the 320-px blur itself)"; return AVD_ERR_ARG; }
     else if ((k = level("pyr")) >= 0) { src = ws.d_pyr[k]; bytes = (size_t)std::min(n, ws.fb_cap + 1) * (AVD_NPIX >> (2 * k)) * 4; }
     else if ((k = level("poly")) >= 0) { src = ws.d_poly[k]; bytes = (size_t)std::min(n, ws.fb_cap + 1) * 5 * (AVD_NPIX >> (2 * k)) * 4; }
+    else if ((k = level("flow")) >= 0 && k == 0 && ws.fb_holds.flow0_late.pairs > 0) {   // a call without dense flow left this one unwritten: form it now
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        if (int e = launch_flow0_late(ctx)) return e;
+        src = ws.fb_holds.flow[0]; bytes = (size_t)std::min(std::max(n - 1, 0), ws.fb_cap) * 2 * AVD_NPIX * 4;
+    }
     else if ((k = level("flow")) >= 0) { src = ws.fb_holds.flow[k] ? ws.fb_holds.flow[k] : ws.d_flow[k]; bytes = (size_t)std::min(std::max(n - 1, 0), ws.fb_cap) * 2 * (AVD_NPIX >> (2 * k)) * 4; }
     else if (std::strcmp(name, "pairdiff") == 0) { src = ws.d_pairdiff; bytes = (size_t)std::min(std::max(n - 1, 0), ws.fb_cap) * kPairDiffTiles * sizeof(int); }
     else if (std::strcmp(name, "vs0") == 0) { src = ws.d_vs0; bytes = fb_two_scratch_size((size_t)ws.fb_cap).vs0 * sizeof(double); }

@@ -870,8 +870,13 @@ int fast_levels(avd_ctx* ctx, const FlowCall& call, int np, FbChunk& chunk)
             for (int it = 0; it < 3; it++) {
                 float* mag = (k == 0 && it == 2) ? ws.d_mag.p : nullptr;
                 const int* identity = cleared && it == 0 && pairdiff ? reinterpret_cast<const int*>(a) : pairdiff;
-                const FbFastLaunch L{call.wide160, 1, it == 0 ? from : FbFlowFrom::level, it == 0 && from_prev ? prev : a, b, a, mag, flags, identity};
+                // the level's last launch: nothing on the device reads the 320-px flow itself -- the statistics read |flow| (d_mag), the exact
+                // re-run writes its pairs' flow without reading it -- unless the call interleaves it for its caller (flow_tail).  The one reader
+                // after the call, avd_debug_fetch "flow0", has the launch repeated with the stores (launch_flow0_late)
+                const bool unread = mag && !call.dense_flow;
+                const FbFastLaunch L{call.wide160, 1, it == 0 ? from : FbFlowFrom::level, it == 0 && from_prev ? prev : a, b, a, mag, flags, identity, !unread};
                 if (int e = launch_fb_fast(ctx, stream, w, ws.d_poly[k], L, np)) return e;
+                if (unread) { chunk.flow0_late.pairs = np; chunk.flow0_late.flow_in = a; chunk.flow0_late.flags = flags; chunk.flow0_late.pairdiff = pairdiff; }
                 float* t = a; a = b; b = t;
             }
         }
@@ -904,6 +909,7 @@ int launch_farneback(avd_ctx* ctx, const FlowCall& call, const uint8_t* d_small,
     const bool fast = ctx->fb_mode == 1;
     FbChunk& chunk = ws.fb_holds;                      // level by level: a launch sequence that fails half way has overwritten those levels
     chunk.mag_valid = fast;
+    chunk.flow0_late = {};
     pyramid_and_polyexp(ctx, call, d_small, n);
     if (int e = fast ? fast_levels(ctx, call, n - 1, chunk) : exact_levels(ctx, call, n - 1, ctx->fb_fused, {ws.d_vs, ws.d_vs0}, nullptr, chunk)) return e;
     HIP_TRY(ctx, hipGetLastError());
@@ -935,6 +941,24 @@ int launch_farneback_rerun(avd_ctx* ctx, const FlowCall& call, const int* h_list
     if (int e = exact_levels(ctx, call, m, fused_mask, {ws.d_vs_rerun, ws.d_vs0_rerun}, ws.d_rlist, ws.fb_holds)) return e;   // the scratch is indexed by position in the list
     flow_tail(ctx, call, ws.fb_holds.flow[0], true, m, ws.d_rlist, np_chunk);
     HIP_TRY(ctx, hipGetLastError());
+    return 0;
+}
+
+// The 320-px level's last launch once more, this time storing the flow (not |flow|: d_mag has it, and the re-run's pairs have theirs there).  Its
+// inputs are all still in the scratch: the polynomial expansions, the flow of the second iteration, the identity words, and the flag words as
+// the call left them -- a flagged pair is skipped by every workgroup, so the flow the exact re-run wrote for it stays; the others are computed
+// exactly as the first time (the launch is deterministic), so no new flag can rise.
+int launch_flow0_late(avd_ctx* ctx)
+{
+    Workspace& ws = ctx->ws;
+    FbChunk& chunk = ws.fb_holds;
+    if (chunk.flow0_late.pairs <= 0) return 0;
+    const auto late = chunk.flow0_late;
+    float* out = const_cast<float*>(chunk.flow[0]);
+    const FbFastLaunch L{false, 1, FbFlowFrom::level, late.flow_in, out, const_cast<float*>(late.flow_in), nullptr, late.flags, late.pairdiff};
+    if (int e = launch_fb_fast(ctx, ctx->stream, S, ws.d_poly[0], L, late.pairs)) return e;
+    HIP_TRY(ctx, hipGetLastError());
+    chunk.flow0_late = {};
     return 0;
 }
 

@@ -28,6 +28,8 @@
 //           columns per step
 // (No touch / prefetch loads: the N waves' own three-entry lead covers the latency, and touching the next rows one dword
 // per line from a fourth wave cost 0.16 ms per level: it is the texture-addresser / L1 path that limits this kernel.)
+// The LAST launch of the 320-px level writes |flow| for the statistics kernels, and the flow itself only for a call that hands it to its caller (k_fb_fast's
+// ST = false: two of the solver wave's three stores per step and 0.8 MB per pair less; -5.7 us of 127.6, profiles/fbfast320_balance_ab.txt).
 // The first launch of the 320-px level, and of the 160-px level where a pair is one strip of this same wave mix, has no input flow of its own size: its chain wave forms it from
 // the coarser level's flow a few rows ahead of the N waves (UP, role_chain), which saves k_flow_up's full-chip pass (320 px: 37 us for +3.5; 160 px: 12 us alone, 50 us among three
 // clips in flight, for +9 us on 119 CUs -- profiles/fold160_pyramid_ab.txt).
@@ -375,7 +377,8 @@ __device__ __forceinline__ bool role_chain(const float* __restrict__ mring, doub
 //   max(|fx|, |fy|) > kFlowMax * W                           a displacement beyond what a 15-px window can estimate at this
 //                                                            level (the same experiment: <= 0.25 W on well-posed pairs)
 // written so that a NaN or a negative determinant also fires.
-template <typename Ge, bool UP>
+// ST: the flow is stored (false: the level's last launch when nobody reads its flow -- |flow| in mag_out is all that is kept)
+template <typename Ge, bool UP, bool ST = true>
 __device__ __forceinline__ bool role_solve(const double* __restrict__ vsring, float* __restrict__ flow_out, float* __restrict__ mag_out,
                                            int* __restrict__ flags, int p, int b, int xi, int lane, int o0, int ow, const volatile int* skip)
 {
@@ -457,7 +460,8 @@ __device__ __forceinline__ bool role_solve(const double* __restrict__ vsring, fl
                     else *reinterpret_cast<float2*>(md) = make_float2(mg[0], mg[1]);
                 }
                 float* dst = fl + y * W;
-                if (CPL == 4) {
+                if constexpr (!ST) {
+                } else if (CPL == 4) {
                     *reinterpret_cast<float4*>(dst) = make_float4(fx[0], fx[1], fx[2 % CPL], fx[3 % CPL]);
                     *reinterpret_cast<float4*>(dst + plane) = make_float4(fy[0], fy[1], fy[2 % CPL], fy[3 % CPL]);
                 } else {
@@ -490,7 +494,8 @@ __device__ __forceinline__ void phase_sync()
 //     pole of a step and cannot take the resize on, while a prologue costs ~1 us and saves k_flow_up's launch.
 // IT  iterations inside the launch (levels whose pairs are ONE strip: no other workgroup reads this one's flow): the flow ping-pongs
 //     between flow_out and flow_tmp through L2, one workgroup barrier between iterations; the result is in flow_out (IT odd).
-template <typename Ge, bool UP, int IT = 1, bool PRO = false>
+// ST  false: the flow itself is not stored, only |flow| (IT = 1 with mag_out: the 320-px level's last launch of a call that wants no dense flow)
+template <typename Ge, bool UP, int IT = 1, bool PRO = false, bool ST = true>
 __global__ __launch_bounds__((64 * Ge::NWAVES)) void k_fb_fast(const float* __restrict__ R, const float* flow_in, float* flow_out, float* flow_tmp,
                                                               float* __restrict__ mag_out, int* __restrict__ flags, const int* __restrict__ pairdiff,
                                                               int npairs, int nstrips, int ow, int zero_first)
@@ -498,6 +503,7 @@ __global__ __launch_bounds__((64 * Ge::NWAVES)) void k_fb_fast(const float* __re
     constexpr int W = Ge::W, NB = Ge::NB;
     static_assert(IT == 1 || IT == 3, "one iteration per launch, or all three");
     static_assert(!(UP && (PRO || IT > 1 || Ge::PN)), "the chain wave's resize belongs to one-iteration launches of the throughput shape");
+    static_assert(ST || (IT == 1 && !UP && !PRO), "only a level's last launch may leave its flow unwritten");
     __shared__ __align__(16) double lds[Ge::LDS_DOUBLES + (UP ? Ge::F_FLOATS / 2 : 0)];
     double* vsring = lds;
     float* mrings = reinterpret_cast<float*>(lds + Ge::VS_DOUBLES);
@@ -512,8 +518,12 @@ __global__ __launch_bounds__((64 * Ge::NWAVES)) void k_fb_fast(const float* __re
     if (p >= npairs) return;                              // whole workgroup
     const int o0 = s * ow;
     const int width = o0 + ow <= W ? ow : W - o0;         // output columns of this strip (multiples of 4)
-    // Waves w, w + 4, w + 8 of a workgroup share a SIMD.  Issue cycles per step: X ~ 900 (double), N ~ 550, C ~ 230: with
-    // NB = 3 the SIMDs get {X, N1, C} of block 0, 1, 2 and {N0, N0, N0} -- 1700 / 1700 / 1700 / 1650 cycles
+    // Waves w, w + 4, w + 8 of a workgroup share a SIMD.  VALU issue cycles per step of four rows (ISA of the loops, tools/isa_loop_table.py): X 849
+    // (159 double instructions), N 329-335, C 307: with NB = 3 the SIMDs get {X, N1, C} of block 0, 1, 2 and {N0, N0, N0} -- 1485 / 1485 / 1485 / 987 of
+    // the ~3200 cycles a step takes.  The slack of the fourth SIMD cannot be used by moving work into its waves: the N waves are the pole of a step (they
+    // wait for their gathers, not for issue slots), and whatever they do after the gather arrives lengthens the step.  Letting the k == 0 wave finish its
+    // own two rows (border attenuation and products; 1405 / 1227 on paper) made the launches 1.3-1.9 us SLOWER (profiles/fbfast320_balance_ab.txt;
+    // round 4 had found the same change neutral, profiles/r04_experiments.md section 2c)
     // role: 0 .. NPB-1 normal equations, NPB the chain, NPB+1 .. solvers
     int b, role;
     if (NB == 3 && Ge::WPB == 4) {
@@ -575,7 +585,7 @@ __global__ __launch_bounds__((64 * Ge::NWAVES)) void k_fb_fast(const float* __re
 #pragma unroll 1
         for (int it = 0; it < IT; it++) {
             if (it > 0) phase_sync();
-            if (role_solve<Ge, UP>(vsring, (it & 1) ? flow_tmp : flow_out, it == IT - 1 ? mag_out : nullptr, flags, p, b, role - Ge::NPB - 1, lane, o0, width,
+            if (role_solve<Ge, UP, ST>(vsring, (it & 1) ? flow_tmp : flow_out, it == IT - 1 ? mag_out : nullptr, flags, p, b, role - Ge::NPB - 1, lane, o0, width,
                                    it == 0 ? skip : nullptr)) return;
         }
     }
@@ -597,6 +607,7 @@ void launch_fast(hipStream_t stream, const float* R, const FbFastLaunch& L, floa
     if constexpr (Ge::W == 160 || Ge::W == 80) { if (pro && !three) return go(k_fb_fast<Ge, false, 1, true>, 0); }
     if constexpr (Ge::W == 80) { if (pro && three) return go(k_fb_fast<Ge, false, 3, true>, 0); }
     if constexpr (Ge::W == 80 || Ge::W == 40) { if (three) return go(k_fb_fast<Ge, false, 3, false>, zero_first); }
+    if constexpr (Ge::W == 320) { if (!L.store_flow) return go(k_fb_fast<Ge, false, 1, false, false>, zero_first); }
     go(k_fb_fast<Ge, false>, zero_first);
 }
 
@@ -616,6 +627,7 @@ int launch_fb_fast(avd_ctx* ctx, hipStream_t stream, int w, const float* R, cons
                   : (one ? (w == 160 || w == 80) : (three && w == 80));      // prologue
     if (!ok) { ctx->err = "launch_fb_fast: this mode does not exist at this level size"; return AVD_ERR_ARG; }
     const bool uses_tmp = three || L.from == FbFlowFrom::prologue;
+    if (!L.store_flow && !(w == 320 && one && L.from == FbFlowFrom::level && L.mag_out)) { ctx->err = "launch_fb_fast: only the 320-px level's last launch can leave its flow unwritten"; return AVD_ERR_ARG; }
     if (L.flow_in == L.flow_out || (uses_tmp && (!L.flow_tmp || L.flow_tmp == L.flow_out))) { ctx->err = "launch_fb_fast: the flow is not updated in place"; return AVD_ERR_ARG; }
     switch (w) {
     case 320:

@@ -193,6 +193,9 @@ inline int fb_fold_up160_eff(int fold_up160, int model) { return model & kCv2Res
 struct FbChunk {
     const float* flow[AVD_FB_LEVELS] = {};   // the final flow of each level (d_flow or d_flow2)
     bool mag_valid = false;                  // d_mag holds |flow| of the chunk already (the fast level kernel wrote it)
+    // fast mode, a call that wants no dense flow: the 320-px level's last launch wrote |flow| only, flow[0] does not hold its flow yet.  Only
+    // avd_debug_fetch "flow0" can ask for it afterwards; launch_flow0_late then repeats that launch with the stores (pairs > 0: pending)
+    struct { int pairs = 0; const float* flow_in = nullptr; int* flags = nullptr; const int* pairdiff = nullptr; } flow0_late;
 };
 
 // Scratch of a context.  Everything here can be given back (avd_release_workspace resets the struct) and is re-reserved on demand.
@@ -473,6 +476,8 @@ int avd_calls_in_flight();      // avd_capi.hip: contexts of this process holdin
 // all pairs of n resident frames, into the Farneback scratch; *left (and ws.fb_holds) = what it holds then
 int launch_farneback(avd_ctx* ctx, const FlowCall& call, const uint8_t* d_small, int n, FbChunk* left);
 int launch_flow_stats(avd_ctx* ctx, const FlowCall& call, const FbChunk& chunk, int n);
+// the 320-px flow of the chunk the scratch holds, where its last launch left it unwritten (FbChunk::flow0_late); nothing else to do otherwise
+int launch_flow0_late(avd_ctx* ctx);
 // avd_vit.hip (extension): patchify + bf16 MFMA GEMM; all pointers device
 int launch_vit_patch_embed(avd_ctx* ctx, const uint8_t* d_bgr, int n, int h, int w, int64_t row_stride, int64_t frame_stride,
                            const uint16_t* d_wt, const float* d_bias, void* d_tokens, int tokens_bf16, uint16_t* d_patches);
@@ -536,6 +541,7 @@ struct FbFastLaunch {
     int iterations; FbFlowFrom from; const float* flow_in; float *flow_out, *flow_tmp;
     float* mag_out;                              // 320-px level, last iteration (else null): float[pair][320][320] receives |flow|
     int* flags; const int* pairdiff;             // may be null, see avd_fbfast.hip
+    bool store_flow = true;                      // false (with mag_out only): flow_out is not written, |flow| alone is kept
 };
 int launch_fb_fast(avd_ctx* ctx, hipStream_t stream, int w, const float* R, const FbFastLaunch& L, int np);
 // avd_farneback.hip: exact re-run of the m flagged pairs h_list[0 .. m) (pair indices inside the chunk the workspace holds; h_list pinned); np_chunk = its pairs
