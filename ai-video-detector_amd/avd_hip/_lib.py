@@ -904,9 +904,10 @@ class Context:
         g = math.gcd(int(rate), cls.AUDIO_OUT_RATE)
         return -(-int(n) * (cls.AUDIO_OUT_RATE // g) // (int(rate) // g))
 
-    def _audio_call(self, ptr, mem, n: int, win: int, nwin: int, pcm16: bool, cuts=(), rate=None, channels: int = 1, last: bool = False) -> np.ndarray:
+    def _audio_call(self, ptr, mem, n: int, win: int, nwin: int, pcm16: bool, cuts=(), rate=None, channels: int = 1, last: bool = False, entries=()) -> np.ndarray:
         """One avd_audio_features call: option "audio_format" -- and, for a track at its decoder's rate, "audio_rate" and "audio_channels" -- set for
-        it and restored (also after an exception), its cuts set in ascending order.  last: option "audio_end" is set for it (a slot call)."""
+        it and restored (also after an exception), its cuts set in ascending order.  last: option "audio_end" is set for it (a slot call).
+        entries: the "audio_track_slot" list of the call, set in track order and cleared if setting it fails (a call takes it whatever becomes of it)."""
         out = np.zeros(nwin, AUDIO_WINDOW_DTYPE)
         if rate is not None:
             # a refused value leaves the options as they were: nothing has been set yet
@@ -914,7 +915,7 @@ class Context:
             self.set_option("audio_rate", int(rate))
             try:
                 self.set_option("audio_channels", int(channels))
-                return self._audio_call(ptr, mem, n, win, nwin, pcm16, cuts, None, 1, last)
+                return self._audio_call(ptr, mem, n, win, nwin, pcm16, cuts, None, 1, last, entries)
             finally:
                 self.set_option("audio_rate", was[0])
                 self.set_option("audio_channels", was[1])
@@ -926,8 +927,12 @@ class Context:
             try:
                 for c in cuts:
                     self.set_option("audio_cut", int(c))
+                for e in entries:
+                    self.set_option("audio_track_slot", int(e))
             except Exception:
                 self.set_option("audio_cut", -1)
+                if entries:
+                    self.set_option("audio_track_slot", -1)
                 raise
             if last:
                 self.set_option("audio_end", 1)
@@ -1088,6 +1093,84 @@ class Context:
             if n == 0:
                 results[i] = np.zeros(0, AUDIO_WINDOW_DTYPE)
         return results
+
+    AUDIO_TRACK_END = 0x10
+
+    def audio_features_mapped(self, chunks, slots, lasts, win: int, rate=None, channels: int = 1) -> list:
+        """Several tracks in ONE call, each a whole track or the continuation of an audio slot (option "audio_track_slot", set for this call; it and
+        the cuts are gone after it, also after an exception).  chunks[i] is what audio_features takes for one track -- all float32 or all int16, all
+        host arrays or all device tensors, at least one frame each; slots[i] = 0 says it is a whole track, 1 ... AUDIO_SLOTS that it continues that
+        slot (each slot once); lasts[i] that it carries the slot's last samples.  Host chunks are concatenated once, device chunks go through one
+        torch.cat.  -> one record array per track, in order: for a slot the windows this call completes (possibly none), the concatenated results
+        of a track's calls being byte for byte the result of one slot-0 call on the joined samples.  The gather, converter, analyzer and save each
+        run once per call, however many tracks it has."""
+        chunks, slots, lasts = list(chunks), [int(s) for s in slots], [bool(l) for l in lasts]
+        if not chunks or not (len(chunks) == len(slots) == len(lasts)):
+            raise ValueError("audio_features_mapped: one slot and one end mark per chunk, at least one chunk")
+        if len(chunks) > self.AUDIO_TRACKS_PER_CALL:
+            raise ValueError("audio_features_mapped: at most %d tracks per call" % self.AUDIO_TRACKS_PER_CALL)
+        if rate is not None:
+            framed = [self._audio_frames(t, channels) for t in chunks]
+            if len({c for _, c in framed}) != 1:
+                raise ValueError("audio_features_mapped: the tracks must have one channel count")
+            chunks, channels = [t for t, _ in framed], framed[0][1]
+        else:
+            channels = 1
+        pcm = {self._is_pcm16(t) for t in chunks}
+        if len(pcm) != 1:
+            raise ValueError("audio_features_mapped: the tracks must be all float32 or all int16")
+        pcm16 = pcm.pop()
+        on_device = {bool(_is_torch_tensor(t) and t.is_cuda) for t in chunks}
+        if len(on_device) != 1:
+            raise ValueError("audio_features_mapped: the tracks must be all host arrays or all device tensors")
+        if any(t.ndim != 1 for t in chunks):
+            raise ValueError("wav must be float32[n] or int16[n]")
+        lens = [int(t.shape[0]) // channels for t in chunks]          # frames
+        if min(lens) < 1:
+            raise ValueError("audio_features_mapped: every track of the call needs a frame (flush an empty stream with audio_features(..., slot=k, last=True))")
+        win = int(win)
+        known = 1 <= win <= 8192 and (rate is None or rate in self.AUDIO_RATES)       # otherwise the library refuses (AvdError)
+        # the record arrays, from the rule (what _audio_slot_features does for one slot); the read-only options want their slot selected, which the
+        # list excludes -- so this comes before the list is set
+        counts = []
+        was = self.get_option("audio_slot")
+        try:
+            for n, slot, last in zip(lens, slots, lasts):
+                if not known:
+                    counts.append(0)
+                elif slot == 0:
+                    counts.append(-(-self.audio_outputs_after(n, rate, True) // win))
+                else:
+                    self.set_option("audio_slot", slot)
+                    frames, held = self.get_option("audio_slot_frames"), self.get_option("audio_slot_held")
+                    if frames < 0x7fffffff:
+                        fresh = self.audio_outputs_after(frames + n, rate, last) - self.audio_outputs_after(frames, rate)
+                        counts.append(-(-(held + fresh) // win) if last else (held + fresh) // win)
+                    else:
+                        raise ValueError("audio_features_mapped: slot %d has absorbed more than 2^31 - 1 frames; continue it with audio_features(slot=)" % slot)
+            self.set_option("audio_slot", 0)
+            if on_device.pop():
+                import torch
+                whole = torch.cat([t if pcm16 else t.to(torch.float32) for t in chunks])
+            else:
+                dt = np.int16 if pcm16 else np.float32
+                whole = np.concatenate([np.asarray(t.numpy() if _is_torch_tensor(t) else t, dtype=dt) for t in chunks])
+            ptr, mem, _, keep = self._audio_ptr(whole, pcm16)
+            cuts = [int(c) for c in np.cumsum(lens)[:-1]]
+            entries = [s | (self.AUDIO_TRACK_END if (l and s) else 0) for s, l in zip(slots, lasts)]
+            rec = self._audio_call(ptr, mem, sum(lens), win, sum(counts), pcm16, cuts, rate, channels, False, entries)
+        finally:
+            self.set_option("audio_slot", was)               # also after an exception (no list is held then: the call has taken it, or a failure cleared it)
+        out, at = [], 0
+        for c in counts:
+            out.append(rec[at:at + c])
+            at += c
+        return out
+
+    def audio_map_call(self):
+        """(tracks, continued tracks, gather launches, converter launches, analyzer passes, save launches) of the last audio_features_mapped call;
+        avd_debug_fetch "audio_map_call"."""
+        return tuple(int(v) for v in self.debug_fetch("audio_map_call", (6,), np.int32))
 
     def audio_tracks(self) -> np.ndarray:
         """int32[tracks, 3] of the last audio_features / audio_features_many call that ran: per track its first window, its windows and the length

@@ -276,3 +276,62 @@ def analyze_decoded_chunks(chunks, sr: int, ctx, slot: int = 1) -> dict:
     one sample type throughout).  -> what analyze_decoded gives for the concatenation; the duration is ceil(N U / D) / 16000 of the N frames seen."""
     rec, n = _chunk_records(chunks, ctx, slot, _decoded, _win_of(SAMPLE_RATE), int(sr))
     return features_to_result(window_values(rec), _converted_duration(n, int(sr), ctx))
+
+
+MAX_STREAMS = 8              # the audio slots (option "audio_slot"; Context.AUDIO_SLOTS)
+
+
+def _stream_records(streams, ctx, prepare, win: int, rate=None):
+    """K <= 8 tracks that arrive in pieces side by side: stream k is continued in audio slot k + 1, and every ROUND -- one piece of each stream that
+    still gives something -- is ONE call (Context.audio_features_mapped: one gather, converter, analyzer and save launch however many streams).
+    A piece is held until its stream's next one shows that it was not the last, so a stream ends in the round that carries its last piece; one
+    that gave nothing at all is the empty track.  Empty pieces are skipped.  The helper owns slots 1 ... K: they are emptied first and, whatever
+    happens, at the end.  -> [(records of the whole track, frames seen)] per stream"""
+    its = [iter(s) for s in streams]
+    if len(its) > MAX_STREAMS:
+        raise ValueError("at most %d streams side by side (the audio slots)" % MAX_STREAMS)
+
+    def pull(it):
+        for chunk in it:
+            chunk = prepare(chunk)
+            if len(chunk):
+                return chunk
+        return None
+
+    recs, frames = [[] for _ in its], [0] * len(its)
+    try:
+        for k in range(len(its)):
+            ctx.set_option("audio_slot_reset", k + 1)
+        held = [pull(it) for it in its]
+        while any(h is not None for h in held):
+            ahead = [pull(it) if h is not None else None for it, h in zip(its, held)]
+            members = [k for k, h in enumerate(held) if h is not None]
+            got = ctx.audio_features_mapped([held[k] for k in members], [k + 1 for k in members], [ahead[k] is None for k in members], win, rate=rate)
+            for k, rec in zip(members, got):
+                recs[k].append(rec)
+                frames[k] += len(held[k])
+            held = ahead
+    finally:
+        for k in range(len(its)):
+            ctx.set_option("audio_slot_reset", k + 1)        # half a track is of no use to the next one; a finished one has left its slot empty
+    empty = None
+    out = []
+    for k in range(len(its)):
+        if recs[k]:
+            out.append((np.concatenate(recs[k]), frames[k]))
+        else:
+            empty = ctx.audio_features(np.zeros(0, np.float32), win) if empty is None else empty
+            out.append((empty, 0))
+    return out
+
+
+def analyze_wave_streams(streams, sr: int, ctx) -> list:
+    """analyze_wave_chunks for up to eight 16 kHz tracks that arrive in pieces side by side (live streams): an iterable of pieces per stream, one
+    sample type throughout.  One call per round of pieces.  -> per stream what analyze_wave gives for its concatenation."""
+    return [features_to_result(window_values(rec), n / sr if sr > 0 else 0.0) for rec, n in _stream_records(streams, ctx, _mono, _win_of(sr))]
+
+
+def analyze_decoded_streams(streams, sr: int, ctx) -> list:
+    """analyze_decoded_chunks for up to eight tracks that arrive as their decoders' packets side by side, all at rate ``sr`` with one channel count
+    and one sample type.  One call per round of packets.  -> per stream what analyze_decoded gives for its concatenation."""
+    return [features_to_result(window_values(rec), _converted_duration(n, int(sr), ctx)) for rec, n in _stream_records(streams, ctx, _decoded, _win_of(SAMPLE_RATE), int(sr))]

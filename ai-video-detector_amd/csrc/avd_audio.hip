@@ -256,17 +256,16 @@ __device__ __forceinline__ int narrow_sample(float x)
     return v != v ? 0 : (int)fminf(fmaxf(v, -32768.f), 32767.f);
 }
 
+// one tile, by the whole workgroup: the body of both converter kernels below
 template <typename S, typename Q, typename Acc>
-__global__ __launch_bounds__(256) void k_audio_resample(const S* __restrict__ wav, const Tile* __restrict__ tiles, const int* __restrict__ taps, int U, int D,
-                                                       int T, int channels, int samples_at, int mono_at, int res_at, int16_t* __restrict__ pcm,
-                                                       long long chunk0, const int16_t* __restrict__ hist, int hist_n)
+__device__ __forceinline__ void resample_tile(const S* __restrict__ wav, const Tile t, const int* __restrict__ taps, int U, int D, int T, int channels, int samples_at,
+                                              int mono_at, int res_at, int16_t* __restrict__ pcm, long long chunk0, const int16_t* __restrict__ hist, int hist_n)
 {
     extern __shared__ __align__(16) unsigned char rs_lds[];
     Q* q = reinterpret_cast<Q*>(rs_lds);
     int16_t* smp = reinterpret_cast<int16_t*>(rs_lds + samples_at);
     int16_t* mono = reinterpret_cast<int16_t*>(rs_lds + mono_at);
     int16_t* res = reinterpret_cast<int16_t*>(rs_lds + res_at);
-    const Tile t = tiles[blockIdx.x];
     const int tid = threadIdx.x;
     for (int i = tid; i < U * T; i += 256) q[i] = (Q)taps[i];
     const int span = T == 0 ? t.count : (t.phase + (t.count - 1) * D) / U + T;
@@ -342,6 +341,41 @@ __global__ __launch_bounds__(256) void k_audio_resample(const S* __restrict__ wa
 }
 
 template <typename S, typename Q, typename Acc>
+__global__ __launch_bounds__(256) void k_audio_resample(const S* __restrict__ wav, const Tile* __restrict__ tiles, const int* __restrict__ taps, int U, int D,
+                                                       int T, int channels, int samples_at, int mono_at, int res_at, int16_t* __restrict__ pcm,
+                                                       long long chunk0, const int16_t* __restrict__ hist, int hist_n)
+{
+    resample_tile<S, Q, Acc>(wav, tiles[blockIdx.x], taps, U, D, T, channels, samples_at, mono_at, res_at, pcm, chunk0, hist, hist_n);
+}
+
+// A call of several tracks (option "audio_track_slot", avd_audio_map.h) has a source PER TRACK: tile_track[tile] is the tile's track, rows[track]
+// says where the track's chunk begins in the call's buffer, how many frames its slot absorbed before, and where its history is -- in place of the
+// three per-launch arguments above.  Both reads are the same for every lane of the workgroup; the bank and the LDS layout are the launch's.
+using avd_audio_map::Source;
+
+template <typename S, typename Q, typename Acc>
+__global__ __launch_bounds__(256) void k_audio_resample_map(const S* __restrict__ wav, const Tile* __restrict__ tiles, const int* __restrict__ tile_track,
+                                                           const Source* __restrict__ rows, const int* __restrict__ taps, int U, int D, int T, int channels,
+                                                           int samples_at, int mono_at, int res_at, int16_t* __restrict__ pcm)
+{
+    const Source row = rows[tile_track[blockIdx.x]];
+    resample_tile<S, Q, Acc>(wav + row.at, tiles[blockIdx.x], taps, U, D, T, channels, samples_at, mono_at, res_at, pcm, row.chunk0,
+                             reinterpret_cast<const int16_t*>(row.hist), row.hist_n);
+}
+
+template <typename S, typename Q, typename Acc>
+int launch_resample_map_as(avd_ctx* ctx, const void* d_in, const Tile* tiles, const int* tile_track, const Source* rows, const int* taps, int ntiles,
+                           const avd_resample::Ratio& r, int channels, int16_t* d_pcm)
+{
+    const size_t at_s = avd_resample::lds_taps_bytes(r), at_m = at_s + avd_resample::lds_samples_bytes(r, channels), at_r = at_m + avd_resample::lds_mono_bytes(r);
+    const size_t lds = avd_resample::lds_bytes(r, channels);
+    HIP_TRY(ctx, hipFuncSetAttribute((const void*)k_audio_resample_map<S, Q, Acc>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL((k_audio_resample_map<S, Q, Acc>), dim3(ntiles), dim3(256), lds, ctx->stream, static_cast<const S*>(d_in), tiles, tile_track, rows, taps, r.U,
+                       r.D, r.T, channels, (int)at_s, (int)at_m, (int)at_r, d_pcm);
+    return 0;
+}
+
+template <typename S, typename Q, typename Acc>
 int launch_resample_as(avd_ctx* ctx, const void* d_in, const Tile* tiles, const int* taps, int ntiles, const avd_resample::Ratio& r, int channels, int16_t* d_pcm,
                        const AudioSource& src)
 {
@@ -360,9 +394,9 @@ int launch_resample_as(avd_ctx* ctx, const void* d_in, const Tile* tiles, const 
 //    (the slot alternates), so no lane reads what another writes; hist_new_n <= n + hist_old_n by the rule.
 //  * the new held remainder: held_words 16-bit words of the analyzer's buffer behind its last window (a float32 sample is two of them).
 template <typename S>
-__global__ __launch_bounds__(256) void k_audio_slot_save(const S* __restrict__ wav, long long n, int channels, const int16_t* __restrict__ hist_old, int hist_old_n,
-                                                        int16_t* __restrict__ hist_new, int hist_new_n, const int16_t* __restrict__ held_src,
-                                                        int16_t* __restrict__ held_dst, int held_words)
+__device__ __forceinline__ void slot_save(const S* __restrict__ wav, long long n, int channels, const int16_t* __restrict__ hist_old, int hist_old_n,
+                                          int16_t* __restrict__ hist_new, int hist_new_n, const int16_t* __restrict__ held_src, int16_t* __restrict__ held_dst,
+                                          int held_words)
 {
     const int tid = threadIdx.x;
     for (int i = tid; i < hist_new_n; i += 256) {
@@ -375,7 +409,102 @@ __global__ __launch_bounds__(256) void k_audio_slot_save(const S* __restrict__ w
     for (int i = tid; i < held_words; i += 256) held_dst[i] = held_src[i];
 }
 
+template <typename S>
+__global__ __launch_bounds__(256) void k_audio_slot_save(const S* __restrict__ wav, long long n, int channels, const int16_t* __restrict__ hist_old, int hist_old_n,
+                                                        int16_t* __restrict__ hist_new, int hist_new_n, const int16_t* __restrict__ held_src,
+                                                        int16_t* __restrict__ held_dst, int held_words)
+{
+    slot_save<S>(wav, n, channels, hist_old, hist_old_n, hist_new, hist_new_n, held_src, held_dst, held_words);
+}
+
+// ---- a call of several tracks (option "audio_track_slot"): ONE gather launch ahead of the converter, ONE save launch behind everything else -----
+// The tables travel BY VALUE, as kernel arguments, like k_stream_copy's: 72 moves of 24 bytes (1728 bytes) and 8 save rows of 64 bytes (512 bytes)
+// fit the 4 KB of arguments with room to spare, and no upload has to be ordered ahead of either launch.
+//
+// The save: workgroup b leaves track rows[b]'s new history and held remainder in its slot -- slot_save's arithmetic, once per continued track
+// that does not end in this call.
+struct SaveTable { AudioSaveRow row[avd_audio_map::kSlots]; };
+
+template <typename S>
+__global__ __launch_bounds__(256) void k_audio_slot_save_map(const SaveTable table, int channels)
+{
+    const AudioSaveRow r = table.row[blockIdx.x];
+    slot_save<S>(static_cast<const S*>(r.wav), r.n, channels, r.hist_old, r.hist_old_n, r.hist_new, r.hist_new_n, r.held_src, r.held_dst, r.held_words);
+}
+
+// The gather: move blockIdx.y of the table, by gridDim.x workgroups in strides.  Held samples go from their slot to the front of the track's region;
+// an unconverted track's own samples from the call's buffer (staged, or the caller's device memory) behind them.  Where source and destination
+// agree mod 16 the body moves in 16-byte lines, with elements (elem bytes each: 2, or 4 for float32) in the partial line at either end; where
+// they do not -- a track cut at an odd sample -- it moves element by element.  Every address is a multiple of elem.
+struct GatherTable { AudioGatherMove move[avd_audio_map::kMaxGather]; };
+
+template <typename E>
+__global__ __launch_bounds__(256) void k_audio_gather(const GatherTable table)
+{
+    const AudioGatherMove m = table.move[blockIdx.y];
+    const char* src = static_cast<const char*>(m.src);
+    char* dst = static_cast<char*>(m.dst);
+    const long long id = (long long)blockIdx.x * 256 + threadIdx.x, stride = (long long)gridDim.x * 256;
+    constexpr long long elem = sizeof(E);
+    if (((reinterpret_cast<uintptr_t>(src) ^ reinterpret_cast<uintptr_t>(dst)) & 15) == 0) {
+        const long long to_line = (long long)((16 - (reinterpret_cast<uintptr_t>(dst) & 15)) & 15);
+        const long long head = to_line < m.bytes ? to_line : m.bytes, lines = (m.bytes - head) / 16, tail_at = head + 16 * lines;
+        for (long long i = id; i < lines; i += stride)
+            *reinterpret_cast<uint4*>(dst + head + 16 * i) = *reinterpret_cast<const uint4*>(src + head + 16 * i);
+        const long long edge = (head + (m.bytes - tail_at)) / elem;          // elements of the two partial lines
+        for (long long e = id; e < edge; e += stride) {
+            const long long at = e * elem < head ? e * elem : tail_at + (e * elem - head);
+            *reinterpret_cast<E*>(dst + at) = *reinterpret_cast<const E*>(src + at);
+        }
+    } else {
+        for (long long e = id; e < m.bytes / elem; e += stride) *reinterpret_cast<E*>(dst + e * elem) = *reinterpret_cast<const E*>(src + e * elem);
+    }
+}
+
 }  // namespace
+
+int launch_audio_gather(avd_ctx* ctx, const AudioGatherMove* moves, int count, int elem)
+{
+    if (count <= 0) return 0;
+    if (count > avd_audio_map::kMaxGather || (elem != 2 && elem != 4)) { ctx->err = "audio_track_slot: internal error (gather table)"; return AVD_ERR_DEVICE; }
+    GatherTable table = {};
+    long long longest = 0;
+    for (int i = 0; i < count; i++) {
+        const AudioGatherMove& m = moves[i];
+        if (m.bytes <= 0 || m.bytes % elem || reinterpret_cast<uintptr_t>(m.src) % elem || reinterpret_cast<uintptr_t>(m.dst) % elem) {
+            ctx->err = "audio_track_slot: internal error (gather extents)";
+            return AVD_ERR_DEVICE;
+        }
+        table.move[i] = m;
+        longest = std::max(longest, m.bytes);
+    }
+    // a workgroup per 16 KB of the longest move, 64 at the most: held samples are one workgroup, a minute of float32 samples 64 in strides
+    const unsigned wgs = (unsigned)std::min<long long>(64, (longest + 16383) / 16384);
+    if (elem == 2) hipLaunchKernelGGL(k_audio_gather<uint16_t>, dim3(wgs, (unsigned)count), dim3(256), 0, ctx->stream, table);
+    else hipLaunchKernelGGL(k_audio_gather<uint32_t>, dim3(wgs, (unsigned)count), dim3(256), 0, ctx->stream, table);
+    HIP_TRY(ctx, hipGetLastError());
+    return 0;
+}
+
+int launch_audio_slot_save_map(avd_ctx* ctx, int format, int channels, const AudioSaveRow* rows, int count, bool* enqueued)
+{
+    if (count <= 0) return 0;
+    if (count > avd_audio_map::kSlots) { ctx->err = "audio_track_slot: internal error (save table)"; return AVD_ERR_DEVICE; }
+    SaveTable table = {};
+    for (int i = 0; i < count; i++) {
+        const AudioSaveRow& r = rows[i];
+        if (r.hist_new_n < 0 || r.hist_new_n > avd_resample::kMaxHistory || r.hist_new_n > r.n + r.hist_old_n || r.held_words < 0 || r.held_words > kAudioSlotHeldWords) {
+            ctx->err = "audio_track_slot: internal error (save extents)";
+            return AVD_ERR_DEVICE;
+        }
+        table.row[i] = r;
+    }
+    if (format == 1) hipLaunchKernelGGL(k_audio_slot_save_map<int16_t>, dim3((unsigned)count), dim3(256), 0, ctx->stream, table, channels);
+    else hipLaunchKernelGGL(k_audio_slot_save_map<float>, dim3((unsigned)count), dim3(256), 0, ctx->stream, table, channels);
+    *enqueued = true;                                        // from here on the slots' memory may have been written
+    HIP_TRY(ctx, hipGetLastError());
+    return 0;
+}
 
 int launch_audio_slot_save(avd_ctx* ctx, const void* d_in, int format, long long n, int channels, const int16_t* hist_old, int hist_old_n, int16_t* hist_new,
                            int hist_new_n, const void* held_src, int16_t* held_dst, int held_words, bool* enqueued)
@@ -404,6 +533,7 @@ static void record_resample_plan(avd_ctx* ctx, const avd_resample::Plan& plan, i
     ctx->audio_rs_ntracks = (int)plan.tracks.size();
     std::memcpy(ctx->audio_rs_tracks, plan.tracks.data(), sizeof(avd_resample::Track) * plan.tracks.size());
     ctx->audio_rs_pcm_at = plan.tracks.empty() ? 0 : plan.tracks[0].first;   // above 0 only behind a slot's held samples
+    ctx->audio_rs_mapped = 0;
     ctx->audio_rs_valid = 1;
 }
 
@@ -450,6 +580,72 @@ int launch_audio_resample(avd_ctx* ctx, const void* d_in, int format, int channe
     if (e) return e;
     HIP_TRY(ctx, hipGetLastError());
     record_resample_plan(ctx, plan, channels);
+    return 0;
+}
+
+// The converter of a call of several tracks (option "audio_track_slot"): ONE launch over the tiles of all of them.  The pinned staging holds, in one
+// upload, the tile table | the source rows (8-byte aligned: a tile is 40 bytes) | each tile's track; the bank follows when the rate changed, as above.
+// plan.sources carry the device address of each continued track's history already.  n_in: the frames of the call's buffer.
+int launch_audio_resample_map(avd_ctx* ctx, const void* d_in, int format, int channels, const avd_audio_map::Plan& plan, const avd_resample::Ratio& r, long long n_in,
+                              int16_t* d_pcm, bool* launched)
+{
+    const int ntiles = (int)plan.tiles.size(), ntracks = (int)plan.tracks.size(), bank = r.U * r.T, idx = avd_resample::rate_index(r.rate);
+    *launched = false;
+    if (idx < 0) return 0;
+    Workspace& ws = ctx->ws;
+    ctx->audio_rs_valid = 0;
+    if (ntiles > 0) {
+        if (ws.audio_rs_upload_pending) { HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); ws.audio_rs_upload_pending = 0; }
+        std::vector<int>& taps = ctx->audio_rs_bank[idx];
+        if (taps.empty() && bank) taps = avd_resample::build_taps(r);       // once per rate and context
+        const bool new_rate = bank && ws.audio_rs_rate != r.rate;
+        const size_t rows_at = sizeof(Tile) * (size_t)ntiles, track_at = rows_at + sizeof(Source) * (size_t)ntracks, up = track_at + sizeof(int) * (size_t)ntiles;
+        const size_t up_tiles = (up + sizeof(Tile) - 1) / sizeof(Tile), bank_tiles = new_rate ? (sizeof(int) * (size_t)bank + sizeof(Tile) - 1) / sizeof(Tile) : 0;
+        if (int e = ws.h_audio_rs.reserve(ctx, up_tiles + bank_tiles)) return e;
+        if (int e = ws.d_audio_rs_tiles.reserve(ctx, up_tiles)) return e;
+        char* hb = reinterpret_cast<char*>(ws.h_audio_rs.p);
+        std::memcpy(hb, plan.tiles.data(), sizeof(Tile) * (size_t)ntiles);
+        std::memcpy(hb + rows_at, plan.sources.data(), sizeof(Source) * (size_t)ntracks);
+        std::memcpy(hb + track_at, plan.tile_track.data(), sizeof(int) * (size_t)ntiles);
+        if (new_rate) {
+            std::memcpy(ws.h_audio_rs.p + up_tiles, taps.data(), sizeof(int) * (size_t)bank);
+            ws.audio_rs_rate = 0;                            // the bank is not valid again until its copy is enqueued
+            if (int e = ws.d_audio_rs_taps.reserve(ctx, (size_t)bank)) return e;
+        }
+        ws.audio_rs_upload_pending = 1;
+        HIP_TRY(ctx, hipMemcpyAsync(ws.d_audio_rs_tiles, hb, up, hipMemcpyHostToDevice, ctx->stream));
+        if (new_rate) {
+            HIP_TRY(ctx, hipMemcpyAsync(ws.d_audio_rs_taps, ws.h_audio_rs.p + up_tiles, sizeof(int) * (size_t)bank, hipMemcpyHostToDevice, ctx->stream));
+            ws.audio_rs_rate = r.rate;
+        }
+        const char* db = reinterpret_cast<const char*>(ws.d_audio_rs_tiles.p);
+        const Tile* tiles = ws.d_audio_rs_tiles;
+        const Source* rows = reinterpret_cast<const Source*>(db + rows_at);
+        const int* tile_track = reinterpret_cast<const int*>(db + track_at);
+        const int* d_taps = ws.d_audio_rs_taps;
+        int e;
+        if (avd_resample::wide(r))
+            e = format == 1 ? launch_resample_map_as<int16_t, int, long long>(ctx, d_in, tiles, tile_track, rows, d_taps, ntiles, r, channels, d_pcm)
+                            : launch_resample_map_as<float, int, long long>(ctx, d_in, tiles, tile_track, rows, d_taps, ntiles, r, channels, d_pcm);
+        else
+            e = format == 1 ? launch_resample_map_as<int16_t, int16_t, int>(ctx, d_in, tiles, tile_track, rows, d_taps, ntiles, r, channels, d_pcm)
+                            : launch_resample_map_as<float, int16_t, int>(ctx, d_in, tiles, tile_track, rows, d_taps, ntiles, r, channels, d_pcm);
+        if (e) return e;
+        HIP_TRY(ctx, hipGetLastError());
+        *launched = true;
+    }
+    // debug buffers "audio_rs_*" / "audio_pcm": per track where its new outputs lie in the analyzer's buffer, and how many
+    const int rs_plan[8] = {r.rate, channels, r.U, r.D, r.T, avd_resample::tile_outputs(r), (int)std::min<long long>(n_in, 0x7fffffff), (int)plan.fresh};
+    std::memcpy(ctx->audio_rs_plan, rs_plan, sizeof rs_plan);
+    ctx->audio_rs_ntracks = ntracks;
+    for (int t = 0; t < ntracks; t++) {
+        const avd_audio_map::Track& tr = plan.tracks[(size_t)t];
+        ctx->audio_rs_tracks[t][0] = (int)(tr.region + tr.c.held_before);
+        ctx->audio_rs_tracks[t][1] = (int)tr.c.fresh();
+    }
+    ctx->audio_rs_pcm_at = 0;
+    ctx->audio_rs_mapped = 1;
+    ctx->audio_rs_valid = 1;
     return 0;
 }
 

@@ -494,6 +494,33 @@ static bool opt_audio_channels(int& v) { return v == 1 || v == 2; }
 // "audio_slot": 0 every avd_audio_features call is a whole track, k = 1 ... 8 it continues the track of audio slot k; durable.  The audio slots are
 // apart from the video stream slots: neither family of options touches the other's.
 static bool opt_audio_slot(int& v) { return v >= 0 && v <= kAudioSlots; }
+// "audio_slot" and "audio_track_slot" never hold at once, as "stream_slot" and "stream_map": selecting a slot is refused while the list holds an
+// entry, setting an entry while a slot is selected
+static const char* audio_slot_check(const avd_ctx* ctx, int v)
+{
+    return v != 0 && ctx->audio_map_n > 0 ? "audio_slot: refused while an \"audio_track_slot\" list is held (clear it first: \"audio_track_slot\" = -1)" : nullptr;
+}
+// "audio_track_slot": what the tracks of the NEXT avd_audio_features call are, one entry at a time in track order -- slot 0 (a whole track) or
+// 1 ... 8 (the track continues that audio slot), | 0x10 the call carries the slot's last samples; -1 clears the list.  Reads back as the number of
+// entries held.  The call takes the list (avd_audio_features).
+static const char* audio_track_slot_check(const avd_ctx* ctx, int v)
+{
+    if (v == -1) return nullptr;
+    if (ctx->audio_slot != 0) return "audio_track_slot: refused while \"audio_slot\" selects a slot (set it to 0 first)";
+    if (v >= 0 && (v & ~(avd_audio_map::kSlotMask | avd_audio_map::kEndBit)) == 0 && (v & avd_audio_map::kEndBit) && (v & avd_audio_map::kSlotMask) == 0)
+        return "audio_track_slot: 0x10 (the track ends) needs a slot 1 ... 8";
+    if (!avd_audio_map::entry_ok(v)) return "audio_track_slot: slot 0 ... 8, | 0x10 (the call carries the slot's last samples), or -1 (clear the list)";
+    for (int i = 0; i < ctx->audio_map_n; i++)
+        if ((v & avd_audio_map::kSlotMask) && ((ctx->audio_map_entries[i] ^ v) & avd_audio_map::kSlotMask) == 0) return "audio_track_slot: the slot is already in the list";
+    if (ctx->audio_map_n >= avd_audio_map::kMaxEntries) return "audio_track_slot: at most 64 entries (64 tracks) per call";
+    return nullptr;
+}
+static void audio_track_slot_set(avd_ctx* ctx, int v)
+{
+    if (v == -1) ctx->audio_map_n = 0;
+    else ctx->audio_map_entries[ctx->audio_map_n++] = v;
+}
+static int audio_track_slot_read(const avd_ctx* ctx) { return ctx->audio_map_n; }
 // "audio_end": one-shot, the next avd_audio_features call carries the last samples of its slot's track; the call takes it (avd_audio_features)
 static bool opt_audio_end(int& v) { return v == 1; }
 static void audio_end_set(avd_ctx* ctx, int) { ctx->audio_end = 1; }
@@ -544,7 +571,8 @@ static const Option kOptions[] = {
     {"audio_cut", nullptr, true, opt_any, nullptr, nullptr, nullptr, audio_cut_set, audio_cut_read, audio_cut_check},
     {"audio_rate", &avd_ctx::audio_rate, true, opt_audio_rate, nullptr, nullptr, "audio_rate: 0 (samples at 16 kHz already) or 8000, 11025, 12000, 16000, 22050, 24000, 32000, 44100, 48000, 88200, 96000, 176400, 192000"},
     {"audio_channels", &avd_ctx::audio_channels, true, opt_audio_channels, nullptr, nullptr, "audio_channels: 1 or 2 interleaved samples per frame (downmix other layouts first)"},
-    {"audio_slot", &avd_ctx::audio_slot, true, opt_audio_slot, nullptr, nullptr, "audio_slot: 0 (every call is a whole track) or audio slot 1 ... 8"},
+    {"audio_slot", &avd_ctx::audio_slot, true, opt_audio_slot, nullptr, nullptr, "audio_slot: 0 (every call is a whole track) or audio slot 1 ... 8", nullptr, nullptr, audio_slot_check},
+    {"audio_track_slot", nullptr, true, opt_any, nullptr, nullptr, nullptr, audio_track_slot_set, audio_track_slot_read, audio_track_slot_check},
     {"audio_end", nullptr, true, opt_audio_end, nullptr, nullptr, "audio_end: 1 (the next avd_audio_features call carries the last samples of its slot's track)", audio_end_set, audio_end_read},
     {"audio_slot_reset", nullptr, true, opt_audio_slot, nullptr, nullptr, "audio_slot_reset: 0 (every audio slot) or audio slot 1 ... 8", audio_slot_reset, audio_slot_reset_read},
     {"audio_slot_frames", nullptr, false, opt_any, nullptr, nullptr, nullptr, nullptr, audio_slot_frames},
@@ -1235,6 +1263,7 @@ static int64_t impl_debug_fetch(avd_ctx* ctx, const char* name, void* out, size_
             {"ingest_call", ctx->ingest_call, sizeof ctx->ingest_call, true, nullptr, "int32[4]"},
             {"ingest_groups", ctx->ingest_groups.data(), sizeof(int) * ctx->ingest_groups.size(), true, nullptr, "int32[launches][4]"},
             {"fb_model", ctx->fb_model, sizeof ctx->fb_model, ctx->fb_model_valid != 0, "no call has run the Farneback stage on this context", "int32[4]"},
+            {"audio_map_call", ctx->audio_map_call, sizeof ctx->audio_map_call, ctx->audio_map_valid != 0, "no avd_audio_features call with an \"audio_track_slot\" list has run on this context", "int32[6]"},
         };
         for (const auto& e : host_state) {
             if (std::strcmp(name, e.name) != 0) continue;
@@ -1273,6 +1302,18 @@ static int64_t impl_debug_fetch(avd_ctx* ctx, const char* name, void* out, size_
         }
         src = ws.d_audio_pcm.p ? ws.d_audio_pcm.p + ctx->audio_rs_pcm_at : nullptr;   // null after avd_release_workspace: "buffer not allocated yet" below
         bytes = sizeof(int16_t) * (size_t)rp[7];
+        if (src && ctx->audio_rs_mapped) {             // a list call ("audio_track_slot"): the tracks' new outputs lie region by region; they are handed over side by side
+            if (out_bytes < bytes) { ctx->err = "audio_pcm is int16[output samples]"; return AVD_ERR_ARG; }
+            HIP_TRY(ctx, hipSetDevice(ctx->device));
+            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+            char* to = static_cast<char*>(out);
+            for (int t = 0; t < ctx->audio_rs_ntracks; t++) {
+                const size_t part = sizeof(int16_t) * (size_t)ctx->audio_rs_tracks[t][1];
+                if (part) HIP_TRY(ctx, hipMemcpy(to, ws.d_audio_pcm.p + ctx->audio_rs_tracks[t][0], part, hipMemcpyDeviceToHost));
+                to += part;
+            }
+            return (int64_t)bytes;
+        }
     }
     else if (std::strncmp(name, "audio_", 6) == 0) {   // the last avd_audio_features of this context: its window plan (host state) and its two scratch arrays
         const bool plan = std::strcmp(name + 6, "plan") == 0, xw = std::strcmp(name + 6, "xw") == 0, mag = std::strcmp(name + 6, "mag") == 0;
@@ -1666,13 +1707,152 @@ static int slot_audio_features(avd_ctx* ctx, const void* wav, int mem, int64_t n
     return AVD_OK;
 }
 
-// cuts / ncuts: the "audio_cut" list the call took from the context (avd_audio_features: one-shot, whatever becomes of the call); last: "audio_end" likewise
+// A call with an "audio_track_slot" list: several tracks, each a whole one or the continuation of an audio slot (avd_audio_map.h plans it;
+// include/avd.h states it).  The analyzer's buffer is ws.d_audio_pcm, a region [held | new] per track.  At most ONE launch of each kind, however
+// many tracks: the gather (held samples, and an unconverted call's own, into the regions), the converter (per-track sources), the analyzer's
+// passes over one window table, the save (every continued track that does not end).  Every slot's memory is reserved before the first launch, the
+// save is the last launch, and the host state of the slots moves only once the call has drained.  *saved as in run_audio_slot.
+static int run_audio_map(avd_ctx* ctx, avd_audio_map::Plan& plan, const avd_resample::Ratio& ratio, const void* wav, int mem, int64_t n, avd_audio_window* windows,
+                         bool* saved)
+{
+    const int format = ctx->audio_format, channels = ratio.rate ? ctx->audio_channels : 1;
+    const bool converted = ratio.rate != 0;
+    const size_t in_size = format == 1 ? sizeof(int16_t) : sizeof(float), an_size = converted ? sizeof(int16_t) : in_size;
+    const int an_format = converted ? 1 : format, nwin = plan.windows.nwin();
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    Workspace& ws = ctx->ws;
+    for (const avd_audio_map::Track& tr : plan.tracks)
+        if (tr.slot)
+            if (int e = ctx->audio_slots[tr.slot - 1].d_mem.reserve(ctx, kAudioSlotWords)) return e;
+    if (int e = ws.d_audio_pcm.reserve(ctx, (size_t)plan.total * an_size / sizeof(int16_t) + 8)) return e;
+    if (int e = ws.d_audio_out.reserve(ctx, (size_t)std::max(nwin, 1))) return e;
+    char* buf = reinterpret_cast<char*>(ws.d_audio_pcm.p);
+    const uint8_t* d_in = reinterpret_cast<const uint8_t*>(buf);                   // n = 0: a valid address nobody reads
+    ctx->audio_rs_valid = 0;
+    int* call = ctx->audio_map_call;
+    ctx->audio_map_valid = 0;
+    call[0] = (int)plan.tracks.size(); call[1] = plan.continued; call[2] = call[3] = call[4] = call[5] = 0;
+    if (n > 0)
+        if (int e = stage_input(ctx, static_cast<const uint8_t*>(wav), mem, (size_t)n * (size_t)channels * in_size, &d_in)) return e;
+    if (!plan.gather.empty()) {
+        AudioGatherMove moves[avd_audio_map::kMaxGather];
+        int count = 0;
+        for (const avd_audio_map::Copy& c : plan.gather) {
+            const void* from = c.held ? static_cast<const void*>(ctx->audio_slots[plan.tracks[(size_t)c.track].slot - 1].held_at())
+                                      : static_cast<const void*>(d_in + (size_t)c.src * in_size);
+            moves[count++] = AudioGatherMove{from, buf + (size_t)c.dst * an_size, (long long)((size_t)c.count * an_size)};
+        }
+        if (int e = launch_audio_gather(ctx, moves, count, (int)an_size)) return e;
+        call[2] = 1;
+    }
+    if (converted) {
+        for (size_t t = 0; t < plan.tracks.size(); t++)
+            if (const int k = plan.sources[t].slot) plan.sources[t].hist = reinterpret_cast<unsigned long long>(ctx->audio_slots[k - 1].hist(ctx->audio_slots[k - 1].hist_side));
+        bool launched = false;
+        if (int e = launch_audio_resample_map(ctx, d_in, format, channels, plan, ratio, n, ws.d_audio_pcm, &launched)) return e;
+        call[3] = launched;
+    }
+    if (nwin > 0) {
+        if (int e = launch_audio_features(ctx, buf, an_format, plan.windows, ws.d_audio_out)) return e;
+        HIP_TRY(ctx, hipMemcpyAsync(windows, ws.d_audio_out, sizeof(avd_audio_window) * nwin, hipMemcpyDeviceToHost, ctx->stream));
+        call[4] = 1;
+    }
+    if (!plan.saves.empty()) {
+        AudioSaveRow rows[avd_audio_map::kSlots];
+        int count = 0;
+        for (const avd_audio_map::Save& s : plan.saves) {
+            AudioSlot& slot = ctx->audio_slots[s.slot - 1];
+            const avd_audio_map::Track& tr = plan.tracks[(size_t)s.track];
+            AudioSaveRow r = {};
+            r.wav = converted ? d_in + (size_t)tr.begin * (size_t)channels * in_size : d_in;
+            r.n = s.n;
+            r.hist_old = slot.hist(slot.hist_side); r.hist_old_n = s.hist_old;
+            r.hist_new = slot.hist(slot.hist_side ^ 1); r.hist_new_n = s.hist_new;
+            r.held_src = reinterpret_cast<const int16_t*>(buf + (size_t)s.held_src * an_size);
+            r.held_dst = slot.held_at();
+            r.held_words = (int)((size_t)s.held * an_size / sizeof(int16_t));
+            rows[count++] = r;
+        }
+        if (int e = launch_audio_slot_save_map(ctx, converted ? format : 1, channels, rows, count, saved)) return e;
+        call[5] = 1;
+    }
+    ctx->audio_map_valid = 1;
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    ws.audio_upload_pending = 0;
+    ws.audio_rs_upload_pending = 0;
+    return AVD_OK;
+}
+
+// The checks of a list call, in the order include/avd.h lists them, all before anything is staged and with every slot untouched; then the call.
+// entries / nentries: the "audio_track_slot" list the call took from the context.
+static int map_audio_features(avd_ctx* ctx, const void* wav, int mem, int64_t n, int win, avd_audio_window* windows, int max_windows, const int* cuts, int ncuts,
+                              const int* entries, int nentries, bool end_pending)
+{
+    const int format = ctx->audio_format, rate = ctx->audio_rate, channels = rate ? ctx->audio_channels : 1;
+    if (n > 0 && format == 1 && (reinterpret_cast<uintptr_t>(wav) & 1)) { ctx->err = "audio_format 1: int16 samples need a 2-byte aligned wav"; return AVD_ERR_ARG; }
+    if (n > 0 && format == 0 && (reinterpret_cast<uintptr_t>(wav) & 3)) { ctx->err = "audio_track_slot: float32 samples need a 4-byte aligned wav"; return AVD_ERR_ARG; }
+    avd_resample::Ratio ratio = avd_resample::identity_ratio();
+    if (rate != 0 && !avd_resample::ratio_of(rate, ratio)) { ctx->err = "audio_rate: not a supported rate"; return AVD_ERR_ARG; }   // (the option refuses such a value)
+    avd_audio_map::SlotState state[kAudioSlots];
+    for (int k = 0; k < kAudioSlots; k++) {
+        const AudioSlot& s = ctx->audio_slots[k];
+        state[k].frames = s.frames;
+        state[k].held = s.held;
+        state[k].hist = avd_resample::history_frames(s.frames, ratio);
+        state[k].same = s.win == win && s.rate == rate && s.channels == channels && s.format == format;
+    }
+    avd_audio_map::Plan plan = avd_audio_map::plan_map(n, win, cuts, ncuts, entries, nentries, state, ratio, channels, max_windows, windows != nullptr, end_pending);
+    switch (plan.refused) {
+    case avd_audio_map::kOk: break;
+    case avd_audio_map::kCutBeyond: ctx->err = "audio_cut: beyond the buffer"; return AVD_ERR_ARG;
+    case avd_audio_map::kEndPending: ctx->err = "audio_track_slot: ends are given in the list (an \"audio_end\" was pending; it and the list are gone)"; return AVD_ERR_ARG;
+    case avd_audio_map::kEntryCount: ctx->err = "audio_track_slot: the list needs one entry per track of the call (the \"audio_cut\" list's cuts + 1)"; return AVD_ERR_ARG;
+    case avd_audio_map::kSlotBinding:
+        ctx->err = "audio_track_slot: win, \"audio_rate\", \"audio_channels\" and \"audio_format\" must be those of the slot's first call (track " + std::to_string(plan.refused_track) + ")";
+        return AVD_ERR_ARG;
+    case avd_audio_map::kTooLong:
+        ctx->err = plan.refused_track < 0 ? std::string("audio_track_slot: more than 2^31 - 1 samples in the analyzer's buffer of all tracks together")
+                                          : "audio_track_slot: more than 2^31 - 1 output samples in a track (track " + std::to_string(plan.refused_track) + ")";
+        return AVD_ERR_ARG;
+    case avd_audio_map::kWindowsTooSmall: ctx->err = "audio_track_slot: windows array too small"; return AVD_ERR_ARG;
+    case avd_audio_map::kTooManyWindows: ctx->err = "audio_track_slot: more than 2^24 records in one call"; return AVD_ERR_ARG;
+    default: ctx->err = "audio_track_slot: internal error (a slot's state contradicts the rule)"; return AVD_ERR_DEVICE;
+    }
+    bool saved = false;
+    const int e = run_audio_map(ctx, plan, ratio, wav, mem, n, windows, &saved);
+    if (e) {
+        if (saved) {
+            for (const avd_audio_map::Track& tr : plan.tracks)
+                if (tr.slot) ctx->audio_slots[tr.slot - 1].clear();
+            ctx->err += " (audio_track_slot: the failure came after the save launch; every slot the call continued was emptied)";
+        }
+        return e;
+    }
+    for (const avd_audio_map::Track& tr : plan.tracks) {
+        if (!tr.slot) continue;
+        AudioSlot& slot = ctx->audio_slots[tr.slot - 1];
+        if (tr.last) { slot.clear(); continue; }
+        if (slot.frames == 0) { slot.win = win; slot.rate = rate; slot.channels = channels; slot.format = format; }
+        slot.frames = tr.c.n_after;
+        slot.held = tr.c.held_after;
+        slot.windows = tr.count;
+        slot.hist_side ^= 1;
+    }
+    return AVD_OK;
+}
+
+// cuts / ncuts: the "audio_cut" list the call took from the context (avd_audio_features: one-shot, whatever becomes of the call); last: "audio_end" likewise;
+// entries / nentries: the "audio_track_slot" list likewise
 static int impl_audio_features(avd_ctx* ctx, const void* wav, int mem, int64_t n, int win, avd_audio_window* windows, int max_windows, const int* cuts, int ncuts,
-                               bool last)
+                               bool last, const int* entries, int nentries)
 {
     if (win < 1 || win > 8192) { ctx->err = "audio window must be 1..8192 samples"; return AVD_ERR_ARG; }   // also for n = 0: a bad window is never "nothing to do"
-    // a slot call that completes no window needs no windows array (slot_audio_features asks for one only where records are written)
-    if (n < 0 || (n > 0 && (!wav || (!windows && ctx->audio_slot == 0)))) { ctx->err = "bad arguments"; return AVD_ERR_ARG; }
+    // a slot call that completes no window needs no windows array (slot_audio_features asks for one only where records are written); a list call likewise
+    if (n < 0 || (n > 0 && (!wav || (!windows && ctx->audio_slot == 0 && nentries == 0)))) { ctx->err = "bad arguments"; return AVD_ERR_ARG; }
+    if (nentries > 0) {                                      // (the option keeps "audio_slot" at 0 while a list is held)
+        if (mem != AVD_MEM_HOST && mem != AVD_MEM_DEVICE) { ctx->err = "mem must be AVD_MEM_HOST or AVD_MEM_DEVICE"; return AVD_ERR_ARG; }
+        return map_audio_features(ctx, wav, mem, n, win, windows, max_windows, cuts, ncuts, entries, nentries, last);
+    }
     if (ctx->audio_slot != 0) {
         if (n > 0 && ctx->audio_format == 1 && (reinterpret_cast<uintptr_t>(wav) & 1)) { ctx->err = "audio_format 1: int16 samples need a 2-byte aligned wav"; return AVD_ERR_ARG; }
         if (n > 0 && ctx->audio_format == 0 && (reinterpret_cast<uintptr_t>(wav) & 3)) { ctx->err = "audio_slot: float32 samples need a 4-byte aligned wav"; return AVD_ERR_ARG; }
@@ -1952,8 +2132,12 @@ int avd_audio_features(avd_ctx* ctx, const float* wav, int mem, int64_t n, int w
         ctx->audio_ncuts = 0;
         const bool last = ctx->audio_end != 0;               // "audio_end" goes the same way
         ctx->audio_end = 0;
+        int entries[avd_audio_map::kMaxEntries];             // ... and the "audio_track_slot" list
+        const int nentries = ctx->audio_map_n;
+        std::copy(ctx->audio_map_entries, ctx->audio_map_entries + nentries, entries);
+        ctx->audio_map_n = 0;
         if (int e = drain_pending(ctx)) return e;
-        return impl_audio_features(ctx, wav, mem, n, win, windows, max_windows, cuts, ncuts, last);
+        return impl_audio_features(ctx, wav, mem, n, win, windows, max_windows, cuts, ncuts, last, entries, nentries);
     }, Pending::keep);
 }
 

@@ -12,6 +12,7 @@
 #include "avd_audio_plan.h"       // the tracks, window table and table arena of one avd_audio_features call (host only)
 #include "avd_audio_resample.h"   // the converter in front of it (option "audio_rate"): ratios, filter bank, output ranges, tile table (host only)
 #include "avd_audio_stream.h"     // a track continued across calls (option "audio_slot"): what one call of it forms, hands out and holds back (host only)
+#include "avd_audio_map.h"        // several continued tracks in one call (option "audio_track_slot"): regions, window / tile / source tables, gather and save lists (host only)
 #include "avd_ingest_group.h"     // which clips of a call share an ingest launch (option "ingest_group"), and kLapSlots (host only)
 
 #define AVD_FB_LEVELS 4            // pyramid scales 1/8,1/4,1/2,1 of 320 (see avd_farneback.hip)
@@ -305,6 +306,11 @@ struct AudioSlot {
 };
 // the two-part source of a continued track's converter launch: `wav` holds the track's frames from chunk0 on, hist its hist_n frames below
 struct AudioSource { long long chunk0 = 0; const int16_t* hist = nullptr; int hist_n = 0; };
+// a call of several tracks (option "audio_track_slot"): one move of its gather launch and one row of its save launch, device addresses throughout
+// (avd_audio_map.h plans both in entries; the call path turns them into these).  They travel to their kernels by value.
+struct AudioGatherMove { const void* src; void* dst; long long bytes; };
+struct AudioSaveRow { const void* wav; long long n; const int16_t* hist_old; int16_t* hist_new; const int16_t* held_src; int16_t* held_dst; int hist_old_n, hist_new_n, held_words, pad; };
+static_assert(sizeof(AudioGatherMove) == 24 && sizeof(AudioSaveRow) == 64, "the tables are kernel arguments: 72 moves and 8 rows stay far below 4 KB");
 
 struct avd_ctx {
     int device = 0;
@@ -393,6 +399,13 @@ struct avd_ctx {
     AudioSlot audio_slots[kAudioSlots];
     int audio_slot = 0;
     int audio_end = 0;
+    // option "audio_track_slot": what each track of the NEXT avd_audio_features call is -- slot | 0x10 (the track ends); one-shot like the cut list.
+    // It and a non-zero "audio_slot" never hold at once.
+    int audio_map_entries[avd_audio_map::kMaxEntries] = {};
+    int audio_map_n = 0;
+    int audio_map_call[6] = {};     // debug buffer "audio_map_call" of the last list call: tracks, continued tracks, gather / converter launches, analyzer passes, save launches
+    int audio_map_valid = 0;        // 0 until a list call ran
+    int audio_rs_mapped = 0;        // the converter's debug state is a list call's: "audio_pcm" is gathered region by region ("audio_rs_tracks")
     int cnn_chunk = 128;            // CNN extension: frames per forward pass (activation scratch = 4 x 1.6 MB per frame)
     int cnn_fuse = 2;               // CNN extension: a block's 3x3 and expanding 1x1 in one launch (stages 1, 2): 2 = with the 3x3's input slab in LDS in the stride-1 blocks (k_slab3_expand), 1 = gathering kernels only, 0 = layer by layer
     int fb_fused = 0xF;             // bit k: pyramid level k runs the fused kernel (avd_fbfused.hip) instead of the two-kernel path (avd_fbtwo.hip)
@@ -504,6 +517,12 @@ int launch_audio_features(avd_ctx* ctx, const void* d_wav, int format, const avd
 // avd_audio.hip: the frames at d_in (format: option "audio_format"; channels interleaved) to the 16 kHz mono int16 tracks of `plan` at d_pcm
 // (device, plan.n_out + 8 entries, 16-byte aligned)
 int launch_audio_resample(avd_ctx* ctx, const void* d_in, int format, int channels, const avd_resample::Plan& plan, int16_t* d_pcm, const AudioSource& src = AudioSource{});
+// avd_audio.hip: the converter of a call of several tracks (option "audio_track_slot"): the tiles, tile tracks and source rows of `plan` (avd_audio_map.h)
+int launch_audio_resample_map(avd_ctx* ctx, const void* d_in, int format, int channels, const avd_audio_map::Plan& plan, const avd_resample::Ratio& r, long long n_in,
+                              int16_t* d_pcm, bool* launched);
+// avd_audio.hip: the gather and the save launch of a call of several tracks (option "audio_track_slot"); elem: bytes of an analysis sample
+int launch_audio_gather(avd_ctx* ctx, const AudioGatherMove* moves, int count, int elem);
+int launch_audio_slot_save_map(avd_ctx* ctx, int format, int channels, const AudioSaveRow* rows, int count, bool* enqueued);
 // avd_audio.hip: what a call leaves in its audio slot -- the last hist_new_n frames of the track (from the call's n frames at d_in and the old
 // history) as mono int16, and held_words 16-bit words of the analyzer's buffer.  *enqueued is set once the launch has been made (not by a refusal before it)
 int launch_audio_slot_save(avd_ctx* ctx, const void* d_in, int format, long long n, int channels, const int16_t* hist_old, int hist_old_n, int16_t* hist_new,

@@ -494,6 +494,45 @@ int avd_softmax(avd_ctx* ctx, const float* x, int mem, int64_t rows, int cols, f
  * "audio_rs_tracks" gives where the new outputs begin in the analyzer's buffer -- behind the held samples -- and their count.  A slot call
  * that completes no window runs no analysis: "audio_plan", "audio_tracks", "audio_xw" and "audio_mag" then still describe the last call that did.
  *
+ * Several continued tracks per call.  A service that follows K live streams hands over a ROUND of them at once: one more option joins "several
+ * tracks per call" ("audio_cut") and "a track across calls" (the audio slots).  No function is added and AVD_ABI_VERSION stays 3; with an empty
+ * list every call enqueues and returns exactly what it did before the option existed.
+ *   "audio_track_slot" (one-shot list for the NEXT avd_audio_features call, in the manner of "audio_cut"): entries are set one at a time, in track
+ *     order; entry i says what track i of that call is, the tracks being counted by the call's cut list.  Low four bits 0: a whole track, as
+ *     today.  Low four bits k = 1 ... 8: the track continues audio slot k.  Bit 0x10: the call carries that slot's last samples -- the per-track
+ *     form of "audio_end".  -1 clears the list; the option reads back as the number of entries held; at most 64 entries.  Each of these is
+ *     AVD_ERR_ARG with a message that begins "audio_track_slot:" and leaves the list as it was: 0x10 with slot 0; a slot already in the list; a
+ *     65th entry; any other bit or a slot above 8; a set while "audio_slot" is not 0.  Setting "audio_slot" to a non-zero value while the list is
+ *     not empty is refused the same way ("audio_slot: ..."), and the old value stays: the two ways of choosing slots never hold at once, as with
+ *     "stream_slot" / "stream_map".  The next avd_audio_features call takes the list whether it succeeds, is refused or fails.
+ * A call with a list of t entries: the buffer holds t tracks under "audio_cut" (so every track has at least one sample; a stream that ends with
+ * nothing left to give is flushed by a single-slot call with n = 0; n = 0 with a list of ONE entry is that entry's empty call).  All tracks share
+ * win and the context's "audio_rate", "audio_channels" and "audio_format": one rate means one filter bank per call.  Each continued track
+ * follows the slot rule above unchanged -- it forms outputs [M_before, M_after) behind its slot's held samples, writes records W_before ...
+ * W_after - 1, leaves the new history and held remainder in its slot, and with 0x10 empties the slot; whole tracks are what they are in a cut
+ * call.  windows receives the records track after track in call order; a track may write none; max_windows must cover the sum, and a null
+ * windows is accepted only when that sum is 0.
+ * Guarantee: take any number of tracks, any split of each into chunks, and any assignment of chunks to calls and to positions within a call.
+ * Then each track's concatenated records are byte for byte those of ONE slot-0 call on its joined samples, and its concatenated new outputs equal
+ * that call's "audio_pcm"; a call through a list and a call through "audio_slot" may alternate on one slot; and a list of zeros gives the
+ * records and the debug buffers of the same call without a list.
+ * Refusals of a list call, all before anything is staged, every slot untouched, each AVD_ERR_ARG, checked in this order: (1) the argument checks
+ * above; (2) alignment -- 2 bytes for int16, 4 bytes for float32 at every rate, as for a slot call; (3) a cut beyond the buffer ("audio_cut:
+ * beyond the buffer"); (4) a pending "audio_end" ("audio_track_slot: ends are given in the list"), which consumes both the end and the list;
+ * (5) a number of entries other than cuts + 1; (6) for a filled slot, win, rate, channels or format other than at its first call; (7) a track
+ * beyond 2^31 - 1 outputs, or more than 2^31 - 1 samples in the analyzer's buffer of all tracks together; (8) max_windows below the sum of the
+ * tracks' records, or a null windows with records to write, then more than 2^24 records.  (4) ... (8) begin "audio_track_slot:".
+ * Atomicity: every slot's memory is reserved before the first launch; the save is the last launch; the host state of all slots moves only after
+ * the call has drained.  A failure before the save launch leaves every slot as it was; a failure after it empties every slot the call continued,
+ * and says so in the error text.  However many tracks a call has, it runs at most ONE launch of each kind: a gather (every continued track's held
+ * samples to the front of its region of the analyzer's buffer; with "audio_rate" 0 the call's own samples behind them), the converter (each
+ * tile reads its own track's source: chunk, frames absorbed before, history), the analyzer's passes over one window table, the save.
+ * avd_debug_fetch after a list call: "audio_tracks" has one row per track (a track may have count 0); "audio_rs_tracks" gives per track where its
+ * new outputs lie in the analyzer's buffer and how many; "audio_pcm" is the tracks' new outputs side by side in track order; "audio_map_call"
+ * int32[6] -- tracks, continued tracks, gather launches, converter launches, analyzer passes, save launches (each of the last four 0 or 1) -- is
+ * an error before the first list call.  "audio_slot_frames" / "audio_slot_held" / "audio_slot_windows" keep their meaning: select a slot after
+ * the call to read them; "audio_slot_windows" is what the last call that continued this slot wrote for it.
+ *
  * avd_debug_fetch, host state of the last call that ran: "audio_tracks" int32[tracks][3] -- per track its first window, its windows and the length
  * of its last window; "audio_plan" int32[4] -- windows of all tracks, win, the LAST track's last length, windows of all tracks that took the
  * 80 x 100 transform; "audio_host" int32[2] -- the microseconds the host spent forming the tables of the call's short window lengths, and how
