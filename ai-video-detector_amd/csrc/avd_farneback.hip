@@ -863,7 +863,7 @@ int fast_levels(avd_ctx* ctx, const FlowCall& call, int np, FbChunk& chunk)
         kmark(ctx, kLevelId[k]);
         level320_mark(ctx, k == 0);
         if (three) {                                     // (prologue: prev -> a,) a -> b -> a -> b
-            const FbFastLaunch L{call.wide160, 3, from, from_prev ? prev : a, b, a, nullptr, flags, pairdiff};
+            const FbFastLaunch L{call.wide160, false, 3, from, from_prev ? prev : a, b, a, nullptr, flags, pairdiff};
             if (int e = launch_fb_fast(ctx, stream, w, ws.d_poly[k], L, np)) return e;
             a = b;
         } else {
@@ -874,7 +874,12 @@ int fast_levels(avd_ctx* ctx, const FlowCall& call, int np, FbChunk& chunk)
                 // re-run writes its pairs' flow without reading it -- unless the call interleaves it for its caller (flow_tail).  The one reader
                 // after the call, avd_debug_fetch "flow0", has the launch repeated with the stores (launch_flow0_late)
                 const bool unread = mag && !call.dense_flow;
-                const FbFastLaunch L{call.wide160, 1, it == 0 ? from : FbFlowFrom::level, it == 0 && from_prev ? prev : a, b, a, mag, flags, identity, !unread};
+                // 320 px: a launch that reads a flow of its own size may run a pair as one five-block workgroup (FlowCall::wide320); the resizing
+                // first launch has no such form (its flow ring does not fit beside five blocks' rings), so the shapes mix within the level
+                const FbFlowFrom from_it = it == 0 ? from : FbFlowFrom::level;
+                const bool wide320 = k == 0 && call.wide320 && from_it == FbFlowFrom::level;
+                if (wide320) ctx->fb_wide320_launches++;
+                const FbFastLaunch L{call.wide160, wide320, 1, from_it, it == 0 && from_prev ? prev : a, b, a, mag, flags, identity, !unread};
                 if (int e = launch_fb_fast(ctx, stream, w, ws.d_poly[k], L, np)) return e;
                 if (unread) { chunk.flow0_late.pairs = np; chunk.flow0_late.flow_in = a; chunk.flow0_late.flags = flags; chunk.flow0_late.pairdiff = pairdiff; }
                 float* t = a; a = b; b = t;
@@ -955,7 +960,7 @@ int launch_flow0_late(avd_ctx* ctx)
     if (chunk.flow0_late.pairs <= 0) return 0;
     const auto late = chunk.flow0_late;
     float* out = const_cast<float*>(chunk.flow[0]);
-    const FbFastLaunch L{false, 1, FbFlowFrom::level, late.flow_in, out, const_cast<float*>(late.flow_in), nullptr, late.flags, late.pairdiff};
+    const FbFastLaunch L{false, false, 1, FbFlowFrom::level, late.flow_in, out, const_cast<float*>(late.flow_in), nullptr, late.flags, late.pairdiff};
     if (int e = launch_fb_fast(ctx, ctx->stream, S, ws.d_poly[0], L, late.pairs)) return e;
     HIP_TRY(ctx, hipGetLastError());
     chunk.flow0_late = {};

@@ -55,10 +55,11 @@ constexpr int kM = 7;                 // (winsize - 1) / 2
 
 typedef double dbl2 __attribute__((ext_vector_type(2)));
 
-// W level size; NB 64-column blocks per strip; GD lead of the bilinear gather; NPB normal-equation waves per block (2: two
-// entries each per step, 4: one each); XPB solver waves per block (1: four columns per lane, 2: two columns per lane).
+// W level size; NB 64-column blocks per strip; GD lead of the bilinear gather; NPB normal-equation waves per block (1: four
+// entries per step, 2: two entries each, 4: one each); XPB solver waves per block (1: four columns per lane, 2: two columns per lane).
 // 2 + 1 + 1 waves per block is the throughput shape (320 px: the chip is full and total issue counts); 4 + 1 + 2 is the
 // latency shape for the small levels, where a launch is steps x the slowest wave of a step and most CUs are idle anyway.
+// 1 + 1 + 1 exists at 320 px as FIVE blocks ("fb_wide320"): the whole pair in one workgroup of 15 waves, every lane on an image column.
 template <int W_, int NB_, int GD_ = 1, int NPB_ = 2, int XPB_ = 1>
 struct FGeo {
     static constexpr int W = W_, NB = NB_, GD = GD_, NPB = NPB_, XPB = XPB_;
@@ -71,13 +72,19 @@ struct FGeo {
     // who applies the border attenuation and forms the five products of M: the chain wave where the N waves are the pole of a step
     // (throughput shape, 320 px), the N waves where the chain wave is (latency shape: four N waves per block, one entry each per step)
     static constexpr bool PN = NPB == 4;
+    // the strip IS the image row: lane column = image column, nothing clamped and nothing computed twice; the seven replicated border columns on
+    // either side exist in the vsum ring only, where the chain waves of the first and the last block leave them (role_chain)
+    static constexpr bool WHOLE = SW == W;
+    // four waves per SIMD (128 registers): the row part of the input loads' offsets is a scalar (ne_load<true>, avd_fb_device.h)
+    static constexpr bool SROW = PN || NWAVES > 12;
     static constexpr int NE = H + kM;                // entries of the vertical chain: image row min(e, H-1)
     static constexpr int NG = (NE + 3) / 4;          // groups of four entries
     static constexpr int T = ((NG + 2 + 3) / 4) * 4; // steps (= barriers): N on group t, C on t-1, X on t-2; the loops unroll by 4
     // doubles per (row slot, channel) line.  Four columns per lane: lanes stride 32 bytes, ROWLEN % 4 == 2 puts the four
     // rows of a solver instruction on different halves of a 32-byte bank pair.  Two columns per lane: lanes stride 16
     // bytes (a row's 16 lanes = one 256-byte bank row), ROWLEN % 32 == 0 keeps the rows of an instruction on it
-    static constexpr int ROWLEN = XPB == 1 ? SW + 18 : ((SW + 18 + 31) / 32) * 32;
+    // (WHOLE: 8 + 7 replicas + W + 7 replicas; the solver's last chunk reads up to index 8 + W - 4 + 17)
+    static constexpr int ROWLEN = WHOLE ? W + 8 + 2 * kM : XPB == 1 ? SW + 18 : ((SW + 18 + 31) / 32) * 32;
     static constexpr int VS_SLOT = 5 * ROWLEN;
     static constexpr int VS_DOUBLES = 8 * VS_SLOT;   // ring of 8 image rows of vsum
     static constexpr int M_SLOT = 5 * 64;            // floats of one row of one block
@@ -87,8 +94,19 @@ struct FGeo {
     // flow resized x 2 -- a few rows ahead of the N waves, in a ring of 16 rows x 2 components per block
     static constexpr int F_SLOT = 2 * 64;            // floats of one row of one block
     static constexpr int F_FLOATS = NB * 16 * F_SLOT;
-    static_assert((LDS_DOUBLES + F_FLOATS / 2) * 8 <= 163840 && NWAVES <= 16, "LDS layout, workgroup size");
-    static_assert(H % 4 == 0 && (NPB == 2 || NPB == 4) && (XPB == 1 || XPB == 2), "whole groups of image rows");
+    template <bool UP> static constexpr int lds_doubles() { return LDS_DOUBLES + (UP ? F_FLOATS / 2 : 0); }   // (the flow ring only where an UP form is instantiated)
+    static_assert(LDS_DOUBLES * 8 + 8 <= 163840 && NWAVES <= 16, "LDS layout, workgroup size");
+    static_assert(H % 4 == 0 && (NPB == 1 || NPB == 2 || NPB == 4) && (XPB == 1 || XPB == 2), "whole groups of image rows");
+    static_assert((2 * (GD + 1)) % EPS == 0 && (XPB != 1 || ROWLEN % 4 == 2), "whole steps per loop body; bank layout of the solver's reads");
+};
+
+// a double of lane `src` (wave-uniform, known when compiled) in every lane
+template <int SRC>
+__device__ __forceinline__ double lane_value(double v)
+{
+    const unsigned long long u = __builtin_bit_cast(unsigned long long, v);
+    const unsigned lo = __builtin_amdgcn_readlane((int)(unsigned)u, SRC), hi = __builtin_amdgcn_readlane((int)(unsigned)(u >> 32), SRC);
+    return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
 };
 
 // workgroup barrier; debug builds (-DAVD_FBF_DEBUG) account the cycles a wave spends waiting at it
@@ -157,7 +175,7 @@ __device__ __forceinline__ bool role_ne(const float* __restrict__ R, const float
     auto flow_of = [&](int row, NeIn& s) { const float* f = fring + (row & 15) * Ge::F_SLOT + lane; s.dx = f[0]; s.dy = f[64]; };
     auto load_in = [&](int row, NeIn& s) {
         if (UP) ne_load_r0(R, r0base, x, row, W, s);
-        else ne_load<Ge::PN>(R, flow, r0base, flbase, x, row, W, plane, s);
+        else ne_load<Ge::SROW>(R, flow, r0base, flbase, x, row, W, plane, s);
     };
     bool first = skip != nullptr;                          // the first barrier of this role has not been passed yet
     if (UP) {
@@ -296,7 +314,7 @@ __device__ __forceinline__ bool role_chain(const float* __restrict__ mring, doub
     const float sx = border_factor(x, W);                 // x part of the border attenuation: a per-lane constant
     float ring[16][5];                                   // ring[e & 15] = M row of entry e (statically indexed)
     double vs[5] = {0., 0., 0., 0., 0.};
-    double* vdst = vsring + 8 + 64 * b + lane;
+    double* vdst = vsring + 8 + (Ge::WHOLE ? kM : 0) + 64 * b + lane;
     const unsigned pbase = (unsigned)p * 2u * (W / 2) * (H / 2);
     UpRows<Ge> up;
     bool first = skip != nullptr;
@@ -348,6 +366,17 @@ __device__ __forceinline__ bool role_chain(const float* __restrict__ mring, doub
                             double* d = vdst + ((e - kM) & 7) * Ge::VS_SLOT;
 #pragma unroll
                             for (int c = 0; c < 5; c++) d[c * Ge::ROWLEN] = vs[c];
+                            if constexpr (Ge::WHOLE) {
+                                // cv2's replicated border of vsum: column 0 (lane 0 of block 0) to the seven slots on its left, column W - 1 (lane 63
+                                // of the last block) to the seven on its right -- what the halo lanes of a strip compute for themselves
+                                if (b == 0) {                                // wave-uniform
+#pragma unroll
+                                    for (int c = 0; c < 5; c++) { const double v = lane_value<0>(vs[c]); if (lane < kM) d[c * Ge::ROWLEN - kM] = v; }
+                                } else if (b == Ge::NB - 1) {
+#pragma unroll
+                                    for (int c = 0; c < 5; c++) { const double v = lane_value<63>(vs[c]); if (lane < kM) d[c * Ge::ROWLEN + 64] = v; }
+                                }
+                            }
                         }
 #pragma unroll
                         for (int c = 0; c < 5; c++) ring[kk][c] = a[c];
@@ -504,7 +533,9 @@ __global__ __launch_bounds__((64 * Ge::NWAVES)) void k_fb_fast(const float* __re
     static_assert(IT == 1 || IT == 3, "one iteration per launch, or all three");
     static_assert(!(UP && (PRO || IT > 1 || Ge::PN)), "the chain wave's resize belongs to one-iteration launches of the throughput shape");
     static_assert(ST || (IT == 1 && !UP && !PRO), "only a level's last launch may leave its flow unwritten");
-    __shared__ __align__(16) double lds[Ge::LDS_DOUBLES + (UP ? Ge::F_FLOATS / 2 : 0)];
+    static_assert(Ge::template lds_doubles<UP>() * 8 + 8 <= 163840, "LDS layout");
+    static_assert(!(Ge::WHOLE && (UP || PRO || IT > 1)), "a pair as one workgroup at 320 px: the flow ring of the resizing form does not fit");
+    __shared__ __align__(16) double lds[Ge::template lds_doubles<UP>()];
     double* vsring = lds;
     float* mrings = reinterpret_cast<float*>(lds + Ge::VS_DOUBLES);
     const int lane = threadIdx.x & 63;
@@ -530,12 +561,27 @@ __global__ __launch_bounds__((64 * Ge::NWAVES)) void k_fb_fast(const float* __re
         const int pos = wave & 3, grp = wave >> 2;
         b = pos == 3 ? grp : pos;
         role = pos == 3 ? 0 : (grp == 0 ? 3 : (grp == 1 ? 1 : 2));
+    } else if (NB == 5 && Ge::WPB == 3) {
+        // 15 waves, waves w, w + 4, w + 8, w + 12 share a SIMD: {X0, X1, C0, C1}, {X2, X3, C2, C3}, {X4, N0, N1, C4}, {N2, N3, N4} (role and block).
+        // VALU issue cycles per step from this shape's ISA (tools/isa_loop_table.py): X 849 (the two-strip shape's loop, instruction for instruction), N 650 (four
+        // entries: 325 VALU instructions and 40 loads; two waves of the two-strip shape are 2 x 329), C 307 as before plus, in blocks 0 and 4, ten v_readlane and
+        // five masked LDS stores per row for the replicas: 2312 / 2312 / 2456 / 1950 per SIMD of a step that measures ~5 900 cycles (203 us / 84 steps; the two-strip
+        // shape: 1485 of ~3 500).  No spills, no scratch: 128 VGPRs, 160 648 B of LDS (profiles/fbfast320_wide_ab.txt)
+        //   wave   0  1  2  3  4  5  6  7  8  9 10 11 12 13 14
+        //   role   X  X  X  N  X  X  N  N  C  C  N  N  C  C  C     (N = 0, C = 1, X = 2: two bits per wave)
+        //   block  0  2  4  2  1  3  0  3  0  2  1  4  1  3  4     (three bits per wave)
+        constexpr unsigned kRole = 2u | 2u << 2 | 2u << 4 | 0u << 6 | 2u << 8 | 2u << 10 | 0u << 12 | 0u << 14 | 1u << 16 | 1u << 18 | 0u << 20 | 0u << 22
+                                   | 1u << 24 | 1u << 26 | 1u << 28;
+        constexpr unsigned long long kBlock = 0ull | 2ull << 3 | 4ull << 6 | 2ull << 9 | 1ull << 12 | 3ull << 15 | 0ull << 18 | 3ull << 21 | 0ull << 24
+                                              | 2ull << 27 | 1ull << 30 | 4ull << 33 | 1ull << 36 | 3ull << 39 | 4ull << 42;
+        role = (int)(kRole >> (2 * wave)) & 3;
+        b = (int)(kBlock >> (3 * wave)) & 7;
     } else {
         b = wave / Ge::WPB;
         role = (wave % Ge::WPB + b) % Ge::WPB;            // rotate the roles over a block's waves: every SIMD gets a mix
     }
-    const int xu = o0 - kM + 64 * b + lane;               // image column of this lane (clamped: replicated border)
-    const int x = xu < 0 ? 0 : (xu > W - 1 ? W - 1 : xu);
+    const int xu = (Ge::WHOLE ? 0 : o0 - kM) + 64 * b + lane;   // image column of this lane (clamped: replicated border; WHOLE: the lane's own column)
+    const int x = Ge::WHOLE ? xu : (xu < 0 ? 0 : (xu > W - 1 ? W - 1 : xu));
     float* mring = mrings + b * 8 * Ge::M_SLOT;
     float* fring = reinterpret_cast<float*>(lds + Ge::LDS_DOUBLES) + b * 16 * Ge::F_SLOT;   // UP only
     // ONE lane reads the pair's flag word (every thread reading it for itself could see different values while another strip of the pair raises it:
@@ -603,7 +649,7 @@ void launch_fast(hipStream_t stream, const float* R, const FbFastLaunch& L, floa
     // spare).  At 320 px it costs the launch 3.5 us and saves k_flow_up's 37; the 160-px level's one-strip shape is the same wave mix.  The
     // latency shapes are bound by exactly the chain wave that would do it (160 px, two strips: 45 -> 84 us per launch against 12 saved)
     const bool pro = L.from == FbFlowFrom::prologue, three = L.iterations == 3;
-    if constexpr (Ge::W == 320 || (Ge::W == 160 && !Ge::PN)) { if (L.from == FbFlowFrom::chain) return go(k_fb_fast<Ge, true>, 0); }
+    if constexpr ((Ge::W == 320 && !Ge::WHOLE) || (Ge::W == 160 && !Ge::PN)) { if (L.from == FbFlowFrom::chain) return go(k_fb_fast<Ge, true>, 0); }
     if constexpr (Ge::W == 160 || Ge::W == 80) { if (pro && !three) return go(k_fb_fast<Ge, false, 1, true>, 0); }
     if constexpr (Ge::W == 80) { if (pro && three) return go(k_fb_fast<Ge, false, 3, true>, 0); }
     if constexpr (Ge::W == 80 || Ge::W == 40) { if (three) return go(k_fb_fast<Ge, false, 3, false>, zero_first); }
@@ -628,12 +674,20 @@ int launch_fb_fast(avd_ctx* ctx, hipStream_t stream, int w, const float* R, cons
     if (!ok) { ctx->err = "launch_fb_fast: this mode does not exist at this level size"; return AVD_ERR_ARG; }
     const bool uses_tmp = three || L.from == FbFlowFrom::prologue;
     if (!L.store_flow && !(w == 320 && one && L.from == FbFlowFrom::level && L.mag_out)) { ctx->err = "launch_fb_fast: only the 320-px level's last launch can leave its flow unwritten"; return AVD_ERR_ARG; }
+    if (L.wide320 && !(w == 320 && one && L.from == FbFlowFrom::level)) { ctx->err = "launch_fb_fast: the five-block shape exists for the 320-px level's one-iteration launches from a flow of its own size"; return AVD_ERR_ARG; }
     if (L.flow_in == L.flow_out || (uses_tmp && (!L.flow_tmp || L.flow_tmp == L.flow_out))) { ctx->err = "launch_fb_fast: the flow is not updated in place"; return AVD_ERR_ARG; }
     switch (w) {
     case 320:
         // (neighbour-shared gathers -- each lane loads its left pixel, the right one comes from lane + 1 by a DPP wave shift -- were built,
         // bit-identical and slower, 164 us per launch against 142: profiles/r04_experiments.md section 2; the code is in the history, commit 3e8b43a)
-        launch_fast<FGeo<320, 3, 2, 2, 1>>(stream, R, L, L.mag_out, np, 2, 160);
+        // two shapes for the launches that read a 320-px flow (FbFastLaunch::wide320, decided per call like wide160: "fb_wide320"): two strips of three blocks,
+        // 12 waves each -- 384 lane columns per pair, 14 halo columns computed twice, half a solver wave masked -- or the pair as ONE workgroup of five blocks,
+        // 15 waves: 320 lanes on 320 columns, 5/6 of the wave rows of every role, one normal-equation wave per block with four entries per step.  Every column
+        // is computed by the same instructions on the same operands, and the solver's chunks of four start at multiples of 4 in both: bit-identical on any content.
+        // Measured (profiles/fbfast320_wide_ab.txt): 120 workgroups x (207 + 199) us against 238 x (127 + 122) us for the level's second and third launch, -18 % CU-microseconds;
+        // three clips in flight +2.5 % frames/s; one clip alone is 0.16 ms slower, which is why the shape is chosen per call.
+        if (L.wide320) launch_fast<FGeo<320, 5, 1, 1, 1>>(stream, R, L, L.mag_out, np, 1, 320);
+        else launch_fast<FGeo<320, 3, 2, 2, 1>>(stream, R, L, L.mag_out, np, 2, 160);
         break;
     case 160:
         // two shapes (ctx->fb_wide160; default 2 = chosen per call, see below): a pair as ONE strip of three blocks with the 320-px level's wave mix (119 workgroups of 12 waves,

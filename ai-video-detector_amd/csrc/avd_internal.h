@@ -178,6 +178,7 @@ struct ClipSlot {
 struct FlowCall {
     int model;                         // option "cv2_model" as it stood when the call was enqueued: every chunk and the deferred exact re-run follow it
     bool wide160;                      // fast mode: the 160-px level as one three-block strip per pair (see avd_ctx::fb_wide160)
+    bool wide320;                      // fast mode: the 320-px level's launches that read a 320-px flow as one five-block workgroup per pair (see avd_ctx::fb_wide320)
     bool dense_flow;                   // the caller fetches the interleaved flow (ws.d_flow_il, reserved): the chunks' flow_tail interleaves it
 };
 // Option "cv2_model": the oracle's model switches (its header; the same bit values) that the library follows.  What each bit changes in the
@@ -367,6 +368,12 @@ struct avd_ctx {
     int fb_fold_blur = 1;           // the 320-px scale's 3 x 3 pyramid blur formed inside the polynomial expansion (no effect on results); AVD_FB_FOLD_BLUR / avd_set_option
     int fb_wide160 = 2;             // fast mode: the 160-px level as one three-block strip per pair (1: fewer CU-microseconds, throughput) or as two strips (0: shorter launches, latency);
                                     // 2 (default) = by what is in flight when the call is enqueued: one strip if another context of the process holds an undrained call, two if this clip is alone; AVD_FB_WIDE160 / avd_set_option
+    int fb_wide320 = 2;             // fast mode: the launches of the 320-px level that read a 320-px flow run a pair as ONE workgroup of five 64-column blocks, 15 waves (1: no halo columns,
+                                    // no idle solver lanes: 120 x 203 us instead of 238 x 124 us per launch, throughput) or as two strips of three blocks (0: a launch is 80 us shorter, latency);
+                                    // 2 (default) = per call by what is in flight, as fb_wide160 = 2.  Bit-identical results on any content (the same instructions on the same operands per
+                                    // column); AVD_FB_WIDE320 / avd_set_option
+    int fb_wide320_used = 0;        // read-only option "fb_wide320_used": FlowCall::wide320 of the last fast-mode call, written when it is enqueued; no launcher reads it
+    int fb_wide320_launches = 0;    // debug buffer "fb_wide320_launches": launches of the last call that ran the Farneback stage (all its chunks) in the five-block shape
     int counted_in_flight = 0;      // this context's enqueued call is counted in avd_calls_in_flight()
     int fb_wide160_used = 0;        // read-only option "fb_wide160_used": FlowCall::wide160 of the last fast-mode call, written when it is enqueued; no launcher reads it
     int gemm_waves = 8;             // patch-embed GEMM: waves per workgroup (8: 8 x 4 MFMA tiles per wave, 16: 4 x 4; measured no faster), the same 256 x 256 tile; AVD_GEMM_WAVES / avd_set_option
@@ -557,6 +564,7 @@ int launch_fb_two(avd_ctx* ctx, hipStream_t stream, int w, const float* R, float
 enum class FbFlowFrom { level, zero, chain, prologue };   // the result is in flow_out (3 iterations: flow_tmp is the second buffer); nothing is updated in place
 struct FbFastLaunch {
     bool wide160;                                // the 160-px shape of the call (FlowCall::wide160); no other level reads it
+    bool wide320;                                // 320 px: this launch runs a pair as one five-block workgroup (from = level, 1 iteration only); no other level reads it
     int iterations; FbFlowFrom from; const float* flow_in; float *flow_out, *flow_tmp;
     float* mag_out;                              // 320-px level, last iteration (else null): float[pair][320][320] receives |flow|
     int* flags; const int* pairdiff;             // may be null, see avd_fbfast.hip

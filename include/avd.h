@@ -641,6 +641,13 @@ int avd_set_profiling(avd_ctx* ctx, int enable);
  * launch 10 us shorter: one clip alone finishes ~25 us sooner), 2 (default) = chosen ONCE when the call is enqueued, for all its launches: one strip if another context of the
  * process holds an undrained avd_analyze_* call, two strips if this clip has the chip to itself.  Same guarantee; the two shapes group the solver's
  * window sums differently (bit-identical on well-posed content, tests/test_gpu_fbfast.py).
+ * "fb_wide320" (fast mode, environment AVD_FB_WIDE320; no effect on results): the shape of the 320-px level's launches that read a 320-px flow
+ * (its second and third; with bit 1 of "fb_fold_up" clear the first as well).  1 = a pair is ONE workgroup of five 64-column blocks, 15 waves:
+ * every lane on an image column, no halo columns computed twice, no masked solver lanes (a launch takes 203 us on 120 CUs instead of 124 us on 238:
+ * -18 % CU-microseconds, +2.5 % frames/s with three clips in flight); 0 = two strips of three blocks, 12 waves each (one clip alone finishes 0.16 ms sooner);
+ * 2 (default) = chosen once per call by what is in flight, exactly as "fb_wide160" = 2.  Every column is computed by the same instructions on the same
+ * operands in both shapes: flow, |flow| and flag words are bit-identical on any content (tests/test_gpu_fbfast_wide320.py).  Read-only
+ * "fb_wide320_used": the shape the last fast-mode call took; avd_debug_fetch "fb_wide320_launches" (int32[1]): its launches in the new shape.
  * "fb_fused" (exact mode only, no effect on results): bit k set = pyramid level k (0 = 320x320 .. 3 = 40x40)
  * of the Farneback stage runs the fused level kernel (default 0xF, or the environment variable AVD_FB_FUSED at
  * avd_create); clear = the two-kernel path that exchanges its double intermediate through HBM.  "cnn_tiles": tiling of the
