@@ -904,11 +904,25 @@ class Context:
         g = math.gcd(int(rate), cls.AUDIO_OUT_RATE)
         return -(-int(n) * (cls.AUDIO_OUT_RATE // g) // (int(rate) // g))
 
-    def _audio_call(self, ptr, mem, n: int, win: int, nwin: int, pcm16: bool, cuts=(), rate=None, channels: int = 1, last: bool = False, entries=()) -> np.ndarray:
+    def _audio_call(self, ptr, mem, n: int, win: int, nwin: int, pcm16: bool, cuts=(), rate=None, channels: int = 1, last: bool = False, entries=(),
+                    layout: int = 0, stride: int = 0) -> np.ndarray:
         """One avd_audio_features call: option "audio_format" -- and, for a track at its decoder's rate, "audio_rate" and "audio_channels" -- set for
         it and restored (also after an exception), its cuts set in ascending order.  last: option "audio_end" is set for it (a slot call).
-        entries: the "audio_track_slot" list of the call, set in track order and cleared if setting it fails (a call takes it whatever becomes of it)."""
+        entries: the "audio_track_slot" list of the call, set in track order and cleared if setting it fails (a call takes it whatever becomes of it).
+        layout (an "audio_layout" value, not 0) and stride: options "audio_layout" / "audio_plane_stride" are set and restored the same way, in place
+        of "audio_channels"; without a layout neither is touched."""
         out = np.zeros(nwin, AUDIO_WINDOW_DTYPE)
+        if rate is not None and layout:
+            was = self.get_option("audio_rate"), self.get_option("audio_layout"), self.get_option("audio_plane_stride")
+            self.set_option("audio_rate", int(rate))          # a refused value leaves the options as they were: nothing has been set yet
+            try:
+                self.set_option("audio_layout", int(layout))
+                self.set_option("audio_plane_stride", int(stride))
+                return self._audio_call(ptr, mem, n, win, nwin, pcm16, cuts, None, 1, last, entries)
+            finally:
+                self.set_option("audio_rate", was[0])
+                self.set_option("audio_layout", was[1])
+                self.set_option("audio_plane_stride", was[2])
         if rate is not None:
             # a refused value leaves the options as they were: nothing has been set yet
             was = self.get_option("audio_rate"), self.get_option("audio_channels")
@@ -954,6 +968,74 @@ class Context:
             raise ValueError("wav does not hold whole frames of %d channels" % channels)
         return wav, channels
 
+    AUDIO_LAYOUTS = (1, 2, 6, 8)             # option "audio_layout": mono, stereo, 5.1, 7.1 -- the id is the channel count
+    AUDIO_PLANAR = 0x100
+
+    def _audio_layout_source(self, wav, rate, layout, planar: bool):
+        """A track with a layout (option "audio_layout") -> (ptr, mem, frames, pcm16, option value, plane stride, keepalive).  Interleaved: [n, c]
+        or flat, as _audio_frames takes it.  planar: [c, n], and a column slice of a wider array (dense rows, one row stride) goes through as it
+        lies, the row stride being the plane stride; anything else is copied dense first.  Device tensors likewise."""
+        layout = int(layout)
+        if rate is None:
+            raise ValueError("layout needs rate: a layout describes a track at its decoder's rate")
+        if layout not in self.AUDIO_LAYOUTS:
+            raise ValueError("layout must be one of %s (the channel count)" % (self.AUDIO_LAYOUTS,))
+        pcm16 = self._is_pcm16(wav)
+        if not planar:
+            flat, channels = self._audio_frames(wav, layout)
+            if channels != layout:
+                raise ValueError("wav holds frames of %d channels, layout %d" % (channels, layout))
+            ptr, mem, size, keep = self._audio_ptr(flat, pcm16)
+            return ptr, mem, size // layout, pcm16, layout, 0, keep
+        if wav.ndim == 1 and layout == 1:
+            wav = wav.reshape(1, -1)
+        if wav.ndim != 2 or int(wav.shape[0]) != layout:
+            raise ValueError("planar wav must be [%d, n]" % layout)
+        n = int(wav.shape[1])
+        if _is_torch_tensor(wav):
+            if str(wav.dtype) != ("torch.int16" if pcm16 else "torch.float32"):
+                raise ValueError("wav must be float32 or int16")
+            t = wav
+            if n and (t.stride(1) != 1 or (layout > 1 and t.stride(0) < n)):
+                t = t.contiguous()
+            if t.is_cuda:
+                self._after_torch_stream(t)
+            stride = int(t.stride(0)) if layout > 1 and n else n
+            return t.data_ptr(), (AVD_MEM_DEVICE if t.is_cuda else AVD_MEM_HOST), n, pcm16, layout | self.AUDIO_PLANAR, stride, t
+        item = 2 if pcm16 else 4
+        a = np.asarray(wav, dtype=np.int16 if pcm16 else np.float32)
+        if n and (a.strides[1] != item or (layout > 1 and (a.strides[0] < n * item or a.strides[0] % item))):
+            a = np.ascontiguousarray(a)
+        stride = a.strides[0] // item if layout > 1 and n else n
+        return a.ctypes.data, AVD_MEM_HOST, n, pcm16, layout | self.AUDIO_PLANAR, stride, a
+
+    def _audio_layout_join(self, tracks, rate, layout, planar: bool, what: str):
+        """Several tracks with one layout, joined along the frame axis for one call -> (_audio_layout_source of the joined buffer, frames per track)"""
+        pcm = {self._is_pcm16(t) for t in tracks}
+        if len(pcm) != 1:
+            raise ValueError("%s: the tracks must be all float32 or all int16" % what)
+        on_device = {bool(_is_torch_tensor(t) and t.is_cuda) for t in tracks}
+        if len(on_device) != 1:
+            raise ValueError("%s: the tracks must be all host arrays or all device tensors" % what)
+        layout = int(layout)
+        if planar:
+            tracks = [t.reshape(1, -1) if t.ndim == 1 and layout == 1 else t for t in tracks]
+            if any(t.ndim != 2 or int(t.shape[0]) != layout for t in tracks):
+                raise ValueError("planar wav must be [%d, n]" % layout)
+            lens, axis = [int(t.shape[1]) for t in tracks], 1
+        else:
+            framed = [self._audio_frames(t, layout) for t in tracks]
+            if any(c != layout for _, c in framed):
+                raise ValueError("%s: the tracks must hold frames of %d channels" % (what, layout))
+            tracks = [t.reshape(-1, layout) for t, _ in framed]
+            lens, axis = [int(t.shape[0]) for t in tracks], 0
+        if on_device.pop():
+            import torch
+            whole = torch.cat(list(tracks), dim=axis)
+        else:
+            whole = np.concatenate([np.asarray(t.numpy() if _is_torch_tensor(t) else t) for t in tracks], axis=axis)
+        return self._audio_layout_source(whole, rate, layout, planar), lens
+
     AUDIO_SLOTS = 8
 
     @classmethod
@@ -975,15 +1057,19 @@ class Context:
         usable = int(frames) if last else max(0, int(frames) - T // 2)
         return -(-usable * U // D)
 
-    def _audio_slot_features(self, wav, win: int, rate, channels: int, slot: int, last: bool) -> np.ndarray:
+    def _audio_slot_features(self, wav, win: int, rate, channels: int, slot: int, last: bool, layout=None, planar: bool = False) -> np.ndarray:
         """audio_features with a slot: option "audio_slot" set for the call and restored, also after an exception"""
-        pcm16 = self._is_pcm16(wav)
-        if rate is not None:
-            wav, channels = self._audio_frames(wav, channels)
+        code = stride = 0
+        if layout is not None:
+            ptr, mem, n, pcm16, code, stride, keep = self._audio_layout_source(wav, rate, layout, planar)
         else:
-            channels = 1
-        ptr, mem, size, keep = self._audio_ptr(wav, pcm16)
-        n = size // channels
+            pcm16 = self._is_pcm16(wav)
+            if rate is not None:
+                wav, channels = self._audio_frames(wav, channels)
+            else:
+                channels = 1
+            ptr, mem, size, keep = self._audio_ptr(wav, pcm16)
+            n = size // channels
         was = self.get_option("audio_slot")
         self.set_option("audio_slot", int(slot))          # a refused value leaves the option as it was
         try:
@@ -999,12 +1085,12 @@ class Context:
                 nwin = (held + -(-(n + T) * U // D) + 1) // win + 1
             else:
                 nwin = 0                                   # the library refuses (AvdError)
-            rec = self._audio_call(ptr, mem, n, win, nwin, pcm16, (), rate, channels, last)
+            rec = self._audio_call(ptr, mem, n, win, nwin, pcm16, (), rate, channels, last, (), code, stride)
             return rec if exact else rec[:int(np.count_nonzero(rec["length"]))]
         finally:
             self.set_option("audio_slot", was)
 
-    def audio_features(self, wav, win: int, rate=None, channels: int = 1, slot: int = 0, last: bool = False) -> np.ndarray:
+    def audio_features(self, wav, win: int, rate=None, channels: int = 1, slot: int = 0, last: bool = False, layout=None, planar: bool = False) -> np.ndarray:
         """wav: mono samples, float32 or 16-bit PCM as decoded (int16: sample s counts as float32(s) * 2^-15, converted on the device), numpy or
         torch-ROCm tensor -> structured array (AUDIO_WINDOW_DTYPE) per window.
 
@@ -1015,9 +1101,19 @@ class Context:
         slot (1 ... AUDIO_SLOTS): the call CONTINUES the track of that audio slot (option "audio_slot", set for this call and restored, also after
         an exception) and returns the records of the windows this call completes -- possibly none; last=True marks the track's final call
         (option "audio_end"), which hands out the short last window and empties the slot.  wav may be empty.  The concatenated results of a
-        track's calls are byte for byte the result of one slot-0 call on the joined samples."""
+        track's calls are byte for byte the result of one slot-0 call on the joined samples.
+
+        layout (one of AUDIO_LAYOUTS: 1 mono, 2 stereo, 6 5.1, 8 7.1 in FFmpeg's native channel order; needs rate): the track goes to the device as
+        its decoder handed it over and is downmixed there by the layout's weights (options "audio_layout" / "audio_plane_stride", set for this call
+        and restored; ``channels`` is not read).  wav is [n, layout] or flat interleaved; with planar=True it is [layout, n], one plane per channel,
+        and a column slice of a wider array (ring[:, a:b]) goes through as it lies.  Without layout nothing of this is touched."""
         if slot:
-            return self._audio_slot_features(wav, int(win), rate, channels, slot, bool(last))
+            return self._audio_slot_features(wav, int(win), rate, channels, slot, bool(last), layout, bool(planar))
+        if layout is not None:
+            ptr, mem, n, pcm16, code, stride, keep = self._audio_layout_source(wav, rate, layout, planar)
+            n_out = self.audio_converted_length(n, rate) if rate in self.AUDIO_RATES else 0          # another rate: the library refuses (AvdError)
+            nwin = (n_out + win - 1) // win if n_out and win > 0 else 0
+            return self._audio_call(ptr, mem, n, win, nwin, pcm16, (), rate, layout, False, (), code, stride)
         pcm16 = self._is_pcm16(wav)
         if rate is None:
             ptr, mem, n, keep = self._audio_ptr(wav, pcm16)
@@ -1032,16 +1128,41 @@ class Context:
 
     AUDIO_TRACKS_PER_CALL = 64
 
-    def audio_features_many(self, tracks, win: int, rate=None, channels: int = 1) -> list:
+    def audio_features_many(self, tracks, win: int, rate=None, channels: int = 1, layout=None, planar: bool = False) -> list:
         """Several mono tracks in as few calls as possible (option "audio_cut": up to 64 tracks share one call and fill the chip together).
         tracks: all float32 or all int16, all host arrays (numpy, host tensors) or all device tensors.  Host tracks are concatenated once, device
         tracks go through one torch.cat.  -> one record array per track, in order: byte for byte what audio_features gives for that track alone.
 
         rate: every track is frames at that rate with the same channel count (see audio_features); the cuts are frame positions, and each track is
-        converted from its own start."""
+        converted from its own start.
+
+        layout / planar: as for audio_features, the same for every track; planar tracks are [layout, n_i] and are joined along the frame axis."""
         tracks = list(tracks)
         if not tracks:
             return []
+        if layout is not None:
+            (ptr, mem, _, pcm16, code, stride, keep), lens = self._audio_layout_join(tracks, rate, layout, bool(planar), "audio_features_many")
+            win = int(win)
+            per = win if 1 <= win <= 8192 else 0
+            analysed = [self.audio_converted_length(n, rate) if rate in self.AUDIO_RATES else 0 for n in lens]
+            size = (2 if pcm16 else 4) * (1 if planar else int(layout))        # bytes from a frame to the next, in a plane or interleaved
+            results = [None] * len(tracks)
+            live = [i for i, n in enumerate(lens) if n > 0]
+            starts = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+            for g in range(0, len(live), self.AUDIO_TRACKS_PER_CALL):
+                group = live[g:g + self.AUDIO_TRACKS_PER_CALL]
+                first, end = int(starts[group[0]]), int(starts[group[-1] + 1])
+                counts = [(analysed[i] + per - 1) // per if per else 0 for i in group]
+                cuts = [int(starts[i]) - first for i in group[1:]]
+                rec = self._audio_call(ptr + first * size, mem, end - first, win, sum(counts), pcm16, cuts, rate, int(layout), False, (), code, stride)
+                at = 0
+                for i, c in zip(group, counts):
+                    results[i] = rec[at:at + c]
+                    at += c
+            for i, n in enumerate(lens):
+                if n == 0:
+                    results[i] = np.zeros(0, AUDIO_WINDOW_DTYPE)
+            return results
         if rate is not None:
             framed = [self._audio_frames(t, channels) for t in tracks]
             if len({c for _, c in framed}) != 1:
@@ -1096,36 +1217,43 @@ class Context:
 
     AUDIO_TRACK_END = 0x10
 
-    def audio_features_mapped(self, chunks, slots, lasts, win: int, rate=None, channels: int = 1) -> list:
+    def audio_features_mapped(self, chunks, slots, lasts, win: int, rate=None, channels: int = 1, layout=None, planar: bool = False) -> list:
         """Several tracks in ONE call, each a whole track or the continuation of an audio slot (option "audio_track_slot", set for this call; it and
         the cuts are gone after it, also after an exception).  chunks[i] is what audio_features takes for one track -- all float32 or all int16, all
         host arrays or all device tensors, at least one frame each; slots[i] = 0 says it is a whole track, 1 ... AUDIO_SLOTS that it continues that
         slot (each slot once); lasts[i] that it carries the slot's last samples.  Host chunks are concatenated once, device chunks go through one
         torch.cat.  -> one record array per track, in order: for a slot the windows this call completes (possibly none), the concatenated results
         of a track's calls being byte for byte the result of one slot-0 call on the joined samples.  The gather, converter, analyzer and save each
-        run once per call, however many tracks it has."""
+        run once per call, however many tracks it has.
+
+        layout / planar: as for audio_features, the same for every chunk; planar chunks are [layout, n_i] and are joined along the frame axis."""
         chunks, slots, lasts = list(chunks), [int(s) for s in slots], [bool(l) for l in lasts]
         if not chunks or not (len(chunks) == len(slots) == len(lasts)):
             raise ValueError("audio_features_mapped: one slot and one end mark per chunk, at least one chunk")
         if len(chunks) > self.AUDIO_TRACKS_PER_CALL:
             raise ValueError("audio_features_mapped: at most %d tracks per call" % self.AUDIO_TRACKS_PER_CALL)
-        if rate is not None:
+        joined = None
+        if layout is not None:
+            joined, lens = self._audio_layout_join(chunks, rate, layout, bool(planar), "audio_features_mapped")
+            pcm16, channels = joined[3], int(layout)
+        elif rate is not None:
             framed = [self._audio_frames(t, channels) for t in chunks]
             if len({c for _, c in framed}) != 1:
                 raise ValueError("audio_features_mapped: the tracks must have one channel count")
             chunks, channels = [t for t, _ in framed], framed[0][1]
         else:
             channels = 1
-        pcm = {self._is_pcm16(t) for t in chunks}
-        if len(pcm) != 1:
-            raise ValueError("audio_features_mapped: the tracks must be all float32 or all int16")
-        pcm16 = pcm.pop()
-        on_device = {bool(_is_torch_tensor(t) and t.is_cuda) for t in chunks}
-        if len(on_device) != 1:
-            raise ValueError("audio_features_mapped: the tracks must be all host arrays or all device tensors")
-        if any(t.ndim != 1 for t in chunks):
-            raise ValueError("wav must be float32[n] or int16[n]")
-        lens = [int(t.shape[0]) // channels for t in chunks]          # frames
+        if joined is None:
+            pcm = {self._is_pcm16(t) for t in chunks}
+            if len(pcm) != 1:
+                raise ValueError("audio_features_mapped: the tracks must be all float32 or all int16")
+            pcm16 = pcm.pop()
+            on_device = {bool(_is_torch_tensor(t) and t.is_cuda) for t in chunks}
+            if len(on_device) != 1:
+                raise ValueError("audio_features_mapped: the tracks must be all host arrays or all device tensors")
+            if any(t.ndim != 1 for t in chunks):
+                raise ValueError("wav must be float32[n] or int16[n]")
+            lens = [int(t.shape[0]) // channels for t in chunks]          # frames
         if min(lens) < 1:
             raise ValueError("audio_features_mapped: every track of the call needs a frame (flush an empty stream with audio_features(..., slot=k, last=True))")
         win = int(win)
@@ -1149,16 +1277,20 @@ class Context:
                     else:
                         raise ValueError("audio_features_mapped: slot %d has absorbed more than 2^31 - 1 frames; continue it with audio_features(slot=)" % slot)
             self.set_option("audio_slot", 0)
-            if on_device.pop():
+            code = stride = 0
+            if joined is not None:
+                ptr, mem, _, _, code, stride, keep = joined
+            elif on_device.pop():
                 import torch
                 whole = torch.cat([t if pcm16 else t.to(torch.float32) for t in chunks])
+                ptr, mem, _, keep = self._audio_ptr(whole, pcm16)
             else:
                 dt = np.int16 if pcm16 else np.float32
                 whole = np.concatenate([np.asarray(t.numpy() if _is_torch_tensor(t) else t, dtype=dt) for t in chunks])
-            ptr, mem, _, keep = self._audio_ptr(whole, pcm16)
+                ptr, mem, _, keep = self._audio_ptr(whole, pcm16)
             cuts = [int(c) for c in np.cumsum(lens)[:-1]]
             entries = [s | (self.AUDIO_TRACK_END if (l and s) else 0) for s, l in zip(slots, lasts)]
-            rec = self._audio_call(ptr, mem, sum(lens), win, sum(counts), pcm16, cuts, rate, channels, False, entries)
+            rec = self._audio_call(ptr, mem, sum(lens), win, sum(counts), pcm16, cuts, rate, channels, False, entries, code, stride)
         finally:
             self.set_option("audio_slot", was)               # also after an exception (no list is held then: the call has taken it, or a failure cleared it)
         out, at = [], 0
@@ -1171,6 +1303,11 @@ class Context:
         """(tracks, continued tracks, gather launches, converter launches, analyzer passes, save launches) of the last audio_features_mapped call;
         avd_debug_fetch "audio_map_call"."""
         return tuple(int(v) for v in self.debug_fetch("audio_map_call", (6,), np.int32))
+
+    def audio_layout(self) -> np.ndarray:
+        """int32[12] of the last call that converted: layout id (0: it went by "audio_channels"), planar 0 / 1, channels, the plane stride in
+        effect, the eight Q15 downmix weights; avd_debug_fetch "audio_layout"."""
+        return self.debug_fetch("audio_layout", (12,), np.int32)
 
     def audio_tracks(self) -> np.ndarray:
         """int32[tracks, 3] of the last audio_features / audio_features_many call that ran: per track its first window, its windows and the length

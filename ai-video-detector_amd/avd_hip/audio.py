@@ -210,38 +210,82 @@ def _decoded(wav):
     if wav.ndim == 1:
         wav = wav[:, None]
     if wav.ndim != 2 or wav.shape[1] not in (1, 2):
-        raise ValueError("a decoded track is [n] or [n, c] with c = 1 or 2 (downmix other layouts first)")
+        raise ValueError("a decoded track is [n] or [n, c] with c = 1 or 2 (other layouts and planar samples: layout=, planar=)")
     return np.ascontiguousarray(wav, np.int16 if wav.dtype == np.int16 else np.float32)
+
+
+# option "audio_layout" (include/avd.h): the Q15 downmix weights of each layout, in FFmpeg's native channel order -- the id is the channel count
+LAYOUT_WEIGHTS = {
+    1: (32768,),
+    2: (16384, 16384),
+    6: (6786, 6786, 9598, 0, 4799, 4799),                       # FL FR FC LFE BL BR
+    8: (5249, 5249, 7422, 0, 3712, 3712, 3712, 3712),           # FL FR FC LFE BL BR SL SR
+}
+
+
+def layout_of(channels: int) -> int:
+    """the "audio_layout" id of a track of ``channels`` channels in FFmpeg's native order: 1, 2, 6 (5.1) or 8 (7.1)"""
+    if channels not in LAYOUT_WEIGHTS:
+        raise ValueError("no layout of %r channels: 1 (mono), 2 (stereo), 6 (5.1) or 8 (7.1)" % (channels,))
+    return int(channels)
+
+
+def _decoded_layout(wav, layout: int, planar: bool):
+    """a decoded track with a layout: interleaved [n, layout] (dense), or planar [layout, n] AS IT LIES -- a column slice of a wider array keeps
+    its strides, which the call passes on; int16 PCM stays int16, everything else becomes float32"""
+    layout_of(layout)
+    wav = np.asarray(wav)
+    wav = wav if wav.dtype == np.int16 or wav.dtype == np.float32 else wav.astype(np.float32)
+    if wav.ndim == 1 and layout == 1:
+        wav = wav[None, :] if planar else wav[:, None]
+    if wav.ndim != 2 or wav.shape[0 if planar else 1] != layout:
+        raise ValueError("a decoded track of layout %d is %s" % (layout, "[%d, n]" % layout if planar else "[n, %d]" % layout))
+    return wav if planar else np.ascontiguousarray(wav)
+
+
+def _layout_tools(layout, planar: bool):
+    """-> (prepare, frames of a prepared chunk, keywords for the Context's calls); layout None: the helpers as they were"""
+    if layout is None:
+        if planar:
+            raise ValueError("planar needs layout")
+        return _decoded, len, {}
+    layout = int(layout)
+    return (lambda w: _decoded_layout(w, layout, planar)), (lambda w: int(w.shape[1 if planar else 0])), {"layout": layout, "planar": bool(planar)}
 
 
 def _converted_duration(n: int, sr: int, ctx) -> float:
     return ctx.audio_converted_length(n, sr) / SAMPLE_RATE
 
 
-def analyze_decoded(wav: np.ndarray, sr: int, ctx) -> dict:
+def analyze_decoded(wav: np.ndarray, sr: int, ctx, layout=None, planar: bool = False) -> dict:
     """audio.py:7-110 for a track as its decoder produced it -- [n] or [n, c], c = 1 or 2, int16 or float32, at one of RESAMPLE_RATES: what the
-    reference's ffmpeg line does (downmix, 16 kHz, 16 bit) happens on the device in front of the analyzer (Context.audio_features, rate=sr)."""
-    wav = _decoded(wav)
-    rec = ctx.audio_features(wav, _win_of(SAMPLE_RATE), rate=int(sr))
-    return features_to_result(window_values(rec), _converted_duration(len(wav), int(sr), ctx))
+    reference's ffmpeg line does (downmix, 16 kHz, 16 bit) happens on the device in front of the analyzer (Context.audio_features, rate=sr).
+
+    layout (1, 2, 6 or 8: see layout_of) names the channel layout; the track is then [n, layout], or with planar=True [layout, n] as planar
+    decoders (AAC, Opus, MP3 ...) hand it over, and is downmixed on the device by LAYOUT_WEIGHTS."""
+    prepare, frames, kw = _layout_tools(layout, planar)
+    wav = prepare(wav)
+    rec = ctx.audio_features(wav, _win_of(SAMPLE_RATE), rate=int(sr), **kw)
+    return features_to_result(window_values(rec), _converted_duration(frames(wav), int(sr), ctx))
 
 
-def analyze_decoded_many(waves, ctx) -> list:
+def analyze_decoded_many(waves, ctx, layout=None, planar: bool = False) -> list:
     """[(wav, sr), ...] -> the list of analyze_decoded's results, in input order.  Tracks of one rate, one channel count and one sample type share
-    calls (Context.audio_features_many: up to 64 tracks per call)."""
-    waves = [(_decoded(w), int(sr)) for w, sr in waves]
+    calls (Context.audio_features_many: up to 64 tracks per call).  layout / planar: as for analyze_decoded, the same for every track."""
+    prepare, frames, kw = _layout_tools(layout, planar)
+    waves = [(prepare(w), int(sr)) for w, sr in waves]
     groups = {}
     for i, (w, sr) in enumerate(waves):
-        groups.setdefault((sr, w.shape[1], w.dtype == np.int16), []).append(i)
+        groups.setdefault((sr, w.shape[0 if planar else 1], w.dtype == np.int16), []).append(i)
     results = [None] * len(waves)
     for (sr, _, _), members in groups.items():
-        recs = ctx.audio_features_many([waves[i][0] for i in members], _win_of(SAMPLE_RATE), rate=sr)
+        recs = ctx.audio_features_many([waves[i][0] for i in members], _win_of(SAMPLE_RATE), rate=sr, **kw)
         for i, rec in zip(members, recs):
-            results[i] = features_to_result(window_values(rec), _converted_duration(len(waves[i][0]), sr, ctx))
+            results[i] = features_to_result(window_values(rec), _converted_duration(frames(waves[i][0]), sr, ctx))
     return results
 
 
-def _chunk_records(chunks, ctx, slot: int, prepare, win: int, rate=None):
+def _chunk_records(chunks, ctx, slot: int, prepare, win: int, rate=None, frames_of=len, **kw):
     """The decode loop read -> analyze -> drop: every chunk goes to the device once, as it comes, and only the LAST one is marked as the end of
     the track (so a chunk is held until its successor shows that it was not the last).  -> (records of the whole track, frames seen)"""
     recs, frames, held = [], 0, None
@@ -250,12 +294,12 @@ def _chunk_records(chunks, ctx, slot: int, prepare, win: int, rate=None):
         for chunk in chunks:
             chunk = prepare(chunk)
             if held is not None:
-                recs.append(ctx.audio_features(held, win, rate=rate, slot=slot))
-                frames += len(held)
+                recs.append(ctx.audio_features(held, win, rate=rate, slot=slot, **kw))
+                frames += frames_of(held)
             held = chunk
         if held is not None:
-            recs.append(ctx.audio_features(held, win, rate=rate, slot=slot, last=True))
-            frames += len(held)
+            recs.append(ctx.audio_features(held, win, rate=rate, slot=slot, last=True, **kw))
+            frames += frames_of(held)
     except BaseException:
         ctx.set_option("audio_slot_reset", int(slot))        # half a track is of no use to the next one
         raise
@@ -271,17 +315,19 @@ def analyze_wave_chunks(chunks, sr: int, ctx, slot: int = 1) -> dict:
     return features_to_result(window_values(rec), n / sr if sr > 0 else 0.0)
 
 
-def analyze_decoded_chunks(chunks, sr: int, ctx, slot: int = 1) -> dict:
+def analyze_decoded_chunks(chunks, sr: int, ctx, slot: int = 1, layout=None, planar: bool = False) -> dict:
     """analyze_decoded for a track that arrives as its decoder's packets: an iterator of [n] or [n, c] arrays at rate ``sr`` (one channel count and
-    one sample type throughout).  -> what analyze_decoded gives for the concatenation; the duration is ceil(N U / D) / 16000 of the N frames seen."""
-    rec, n = _chunk_records(chunks, ctx, slot, _decoded, _win_of(SAMPLE_RATE), int(sr))
+    one sample type throughout).  -> what analyze_decoded gives for the concatenation; the duration is ceil(N U / D) / 16000 of the N frames seen.
+    layout / planar: as for analyze_decoded; planar packets are [layout, n]."""
+    prepare, frames, kw = _layout_tools(layout, planar)
+    rec, n = _chunk_records(chunks, ctx, slot, prepare, _win_of(SAMPLE_RATE), int(sr), frames, **kw)
     return features_to_result(window_values(rec), _converted_duration(n, int(sr), ctx))
 
 
 MAX_STREAMS = 8              # the audio slots (option "audio_slot"; Context.AUDIO_SLOTS)
 
 
-def _stream_records(streams, ctx, prepare, win: int, rate=None):
+def _stream_records(streams, ctx, prepare, win: int, rate=None, frames_of=len, **kw):
     """K <= 8 tracks that arrive in pieces side by side: stream k is continued in audio slot k + 1, and every ROUND -- one piece of each stream that
     still gives something -- is ONE call (Context.audio_features_mapped: one gather, converter, analyzer and save launch however many streams).
     A piece is held until its stream's next one shows that it was not the last, so a stream ends in the round that carries its last piece; one
@@ -294,7 +340,7 @@ def _stream_records(streams, ctx, prepare, win: int, rate=None):
     def pull(it):
         for chunk in it:
             chunk = prepare(chunk)
-            if len(chunk):
+            if frames_of(chunk):
                 return chunk
         return None
 
@@ -306,10 +352,10 @@ def _stream_records(streams, ctx, prepare, win: int, rate=None):
         while any(h is not None for h in held):
             ahead = [pull(it) if h is not None else None for it, h in zip(its, held)]
             members = [k for k, h in enumerate(held) if h is not None]
-            got = ctx.audio_features_mapped([held[k] for k in members], [k + 1 for k in members], [ahead[k] is None for k in members], win, rate=rate)
+            got = ctx.audio_features_mapped([held[k] for k in members], [k + 1 for k in members], [ahead[k] is None for k in members], win, rate=rate, **kw)
             for k, rec in zip(members, got):
                 recs[k].append(rec)
-                frames[k] += len(held[k])
+                frames[k] += frames_of(held[k])
             held = ahead
     finally:
         for k in range(len(its)):
@@ -331,7 +377,10 @@ def analyze_wave_streams(streams, sr: int, ctx) -> list:
     return [features_to_result(window_values(rec), n / sr if sr > 0 else 0.0) for rec, n in _stream_records(streams, ctx, _mono, _win_of(sr))]
 
 
-def analyze_decoded_streams(streams, sr: int, ctx) -> list:
+def analyze_decoded_streams(streams, sr: int, ctx, layout=None, planar: bool = False) -> list:
     """analyze_decoded_chunks for up to eight tracks that arrive as their decoders' packets side by side, all at rate ``sr`` with one channel count
-    and one sample type.  One call per round of packets.  -> per stream what analyze_decoded gives for its concatenation."""
-    return [features_to_result(window_values(rec), _converted_duration(n, int(sr), ctx)) for rec, n in _stream_records(streams, ctx, _decoded, _win_of(SAMPLE_RATE), int(sr))]
+    and one sample type.  One call per round of packets.  -> per stream what analyze_decoded gives for its concatenation.
+    layout / planar: as for analyze_decoded, the same for every stream."""
+    prepare, frames, kw = _layout_tools(layout, planar)
+    return [features_to_result(window_values(rec), _converted_duration(n, int(sr), ctx))
+            for rec, n in _stream_records(streams, ctx, prepare, _win_of(SAMPLE_RATE), int(sr), frames, **kw)]

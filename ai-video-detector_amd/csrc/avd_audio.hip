@@ -256,10 +256,67 @@ __device__ __forceinline__ int narrow_sample(float x)
     return v != v ? 0 : (int)fminf(fmaxf(v, -32768.f), 32767.f);
 }
 
-// one tile, by the whole workgroup: the body of both converter kernels below
-template <typename S, typename Q, typename Acc>
+// The source phase of a layout launch (option "audio_layout"): the downmix of the span's frames [f_lo, f_hi), which `wav` holds from chunk0 on,
+// as acc[f - f_lo] = sum_c w_c s_c -- the samples go from global memory straight into the sums, no staging area.  A run is what is contiguous:
+// the track's part of ONE plane (planar; plane c begins c * stride samples behind plane 0, so every plane has its own misalignment), or the
+// whole interleaved stretch.  Every sample of a run is read once: in 16-byte loads where a whole 16-byte line lies inside the run, sample by
+// sample in the partial line at either end.  A plane whose weight is 0 (LFE) is not read at all; interleaved, its samples come with their
+// lines and are dropped.  The sums are LDS integer adds: lines of an interleaved run straddle frames and planes meet in every frame, and integer
+// addition does not care about the order.  wl: the weights in LDS (a lane's channel is data).  The caller's barrier follows.
+template <typename S>
+__device__ __forceinline__ void mix_span(const S* __restrict__ wav, const avd_resample::Mix& mix, long long chunk0, long long f_lo, long long f_hi, int* __restrict__ acc,
+                                         const int* __restrict__ wl)
+{
+    const int tid = threadIdx.x;
+    constexpr int per = 16 / (int)sizeof(S);                // samples in a 16-byte line
+    const int frames = f_hi > f_lo ? (int)(f_hi - f_lo) : 0;
+    const int C = mix.channels;
+    const int runs = mix.planar ? C : 1, run_len = mix.planar ? frames : frames * C;
+    for (int r = 0; r < runs; r++) {
+        if (mix.planar && wl[r] == 0) continue;             // the same for every lane
+        const S* run = mix.planar ? wav + (long long)r * mix.stride + (f_lo - chunk0) : wav + (f_lo - chunk0) * C;
+        const int lead = (int)((reinterpret_cast<uintptr_t>(run) & 15) / sizeof(S));   // the run begins `lead` samples above a line boundary
+        const int lines = run_len > 0 ? (lead + run_len + per - 1) / per : 0;
+        for (int l = tid; l < lines; l += 256) {
+            const int lo = l * per - lead;                  // the line's first sample, counted in the run
+            const int first = lo > 0 ? lo : 0;
+            int f = mix.planar ? first : first / C, c = mix.planar ? r : first - f * C;   // frame (counted from f_lo) and channel of sample `first`
+            if (lo >= 0 && lo + per <= run_len) {
+                int v[per];
+                const uint4 q = *reinterpret_cast<const uint4*>(run + lo);
+                if constexpr (sizeof(S) == 2) {
+                    v[0] = (int16_t)(q.x & 0xffff); v[1] = (int)q.x >> 16; v[2] = (int16_t)(q.y & 0xffff); v[3] = (int)q.y >> 16;
+                    v[4] = (int16_t)(q.z & 0xffff); v[5] = (int)q.z >> 16; v[6] = (int16_t)(q.w & 0xffff); v[7] = (int)q.w >> 16;
+                } else {
+                    v[0] = narrow_sample(__uint_as_float(q.x)); v[1] = narrow_sample(__uint_as_float(q.y));
+                    v[2] = narrow_sample(__uint_as_float(q.z)); v[3] = narrow_sample(__uint_as_float(q.w));
+                }
+#pragma unroll
+                for (int e = 0; e < per; e++) {
+                    const int w = wl[c];
+                    if (w) atomicAdd(&acc[f], w * v[e]);
+                    if (mix.planar) f++;
+                    else if (++c == C) { c = 0; f++; }
+                }
+            } else {
+                const int stop = lo + per < run_len ? lo + per : run_len;
+                for (int s = first; s < stop; s++) {
+                    const int w = wl[c];
+                    if (w) atomicAdd(&acc[f], w * narrow_sample(run[s]));
+                    if (mix.planar) f++;
+                    else if (++c == C) { c = 0; f++; }
+                }
+            }
+        }
+    }
+}
+
+// one tile, by the whole workgroup: the body of the converter kernels below.  kLayout: the source phase is mix_span's (samples_at is where acc
+// lies, the weights behind it); without it `mix` is not read and the code is what it was before layouts existed.
+template <typename S, typename Q, typename Acc, bool kLayout = false>
 __device__ __forceinline__ void resample_tile(const S* __restrict__ wav, const Tile t, const int* __restrict__ taps, int U, int D, int T, int channels, int samples_at,
-                                              int mono_at, int res_at, int16_t* __restrict__ pcm, long long chunk0, const int16_t* __restrict__ hist, int hist_n)
+                                              int mono_at, int res_at, int16_t* __restrict__ pcm, long long chunk0, const int16_t* __restrict__ hist, int hist_n,
+                                              const avd_resample::Mix& mix = avd_resample::Mix{})
 {
     extern __shared__ __align__(16) unsigned char rs_lds[];
     Q* q = reinterpret_cast<Q*>(rs_lds);
@@ -272,47 +329,72 @@ __device__ __forceinline__ void resample_tile(const S* __restrict__ wav, const T
     // the span's frames that `wav` holds: [f_lo, f_hi) of the track; samples [s0, s1) of the buffer
     const long long f_min = t.begin > chunk0 ? t.begin : chunk0;
     const long long f_lo = t.in0 > f_min ? t.in0 : f_min, f_hi = t.in0 + span < t.end ? t.in0 + span : t.end;
-    const long long s0 = (f_lo - chunk0) * channels, s1 = (f_hi - chunk0) * channels;
     const long long h_lo = chunk0 - hist_n;                 // the history holds frames [h_lo, chunk0)
-    constexpr int per = 16 / (int)sizeof(S);                // samples in a 16-byte line
-    const int lead = (int)((reinterpret_cast<uintptr_t>(wav + s0) & 15) / sizeof(S));   // smp[0] is the sample at the line boundary at or below s0
-    const int lines = s1 > s0 ? (lead + (int)(s1 - s0) + per - 1) / per : 0;
-    for (int c = tid; c < lines; c += 256) {
-        const long long lo = s0 - lead + (long long)c * per;
-        int16_t* dst = smp + c * per;
-        if (lo >= s0 && lo + per <= s1) {
-            const uint4 v = *reinterpret_cast<const uint4*>(wav + lo);
-            if constexpr (sizeof(S) == 2) {
-                *reinterpret_cast<uint4*>(dst) = v;
+    if constexpr (kLayout) {
+        int* acc = reinterpret_cast<int*>(rs_lds + samples_at);
+        int* wl = acc + (mono_at - samples_at) / 4 - avd_resample::kMaxChannels;
+        const int frames = f_hi > f_lo ? (int)(f_hi - f_lo) : 0;
+        for (int i = tid; i < frames; i += 256) acc[i] = 0;
+        if (tid < avd_resample::kMaxChannels) {
+            int w = 0;
+#pragma unroll
+            for (int c = 0; c < avd_resample::kMaxChannels; c++) w = tid == c ? mix.w[c] : w;
+            wl[tid] = w;
+        }
+        __syncthreads();
+        mix_span<S>(wav, mix, chunk0, f_lo, f_hi, acc, wl);
+        __syncthreads();
+        // step 2: M = (sum_c w_c s_c + 16384) >> 15; 0 outside the track
+        for (int i = tid; i < span; i += 256) {
+            const long long f = t.in0 + i;
+            int m = 0;
+            if (f >= f_lo && f < f_hi) m = (acc[(int)(f - f_lo)] + 16384) >> 15;
+            else if (f >= h_lo && f < chunk0) m = hist[f - h_lo];
+            mono[i] = (int16_t)m;
+        }
+        __syncthreads();
+    } else {
+        const long long s0 = (f_lo - chunk0) * channels, s1 = (f_hi - chunk0) * channels;
+        constexpr int per = 16 / (int)sizeof(S);                // samples in a 16-byte line
+        const int lead = (int)((reinterpret_cast<uintptr_t>(wav + s0) & 15) / sizeof(S));   // smp[0] is the sample at the line boundary at or below s0
+        const int lines = s1 > s0 ? (lead + (int)(s1 - s0) + per - 1) / per : 0;
+        for (int c = tid; c < lines; c += 256) {
+            const long long lo = s0 - lead + (long long)c * per;
+            int16_t* dst = smp + c * per;
+            if (lo >= s0 && lo + per <= s1) {
+                const uint4 v = *reinterpret_cast<const uint4*>(wav + lo);
+                if constexpr (sizeof(S) == 2) {
+                    *reinterpret_cast<uint4*>(dst) = v;
+                } else {
+                    const int a = narrow_sample(__uint_as_float(v.x)), b = narrow_sample(__uint_as_float(v.y));
+                    const int c2 = narrow_sample(__uint_as_float(v.z)), d = narrow_sample(__uint_as_float(v.w));
+                    uint2 o;
+                    o.x = (unsigned)(a & 0xffff) | ((unsigned)b << 16);
+                    o.y = (unsigned)(c2 & 0xffff) | ((unsigned)d << 16);
+                    *reinterpret_cast<uint2*>(dst) = o;
+                }
             } else {
-                const int a = narrow_sample(__uint_as_float(v.x)), b = narrow_sample(__uint_as_float(v.y));
-                const int c2 = narrow_sample(__uint_as_float(v.z)), d = narrow_sample(__uint_as_float(v.w));
-                uint2 o;
-                o.x = (unsigned)(a & 0xffff) | ((unsigned)b << 16);
-                o.y = (unsigned)(c2 & 0xffff) | ((unsigned)d << 16);
-                *reinterpret_cast<uint2*>(dst) = o;
-            }
-        } else {
-            for (int e = 0; e < per; e++) {
-                const long long s = lo + e;
-                dst[e] = s >= s0 && s < s1 ? (int16_t)narrow_sample(wav[s]) : (int16_t)0;
+                for (int e = 0; e < per; e++) {
+                    const long long s = lo + e;
+                    dst[e] = s >= s0 && s < s1 ? (int16_t)narrow_sample(wav[s]) : (int16_t)0;
+                }
             }
         }
-    }
-    __syncthreads();
-    // step 2: M = s, or floor((L + R + 1) / 2); 0 outside the track
-    for (int i = tid; i < span; i += 256) {
-        const long long f = t.in0 + i;
-        int m = 0;
-        if (f >= f_lo && f < f_hi) {
-            const int at = lead + (int)(f - f_lo) * channels;
-            m = channels == 2 ? ((int)smp[at] + (int)smp[at + 1] + 1) >> 1 : (int)smp[at];
-        } else if (f >= h_lo && f < chunk0) {
-            m = hist[f - h_lo];
+        __syncthreads();
+        // step 2: M = s, or floor((L + R + 1) / 2); 0 outside the track
+        for (int i = tid; i < span; i += 256) {
+            const long long f = t.in0 + i;
+            int m = 0;
+            if (f >= f_lo && f < f_hi) {
+                const int at = lead + (int)(f - f_lo) * channels;
+                m = channels == 2 ? ((int)smp[at] + (int)smp[at + 1] + 1) >> 1 : (int)smp[at];
+            } else if (f >= h_lo && f < chunk0) {
+                m = hist[f - h_lo];
+            }
+            mono[i] = (int16_t)m;
         }
-        mono[i] = (int16_t)m;
+        __syncthreads();
     }
-    __syncthreads();
     // step 4; res[e] is entry e of the converted buffer counted from the 16-byte row boundary at or below the tile's first output
     const int shift = (int)(t.out0 & 7);
     for (int j = tid; j < t.count; j += 256) {
@@ -363,10 +445,45 @@ __global__ __launch_bounds__(256) void k_audio_resample_map(const S* __restrict_
                              reinterpret_cast<const int16_t*>(row.hist), row.hist_n);
 }
 
+// The same two kernels for a call with a layout (option "audio_layout"): the mix travels by value, `samples_at` is where the sums lie
+template <typename S, typename Q, typename Acc>
+__global__ __launch_bounds__(256) void k_audio_resample_layout(const S* __restrict__ wav, const Tile* __restrict__ tiles, const int* __restrict__ taps, int U, int D,
+                                                              int T, const avd_resample::Mix mix, int acc_at, int mono_at, int res_at, int16_t* __restrict__ pcm,
+                                                              long long chunk0, const int16_t* __restrict__ hist, int hist_n)
+{
+    resample_tile<S, Q, Acc, true>(wav, tiles[blockIdx.x], taps, U, D, T, mix.channels, acc_at, mono_at, res_at, pcm, chunk0, hist, hist_n, mix);
+}
+
+// row.at counts FRAMES of a planar buffer (applied to every plane alike), samples of an interleaved one
+template <typename S, typename Q, typename Acc>
+__global__ __launch_bounds__(256) void k_audio_resample_map_layout(const S* __restrict__ wav, const Tile* __restrict__ tiles, const int* __restrict__ tile_track,
+                                                                  const Source* __restrict__ rows, const int* __restrict__ taps, int U, int D, int T,
+                                                                  const avd_resample::Mix mix, int acc_at, int mono_at, int res_at, int16_t* __restrict__ pcm)
+{
+    const Source row = rows[tile_track[blockIdx.x]];
+    resample_tile<S, Q, Acc, true>(wav + row.at, tiles[blockIdx.x], taps, U, D, T, mix.channels, acc_at, mono_at, res_at, pcm, row.chunk0,
+                                   reinterpret_cast<const int16_t*>(row.hist), row.hist_n, mix);
+}
+
+// where a layout launch's parts lie in LDS (avd_audio_resample.h): taps | acc | weights | mono | results
+struct LayoutLds { int acc_at, mono_at, res_at; size_t bytes; };
+static LayoutLds layout_lds(const avd_resample::Ratio& r)
+{
+    const size_t at_a = avd_resample::lds_taps_bytes(r), at_m = at_a + avd_resample::lds_acc_bytes(r) + avd_resample::lds_weights_bytes();
+    return LayoutLds{(int)at_a, (int)at_m, (int)(at_m + avd_resample::lds_mono_bytes(r)), avd_resample::lds_layout_bytes(r)};
+}
+
 template <typename S, typename Q, typename Acc>
 int launch_resample_map_as(avd_ctx* ctx, const void* d_in, const Tile* tiles, const int* tile_track, const Source* rows, const int* taps, int ntiles,
-                           const avd_resample::Ratio& r, int channels, int16_t* d_pcm)
+                           const avd_resample::Ratio& r, int channels, int16_t* d_pcm, const avd_resample::Mix& mix)
 {
+    if (mix.id) {
+        const LayoutLds l = layout_lds(r);
+        HIP_TRY(ctx, hipFuncSetAttribute((const void*)k_audio_resample_map_layout<S, Q, Acc>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l.bytes));
+        hipLaunchKernelGGL((k_audio_resample_map_layout<S, Q, Acc>), dim3(ntiles), dim3(256), l.bytes, ctx->stream, static_cast<const S*>(d_in), tiles, tile_track, rows,
+                           taps, r.U, r.D, r.T, mix, l.acc_at, l.mono_at, l.res_at, d_pcm);
+        return 0;
+    }
     const size_t at_s = avd_resample::lds_taps_bytes(r), at_m = at_s + avd_resample::lds_samples_bytes(r, channels), at_r = at_m + avd_resample::lds_mono_bytes(r);
     const size_t lds = avd_resample::lds_bytes(r, channels);
     HIP_TRY(ctx, hipFuncSetAttribute((const void*)k_audio_resample_map<S, Q, Acc>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -377,8 +494,15 @@ int launch_resample_map_as(avd_ctx* ctx, const void* d_in, const Tile* tiles, co
 
 template <typename S, typename Q, typename Acc>
 int launch_resample_as(avd_ctx* ctx, const void* d_in, const Tile* tiles, const int* taps, int ntiles, const avd_resample::Ratio& r, int channels, int16_t* d_pcm,
-                       const AudioSource& src)
+                       const AudioSource& src, const avd_resample::Mix& mix)
 {
+    if (mix.id) {
+        const LayoutLds l = layout_lds(r);
+        HIP_TRY(ctx, hipFuncSetAttribute((const void*)k_audio_resample_layout<S, Q, Acc>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l.bytes));
+        hipLaunchKernelGGL((k_audio_resample_layout<S, Q, Acc>), dim3(ntiles), dim3(256), l.bytes, ctx->stream, static_cast<const S*>(d_in), tiles, taps, r.U, r.D, r.T,
+                           mix, l.acc_at, l.mono_at, l.res_at, d_pcm, src.chunk0, src.hist, src.hist_n);
+        return 0;
+    }
     const size_t at_s = avd_resample::lds_taps_bytes(r), at_m = at_s + avd_resample::lds_samples_bytes(r, channels), at_r = at_m + avd_resample::lds_mono_bytes(r);
     const size_t lds = avd_resample::lds_bytes(r, channels);
     // per call (a function attribute belongs to the current device; a process may hold contexts on several)
@@ -409,6 +533,36 @@ __device__ __forceinline__ void slot_save(const S* __restrict__ wav, long long n
     for (int i = tid; i < held_words; i += 256) held_dst[i] = held_src[i];
 }
 
+// ... and of a call with a layout: the same frames by the layout's rule, M = (sum_c w_c s_c + 16384) >> 15, a channel of weight 0 not read
+template <typename S>
+__device__ __forceinline__ void slot_save_layout(const S* __restrict__ wav, long long n, const avd_resample::Mix& mix, const int16_t* __restrict__ hist_old, int hist_old_n,
+                                                 int16_t* __restrict__ hist_new, int hist_new_n, const int16_t* __restrict__ held_src,
+                                                 int16_t* __restrict__ held_dst, int held_words)
+{
+    const int tid = threadIdx.x;
+    for (int i = tid; i < hist_new_n; i += 256) {
+        const long long r = n - hist_new_n + i;
+        int m;
+        if (r >= 0) {
+            int sum = 16384;
+#pragma unroll
+            for (int c = 0; c < avd_resample::kMaxChannels; c++)
+                if (c < mix.channels && mix.w[c] != 0) sum += mix.w[c] * narrow_sample(mix.planar ? wav[(long long)c * mix.stride + r] : wav[r * mix.channels + c]);
+            m = sum >> 15;
+        } else m = hist_old[hist_old_n + r];
+        hist_new[i] = (int16_t)m;
+    }
+    for (int i = tid; i < held_words; i += 256) held_dst[i] = held_src[i];
+}
+
+template <typename S>
+__global__ __launch_bounds__(256) void k_audio_slot_save_layout(const S* __restrict__ wav, long long n, const avd_resample::Mix mix, const int16_t* __restrict__ hist_old,
+                                                               int hist_old_n, int16_t* __restrict__ hist_new, int hist_new_n, const int16_t* __restrict__ held_src,
+                                                               int16_t* __restrict__ held_dst, int held_words)
+{
+    slot_save_layout<S>(wav, n, mix, hist_old, hist_old_n, hist_new, hist_new_n, held_src, held_dst, held_words);
+}
+
 template <typename S>
 __global__ __launch_bounds__(256) void k_audio_slot_save(const S* __restrict__ wav, long long n, int channels, const int16_t* __restrict__ hist_old, int hist_old_n,
                                                         int16_t* __restrict__ hist_new, int hist_new_n, const int16_t* __restrict__ held_src,
@@ -430,6 +584,13 @@ __global__ __launch_bounds__(256) void k_audio_slot_save_map(const SaveTable tab
 {
     const AudioSaveRow r = table.row[blockIdx.x];
     slot_save<S>(static_cast<const S*>(r.wav), r.n, channels, r.hist_old, r.hist_old_n, r.hist_new, r.hist_new_n, r.held_src, r.held_dst, r.held_words);
+}
+
+template <typename S>
+__global__ __launch_bounds__(256) void k_audio_slot_save_map_layout(const SaveTable table, const avd_resample::Mix mix)
+{
+    const AudioSaveRow r = table.row[blockIdx.x];
+    slot_save_layout<S>(static_cast<const S*>(r.wav), r.n, mix, r.hist_old, r.hist_old_n, r.hist_new, r.hist_new_n, r.held_src, r.held_dst, r.held_words);
 }
 
 // The gather: move blockIdx.y of the table, by gridDim.x workgroups in strides.  Held samples go from their slot to the front of the track's region;
@@ -486,7 +647,7 @@ int launch_audio_gather(avd_ctx* ctx, const AudioGatherMove* moves, int count, i
     return 0;
 }
 
-int launch_audio_slot_save_map(avd_ctx* ctx, int format, int channels, const AudioSaveRow* rows, int count, bool* enqueued)
+int launch_audio_slot_save_map(avd_ctx* ctx, int format, int channels, const AudioSaveRow* rows, int count, bool* enqueued, const avd_resample::Mix& mix)
 {
     if (count <= 0) return 0;
     if (count > avd_audio_map::kSlots) { ctx->err = "audio_track_slot: internal error (save table)"; return AVD_ERR_DEVICE; }
@@ -499,7 +660,9 @@ int launch_audio_slot_save_map(avd_ctx* ctx, int format, int channels, const Aud
         }
         table.row[i] = r;
     }
-    if (format == 1) hipLaunchKernelGGL(k_audio_slot_save_map<int16_t>, dim3((unsigned)count), dim3(256), 0, ctx->stream, table, channels);
+    if (mix.id && format == 1) hipLaunchKernelGGL(k_audio_slot_save_map_layout<int16_t>, dim3((unsigned)count), dim3(256), 0, ctx->stream, table, mix);
+    else if (mix.id) hipLaunchKernelGGL(k_audio_slot_save_map_layout<float>, dim3((unsigned)count), dim3(256), 0, ctx->stream, table, mix);
+    else if (format == 1) hipLaunchKernelGGL(k_audio_slot_save_map<int16_t>, dim3((unsigned)count), dim3(256), 0, ctx->stream, table, channels);
     else hipLaunchKernelGGL(k_audio_slot_save_map<float>, dim3((unsigned)count), dim3(256), 0, ctx->stream, table, channels);
     *enqueued = true;                                        // from here on the slots' memory may have been written
     HIP_TRY(ctx, hipGetLastError());
@@ -507,13 +670,19 @@ int launch_audio_slot_save_map(avd_ctx* ctx, int format, int channels, const Aud
 }
 
 int launch_audio_slot_save(avd_ctx* ctx, const void* d_in, int format, long long n, int channels, const int16_t* hist_old, int hist_old_n, int16_t* hist_new,
-                           int hist_new_n, const void* held_src, int16_t* held_dst, int held_words, bool* enqueued)
+                           int hist_new_n, const void* held_src, int16_t* held_dst, int held_words, bool* enqueued, const avd_resample::Mix& mix)
 {
     if (hist_new_n < 0 || hist_new_n > avd_resample::kMaxHistory || hist_new_n > n + hist_old_n || held_words < 0 || held_words > kAudioSlotHeldWords) {
         ctx->err = "audio_slot: internal error (save extents)";
         return AVD_ERR_DEVICE;
     }
-    if (format == 1)
+    if (mix.id && format == 1)
+        hipLaunchKernelGGL(k_audio_slot_save_layout<int16_t>, dim3(1), dim3(256), 0, ctx->stream, static_cast<const int16_t*>(d_in), n, mix, hist_old, hist_old_n,
+                           hist_new, hist_new_n, static_cast<const int16_t*>(held_src), held_dst, held_words);
+    else if (mix.id)
+        hipLaunchKernelGGL(k_audio_slot_save_layout<float>, dim3(1), dim3(256), 0, ctx->stream, static_cast<const float*>(d_in), n, mix, hist_old, hist_old_n,
+                           hist_new, hist_new_n, static_cast<const int16_t*>(held_src), held_dst, held_words);
+    else if (format == 1)
         hipLaunchKernelGGL(k_audio_slot_save<int16_t>, dim3(1), dim3(256), 0, ctx->stream, static_cast<const int16_t*>(d_in), n, channels, hist_old, hist_old_n,
                            hist_new, hist_new_n, static_cast<const int16_t*>(held_src), held_dst, held_words);
     else
@@ -537,7 +706,8 @@ static void record_resample_plan(avd_ctx* ctx, const avd_resample::Plan& plan, i
     ctx->audio_rs_valid = 1;
 }
 
-int launch_audio_resample(avd_ctx* ctx, const void* d_in, int format, int channels, const avd_resample::Plan& plan, int16_t* d_pcm, const AudioSource& src)
+int launch_audio_resample(avd_ctx* ctx, const void* d_in, int format, int channels, const avd_resample::Plan& plan, int16_t* d_pcm, const AudioSource& src,
+                          const avd_resample::Mix& mix)
 {
     const avd_resample::Ratio& r = plan.r;
     const int ntiles = (int)plan.tiles.size(), bank = r.U * r.T, idx = avd_resample::rate_index(r.rate);
@@ -572,11 +742,11 @@ int launch_audio_resample(avd_ctx* ctx, const void* d_in, int format, int channe
     const int* d_taps = ws.d_audio_rs_taps;                  // null at rate 16000 before any other rate ran: T = 0 reads none
     int e;
     if (avd_resample::wide(r))
-        e = format == 1 ? launch_resample_as<int16_t, int, long long>(ctx, d_in, tiles, d_taps, ntiles, r, channels, d_pcm, src)
-                        : launch_resample_as<float, int, long long>(ctx, d_in, tiles, d_taps, ntiles, r, channels, d_pcm, src);
+        e = format == 1 ? launch_resample_as<int16_t, int, long long>(ctx, d_in, tiles, d_taps, ntiles, r, channels, d_pcm, src, mix)
+                        : launch_resample_as<float, int, long long>(ctx, d_in, tiles, d_taps, ntiles, r, channels, d_pcm, src, mix);
     else
-        e = format == 1 ? launch_resample_as<int16_t, int16_t, int>(ctx, d_in, tiles, d_taps, ntiles, r, channels, d_pcm, src)
-                        : launch_resample_as<float, int16_t, int>(ctx, d_in, tiles, d_taps, ntiles, r, channels, d_pcm, src);
+        e = format == 1 ? launch_resample_as<int16_t, int16_t, int>(ctx, d_in, tiles, d_taps, ntiles, r, channels, d_pcm, src, mix)
+                        : launch_resample_as<float, int16_t, int>(ctx, d_in, tiles, d_taps, ntiles, r, channels, d_pcm, src, mix);
     if (e) return e;
     HIP_TRY(ctx, hipGetLastError());
     record_resample_plan(ctx, plan, channels);
@@ -587,7 +757,7 @@ int launch_audio_resample(avd_ctx* ctx, const void* d_in, int format, int channe
 // upload, the tile table | the source rows (8-byte aligned: a tile is 40 bytes) | each tile's track; the bank follows when the rate changed, as above.
 // plan.sources carry the device address of each continued track's history already.  n_in: the frames of the call's buffer.
 int launch_audio_resample_map(avd_ctx* ctx, const void* d_in, int format, int channels, const avd_audio_map::Plan& plan, const avd_resample::Ratio& r, long long n_in,
-                              int16_t* d_pcm, bool* launched)
+                              int16_t* d_pcm, bool* launched, const avd_resample::Mix& mix)
 {
     const int ntiles = (int)plan.tiles.size(), ntracks = (int)plan.tracks.size(), bank = r.U * r.T, idx = avd_resample::rate_index(r.rate);
     *launched = false;
@@ -625,11 +795,11 @@ int launch_audio_resample_map(avd_ctx* ctx, const void* d_in, int format, int ch
         const int* d_taps = ws.d_audio_rs_taps;
         int e;
         if (avd_resample::wide(r))
-            e = format == 1 ? launch_resample_map_as<int16_t, int, long long>(ctx, d_in, tiles, tile_track, rows, d_taps, ntiles, r, channels, d_pcm)
-                            : launch_resample_map_as<float, int, long long>(ctx, d_in, tiles, tile_track, rows, d_taps, ntiles, r, channels, d_pcm);
+            e = format == 1 ? launch_resample_map_as<int16_t, int, long long>(ctx, d_in, tiles, tile_track, rows, d_taps, ntiles, r, channels, d_pcm, mix)
+                            : launch_resample_map_as<float, int, long long>(ctx, d_in, tiles, tile_track, rows, d_taps, ntiles, r, channels, d_pcm, mix);
         else
-            e = format == 1 ? launch_resample_map_as<int16_t, int16_t, int>(ctx, d_in, tiles, tile_track, rows, d_taps, ntiles, r, channels, d_pcm)
-                            : launch_resample_map_as<float, int16_t, int>(ctx, d_in, tiles, tile_track, rows, d_taps, ntiles, r, channels, d_pcm);
+            e = format == 1 ? launch_resample_map_as<int16_t, int16_t, int>(ctx, d_in, tiles, tile_track, rows, d_taps, ntiles, r, channels, d_pcm, mix)
+                            : launch_resample_map_as<float, int16_t, int>(ctx, d_in, tiles, tile_track, rows, d_taps, ntiles, r, channels, d_pcm, mix);
         if (e) return e;
         HIP_TRY(ctx, hipGetLastError());
         *launched = true;

@@ -179,4 +179,72 @@ inline size_t lds_samples_bytes(const Ratio& r, int channels) { return up16(((si
 inline size_t lds_mono_bytes(const Ratio& r) { return up16((size_t)max_span(r) * 2); }
 inline size_t lds_bytes(const Ratio& r, int channels) { return lds_taps_bytes(r) + lds_samples_bytes(r, channels) + lds_mono_bytes(r) + up16(((size_t)tile_outputs(r) + 8) * 2); }
 
+// ---- channel layouts (option "audio_layout", include/avd.h): the downmix as ONE rule, M = (sum_c w_c s_c + 16384) >> 15 with Q15 weights ----
+// A layout's id is its channel count, in FFmpeg's / WAVE's native order: 1 mono | 2 FL FR | 6 FL FR FC LFE BL BR | 8 FL FR FC LFE BL BR SL SR.
+// The gains (FC 1, FL / FR sqrt(1/2), back and side 1/2, LFE 0) are modelled on libswresample's default matrix for one output channel, unpinned
+// against a real ffmpeg like the rest of the rule.  w_c = rint(g_c / sum g * 32768), and 32768 - sum w goes to the channel with the largest gain
+// (the lowest index on a tie), as a bank row's remainder goes to its largest tap: every row sums to exactly 32768, |sum w s| <= 2^30.
+constexpr int kLayoutPlanar = 0x100;             // flag of the option's value: one plane per channel
+constexpr int kMaxChannels = 8;
+
+inline bool layout_id_ok(int id) { return id == 1 || id == 2 || id == 6 || id == 8; }
+// what option "audio_layout" accepts: 0 ("audio_channels" decides), or id | flags
+inline bool layout_ok(int v) { return v == 0 || (v > 0 && layout_id_ok(v & ~kLayoutPlanar)); }
+
+// the gains of layout `id`, in its channel order -> the channel count; 0 for an unknown id
+inline int layout_gains(int id, double g[kMaxChannels])
+{
+    const double c = 1.0, f = std::sqrt(0.5), s = 0.5, lfe = 0.0;
+    const double six[6] = {f, f, c, lfe, s, s}, eight[8] = {f, f, c, lfe, s, s, s, s};
+    for (int i = 0; i < kMaxChannels; i++) g[i] = 0.0;
+    switch (id) {
+    case 1: g[0] = 1.0; return 1;
+    case 2: g[0] = g[1] = f; return 2;
+    case 6: std::copy(six, six + 6, g); return 6;
+    case 8: std::copy(eight, eight + 8, g); return 8;
+    default: return 0;
+    }
+}
+// w[0 .. channels) of layout `id`, zero-filled to kMaxChannels -> the channel count; 0 for an unknown id
+inline int layout_weights(int id, int w[kMaxChannels])
+{
+    double g[kMaxChannels];
+    const int channels = layout_gains(id, g);
+    for (int i = 0; i < kMaxChannels; i++) w[i] = 0;
+    if (!channels) return 0;
+    double sum = 0.0;
+    for (int c = 0; c < channels; c++) sum += g[c];
+    int total = 0, best = 0;
+    for (int c = 0; c < channels; c++) {
+        w[c] = (int)std::nearbyint(g[c] / sum * 32768.0);
+        total += w[c];
+        if (g[c] > g[best]) best = c;                            // the lowest index on a tie
+    }
+    w[best] += 32768 - total;
+    return channels;
+}
+
+// What the converter's source phase goes by, as it travels to the kernels (by value).  id 0: no layout -- the launch takes today's path and its
+// `channels` argument decides.  planar: plane c begins c * stride samples behind plane 0; interleaved: frames of `channels` samples, stride unused.
+struct Mix { long long stride = 0; int id = 0, planar = 0, channels = 0, pad = 0; int w[kMaxChannels] = {}; };
+static_assert(sizeof(Mix) == 56, "a kernel argument");
+
+// option value (layout_ok, not 0) and the plane stride in effect -> the mix
+inline Mix mix_of(int layout, long long stride)
+{
+    Mix m;
+    m.id = layout & ~kLayoutPlanar;
+    m.planar = (layout & kLayoutPlanar) != 0;
+    m.channels = layout_weights(m.id, m.w);
+    m.stride = m.planar ? stride : 0;
+    return m;
+}
+
+// LDS of a layout launch: taps | acc [max_span] int32, w_c s_c summed per span frame | weights [8] int32 | mono | results.  The span's samples
+// go from global memory straight into acc (no staging area), so any layout stays below today's stereo footprint plus the accumulators:
+// lds_layout_bytes(r) <= lds_bytes(r, 2) + 4 * max_span(r) + 16 at every rate.
+inline size_t lds_acc_bytes(const Ratio& r) { return up16((size_t)max_span(r) * 4); }
+inline size_t lds_weights_bytes() { return (size_t)kMaxChannels * 4; }
+inline size_t lds_layout_bytes(const Ratio& r) { return lds_taps_bytes(r) + lds_acc_bytes(r) + lds_weights_bytes() + lds_mono_bytes(r) + up16(((size_t)tile_outputs(r) + 8) * 2); }
+
 }  // namespace avd_resample

@@ -494,6 +494,10 @@ static int audio_cut_read(const avd_ctx* ctx) { return ctx->audio_ncuts; }
 static bool opt_audio_rate(int& v) { return v == 0 || avd_resample::rate_index(v) >= 0; }
 // "audio_channels": interleaved samples per frame of a converted call, 1 or 2; durable
 static bool opt_audio_channels(int& v) { return v == 1 || v == 2; }
+// "audio_layout": 0 "audio_channels" decides, or id | flags -- id 1 (mono), 2 (stereo), 6 (5.1), 8 (7.1), flag 0x100 planar; durable
+static bool opt_audio_layout(int& v) { return avd_resample::layout_ok(v); }
+// "audio_plane_stride": samples from plane c to plane c + 1 of a planar call, 0 = the call's frame count; durable
+static bool opt_audio_plane_stride(int& v) { return v >= 0; }
 // "audio_slot": 0 every avd_audio_features call is a whole track, k = 1 ... 8 it continues the track of audio slot k; durable.  The audio slots are
 // apart from the video stream slots: neither family of options touches the other's.
 static bool opt_audio_slot(int& v) { return v >= 0 && v <= kAudioSlots; }
@@ -575,7 +579,9 @@ static const Option kOptions[] = {
     {"audio_format", &avd_ctx::audio_format, true, opt_audio_format, nullptr, nullptr, "audio_format: 0 (float32 samples) or 1 (little-endian int16 PCM)"},
     {"audio_cut", nullptr, true, opt_any, nullptr, nullptr, nullptr, audio_cut_set, audio_cut_read, audio_cut_check},
     {"audio_rate", &avd_ctx::audio_rate, true, opt_audio_rate, nullptr, nullptr, "audio_rate: 0 (samples at 16 kHz already) or 8000, 11025, 12000, 16000, 22050, 24000, 32000, 44100, 48000, 88200, 96000, 176400, 192000"},
-    {"audio_channels", &avd_ctx::audio_channels, true, opt_audio_channels, nullptr, nullptr, "audio_channels: 1 or 2 interleaved samples per frame (downmix other layouts first)"},
+    {"audio_channels", &avd_ctx::audio_channels, true, opt_audio_channels, nullptr, nullptr, "audio_channels: 1 or 2 interleaved samples per frame (planar samples and other layouts: option \"audio_layout\")"},
+    {"audio_layout", &avd_ctx::audio_layout, true, opt_audio_layout, nullptr, nullptr, "audio_layout: 0 (\"audio_channels\" decides) or 1 (mono), 2 (stereo), 6 (5.1), 8 (7.1), | 0x100 (planar: one plane per channel)"},
+    {"audio_plane_stride", &avd_ctx::audio_plane_stride, true, opt_audio_plane_stride, nullptr, nullptr, "audio_plane_stride: samples from one plane to the next, 0 (the call's frame count) or above"},
     {"audio_slot", &avd_ctx::audio_slot, true, opt_audio_slot, nullptr, nullptr, "audio_slot: 0 (every call is a whole track) or audio slot 1 ... 8", nullptr, nullptr, audio_slot_check},
     {"audio_track_slot", nullptr, true, opt_any, nullptr, nullptr, nullptr, audio_track_slot_set, audio_track_slot_read, audio_track_slot_check},
     {"audio_end", nullptr, true, opt_audio_end, nullptr, nullptr, "audio_end: 1 (the next avd_audio_features call carries the last samples of its slot's track)", audio_end_set, audio_end_read},
@@ -1269,6 +1275,7 @@ static int64_t impl_debug_fetch(avd_ctx* ctx, const char* name, void* out, size_
             {"ingest_groups", ctx->ingest_groups.data(), sizeof(int) * ctx->ingest_groups.size(), true, nullptr, "int32[launches][4]"},
             {"fb_model", ctx->fb_model, sizeof ctx->fb_model, ctx->fb_model_valid != 0, "no call has run the Farneback stage on this context", "int32[4]"},
             {"fb_wide320_launches", &ctx->fb_wide320_launches, sizeof ctx->fb_wide320_launches, ctx->fb_model_valid != 0, "no call has run the Farneback stage on this context", "int32[1]"},
+            {"audio_layout", ctx->audio_layout_rec, sizeof ctx->audio_layout_rec, ctx->audio_layout_valid != 0, "no avd_audio_features call has converted on this context (option \"audio_rate\")", "int32[12]"},
             {"audio_map_call", ctx->audio_map_call, sizeof ctx->audio_map_call, ctx->audio_map_valid != 0, "no avd_audio_features call with an \"audio_track_slot\" list has run on this context", "int32[6]"},
         };
         for (const auto& e : host_state) {
@@ -1588,10 +1595,71 @@ static int impl_rowop(avd_ctx* ctx, int op, const void* x, int mem, int bf16, in
 // 16 kHz mono int16 tracks into ws.d_audio_pcm, then the analyzer runs over that buffer and the output-side cuts exactly as it runs over a caller's
 // int16 track (format 1).  Every check comes before anything is staged, in the order include/avd.h lists: the argument checks and the int16
 // alignment (impl_audio_features), the float32 alignment, a cut beyond the buffer, the windows array against the OUTPUT's window count.
+// What a converted call's buffer is: the channel count, the mix its launches go by (id 0: no layout, "audio_channels" decides and every launch
+// takes the path it took before layouts existed), and the plane stride of the CALLER's buffer.  step: what a frame offset is multiplied by to
+// reach the track's first sample -- the channel count of an interleaved buffer, 1 within each plane of a planar one.
+struct AudioInput { int channels = 1, step = 1, layout = 0; long long stride = 0; avd_resample::Mix mix; };
+static AudioInput audio_input(const avd_ctx* ctx, int64_t n)
+{
+    AudioInput in;
+    if (ctx->audio_rate == 0) return in;
+    in.channels = in.step = ctx->audio_channels;
+    if (ctx->audio_layout == 0) return in;
+    in.layout = ctx->audio_layout;
+    in.stride = (in.layout & avd_resample::kLayoutPlanar) ? (ctx->audio_plane_stride ? ctx->audio_plane_stride : n) : 0;
+    in.mix = avd_resample::mix_of(in.layout, in.stride);
+    in.channels = in.mix.channels;
+    in.step = in.mix.planar ? 1 : in.channels;
+    return in;
+}
+// refusal 3 of a call, behind the alignment checks: planes that would overlap
+static bool audio_stride_refused(avd_ctx* ctx, const AudioInput& in, int64_t n)
+{
+    if (!in.mix.planar || in.stride >= n) return false;
+    ctx->err = "audio_plane_stride: " + std::to_string(in.stride) + " samples from plane to plane, below the call's " + std::to_string((long long)n) + " frames";
+    return true;
+}
+// The staging of a converted call.  Without a layout: stage_input, as ever.  With one, device input is read in place with its stride; a dense
+// host buffer (interleaved, or planes n samples apart) is staged in one copy, a strided one plane by plane into a dense device buffer -- no byte
+// twice, none outside the planes -- whose stride, n, replaces the caller's in in.mix.  "stage_bytes" / "stage_copies" say what was copied.
+static int stage_audio(avd_ctx* ctx, const void* wav, int mem, int64_t n, size_t in_size, AudioInput& in, const uint8_t** d_in)
+{
+    const size_t plane = (size_t)n * in_size, all = plane * (size_t)in.channels;
+    if (!in.mix.id) return stage_input(ctx, static_cast<const uint8_t*>(wav), mem, all, d_in);
+    if (mem == AVD_MEM_DEVICE) { *d_in = static_cast<const uint8_t*>(wav); ctx->ingest.stage_bytes = 0; ctx->ingest.stage_copies = 0; return 0; }
+    if (!in.mix.planar || in.stride == n) {
+        if (int e = stage_input(ctx, static_cast<const uint8_t*>(wav), mem, all, d_in)) return e;
+        ctx->ingest.stage_copies = 1;
+    } else {
+        Workspace& ws = ctx->ws;
+        if (int e = ws.d_stage.reserve(ctx, all)) return e;
+        for (int c = 0; c < in.channels; c++)
+            HIP_TRY(ctx, hipMemcpyAsync(ws.d_stage.p + (size_t)c * plane, static_cast<const uint8_t*>(wav) + (size_t)c * (size_t)in.stride * in_size, plane,
+                                        hipMemcpyHostToDevice, ctx->stream));
+        *d_in = ws.d_stage;
+        in.mix.stride = n;
+        ctx->ingest.stage_copies = in.channels;
+    }
+    ctx->ingest.stage_bytes = (int64_t)all;
+    return 0;
+}
+// debug buffer "audio_layout": a converted call has enqueued its launches
+static void record_audio_layout(avd_ctx* ctx, const AudioInput& in)
+{
+    int* rec = ctx->audio_layout_rec;
+    rec[0] = in.mix.id; rec[1] = in.mix.planar; rec[2] = in.channels; rec[3] = (int)std::min<long long>(in.stride, 0x7fffffff);
+    if (in.mix.id) std::copy(in.mix.w, in.mix.w + avd_resample::kMaxChannels, rec + 4);
+    else avd_resample::layout_weights(in.channels, rec + 4);
+    ctx->audio_layout_valid = 1;
+}
+
 static int convert_audio_features(avd_ctx* ctx, const void* wav, int mem, int64_t n, int win, avd_audio_window* windows, int max_windows, const int* cuts, int ncuts)
 {
-    const int format = ctx->audio_format, channels = ctx->audio_channels;
+    const int format = ctx->audio_format;
+    AudioInput in = audio_input(ctx, n);
+    const int channels = in.channels;
     if (format == 0 && (reinterpret_cast<uintptr_t>(wav) & 3)) { ctx->err = "audio_rate: float32 samples need a 4-byte aligned wav"; return AVD_ERR_ARG; }
+    if (audio_stride_refused(ctx, in, n)) return AVD_ERR_ARG;
     if (mem != AVD_MEM_HOST && mem != AVD_MEM_DEVICE) { ctx->err = "mem must be AVD_MEM_HOST or AVD_MEM_DEVICE"; return AVD_ERR_ARG; }
     avd_resample::Ratio ratio;
     if (!avd_resample::ratio_of(ctx->audio_rate, ratio)) { ctx->err = "audio_rate: not a supported rate"; return AVD_ERR_ARG; }   // (the option refuses such a value)
@@ -1604,10 +1672,11 @@ static int convert_audio_features(avd_ctx* ctx, const void* wav, int mem, int64_
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     Workspace& ws = ctx->ws;
     const uint8_t* d_in = nullptr;
-    if (int e = stage_input(ctx, static_cast<const uint8_t*>(wav), mem, (size_t)n * (size_t)channels * (format == 1 ? sizeof(int16_t) : sizeof(float)), &d_in)) return e;
+    if (int e = stage_audio(ctx, wav, mem, n, format == 1 ? sizeof(int16_t) : sizeof(float), in, &d_in)) return e;
     if (int e = ws.d_audio_pcm.reserve(ctx, (size_t)conv.n_out + 8)) return e;
     if (int e = ws.d_audio_out.reserve(ctx, (size_t)nwin)) return e;
-    if (int e = launch_audio_resample(ctx, d_in, format, channels, conv, ws.d_audio_pcm)) return e;
+    if (int e = launch_audio_resample(ctx, d_in, format, channels, conv, ws.d_audio_pcm, AudioSource{}, in.mix)) return e;
+    record_audio_layout(ctx, in);
     if (int e = launch_audio_features(ctx, ws.d_audio_pcm, 1, plan, ws.d_audio_out)) return e;
     HIP_TRY(ctx, hipMemcpyAsync(windows, ws.d_audio_out, sizeof(avd_audio_window) * nwin, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -1623,9 +1692,9 @@ static int convert_audio_features(avd_ctx* ctx, const void* wav, int mem, int64_
 // stream; the host state of the slot changes only once the call has drained.  *saved: the save launch was enqueued -- a failure from there on
 // has left the slot's memory in an unknown state.
 static int run_audio_slot(avd_ctx* ctx, AudioSlot& slot, const avd_resample::Continue& c, const avd_resample::Ratio& ratio, const void* wav, int mem, int64_t n,
-                          int win, avd_audio_window* windows, int max_windows, bool last, bool* saved)
+                          int win, avd_audio_window* windows, int max_windows, bool last, bool* saved, AudioInput& in)
 {
-    const int format = ctx->audio_format, channels = ratio.rate ? ctx->audio_channels : 1;
+    const int format = ctx->audio_format, channels = in.channels;
     const bool converted = ratio.rate != 0;
     const size_t in_size = format == 1 ? sizeof(int16_t) : sizeof(float), an_size = converted ? sizeof(int16_t) : in_size;   // bytes per input / analysed sample
     const int an_format = converted ? 1 : format;
@@ -1647,7 +1716,7 @@ static int run_audio_slot(avd_ctx* ctx, AudioSlot& slot, const avd_resample::Con
     ctx->audio_rs_valid = 0;
     if (converted) {
         if (n > 0)
-            if (int e = stage_input(ctx, static_cast<const uint8_t*>(wav), mem, (size_t)n * (size_t)channels * in_size, &d_in)) return e;
+            if (int e = stage_audio(ctx, wav, mem, n, in_size, in, &d_in)) return e;
         avd_resample::Plan conv;
         conv.r = ratio;
         conv.tile_out = c.tile_out;
@@ -1659,7 +1728,8 @@ static int run_audio_slot(avd_ctx* ctx, AudioSlot& slot, const avd_resample::Con
         src.chunk0 = c.n_before;
         src.hist = slot.hist(slot.hist_side);
         src.hist_n = c.hist_before;
-        if (int e = launch_audio_resample(ctx, d_in, format, channels, conv, ws.d_audio_pcm, src)) return e;
+        if (int e = launch_audio_resample(ctx, d_in, format, channels, conv, ws.d_audio_pcm, src, in.mix)) return e;
+        record_audio_layout(ctx, in);
     } else if (n > 0) {
         d_in = reinterpret_cast<const uint8_t*>(buf + (size_t)c.held_before * an_size);
         HIP_TRY(ctx, hipMemcpyAsync(buf + (size_t)c.held_before * an_size, wav, (size_t)n * in_size, mem == AVD_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, ctx->stream));
@@ -1671,7 +1741,7 @@ static int run_audio_slot(avd_ctx* ctx, AudioSlot& slot, const avd_resample::Con
     if (!last) {
         if (int e = launch_audio_slot_save(ctx, d_in, converted ? format : 1, converted ? n : 0, channels, slot.hist(slot.hist_side), c.hist_before,
                                            slot.hist(slot.hist_side ^ 1), c.hist_after, buf + (size_t)c.analysed * an_size, slot.held_at(),
-                                           (int)((size_t)c.held_after * an_size / sizeof(int16_t)), saved)) return e;
+                                           (int)((size_t)c.held_after * an_size / sizeof(int16_t)), saved, in.mix)) return e;
     }
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     ws.audio_upload_pending = 0;
@@ -1683,9 +1753,12 @@ static int run_audio_slot(avd_ctx* ctx, AudioSlot& slot, const avd_resample::Con
 static int slot_audio_features(avd_ctx* ctx, const void* wav, int mem, int64_t n, int win, avd_audio_window* windows, int max_windows, int ncuts, bool last)
 {
     AudioSlot& slot = ctx->audio_slots[ctx->audio_slot - 1];
-    const int format = ctx->audio_format, rate = ctx->audio_rate, channels = rate ? ctx->audio_channels : 1;
+    const int format = ctx->audio_format, rate = ctx->audio_rate;
+    AudioInput in = audio_input(ctx, n);
+    const int channels = in.channels;
+    if (audio_stride_refused(ctx, in, n)) return AVD_ERR_ARG;
     if (ncuts > 0) { ctx->err = "audio_slot: one track per call (an \"audio_cut\" list was pending; it is gone)"; return AVD_ERR_ARG; }
-    if (slot.frames > 0 && (slot.win != win || slot.rate != rate || slot.channels != channels || slot.format != format)) {
+    if (slot.frames > 0 && (slot.win != win || slot.rate != rate || slot.channels != channels || slot.format != format || slot.layout != in.layout)) {
         ctx->err = "audio_slot: win, \"audio_rate\", \"audio_channels\" and \"audio_format\" must be those of the slot's first call";
         return AVD_ERR_ARG;
     }
@@ -1699,13 +1772,13 @@ static int slot_audio_features(avd_ctx* ctx, const void* wav, int mem, int64_t n
         return AVD_OK;
     }
     bool saved = false;
-    const int e = run_audio_slot(ctx, slot, c, ratio, wav, mem, n, win, windows, max_windows, last, &saved);
+    const int e = run_audio_slot(ctx, slot, c, ratio, wav, mem, n, win, windows, max_windows, last, &saved, in);
     if (e) {
         if (saved) { slot.clear(); ctx->err += " (audio_slot: the failure came after the slot's save launch; the slot was emptied)"; }
         return e;
     }
     if (last) { slot.clear(); return AVD_OK; }
-    if (slot.frames == 0) { slot.win = win; slot.rate = rate; slot.channels = channels; slot.format = format; }
+    if (slot.frames == 0) { slot.win = win; slot.rate = rate; slot.channels = channels; slot.format = format; slot.layout = in.layout; }
     slot.frames = c.n_after;
     slot.held = c.held_after;
     slot.windows = (int)c.windows;
@@ -1719,9 +1792,9 @@ static int slot_audio_features(avd_ctx* ctx, const void* wav, int mem, int64_t n
 // passes over one window table, the save (every continued track that does not end).  Every slot's memory is reserved before the first launch, the
 // save is the last launch, and the host state of the slots moves only once the call has drained.  *saved as in run_audio_slot.
 static int run_audio_map(avd_ctx* ctx, avd_audio_map::Plan& plan, const avd_resample::Ratio& ratio, const void* wav, int mem, int64_t n, avd_audio_window* windows,
-                         bool* saved)
+                         bool* saved, AudioInput& in)
 {
-    const int format = ctx->audio_format, channels = ratio.rate ? ctx->audio_channels : 1;
+    const int format = ctx->audio_format, channels = in.channels;
     const bool converted = ratio.rate != 0;
     const size_t in_size = format == 1 ? sizeof(int16_t) : sizeof(float), an_size = converted ? sizeof(int16_t) : in_size;
     const int an_format = converted ? 1 : format, nwin = plan.windows.nwin();
@@ -1739,7 +1812,7 @@ static int run_audio_map(avd_ctx* ctx, avd_audio_map::Plan& plan, const avd_resa
     ctx->audio_map_valid = 0;
     call[0] = (int)plan.tracks.size(); call[1] = plan.continued; call[2] = call[3] = call[4] = call[5] = 0;
     if (n > 0)
-        if (int e = stage_input(ctx, static_cast<const uint8_t*>(wav), mem, (size_t)n * (size_t)channels * in_size, &d_in)) return e;
+        if (int e = stage_audio(ctx, wav, mem, n, in_size, in, &d_in)) return e;
     if (!plan.gather.empty()) {
         AudioGatherMove moves[avd_audio_map::kMaxGather];
         int count = 0;
@@ -1755,7 +1828,8 @@ static int run_audio_map(avd_ctx* ctx, avd_audio_map::Plan& plan, const avd_resa
         for (size_t t = 0; t < plan.tracks.size(); t++)
             if (const int k = plan.sources[t].slot) plan.sources[t].hist = reinterpret_cast<unsigned long long>(ctx->audio_slots[k - 1].hist(ctx->audio_slots[k - 1].hist_side));
         bool launched = false;
-        if (int e = launch_audio_resample_map(ctx, d_in, format, channels, plan, ratio, n, ws.d_audio_pcm, &launched)) return e;
+        if (int e = launch_audio_resample_map(ctx, d_in, format, channels, plan, ratio, n, ws.d_audio_pcm, &launched, in.mix)) return e;
+        record_audio_layout(ctx, in);
         call[3] = launched;
     }
     if (nwin > 0) {
@@ -1770,7 +1844,7 @@ static int run_audio_map(avd_ctx* ctx, avd_audio_map::Plan& plan, const avd_resa
             AudioSlot& slot = ctx->audio_slots[s.slot - 1];
             const avd_audio_map::Track& tr = plan.tracks[(size_t)s.track];
             AudioSaveRow r = {};
-            r.wav = converted ? d_in + (size_t)tr.begin * (size_t)channels * in_size : d_in;
+            r.wav = converted ? d_in + (size_t)tr.begin * (size_t)in.step * in_size : d_in;
             r.n = s.n;
             r.hist_old = slot.hist(slot.hist_side); r.hist_old_n = s.hist_old;
             r.hist_new = slot.hist(slot.hist_side ^ 1); r.hist_new_n = s.hist_new;
@@ -1779,7 +1853,7 @@ static int run_audio_map(avd_ctx* ctx, avd_audio_map::Plan& plan, const avd_resa
             r.held_words = (int)((size_t)s.held * an_size / sizeof(int16_t));
             rows[count++] = r;
         }
-        if (int e = launch_audio_slot_save_map(ctx, converted ? format : 1, channels, rows, count, saved)) return e;
+        if (int e = launch_audio_slot_save_map(ctx, converted ? format : 1, channels, rows, count, saved, in.mix)) return e;
         call[5] = 1;
     }
     ctx->audio_map_valid = 1;
@@ -1794,9 +1868,12 @@ static int run_audio_map(avd_ctx* ctx, avd_audio_map::Plan& plan, const avd_resa
 static int map_audio_features(avd_ctx* ctx, const void* wav, int mem, int64_t n, int win, avd_audio_window* windows, int max_windows, const int* cuts, int ncuts,
                               const int* entries, int nentries, bool end_pending)
 {
-    const int format = ctx->audio_format, rate = ctx->audio_rate, channels = rate ? ctx->audio_channels : 1;
+    const int format = ctx->audio_format, rate = ctx->audio_rate;
+    AudioInput in = audio_input(ctx, n);
+    const int channels = in.channels;
     if (n > 0 && format == 1 && (reinterpret_cast<uintptr_t>(wav) & 1)) { ctx->err = "audio_format 1: int16 samples need a 2-byte aligned wav"; return AVD_ERR_ARG; }
     if (n > 0 && format == 0 && (reinterpret_cast<uintptr_t>(wav) & 3)) { ctx->err = "audio_track_slot: float32 samples need a 4-byte aligned wav"; return AVD_ERR_ARG; }
+    if (audio_stride_refused(ctx, in, n)) return AVD_ERR_ARG;
     avd_resample::Ratio ratio = avd_resample::identity_ratio();
     if (rate != 0 && !avd_resample::ratio_of(rate, ratio)) { ctx->err = "audio_rate: not a supported rate"; return AVD_ERR_ARG; }   // (the option refuses such a value)
     avd_audio_map::SlotState state[kAudioSlots];
@@ -1805,9 +1882,9 @@ static int map_audio_features(avd_ctx* ctx, const void* wav, int mem, int64_t n,
         state[k].frames = s.frames;
         state[k].held = s.held;
         state[k].hist = avd_resample::history_frames(s.frames, ratio);
-        state[k].same = s.win == win && s.rate == rate && s.channels == channels && s.format == format;
+        state[k].same = s.win == win && s.rate == rate && s.channels == channels && s.format == format && s.layout == in.layout;
     }
-    avd_audio_map::Plan plan = avd_audio_map::plan_map(n, win, cuts, ncuts, entries, nentries, state, ratio, channels, max_windows, windows != nullptr, end_pending);
+    avd_audio_map::Plan plan = avd_audio_map::plan_map(n, win, cuts, ncuts, entries, nentries, state, ratio, in.step, max_windows, windows != nullptr, end_pending);
     switch (plan.refused) {
     case avd_audio_map::kOk: break;
     case avd_audio_map::kCutBeyond: ctx->err = "audio_cut: beyond the buffer"; return AVD_ERR_ARG;
@@ -1825,7 +1902,7 @@ static int map_audio_features(avd_ctx* ctx, const void* wav, int mem, int64_t n,
     default: ctx->err = "audio_track_slot: internal error (a slot's state contradicts the rule)"; return AVD_ERR_DEVICE;
     }
     bool saved = false;
-    const int e = run_audio_map(ctx, plan, ratio, wav, mem, n, windows, &saved);
+    const int e = run_audio_map(ctx, plan, ratio, wav, mem, n, windows, &saved, in);
     if (e) {
         if (saved) {
             for (const avd_audio_map::Track& tr : plan.tracks)
@@ -1838,7 +1915,7 @@ static int map_audio_features(avd_ctx* ctx, const void* wav, int mem, int64_t n,
         if (!tr.slot) continue;
         AudioSlot& slot = ctx->audio_slots[tr.slot - 1];
         if (tr.last) { slot.clear(); continue; }
-        if (slot.frames == 0) { slot.win = win; slot.rate = rate; slot.channels = channels; slot.format = format; }
+        if (slot.frames == 0) { slot.win = win; slot.rate = rate; slot.channels = channels; slot.format = format; slot.layout = in.layout; }
         slot.frames = tr.c.n_after;
         slot.held = tr.c.held_after;
         slot.windows = tr.count;

@@ -301,6 +301,7 @@ struct AudioSlot {
     int windows = 0;                 // records the last call on the slot wrote
     int hist_side = 0;
     int win = 0, rate = 0, channels = 0, format = 0;
+    int layout = 0;                  // option "audio_layout" of the first call (0: none); the plane stride may differ from call to call
     int16_t* hist(int side) { return d_mem.p + kAudioSlotHistAt + 1024 * (size_t)side; }
     int16_t* held_at() { return d_mem.p + kAudioSlotHeldAt; }
     void clear() { frames = 0; held = 0; windows = 0; }
@@ -395,6 +396,13 @@ struct avd_ctx {
     // on the device to the 16 kHz mono int16 track the analyzer runs over (avd_audio_resample.h); audio_rate 0 = the samples are that track already
     int audio_rate = 0;
     int audio_channels = 1;
+    // options "audio_layout" / "audio_plane_stride" (read only while audio_rate != 0): 0 = "audio_channels" decides; otherwise id | flags of
+    // avd_audio_resample.h -- 1, 2, 6 or 8 channels in FFmpeg's native order, | 0x100 one plane per channel, plane c beginning c * stride samples
+    // behind plane 0 (stride 0: the call's frame count, a dense [channels, n] buffer) -- downmixed by the layout's Q15 weights
+    int audio_layout = 0;
+    int audio_plane_stride = 0;
+    int audio_layout_rec[12] = {};  // debug buffer "audio_layout" of the last call that converted: id, planar, channels, the stride in effect, the eight weights
+    int audio_layout_valid = 0;     // 0 until a call converted
     std::vector<int> audio_rs_bank[avd_resample::kNumRates];   // the filter bank of each rate a call has used, built once (avd_resample::build_taps)
     int audio_rs_plan[8] = {};      // debug buffer "audio_rs_plan" of the last avd_audio_features call, if it converted: rate, channels, U, D, T, outputs per tile, input frames, output samples
     int audio_rs_valid = 0;         // 0 while the last call that ran did not convert (or none ran)
@@ -521,19 +529,24 @@ int comm_allgather_records(avd_ctx* ctx, const avd_frame_record* local, int coun
 int comm_allgather_last_records(avd_ctx* ctx, int count, avd_frame_record* all);
 // avd_audio.hip: per-window features of the mono tracks of `plan` (device pointers; format: option "audio_format")
 int launch_audio_features(avd_ctx* ctx, const void* d_wav, int format, const avd_audio::Plan& plan, avd_audio_window* d_out);
+// A non-zero mix.id (option "audio_layout") makes the launchers below take the layout kernels: `channels` is then mix.channels, and d_in is
+// addressed by the mix (planes mix.stride samples apart, or interleaved frames).
 // avd_audio.hip: the frames at d_in (format: option "audio_format"; channels interleaved) to the 16 kHz mono int16 tracks of `plan` at d_pcm
 // (device, plan.n_out + 8 entries, 16-byte aligned)
-int launch_audio_resample(avd_ctx* ctx, const void* d_in, int format, int channels, const avd_resample::Plan& plan, int16_t* d_pcm, const AudioSource& src = AudioSource{});
+int launch_audio_resample(avd_ctx* ctx, const void* d_in, int format, int channels, const avd_resample::Plan& plan, int16_t* d_pcm, const AudioSource& src = AudioSource{},
+                          const avd_resample::Mix& mix = avd_resample::Mix{});
 // avd_audio.hip: the converter of a call of several tracks (option "audio_track_slot"): the tiles, tile tracks and source rows of `plan` (avd_audio_map.h)
 int launch_audio_resample_map(avd_ctx* ctx, const void* d_in, int format, int channels, const avd_audio_map::Plan& plan, const avd_resample::Ratio& r, long long n_in,
-                              int16_t* d_pcm, bool* launched);
+                              int16_t* d_pcm, bool* launched, const avd_resample::Mix& mix = avd_resample::Mix{});
 // avd_audio.hip: the gather and the save launch of a call of several tracks (option "audio_track_slot"); elem: bytes of an analysis sample
 int launch_audio_gather(avd_ctx* ctx, const AudioGatherMove* moves, int count, int elem);
-int launch_audio_slot_save_map(avd_ctx* ctx, int format, int channels, const AudioSaveRow* rows, int count, bool* enqueued);
+int launch_audio_slot_save_map(avd_ctx* ctx, int format, int channels, const AudioSaveRow* rows, int count, bool* enqueued,
+                               const avd_resample::Mix& mix = avd_resample::Mix{});
 // avd_audio.hip: what a call leaves in its audio slot -- the last hist_new_n frames of the track (from the call's n frames at d_in and the old
 // history) as mono int16, and held_words 16-bit words of the analyzer's buffer.  *enqueued is set once the launch has been made (not by a refusal before it)
 int launch_audio_slot_save(avd_ctx* ctx, const void* d_in, int format, long long n, int channels, const int16_t* hist_old, int hist_old_n, int16_t* hist_new,
-                           int hist_new_n, const void* held_src, int16_t* held_dst, int held_words, bool* enqueued);
+                           int hist_new_n, const void* held_src, int16_t* held_dst, int held_words, bool* enqueued,
+                           const avd_resample::Mix& mix = avd_resample::Mix{});
 // avd_fbfused.hip: all blur iterations of one pyramid level (w = 40 / 80 / 160 / 320) in one launch, one workgroup per pair
 // zero_first: the initial flow is zero whatever the buffer holds (the coarsest level: no clearing launch)
 // plist (may be null): the launch works on pairs plist[0 .. np)

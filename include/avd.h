@@ -425,7 +425,8 @@ int avd_softmax(avd_ctx* ctx, const float* x, int mem, int64_t rows, int cols, f
  *     24000, 32000, 44100, 48000, 88200, 96000, 176400, 192000: wav holds n sample FRAMES at that rate.  Any other value is AVD_ERR_ARG with a
  *     message that begins "audio_rate:", and the old value stays.
  *   "audio_channels" (durable, reads back; read only while "audio_rate" is not 0): 1 (default) or 2 interleaved samples per frame.  Any other
- *     value is AVD_ERR_ARG with a message that begins "audio_channels:"; the caller downmixes other layouts first.
+ *     value is AVD_ERR_ARG with a message that begins "audio_channels:".  Not read while "audio_layout" is not 0, which covers every other
+ *     shape a decoder hands over: planar samples, 5.1 and 7.1 (below).
  * While "audio_rate" is not 0: "audio_format" gives the sample type of the input (n * channels samples); win, max_windows and the records refer
  * to the 16 kHz OUTPUT; "audio_cut" positions are input frames; each track is converted from its own start with zeros beyond both of its ends
  * and has ceil(n_t * U / D) output samples, and its records are byte for byte those of the track alone.  The analyzer sees an output sample y
@@ -439,7 +440,8 @@ int avd_softmax(avd_ctx* ctx, const float* x, int mem, int64_t rows, int cols, f
  * with, so nothing here promises ffmpeg's bits.  After step 1 it is integer arithmetic throughout, so a restatement matches it bit for bit
  * (tests/audio_resample_reference.py).  R the rate, g = gcd(R, 16000), U = 16000 / g, D = R / g.
  *   1. Narrow.  An int16 sample is itself.  A float32 sample x is clamp(rint(x * 32768), -32768, 32767), ties to even; NaN is 0, +-inf clamp.
- *   2. Downmix.  One channel: M = s.  Two: M = floor((L + R + 1) / 2).
+ *   2. Downmix.  M = (sum_c w_c s_c + 16384) >> 15 with the layout's Q15 weights w_c (below), the shift arithmetic.  |sum| is at most 2^30, so
+ *      a 32-bit accumulator is exact and nothing is clamped.  One channel, w = {32768}: M = s.  Two, w = {16384, 16384}: M = floor((L + R + 1) / 2).
  *   3. Filter bank (none at R = 16000, which is steps 1 and 2 only; T is then reported as 0).  f = min(1, 0.97 U / D), T = 2 ceil(16 / f) taps
  *      per phase (48000: U 1, D 3, T 100; 44100: U 160, D 441, T 92).  For phase p in [0, U) and tap k in [0, T): x = (k - T/2 + 1) - p / U,
  *      h = f sinc(f x) I0(9 sqrt(1 - (2 x / T)^2)) / I0(9) with sinc(t) = sin(pi t) / (pi t), h = 0 where the root's argument is negative, all in
@@ -454,6 +456,38 @@ int avd_softmax(avd_ctx* ctx, const float* x, int mem, int64_t rows, int cols, f
  * per tile (a tile: one workgroup's run of outputs of one track), input frames, output samples; "audio_rs_taps" int32[U][T]; "audio_rs_tracks"
  * int32[tracks][2] -- per track its first output sample and its output samples; "audio_pcm" int16[output samples] -- the converted tracks side
  * by side (an error after avd_release_workspace).  "audio_plan", "audio_tracks", "audio_xw" and "audio_mag" then describe the analysis of that output.
+ *
+ * Tracks as the decoder hands them over: planar samples, 5.1 and 7.1.  libavcodec's AAC, Opus, MP3, Vorbis and AC-3 decoders emit PLANAR samples,
+ * one plane per channel (PyAV's AudioFrame.to_ndarray() is [channels, samples]); film and broadcast tracks have six or eight channels.  Two more
+ * durable options let such a buffer go to the device as it is -- no host transpose, no host downmix.  No function is added and AVD_ABI_VERSION
+ * stays 3; with both at their defaults every call enqueues and returns exactly what it did before they existed.
+ *   "audio_layout" (durable, reads back; read only while "audio_rate" is not 0): 0 (default) -- "audio_channels" decides.  Otherwise id | flags.
+ *     The id is the channel count, the order FFmpeg's and WAVE's native one: AVD_AUDIO_LAYOUT_MONO 1; AVD_AUDIO_LAYOUT_STEREO 2, FL FR;
+ *     AVD_AUDIO_LAYOUT_5POINT1 6, FL FR FC LFE BL BR (side surrounds take the back slots); AVD_AUDIO_LAYOUT_7POINT1 8, FL FR FC LFE BL BR SL SR.
+ *     Flag AVD_AUDIO_PLANAR 0x100: one plane per channel.  Any other value is AVD_ERR_ARG with a message that begins "audio_layout:", and the old
+ *     value stays.  While the option is not 0, "audio_channels" is not read.
+ *   "audio_plane_stride" (durable, reads back; read only with the planar flag): the distance in SAMPLES from plane c to plane c + 1.  0 (default)
+ *     means n, the call's frame count: a dense [channels, n] buffer.  A negative value is AVD_ERR_ARG ("audio_plane_stride: ...") at the set; a
+ *     non-zero value below n is refused at the call ("audio_plane_stride: ..."), after the alignment check and before every later check.
+ * Addressing.  Planar: wav points at plane 0, plane c begins c * stride samples further.  n, "audio_cut" positions and the per-track extents of
+ * a list call count frames WITHIN EACH PLANE: several tracks in one call are joined along the frame axis (np.concatenate(tracks, axis=1)).
+ * Interleaved 5.1 / 7.1: frames of 6 / 8 samples, as stereo has 2.  Alignment is the sample type's, for wav; the stride is in samples, so every
+ * plane inherits it.  Host input: a dense buffer is staged in one copy; a strided one plane by plane into a dense device buffer -- no byte
+ * twice, none outside the planes; debug buffer "stage_bytes" then says channels * n * sizeof(sample) ("stage_copies": 1, or the channel count).
+ * Device input is read in place with its stride ("stage_bytes" 0).
+ * The weights of step 2 come from gains g: FC 1, FL / FR sqrt(1/2), back and side 1/2, LFE 0.  They are modelled on libswresample's default
+ * matrix for "-ac 1" and, like the rest of the rule, unpinned against a real ffmpeg.  w_c = rint(g_c / sum g * 32768); then 32768 - sum w is
+ * added to the channel with the largest g (the lowest index on a tie), so every row sums to exactly 32768:
+ *     mono {32768}    stereo {16384, 16384}    5.1 {6786, 6786, 9598, 0, 4799, 4799}    7.1 {5249, 5249, 7422, 0, 3712, 3712, 3712, 3712}
+ * Narrowing (step 1) stays per sample and comes before the mix.  So layouts 1 and 2, interleaved, are byte for byte "audio_channels" 1 and 2,
+ * and planar stereo is interleaved stereo on the same samples.  A channel of weight 0 contributes nothing whatever it holds; a planar LFE plane
+ * is not even read.
+ * The layout goes through every call form: whole tracks, "audio_cut" batches, audio slots and "audio_track_slot" lists.  A slot remembers the
+ * layout of its first call with win, rate and format -- another layout on a filled slot is refused where those mismatches are, with their
+ * message -- while the plane stride may differ from call to call.  The history a slot keeps is the downmixed frames.
+ * avd_debug_fetch "audio_layout" int32[12], host state of the last call that converted (an error before any did): the layout id (0: the call
+ * went by "audio_channels"), planar 0 / 1, channels, the plane stride of the caller's buffer in effect (0: interleaved), the eight weights,
+ * zero-filled.  "audio_rs_plan"[1] reports the channel count.
  *
  * A track continued across calls (audio slots).  A decoder hands audio out in packets; four more options let a track arrive in as many
  * avd_audio_features calls as the caller likes, in bounded memory, with the records of the whole track.  No function is added and AVD_ABI_VERSION
@@ -547,6 +581,12 @@ typedef struct avd_audio_window {
     int32_t rolloff_index;   /* first k with running sum >= 0.85 * sum_mag, else 0       (audio.py:51-58) */
     int32_t nbins;           /* length / 2 + 1 */
 } avd_audio_window;          /* 48 bytes */
+/* option "audio_layout": id | flags (0: "audio_channels" decides) */
+#define AVD_AUDIO_LAYOUT_MONO    1
+#define AVD_AUDIO_LAYOUT_STEREO  2      /* FL FR */
+#define AVD_AUDIO_LAYOUT_5POINT1 6      /* FL FR FC LFE BL BR */
+#define AVD_AUDIO_LAYOUT_7POINT1 8      /* FL FR FC LFE BL BR SL SR */
+#define AVD_AUDIO_PLANAR         0x100  /* one plane per channel, "audio_plane_stride" samples apart */
 int avd_audio_features(avd_ctx* ctx, const float* wav, int mem, int64_t n, int win, avd_audio_window* windows, int max_windows);
 
 /* The one exchange step of the path: frames and clips shard across GPUs with no data-path collective;
