@@ -256,11 +256,11 @@ static int run_flow_chunks(avd_ctx* ctx, const uint8_t* d_small, int n, float* h
     // The plan of this call, handed to every launch of it.  Fast mode: the shape of the 160-px level, once for all chunks.  fb_wide160 = 2 chooses by what is
     // in flight: this call is being enqueued and not yet counted, so > 0 means SOMEBODY ELSE's kernels will share the chip with it.
     // The interleaved flow is formed only for a caller who fetches it.
-    // fb_wide320 likewise chooses the shape of the 320-px level's launches that read a 320-px flow.
+    // fb_wide320 likewise chooses the shape of the 320-px level's launches that read a 320-px flow, and of its resizing first launch where fb_wide320_up allows it.
     const bool shared = avd_calls_in_flight() - ctx->counted_in_flight > 0;
     const FlowCall call{ctx->cv2_model, ctx->fb_wide160 == 1 || (ctx->fb_wide160 == 2 && shared), ctx->fb_wide320 == 1 || (ctx->fb_wide320 == 2 && shared), h_flow_out != nullptr};
     if (ctx->fb_mode == 1) { ctx->fb_wide160_used = call.wide160; ctx->fb_wide320_used = call.wide320; }      // the records behind the read-only options
-    ctx->fb_wide320_launches = 0;
+    ctx->fb_wide320_launches = ctx->fb_wide320_up_launches = 0;
     ctx->fb_model[0] = call.model; ctx->fb_model[1] = fb_coarsest(call.model) + 1;
     ctx->fb_model[2] = fb_fold_up_eff(ctx->fb_fold_up, call.model); ctx->fb_model[3] = fb_fold_blur_eff(ctx->fb_fold_blur, call.model);
     ctx->fb_model_valid = 1;
@@ -565,6 +565,7 @@ static const Option kOptions[] = {
     {"fb_wide160_used", &avd_ctx::fb_wide160_used, false, opt_any},
     {"fb_wide320", &avd_ctx::fb_wide320, true, opt_wide160, "AVD_FB_WIDE320", std::atoi},         // the same three values
     {"fb_wide320_used", &avd_ctx::fb_wide320_used, false, opt_any},
+    {"fb_wide320_up", &avd_ctx::fb_wide320_up, true, opt_flag, "AVD_FB_WIDE320_UP", std::atoi},
     {"fb_fold_blur", &avd_ctx::fb_fold_blur, true, opt_flag, "AVD_FB_FOLD_BLUR", std::atoi},
     {"gemm_waves", &avd_ctx::gemm_waves, true, opt_gemm_waves, "AVD_GEMM_WAVES", std::atoi},
     {"cnn_tiles", &avd_ctx::cnn_tiles, true, opt_any},
@@ -1275,6 +1276,7 @@ static int64_t impl_debug_fetch(avd_ctx* ctx, const char* name, void* out, size_
             {"ingest_groups", ctx->ingest_groups.data(), sizeof(int) * ctx->ingest_groups.size(), true, nullptr, "int32[launches][4]"},
             {"fb_model", ctx->fb_model, sizeof ctx->fb_model, ctx->fb_model_valid != 0, "no call has run the Farneback stage on this context", "int32[4]"},
             {"fb_wide320_launches", &ctx->fb_wide320_launches, sizeof ctx->fb_wide320_launches, ctx->fb_model_valid != 0, "no call has run the Farneback stage on this context", "int32[1]"},
+            {"fb_wide320_up_launches", &ctx->fb_wide320_up_launches, sizeof ctx->fb_wide320_up_launches, ctx->fb_model_valid != 0, "no call has run the Farneback stage on this context", "int32[1]"},
             {"audio_layout", ctx->audio_layout_rec, sizeof ctx->audio_layout_rec, ctx->audio_layout_valid != 0, "no avd_audio_features call has converted on this context (option \"audio_rate\")", "int32[12]"},
             {"audio_map_call", ctx->audio_map_call, sizeof ctx->audio_map_call, ctx->audio_map_valid != 0, "no avd_audio_features call with an \"audio_track_slot\" list has run on this context", "int32[6]"},
         };

@@ -874,11 +874,13 @@ int fast_levels(avd_ctx* ctx, const FlowCall& call, int np, FbChunk& chunk)
                 // re-run writes its pairs' flow without reading it -- unless the call interleaves it for its caller (flow_tail).  The one reader
                 // after the call, avd_debug_fetch "flow0", has the launch repeated with the stores (launch_flow0_late)
                 const bool unread = mag && !call.dense_flow;
-                // 320 px: a launch that reads a flow of its own size may run a pair as one five-block workgroup (FlowCall::wide320); the resizing
-                // first launch has no such form (its flow ring does not fit beside five blocks' rings), so the shapes mix within the level
+                // 320 px: a launch may run a pair as one five-block workgroup (FlowCall::wide320): those that read a flow of their own size, and -- where
+                // fb_wide320_up allows it -- the resizing first launch, whose normal-equation waves then resize the 160-px flow themselves (avd_fbfast.hip, UpN)
                 const FbFlowFrom from_it = it == 0 ? from : FbFlowFrom::level;
-                const bool wide320 = k == 0 && call.wide320 && from_it == FbFlowFrom::level;
-                if (wide320) ctx->fb_wide320_launches++;
+                const bool wide320_up = k == 0 && call.wide320 && from_it == FbFlowFrom::chain && ctx->fb_wide320_up != 0;
+                const bool wide320 = (k == 0 && call.wide320 && from_it == FbFlowFrom::level) || wide320_up;
+                if (wide320_up) ctx->fb_wide320_up_launches++;
+                else if (wide320) ctx->fb_wide320_launches++;
                 const FbFastLaunch L{call.wide160, wide320, 1, from_it, it == 0 && from_prev ? prev : a, b, a, mag, flags, identity, !unread};
                 if (int e = launch_fb_fast(ctx, stream, w, ws.d_poly[k], L, np)) return e;
                 if (unread) { chunk.flow0_late.pairs = np; chunk.flow0_late.flow_in = a; chunk.flow0_late.flags = flags; chunk.flow0_late.pairdiff = pairdiff; }

@@ -81,10 +81,13 @@ __device__ __forceinline__ void ne_load(const float* __restrict__ R, const float
     in.r0[0] = v.a; in.r0[1] = v.b; in.r0[2] = v.c; in.r0[3] = v.d; in.r0[4] = ld_off_i<float, 16>(R, pb);
 }
 
-// the R0 part alone (the flow comes from elsewhere)
+// the R0 part alone (the flow comes from elsewhere); SCALAR_ROW as in ne_load
+template <bool SCALAR_ROW = false>
 __device__ __forceinline__ void ne_load_r0(const float* __restrict__ R, unsigned r0base, int x, int y, int w, NeIn& in)
 {
-    const unsigned pb = (r0base + (unsigned)(y * w + x) * 5u) * 4u;
+    unsigned pb;
+    if constexpr (!SCALAR_ROW) pb = (r0base + (unsigned)(y * w + x) * 5u) * 4u;
+    else pb = r0base * 4u + ((unsigned)__builtin_amdgcn_readfirstlane(y * w) + (unsigned)x) * 20u;
     const F4 v = ld_off<F4>(R, pb);
     in.r0[0] = v.a; in.r0[1] = v.b; in.r0[2] = v.c; in.r0[3] = v.d; in.r0[4] = ld_off_i<float, 16>(R, pb);
 }

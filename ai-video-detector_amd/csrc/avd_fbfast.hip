@@ -32,7 +32,9 @@
 // ST = false: two of the solver wave's three stores per step and 0.8 MB per pair less; -5.7 us of 127.6, profiles/fbfast320_balance_ab.txt).
 // The first launch of the 320-px level, and of the 160-px level where a pair is one strip of this same wave mix, has no input flow of its own size: its chain wave forms it from
 // the coarser level's flow a few rows ahead of the N waves (UP, role_chain), which saves k_flow_up's full-chip pass (320 px: 37 us for +3.5; 160 px: 12 us alone, 50 us among three
-// clips in flight, for +9 us on 119 CUs -- profiles/fold160_pyramid_ab.txt).
+// clips in flight, for +9 us on 119 CUs -- profiles/fold160_pyramid_ab.txt).  Where the 320-px level runs a pair as one workgroup of five blocks there is no LDS left for that
+// hand-over and no need of it: each lane sits on an image column, and the N waves form the flow of their own columns in registers (UpN, role_ne; 119 x 210 us instead of
+// 238 x 129 us, profiles/fbfast320_wide_up_ab.txt).
 // One workgroup barrier per step of 4 rows; N works on group t, C on group t-1, X on group t-2.  A launch is one blur
 // iteration: the flow is read from one buffer and written to another (strips of a pair read each other's columns), and the
 // next iteration is the next launch.
@@ -95,9 +97,19 @@ struct FGeo {
     static constexpr int F_SLOT = 2 * 64;            // floats of one row of one block
     static constexpr int F_FLOATS = NB * 16 * F_SLOT;
     template <bool UP> static constexpr int lds_doubles() { return LDS_DOUBLES + (UP ? F_FLOATS / 2 : 0); }   // (the flow ring only where an UP form is instantiated)
+    static constexpr bool UPN = false;               // (see UpN below)
     static_assert(LDS_DOUBLES * 8 + 8 <= 163840 && NWAVES <= 16, "LDS layout, workgroup size");
     static_assert(H % 4 == 0 && (NPB == 1 || NPB == 2 || NPB == 4) && (XPB == 1 || XPB == 2), "whole groups of image rows");
     static_assert((2 * (GD + 1)) % EPS == 0 && (XPB != 1 || ROWLEN % 4 == 2), "whole steps per loop body; bank layout of the solver's reads");
+};
+
+// A geometry whose first launch of a level resizes the coarser level's flow in the NORMAL-EQUATION waves' own registers (role_ne, UPN) instead of the
+// chain wave's LDS ring (k_fb_fast's UP): the other two roles, the LDS layout and the barriers are those of a launch that reads a flow of its own size.
+// A trait of the geometry, not a template argument of the kernel: the kernels that exist keep their names.
+template <typename G>
+struct UpN : G {
+    static constexpr bool UPN = true;
+    static_assert(G::EPS == 4 && G::GD == 1, "one normal-equation wave per block: its entries are consecutive image rows; entry i forms the flow of entry i + 2");
 };
 
 // a double of lane `src` (wave-uniform, known when compiled) in every lane
@@ -132,6 +144,47 @@ __device__ __forceinline__ void fb_barrier() { __syncthreads(); }
 #endif
 
 // ------------------------------------------------------------------------------------------------------------------
+// cv2's resize(prev_flow, INTER_LINEAR) * 2 for one lane column, as k_flow_up (avd_farneback.hip) computes it: source coordinate d / 2 - 0.25, weights
+// 0.25 / 0.75, the first column with weights (1, 0), the last one copied; vertically the coarse rows are clipped and the weights kept.  Shared by the two
+// resizing forms of a launch (the chain wave's, role_chain UP; the normal-equation waves' own, role_ne UPN): the same operations on the same operands.
+// ------------------------------------------------------------------------------------------------------------------
+// the two coarse values under lane column x: component c of coarse row r (clipped by the caller, up_row)
+template <typename Ge>
+__device__ __forceinline__ F2 up_load(const float* __restrict__ prev, unsigned pbase, int x, int c, int r)
+{
+    constexpr int PW = Ge::W / 2, PH = Ge::H / 2;
+    const int sx = x == 0 ? 0 : (x - 1) >> 1;            // floor(x / 2 - 0.25), the first column snapped to 0
+    const int xs = sx < PW - 2 ? sx : PW - 2;            // an 8-byte load never leaves the row
+    return ld_off<F2>(prev, (pbase + (unsigned)(c * PW * PH + r * PW + xs)) * 4u);
+}
+template <typename Ge>
+__device__ __forceinline__ int up_row(int r) { return r < 0 ? 0 : (r > Ge::H / 2 - 1 ? Ge::H / 2 - 1 : r); }
+
+// horizontal blend of N coarse rows (both components) as loaded by up_load
+template <typename Ge, int N>
+__device__ __forceinline__ void up_hrows(int x, const F2 (&v)[N][2], float (&d)[N][2])
+{
+    constexpr int W = Ge::W, PW = W / 2;
+    const int sx = x == 0 ? 0 : (x - 1) >> 1;
+    const bool edge = sx + 1 >= PW;                      // the last column: the value is copied, no weights
+    const float a1 = x == 0 ? 0.f : ((x & 1) ? 0.25f : 0.75f), a0 = 1.f - a1;
+#pragma unroll
+    for (int q = 0; q < N; q++)
+#pragma unroll
+        for (int c = 0; c < 2; c++) {
+            const float lo = sx > PW - 2 ? v[q][c].b : v[q][c].a, hi = v[q][c].b;
+            d[q][c] = edge ? lo * 1.f : lo * a0 + hi * a1;
+        }
+}
+
+// image row y from the blended coarse rows floor(y / 2 - 0.25) = (y - 1) >> 1 (d0) and the one below it (d1)
+__device__ __forceinline__ float up_vblend(float d0, float d1, bool odd)
+{
+    const float b1 = odd ? 0.25f : 0.75f, b0 = 1.f - b1;
+    return (d0 * b0 + d1 * b1) * 2.f;
+}
+
+// ------------------------------------------------------------------------------------------------------------------
 // N: normal equations of entries 4t + 2k, 4t + 2k + 1 at step t (k = 0, 1), columns of one block.
 // ------------------------------------------------------------------------------------------------------------------
 // GD = entries of lead of the bilinear gather of R1 (its address needs the flow, so it cannot be issued arbitrarily early):
@@ -154,8 +207,9 @@ __device__ __forceinline__ bool role_ne(const float* __restrict__ R, const float
                                         const float* __restrict__ fring, int p, int x, int k, int lane, int* __restrict__ flags, bool chk,
                                         const volatile int* skip)
 {
-    constexpr bool zf = ZF;
+    constexpr bool zf = ZF, UPN = Ge::UPN;
     constexpr int W = Ge::W, GD = Ge::GD, EPS = Ge::EPS;
+    static_assert(!(UPN && (UP || ZF)), "one resizing form per launch");
     FBF_WAIT_DECL
 #ifdef AVD_FBF_DEBUG
     const long long fbf_t0 = __builtin_amdgcn_s_memtime();
@@ -175,7 +229,44 @@ __device__ __forceinline__ bool role_ne(const float* __restrict__ R, const float
     auto flow_of = [&](int row, NeIn& s) { const float* f = fring + (row & 15) * Ge::F_SLOT + lane; s.dx = f[0]; s.dy = f[64]; };
     auto load_in = [&](int row, NeIn& s) {
         if (UP) ne_load_r0(R, r0base, x, row, W, s);
+        else if (UPN) ne_load_r0<Ge::SROW>(R, r0base, x, row, W, s);
         else ne_load<Ge::SROW>(R, flow, r0base, flbase, x, row, W, plane, s);
+    };
+    // UPN.  This wave's entries are consecutive image rows, and image row y is blended from the coarse rows (y - 1) >> 1 and the next: rows slide over the
+    // coarse rows by half a row each.  Entry i forms the flow of entry i + GD + 1 = i + 2, so step t forms rows 4t + 2 .. 4t + 5 from coarse rows 2t .. 2t + 3:
+    //   uab[0], uab[1]  rows 2t, 2t + 1, blended horizontally during step t - 1 (one float per component)
+    //   uc              row 2t + 2: in flight (rc) since entry 1 of step t - 1, blended at entry 1 of step t
+    //   (ud)            row 2t + 3: in flight (rd) since entry 3 of step t - 1, blended at entry 3 of step t; the two then become uab
+    // Every coarse load is issued a whole step before its value is wanted and a step and an entry before the first gather that needs its flow; `flow` is the
+    // launch's input, so nothing but registers limits the lead.  Coarse rows are clipped at PH - 1: rows H and H + 1, which the last step forms for gathers
+    // nobody evaluates, come out as row H - 1 bit for bit (both of their coarse rows are PH - 1, and a b0 + a b1 commutes).
+    const unsigned pbase = (unsigned)p * 2u * (W / 2) * (H / 2);
+    float uab[2][2], uc[1][2];
+    F2 rc[1][2], rd[1][2];
+    auto up_form = [&](int t, int j, NeIn& s) __attribute__((always_inline)) {   // j static: the flow of image row 4t + 2 + j
+        float f[2];
+        if (j == 1) {
+            up_hrows<Ge, 1>(x, rc, uc);
+#pragma unroll
+            for (int c = 0; c < 2; c++) rc[0][c] = up_load<Ge>(flow, pbase, x, c, up_row<Ge>(2 * t + 4));
+        }
+        float ud[1][2];
+        if (j == 3) {
+            up_hrows<Ge, 1>(x, rd, ud);
+#pragma unroll
+            for (int c = 0; c < 2; c++) rd[0][c] = up_load<Ge>(flow, pbase, x, c, up_row<Ge>(2 * t + 5));
+        }
+#pragma unroll
+        for (int c = 0; c < 2; c++) {
+            if (j == 0) f[c] = up_vblend(uab[0][c], uab[1][c], false);
+            else if (j == 1) f[c] = up_vblend(uab[1][c], uc[0][c], true);
+            else if (j == 2) f[c] = up_vblend(uab[1][c], uc[0][c], false);
+            else {
+                f[c] = up_vblend(uc[0][c], ud[0][c], true);
+                uab[0][c] = uc[0][c]; uab[1][c] = ud[0][c];
+            }
+        }
+        s.dx = f[0]; s.dy = f[1];
     };
     bool first = skip != nullptr;                          // the first barrier of this role has not been passed yet
     if (UP) {
@@ -183,11 +274,23 @@ __device__ __forceinline__ bool role_ne(const float* __restrict__ R, const float
         if (first && *skip) return true;
         first = false;
     }
+    [[maybe_unused]] F2 r01[2][2];
+    if constexpr (UPN) {                                   // coarse rows 0 .. 3, ahead of the R0 loads: rows 0 and 1 are waited for first
+#pragma unroll
+        for (int c = 0; c < 2; c++) { r01[0][c] = up_load<Ge>(flow, pbase, x, c, 0); r01[1][c] = up_load<Ge>(flow, pbase, x, c, 1); }
+#pragma unroll
+        for (int c = 0; c < 2; c++) { rc[0][c] = up_load<Ge>(flow, pbase, x, c, 2); rd[0][c] = up_load<Ge>(flow, pbase, x, c, 3); }
+    }
 #pragma unroll
     for (int i = 0; i < NIS - 1; i++) load_in(row_of(ent(i)), in[i]);
     if (UP) {
 #pragma unroll
         for (int i = 0; i <= GD; i++) flow_of(row_of(ent(i)), in[i]);
+    }
+    if constexpr (UPN) {                                   // image rows 0 (coarse rows -1 -> 0 and 0) and 1 (0 and 1)
+        up_hrows<Ge, 2>(x, r01, uab);
+        in[0].dx = up_vblend(uab[0][0], uab[0][0], false); in[0].dy = up_vblend(uab[0][1], uab[0][1], false);
+        in[1].dx = up_vblend(uab[0][0], uab[1][0], true);  in[1].dy = up_vblend(uab[0][1], uab[1][1], true);
     }
 #pragma unroll
     for (int i = 0; i < GD; i++) gather(in[i], row_of(ent(i)), g[i]);
@@ -201,6 +304,7 @@ __device__ __forceinline__ bool role_ne(const float* __restrict__ R, const float
             gather(in[(ii + GD) % NIS], row_of(ent(i + GD)), g[(ii + GD) % NGS]);
             load_in(row_of(ent(i + NIS - 1)), in[(ii + NIS - 1) % NIS]);
             if (UP) flow_of(row_of(ent(i + GD + 1)), in[(ii + GD + 1) % NIS]);   // for the gather issued with the next entry
+            if constexpr (UPN) up_form(t, j, in[(ii + GD + 1) % NIS]);
             __builtin_amdgcn_sched_barrier(0);
             float a[5];                                                      // r2 .. r6: the chain wave attenuates and multiplies (PN: done here)
             ne_finish_r(in[ii % NIS], g[ii % NGS], a, zf);
@@ -253,8 +357,7 @@ __device__ __forceinline__ bool role_ne(const float* __restrict__ R, const float
 // while the window still touches the top edge) leaves and the vsum row of image row e - 7 is published.
 // ------------------------------------------------------------------------------------------------------------------
 // UP: the same wave (it has issue slots and registers to spare) also forms the launch's input flow, cv2's
-// resize(prev_flow, INTER_LINEAR) * 2 as k_flow_up (avd_farneback.hip) computes it: source coordinate d / 2 - 0.25, weights
-// 0.25 / 0.75, the first column with weights (1, 0), the last one copied.  Group g = rows 4g .. 4g+3 needs the four coarse
+// resize(prev_flow, INTER_LINEAR) * 2 (up_load, up_hrows, up_vblend above).  Group g = rows 4g .. 4g+3 needs the four coarse
 // rows 2g-1 .. 2g+2 (clamped); it is written during step g - 3 (groups 0 .. 2 before the first step), read by the N waves
 // from step g - 2 on, and its ring slot is reused four steps later.
 template <typename Ge>
@@ -263,41 +366,26 @@ struct UpRows { F2 v[4][2]; };
 template <typename Ge>
 __device__ __forceinline__ void up_issue(const float* __restrict__ prev, unsigned pbase, int g, int x, UpRows<Ge>& u)
 {
-    constexpr int PW = Ge::W / 2, PH = Ge::H / 2;
-    const int sx = x == 0 ? 0 : (x - 1) >> 1;            // floor(x / 2 - 0.25), the first column snapped to 0
-    const int xs = sx < PW - 2 ? sx : PW - 2;            // an 8-byte load never leaves the row
 #pragma unroll
     for (int q = 0; q < 4; q++) {
-        int r = 2 * g - 1 + q;
-        r = r < 0 ? 0 : (r > PH - 1 ? PH - 1 : r);
+        const int r = up_row<Ge>(2 * g - 1 + q);
 #pragma unroll
-        for (int c = 0; c < 2; c++) u.v[q][c] = ld_off<F2>(prev, (pbase + (unsigned)(c * PW * PH + r * PW + xs)) * 4u);
+        for (int c = 0; c < 2; c++) u.v[q][c] = up_load<Ge>(prev, pbase, x, c, r);
     }
 }
 
 template <typename Ge>
 __device__ __forceinline__ void up_finish(float* __restrict__ fring, int g, int x, int lane, const UpRows<Ge>& u)
 {
-    constexpr int W = Ge::W, PW = W / 2;
-    const int sx = x == 0 ? 0 : (x - 1) >> 1;
-    const bool edge = sx + 1 >= PW;                      // the last column: the value is copied, no weights
-    const float a1 = x == 0 ? 0.f : ((x & 1) ? 0.25f : 0.75f), a0 = 1.f - a1;
     float d[4][2];
-#pragma unroll
-    for (int q = 0; q < 4; q++)
-#pragma unroll
-        for (int c = 0; c < 2; c++) {
-            const float lo = sx > PW - 2 ? u.v[q][c].b : u.v[q][c].a, hi = u.v[q][c].b;
-            d[q][c] = edge ? lo * 1.f : lo * a0 + hi * a1;
-        }
+    up_hrows<Ge, 4>(x, u.v, d);
 #pragma unroll
     for (int j = 0; j < 4; j++) {
         const int y = 4 * g + j;                          // < H: only whole groups of image rows are formed
         const int q0 = j == 0 ? 0 : (j == 3 ? 2 : 1);     // floor(y / 2 - 0.25) - (2g - 1)
-        const float b1 = (j & 1) ? 0.25f : 0.75f, b0 = 1.f - b1;
         float* dst = fring + (y & 15) * Ge::F_SLOT + lane;
 #pragma unroll
-        for (int c = 0; c < 2; c++) dst[c * 64] = (d[q0][c] * b0 + d[q0 + 1][c] * b1) * 2.f;
+        for (int c = 0; c < 2; c++) dst[c * 64] = up_vblend(d[q0][c], d[q0 + 1][c], j & 1);
     }
 }
 
@@ -524,6 +612,8 @@ __device__ __forceinline__ void phase_sync()
 // IT  iterations inside the launch (levels whose pairs are ONE strip: no other workgroup reads this one's flow): the flow ping-pongs
 //     between flow_out and flow_tmp through L2, one workgroup barrier between iterations; the result is in flow_out (IT odd).
 // ST  false: the flow itself is not stored, only |flow| (IT = 1 with mag_out: the 320-px level's last launch of a call that wants no dense flow)
+// Ge = UpN<...> (320 px, five blocks): flow_in is the PREVIOUS level's flow as under UP, resized by each normal-equation wave for its own columns in
+//     registers (role_ne); UP is false, and the chain and solver waves run as in a launch that reads a flow of its own size.
 template <typename Ge, bool UP, int IT = 1, bool PRO = false, bool ST = true>
 __global__ __launch_bounds__((64 * Ge::NWAVES)) void k_fb_fast(const float* __restrict__ R, const float* flow_in, float* flow_out, float* flow_tmp,
                                                               float* __restrict__ mag_out, int* __restrict__ flags, const int* __restrict__ pairdiff,
@@ -534,7 +624,8 @@ __global__ __launch_bounds__((64 * Ge::NWAVES)) void k_fb_fast(const float* __re
     static_assert(!(UP && (PRO || IT > 1 || Ge::PN)), "the chain wave's resize belongs to one-iteration launches of the throughput shape");
     static_assert(ST || (IT == 1 && !UP && !PRO), "only a level's last launch may leave its flow unwritten");
     static_assert(Ge::template lds_doubles<UP>() * 8 + 8 <= 163840, "LDS layout");
-    static_assert(!(Ge::WHOLE && (UP || PRO || IT > 1)), "a pair as one workgroup at 320 px: the flow ring of the resizing form does not fit");
+    static_assert(!(Ge::WHOLE && (UP || PRO || IT > 1)), "a pair as one workgroup at 320 px: no room for the chain wave's flow ring, no prologue, one iteration");
+    static_assert(!(Ge::UPN && (UP || PRO || IT > 1 || !ST)), "the normal-equation waves' own resize (UpN): flow_in is the coarser level's flow, one iteration, stored");
     __shared__ __align__(16) double lds[Ge::template lds_doubles<UP>()];
     double* vsring = lds;
     float* mrings = reinterpret_cast<float*>(lds + Ge::VS_DOUBLES);
@@ -647,9 +738,12 @@ void launch_fast(hipStream_t stream, const float* R, const FbFastLaunch& L, floa
     auto go = [&](auto kernel, int zf) { hipLaunchKernelGGL(kernel, g, t, 0, stream, R, L.flow_in, L.flow_out, L.flow_tmp, mag, L.flags, L.pairdiff, np, nstrips, ow, zf); };
     // the chain wave's resize only exists where it pays: in the throughput shape (2 + 1 + 1 waves per block: the chain wave has issue slots to
     // spare).  At 320 px it costs the launch 3.5 us and saves k_flow_up's 37; the 160-px level's one-strip shape is the same wave mix.  The
-    // latency shapes are bound by exactly the chain wave that would do it (160 px, two strips: 45 -> 84 us per launch against 12 saved)
+    // latency shapes are bound by exactly the chain wave that would do it (160 px, two strips: 45 -> 84 us per launch against 12 saved).
+    // The five-block shape of the 320-px level has no LDS left for the flow ring (160 648 B of 163 840 without it) and needs none: every lane sits on an
+    // image column, so its normal-equation wave resizes the flow of its own columns in registers (UpN) -- FbFlowFrom::chain names both forms
     const bool pro = L.from == FbFlowFrom::prologue, three = L.iterations == 3;
     if constexpr ((Ge::W == 320 && !Ge::WHOLE) || (Ge::W == 160 && !Ge::PN)) { if (L.from == FbFlowFrom::chain) return go(k_fb_fast<Ge, true>, 0); }
+    if constexpr (Ge::W == 320 && Ge::WHOLE) { if (L.from == FbFlowFrom::chain) return go(k_fb_fast<UpN<Ge>, false>, 0); }
     if constexpr (Ge::W == 160 || Ge::W == 80) { if (pro && !three) return go(k_fb_fast<Ge, false, 1, true>, 0); }
     if constexpr (Ge::W == 80) { if (pro && three) return go(k_fb_fast<Ge, false, 3, true>, 0); }
     if constexpr (Ge::W == 80 || Ge::W == 40) { if (three) return go(k_fb_fast<Ge, false, 3, false>, zero_first); }
@@ -674,7 +768,7 @@ int launch_fb_fast(avd_ctx* ctx, hipStream_t stream, int w, const float* R, cons
     if (!ok) { ctx->err = "launch_fb_fast: this mode does not exist at this level size"; return AVD_ERR_ARG; }
     const bool uses_tmp = three || L.from == FbFlowFrom::prologue;
     if (!L.store_flow && !(w == 320 && one && L.from == FbFlowFrom::level && L.mag_out)) { ctx->err = "launch_fb_fast: only the 320-px level's last launch can leave its flow unwritten"; return AVD_ERR_ARG; }
-    if (L.wide320 && !(w == 320 && one && L.from == FbFlowFrom::level)) { ctx->err = "launch_fb_fast: the five-block shape exists for the 320-px level's one-iteration launches from a flow of its own size"; return AVD_ERR_ARG; }
+    if (L.wide320 && !(w == 320 && one && (L.from == FbFlowFrom::level || L.from == FbFlowFrom::chain))) { ctx->err = "launch_fb_fast: the five-block shape exists for the 320-px level's one-iteration launches from a flow of its own size or the 160-px level's"; return AVD_ERR_ARG; }
     if (L.flow_in == L.flow_out || (uses_tmp && (!L.flow_tmp || L.flow_tmp == L.flow_out))) { ctx->err = "launch_fb_fast: the flow is not updated in place"; return AVD_ERR_ARG; }
     switch (w) {
     case 320:
@@ -685,7 +779,8 @@ int launch_fb_fast(avd_ctx* ctx, hipStream_t stream, int w, const float* R, cons
         // 15 waves: 320 lanes on 320 columns, 5/6 of the wave rows of every role, one normal-equation wave per block with four entries per step.  Every column
         // is computed by the same instructions on the same operands, and the solver's chunks of four start at multiples of 4 in both: bit-identical on any content.
         // Measured (profiles/fbfast320_wide_ab.txt): 120 workgroups x (207 + 199) us against 238 x (127 + 122) us for the level's second and third launch, -18 % CU-microseconds;
-        // three clips in flight +2.5 % frames/s; one clip alone is 0.16 ms slower, which is why the shape is chosen per call.
+        // three clips in flight +2.5 % frames/s; one clip alone is 0.16 ms slower, which is why the shape is chosen per call.  The resizing first launch
+        // (FbFlowFrom::chain) has both shapes as well; which one it takes is the schedule's decision ("fb_wide320_up", fast_levels).
         if (L.wide320) launch_fast<FGeo<320, 5, 1, 1, 1>>(stream, R, L, L.mag_out, np, 1, 320);
         else launch_fast<FGeo<320, 3, 2, 2, 1>>(stream, R, L, L.mag_out, np, 2, 160);
         break;

@@ -369,12 +369,17 @@ struct avd_ctx {
     int fb_fold_blur = 1;           // the 320-px scale's 3 x 3 pyramid blur formed inside the polynomial expansion (no effect on results); AVD_FB_FOLD_BLUR / avd_set_option
     int fb_wide160 = 2;             // fast mode: the 160-px level as one three-block strip per pair (1: fewer CU-microseconds, throughput) or as two strips (0: shorter launches, latency);
                                     // 2 (default) = by what is in flight when the call is enqueued: one strip if another context of the process holds an undrained call, two if this clip is alone; AVD_FB_WIDE160 / avd_set_option
-    int fb_wide320 = 2;             // fast mode: the launches of the 320-px level that read a 320-px flow run a pair as ONE workgroup of five 64-column blocks, 15 waves (1: no halo columns,
+    int fb_wide320 = 2;             // fast mode: the launches of the 320-px level that read a 320-px flow (and, under fb_wide320_up, the first one, which reads the 160-px flow) run a pair as ONE workgroup of five 64-column blocks, 15 waves (1: no halo columns,
                                     // no idle solver lanes: 120 x 203 us instead of 238 x 124 us per launch, throughput) or as two strips of three blocks (0: a launch is 80 us shorter, latency);
                                     // 2 (default) = per call by what is in flight, as fb_wide160 = 2.  Bit-identical results on any content (the same instructions on the same operands per
                                     // column); AVD_FB_WIDE320 / avd_set_option
     int fb_wide320_used = 0;        // read-only option "fb_wide320_used": FlowCall::wide320 of the last fast-mode call, written when it is enqueued; no launcher reads it
     int fb_wide320_launches = 0;    // debug buffer "fb_wide320_launches": launches of the last call that ran the Farneback stage (all its chunks) in the five-block shape
+                                    // from a 320-px flow
+    int fb_wide320_up = 1;          // fast mode: the level's FIRST launch, the one that resizes the 160-px flow itself (fb_fold_up bit 1), follows FlowCall::wide320 too (1) -- its
+                                    // normal-equation waves resize the flow of their own columns in registers, the five-block shape has no LDS left for the chain wave's ring -- or
+                                    // stays in two strips whatever the call chose (0).  Bit-identical results; AVD_FB_WIDE320_UP / avd_set_option
+    int fb_wide320_up_launches = 0; // debug buffer "fb_wide320_up_launches": the same count for the resizing launch in the five-block shape
     int counted_in_flight = 0;      // this context's enqueued call is counted in avd_calls_in_flight()
     int fb_wide160_used = 0;        // read-only option "fb_wide160_used": FlowCall::wide160 of the last fast-mode call, written when it is enqueued; no launcher reads it
     int gemm_waves = 8;             // patch-embed GEMM: waves per workgroup (8: 8 x 4 MFMA tiles per wave, 16: 4 x 4; measured no faster), the same 256 x 256 tile; AVD_GEMM_WAVES / avd_set_option
@@ -572,12 +577,12 @@ int launch_fb_two(avd_ctx* ctx, hipStream_t stream, int w, const float* R, float
 //   level     flow_in, a buffer of this level (every width)
 //   zero      like level, but at 40 px (the coarsest level) the flow is taken as zero whatever flow_in holds: no clearing launch
 //   chain     flow_in = the COARSER level's final flow [pair][2][w/2][w/2], resized by the chain wave on the fly (320 px, and 160 px in the one-strip
-//             shape: wide160; 1 iteration)
+//             shape: wide160; 1 iteration); in the 320-px level's five-block shape (wide320) by the normal-equation waves, in registers
 //   prologue  the same, resized by the whole workgroup into flow_tmp first (160 / 80 px with 1 iteration, 80 px with 3)
 enum class FbFlowFrom { level, zero, chain, prologue };   // the result is in flow_out (3 iterations: flow_tmp is the second buffer); nothing is updated in place
 struct FbFastLaunch {
     bool wide160;                                // the 160-px shape of the call (FlowCall::wide160); no other level reads it
-    bool wide320;                                // 320 px: this launch runs a pair as one five-block workgroup (from = level, 1 iteration only); no other level reads it
+    bool wide320;                                // 320 px: this launch runs a pair as one five-block workgroup (from = level or chain, 1 iteration only); no other level reads it
     int iterations; FbFlowFrom from; const float* flow_in; float *flow_out, *flow_tmp;
     float* mag_out;                              // 320-px level, last iteration (else null): float[pair][320][320] receives |flow|
     int* flags; const int* pairdiff;             // may be null, see avd_fbfast.hip

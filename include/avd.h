@@ -688,6 +688,10 @@ int avd_set_profiling(avd_ctx* ctx, int enable);
  * 2 (default) = chosen once per call by what is in flight, exactly as "fb_wide160" = 2.  Every column is computed by the same instructions on the same
  * operands in both shapes: flow, |flow| and flag words are bit-identical on any content (tests/test_gpu_fbfast_wide320.py).  Read-only
  * "fb_wide320_used": the shape the last fast-mode call took; avd_debug_fetch "fb_wide320_launches" (int32[1]): its launches in the new shape.
+ * "fb_wide320_up" (default 1, environment AVD_FB_WIDE320_UP; no effect on results): 1 = the level's first launch, which resizes the 160-px flow
+ * itself (bit 1 of "fb_fold_up"), takes the five-block shape as well whenever the call does -- each normal-equation wave resizes the flow of its
+ * own columns in registers; 0 = that launch stays in two strips.  avd_debug_fetch "fb_wide320_up_launches" (int32[1]) counts it apart from
+ * "fb_wide320_launches", which keeps counting the launches that read a 320-px flow.
  * "fb_fused" (exact mode only, no effect on results): bit k set = pyramid level k (0 = 320x320 .. 3 = 40x40)
  * of the Farneback stage runs the fused level kernel (default 0xF, or the environment variable AVD_FB_FUSED at
  * avd_create); clear = the two-kernel path that exchanges its double intermediate through HBM.  "cnn_tiles": tiling of the
